@@ -15,7 +15,12 @@ max-over-ranks of the elapsed time.  `python bench.py --gpus N` starts its own N
 torch.distributed.run (ranks beyond the device count share devices round-robin, which is how the N > 1 path is
 exercised on a 1-GPU box).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fwd_bf16_d128|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fwd_bf16_d128|...] [--dump-outputs DIR]
+
+--dump-outputs DIR (e.g. bench_outputs/, which git ignores) writes what the timed kernels computed in the last timed step as
+DIR/<operand>.npy (float32): forward O, L; backwardQuery D, dQ; backwardKeyValue dK, dV.  Inputs are seeded, so two builds can
+be compared output for output.  Outputs larger than DUMP_BYTES in all are sampled by whole heads, the same seeded heads for
+every operand (listed in the JSON line).
 
 Workloads: fwd_bf16_d128 = the headline (BASELINE config 4's dtype at the metric's N and D); fwd_bf16_d128_n16k =
 BASELINE config 5's per-GPU shard (32 heads of N=16384 per GPU: `--gpus 8 --workload fwd_bf16_d128_n16k` is the
@@ -30,7 +35,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-PEAK_TFLOPS = {"bf16": 2500.0, "f16": 2500.0, "f32": 157.3}  # /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_TFLOPS = {"bf16": 2500.0, "f16": 2500.0, "f32": 157.3}  # MI355X spec peaks (dense, per chip)
 # Calibration of the power-limited ceiling, measured (not assumed): the vendor GEMM (hipBLASLt bf16, n = 8192, A B^T) on N(0,1)
 # operands on an MI355X of this pool under the same counters as the attention kernel -- TF/s un-profiled, matrix-pipe busy fraction
 # and effective clock from the PMC pass (tools/vendor_calib.sh -> profiles/r06_vendor_gemm_calibration.txt).  A body that is almost
@@ -44,6 +49,9 @@ VENDOR_GEMM_CALIBRATION["f16"] = VENDOR_GEMM_CALIBRATION["bf16"]
 # profiles/traffic.json with the SHA-256 of the libmfa_hip.so it profiled; the bench line carries a number only when
 # that hash is the hash of the library loaded NOW and the kernel variant matches -- otherwise null (never stale).
 TRAFFIC_JSON = os.path.join(ROOT, "profiles", "traffic.json")
+# --dump-outputs: the operands each kernel type writes, and the size limit of one dump (all files together)
+OUTPUT_OPERANDS = {"forward": ("O", "L"), "backwardQuery": ("D", "dQ"), "backwardKeyValue": ("dK", "dV")}
+DUMP_BYTES = 60 * 2**20
 EADDRINUSE_EXIT = 98   # a self-spawned rank could not join the rendezvous: spawn_ranks starts the group again on another port
 
 
@@ -154,7 +162,12 @@ def main():
     ap.add_argument("--fill", default="normal", choices=("normal", "zero"),
                     help="zero: all-zero Q/K/V/dO -- NOT a valid measurement, only the clock experiment of tools/zero_vs_random.sh "
                          "(MI355X_MICROARCH.md DVFS note: operand toggling sets the power-limited clock); the line says so in `data`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<operand>.npy (float32; sampled by whole heads above "
+                         "%d MiB in all)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.workload == "c1_cpu":
         print(json.dumps(c1_cpu_line(args)))
@@ -409,10 +422,39 @@ def main():
         out["config"]["fp32_intermediates"] = other_mode
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(np, torch, w, bufs, Op, args.cpu_seconds, backward)
+    if args.dump_outputs:
+        # nothing after the timed loop writes these buffers (the fp32-intermediates pass has its own O and L)
+        names = [n for t in types for n in OUTPUT_OPERANDS[t.name]]
+        out["dumped_outputs"] = dump_outputs(np, args.dump_outputs, {n: bufs[Op[n]] for n in names},
+                                             prefix="" if world == 1 else "rank%d_" % rank)
     if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(np, directory, arrays, prefix=""):
+    """arrays: operand name -> [batch][head][...] tensor.  Writes directory/<prefix><name>.npy as float32 (every output
+    precision of the library converts exactly).  When all of them together exceed DUMP_BYTES, the same seeded sample of whole
+    heads (flattened batch x head index, ascending) is taken from every array.  Returns what was written, for the JSON line."""
+    os.makedirs(directory, exist_ok=True)
+    flat = {n: t.reshape(-1, *t.shape[2:]) for n, t in arrays.items()}
+    heads = next(iter(flat.values())).shape[0]
+    head_bytes = sum(4 * int(np.prod(t.shape[1:])) for t in flat.values())
+    keep = min(heads, DUMP_BYTES // head_bytes)
+    if keep < 1:
+        raise SystemExit(f"--dump-outputs: one head of the outputs is {head_bytes} bytes, more than the {DUMP_BYTES} allowed")
+    index = None
+    if keep < heads:
+        index = np.sort(np.random.default_rng(0).choice(heads, size=keep, replace=False))
+    files = {}
+    for name, t in flat.items():
+        sel = t if index is None else t[index.tolist()]
+        data = sel.float().cpu().numpy() if hasattr(sel, "cpu") else np.asarray(sel, dtype=np.float32)
+        np.save(os.path.join(directory, prefix + name + ".npy"), data)
+        files[prefix + name] = list(data.shape)
+    return {"dir": directory, "files": files, "dtype": "float32",
+            "heads": "all %d" % heads if index is None else [int(i) for i in index]}
 
 
 def spawn_ranks(n):
@@ -462,7 +504,7 @@ def c1_cpu_line(args):
         return ops * reps / (time.perf_counter() - t0) / 1e9
 
     one, many = rate(1), rate(0)
-    return {"metric": "GINSTR/s c1_cpu", "value": round(many, 3), "unit": "GINSTR/s", "n_gpus": 0, "steps": args.steps,
+    line = {"metric": "GINSTR/s c1_cpu", "value": round(many, 3), "unit": "GINSTR/s", "n_gpus": 0, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ops / many / 1e6, 4), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "attention forward N=128 D=64 fp32, one head, CPU oracle only (BASELINE config 1)"},
@@ -470,6 +512,10 @@ def c1_cpu_line(args):
                              "single_thread_value": round(one, 3),
                              "sample": "the whole workload, repeated for 1 s per thread count; O and L equal the committed "
                                        "fixture tests/golden/network_golden.npz bit for bit"}}
+    if args.dump_outputs:   # (what every timed run computed: rate() checked it against the fixture)
+        res = Network(NetworkDescriptor(N, N, D), seed=10, threads=0).run(backward=False)
+        line["dumped_outputs"] = dump_outputs(np, args.dump_outputs, {n: res[n][None, None] for n in OUTPUT_OPERANDS["forward"]})
+    return line
 
 
 def cpu_baseline(np, torch, w, bufs, Op, target_seconds, backward):

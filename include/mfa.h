@@ -6,7 +6,7 @@
  * The reference has no FFI: its boundary is the public Swift API plus the Metal calls its
  * callers make (compile source, bind buffers 0-9, set threadgroup memory, dispatch).  Each
  * entry point below names the reference interface it replaces (paths relative to
- * /root/reference).  The reference-side binding a maintainer would add is in INTEGRATION.md.
+ * the reference repository, philipturner/metal-flash-attention).  The reference-side binding a maintainer would add is in INTEGRATION.md.
  *
  * Conventions: plain pointers and sizes only (no torch / HIP types in signatures; a stream is
  * passed as void* = hipStream_t).  Every function returns an mfa_status; nothing aborts the

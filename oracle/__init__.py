@@ -3,7 +3,7 @@
 TEST INFRASTRUCTURE ONLY.  May be imported by tests/, __graft_entry__.smoke()
 and bench.py's cpu_baseline leg; never by metal_flash_attention_amd/.
 
-Follows /root/reference/Tests/FlashAttentionTests/Utilities/Network.swift:70-402
+Follows the reference's Tests/FlashAttentionTests/Utilities/Network.swift:70-402
 (see network.c for per-function line citations).  PARITY STATUS: parity
 unpinned -- the reference holds no golden vectors and no Swift toolchain exists
 here; the restatement is cross-checked against an fp64 numpy twin, finite

@@ -2,9 +2,9 @@
  * oracle/network.c -- TEST INFRASTRUCTURE, NOT PRODUCT CODE.
  *
  * CPU restatement (plain C99) of the reference's naive attention "Network":
- *   /root/reference/Tests/FlashAttentionTests/Utilities/Network.swift:70-402
+ *   Tests/FlashAttentionTests/Utilities/Network.swift:70-402
  * plus the dtype round-trips of the reference's buffer helpers:
- *   /root/reference/Tests/FlashAttentionTests/Utilities/MTLContext+Buffers.swift:5-78
+ *   Tests/FlashAttentionTests/Utilities/MTLContext+Buffers.swift:5-78
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may use
  * this file.  Nothing under metal_flash_attention_amd/ links or imports it.

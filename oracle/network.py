@@ -1,7 +1,7 @@
 """ctypes front end of oracle/network.c (TEST INFRASTRUCTURE ONLY).
 
 Mirrors the reference's test utility API
-(/root/reference/Tests/FlashAttentionTests/Utilities/Network.swift:64-130):
+(the reference's Tests/FlashAttentionTests/Utilities/Network.swift:64-130):
 `NetworkDescriptor{rowDimension,columnDimension,headDimension}` -> `Network`
 with fields Q, K, V, dO and methods inferenceAttention(), createLTerm-as-vector,
 createDTerm-as-vector, derivativeV/K/Q(), loss().

@@ -1,6 +1,6 @@
 """Closed-form answers that pin the attention oracle (and the HIP kernels) to something outside this repository's
 own code: each case picks inputs for which the formulas of the reference's CPU network
-(/root/reference/Tests/FlashAttentionTests/Utilities/Network.swift:134-402) collapse to expressions that can be
+(the reference's Tests/FlashAttentionTests/Utilities/Network.swift:134-402) collapse to expressions that can be
 written down by hand and evaluated WITHOUT any softmax code:
 
     S = Q K^T / sqrt(D)                      createMatrixSRow      :134-149
