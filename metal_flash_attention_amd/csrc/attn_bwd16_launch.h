@@ -8,55 +8,58 @@ namespace mfa {
 
 
 template <typename T, int D, int NW, typename TG = T>
-static void launch_dq16(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_dq16<T, D, NW, TG>), dim3(grid.x * grid.y * grid.z), dim3(NW * 64),
-                     (dq16_lds_bytes<D, NW>()), stream, args, g);
+static const char *launch_dq16(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_dq16<T, D, NW, TG>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(NW * 64),
+          (dq16_lds_bytes<D, NW>()), l.args, g);
+  return nullptr;
 }
 template <typename T, int D, int NW, int PRE = 1, typename TG = T>
-static void launch_dkv16(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_dkv16<T, D, NW, PRE, TG>), dim3(grid.x * grid.y * grid.z), dim3(NW * 64),
-                     (dkv16_lds_bytes<D, NW>()), stream, args, g);
+static const char *launch_dkv16(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_dkv16<T, D, NW, PRE, TG>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(NW * 64),
+          (dkv16_lds_bytes<D, NW>()), l.args, g);
+  return nullptr;
 }
 
 template <typename T, int D, int NW, typename TG = T>
-static void launch_dq16_causal(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_dq16<T, D, NW, TG, true>), dim3(grid.x * grid.y * grid.z), dim3(NW * 64),
-                     (dq16_lds_bytes<D, NW>()), stream, args, g);
+static const char *launch_dq16_causal(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_dq16<T, D, NW, TG, true>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(NW * 64),
+          (dq16_lds_bytes<D, NW>()), l.args, g);
+  return nullptr;
 }
 template <typename T, int D, int NW, int PRE = 1, typename TG = T>
-static void launch_dkv16_causal(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_dkv16<T, D, NW, PRE, TG, true>), dim3(grid.x * grid.y * grid.z), dim3(NW * 64),
-                     (dkv16_lds_bytes<D, NW>()), stream, args, g);
+static const char *launch_dkv16_causal(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_dkv16<T, D, NW, PRE, TG, true>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(NW * 64),
+          (dkv16_lds_bytes<D, NW>()), l.args, g);
+  return nullptr;
 }
 
 template <typename T, int D, int NW, typename TG>
-static void launch_dq16_sparse(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  if (args.causal)
-    hipLaunchKernelGGL((attn_dq16<T, D, NW, TG, true, true>), dim3(grid.x * grid.y * grid.z), dim3(NW * 64), (dq16_lds_bytes<D, NW>()), stream, args, g);
+static const char *launch_dq16_sparse(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  if (l.args.causal)
+    l.start(&attn_dq16<T, D, NW, TG, true, true>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(NW * 64), (dq16_lds_bytes<D, NW>()), l.args, g);
   else
-    hipLaunchKernelGGL((attn_dq16<T, D, NW, TG, false, true>), dim3(grid.x * grid.y * grid.z), dim3(NW * 64), (dq16_lds_bytes<D, NW>()), stream, args, g);
+    l.start(&attn_dq16<T, D, NW, TG, false, true>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(NW * 64), (dq16_lds_bytes<D, NW>()), l.args, g);
+  return nullptr;
 }
 
 template <typename T, int D, int NW, typename TG>
-static void launch_dq16_split(dim3 grid, uint32_t splits, float *ws, float *, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z, splits, ws, nullptr};
-  const dim3 blocks(grid.x * grid.y * grid.z * splits);
-  if (args.causal)
-    hipLaunchKernelGGL((attn_dq16<T, D, NW, TG, true, false, true>), blocks, dim3(NW * 64), (dq16_lds_bytes<D, NW>()), stream, args, g);
-  else
-    hipLaunchKernelGGL((attn_dq16<T, D, NW, TG, false, false, true>), blocks, dim3(NW * 64), (dq16_lds_bytes<D, NW>()), stream, args, g);
-  const uint64_t rows = (uint64_t)grid.y * grid.z * args.R;
-  hipLaunchKernelGGL(attn_bwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args, g, (int)SLOT_dQ, args.R, (const float *)ws);
+static const char *launch_dq16_split(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z, l.splits, l.wsO, nullptr};
+  const dim3 blocks(l.grid.x * l.grid.y * l.grid.z * l.splits);
+  if (l.args.causal) l.start(&attn_dq16<T, D, NW, TG, true, false, true>, blocks, dim3(NW * 64), (dq16_lds_bytes<D, NW>()), l.args, g);
+  else l.start(&attn_dq16<T, D, NW, TG, false, false, true>, blocks, dim3(NW * 64), (dq16_lds_bytes<D, NW>()), l.args, g);
+  const uint64_t rows = (uint64_t)l.grid.y * l.grid.z * l.args.R;
+  l.start(&attn_bwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, l.args, g, (int)SLOT_dQ, l.args.R, (const float *)l.wsO);
+  return nullptr;
 }
 
 template <typename T, int D, int NW, typename TG = T>
 static void fill_dq(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_dq16<T, D, NW, TG>);
   v->name = name;
   v->parallelization = NW * 32;
   v->traversal = 64;
@@ -67,18 +70,12 @@ static void fill_dq(VariantInfo *v, const char *name) {
   v->cacheSecond = true;
   v->launch = &launch_dq16<T, D, NW, TG>;
   v->launchCausal = &launch_dq16_causal<T, D, NW, TG>;
-  v->funcCausal = reinterpret_cast<const void *>(&attn_dq16<T, D, NW, TG, true>);
   v->causal = true;
   v->launchSparse = &launch_dq16_sparse<T, D, NW, TG>;
-  v->funcSparse = reinterpret_cast<const void *>(&attn_dq16<T, D, NW, TG, false, true>);
-  v->funcSparseCausal = reinterpret_cast<const void *>(&attn_dq16<T, D, NW, TG, true, true>);
   v->launchSplit = &launch_dq16_split<T, D, NW, TG>;
-  v->funcSplit = reinterpret_cast<const void *>(&attn_dq16<T, D, NW, TG, false, false, true>);
-  v->funcSplitCausal = reinterpret_cast<const void *>(&attn_dq16<T, D, NW, TG, true, false, true>);
 }
 template <typename T, int D, int NW, int PRE = 1, typename TG = T>
 static void fill_dkv(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_dkv16<T, D, NW, PRE, TG>);
   v->name = name;
   v->parallelization = NW * 32;
   v->traversal = 64;
@@ -89,7 +86,6 @@ static void fill_dkv(VariantInfo *v, const char *name) {
   v->cacheSecond = true;
   v->launch = &launch_dkv16<T, D, NW, PRE, TG>;
   v->launchCausal = &launch_dkv16_causal<T, D, NW, PRE, TG>;
-  v->funcCausal = reinterpret_cast<const void *>(&attn_dkv16<T, D, NW, PRE, TG, true>);
   v->causal = true;
 }
 

@@ -7,28 +7,29 @@
 namespace mfa {
 
 template <typename T, int STREAM, bool CAUSAL>
-static void launch_dkv_p5(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
+static const char *launch_dkv_p5(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
   constexpr int LDS = dkv5::lds_bytes(dkv5::stream_bucket(STREAM));
-  hipLaunchKernelGGL((attn_dkv16_p5<T, STREAM, CAUSAL>), dim3(grid.x * grid.y * grid.z), dim3(256), LDS, stream, args, g);
+  l.start(&attn_dkv16_p5<T, STREAM, CAUSAL>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(256), LDS, l.args, g);
+  return nullptr;
 }
 
 // row-parallel launch (round 6): the 32-row blocks in `splits` pieces (SPLIT of attn_dkv16_p5.h), then the sums of the dV and dK slabs
 template <typename T, int STREAM>
-static void launch_dkv_p5_split(dim3 grid, uint32_t splits, float *ws, float *, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z, splits, ws, nullptr};
+static const char *launch_dkv_p5_split(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z, l.splits, l.wsO, nullptr};
   constexpr int LDS = dkv5::lds_bytes(dkv5::stream_bucket(STREAM));
-  hipLaunchKernelGGL((attn_dkv16_p5<T, STREAM, false, true>), dim3(grid.x * grid.y * grid.z * splits), dim3(256), LDS, stream, args, g);
-  const uint64_t rows = (uint64_t)grid.y * grid.z * args.C;
-  const float *dk_slabs = ws + (uint64_t)splits * rows * args.D;   // dV slabs first, then dK slabs
-  hipLaunchKernelGGL(attn_bwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args, g, (int)SLOT_dV, args.C, (const float *)ws);
-  hipLaunchKernelGGL(attn_bwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args, g, (int)SLOT_dK, args.C, dk_slabs);
+  l.start(&attn_dkv16_p5<T, STREAM, false, true>, dim3(l.grid.x * l.grid.y * l.grid.z * l.splits), dim3(256), LDS, l.args, g);
+  const uint64_t rows = (uint64_t)l.grid.y * l.grid.z * l.args.C;
+  const float *dk_slabs = l.wsO + (uint64_t)l.splits * rows * l.args.D;   // dV slabs first, then dK slabs
+  l.start(&attn_bwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, l.args, g, (int)SLOT_dV, l.args.C, (const float *)l.wsO);
+  l.start(&attn_bwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, l.args, g, (int)SLOT_dK, l.args.C, dk_slabs);
+  return nullptr;
 }
 
 // `v` arrives filled by dkv16_rs_variant*: block-sparse and CAUSAL row-parallel launches keep the 32-key role-split kernel's code objects
 template <typename T, int STREAM> static void fill_dkv_p5(VariantInfo *v, const char *name) {
   constexpr int LDS = dkv5::lds_bytes(dkv5::stream_bucket(STREAM));
-  v->func = reinterpret_cast<const void *>(&attn_dkv16_p5<T, STREAM, false>);
   if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
   v->siblingParallelization = v->parallelization;   // split / block-sparse launches: the 32-key role-split kernel's workgroups
@@ -41,12 +42,10 @@ template <typename T, int STREAM> static void fill_dkv_p5(VariantInfo *v, const 
   v->cacheSecond = true;
   v->launch = &launch_dkv_p5<T, STREAM, false>;
   v->launchCausal = &launch_dkv_p5<T, STREAM, true>;
-  v->funcCausal = reinterpret_cast<const void *>(&attn_dkv16_p5<T, STREAM, true>);
   v->causal = true;
   if constexpr (!dkv5::stream_profiles(STREAM)) {
     v->launchSplitCausal = v->launchSplit;   // (the sibling's)
     v->launchSplit = &launch_dkv_p5_split<T, STREAM>;
-    v->funcSplit = reinterpret_cast<const void *>(&attn_dkv16_p5<T, STREAM, false, true>);
     v->splitParallelization = dkv5::WGKEYS;
     v->splitTarget = 256;   // one workgroup per compute unit (512 registers per lane)
   }

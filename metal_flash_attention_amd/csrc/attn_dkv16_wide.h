@@ -11,8 +11,8 @@
 //     step -- two barriers per step (tile ready / P ready).  Each wave has a SIMD's matrix pipe to itself, so what a software pipeline
 //     would buy is the softmax arithmetic (~300 of a step's ~2000 clocks), not a second wave's matrix work;
 //   * the epilogue's staging rows one role at a time (2 x 32 x (D + 4) floats = 97 KiB).
-// Two pairs = 64 keys per workgroup.  Dense, causal and per-batch lengths; block masks, traversal-parallel pieces and transposed
-// operands keep the general kernel.  LDS-bound like attn_fwd16_wide (every fragment read feeds ONE matrix instruction).
+// Two pairs = 64 keys per workgroup.  Dense, causal and per-batch lengths; transposed operands through the re-layout pass into the
+// caller's workspace (without one: the general kernel); block masks and traversal-parallel pieces keep the general kernel.  LDS-bound like attn_fwd16_wide (every fragment read feeds ONE matrix instruction).
 // Reference: the `| 384 | ... |` rows of the mixed backwardKeyValue table (AttentionDescriptor+Parameters.swift:185-201),
 // +Source.swift:244-293, +Softmax.swift:406-427.
 #pragma once

@@ -5,25 +5,26 @@
 namespace mfa {
 
 template <typename T, int STREAM, bool CAUSAL, typename TG>
-static void launch_dq_p4(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_dq16_p4<T, STREAM, CAUSAL, TG>), dim3(grid.x * grid.y * grid.z), dim3(256), dq4::LDS_BYTES, stream, args, g);
+static const char *launch_dq_p4(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_dq16_p4<T, STREAM, CAUSAL, TG>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(256), dq4::LDS_BYTES, l.args, g);
+  return nullptr;
 }
 
 // column-parallel launch: the key tiles in `splits` pieces (SPLIT of attn_dq16_p4.h), then the sum of the slabs
 template <typename T, int STREAM, typename TG>
-static void launch_dq_p4_split(dim3 grid, uint32_t splits, float *ws, float *, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z, splits, ws, nullptr};
-  hipLaunchKernelGGL((attn_dq16_p4<T, STREAM, false, TG, true>), dim3(grid.x * grid.y * grid.z * splits), dim3(256), dq4::LDS_BYTES, stream,
-                     args, g);
-  const uint64_t rows = (uint64_t)grid.y * grid.z * args.R;
-  hipLaunchKernelGGL(attn_bwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args, g, (int)SLOT_dQ, args.R, (const float *)ws);
+static const char *launch_dq_p4_split(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z, l.splits, l.wsO, nullptr};
+  l.start(&attn_dq16_p4<T, STREAM, false, TG, true>, dim3(l.grid.x * l.grid.y * l.grid.z * l.splits), dim3(256), dq4::LDS_BYTES,
+          l.args, g);
+  const uint64_t rows = (uint64_t)l.grid.y * l.grid.z * l.args.R;
+  l.start(&attn_bwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, l.args, g, (int)SLOT_dQ, l.args.R, (const float *)l.wsO);
+  return nullptr;
 }
 
 // `v` arrives filled by dq16_variant (eight waves x 32 rows, the same 256 rows per workgroup): block-sparse launches and
 // causal column-parallel ones keep that kernel's code objects
 template <typename T, int STREAM, typename TG = T> static void fill_dq_p4(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_dq16_p4<T, STREAM, false, TG>);
   if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
   v->parallelization = 256;
@@ -35,11 +36,9 @@ template <typename T, int STREAM, typename TG = T> static void fill_dq_p4(Varian
   v->cacheSecond = true;
   v->launch = &launch_dq_p4<T, STREAM, false, TG>;
   v->launchCausal = &launch_dq_p4<T, STREAM, true, TG>;
-  v->funcCausal = reinterpret_cast<const void *>(&attn_dq16_p4<T, STREAM, true, TG>);
   v->causal = true;
   v->launchSplitCausal = v->launchSplit;   // (the eight-wave kernel's)
   v->launchSplit = &launch_dq_p4_split<T, STREAM, TG>;
-  v->funcSplit = reinterpret_cast<const void *>(&attn_dq16_p4<T, STREAM, false, TG, true>);
   v->splitParallelization = 256;
   v->splitTarget = 256;   // one workgroup per compute unit (512 registers per lane)
 }

@@ -8,26 +8,27 @@
 namespace mfa {
 
 template <typename T, int STREAM, bool CAUSAL, typename TG>
-static void launch_dq_p5(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
+static const char *launch_dq_p5(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
   constexpr int LDS = dq5::lds_bytes(dq5::stream_bucket(STREAM));
-  hipLaunchKernelGGL((attn_dq16_p5<T, STREAM, CAUSAL, TG>), dim3(grid.x * grid.y * grid.z), dim3(256), LDS, stream, args, g);
+  l.start(&attn_dq16_p5<T, STREAM, CAUSAL, TG>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(256), LDS, l.args, g);
+  return nullptr;
 }
 
 // column-parallel launch (round 6): the 32-key blocks in `splits` pieces (SPLIT of attn_dq16_p5.h), then the sum of the slabs
 template <typename T, int STREAM, typename TG>
-static void launch_dq_p5_split(dim3 grid, uint32_t splits, float *ws, float *, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z, splits, ws, nullptr};
+static const char *launch_dq_p5_split(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z, l.splits, l.wsO, nullptr};
   constexpr int LDS = dq5::lds_bytes(dq5::stream_bucket(STREAM));
-  hipLaunchKernelGGL((attn_dq16_p5<T, STREAM, false, TG, true>), dim3(grid.x * grid.y * grid.z * splits), dim3(256), LDS, stream, args, g);
-  const uint64_t rows = (uint64_t)grid.y * grid.z * args.R;
-  hipLaunchKernelGGL(attn_bwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args, g, (int)SLOT_dQ, args.R, (const float *)ws);
+  l.start(&attn_dq16_p5<T, STREAM, false, TG, true>, dim3(l.grid.x * l.grid.y * l.grid.z * l.splits), dim3(256), LDS, l.args, g);
+  const uint64_t rows = (uint64_t)l.grid.y * l.grid.z * l.args.R;
+  l.start(&attn_bwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, l.args, g, (int)SLOT_dQ, l.args.R, (const float *)l.wsO);
+  return nullptr;
 }
 
 // `v` arrives filled by dq16_variant*: block-sparse and CAUSAL column-parallel launches keep the 32-row-wave kernel's code objects
 template <typename T, int STREAM, typename TG = T> static void fill_dq_p5(VariantInfo *v, const char *name) {
   constexpr int LDS = dq5::lds_bytes(dq5::stream_bucket(STREAM));
-  v->func = reinterpret_cast<const void *>(&attn_dq16_p5<T, STREAM, false, TG>);
   if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
   v->siblingParallelization = v->parallelization;
@@ -40,12 +41,10 @@ template <typename T, int STREAM, typename TG = T> static void fill_dq_p5(Varian
   v->cacheSecond = true;
   v->launch = &launch_dq_p5<T, STREAM, false, TG>;
   v->launchCausal = &launch_dq_p5<T, STREAM, true, TG>;
-  v->funcCausal = reinterpret_cast<const void *>(&attn_dq16_p5<T, STREAM, true, TG>);
   v->causal = true;
   if constexpr (!dq5::stream_profiles(STREAM)) {
     v->launchSplitCausal = v->launchSplit;   // (the sibling's)
     v->launchSplit = &launch_dq_p5_split<T, STREAM, TG>;
-    v->funcSplit = reinterpret_cast<const void *>(&attn_dq16_p5<T, STREAM, false, TG, true>);
     v->splitParallelization = dq5::WGROWS;
     v->splitTarget = 256;   // one workgroup per compute unit (512 registers per lane)
   }

@@ -1,85 +1,51 @@
-// attn_f32.hip -- instantiations and launchers of the FP32 production kernels (attn_f32.h).  The general kernels' launchers
-// (attn_generic_{fwd,dq,dkv}.hip) hand a launch over when f32k::serves() says its operands qualify; the launch form names the
-// code object that ran (mfa_attention_kernel_launch_form).
+// attn_f32.hip -- instantiations and launchers of the FP32 production kernels (attn_f32.h).  The variant's launcher takes a launch
+// when f32k::serves() says its operands qualify and hands the others to the general kernel (attn_generic_{fwd,dq,dkv}.hip); its
+// return value names the code object that ran (mfa_attention_kernel_launch_form).
 #include "attn_f32.h"
 #include "launchers.h"
 
 #include <cstdlib>
-#include <mutex>
-#include <set>
-#include <utility>
 
 namespace mfa {
 
 namespace {
 
-// the large-LDS attribute of a code object, once per (kernel, device): launches stay free of driver calls after the first one
-template <typename Kernel> bool raise_lds(Kernel kernel, int bytes) {
-  static std::mutex guard;
-  static std::set<std::pair<const void *, int>> done;
-  int device = 0;
-  if (hipGetDevice(&device) != hipSuccess) return false;
-  const std::pair<const void *, int> key(reinterpret_cast<const void *>(kernel), device);
-  std::lock_guard<std::mutex> lock(guard);
-  if (done.count(key)) return true;
-  if (hipFuncSetAttribute(key.first, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
-  done.insert(key);
-  return true;
-}
-
-template <int DP> bool launch(int type, dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  const dim3 flat(grid.x * grid.y * grid.z);
+template <int DP> void start(int type, const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  const dim3 flat(l.grid.x * l.grid.y * l.grid.z);
   switch (type) {
     case 0:
-      if (!raise_lds(&f32k::attn_f32_fwd<DP>, f32k::lds_bytes<DP>())) return false;
-      hipLaunchKernelGGL((f32k::attn_f32_fwd<DP>), flat, dim3(256), f32k::lds_bytes<DP>(), stream, args, g);
-      return true;
+      l.start(&f32k::attn_f32_fwd<DP>, flat, dim3(256), f32k::lds_bytes<DP>(), l.args, g);
+      return;
     case 1:
 #ifdef MFA_DEV_VARIANTS   // MFA_F32_PROF=1: phase clocks instead of dQ (attn_f32.h, PROF)
       if constexpr (DP == 128) {
-        if (std::getenv("MFA_F32_PROF")) {
-          if (!raise_lds(&f32k::attn_f32_dq<DP, true>, f32k::lds_bytes_dq<DP>())) return false;
-          hipLaunchKernelGGL((f32k::attn_f32_dq<DP, true>), flat, dim3(256), f32k::lds_bytes_dq<DP>(), stream, args, g);
-          return true;
-        }
+        if (std::getenv("MFA_F32_PROF")) { l.start(&f32k::attn_f32_dq<DP, true>, flat, dim3(256), f32k::lds_bytes_dq<DP>(), l.args, g); return; }
       }
 #endif
-      if (!raise_lds(&f32k::attn_f32_dq<DP>, f32k::lds_bytes_dq<DP>())) return false;
-      hipLaunchKernelGGL((f32k::attn_f32_dq<DP>), flat, dim3(256), f32k::lds_bytes_dq<DP>(), stream, args, g);
-      return true;
+      l.start(&f32k::attn_f32_dq<DP>, flat, dim3(256), f32k::lds_bytes_dq<DP>(), l.args, g);
+      return;
     default:
-      if (!raise_lds(&f32k::attn_f32_dkv<DP>, f32k::lds_bytes_dkv<DP>())) return false;
-      hipLaunchKernelGGL((f32k::attn_f32_dkv<DP>), flat, dim3(256), f32k::lds_bytes_dkv<DP>(), stream, args, g);
-      return true;
+      l.start(&f32k::attn_f32_dkv<DP>, flat, dim3(256), f32k::lds_bytes_dkv<DP>(), l.args, g);
+      return;
   }
 }
 
-bool taken(int type, int DP, const KernelArgs &args) {
+// the general kernel's launcher of the same head block (generic_*_variant(DP), which `out` of f32_variant arrives filled by)
+template <int TYPE, int DP> struct General { static LaunchFn launch; };
+template <int TYPE, int DP> LaunchFn General<TYPE, DP>::launch = nullptr;
+
+// the FP32 kernel when the operands qualify (grid as the general kernel's: blocks of 128, heads, batches), else the general kernel
+template <int TYPE, int DP> const char *launch_f32(const Launch &l) {
+  bool taken = f32k::serves(TYPE, DP, l.args);
 #ifdef MFA_DEV_VARIANTS   // developer builds: MFA_F32_GENERAL=1 keeps the general kernels on these launches (A/B runs)
-  if (std::getenv("MFA_F32_GENERAL")) return false;
+  if (std::getenv("MFA_F32_GENERAL")) taken = false;
 #endif
-  return f32k::serves(type, DP, args);
-}
-
-}  // namespace
-
-bool f32_launch(int type, int DP, dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  if (!taken(type, DP, args)) return false;
-  return DP == 64 ? launch<64>(type, grid, stream, args) : launch<128>(type, grid, stream, args);
-}
-
-const char *f32_form(int type, int DP, const KernelArgs &args) {
-  if (!taken(type, DP, args)) return nullptr;
-  static const char *const names[3][2] = {{"attn_f32_fwd_d64_w4x32", "attn_f32_fwd_d128_w4x32"},
-                                          {"attn_f32_dq_d64_w4x32", "attn_f32_dq_d128_w4x32"},
-                                          {"attn_f32_dkv_d64_w4x32", "attn_f32_dkv_d128_w4x32"}};
-  return names[type][DP == 128];
-}
-
-namespace {
-template <int TYPE, int DP> const char *form_or_general(const KernelArgs &args) {
-  if (taken(TYPE, DP, args)) return nullptr;   // (the variant's own name: the FP32 production kernel runs)
+  if (taken) {
+    start<DP>(TYPE, l);
+    return nullptr;   // (the variant's own name: the FP32 production kernel)
+  }
+  General<TYPE, DP>::launch(l);
   static const char *const general[3][2] = {
       {"attn_generic_fwd_f32mfma_d64_w4_cached (general kernel: an operand's rows are not 16-byte aligned)",
        "attn_generic_fwd_f32mfma_d128_w4_cached (general kernel: an operand's rows are not 16-byte aligned)"},
@@ -89,16 +55,18 @@ template <int TYPE, int DP> const char *form_or_general(const KernelArgs &args) 
        "attn_generic_dkv_f32mfma_d128_w4_cached (general kernel: an operand's rows are not 16-byte aligned)"}};
   return general[TYPE][DP == 128];
 }
+
 template <int TYPE, int DP> void fill_f32(VariantInfo *v) {
   static const char *const names[3][2] = {{"attn_f32_fwd_d64_w4x32", "attn_f32_fwd_d128_w4x32"},
                                           {"attn_f32_dq_d64_w4x32", "attn_f32_dq_d128_w4x32"},
                                           {"attn_f32_dkv_d64_w4x32", "attn_f32_dkv_d128_w4x32"}};
   v->siblingName = v->name;
   v->name = names[TYPE][DP == 128];
-  v->attrLdsBytes = v->ldsBytes;
   v->ldsBytes = TYPE == 0 ? f32k::lds_bytes<DP>() : TYPE == 1 ? f32k::lds_bytes_dq<DP>() : f32k::lds_bytes_dkv<DP>();
-  v->launchForm = &form_or_general<TYPE, DP>;
+  General<TYPE, DP>::launch = v->launch;
+  v->launch = &launch_f32<TYPE, DP>;
 }
+
 }  // namespace
 
 bool f32_variant(int type, int DP, VariantInfo *out) {

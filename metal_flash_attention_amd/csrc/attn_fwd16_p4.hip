@@ -4,44 +4,42 @@
 
 namespace mfa {
 
-// persistent form (attn_fwd16_p4p.hip): dense launches without per-batch lengths; false = not served, launch this kernel
-template <typename T, bool FOLD> bool launch_p4p(dim3 grid, hipStream_t stream, const KernelArgs &args);
-template <typename T, bool FOLD> const char *p4p_form(const KernelArgs &args);
-template <typename T, bool FOLD> bool launch_p4p_split(dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream, const KernelArgs &args);
-template <typename T, bool FOLD> bool p4p_split_serves(const KernelArgs &args, uint32_t splits);
+// persistent form (attn_fwd16_p4p.hip): the launch form's text of the launches it serves (started when l.run), nullptr = not served
+template <typename T, bool FOLD> const char *launch_p4p(const Launch &l);
+template <typename T, bool FOLD> const char *launch_p4p_split(const Launch &l);
+
+template <int STREAM> constexpr bool has_persistent() {
+  return STREAM == p4::S_BF16_THR8 || STREAM == p4::S_F16_THR8 || STREAM == p4::S_BF16_FOLD || STREAM == p4::S_F16_FOLD;
+}
 
 template <typename T, int STREAM, bool CAUSAL>
-static void launch_p4(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  if constexpr (STREAM == p4::S_BF16_THR8 || STREAM == p4::S_F16_THR8 || STREAM == p4::S_BF16_FOLD || STREAM == p4::S_F16_FOLD) {
-    if (launch_p4p<T, p4::stream_folds(STREAM)>(grid, stream, args)) return;   // (dense and causal)
+static const char *launch_p4(const Launch &l) {
+  if constexpr (has_persistent<STREAM>()) {
+    if (const char *form = launch_p4p<T, p4::stream_folds(STREAM)>(l)) return form;   // (dense and causal)
   }
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  const uint32_t groups = CAUSAL ? (grid.x + 1) / 2 : grid.x;   // causal: one workgroup per pair of row blocks (last - i, i)
-  hipLaunchKernelGGL((attn_fwd16_p4<T, STREAM, CAUSAL>), dim3(groups * grid.y * grid.z), dim3(256), p4::LDS_BYTES, stream, args, g);
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  const uint32_t groups = CAUSAL ? (l.grid.x + 1) / 2 : l.grid.x;   // causal: one workgroup per pair of row blocks (last - i, i)
+  l.start(&attn_fwd16_p4<T, STREAM, CAUSAL>, dim3(groups * l.grid.y * l.grid.z), dim3(256), p4::LDS_BYTES, l.args, g);
+  return nullptr;
 }
 
 // column-parallel launch (few-workgroup problems: one head, long sequences): pieces of the key range, then the combine pass
 template <typename T, int STREAM>
-static void launch_p4_split(dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z, splits, wsO, wsML};
-  bool persistent = false;
-  if constexpr (STREAM == p4::S_BF16_THR8 || STREAM == p4::S_F16_THR8 || STREAM == p4::S_BF16_FOLD || STREAM == p4::S_F16_FOLD)
-    persistent = launch_p4p_split<T, p4::stream_folds(STREAM)>(grid, splits, wsO, wsML, stream, args);   // (round 6: the pieces on the persistent kernel)
-  if (!persistent)
-    hipLaunchKernelGGL((attn_fwd16_p4<T, STREAM, false, true>), dim3(grid.x * grid.y * grid.z * splits), dim3(256), p4::LDS_BYTES, stream, args, g);
-  const uint64_t rows = (uint64_t)grid.y * grid.z * args.R;
-  hipLaunchKernelGGL(attn_fwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args, g);
-}
-
-template <typename T, int STREAM> static const char *p4_split_form(const KernelArgs &args, uint32_t splits) {
-  if constexpr (STREAM == p4::S_BF16_THR8 || STREAM == p4::S_F16_THR8 || STREAM == p4::S_BF16_FOLD || STREAM == p4::S_F16_FOLD) {
-    if (p4p_split_serves<T, p4::stream_folds(STREAM)>(args, splits)) return "pieces by attn_fwd16_p4p, persistent";
+static const char *launch_p4_split(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z, l.splits, l.wsO, l.wsML};
+  const char *pieces = nullptr;
+  if constexpr (has_persistent<STREAM>())
+    pieces = launch_p4p_split<T, p4::stream_folds(STREAM)>(l);   // (round 6: the pieces on the persistent kernel)
+  if (!pieces) {
+    pieces = "pieces by attn_fwd16_p4, one block per workgroup";
+    l.start(&attn_fwd16_p4<T, STREAM, false, true>, dim3(l.grid.x * l.grid.y * l.grid.z * l.splits), dim3(256), p4::LDS_BYTES, l.args, g);
   }
-  return "pieces by attn_fwd16_p4, one block per workgroup";
+  const uint64_t rows = (uint64_t)l.grid.y * l.grid.z * l.args.R;
+  l.start(&attn_fwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, l.args, g);
+  return pieces;
 }
 
 template <typename T, int STREAM> static void fill_p4(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_fwd16_p4<T, STREAM, false>);
   if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
   v->parallelization = 256;
@@ -53,26 +51,19 @@ template <typename T, int STREAM> static void fill_p4(VariantInfo *v, const char
   v->cacheSecond = true;
   v->launch = &launch_p4<T, STREAM, false>;
   v->launchCausal = &launch_p4<T, STREAM, true>;
-  v->funcCausal = reinterpret_cast<const void *>(&attn_fwd16_p4<T, STREAM, true>);
   v->causal = true;
   v->launchSplit = &launch_p4_split<T, STREAM>;   // (block-sparse launches keep the sibling of the 8 x 32 kernel)
-  v->funcSplit = reinterpret_cast<const void *>(&attn_fwd16_p4<T, STREAM, false, true>);
   v->splitTarget = 256;   // one workgroup per compute unit
   v->splitParallelization = 256;   // (the pieces of a column-parallel launch are THIS kernel's: attn_fwd16_p4<..., split>, not the sibling's)
-  v->splitForm = &p4_split_form<T, STREAM>;
-  if constexpr (STREAM == p4::S_BF16_THR8 || STREAM == p4::S_F16_THR8 || STREAM == p4::S_BF16_FOLD || STREAM == p4::S_F16_FOLD)
-    v->launchForm = &p4p_form<T, p4::stream_folds(STREAM)>;
 }
 
 template <typename T, int STREAM> static void fill_p4_dev(VariantInfo *v, const char *name) {   // dense launches only
   fill_p4<T, p4::S_BF16_THR8>(v, name);
-  v->func = reinterpret_cast<const void *>(&attn_fwd16_p4<T, STREAM, false>);
   v->launch = &launch_p4<T, STREAM, false>;
   if constexpr (p4::stream_profiles(STREAM)) {   // phase clocks of causal launches too (tools/p4_prof.py --causal)
     v->launchCausal = &launch_p4<T, STREAM, true>;
-    v->funcCausal = reinterpret_cast<const void *>(&attn_fwd16_p4<T, STREAM, true>);
   } else {
-    v->launchCausal = nullptr; v->funcCausal = nullptr; v->causal = false;
+    v->launchCausal = nullptr; v->causal = false;
   }
 }
 

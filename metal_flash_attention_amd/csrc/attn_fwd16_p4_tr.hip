@@ -18,23 +18,9 @@ static bool p4_tr_takes(const KernelArgs &a, int pattern) {
   return aligned(a.op[SLOT_K]) && aligned(a.op[SLOT_V]) && aligned(a.op[SLOT_Q]);
 }
 
-template <typename T, int STREAM>
-static void launch_p4_tr(dim3 grid, hipStream_t stream, const KernelArgs &args) {
+// the launch form's text of a launch the stream takes
+template <int STREAM> static const char *stream_text() {
   constexpr int PATTERN = p4tr::stream_pattern(STREAM);
-  // grid arrives in the 8 x 32 kernel's 256-row workgroups: the same row blocks
-  if (!p4_tr_takes(args, PATTERN)) { launch_v3_tr<T, 128, 8, 3, 0, 4 | PATTERN>(grid, stream, args); return; }
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  if (args.causal) {
-    const uint32_t groups = (grid.x + 1) / 2;   // one workgroup per pair of row blocks (last - i, i)
-    hipLaunchKernelGGL((attn_fwd16_p4_tr<T, STREAM, true>), dim3(groups * grid.y * grid.z), dim3(256), p4::LDS_BYTES, stream, args, g);
-  } else {
-    hipLaunchKernelGGL((attn_fwd16_p4_tr<T, STREAM, false>), dim3(grid.x * grid.y * grid.z), dim3(256), p4::LDS_BYTES, stream, args, g);
-  }
-}
-
-template <typename T, int STREAM> static const char *p4_tr_form(const KernelArgs &args) {
-  constexpr int PATTERN = p4tr::stream_pattern(STREAM);
-  if (!p4_tr_takes(args, PATTERN)) return nullptr;
   if (PATTERN == 3)
     return p4tr::stream_folds(STREAM) ? "attn_fwd16_p4_tr (four waves x 64 rows, hand-placed stream on transposed K / V; scale folded into Q)"
                                        : "attn_fwd16_p4_tr (four waves x 64 rows, hand-placed stream on transposed K / V)";
@@ -45,12 +31,23 @@ template <typename T, int STREAM> static const char *p4_tr_form(const KernelArgs
                                      : "attn_fwd16_p4_tr (four waves x 64 rows, hand-placed stream on transposed V)";
 }
 
+template <typename T, int STREAM>
+static const char *launch_p4_tr(const Launch &l) {
+  constexpr int PATTERN = p4tr::stream_pattern(STREAM);
+  // grid arrives in the 8 x 32 kernel's 256-row workgroups: the same row blocks
+  if (!p4_tr_takes(l.args, PATTERN)) return launch_v3_tr<T, 128, 8, 3, 0, 4 | PATTERN>(l);
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  if (l.args.causal) {
+    const uint32_t groups = (l.grid.x + 1) / 2;   // one workgroup per pair of row blocks (last - i, i)
+    l.start(&attn_fwd16_p4_tr<T, STREAM, true>, dim3(groups * l.grid.y * l.grid.z), dim3(256), p4::LDS_BYTES, l.args, g);
+  } else {
+    l.start(&attn_fwd16_p4_tr<T, STREAM, false>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(256), p4::LDS_BYTES, l.args, g);
+  }
+  return stream_text<STREAM>();
+}
+
 template <typename T, int STREAM> static void attach(VariantInfo *v) {
   v->launch = &launch_p4_tr<T, STREAM>;
-  v->launchForm = &p4_tr_form<T, STREAM>;
-  // (fields that only name code objects whose LDS limit must be raised before the first launch)
-  v->funcCausal = reinterpret_cast<const void *>(&attn_fwd16_p4_tr<T, STREAM, true>);
-  v->funcSplit = reinterpret_cast<const void *>(&attn_fwd16_p4_tr<T, STREAM, false>);
   v->ldsBytes = v->ldsBytes > (uint32_t)p4::LDS_BYTES ? v->ldsBytes : (uint32_t)p4::LDS_BYTES;
 }
 

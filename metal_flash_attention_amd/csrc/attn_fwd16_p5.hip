@@ -5,24 +5,25 @@
 namespace mfa {
 
 template <typename T, int STREAM, bool CAUSAL>
-static void launch_p5(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  const uint32_t groups = CAUSAL ? (grid.x + 1) / 2 : grid.x;   // causal: one workgroup per pair of row blocks (last - i, i)
-  hipLaunchKernelGGL((attn_fwd16_p5<T, STREAM, CAUSAL>), dim3(groups * grid.y * grid.z), dim3(256), p5::LDS_BYTES, stream, args, g);
+static const char *launch_p5(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  const uint32_t groups = CAUSAL ? (l.grid.x + 1) / 2 : l.grid.x;   // causal: one workgroup per pair of row blocks (last - i, i)
+  l.start(&attn_fwd16_p5<T, STREAM, CAUSAL>, dim3(groups * l.grid.y * l.grid.z), dim3(256), p5::LDS_BYTES, l.args, g);
+  return nullptr;
 }
 
 // column-parallel launch (few-workgroup problems: one head, long sequences): pieces of the key range, then the combine pass
 template <typename T, int STREAM>
-static void launch_p5_split(dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z, splits, wsO, wsML};
-  hipLaunchKernelGGL((attn_fwd16_p5<T, STREAM, false, true>), dim3(grid.x * grid.y * grid.z * splits), dim3(256), p5::LDS_BYTES, stream, args, g);
-  const uint64_t rows = (uint64_t)grid.y * grid.z * args.R;
-  hipLaunchKernelGGL(attn_fwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args, g);
+static const char *launch_p5_split(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z, l.splits, l.wsO, l.wsML};
+  l.start(&attn_fwd16_p5<T, STREAM, false, true>, dim3(l.grid.x * l.grid.y * l.grid.z * l.splits), dim3(256), p5::LDS_BYTES, l.args, g);
+  const uint64_t rows = (uint64_t)l.grid.y * l.grid.z * l.args.R;
+  l.start(&attn_fwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, l.args, g);
+  return nullptr;
 }
 
 // `v` arrives filled by fwd16_v3_variant (D = 256: four waves x 32 rows): block-sparse launches keep its code objects
 template <typename T, int STREAM> static void fill_p5(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_fwd16_p5<T, STREAM, false>);
   if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
   v->siblingParallelization = v->parallelization;
@@ -35,10 +36,8 @@ template <typename T, int STREAM> static void fill_p5(VariantInfo *v, const char
   v->cacheSecond = true;
   v->launch = &launch_p5<T, STREAM, false>;
   v->launchCausal = &launch_p5<T, STREAM, true>;
-  v->funcCausal = reinterpret_cast<const void *>(&attn_fwd16_p5<T, STREAM, true>);
   v->causal = true;
   v->launchSplit = &launch_p5_split<T, STREAM>;
-  v->funcSplit = reinterpret_cast<const void *>(&attn_fwd16_p5<T, STREAM, false, true>);
   v->splitParallelization = 256;
   v->splitTarget = 256;   // one workgroup per compute unit
 }

@@ -10,7 +10,6 @@
 
 namespace mfa {
 
-typedef void (*LaunchFn)(dim3 grid, hipStream_t stream, const KernelArgs &args);
 // the launcher of the code object `out` arrived with (fwd16_v3_tr_variant_dNN of the same pattern): one per (type, stream)
 template <typename T, int STREAM> struct P5TrFallback { static LaunchFn launch; };
 template <typename T, int STREAM> LaunchFn P5TrFallback<T, STREAM>::launch = nullptr;
@@ -33,23 +32,9 @@ static bool p5_tr_takes(const KernelArgs &a, int pattern) {
   return a.op[SLOT_Q].transposed || aligned(a.op[SLOT_Q]);
 }
 
-template <typename T, int STREAM>
-static void launch_p5_tr(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  if (!p5_tr_takes(args, p5tr::stream_pattern(STREAM))) { P5TrFallback<T, STREAM>::launch(grid, stream, args); return; }
-  // grid arrives in the 8 x 32 kernel's row blocks (VariantInfo.parallelization); this kernel's are 256 rows
-  const uint32_t blocks = ((uint32_t)args.R + 255) / 256;
-  Fwd16Grid g{blocks, grid.y, grid.z};
-  if (args.causal) {
-    const uint32_t groups = (blocks + 1) / 2;   // one workgroup per pair of row blocks (last - i, i)
-    hipLaunchKernelGGL((attn_fwd16_p5_tr<T, STREAM, true>), dim3(groups * grid.y * grid.z), dim3(256), p5::LDS_BYTES, stream, args, g);
-  } else {
-    hipLaunchKernelGGL((attn_fwd16_p5_tr<T, STREAM, false>), dim3(blocks * grid.y * grid.z), dim3(256), p5::LDS_BYTES, stream, args, g);
-  }
-}
-
-template <typename T, int STREAM> static const char *p5_tr_form(const KernelArgs &args) {
+// the launch form's text of a launch the stream takes
+template <int STREAM> static const char *stream_text() {
   constexpr int PATTERN = p5tr::stream_pattern(STREAM);
-  if (!p5_tr_takes(args, PATTERN)) return nullptr;
   if (PATTERN == 1)
     return p5tr::stream_folds(STREAM) ? "attn_fwd16_p5_tr (four waves x 64 rows, 32-key steps, hand-placed stream on transposed K; scale folded into Q)"
                                        : "attn_fwd16_p5_tr (four waves x 64 rows, 32-key steps, hand-placed stream on transposed K)";
@@ -60,13 +45,24 @@ template <typename T, int STREAM> static const char *p5_tr_form(const KernelArgs
                                      : "attn_fwd16_p5_tr (four waves x 64 rows, 32-key steps, hand-placed stream on transposed K / V)";
 }
 
+template <typename T, int STREAM>
+static const char *launch_p5_tr(const Launch &l) {
+  if (!p5_tr_takes(l.args, p5tr::stream_pattern(STREAM))) return P5TrFallback<T, STREAM>::launch(l);
+  // grid arrives in the 8 x 32 kernel's row blocks (VariantInfo.parallelization); this kernel's are 256 rows
+  const uint32_t blocks = ((uint32_t)l.args.R + 255) / 256;
+  Fwd16Grid g{blocks, l.grid.y, l.grid.z};
+  if (l.args.causal) {
+    const uint32_t groups = (blocks + 1) / 2;   // one workgroup per pair of row blocks (last - i, i)
+    l.start(&attn_fwd16_p5_tr<T, STREAM, true>, dim3(groups * l.grid.y * l.grid.z), dim3(256), p5::LDS_BYTES, l.args, g);
+  } else {
+    l.start(&attn_fwd16_p5_tr<T, STREAM, false>, dim3(blocks * l.grid.y * l.grid.z), dim3(256), p5::LDS_BYTES, l.args, g);
+  }
+  return stream_text<STREAM>();
+}
+
 template <typename T, int STREAM> static void attach(VariantInfo *v) {
   P5TrFallback<T, STREAM>::launch = v->launch;
   v->launch = &launch_p5_tr<T, STREAM>;
-  v->launchForm = &p5_tr_form<T, STREAM>;
-  // (fields that only name code objects whose LDS limit must be raised before the first launch)
-  v->funcCausal = reinterpret_cast<const void *>(&attn_fwd16_p5_tr<T, STREAM, true>);
-  v->funcSplit = reinterpret_cast<const void *>(&attn_fwd16_p5_tr<T, STREAM, false>);
   v->ldsBytes = v->ldsBytes > (uint32_t)p5::LDS_BYTES ? v->ldsBytes : (uint32_t)p5::LDS_BYTES;
 }
 

@@ -4,37 +4,20 @@
 
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 
 namespace mfa {
 
 namespace {
 
-struct DeviceInfo { int cus = 0; uint64_t attrMask[p6::S_COUNT + 1] = {}; };
-std::mutex g_mutex;
-DeviceInfo g_devices[64];
-
-template <typename T, int STREAM>
-bool launch_stream(dim3 grid, hipStream_t stream, const KernelArgs &args, uint32_t splits = 1, float *wsO = nullptr, float *wsML = nullptr) {
-  int device = 0;
-  if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= 64) return false;
-  int cus;
-  {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceInfo &d = g_devices[device];
-    if (d.cus == 0) {
-      int n = 0;
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n <= 0) return false;
-      d.cus = n;
-    }
-    cus = d.cus;
-    if (!d.attrMask[STREAM]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(&attn_fwd16_p6<T, STREAM>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              p6::LDS_BYTES) != hipSuccess)
-        return false;
-      d.attrMask[STREAM] = 1;
-    }
-  }
+// starts one stream (when l.run) and returns `form`: once a stream is chosen, a failed HIP call is the launch's error (l.err), nothing
+// else runs instead
+template <typename T, int STREAM> const char *launch_stream(const Launch &l, const char *form) {
+  if (!l.run || l.err != hipSuccess) return form;
+  int cus = 0;
+  l.err = compute_units(&cus);
+  if (l.err != hipSuccess) return form;
+  const dim3 grid = l.grid;
+  const uint32_t splits = l.splits;
   // units: row blocks, or (causal) pairs of row blocks -- two table entries each
   constexpr bool CAUSAL = p6::traits(STREAM).causal;
   constexpr uint64_t PER_UNIT = CAUSAL ? 2 : 1;
@@ -45,11 +28,10 @@ bool launch_stream(dim3 grid, hipStream_t stream, const KernelArgs &args, uint32
   constexpr uint64_t MAX_UNITS = (p6::TABLE_ENTRIES - 1) / PER_UNIT;   // (the table's last word holds the block count)
   if ((total + groups - 1) / groups > MAX_UNITS) groups = (total + MAX_UNITS - 1) / MAX_UNITS;
   if (groups >= 8) groups = (groups + 7) / 8 * 8;
-  if (groups > total) groups = total;
-  if ((total + groups - 1) / groups > MAX_UNITS) return false;
-  Fwd16Grid g{grid.x, grid.y, grid.z, splits, wsO, wsML};
-  hipLaunchKernelGGL((attn_fwd16_p6<T, STREAM>), dim3((uint32_t)groups), dim3(256), p6::LDS_BYTES, stream, args, g, (uint32_t)total);
-  return true;
+  if (groups > total) groups = total;   // (so every workgroup's share fits the table)
+  Fwd16Grid g{grid.x, grid.y, grid.z, splits, l.wsO, l.wsML};
+  l.start(&attn_fwd16_p6<T, STREAM>, dim3((uint32_t)groups), dim3(256), p6::LDS_BYTES, l.args, g, (uint32_t)total);
+  return form;
 }
 
 bool serves(int precision, bool fold, const KernelArgs &args) {
@@ -67,107 +49,86 @@ bool serves(int precision, bool fold, const KernelArgs &args) {
 
 }  // namespace
 
-// Dense launch of a D <= 64 forward problem on the persistent kernel; false = not one it serves (the caller launches attn_fwd16_v3)
-bool launch_p6(int precision, bool fold, dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  if (!serves(precision, fold, args)) return false;
+// Dense launch of a D <= 64 forward problem on the persistent kernel: the launch form's text, nullptr = not one it serves (the caller
+// launches attn_fwd16_v3)
+static const char *launch_p6(int precision, bool fold, const Launch &l) {
+  const KernelArgs &args = l.args;
+  if (!serves(precision, fold, args)) return nullptr;
+  const char *form =
+      (args.rowLen || args.colLen)
+          ? (fold ? "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row-block pairs; per-batch lengths in the block table; row sums in the matrix pipe)"
+                  : "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row-block pairs; per-batch lengths in the block table)")
+      : args.causal ? (fold ? "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row-block pairs; row sums in the matrix pipe)"
+                            : "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row-block pairs)")
+                    : (fold ? "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row blocks; row sums in the matrix pipe)"
+                            : "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row blocks)");
 #ifdef MFA_DEV_VARIANTS
-  if (std::getenv("MFA_P6_OFF")) return false;
+  if (std::getenv("MFA_P6_OFF")) return nullptr;
   if (const char *want = std::getenv("MFA_P6_DEV_STREAM")) {
     if (*want && precision == PREC_BF16 && args.op[SLOT_O].precision == PREC_FP32) {
 #define MFA_P6_BYNAME(name, f16, sfold, o16, l16, scausal, ssplit) \
-      if constexpr (!f16 && !o16 && !ssplit) { if ((sfold != 0) == fold && (scausal != 0) == (args.causal != 0 || args.rowLen || args.colLen) && std::strcmp(want, #name) == 0) return launch_stream<__bf16, p6::S_##name>(grid, stream, args); }
+      if constexpr (!f16 && !o16 && !ssplit) { if ((sfold != 0) == fold && (scausal != 0) == (args.causal != 0 || args.rowLen || args.colLen) && std::strcmp(want, #name) == 0) return launch_stream<__bf16, p6::S_##name>(l, form); }
       MFA_P6_DEV_STREAM_LIST(MFA_P6_BYNAME)
 #undef MFA_P6_BYNAME
-      return false;
+      return nullptr;
     }
   }
 #endif
   const bool o16 = args.op[SLOT_O].precision != PREC_FP32;
 #define MFA_P6_PICK(T, PFX)                                                                                                          \
   if (args.causal || args.rowLen || args.colLen) {   /* the "geometry" streams; KernelArgs.causal is their run-time flag */           \
-    if (fold) return o16 ? launch_stream<T, p6::S_##PFX##_FOLD_O16_L16_CAUSAL>(grid, stream, args) : launch_stream<T, p6::S_##PFX##_FOLD_L16_CAUSAL>(grid, stream, args); \
-    return o16 ? launch_stream<T, p6::S_##PFX##_EXACT_O16_CAUSAL>(grid, stream, args) : launch_stream<T, p6::S_##PFX##_EXACT_CAUSAL>(grid, stream, args); \
+    if (fold) return o16 ? launch_stream<T, p6::S_##PFX##_FOLD_O16_L16_CAUSAL>(l, form) : launch_stream<T, p6::S_##PFX##_FOLD_L16_CAUSAL>(l, form); \
+    return o16 ? launch_stream<T, p6::S_##PFX##_EXACT_O16_CAUSAL>(l, form) : launch_stream<T, p6::S_##PFX##_EXACT_CAUSAL>(l, form); \
   }                                                                                                                                  \
-  if (fold) return o16 ? launch_stream<T, p6::S_##PFX##_FOLD_O16_L16>(grid, stream, args) : launch_stream<T, p6::S_##PFX##_FOLD_L16>(grid, stream, args); \
-  return o16 ? launch_stream<T, p6::S_##PFX##_EXACT_O16>(grid, stream, args) : launch_stream<T, p6::S_##PFX##_EXACT>(grid, stream, args);
+  if (fold) return o16 ? launch_stream<T, p6::S_##PFX##_FOLD_O16_L16>(l, form) : launch_stream<T, p6::S_##PFX##_FOLD_L16>(l, form); \
+  return o16 ? launch_stream<T, p6::S_##PFX##_EXACT_O16>(l, form) : launch_stream<T, p6::S_##PFX##_EXACT>(l, form);
   if (precision == PREC_BF16) { MFA_P6_PICK(__bf16, BF16) }
   MFA_P6_PICK(_Float16, F16)
 #undef MFA_P6_PICK
 }
 
 // Column-parallel launch (few-workgroup problems: one head, BASELINE config 2 as written): pieces of the key range on the persistent
-// kernel, then the combine pass.  false = not one it serves (pieces that are not whole multiples of four tiles, ...): the caller
+// kernel, then the combine pass.  nullptr = not one it serves (pieces that are not whole multiples of four tiles, ...): the caller
 // launches the eight-wave kernel's split sibling
-bool launch_p6_split(int precision, bool fold, dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream, const KernelArgs &args) {
-  if (!serves(precision, fold, args) || args.causal || args.rowLen || args.colLen || splits < 2) return false;
-  if (args.C % (256u * splits) != 0) return false;
+static const char *launch_p6_split(int precision, bool fold, const Launch &l) {
+  const KernelArgs &args = l.args;
+  if (!serves(precision, fold, args) || args.causal || args.rowLen || args.colLen || l.splits < 2) return nullptr;
+  if (args.C % (256u * l.splits) != 0) return nullptr;
 #ifdef MFA_DEV_VARIANTS
-  if (std::getenv("MFA_P6_OFF") || std::getenv("MFA_P6_NO_SPLIT")) return false;
+  if (std::getenv("MFA_P6_OFF") || std::getenv("MFA_P6_NO_SPLIT")) return nullptr;
 #endif
-  bool ok;
-  if (precision == PREC_BF16) ok = fold ? launch_stream<__bf16, p6::S_BF16_FOLD_SPLIT>(grid, stream, args, splits, wsO, wsML)
-                                        : launch_stream<__bf16, p6::S_BF16_EXACT_SPLIT>(grid, stream, args, splits, wsO, wsML);
-  else ok = fold ? launch_stream<_Float16, p6::S_F16_FOLD_SPLIT>(grid, stream, args, splits, wsO, wsML)
-                 : launch_stream<_Float16, p6::S_F16_EXACT_SPLIT>(grid, stream, args, splits, wsO, wsML);
-  if (!ok) return false;
-  Fwd16Grid g{grid.x, grid.y, grid.z, splits, wsO, wsML};
-  const uint64_t rows = (uint64_t)grid.y * grid.z * args.R;
-  hipLaunchKernelGGL(attn_fwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args, g);
-  return true;
+  const char *form = "pieces by attn_fwd16_p6, persistent";
+  if (precision == PREC_BF16 && fold) launch_stream<__bf16, p6::S_BF16_FOLD_SPLIT>(l, form);
+  else if (precision == PREC_BF16) launch_stream<__bf16, p6::S_BF16_EXACT_SPLIT>(l, form);
+  else if (fold) launch_stream<_Float16, p6::S_F16_FOLD_SPLIT>(l, form);
+  else launch_stream<_Float16, p6::S_F16_EXACT_SPLIT>(l, form);
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z, l.splits, l.wsO, l.wsML};
+  const uint64_t rows = (uint64_t)l.grid.y * l.grid.z * args.R;
+  l.start(&attn_fwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, args, g);
+  return form;
 }
 
-// what runs instead when this kernel does not serve a launch (launch_p6_or_v3*): the name rocprofv3 shows is the eight-wave kernel's
-static const char *unserved_form(int precision, const KernelArgs &args) {
-  if (precision == PREC_BF16)
-    return args.causal ? "attn_fwd16v3_bf16_d64_w8x32_thr8 causal (eight-wave kernel: the launch is not one attn_fwd16_p6 serves)"
-                       : "attn_fwd16v3_bf16_d64_w8x32_thr8 (eight-wave kernel: the launch is not one attn_fwd16_p6 serves)";
-  return args.causal ? "attn_fwd16v3_f16_d64_w8x32_thr8 causal (eight-wave kernel: the launch is not one attn_fwd16_p6 serves)"
-                     : "attn_fwd16v3_f16_d64_w8x32_thr8 (eight-wave kernel: the launch is not one attn_fwd16_p6 serves)";
-}
+// the eight-wave kernel's launchers (attn_fwd16_v3.hip) for the launches this kernel does not serve
+const char *fwd16_v3_d64_launch(int precision, const Launch &l);
+const char *fwd16_v3_d64_launch_causal(int precision, const Launch &l);
+const char *fwd16_v3_d64_launch_split(int precision, const Launch &l);
 
-const char *p6_form(int precision, bool fold, const KernelArgs &args) {
-  if (!serves(precision, fold, args)) return nullptr;
-#ifdef MFA_DEV_VARIANTS
-  if (std::getenv("MFA_P6_OFF")) return nullptr;
-#endif
-  if (args.rowLen || args.colLen)
-    return fold ? "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row-block pairs; per-batch lengths in the block table; row sums in the matrix pipe)"
-                : "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row-block pairs; per-batch lengths in the block table)";
-  if (args.causal)
-    return fold ? "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row-block pairs; row sums in the matrix pipe)"
-                : "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row-block pairs)";
-  return fold ? "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row blocks; row sums in the matrix pipe)"
-              : "attn_fwd16_p6 (persistent: one workgroup per compute unit walks the row blocks)";
+template <int PREC, bool FOLD, bool CAUSAL> static const char *launch_p6_or_v3(const Launch &l) {
+  if (const char *form = launch_p6(PREC, FOLD, l)) return form;
+  if (CAUSAL) fwd16_v3_d64_launch_causal(PREC, l);
+  else fwd16_v3_d64_launch(PREC, l);
+  // (the name rocprofv3 shows is the eight-wave kernel's)
+  if (PREC == PREC_BF16)
+    return CAUSAL ? "attn_fwd16v3_bf16_d64_w8x32_thr8 causal (eight-wave kernel: the launch is not one attn_fwd16_p6 serves)"
+                  : "attn_fwd16v3_bf16_d64_w8x32_thr8 (eight-wave kernel: the launch is not one attn_fwd16_p6 serves)";
+  return CAUSAL ? "attn_fwd16v3_f16_d64_w8x32_thr8 causal (eight-wave kernel: the launch is not one attn_fwd16_p6 serves)"
+                : "attn_fwd16v3_f16_d64_w8x32_thr8 (eight-wave kernel: the launch is not one attn_fwd16_p6 serves)";
 }
-
-void fwd16_v3_d64_launch(int precision, dim3 grid, hipStream_t stream, const KernelArgs &args);   // attn_fwd16_v3.hip
-
-template <int PREC, bool FOLD> static void launch_p6_or_v3(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  if (launch_p6(PREC, FOLD, grid, stream, args)) return;
-  fwd16_v3_d64_launch(PREC, grid, stream, args);
-}
-void fwd16_v3_d64_launch_causal(int precision, dim3 grid, hipStream_t stream, const KernelArgs &args);   // attn_fwd16_v3.hip
-void fwd16_v3_d64_launch_split(int precision, dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream, const KernelArgs &args);
-template <int PREC, bool FOLD> static void launch_p6_or_v3_split(dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream, const KernelArgs &args) {
-  if (launch_p6_split(PREC, FOLD, grid, splits, wsO, wsML, stream, args)) return;
-  fwd16_v3_d64_launch_split(PREC, grid, splits, wsO, wsML, stream, args);
-}
-template <int PREC, bool FOLD> static void launch_p6_or_v3_causal(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  if (launch_p6(PREC, FOLD, grid, stream, args)) return;
-  fwd16_v3_d64_launch_causal(PREC, grid, stream, args);
-}
-template <int PREC, bool FOLD> static const char *p6_split_form_of(const KernelArgs &args, uint32_t splits) {
-  static const char *const sibling = PREC == PREC_BF16 ? "pieces by the eight-wave kernel attn_fwd16v3_bf16_d64_w8x32_thr8 (not a split attn_fwd16_p6 serves)"
-                                                       : "pieces by the eight-wave kernel attn_fwd16v3_f16_d64_w8x32_thr8 (not a split attn_fwd16_p6 serves)";
-  if (!p6_form(PREC, FOLD, args) || args.causal || splits < 2 || args.C % (256u * splits) != 0) return sibling;
-#ifdef MFA_DEV_VARIANTS
-  if (std::getenv("MFA_P6_NO_SPLIT")) return sibling;
-#endif
-  return "pieces by attn_fwd16_p6, persistent";
-}
-template <int PREC, bool FOLD> static const char *p6_form_of(const KernelArgs &args) {
-  const char *form = p6_form(PREC, FOLD, args);
-  return form ? form : unserved_form(PREC, args);
+template <int PREC, bool FOLD> static const char *launch_p6_or_v3_split(const Launch &l) {
+  if (const char *pieces = launch_p6_split(PREC, FOLD, l)) return pieces;
+  fwd16_v3_d64_launch_split(PREC, l);
+  return PREC == PREC_BF16 ? "pieces by the eight-wave kernel attn_fwd16v3_bf16_d64_w8x32_thr8 (not a split attn_fwd16_p6 serves)"
+                           : "pieces by the eight-wave kernel attn_fwd16v3_f16_d64_w8x32_thr8 (not a split attn_fwd16_p6 serves)";
 }
 
 // `out` arrives filled by fwd16_v3_variant(precision, 64, 0): its causal, block-sparse and column-parallel launches (and the dense
@@ -185,11 +146,11 @@ bool fwd16_p6_variant(int precision, bool fold, VariantInfo *out) {
   out->ldsBytes = out->ldsBytes > (uint32_t)p6::LDS_BYTES ? out->ldsBytes : (uint32_t)p6::LDS_BYTES;
   out->splitTarget = 256;   // one workgroup per compute unit
   if (precision == PREC_BF16) {
-    if (fold) { out->launch = &launch_p6_or_v3<PREC_BF16, true>; out->launchCausal = &launch_p6_or_v3_causal<PREC_BF16, true>; out->launchSplit = &launch_p6_or_v3_split<PREC_BF16, true>; out->splitForm = &p6_split_form_of<PREC_BF16, true>; out->launchForm = &p6_form_of<PREC_BF16, true>; }
-    else { out->launch = &launch_p6_or_v3<PREC_BF16, false>; out->launchCausal = &launch_p6_or_v3_causal<PREC_BF16, false>; out->launchSplit = &launch_p6_or_v3_split<PREC_BF16, false>; out->splitForm = &p6_split_form_of<PREC_BF16, false>; out->launchForm = &p6_form_of<PREC_BF16, false>; }
+    if (fold) { out->launch = &launch_p6_or_v3<PREC_BF16, true, false>; out->launchCausal = &launch_p6_or_v3<PREC_BF16, true, true>; out->launchSplit = &launch_p6_or_v3_split<PREC_BF16, true>; }
+    else { out->launch = &launch_p6_or_v3<PREC_BF16, false, false>; out->launchCausal = &launch_p6_or_v3<PREC_BF16, false, true>; out->launchSplit = &launch_p6_or_v3_split<PREC_BF16, false>; }
   } else {
-    if (fold) { out->launch = &launch_p6_or_v3<PREC_FP16, true>; out->launchCausal = &launch_p6_or_v3_causal<PREC_FP16, true>; out->launchSplit = &launch_p6_or_v3_split<PREC_FP16, true>; out->splitForm = &p6_split_form_of<PREC_FP16, true>; out->launchForm = &p6_form_of<PREC_FP16, true>; }
-    else { out->launch = &launch_p6_or_v3<PREC_FP16, false>; out->launchCausal = &launch_p6_or_v3_causal<PREC_FP16, false>; out->launchSplit = &launch_p6_or_v3_split<PREC_FP16, false>; out->splitForm = &p6_split_form_of<PREC_FP16, false>; out->launchForm = &p6_form_of<PREC_FP16, false>; }
+    if (fold) { out->launch = &launch_p6_or_v3<PREC_FP16, true, false>; out->launchCausal = &launch_p6_or_v3<PREC_FP16, true, true>; out->launchSplit = &launch_p6_or_v3_split<PREC_FP16, true>; }
+    else { out->launch = &launch_p6_or_v3<PREC_FP16, false, false>; out->launchCausal = &launch_p6_or_v3<PREC_FP16, false, true>; out->launchSplit = &launch_p6_or_v3_split<PREC_FP16, false>; }
   }
   return true;
 }

@@ -13,24 +13,25 @@ template <int D, int NW, int RB, int RING, int VD> constexpr int fwd16v3_lds_byt
 }
 
 template <typename T, int D, int NW, int RB, int THR, int PRE, int ABL = 0, int RING = 3, int VD = 0>
-static void launch_v3(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_fwd16_v3<T, D, NW, RB, THR, PRE, ABL, RING, false, false, VD>), dim3(grid.x * grid.y * grid.z), dim3(NW * 64),
-                     (fwd16v3_lds_bytes<D, NW, RB, RING, VD>()), stream, args, g);
+static const char *launch_v3(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_fwd16_v3<T, D, NW, RB, THR, PRE, ABL, RING, false, false, VD>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(NW * 64),
+          (fwd16v3_lds_bytes<D, NW, RB, RING, VD>()), l.args, g);
+  return nullptr;
 }
 
 template <typename T, int D, int NW, int RB, int THR, int PRE, int ABL = 0, int RING = 3, int VD = 0>
-static void launch_v3_split(dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z, splits, wsO, wsML};
-  hipLaunchKernelGGL((attn_fwd16_v3<T, D, NW, RB, THR, PRE, ABL, RING, true, false, VD>), dim3(grid.x * grid.y * grid.z * splits),
-                     dim3(NW * 64), (fwd16v3_lds_bytes<D, NW, RB, RING, VD>()), stream, args, g);
-  const uint64_t rows = (uint64_t)grid.y * grid.z * args.R;
-  hipLaunchKernelGGL(attn_fwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args, g);
+static const char *launch_v3_split(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z, l.splits, l.wsO, l.wsML};
+  l.start(&attn_fwd16_v3<T, D, NW, RB, THR, PRE, ABL, RING, true, false, VD>, dim3(l.grid.x * l.grid.y * l.grid.z * l.splits),
+          dim3(NW * 64), (fwd16v3_lds_bytes<D, NW, RB, RING, VD>()), l.args, g);
+  const uint64_t rows = (uint64_t)l.grid.y * l.grid.z * l.args.R;
+  l.start(&attn_fwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, l.args, g);
+  return nullptr;
 }
 
 template <typename T, int D, int NW, int RB, int THR, int PRE, int ABL = 0, int RING = 3, int VD = 0>
 static void fill(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_fwd16_v3<T, D, NW, RB, THR, PRE, ABL, RING, false, false, VD>);
   v->name = name;
   v->parallelization = NW * RB * 32;
   v->traversal = 32;   // pipeline step: half a 64-key LDS tile (attn_fwd16_v3.h)
@@ -43,21 +44,23 @@ static void fill(VariantInfo *v, const char *name) {
 }
 
 template <typename T, int D, int NW, int RB, int THR, int PRE, int RING, int VD>
-static void launch_v3_causal(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_fwd16_v3<T, D, NW, RB, THR, PRE, 0, RING, false, true, VD>), dim3(grid.x * grid.y * grid.z),
-                     dim3(NW * 64), (fwd16v3_lds_bytes<D, NW, RB, RING, VD>()), stream, args, g);
+static const char *launch_v3_causal(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_fwd16_v3<T, D, NW, RB, THR, PRE, 0, RING, false, true, VD>, dim3(l.grid.x * l.grid.y * l.grid.z),
+          dim3(NW * 64), (fwd16v3_lds_bytes<D, NW, RB, RING, VD>()), l.args, g);
+  return nullptr;
 }
 
 template <typename T, int D, int NW, int RB, int THR, int PRE, int RING, int VD>
-static void launch_v3_sparse(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  if (args.causal)
-    hipLaunchKernelGGL((attn_fwd16_v3<T, D, NW, RB, THR, PRE, 0, RING, false, true, VD, true>), dim3(grid.x * grid.y * grid.z),
-                       dim3(NW * 64), (fwd16v3_lds_bytes<D, NW, RB, RING, VD>()), stream, args, g);
+static const char *launch_v3_sparse(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  if (l.args.causal)
+    l.start(&attn_fwd16_v3<T, D, NW, RB, THR, PRE, 0, RING, false, true, VD, true>, dim3(l.grid.x * l.grid.y * l.grid.z),
+            dim3(NW * 64), (fwd16v3_lds_bytes<D, NW, RB, RING, VD>()), l.args, g);
   else
-    hipLaunchKernelGGL((attn_fwd16_v3<T, D, NW, RB, THR, PRE, 0, RING, false, false, VD, true>), dim3(grid.x * grid.y * grid.z),
-                       dim3(NW * 64), (fwd16v3_lds_bytes<D, NW, RB, RING, VD>()), stream, args, g);
+    l.start(&attn_fwd16_v3<T, D, NW, RB, THR, PRE, 0, RING, false, false, VD, true>, dim3(l.grid.x * l.grid.y * l.grid.z),
+            dim3(NW * 64), (fwd16v3_lds_bytes<D, NW, RB, RING, VD>()), l.args, g);
+  return nullptr;
 }
 
 // product variants: the dense code object plus its causal, block-sparse and column-parallel siblings (VDS: schedule
@@ -66,12 +69,8 @@ template <typename T, int D, int NW, int RB, int THR, int PRE, int RING = 3, int
 static void fill_with_split(VariantInfo *v, const char *name) {
   fill<T, D, NW, RB, THR, PRE, 0, RING, VD>(v, name);
   v->launchSparse = &launch_v3_sparse<T, D, NW, RB, THR, PRES, RING, VDS>;
-  v->funcSparse = reinterpret_cast<const void *>(&attn_fwd16_v3<T, D, NW, RB, THR, PRES, 0, RING, false, false, VDS, true>);
-  v->funcSparseCausal = reinterpret_cast<const void *>(&attn_fwd16_v3<T, D, NW, RB, THR, PRES, 0, RING, false, true, VDS, true>);
   v->launchSplit = &launch_v3_split<T, D, NW, RB, THR, PRE, 0, RING, VD>;
-  v->funcSplit = reinterpret_cast<const void *>(&attn_fwd16_v3<T, D, NW, RB, THR, PRE, 0, RING, true, false, VD>);
   v->launchCausal = &launch_v3_causal<T, D, NW, RB, THR, PRE, RING, VD>;
-  v->funcCausal = reinterpret_cast<const void *>(&attn_fwd16_v3<T, D, NW, RB, THR, PRE, 0, RING, false, true, VD>);
   v->causal = true;
 }
 
@@ -79,16 +78,16 @@ static void fill_with_split(VariantInfo *v, const char *name) {
 // are run-time flags of these kernels.  No column-parallel or block-sparse siblings: such launches stay row-parallel /
 // go to the general kernel.
 template <typename T, int D, int NW, int RING, int VD, int TR>
-static void launch_v3_tr(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_fwd16_v3<T, D, NW, 1, 8, 0, 0, RING, false, true, VD, false, TR>), dim3(grid.x * grid.y * grid.z),
-                     dim3(NW * 64), (fwd16v3_lds_bytes<D, NW, 1, RING, VD>()), stream, args, g);
+static const char *launch_v3_tr(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_fwd16_v3<T, D, NW, 1, 8, 0, 0, RING, false, true, VD, false, TR>, dim3(l.grid.x * l.grid.y * l.grid.z),
+          dim3(NW * 64), (fwd16v3_lds_bytes<D, NW, 1, RING, VD>()), l.args, g);
+  return nullptr;
 }
 
 template <typename T, int D, int NW, int RING, int VD, int TR>
 static void fill_tr(VariantInfo *v, const char *name) {
   *v = VariantInfo();
-  v->func = reinterpret_cast<const void *>(&attn_fwd16_v3<T, D, NW, 1, 8, 0, 0, RING, false, true, VD, false, TR>);
   v->name = name;
   v->parallelization = NW * 32;
   v->traversal = 32;

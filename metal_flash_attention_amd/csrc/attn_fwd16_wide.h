@@ -19,7 +19,8 @@
 //     is the B operand of the second; K image rows of D x 2 bytes with their 16-byte chunks XOR-swizzled by (key & 7), V image
 //     [D / 32][32 keys][64 bytes] read by ds_read_b64_tr_b16 pairs.
 // Dense, causal (CAUSAL code object) and per-batch lengths; row-major operands with 16-byte aligned rows (the host checks);
-// transposed operands and block masks keep the general kernel.  Exact-scale arithmetic (s * scale2 - m in fp32) in both
+// transposed operands run on row-major copies in the caller's workspace (the re-layout pass of mfa_kernel.hip; without a workspace,
+// the general kernel); block masks keep the general kernel.  Exact-scale arithmetic (s * scale2 - m in fp32) in both
 // precision modes; L in the descriptor's storage type.
 #pragma once
 #include "attn_fwd16_common.h"

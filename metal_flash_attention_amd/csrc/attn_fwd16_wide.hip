@@ -5,14 +5,13 @@
 namespace mfa {
 
 template <typename T, int DP, bool CAUSAL>
-static void launch_wide(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_fwd16_wide<T, DP, CAUSAL>), dim3(grid.x * grid.y * grid.z), dim3(256), wide::lds_bytes<DP>(), stream, args, g);
+static const char *launch_wide(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_fwd16_wide<T, DP, CAUSAL>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(256), wide::lds_bytes<DP>(), l.args, g);
+  return nullptr;
 }
 
 template <typename T, int DP> static void fill_wide(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_fwd16_wide<T, DP, false>);
-  v->funcCausal = reinterpret_cast<const void *>(&attn_fwd16_wide<T, DP, true>);
   v->name = name;
   v->parallelization = wide::ROWS;
   v->traversal = wide::BK;

@@ -6,24 +6,21 @@
 namespace mfa {
 
 template <int DP, int NW, bool CACHE, bool X = false>
-static void launch_dkv(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  if constexpr (NW == 4 && CACHE && (DP == 64 || DP == 128))   // the FP32 production case: attn_f32.h
-    if (f32_launch(2, DP, grid, stream, args)) return;
+static const char *launch_dkv(const Launch &l) {
   constexpr uint32_t lds = generic_dkv_lds_floats<DP, NW, CACHE, X>() * sizeof(float);
-  hipLaunchKernelGGL((attn_generic_dkv<DP, NW, CACHE, false, X>), grid, dim3(NW * 64), lds, stream, args);
+  l.start(&attn_generic_dkv<DP, NW, CACHE, false, X>, l.grid, dim3(NW * 64), lds, l.args);
+  return nullptr;
 }
 
 template <int DP, int NW, bool CACHE, bool X = false>
-static void launch_dkv_masked(dim3 grid, hipStream_t stream, const KernelArgs &args) {
+static const char *launch_dkv_masked(const Launch &l) {
   constexpr uint32_t lds = generic_dkv_lds_floats<DP, NW, CACHE, X>() * sizeof(float);
-  hipLaunchKernelGGL((attn_generic_dkv<DP, NW, CACHE, true, X>), grid, dim3(NW * 64), lds, stream, args);
+  l.start(&attn_generic_dkv<DP, NW, CACHE, true, X>, l.grid, dim3(NW * 64), lds, l.args);
+  return nullptr;
 }
-
-template <int DP> static const char *f32_form_of(const KernelArgs &args) { return f32_form(2, DP, args); }
 
 template <int DP, int NW, bool CACHE, bool X = false>
 static void fill(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_generic_dkv<DP, NW, CACHE, false, X>);
   v->name = name;
   v->parallelization = NW * 32;
   v->traversal = 32;
@@ -34,9 +31,7 @@ static void fill(VariantInfo *v, const char *name) {
   v->cacheSecond = CACHE;
   v->causal = true;
   v->launchSparse = &launch_dkv_masked<DP, NW, CACHE, X>;   // block mask: own code objects
-  v->funcSparse = reinterpret_cast<const void *>(&attn_generic_dkv<DP, NW, CACHE, true, X>);
   v->launch = &launch_dkv<DP, NW, CACHE, X>;
-  if constexpr (NW == 4 && CACHE && (DP == 64 || DP == 128)) v->launchForm = &f32_form_of<DP>;
 }
 
 bool generic_dkv_variant(int DP, VariantInfo *out) {

@@ -6,24 +6,21 @@
 namespace mfa {
 
 template <int DP, int NW, bool CACHE>
-static void launch_fwd(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  if constexpr (NW == 4 && CACHE && (DP == 64 || DP == 128))   // the FP32 production case: attn_f32.h
-    if (f32_launch(0, DP, grid, stream, args)) return;
+static const char *launch_fwd(const Launch &l) {
   constexpr uint32_t lds = generic_fwd_lds_floats<DP, NW, CACHE>() * sizeof(float);
-  hipLaunchKernelGGL((attn_generic_fwd<DP, NW, CACHE>), grid, dim3(NW * 64), lds, stream, args);
+  l.start(&attn_generic_fwd<DP, NW, CACHE>, l.grid, dim3(NW * 64), lds, l.args);
+  return nullptr;
 }
 
 template <int DP, int NW, bool CACHE>
-static void launch_fwd_masked(dim3 grid, hipStream_t stream, const KernelArgs &args) {
+static const char *launch_fwd_masked(const Launch &l) {
   constexpr uint32_t lds = generic_fwd_lds_floats<DP, NW, CACHE>() * sizeof(float);
-  hipLaunchKernelGGL((attn_generic_fwd<DP, NW, CACHE, true>), grid, dim3(NW * 64), lds, stream, args);
+  l.start(&attn_generic_fwd<DP, NW, CACHE, true>, l.grid, dim3(NW * 64), lds, l.args);
+  return nullptr;
 }
-
-template <int DP> static const char *f32_form_of(const KernelArgs &args) { return f32_form(0, DP, args); }
 
 template <int DP, int NW, bool CACHE>
 static void fill(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_generic_fwd<DP, NW, CACHE>);
   v->name = name;
   v->parallelization = NW * 32;
   v->traversal = 32;
@@ -34,9 +31,7 @@ static void fill(VariantInfo *v, const char *name) {
   v->cacheSecond = CACHE;
   v->causal = true;
   v->launchSparse = &launch_fwd_masked<DP, NW, CACHE>;   // block mask: own code objects
-  v->funcSparse = reinterpret_cast<const void *>(&attn_generic_fwd<DP, NW, CACHE, true>);
   v->launch = &launch_fwd<DP, NW, CACHE>;
-  if constexpr (NW == 4 && CACHE && (DP == 64 || DP == 128)) v->launchForm = &f32_form_of<DP>;
 }
 
 bool generic_fwd_variant(int DP, VariantInfo *out) {

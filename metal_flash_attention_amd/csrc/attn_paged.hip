@@ -6,13 +6,13 @@
 namespace mfa {
 
 template <void (*KERNEL)(const KernelArgs, const paged::Grid)>
-static void launch_paged(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  paged::Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL(KERNEL, dim3(grid.x * grid.y * grid.z), dim3(256), 0, stream, args, g);
+static const char *launch_paged(const Launch &l) {
+  paged::Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(KERNEL, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(256), 0, l.args, g);
+  return nullptr;
 }
 
 template <void (*KERNEL)(const KernelArgs, const paged::Grid)> static void fill_paged(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(KERNEL);
   v->name = name;
   v->parallelization = paged::BR;   // rows (forward, backwardQuery) or keys (backwardKeyValue) per workgroup
   v->traversal = paged::BC;

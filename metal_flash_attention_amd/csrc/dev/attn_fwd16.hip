@@ -5,16 +5,16 @@
 namespace mfa {
 
 template <typename T, int D, int NW, int RB>
-static void launch_fwd16(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  // `grid` arrives as (row blocks, heads, batches); the kernel uses a flat XCD-aware order
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_fwd16<T, D, NW, RB>), dim3(grid.x * grid.y * grid.z), dim3(NW * 64),
-                     fwd16_lds_bytes<D>(), stream, args, g);
+static const char *launch_fwd16(const Launch &l) {
+  // `l.grid` arrives as (row blocks, heads, batches); the kernel uses a flat XCD-aware order
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_fwd16<T, D, NW, RB>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(NW * 64),
+          fwd16_lds_bytes<D>(), l.args, g);
+  return nullptr;
 }
 
 template <typename T, int D, int NW, int RB>
 static void fill(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_fwd16<T, D, NW, RB>);
   v->name = name;
   v->parallelization = NW * RB * 32;
   v->traversal = 64;

@@ -5,15 +5,15 @@
 namespace mfa {
 
 template <typename T, int D, int NW, int RB, int THR, bool MSUM>
-static void launch_v2(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_fwd16_v2<T, D, NW, RB, THR, MSUM>), dim3(grid.x * grid.y * grid.z), dim3(NW * 64),
-                     (fwd16v2_lds_bytes<D, NW, RB>()), stream, args, g);
+static const char *launch_v2(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_fwd16_v2<T, D, NW, RB, THR, MSUM>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(NW * 64),
+          (fwd16v2_lds_bytes<D, NW, RB>()), l.args, g);
+  return nullptr;
 }
 
 template <typename T, int D, int NW, int RB, int THR, bool MSUM>
 static void fill(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_fwd16_v2<T, D, NW, RB, THR, MSUM>);
   v->name = name;
   v->parallelization = NW * RB * 32;
   v->traversal = 64;

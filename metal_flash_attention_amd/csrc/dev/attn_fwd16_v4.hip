@@ -5,29 +5,31 @@
 namespace mfa {
 
 template <typename T, int D, int THR, int OPT, int RING>
-static void launch_v4(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_fwd16_v4<T, D, 8, THR, OPT, RING, false, false>), dim3(grid.x * grid.y * grid.z), dim3(512),
-                     (fwd16v2_lds_bytes<D, 8, 1, RING>()), stream, args, g);
+static const char *launch_v4(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_fwd16_v4<T, D, 8, THR, OPT, RING, false, false>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(512),
+          (fwd16v2_lds_bytes<D, 8, 1, RING>()), l.args, g);
+  return nullptr;
 }
 template <typename T, int D, int THR, int OPT, int RING>
-static void launch_v4_causal(dim3 grid, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z};
-  hipLaunchKernelGGL((attn_fwd16_v4<T, D, 8, THR, OPT, RING, false, true>), dim3(grid.x * grid.y * grid.z), dim3(512),
-                     (fwd16v2_lds_bytes<D, 8, 1, RING>()), stream, args, g);
+static const char *launch_v4_causal(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
+  l.start(&attn_fwd16_v4<T, D, 8, THR, OPT, RING, false, true>, dim3(l.grid.x * l.grid.y * l.grid.z), dim3(512),
+          (fwd16v2_lds_bytes<D, 8, 1, RING>()), l.args, g);
+  return nullptr;
 }
 template <typename T, int D, int THR, int OPT, int RING>
-static void launch_v4_split(dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream, const KernelArgs &args) {
-  Fwd16Grid g{grid.x, grid.y, grid.z, splits, wsO, wsML};
-  hipLaunchKernelGGL((attn_fwd16_v4<T, D, 8, THR, OPT, RING, true, false>), dim3(grid.x * grid.y * grid.z * splits), dim3(512),
-                     (fwd16v2_lds_bytes<D, 8, 1, RING>()), stream, args, g);
-  const uint64_t rows = (uint64_t)grid.y * grid.z * args.R;
-  hipLaunchKernelGGL(attn_fwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args, g);
+static const char *launch_v4_split(const Launch &l) {
+  Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z, l.splits, l.wsO, l.wsML};
+  l.start(&attn_fwd16_v4<T, D, 8, THR, OPT, RING, true, false>, dim3(l.grid.x * l.grid.y * l.grid.z * l.splits), dim3(512),
+          (fwd16v2_lds_bytes<D, 8, 1, RING>()), l.args, g);
+  const uint64_t rows = (uint64_t)l.grid.y * l.grid.z * l.args.R;
+  l.start(&attn_fwd_combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, l.args, g);
+  return nullptr;
 }
 
 template <typename T, int D, int THR, int OPT, int RING, bool FULL>
 static void fill(VariantInfo *v, const char *name) {
-  v->func = reinterpret_cast<const void *>(&attn_fwd16_v4<T, D, 8, THR, OPT, RING, false, false>);
   v->name = name;
   v->parallelization = 256;
   v->traversal = 64;
@@ -40,7 +42,6 @@ static void fill(VariantInfo *v, const char *name) {
   if constexpr (FULL) {
     v->launchSplit = &launch_v4_split<T, D, THR, OPT, RING>;
     v->launchCausal = &launch_v4_causal<T, D, THR, OPT, RING>;
-    v->funcCausal = reinterpret_cast<const void *>(&attn_fwd16_v4<T, D, 8, THR, OPT, RING, false, true>);
     v->causal = true;
   }
 }

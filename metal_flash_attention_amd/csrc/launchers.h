@@ -4,8 +4,43 @@
 
 namespace mfa {
 
+// Every attention launch goes through launch_kernel: a kernel that takes more than 64 KiB of dynamic LDS has that limit raised the
+// first time it is launched on a device (raise_lds_limit, mfa_kernel.hip); after that a launch makes no driver call but the launch
+// itself, which is what graph capture needs.  A failure to raise the limit launches nothing and is returned.
+hipError_t raise_lds_limit(const void *kernel, uint32_t bytes);
+template <typename... Params, typename... Args>
+hipError_t launch_kernel(void (*kernel)(Params...), dim3 grid, dim3 block, uint32_t lds, hipStream_t stream, const Args &...args) {
+  if (lds > 64 * 1024) {
+    const hipError_t err = raise_lds_limit(reinterpret_cast<const void *>(kernel), lds);
+    if (err != hipSuccess) return err;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+  return hipSuccess;
+}
+
+// One launch as an entry point of a variant sees it.  The entry point decides which code object serves the launch, starts it when
+// `run` is set, and returns the launch form's text for that choice (mfa_attention_kernel_launch_form): nullptr = the variant's own
+// code object (VariantInfo::name); for launchSplit / launchSplitCausal, the text of the pieces (nullptr: the sibling's).  The same
+// entry point answers mfa_attention_kernel_launch / _time (run) and _launch_form (not run), so what runs is what the form names.
+struct Launch {
+  const KernelArgs &args;
+  dim3 grid;
+  uint32_t splits;         // > 1: column-parallel pieces, partial results in wsO (and wsML: forward)
+  float *wsO, *wsML;
+  hipStream_t stream;
+  bool run;
+  mutable hipError_t err;  // the first failed HIP call of a run; nothing is started after it
+  template <typename... Params, typename... Args>
+  void start(void (*kernel)(Params...), dim3 g, dim3 block, uint32_t lds, const Args &...a) const {
+    if (run && err == hipSuccess) err = launch_kernel(kernel, g, block, lds, stream, a...);
+  }
+};
+typedef const char *(*LaunchFn)(const Launch &l);
+
+// compute units of the current device (mfa_kernel.hip; cached per device)
+hipError_t compute_units(int *cus);
+
 struct VariantInfo {
-  const void *func = nullptr;   // __global__ function address (for hipFuncSetAttribute)
   const char *name = "";
   // the variant whose launchSplit / launchSplitCausal / launchSparse this one inherited (a hand-placed stream laid over the 8 x 32 /
   // role-split kernel of the same block dimensions): named in the launch form of such launches; nullptr = they are its own
@@ -19,52 +54,34 @@ struct VariantInfo {
   uint16_t headBlock = 0;       // padded head dimension the code object is unrolled for
   uint32_t threads = 0;         // work-items per workgroup
   uint32_t ldsBytes = 0;        // dynamic LDS of the variant's code object (mfa_attention_kernel_threadgroup_memory_allocation)
-  uint32_t attrLdsBytes = 0;    // what `func` (+ siblings) is raised to when that differs (0: ldsBytes): the FP32 production variants keep
-                                // the general kernel in `func` for the launches it still serves (attn_f32.hip raises its own kernels)
   bool cacheLeft = false;       // left-hand operands cached in VGPRs (Q / Q,dO / K,V)
   bool cacheSecond = false;     // the second of them alone (dO / V); fill code sets it = cacheLeft unless a variant splits the pair
   bool pagedAccumulators = false;   // accumulators paged through the output buffers (any-D kernels, attn_paged.h); else in registers
   bool causal = false;          // the code object implements the causal mask itself (general kernels: always)
   bool transposedInPlace = false;   // reads / writes transposed operands where they lie, whatever their alignment (attn_fwd16_v3.h, TR)
-  void (*launch)(dim3 grid, hipStream_t stream, const KernelArgs &args) = nullptr;
-  // dense / causal launches that `launch` / `launchCausal` hand to another code object (the persistent form of the D <= 128
-  // forward kernel): its name for such a launch, nullptr when the variant's own kernel runs (mfa_attention_kernel_launch_form)
-  const char *(*launchForm)(const KernelArgs &args) = nullptr;
-  // the same for a column-parallel launch whose pieces `launchSplit` hands to another code object than the sibling's (the persistent
-  // D <= 64 forward kernel cuts launches of whole four-tile pieces itself): text for the launch form, nullptr = the sibling's pieces
-  const char *(*splitForm)(const KernelArgs &args, uint32_t splits) = nullptr;
+  LaunchFn launch = nullptr;
   // forward only: column-parallel launch (key range cut into `splits` pieces, partial results in the
   // caller's workspace, then the combine kernel); nullptr if the variant has none
-  void (*launchSplit)(dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream,
-                      const KernelArgs &args) = nullptr;
+  LaunchFn launchSplit = nullptr;
   // causal traversal-parallel launches, when they belong to another kernel than launchSplit (nullptr: launchSplit takes both)
-  void (*launchSplitCausal)(dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream, const KernelArgs &args) = nullptr;
+  LaunchFn launchSplitCausal = nullptr;
   // separate code object implementing the causal mask (the unmasked loop bodies stay branch-free);
   // nullptr when `launch` handles the flag itself (general kernels) or the variant has no mask
-  void (*launchCausal)(dim3 grid, hipStream_t stream, const KernelArgs &args) = nullptr;
-  const void *funcCausal = nullptr;
+  LaunchFn launchCausal = nullptr;
   // code objects that honour KernelArgs.mask (block-sparse extension; the launcher picks the causal or the
   // unmasked one from args.causal); nullptr = the variant has none and the general kernels serve the launch
-  void (*launchSparse)(dim3 grid, hipStream_t stream, const KernelArgs &args) = nullptr;
-  const void *funcSparse = nullptr, *funcSparseCausal = nullptr;
+  LaunchFn launchSparse = nullptr;
   bool sparse = false;   // `launch` itself honours the mask (general kernels)
-  // code objects of launchSplit that need the large-LDS attribute (backward kernels; the forward split variant
-  // is registered by its launcher's first use of the same attribute path)
-  const void *funcSplit = nullptr, *funcSplitCausal = nullptr;
 };
 
 // any head dimension (D > 384): D-blocked products, accumulators paged through the FP32 output buffers (attn_paged.h); type = kernel type
 bool paged_variant(int type, VariantInfo *out);
 
 // generic (fp32-MFMA) family: returns false if (DP) is not compiled
-// FP32 production kernels (attn_f32.h): the general kernels' launchers of the 64 / 128 head blocks hand over the launches whose
-// operands qualify (all FP32, row-major, 16-byte aligned rows, D % 4 == 0, no block mask).  type: 0 forward, 1 backwardQuery,
-// 2 backwardKeyValue; grid as the general kernel's (blocks of 128, heads, batches).  false / nullptr: not one of theirs
-bool f32_launch(int type, int DP, dim3 grid, hipStream_t stream, const KernelArgs &args);
-const char *f32_form(int type, int DP, const KernelArgs &args);
 // FP32 descriptors with row-major operands and D % 4 == 0 at the 64 / 128 head blocks: the variant IS the FP32 production kernel
 // (own name, own LDS bytes); `out` arrives filled by generic_*_variant(DP), whose kernel becomes the sibling that keeps block-sparse
-// launches and launches whose operands miss the 16-byte row alignment
+// launches and launches whose operands miss the 16-byte row alignment.  The FP32 kernels take the launches whose operands qualify
+// (all FP32, row-major, 16-byte aligned rows, D % 4 == 0, no block mask).  type: 0 forward, 1 backwardQuery, 2 backwardKeyValue
 bool f32_variant(int type, int DP, VariantInfo *out);
 bool generic_fwd_variant(int DP, VariantInfo *out);
 bool generic_dq_variant(int DP, VariantInfo *out);
@@ -82,9 +99,6 @@ bool fwd16_p4_variant(int precision, int D, int impl, VariantInfo *out);
 // scale folded into Q, row sums in the matrix pipe); `out` arrives filled by fwd16_v3_variant(precision, 64, 0), whose kernel keeps
 // the launches this one does not serve
 bool fwd16_p6_variant(int precision, bool fold, VariantInfo *out);
-bool launch_p6(int precision, bool fold, dim3 grid, hipStream_t stream, const KernelArgs &args);
-const char *p6_form(int precision, bool fold, const KernelArgs &args);
-bool launch_p6_split(int precision, bool fold, dim3 grid, uint32_t splits, float *wsO, float *wsML, hipStream_t stream, const KernelArgs &args);
 // 256 < D <= 384 (head blocks 320, 384): four waves x 32 rows, 32-key steps, compiler-scheduled (attn_fwd16_wide.h, round 6)
 bool fwd16_wide_variant(int precision, int D, VariantInfo *out);
 // the backward kernels of the same head blocks (attn_bwd16_wide.hip: attn_dq16 with 32-key tiles, attn_dkv16_wide.h; round 6)
@@ -133,9 +147,9 @@ bool dkv16_rs_variant_d96(int precision, int gprecision, VariantInfo *out);
 bool dkv16_rs_variant_d160(int precision, int gprecision, VariantInfo *out);
 bool dkv16_rs_variant_d192(int precision, int gprecision, VariantInfo *out);
 
-// backward kernels that read transposed operands in place (attn_bwd16_p4_tr.hip); false = not such a launch
-bool bwd16_p4_tr_launch(int type, const KernelArgs &args, uint32_t heads, uint32_t batches, hipStream_t stream, bool fold);
-const char *bwd16_p4_tr_form(int type, const KernelArgs &args);
+// backward kernels that read transposed operands in place (attn_bwd16_p4_tr.hip; l.grid = (row or column blocks, heads, batches)):
+// the launch form's text, nullptr = not a launch these kernels take (nothing is started then)
+const char *bwd16_p4_tr_launch(int type, bool fold, const Launch &l);
 // launches with K^T and / or V^T at the buckets 160 / 192 / 256 that are whole 32-key steps of aligned rows go
 // to the hand-placed stream (attn_fwd16_p5_tr.h); `out` arrives filled by fwd16_v3_tr_variant_dNN, whose kernel keeps the others
 bool fwd16_p5_tr_variant(int precision, int bucket, int pattern, bool fold, VariantInfo *out);

@@ -12,7 +12,9 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "launchers.h"
@@ -27,10 +29,38 @@ struct mfa_attention_kernel {
   VariantInfo fallback;           // general code object, used when a launch does not meet the
   bool hasFallback = false;       // preferred variant's alignment requirements
   bool relayout = false;          // transposed operands: the preferred variant runs on row-major copies in the caller's workspace
-  std::mutex attrMutex;
-  uint64_t attrDeviceMask = 0;    // devices on which the LDS attribute has been raised (variant)
-  uint64_t attrDeviceMaskFallback = 0;
 };
+
+// launch_kernel (launchers.h): the dynamic-LDS limit of a code object, raised once per (kernel, device)
+hipError_t mfa::raise_lds_limit(const void *kernel, uint32_t bytes) {
+  static std::mutex guard;
+  static std::set<std::pair<const void *, int>> raised;
+  int device = 0;
+  hipError_t err = hipGetDevice(&device);
+  if (err != hipSuccess) return err;
+  const std::pair<const void *, int> key(kernel, device);
+  std::lock_guard<std::mutex> lock(guard);
+  if (raised.count(key)) return hipSuccess;
+  err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (err == hipSuccess) raised.insert(key);
+  return err;
+}
+
+// the persistent launchers (attn_fwd16_p4p.hip, attn_fwd16_p6.hip): compute units of the current device, cached per device
+hipError_t mfa::compute_units(int *cus) {
+  static std::mutex guard;
+  static int cached[64] = {};
+  int device = 0;
+  hipError_t err = hipGetDevice(&device);
+  if (err != hipSuccess) return err;
+  const bool cache = device >= 0 && device < 64;
+  std::lock_guard<std::mutex> lock(guard);
+  if (cache && cached[device] > 0) { *cus = cached[device]; return hipSuccess; }
+  err = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device);
+  if (err == hipSuccess && *cus <= 0) err = hipErrorInvalidValue;
+  if (err == hipSuccess && cache) cached[device] = *cus;
+  return err;
+}
 
 static mfa_status hip_fail(hipError_t err, const char *what) {
   return fail(MFA_ERR_HIP, std::string(what) + ": " + hipGetErrorName(err) + " (" + hipGetErrorString(err) + ")");
@@ -189,8 +219,8 @@ mfa_status mfa_attention_kernel_create(const mfa_attention_kernel_descriptor *kd
         // 32-row waves of attn_fwd16_v3.h, which also keep this kernel's causal / block-sparse / column-parallel launches
         v = v3;
         // (D <= 32 on this kernel: the launches it does not serve -- per-batch lengths, an L of the other storage type, pieces that
-        // are not whole multiples of four tiles -- go to the D = 64 eight-wave kernels, so the base must be THEIR variant: functions
-        // whose dynamic LDS attribute ensure_lds_attribute raises, 256-row blocks for split grids and choose_splits)
+        // are not whole multiples of four tiles -- go to the D = 64 eight-wave kernels, so the base must be THEIR variant: 256-row
+        // blocks for split grids and choose_splits)
         if (b16 == 32 && !fwd16_v3_variant(pq, 64, 0, &v)) v = v3;
         add(fwd16_p6_variant(pq, kdesc->registerPrecisions[MFA_P] > MFA_FP32, &v), v);
       }
@@ -471,9 +501,9 @@ struct LaunchPlan {
   Relayout relayouts[MFA_BUFFER_SLOTS];
   int nRelayouts = 0;
   uint32_t heads = 1, batches = 1;
-  // the missing workspace is the ONLY reason this launch left the matrix-core kernel (every operand meets the alignment and
-  // 32-bit slice-size requirements of the buffer descriptors): the condition under which the in-place backward kernels may take it
-  bool onlyWorkspaceMissing = false;
+  // a transposed backward launch without a workspace that the in-place kernels take (attn_bwd16_p4_tr.hip; AttentionKernel.swift:
+  // 189-204: the reference reads transposed operands in place in every kernel) instead of the general kernel
+  bool inPlaceBackward = false;
 };
 
 // ---- re-layout pass: element (r, d) of a [seq][D] matrix between a transposed view ([D][seq], leading dimension ld) and a
@@ -545,15 +575,15 @@ static __global__ __launch_bounds__(256) void attn_relayout(const char *tptr, ch
 
 extern "C" {
 
-static void launch_relayout(const LaunchPlan &plan, const LaunchPlan::Relayout &r, hipStream_t stream) {
+static hipError_t launch_relayout(const LaunchPlan &plan, const LaunchPlan::Relayout &r, hipStream_t stream) {
   const uint32_t D = plan.args.D;
   const dim3 grid(((r.seq + 63) / 64) * ((D + 63) / 64), plan.heads, plan.batches);
   const char *t = static_cast<const char *>(r.user.ptr);
   char *c = static_cast<char *>(r.copy);
+  const int toTransposed = r.output ? 1 : 0;
   if (r.user.precision == PREC_FP32)
-    hipLaunchKernelGGL(attn_relayout<uint32_t>, grid, dim3(256), 0, stream, t, c, r.seq, D, r.user.ld, r.user.headStride, r.user.batchStride, plan.heads, r.output ? 1 : 0);
-  else
-    hipLaunchKernelGGL(attn_relayout<uint16_t>, grid, dim3(256), 0, stream, t, c, r.seq, D, r.user.ld, r.user.headStride, r.user.batchStride, plan.heads, r.output ? 1 : 0);
+    return launch_kernel(&attn_relayout<uint32_t>, grid, dim3(256), 0, stream, t, c, r.seq, D, r.user.ld, r.user.headStride, r.user.batchStride, plan.heads, toTransposed);
+  return launch_kernel(&attn_relayout<uint16_t>, grid, dim3(256), 0, stream, t, c, r.seq, D, r.user.ld, r.user.headStride, r.user.batchStride, plan.heads, toTransposed);
 }
 
 static bool is_output_slot(int type, int slot) {
@@ -593,8 +623,12 @@ static uint32_t choose_splits(uint64_t blocks, uint32_t traversal, uint32_t para
   const uint32_t tiles = (traversal + 63) / 64;
   if (blocks >= 192 || tiles < 8) return 1;
   uint64_t s = target / blocks;
-  uint64_t best = 1;
-  while ((best + 1) * (best + 1) * (uint64_t)parallel <= 117ull * traversal + (uint64_t)parallel * (best + 1)) ++best;   // ~ round(sqrt(117 t / p))
+  // the cap ~ round(sqrt(117 t / p)): the largest b >= 1 with b (b - 1) p <= 117 t, i.e. b (b - 1) <= q -- the square root's estimate
+  // is off by at most one either way
+  const uint64_t q = 117ull * traversal / parallel;
+  uint64_t best = (1 + (uint64_t)std::sqrt(4.0 * (double)q + 1.0)) / 2;
+  while (best > 1 && best * (best - 1) > q) --best;
+  while ((best + 1) * best <= q) ++best;
   if (s > best) s = best;
 #ifdef MFA_DEV_VARIANTS
   if (const char *knob = std::getenv("MFA_SPLITS")) s = (uint64_t)std::atoi(knob);   // developer library: sweep of the piece count (tools/sweep_splits.py)
@@ -606,6 +640,19 @@ static uint32_t choose_splits(uint64_t blocks, uint32_t traversal, uint32_t para
   for (uint64_t c = s; c >= 2 && 2 * c > s; --c)
     if (traversal % (256 * c) == 0) { s = c; break; }
   return s < 2 ? 1 : (uint32_t)s;
+}
+
+// column-parallel geometry of a launch of `v` (workspace query and launch alike): workgroups along the parallelization dimension and
+// pieces of the traversal (1: no split).  The pieces are the variant's own kernel's (splitParallelization) or its sibling's
+struct SplitGeometry { uint32_t blocks, splits; };
+static SplitGeometry split_geometry(const VariantInfo &v, int type, uint32_t row, uint32_t column, bool causal, uint32_t heads, uint32_t batches) {
+  const bool kv = type == MFA_BACKWARD_KEY_VALUE;
+  const uint32_t par = kv ? column : row;   // (SquareAttentionTest.swift:355-367)
+  // (the hand-placed backward kernels split dense launches themselves; causal ones stay with their siblings)
+  const bool ownSplit = v.splitParallelization && !(causal && v.launchSplitCausal);
+  const uint32_t wg = ownSplit ? v.splitParallelization : v.siblingParallelization ? v.siblingParallelization : v.parallelization;
+  const uint32_t blocks = (par + wg - 1) / wg;
+  return {blocks, choose_splits((uint64_t)blocks * heads * batches, kv ? row : column, par, v.splitTarget ? v.splitTarget : 512)};
 }
 
 // bytes of workspace a launch cut into `s` pieces needs
@@ -700,13 +747,22 @@ static mfa_status prepare_launch(const mfa_attention_kernel *kernel, void *const
                             // attn_dkv16_rs lists at most 4096 active 256-row blocks in LDS
                             (args->mask && type == MFA_BACKWARD_KEY_VALUE && p->row > 4096u * 256u);
   plan->useFallback = kernel->hasFallback && (relayoutMissing || otherReasons);
-  plan->onlyWorkspaceMissing = kernel->hasFallback && relayoutMissing && !otherReasons;
+  // a transposed backward launch whose ONLY reason to leave the matrix-core kernel is the missing workspace (every operand meets the
+  // alignment and 32-bit slice-size requirements of the buffer descriptors, which the in-place kernels address every operand
+  // through) goes to the in-place kernels when they take it
+  if (kernel->hasFallback && relayoutMissing && !otherReasons && type != MFA_FORWARD) {
+    const Launch probe{*args, dim3(1, heads, batches), 1, nullptr, nullptr, nullptr, false, hipSuccess};
+    plan->inPlaceBackward = bwd16_p4_tr_launch(type, kernel->desc.registerPrecisions[MFA_P] > MFA_FP32, probe) != nullptr;
+  }
+#ifdef MFA_DEV_VARIANTS
+  const char *knob = std::getenv("MFA_BWD16_TR");   // developer library: MFA_BWD16_TR=0 -- never (A/B runs against the general kernel)
+  if (knob && std::strcmp(knob, "0") == 0) plan->inPlaceBackward = false;
+#endif
   // strictBlockDimensions: a backward launch on 16-bit transposed operands that has no workspace for the re-layout path and is not
   // one the in-place kernels take would run the general fp32 kernel -- 20-50 x slower than the code object the descriptor selected
   // (the reference reads transposed operands in place at every head dimension, AttentionKernel.swift:189-204).  A strict caller
   // gets an error that names the remedy instead of the silent fallback
-  if (kernel->desc.strictBlockDimensions && kernel->hasFallback && relayoutMissing && type != MFA_FORWARD &&
-      !(plan->onlyWorkspaceMissing && bwd16_p4_tr_form(type, *args) != nullptr)) {
+  if (kernel->desc.strictBlockDimensions && kernel->hasFallback && relayoutMissing && type != MFA_FORWARD && !plan->inPlaceBackward) {
     return fail(MFA_ERR_UNSUPPORTED,
                 std::string("strictBlockDimensions: this launch of ") + kernel->variant.name + " on transposed operands has no (or too small / "
                 "misaligned) workspace and would run the general kernel " + kernel->fallback.name + "; pass a 256-byte aligned workspace of " +
@@ -721,12 +777,10 @@ static mfa_status prepare_launch(const mfa_attention_kernel *kernel, void *const
   // parallelization dimension: rows for forward / backwardQuery, columns for backwardKeyValue
   // (SquareAttentionTest.swift:355-367)
   const uint32_t par = (type == MFA_BACKWARD_KEY_VALUE) ? p->column : p->row;
-  uint32_t blocks = (par + plan->variant->parallelization - 1) / plan->variant->parallelization;
-  // block-sparse and split launches may belong to a sibling kernel with its own workgroup shape (attn_dkv16_p4 keeps those of
-  // attn_dkv16_rs)
-  const uint32_t sibPar = plan->variant->siblingParallelization ? plan->variant->siblingParallelization : plan->variant->parallelization;
-  const uint32_t siblingBlocks = (par + sibPar - 1) / sibPar;
-  if (args->mask && plan->variant->launchSparse && !plan->useFallback) blocks = siblingBlocks;
+  // block-sparse launches may belong to a sibling kernel with its own workgroup shape (attn_dkv16_p4 keeps those of attn_dkv16_rs)
+  const uint32_t wgPar = args->mask && plan->variant->launchSparse && !plan->useFallback && plan->variant->siblingParallelization
+                             ? plan->variant->siblingParallelization : plan->variant->parallelization;
+  const uint32_t blocks = (par + wgPar - 1) / wgPar;
   if ((uint64_t)blocks * heads * batches > 0x7FFFFFFFull) return fail(MFA_ERR_INVALID_ARGUMENT, "grid too large");
   plan->grid = dim3(blocks, heads, batches);
   plan->splits = 1;
@@ -736,17 +790,14 @@ static mfa_status prepare_launch(const mfa_attention_kernel *kernel, void *const
   const bool splittable = !plan->useFallback && !kernel->relayout && plan->variant->launchSplit && !args->rowLen && !args->colLen && !args->mask &&
                           (type != MFA_FORWARD || !args->causal);
   if (splittable) {
-    // (the hand-placed backward kernels split dense launches themselves; causal ones stay with their siblings)
-    const bool ownSplit = plan->variant->splitParallelization && !(args->causal && plan->variant->launchSplitCausal);
-    const uint32_t sibBlocks = ownSplit ? (par + plan->variant->splitParallelization - 1) / plan->variant->splitParallelization : siblingBlocks;
-    const uint32_t s = choose_splits((uint64_t)sibBlocks * heads * batches, type == MFA_BACKWARD_KEY_VALUE ? p->row : p->column,
-                                     type == MFA_BACKWARD_KEY_VALUE ? p->column : p->row, plan->variant->splitTarget ? plan->variant->splitTarget : 512);
+    const SplitGeometry sg = split_geometry(*plan->variant, type, p->row, p->column, args->causal != 0, heads, batches);
+    const uint32_t s = sg.splits;
     if (s > 1) {
       plan->workspaceNeeded = split_workspace_bytes(type, s, heads, batches, p->row, p->column, D);
       if (p->workspace && p->workspaceBytes >= plan->workspaceNeeded &&
           (reinterpret_cast<uintptr_t>(p->workspace) & 15) == 0 && (D % 4) == 0 &&
-          (uint64_t)sibBlocks * heads * batches * s <= 0x7FFFFFFFull) {
-        plan->grid = dim3(sibBlocks, heads, batches);
+          (uint64_t)sg.blocks * heads * batches * s <= 0x7FFFFFFFull) {
+        plan->grid = dim3(sg.blocks, heads, batches);
         plan->splits = s;
         plan->wsO = static_cast<float *>(p->workspace);
         plan->wsML = plan->wsO + (uint64_t)s * heads * batches * p->row * D;   // forward only
@@ -756,76 +807,60 @@ static mfa_status prepare_launch(const mfa_attention_kernel *kernel, void *const
   return MFA_OK;
 }
 
-static auto split_launcher(const LaunchPlan &plan) -> decltype(plan.variant->launchSplit) {
-  return (plan.args.causal && plan.variant->launchSplitCausal) ? plan.variant->launchSplitCausal : plan.variant->launchSplit;
+// The one route of a prepared launch, for mfa_attention_kernel_launch / _time (run) and _launch_form (not run; `form` receives the
+// text): the in-place backward kernels, or the re-layout passes around the column-parallel (split + combine), block-sparse, causal or
+// dense entry point of the plan's variant.  Each entry point decides which code object serves the launch and names it.  Returns the
+// first failed HIP call of a run.
+static hipError_t run_plan(const mfa_attention_kernel *kernel, const LaunchPlan &plan, hipStream_t stream, bool run, std::string *form = nullptr) {
+  const Launch l{plan.args, plan.grid, plan.splits, plan.wsO, plan.wsML, stream, run, hipSuccess};
+  if (plan.inPlaceBackward) {
+    const char *chosen = bwd16_p4_tr_launch(kernel->desc.type, kernel->desc.registerPrecisions[MFA_P] > MFA_FP32, l);
+    if (form) *form = chosen;
+    return l.err;
+  }
+  for (int i = 0; i < plan.nRelayouts && run && l.err == hipSuccess; ++i)
+    if (!plan.relayouts[i].output) l.err = launch_relayout(plan, plan.relayouts[i], stream);
+  const VariantInfo &v = *plan.variant;
+  const bool causal = plan.args.causal != 0, sparse = plan.args.mask && v.launchSparse;
+  const char *chosen;
+  if (plan.splits > 1) chosen = (causal && v.launchSplitCausal ? v.launchSplitCausal : v.launchSplit)(l);
+  else if (sparse) chosen = v.launchSparse(l);
+  else chosen = (causal && v.launchCausal ? v.launchCausal : v.launch)(l);
+  for (int i = 0; i < plan.nRelayouts && run && l.err == hipSuccess; ++i)
+    if (plan.relayouts[i].output) l.err = launch_relayout(plan, plan.relayouts[i], stream);
+  if (form) {
+    std::string &text = *form;
+    text = plan.nRelayouts ? "attn_relayout x" + std::to_string(plan.nRelayouts) + " + " : "";
+    if (plan.useFallback) {
+      text += std::string(chosen ? chosen : v.name) + " (general kernel: the launch does not meet the requirements of " + kernel->variant.name + ")";
+    } else if (plan.splits > 1) {
+      text += std::string(v.name) + " column-parallel x" + std::to_string(plan.splits) + " + combine";
+      const bool own = v.splitParallelization && !(causal && v.launchSplitCausal);
+      if (chosen) text += std::string(" (") + chosen + ")";
+      else if (!own && v.siblingName) text += std::string(" (pieces by the sibling kernel ") + v.siblingName + ")";
+    } else {
+      text += chosen ? chosen : v.name;
+      if (sparse) text += v.siblingName ? std::string(" (block-sparse sibling ") + v.siblingName + ")" : std::string(" (block-sparse code object)");
+    }
+  }
+  return l.err;
 }
 
-// does this launch go to the in-place backward kernels? (transposed operands, no workspace)
-static bool dev_in_place_backward(const mfa_attention_kernel *kernel, const LaunchPlan &plan) {
-  // (a launch that ALSO misses the 16-byte alignment or the 32-bit slice size of the buffer descriptors stays with the general
-  // kernel and its 64-bit addressing: the in-place kernels address every operand through such descriptors)
-  if (!plan.useFallback || !plan.onlyWorkspaceMissing || !kernel->relayout || kernel->desc.type == MFA_FORWARD) return false;
-#ifdef MFA_DEV_VARIANTS
-  const char *knob = std::getenv("MFA_BWD16_TR");   // developer library: MFA_BWD16_TR=0 -- never (A/B runs against the general kernel)
-  if (knob && std::strcmp(knob, "0") == 0) return false;
-#endif
-  return bwd16_p4_tr_form(kernel->desc.type, plan.args) != nullptr;
-}
-
-static mfa_status ensure_lds_attribute(mfa_attention_kernel *kernel, const LaunchPlan &plan) {
-  const uint32_t attrBytes = plan.variant->attrLdsBytes > plan.variant->ldsBytes ? plan.variant->attrLdsBytes : plan.variant->ldsBytes;
-  if (attrBytes <= 64 * 1024) return MFA_OK;
-  int device = 0;
-  hipError_t err = hipGetDevice(&device);
-  if (err != hipSuccess) return hip_fail(err, "hipGetDevice");
-  std::lock_guard<std::mutex> lock(kernel->attrMutex);
-  uint64_t &mask = plan.useFallback ? kernel->attrDeviceMaskFallback : kernel->attrDeviceMask;
-  if (device < 64 && (mask >> device) & 1ull) return MFA_OK;
-  err = hipFuncSetAttribute(plan.variant->func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attrBytes);
-  if (err == hipSuccess && plan.variant->funcCausal)
-    err = hipFuncSetAttribute(plan.variant->funcCausal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attrBytes);
-  if (err == hipSuccess && plan.variant->funcSparse)
-    err = hipFuncSetAttribute(plan.variant->funcSparse, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attrBytes);
-  if (err == hipSuccess && plan.variant->funcSparseCausal)
-    err = hipFuncSetAttribute(plan.variant->funcSparseCausal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attrBytes);
-  if (err == hipSuccess && plan.variant->funcSplit)
-    err = hipFuncSetAttribute(plan.variant->funcSplit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attrBytes);
-  if (err == hipSuccess && plan.variant->funcSplitCausal)
-    err = hipFuncSetAttribute(plan.variant->funcSplitCausal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attrBytes);
-  if (err != hipSuccess) return hip_fail(err, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-  if (device < 64) mask |= 1ull << device;
-  return MFA_OK;
-}
+static const char *plan_name(const LaunchPlan &plan) { return plan.inPlaceBackward ? "attn_bwd16_p4_tr" : plan.variant->name; }
 
 mfa_status mfa_attention_kernel_launch(const mfa_attention_kernel *kernel, void *const buffers[MFA_BUFFER_SLOTS],
                                        const mfa_launch_params *params, void *stream) {
   LaunchPlan plan;
   mfa_status st = prepare_launch(kernel, buffers, params, &plan);
   if (st != MFA_OK) return st;
-  // a transposed backward launch without a workspace goes to the kernels that read the operands in place when they take it
-  // (attn_bwd16_p4_tr.hip; AttentionKernel.swift:189-204: the reference reads transposed operands in place in every kernel)
-  if (dev_in_place_backward(kernel, plan)) {
-    bwd16_p4_tr_launch(kernel->desc.type, plan.args, plan.heads, plan.batches, (hipStream_t)stream, kernel->desc.registerPrecisions[MFA_P] > MFA_FP32);
-    hipError_t derr = hipGetLastError();
+  hipError_t err = run_plan(kernel, plan, (hipStream_t)stream, true);
+  if (err == hipSuccess) err = hipGetLastError();
 #ifdef MFA_DEV_VARIANTS
-    const char *knob = std::getenv("MFA_BWD16_TR");
-    if (knob && std::strcmp(knob, "verbose") == 0)
-      std::fprintf(stderr, "mfa: %s on transposed operands in place\n", kernel->desc.type == MFA_BACKWARD_QUERY ? "attn_dq16_p4_tr" : "attn_dkv16_p4_tr");
+  const char *knob = std::getenv("MFA_BWD16_TR");
+  if (plan.inPlaceBackward && knob && std::strcmp(knob, "verbose") == 0)
+    std::fprintf(stderr, "mfa: %s on transposed operands in place\n", kernel->desc.type == MFA_BACKWARD_QUERY ? "attn_dq16_p4_tr" : "attn_dkv16_p4_tr");
 #endif
-    return derr == hipSuccess ? MFA_OK : hip_fail(derr, "attn_bwd16_p4_tr");
-  }
-  st = ensure_lds_attribute(const_cast<mfa_attention_kernel *>(kernel), plan);
-  if (st != MFA_OK) return st;
-  for (int i = 0; i < plan.nRelayouts; ++i)
-    if (!plan.relayouts[i].output) launch_relayout(plan, plan.relayouts[i], (hipStream_t)stream);
-  if (plan.splits > 1) split_launcher(plan)(plan.grid, plan.splits, plan.wsO, plan.wsML, (hipStream_t)stream, plan.args);
-  else if (plan.args.mask && plan.variant->launchSparse) plan.variant->launchSparse(plan.grid, (hipStream_t)stream, plan.args);
-  else if (plan.args.causal && plan.variant->launchCausal) plan.variant->launchCausal(plan.grid, (hipStream_t)stream, plan.args);
-  else plan.variant->launch(plan.grid, (hipStream_t)stream, plan.args);
-  for (int i = 0; i < plan.nRelayouts; ++i)
-    if (plan.relayouts[i].output) launch_relayout(plan, plan.relayouts[i], (hipStream_t)stream);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return hip_fail(err, plan.variant->name);
+  if (err != hipSuccess) return hip_fail(err, plan_name(plan));
   return MFA_OK;
 }
 
@@ -836,25 +871,7 @@ mfa_status mfa_attention_kernel_launch_form(const mfa_attention_kernel *kernel, 
   mfa_status st = prepare_launch(kernel, buffers, params, &plan);
   if (st != MFA_OK) return st;
   std::string text;
-  if (plan.nRelayouts) text += "attn_relayout x" + std::to_string(plan.nRelayouts) + " + ";
-  if (dev_in_place_backward(kernel, plan)) {
-    std::snprintf(out, capacity, "%s", bwd16_p4_tr_form(kernel->desc.type, plan.args));
-    return MFA_OK;
-  }
-  if (plan.useFallback) {
-    text += std::string(plan.variant->name) + " (general kernel: the launch does not meet the requirements of " + kernel->variant.name + ")";
-  } else if (plan.splits > 1) {
-    text += std::string(plan.variant->name) + " column-parallel x" + std::to_string(plan.splits) + " + combine";
-    const bool own = plan.variant->splitParallelization && !(plan.args.causal && plan.variant->launchSplitCausal);
-    const char *pieces = plan.variant->splitForm ? plan.variant->splitForm(plan.args, plan.splits) : nullptr;
-    if (pieces) text += std::string(" (") + pieces + ")";
-    else if (!own && plan.variant->siblingName) text += std::string(" (pieces by the sibling kernel ") + plan.variant->siblingName + ")";
-  } else {
-    const bool sparse = plan.args.mask && plan.variant->launchSparse;
-    const char *form = (!sparse && plan.variant->launchForm) ? plan.variant->launchForm(plan.args) : nullptr;
-    text += form ? form : plan.variant->name;
-    if (sparse) text += plan.variant->siblingName ? std::string(" (block-sparse sibling ") + plan.variant->siblingName + ")" : std::string(" (block-sparse code object)");
-  }
+  (void)run_plan(kernel, plan, nullptr, false, &text);   // (nothing is started: no HIP call)
   std::snprintf(out, capacity, "%s", text.c_str());
   return MFA_OK;
 }
@@ -872,13 +889,7 @@ mfa_status mfa_attention_kernel_workspace_size(const mfa_attention_kernel *kerne
   const int type = kernel->desc.type;
   if (params->rowLengths || params->columnLengths || params->blockMask || (type == MFA_FORWARD && params->causal)) return MFA_OK;
   const uint32_t heads = params->heads ? params->heads : 1, batches = params->batches ? params->batches : 1;
-  const uint32_t par = (type == MFA_BACKWARD_KEY_VALUE) ? params->column : params->row;
-  const bool ownSplit = kernel->variant.splitParallelization && !(params->causal && kernel->variant.launchSplitCausal);
-  const uint32_t wgPar = ownSplit ? kernel->variant.splitParallelization
-                                  : kernel->variant.siblingParallelization ? kernel->variant.siblingParallelization : kernel->variant.parallelization;
-  const uint32_t blocks = (par + wgPar - 1) / wgPar;
-  const uint32_t s = choose_splits((uint64_t)blocks * heads * batches, type == MFA_BACKWARD_KEY_VALUE ? params->row : params->column,
-                                   type == MFA_BACKWARD_KEY_VALUE ? params->column : params->row, kernel->variant.splitTarget ? kernel->variant.splitTarget : 512);
+  const uint32_t s = split_geometry(kernel->variant, type, params->row, params->column, params->causal != 0, heads, batches).splits;
   if (s > 1) *bytes = split_workspace_bytes(type, s, heads, batches, params->row, params->column, kernel->desc.headDimension);
   return MFA_OK;
 }
@@ -890,38 +901,23 @@ mfa_status mfa_attention_kernel_time(const mfa_attention_kernel *kernel, void *c
   LaunchPlan plan;
   mfa_status st = prepare_launch(kernel, buffers, params, &plan);
   if (st != MFA_OK) return st;
-  st = ensure_lds_attribute(const_cast<mfa_attention_kernel *>(kernel), plan);
-  if (st != MFA_OK) return st;
   hipStream_t s = (hipStream_t)stream;
   hipEvent_t start, stop;
   hipError_t err = hipEventCreate(&start);
   if (err != hipSuccess) return hip_fail(err, "hipEventCreate");
   err = hipEventCreate(&stop);
   if (err != hipSuccess) { (void)hipEventDestroy(start); return hip_fail(err, "hipEventCreate"); }
-  auto go = [&]() {
-    if (dev_in_place_backward(kernel, plan)) {
-      bwd16_p4_tr_launch(kernel->desc.type, plan.args, plan.heads, plan.batches, s, kernel->desc.registerPrecisions[MFA_P] > MFA_FP32);
-      return;
-    }
-    for (int i = 0; i < plan.nRelayouts; ++i)
-      if (!plan.relayouts[i].output) launch_relayout(plan, plan.relayouts[i], s);
-    if (plan.splits > 1) split_launcher(plan)(plan.grid, plan.splits, plan.wsO, plan.wsML, s, plan.args);
-    else if (plan.args.mask && plan.variant->launchSparse) plan.variant->launchSparse(plan.grid, s, plan.args);
-    else if (plan.args.causal && plan.variant->launchCausal) plan.variant->launchCausal(plan.grid, s, plan.args);
-    else plan.variant->launch(plan.grid, s, plan.args);
-    for (int i = 0; i < plan.nRelayouts; ++i)
-      if (plan.relayouts[i].output) launch_relayout(plan, plan.relayouts[i], s);
-  };
-  for (int i = 0; i < warmup; ++i) go();
-  (void)hipEventRecord(start, s);
-  for (int i = 0; i < iterations; ++i) go();
-  (void)hipEventRecord(stop, s);
-  err = hipEventSynchronize(stop);
+  // (a code object's first launch on a device raises its LDS limit, a host-side call: with warmup = 0 the first timed launch pays it)
+  for (int i = 0; i < warmup && err == hipSuccess; ++i) err = run_plan(kernel, plan, s, true);
+  if (err == hipSuccess) err = hipEventRecord(start, s);
+  for (int i = 0; i < iterations && err == hipSuccess; ++i) err = run_plan(kernel, plan, s, true);
+  if (err == hipSuccess) err = hipEventRecord(stop, s);
+  if (err == hipSuccess) err = hipEventSynchronize(stop);
   if (err == hipSuccess) err = hipGetLastError();
   if (err == hipSuccess) err = hipEventElapsedTime(milliseconds, start, stop);
   (void)hipEventDestroy(start);
   (void)hipEventDestroy(stop);
-  if (err != hipSuccess) return hip_fail(err, plan.variant->name);
+  if (err != hipSuccess) return hip_fail(err, plan_name(plan));
   return MFA_OK;
 }
 

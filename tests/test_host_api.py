@@ -200,6 +200,40 @@ def test_piece_count_of_one_head_launches():
         assert k.workspaceSize(row=N, column=N) == want * N * (D + 2) * 4, (N, D)
         dq = AttentionKernel(low.kernelDescriptor(T.backwardQuery)).workspaceSize(row=N, column=N)
         assert dq % (N * D * 4) == 0 and 2 <= dq // (N * D * 4) <= 11 and (N // 256) * (dq // (N * D * 4)) <= 256
+    # decode-like shapes (one row block, long key ranges up to 2^31): the cap of sqrt(117 traversal / parallel) is a closed form now;
+    # the counts are the ones the earlier linear search gave (at most 64 pieces, at least four tiles each, whole 256-key blocks preferred)
+    for R, C, D, want in ((1, 4096, 128, 16), (1, 1 << 20, 64, 64), (1, 1 << 31, 128, 64), (1, 5000, 64, 19), (8, 3000, 128, 11),
+                          (16, 1 << 16, 64, 64), (64, 1 << 31, 128, 64), (4, 100000, 64, 64), (32, 777777, 128, 64), (64, 4096, 64, 16),
+                          (1, 1000, 128, 4)):
+        k = AttentionKernel(_desc(dims=(R, C, D), low_in=True, in_type=P.BF16).kernelDescriptor(T.forward))
+        assert k.workspaceSize(row=R, column=C) == want * R * (D + 2) * 4, (R, C, D)
+    # a rectangular one-head launch where the square-root cap binds (16 row blocks, cap 15: eight whole 1024-key pieces; a cap one
+    # higher would give 16)
+    k = AttentionKernel(_desc(dims=(4096, 8192, 128), low_in=True, in_type=P.BF16).kernelDescriptor(T.forward))
+    assert k.workspaceSize(row=4096, column=8192) == 8 * 4096 * 130 * 4
+
+    def earlier_count(blocks, traversal, parallel, target):   # the linear search the closed form replaced, step for step
+        tiles = (traversal + 63) // 64
+        if blocks >= 192 or tiles < 8:
+            return 1
+        best = 1
+        while (best + 1) * (best + 1) * parallel <= 117 * traversal + parallel * (best + 1):
+            best += 1
+        s = min(target // blocks, best, tiles // 4, 64)
+        for c in range(s, 1, -1):
+            if 2 * c <= s:
+                break
+            if traversal % (256 * c) == 0:
+                s = c
+                break
+        return 1 if s < 2 else s
+
+    # the D = 128 forward kernel's pieces (256-row workgroups, one round of 256) over row / column shapes
+    k = AttentionKernel(_desc(dims=(4096, 4096, 128), low_in=True, in_type=P.BF16).kernelDescriptor(T.forward))
+    for R in (1, 7, 64, 255, 256, 300, 1000, 2048, 3000, 4096, 8192, 12288, 16384, 30000, 49000):
+        for C in (512, 1000, 2047, 2048, 3000, 4096, 6144, 8192, 10000, 12345, 16384, 65536, 99999, 1 << 20, 3 << 22):
+            s = earlier_count((R + 255) // 256, C, R, 256)
+            assert k.workspaceSize(row=R, column=C) == (s * R * 130 * 4 if s > 1 else 0), (R, C, s)
     # D > 128 (round 6): the role-split backward kernels cut the launch themselves -- 128-row / 128-key workgroups, at most 256 of them
     low = _desc(dims=(8192, 8192, 256), low_in=True, in_type=P.BF16)
     assert AttentionKernel(low.kernelDescriptor(T.backwardQuery)).workspaceSize(row=8192, column=8192) == 4 * 8192 * 256 * 4
