@@ -68,11 +68,10 @@ static void fill_dq(VariantInfo *v, const char *name) {
   v->ldsBytes = dq16_lds_bytes<D, NW>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_dq16<T, D, NW, TG>;
-  v->launchCausal = &launch_dq16_causal<T, D, NW, TG>;
-  v->causal = true;
-  v->launchSparse = &launch_dq16_sparse<T, D, NW, TG>;
-  v->launchSplit = &launch_dq16_split<T, D, NW, TG>;
+  v->dense = v->own(&launch_dq16<T, D, NW, TG>);
+  v->causal = v->own(&launch_dq16_causal<T, D, NW, TG>);
+  v->sparse = v->own(&launch_dq16_sparse<T, D, NW, TG>);
+  v->split = v->splitCausal = v->own(&launch_dq16_split<T, D, NW, TG>);   // (the causal mask: a run-time flag of the pieces)
 }
 template <typename T, int D, int NW, int PRE = 1, typename TG = T>
 static void fill_dkv(VariantInfo *v, const char *name) {
@@ -84,9 +83,8 @@ static void fill_dkv(VariantInfo *v, const char *name) {
   v->ldsBytes = dkv16_lds_bytes<D, NW>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_dkv16<T, D, NW, PRE, TG>;
-  v->launchCausal = &launch_dkv16_causal<T, D, NW, PRE, TG>;
-  v->causal = true;
+  v->dense = v->own(&launch_dkv16<T, D, NW, PRE, TG>);
+  v->causal = v->own(&launch_dkv16_causal<T, D, NW, PRE, TG>);
 }
 
 } // namespace mfa

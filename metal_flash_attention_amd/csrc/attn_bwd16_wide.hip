@@ -27,9 +27,8 @@ template <typename T, int D, typename TG = T> static void fill_dq_wide(VariantIn
   v->ldsBytes = dq16_lds_bytes<D, 4, 32>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_dq16_wide<T, D, TG, false>;
-  v->launchCausal = &launch_dq16_wide<T, D, TG, true>;
-  v->causal = true;
+  v->dense = v->own(&launch_dq16_wide<T, D, TG, false>);
+  v->causal = v->own(&launch_dq16_wide<T, D, TG, true>);
 }
 
 // precision: storage type of Q, K, V; gprecision: of dO (equal, or BF16 next to FP16)
@@ -62,9 +61,8 @@ template <typename T, int D, typename TG = T> static void fill_dkv_wide(VariantI
   v->ldsBytes = dkv16w_lds_bytes<D>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_dkv16_wide<T, D, TG, false>;
-  v->launchCausal = &launch_dkv16_wide<T, D, TG, true>;
-  v->causal = true;
+  v->dense = v->own(&launch_dkv16_wide<T, D, TG, false>);
+  v->causal = v->own(&launch_dkv16_wide<T, D, TG, true>);
 }
 
 bool dkv16_wide_variant(int precision, int gprecision, int D, VariantInfo *out) {

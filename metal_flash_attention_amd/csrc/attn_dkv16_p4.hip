@@ -23,11 +23,9 @@ static const char *launch_dkv_p4_split(const Launch &l) {
   return nullptr;
 }
 
-// `v` arrives filled by dkv16_rs_variant: block-sparse launches and causal row-parallel ones keep the role-split kernel's code objects
+// `v` arrives filled by dkv16_rs_variant: block-sparse launches and causal row-parallel ones keep the role-split kernel's routes
 template <typename T, int STREAM> static void fill_dkv_p4(VariantInfo *v, const char *name) {
-  if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
-  v->siblingParallelization = v->parallelization;   // split / block-sparse launches: the role-split kernel's workgroups
   v->parallelization = 256;   // key columns per workgroup: four waves x 64
   v->traversal = 32;
   v->headBlock = dkv4::stream_bucket(STREAM);
@@ -35,13 +33,10 @@ template <typename T, int STREAM> static void fill_dkv_p4(VariantInfo *v, const 
   v->ldsBytes = v->ldsBytes > (uint32_t)dkv4::LDS_BYTES ? v->ldsBytes : (uint32_t)dkv4::LDS_BYTES;
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_dkv_p4<T, STREAM, false>;
-  v->launchCausal = &launch_dkv_p4<T, STREAM, true>;
-  v->causal = true;
-  v->launchSplitCausal = v->launchSplit;   // (the role-split kernel's)
-  v->launchSplit = &launch_dkv_p4_split<T, STREAM>;
-  v->splitParallelization = 256;
-  v->splitTarget = 256;   // one workgroup per compute unit (512 registers per lane)
+  v->dense = v->own(&launch_dkv_p4<T, STREAM, false>);
+  v->causal = v->own(&launch_dkv_p4<T, STREAM, true>);
+  v->split = v->own(&launch_dkv_p4_split<T, STREAM>, 256);   // one workgroup per compute unit (512 registers per lane)
+  v->splitCausal.splitTarget = 256;   // (the role-split kernel's pieces, as many as this kernel's)
 }
 
 // precision: Q, K, V and dO (one 16-bit type); lprec / dprec: storage types of L and D.  The streams exist for the two

@@ -27,12 +27,10 @@ static const char *launch_dkv_p5_split(const Launch &l) {
   return nullptr;
 }
 
-// `v` arrives filled by dkv16_rs_variant*: block-sparse and CAUSAL row-parallel launches keep the 32-key role-split kernel's code objects
+// `v` arrives filled by dkv16_rs_variant*: block-sparse and CAUSAL row-parallel launches keep the 32-key role-split kernel's routes
 template <typename T, int STREAM> static void fill_dkv_p5(VariantInfo *v, const char *name) {
   constexpr int LDS = dkv5::lds_bytes(dkv5::stream_bucket(STREAM));
-  if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
-  v->siblingParallelization = v->parallelization;   // split / block-sparse launches: the 32-key role-split kernel's workgroups
   v->parallelization = dkv5::WGKEYS;   // key columns per workgroup: two wave pairs x 64
   v->traversal = 32;
   v->headBlock = dkv5::stream_bucket(STREAM);
@@ -40,14 +38,11 @@ template <typename T, int STREAM> static void fill_dkv_p5(VariantInfo *v, const 
   v->ldsBytes = v->ldsBytes > (uint32_t)LDS ? v->ldsBytes : (uint32_t)LDS;
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_dkv_p5<T, STREAM, false>;
-  v->launchCausal = &launch_dkv_p5<T, STREAM, true>;
-  v->causal = true;
+  v->dense = v->own(&launch_dkv_p5<T, STREAM, false>);
+  v->causal = v->own(&launch_dkv_p5<T, STREAM, true>);
   if constexpr (!dkv5::stream_profiles(STREAM)) {
-    v->launchSplitCausal = v->launchSplit;   // (the sibling's)
-    v->launchSplit = &launch_dkv_p5_split<T, STREAM>;
-    v->splitParallelization = dkv5::WGKEYS;
-    v->splitTarget = 256;   // one workgroup per compute unit (512 registers per lane)
+    v->split = v->own(&launch_dkv_p5_split<T, STREAM>, 256);   // one workgroup per compute unit (512 registers per lane)
+    v->splitCausal.splitTarget = 256;   // (the sibling's pieces, as many as this kernel's)
   }
 }
 

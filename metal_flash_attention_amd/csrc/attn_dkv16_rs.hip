@@ -7,14 +7,12 @@ bool dkv16_rs_variant(int precision, int gprecision, int D, int impl, VariantInf
 #ifdef MFA_DEV_VARIANTS
   if (impl >= 1 && impl <= 4 && precision == PREC_BF16 && gprecision == PREC_BF16 && D == 128) {   // timing-only ablations
     fill<__bf16, 128>(out, "ablate_dkv16rs_WRONG_RESULTS");
-    out->launchCausal = nullptr; out->causal = false;
-    out->launchSparse = nullptr;
-    out->launchSplit = nullptr;
+    out->causal = out->sparse = out->split = out->splitCausal = Route();   // (dense launches only)
     switch (impl) {
-      case 1: out->launch = &launch_rs<__bf16, 128, __bf16, false, 1>; break;
-      case 2: out->launch = &launch_rs<__bf16, 128, __bf16, false, 2>; break;
-      case 3: out->launch = &launch_rs<__bf16, 128, __bf16, false, 3>; break;
-      default: out->launch = &launch_rs<__bf16, 128, __bf16, false, 4>; break;
+      case 1: out->dense = out->own(&launch_rs<__bf16, 128, __bf16, false, 1>); break;
+      case 2: out->dense = out->own(&launch_rs<__bf16, 128, __bf16, false, 2>); break;
+      case 3: out->dense = out->own(&launch_rs<__bf16, 128, __bf16, false, 3>); break;
+      default: out->dense = out->own(&launch_rs<__bf16, 128, __bf16, false, 4>); break;
     }
     return true;
   }

@@ -47,11 +47,10 @@ static void fill(VariantInfo *v, const char *name) {
   v->ldsBytes = dkv16rs_lds_bytes<D>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_rs<T, D, TG, false>;
-  v->launchCausal = &launch_rs<T, D, TG, true>;
-  v->causal = true;
-  v->launchSparse = &launch_rs_sparse<T, D, TG>;
-  v->launchSplit = &launch_rs_split<T, D, TG>;
+  v->dense = v->own(&launch_rs<T, D, TG, false>);
+  v->causal = v->own(&launch_rs<T, D, TG, true>);
+  v->sparse = v->own(&launch_rs_sparse<T, D, TG>);
+  v->split = v->splitCausal = v->own(&launch_rs_split<T, D, TG>);   // (the causal mask: a run-time flag of the pieces)
 }
 
 } // namespace mfa

@@ -22,10 +22,9 @@ static const char *launch_dq_p4_split(const Launch &l) {
   return nullptr;
 }
 
-// `v` arrives filled by dq16_variant (eight waves x 32 rows, the same 256 rows per workgroup): block-sparse launches and
-// causal column-parallel ones keep that kernel's code objects
+// `v` arrives filled by dq16_variant (eight waves x 32 rows): block-sparse launches and causal column-parallel ones keep that
+// kernel's routes
 template <typename T, int STREAM, typename TG = T> static void fill_dq_p4(VariantInfo *v, const char *name) {
-  if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
   v->parallelization = 256;
   v->traversal = 64;
@@ -34,13 +33,10 @@ template <typename T, int STREAM, typename TG = T> static void fill_dq_p4(Varian
   v->ldsBytes = v->ldsBytes > (uint32_t)dq4::LDS_BYTES ? v->ldsBytes : (uint32_t)dq4::LDS_BYTES;
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_dq_p4<T, STREAM, false, TG>;
-  v->launchCausal = &launch_dq_p4<T, STREAM, true, TG>;
-  v->causal = true;
-  v->launchSplitCausal = v->launchSplit;   // (the eight-wave kernel's)
-  v->launchSplit = &launch_dq_p4_split<T, STREAM, TG>;
-  v->splitParallelization = 256;
-  v->splitTarget = 256;   // one workgroup per compute unit (512 registers per lane)
+  v->dense = v->own(&launch_dq_p4<T, STREAM, false, TG>);
+  v->causal = v->own(&launch_dq_p4<T, STREAM, true, TG>);
+  v->split = v->own(&launch_dq_p4_split<T, STREAM, TG>, 256);   // one workgroup per compute unit (512 registers per lane)
+  v->splitCausal.splitTarget = 256;   // (the eight-wave kernel's pieces, as many as this kernel's)
 }
 
 // impl 0: Q as stored, softmax scale in fp32 (descriptors that keep the attention matrix in FP32 registers); impl 10: Q

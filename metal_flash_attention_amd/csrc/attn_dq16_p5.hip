@@ -26,12 +26,10 @@ static const char *launch_dq_p5_split(const Launch &l) {
   return nullptr;
 }
 
-// `v` arrives filled by dq16_variant*: block-sparse and CAUSAL column-parallel launches keep the 32-row-wave kernel's code objects
+// `v` arrives filled by dq16_variant*: block-sparse and CAUSAL column-parallel launches keep the 32-row-wave kernel's routes
 template <typename T, int STREAM, typename TG = T> static void fill_dq_p5(VariantInfo *v, const char *name) {
   constexpr int LDS = dq5::lds_bytes(dq5::stream_bucket(STREAM));
-  if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
-  v->siblingParallelization = v->parallelization;
   v->parallelization = dq5::WGROWS;   // rows per workgroup: two wave pairs x 64
   v->traversal = 32;
   v->headBlock = dq5::stream_bucket(STREAM);
@@ -39,14 +37,11 @@ template <typename T, int STREAM, typename TG = T> static void fill_dq_p5(Varian
   v->ldsBytes = v->ldsBytes > (uint32_t)LDS ? v->ldsBytes : (uint32_t)LDS;
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_dq_p5<T, STREAM, false, TG>;
-  v->launchCausal = &launch_dq_p5<T, STREAM, true, TG>;
-  v->causal = true;
+  v->dense = v->own(&launch_dq_p5<T, STREAM, false, TG>);
+  v->causal = v->own(&launch_dq_p5<T, STREAM, true, TG>);
   if constexpr (!dq5::stream_profiles(STREAM)) {
-    v->launchSplitCausal = v->launchSplit;   // (the sibling's)
-    v->launchSplit = &launch_dq_p5_split<T, STREAM, TG>;
-    v->splitParallelization = dq5::WGROWS;
-    v->splitTarget = 256;   // one workgroup per compute unit (512 registers per lane)
+    v->split = v->own(&launch_dq_p5_split<T, STREAM, TG>, 256);   // one workgroup per compute unit (512 registers per lane)
+    v->splitCausal.splitTarget = 256;   // (the sibling's pieces, as many as this kernel's)
   }
 }
 

@@ -1,6 +1,6 @@
 // attn_f32.hip -- instantiations and launchers of the FP32 production kernels (attn_f32.h).  The variant's launcher takes a launch
-// when f32k::serves() says its operands qualify and hands the others to the general kernel (attn_generic_{fwd,dq,dkv}.hip); its
-// return value names the code object that ran (mfa_attention_kernel_launch_form).
+// when f32k::serves() says its operands qualify and hands the others to the dense route of the general kernel
+// (attn_generic_{fwd,dq,dkv}.hip); its return value names the code object that ran (mfa_attention_kernel_launch_form).
 #include "attn_f32.h"
 #include "launchers.h"
 
@@ -31,11 +31,7 @@ template <int DP> void start(int type, const Launch &l) {
   }
 }
 
-// the general kernel's launcher of the same head block (generic_*_variant(DP), which `out` of f32_variant arrives filled by)
-template <int TYPE, int DP> struct General { static LaunchFn launch; };
-template <int TYPE, int DP> LaunchFn General<TYPE, DP>::launch = nullptr;
-
-// the FP32 kernel when the operands qualify (grid as the general kernel's: blocks of 128, heads, batches), else the general kernel
+// the FP32 kernel when the operands qualify, else the general kernel of the head block: both in blocks of f32k::ROWS, heads, batches
 template <int TYPE, int DP> const char *launch_f32(const Launch &l) {
   bool taken = f32k::serves(TYPE, DP, l.args);
 #ifdef MFA_DEV_VARIANTS   // developer builds: MFA_F32_GENERAL=1 keeps the general kernels on these launches (A/B runs)
@@ -45,7 +41,9 @@ template <int TYPE, int DP> const char *launch_f32(const Launch &l) {
     start<DP>(TYPE, l);
     return nullptr;   // (the variant's own name: the FP32 production kernel)
   }
-  General<TYPE, DP>::launch(l);
+  VariantInfo generic;
+  (TYPE == 0 ? generic_fwd_variant : TYPE == 1 ? generic_dq_variant : generic_dkv_variant)(DP, &generic);
+  generic.dense.launch(l);
   static const char *const general[3][2] = {
       {"attn_generic_fwd_f32mfma_d64_w4_cached (general kernel: an operand's rows are not 16-byte aligned)",
        "attn_generic_fwd_f32mfma_d128_w4_cached (general kernel: an operand's rows are not 16-byte aligned)"},
@@ -60,17 +58,15 @@ template <int TYPE, int DP> void fill_f32(VariantInfo *v) {
   static const char *const names[3][2] = {{"attn_f32_fwd_d64_w4x32", "attn_f32_fwd_d128_w4x32"},
                                           {"attn_f32_dq_d64_w4x32", "attn_f32_dq_d128_w4x32"},
                                           {"attn_f32_dkv_d64_w4x32", "attn_f32_dkv_d128_w4x32"}};
-  v->siblingName = v->name;
   v->name = names[TYPE][DP == 128];
   v->ldsBytes = TYPE == 0 ? f32k::lds_bytes<DP>() : TYPE == 1 ? f32k::lds_bytes_dq<DP>() : f32k::lds_bytes_dkv<DP>();
-  General<TYPE, DP>::launch = v->launch;
-  v->launch = &launch_f32<TYPE, DP>;
+  v->dense = v->causal = v->own(&launch_f32<TYPE, DP>);   // (block-sparse launches keep the general kernel's route)
 }
 
 }  // namespace
 
 bool f32_variant(int type, int DP, VariantInfo *out) {
-  if (DP != 64 && DP != 128) return false;
+  if ((DP != 64 && DP != 128) || out->dense.parallelization != f32k::ROWS) return false;
   switch (type) {
     case 0: if (DP == 64) fill_f32<0, 64>(out); else fill_f32<0, 128>(out); break;
     case 1: if (DP == 64) fill_f32<1, 64>(out); else fill_f32<1, 128>(out); break;

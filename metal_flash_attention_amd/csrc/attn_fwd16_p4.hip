@@ -40,7 +40,6 @@ static const char *launch_p4_split(const Launch &l) {
 }
 
 template <typename T, int STREAM> static void fill_p4(VariantInfo *v, const char *name) {
-  if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
   v->parallelization = 256;
   v->traversal = 64;
@@ -49,22 +48,16 @@ template <typename T, int STREAM> static void fill_p4(VariantInfo *v, const char
   v->ldsBytes = v->ldsBytes > (uint32_t)p4::LDS_BYTES ? v->ldsBytes : (uint32_t)p4::LDS_BYTES;   // (siblings of the 8 x 32 kernel keep theirs)
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_p4<T, STREAM, false>;
-  v->launchCausal = &launch_p4<T, STREAM, true>;
-  v->causal = true;
-  v->launchSplit = &launch_p4_split<T, STREAM>;   // (block-sparse launches keep the sibling of the 8 x 32 kernel)
-  v->splitTarget = 256;   // one workgroup per compute unit
-  v->splitParallelization = 256;   // (the pieces of a column-parallel launch are THIS kernel's: attn_fwd16_p4<..., split>, not the sibling's)
+  v->dense = v->own(&launch_p4<T, STREAM, false>);
+  v->causal = v->own(&launch_p4<T, STREAM, true>);
+  v->split = v->own(&launch_p4_split<T, STREAM>, 256);   // one workgroup per compute unit (block-sparse launches keep the 8 x 32 kernel's route)
 }
 
 template <typename T, int STREAM> static void fill_p4_dev(VariantInfo *v, const char *name) {   // dense launches only
   fill_p4<T, p4::S_BF16_THR8>(v, name);
-  v->launch = &launch_p4<T, STREAM, false>;
-  if constexpr (p4::stream_profiles(STREAM)) {   // phase clocks of causal launches too (tools/p4_prof.py --causal)
-    v->launchCausal = &launch_p4<T, STREAM, true>;
-  } else {
-    v->launchCausal = nullptr; v->causal = false;
-  }
+  v->dense = v->own(&launch_p4<T, STREAM, false>);
+  if constexpr (p4::stream_profiles(STREAM)) v->causal = v->own(&launch_p4<T, STREAM, true>);   // phase clocks of causal launches too (tools/p4_prof.py --causal)
+  else v->causal = Route();
 }
 
 // Product streams: impl 0 = scale applied in fp32 (exact S; selected when the descriptor keeps the attention matrix in

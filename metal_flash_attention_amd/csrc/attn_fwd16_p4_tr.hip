@@ -34,7 +34,7 @@ template <int STREAM> static const char *stream_text() {
 template <typename T, int STREAM>
 static const char *launch_p4_tr(const Launch &l) {
   constexpr int PATTERN = p4tr::stream_pattern(STREAM);
-  // grid arrives in the 8 x 32 kernel's 256-row workgroups: the same row blocks
+  // (l.grid counts 256-row blocks, the 8 x 32 kernel's and this kernel's: fwd16_p4_tr_variant)
   if (!p4_tr_takes(l.args, PATTERN)) return launch_v3_tr<T, 128, 8, 3, 0, 4 | PATTERN>(l);
   Fwd16Grid g{l.grid.x, l.grid.y, l.grid.z};
   if (l.args.causal) {
@@ -47,14 +47,15 @@ static const char *launch_p4_tr(const Launch &l) {
 }
 
 template <typename T, int STREAM> static void attach(VariantInfo *v) {
-  v->launch = &launch_p4_tr<T, STREAM>;
+  v->dense = v->causal = v->own(&launch_p4_tr<T, STREAM>);   // (the causal mask: a run-time flag of both kernels)
   v->ldsBytes = v->ldsBytes > (uint32_t)p4::LDS_BYTES ? v->ldsBytes : (uint32_t)p4::LDS_BYTES;
 }
 
 // `out` arrives filled by fwd16_v3_tr_variant_d128 for `pattern` (bit 0 = K, bit 1 = V transposed; 0 = only Q / O: nothing to do):
 // launches the stream can take go to it, the others stay.  fold: Q pre-multiplied by the softmax scale in the 16-bit type
-// (mixed-precision descriptors)
+// (mixed-precision descriptors).  The launches the stream does not take go to the 8 x 32 kernel in the same 256-row blocks
 bool fwd16_p4_tr_variant(int precision, int pattern, bool fold, VariantInfo *out) {
+  if (out->dense.parallelization != 256) return false;
 #define MFA_P4TR_ATTACH(T, TN)                                                                        \
   switch (pattern) {                                                                                   \
     case 1: if (fold) attach<T, p4tr::S_##TN##_FOLD_TRK>(out); else attach<T, p4tr::S_##TN##_THR8_TRK>(out); return true; \

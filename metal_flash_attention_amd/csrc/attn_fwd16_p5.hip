@@ -22,11 +22,9 @@ static const char *launch_p5_split(const Launch &l) {
   return nullptr;
 }
 
-// `v` arrives filled by fwd16_v3_variant (D = 256: four waves x 32 rows): block-sparse launches keep its code objects
+// `v` arrives filled by fwd16_v3_variant (D = 256: four waves x 32 rows): block-sparse launches keep its route
 template <typename T, int STREAM> static void fill_p5(VariantInfo *v, const char *name) {
-  if (v->name && v->name[0]) v->siblingName = v->name;   // (arrives filled by the kernel whose split / sparse launches it keeps)
   v->name = name;
-  v->siblingParallelization = v->parallelization;
   v->parallelization = 256;
   v->traversal = 32;
   v->headBlock = p5::stream_bucket(STREAM);
@@ -34,12 +32,9 @@ template <typename T, int STREAM> static void fill_p5(VariantInfo *v, const char
   v->ldsBytes = v->ldsBytes > (uint32_t)p5::LDS_BYTES ? v->ldsBytes : (uint32_t)p5::LDS_BYTES;
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_p5<T, STREAM, false>;
-  v->launchCausal = &launch_p5<T, STREAM, true>;
-  v->causal = true;
-  v->launchSplit = &launch_p5_split<T, STREAM>;
-  v->splitParallelization = 256;
-  v->splitTarget = 256;   // one workgroup per compute unit
+  v->dense = v->own(&launch_p5<T, STREAM, false>);
+  v->causal = v->own(&launch_p5<T, STREAM, true>);
+  v->split = v->own(&launch_p5_split<T, STREAM>, 256);   // one workgroup per compute unit
 }
 
 // impl 0 = scale applied in fp32; impl 10 = FOLD (see attn_fwd16_p4.hip); 1000 + stream index: developer streams

@@ -5,14 +5,11 @@
 // profiles/r04_candidate/time_p5_tr_32heads.txt.
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include "attn_fwd16_p5_tr.h"
 #include "launchers.h"
 
 namespace mfa {
-
-// the launcher of the code object `out` arrived with (fwd16_v3_tr_variant_dNN of the same pattern): one per (type, stream)
-template <typename T, int STREAM> struct P5TrFallback { static LaunchFn launch; };
-template <typename T, int STREAM> LaunchFn P5TrFallback<T, STREAM>::launch = nullptr;
 
 // what the step walk of attn_fwd16_p5_tr needs (its header): K / V transposed as the stream's pattern says (bit 0 = K, bit 1 = V),
 // no per-batch lengths, no block mask, whole 32-key steps, 16-byte aligned rows of K and V in either orientation (and of Q when
@@ -47,8 +44,14 @@ template <int STREAM> static const char *stream_text() {
 
 template <typename T, int STREAM>
 static const char *launch_p5_tr(const Launch &l) {
-  if (!p5_tr_takes(l.args, p5tr::stream_pattern(STREAM))) return P5TrFallback<T, STREAM>::launch(l);
-  // grid arrives in the 8 x 32 kernel's row blocks (VariantInfo.parallelization); this kernel's are 256 rows
+  constexpr int D = p5tr::stream_bucket(STREAM), PATTERN = p5tr::stream_pattern(STREAM);
+  if (!p5_tr_takes(l.args, PATTERN)) {   // the dense route of the transposed code object `out` arrived with (attn_fwd16_v3_tr_dNNN.hip)
+    VariantInfo tr;
+    (D == 160 ? fwd16_v3_tr_variant_d160 : D == 192 ? fwd16_v3_tr_variant_d192 : fwd16_v3_tr_variant_d256)(
+        std::is_same<T, __bf16>::value ? PREC_BF16 : PREC_FP16, D, PATTERN, &tr);
+    return tr.dense.launch(l);
+  }
+  // l.grid counts the transposed code object's 128-row blocks; this kernel's take 256 rows
   const uint32_t blocks = ((uint32_t)l.args.R + 255) / 256;
   Fwd16Grid g{blocks, l.grid.y, l.grid.z};
   if (l.args.causal) {
@@ -61,8 +64,7 @@ static const char *launch_p5_tr(const Launch &l) {
 }
 
 template <typename T, int STREAM> static void attach(VariantInfo *v) {
-  P5TrFallback<T, STREAM>::launch = v->launch;
-  v->launch = &launch_p5_tr<T, STREAM>;
+  v->dense = v->causal = v->own(&launch_p5_tr<T, STREAM>);   // (the causal mask: a run-time flag of both kernels)
   v->ldsBytes = v->ldsBytes > (uint32_t)p5::LDS_BYTES ? v->ldsBytes : (uint32_t)p5::LDS_BYTES;
 }
 
@@ -70,7 +72,7 @@ template <typename T, int STREAM> static void attach(VariantInfo *v) {
 // nothing to do): launches the stream can take go to it, the others stay.  fold: Q pre-multiplied by the softmax scale in the 16-bit
 // type (mixed-precision descriptors)
 bool fwd16_p5_tr_variant(int precision, int bucket, int pattern, bool fold, VariantInfo *out) {
-  if (!out->launch || out->launchCausal || out->launchSplit) return false;   // (the transposed code objects take the causal flag at run time and are never split)
+  if (!out->transposedInPlace) return false;
 #define MFA_P5TR_ATTACH1(T, TN, B, SFX) { if (fold) attach<T, p5tr::S_D##B##_##TN##_FOLD_##SFX>(out); else attach<T, p5tr::S_D##B##_##TN##_THR8_##SFX>(out); return true; }
 #define MFA_P5TR_ATTACH(T, TN, SFX)                \
   switch (bucket) {                                \

@@ -131,27 +131,27 @@ template <int PREC, bool FOLD> static const char *launch_p6_or_v3_split(const La
                            : "pieces by the eight-wave kernel attn_fwd16v3_f16_d64_w8x32_thr8 (not a split attn_fwd16_p6 serves)";
 }
 
-// `out` arrives filled by fwd16_v3_variant(precision, 64, 0): its causal, block-sparse and column-parallel launches (and the dense
-// launches this kernel does not serve: transposed operands, other storage types of L) stay with that kernel, which becomes the sibling
+template <int PREC, bool FOLD> static void attach(VariantInfo *v) {
+  v->dense = v->own(&launch_p6_or_v3<PREC, FOLD, false>);
+  v->causal = v->own(&launch_p6_or_v3<PREC, FOLD, true>);
+  v->split = v->own(&launch_p6_or_v3_split<PREC, FOLD>, 256);   // one workgroup per compute unit
+}
+
+// `out` arrives filled by fwd16_v3_variant(precision, 64, 0): its block-sparse launches stay with that kernel, and so do the dense,
+// causal and column-parallel launches this kernel does not serve (transposed operands, other storage types of L) -- in the same
+// 256-row blocks, so that a launch handed over keeps its grid
 bool fwd16_p6_variant(int precision, bool fold, VariantInfo *out) {
   if (precision != PREC_BF16 && precision != PREC_FP16) return false;
-  if (out->name && out->name[0]) out->siblingName = out->name;
+  if (out->dense.parallelization != 256 || out->split.parallelization != 256) return false;
   out->name = precision == PREC_BF16 ? (fold ? "attn_fwd16p6_bf16_d64_w4x64_thr8_fold" : "attn_fwd16p6_bf16_d64_w4x64_thr8")
                                      : (fold ? "attn_fwd16p6_f16_d64_w4x64_thr8_fold" : "attn_fwd16p6_f16_d64_w4x64_thr8");
-  out->siblingParallelization = out->parallelization;
   out->parallelization = 256;
   out->traversal = 64;
   out->headBlock = 64;
   out->threads = 256;
   out->ldsBytes = out->ldsBytes > (uint32_t)p6::LDS_BYTES ? out->ldsBytes : (uint32_t)p6::LDS_BYTES;
-  out->splitTarget = 256;   // one workgroup per compute unit
-  if (precision == PREC_BF16) {
-    if (fold) { out->launch = &launch_p6_or_v3<PREC_BF16, true, false>; out->launchCausal = &launch_p6_or_v3<PREC_BF16, true, true>; out->launchSplit = &launch_p6_or_v3_split<PREC_BF16, true>; }
-    else { out->launch = &launch_p6_or_v3<PREC_BF16, false, false>; out->launchCausal = &launch_p6_or_v3<PREC_BF16, false, true>; out->launchSplit = &launch_p6_or_v3_split<PREC_BF16, false>; }
-  } else {
-    if (fold) { out->launch = &launch_p6_or_v3<PREC_FP16, true, false>; out->launchCausal = &launch_p6_or_v3<PREC_FP16, true, true>; out->launchSplit = &launch_p6_or_v3_split<PREC_FP16, true>; }
-    else { out->launch = &launch_p6_or_v3<PREC_FP16, false, false>; out->launchCausal = &launch_p6_or_v3<PREC_FP16, false, true>; out->launchSplit = &launch_p6_or_v3_split<PREC_FP16, false>; }
-  }
+  if (precision == PREC_BF16) fold ? attach<PREC_BF16, true>(out) : attach<PREC_BF16, false>(out);
+  else fold ? attach<PREC_FP16, true>(out) : attach<PREC_FP16, false>(out);
   return true;
 }
 

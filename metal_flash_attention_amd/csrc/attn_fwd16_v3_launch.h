@@ -40,7 +40,7 @@ static void fill(VariantInfo *v, const char *name) {
   v->ldsBytes = fwd16v3_lds_bytes<D, NW, RB, RING, VD>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_v3<T, D, NW, RB, THR, PRE, ABL, RING, VD>;
+  v->dense = v->own(&launch_v3<T, D, NW, RB, THR, PRE, ABL, RING, VD>);
 }
 
 template <typename T, int D, int NW, int RB, int THR, int PRE, int RING, int VD>
@@ -68,10 +68,9 @@ static const char *launch_v3_sparse(const Launch &l) {
 template <typename T, int D, int NW, int RB, int THR, int PRE, int RING = 3, int VD = 0, int PRES = PRE, int VDS = VD>
 static void fill_with_split(VariantInfo *v, const char *name) {
   fill<T, D, NW, RB, THR, PRE, 0, RING, VD>(v, name);
-  v->launchSparse = &launch_v3_sparse<T, D, NW, RB, THR, PRES, RING, VDS>;
-  v->launchSplit = &launch_v3_split<T, D, NW, RB, THR, PRE, 0, RING, VD>;
-  v->launchCausal = &launch_v3_causal<T, D, NW, RB, THR, PRE, RING, VD>;
-  v->causal = true;
+  v->sparse = v->own(&launch_v3_sparse<T, D, NW, RB, THR, PRES, RING, VDS>);
+  v->split = v->own(&launch_v3_split<T, D, NW, RB, THR, PRE, 0, RING, VD>);
+  v->causal = v->own(&launch_v3_causal<T, D, NW, RB, THR, PRE, RING, VD>);
 }
 
 // transposed operands read in place (TR of attn_fwd16_v3.h): one code object per pattern of (K, V); Q / O and the causal mask
@@ -96,9 +95,8 @@ static void fill_tr(VariantInfo *v, const char *name) {
   v->ldsBytes = fwd16v3_lds_bytes<D, NW, 1, RING, VD>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->causal = true;
   v->transposedInPlace = true;
-  v->launch = &launch_v3_tr<T, D, NW, RING, VD, TR>;
+  v->dense = v->causal = v->own(&launch_v3_tr<T, D, NW, RING, VD, TR>);   // (the causal mask: a run-time flag)
 }
 
 // pattern: bit 0 = K transposed, bit 1 = V transposed (Q / O: any)

@@ -20,9 +20,8 @@ template <typename T, int DP> static void fill_wide(VariantInfo *v, const char *
   v->ldsBytes = wide::lds_bytes<DP>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->causal = true;
-  v->launch = &launch_wide<T, DP, false>;
-  v->launchCausal = &launch_wide<T, DP, true>;
+  v->dense = v->own(&launch_wide<T, DP, false>);
+  v->causal = v->own(&launch_wide<T, DP, true>);
 }
 
 // head blocks 320 and 384: four waves x 32 rows, 32-key steps (attn_fwd16_wide.h); no column-parallel / block-sparse siblings (such

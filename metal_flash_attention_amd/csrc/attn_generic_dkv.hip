@@ -29,9 +29,8 @@ static void fill(VariantInfo *v, const char *name) {
   v->ldsBytes = generic_dkv_lds_floats<DP, NW, CACHE, X>() * sizeof(float);
   v->cacheLeft = CACHE;
   v->cacheSecond = CACHE;
-  v->causal = true;
-  v->launchSparse = &launch_dkv_masked<DP, NW, CACHE, X>;   // block mask: own code objects
-  v->launch = &launch_dkv<DP, NW, CACHE, X>;
+  v->sparse = v->own(&launch_dkv_masked<DP, NW, CACHE, X>);       // block mask: own code objects
+  v->dense = v->causal = v->own(&launch_dkv<DP, NW, CACHE, X>);   // (the causal mask: a run-time flag)
 }
 
 bool generic_dkv_variant(int DP, VariantInfo *out) {

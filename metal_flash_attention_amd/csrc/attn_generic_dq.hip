@@ -29,9 +29,8 @@ static void fill(VariantInfo *v, const char *name) {
   v->ldsBytes = generic_dq_lds_floats<DP, NW, CACHE, X>() * sizeof(float);
   v->cacheLeft = CACHE || X;
   v->cacheSecond = CACHE;
-  v->causal = true;
-  v->launchSparse = &launch_dq_masked<DP, NW, CACHE, X>;   // block mask: own code objects
-  v->launch = &launch_dq<DP, NW, CACHE, X>;
+  v->sparse = v->own(&launch_dq_masked<DP, NW, CACHE, X>);       // block mask: own code objects
+  v->dense = v->causal = v->own(&launch_dq<DP, NW, CACHE, X>);   // (the causal mask: a run-time flag)
 }
 
 bool generic_dq_variant(int DP, VariantInfo *out) {

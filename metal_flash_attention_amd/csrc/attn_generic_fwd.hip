@@ -29,9 +29,8 @@ static void fill(VariantInfo *v, const char *name) {
   v->ldsBytes = generic_fwd_lds_floats<DP, NW, CACHE>() * sizeof(float);
   v->cacheLeft = CACHE;
   v->cacheSecond = CACHE;
-  v->causal = true;
-  v->launchSparse = &launch_fwd_masked<DP, NW, CACHE>;   // block mask: own code objects
-  v->launch = &launch_fwd<DP, NW, CACHE>;
+  v->sparse = v->own(&launch_fwd_masked<DP, NW, CACHE>);       // block mask: own code objects
+  v->dense = v->causal = v->own(&launch_fwd<DP, NW, CACHE>);   // (the causal mask: a run-time flag)
 }
 
 bool generic_fwd_variant(int DP, VariantInfo *out) {

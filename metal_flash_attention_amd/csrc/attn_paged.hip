@@ -22,9 +22,8 @@ template <void (*KERNEL)(const KernelArgs, const paged::Grid)> static void fill_
   v->cacheLeft = false;             // nothing is cached: every operand block is re-staged per traversal step
   v->cacheSecond = false;
   v->pagedAccumulators = true;
-  v->causal = true;                 // causal mask, per-batch lengths and block masks are handled by the one code object
-  v->sparse = true;
-  v->launch = &launch_paged<KERNEL>;
+  // causal mask, per-batch lengths and block masks are handled by the one code object
+  v->dense = v->causal = v->sparse = v->own(&launch_paged<KERNEL>);
 }
 
 bool paged_variant(int type, VariantInfo *out) {

@@ -23,7 +23,7 @@ static void fill(VariantInfo *v, const char *name) {
   v->ldsBytes = fwd16_lds_bytes<D>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_fwd16<T, D, NW, RB>;
+  v->dense = v->own(&launch_fwd16<T, D, NW, RB>);
 }
 
 // precision: PREC_FP16 or PREC_BF16; D: padded head dimension bucket

@@ -22,7 +22,7 @@ static void fill(VariantInfo *v, const char *name) {
   v->ldsBytes = fwd16v2_lds_bytes<D, NW, RB>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_v2<T, D, NW, RB, THR, MSUM>;
+  v->dense = v->own(&launch_v2<T, D, NW, RB, THR, MSUM>);
 }
 
 // impl: 0 = default (8 waves x 32 rows, deferred rescale THR=8, row sum on the matrix pipe),

@@ -38,11 +38,10 @@ static void fill(VariantInfo *v, const char *name) {
   v->ldsBytes = fwd16v2_lds_bytes<D, 8, 1, RING>();
   v->cacheLeft = true;
   v->cacheSecond = true;
-  v->launch = &launch_v4<T, D, THR, OPT, RING>;
+  v->dense = v->own(&launch_v4<T, D, THR, OPT, RING>);
   if constexpr (FULL) {
-    v->launchSplit = &launch_v4_split<T, D, THR, OPT, RING>;
-    v->launchCausal = &launch_v4_causal<T, D, THR, OPT, RING>;
-    v->causal = true;
+    v->split = v->own(&launch_v4_split<T, D, THR, OPT, RING>);
+    v->causal = v->own(&launch_v4_causal<T, D, THR, OPT, RING>);
   }
 }
 

@@ -19,9 +19,10 @@ hipError_t launch_kernel(void (*kernel)(Params...), dim3 grid, dim3 block, uint3
 }
 
 // One launch as an entry point of a variant sees it.  The entry point decides which code object serves the launch, starts it when
-// `run` is set, and returns the launch form's text for that choice (mfa_attention_kernel_launch_form): nullptr = the variant's own
-// code object (VariantInfo::name); for launchSplit / launchSplitCausal, the text of the pieces (nullptr: the sibling's).  The same
-// entry point answers mfa_attention_kernel_launch / _time (run) and _launch_form (not run), so what runs is what the form names.
+// `run` is set, and returns the launch form's text for that choice (mfa_attention_kernel_launch_form): nullptr = the code object of
+// the variant that owns the route (Route::owner).  The same entry point answers mfa_attention_kernel_launch / _time (run) and
+// _launch_form (not run), so what runs is what the form names.  `grid` counts the route's workgroups (Route::parallelization); an
+// entry point that starts a kernel of another workgroup size derives that kernel's block count from `args`.
 struct Launch {
   const KernelArgs &args;
   dim3 grid;
@@ -40,16 +41,21 @@ typedef const char *(*LaunchFn)(const Launch &l);
 // compute units of the current device (mfa_kernel.hip; cached per device)
 hipError_t compute_units(int *cus);
 
+// How a variant serves one kind of launch: the entry point, the rows (fwd, dQ) or columns (dK/dV) per workgroup of the kernel it
+// starts, and the variant the route belongs to.  A hand-placed variant laid over a compiler-scheduled one arrives filled by it and
+// overwrites only the routes it serves; the others keep their owner, who the launch form then names.  An empty route: the variant
+// does not serve that kind of launch (the general kernel does; split routes: the launch is not split).
+struct Route {
+  LaunchFn launch = nullptr;
+  uint16_t parallelization = 0;
+  uint16_t splitTarget = 0;     // split routes: workgroups the pieces aim at (0: 512 = two per compute unit)
+  const char *owner = nullptr;
+  explicit operator bool() const { return launch != nullptr; }
+};
+
 struct VariantInfo {
   const char *name = "";
-  // the variant whose launchSplit / launchSplitCausal / launchSparse this one inherited (a hand-placed stream laid over the 8 x 32 /
-  // role-split kernel of the same block dimensions): named in the launch form of such launches; nullptr = they are its own
-  const char *siblingName = nullptr;
   uint16_t parallelization = 0; // rows (fwd, dQ) or columns (dK/dV) per workgroup
-  uint16_t siblingParallelization = 0;   // the same for launchSparse / launchSplit when they belong to another kernel (0: equal)
-  uint16_t splitTarget = 0;     // workgroups a traversal-parallel launch aims at (0: 512 = two per compute unit)
-  uint16_t splitParallelization = 0;   // rows / columns per workgroup of launchSplit when it is the variant's own kernel again and
-                                       // only launchSplitCausal / launchSparse belong to the sibling (0: as the sibling)
   uint16_t traversal = 0;       // columns (fwd, dQ) or rows (dK/dV) per main-loop step
   uint16_t headBlock = 0;       // padded head dimension the code object is unrolled for
   uint32_t threads = 0;         // work-items per workgroup
@@ -57,21 +63,18 @@ struct VariantInfo {
   bool cacheLeft = false;       // left-hand operands cached in VGPRs (Q / Q,dO / K,V)
   bool cacheSecond = false;     // the second of them alone (dO / V); fill code sets it = cacheLeft unless a variant splits the pair
   bool pagedAccumulators = false;   // accumulators paged through the output buffers (any-D kernels, attn_paged.h); else in registers
-  bool causal = false;          // the code object implements the causal mask itself (general kernels: always)
   bool transposedInPlace = false;   // reads / writes transposed operands where they lie, whatever their alignment (attn_fwd16_v3.h, TR)
-  LaunchFn launch = nullptr;
-  // forward only: column-parallel launch (key range cut into `splits` pieces, partial results in the
-  // caller's workspace, then the combine kernel); nullptr if the variant has none
-  LaunchFn launchSplit = nullptr;
-  // causal traversal-parallel launches, when they belong to another kernel than launchSplit (nullptr: launchSplit takes both)
-  LaunchFn launchSplitCausal = nullptr;
-  // separate code object implementing the causal mask (the unmasked loop bodies stay branch-free);
-  // nullptr when `launch` handles the flag itself (general kernels) or the variant has no mask
-  LaunchFn launchCausal = nullptr;
-  // code objects that honour KernelArgs.mask (block-sparse extension; the launcher picks the causal or the
-  // unmasked one from args.causal); nullptr = the variant has none and the general kernels serve the launch
-  LaunchFn launchSparse = nullptr;
-  bool sparse = false;   // `launch` itself honours the mask (general kernels)
+  // one route per kind of launch.  A code object that takes the causal flag or the block mask itself serves those routes with its
+  // dense entry point.  Forward split entry points take no causal flag: forward splitCausal stays empty
+  Route dense, causal, sparse, split, splitCausal;
+  // a route of this variant's own kernel (name and parallelization as set)
+  Route own(LaunchFn f, uint16_t splitTarget = 0) const { return {f, parallelization, splitTarget, name}; }
+  // the route of a launch: pieces of a column-parallel launch, a block mask, the causal mask or none
+  const Route &route(bool pieces, bool masked, bool isCausal) const {
+    if (pieces) return isCausal ? splitCausal : split;
+    if (masked) return sparse;
+    return isCausal ? causal : dense;
+  }
 };
 
 // any head dimension (D > 384): D-blocked products, accumulators paged through the FP32 output buffers (attn_paged.h); type = kernel type

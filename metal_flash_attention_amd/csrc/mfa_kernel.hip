@@ -168,6 +168,10 @@ mfa_status mfa_attention_kernel_create(const mfa_attention_kernel_descriptor *kd
   const bool same16 = pq != MFA_FP32 && pq == kdesc->memoryPrecisions[MFA_K] && pq == kdesc->memoryPrecisions[MFA_V];
   auto f32_or_inputs = [&](int op) { return kdesc->memoryPrecisions[op] == MFA_FP32 || kdesc->memoryPrecisions[op] == pq; };
   auto add = [&](bool ok, const VariantInfo &v) { if (ok) candidates.push_back(v); };
+  // a hand-placed variant laid over `base`, the compiler-scheduled kernel of its block dimensions: it arrives filled by base and
+  // overwrites the routes it serves
+  auto add_over = [&](const VariantInfo &base, auto fill) { VariantInfo c = base; add(fill(&c), c); };
+  const bool lowP = kdesc->registerPrecisions[MFA_P] > MFA_FP32;   // the attention matrix in 16-bit registers
   VariantInfo v;
   bool relayout = false;
   if (type == MFA_FORWARD) {
@@ -203,31 +207,27 @@ mfa_status mfa_attention_kernel_create(const mfa_attention_kernel_descriptor *kd
         default: have3 = fwd16_v3_variant(pq, b16, 0, &v3); break;
       }
       if (have3 && b16 == 128) {
-        // four waves x 64 rows, hand-placed stream (attn_fwd16_p4.h); split / block-sparse launches keep the siblings of
+        // four waves x 64 rows, hand-placed stream (attn_fwd16_p4.h); block-sparse launches keep the route of
         // the 8 x 32 kernel.  A descriptor that holds the attention matrix in 16-bit registers (the reference's
         // lowPrecisionIntermediates: P, and for FP16 also S, +Precisions.swift:149-215) selects the stream that
         // pre-multiplies Q by the softmax scale in the 16-bit type; otherwise the scale is applied in fp32 per score
-        const bool lowS = kdesc->registerPrecisions[MFA_P] > MFA_FP32;
-        v = v3;
-        add(fwd16_p4_variant(pq, 128, lowS ? 10 : 0, &v), v);
+        add_over(v3, [&](VariantInfo *c) { return fwd16_p4_variant(pq, 128, lowP ? 10 : 0, c); });
       }
       // (D <= 32: the same kernel on zero-padded chunks, selected by a | 32 | 256 | 64 | 64 | row -- the FOLD streams from D = 16 on: with
       // fewer terms per score the rounding of Q' = Q log2(e)/sqrt(D) to BF16 no longer averages out and L leaves the reference's 7e-3)
       if (have3 && (b16 == 64 || (b16 == 32 && (D >= 16 || kdesc->registerPrecisions[MFA_P] <= MFA_FP32)))) {
         // D <= 64 (buckets 32 and 64 of the eight-wave kernel): four waves x 64 rows, persistent, 64-key steps (attn_fwd16_p6.h, round 5);
         // mixed-precision descriptors get the streams with the row sums in the matrix pipe.  | 64 | 256 | 32 | 64 | selects the eight
-        // 32-row waves of attn_fwd16_v3.h, which also keep this kernel's causal / block-sparse / column-parallel launches
-        v = v3;
+        // 32-row waves of attn_fwd16_v3.h, which also keep this kernel's block-sparse launches
         // (D <= 32 on this kernel: the launches it does not serve -- per-batch lengths, an L of the other storage type, pieces that
         // are not whole multiples of four tiles -- go to the D = 64 eight-wave kernels, so the base must be THEIR variant: 256-row
         // blocks for split grids and choose_splits)
-        if (b16 == 32 && !fwd16_v3_variant(pq, 64, 0, &v)) v = v3;
-        add(fwd16_p6_variant(pq, kdesc->registerPrecisions[MFA_P] > MFA_FP32, &v), v);
+        VariantInfo base = v3;
+        if (b16 == 32) fwd16_v3_variant(pq, 64, 0, &base);
+        add_over(base, [&](VariantInfo *c) { return fwd16_p6_variant(pq, lowP, c); });
       }
       if (have3 && (b16 == 160 || b16 == 192 || b16 == 256)) {   // four waves x 64 rows, 32-key steps (attn_fwd16_p5.h)
-        const bool lowS = kdesc->registerPrecisions[MFA_P] > MFA_FP32;
-        v = v3;
-        add(fwd16_p5_variant(pq, b16, lowS ? 10 : 0, &v), v);
+        add_over(v3, [&](VariantInfo *c) { return fwd16_p5_variant(pq, b16, lowP ? 10 : 0, c); });
       }
       add(have3, v3);
     } else if (same16 && f32_or_inputs(MFA_O) && (D % 8) == 0 && D > 256 && D <= 384) {
@@ -249,10 +249,7 @@ mfa_status mfa_attention_kernel_create(const mfa_attention_kernel_descriptor *kd
         // buckets 160, 192, 256: two wave pairs x 64 rows, hand-placed role-split stream (attn_dq16_p5.h), in front of the four
         // 32-row waves of the same bucket (| D | 128 | 64 | D | selects those)
         auto add_dq5 = [&](bool w4, int b) {
-          if (w4) {
-            VariantInfo v5 = v;
-            add(dq16_p5_variant(pq, pg, b, kdesc->registerPrecisions[MFA_P] > MFA_FP32 ? 10 : 0, &v5), v5);
-          }
+          if (w4) add_over(v, [&](VariantInfo *c) { return dq16_p5_variant(pq, pg, b, lowP ? 10 : 0, c); });
           add(w4, v);
         };
         switch (b16) {
@@ -261,10 +258,8 @@ mfa_status mfa_attention_kernel_create(const mfa_attention_kernel_descriptor *kd
           case 256: add_dq5(dq16_variant(pq, pg, 256, &v), 256); break;
           default: {
             const bool w8 = dq16_variant(pq, pg, b16, &v);
-            if (w8 && (b16 == 128 || b16 == 64)) {   // four waves x 64 rows, hand-placed stream (attn_dq16_p4.h): the same block
-              VariantInfo v4 = v;                    // dimensions as the 8 x 32 kernel, which keeps the launches this one lacks
-              add(dq16_p4_variant(pq, pg, b16, kdesc->registerPrecisions[MFA_P] > MFA_FP32 ? 10 : 0, &v4), v4);
-            }
+            if (w8 && (b16 == 128 || b16 == 64))   // four waves x 64 rows, hand-placed stream (attn_dq16_p4.h)
+              add_over(v, [&](VariantInfo *c) { return dq16_p4_variant(pq, pg, b16, lowP ? 10 : 0, c); });
             add(w8, v);
             break;
           }
@@ -274,20 +269,16 @@ mfa_status mfa_attention_kernel_create(const mfa_attention_kernel_descriptor *kd
           kdesc->memoryPrecisions[MFA_dK] == kdesc->memoryPrecisions[MFA_dV]) {
         // buckets 160, 192, 256: two wave pairs x 64 keys, hand-placed role-split stream (attn_dkv16_p5.h), in front of the
         // 32-key pairs of the same bucket (| D | 64 | 32 | D | selects those)
+        const int lprec = kdesc->memoryPrecisions[MFA_L], dprec = kdesc->memoryPrecisions[MFA_D];   // (fixed per stream)
         auto add_p5 = [&](bool rs, int b) {
-          if (rs) {
-            VariantInfo v5 = v;
-            add(dkv16_p5_variant(pq, pg, kdesc->memoryPrecisions[MFA_L], kdesc->memoryPrecisions[MFA_D], b, &v5), v5);
-          }
+          if (rs) add_over(v, [&](VariantInfo *c) { return dkv16_p5_variant(pq, pg, lprec, dprec, b, c); });
           add(rs, v);
         };
         auto add_bucket = [&](int b) {   // buckets 64, 128, 256
           const bool rs = dkv16_rs_variant(pq, pg, b, 0, &v);
           if (b == 256) { add_p5(rs, 256); return; }
-          if (rs && (b == 128 || b == 64)) {   // four waves x 64 keys, hand-placed stream (attn_dkv16_p4.h)
-            VariantInfo v4 = v;
-            add(dkv16_p4_variant(pq, pg, kdesc->memoryPrecisions[MFA_L], kdesc->memoryPrecisions[MFA_D], b, 0, &v4), v4);
-          }
+          if (rs && (b == 128 || b == 64))   // four waves x 64 keys, hand-placed stream (attn_dkv16_p4.h)
+            add_over(v, [&](VariantInfo *c) { return dkv16_p4_variant(pq, pg, lprec, dprec, b, 0, c); });
           add(rs, v);
         };
         switch (b16) {   // role-split wave pairs (attn_dkv16_rs.h)
@@ -298,7 +289,9 @@ mfa_status mfa_attention_kernel_create(const mfa_attention_kernel_descriptor *kd
           case 192: add_p5(dkv16_rs_variant_d192(pq, pg, &v), 192); break;
           default: add_bucket(b16); break;
         }
-        add(dkv16_variant(pq, pg, b16 == 96 ? 128 : b16, &v), v);   // one wave per key block (attn_bwd16.h; D = 64, 128 only)
+        // one wave per key block (attn_bwd16.h; D = 64, 128 only): laid over the role-split kernel, whose block-sparse and split
+        // routes it keeps
+        add(dkv16_variant(pq, pg, b16 == 96 ? 128 : b16, &v), v);
       }
     } else if (same16 && pg != MFA_FP32 && (D % 8) == 0 && D > 256 && D <= 384) {
       // 256 < D <= 384 (round 6): the backward kernels of the head blocks 320 / 384 on the 16-bit matrix cores (attn_bwd16_wide.hip;
@@ -492,6 +485,7 @@ struct LaunchPlan {
   KernelArgs args;
   dim3 grid;
   const VariantInfo *variant;
+  const Route *route;           // of `variant`, for this launch
   bool useFallback;
   uint32_t splits = 1;          // > 1: column-parallel forward through the caller's workspace
   float *wsO = nullptr, *wsML = nullptr;
@@ -642,17 +636,14 @@ static uint32_t choose_splits(uint64_t blocks, uint32_t traversal, uint32_t para
   return s < 2 ? 1 : (uint32_t)s;
 }
 
-// column-parallel geometry of a launch of `v` (workspace query and launch alike): workgroups along the parallelization dimension and
-// pieces of the traversal (1: no split).  The pieces are the variant's own kernel's (splitParallelization) or its sibling's
+// column-parallel geometry of a launch on split route `r` (workspace query and launch alike): workgroups along the parallelization
+// dimension and pieces of the traversal (1: no split)
 struct SplitGeometry { uint32_t blocks, splits; };
-static SplitGeometry split_geometry(const VariantInfo &v, int type, uint32_t row, uint32_t column, bool causal, uint32_t heads, uint32_t batches) {
+static SplitGeometry split_geometry(const Route &r, int type, uint32_t row, uint32_t column, uint32_t heads, uint32_t batches) {
   const bool kv = type == MFA_BACKWARD_KEY_VALUE;
   const uint32_t par = kv ? column : row;   // (SquareAttentionTest.swift:355-367)
-  // (the hand-placed backward kernels split dense launches themselves; causal ones stay with their siblings)
-  const bool ownSplit = v.splitParallelization && !(causal && v.launchSplitCausal);
-  const uint32_t wg = ownSplit ? v.splitParallelization : v.siblingParallelization ? v.siblingParallelization : v.parallelization;
-  const uint32_t blocks = (par + wg - 1) / wg;
-  return {blocks, choose_splits((uint64_t)blocks * heads * batches, kv ? row : column, par, v.splitTarget ? v.splitTarget : 512)};
+  const uint32_t blocks = (par + r.parallelization - 1) / r.parallelization;
+  return {blocks, choose_splits((uint64_t)blocks * heads * batches, kv ? row : column, par, r.splitTarget ? r.splitTarget : 512)};
 }
 
 // bytes of workspace a launch cut into `s` pieces needs
@@ -743,7 +734,7 @@ static mfa_status prepare_launch(const mfa_attention_kernel *kernel, void *const
     }
   }
   const bool otherReasons = !meets_fast_requirements(kernel, *args) || (args->causal && !kernel->variant.causal) ||
-                            (args->mask && !kernel->variant.launchSparse && !kernel->variant.sparse) ||
+                            (args->mask && !kernel->variant.sparse) ||
                             // attn_dkv16_rs lists at most 4096 active 256-row blocks in LDS
                             (args->mask && type == MFA_BACKWARD_KEY_VALUE && p->row > 4096u * 256u);
   plan->useFallback = kernel->hasFallback && (relayoutMissing || otherReasons);
@@ -774,29 +765,27 @@ static mfa_status prepare_launch(const mfa_attention_kernel *kernel, void *const
     plan->nRelayouts = 0;
   }
   plan->variant = plan->useFallback ? &kernel->fallback : &kernel->variant;
+  plan->route = &plan->variant->route(false, args->mask != nullptr, args->causal != 0);
   // parallelization dimension: rows for forward / backwardQuery, columns for backwardKeyValue
   // (SquareAttentionTest.swift:355-367)
   const uint32_t par = (type == MFA_BACKWARD_KEY_VALUE) ? p->column : p->row;
-  // block-sparse launches may belong to a sibling kernel with its own workgroup shape (attn_dkv16_p4 keeps those of attn_dkv16_rs)
-  const uint32_t wgPar = args->mask && plan->variant->launchSparse && !plan->useFallback && plan->variant->siblingParallelization
-                             ? plan->variant->siblingParallelization : plan->variant->parallelization;
-  const uint32_t blocks = (par + wgPar - 1) / wgPar;
+  const uint32_t blocks = (par + plan->route->parallelization - 1) / plan->route->parallelization;
   if ((uint64_t)blocks * heads * batches > 0x7FFFFFFFull) return fail(MFA_ERR_INVALID_ARGUMENT, "grid too large");
   plan->grid = dim3(blocks, heads, batches);
   plan->splits = 1;
   // Traversal-parallel launches through the caller's workspace, for grids that cannot fill the GPU: forward cuts
   // the key range (partial (O, m, l), online-softmax merge), backwardQuery the key range and backwardKeyValue
   // the row range (partial dQ / dK, dV in fp32 slabs, summed by attn_bwd_combine).
-  const bool splittable = !plan->useFallback && !kernel->relayout && plan->variant->launchSplit && !args->rowLen && !args->colLen && !args->mask &&
-                          (type != MFA_FORWARD || !args->causal);
-  if (splittable) {
-    const SplitGeometry sg = split_geometry(*plan->variant, type, p->row, p->column, args->causal != 0, heads, batches);
+  const Route &split = plan->variant->route(true, false, args->causal != 0);
+  if (!plan->useFallback && !kernel->relayout && split && !args->rowLen && !args->colLen && !args->mask) {
+    const SplitGeometry sg = split_geometry(split, type, p->row, p->column, heads, batches);
     const uint32_t s = sg.splits;
     if (s > 1) {
       plan->workspaceNeeded = split_workspace_bytes(type, s, heads, batches, p->row, p->column, D);
       if (p->workspace && p->workspaceBytes >= plan->workspaceNeeded &&
           (reinterpret_cast<uintptr_t>(p->workspace) & 15) == 0 && (D % 4) == 0 &&
           (uint64_t)sg.blocks * heads * batches * s <= 0x7FFFFFFFull) {
+        plan->route = &split;
         plan->grid = dim3(sg.blocks, heads, batches);
         plan->splits = s;
         plan->wsO = static_cast<float *>(p->workspace);
@@ -808,9 +797,9 @@ static mfa_status prepare_launch(const mfa_attention_kernel *kernel, void *const
 }
 
 // The one route of a prepared launch, for mfa_attention_kernel_launch / _time (run) and _launch_form (not run; `form` receives the
-// text): the in-place backward kernels, or the re-layout passes around the column-parallel (split + combine), block-sparse, causal or
-// dense entry point of the plan's variant.  Each entry point decides which code object serves the launch and names it.  Returns the
-// first failed HIP call of a run.
+// text): the in-place backward kernels, or the re-layout passes around the plan's route of its variant (split + combine, block-sparse,
+// causal or dense).  Each entry point decides which code object serves the launch and names it.  Returns the first failed HIP call
+// of a run.
 static hipError_t run_plan(const mfa_attention_kernel *kernel, const LaunchPlan &plan, hipStream_t stream, bool run, std::string *form = nullptr) {
   const Launch l{plan.args, plan.grid, plan.splits, plan.wsO, plan.wsML, stream, run, hipSuccess};
   if (plan.inPlaceBackward) {
@@ -821,11 +810,8 @@ static hipError_t run_plan(const mfa_attention_kernel *kernel, const LaunchPlan 
   for (int i = 0; i < plan.nRelayouts && run && l.err == hipSuccess; ++i)
     if (!plan.relayouts[i].output) l.err = launch_relayout(plan, plan.relayouts[i], stream);
   const VariantInfo &v = *plan.variant;
-  const bool causal = plan.args.causal != 0, sparse = plan.args.mask && v.launchSparse;
-  const char *chosen;
-  if (plan.splits > 1) chosen = (causal && v.launchSplitCausal ? v.launchSplitCausal : v.launchSplit)(l);
-  else if (sparse) chosen = v.launchSparse(l);
-  else chosen = (causal && v.launchCausal ? v.launchCausal : v.launch)(l);
+  const Route &r = *plan.route;
+  const char *chosen = r.launch(l);
   for (int i = 0; i < plan.nRelayouts && run && l.err == hipSuccess; ++i)
     if (plan.relayouts[i].output) l.err = launch_relayout(plan, plan.relayouts[i], stream);
   if (form) {
@@ -835,12 +821,13 @@ static hipError_t run_plan(const mfa_attention_kernel *kernel, const LaunchPlan 
       text += std::string(chosen ? chosen : v.name) + " (general kernel: the launch does not meet the requirements of " + kernel->variant.name + ")";
     } else if (plan.splits > 1) {
       text += std::string(v.name) + " column-parallel x" + std::to_string(plan.splits) + " + combine";
-      const bool own = v.splitParallelization && !(causal && v.launchSplitCausal);
       if (chosen) text += std::string(" (") + chosen + ")";
-      else if (!own && v.siblingName) text += std::string(" (pieces by the sibling kernel ") + v.siblingName + ")";
+      else if (std::strcmp(r.owner, v.name)) text += std::string(" (pieces by the sibling kernel ") + r.owner + ")";
     } else {
       text += chosen ? chosen : v.name;
-      if (sparse) text += v.siblingName ? std::string(" (block-sparse sibling ") + v.siblingName + ")" : std::string(" (block-sparse code object)");
+      // (a mask taken by the dense code object itself, attn_paged.h, is not a block-sparse code object)
+      if (&r == &v.sparse && r.launch != v.dense.launch)
+        text += std::strcmp(r.owner, v.name) ? std::string(" (block-sparse sibling ") + r.owner + ")" : std::string(" (block-sparse code object)");
     }
   }
   return l.err;
@@ -885,11 +872,11 @@ mfa_status mfa_attention_kernel_workspace_size(const mfa_attention_kernel *kerne
     *bytes = relayout_workspace_bytes(kernel, params->row, params->column, params->heads ? params->heads : 1, params->batches ? params->batches : 1);
     return MFA_OK;
   }
-  if (!kernel->variant.launchSplit) return MFA_OK;
+  const Route &split = kernel->variant.route(true, false, params->causal != 0);
+  if (!split || params->rowLengths || params->columnLengths || params->blockMask) return MFA_OK;
   const int type = kernel->desc.type;
-  if (params->rowLengths || params->columnLengths || params->blockMask || (type == MFA_FORWARD && params->causal)) return MFA_OK;
   const uint32_t heads = params->heads ? params->heads : 1, batches = params->batches ? params->batches : 1;
-  const uint32_t s = split_geometry(kernel->variant, type, params->row, params->column, params->causal != 0, heads, batches).splits;
+  const uint32_t s = split_geometry(split, type, params->row, params->column, heads, batches).splits;
   if (s > 1) *bytes = split_workspace_bytes(type, s, heads, batches, params->row, params->column, kernel->desc.headDimension);
   return MFA_OK;
 }
