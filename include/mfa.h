@@ -242,7 +242,23 @@ typedef struct mfa_launch_params {
    * README.md:7): non-zero = row r attends column c iff c <= r + (column - row), i.e. lower-triangular
    * for square problems.  Requires column >= row.  Applies to all three kernel types. */
   uint32_t causal;
-  uint32_t reserved;
+  /* Grouped-query attention (extension; the reference has one K / V head per query head): the number G of query heads that
+   * share one K / V head.  0 (mfa_launch_params_init) and 1 = every head has its own, as before.  `heads` stays the number of
+   * query heads Hq and must be a multiple of G (else MFA_ERR_INVALID_ARGUMENT); query head h reads K / V head h / G (torch's
+   * repeat_interleave / enable_gqa order).  headStride and batchStride of the K, V, dK and dV slots count K / V heads; Q, O, L, D,
+   * dO, dQ and blockMaskHeadStride keep counting query heads.  dK / dV head j is the sum over g < G of the gradients of query
+   * heads jG + g.  Forward and backwardQuery run exactly the launches they would run on materialised K / V (split ones included).
+   * backwardKeyValue with G > 1 needs `workspace` (256-byte aligned; too small or missing = MFA_ERR_INVALID_ARGUMENT naming the
+   * byte count): its dK / dV kernel writes fp32 per-query-head gradients to slabs [batch][query head][column][D] there -- 2 x Hq x
+   * batches x column x D x 4 bytes, plus, when operands are transposed, the re-layout copies of Q^T / dO^T (Hq heads) and K^T /
+   * V^T (Hkv = Hq / G heads) behind the slabs (mfa_attention_kernel_workspace_size reports the total) -- and attn_kv_group_sum
+   * adds each group's G slabs in order g = 0 .. G-1 in fp32 (no atomics) and stores dK / dV in their precision, leading dimension
+   * and strides.  Transposed dK^T / dV^T are written in place by attn_kv_group_sum (no re-layout copy of them).  Only the
+   * columns < columnLengths[b] of each batch entry are stored: the padding stays untouched.  Such launches are never
+   * column-split (their grid already spans Hq heads).  G > 1 launches are not taken by the in-place transposed backward kernels
+   * (attn_dq16_p4_tr / attn_dkv16_p4_tr): a backwardQuery launch on transposed operands without a workspace runs the general
+   * kernel; with one, the re-layout path. */
+  uint32_t headsPerKeyValue;
   /* Variable sequence lengths (extension): device arrays of `batches` uint32
    * entries, or NULL.  Batch entry b uses the first rowLengths[b] rows and columnLengths[b] columns of its
    * row x column problem (entries are clamped to row / column); the rest of its buffers is padding that is
@@ -275,7 +291,8 @@ mfa_status mfa_attention_kernel_launch(const mfa_attention_kernel *kernel,
                                        void *const buffers[MFA_BUFFER_SLOTS],
                                        const mfa_launch_params *params, void *stream);
 
-/* Bytes of mfa_launch_params.workspace this launch would use (0 if it would not be split). */
+/* Bytes of mfa_launch_params.workspace this launch would use (0 if it would not be split; backwardKeyValue with
+ * headsPerKeyValue > 1: the slabs and re-layout copies it requires). */
 mfa_status mfa_attention_kernel_workspace_size(const mfa_attention_kernel *kernel,
                                                const mfa_launch_params *params, uint64_t *bytes);
 /* What a launch with these buffers and parameters would run, as text -- nothing is launched.  The code object is a property of

@@ -87,7 +87,7 @@ class mfa_launch_params(ctypes.Structure):
         ("workspace", ctypes.c_void_p),
         ("workspaceBytes", ctypes.c_uint64),
         ("causal", ctypes.c_uint32),
-        ("reserved", ctypes.c_uint32),
+        ("headsPerKeyValue", ctypes.c_uint32),
         ("rowLengths", ctypes.c_void_p),
         ("columnLengths", ctypes.c_void_p),
         ("blockMask", ctypes.c_void_p),

@@ -300,7 +300,7 @@ class AttentionKernel:
     @staticmethod
     def _marshal(buffers, row, column, heads, batches, leadingDimensions, headStrides, batchStrides,
                  workspace=None, causal=False, rowLengths=None, columnLengths=None, blockMask=None,
-                 blockMaskWords=0, blockMaskStrides=(0, 0)):
+                 blockMaskWords=0, blockMaskStrides=(0, 0), headsPerKeyValue=1):
         """`buffers`: dict {AttentionOperand: tensor | int} or a 10-sequence indexed by bufferBinding."""
         slots = [None] * _abi.MFA_BUFFER_SLOTS
         if isinstance(buffers, Mapping):
@@ -323,6 +323,8 @@ class AttentionKernel:
                 for op, v in src.items():
                     dst[AttentionOperand(op).bufferBinding] = int(v)
         params.causal = int(bool(causal))
+        # grouped-query attention (extension): query heads per K / V head; K, V, dK, dV strides count K / V heads
+        params.headsPerKeyValue = int(headsPerKeyValue)
         # variable sequence lengths (extension): device arrays of `batches` uint32 / int32 entries
         params.rowLengths = _pointer(rowLengths)
         params.columnLengths = _pointer(columnLengths)
@@ -336,12 +338,13 @@ class AttentionKernel:
                 if hasattr(workspace, "numel") else int(getattr(workspace, "nbytes"))
         return arr, params, slots
 
-    def workspaceSize(self, *, row: int, column: int, heads: int = 1, batches: int = 1) -> int:
-        """Bytes of scratch a forward launch of this shape would use if given a workspace (0 = the
-        launch fills the GPU without splitting the key range)."""
+    def workspaceSize(self, *, row: int, column: int, heads: int = 1, batches: int = 1, headsPerKeyValue: int = 1) -> int:
+        """Bytes of scratch a launch of this shape would use if given a workspace (0 = the launch fills the GPU without
+        splitting the key range).  backwardKeyValue with headsPerKeyValue > 1: the per-query-head dK / dV slabs it requires."""
         params = _abi.mfa_launch_params()
         lib().mfa_launch_params_init(ctypes.byref(params))
         params.row, params.column, params.heads, params.batches = int(row), int(column), int(heads), int(batches)
+        params.headsPerKeyValue = int(headsPerKeyValue)
         out = ctypes.c_uint64()
         check(lib().mfa_attention_kernel_workspace_size(self._handle, ctypes.byref(params), ctypes.byref(out)))
         return int(out.value)
@@ -350,22 +353,24 @@ class AttentionKernel:
                  leadingDimensions: Optional[Mapping] = None, headStrides: Optional[Mapping] = None,
                  batchStrides: Optional[Mapping] = None, stream: Optional[int] = None,
                  workspace=None, causal: bool = False, rowLengths=None, columnLengths=None, blockMask=None,
-                 blockMaskWords: int = 0, blockMaskStrides=(0, 0)) -> None:
+                 blockMaskWords: int = 0, blockMaskStrides=(0, 0), headsPerKeyValue: int = 1) -> None:
         arr, params, _keep = self._marshal(buffers, row, column, heads, batches, leadingDimensions,
                                            headStrides, batchStrides, workspace, causal, rowLengths, columnLengths,
-                                           blockMask, blockMaskWords, blockMaskStrides)
+                                           blockMask, blockMaskWords, blockMaskStrides, headsPerKeyValue)
         check(lib().mfa_attention_kernel_launch(self._handle, ctypes.byref(arr), ctypes.byref(params),
                                                 ctypes.c_void_p(stream or 0)))
 
     def launchForm(self, buffers, *, row: int, column: int, heads: int = 1, batches: int = 1,
                    leadingDimensions: Optional[Mapping] = None, headStrides: Optional[Mapping] = None,
                    batchStrides: Optional[Mapping] = None, workspace=None, causal: bool = False, rowLengths=None,
-                   columnLengths=None, blockMask=None, blockMaskWords: int = 0, blockMaskStrides=(0, 0)) -> str:
+                   columnLengths=None, blockMask=None, blockMaskWords: int = 0, blockMaskStrides=(0, 0),
+                   headsPerKeyValue: int = 1) -> str:
         """What `dispatch` with the same arguments would run (nothing is launched): the variant's own kernel, the general
         kernel, column-parallel pieces + combine, a re-layout pass in front, or the persistent form `attn_fwd16_p4p` --
         the name rocprofv3 shows for dense / causal forward launches at D <= 128 (mfa_attention_kernel_launch_form)."""
         arr, params, _keep = self._marshal(buffers, row, column, heads, batches, leadingDimensions, headStrides, batchStrides,
-                                           workspace, causal, rowLengths, columnLengths, blockMask, blockMaskWords, blockMaskStrides)
+                                           workspace, causal, rowLengths, columnLengths, blockMask, blockMaskWords, blockMaskStrides,
+                                           headsPerKeyValue)
         out = ctypes.create_string_buffer(512)
         check(lib().mfa_attention_kernel_launch_form(self._handle, ctypes.byref(arr), ctypes.byref(params), out, len(out)))
         return out.value.decode()
@@ -373,10 +378,10 @@ class AttentionKernel:
     def time(self, buffers, *, row: int, column: int, heads: int = 1, batches: int = 1,
              leadingDimensions: Optional[Mapping] = None, headStrides: Optional[Mapping] = None,
              batchStrides: Optional[Mapping] = None, stream: Optional[int] = None,
-             warmup: int = 1, iterations: int = 5, workspace=None, causal: bool = False) -> float:
+             warmup: int = 1, iterations: int = 5, workspace=None, causal: bool = False, headsPerKeyValue: int = 1) -> float:
         """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
         arr, params, _keep = self._marshal(buffers, row, column, heads, batches, leadingDimensions,
-                                           headStrides, batchStrides, workspace, causal)
+                                           headStrides, batchStrides, workspace, causal, headsPerKeyValue=headsPerKeyValue)
         ms = ctypes.c_float()
         check(lib().mfa_attention_kernel_time(self._handle, ctypes.byref(arr), ctypes.byref(params),
                                               ctypes.c_void_p(stream or 0), int(warmup), int(iterations),

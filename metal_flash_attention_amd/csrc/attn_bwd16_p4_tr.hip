@@ -37,6 +37,9 @@ static bool takes(int type, const KernelArgs &a) {
   const bool gmix = p == PREC_FP16 && pg == PREC_BF16;
   if (p == PREC_FP32 || a.op[SLOT_K].precision != p || a.op[SLOT_V].precision != p || (pg != p && !gmix)) return false;
   if (a.rowLen || a.colLen || a.mask || a.D <= 64 || a.D > 128 || a.D % 8) return false;
+  // grouped-query launches: these kernels address K / V by the query head (the divisor in their prologue kept hipcc's register
+  // allocator from finishing this unit)
+  if (a.kvHeadMul || a.kvHeadShift) return false;
   if (a.causal && a.C < a.R) return false;
   if (type == 1) {
     if (!a.op[SLOT_K].transposed || !a.op[SLOT_V].transposed || a.C % 64 != 0) return false;

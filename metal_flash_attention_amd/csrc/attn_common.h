@@ -53,6 +53,10 @@ struct KernelArgs {
   const uint32_t *mask;
   uint32_t maskWords;
   int64_t maskHeadStride, maskBatchStride;
+  // extension: grouped-query attention, G query heads per K / V head (kv_head below; mfa_launch_params.headsPerKeyValue); 0, 0 = one
+  // K / V head per query head.  Last in the block, so the fields before it keep their offsets: with the divisor inside OperandView,
+  // hipcc's register allocator did not finish attn_bwd16_p4_tr.hip within the build's time limit (2 min before the change)
+  uint32_t kvHeadMul, kvHeadShift;
 };
 constexpr int MASK_BLOCK_ROWS = 256, MASK_BLOCK_COLUMNS = 128;
 
@@ -85,6 +89,12 @@ __device__ __forceinline__ int elem_size(int prec) { return prec == PREC_FP32 ? 
 __device__ __forceinline__ char *operand_base(const OperandView &v, uint32_t head, uint32_t batch) {
   const int64_t off = (int64_t)head * v.headStride + (int64_t)batch * v.batchStride;
   return (char *)v.ptr + off * elem_size(v.precision);
+}
+
+// grouped-query attention: the K / V head of query head `head` (< 65536), (umulhi(head, kvHeadMul) + head) >> kvHeadShift = head / G
+// -- uniform multiply-high, add and shift, no divide.  Every K and V base pointer goes through it
+__device__ __forceinline__ uint32_t kv_head(const KernelArgs &a, uint32_t head) {
+  return (__umulhi(head, a.kvHeadMul) + head) >> a.kvHeadShift;
 }
 
 // the problem size of one batch entry (variable-length extension); rows / columns beyond it are never

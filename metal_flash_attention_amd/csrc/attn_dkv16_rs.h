@@ -84,7 +84,7 @@ __global__ __launch_bounds__(dkv16rs_pairs<D>() * 128) void attn_dkv16_rs(const 
   {
     const int slot = role ? SLOT_V : SLOT_K;
     const uint32_t ld2 = (uint32_t)a.op[slot].ld * 2;
-    const __amdgpu_buffer_rsrc_t res = __builtin_amdgcn_make_buffer_rsrc(operand_base(a.op[slot], head, batch), 0, (uint32_t)C * ld2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t res = __builtin_amdgcn_make_buffer_rsrc(operand_base(a.op[slot], kv_head(a, head), batch), 0, (uint32_t)C * ld2, 0x00020000);
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
       const int d0 = 16 * s + 8 * hi;

@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32_fwd(const KernelArgs a, const
   const bool causal = a.causal != 0;
 
   const __amdgpu_buffer_rsrc_t qres = rows_resource(a.op[SLOT_Q], head, batch, R);
-  const char *kbase = operand_base(a.op[SLOT_K], head, batch), *vbase = operand_base(a.op[SLOT_V], head, batch);
+  const char *kbase = operand_base(a.op[SLOT_K], kv_head(a, head), batch), *vbase = operand_base(a.op[SLOT_V], kv_head(a, head), batch);
   const uint32_t ldk = (uint32_t)a.op[SLOT_K].ld, ldv = (uint32_t)a.op[SLOT_V].ld;
   // Q fragments, pre-multiplied by log2(e) / sqrt(D): the scores leave the matrix instructions in base-2 units
   float qf[DP / 2];
@@ -552,7 +552,7 @@ __global__ __launch_bounds__(256) void attn_f32_dq(const KernelArgs a, const Fwd
   const __amdgpu_buffer_rsrc_t qres = rows_resource(a.op[SLOT_Q], head, batch, R);
   const __amdgpu_buffer_rsrc_t gres = rows_resource(a.op[SLOT_dO], head, batch, R);
   const __amdgpu_buffer_rsrc_t ores = rows_resource(a.op[SLOT_O], head, batch, R);
-  const char *kbase = operand_base(a.op[SLOT_K], head, batch), *vbase = operand_base(a.op[SLOT_V], head, batch);
+  const char *kbase = operand_base(a.op[SLOT_K], kv_head(a, head), batch), *vbase = operand_base(a.op[SLOT_V], kv_head(a, head), batch);
   const uint32_t ldk = (uint32_t)a.op[SLOT_K].ld, ldv = (uint32_t)a.op[SLOT_V].ld;
   float qf[DP / 2], gf[DP / 2];
   load_fragments<DP>(qf, qres, (uint32_t)row * (uint32_t)a.op[SLOT_Q].ld * 4u, row < R, hi, D);
@@ -701,8 +701,8 @@ __global__ __launch_bounds__(256) void attn_f32_dkv(const KernelArgs a, const Fw
   const int64_t col = c0 + wave * 32 + kc;
   const bool causal = a.causal != 0;
 
-  const __amdgpu_buffer_rsrc_t kres = rows_resource(a.op[SLOT_K], head, batch, C);
-  const __amdgpu_buffer_rsrc_t vres = rows_resource(a.op[SLOT_V], head, batch, C);
+  const __amdgpu_buffer_rsrc_t kres = rows_resource(a.op[SLOT_K], kv_head(a, head), batch, C);
+  const __amdgpu_buffer_rsrc_t vres = rows_resource(a.op[SLOT_V], kv_head(a, head), batch, C);
   const char *qbase = operand_base(a.op[SLOT_Q], head, batch), *gbase = operand_base(a.op[SLOT_dO], head, batch);
   const char *lbase = operand_base(a.op[SLOT_L], head, batch), *dbase = operand_base(a.op[SLOT_D], head, batch);
   const uint32_t ldq = (uint32_t)a.op[SLOT_Q].ld, ldg = (uint32_t)a.op[SLOT_dO].ld;

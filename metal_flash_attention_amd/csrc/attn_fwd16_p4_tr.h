@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void attn_fwd16_p4_tr(const KernelArgs a, cons
   const int64_t r0 = (int64_t)rblk * GROWS + wave * WROWS;
   const uint32_t ldq2 = (uint32_t)a.op[SLOT_Q].ld * 2, ldk2 = (uint32_t)a.op[SLOT_K].ld * 2,
                  ldv2 = (uint32_t)a.op[SLOT_V].ld * 2;
-  const char *kptr = operand_base(a.op[SLOT_K], head, batch), *vptr = operand_base(a.op[SLOT_V], head, batch);
+  const char *kptr = operand_base(a.op[SLOT_K], kv_head(a, head), batch), *vptr = operand_base(a.op[SLOT_V], kv_head(a, head), batch);
   const __amdgpu_buffer_rsrc_t qres = __builtin_amdgcn_make_buffer_rsrc(
       operand_base(a.op[SLOT_Q], head, batch), 0, (uint32_t)(qT ? Dr : R) * ldq2, 0x00020000);
   const uint32_t knrec = (uint32_t)(KT ? Dr : C) * ldk2, vnrec = (uint32_t)(VT ? Dr : C) * ldv2;

@@ -95,8 +95,8 @@ __global__ __launch_bounds__(256) void attn_fwd16_p4p(const KernelArgs a, const 
   if ((uint32_t)tid < nunits) {
     uint32_t pos = 0;
     for (int i = 0; i < tid; ++i) pos += counts[i];
-    uint64_t base[5] = {(uint64_t)(uintptr_t)operand_base(a.op[SLOT_Q], myhead, mybatch), (uint64_t)(uintptr_t)operand_base(a.op[SLOT_K], myhead, mybatch),
-                        (uint64_t)(uintptr_t)operand_base(a.op[SLOT_V], myhead, mybatch), (uint64_t)(uintptr_t)operand_base(a.op[SLOT_O], myhead, mybatch),
+    uint64_t base[5] = {(uint64_t)(uintptr_t)operand_base(a.op[SLOT_Q], myhead, mybatch), (uint64_t)(uintptr_t)operand_base(a.op[SLOT_K], kv_head(a, myhead), mybatch),
+                        (uint64_t)(uintptr_t)operand_base(a.op[SLOT_V], kv_head(a, myhead), mybatch), (uint64_t)(uintptr_t)operand_base(a.op[SLOT_O], myhead, mybatch),
                         (uint64_t)(uintptr_t)operand_base(a.op[SLOT_L], myhead, mybatch)};
     if constexpr (TR.split) {
       // K / V start at the piece (C / splits keys, a multiple of 128: the launcher checks); O and (m, l) go to the piece's slabs of

@@ -99,8 +99,8 @@ __global__ __launch_bounds__(256) void attn_fwd16_p6(const KernelArgs a, const F
     const uint32_t head = myhead, batch = mybatch, piece = mypiece;
     uint32_t pos = 0;
     for (int i = 0; i < tid; ++i) pos += counts[i];
-    uint64_t base[5] = {(uint64_t)(uintptr_t)operand_base(a.op[SLOT_Q], head, batch), (uint64_t)(uintptr_t)operand_base(a.op[SLOT_K], head, batch),
-                        (uint64_t)(uintptr_t)operand_base(a.op[SLOT_V], head, batch), (uint64_t)(uintptr_t)operand_base(a.op[SLOT_O], head, batch),
+    uint64_t base[5] = {(uint64_t)(uintptr_t)operand_base(a.op[SLOT_Q], head, batch), (uint64_t)(uintptr_t)operand_base(a.op[SLOT_K], kv_head(a, head), batch),
+                        (uint64_t)(uintptr_t)operand_base(a.op[SLOT_V], kv_head(a, head), batch), (uint64_t)(uintptr_t)operand_base(a.op[SLOT_O], head, batch),
                         (uint64_t)(uintptr_t)operand_base(a.op[SLOT_L], head, batch)};
     if constexpr (TR.split) {
       // K / V start at the piece (C / splits keys, a multiple of 256: the launcher checks); O and (m, l) go to the piece's slabs of

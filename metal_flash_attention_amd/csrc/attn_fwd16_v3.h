@@ -139,9 +139,9 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd16_v3(const KernelArgs a, con
   const __amdgpu_buffer_rsrc_t qres = __builtin_amdgcn_make_buffer_rsrc(
       operand_base(a.op[SLOT_Q], head, batch), 0, (uint32_t)(qT ? Dr : R) * ldq2, 0x00020000);
   const __amdgpu_buffer_rsrc_t kres = __builtin_amdgcn_make_buffer_rsrc(
-      operand_base(a.op[SLOT_K], head, batch), 0, (uint32_t)(KT ? Dr : C) * ldk2, 0x00020000);
+      operand_base(a.op[SLOT_K], kv_head(a, head), batch), 0, (uint32_t)(KT ? Dr : C) * ldk2, 0x00020000);
   const __amdgpu_buffer_rsrc_t vres = __builtin_amdgcn_make_buffer_rsrc(
-      operand_base(a.op[SLOT_V], head, batch), 0, (uint32_t)(VT ? Dr : C) * ldv2, 0x00020000);
+      operand_base(a.op[SLOT_V], kv_head(a, head), batch), 0, (uint32_t)(VT ? Dr : C) * ldv2, 0x00020000);
   constexpr uint32_t OOB = 0xFFFFFF00u;
 
   // ---- Q fragments (B operand of S^T = K Q^T), cached in registers for the whole kernel
@@ -206,8 +206,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd16_v3(const KernelArgs a, con
   int lcol = tile0 * BC, wcol = tile0 * BC;
   // rows of a transposed operand that do not begin on 16-byte boundaries (leading dimension = an odd sequence length, say):
   // the chunk is gathered by eight 16-bit loads instead of one 128-bit load -- slower, but still the matrix-core kernel
-  const bool kGather = KT && (((uintptr_t)operand_base(a.op[SLOT_K], head, batch) | ldk2) & 15) != 0;
-  const bool vGather = VT && (((uintptr_t)operand_base(a.op[SLOT_V], head, batch) | ldv2) & 15) != 0;
+  const bool kGather = KT && (((uintptr_t)operand_base(a.op[SLOT_K], kv_head(a, head), batch) | ldk2) & 15) != 0;
+  const bool vGather = VT && (((uintptr_t)operand_base(a.op[SLOT_V], kv_head(a, head), batch) | ldv2) & 15) != 0;
   auto gather_chunk = [&](const __amdgpu_buffer_rsrc_t &res, uint32_t off, int col) {   // keys col .. col + 7 of one row
     uint16_t e[8];
     const bool row = off < OOB;   // (rows beyond the head dimension: their offset saturates at 2^32 - 1 as the tiles advance,

@@ -245,8 +245,8 @@ __global__ __launch_bounds__(NW * 64, (DP <= 128 ? 2 : 1)) void attn_generic_fwd
   float m = -3.402823466e+38f;          // +Caching.swift:310
   float l = 1.401298464e-45f;           // +Caching.swift:311 (denorm_min)
 
-  const char *kbase = operand_base(a.op[SLOT_K], head, batch);
-  const char *vbase = operand_base(a.op[SLOT_V], head, batch);
+  const char *kbase = operand_base(a.op[SLOT_K], kv_head(a, head), batch);
+  const char *vbase = operand_base(a.op[SLOT_V], kv_head(a, head), batch);
 
   // fp32 row-major operands (the FP32 production case): the next tile's global loads are issued
   // before the arithmetic of this tile and land in registers; other layouts stage synchronously.
@@ -412,8 +412,8 @@ __global__ __launch_bounds__(NW * 64) void attn_generic_dq(const KernelArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[db][r] = 0.f;
 
-  const char *kbase = operand_base(a.op[SLOT_K], head, batch);
-  const char *vbase = operand_base(a.op[SLOT_V], head, batch);
+  const char *kbase = operand_base(a.op[SLOT_K], kv_head(a, head), batch);
+  const char *vbase = operand_base(a.op[SLOT_V], kv_head(a, head), batch);
   // fp32 row-major operands (the FP32 production case): the next tile's global loads are issued
   // before the arithmetic of this tile and land in registers; other layouts stage synchronously.
   // causal extension: row r sees column c iff c <= r + coff; columns past the last row's limit are
@@ -512,14 +512,14 @@ __global__ __launch_bounds__(NW * 64) void attn_generic_dkv(const KernelArgs a) 
   float kf[CACHE ? NS : 1], vf[CACHE ? NS : 1];
   const float *krow = Kst + (wave * 32 + kc) * LD + hi;
   const float *vrow = Vst + (wave * 32 + kc) * LD + hi;
-  stage_tile<BCOL, DP, NT>(Kst, a.op[SLOT_K], operand_base(a.op[SLOT_K], head, batch), c0, C, D, tid);
+  stage_tile<BCOL, DP, NT>(Kst, a.op[SLOT_K], operand_base(a.op[SLOT_K], kv_head(a, head), batch), c0, C, D, tid);
   __syncthreads();
   if constexpr (CACHE) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) kf[s] = krow[2 * s];
     __syncthreads();
   }
-  stage_tile<BCOL, DP, NT>(Vst, a.op[SLOT_V], operand_base(a.op[SLOT_V], head, batch), c0, C, D, tid);
+  stage_tile<BCOL, DP, NT>(Vst, a.op[SLOT_V], operand_base(a.op[SLOT_V], kv_head(a, head), batch), c0, C, D, tid);
   __syncthreads();
   if constexpr (CACHE) {
 #pragma unroll

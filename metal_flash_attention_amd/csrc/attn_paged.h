@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void attn_paged_fwd(const KernelArgs a, const 
   batch_lengths(a, batch, R, C);
   const int64_t r0 = (int64_t)rblk * BR, row = r0 + r;
   if (r0 >= R) return;
-  const char *qb = operand_base(a.op[SLOT_Q], head, batch), *kb = operand_base(a.op[SLOT_K], head, batch), *vb = operand_base(a.op[SLOT_V], head, batch);
+  const char *qb = operand_base(a.op[SLOT_Q], head, batch), *kb = operand_base(a.op[SLOT_K], kv_head(a, head), batch), *vb = operand_base(a.op[SLOT_V], kv_head(a, head), batch);
   float *ob = reinterpret_cast<float *>(operand_base(a.op[SLOT_O], head, batch));
   const OperandView &ov = a.op[SLOT_O];
   const uint32_t *mk = mask_base(a, head, batch);
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void attn_paged_dq(const KernelArgs a, const p
   batch_lengths(a, batch, R, C);
   const int64_t r0 = (int64_t)rblk * BR, row = r0 + r;
   if (r0 >= R) return;
-  const char *qb = operand_base(a.op[SLOT_Q], head, batch), *kb = operand_base(a.op[SLOT_K], head, batch), *vb = operand_base(a.op[SLOT_V], head, batch);
+  const char *qb = operand_base(a.op[SLOT_Q], head, batch), *kb = operand_base(a.op[SLOT_K], kv_head(a, head), batch), *vb = operand_base(a.op[SLOT_V], kv_head(a, head), batch);
   const char *gb = operand_base(a.op[SLOT_dO], head, batch), *obase = operand_base(a.op[SLOT_O], head, batch);
   float *qg = reinterpret_cast<float *>(operand_base(a.op[SLOT_dQ], head, batch));
   const OperandView &qgv = a.op[SLOT_dQ], &gv = a.op[SLOT_dO], &ovw = a.op[SLOT_O];
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void attn_paged_dkv(const KernelArgs a, const 
   batch_lengths(a, batch, R, C);
   const int64_t c0 = (int64_t)cblk * BC, col = c0 + kc;
   if (c0 >= C) return;
-  const char *qb = operand_base(a.op[SLOT_Q], head, batch), *kb = operand_base(a.op[SLOT_K], head, batch), *vb = operand_base(a.op[SLOT_V], head, batch);
+  const char *qb = operand_base(a.op[SLOT_Q], head, batch), *kb = operand_base(a.op[SLOT_K], kv_head(a, head), batch), *vb = operand_base(a.op[SLOT_V], kv_head(a, head), batch);
   const char *gb = operand_base(a.op[SLOT_dO], head, batch);
   const char *lb = operand_base(a.op[SLOT_L], head, batch), *db = operand_base(a.op[SLOT_D], head, batch);
   float *vg = reinterpret_cast<float *>(operand_base(a.op[SLOT_dV], head, batch)), *kg = reinterpret_cast<float *>(operand_base(a.op[SLOT_dK], head, batch));

@@ -46,8 +46,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd16(const KernelArgs a, const 
   const int64_t r0 = (int64_t)rblk * (NW * RB * 32) + wave * (RB * 32);
 
   const char *qbase = operand_base(a.op[SLOT_Q], head, batch);
-  const char *kbase = operand_base(a.op[SLOT_K], head, batch);
-  const char *vbase = operand_base(a.op[SLOT_V], head, batch);
+  const char *kbase = operand_base(a.op[SLOT_K], kv_head(a, head), batch);
+  const char *vbase = operand_base(a.op[SLOT_V], kv_head(a, head), batch);
   const int64_t ldq = a.op[SLOT_Q].ld, ldk = a.op[SLOT_K].ld, ldv = a.op[SLOT_V].ld;
   const int Dr = a.D;  // runtime head dimension (multiple of 8, <= D): chunks beyond it read as zero
 

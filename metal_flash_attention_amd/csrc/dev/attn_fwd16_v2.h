@@ -52,9 +52,9 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd16_v2(const KernelArgs a, con
   const __amdgpu_buffer_rsrc_t qres = __builtin_amdgcn_make_buffer_rsrc(
       operand_base(a.op[SLOT_Q], head, batch), 0, (uint32_t)R * ldq2, 0x00020000);
   const __amdgpu_buffer_rsrc_t kres = __builtin_amdgcn_make_buffer_rsrc(
-      operand_base(a.op[SLOT_K], head, batch), 0, (uint32_t)C * ldk2, 0x00020000);
+      operand_base(a.op[SLOT_K], kv_head(a, head), batch), 0, (uint32_t)C * ldk2, 0x00020000);
   const __amdgpu_buffer_rsrc_t vres = __builtin_amdgcn_make_buffer_rsrc(
-      operand_base(a.op[SLOT_V], head, batch), 0, (uint32_t)C * ldv2, 0x00020000);
+      operand_base(a.op[SLOT_V], kv_head(a, head), batch), 0, (uint32_t)C * ldv2, 0x00020000);
   constexpr uint32_t OOB = 0xFFFFFF00u;
 
   // ---- Q fragments (B operand of S^T = K Q^T)

@@ -157,4 +157,9 @@ const char *bwd16_p4_tr_launch(int type, bool fold, const Launch &l);
 // to the hand-placed stream (attn_fwd16_p5_tr.h); `out` arrives filled by fwd16_v3_tr_variant_dNN, whose kernel keeps the others
 bool fwd16_p5_tr_variant(int precision, int bucket, int pattern, bool fold, VariantInfo *out);
 
+// grouped-query backwardKeyValue (attn_kv_group_sum.hip): dK / dV head j = sum over g < G, in order, of the fp32 slabs
+// [batch][query head][column][D] of query heads jG + g, stored through the caller's views `dv` / `dk` (whose strides count K / V heads)
+hipError_t launch_kv_group_sum(const float *dvSlabs, const float *dkSlabs, const OperandView &dv, const OperandView &dk, uint32_t G,
+                               uint32_t kvHeads, uint32_t batches, uint32_t C, uint32_t D, const uint32_t *colLen, hipStream_t stream);
+
 } // namespace mfa

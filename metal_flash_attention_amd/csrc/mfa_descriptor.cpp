@@ -327,7 +327,7 @@ void mfa_attention_kernel_descriptor_init(mfa_attention_kernel_descriptor *k) {
 void mfa_launch_params_init(mfa_launch_params *params) {
   if (!params) return;
   std::memset(params, 0, sizeof(*params));
-  params->heads = params->batches = 1;
+  params->heads = params->batches = 1;   // (headsPerKeyValue 0: one K / V head per query head)
 }
 
 mfa_status mfa_attention_descriptor_memory_precisions(const mfa_attention_descriptor *desc, int8_t *out) {

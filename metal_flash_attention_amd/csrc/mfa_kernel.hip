@@ -491,10 +491,15 @@ struct LaunchPlan {
   float *wsO = nullptr, *wsML = nullptr;
   uint64_t workspaceNeeded = 0;
   // transposed operands served through row-major copies in the caller's workspace
-  struct Relayout { int slot; OperandView user; void *copy; uint32_t seq; bool output; };
+  struct Relayout { int slot; OperandView user; void *copy; uint32_t seq; uint32_t heads; bool output; };
   Relayout relayouts[MFA_BUFFER_SLOTS];
   int nRelayouts = 0;
   uint32_t heads = 1, batches = 1;
+  // grouped-query backwardKeyValue (G = headsPerKeyValue > 1): the kernels write per-query-head fp32 slabs (wsKV: dV slabs, then dK
+  // slabs) and attn_kv_group_sum stores their group sums through the caller's views kvOut (dV, dK)
+  uint32_t groups = 1;
+  float *wsKV = nullptr;
+  OperandView kvOut[2];
   // a transposed backward launch without a workspace that the in-place kernels take (attn_bwd16_p4_tr.hip; AttentionKernel.swift:
   // 189-204: the reference reads transposed operands in place in every kernel) instead of the general kernel
   bool inPlaceBackward = false;
@@ -571,13 +576,13 @@ extern "C" {
 
 static hipError_t launch_relayout(const LaunchPlan &plan, const LaunchPlan::Relayout &r, hipStream_t stream) {
   const uint32_t D = plan.args.D;
-  const dim3 grid(((r.seq + 63) / 64) * ((D + 63) / 64), plan.heads, plan.batches);
+  const dim3 grid(((r.seq + 63) / 64) * ((D + 63) / 64), r.heads, plan.batches);
   const char *t = static_cast<const char *>(r.user.ptr);
   char *c = static_cast<char *>(r.copy);
   const int toTransposed = r.output ? 1 : 0;
   if (r.user.precision == PREC_FP32)
-    return launch_kernel(&attn_relayout<uint32_t>, grid, dim3(256), 0, stream, t, c, r.seq, D, r.user.ld, r.user.headStride, r.user.batchStride, plan.heads, toTransposed);
-  return launch_kernel(&attn_relayout<uint16_t>, grid, dim3(256), 0, stream, t, c, r.seq, D, r.user.ld, r.user.headStride, r.user.batchStride, plan.heads, toTransposed);
+    return launch_kernel(&attn_relayout<uint32_t>, grid, dim3(256), 0, stream, t, c, r.seq, D, r.user.ld, r.user.headStride, r.user.batchStride, r.heads, toTransposed);
+  return launch_kernel(&attn_relayout<uint16_t>, grid, dim3(256), 0, stream, t, c, r.seq, D, r.user.ld, r.user.headStride, r.user.batchStride, r.heads, toTransposed);
 }
 
 static bool is_output_slot(int type, int slot) {
@@ -588,20 +593,54 @@ static bool is_output_slot(int type, int slot) {
   }
 }
 
-// bytes of workspace the row-major copies of this launch's transposed operands take (256-byte aligned each)
-static uint64_t relayout_workspace_bytes(const mfa_attention_kernel *kernel, uint32_t row, uint32_t column, uint32_t heads, uint32_t batches) {
+// grouped-query attention: G query heads per K / V head (mfa_launch_params.headsPerKeyValue; 0 and 1 = one K / V head per query head)
+static uint32_t heads_per_kv(const mfa_launch_params *p) { return p->headsPerKeyValue > 1 ? p->headsPerKeyValue : 1; }
+static bool kv_slot(int slot) { return slot == SLOT_K || slot == SLOT_V || slot == SLOT_dK || slot == SLOT_dV; }
+// a grouped-query backwardKeyValue launch: dK / dV go through per-query-head slabs and attn_kv_group_sum
+static bool grouped_dkv(const mfa_attention_kernel *kernel, uint32_t G) { return G > 1 && kernel->desc.type == MFA_BACKWARD_KEY_VALUE; }
+
+// the K / V head of a query head: h / G as (umulhi(h, m) + h) >> l (kv_head, attn_common.h) with l = ceil(log2 G) and
+// m = floor(2^32 (2^l - G) / G) + 1 -- i.e. floor(h M / 2^(32 + l)) with M = 2^32 + m = floor(2^(32 + l) / G) + 1, whose error
+// h (MG - 2^(32 + l)) / (G 2^(32 + l)) < h / 2^(32 + l) stays below 1 / G for h < 2^16 (heads <= 65535): exact.  G = 1: (0, 0)
+static void set_head_divisor(KernelArgs &a, uint32_t G) {
+  a.kvHeadMul = a.kvHeadShift = 0;
+  if (G <= 1) return;
+  uint32_t l = 0;
+  while ((1u << l) < G) ++l;
+  a.kvHeadShift = l;
+  a.kvHeadMul = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - G)) / G + 1);
+}
+
+// bytes of workspace the row-major copies of this launch's transposed operands take (256-byte aligned each); K / V copies hold the
+// Hq / G K / V heads, and grouped-query backwardKeyValue writes dK^T / dV^T in place (attn_kv_group_sum): no copy of them
+static uint64_t relayout_workspace_bytes(const mfa_attention_kernel *kernel, uint32_t row, uint32_t column, uint32_t heads, uint32_t batches,
+                                         uint32_t G) {
   const int type = kernel->desc.type;
   uint64_t total = 0;
   for (int slot = 0; slot < MFA_BUFFER_SLOTS; ++slot) {
     if (!slot_used(type, slot) || slot == SLOT_L || slot == SLOT_D) continue;
+    if (grouped_dkv(kernel, G) && (slot == SLOT_dK || slot == SLOT_dV)) continue;
     const int op = slot_operand(slot);
     if (!kernel->desc.transposeState[op]) continue;
     const bool rowOperand = (op == MFA_Q || op == MFA_O || op == MFA_dO || op == MFA_dQ);
     const uint64_t seq = rowOperand ? row : column;
     const uint64_t esz = kernel->desc.memoryPrecisions[op] == MFA_FP32 ? 4 : 2;
-    total += ((uint64_t)heads * batches * seq * kernel->desc.headDimension * esz + 255) & ~255ull;
+    const uint64_t h = kv_slot(slot) ? heads / G : heads;
+    total += (h * batches * seq * kernel->desc.headDimension * esz + 255) & ~255ull;
   }
   return total;
+}
+
+// grouped-query backwardKeyValue: the fp32 dV and dK slabs [batch][query head][column][D] (2 x Hq x batches x column x D x 4 bytes)
+static uint64_t group_slab_bytes(uint32_t heads, uint32_t batches, uint32_t column, uint32_t D) {
+  return 2ull * heads * batches * column * D * sizeof(float);
+}
+// everything such a launch needs: the slabs, then (256-byte aligned) the re-layout copies of its transposed inputs
+static uint64_t grouped_dkv_workspace_bytes(const mfa_attention_kernel *kernel, uint32_t row, uint32_t column, uint32_t heads,
+                                            uint32_t batches, uint32_t G) {
+  const uint64_t slabs = group_slab_bytes(heads, batches, column, kernel->desc.headDimension);
+  if (!kernel->relayout) return slabs;
+  return ((slabs + 255) & ~255ull) + relayout_workspace_bytes(kernel, row, column, heads, batches, G);
 }
 
 // Column-parallel heuristic: split only when the row-parallel grid cannot fill the 256 CUs and the traversal is long enough to
@@ -706,28 +745,57 @@ static mfa_status prepare_launch(const mfa_attention_kernel *kernel, void *const
   plan->heads = heads;
   plan->batches = batches;
   plan->nRelayouts = 0;
+  const uint32_t G = heads_per_kv(p);
+  if (heads % G != 0)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "heads (" + std::to_string(heads) + ") is not a multiple of headsPerKeyValue (" + std::to_string(G) + ")");
+  plan->groups = G;
+  set_head_divisor(*args, G);
+  uint64_t relayoutOffset = 0;   // where the re-layout copies start in the workspace
+  if (grouped_dkv(kernel, G)) {
+    // dK / dV of every query head to fp32 slabs of the workspace; attn_kv_group_sum adds each group's slabs into the caller's views
+    const uint64_t need = grouped_dkv_workspace_bytes(kernel, p->row, p->column, heads, batches, G);
+    plan->workspaceNeeded = need;
+    if (!p->workspace || p->workspaceBytes < need || (reinterpret_cast<uintptr_t>(p->workspace) & 255) != 0)
+      return fail(MFA_ERR_INVALID_ARGUMENT, "backwardKeyValue with headsPerKeyValue " + std::to_string(G) + " needs a 256-byte aligned workspace of " +
+                                                std::to_string(need) + " bytes (mfa_attention_kernel_workspace_size) for its per-query-head dK / dV slabs");
+    if ((uint64_t)p->column * D > 0xFFFFFFFFull - 255)
+      return fail(MFA_ERR_INVALID_ARGUMENT, "backwardKeyValue with headsPerKeyValue > 1: column x head dimension must stay below 2^32");
+    const uint64_t half = (uint64_t)heads * batches * p->column * D;   // floats per slab set
+    plan->wsKV = static_cast<float *>(p->workspace);
+    plan->kvOut[0] = args->op[SLOT_dV];
+    plan->kvOut[1] = args->op[SLOT_dK];
+    for (int i = 0; i < 2; ++i) {
+      OperandView &v = args->op[i ? SLOT_dK : SLOT_dV];
+      v.ptr = plan->wsKV + i * half;
+      v.precision = PREC_FP32; v.transposed = 0; v.ld = D;
+      v.headStride = (int64_t)p->column * D; v.batchStride = (int64_t)heads * p->column * D;
+    }
+    relayoutOffset = (group_slab_bytes(heads, batches, p->column, D) + 255) & ~255ull;
+  }
   bool relayoutMissing = false;
   if (kernel->relayout) {
-    const uint64_t need = relayout_workspace_bytes(kernel, p->row, p->column, heads, batches);
+    const uint64_t need = relayoutOffset + relayout_workspace_bytes(kernel, p->row, p->column, heads, batches, G);
     plan->workspaceNeeded = need;
     // per-batch lengths: the matrix-core kernels never write the padding rows of an output, so the write-back of a row-major
     // output copy (uninitialised workspace) would overwrite the caller's padding region -- such launches take the general
     // kernel, which reads and writes the transposed views in place
     const bool lengths = args->rowLen || args->colLen;
     if (!lengths && p->workspace && p->workspaceBytes >= need && (reinterpret_cast<uintptr_t>(p->workspace) & 255) == 0) {
-      char *cursor = static_cast<char *>(p->workspace);
+      char *cursor = static_cast<char *>(p->workspace) + relayoutOffset;
+      // (grouped-query backwardKeyValue: dK / dV are the slabs by now, row-major -- attn_kv_group_sum writes dK^T / dV^T in place)
       for (int slot = 0; slot < MFA_BUFFER_SLOTS; ++slot) {
         if (!slot_used(type, slot) || slot == SLOT_L || slot == SLOT_D || !args->op[slot].transposed) continue;
         OperandView &v = args->op[slot];
         const int op = slot_operand(slot);
         const bool rowOperand = (op == MFA_Q || op == MFA_O || op == MFA_dO || op == MFA_dQ);
         const uint32_t seq = rowOperand ? p->row : p->column;
+        const uint32_t h = kv_slot(slot) ? heads / G : heads;   // (K / V copies: the K / V heads, addressed through kv_head)
         LaunchPlan::Relayout &r = plan->relayouts[plan->nRelayouts++];
-        r.slot = slot; r.user = v; r.copy = cursor; r.seq = seq; r.output = is_output_slot(type, slot);
+        r.slot = slot; r.user = v; r.copy = cursor; r.seq = seq; r.heads = h; r.output = is_output_slot(type, slot);
         const uint64_t esz = v.precision == PREC_FP32 ? 4 : 2;
-        cursor += ((uint64_t)heads * batches * seq * D * esz + 255) & ~255ull;
+        cursor += ((uint64_t)h * batches * seq * D * esz + 255) & ~255ull;
         v.ptr = r.copy; v.transposed = 0; v.ld = D;
-        v.headStride = (int64_t)seq * D; v.batchStride = (int64_t)heads * seq * D;
+        v.headStride = (int64_t)seq * D; v.batchStride = (int64_t)h * seq * D;
       }
     } else {
       relayoutMissing = true;   // no (or too small a) workspace: the general kernel reads the transposed operands in place
@@ -777,7 +845,8 @@ static mfa_status prepare_launch(const mfa_attention_kernel *kernel, void *const
   // the key range (partial (O, m, l), online-softmax merge), backwardQuery the key range and backwardKeyValue
   // the row range (partial dQ / dK, dV in fp32 slabs, summed by attn_bwd_combine).
   const Route &split = plan->variant->route(true, false, args->causal != 0);
-  if (!plan->useFallback && !kernel->relayout && split && !args->rowLen && !args->colLen && !args->mask) {
+  // (grouped-query backwardKeyValue is never split: its grid already spans the Hq query heads)
+  if (!plan->useFallback && !kernel->relayout && split && !args->rowLen && !args->colLen && !args->mask && !grouped_dkv(kernel, G)) {
     const SplitGeometry sg = split_geometry(split, type, p->row, p->column, heads, batches);
     const uint32_t s = sg.splits;
     if (s > 1) {
@@ -802,9 +871,19 @@ static mfa_status prepare_launch(const mfa_attention_kernel *kernel, void *const
 // of a run.
 static hipError_t run_plan(const mfa_attention_kernel *kernel, const LaunchPlan &plan, hipStream_t stream, bool run, std::string *form = nullptr) {
   const Launch l{plan.args, plan.grid, plan.splits, plan.wsO, plan.wsML, stream, run, hipSuccess};
+  // grouped-query backwardKeyValue: the group sums of the per-query-head slabs into the caller's dK / dV
+  auto group_sum = [&]() {
+    if (plan.groups <= 1 || kernel->desc.type != MFA_BACKWARD_KEY_VALUE) return;
+    const uint64_t half = (uint64_t)plan.heads * plan.batches * plan.args.C * plan.args.D;
+    if (run && l.err == hipSuccess)
+      l.err = launch_kv_group_sum(plan.wsKV, plan.wsKV + half, plan.kvOut[0], plan.kvOut[1], plan.groups, plan.heads / plan.groups,
+                                  plan.batches, plan.args.C, plan.args.D, plan.args.colLen, stream);
+    if (form) *form += " + attn_kv_group_sum x" + std::to_string(plan.groups);
+  };
   if (plan.inPlaceBackward) {
     const char *chosen = bwd16_p4_tr_launch(kernel->desc.type, kernel->desc.registerPrecisions[MFA_P] > MFA_FP32, l);
     if (form) *form = chosen;
+    group_sum();
     return l.err;
   }
   for (int i = 0; i < plan.nRelayouts && run && l.err == hipSuccess; ++i)
@@ -830,6 +909,7 @@ static hipError_t run_plan(const mfa_attention_kernel *kernel, const LaunchPlan 
         text += std::strcmp(r.owner, v.name) ? std::string(" (block-sparse sibling ") + r.owner + ")" : std::string(" (block-sparse code object)");
     }
   }
+  group_sum();
   return l.err;
 }
 
@@ -868,8 +948,15 @@ mfa_status mfa_attention_kernel_workspace_size(const mfa_attention_kernel *kerne
   if (!kernel || !params || !bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   *bytes = 0;
   if (params->row == 0 || params->column == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "row and column must be non-zero");
+  const uint32_t G = heads_per_kv(params), H = params->heads ? params->heads : 1, B = params->batches ? params->batches : 1;
+  if (H % G != 0)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "heads (" + std::to_string(H) + ") is not a multiple of headsPerKeyValue (" + std::to_string(G) + ")");
+  if (grouped_dkv(kernel, G)) {   // per-query-head dK / dV slabs (+ re-layout copies): required, whatever the launch would otherwise do
+    *bytes = grouped_dkv_workspace_bytes(kernel, params->row, params->column, H, B, G);
+    return MFA_OK;
+  }
   if (kernel->relayout) {   // row-major copies of the transposed operands (without them the launch runs the general kernel)
-    *bytes = relayout_workspace_bytes(kernel, params->row, params->column, params->heads ? params->heads : 1, params->batches ? params->batches : 1);
+    *bytes = relayout_workspace_bytes(kernel, params->row, params->column, H, B, G);
     return MFA_OK;
   }
   const Route &split = kernel->variant.route(true, false, params->causal != 0);

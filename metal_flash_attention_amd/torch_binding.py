@@ -2,7 +2,7 @@
 reference does not have -- only its tests call the kernels, Tests/FlashAttentionTests/Attention/*.swift).
 
     from metal_flash_attention_amd.torch_binding import flash_attention
-    o = flash_attention(q, k, v, causal=False)      # q [B, H, R, D], k / v [B, H, C, D]; bf16, fp16 or fp32
+    o = flash_attention(q, k, v, causal=False)      # q [B, H, R, D], k / v [B, Hkv, C, D] (H % Hkv == 0); bf16, fp16 or fp32
     o.sum().backward()                              # dQ, dK, dV through backwardQuery / backwardKeyValue
 
     from metal_flash_attention_amd.torch_binding import flash_attention_op   # the same through torch.library ops
@@ -53,8 +53,11 @@ def _check(q, k, v):
         raise RuntimeError("flash_attention: tensors must live on the GPU (there is no CPU path)")
     if q.dtype not in (torch.bfloat16, torch.float16, torch.float32) or k.dtype != q.dtype or v.dtype != q.dtype:
         raise TypeError("flash_attention: q, k, v must share one of bfloat16 / float16 / float32")
-    if q.dim() != 4 or k.dim() != 4 or v.shape != k.shape or q.shape[:2] != k.shape[:2] or q.shape[3] != k.shape[3]:
-        raise ValueError("flash_attention: expected q [B, H, R, D] and k, v [B, H, C, D]")
+    # grouped-query attention: H query heads over Hkv K / V heads, query head h reads K / V head h // (H // Hkv)
+    if q.dim() != 4 or k.dim() != 4 or v.shape != k.shape or q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3] or \
+            k.shape[1] == 0 or q.shape[1] % k.shape[1] != 0:
+        raise ValueError("flash_attention: expected q [B, H, R, D] and k, v [B, Hkv, C, D] with H a multiple of Hkv "
+                         f"(got q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)})")
     if k.device != q.device or v.device != q.device:
         raise RuntimeError(f"flash_attention: q, k, v must live on one device (got {q.device}, {k.device}, {v.device})")
 
@@ -69,10 +72,13 @@ def _check_block_mask(block_mask, R, C):
                          f"({rows_needed}, {words_needed}) for R={R}, C={C}")
 
 
-def _strides(B, H, R, C, D):
+def _strides(B, H, R, C, D, Hkv=None):
+    """packed head / batch strides; K, V, dK, dV count the Hkv K / V heads (grouped-query attention), the rest the H query heads"""
+    Hkv = H if Hkv is None else Hkv
     hs = {Op.Q: R * D, Op.K: C * D, Op.V: C * D, Op.O: R * D, Op.L: R, Op.D: R,
           Op.dO: R * D, Op.dV: C * D, Op.dK: C * D, Op.dQ: R * D}
-    return hs, {op: s * H for op, s in hs.items()}
+    kv = (Op.K, Op.V, Op.dK, Op.dV)
+    return hs, {op: s * (Hkv if op in kv else H) for op, s in hs.items()}
 
 
 def _as_strided_operand(t):
@@ -99,8 +105,8 @@ def _run_forward(q, k, v, causal, q_lengths, k_lengths, block_mask, fast_scale):
     """forward dispatch -> (o, l, the (possibly strided) views handed to the kernel, lengths, mask arguments, fast_scale)"""
     _check(q, k, v)
     B, H, R, D = q.shape
-    C = k.shape[2]
-    hs, bs = _strides(B, H, R, C, D)
+    C, Hkv = k.shape[2], k.shape[1]
+    hs, bs = _strides(B, H, R, C, D, Hkv)
     lds = {}
     views = _apply_layouts(hs, bs, lds, Q=q, K=k, V=v)
     q, k, v = views["Q"], views["K"], views["V"]
@@ -108,7 +114,7 @@ def _run_forward(q, k, v, causal, q_lengths, k_lengths, block_mask, fast_scale):
     fast_scale = bool(fast_scale) and q.dtype != torch.float32
     l = torch.empty((B, H, R), dtype=torch.float16 if fast_scale else torch.float32, device=q.device)
     kernel = _kernel(q.dtype, R, C, D, AttentionKernelType.forward, fast_scale)
-    need = kernel.workspaceSize(row=R, column=C, heads=H, batches=B)
+    need = kernel.workspaceSize(row=R, column=C, heads=H, batches=B, headsPerKeyValue=H // Hkv)
     lengths = q_lengths is not None or k_lengths is not None
     mask_kw = {}
     if block_mask is not None:   # int32 [ceil(R / 256)][words]: bit b of word w = column block 32 w + b (128 keys each)
@@ -125,24 +131,26 @@ def _run_forward(q, k, v, causal, q_lengths, k_lengths, block_mask, fast_scale):
     with torch.cuda.device(q.device):
         kernel.dispatch({Op.Q: q, Op.K: k, Op.V: v, Op.O: o, Op.L: l}, row=R, column=C, heads=H, batches=B,
                         headStrides=hs, batchStrides=bs, leadingDimensions=lds,
-                        stream=torch.cuda.current_stream(q.device).cuda_stream, workspace=ws, causal=causal, rowLengths=q_lengths, columnLengths=k_lengths, **mask_kw)
+                        stream=torch.cuda.current_stream(q.device).cuda_stream, workspace=ws, causal=causal, rowLengths=q_lengths, columnLengths=k_lengths,
+                        headsPerKeyValue=H // Hkv, **mask_kw)
     return o, l, (q, k, v), (q_lengths, k_lengths), mask_kw, fast_scale
 
 
 def _run_backward(q, k, v, o, l, grad_out, causal, lengths, mask_kw, fast_scale):
     """backwardQuery (writes D, dQ) then backwardKeyValue (dK, dV), the dispatch order of SquareAttentionTest.swift:355-368"""
     B, H, R, D = q.shape
-    C = k.shape[2]
+    C, Hkv = k.shape[2], k.shape[1]
+    G = H // Hkv
     # dO in the kernels' gradient storage type (AttentionDescriptor+Precisions.swift:13-17): BF16 whenever
     # the inputs are 16-bit (also next to FP16 Q/K/V, the reference's mix), FP32 with FP32 inputs
     do = grad_out.to(torch.float32 if q.dtype == torch.float32 else torch.bfloat16)   # no copy when it already is
     alloc = torch.zeros if lengths != (None, None) else torch.empty   # padding gets zero gradients
     dq = alloc((B, H, R, D), dtype=q.dtype, device=q.device)
-    dk = alloc((B, H, C, D), dtype=q.dtype, device=q.device)
-    dv = alloc((B, H, C, D), dtype=q.dtype, device=q.device)
+    dk = alloc((B, Hkv, C, D), dtype=q.dtype, device=q.device)
+    dv = alloc((B, Hkv, C, D), dtype=q.dtype, device=q.device)
     dterm = alloc((B, H, R), dtype=torch.bfloat16 if fast_scale else torch.float32, device=q.device)
     bufs = {Op.Q: q, Op.K: k, Op.V: v, Op.O: o, Op.L: l, Op.D: dterm, Op.dO: do, Op.dQ: dq, Op.dK: dk, Op.dV: dv}
-    hs, bs = _strides(B, H, R, C, D)
+    hs, bs = _strides(B, H, R, C, D, Hkv)
     lds = {}
     # saved as the (possibly strided) views the forward used; a strided grad_out (e.g. the gradient of a permuted view)
     # is passed with its own leading dimension / head / batch strides instead of being copied
@@ -153,9 +161,12 @@ def _run_backward(q, k, v, o, l, grad_out, causal, lengths, mask_kw, fast_scale)
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream(q.device).cuda_stream
         for kind in (AttentionKernelType.backwardQuery, AttentionKernelType.backwardKeyValue):   # dQ writes D first
-            _kernel(q.dtype, R, C, D, kind, fast_scale).dispatch(bufs, row=R, column=C, heads=H, batches=B, headStrides=hs,
-                                                                  batchStrides=bs, leadingDimensions=lds, stream=stream, causal=causal,
-                                                                  rowLengths=lengths[0], columnLengths=lengths[1], **mask_kw)
+            kernel = _kernel(q.dtype, R, C, D, kind, fast_scale)
+            ws = None
+            if kind == AttentionKernelType.backwardKeyValue and G > 1:   # per-query-head dK / dV slabs, summed per group by the library
+                ws = torch.empty(kernel.workspaceSize(row=R, column=C, heads=H, batches=B, headsPerKeyValue=G), dtype=torch.uint8, device=q.device)
+            kernel.dispatch(bufs, row=R, column=C, heads=H, batches=B, headStrides=hs, batchStrides=bs, leadingDimensions=lds, stream=stream,
+                            causal=causal, rowLengths=lengths[0], columnLengths=lengths[1], workspace=ws, headsPerKeyValue=G, **mask_kw)
     return dq, dk, dv
 
 
