@@ -188,6 +188,23 @@ def test_strided_views_are_passed_without_a_copy(dtype, monkeypatch):
     orf.sum().backward()
     got = q2.grad[:, :, 0].permute(0, 2, 1, 3).float()
     assert (got - qr.grad).abs().max().item() < (6e-2 if dtype != torch.float32 else 5e-5)
+    # K and V gradients too, at the other head-dimension buckets, dense and causal, with an upstream gradient that is itself a
+    # permuted [B, N, H, D] view: dQ / dK / dV land in the three slices of one fused gradient tensor
+    tol = 6e-2 if dtype != torch.float32 else 5e-5
+    for D2, causal in ((64, False), (64, True), (128, False), (128, True), (192, False), (192, True)):
+        fused = torch.randn(B, N, 3, H, D2, generator=g, device="cuda").to(dtype)
+        w = (torch.randn(B, N, H, D2, generator=g, device="cuda") / 8).to(dtype).permute(0, 2, 1, 3)
+        assert not w.is_contiguous()
+        leaf = fused.detach().clone().requires_grad_(True)
+        views = [leaf[:, :, i].permute(0, 2, 1, 3) for i in range(3)]
+        out = tb.flash_attention(*views, causal=causal)
+        out.backward(w)
+        rq, rk, rv, ro = reference(*(fused[:, :, i].permute(0, 2, 1, 3) for i in range(3)), causal)
+        ro.backward(w.float())
+        assert (out.float() - ro).abs().max().item() < (3e-2 if dtype != torch.float32 else 2e-5), (D2, causal)
+        for i, (name, ref) in enumerate((("dQ", rq.grad), ("dK", rk.grad), ("dV", rv.grad))):
+            got = leaf.grad[:, :, i].permute(0, 2, 1, 3).float()
+            assert (got - ref).abs().max().item() < tol, (name, D2, causal, (got - ref).abs().max().item())
 
 
 @pytest.mark.gpu
