@@ -5,6 +5,7 @@ No CPU / PyTorch compute fallback exists: importing works without the library, u
 """
 from ._abi import LIB_PATH, MFAError  # noqa: F401
 from .attention import (  # noqa: F401
+    AttentionDecode,
     AttentionDescriptor,
     AttentionKernel,
     AttentionKernelDescriptor,

@@ -160,6 +160,34 @@ GEMM_SYMBOLS = [
       ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
 ]
 
+class mfa_decode_params(ctypes.Structure):   # include/mfa_decode.h
+    _fields_ = [
+        ("rows", ctypes.c_uint32), ("column", ctypes.c_uint32), ("heads", ctypes.c_uint32), ("batches", ctypes.c_uint32),
+        ("headsPerKeyValue", ctypes.c_uint32), ("causal", ctypes.c_uint32),
+        ("headDimension", ctypes.c_uint16), ("precision", ctypes.c_uint8), ("outputPrecision", ctypes.c_uint8),
+        ("pageSize", ctypes.c_uint32),
+        ("cacheLengths", ctypes.c_void_p), ("blockTable", ctypes.c_void_p), ("blockTableStride", ctypes.c_int64),
+        ("leadingDimension", ctypes.c_int64 * 4), ("headStride", ctypes.c_int64 * 4), ("batchStride", ctypes.c_int64 * 4),
+        ("pageStride", ctypes.c_int64 * 2),
+        ("lHeadStride", ctypes.c_int64), ("lBatchStride", ctypes.c_int64),
+        ("workspace", ctypes.c_void_p), ("workspaceBytes", ctypes.c_uint64),
+    ]
+
+
+MFA_DECODE_KEY_TILE, MFA_DECODE_MAX_PACKED_ROWS, MFA_DECODE_WORKGROUP_TARGET, MFA_DECODE_MAX_PIECES = 64, 32, 512, 64
+_DECODE_BUFS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+
+DECODE_SYMBOLS = [
+    ("mfa_decode_params_init", None, [ctypes.POINTER(mfa_decode_params)]),
+    ("mfa_attention_decode_workspace_size", ctypes.c_int, [ctypes.POINTER(mfa_decode_params), ctypes.POINTER(ctypes.c_uint64)]),
+    ("mfa_attention_decode_launch", ctypes.c_int, _DECODE_BUFS + [ctypes.POINTER(mfa_decode_params), ctypes.c_void_p]),
+    ("mfa_attention_decode_launch_form", ctypes.c_int, [ctypes.POINTER(mfa_decode_params), ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_decode_time", ctypes.c_int,
+     _DECODE_BUFS + [ctypes.POINTER(mfa_decode_params), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    ("mfa_attention_decode_piece_range", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+]
+
 SYMBOLS = [
     ("mfa_precision_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mfa_precision_size", ctypes.c_int, [ctypes.c_int]),
@@ -235,7 +263,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

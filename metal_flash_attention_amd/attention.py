@@ -399,3 +399,89 @@ def deviceName(device: int = 0) -> str:
     buf = ctypes.create_string_buffer(256)
     check(lib().mfa_device_name(device, buf, len(buf)))
     return buf.value.decode()
+
+
+class AttentionDecode:
+    """Decode attention over a KV cache (include/mfa_decode.h; an extension, the reference has no such entry): `rows` new query rows
+    per sequence against caches of `heads // headsPerKeyValue` K / V heads, per-sequence lengths on the device, contiguous or paged.
+
+        decode = AttentionDecode(headDimension=128, precision=GEMMOperandPrecision.BF16)
+        need = decode.workspaceSize(rows=1, column=C, heads=64, batches=B, headsPerKeyValue=8)
+        decode.dispatch(q, k, v, o, l, cacheLengths=lengths, rows=1, column=C, heads=64, batches=B, headsPerKeyValue=8,
+                        strides=dict(Q=(ld, head, batch), K=..., V=..., O=...), workspace=ws)
+
+    `strides`: operand name -> (leadingDimension, headStride, batchStride) in elements; an operand left out is packed
+    ([batch][head][row or key][D]).  Paged caches: pageSize, blockTable (device int32 [batches][blockTableStride]) and
+    pageStrides=(K, V); a cache operand's batchStride is then unused."""
+
+    OPERANDS = ("Q", "K", "V", "O")
+
+    def __init__(self, headDimension: int, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16,
+                 outputPrecision: Optional[GEMMOperandPrecision] = None):
+        self.headDimension = int(headDimension)
+        self.precision = GEMMOperandPrecision(precision)
+        self.outputPrecision = self.precision if outputPrecision is None else GEMMOperandPrecision(outputPrecision)
+
+    def _params(self, *, rows: int, column: int, heads: int = 1, batches: int = 1, headsPerKeyValue: int = 1, causal: bool = True,
+                cacheLengths=None, pageSize: int = 0, blockTable=None, blockTableStride: int = 0, strides: Optional[Mapping] = None,
+                pageStrides: Optional[Sequence[int]] = None, lStrides: Optional[Sequence[int]] = None, workspace=None,
+                workspaceBytes: Optional[int] = None):
+        p = _abi.mfa_decode_params()
+        lib().mfa_decode_params_init(ctypes.byref(p))
+        p.rows, p.column, p.heads, p.batches = int(rows), int(column), int(heads), int(batches)
+        p.headsPerKeyValue, p.causal = int(headsPerKeyValue), int(bool(causal))
+        p.headDimension, p.precision, p.outputPrecision = self.headDimension, int(self.precision), int(self.outputPrecision)
+        p.pageSize = int(pageSize)
+        p.cacheLengths = _pointer(cacheLengths)
+        p.blockTable = _pointer(blockTable)
+        p.blockTableStride = int(blockTableStride)
+        D, G = self.headDimension, max(1, int(headsPerKeyValue))
+        kvHeads = max(1, int(heads) // G)
+        for i, name in enumerate(self.OPERANDS):
+            seq, h = (int(rows), int(heads)) if name in ("Q", "O") else (int(column), kvHeads)
+            ld, hs, bs = (strides or {}).get(name, (D, seq * D, h * seq * D))
+            p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
+        if pageStrides is not None:
+            p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
+        p.lHeadStride, p.lBatchStride = (int(lStrides[0]), int(lStrides[1])) if lStrides is not None else (int(rows), int(heads) * int(rows))
+        p.workspace = _pointer(workspace)
+        if workspaceBytes is None:
+            workspaceBytes = int(workspace.numel() * workspace.element_size()) if hasattr(workspace, "numel") else 0
+        p.workspaceBytes = int(workspaceBytes)
+        return p, (cacheLengths, blockTable, workspace)
+
+    def workspaceSize(self, **shape) -> int:
+        """Bytes a launch of this shape wants to be cut along the keys (0: the plan has one piece).  Without a workspace the launch
+        runs unsplit in one kernel."""
+        p, _keep = self._params(**shape)
+        out = ctypes.c_uint64(0)
+        check(lib().mfa_attention_decode_workspace_size(ctypes.byref(p), ctypes.byref(out)))
+        return int(out.value)
+
+    def launchForm(self, **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the pieces kernel, the piece count and the combine
+        kernel, or the single kernel."""
+        p, _keep = self._params(**shape)
+        out = ctypes.create_string_buffer(512)
+        check(lib().mfa_attention_decode_launch_form(ctypes.byref(p), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        p, _keep = self._params(**shape)
+        check(lib().mfa_attention_decode_launch(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
+                                                ctypes.c_void_p(stream or 0)))
+
+    def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
+        p, _keep = self._params(**shape)
+        ms = ctypes.c_float(0.0)
+        check(lib().mfa_attention_decode_time(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
+                                              ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
+        return float(ms.value)
+
+    @staticmethod
+    def pieceRange(length: int, pieces: int, piece: int) -> Tuple[int, int]:
+        """keys [begin, end) of piece `piece` of `pieces` for a sequence of `length` keys: the kernels' own function, on the host"""
+        b, e = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        check(lib().mfa_attention_decode_piece_range(int(length), int(pieces), int(piece), ctypes.byref(b), ctypes.byref(e)))
+        return int(b.value), int(e.value)

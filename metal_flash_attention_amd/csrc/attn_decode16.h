@@ -1,0 +1,327 @@
+// attn_decode16.h -- decode attention on the 16-bit matrix cores of gfx950: R new query rows per sequence against a long cache of
+// keys and values (include/mfa_decode.h; an extension of this port).
+//
+// The work is bound by the bytes of K and V, so the kernel is built around reading them once and keeping many loads in flight:
+//   * one workgroup (4 waves) serves ONE K / V head of one sequence (and one piece of its keys): the G query heads x R rows that share
+//     the head are packed as the M = G R <= 32 columns of one 32-wide matrix tile, so K and V are read once, not G times.
+//   * every wave walks its own 32-key steps (wave w takes steps w, w + 4, ... of the piece) with its own running (m, l, O): no barrier
+//     inside the loop.  The four partial results are merged through LDS once, at the end.
+//   * S^T = K Q^T with v_mfma_f32_32x32x16 (the fragment maps of dev/attn_fwd16.h: a lane owns one packed query row, softmax is
+//     lane-local plus one half-wave exchange).  K goes from memory STRAIGHT to registers as the A operand (a lane = a key row, 16-byte
+//     loads); V is loaded as whole rows (coalesced), written to a wave-private LDS image [D/32][32 keys][32 d] and gathered as V^T by
+//     ds_read_b64_tr_b16.  The loads of the wave's next step are issued as soon as the registers of the current one are consumed.
+//   * keys are addressed in groups of 16 (a tile starts on a multiple of 64 and a page holds at least 16 keys, so a group never
+//     straddles a page): two wave-uniform block-table reads per step, none per lane.
+//   * what may hold poison is never loaded: key rows at or past the piece's end come in as zeros (K and V), a masked score is REPLACED
+//     (p = 0 exactly), and the running maximum only ever sees visible keys -- a step, a wave or a piece without a visible key keeps
+//     m = -FLT_MAX, l = 0.
+//   * SPLIT: piece p of sequence b takes decode_piece_range(len_b, pieces, p) -- the same function the host exports -- and publishes
+//     un-normalised O, m, l in FP32 (wsO [pieces][B Hq R][D], wsML [pieces][B Hq R][2]); attn_decode16_combine merges them.
+#pragma once
+#include "attn_fwd16_common.h"
+
+namespace mfa {
+
+constexpr int DEC_KEY_TILE = 64;   // pieces are whole tiles of this many keys (MFA_DECODE_KEY_TILE)
+constexpr int DEC_STEP = 32;       // keys per wave step
+constexpr int DEC_WAVES = 4;
+constexpr float DEC_MINUS_HUGE = -3.402823466e+38f;
+
+struct DecodeArgs {
+  const char *q, *k, *v;
+  char *o;
+  float *l;                       // null: not stored
+  const uint32_t *lengths;
+  const int32_t *table;           // paged launches
+  int64_t tableStride;
+  int64_t ldq, hsq, bsq;          // elements
+  int64_t ldk, hsk, bsk, psk;
+  int64_t ldv, hsv, bsv, psv;
+  int64_t ldo, hso, bso;
+  int64_t lhs, lbs;
+  uint32_t R, G, Hq, Hkv, batches, column;
+  uint32_t paged, pageShift;      // pageSize = 1 << pageShift
+  uint32_t causal, outF32;
+  uint32_t pieces;
+  float scale2;                   // log2(e) / sqrt(D)
+  float *wsO, *wsML;
+};
+
+// keys [*begin, *end) of piece `piece` of `pieces` for a sequence of `length` keys: an equal share of the sequence's whole 64-key
+// tiles; only the last tile of the sequence may be partial.  Device and host (mfa_attention_decode_piece_range) run this one body.
+__host__ __device__ __forceinline__ void decode_piece_range(uint32_t length, uint32_t pieces, uint32_t piece, uint32_t *begin,
+                                                            uint32_t *end) {
+  const uint64_t tiles = ((uint64_t)length + DEC_KEY_TILE - 1) / DEC_KEY_TILE;
+  const uint64_t t0 = (uint64_t)piece * tiles / pieces, t1 = ((uint64_t)piece + 1) * tiles / pieces;
+  uint64_t b = t0 * DEC_KEY_TILE, e = t1 * DEC_KEY_TILE;
+  if (e > length) e = length;
+  if (b > e) b = e;
+  *begin = (uint32_t)b;
+  *end = (uint32_t)e;
+}
+
+template <int D> constexpr int decode16_lds_bytes() {
+  constexpr int images = DEC_WAVES * DEC_STEP * D * 2;
+  constexpr int merge = DEC_WAVES * 32 * (D + 4) * 4 + 2 * DEC_WAVES * 32 * 4;
+  return images > merge ? images : merge;
+}
+
+template <typename T, int D, bool SPLIT>
+__device__ __forceinline__ void decode16_body(const DecodeArgs &a) {
+  typedef Frag16<T> F;
+  typedef typename F::v8 v8;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NDB = D / 32, NKS = D / 16;
+  constexpr int CPR = D / 8;                   // 16-byte chunks per row
+  constexpr int RPI = 64 / CPR;                // V rows one wave-instruction covers
+  constexpr int NCH = DEC_STEP / RPI;          // V chunks per lane per step
+  constexpr int IMAGE = DEC_STEP * D * 2;      // bytes of a wave's V image
+  static_assert(16 % RPI == 0, "a lane's V rows of one instruction stay inside a 16-key group");
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, q = lane & 31, hi = lane >> 5;
+  const uint32_t piece = SPLIT ? blockIdx.x % a.pieces : 0u;
+  const uint32_t hb = SPLIT ? blockIdx.x / a.pieces : blockIdx.x;
+  const uint32_t kvh = hb % a.Hkv, batch = hb / a.Hkv;
+  const uint32_t R = a.R, M = a.G * R;
+  const uint32_t len = min(a.lengths[batch], a.column);
+  uint32_t begin = 0, end = len;
+  if constexpr (SPLIT) decode_piece_range(len, a.pieces, piece, &begin, &end);
+
+  // ---- the lane's packed query row: p = (query head within the group) R + row; columns >= M repeat the last one and are not stored
+  const uint32_t pc = min((uint32_t)q, M - 1);
+  const uint32_t qhead = kvh * a.G + pc / R, qrow = pc % R;
+  v8 qf[NKS];
+  {
+    const char *qp = a.q + ((int64_t)batch * a.bsq + (int64_t)qhead * a.hsq + (int64_t)qrow * a.ldq) * 2;
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + (16 * s + 8 * hi) * 2));
+  }
+  // keys this row sees: c < lim  (causal: c <= row + max(len - R, 0); always c < len, and inside this piece c < end)
+  uint32_t lim = end;
+  if (a.causal) lim = min(lim, qrow + (len > R ? len - R : 0u) + 1u);
+
+  // ---- addresses of a step's two 16-key groups (wave-uniform; element offsets from a.k / a.v)
+  const int64_t khead = (int64_t)kvh * a.hsk, vhead = (int64_t)kvh * a.hsv;
+  const uint32_t pageMask = (1u << a.pageShift) - 1u;
+  auto group_offsets = [&](uint32_t key0, int64_t (&ko)[2], int64_t (&vo)[2]) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const uint32_t key = key0 + 16u * u;
+      if (a.paged) {
+        // (entries past the sequence's last page are never read)
+        const int64_t page = key < end ? (int64_t)a.table[(int64_t)batch * a.tableStride + (key >> a.pageShift)] : 0;
+        const int64_t in = (int64_t)(key & pageMask);
+        ko[u] = page * a.psk + khead + in * a.ldk;
+        vo[u] = page * a.psv + vhead + in * a.ldv;
+      } else {
+        ko[u] = (int64_t)batch * a.bsk + khead + (int64_t)key * a.ldk;
+        vo[u] = (int64_t)batch * a.bsv + vhead + (int64_t)key * a.ldv;
+      }
+    }
+  };
+
+  // K: lane = key row q of the step, chunks 2t + hi (the A operand as it stands).  V: instruction i covers rows i RPI .. + RPI - 1 whole.
+  u32x4 kreg[NKS], vreg[NCH];
+  const int vrow0 = lane / CPR, vc = lane % CPR;
+  auto issue_loads = [&](uint32_t key0) {
+    int64_t ko[2], vo[2];
+    group_offsets(key0, ko, vo);
+    const bool kvalid = key0 + (uint32_t)q < end;
+    const char *kp = a.k + ((q >> 4 ? ko[1] : ko[0]) + (int64_t)(q & 15) * a.ldk + 8 * hi) * 2;
+#pragma unroll
+    for (int t = 0; t < NKS; ++t) {
+      u32x4 z = {0u, 0u, 0u, 0u};
+      if (kvalid) z = *reinterpret_cast<const u32x4 *>(kp + 32 * t);
+      kreg[t] = z;
+    }
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int row = i * RPI + vrow0;
+      u32x4 z = {0u, 0u, 0u, 0u};
+      if (key0 + (uint32_t)row < end)
+        z = *reinterpret_cast<const u32x4 *>(a.v + (vo[(i * RPI) >> 4] + (int64_t)(row & 15) * a.ldv + vc * 8) * 2);
+      vreg[i] = z;
+    }
+  };
+
+  f32x16 o[NDB];
+  float m = DEC_MINUS_HUGE, l = 0.f;
+#pragma unroll
+  for (int db = 0; db < NDB; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+
+  char *Vs = smem + wave * IMAGE;   // this wave's V image: [D/32][32 keys][32 d]
+  // tr read: lane n of a 16-lane group supplies row (n>>2), columns 4*(n&3)..+3 of a [4][16] block;
+  // group (lane>>4): bit0 = d half of the 32-wide d block, bit1 = hi   (dev/attn_fwd16.h)
+  const int n16 = lane & 15;
+  const int vtr_off = ((n16 >> 2) + 4 * hi) * 64 + (((lane >> 4) & 1) * 16 + 4 * (n16 & 3)) * 2;
+
+  uint32_t key0 = begin + (uint32_t)wave * DEC_STEP;
+  if (key0 < end) issue_loads(key0);
+  while (key0 < end) {
+    // ---- S^T = K Q^T: s[r] = key key0 + crow(r, hi), packed query row q
+    f32x16 s;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+    for (int t = 0; t < NKS; ++t) s = F::mfma(__builtin_bit_cast(v8, kreg[t]), qf[t], s);
+    // ---- V rows to the wave's image (the image's previous reads were issued before these writes: one wave, in order)
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int row = i * RPI + vrow0;
+      *reinterpret_cast<u32x4 *>(Vs + ((vc >> 2) * DEC_STEP + row) * 64 + (vc & 3) * 16) = vreg[i];
+    }
+    // ---- the registers are free: the next step's loads fly during the rest of this one
+    const uint32_t cur = key0;
+    key0 += DEC_WAVES * DEC_STEP;
+    if (key0 < end) issue_loads(key0);
+
+    // ---- online softmax over the visible keys only
+    float mx = DEC_MINUS_HUGE;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool visible = cur + (uint32_t)crow(r, hi) < lim;
+      s[r] = visible ? s[r] * a.scale2 : DEC_MINUS_HUGE;
+      mx = fmaxf(mx, s[r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    if (mx > m) {
+      const float corr = fast_exp2(m - mx);
+      m = mx;
+      l *= corr;
+#pragma unroll
+      for (int db = 0; db < NDB; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[db][r] *= corr;
+    }
+    float psum = 0.f;
+    v8 pf[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool visible = cur + (uint32_t)crow(r, hi) < lim;
+      const float p = visible ? fast_exp2(s[r] - m) : 0.f;   // replaced, never multiplied
+      psum += p;
+      pf[r >> 3][r & 7] = (T)p;
+    }
+    l += psum;
+
+    // ---- O^T += V^T P^T
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int db = 0; db < NDB; ++db) {
+        const char *vp = Vs + (db * DEC_STEP + 16 * u) * 64 + vtr_off;
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vp));
+        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vp + 8 * 64));
+        const s16x8 both = __builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
+        o[db] = F::mfma(__builtin_bit_cast(v8, both), pf[u], o[db]);
+      }
+  }
+
+  // ---- merge the four waves through LDS: m* = max m_w, weights exp2(m_w - m*), sums of l and O
+  constexpr int OLD = D + 4;
+  float *Om = reinterpret_cast<float *>(smem);                       // [waves][32][OLD]
+  float *ms = Om + DEC_WAVES * 32 * OLD, *ls = ms + DEC_WAVES * 32;   // [waves][32] each
+  const float l_tot = l + __shfl_xor(l, 32);
+  __syncthreads();   // every wave is done with its image
+  if (hi == 0) ms[wave * 32 + q] = m;
+  __syncthreads();
+  float mstar = ms[q];
+#pragma unroll
+  for (int w = 1; w < DEC_WAVES; ++w) mstar = fmaxf(mstar, ms[w * 32 + q]);
+  const float wgt = fast_exp2(m - mstar);   // (all of them -FLT_MAX: 1, on zeros)
+  {
+    float *orow = Om + (wave * 32 + q) * OLD;
+#pragma unroll
+    for (int db = 0; db < NDB; ++db)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)   // crow(4g + i, hi) = i + 8g + 4hi
+        *reinterpret_cast<float4 *>(orow + 32 * db + 8 * g + 4 * hi) =
+            make_float4(o[db][4 * g] * wgt, o[db][4 * g + 1] * wgt, o[db][4 * g + 2] * wgt, o[db][4 * g + 3] * wgt);
+    if (hi == 0) ls[wave * 32 + q] = l_tot * wgt;
+  }
+  __syncthreads();
+  constexpr int CL = D / 4;   // float4 columns per row
+  for (int idx = tid; idx < 32 * CL; idx += DEC_WAVES * 64) {
+    const uint32_t p = (uint32_t)idx / CL, c = (uint32_t)idx % CL;
+    if (p >= M) break;
+    float4 acc = *reinterpret_cast<const float4 *>(Om + p * OLD + 4 * c);
+    float lsum = ls[p], mrow = ms[p];
+#pragma unroll
+    for (int w = 1; w < DEC_WAVES; ++w) {
+      const float4 x = *reinterpret_cast<const float4 *>(Om + (w * 32 + p) * OLD + 4 * c);
+      acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+      lsum += ls[w * 32 + p];
+      mrow = fmaxf(mrow, ms[w * 32 + p]);
+    }
+    const uint32_t head = kvh * a.G + p / R, row = p % R;
+    if constexpr (SPLIT) {
+      const size_t slab = (((size_t)piece * a.batches + batch) * a.Hq + head) * R + row;
+      *reinterpret_cast<float4 *>(a.wsO + slab * D + 4 * c) = acc;
+      if (c == 0) *reinterpret_cast<float2 *>(a.wsML + slab * 2) = make_float2(mrow, lsum);
+    } else {
+      const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;   // a sequence of length 0: O = 0
+      acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
+      const int64_t at = (int64_t)batch * a.bso + (int64_t)head * a.hso + (int64_t)row * a.ldo + 4 * c;
+      if (a.outF32) *reinterpret_cast<float4 *>(a.o + at * 4) = acc;
+      else *reinterpret_cast<u32x2 *>(a.o + at * 2) = u32x2{pack16<T>(acc.x, acc.y), pack16<T>(acc.z, acc.w)};
+      if (c == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)head * a.lhs + row] = lsum > 0.f ? mrow + log2f(lsum) : DEC_MINUS_HUGE;
+    }
+  }
+}
+
+// Merge the pieces (the online-softmax merge of attn_fwd_combine, attn_fwd16_v3.h, across pieces).  One wave per query row: lane s holds
+// (m_s, l_s) of piece s (pieces <= 64); for O the wave is D / 4 column lanes x 64 / (D / 4) piece groups.  A piece without keys has
+// l = 0 and m = -FLT_MAX: its weight is exp2(-huge) = 0 beside any piece that saw a key, and its slab holds zeros.
+template <typename T, int D>
+__device__ __forceinline__ void decode16_combine_body(const DecodeArgs &a) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t R = a.R, S = a.pieces;
+  const uint64_t rows = (uint64_t)a.batches * a.Hq * R;
+  const uint64_t rowid = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (rowid >= rows) return;
+  const uint32_t row = (uint32_t)(rowid % R), bh = (uint32_t)(rowid / R);
+  const uint32_t head = bh % a.Hq, batch = bh / a.Hq;
+  float ms = DEC_MINUS_HUGE, ls = 0.f;
+  if ((uint32_t)lane < S) {
+    const float2 ml = *reinterpret_cast<const float2 *>(a.wsML + ((uint64_t)lane * rows + rowid) * 2);
+    ms = ml.x; ls = ml.y;
+  }
+  float mstar = ms;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) mstar = fmaxf(mstar, __shfl_xor(mstar, off, 64));
+  const float w = ((uint32_t)lane < S && ls > 0.f) ? fast_exp2(ms - mstar) : 0.f;
+  float lstar = w * ls;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) lstar += __shfl_xor(lstar, off, 64);
+  constexpr uint32_t CL = D / 4, GR = 64 / CL;
+  const uint32_t c = (uint32_t)lane % CL, g = (uint32_t)lane / CL;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (uint32_t s0 = 0; s0 < S; s0 += GR) {
+    const uint32_t s_ = s0 + g;
+    const float ws = __shfl(w, (int)(s_ < 64 ? s_ : 63), 64);   // (every lane takes part in the exchange)
+    if (s_ < S && ws > 0.f) {
+      const float4 x = *reinterpret_cast<const float4 *>(a.wsO + ((uint64_t)s_ * rows + rowid) * D + c * 4);
+      acc.x += ws * x.x; acc.y += ws * x.y; acc.z += ws * x.z; acc.w += ws * x.w;
+    }
+  }
+#pragma unroll
+  for (uint32_t off = CL; off < 64; off <<= 1) {
+    acc.x += __shfl_xor(acc.x, (int)off, 64); acc.y += __shfl_xor(acc.y, (int)off, 64);
+    acc.z += __shfl_xor(acc.z, (int)off, 64); acc.w += __shfl_xor(acc.w, (int)off, 64);
+  }
+  const float inv = lstar > 0.f ? 1.0f / lstar : 0.f;
+  if (g == 0) {
+    acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
+    const int64_t at = (int64_t)batch * a.bso + (int64_t)head * a.hso + (int64_t)row * a.ldo + 4 * c;
+    if (a.outF32) *reinterpret_cast<float4 *>(a.o + at * 4) = acc;
+    else *reinterpret_cast<u32x2 *>(a.o + at * 2) = u32x2{pack16<T>(acc.x, acc.y), pack16<T>(acc.z, acc.w)};
+  }
+  if (lane == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)head * a.lhs + row] = lstar > 0.f ? mstar + log2f(lstar) : DEC_MINUS_HUGE;
+}
+
+} // namespace mfa

@@ -8,6 +8,9 @@ reference does not have -- only its tests call the kernels, Tests/FlashAttention
     from metal_flash_attention_amd.torch_binding import flash_attention_op   # the same through torch.library ops
     f = torch.compile(lambda q, k, v: flash_attention_op(q, k, v, causal=True), fullgraph=True)
 
+    from metal_flash_attention_amd.torch_binding import flash_decode          # token-by-token generation over a KV cache
+    o = flash_decode(q, k_cache, v_cache, cache_lengths)                      # q [B, H, R, D], R = 1 or a few; forward only
+
 forward  = AttentionKernelType.forward           -> O (the inputs' dtype, fused cast), L (fp32), both saved
 backward = AttentionKernelType.backwardQuery     -> D, dQ      (needs O, dO, L)
            AttentionKernelType.backwardKeyValue  -> dK, dV     (needs L, D)
@@ -17,11 +20,11 @@ library or a CPU tensor raises).
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDescriptor, AttentionKernel, AttentionKernelType, AttentionOperand as Op,
+from .attention import (AttentionDecode, AttentionDescriptor, AttentionKernel, AttentionKernelType, AttentionOperand as Op,
                         GEMMOperandPrecision as P)
 
 _KERNELS: Dict[Tuple, AttentionKernel] = {}
@@ -280,3 +283,106 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
     folded into the 16-bit operand once instead of being applied in fp32 per score (2-4 % faster; |dL| ~ 2e-3 with bf16),
     L is kept in FP16 and D in BF16 between forward and backward."""
     return _FlashAttention.apply(q, k, v, causal, q_lengths, k_lengths, block_mask, fast_scale)
+
+
+# ---- decode attention over a KV cache (include/mfa_decode.h): forward only, per-sequence lengths on the device, contiguous or paged
+_DECODERS: Dict[Tuple, AttentionDecode] = {}
+
+
+def _cache_strides(t, paged):
+    """(leadingDimension, headStride, batchStride) of a [B or pages, Hkv, keys, D] cache view, passed through as they are"""
+    return (int(t.stride(2)) if t.shape[2] > 1 else int(t.shape[3]), int(t.stride(1)), 0 if paged else int(t.stride(0)))
+
+
+def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal):
+    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
+        raise RuntimeError("flash_decode: tensors must live on the GPU (there is no CPU path)")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise TypeError("flash_decode: q and the caches must share one of bfloat16 / float16")
+    paged = block_table is not None
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[3] != k_cache.shape[3] or k_cache.shape[1] == 0 or \
+            q.shape[1] % k_cache.shape[1] != 0 or (not paged and k_cache.shape[0] != q.shape[0]):
+        raise ValueError("flash_decode: expected q [B, H, R, D] and caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) with H a "
+                         f"multiple of Hkv (got q {tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)})")
+    B, H, R, D = q.shape
+    Hkv = k_cache.shape[1]
+    if cache_lengths.shape != (B,) or cache_lengths.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"flash_decode: cache_lengths must be [B] = [{B}] int32 or int64 (got {tuple(cache_lengths.shape)}, {cache_lengths.dtype})")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
+            raise ValueError(f"flash_decode: {name} must have a contiguous last dimension (a cache is never copied)")
+    kw = {}
+    if paged:
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
+                not block_table.is_cuda:
+            raise ValueError(f"flash_decode: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
+                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
+        page = int(k_cache.shape[2])
+        column = page * int(block_table.shape[1])
+        kw = dict(pageSize=page, blockTable=block_table, blockTableStride=int(block_table.stride(0)),
+                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
+    else:
+        column = int(k_cache.shape[2])
+    q = q if q.stride(3) == 1 and all(st >= 0 for st in q.stride()) else q.contiguous()
+    lengths = cache_lengths.to(torch.int32)   # (no copy when it already is; stays on the device)
+    o = torch.empty((B, H, R, D), dtype=q.dtype, device=q.device)
+    l = torch.empty((B, H, R), dtype=torch.float32, device=q.device)
+    key = (q.dtype, D)
+    dec = _DECODERS.get(key)
+    if dec is None:
+        dec = _DECODERS[key] = AttentionDecode(D, P.BF16 if q.dtype == torch.bfloat16 else P.FP16)
+    kw.update(rows=R, column=column, heads=H, batches=B, headsPerKeyValue=H // Hkv, causal=bool(causal), cacheLengths=lengths,
+              strides=dict(Q=(int(q.stride(2)) if R > 1 else D, int(q.stride(1)), int(q.stride(0))),
+                           K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
+    need = dec.workspaceSize(**kw)
+    ws = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
+    with torch.cuda.device(q.device):
+        dec.dispatch(q, k_cache, v_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, workspace=ws, **kw)
+    return o, l
+
+
+def _register_decode_op():
+    if not hasattr(torch.library, "custom_op"):
+        return False
+    try:
+        torch.ops.mfa.attention_decode  # noqa: B018 -- AttributeError when the op is not defined yet
+        return True
+    except (AttributeError, RuntimeError):
+        pass
+
+    @torch.library.custom_op("mfa::attention_decode", mutates_args=(), device_types="cuda")
+    def _op_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                   block_table: Optional[torch.Tensor], causal: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+        return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)
+
+    @_op_decode.register_fake
+    def _op_decode_fake(q, k_cache, v_cache, cache_lengths, block_table, causal):
+        B, H, R, D = q.shape
+        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
+
+    return True
+
+
+_HAVE_DECODE_OP = _register_decode_op()
+
+
+def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                 block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False):
+    """Attention of the R new rows of every sequence (q [B, H, R, D]; R = 1, or a few speculative tokens; G R <= 32 with G = H / Hkv)
+    against its KV cache.  cache_lengths [B] (GPU, int32): valid keys per sequence INCLUDING the R new tokens, which the caller has
+    already written into the cache; with `causal` row r sees key c iff c <= r + max(len - R, 0).  Caches: [B, Hkv, C, D], or any view
+    of that shape with a contiguous last dimension (a token-major [B, C, Hkv, D] cache permuted, slices of a fused allocation:
+    strides are passed through, nothing is copied); with block_table [B, n] int32 the caches are page pools [pages, Hkv, pageSize, D]
+    and entry (b, i) names the page of keys i pageSize .. of sequence b.  Forward only.  return_lse: also L [B, H, R] fp32 in natural
+    units (log of the softmax denominator, the scale included), to merge results across cache shards.  A sequence of length 0 gets
+    O = 0.  Goes through the torch.library op `mfa::attention_decode` where torch has custom ops, so it traces under torch.compile."""
+    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
+        raise RuntimeError("flash_decode: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, k_cache, v_cache):
+        if t.requires_grad:
+            raise RuntimeError("flash_decode is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
+    if _HAVE_DECODE_OP:
+        o, l = torch.ops.mfa.attention_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)
+    else:
+        o, l = _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)
+    return (o, l * 0.6931471805599453) if return_lse else o
