@@ -6,15 +6,20 @@ No CPU / PyTorch compute fallback exists: importing works without the library, u
 from ._abi import LIB_PATH, MFAError  # noqa: F401
 from .attention import (  # noqa: F401
     AttentionDecode,
+    AttentionDecodeFP8,
     AttentionDescriptor,
     AttentionKernel,
     AttentionKernelDescriptor,
     AttentionKernelType,
     AttentionOperand,
     GEMMOperandPrecision,
+    KVCacheAppend,
+    KVCachePrecision,
     deviceCount,
     deviceName,
+    dequantizeE4M3,
     parameterFile,
+    quantizeE4M3,
     resetParameterFiles,
     selectParameterRow,
     setParameterFile,

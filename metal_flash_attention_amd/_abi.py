@@ -188,6 +188,39 @@ DECODE_SYMBOLS = [
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
 ]
 
+class mfa_kv_append_params(ctypes.Structure):   # include/mfa_kvcache.h
+    _fields_ = [
+        ("rows", ctypes.c_uint32), ("heads", ctypes.c_uint32), ("batches", ctypes.c_uint32), ("column", ctypes.c_uint32),
+        ("headDimension", ctypes.c_uint16), ("precision", ctypes.c_uint8), ("cachePrecision", ctypes.c_uint8),
+        ("pageSize", ctypes.c_uint32),
+        ("cacheLengths", ctypes.c_void_p), ("blockTable", ctypes.c_void_p), ("blockTableStride", ctypes.c_int64),
+        ("leadingDimension", ctypes.c_int64 * 4), ("headStride", ctypes.c_int64 * 4), ("batchStride", ctypes.c_int64 * 4),
+        ("pageStride", ctypes.c_int64 * 2),
+        ("keyScale", ctypes.c_void_p), ("valueScale", ctypes.c_void_p),
+    ]
+
+
+class mfa_kv_quant(ctypes.Structure):   # include/mfa_kvcache.h
+    _fields_ = [("cachePrecision", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("keyScale", ctypes.c_void_p), ("valueScale", ctypes.c_void_p)]
+
+
+MFA_KV_E4M3, MFA_KV_E5M2 = 16, 17
+_QUANT = ctypes.POINTER(mfa_kv_quant)
+
+KVCACHE_SYMBOLS = [
+    ("mfa_kv_quantize_e4m3", ctypes.c_uint8, [ctypes.c_float, ctypes.c_float]),
+    ("mfa_kv_dequantize_e4m3", ctypes.c_float, [ctypes.c_uint8]),
+    ("mfa_kv_append_params_init", None, [ctypes.POINTER(mfa_kv_append_params)]),
+    ("mfa_kv_cache_append_launch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(mfa_kv_append_params), ctypes.c_void_p]),
+    ("mfa_kv_quant_init", None, [_QUANT]),
+    ("mfa_attention_decode_fp8_workspace_size", ctypes.c_int, [ctypes.POINTER(mfa_decode_params), _QUANT, ctypes.POINTER(ctypes.c_uint64)]),
+    ("mfa_attention_decode_fp8_launch", ctypes.c_int, _DECODE_BUFS + [ctypes.POINTER(mfa_decode_params), _QUANT, ctypes.c_void_p]),
+    ("mfa_attention_decode_fp8_launch_form", ctypes.c_int, [ctypes.POINTER(mfa_decode_params), _QUANT, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_decode_fp8_time", ctypes.c_int,
+     _DECODE_BUFS + [ctypes.POINTER(mfa_decode_params), _QUANT, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+]
+
 SYMBOLS = [
     ("mfa_precision_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mfa_precision_size", ctypes.c_int, [ctypes.c_int]),
@@ -263,7 +296,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

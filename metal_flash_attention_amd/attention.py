@@ -485,3 +485,109 @@ class AttentionDecode:
         b, e = ctypes.c_uint32(0), ctypes.c_uint32(0)
         check(lib().mfa_attention_decode_piece_range(int(length), int(pieces), int(piece), ctypes.byref(b), ctypes.byref(e)))
         return int(b.value), int(e.value)
+
+
+class KVCachePrecision(enum.IntEnum):
+    """precision codes of a KV cache beside the 16-bit types (include/mfa_kvcache.h)"""
+    E4M3 = _abi.MFA_KV_E4M3
+    E5M2 = _abi.MFA_KV_E5M2   # recognised only to be refused
+
+
+class AttentionDecodeFP8(AttentionDecode):
+    """Decode attention over an FP8 (OCP e4m3) KV cache (include/mfa_kvcache.h): AttentionDecode's methods and arguments -- the K / V
+    strides count bytes -- plus keyScale / valueScale (device FP32 [heads // headsPerKeyValue], None = 1.0): a cache byte of K / V
+    head j stands for scale[j] x e4m3(byte).  `precision` is the 16-bit type of Q."""
+
+    def __init__(self, headDimension: int, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16,
+                 outputPrecision: Optional[GEMMOperandPrecision] = None, cachePrecision: int = KVCachePrecision.E4M3):
+        super().__init__(headDimension, precision, outputPrecision)
+        self.cachePrecision = int(cachePrecision)
+
+    def _quant(self, shape):
+        quant = _abi.mfa_kv_quant()
+        lib().mfa_kv_quant_init(ctypes.byref(quant))
+        quant.cachePrecision = self.cachePrecision
+        keep = (shape.pop("keyScale", None), shape.pop("valueScale", None))
+        quant.keyScale, quant.valueScale = _pointer(keep[0]), _pointer(keep[1])
+        return quant, keep
+
+    def workspaceSize(self, **shape) -> int:
+        quant, _scales = self._quant(shape)
+        p, _keep = self._params(**shape)
+        out = ctypes.c_uint64(0)
+        check(lib().mfa_attention_decode_fp8_workspace_size(ctypes.byref(p), ctypes.byref(quant), ctypes.byref(out)))
+        return int(out.value)
+
+    def launchForm(self, **shape) -> str:
+        quant, _scales = self._quant(shape)
+        p, _keep = self._params(**shape)
+        out = ctypes.create_string_buffer(512)
+        check(lib().mfa_attention_decode_fp8_launch_form(ctypes.byref(p), ctypes.byref(quant), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        quant, _scales = self._quant(shape)
+        p, _keep = self._params(**shape)
+        check(lib().mfa_attention_decode_fp8_launch(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
+                                                    ctypes.byref(quant), ctypes.c_void_p(stream or 0)))
+
+    def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        quant, _scales = self._quant(shape)
+        p, _keep = self._params(**shape)
+        ms = ctypes.c_float(0.0)
+        check(lib().mfa_attention_decode_fp8_time(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
+                                                  ctypes.byref(quant), ctypes.c_void_p(stream or 0), int(warmup), int(iterations),
+                                                  ctypes.byref(ms)))
+        return float(ms.value)
+
+
+class KVCacheAppend:
+    """Appends the `rows` new key / value rows of every sequence to a KV cache (include/mfa_kvcache.h), quantising them to e4m3 when
+    the cache is FP8 (cachePrecision=KVCachePrecision.E4M3) or copying their bits when it is the rows' 16-bit type (None).
+
+        append = KVCacheAppend(128, GEMMOperandPrecision.BF16, KVCachePrecision.E4M3)
+        append.dispatch(k_new, v_new, k_cache, v_cache, rows=1, heads=8, batches=B, column=C, cacheLengths=lengths, keyScale=ks, valueScale=vs)
+
+    cacheLengths already includes the new rows: row r of sequence b goes to key cacheLengths[b] - rows + r.  `strides`: operand name
+    (kNew, vNew, kCache, vCache) -> (leadingDimension, headStride, batchStride) in elements; an operand left out is packed
+    ([batch][head][row or key][D]).  Paged caches: pageSize, blockTable, blockTableStride and pageStrides=(K, V)."""
+
+    OPERANDS = ("kNew", "vNew", "kCache", "vCache")
+
+    def __init__(self, headDimension: int, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16, cachePrecision: Optional[int] = None):
+        self.headDimension = int(headDimension)
+        self.precision = GEMMOperandPrecision(precision)
+        self.cachePrecision = int(self.precision) if cachePrecision is None else int(cachePrecision)
+
+    def _params(self, *, rows: int, heads: int, batches: int = 1, column: int = 0, cacheLengths=None, pageSize: int = 0, blockTable=None,
+                blockTableStride: int = 0, strides: Optional[Mapping] = None, pageStrides: Optional[Sequence[int]] = None,
+                keyScale=None, valueScale=None):
+        p = _abi.mfa_kv_append_params()
+        lib().mfa_kv_append_params_init(ctypes.byref(p))
+        p.rows, p.heads, p.batches, p.column = int(rows), int(heads), int(batches), int(column)
+        p.headDimension, p.precision, p.cachePrecision = self.headDimension, int(self.precision), self.cachePrecision
+        p.pageSize = int(pageSize)
+        p.cacheLengths, p.blockTable, p.blockTableStride = _pointer(cacheLengths), _pointer(blockTable), int(blockTableStride)
+        D = self.headDimension
+        for i, name in enumerate(self.OPERANDS):
+            seq = int(rows) if i < 2 else (int(pageSize) or int(column))
+            ld, hs, bs = (strides or {}).get(name, (D, seq * D, int(heads) * seq * D))
+            p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
+        if pageStrides is not None:
+            p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
+        p.keyScale, p.valueScale = _pointer(keyScale), _pointer(valueScale)
+        return p
+
+    def dispatch(self, kNew, vNew, kCache, vCache, *, stream: Optional[int] = None, **shape) -> None:
+        p = self._params(**shape)
+        check(lib().mfa_kv_cache_append_launch(_pointer(kNew), _pointer(vNew), _pointer(kCache), _pointer(vCache), ctypes.byref(p),
+                                               ctypes.c_void_p(stream or 0)))
+
+
+def quantizeE4M3(x: float, scale: float = 1.0) -> int:
+    """the cache byte of `x` under `scale`: mfa_kv_quantize_e4m3, the contract of writer and reader"""
+    return int(lib().mfa_kv_quantize_e4m3(float(x), float(scale)))
+
+
+def dequantizeE4M3(byte: int) -> float:
+    return float(lib().mfa_kv_dequantize_e4m3(int(byte)))

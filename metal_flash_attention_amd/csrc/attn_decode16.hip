@@ -9,6 +9,7 @@
 
 #include "../../include/mfa_decode.h"
 #include "attn_decode16.h"
+#include "attn_decode_plan.h"
 #include "launchers.h"
 #include "mfa_internal.h"
 
@@ -183,6 +184,24 @@ hipError_t run(const DecodePlan &plan, hipStream_t stream) {
 }
 
 } // namespace
+
+namespace mfa {
+
+mfa_status decode_host_plan(const mfa_decode_params *params, DecodeHostPlan *out) {
+  DecodePlan plan;
+  const mfa_status st = prepare(params, &plan);
+  if (st != MFA_OK) return st;
+  out->args = plan.args;
+  out->pieces = plan.pieces; out->planned = plan.planned; out->blocks = plan.blocks;
+  out->lds = plan.set->lds;
+  out->combine = plan.set->combine;
+  out->combineName = plan.set->combineName;
+  return MFA_OK;
+}
+
+uint64_t decode_workspace_bytes(uint32_t pieces, const mfa_decode_params *params) { return pieces_workspace_bytes(pieces, params); }
+
+} // namespace mfa
 
 extern "C" {
 

@@ -1,0 +1,194 @@
+// kv_cache_append.hip -- appends the R new key / value rows of every sequence to a KV cache (include/mfa_kvcache.h): an elementwise
+// kernel; 16-byte loads of the 16-bit source rows, 8-byte stores into an e4m3 cache (quantised by kv_quantize_e4m3, the exported
+// contract) or 16-byte stores into a 16-bit cache (bits copied).  One workgroup per (sequence, new row): the row's position and, for a
+// paged cache, its one block-table entry are workgroup-uniform.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+
+#include "../../include/mfa_kvcache.h"
+#include "attn_common.h"
+#include "kv_e4m3.h"
+#include "launchers.h"
+#include "mfa_internal.h"
+
+using namespace mfa;
+
+namespace {
+
+struct AppendArgs {
+  const char *src[2];             // kNew, vNew
+  char *dst[2];                   // kCache, vCache
+  const float *scale[2];
+  const uint32_t *lengths;
+  const int32_t *table;
+  int64_t tableStride;
+  int64_t lds[2], hss[2], bss[2]; // sources; elements
+  int64_t ldc[2], hsc[2], bsc[2], psc[2];
+  uint32_t R, H, column;
+  uint32_t paged, pageShift;
+};
+
+template <typename T> __device__ __forceinline__ float to_float(uint16_t bits);
+template <> __device__ __forceinline__ float to_float<__bf16>(uint16_t bits) { return __builtin_bit_cast(float, (uint32_t)bits << 16); }
+template <> __device__ __forceinline__ float to_float<_Float16>(uint16_t bits) { return (float)__builtin_bit_cast(_Float16, bits); }
+
+template <typename T, int D, bool FP8>
+__device__ __forceinline__ void kv_append_body(const AppendArgs &a) {
+  constexpr uint32_t CPR = D / 8;   // 16-byte source chunks per row
+  const uint32_t batch = blockIdx.x / a.R, row = blockIdx.x % a.R;
+  const int64_t pos = (int64_t)a.lengths[batch] - (int64_t)a.R + (int64_t)row;
+  if (pos < 0) return;
+  int64_t base[2];
+  if (a.paged) {
+    const int64_t pageIndex = pos >> a.pageShift;
+    if (pageIndex >= a.tableStride) return;
+    const int64_t page = (int64_t)a.table[(int64_t)batch * a.tableStride + pageIndex];
+    if (page < 0) return;
+    const int64_t in = pos & (((int64_t)1 << a.pageShift) - 1);
+#pragma unroll
+    for (int o = 0; o < 2; ++o) base[o] = page * a.psc[o] + in * a.ldc[o];
+  } else {
+    if (pos >= (int64_t)a.column) return;
+#pragma unroll
+    for (int o = 0; o < 2; ++o) base[o] = (int64_t)batch * a.bsc[o] + pos * a.ldc[o];
+  }
+  const uint32_t items = 2u * a.H * CPR;
+  for (uint32_t idx = threadIdx.x; idx < items; idx += blockDim.x) {
+    const uint32_t c = idx % CPR, head = (idx / CPR) % a.H, o = idx / (CPR * a.H);
+    const char *sp = a.src[o] + ((int64_t)batch * a.bss[o] + (int64_t)head * a.hss[o] + (int64_t)row * a.lds[o] + 8 * c) * 2;
+    const u32x4 x = *reinterpret_cast<const u32x4 *>(sp);
+    const int64_t at = base[o] + (int64_t)head * a.hsc[o] + 8 * c;
+    if constexpr (FP8) {
+      const float scale = a.scale[o] ? a.scale[o][head] : 1.0f;
+      u32x2 out = {0u, 0u};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const uint16_t bits = (uint16_t)(x[i >> 1] >> (16 * (i & 1)));
+        out[i >> 2] |= (uint32_t)kv_quantize_e4m3(to_float<T>(bits), scale) << (8 * (i & 3));
+      }
+      *reinterpret_cast<u32x2 *>(a.dst[o] + at) = out;
+    } else {
+      *reinterpret_cast<u32x4 *>(a.dst[o] + at * 2) = x;
+    }
+  }
+}
+
+} // namespace
+
+#define MFA_KV_APPEND_KERNELS(TN, T, D)                                                                                               \
+  extern "C" __global__ __launch_bounds__(256) void kv_cache_append_d##D##_##TN##_e4m3(const AppendArgs a) {                          \
+    kv_append_body<T, D, true>(a);                                                                                                    \
+  }
+MFA_KV_APPEND_KERNELS(bf16, __bf16, 64)
+MFA_KV_APPEND_KERNELS(bf16, __bf16, 128)
+MFA_KV_APPEND_KERNELS(f16, _Float16, 64)
+MFA_KV_APPEND_KERNELS(f16, _Float16, 128)
+// a 16-bit cache takes the bits as they are: one kernel per head dimension serves both types
+extern "C" __global__ __launch_bounds__(256) void kv_cache_append_d64_copy16(const AppendArgs a) { kv_append_body<__bf16, 64, false>(a); }
+extern "C" __global__ __launch_bounds__(256) void kv_cache_append_d128_copy16(const AppendArgs a) { kv_append_body<__bf16, 128, false>(a); }
+
+namespace {
+
+typedef void (*AppendKernel)(const AppendArgs);
+bool multiple_of(int64_t x, int64_t n) { return x % n == 0; }
+
+mfa_status prepare(const mfa_kv_append_params *p, AppendArgs *a, AppendKernel *kernel, const char **name) {
+  if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (p->precision != MFA_BF16 && p->precision != MFA_FP16)
+    return fail(p->precision == MFA_FP32 ? MFA_ERR_UNSUPPORTED : MFA_ERR_INVALID_ARGUMENT,
+                "the new key / value rows must be 16-bit (precision MFA_FP16 or MFA_BF16)");
+  if (p->cachePrecision == MFA_KV_E5M2)
+    return fail(MFA_ERR_UNSUPPORTED, "an FP8 KV cache is e4m3 (MFA_KV_E4M3, OCP e4m3fn); e5m2 caches have no kernel");
+  const bool fp8 = p->cachePrecision == MFA_KV_E4M3;
+  if (!fp8 && p->cachePrecision != p->precision)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "cachePrecision must be the rows' 16-bit type (`precision`) or MFA_KV_E4M3");
+  if (p->headDimension != 64 && p->headDimension != 128)
+    return fail(MFA_ERR_UNSUPPORTED, "the KV cache append is compiled for head dimensions 64 and 128, not " + std::to_string(p->headDimension));
+  if (p->rows == 0 || p->heads == 0 || p->batches == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "rows, heads and batches must be non-zero");
+  if ((uint64_t)p->rows * p->batches > 0x7FFFFFFFull) return fail(MFA_ERR_INVALID_ARGUMENT, "rows x batches must fit a grid of 2^31 - 1 workgroups");
+  if (!p->cacheLengths) return fail(MFA_ERR_INVALID_ARGUMENT, "cacheLengths is required (device array of `batches` uint32)");
+  if (!fp8 && (p->keyScale || p->valueScale))
+    return fail(MFA_ERR_INVALID_ARGUMENT, "keyScale / valueScale go with an e4m3 cache (MFA_KV_E4M3); a 16-bit cache takes the rows' bits unscaled");
+  uint32_t pageShift = 0;
+  if (p->pageSize) {
+    if (p->pageSize < 16 || p->pageSize > 1024 || (p->pageSize & (p->pageSize - 1)))
+      return fail(MFA_ERR_INVALID_ARGUMENT, "pageSize must be a power of two from 16 to 1024 (or 0: contiguous), not " + std::to_string(p->pageSize));
+    if (!p->blockTable) return fail(MFA_ERR_INVALID_ARGUMENT, "a paged launch (pageSize != 0) needs blockTable");
+    if (p->blockTableStride <= 0) return fail(MFA_ERR_INVALID_ARGUMENT, "blockTableStride must be positive: the pages a sequence may name");
+    while ((1u << pageShift) < p->pageSize) ++pageShift;
+  } else if (p->column == 0) {
+    return fail(MFA_ERR_INVALID_ARGUMENT, "column (the capacity of a contiguous cache) must be non-zero");
+  }
+  static const char *names[4] = {"kNew", "vNew", "kCache", "vCache"};
+  for (int i = 0; i < 4; ++i) {
+    const bool cache = i >= 2;
+    const int64_t need = (cache && fp8) ? 16 : 8;
+    if (p->leadingDimension[i] < (int64_t)p->headDimension)
+      return fail(MFA_ERR_INVALID_ARGUMENT, std::string("leadingDimension of ") + names[i] + " is smaller than the head dimension");
+    bool ok = multiple_of(p->leadingDimension[i], need) && multiple_of(p->headStride[i], need);
+    if (cache && p->pageSize) ok = ok && multiple_of(p->pageStride[i - 2], need);
+    else ok = ok && multiple_of(p->batchStride[i], need);
+    if (!ok)
+      return fail(MFA_ERR_INVALID_ARGUMENT, std::string("strides of ") + names[i] + " must be multiples of " + std::to_string(need) +
+                                                " elements (16-byte rows of 16-bit operands; an e4m3 cache: multiples of 16 elements)");
+  }
+  std::memset(a, 0, sizeof(*a));
+  a->scale[0] = p->keyScale; a->scale[1] = p->valueScale;
+  a->lengths = p->cacheLengths;
+  a->table = p->blockTable;
+  a->tableStride = p->blockTableStride;
+  for (int o = 0; o < 2; ++o) {
+    a->lds[o] = p->leadingDimension[o]; a->hss[o] = p->headStride[o]; a->bss[o] = p->batchStride[o];
+    a->ldc[o] = p->leadingDimension[2 + o]; a->hsc[o] = p->headStride[2 + o]; a->bsc[o] = p->batchStride[2 + o];
+    a->psc[o] = p->pageStride[o];
+  }
+  a->R = p->rows; a->H = p->heads; a->column = p->column;
+  a->paged = p->pageSize != 0; a->pageShift = pageShift;
+  const bool d128 = p->headDimension == 128, bf = p->precision == MFA_BF16;
+  if (!fp8) {
+    *kernel = d128 ? kv_cache_append_d128_copy16 : kv_cache_append_d64_copy16;
+    *name = d128 ? "kv_cache_append_d128_copy16" : "kv_cache_append_d64_copy16";
+  } else if (bf) {
+    *kernel = d128 ? kv_cache_append_d128_bf16_e4m3 : kv_cache_append_d64_bf16_e4m3;
+    *name = d128 ? "kv_cache_append_d128_bf16_e4m3" : "kv_cache_append_d64_bf16_e4m3";
+  } else {
+    *kernel = d128 ? kv_cache_append_d128_f16_e4m3 : kv_cache_append_d64_f16_e4m3;
+    *name = d128 ? "kv_cache_append_d128_f16_e4m3" : "kv_cache_append_d64_f16_e4m3";
+  }
+  return MFA_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+uint8_t mfa_kv_quantize_e4m3(float x, float scale) { return kv_quantize_e4m3(x, scale); }
+float mfa_kv_dequantize_e4m3(uint8_t byte) { return kv_dequantize_e4m3(byte); }
+
+void mfa_kv_append_params_init(mfa_kv_append_params *params) {
+  if (!params) return;
+  std::memset(params, 0, sizeof(*params));
+  params->precision = params->cachePrecision = MFA_BF16;
+}
+
+mfa_status mfa_kv_cache_append_launch(const void *kNew, const void *vNew, void *kCache, void *vCache, const mfa_kv_append_params *params,
+                                      void *stream) {
+  AppendArgs a;
+  AppendKernel kernel = nullptr;
+  const char *name = "";
+  const mfa_status st = prepare(params, &a, &kernel, &name);
+  if (st != MFA_OK) return st;
+  if (!kNew || !vNew || !kCache || !vCache) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if ((uintptr_t)kNew % 16 || (uintptr_t)vNew % 16 || (uintptr_t)kCache % 16 || (uintptr_t)vCache % 16)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "kNew, vNew, kCache and vCache must be 16-byte aligned");
+  a.src[0] = (const char *)kNew; a.src[1] = (const char *)vNew;
+  a.dst[0] = (char *)kCache; a.dst[1] = (char *)vCache;
+  hipError_t err = launch_kernel(kernel, dim3(params->batches * params->rows), dim3(256), 0, (hipStream_t)stream, a);
+  if (err == hipSuccess) err = hipGetLastError();
+  if (err != hipSuccess) return fail(MFA_ERR_HIP, std::string(name) + ": " + hipGetErrorName(err) + " (" + hipGetErrorString(err) + ")");
+  return MFA_OK;
+}
+
+} // extern "C"

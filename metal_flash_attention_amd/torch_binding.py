@@ -11,6 +11,10 @@ reference does not have -- only its tests call the kernels, Tests/FlashAttention
     from metal_flash_attention_amd.torch_binding import flash_decode          # token-by-token generation over a KV cache
     o = flash_decode(q, k_cache, v_cache, cache_lengths)                      # q [B, H, R, D], R = 1 or a few; forward only
 
+    from metal_flash_attention_amd.torch_binding import kv_cache_append       # write the new tokens' K / V rows, in place
+    kv_cache_append(k_new, v_new, k_cache, v_cache, cache_lengths, k_scale=ks, v_scale=vs)   # float8_e4m3fn or 16-bit caches
+    o = flash_decode(q, k_cache, v_cache, cache_lengths, k_scale=ks, v_scale=vs)
+
 forward  = AttentionKernelType.forward           -> O (the inputs' dtype, fused cast), L (fp32), both saved
 backward = AttentionKernelType.backwardQuery     -> D, dQ      (needs O, dO, L)
            AttentionKernelType.backwardKeyValue  -> dK, dV     (needs L, D)
@@ -24,8 +28,8 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDescriptor, AttentionKernel, AttentionKernelType, AttentionOperand as Op,
-                        GEMMOperandPrecision as P)
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+                        AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCachePrecision)
 
 _KERNELS: Dict[Tuple, AttentionKernel] = {}
 
@@ -294,10 +298,16 @@ def _cache_strides(t, paged):
     return (int(t.stride(2)) if t.shape[2] > 1 else int(t.shape[3]), int(t.stride(1)), 0 if paged else int(t.stride(0)))
 
 
-def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal):
+def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None):
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
         raise RuntimeError("flash_decode: tensors must live on the GPU (there is no CPU path)")
-    if q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+    if fp8:
+        if k_cache.dtype != v_cache.dtype or k_cache.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"flash_decode: an FP8 KV cache is torch.float8_e4m3fn for both K and V (got {k_cache.dtype}, {v_cache.dtype}); "
+                            "e5m2 and fnuz caches have no kernel")
+        if q.dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError("flash_decode: q must be bfloat16 or float16")
+    elif q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise TypeError("flash_decode: q and the caches must share one of bfloat16 / float16")
     paged = block_table is not None
     if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[3] != k_cache.shape[3] or k_cache.shape[1] == 0 or \
@@ -327,10 +337,13 @@ def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal):
     lengths = cache_lengths.to(torch.int32)   # (no copy when it already is; stays on the device)
     o = torch.empty((B, H, R, D), dtype=q.dtype, device=q.device)
     l = torch.empty((B, H, R), dtype=torch.float32, device=q.device)
-    key = (q.dtype, D)
+    key = (q.dtype, D, bool(fp8))
     dec = _DECODERS.get(key)
     if dec is None:
-        dec = _DECODERS[key] = AttentionDecode(D, P.BF16 if q.dtype == torch.bfloat16 else P.FP16)
+        dec = _DECODERS[key] = (AttentionDecodeFP8 if fp8 else AttentionDecode)(D, P.BF16 if q.dtype == torch.bfloat16 else P.FP16)
+    if fp8:
+        kw.update(keyScale=_scale_operand("flash_decode", "k_scale", k_scale, Hkv, q.device),
+                  valueScale=_scale_operand("flash_decode", "v_scale", v_scale, Hkv, q.device))
     kw.update(rows=R, column=column, heads=H, batches=B, headsPerKeyValue=H // Hkv, causal=bool(causal), cacheLengths=lengths,
               strides=dict(Q=(int(q.stride(2)) if R > 1 else D, int(q.stride(1)), int(q.stride(0))),
                            K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
@@ -339,6 +352,134 @@ def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal):
     with torch.cuda.device(q.device):
         dec.dispatch(q, k_cache, v_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, workspace=ws, **kw)
     return o, l
+
+
+def _scale_operand(who, name, t, heads, device):
+    """a per-head scale as the kernels read it: fp32 [heads] on the cache's device, contiguous; None stays None (1.0)"""
+    if t is None:
+        return None
+    if not t.is_cuda or t.device != device:
+        raise RuntimeError(f"{who}: {name} must live on the GPU of the cache (the host never reads a scale)")
+    if t.shape != (heads,) or t.dtype != torch.float32:
+        raise ValueError(f"{who}: {name} must be float32 [Hkv] = [{heads}] (got {tuple(t.shape)}, {t.dtype})")
+    return t.contiguous()
+
+
+def _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale):
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, True, k_scale, v_scale)
+
+
+def _run_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale):
+    who = "kv_cache_append"
+    tensors = (k_new, v_new, k_cache, v_cache, cache_lengths)
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    if k_new.dtype not in (torch.bfloat16, torch.float16) or v_new.dtype != k_new.dtype:
+        raise TypeError(f"{who}: k_new and v_new must share one of bfloat16 / float16")
+    if k_cache.dtype != v_cache.dtype or k_cache.dtype not in (k_new.dtype, torch.float8_e4m3fn):
+        raise TypeError(f"{who}: the caches must both be torch.float8_e4m3fn or the new rows' {k_new.dtype} (got {k_cache.dtype}, "
+                        f"{v_cache.dtype}); e5m2 and fnuz caches have no kernel")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError(f"{who}: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache takes the rows' bits")
+    paged = block_table is not None
+    if k_new.dim() != 4 or v_new.shape != k_new.shape or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or \
+            k_cache.shape[1] != k_new.shape[1] or k_cache.shape[3] != k_new.shape[3] or (not paged and k_cache.shape[0] != k_new.shape[0]):
+        raise ValueError(f"{who}: expected k_new, v_new [B, Hkv, R, D] and caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) "
+                         f"(got {tuple(k_new.shape)}, {tuple(v_new.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
+    B, Hkv, R, D = k_new.shape
+    if cache_lengths.shape != (B,) or cache_lengths.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{who}: cache_lengths must be [B] = [{B}] int32 or int64 (got {tuple(cache_lengths.shape)}, {cache_lengths.dtype})")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
+            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is written where it lies)")
+    kw = {}
+    if paged:
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
+                not block_table.is_cuda:
+            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
+                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
+        block_table = block_table.contiguous()   # (the row stride is the bound on the pages a sequence may name)
+        kw = dict(pageSize=int(k_cache.shape[2]), blockTable=block_table, blockTableStride=int(block_table.shape[1]),
+                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
+    else:
+        kw = dict(column=int(k_cache.shape[2]))
+    news = [t if t.stride(3) == 1 and all(st >= 0 for st in t.stride()) else t.contiguous() for t in (k_new, v_new)]
+    new_strides = lambda t: (int(t.stride(2)) if R > 1 else D, int(t.stride(1)), int(t.stride(0)))  # noqa: E731
+    lengths = cache_lengths.to(torch.int32)
+    key = (k_new.dtype, D, fp8)
+    app = _APPENDERS.get(key)
+    if app is None:
+        app = _APPENDERS[key] = KVCacheAppend(D, P.BF16 if k_new.dtype == torch.bfloat16 else P.FP16, KVCachePrecision.E4M3 if fp8 else None)
+    if fp8:
+        kw.update(keyScale=_scale_operand(who, "k_scale", k_scale, Hkv, k_new.device), valueScale=_scale_operand(who, "v_scale", v_scale, Hkv, k_new.device))
+    with torch.cuda.device(k_new.device):
+        app.dispatch(news[0], news[1], k_cache, v_cache, stream=torch.cuda.current_stream(k_new.device).cuda_stream, rows=R, heads=Hkv,
+                     batches=B, cacheLengths=lengths,
+                     strides=dict(kNew=new_strides(news[0]), vNew=new_strides(news[1]), kCache=_cache_strides(k_cache, paged),
+                                  vCache=_cache_strides(v_cache, paged)), **kw)
+
+
+_APPENDERS: Dict[Tuple, KVCacheAppend] = {}
+_FP8_DTYPES = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz") if hasattr(torch, n))
+
+
+def _register_kvcache_ops():
+    if not hasattr(torch.library, "custom_op"):
+        return False
+    try:
+        torch.ops.mfa.attention_decode_fp8  # noqa: B018 -- AttributeError when the op is not defined yet
+        torch.ops.mfa.kv_cache_append  # noqa: B018
+        return True
+    except (AttributeError, RuntimeError):
+        pass
+
+    @torch.library.custom_op("mfa::attention_decode_fp8", mutates_args=(), device_types="cuda")
+    def _op_decode_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                       block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
+                       v_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        return _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale)
+
+    @_op_decode_fp8.register_fake
+    def _op_decode_fp8_fake(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale):
+        B, H, R, D = q.shape
+        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
+
+    @torch.library.custom_op("mfa::kv_cache_append", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+    def _op_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                   block_table: Optional[torch.Tensor], k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor]) -> None:
+        _run_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
+
+    @_op_append.register_fake
+    def _op_append_fake(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale):
+        return None
+
+    return True
+
+
+_HAVE_KVCACHE_OPS = _register_kvcache_ops()
+
+
+def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                    block_table: Optional[torch.Tensor] = None, k_scale: Optional[torch.Tensor] = None,
+                    v_scale: Optional[torch.Tensor] = None) -> None:
+    """Writes the R new key / value rows of every sequence (k_new, v_new [B, Hkv, R, D], bf16 or fp16) into the caches IN PLACE and
+    returns nothing.  cache_lengths [B] (GPU) ALREADY INCLUDES the new tokens -- the tensor flash_decode takes next: row r of sequence
+    b goes to key cache_lengths[b] - R + r; rows that fall before key 0, past the cache's capacity or past the block table's row are
+    not written, and no other byte of the cache is touched.  Caches: [B, Hkv, C, D] (or a strided view with a contiguous last
+    dimension) or, with block_table [B, n] int32, page pools [pages, Hkv, pageSize, D]; dtype torch.float8_e4m3fn (the rows are
+    quantised: byte = e4m3(x / scale[j]), round to nearest even, saturating at +-448; k_scale / v_scale fp32 [Hkv], None = 1.0) or
+    the rows' own 16-bit type (bits copied; scales are an error).  Goes through the op `mfa::kv_cache_append` (mutates_args) where
+    torch has custom ops."""
+    for t in (k_new, v_new, k_cache, v_cache):
+        if t.requires_grad:
+            raise RuntimeError("kv_cache_append writes in place and has no autograd: detach the inputs")
+    if not all(t.is_cuda for t in (k_new, v_new, k_cache, v_cache, cache_lengths)):
+        raise RuntimeError("kv_cache_append: tensors must live on the GPU (there is no CPU path)")
+    if _HAVE_KVCACHE_OPS:
+        torch.ops.mfa.kv_cache_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
+    else:
+        _run_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
 
 
 def _register_decode_op():
@@ -367,7 +508,8 @@ _HAVE_DECODE_OP = _register_decode_op()
 
 
 def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
-                 block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False):
+                 block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False,
+                 k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None):
     """Attention of the R new rows of every sequence (q [B, H, R, D]; R = 1, or a few speculative tokens; G R <= 32 with G = H / Hkv)
     against its KV cache.  cache_lengths [B] (GPU, int32): valid keys per sequence INCLUDING the R new tokens, which the caller has
     already written into the cache; with `causal` row r sees key c iff c <= r + max(len - R, 0).  Caches: [B, Hkv, C, D], or any view
@@ -375,13 +517,23 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     strides are passed through, nothing is copied); with block_table [B, n] int32 the caches are page pools [pages, Hkv, pageSize, D]
     and entry (b, i) names the page of keys i pageSize .. of sequence b.  Forward only.  return_lse: also L [B, H, R] fp32 in natural
     units (log of the softmax denominator, the scale included), to merge results across cache shards.  A sequence of length 0 gets
-    O = 0.  Goes through the torch.library op `mfa::attention_decode` where torch has custom ops, so it traces under torch.compile."""
+    O = 0.  Goes through the torch.library op `mfa::attention_decode` where torch has custom ops, so it traces under torch.compile.
+    FP8 caches (torch.float8_e4m3fn, written by kv_cache_append): k_scale / v_scale [Hkv] fp32 on the GPU (None = 1.0), a cache byte
+    of head j stands for scale[j] x e4m3(byte); the launch goes through the op `mfa::attention_decode_fp8`.  Scales with a 16-bit
+    cache are an error."""
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
         raise RuntimeError("flash_decode: tensors must live on the GPU (there is no CPU path)")
     for t in (q, k_cache, v_cache):
         if t.requires_grad:
             raise RuntimeError("flash_decode is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
-    if _HAVE_DECODE_OP:
+    if k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES:
+        if _HAVE_KVCACHE_OPS:
+            o, l = torch.ops.mfa.attention_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale)
+        else:
+            o, l = _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale)
+    elif k_scale is not None or v_scale is not None:
+        raise ValueError("flash_decode: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache holds the values themselves")
+    elif _HAVE_DECODE_OP:
         o, l = torch.ops.mfa.attention_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)
     else:
         o, l = _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)

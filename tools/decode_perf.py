@@ -15,6 +15,8 @@ launch).  TB/s = algorithmic bytes (sum_b len_b x Hkv x D x 2 operands x 2 bytes
 
     python tools/decode_perf.py                  # the table
     python tools/decode_perf.py --trace-only     # a few launches of each arm, nothing timed: for rocprofv3 --kernel-trace --stats
+    python tools/decode_perf.py --fp8            # another table: decode over an e4m3 cache (include/mfa_kvcache.h) against the 16-bit
+                                                 # decode launch, R = 1, same method; plus the append launch at B = 64
 """
 import argparse
 import hashlib
@@ -27,7 +29,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from metal_flash_attention_amd import (AttentionDecode, AttentionDescriptor, AttentionKernel, AttentionKernelType, AttentionOperand as Op,  # noqa: E402
+from metal_flash_attention_amd import (AttentionDecode, AttentionDecodeFP8, KVCacheAppend, KVCachePrecision, AttentionDescriptor, AttentionKernel, AttentionKernelType, AttentionOperand as Op,  # noqa: E402
                                        GEMMOperandPrecision as P, _abi)
 
 HQ, HKV, D = 64, 8, 128
@@ -127,8 +129,105 @@ def measure(row, rounds, window_ms):
     return out
 
 
+class RowFP8:
+    """R = 1: the FP8 decode launch (arm "fp8") and the 16-bit decode launch (arm "bf16") of the same shape, each rotating over its own
+    cache copies whose sum is >= rotate_bytes; "append": the append launch that precedes a decode step (e4m3 cache)"""
+
+    def __init__(self, B, C, mixed, rotate_bytes):
+        self.B, self.C, self.R, self.mixed = B, C, 1, mixed
+        g = torch.Generator().manual_seed(B * 131 + C + 1)
+        lens = torch.randint(C // 4, C + 1, (B,), generator=g, dtype=torch.int32) if mixed else torch.full((B,), C, dtype=torch.int32)
+        self.keys = int(lens.sum())
+        self.lens = lens.cuda()
+        self.q = torch.randn(B, HQ, 1, D, device="cuda").to(torch.bfloat16)
+        self.o = torch.empty(B, HQ, 1, D, dtype=torch.bfloat16, device="cuda")
+        self.l = torch.empty(B, HQ, 1, dtype=torch.float32, device="cuda")
+        self.kscale, self.vscale = (0.5 + 1.5 * torch.rand(HKV, device="cuda") for _ in range(2))
+        self.copies, self.k, self.v = {}, {}, {}
+        for arm, esz in (("bf16", 2), ("fp8", 1)):
+            n = self.copies[arm] = max(2, min(64, -(-rotate_bytes // (2 * B * HKV * C * D * esz))))
+            make = (lambda: (torch.randn(B, HKV, C, D, device="cuda") * 0.5).to(torch.bfloat16)) if esz == 2 else \
+                (lambda: (torch.randn(B, HKV, C, D, device="cuda") * 0.5).to(torch.float8_e4m3fn))
+            self.k[arm], self.v[arm] = [make() for _ in range(n)], [make() for _ in range(n)]
+        self.bytes = {"bf16": self.keys * HKV * D * 2 * 2 + 2 * B * HQ * D * 2, "fp8": self.keys * HKV * D * 2 + 2 * B * HQ * D * 2}
+        self.dec = {"bf16": AttentionDecode(D, P.BF16), "fp8": AttentionDecodeFP8(D, P.BF16)}
+        self.kw = {"bf16": dict(rows=1, column=C, heads=HQ, batches=B, headsPerKeyValue=G, causal=True, cacheLengths=self.lens)}
+        self.kw["fp8"] = dict(self.kw["bf16"], keyScale=self.kscale, valueScale=self.vscale)
+        need = self.dec["bf16"].workspaceSize(**self.kw["bf16"])
+        assert need == self.dec["fp8"].workspaceSize(**self.kw["fp8"])
+        self.ws = torch.empty(need, dtype=torch.uint8, device="cuda") if need else None
+        self.form = self.dec["fp8"].launchForm(workspace=self.ws, **self.kw["fp8"])
+        self.append = KVCacheAppend(D, P.BF16, KVCachePrecision.E4M3)
+        self.knew, self.vnew = (torch.randn(B, HKV, 1, D, device="cuda").to(torch.bfloat16) for _ in range(2))
+        self.copies["append"] = self.copies["fp8"]
+
+    def launch(self, arm, i, stream):
+        if arm == "append":
+            c = i % self.copies["fp8"]
+            self.append.dispatch(self.knew, self.vnew, self.k["fp8"][c], self.v["fp8"][c], stream=stream, rows=1, heads=HKV, batches=self.B,
+                                 column=self.C, cacheLengths=self.lens, keyScale=self.kscale, valueScale=self.vscale)
+            return
+        c = i % self.copies[arm]
+        self.dec[arm].dispatch(self.q, self.k[arm][c], self.v[arm][c], self.o, self.l, stream=stream, workspace=self.ws, **self.kw[arm])
+
+    def graph(self, arm, launches):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            stream = torch.cuda.current_stream().cuda_stream
+            for i in range(launches):
+                self.launch(arm, i, stream)
+        return g
+
+
+def measure_arms(row, arms, rounds, window_ms):
+    """measure() for any set of arms of a row whose copy count is per arm"""
+    stream = torch.cuda.current_stream().cuda_stream
+    est = {}
+    for arm in arms:
+        row.launch(arm, 0, stream)
+        torch.cuda.synchronize()
+        probe = row.graph(arm, row.copies[arm])
+        once(probe)
+        est[arm] = once(probe) / row.copies[arm]
+    graphs = {arm: (row.graph(arm, n), n) for arm, n in ((a, max(row.copies[a], min(4000, int(window_ms / max(est[a], 1e-4))))) for a in arms)}
+    samples = {arm: [] for arm in arms}
+    for arm in arms:
+        once(graphs[arm][0])
+    for _ in range(rounds):
+        for arm in arms:   # alternate
+            g, n = graphs[arm]
+            samples[arm].append(once(g) / n * 1e3)
+    return {arm: (statistics.median(v), min(v), max(v), graphs[arm][1]) for arm, v in samples.items()}
+
+
+def main_fp8(a):
+    print("bf16 Q, D %d, Hq %d, Hkv %d (G %d), causal, R 1; arm (a) = decode over an e4m3 cache with per-head scales, arm (b) = the 16-bit decode "
+          "launch; us per launch: median (min .. max) of %d rounds; TB/s = each arm's own algorithmic bytes over its time; achievable HBM "
+          "rate 6.0-6.3 TB/s" % (D, HQ, HKV, G, a.rounds))
+    for B in (1, 8, 64):
+        for C in (4096, 32768):
+            if a.quick and (B == 64 or C != 4096):
+                continue
+            for mixed in (False, True):
+                row = RowFP8(B, C, mixed, a.rotate_bytes)
+                arms = ("bf16", "fp8") + (("append",) if B == 64 else ())
+                r = measure_arms(row, arms, a.rounds, a.window_ms)
+                (fa, flo, fhi, fn), (ba, blo, bhi, bn) = r["fp8"], r["bf16"]
+                extra = ""
+                if "append" in r:
+                    extra = " | append %6.1f (%6.1f .. %6.1f) x%d" % r["append"]
+                print("B %2d  keys %5d %-5s copies %2d / %2d | (a) fp8 %9.1f (%9.1f .. %9.1f) x%-4d | (b) 16-bit %9.1f (%9.1f .. %9.1f) x%-4d | "
+                      "(a)/(b) %5.3f | (a) %5.2f TB/s (b) %5.2f TB/s | %s%s" % (
+                          B, C, "mixed" if mixed else "full", row.copies["fp8"], row.copies["bf16"], fa, flo, fhi, fn, ba, blo, bhi, bn, fa / ba,
+                          row.bytes["fp8"] / (fa * 1e-6) / 1e12, row.bytes["bf16"] / (ba * 1e-6) / 1e12,
+                          row.form.split(" (")[0] + (" + combine" if "combine" in row.form else ""), extra), flush=True)
+                del row
+                torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fp8", action="store_true", help="the e4m3-cache decode launch against the 16-bit decode launch (another table)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--window-ms", type=float, default=150.0, help="device time one timed replay aims at")
     ap.add_argument("--rotate-bytes", type=int, default=1 << 30)
@@ -138,6 +237,8 @@ def main():
     assert torch.cuda.is_available(), "decode_perf.py measures on the GPU: there is nothing to report without one"
     sha = hashlib.sha256(open(_abi.library_path(), "rb").read()).hexdigest()
     print("library sha256 %s" % sha)
+    if a.fp8:
+        return main_fp8(a)
     print("bf16, D %d, Hq %d, Hkv %d (G %d), causal; arm (a) = decode launch, arm (b) = forward launch with headsPerKeyValue + "
           "columnLengths + causal; us per launch: median (min .. max) of %d rounds; achievable HBM rate 6.0-6.3 TB/s" % (D, HQ, HKV, G, a.rounds))
     rows = []
