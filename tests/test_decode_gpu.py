@@ -7,9 +7,15 @@ paged caches also in the tail of last pages and in pages the table does not name
 around the workspace and in a guard page behind the pool; after every launch no output holds a NaN, the canaries are intact and K,
 V, the table and the lengths are byte-identical to before.
 
+Beside those bounds every comparison with the model is held to the per-element bounds of tests/decode_model.py (derived from the
+number formats; tests/test_decode_sensitivity.py proves on the CPU that they flag every named defect), and every test also runs
+with that module's needle queries, in which single keys -- the first and last of every step, piece and page, each row's causal
+frontier -- carry a visible share of the softmax, and the key just behind a row's frontier would take the row over.  Non-causal
+launches have no such forbidden key: every key below the length is visible to every row.
+
 Maxima seen on an MI355X are recorded in DESIGN.md 4.9.
 """
-import math
+import re
 
 import numpy as np
 import pytest
@@ -18,7 +24,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import decode_model  # noqa: E402
 import harness  # noqa: E402
+from decode_model import MARGIN, bounds, compare, model  # noqa: E402,F401  (the bound proven by tests/test_decode_sensitivity.py)
 from metal_flash_attention_amd import (AttentionDecode, AttentionDescriptor, AttentionKernel, AttentionKernelType,  # noqa: E402
                                        AttentionOperand as Op, GEMMOperandPrecision as P)
 
@@ -47,27 +55,29 @@ def make_values(B, Hq, G, R, C, D, dtype, seed, shared=False):
     return q, k, v
 
 
-def model(q, k, v, lens, G, causal):
-    """float64 attention -> O [B, Hq, R, D], L [B, Hq, R] in natural units (-inf for an empty sequence)"""
-    q, k, v = (t.to(torch.float64).numpy() for t in (q, k, v))
-    B, Hq, R, D = q.shape
-    O = np.zeros((B, Hq, R, D))
-    L = np.full((B, Hq, R), -np.inf)
-    for b in range(B):
-        n = int(lens[b])
-        if n == 0:
-            continue
-        for h in range(Hq):
-            S = q[b, h] @ k[b, h // G, :n].T / math.sqrt(D)
-            if causal:
-                c, r = np.arange(n)[None, :], np.arange(R)[:, None]
-                S = np.where(c <= r + max(n - R, 0), S, -np.inf)
-            m = S.max(axis=1, keepdims=True)
-            p = np.exp(S - m)
-            s = p.sum(axis=1, keepdims=True)
-            O[b, h] = (p / s) @ v[b, h // G, :n]
-            L[b, h] = (m + np.log(s))[:, 0]
-    return O, L
+def pieces_of(text):
+    found = re.search(r"(\d+) pieces", text)
+    return int(found.group(1)) if found else None
+
+
+def planned_pieces(shape, dtype, cache, G, C, causal, workspace, decode=AttentionDecode):
+    """the piece count the launch will use (the host's plan; nothing is launched), None for an unsplit launch"""
+    if not workspace:
+        return None
+    B, Hq, R, D = shape
+    prec = P.BF16 if dtype == torch.bfloat16 else P.FP16
+    dec = decode(D, prec, prec)
+    kw = dict(cache.kw, rows=R, column=C, heads=Hq, batches=B, headsPerKeyValue=G, causal=causal, cacheLengths=cache.lens)
+    need = dec.workspaceSize(**kw)
+    return pieces_of(dec.launchForm(workspace=0x4000, workspaceBytes=need, **kw)) if need else None
+
+
+def needle_q(k, lens, Hq, G, R, dtype, causal, pieces=None, page=None):
+    """needle queries (tests/decode_model.py) for a cache whose values, as the model sees them, are k -> (q, info)"""
+    q64, info = decode_model.needle_queries(k, lens, Hq, G, R, causal, decode_model.fmt_of(dtype), pieces=pieces, page=page)
+    q = torch.from_numpy(q64).to(dtype)
+    assert torch.equal(q.to(torch.float64), torch.from_numpy(q64)), "needle queries are values of the 16-bit type"
+    return q, info
 
 
 def lengths_for(B, C, R, seed, page=64):
@@ -190,12 +200,17 @@ def run(q, cache, G, C, causal=True, workspace=True, out32=False, want_l=True, f
     return ov.float().cpu(), lv, ov.contiguous().view(ibits).cpu(), text
 
 
-def check_against_model(tag, got_o, got_l, q, k, v, lens, G, causal):
-    ref_o, ref_l = model(q, k, v, lens, G, causal)
+def check_against_model(tag, got_o, got_l, q, k, v, lens, G, causal, out32=False, pieces=None, page=None, info=None, kscale=None,
+                        vscale=None):
+    """the former bounds on the maxima, and the per-element bounds of tests/decode_model.py on O and on L wherever L was written;
+    k, v are the cache's values without kscale / vscale when those are given"""
+    ref = model(q, k, v, lens, G, causal, pieces=pieces, page=page, kscale=kscale, vscale=vscale)
+    ref_o, ref_l = ref.O, ref.L
     err_o = float(np.abs(got_o.numpy().astype(np.float64) - ref_o).max())
     SEEN[tag + " O"] = max(SEEN.get(tag + " O", 0.0), err_o)
     print(f"{tag}: max |dO| = {err_o:.3e}", end="")
     err_l = 0.0
+    nat_l = None
     if got_l is not None:
         gl = got_l.numpy().astype(np.float64)
         empty = np.isinf(ref_l)
@@ -203,12 +218,26 @@ def check_against_model(tag, got_o, got_l, q, k, v, lens, G, causal):
         if (~empty).any():
             err_l = float(np.abs(gl[~empty] / LOG2E - ref_l[~empty]).max())
         print(f", max |dL| = {err_l:.3e}", end="")
+        nat_l = gl / LOG2E
     print()
     assert err_o <= TOL_O, (tag, err_o)
     assert err_l <= TOL_L, (tag, err_l)
     for b in np.nonzero(lens == 0)[0]:
         assert float(got_o[b].abs().max()) == 0.0, "an empty sequence must get O = 0"
+    fmt = decode_model.fmt_of(q.dtype)
+    ratio_o, ratio_l, text = compare(got_o.numpy(), nat_l, ref, fmt, "f32" if out32 else fmt, lens, info=info, pieces=pieces, page=page)
+    print(f"RATIO {fmt} O{'32' if out32 else '16'} {'needles' if info is not None else 'plain'} | {tag} | err / bound at margin 1: "
+          f"O {ratio_o * MARGIN:.3f} L {ratio_l * MARGIN:.3f}")
+    assert ratio_o <= 1.0 and ratio_l <= 1.0, (tag, text)
     return err_o, err_l
+
+
+def both_inputs(q, k, lens, G, causal, cache, C, workspace, page=None, decode=AttentionDecode):
+    """the test's own queries, then the needle queries for the same cache and launch geometry: [(name, q, info)]"""
+    B, Hq, R, _D = q.shape
+    pieces = planned_pieces(q.shape, q.dtype, cache, G, C, causal, workspace, decode)
+    nq, info = needle_q(k, lens, Hq, G, R, q.dtype, causal, pieces=pieces, page=page)
+    return [("", q, None), (" needles", nq, info)]
 
 
 PARITY = [(prec, D, Hq, G, R) for prec in (P.BF16, P.FP16) for D in (64, 128) for Hq, G in ((8, 1), (8, 4), (32, 8), (16, 16))
@@ -225,9 +254,11 @@ def test_parity_with_the_float64_model(index, case):
     for variant in range(4):   # causal x workspace, with FP32 O and a NULL L rotating over the cases
         causal, workspace = bool(variant & 1), bool(variant & 2)
         out32, want_l = bool((index + variant) & 1), (index + variant) % 3 != 0
-        o, l, _bits, text = run(q, cache, G, C, causal=causal, workspace=workspace, out32=out32, want_l=want_l)
-        assert ("_pieces" in text) == workspace, text
-        check_against_model(f"{prec.name} D={D} Hq={Hq} G={G} R={R} causal={causal} split={workspace} O32={out32}", o, l, q, k, v, lens, G, causal)
+        for name, qq, info in both_inputs(q, k, lens, G, causal, cache, C, workspace):
+            o, l, _bits, text = run(qq, cache, G, C, causal=causal, workspace=workspace, out32=out32, want_l=want_l)
+            assert ("_pieces" in text) == workspace, text
+            check_against_model(f"{prec.name} D={D} Hq={Hq} G={G} R={R} causal={causal} split={workspace} O32={out32}{name}", o, l, qq,
+                                k, v, lens, G, causal, out32=out32, pieces=pieces_of(text), info=info)
 
 
 @pytest.mark.parametrize("page", [16, 64, 256])
@@ -237,12 +268,15 @@ def test_paged_equals_contiguous_bit_for_bit(prec, D, Hq, G, R, page):
     q, k, v = make_values(B, Hq, G, R, C, D, DTYPE[prec], seed=page + D)
     lens = lengths_for(B, C, R, seed=page, page=page)
     for workspace in (False, True):
-        o0, l0, b0, t0 = run(q, Cache(k, v, lens, "packed"), G, C, workspace=workspace)
-        o1, l1, b1, t1 = run(q, Cache(k, v, lens, f"paged:{page}", seed=page), G, C, workspace=workspace)
-        assert t0.replace("contiguous", "paged") == t1, (t0, t1)   # the same kernels and piece count
-        assert torch.equal(b0, b1), "O differs between the paged and the contiguous cache"
-        assert torch.equal(l0.view(torch.int32), l1.view(torch.int32)), "L differs between the paged and the contiguous cache"
-        check_against_model(f"paged {page} {prec.name} D={D} split={workspace}", o1, l1, q, k, v, lens, G, True)
+        packed, paged = Cache(k, v, lens, "packed"), Cache(k, v, lens, f"paged:{page}", seed=page)
+        for name, qq, info in both_inputs(q, k, lens, G, True, paged, C, workspace, page=page):
+            o0, l0, b0, t0 = run(qq, packed, G, C, workspace=workspace)
+            o1, l1, b1, t1 = run(qq, paged, G, C, workspace=workspace)
+            assert t0.replace("contiguous", "paged") == t1, (t0, t1)   # the same kernels and piece count
+            assert torch.equal(b0, b1), "O differs between the paged and the contiguous cache"
+            assert torch.equal(l0.view(torch.int32), l1.view(torch.int32)), "L differs between the paged and the contiguous cache"
+            check_against_model(f"paged {page} {prec.name} D={D} split={workspace}{name}", o1, l1, qq, k, v, lens, G, True,
+                                pieces=pieces_of(t1), page=page, info=info)
 
 
 @pytest.mark.parametrize("prec,D", [(P.BF16, 128), (P.FP16, 64)])
@@ -251,12 +285,16 @@ def test_split_against_unsplit(prec, D):
     q, k, v = make_values(B, Hq, G, R, C, D, DTYPE[prec], seed=5)
     lens = np.array([C, 1500, 65], dtype=np.uint32)
     cache = Cache(k, v, lens, "packed")
-    o0, l0, _b, t0 = run(q, cache, G, C, workspace=False, out32=True)
-    o1, l1, _b, t1 = run(q, cache, G, C, workspace=True, out32=True)
-    assert "_single" in t0 and "_pieces" in t1 and "_combine" in t1, (t0, t1)
-    do, dl = float((o0 - o1).abs().max()), float((l0 - l1).abs().max())
-    print(f"split against unsplit {prec.name} D={D}: max |dO| = {do:.3e} (fp32 O), max |dL| = {dl:.3e}; {t1}")
-    assert do <= TOL_O and dl / LOG2E <= TOL_L
+    for name, qq, info in both_inputs(q, k, lens, G, True, cache, C, True):
+        o0, l0, _b, t0 = run(qq, cache, G, C, workspace=False, out32=True)
+        o1, l1, _b, t1 = run(qq, cache, G, C, workspace=True, out32=True)
+        assert "_single" in t0 and "_pieces" in t1 and "_combine" in t1, (t0, t1)
+        do, dl = float((o0 - o1).abs().max()), float((l0 - l1).abs().max())
+        print(f"split against unsplit {prec.name} D={D}{name}: max |dO| = {do:.3e} (fp32 O), max |dL| = {dl:.3e}; {t1}")
+        assert do <= TOL_O and dl / LOG2E <= TOL_L
+        # each side on its own against the model: with FP32 O this is what gives the comparison a meaning
+        check_against_model(f"unsplit side {prec.name} D={D}{name}", o0, l0, qq, k, v, lens, G, True, out32=True, info=info)
+        check_against_model(f"split side {prec.name} D={D}{name}", o1, l1, qq, k, v, lens, G, True, out32=True, pieces=pieces_of(t1), info=info)
 
 
 @pytest.mark.parametrize("prec,D,Hq,G,R,causal", [(P.BF16, 128, 32, 8, 1, True), (P.FP16, 64, 8, 4, 4, True), (P.BF16, 64, 8, 1, 2, False)])
@@ -267,25 +305,33 @@ def test_agrees_with_the_forward_kernel(prec, D, Hq, G, R, causal):
     q, k, v = make_values(B, Hq, G, R, C, D, DTYPE[prec], seed=9)
     lens = lengths_for(B, C, R, seed=3)
     cache = Cache(k, v, lens, "packed")
-    o, l, _bits, _text = run(q, cache, G, C, causal=causal, out32=True)
     desc = AttentionDescriptor()
     desc.lowPrecisionInputs, desc.lowPrecisionIntermediates, desc.lowPrecisionInputType = True, False, prec
     desc.matrixDimensions = (R, C, D)
     desc.transposeState = (False, False, False, False)
     kernel = AttentionKernel(desc.kernelDescriptor(AttentionKernelType.forward))
-    fo = torch.zeros((B, Hq, R, D), dtype=torch.float32, device="cuda")
-    fl = torch.zeros((B, Hq, R), dtype=torch.float32, device="cuda")
     Hkv = Hq // G
-    kernel.dispatch({Op.Q: q.cuda(), Op.K: cache.k, Op.V: cache.v, Op.O: fo, Op.L: fl}, row=R, column=C, heads=Hq, batches=B,
-                    headStrides={Op.Q: R * D, Op.K: C * D, Op.V: C * D, Op.O: R * D, Op.L: R},
-                    batchStrides={Op.Q: Hq * R * D, Op.K: Hkv * C * D, Op.V: Hkv * C * D, Op.O: Hq * R * D, Op.L: Hq * R},
-                    causal=causal, columnLengths=cache.lens, headsPerKeyValue=G, stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
     keep = torch.from_numpy(lens != 0)
-    do = float((o[keep] - fo.cpu()[keep]).abs().max())
-    dl = float((l[keep] - fl.cpu()[keep]).abs().max()) / LOG2E
-    print(f"decode against forward {prec.name} D={D} G={G} R={R}: max |dO| = {do:.3e}, max |dL| = {dl:.3e}")
-    assert do <= TOL_O and dl <= TOL_L
+    for name, qq, info in both_inputs(q, k, lens, G, causal, cache, C, True):
+        o, l, _bits, text = run(qq, cache, G, C, causal=causal, out32=True)
+        fo = torch.zeros((B, Hq, R, D), dtype=torch.float32, device="cuda")
+        fl = torch.zeros((B, Hq, R), dtype=torch.float32, device="cuda")
+        kernel.dispatch({Op.Q: qq.cuda(), Op.K: cache.k, Op.V: cache.v, Op.O: fo, Op.L: fl}, row=R, column=C, heads=Hq, batches=B,
+                        headStrides={Op.Q: R * D, Op.K: C * D, Op.V: C * D, Op.O: R * D, Op.L: R},
+                        batchStrides={Op.Q: Hq * R * D, Op.K: Hkv * C * D, Op.V: Hkv * C * D, Op.O: Hq * R * D, Op.L: Hq * R},
+                        causal=causal, columnLengths=cache.lens, headsPerKeyValue=G, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        do = float((o[keep] - fo.cpu()[keep]).abs().max())
+        dl = float((l[keep] - fl.cpu()[keep]).abs().max()) / LOG2E
+        print(f"decode against forward {prec.name} D={D} G={G} R={R}{name}: max |dO| = {do:.3e}, max |dL| = {dl:.3e}")
+        assert do <= TOL_O and dl <= TOL_L
+        # each side on its own against the model (the forward launch on the sequences it defines: those with a key)
+        check_against_model(f"decode side {prec.name} D={D} G={G} R={R}{name}", o, l, qq, k, v, lens, G, causal, out32=True,
+                            pieces=pieces_of(text), info=info)
+        some = np.nonzero(lens != 0)[0]
+        sub = {(int(np.nonzero(some == b)[0][0]), h, r): x for (b, h, r), x in info.items() if b in some} if info is not None else None
+        check_against_model(f"forward side {prec.name} D={D} G={G} R={R}{name}", fo.cpu()[keep], fl.cpu()[keep], qq[keep], k[keep], v[keep],
+                            lens[some], G, causal, out32=True, info=sub)
 
 
 @pytest.mark.parametrize("layout", ["token_major", "fused", "shared"])
@@ -295,16 +341,58 @@ def test_strided_layouts_are_bit_identical_to_packed(prec, D, Hq, G, R, layout):
     q, k, v = make_values(B, Hq, G, R, C, D, DTYPE[prec], seed=21, shared=layout == "shared")
     lens = lengths_for(B, C, R, seed=4)
     for workspace in (False, True):
-        o0, l0, b0, _t = run(q, Cache(k, v, lens, "packed"), G, C, workspace=workspace)
-        o1, l1, b1, _t = run(q, Cache(k, v, lens, layout), G, C, workspace=workspace)
-        assert torch.equal(b0, b1) and torch.equal(l0.view(torch.int32), l1.view(torch.int32)), layout
-        check_against_model(f"{layout} {prec.name} D={D} split={workspace}", o1, l1, q, k, v, lens, G, True)
+        packed, other = Cache(k, v, lens, "packed"), Cache(k, v, lens, layout)
+        for name, qq, info in both_inputs(q, k, lens, G, True, other, C, workspace):
+            o0, l0, b0, _t = run(qq, packed, G, C, workspace=workspace)
+            o1, l1, b1, t1 = run(qq, other, G, C, workspace=workspace)
+            assert torch.equal(b0, b1) and torch.equal(l0.view(torch.int32), l1.view(torch.int32)), layout
+            check_against_model(f"{layout} {prec.name} D={D} split={workspace}{name}", o1, l1, qq, k, v, lens, G, True,
+                                pieces=pieces_of(t1), info=info)
 
 
 def test_one_long_sequence_split():
     Hq, G, R, C, D = 64, 8, 1, 32768, 128
     q, k, v = make_values(1, Hq, G, R, C, D, torch.bfloat16, seed=77)
     lens = np.array([C], dtype=np.uint32)
-    o, l, _bits, text = run(q, Cache(k, v, lens, "packed"), G, C, workspace=True)
-    assert "_pieces" in text and "64 pieces" in text, text
-    check_against_model("long B=1 Hq=64 G=8 D=128 C=32768", o, l, q, k, v, lens, G, True)
+    cache = Cache(k, v, lens, "packed")
+    for name, qq, info in both_inputs(q, k, lens, G, True, cache, C, True):
+        o, l, _bits, text = run(qq, cache, G, C, workspace=True)
+        assert "_pieces" in text and "64 pieces" in text, text
+        check_against_model("long B=1 Hq=64 G=8 D=128 C=32768" + name, o, l, qq, k, v, lens, G, True, pieces=64, info=info)
+        if info is not None:   # every piece's first and last key is some row's needle
+            keys = decode_model.needle_keys(info)[0]
+            assert all(b in keys and e - 1 in keys for b, e in decode_model.piece_ranges(C, 64)), "a piece boundary without a needle"
+
+
+# packed groups at the edges of the 32-wide tile: G R = 32 exactly; G R odd (the columns >= M repeat the last one: O's padding and
+# the rows of the next head are checked by run()'s canaries and by the model); fewer keys than rows
+@pytest.mark.parametrize("prec,D,Hq,G,R", [(P.BF16, 128, 16, 8, 4), (P.FP16, 64, 32, 16, 2), (P.BF16, 64, 6, 3, 1), (P.FP16, 128, 10, 5, 3),
+                                           (P.BF16, 128, 7, 7, 1)])
+def test_packed_groups_of_exactly_32_and_of_odd_size(prec, D, Hq, G, R):
+    C, B = 600, 8
+    assert G * R == 32 or (G * R) % 2 == 1
+    q, k, v = make_values(B, Hq, G, R, C, D, DTYPE[prec], seed=31 + G)
+    lens = lengths_for(B, C, R, seed=G, page=256)
+    cache = Cache(k, v, lens, "packed")
+    for workspace in (False, True):
+        for causal in (True, False):
+            for name, qq, info in both_inputs(q, k, lens, G, causal, cache, C, workspace):
+                o, l, _bits, text = run(qq, cache, G, C, causal=causal, workspace=workspace)
+                check_against_model(f"M={G * R} {prec.name} D={D} G={G} R={R} causal={causal} split={workspace}{name}", o, l, qq, k, v, lens,
+                                    G, causal, pieces=pieces_of(text), info=info)
+
+
+@pytest.mark.parametrize("prec,D,Hq,G,R", [(P.BF16, 128, 8, 4, 4), (P.FP16, 64, 4, 1, 4)])
+def test_fewer_keys_than_rows(prec, D, Hq, G, R):
+    """n < R: max(n - R, 0) = 0, row r sees the keys c <= r below the length"""
+    C = 600
+    lens = np.array([1, 2, 3, 4, 0, 5, 600], dtype=np.uint32)
+    B = len(lens)
+    q, k, v = make_values(B, Hq, G, R, C, D, DTYPE[prec], seed=47)
+    cache = Cache(k, v, lens, "packed")
+    for workspace in (False, True):
+        for causal in (True, False):
+            for name, qq, info in both_inputs(q, k, lens, G, causal, cache, C, workspace):
+                o, l, _bits, text = run(qq, cache, G, C, causal=causal, workspace=workspace, out32=causal)
+                check_against_model(f"n < R {prec.name} D={D} G={G} R={R} causal={causal} split={workspace}{name}", o, l, qq, k, v, lens, G,
+                                    causal, out32=causal, pieces=pieces_of(text), info=info)

@@ -147,3 +147,27 @@ def test_errors():
         flash_decode(q, k, v, lens[:2])
     with pytest.raises(RuntimeError, match="GPU"):
         flash_decode(q.cpu(), k.cpu(), v.cpu(), lens.cpu())
+
+
+def test_needle_queries_through_the_binding():
+    """queries in which single keys matter (tests/decode_model.py), through flash_decode's own stride plumbing: a token-major cache
+    view and a permuted q, checked element by element against the float64 model"""
+    import numpy as np
+
+    import decode_model
+    B, H, Hkv, R, C, D = 4, 16, 2, 2, 700, 128
+    _q, k, v, lens = inputs(B, H, Hkv, R, C, D, torch.bfloat16, seed=13)
+    n = lens.cpu().numpy()
+    q64, info = decode_model.needle_queries(k.cpu(), n, H, H // Hkv, R, True, "bf16")
+    q = torch.from_numpy(q64).to(torch.bfloat16).cuda()
+    poison(k, v, lens)
+    tk, tv = k.permute(0, 2, 1, 3).contiguous(), v.permute(0, 2, 1, 3).contiguous()              # [B][C][Hkv][D]
+    qv = q.permute(0, 2, 1, 3).contiguous().permute(0, 2, 1, 3)                                  # [B][R][H][D], permuted back
+    o, lse = flash_decode(qv, tk.permute(0, 2, 1, 3), tv.permute(0, 2, 1, 3), lens, return_lse=True)
+    kk, vv = torch.nan_to_num(k.cpu().float()), torch.nan_to_num(v.cpu().float())
+    ref = decode_model.model(q.cpu(), kk, vv, n, H // Hkv, True)
+    ro, rl, text = decode_model.compare(o.float().cpu().numpy(), lse.cpu().numpy(), ref, "bf16", "bf16", n, info=info)
+    print(f"RATIO bf16 O16 needles | flash_decode | err / bound at margin 1: O {ro * decode_model.MARGIN:.3f} L {rl * decode_model.MARGIN:.3f}")
+    assert ro <= 1.0 and rl <= 1.0, text
+    assert float(np.abs(o.float().cpu().numpy() - ref.O).max()) <= TOL_O
+    assert bool((o[2] == 0).all()) and bool((lse[2] < -1e30).all())

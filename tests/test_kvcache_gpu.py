@@ -7,6 +7,11 @@ converts the bytes exactly to the launch's 16-bit type, the arithmetic after tha
 head in [0.5, 2].  Every decode launch runs on poisoned caches (0x7f = NaN in every byte at or past a length, in the rest of a last
 page and in pages nobody names) with canaries behind O and L and around the workspace.
 
+Beside those bounds every comparison with the model is held to the per-element bounds of tests/decode_model.py, and every decode
+test also runs with that module's needle queries (built from the dequantised K, so a key's share of the softmax survives the
+quantisation).  The per-head scales are pairwise at least 1.25 x apart, so a scale taken from another head moves the scores or O far
+outside the bound.  Non-causal launches have no forbidden key.
+
 Maxima seen on an MI355X are recorded in DESIGN.md 4.10.
 """
 import numpy as np
@@ -16,7 +21,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import decode_model  # noqa: E402
 import harness  # noqa: E402
+from decode_model import MARGIN, bounds, compare  # noqa: E402,F401  (the bound proven by tests/test_decode_sensitivity.py)
 import test_decode_gpu as ref16  # noqa: E402  (the float64 model, the 16-bit launch's runner and its bounds)
 from metal_flash_attention_amd import (AttentionDecodeFP8, GEMMOperandPrecision as P, KVCacheAppend, KVCachePrecision, _abi)  # noqa: E402
 
@@ -54,7 +61,8 @@ def make_case(B, Hq, G, R, C, D, dtype, seed, shared=False):
     k, v = (torch.randn(1 if shared else B, Hkv, C, D, generator=g).to(dtype) for _ in range(2))
     if shared:
         k, v = k.expand(B, -1, -1, -1).contiguous(), v.expand(B, -1, -1, -1).contiguous()
-    ks, vs = (0.5 + 1.5 * torch.rand(Hkv, generator=g).numpy().astype(np.float32) for _ in range(2))
+    rng = np.random.default_rng(seed)
+    ks, vs = decode_model.spread_scales(rng, Hkv), decode_model.spread_scales(rng, Hkv)
     return q, quantise(k, ks), quantise(v, vs), ks, vs
 
 
@@ -162,8 +170,19 @@ def run8(q, cache, G, C, ks=None, vs=None, causal=True, workspace=True, out32=Fa
     return ov.float().cpu(), lv, ov.contiguous().view(ibits).cpu(), text
 
 
-def check(tag, o, l, q, kb, vb, ks, vs, lens, G, causal):
-    return ref16.check_against_model(tag, o, l, q, dequantise(kb, ks), dequantise(vb, vs), lens, G, causal)
+ONES = lambda b: np.ones(b.shape[1], dtype=np.float32)  # noqa: E731
+
+
+def check(tag, o, l, q, kb, vb, ks, vs, lens, G, causal, **how):
+    """the model sees the bytes' own values and the scales apart, as the kernel does (how: out32, pieces, page, info)"""
+    return ref16.check_against_model(tag, o, l, q, dequantise(kb, ONES(kb)), dequantise(vb, ONES(vb)), lens, G, causal,
+                                     kscale=None if ks is None else ks, vscale=None if vs is None else vs, **how)
+
+
+def both_inputs(q, kb, ks, lens, G, causal, cache, C, workspace, page=None):
+    """the test's own queries and the needle queries for the dequantised K: [(name, q, info)]"""
+    return ref16.both_inputs(q, dequantise(kb, ONES(kb) if ks is None else ks), lens, G, causal, cache, C, workspace, page=page,
+                             decode=AttentionDecodeFP8)
 
 
 # ---------------------------------------------------------------------------------------------------------------- decode parity
@@ -180,18 +199,40 @@ def test_parity_with_the_float64_model_on_the_dequantised_cache(index, case):
     for variant in range(4):   # causal x split, with FP32 O and a NULL L rotating over the cases
         causal, workspace = bool(variant & 1), bool(variant & 2)
         out32, want_l = bool((index + variant) & 1), (index + variant) % 3 != 0
-        o, l, _bits, text = run8(q, cache, G, C, ks, vs, causal=causal, workspace=workspace, out32=out32, want_l=want_l)
-        assert ("_pieces" in text) == workspace and "attn_decode8_" in text, text
-        check(f"fp8 {prec.name} D={D} G={G} R={R} causal={causal} split={workspace} O32={out32}", o, l, q, kb, vb, ks, vs, LENGTHS, G, causal)
+        for name, qq, info in both_inputs(q, kb, ks, LENGTHS, G, causal, cache, C, workspace):
+            o, l, _bits, text = run8(qq, cache, G, C, ks, vs, causal=causal, workspace=workspace, out32=out32, want_l=want_l)
+            assert ("_pieces" in text) == workspace and "attn_decode8_" in text, text
+            check(f"fp8 {prec.name} D={D} G={G} R={R} causal={causal} split={workspace} O32={out32}{name}", o, l, qq, kb, vb, ks, vs, LENGTHS,
+                  G, causal, out32=out32, pieces=ref16.pieces_of(text), info=info)
 
 
 def test_one_long_sequence_in_64_pieces():
     Hq, G, R, C, D = 64, 8, 1, 32768, 128
     q, kb, vb, ks, vs = make_case(1, Hq, G, R, C, D, torch.bfloat16, seed=77)
     lens = np.array([C], dtype=np.uint32)
-    o, l, _bits, text = run8(q, Cache8(kb, vb, lens, "packed"), G, C, ks, vs, workspace=True)
-    assert "attn_decode8_d128_bf16_pieces" in text and "64 pieces" in text, text
-    check("fp8 long B=1 Hq=64 G=8 D=128 C=32768", o, l, q, kb, vb, ks, vs, lens, G, True)
+    cache = Cache8(kb, vb, lens, "packed")
+    for name, qq, info in both_inputs(q, kb, ks, lens, G, True, cache, C, True):
+        o, l, _bits, text = run8(qq, cache, G, C, ks, vs, workspace=True)
+        assert "attn_decode8_d128_bf16_pieces" in text and "64 pieces" in text, text
+        check("fp8 long B=1 Hq=64 G=8 D=128 C=32768" + name, o, l, qq, kb, vb, ks, vs, lens, G, True, pieces=64, info=info)
+        if info is not None:   # every piece's first and last key is some row's needle
+            keys = decode_model.needle_keys(info)[0]
+            assert all(b in keys and e - 1 in keys for b, e in decode_model.piece_ranges(C, 64)), "a piece boundary without a needle"
+
+
+@pytest.mark.parametrize("prec,D,Hq,G,R", [(P.BF16, 128, 8, 4, 4), (P.FP16, 64, 8, 1, 4), (P.BF16, 64, 16, 8, 4), (P.FP16, 128, 6, 3, 1)])
+def test_fewer_keys_than_rows_and_packed_groups_at_the_tile_edges(prec, D, Hq, G, R):
+    """n < R (row r sees the keys c <= r below the length), G R = 32 exactly and G R odd, over an e4m3 cache"""
+    C = 600
+    lens = np.array([1, 2, 3, 4, 0, 5, 600], dtype=np.uint32)
+    q, kb, vb, ks, vs = make_case(len(lens), Hq, G, R, C, D, DTYPE[prec], seed=470 + G)
+    cache = Cache8(kb, vb, lens, "packed")
+    for workspace in (False, True):
+        for causal in (True, False):
+            for name, qq, info in both_inputs(q, kb, ks, lens, G, causal, cache, C, workspace):
+                o, l, _bits, text = run8(qq, cache, G, C, ks, vs, causal=causal, workspace=workspace, out32=causal)
+                check(f"fp8 n < R {prec.name} D={D} G={G} R={R} causal={causal} split={workspace}{name}", o, l, qq, kb, vb, ks, vs, lens, G,
+                      causal, out32=causal, pieces=ref16.pieces_of(text), info=info)
 
 
 # ------------------------------------------------------------------------------------------------- same inputs, the 16-bit route
@@ -206,12 +247,19 @@ def test_same_values_through_the_16_bit_launch(prec, D, G, R):
     k16, v16 = (b.view(torch.float8_e4m3fn).to(DTYPE[prec]) for b in (kb, vb))
     assert torch.equal(k16.to(torch.float64), kb.view(torch.float8_e4m3fn).to(torch.float64))   # the conversion is exact
     for workspace in (False, True):
-        o8, l8, _b, t8 = run8(q, Cache8(kb, vb, lens, "packed"), G, C, None, None, workspace=workspace, out32=True)
-        o16, l16, _b, t16 = ref16.run(q, ref16.Cache(k16, v16, lens, "packed"), G, C, workspace=workspace, out32=True)
-        assert t8.replace("attn_decode8_", "attn_decode16_") == t16, (t8, t16)
-        do, dl = float((o8 - o16).abs().max()), float((l8 - l16).abs().max())
-        print(f"fp8 against the 16-bit launch {prec.name} D={D} G={G} R={R} split={workspace}: max |dO| = {do:.3e} (fp32 O), max |dL| = {dl:.3e}")
-        assert do <= TOL_O and dl / LOG2E <= TOL_L
+        c8, c16 = Cache8(kb, vb, lens, "packed"), ref16.Cache(k16, v16, lens, "packed")
+        for name, qq, info in both_inputs(q, kb, None, lens, G, True, c8, C, workspace):
+            o8, l8, _b, t8 = run8(qq, c8, G, C, None, None, workspace=workspace, out32=True)
+            o16, l16, _b, t16 = ref16.run(qq, c16, G, C, workspace=workspace, out32=True)
+            assert t8.replace("attn_decode8_", "attn_decode16_") == t16, (t8, t16)
+            do, dl = float((o8 - o16).abs().max()), float((l8 - l16).abs().max())
+            print(f"fp8 against the 16-bit launch {prec.name} D={D} G={G} R={R} split={workspace}{name}: max |dO| = {do:.3e} (fp32 O), "
+                  f"max |dL| = {dl:.3e}")
+            assert do <= TOL_O and dl / LOG2E <= TOL_L
+            # each side on its own against the model: with FP32 O this is what gives the comparison a meaning
+            how = dict(out32=True, pieces=ref16.pieces_of(t8), info=info)
+            check(f"fp8 side {prec.name} D={D} G={G} R={R} split={workspace}{name}", o8, l8, qq, kb, vb, None, None, lens, G, True, **how)
+            check(f"16-bit side {prec.name} D={D} G={G} R={R} split={workspace}{name}", o16, l16, qq, kb, vb, None, None, lens, G, True, **how)
 
 
 # ------------------------------------------------------------------------------------------------------------------ layouts
@@ -221,13 +269,17 @@ def test_layouts_are_bit_identical_to_packed(prec, D, Hq, G, R, layout):
     C, B = 1000, 9
     q, kb, vb, ks, vs = make_case(B, Hq, G, R, C, D, DTYPE[prec], seed=21 + D, shared=layout == "shared")
     lens = ref16.lengths_for(B, C, R, seed=4, page=int(layout.split(":")[1]) if ":" in layout else 64)
+    page = int(layout.split(":")[1]) if ":" in layout else None
     for workspace in (False, True):
-        o0, l0, b0, t0 = run8(q, Cache8(kb, vb, lens, "packed"), G, C, ks, vs, workspace=workspace)
-        o1, l1, b1, t1 = run8(q, Cache8(kb, vb, lens, layout, seed=5), G, C, ks, vs, workspace=workspace)
-        assert t0.replace("contiguous", "paged") == t1.replace("contiguous", "paged"), (t0, t1)   # the same kernels and piece count
-        assert torch.equal(b0, b1), f"O differs between the {layout} and the packed cache"
-        assert torch.equal(l0.view(torch.int32), l1.view(torch.int32)), f"L differs between the {layout} and the packed cache"
-        check(f"fp8 {layout} {prec.name} D={D} split={workspace}", o1, l1, q, kb, vb, ks, vs, lens, G, True)
+        packed, other = Cache8(kb, vb, lens, "packed"), Cache8(kb, vb, lens, layout, seed=5)
+        for name, qq, info in both_inputs(q, kb, ks, lens, G, True, other, C, workspace, page=page):
+            o0, l0, b0, t0 = run8(qq, packed, G, C, ks, vs, workspace=workspace)
+            o1, l1, b1, t1 = run8(qq, other, G, C, ks, vs, workspace=workspace)
+            assert t0.replace("contiguous", "paged") == t1.replace("contiguous", "paged"), (t0, t1)   # the same kernels and piece count
+            assert torch.equal(b0, b1), f"O differs between the {layout} and the packed cache"
+            assert torch.equal(l0.view(torch.int32), l1.view(torch.int32)), f"L differs between the {layout} and the packed cache"
+            check(f"fp8 {layout} {prec.name} D={D} split={workspace}{name}", o1, l1, qq, kb, vb, ks, vs, lens, G, True,
+                  pieces=ref16.pieces_of(t1), page=page, info=info)
 
 
 # ------------------------------------------------------------------------------------------------------------------- poison
@@ -345,7 +397,7 @@ def test_eight_generation_steps_append_then_decode():
     table = torch.from_numpy(rng.permutation(pages)[:B * per].reshape(B, per).astype(np.int32)).to(dev)
     poolk = torch.full((pages, Hkv, ps, D), NAN8, dtype=torch.uint8, device=dev).view(torch.float8_e4m3fn)
     poolv = torch.full((pages, Hkv, ps, D), NAN8, dtype=torch.uint8, device=dev).view(torch.float8_e4m3fn)
-    ks, vs = (0.5 + 1.5 * torch.rand(Hkv, generator=g) for _ in range(2))
+    ks, vs = (torch.from_numpy(decode_model.spread_scales(rng, Hkv)) for _ in range(2))
     ksd, vsd = ks.to(dev), vs.to(dev)
     history_k = [torch.randn(Hkv, int(n), D, generator=g).to(dtype) for n in start]
     history_v = [torch.randn(Hkv, int(n), D, generator=g).to(dtype) for n in start]
@@ -359,11 +411,7 @@ def test_eight_generation_steps_append_then_decode():
             kn[b, :, 0], vn[b, :, 0] = history_k[b][:, t], history_v[b][:, t]
             kv_cache_append(kn.to(dev), vn.to(dev), poolk, poolv, one, block_table=table, k_scale=ksd, v_scale=vsd)
     for step in range(STEPS):
-        q = torch.randn(B, Hq, 1, D, generator=g).to(dtype)
         kn, vn = torch.randn(B, Hkv, 1, D, generator=g).to(dtype), torch.randn(B, Hkv, 1, D, generator=g).to(dtype)
-        lens += 1                                            # on the device
-        assert kv_cache_append(kn.to(dev), vn.to(dev), poolk, poolv, lens, block_table=table, k_scale=ksd, v_scale=vsd) is None
-        o, lse = flash_decode(q.to(dev), poolk, poolv, lens, block_table=table, return_lse=True, k_scale=ksd, v_scale=vsd)
         for b in range(B):
             history_k[b] = torch.cat([history_k[b], kn[b]], dim=1)
             history_v[b] = torch.cat([history_v[b], vn[b]], dim=1)
@@ -373,7 +421,14 @@ def test_eight_generation_steps_append_then_decode():
         for b in range(B):
             kb[b, :, :int(n[b])] = quantise(history_k[b][None], ks.numpy())[0]
             vb[b, :, :int(n[b])] = quantise(history_v[b][None], vs.numpy())[0]
+        # the step's query: the row just appended (key n - 1, the row's frontier) and the one before it are among its needles, so
+        # an append that went to another position, page or head, or stale bytes there, move O far outside the bound
+        q, info = ref16.needle_q(dequantise(kb, ks.numpy()), n, Hq, G, 1, dtype, True, page=ps)
+        assert all(int(n[b]) - 1 in info[(b, h, 0)][0] for b in range(B) for h in range(Hq))
+        lens += 1                                            # on the device
+        assert kv_cache_append(kn.to(dev), vn.to(dev), poolk, poolv, lens, block_table=table, k_scale=ksd, v_scale=vsd) is None
+        o, lse = flash_decode(q.to(dev), poolk, poolv, lens, block_table=table, return_lse=True, k_scale=ksd, v_scale=vsd)
         assert bool(torch.isfinite(o.float()).all())
         check(f"round trip step {step} lengths {n.tolist()}", o.float().cpu(), (lse.cpu() * LOG2E), q, kb, vb, ks.numpy(), vs.numpy(),
-              n.astype(np.uint32), G, True)
+              n.astype(np.uint32), G, True, page=ps, info=info)
     assert lens.cpu().tolist() == (start + STEPS).tolist()

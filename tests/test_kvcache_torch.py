@@ -142,3 +142,28 @@ def test_errors():
         flash_decode(q, kq, vq, lens, k_scale=ks[:1])
     with pytest.raises(TypeError):
         kv_cache_append(kn.to(torch.float16), vn, kq, vq, lens)
+
+
+def test_needle_queries_over_an_fp8_cache_through_the_binding():
+    """queries in which single keys matter (tests/decode_model.py) against the float64 model of the dequantised cache: the binding's
+    own scale and stride plumbing (per-head scales pairwise 1.25 x apart, a token-major cache view)"""
+    import numpy as np
+
+    import decode_model
+    B, H, Hkv, R, C, D = 4, 16, 4, 2, 700, 128
+    q, kq, vq, _ks, _vs, lens = inputs(B, H, Hkv, R, C, D, torch.bfloat16, seed=17)
+    rng = np.random.default_rng(17)
+    ks, vs = decode_model.spread_scales(rng, Hkv), decode_model.spread_scales(rng, Hkv)
+    n = lens.cpu().numpy()
+    k64, v64 = kq.cpu().to(torch.float64).numpy(), vq.cpu().to(torch.float64).numpy()
+    q64, info = decode_model.needle_queries(k64 * ks.astype(np.float64)[None, :, None, None], n, H, H // Hkv, R, True, "bf16")
+    q = torch.from_numpy(q64).to(torch.bfloat16).cuda()
+    tk = kq.view(torch.uint8).permute(0, 2, 1, 3).contiguous().view(E4M3).permute(0, 2, 1, 3)     # [B][C][Hkv][D] underneath
+    tv = vq.view(torch.uint8).permute(0, 2, 1, 3).contiguous().view(E4M3).permute(0, 2, 1, 3)
+    o, lse = flash_decode(q, tk, tv, lens, return_lse=True, k_scale=torch.from_numpy(ks).cuda(), v_scale=torch.from_numpy(vs).cuda())
+    assert torch.equal(o, flash_decode(q, kq, vq, lens, k_scale=torch.from_numpy(ks).cuda(), v_scale=torch.from_numpy(vs).cuda()))
+    ref = decode_model.model(q.cpu(), k64, v64, n, H // Hkv, True, kscale=ks, vscale=vs)
+    ro, rl, text = decode_model.compare(o.float().cpu().numpy(), lse.cpu().numpy(), ref, "bf16", "bf16", n, info=info)
+    print(f"RATIO bf16 O16 needles | flash_decode fp8 | err / bound at margin 1: O {ro * decode_model.MARGIN:.3f} L {rl * decode_model.MARGIN:.3f}")
+    assert ro <= 1.0 and rl <= 1.0, text
+    assert bool((o[2] == 0).all()) and bool((lse[2] < -1e30).all())
