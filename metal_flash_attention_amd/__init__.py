@@ -12,6 +12,7 @@ from .attention import (  # noqa: F401
     AttentionKernelDescriptor,
     AttentionKernelType,
     AttentionOperand,
+    AttentionPrefill,
     GEMMOperandPrecision,
     KVCacheAppend,
     KVCachePrecision,

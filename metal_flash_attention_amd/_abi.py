@@ -221,6 +221,38 @@ KVCACHE_SYMBOLS = [
      _DECODE_BUFS + [ctypes.POINTER(mfa_decode_params), _QUANT, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
 ]
 
+class mfa_prefill_params(ctypes.Structure):   # include/mfa_prefill.h
+    _fields_ = [
+        ("rows", ctypes.c_uint32), ("column", ctypes.c_uint32), ("heads", ctypes.c_uint32), ("batches", ctypes.c_uint32),
+        ("headsPerKeyValue", ctypes.c_uint32), ("causal", ctypes.c_uint32),
+        ("headDimension", ctypes.c_uint16), ("precision", ctypes.c_uint8), ("outputPrecision", ctypes.c_uint8),
+        ("pageSize", ctypes.c_uint32),
+        ("cacheLengths", ctypes.c_void_p), ("queryLengths", ctypes.c_void_p), ("blockTable", ctypes.c_void_p),
+        ("blockTableStride", ctypes.c_int64),
+        ("leadingDimension", ctypes.c_int64 * 4), ("headStride", ctypes.c_int64 * 4), ("batchStride", ctypes.c_int64 * 4),
+        ("pageStride", ctypes.c_int64 * 2),
+        ("lHeadStride", ctypes.c_int64), ("lBatchStride", ctypes.c_int64),
+        ("cachePrecision", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("keyScale", ctypes.c_void_p), ("valueScale", ctypes.c_void_p),
+    ]
+
+
+MFA_PREFILL_KEY_TILE, MFA_PREFILL_PACKED_ROWS, MFA_PREFILL_MAX_GROUP = 64, 128, 32
+_PREFILL = ctypes.POINTER(mfa_prefill_params)
+_U32P = ctypes.POINTER(ctypes.c_uint32)
+
+PREFILL_SYMBOLS = [
+    ("mfa_prefill_params_init", None, [_PREFILL]),
+    ("mfa_prefill_params_size", ctypes.c_size_t, []),
+    ("mfa_prefill_params_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
+    ("mfa_attention_prefill_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_void_p]),
+    ("mfa_attention_prefill_launch_form", ctypes.c_int, [_PREFILL, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_prefill_time", ctypes.c_int,
+     _DECODE_BUFS + [_PREFILL, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    ("mfa_attention_prefill_tile_range", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U32P, _U32P]),
+]
+
 SYMBOLS = [
     ("mfa_precision_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mfa_precision_size", ctypes.c_int, [ctypes.c_int]),
@@ -296,7 +328,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -541,6 +541,86 @@ class AttentionDecodeFP8(AttentionDecode):
         return float(ms.value)
 
 
+class AttentionPrefill:
+    """Prefill attention over a KV cache (include/mfa_prefill.h): a block of up to `rows` new query rows per sequence -- longer than a
+    decode step -- against caches of `heads // headsPerKeyValue` K / V heads that already hold the new tokens; per-sequence cache and
+    query lengths on the device, contiguous or paged, 16-bit or FP8.
+
+        prefill = AttentionPrefill(headDimension=128, precision=GEMMOperandPrecision.BF16)
+        prefill.dispatch(q, k, v, o, l, cacheLengths=lengths, queryLengths=qlens, rows=R, column=C, heads=64, batches=B,
+                         headsPerKeyValue=8, strides=dict(Q=(ld, head, batch), K=..., V=..., O=...))
+
+    `strides`, pageSize / blockTable / blockTableStride / pageStrides, lStrides: as AttentionDecode.  cachePrecision=
+    KVCachePrecision.E4M3 reads an e4m3 cache (the quantisation block is part of mfa_prefill_params, so one class serves both): the
+    K / V strides then count bytes, and keyScale / valueScale (device FP32 [heads // headsPerKeyValue], None = 1.0) go with the shape
+    arguments.  The launch takes no workspace."""
+
+    OPERANDS = ("Q", "K", "V", "O")
+
+    def __init__(self, headDimension: int, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16,
+                 outputPrecision: Optional[GEMMOperandPrecision] = None, cachePrecision: Optional[int] = None):
+        self.headDimension = int(headDimension)
+        self.precision = GEMMOperandPrecision(precision)
+        self.outputPrecision = self.precision if outputPrecision is None else GEMMOperandPrecision(outputPrecision)
+        self.cachePrecision = int(self.precision) if cachePrecision is None else int(cachePrecision)
+
+    def _params(self, *, rows: int, column: int, heads: int = 1, batches: int = 1, headsPerKeyValue: int = 1, causal: bool = True,
+                cacheLengths=None, queryLengths=None, pageSize: int = 0, blockTable=None, blockTableStride: int = 0,
+                strides: Optional[Mapping] = None, pageStrides: Optional[Sequence[int]] = None, lStrides: Optional[Sequence[int]] = None,
+                keyScale=None, valueScale=None):
+        p = _abi.mfa_prefill_params()
+        lib().mfa_prefill_params_init(ctypes.byref(p))
+        p.rows, p.column, p.heads, p.batches = int(rows), int(column), int(heads), int(batches)
+        p.headsPerKeyValue, p.causal = int(headsPerKeyValue), int(bool(causal))
+        p.headDimension, p.precision, p.outputPrecision = self.headDimension, int(self.precision), int(self.outputPrecision)
+        p.cachePrecision = self.cachePrecision
+        p.pageSize = int(pageSize)
+        p.cacheLengths, p.queryLengths = _pointer(cacheLengths), _pointer(queryLengths)
+        p.blockTable, p.blockTableStride = _pointer(blockTable), int(blockTableStride)
+        D, G = self.headDimension, max(1, int(headsPerKeyValue))
+        kvHeads = max(1, int(heads) // G)
+        for i, name in enumerate(self.OPERANDS):
+            seq, h = (int(rows), int(heads)) if name in ("Q", "O") else (int(pageSize) or int(column), kvHeads)
+            ld, hs, bs = (strides or {}).get(name, (D, seq * D, h * seq * D))
+            p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
+        if pageStrides is not None:
+            p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
+        elif pageSize:
+            p.pageStride[0] = p.pageStride[1] = kvHeads * int(pageSize) * D
+        p.lHeadStride, p.lBatchStride = (int(lStrides[0]), int(lStrides[1])) if lStrides is not None else (int(rows), int(heads) * int(rows))
+        p.keyScale, p.valueScale = _pointer(keyScale), _pointer(valueScale)
+        return p, (cacheLengths, queryLengths, blockTable, keyScale, valueScale)
+
+    def launchForm(self, **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name and the grid."""
+        p, _keep = self._params(**shape)
+        out = ctypes.create_string_buffer(512)
+        check(lib().mfa_attention_prefill_launch_form(ctypes.byref(p), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        p, _keep = self._params(**shape)
+        check(lib().mfa_attention_prefill_launch(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
+                                                 ctypes.c_void_p(stream or 0)))
+
+    def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
+        p, _keep = self._params(**shape)
+        ms = ctypes.c_float(0.0)
+        check(lib().mfa_attention_prefill_time(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
+                                               ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
+        return float(ms.value)
+
+    @staticmethod
+    def tileRange(length: int, queryLength: int, firstRow: int, blockRows: int, causal: bool = True) -> Tuple[int, int]:
+        """(first_masked, end) of the block of rows [firstRow, firstRow + blockRows) of a sequence of `length` keys and `queryLength`
+        rows, in 64-key tiles: the kernels' own function, on the host"""
+        f, e = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        check(lib().mfa_attention_prefill_tile_range(int(length), int(queryLength), int(firstRow), int(blockRows), int(bool(causal)),
+                                                     ctypes.byref(f), ctypes.byref(e)))
+        return int(f.value), int(e.value)
+
+
 class KVCacheAppend:
     """Appends the `rows` new key / value rows of every sequence to a KV cache (include/mfa_kvcache.h), quantising them to e4m3 when
     the cache is FP8 (cachePrecision=KVCachePrecision.E4M3) or copying their bits when it is the rows' 16-bit type (None).

@@ -1,0 +1,312 @@
+// attn_prefill16.h -- prefill attention over a KV cache on the 16-bit matrix cores of gfx950: a block of new query rows per sequence
+// against keys that already live in a 16-bit or FP8 (e4m3), contiguous or paged cache (include/mfa_prefill.h).
+// Compiler-scheduled HIP built from what attn_decode16.h and attn_fwd16_v3.h have proven:
+//   * PACKING, decode's idea widened: one workgroup of 4 waves owns 128 packed rows of ONE K / V head of one sequence -- RB = 128 / G
+//     consecutive query rows for each of the G query heads of the group -- so K and V are read once per group, not G times.  Packed row
+//     p < G RB is head kvh G + p / RB, row r0 + p % RB; wave w owns packed rows 32 w .. 32 w + 31; rows >= G RB (G = 3: 126, 127) and
+//     rows at or past the sequence's queryLengths repeat the last live one and store nothing.
+//   * the fragment maps of dev/attn_fwd16.h: S^T = K Q^T with v_mfma_f32_32x32x16, a lane owns one packed row (frontier, running
+//     (m, l) and the rescale are lane-local plus one half-wave exchange), P converted in registers is the B operand of O^T += V^T P^T.
+//     Q fragments stay in registers (D/16 x 4 VGPRs), O^T is D/32 x 16 accumulators.
+//   * K and V go through LDS, shared by the four waves (every wave needs every key): tiles of 64 keys, double-buffered; a row-major K
+//     image XOR-swizzled by kswz (attn_fwd16_common.h) and read as A fragments with ds_read_b128, and the V image [D/32][64 keys][32 d]
+//     gathered as V^T by ds_read_b64_tr_b16 exactly as attn_decode16.h does.  Staged through registers (global load -> VGPR ->
+//     ds_write): the loads of tile t + 1 are issued before tile t is computed and written to the other buffer after it, one barrier
+//     per tile.
+//   * FP8 is one template parameter: the e4m3 bytes are converted in the staging registers (cvt8_e4m3, attn_decode8.h: exact) between
+//     the load and the LDS write.  From the LDS images on the two kernels are the same code, with no permuted contraction: on exactly
+//     convertible values the e4m3 and the 16-bit launch are byte-identical.
+//   * keys are addressed in groups of 16 (a tile starts on a multiple of 64 and a page holds at least 16 keys, so a group never
+//     straddles a page): four wave-uniform block-table reads per tile, none per lane.  The contiguous layout takes the same path with
+//     the batch stride in place of the page, so paged and contiguous launches run the same arithmetic in the same order.
+//   * prefill_tile_range -- one function, device and host (mfa_attention_prefill_tile_range) -- gives the block its tiles: [0,
+//     first_masked) run without the per-element mask, [first_masked, end) with it, tiles at or past end are never loaded.
+//   * what may hold poison is never loaded: key rows at or past n come in as zeros (K and V), a masked score is REPLACED (p = 0 exactly),
+//     and the running maximum only ever sees visible keys -- a row without a visible key keeps m = -FLT_MAX, l = 0.
+#pragma once
+#include "attn_decode8.h"
+#include <type_traits>
+
+#define MFA_PREFILL_INLINE __attribute__((always_inline))   // (tile-load lambdas forced inline: see the top of attn_fwd16_v3.h)
+
+namespace mfa {
+
+constexpr int PF_TILE = 64;      // keys per tile (MFA_PREFILL_KEY_TILE)
+constexpr int PF_ROWS = 128;     // packed rows per workgroup (MFA_PREFILL_PACKED_ROWS)
+constexpr int PF_THREADS = 256;
+
+struct PrefillArgs {
+  const char *q, *k, *v;
+  char *o;
+  float *l;                       // null: not stored
+  const uint32_t *lengths;
+  const uint32_t *qlengths;       // null: every sequence has `rows`
+  const int32_t *table;           // paged launches
+  int64_t tableStride;
+  int64_t ldq, hsq, bsq;          // elements
+  int64_t ldk, hsk, bsk, psk;
+  int64_t ldv, hsv, bsv, psv;
+  int64_t ldo, hso, bso;
+  int64_t lhs, lbs;
+  const float *keyScale, *valueScale;   // null: 1.0
+  uint32_t rows, G, RB, rowBlocks, Hkv, batches, column;
+  uint32_t paged, pageShift;      // pageSize = 1 << pageShift
+  uint32_t causal, outF32;
+  float scale2;                   // log2(e) / sqrt(D)
+};
+
+// The tiles of the block of rows [r0, r0 + RB) of a sequence of n keys and qn rows.  Row r sees keys c < lim(r) = n, or with `causal`
+// min(n, r + max(n - qn, 0) + 1): *end = ceil(lim(last live row) / 64), *firstMasked = floor(lim(r0) / 64) -- below it every key of a
+// tile is visible to every live row.  Device and host (mfa_attention_prefill_tile_range) run this one body.
+__host__ __device__ __forceinline__ void prefill_tile_range(uint32_t n, uint32_t qn, uint32_t r0, uint32_t RB, uint32_t causal,
+                                                            uint32_t *firstMasked, uint32_t *end) {
+  if (r0 >= qn || n == 0) {
+    *firstMasked = *end = 0;
+    return;
+  }
+  uint64_t lo = n, hi = n;
+  if (causal) {
+    const uint64_t off = n > qn ? (uint64_t)n - qn : 0;
+    uint64_t last = (uint64_t)r0 + RB;
+    if (last > qn) last = qn;
+    lo = (uint64_t)r0 + off + 1;
+    hi = last + off;   // (last - 1) + off + 1
+    if (lo > n) lo = n;
+    if (hi > n) hi = n;
+  }
+  const uint64_t e = (hi + PF_TILE - 1) / PF_TILE;
+  uint64_t f = lo / PF_TILE;
+  if (f > e) f = e;
+  *firstMasked = (uint32_t)f;
+  *end = (uint32_t)e;
+}
+
+template <int D> constexpr int prefill16_lds_bytes() { return 2 /*buffers*/ * 2 /*K, V*/ * PF_TILE * D * 2; }
+
+template <typename T, int D, bool FP8>
+__device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
+  typedef Frag16<T> F;
+  typedef typename F::v8 v8;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NDB = D / 32, NKS = D / 16;
+  constexpr int ROWB = D * 2, KIMG = PF_TILE * ROWB, VIMG = PF_TILE * D * 2, STAGE = KIMG + VIMG;
+  constexpr int ESZ = FP8 ? 1 : 2;                // bytes of a cache element
+  constexpr int CPR = D * ESZ / 16;               // 16-byte chunks of a cache row
+  constexpr int RPI = PF_THREADS / CPR;           // rows one workgroup-instruction covers
+  constexpr int NCH = PF_TILE / RPI;              // chunks per thread, per operand, per tile
+  static_assert(PF_TILE % RPI == 0 && NCH >= 1, "a tile divides evenly over the workgroup");
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, q = lane & 31, hi = lane >> 5;
+
+  // ---- the block: (row block, K / V head, sequence); the blocks of one (sequence, K / V head) are neighbours on one XCD
+  uint32_t rb, kvh, batch;
+  {
+    const Fwd16Grid g{a.rowBlocks, a.Hkv, a.batches, 1u, nullptr, nullptr};
+    fwd16_decode_block(g, blockIdx.x, &rb, &kvh, &batch);
+  }
+  if (a.causal) rb = a.rowBlocks - 1 - rb;   // later row blocks traverse more keys: start them first
+  const uint32_t n = min(a.lengths[batch], a.column);
+  const uint32_t qn = a.qlengths ? min(a.qlengths[batch], a.rows) : a.rows;
+  const uint32_t RB = a.RB, r0 = rb * RB;
+  if (r0 >= qn) return;   // no live row: nothing is read or written
+  uint32_t firstMasked, endTile;
+  prefill_tile_range(n, qn, r0, RB, a.causal, &firstMasked, &endTile);
+  const float kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
+  const float vscale = a.valueScale ? a.valueScale[kvh] : 1.0f;
+
+  // ---- the lane's packed row
+  const uint32_t M = a.G * RB;
+  const uint32_t p = (uint32_t)wave * 32u + (uint32_t)q, pc = min(p, M - 1);
+  const uint32_t qhead = kvh * a.G + pc / RB, rowt = r0 + pc % RB;
+  const bool live = p < M && rowt < qn;
+  const uint32_t row = min(rowt, qn - 1);   // (rows at or past qn are not read: the lane repeats the last live one)
+  v8 qf[NKS];
+  {
+    const char *qp = a.q + ((int64_t)batch * a.bsq + (int64_t)qhead * a.hsq + (int64_t)row * a.ldq) * 2;
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + (16 * s + 8 * hi) * 2));
+  }
+  // keys this row sees: c < lim
+  uint32_t lim = n;
+  if (a.causal) lim = min(lim, row + (n > qn ? n - qn : 0u) + 1u);
+
+  // ---- addresses of a 16-key group (wave-uniform; element offsets from a.k / a.v)
+  const int64_t ldk = a.ldk, ldv = a.ldv, psk = a.psk, psv = a.psv;   // (values, not fields of `a`: hipcc otherwise selects between
+  const bool paged = a.paged != 0;                                     //  the FIELDS' addresses and parks the block in scratch)
+  const int64_t khead = (int64_t)kvh * a.hsk, vhead = (int64_t)kvh * a.hsv;
+  const int64_t kseq = (int64_t)batch * a.bsk + khead, vseq = (int64_t)batch * a.bsv + vhead;
+  const int64_t tableRow = (int64_t)batch * a.tableStride;
+  const uint32_t pageShift = a.pageShift, pageMask = (1u << pageShift) - 1u;
+  auto group_offsets = [&](uint32_t key, int64_t &ko, int64_t &vo) MFA_PREFILL_INLINE {
+    if (paged) {
+      // (entries past the sequence's last page are never read)
+      const int64_t page = key < n ? (int64_t)a.table[tableRow + (key >> pageShift)] : 0;
+      const int64_t in = (int64_t)(key & pageMask);
+      ko = page * psk + khead + in * ldk;
+      vo = page * psv + vhead + in * ldv;
+    } else {
+      ko = kseq + (int64_t)key * ldk;
+      vo = vseq + (int64_t)key * ldv;
+    }
+  };
+
+  // ---- staging: instruction i of the workgroup covers rows i RPI .. + RPI - 1 of the tile whole; thread = (row lrow0, chunk lc).
+  // The rows of one wave-instruction lie inside one 16-key group (64 / CPR <= 16 consecutive rows, aligned), so its group is
+  // wave-uniform; a thread's row inside the group and its chunk do not depend on i.
+  static_assert(RPI % 16 == 0 && 64 / CPR <= 16, "the rows of a wave-instruction stay inside a 16-key group");
+  u32x4 kreg[NCH], vreg[NCH];
+  const int lrow0 = tid / CPR, lc = tid % CPR;
+  const int64_t kin = (int64_t)(lrow0 & 15) * ldk * ESZ + lc * 16, vin = (int64_t)(lrow0 & 15) * ldv * ESZ + lc * 16;   // bytes
+  auto issue_loads = [&](uint32_t key0) MFA_PREFILL_INLINE {
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int r = j * RPI + lrow0;
+      const uint32_t g = (uint32_t)__builtin_amdgcn_readfirstlane(r >> 4);
+      int64_t ko, vo;
+      group_offsets(key0 + 16u * g, ko, vo);
+      u32x4 zk = {0u, 0u, 0u, 0u}, zv = {0u, 0u, 0u, 0u};
+      if (key0 + (uint32_t)r < n) {   // rows at or past n are never loaded: zeros
+        zk = *reinterpret_cast<const u32x4 *>(a.k + ko * ESZ + kin);
+        zv = *reinterpret_cast<const u32x4 *>(a.v + vo * ESZ + vin);
+      }
+      kreg[j] = zk;
+      vreg[j] = zv;
+    }
+  };
+  // 16-bit chunk c (8 values of d) of key row r: K image row-major, chunk kswz(r, c); V image [D/32][64 keys][32 d]
+  auto write_lds = [&](int buf) MFA_PREFILL_INLINE {
+    char *Ks = smem + buf * STAGE, *Vs = Ks + KIMG;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int r = j * RPI + lrow0;
+      if constexpr (FP8) {
+        const int c = 2 * lc;
+        *reinterpret_cast<u32x4 *>(Ks + r * ROWB + kswz<D>(r, c) * 16) = cvt8_e4m3<T>(kreg[j][0], kreg[j][1]);
+        *reinterpret_cast<u32x4 *>(Ks + r * ROWB + kswz<D>(r, c + 1) * 16) = cvt8_e4m3<T>(kreg[j][2], kreg[j][3]);
+        char *dst = Vs + ((c >> 2) * PF_TILE + r) * 64 + (c & 3) * 16;
+        *reinterpret_cast<u32x4 *>(dst) = cvt8_e4m3<T>(vreg[j][0], vreg[j][1]);
+        *reinterpret_cast<u32x4 *>(dst + 16) = cvt8_e4m3<T>(vreg[j][2], vreg[j][3]);
+      } else {
+        *reinterpret_cast<u32x4 *>(Ks + r * ROWB + kswz<D>(r, lc) * 16) = kreg[j];
+        *reinterpret_cast<u32x4 *>(Vs + ((lc >> 2) * PF_TILE + r) * 64 + (lc & 3) * 16) = vreg[j];
+      }
+    }
+  };
+
+  f32x16 o[NDB];
+  float m = DEC_MINUS_HUGE, l = 0.f;
+#pragma unroll
+  for (int db = 0; db < NDB; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+
+  // tr read: lane n of a 16-lane group supplies row (n>>2), columns 4*(n&3)..+3 of a [4][16] block;
+  // group (lane>>4): bit0 = d half of the 32-wide d block, bit1 = hi   (dev/attn_fwd16.h)
+  const int n16 = lane & 15;
+  const int vtr_off = ((n16 >> 2) + 4 * hi) * 64 + (((lane >> 4) & 1) * 16 + 4 * (n16 & 3)) * 2;
+
+  // A fragment t of key row kr = 32 half + q: chunk kswz(kr, 2 t + hi).  The swizzle XORs the chunk with bits of the row that 32 half
+  // does not touch, 2 t + hi = 2 t ^ hi, and a row starts on a multiple of its own size (a power of two): the byte offset is
+  // (offset of t = 0, half = 0) ^ 32 t, plus 32 half rows -- one register and immediates.
+  static_assert((ROWB & (ROWB - 1)) == 0, "a K image row is a power of two");
+  const int kfrag0 = q * ROWB + kswz<D>(q, hi) * 16;
+
+  // step `half` (32 keys) of a tile from the images of `buf`; MASK = the per-element mask (tiles at or past first_masked)
+  auto compute = [&](auto maskTag, uint32_t key0, int buf, int half) MFA_PREFILL_INLINE {
+    constexpr bool MASK = decltype(maskTag)::value;
+    const char *Ks = smem + buf * STAGE, *Vs = Ks + KIMG;
+    {
+      const uint32_t cur = key0 + 32u * half;
+      // ---- S^T = K Q^T: s[r] = key cur + crow(r, hi), packed row q
+      f32x16 s;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+      for (int t = 0; t < NKS; ++t) {
+        const u32x4 kf = *reinterpret_cast<const u32x4 *>(Ks + 32 * half * ROWB + (kfrag0 ^ (32 * t)));
+        s = F::mfma(__builtin_bit_cast(v8, kf), qf[t], s);
+      }
+      // ---- online softmax over the visible keys only (the K scale rides on the softmax scale)
+      float mx = DEC_MINUS_HUGE;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bool visible = !MASK || cur + (uint32_t)crow(r, hi) < lim;
+        s[r] = visible ? s[r] * kscale : DEC_MINUS_HUGE;
+        mx = fmaxf(mx, s[r]);
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      if (mx > m) {
+        const float corr = fast_exp2(m - mx);
+        m = mx;
+        l *= corr;
+#pragma unroll
+        for (int db = 0; db < NDB; ++db)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) o[db][r] *= corr;
+      }
+      float psum = 0.f;
+      v8 pf[2];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bool visible = !MASK || cur + (uint32_t)crow(r, hi) < lim;
+        const float pr = visible ? fast_exp2(s[r] - m) : 0.f;   // replaced, never multiplied
+        psum += pr;
+        pf[r >> 3][r & 7] = (T)pr;
+      }
+      l += psum;
+      // ---- O^T += V^T P^T
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) {
+          const char *vp = Vs + (db * PF_TILE + 32 * half + 16 * u) * 64 + vtr_off;
+          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vp));
+          const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vp + 8 * 64));
+          const s16x8 both = __builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
+          o[db] = F::mfma(__builtin_bit_cast(v8, both), pf[u], o[db]);
+        }
+    }
+  };
+
+  // ---- the tiles: the loads of tile t + 1 fly under the arithmetic of tile t and land in the other buffer behind it.  One barrier
+  // per tile: the buffer written in iteration t was last read in iteration t - 1, which every wave left through that barrier.
+  if (endTile > 0) {
+    issue_loads(0u);
+    write_lds(0);
+  }
+  __syncthreads();
+  auto tile = [&](auto maskTag, uint32_t t) MFA_PREFILL_INLINE {
+    const bool more = t + 1 < endTile;
+    const int buf = (int)(t & 1u);
+    if (more) issue_loads((t + 1) * PF_TILE);
+    compute(maskTag, t * PF_TILE, buf, 0);
+    compute(maskTag, t * PF_TILE, buf, 1);
+    if (more) write_lds(buf ^ 1);
+    __syncthreads();
+  };
+  // (two loops, not one loop with the choice inside: with both forms of a step merging in one loop body hipcc spilled 6 .. 19 VGPRs
+  // of the D = 128 kernels; like this the largest takes 232 of 256)
+  uint32_t t = 0;
+  for (; t < firstMasked; ++t) tile(std::false_type{}, t);
+  for (; t < endTile; ++t) tile(std::true_type{}, t);
+
+  // ---- normalise and store straight from the accumulators: o[db][4 g + i] is d = 32 db + 8 g + 4 hi + i of the lane's row
+  const float l_tot = l + __shfl_xor(l, 32);
+  if (!live) return;
+  const float inv = l_tot > 0.f ? vscale / l_tot : 0.f;   // a row without a visible key: O = 0
+  const int64_t at = (int64_t)batch * a.bso + (int64_t)qhead * a.hso + (int64_t)rowt * a.ldo;
+#pragma unroll
+  for (int db = 0; db < NDB; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float x0 = o[db][4 * g] * inv, x1 = o[db][4 * g + 1] * inv, x2 = o[db][4 * g + 2] * inv, x3 = o[db][4 * g + 3] * inv;
+      const int64_t e = at + 32 * db + 8 * g + 4 * hi;
+      if (a.outF32) *reinterpret_cast<float4 *>(a.o + e * 4) = make_float4(x0, x1, x2, x3);
+      else *reinterpret_cast<u32x2 *>(a.o + e * 2) = u32x2{pack16<T>(x0, x1), pack16<T>(x2, x3)};
+    }
+  if (hi == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)qhead * a.lhs + rowt] = l_tot > 0.f ? m + log2f(l_tot) : DEC_MINUS_HUGE;
+}
+
+} // namespace mfa

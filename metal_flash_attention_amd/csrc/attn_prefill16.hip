@@ -1,0 +1,254 @@
+// attn_prefill16.hip -- prefill attention over a KV cache: the kernels' code objects and the C ABI of include/mfa_prefill.h.
+// (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstddef>
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+#include "../../include/mfa_prefill.h"
+#include "attn_prefill16.h"
+#include "launchers.h"
+#include "mfa_internal.h"
+
+using namespace mfa;
+
+// Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_prefill16_d<D>_<type>[_e4m3]
+#define MFA_PREFILL_KERNELS(TN, T, D)                                                                                                 \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16_d##D##_##TN(const PrefillArgs a) {                              \
+    prefill16_body<T, D, false>(a);                                                                                                   \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16_d##D##_##TN##_e4m3(const PrefillArgs a) {                       \
+    prefill16_body<T, D, true>(a);                                                                                                    \
+  }
+MFA_PREFILL_KERNELS(bf16, __bf16, 64)
+MFA_PREFILL_KERNELS(bf16, __bf16, 128)
+MFA_PREFILL_KERNELS(f16, _Float16, 64)
+MFA_PREFILL_KERNELS(f16, _Float16, 128)
+
+namespace {
+
+typedef void (*PrefillKernel)(const PrefillArgs);
+struct PrefillSet {
+  uint32_t D;
+  int precision;
+  uint32_t lds;
+  PrefillKernel plain, e4m3;
+  const char *plainName, *e4m3Name;
+};
+#define MFA_PREFILL_SET(TN, PREC, D)                                                                                                  \
+  {D, PREC, (uint32_t)prefill16_lds_bytes<D>(), attn_prefill16_d##D##_##TN, attn_prefill16_d##D##_##TN##_e4m3,                        \
+   "attn_prefill16_d" #D "_" #TN, "attn_prefill16_d" #D "_" #TN "_e4m3"}
+const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(f16, MFA_FP16, 64),
+                            MFA_PREFILL_SET(f16, MFA_FP16, 128)};
+
+mfa_status hip_fail(hipError_t err, const char *what) {
+  return fail(MFA_ERR_HIP, std::string(what) + ": " + hipGetErrorName(err) + " (" + hipGetErrorString(err) + ")");
+}
+
+struct PrefillPlan {
+  PrefillArgs args;
+  const PrefillSet *set;
+  bool fp8;
+  uint32_t blocks;   // batches x K/V heads x row blocks
+  PrefillKernel kernel() const { return fp8 ? set->e4m3 : set->plain; }
+  const char *name() const { return fp8 ? set->e4m3Name : set->plainName; }
+};
+
+bool multiple_of(int64_t x, int64_t n) { return x % n == 0; }
+
+// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind)
+mfa_status prepare(const mfa_prefill_params *p, PrefillPlan *plan) {
+  if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (p->precision == MFA_FP32)
+    return fail(MFA_ERR_UNSUPPORTED, "prefill attention takes a 16-bit Q (precision MFA_BF16 or MFA_FP16); FP32 Q has no kernel");
+  if (p->precision != MFA_BF16 && p->precision != MFA_FP16) return fail(MFA_ERR_INVALID_ARGUMENT, "precision must be MFA_FP16 or MFA_BF16");
+  if (p->outputPrecision != p->precision && p->outputPrecision != MFA_FP32)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "outputPrecision must be the inputs' 16-bit type or MFA_FP32");
+  if (p->cachePrecision == MFA_KV_E5M2)
+    return fail(MFA_ERR_UNSUPPORTED, "an FP8 KV cache is e4m3 (MFA_KV_E4M3, OCP e4m3fn); e5m2 caches have no kernel");
+  if (p->cachePrecision != MFA_KV_E4M3 && p->cachePrecision != p->precision)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "cachePrecision must be `precision` (a 16-bit cache of Q's type) or MFA_KV_E4M3");
+  const bool fp8 = p->cachePrecision == MFA_KV_E4M3;
+  if (!fp8 && (p->keyScale || p->valueScale))
+    return fail(MFA_ERR_INVALID_ARGUMENT, "keyScale / valueScale go with an e4m3 cache (cachePrecision MFA_KV_E4M3); a 16-bit cache holds the values themselves");
+  const PrefillSet *set = nullptr;
+  for (const PrefillSet &s : kSets)
+    if (s.D == p->headDimension && s.precision == p->precision) set = &s;
+  if (!set)
+    return fail(MFA_ERR_UNSUPPORTED, "prefill attention is compiled for head dimensions 64 and 128, not " + std::to_string(p->headDimension));
+  if (p->rows == 0 || p->column == 0 || p->heads == 0 || p->batches == 0)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "rows, column, heads and batches must be non-zero");
+  const uint32_t G = p->headsPerKeyValue > 1 ? p->headsPerKeyValue : 1;
+  if (G > MFA_PREFILL_MAX_GROUP)
+    return fail(MFA_ERR_UNSUPPORTED, "prefill attention packs the headsPerKeyValue query heads of a K/V head into one workgroup: headsPerKeyValue must be "
+                                     "at most 32, not " + std::to_string(G));
+  if (p->heads % G != 0)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "heads (" + std::to_string(p->heads) + ") must be a multiple of headsPerKeyValue (" + std::to_string(G) + ")");
+  if (!p->cacheLengths) return fail(MFA_ERR_INVALID_ARGUMENT, "cacheLengths is required (device array of `batches` uint32)");
+  uint32_t pageShift = 0;
+  if (p->pageSize) {
+    if (p->pageSize < 16 || p->pageSize > 1024 || (p->pageSize & (p->pageSize - 1)))
+      return fail(MFA_ERR_INVALID_ARGUMENT, "pageSize must be a power of two from 16 to 1024 (or 0: contiguous), not " + std::to_string(p->pageSize));
+    if (!p->blockTable) return fail(MFA_ERR_INVALID_ARGUMENT, "a paged launch (pageSize != 0) needs blockTable");
+    const int64_t pagesPerSequence = ((int64_t)p->column + p->pageSize - 1) / p->pageSize;
+    if (p->blockTableStride < pagesPerSequence)
+      return fail(MFA_ERR_INVALID_ARGUMENT, "blockTableStride must hold the " + std::to_string(pagesPerSequence) + " pages of `column` keys");
+    while ((1u << pageShift) < p->pageSize) ++pageShift;
+  }
+  static const char *names[4] = {"Q", "K", "V", "O"};
+  for (int i = 0; i < 4; ++i) {
+    const bool kv = i == 1 || i == 2;
+    const int64_t need = (i == 3) ? 4 : (kv && fp8) ? 16 : 8;   // 16-byte rows of Q, K, V; 8- or 16-byte stores of O
+    if (p->leadingDimension[i] < (int64_t)p->headDimension)
+      return fail(MFA_ERR_INVALID_ARGUMENT, std::string("leadingDimension of ") + names[i] + " is smaller than the head dimension");
+    bool ok = multiple_of(p->leadingDimension[i], need) && multiple_of(p->headStride[i], need);
+    if (!(kv && p->pageSize)) ok = ok && multiple_of(p->batchStride[i], need);
+    if (kv && p->pageSize) ok = ok && multiple_of(p->pageStride[i - 1], need);
+    if (!ok)
+      return fail(MFA_ERR_INVALID_ARGUMENT, std::string("strides of ") + names[i] + " must be multiples of " + std::to_string(need) +
+                                                (kv && fp8 ? " elements (16-byte rows of an e4m3 cache)"
+                                                           : " elements (16-byte rows for Q, K, V; whole 4-element stores for O)"));
+  }
+  const uint32_t RB = MFA_PREFILL_PACKED_ROWS / G;
+  const uint64_t rowBlocks = ((uint64_t)p->rows + RB - 1) / RB;
+  const uint64_t blocks = (uint64_t)p->batches * (p->heads / G) * rowBlocks;
+  if (blocks > 0x7fffffffull)
+    return fail(MFA_ERR_UNSUPPORTED, "batches x K/V heads x row blocks = " + std::to_string(blocks) + " workgroups exceed one grid (2^31 - 1)");
+  plan->set = set;
+  plan->fp8 = fp8;
+  plan->blocks = (uint32_t)blocks;
+  PrefillArgs &a = plan->args;
+  std::memset(&a, 0, sizeof(a));
+  a.lengths = p->cacheLengths;
+  a.qlengths = p->queryLengths;
+  a.table = p->blockTable;
+  a.tableStride = p->blockTableStride;
+  a.ldq = p->leadingDimension[0]; a.hsq = p->headStride[0]; a.bsq = p->batchStride[0];
+  a.ldk = p->leadingDimension[1]; a.hsk = p->headStride[1]; a.bsk = p->batchStride[1]; a.psk = p->pageStride[0];
+  a.ldv = p->leadingDimension[2]; a.hsv = p->headStride[2]; a.bsv = p->batchStride[2]; a.psv = p->pageStride[1];
+  a.ldo = p->leadingDimension[3]; a.hso = p->headStride[3]; a.bso = p->batchStride[3];
+  a.lhs = p->lHeadStride; a.lbs = p->lBatchStride;
+  a.keyScale = fp8 ? p->keyScale : nullptr;
+  a.valueScale = fp8 ? p->valueScale : nullptr;
+  a.rows = p->rows; a.G = G; a.RB = RB; a.rowBlocks = (uint32_t)rowBlocks; a.Hkv = p->heads / G; a.batches = p->batches;
+  a.column = p->column;
+  a.paged = p->pageSize != 0; a.pageShift = pageShift;
+  a.causal = p->causal != 0; a.outF32 = p->outputPrecision == MFA_FP32;
+  a.scale2 = 1.44269504089f / std::sqrt((float)p->headDimension);
+  return MFA_OK;
+}
+
+mfa_status bind(PrefillPlan *plan, const void *q, const void *k, const void *v, void *o, float *l) {
+  if (!q || !k || !v || !o) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if ((uintptr_t)q % 16 || (uintptr_t)k % 16 || (uintptr_t)v % 16 || (uintptr_t)o % 16)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "Q, K, V and O must be 16-byte aligned");
+  if ((uintptr_t)l % 4) return fail(MFA_ERR_INVALID_ARGUMENT, "L must be 4-byte aligned");
+  if ((uintptr_t)plan->args.keyScale % 4 || (uintptr_t)plan->args.valueScale % 4)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "keyScale and valueScale must be 4-byte aligned");
+  plan->args.q = (const char *)q; plan->args.k = (const char *)k; plan->args.v = (const char *)v;
+  plan->args.o = (char *)o; plan->args.l = l;
+  return MFA_OK;
+}
+
+hipError_t run(const PrefillPlan &plan, hipStream_t stream) {
+  const hipError_t err = launch_kernel(plan.kernel(), dim3(plan.blocks), dim3(PF_THREADS), plan.set->lds, stream, plan.args);
+  if (err != hipSuccess) return err;
+  return hipGetLastError();
+}
+
+} // namespace
+
+extern "C" {
+
+void mfa_prefill_params_init(mfa_prefill_params *params) {
+  if (!params) return;
+  std::memset(params, 0, sizeof(*params));
+  params->precision = params->outputPrecision = MFA_BF16;
+  params->cachePrecision = MFA_BF16;
+  params->headsPerKeyValue = 1;
+  params->causal = 1;
+}
+
+size_t mfa_prefill_params_size(void) { return sizeof(mfa_prefill_params); }
+
+mfa_status mfa_prefill_params_offsets(uint32_t *offsets, uint32_t capacity, uint32_t *count) {
+  if (!offsets || !count) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+#define MFA_OFF(f) (uint32_t)offsetof(mfa_prefill_params, f)
+  static const uint32_t table[] = {
+      MFA_OFF(rows), MFA_OFF(column), MFA_OFF(heads), MFA_OFF(batches), MFA_OFF(headsPerKeyValue), MFA_OFF(causal), MFA_OFF(headDimension),
+      MFA_OFF(precision), MFA_OFF(outputPrecision), MFA_OFF(pageSize), MFA_OFF(cacheLengths), MFA_OFF(queryLengths), MFA_OFF(blockTable),
+      MFA_OFF(blockTableStride), MFA_OFF(leadingDimension), MFA_OFF(headStride), MFA_OFF(batchStride), MFA_OFF(pageStride),
+      MFA_OFF(lHeadStride), MFA_OFF(lBatchStride), MFA_OFF(cachePrecision), MFA_OFF(reserved), MFA_OFF(keyScale), MFA_OFF(valueScale)};
+#undef MFA_OFF
+  const uint32_t total = (uint32_t)(sizeof(table) / sizeof(table[0]));
+  *count = total;
+  for (uint32_t i = 0; i < total && i < capacity; ++i) offsets[i] = table[i];
+  return MFA_OK;
+}
+
+mfa_status mfa_attention_prefill_tile_range(uint32_t length, uint32_t queryLength, uint32_t firstRow, uint32_t blockRows, uint32_t causal,
+                                            uint32_t *firstMasked, uint32_t *end) {
+  if (!firstMasked || !end) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (blockRows == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "blockRows must be non-zero");
+  prefill_tile_range(length, queryLength, firstRow, blockRows, causal, firstMasked, end);
+  return MFA_OK;
+}
+
+mfa_status mfa_attention_prefill_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                        void *stream) {
+  PrefillPlan plan;
+  mfa_status st = prepare(params, &plan);
+  if (st != MFA_OK) return st;
+  st = bind(&plan, q, k, v, o, l);
+  if (st != MFA_OK) return st;
+  const hipError_t err = run(plan, (hipStream_t)stream);
+  if (err != hipSuccess) return hip_fail(err, plan.name());
+  return MFA_OK;
+}
+
+mfa_status mfa_attention_prefill_launch_form(const mfa_prefill_params *params, char *out, size_t capacity) {
+  if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  out[0] = '\0';
+  PrefillPlan plan;
+  const mfa_status st = prepare(params, &plan);
+  if (st != MFA_OK) return st;
+  const PrefillArgs &a = plan.args;
+  char text[512];
+  std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s)", plan.name(),
+                plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous");
+  std::strncpy(out, text, capacity - 1);
+  out[capacity - 1] = '\0';
+  return MFA_OK;
+}
+
+mfa_status mfa_attention_prefill_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                      void *stream, int warmup, int iterations, float *milliseconds) {
+  if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
+  PrefillPlan plan;
+  mfa_status st = prepare(params, &plan);
+  if (st != MFA_OK) return st;
+  st = bind(&plan, q, k, v, o, l);
+  if (st != MFA_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  hipEvent_t start, stop;
+  hipError_t err = hipEventCreate(&start);
+  if (err != hipSuccess) return hip_fail(err, "hipEventCreate");
+  err = hipEventCreate(&stop);
+  if (err != hipSuccess) { (void)hipEventDestroy(start); return hip_fail(err, "hipEventCreate"); }
+  for (int i = 0; i < warmup && err == hipSuccess; ++i) err = run(plan, s);
+  if (err == hipSuccess) err = hipEventRecord(start, s);
+  for (int i = 0; i < iterations && err == hipSuccess; ++i) err = run(plan, s);
+  if (err == hipSuccess) err = hipEventRecord(stop, s);
+  if (err == hipSuccess) err = hipEventSynchronize(stop);
+  if (err == hipSuccess) err = hipGetLastError();
+  if (err == hipSuccess) err = hipEventElapsedTime(milliseconds, start, stop);
+  (void)hipEventDestroy(start);
+  (void)hipEventDestroy(stop);
+  if (err != hipSuccess) return hip_fail(err, plan.name());
+  return MFA_OK;
+}
+
+} // extern "C"

@@ -28,7 +28,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCachePrecision)
 
 _KERNELS: Dict[Tuple, AttentionKernel] = {}
@@ -537,4 +537,121 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
         o, l = torch.ops.mfa.attention_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)
     else:
         o, l = _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)
+    return (o, l * 0.6931471805599453) if return_lse else o
+
+
+# ---- prefill attention over a KV cache (include/mfa_prefill.h): a block of new rows per sequence against a 16-bit or FP8 cache
+_PREFILLERS: Dict[Tuple, AttentionPrefill] = {}
+
+
+def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale):
+    who = "flash_prefill"
+    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{who}: q must be bfloat16 or float16")
+    if fp8:
+        if k_cache.dtype != v_cache.dtype or k_cache.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"{who}: an FP8 KV cache is torch.float8_e4m3fn for both K and V (got {k_cache.dtype}, {v_cache.dtype}); "
+                            "e5m2 and fnuz caches have no kernel")
+    elif k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise TypeError(f"{who}: q and the caches must share one of bfloat16 / float16 (or the caches are float8_e4m3fn)")
+    elif k_scale is not None or v_scale is not None:
+        raise ValueError(f"{who}: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache holds the values themselves")
+    paged = block_table is not None
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[3] != k_cache.shape[3] or k_cache.shape[1] == 0 or \
+            q.shape[1] % k_cache.shape[1] != 0 or (not paged and k_cache.shape[0] != q.shape[0]):
+        raise ValueError(f"{who}: expected q [B, H, R, D] and caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) with H a "
+                         f"multiple of Hkv (got q {tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)})")
+    B, H, R, D = q.shape
+    Hkv = k_cache.shape[1]
+    for name, t in (("cache_lengths", cache_lengths), ("q_lengths", q_lengths)):
+        if t is not None and (not t.is_cuda or t.shape != (B,) or t.dtype not in (torch.int32, torch.int64)):
+            raise ValueError(f"{who}: {name} must be a GPU tensor [B] = [{B}] int32 or int64 (got {tuple(t.shape)}, {t.dtype})")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
+            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is never copied)")
+    kw = {}
+    if paged:
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
+                not block_table.is_cuda:
+            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
+                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
+        page = int(k_cache.shape[2])
+        column = page * int(block_table.shape[1])
+        kw = dict(pageSize=page, blockTable=block_table, blockTableStride=int(block_table.stride(0)),
+                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
+    else:
+        column = int(k_cache.shape[2])
+    q = q if q.stride(3) == 1 and all(st >= 0 for st in q.stride()) else q.contiguous()
+    lengths = cache_lengths.to(torch.int32)   # (no copy when it already is; stays on the device)
+    qlens = None if q_lengths is None else q_lengths.to(torch.int32)
+    # (rows at or past q_lengths[b] are not written by the launch: no memset is spent on them, they come back uninitialised)
+    o = torch.empty((B, H, R, D), dtype=q.dtype, device=q.device)
+    l = torch.empty((B, H, R), dtype=torch.float32, device=q.device)
+    key = (q.dtype, D, bool(fp8))
+    pre = _PREFILLERS.get(key)
+    if pre is None:
+        pre = _PREFILLERS[key] = AttentionPrefill(D, P.BF16 if q.dtype == torch.bfloat16 else P.FP16,
+                                                  cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
+    if fp8:
+        kw.update(keyScale=_scale_operand(who, "k_scale", k_scale, Hkv, q.device), valueScale=_scale_operand(who, "v_scale", v_scale, Hkv, q.device))
+    kw.update(rows=R, column=column, heads=H, batches=B, headsPerKeyValue=H // Hkv, causal=bool(causal), cacheLengths=lengths,
+              queryLengths=qlens,
+              strides=dict(Q=(int(q.stride(2)) if R > 1 else D, int(q.stride(1)), int(q.stride(0))),
+                           K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
+    with torch.cuda.device(q.device):
+        pre.dispatch(q, k_cache, v_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
+    return o, l
+
+
+def _register_prefill_op():
+    if not hasattr(torch.library, "custom_op"):
+        return False
+    try:
+        torch.ops.mfa.attention_prefill  # noqa: B018 -- AttributeError when the op is not defined yet
+        return True
+    except (AttributeError, RuntimeError):
+        pass
+
+    @torch.library.custom_op("mfa::attention_prefill", mutates_args=(), device_types="cuda")
+    def _op_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                    q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
+                    k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
+
+    @_op_prefill.register_fake
+    def _op_prefill_fake(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale):
+        B, H, R, D = q.shape
+        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
+
+    return True
+
+
+_HAVE_PREFILL_OP = _register_prefill_op()
+
+
+def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                  q_lengths: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None, causal: bool = True,
+                  k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, return_lse: bool = False):
+    """Attention of a BLOCK of new rows of every sequence (q [B, H, R, D], any R: a chunk of a prompt, a reused prefix's tail, a long
+    speculative block) against its KV cache, which already holds the new tokens (kv_cache_append first).  cache_lengths [B] (GPU):
+    valid keys per sequence INCLUDING the new tokens; q_lengths [B] (GPU, None = R for every sequence): the new rows of sequence b,
+    its first q_lengths[b] rows of q.  With `causal` row r sees key c iff c <= r + max(len - q_len, 0).  Rows at or past q_lengths[b]
+    are not written: they come back uninitialised, in O and in L.  A live row without a visible key gets O = 0 (L: -FLT_MAX ln 2).  Caches: flash_decode's -- [B, Hkv, C, D] or any view of that shape
+    with a contiguous last dimension, or with block_table [B, n] int32 page pools [pages, Hkv, pageSize, D]; bfloat16 / float16 like
+    q, or torch.float8_e4m3fn with k_scale / v_scale [Hkv] fp32 on the GPU (None = 1.0; a byte of head j stands for scale[j] x
+    e4m3(byte)).  The G = H / Hkv query heads of a K/V head share one workgroup (G <= 32), so K and V are read once per group.
+    Forward only.  return_lse: also L [B, H, R] fp32 in natural units.  Goes through the torch.library op `mfa::attention_prefill`
+    where torch has custom ops, so it traces under torch.compile."""
+    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
+        raise RuntimeError("flash_prefill: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, k_cache, v_cache):
+        if t.requires_grad:
+            raise RuntimeError("flash_prefill is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
+    if _HAVE_PREFILL_OP:
+        o, l = torch.ops.mfa.attention_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
+    else:
+        o, l = _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
     return (o, l * 0.6931471805599453) if return_lse else o
