@@ -17,8 +17,23 @@
 //     m = -FLT_MAX, l = 0.
 //   * SPLIT: piece p of sequence b takes decode_piece_range(len_b, pieces, p) -- the same function the host exports -- and publishes
 //     un-normalised O, m, l in FP32 (wsO [pieces][B Hq R][D], wsML [pieces][B Hq R][2]); attn_decode16_combine merges them.
+//
+// FP8: the same body over an FP8 (OCP e4m3) KV cache (include/mfa_kvcache.h), K and V read as bytes.  Everything above
+// holds, and so do decode_piece_range, the workspace slabs and the combine kernel.  What the parameter switches:
+//   * Q stays 16-bit; K and V bytes are CONVERTED in registers to the launch's 16-bit type (cvt8_e4m3, kv_e4m3.h: exact) and feed the
+//     same v_mfma_f32_32x32x16.  The FP8 matrix instruction is not used: the kernel is bound by bytes, not by the matrix pipe.
+//   * K: a lane is still a key row, but a 16-byte load now spans 16 values of d.  The loads stay 16 bytes wide (half as many per step)
+//     and the contraction index is permuted instead: matrix step 2u + v of the lane half `hi` contracts d = 32 u + 16 hi + 8 v .. + 7,
+//     the bytes 8 v .. 8 v + 7 of load u, and the Q fragments are loaded with the same permutation.  The raw bytes wait in registers;
+//     a slice is converted at its matrix instruction.
+//   * V: 16-byte loads of whole rows (half as many per step), converted before the LDS write, so that the wave's V image
+//     [D/32][32 keys][32 d] and the ds_read_b64_tr_b16 gather are those of the 16-bit kernel.
+//   * the scales are per K / V head: keyScale folds into the softmax scale, valueScale into the final normalisation (pieces: into
+//     the un-normalised O they publish, so that the combine kernel needs no change).  The 16-bit kernels read neither.
+//   * poison: rows at or past the piece's end are not loaded (zero bytes = +0.0), so a 0x7f beyond a length never reaches a product.
 #pragma once
 #include "attn_fwd16_common.h"
+#include "kv_e4m3.h"
 
 namespace mfa {
 
@@ -35,7 +50,7 @@ struct DecodeArgs {
   const int32_t *table;           // paged launches
   int64_t tableStride;
   int64_t ldq, hsq, bsq;          // elements
-  int64_t ldk, hsk, bsk, psk;
+  int64_t ldk, hsk, bsk, psk;     // (K, V of an e4m3 cache: an element is a byte)
   int64_t ldv, hsv, bsv, psv;
   int64_t ldo, hso, bso;
   int64_t lhs, lbs;
@@ -45,6 +60,7 @@ struct DecodeArgs {
   uint32_t pieces;
   float scale2;                   // log2(e) / sqrt(D)
   float *wsO, *wsML;
+  const float *keyScale, *valueScale;   // e4m3 caches, per K / V head; null: 1.0
 };
 
 // keys [*begin, *end) of piece `piece` of `pieces` for a sequence of `length` keys: an equal share of the sequence's whole 64-key
@@ -66,16 +82,18 @@ template <int D> constexpr int decode16_lds_bytes() {
   return images > merge ? images : merge;
 }
 
-template <typename T, int D, bool SPLIT>
-__device__ __forceinline__ void decode16_body(const DecodeArgs &a) {
+template <typename T, int D, bool SPLIT, bool FP8>
+__device__ __forceinline__ void decode_body(const DecodeArgs &a) {
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NDB = D / 32, NKS = D / 16;
-  constexpr int CPR = D / 8;                   // 16-byte chunks per row
+  constexpr int ESZ = FP8 ? 1 : 2;             // bytes of a cache element
+  constexpr int NDB = D / 32, NKS = D / 16;    // matrix steps along d
+  constexpr int NKL = D * ESZ / 32;            // 16-byte K loads per lane
+  constexpr int CPR = D * ESZ / 16;            // 16-byte chunks per row
   constexpr int RPI = 64 / CPR;                // V rows one wave-instruction covers
   constexpr int NCH = DEC_STEP / RPI;          // V chunks per lane per step
-  constexpr int IMAGE = DEC_STEP * D * 2;      // bytes of a wave's V image
+  constexpr int IMAGE = DEC_STEP * D * 2;      // bytes of a wave's V image (16-bit values)
   static_assert(16 % RPI == 0, "a lane's V rows of one instruction stay inside a 16-key group");
 
   const int tid = threadIdx.x;
@@ -88,21 +106,30 @@ __device__ __forceinline__ void decode16_body(const DecodeArgs &a) {
   const uint32_t len = min(a.lengths[batch], a.column);
   uint32_t begin = 0, end = len;
   if constexpr (SPLIT) decode_piece_range(len, a.pieces, piece, &begin, &end);
+  float kscale = a.scale2, vscale = 1.0f;   // (16-bit: scale2 as it stands, and vscale is never used)
+  if constexpr (FP8) {
+    kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
+    vscale = a.valueScale ? a.valueScale[kvh] : 1.0f;
+  }
 
   // ---- the lane's packed query row: p = (query head within the group) R + row; columns >= M repeat the last one and are not stored
+  // (FP8: its fragments in the permuted contraction order of the K bytes)
   const uint32_t pc = min((uint32_t)q, M - 1);
   const uint32_t qhead = kvh * a.G + pc / R, qrow = pc % R;
   v8 qf[NKS];
   {
     const char *qp = a.q + ((int64_t)batch * a.bsq + (int64_t)qhead * a.hsq + (int64_t)qrow * a.ldq) * 2;
 #pragma unroll
-    for (int s = 0; s < NKS; ++s) qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + (16 * s + 8 * hi) * 2));
+    for (int s = 0; s < NKS; ++s) {
+      const int d0 = FP8 ? 32 * (s >> 1) + 16 * hi + 8 * (s & 1) : 16 * s + 8 * hi;
+      qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + d0 * 2));
+    }
   }
   // keys this row sees: c < lim  (causal: c <= row + max(len - R, 0); always c < len, and inside this piece c < end)
   uint32_t lim = end;
   if (a.causal) lim = min(lim, qrow + (len > R ? len - R : 0u) + 1u);
 
-  // ---- addresses of a step's two 16-key groups (wave-uniform; element offsets from a.k / a.v)
+  // ---- addresses of a step's two 16-key groups (wave-uniform; element offsets from a.k / a.v, which are byte offsets under FP8)
   const int64_t khead = (int64_t)kvh * a.hsk, vhead = (int64_t)kvh * a.hsv;
   const uint32_t pageMask = (1u << a.pageShift) - 1u;
   auto group_offsets = [&](uint32_t key0, int64_t (&ko)[2], int64_t (&vo)[2]) {
@@ -122,16 +149,19 @@ __device__ __forceinline__ void decode16_body(const DecodeArgs &a) {
     }
   };
 
-  // K: lane = key row q of the step, chunks 2t + hi (the A operand as it stands).  V: instruction i covers rows i RPI .. + RPI - 1 whole.
-  u32x4 kreg[NKS], vreg[NCH];
+  // K: lane = key row q of the step, chunks 2t + hi (the A operand as it stands; FP8: bytes 32 t + 16 hi .. + 15 of the row).
+  // V: instruction i covers rows i RPI .. + RPI - 1 whole.
+  u32x4 kreg[NKL], vreg[NCH];
   const int vrow0 = lane / CPR, vc = lane % CPR;
   auto issue_loads = [&](uint32_t key0) {
     int64_t ko[2], vo[2];
     group_offsets(key0, ko, vo);
     const bool kvalid = key0 + (uint32_t)q < end;
-    const char *kp = a.k + ((q >> 4 ? ko[1] : ko[0]) + (int64_t)(q & 15) * a.ldk + 8 * hi) * 2;
+    const char *kp;
+    if constexpr (FP8) kp = a.k + (q >> 4 ? ko[1] : ko[0]) + (int64_t)(q & 15) * a.ldk + 16 * hi;
+    else kp = a.k + ((q >> 4 ? ko[1] : ko[0]) + (int64_t)(q & 15) * a.ldk + 8 * hi) * 2;
 #pragma unroll
-    for (int t = 0; t < NKS; ++t) {
+    for (int t = 0; t < NKL; ++t) {
       u32x4 z = {0u, 0u, 0u, 0u};
       if (kvalid) z = *reinterpret_cast<const u32x4 *>(kp + 32 * t);
       kreg[t] = z;
@@ -140,8 +170,10 @@ __device__ __forceinline__ void decode16_body(const DecodeArgs &a) {
     for (int i = 0; i < NCH; ++i) {
       const int row = i * RPI + vrow0;
       u32x4 z = {0u, 0u, 0u, 0u};
-      if (key0 + (uint32_t)row < end)
-        z = *reinterpret_cast<const u32x4 *>(a.v + (vo[(i * RPI) >> 4] + (int64_t)(row & 15) * a.ldv + vc * 8) * 2);
+      if (key0 + (uint32_t)row < end) {
+        if constexpr (FP8) z = *reinterpret_cast<const u32x4 *>(a.v + vo[(i * RPI) >> 4] + (int64_t)(row & 15) * a.ldv + vc * 16);
+        else z = *reinterpret_cast<const u32x4 *>(a.v + (vo[(i * RPI) >> 4] + (int64_t)(row & 15) * a.ldv + vc * 8) * 2);
+      }
       vreg[i] = z;
     }
   };
@@ -167,24 +199,38 @@ __device__ __forceinline__ void decode16_body(const DecodeArgs &a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
-    for (int t = 0; t < NKS; ++t) s = F::mfma(__builtin_bit_cast(v8, kreg[t]), qf[t], s);
+    for (int t = 0; t < NKS; ++t) {
+      if constexpr (FP8) {   // a slice of K is converted at its matrix instruction
+        const u32x4 kb = kreg[t >> 1];
+        const u32x4 kf = (t & 1) ? cvt8_e4m3<T>(kb[2], kb[3]) : cvt8_e4m3<T>(kb[0], kb[1]);
+        s = F::mfma(__builtin_bit_cast(v8, kf), qf[t], s);
+      } else {
+        s = F::mfma(__builtin_bit_cast(v8, kreg[t]), qf[t], s);
+      }
+    }
     // ---- V rows to the wave's image (the image's previous reads were issued before these writes: one wave, in order)
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int row = i * RPI + vrow0;
-      *reinterpret_cast<u32x4 *>(Vs + ((vc >> 2) * DEC_STEP + row) * 64 + (vc & 3) * 16) = vreg[i];
+      if constexpr (FP8) {   // converted: a lane's 16 values of d are the 16-bit chunks 2 vc and 2 vc + 1 of its row
+        char *dst = Vs + ((vc >> 1) * DEC_STEP + row) * 64 + (vc & 1) * 32;
+        *reinterpret_cast<u32x4 *>(dst) = cvt8_e4m3<T>(vreg[i][0], vreg[i][1]);
+        *reinterpret_cast<u32x4 *>(dst + 16) = cvt8_e4m3<T>(vreg[i][2], vreg[i][3]);
+      } else {
+        *reinterpret_cast<u32x4 *>(Vs + ((vc >> 2) * DEC_STEP + row) * 64 + (vc & 3) * 16) = vreg[i];
+      }
     }
     // ---- the registers are free: the next step's loads fly during the rest of this one
     const uint32_t cur = key0;
     key0 += DEC_WAVES * DEC_STEP;
     if (key0 < end) issue_loads(key0);
 
-    // ---- online softmax over the visible keys only
+    // ---- online softmax over the visible keys only (FP8: the K scale rides on the softmax scale)
     float mx = DEC_MINUS_HUGE;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const bool visible = cur + (uint32_t)crow(r, hi) < lim;
-      s[r] = visible ? s[r] * a.scale2 : DEC_MINUS_HUGE;
+      s[r] = visible ? s[r] * kscale : DEC_MINUS_HUGE;
       mx = fmaxf(mx, s[r]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -222,7 +268,8 @@ __device__ __forceinline__ void decode16_body(const DecodeArgs &a) {
       }
   }
 
-  // ---- merge the four waves through LDS: m* = max m_w, weights exp2(m_w - m*), sums of l and O
+  // ---- merge the four waves through LDS: m* = max m_w, weights exp2(m_w - m*), sums of l and O (FP8: the V scale multiplies what
+  // leaves the workgroup)
   constexpr int OLD = D + 4;
   float *Om = reinterpret_cast<float *>(smem);                       // [waves][32][OLD]
   float *ms = Om + DEC_WAVES * 32 * OLD, *ls = ms + DEC_WAVES * 32;   // [waves][32] each
@@ -261,10 +308,11 @@ __device__ __forceinline__ void decode16_body(const DecodeArgs &a) {
     const uint32_t head = kvh * a.G + p / R, row = p % R;
     if constexpr (SPLIT) {
       const size_t slab = (((size_t)piece * a.batches + batch) * a.Hq + head) * R + row;
+      if constexpr (FP8) { acc.x *= vscale; acc.y *= vscale; acc.z *= vscale; acc.w *= vscale; }
       *reinterpret_cast<float4 *>(a.wsO + slab * D + 4 * c) = acc;
       if (c == 0) *reinterpret_cast<float2 *>(a.wsML + slab * 2) = make_float2(mrow, lsum);
     } else {
-      const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;   // a sequence of length 0: O = 0
+      const float inv = lsum > 0.f ? (FP8 ? vscale : 1.0f) / lsum : 0.f;   // a sequence of length 0: O = 0
       acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
       const int64_t at = (int64_t)batch * a.bso + (int64_t)head * a.hso + (int64_t)row * a.ldo + 4 * c;
       if (a.outF32) *reinterpret_cast<float4 *>(a.o + at * 4) = acc;

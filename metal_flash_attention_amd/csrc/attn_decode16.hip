@@ -1,4 +1,7 @@
-// attn_decode16.hip -- decode attention over a KV cache: the kernels' code objects and the C ABI of include/mfa_decode.h.
+// attn_decode16.hip -- decode attention over a KV cache, 16-bit or FP8 (e4m3): the kernels' code objects, the C ABI of
+// include/mfa_decode.h and the decode entries of include/mfa_kvcache.h.  One plan serves both: the launch over an e4m3 cache adds its
+// own checks in front of the 16-bit launch's, starts the attn_decode8_* kernels in place of _single / _pieces, and shares the piece
+// count, the workspace formula and the combine kernel.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
 
@@ -8,20 +11,28 @@
 #include <string>
 
 #include "../../include/mfa_decode.h"
+#include "../../include/mfa_kvcache.h"
 #include "attn_decode16.h"
-#include "attn_decode_plan.h"
+#include "cache_launch.h"
 #include "launchers.h"
 #include "mfa_internal.h"
 
 using namespace mfa;
 
-// Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_decode16_d<D>_<type>_{single,pieces,combine}
+// Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_decode16_d<D>_<type>_{single,pieces,combine} and, over
+// an e4m3 cache, attn_decode8_d<D>_<type of Q>_{single,pieces}, whose pieces attn_decode16_d<D>_<type>_combine merges
 #define MFA_DECODE_KERNELS(TN, T, D)                                                                                                  \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16_d##D##_##TN##_single(const DecodeArgs a) {                       \
-    decode16_body<T, D, false>(a);                                                                                                    \
+    decode_body<T, D, false, false>(a);                                                                                               \
   }                                                                                                                                   \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16_d##D##_##TN##_pieces(const DecodeArgs a) {                       \
-    decode16_body<T, D, true>(a);                                                                                                     \
+    decode_body<T, D, true, false>(a);                                                                                                \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8_d##D##_##TN##_single(const DecodeArgs a) {                        \
+    decode_body<T, D, false, true>(a);                                                                                                \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8_d##D##_##TN##_pieces(const DecodeArgs a) {                        \
+    decode_body<T, D, true, true>(a);                                                                                                 \
   }                                                                                                                                   \
   extern "C" __global__ __launch_bounds__(256) void attn_decode16_d##D##_##TN##_combine(const DecodeArgs a) {                         \
     decode16_combine_body<T, D>(a);                                                                                                   \
@@ -38,19 +49,17 @@ struct DecodeSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  DecodeKernel single, pieces, combine;
-  const char *singleName, *piecesName, *combineName;
+  DecodeKernel single[2], pieces[2], combine;   // [fp8]
+  const char *singleName[2], *piecesName[2], *combineName;
 };
 #define MFA_DECODE_SET(TN, PREC, D)                                                                                                   \
-  {D, PREC, (uint32_t)decode16_lds_bytes<D>(), attn_decode16_d##D##_##TN##_single, attn_decode16_d##D##_##TN##_pieces,                \
-   attn_decode16_d##D##_##TN##_combine, "attn_decode16_d" #D "_" #TN "_single", "attn_decode16_d" #D "_" #TN "_pieces",              \
-   "attn_decode16_d" #D "_" #TN "_combine"}
+  {D, PREC, (uint32_t)decode16_lds_bytes<D>(),                                                                                        \
+   {attn_decode16_d##D##_##TN##_single, attn_decode8_d##D##_##TN##_single},                                                           \
+   {attn_decode16_d##D##_##TN##_pieces, attn_decode8_d##D##_##TN##_pieces}, attn_decode16_d##D##_##TN##_combine,                      \
+   {"attn_decode16_d" #D "_" #TN "_single", "attn_decode8_d" #D "_" #TN "_single"},                                                   \
+   {"attn_decode16_d" #D "_" #TN "_pieces", "attn_decode8_d" #D "_" #TN "_pieces"}, "attn_decode16_d" #D "_" #TN "_combine"}
 const DecodeSet kSets[] = {MFA_DECODE_SET(bf16, MFA_BF16, 64), MFA_DECODE_SET(bf16, MFA_BF16, 128), MFA_DECODE_SET(f16, MFA_FP16, 64),
                            MFA_DECODE_SET(f16, MFA_FP16, 128)};
-
-mfa_status hip_fail(hipError_t err, const char *what) {
-  return fail(MFA_ERR_HIP, std::string(what) + ": " + hipGetErrorName(err) + " (" + hipGetErrorString(err) + ")");
-}
 
 // Pieces of the keys: chosen from the workgroups the launch has without a split (batches x K/V heads) and `column` only -- the lengths
 // live on the device.  Aims at MFA_DECODE_WORKGROUP_TARGET workgroups (two per compute unit of a 256-CU chip, what choose_splits of
@@ -71,16 +80,32 @@ uint64_t pieces_workspace_bytes(uint32_t pieces, const mfa_decode_params *p) {
 struct DecodePlan {
   DecodeArgs args;
   const DecodeSet *set;
+  bool fp8;
   uint32_t pieces;      // as the launch runs: 1 without a workspace
   uint32_t planned;     // what the host would cut the keys into
   uint32_t blocks;      // batches x K/V heads
+  // the kernel that reads the cache, and the name a HIP failure is reported under
+  const char *name() const { return pieces > 1 ? set->piecesName[fp8] : set->singleName[fp8]; }
 };
 
-bool multiple_of(int64_t x, int64_t n) { return x % n == 0; }
-
-// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by the launch)
-mfa_status prepare(const mfa_decode_params *p, DecodePlan *plan) {
+// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `quant` is null for a
+// 16-bit cache; an e4m3 cache puts its own checks first, then the 16-bit launch's
+mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, DecodePlan *plan) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (quant) {
+    bool e4m3;
+    const mfa_status st = check_cache_precision(quant->cachePrecision, &e4m3);
+    if (st != MFA_OK) return st;
+    if (!e4m3)
+      return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_kv_quant.cachePrecision must be MFA_KV_E4M3 (16-bit caches: mfa_attention_decode_launch)");
+    if (p->precision == MFA_FP32)
+      return fail(MFA_ERR_UNSUPPORTED, "decode attention over an e4m3 cache takes a 16-bit Q (precision MFA_BF16 or MFA_FP16); FP32 Q has no kernel");
+    for (int i = 1; i <= 2; ++i) {
+      const mfa_status ok = check_stride_multiples(i == 1 ? "K" : "V", p->leadingDimension[i], p->headStride[i],
+                                                   p->pageSize ? p->pageStride[i - 1] : p->batchStride[i], 16, "(16-byte rows of an e4m3 cache)");
+      if (ok != MFA_OK) return ok;
+    }
+  }
   if (p->precision == MFA_FP32)
     return fail(MFA_ERR_UNSUPPORTED, "decode attention reads 16-bit caches (MFA_BF16 or MFA_FP16); an FP32 cache has no kernel");
   if (p->precision != MFA_BF16 && p->precision != MFA_FP16) return fail(MFA_ERR_INVALID_ARGUMENT, "precision must be MFA_FP16 or MFA_BF16");
@@ -102,29 +127,19 @@ mfa_status prepare(const mfa_decode_params *p, DecodePlan *plan) {
                                          "mfa_attention_kernel_launch with headsPerKeyValue, columnLengths and causal");
   if (!p->cacheLengths) return fail(MFA_ERR_INVALID_ARGUMENT, "cacheLengths is required (device array of `batches` uint32)");
   uint32_t pageShift = 0;
-  if (p->pageSize) {
-    if (p->pageSize < 16 || p->pageSize > 1024 || (p->pageSize & (p->pageSize - 1)))
-      return fail(MFA_ERR_INVALID_ARGUMENT, "pageSize must be a power of two from 16 to 1024 (or 0: contiguous), not " + std::to_string(p->pageSize));
-    if (!p->blockTable) return fail(MFA_ERR_INVALID_ARGUMENT, "a paged launch (pageSize != 0) needs blockTable");
-    const int64_t pagesPerSequence = ((int64_t)p->column + p->pageSize - 1) / p->pageSize;
-    if (p->blockTableStride < pagesPerSequence)
-      return fail(MFA_ERR_INVALID_ARGUMENT, "blockTableStride must hold the " + std::to_string(pagesPerSequence) + " pages of `column` keys");
-    while ((1u << pageShift) < p->pageSize) ++pageShift;
-  }
+  mfa_status st = check_paging(p->pageSize, p->blockTable, p->blockTableStride, p->column, &pageShift);
+  if (st != MFA_OK) return st;
   static const char *names[4] = {"Q", "K", "V", "O"};
   for (int i = 0; i < 4; ++i) {
     const int64_t need = (i == 3) ? 4 : 8;   // 16-byte rows of Q, K, V; 8- or 16-byte stores of O
     const bool kv = i == 1 || i == 2;
-    if (p->leadingDimension[i] < (int64_t)p->headDimension)
-      return fail(MFA_ERR_INVALID_ARGUMENT, std::string("leadingDimension of ") + names[i] + " is smaller than the head dimension");
-    bool ok = multiple_of(p->leadingDimension[i], need) && multiple_of(p->headStride[i], need);
-    if (!(kv && p->pageSize)) ok = ok && multiple_of(p->batchStride[i], need);
-    if (kv && p->pageSize) ok = ok && multiple_of(p->pageStride[i - 1], need);
-    if (!ok)
-      return fail(MFA_ERR_INVALID_ARGUMENT, std::string("strides of ") + names[i] + " must be multiples of " + std::to_string(need) +
-                                                " elements (16-byte rows for Q, K, V; whole 4-element stores for O)");
+    st = check_operand_strides(names[i], p->headDimension, p->leadingDimension[i], p->headStride[i],
+                               kv && p->pageSize ? p->pageStride[i - 1] : p->batchStride[i], need,
+                               "(16-byte rows for Q, K, V; whole 4-element stores for O)");
+    if (st != MFA_OK) return st;
   }
   plan->set = set;
+  plan->fp8 = quant != nullptr;
   plan->blocks = p->batches * (p->heads / G);
   plan->planned = choose_pieces(plan->blocks, p->column);
   plan->pieces = plan->planned;
@@ -155,14 +170,15 @@ mfa_status prepare(const mfa_decode_params *p, DecodePlan *plan) {
     a.wsO = (float *)p->workspace;
     a.wsML = a.wsO + (uint64_t)plan->pieces * p->batches * p->heads * p->rows * p->headDimension;
   }
+  if (quant) { a.keyScale = quant->keyScale; a.valueScale = quant->valueScale; }
   return MFA_OK;
 }
 
 mfa_status bind(DecodePlan *plan, const void *q, const void *k, const void *v, void *o, float *l) {
-  if (!q || !k || !v || !o) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  if ((uintptr_t)q % 16 || (uintptr_t)k % 16 || (uintptr_t)v % 16 || (uintptr_t)o % 16)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "Q, K, V and O must be 16-byte aligned");
-  if ((uintptr_t)l % 4) return fail(MFA_ERR_INVALID_ARGUMENT, "L must be 4-byte aligned");
+  mfa_status st = check_buffers({q, k, v, o}, "Q, K, V and O");
+  if (st == MFA_OK) st = check_float_arrays({l}, "L");
+  if (st == MFA_OK) st = check_float_arrays({plan->args.keyScale, plan->args.valueScale}, "keyScale and valueScale");
+  if (st != MFA_OK) return st;
   plan->args.q = (const char *)q; plan->args.k = (const char *)k; plan->args.v = (const char *)v;
   plan->args.o = (char *)o; plan->args.l = l;
   return MFA_OK;
@@ -172,36 +188,76 @@ hipError_t run(const DecodePlan &plan, hipStream_t stream) {
   const DecodeSet &s = *plan.set;
   hipError_t err;
   if (plan.pieces > 1) {
-    err = launch_kernel(s.pieces, dim3(plan.blocks * plan.pieces), dim3(256), s.lds, stream, plan.args);
+    err = launch_kernel(s.pieces[plan.fp8], dim3(plan.blocks * plan.pieces), dim3(256), s.lds, stream, plan.args);
     if (err != hipSuccess) return err;
     const uint64_t rows = (uint64_t)plan.args.batches * plan.args.Hq * plan.args.R;
     err = launch_kernel(s.combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, plan.args);
   } else {
-    err = launch_kernel(s.single, dim3(plan.blocks), dim3(256), s.lds, stream, plan.args);
+    err = launch_kernel(s.single[plan.fp8], dim3(plan.blocks), dim3(256), s.lds, stream, plan.args);
   }
   if (err != hipSuccess) return err;
   return hipGetLastError();
 }
 
-} // namespace
-
-namespace mfa {
-
-mfa_status decode_host_plan(const mfa_decode_params *params, DecodeHostPlan *out) {
+// the bytes of the workspace the launch would split into: 0 for an unsplit plan, whatever workspace the caller may already have bound
+mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint64_t *bytes) {
+  if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  *bytes = 0;
+  if (!params) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  mfa_decode_params probe = *params;
+  probe.workspace = nullptr;
+  probe.workspaceBytes = 0;
   DecodePlan plan;
-  const mfa_status st = prepare(params, &plan);
+  const mfa_status st = prepare(&probe, quant, &plan);
   if (st != MFA_OK) return st;
-  out->args = plan.args;
-  out->pieces = plan.pieces; out->planned = plan.planned; out->blocks = plan.blocks;
-  out->lds = plan.set->lds;
-  out->combine = plan.set->combine;
-  out->combineName = plan.set->combineName;
+  if (plan.planned > 1) *bytes = pieces_workspace_bytes(plan.planned, params);
   return MFA_OK;
 }
 
-uint64_t decode_workspace_bytes(uint32_t pieces, const mfa_decode_params *params) { return pieces_workspace_bytes(pieces, params); }
+mfa_status decode_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params, const mfa_kv_quant *quant,
+                         void *stream) {
+  DecodePlan plan;
+  mfa_status st = prepare(params, quant, &plan);
+  if (st != MFA_OK) return st;
+  st = bind(&plan, q, k, v, o, l);
+  if (st != MFA_OK) return st;
+  const hipError_t err = run(plan, (hipStream_t)stream);
+  if (err != hipSuccess) return hip_fail(err, plan.name());
+  return MFA_OK;
+}
 
-} // namespace mfa
+mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, char *out, size_t capacity) {
+  if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  out[0] = '\0';
+  DecodePlan plan;
+  const mfa_status st = prepare(params, quant, &plan);
+  if (st != MFA_OK) return st;
+  char text[512];
+  const uint32_t M = plan.args.G * plan.args.R;
+  if (plan.pieces > 1)
+    std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x K/V heads x %u pieces, %u packed rows, %s) + %s (grid %llu)", plan.name(),
+                  plan.blocks * plan.pieces, plan.blocks, plan.pieces, M, plan.args.paged ? "paged" : "contiguous", plan.set->combineName,
+                  (unsigned long long)(((uint64_t)plan.args.batches * plan.args.Hq * plan.args.R + 3) / 4));
+  else
+    std::snprintf(text, sizeof(text), "%s (grid %u sequences x K/V heads, %u packed rows, %s%s)", plan.name(), plan.blocks, M,
+                  plan.args.paged ? "paged" : "contiguous",
+                  plan.planned > 1 ? (", unsplit without a workspace: the plan has " + std::to_string(plan.planned) + " pieces").c_str() : "");
+  copy_text(out, capacity, text);
+  return MFA_OK;
+}
+
+mfa_status decode_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params, const mfa_kv_quant *quant,
+                       void *stream, int warmup, int iterations, float *milliseconds) {
+  if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
+  DecodePlan plan;
+  mfa_status st = prepare(params, quant, &plan);
+  if (st != MFA_OK) return st;
+  st = bind(&plan, q, k, v, o, l);
+  if (st != MFA_OK) return st;
+  return time_launches((hipStream_t)stream, warmup, iterations, milliseconds, plan.name(), [&](hipStream_t s) { return run(plan, s); });
+}
+
+} // namespace
 
 extern "C" {
 
@@ -220,79 +276,55 @@ mfa_status mfa_attention_decode_piece_range(uint32_t length, uint32_t pieces, ui
   return MFA_OK;
 }
 
-mfa_status mfa_attention_decode_workspace_size(const mfa_decode_params *params, uint64_t *bytes) {
-  if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  *bytes = 0;
-  if (!params) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  mfa_decode_params probe = *params;   // the size does not depend on the workspace the caller may already have bound
-  probe.workspace = nullptr;
-  probe.workspaceBytes = 0;
-  DecodePlan plan;
-  const mfa_status st = prepare(&probe, &plan);
-  if (st != MFA_OK) return st;
-  if (plan.planned > 1) *bytes = pieces_workspace_bytes(plan.planned, params);
-  return MFA_OK;
-}
+mfa_status mfa_attention_decode_workspace_size(const mfa_decode_params *params, uint64_t *bytes) { return decode_workspace_size(params, nullptr, bytes); }
 
 mfa_status mfa_attention_decode_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                        void *stream) {
-  DecodePlan plan;
-  mfa_status st = prepare(params, &plan);
-  if (st != MFA_OK) return st;
-  st = bind(&plan, q, k, v, o, l);
-  if (st != MFA_OK) return st;
-  const hipError_t err = run(plan, (hipStream_t)stream);
-  if (err != hipSuccess) return hip_fail(err, plan.pieces > 1 ? plan.set->piecesName : plan.set->singleName);
-  return MFA_OK;
+  return decode_launch(q, k, v, o, l, params, nullptr, stream);
 }
 
 mfa_status mfa_attention_decode_launch_form(const mfa_decode_params *params, char *out, size_t capacity) {
-  if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  out[0] = '\0';
-  DecodePlan plan;
-  const mfa_status st = prepare(params, &plan);
-  if (st != MFA_OK) return st;
-  const DecodeSet &s = *plan.set;
-  char text[512];
-  const uint32_t M = plan.args.G * plan.args.R;
-  if (plan.pieces > 1)
-    std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x K/V heads x %u pieces, %u packed rows, %s) + %s (grid %llu)", s.piecesName,
-                  plan.blocks * plan.pieces, plan.blocks, plan.pieces, M, plan.args.paged ? "paged" : "contiguous", s.combineName,
-                  (unsigned long long)(((uint64_t)plan.args.batches * plan.args.Hq * plan.args.R + 3) / 4));
-  else
-    std::snprintf(text, sizeof(text), "%s (grid %u sequences x K/V heads, %u packed rows, %s%s)", s.singleName, plan.blocks, M,
-                  plan.args.paged ? "paged" : "contiguous",
-                  plan.planned > 1 ? (", unsplit without a workspace: the plan has " + std::to_string(plan.planned) + " pieces").c_str() : "");
-  std::strncpy(out, text, capacity - 1);
-  out[capacity - 1] = '\0';
-  return MFA_OK;
+  return decode_launch_form(params, nullptr, out, capacity);
 }
 
 mfa_status mfa_attention_decode_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                      void *stream, int warmup, int iterations, float *milliseconds) {
+  return decode_time(q, k, v, o, l, params, nullptr, stream, warmup, iterations, milliseconds);
+}
+
+// ---- over an e4m3 cache (include/mfa_kvcache.h): the same four with the cache's mfa_kv_quant, which is required
+
+void mfa_kv_quant_init(mfa_kv_quant *quant) {
+  if (!quant) return;
+  std::memset(quant, 0, sizeof(*quant));
+  quant->cachePrecision = MFA_KV_E4M3;
+}
+
+mfa_status mfa_attention_decode_fp8_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint64_t *bytes) {
+  if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  *bytes = 0;
+  if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return decode_workspace_size(params, quant, bytes);
+}
+
+mfa_status mfa_attention_decode_fp8_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
+                                           const mfa_kv_quant *quant, void *stream) {
+  if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return decode_launch(q, k, v, o, l, params, quant, stream);
+}
+
+mfa_status mfa_attention_decode_fp8_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, char *out, size_t capacity) {
+  if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  out[0] = '\0';
+  if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return decode_launch_form(params, quant, out, capacity);
+}
+
+mfa_status mfa_attention_decode_fp8_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
+                                         const mfa_kv_quant *quant, void *stream, int warmup, int iterations, float *milliseconds) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
-  DecodePlan plan;
-  mfa_status st = prepare(params, &plan);
-  if (st != MFA_OK) return st;
-  st = bind(&plan, q, k, v, o, l);
-  if (st != MFA_OK) return st;
-  hipStream_t s = (hipStream_t)stream;
-  hipEvent_t start, stop;
-  hipError_t err = hipEventCreate(&start);
-  if (err != hipSuccess) return hip_fail(err, "hipEventCreate");
-  err = hipEventCreate(&stop);
-  if (err != hipSuccess) { (void)hipEventDestroy(start); return hip_fail(err, "hipEventCreate"); }
-  for (int i = 0; i < warmup && err == hipSuccess; ++i) err = run(plan, s);
-  if (err == hipSuccess) err = hipEventRecord(start, s);
-  for (int i = 0; i < iterations && err == hipSuccess; ++i) err = run(plan, s);
-  if (err == hipSuccess) err = hipEventRecord(stop, s);
-  if (err == hipSuccess) err = hipEventSynchronize(stop);
-  if (err == hipSuccess) err = hipGetLastError();
-  if (err == hipSuccess) err = hipEventElapsedTime(milliseconds, start, stop);
-  (void)hipEventDestroy(start);
-  (void)hipEventDestroy(stop);
-  if (err != hipSuccess) return hip_fail(err, plan.set->singleName);
-  return MFA_OK;
+  if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return decode_time(q, k, v, o, l, params, quant, stream, warmup, iterations, milliseconds);
 }
 
 } // extern "C"

@@ -13,7 +13,7 @@
 //     gathered as V^T by ds_read_b64_tr_b16 exactly as attn_decode16.h does.  Staged through registers (global load -> VGPR ->
 //     ds_write): the loads of tile t + 1 are issued before tile t is computed and written to the other buffer after it, one barrier
 //     per tile.
-//   * FP8 is one template parameter: the e4m3 bytes are converted in the staging registers (cvt8_e4m3, attn_decode8.h: exact) between
+//   * FP8 is one template parameter: the e4m3 bytes are converted in the staging registers (cvt8_e4m3, kv_e4m3.h: exact) between
 //     the load and the LDS write.  From the LDS images on the two kernels are the same code, with no permuted contraction: on exactly
 //     convertible values the e4m3 and the 16-bit launch are byte-identical.
 //   * keys are addressed in groups of 16 (a tile starts on a multiple of 64 and a page holds at least 16 keys, so a group never
@@ -24,7 +24,8 @@
 //   * what may hold poison is never loaded: key rows at or past n come in as zeros (K and V), a masked score is REPLACED (p = 0 exactly),
 //     and the running maximum only ever sees visible keys -- a row without a visible key keeps m = -FLT_MAX, l = 0.
 #pragma once
-#include "attn_decode8.h"
+#include "attn_decode16.h"
+#include "kv_e4m3.h"
 #include <type_traits>
 
 #define MFA_PREFILL_INLINE __attribute__((always_inline))   // (tile-load lambdas forced inline: see the top of attn_fwd16_v3.h)

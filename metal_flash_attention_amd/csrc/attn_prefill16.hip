@@ -10,6 +10,7 @@
 
 #include "../../include/mfa_prefill.h"
 #include "attn_prefill16.h"
+#include "cache_launch.h"
 #include "launchers.h"
 #include "mfa_internal.h"
 
@@ -44,10 +45,6 @@ struct PrefillSet {
 const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(f16, MFA_FP16, 64),
                             MFA_PREFILL_SET(f16, MFA_FP16, 128)};
 
-mfa_status hip_fail(hipError_t err, const char *what) {
-  return fail(MFA_ERR_HIP, std::string(what) + ": " + hipGetErrorName(err) + " (" + hipGetErrorString(err) + ")");
-}
-
 struct PrefillPlan {
   PrefillArgs args;
   const PrefillSet *set;
@@ -57,8 +54,6 @@ struct PrefillPlan {
   const char *name() const { return fp8 ? set->e4m3Name : set->plainName; }
 };
 
-bool multiple_of(int64_t x, int64_t n) { return x % n == 0; }
-
 // every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind)
 mfa_status prepare(const mfa_prefill_params *p, PrefillPlan *plan) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
@@ -67,11 +62,11 @@ mfa_status prepare(const mfa_prefill_params *p, PrefillPlan *plan) {
   if (p->precision != MFA_BF16 && p->precision != MFA_FP16) return fail(MFA_ERR_INVALID_ARGUMENT, "precision must be MFA_FP16 or MFA_BF16");
   if (p->outputPrecision != p->precision && p->outputPrecision != MFA_FP32)
     return fail(MFA_ERR_INVALID_ARGUMENT, "outputPrecision must be the inputs' 16-bit type or MFA_FP32");
-  if (p->cachePrecision == MFA_KV_E5M2)
-    return fail(MFA_ERR_UNSUPPORTED, "an FP8 KV cache is e4m3 (MFA_KV_E4M3, OCP e4m3fn); e5m2 caches have no kernel");
-  if (p->cachePrecision != MFA_KV_E4M3 && p->cachePrecision != p->precision)
+  bool fp8;
+  mfa_status st = check_cache_precision(p->cachePrecision, &fp8);
+  if (st != MFA_OK) return st;
+  if (!fp8 && p->cachePrecision != p->precision)
     return fail(MFA_ERR_INVALID_ARGUMENT, "cachePrecision must be `precision` (a 16-bit cache of Q's type) or MFA_KV_E4M3");
-  const bool fp8 = p->cachePrecision == MFA_KV_E4M3;
   if (!fp8 && (p->keyScale || p->valueScale))
     return fail(MFA_ERR_INVALID_ARGUMENT, "keyScale / valueScale go with an e4m3 cache (cachePrecision MFA_KV_E4M3); a 16-bit cache holds the values themselves");
   const PrefillSet *set = nullptr;
@@ -89,28 +84,16 @@ mfa_status prepare(const mfa_prefill_params *p, PrefillPlan *plan) {
     return fail(MFA_ERR_INVALID_ARGUMENT, "heads (" + std::to_string(p->heads) + ") must be a multiple of headsPerKeyValue (" + std::to_string(G) + ")");
   if (!p->cacheLengths) return fail(MFA_ERR_INVALID_ARGUMENT, "cacheLengths is required (device array of `batches` uint32)");
   uint32_t pageShift = 0;
-  if (p->pageSize) {
-    if (p->pageSize < 16 || p->pageSize > 1024 || (p->pageSize & (p->pageSize - 1)))
-      return fail(MFA_ERR_INVALID_ARGUMENT, "pageSize must be a power of two from 16 to 1024 (or 0: contiguous), not " + std::to_string(p->pageSize));
-    if (!p->blockTable) return fail(MFA_ERR_INVALID_ARGUMENT, "a paged launch (pageSize != 0) needs blockTable");
-    const int64_t pagesPerSequence = ((int64_t)p->column + p->pageSize - 1) / p->pageSize;
-    if (p->blockTableStride < pagesPerSequence)
-      return fail(MFA_ERR_INVALID_ARGUMENT, "blockTableStride must hold the " + std::to_string(pagesPerSequence) + " pages of `column` keys");
-    while ((1u << pageShift) < p->pageSize) ++pageShift;
-  }
+  st = check_paging(p->pageSize, p->blockTable, p->blockTableStride, p->column, &pageShift);
+  if (st != MFA_OK) return st;
   static const char *names[4] = {"Q", "K", "V", "O"};
   for (int i = 0; i < 4; ++i) {
     const bool kv = i == 1 || i == 2;
     const int64_t need = (i == 3) ? 4 : (kv && fp8) ? 16 : 8;   // 16-byte rows of Q, K, V; 8- or 16-byte stores of O
-    if (p->leadingDimension[i] < (int64_t)p->headDimension)
-      return fail(MFA_ERR_INVALID_ARGUMENT, std::string("leadingDimension of ") + names[i] + " is smaller than the head dimension");
-    bool ok = multiple_of(p->leadingDimension[i], need) && multiple_of(p->headStride[i], need);
-    if (!(kv && p->pageSize)) ok = ok && multiple_of(p->batchStride[i], need);
-    if (kv && p->pageSize) ok = ok && multiple_of(p->pageStride[i - 1], need);
-    if (!ok)
-      return fail(MFA_ERR_INVALID_ARGUMENT, std::string("strides of ") + names[i] + " must be multiples of " + std::to_string(need) +
-                                                (kv && fp8 ? " elements (16-byte rows of an e4m3 cache)"
-                                                           : " elements (16-byte rows for Q, K, V; whole 4-element stores for O)"));
+    st = check_operand_strides(names[i], p->headDimension, p->leadingDimension[i], p->headStride[i],
+                               kv && p->pageSize ? p->pageStride[i - 1] : p->batchStride[i], need,
+                               kv && fp8 ? "(16-byte rows of an e4m3 cache)" : "(16-byte rows for Q, K, V; whole 4-element stores for O)");
+    if (st != MFA_OK) return st;
   }
   const uint32_t RB = MFA_PREFILL_PACKED_ROWS / G;
   const uint64_t rowBlocks = ((uint64_t)p->rows + RB - 1) / RB;
@@ -142,12 +125,10 @@ mfa_status prepare(const mfa_prefill_params *p, PrefillPlan *plan) {
 }
 
 mfa_status bind(PrefillPlan *plan, const void *q, const void *k, const void *v, void *o, float *l) {
-  if (!q || !k || !v || !o) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  if ((uintptr_t)q % 16 || (uintptr_t)k % 16 || (uintptr_t)v % 16 || (uintptr_t)o % 16)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "Q, K, V and O must be 16-byte aligned");
-  if ((uintptr_t)l % 4) return fail(MFA_ERR_INVALID_ARGUMENT, "L must be 4-byte aligned");
-  if ((uintptr_t)plan->args.keyScale % 4 || (uintptr_t)plan->args.valueScale % 4)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "keyScale and valueScale must be 4-byte aligned");
+  mfa_status st = check_buffers({q, k, v, o}, "Q, K, V and O");
+  if (st == MFA_OK) st = check_float_arrays({l}, "L");
+  if (st == MFA_OK) st = check_float_arrays({plan->args.keyScale, plan->args.valueScale}, "keyScale and valueScale");
+  if (st != MFA_OK) return st;
   plan->args.q = (const char *)q; plan->args.k = (const char *)k; plan->args.v = (const char *)v;
   plan->args.o = (char *)o; plan->args.l = l;
   return MFA_OK;
@@ -219,8 +200,7 @@ mfa_status mfa_attention_prefill_launch_form(const mfa_prefill_params *params, c
   char text[512];
   std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s)", plan.name(),
                 plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous");
-  std::strncpy(out, text, capacity - 1);
-  out[capacity - 1] = '\0';
+  copy_text(out, capacity, text);
   return MFA_OK;
 }
 
@@ -232,23 +212,7 @@ mfa_status mfa_attention_prefill_time(const void *q, const void *k, const void *
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
-  hipStream_t s = (hipStream_t)stream;
-  hipEvent_t start, stop;
-  hipError_t err = hipEventCreate(&start);
-  if (err != hipSuccess) return hip_fail(err, "hipEventCreate");
-  err = hipEventCreate(&stop);
-  if (err != hipSuccess) { (void)hipEventDestroy(start); return hip_fail(err, "hipEventCreate"); }
-  for (int i = 0; i < warmup && err == hipSuccess; ++i) err = run(plan, s);
-  if (err == hipSuccess) err = hipEventRecord(start, s);
-  for (int i = 0; i < iterations && err == hipSuccess; ++i) err = run(plan, s);
-  if (err == hipSuccess) err = hipEventRecord(stop, s);
-  if (err == hipSuccess) err = hipEventSynchronize(stop);
-  if (err == hipSuccess) err = hipGetLastError();
-  if (err == hipSuccess) err = hipEventElapsedTime(milliseconds, start, stop);
-  (void)hipEventDestroy(start);
-  (void)hipEventDestroy(stop);
-  if (err != hipSuccess) return hip_fail(err, plan.name());
-  return MFA_OK;
+  return time_launches((hipStream_t)stream, warmup, iterations, milliseconds, plan.name(), [&](hipStream_t s) { return run(plan, s); });
 }
 
 } // extern "C"

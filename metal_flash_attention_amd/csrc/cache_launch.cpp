@@ -1,0 +1,71 @@
+// cache_launch.cpp -- the host checks the launches over a KV cache share (cache_launch.h).
+#include "cache_launch.h"
+
+#include <cstring>
+#include <string>
+
+#include "../../include/mfa_kvcache.h"
+
+namespace mfa {
+
+mfa_status hip_fail(hipError_t err, const char *what) {
+  return fail(MFA_ERR_HIP, std::string(what) + ": " + hipGetErrorName(err) + " (" + hipGetErrorString(err) + ")");
+}
+
+void copy_text(char *out, size_t capacity, const char *text) {
+  std::strncpy(out, text, capacity - 1);
+  out[capacity - 1] = '\0';
+}
+
+mfa_status check_paging(uint32_t pageSize, const void *blockTable, int64_t blockTableStride, uint32_t column, uint32_t *pageShift) {
+  *pageShift = 0;
+  if (!pageSize) return MFA_OK;
+  if (pageSize < 16 || pageSize > 1024 || (pageSize & (pageSize - 1)))
+    return fail(MFA_ERR_INVALID_ARGUMENT, "pageSize must be a power of two from 16 to 1024 (or 0: contiguous), not " + std::to_string(pageSize));
+  if (!blockTable) return fail(MFA_ERR_INVALID_ARGUMENT, "a paged launch (pageSize != 0) needs blockTable");
+  if (column) {
+    const int64_t pagesPerSequence = ((int64_t)column + pageSize - 1) / pageSize;
+    if (blockTableStride < pagesPerSequence)
+      return fail(MFA_ERR_INVALID_ARGUMENT, "blockTableStride must hold the " + std::to_string(pagesPerSequence) + " pages of `column` keys");
+  } else if (blockTableStride <= 0) {
+    return fail(MFA_ERR_INVALID_ARGUMENT, "blockTableStride must be positive: the pages a sequence may name");
+  }
+  while ((1u << *pageShift) < pageSize) ++*pageShift;
+  return MFA_OK;
+}
+
+mfa_status check_stride_multiples(const char *name, int64_t leadingDimension, int64_t headStride, int64_t outer, int64_t need, const char *why) {
+  if (leadingDimension % need || headStride % need || outer % need)
+    return fail(MFA_ERR_INVALID_ARGUMENT, std::string("strides of ") + name + " must be multiples of " + std::to_string(need) + " elements " + why);
+  return MFA_OK;
+}
+
+mfa_status check_operand_strides(const char *name, uint32_t headDimension, int64_t leadingDimension, int64_t headStride, int64_t outer,
+                                 int64_t need, const char *why) {
+  if (leadingDimension < (int64_t)headDimension)
+    return fail(MFA_ERR_INVALID_ARGUMENT, std::string("leadingDimension of ") + name + " is smaller than the head dimension");
+  return check_stride_multiples(name, leadingDimension, headStride, outer, need, why);
+}
+
+mfa_status check_cache_precision(uint32_t cachePrecision, bool *fp8) {
+  if (cachePrecision == MFA_KV_E5M2)
+    return fail(MFA_ERR_UNSUPPORTED, "an FP8 KV cache is e4m3 (MFA_KV_E4M3, OCP e4m3fn); e5m2 caches have no kernel");
+  *fp8 = cachePrecision == MFA_KV_E4M3;
+  return MFA_OK;
+}
+
+mfa_status check_buffers(std::initializer_list<const void *> buffers, const char *names) {
+  for (const void *b : buffers)
+    if (!b) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  for (const void *b : buffers)
+    if ((uintptr_t)b % 16) return fail(MFA_ERR_INVALID_ARGUMENT, std::string(names) + " must be 16-byte aligned");
+  return MFA_OK;
+}
+
+mfa_status check_float_arrays(std::initializer_list<const void *> arrays, const char *names) {
+  for (const void *a : arrays)
+    if ((uintptr_t)a % 4) return fail(MFA_ERR_INVALID_ARGUMENT, std::string(names) + " must be 4-byte aligned");
+  return MFA_OK;
+}
+
+} // namespace mfa

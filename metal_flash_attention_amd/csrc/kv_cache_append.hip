@@ -9,6 +9,7 @@
 
 #include "../../include/mfa_kvcache.h"
 #include "attn_common.h"
+#include "cache_launch.h"
 #include "kv_e4m3.h"
 #include "launchers.h"
 #include "mfa_internal.h"
@@ -92,16 +93,15 @@ extern "C" __global__ __launch_bounds__(256) void kv_cache_append_d128_copy16(co
 namespace {
 
 typedef void (*AppendKernel)(const AppendArgs);
-bool multiple_of(int64_t x, int64_t n) { return x % n == 0; }
 
 mfa_status prepare(const mfa_kv_append_params *p, AppendArgs *a, AppendKernel *kernel, const char **name) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   if (p->precision != MFA_BF16 && p->precision != MFA_FP16)
     return fail(p->precision == MFA_FP32 ? MFA_ERR_UNSUPPORTED : MFA_ERR_INVALID_ARGUMENT,
                 "the new key / value rows must be 16-bit (precision MFA_FP16 or MFA_BF16)");
-  if (p->cachePrecision == MFA_KV_E5M2)
-    return fail(MFA_ERR_UNSUPPORTED, "an FP8 KV cache is e4m3 (MFA_KV_E4M3, OCP e4m3fn); e5m2 caches have no kernel");
-  const bool fp8 = p->cachePrecision == MFA_KV_E4M3;
+  bool fp8;
+  mfa_status st = check_cache_precision(p->cachePrecision, &fp8);
+  if (st != MFA_OK) return st;
   if (!fp8 && p->cachePrecision != p->precision)
     return fail(MFA_ERR_INVALID_ARGUMENT, "cachePrecision must be the rows' 16-bit type (`precision`) or MFA_KV_E4M3");
   if (p->headDimension != 64 && p->headDimension != 128)
@@ -112,27 +112,16 @@ mfa_status prepare(const mfa_kv_append_params *p, AppendArgs *a, AppendKernel *k
   if (!fp8 && (p->keyScale || p->valueScale))
     return fail(MFA_ERR_INVALID_ARGUMENT, "keyScale / valueScale go with an e4m3 cache (MFA_KV_E4M3); a 16-bit cache takes the rows' bits unscaled");
   uint32_t pageShift = 0;
-  if (p->pageSize) {
-    if (p->pageSize < 16 || p->pageSize > 1024 || (p->pageSize & (p->pageSize - 1)))
-      return fail(MFA_ERR_INVALID_ARGUMENT, "pageSize must be a power of two from 16 to 1024 (or 0: contiguous), not " + std::to_string(p->pageSize));
-    if (!p->blockTable) return fail(MFA_ERR_INVALID_ARGUMENT, "a paged launch (pageSize != 0) needs blockTable");
-    if (p->blockTableStride <= 0) return fail(MFA_ERR_INVALID_ARGUMENT, "blockTableStride must be positive: the pages a sequence may name");
-    while ((1u << pageShift) < p->pageSize) ++pageShift;
-  } else if (p->column == 0) {
-    return fail(MFA_ERR_INVALID_ARGUMENT, "column (the capacity of a contiguous cache) must be non-zero");
-  }
+  st = check_paging(p->pageSize, p->blockTable, p->blockTableStride, 0, &pageShift);   // (0: the kernel drops a row past the stride)
+  if (st != MFA_OK) return st;
+  if (!p->pageSize && p->column == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "column (the capacity of a contiguous cache) must be non-zero");
   static const char *names[4] = {"kNew", "vNew", "kCache", "vCache"};
   for (int i = 0; i < 4; ++i) {
     const bool cache = i >= 2;
-    const int64_t need = (cache && fp8) ? 16 : 8;
-    if (p->leadingDimension[i] < (int64_t)p->headDimension)
-      return fail(MFA_ERR_INVALID_ARGUMENT, std::string("leadingDimension of ") + names[i] + " is smaller than the head dimension");
-    bool ok = multiple_of(p->leadingDimension[i], need) && multiple_of(p->headStride[i], need);
-    if (cache && p->pageSize) ok = ok && multiple_of(p->pageStride[i - 2], need);
-    else ok = ok && multiple_of(p->batchStride[i], need);
-    if (!ok)
-      return fail(MFA_ERR_INVALID_ARGUMENT, std::string("strides of ") + names[i] + " must be multiples of " + std::to_string(need) +
-                                                " elements (16-byte rows of 16-bit operands; an e4m3 cache: multiples of 16 elements)");
+    st = check_operand_strides(names[i], p->headDimension, p->leadingDimension[i], p->headStride[i],
+                               cache && p->pageSize ? p->pageStride[i - 2] : p->batchStride[i], (cache && fp8) ? 16 : 8,
+                               "(16-byte rows of 16-bit operands; an e4m3 cache: multiples of 16 elements)");
+    if (st != MFA_OK) return st;
   }
   std::memset(a, 0, sizeof(*a));
   a->scale[0] = p->keyScale; a->scale[1] = p->valueScale;
@@ -178,16 +167,14 @@ mfa_status mfa_kv_cache_append_launch(const void *kNew, const void *vNew, void *
   AppendArgs a;
   AppendKernel kernel = nullptr;
   const char *name = "";
-  const mfa_status st = prepare(params, &a, &kernel, &name);
+  mfa_status st = prepare(params, &a, &kernel, &name);
+  if (st == MFA_OK) st = check_buffers({kNew, vNew, kCache, vCache}, "kNew, vNew, kCache and vCache");
   if (st != MFA_OK) return st;
-  if (!kNew || !vNew || !kCache || !vCache) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  if ((uintptr_t)kNew % 16 || (uintptr_t)vNew % 16 || (uintptr_t)kCache % 16 || (uintptr_t)vCache % 16)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "kNew, vNew, kCache and vCache must be 16-byte aligned");
   a.src[0] = (const char *)kNew; a.src[1] = (const char *)vNew;
   a.dst[0] = (char *)kCache; a.dst[1] = (char *)vCache;
   hipError_t err = launch_kernel(kernel, dim3(params->batches * params->rows), dim3(256), 0, (hipStream_t)stream, a);
   if (err == hipSuccess) err = hipGetLastError();
-  if (err != hipSuccess) return fail(MFA_ERR_HIP, std::string(name) + ": " + hipGetErrorName(err) + " (" + hipGetErrorString(err) + ")");
+  if (err != hipSuccess) return hip_fail(err, name);
   return MFA_OK;
 }
 

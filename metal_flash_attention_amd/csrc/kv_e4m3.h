@@ -1,8 +1,11 @@
 // kv_e4m3.h -- the e4m3 (OCP e4m3fn) codec of the FP8 KV cache: ONE body for the exported host functions (mfa_kv_quantize_e4m3 /
 // mfa_kv_dequantize_e4m3, include/mfa_kvcache.h) and for the append kernel, so that the writer, the reader and the tests agree on
 // rounding, saturation and the scale convention by construction.  Integer arithmetic but for the IEEE division and one FP32 add.
+//
+// cvt8_e4m3 is what the attention kernels read the cache with (attn_decode16.h, attn_prefill16.h): the hardware's conversion to the
+// launch's 16-bit type, exact (e4m3 has 3 mantissa bits and a range of 2^-9 .. 448), so it agrees with kv_dequantize_e4m3 bit for bit.
 #pragma once
-#include <cstdint>
+#include "attn_common.h"
 
 namespace mfa {
 
@@ -27,6 +30,21 @@ __host__ __device__ __forceinline__ float kv_dequantize_e4m3(uint8_t byte) {
   if ((byte & 0x7Fu) == 0x7Fu) return __builtin_bit_cast(float, sign | 0x7FC00000u);
   if (e == 0) return __builtin_bit_cast(float, sign | __builtin_bit_cast(uint32_t, (float)m * 0.001953125f));
   return __builtin_bit_cast(float, sign | ((e + 120u) << 23) | (m << 20));
+}
+
+// eight e4m3 bytes (two dwords) -> eight values of the 16-bit type T, in order (v_cvt_scalef32_pk_{bf16,f16}_fp8 with scale 1.0)
+template <typename T> __device__ __forceinline__ u32x4 cvt8_e4m3(uint32_t lo, uint32_t hi) {
+  if constexpr (__is_same(T, __bf16)) {
+    return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true))};
+  } else {
+    return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, true)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true))};
+  }
 }
 
 } // namespace mfa

@@ -17,6 +17,7 @@
 #include <utility>
 #include <vector>
 
+#include "cache_launch.h"
 #include "launchers.h"
 #include "mfa_internal.h"
 
@@ -60,10 +61,6 @@ hipError_t mfa::compute_units(int *cus) {
   if (err == hipSuccess && *cus <= 0) err = hipErrorInvalidValue;
   if (err == hipSuccess && cache) cached[device] = *cus;
   return err;
-}
-
-static mfa_status hip_fail(hipError_t err, const char *what) {
-  return fail(MFA_ERR_HIP, std::string(what) + ": " + hipGetErrorName(err) + " (" + hipGetErrorString(err) + ")");
 }
 
 static int slot_operand(int slot) {
@@ -939,7 +936,7 @@ mfa_status mfa_attention_kernel_launch_form(const mfa_attention_kernel *kernel, 
   if (st != MFA_OK) return st;
   std::string text;
   (void)run_plan(kernel, plan, nullptr, false, &text);   // (nothing is started: no HIP call)
-  std::snprintf(out, capacity, "%s", text.c_str());
+  copy_text(out, capacity, text.c_str());
   return MFA_OK;
 }
 
@@ -975,24 +972,9 @@ mfa_status mfa_attention_kernel_time(const mfa_attention_kernel *kernel, void *c
   LaunchPlan plan;
   mfa_status st = prepare_launch(kernel, buffers, params, &plan);
   if (st != MFA_OK) return st;
-  hipStream_t s = (hipStream_t)stream;
-  hipEvent_t start, stop;
-  hipError_t err = hipEventCreate(&start);
-  if (err != hipSuccess) return hip_fail(err, "hipEventCreate");
-  err = hipEventCreate(&stop);
-  if (err != hipSuccess) { (void)hipEventDestroy(start); return hip_fail(err, "hipEventCreate"); }
   // (a code object's first launch on a device raises its LDS limit, a host-side call: with warmup = 0 the first timed launch pays it)
-  for (int i = 0; i < warmup && err == hipSuccess; ++i) err = run_plan(kernel, plan, s, true);
-  if (err == hipSuccess) err = hipEventRecord(start, s);
-  for (int i = 0; i < iterations && err == hipSuccess; ++i) err = run_plan(kernel, plan, s, true);
-  if (err == hipSuccess) err = hipEventRecord(stop, s);
-  if (err == hipSuccess) err = hipEventSynchronize(stop);
-  if (err == hipSuccess) err = hipGetLastError();
-  if (err == hipSuccess) err = hipEventElapsedTime(milliseconds, start, stop);
-  (void)hipEventDestroy(start);
-  (void)hipEventDestroy(stop);
-  if (err != hipSuccess) return hip_fail(err, plan_name(plan));
-  return MFA_OK;
+  return time_launches((hipStream_t)stream, warmup, iterations, milliseconds, plan_name(plan),
+                       [&](hipStream_t s) { return run_plan(kernel, plan, s, true); });
 }
 
 mfa_status mfa_device_count(int *count) {
@@ -1007,8 +989,7 @@ mfa_status mfa_device_name(int device, char *out, size_t capacity) {
   hipDeviceProp_t prop;
   hipError_t err = hipGetDeviceProperties(&prop, device);
   if (err != hipSuccess) return hip_fail(err, "hipGetDeviceProperties");
-  std::strncpy(out, prop.gcnArchName, capacity - 1);
-  out[capacity - 1] = '\0';
+  copy_text(out, capacity, prop.gcnArchName);
   return MFA_OK;
 }
 
