@@ -253,6 +253,23 @@ PREFILL_SYMBOLS = [
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U32P, _U32P]),
 ]
 
+_DECODE = ctypes.POINTER(mfa_decode_params)
+_TIMING = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+
+WINDOW_SYMBOLS = [   # include/mfa_window.h: `window` (uint32, 0 = none) after `quant` (decode; NULL: a 16-bit cache) / `params` (prefill)
+    ("mfa_attention_decode_window_workspace_size", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),
+    ("mfa_attention_decode_window_launch", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, ctypes.c_void_p]),
+    ("mfa_attention_decode_window_launch_form", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_decode_window_time", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, ctypes.c_void_p] + _TIMING),
+    ("mfa_attention_decode_window_piece_range", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U32P, _U32P]),
+    ("mfa_attention_prefill_window_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, ctypes.c_void_p]),
+    ("mfa_attention_prefill_window_launch_form", ctypes.c_int, [_PREFILL, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_prefill_window_time", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, ctypes.c_void_p] + _TIMING),
+    ("mfa_attention_prefill_window_tile_range", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U32P, _U32P, _U32P, _U32P]),
+]
+
 SYMBOLS = [
     ("mfa_precision_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mfa_precision_size", ctypes.c_int, [ctypes.c_int]),
@@ -328,7 +345,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -412,7 +412,10 @@ class AttentionDecode:
 
     `strides`: operand name -> (leadingDimension, headStride, batchStride) in elements; an operand left out is packed
     ([batch][head][row or key][D]).  Paged caches: pageSize, blockTable (device int32 [batches][blockTableStride]) and
-    pageStrides=(K, V); a cache operand's batchStride is then unused."""
+    pageStrides=(K, V); a cache operand's batchStride is then unused.
+
+    window=W (workspaceSize, launchForm, dispatch, time): sliding-window attention, include/mfa_window.h -- row r sees its causal
+    frontier and the W - 1 keys before it.  None: the plain launch; 0 goes through the window entries and is the plain launch."""
 
     OPERANDS = ("Q", "K", "V", "O")
 
@@ -421,6 +424,17 @@ class AttentionDecode:
         self.headDimension = int(headDimension)
         self.precision = GEMMOperandPrecision(precision)
         self.outputPrecision = self.precision if outputPrecision is None else GEMMOperandPrecision(outputPrecision)
+
+    def _quant(self, shape):
+        """the mfa_kv_quant block of the window entries: none for a 16-bit cache"""
+        return None, None
+
+    def _window(self, entry, window, shape, *head, tail=()):
+        """one of the four mfa_attention_decode_window_* entries: `head` arguments, params, quant, window, `tail` arguments"""
+        quant, _scales = self._quant(shape)
+        p, _keep = self._params(**shape)
+        check(getattr(lib(), "mfa_attention_decode_window_" + entry)(*head, ctypes.byref(p), None if quant is None else ctypes.byref(quant),
+                                                                     int(window), *tail))
 
     def _params(self, *, rows: int, column: int, heads: int = 1, batches: int = 1, headsPerKeyValue: int = 1, causal: bool = True,
                 cacheLengths=None, pageSize: int = 0, blockTable=None, blockTableStride: int = 0, strides: Optional[Mapping] = None,
@@ -453,28 +467,45 @@ class AttentionDecode:
     def workspaceSize(self, **shape) -> int:
         """Bytes a launch of this shape wants to be cut along the keys (0: the plan has one piece).  Without a workspace the launch
         runs unsplit in one kernel."""
-        p, _keep = self._params(**shape)
+        window = shape.pop("window", None)
         out = ctypes.c_uint64(0)
+        if window is not None:
+            self._window("workspace_size", window, shape, tail=(ctypes.byref(out),))
+            return int(out.value)
+        p, _keep = self._params(**shape)
         check(lib().mfa_attention_decode_workspace_size(ctypes.byref(p), ctypes.byref(out)))
         return int(out.value)
 
     def launchForm(self, **shape) -> str:
         """What `dispatch` with the same arguments would run (nothing is launched): the pieces kernel, the piece count and the combine
         kernel, or the single kernel."""
-        p, _keep = self._params(**shape)
+        window = shape.pop("window", None)
         out = ctypes.create_string_buffer(512)
+        if window is not None:
+            self._window("launch_form", window, shape, tail=(out, len(out)))
+            return out.value.decode()
+        p, _keep = self._params(**shape)
         check(lib().mfa_attention_decode_launch_form(ctypes.byref(p), out, len(out)))
         return out.value.decode()
 
     def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        window = shape.pop("window", None)
+        if window is not None:
+            return self._window("launch", window, shape, _pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l),
+                                tail=(ctypes.c_void_p(stream or 0),))
         p, _keep = self._params(**shape)
         check(lib().mfa_attention_decode_launch(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
                                                 ctypes.c_void_p(stream or 0)))
 
     def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
         """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
-        p, _keep = self._params(**shape)
+        window = shape.pop("window", None)
         ms = ctypes.c_float(0.0)
+        if window is not None:
+            self._window("time", window, shape, _pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l),
+                         tail=(ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
+            return float(ms.value)
+        p, _keep = self._params(**shape)
         check(lib().mfa_attention_decode_time(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
                                               ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
         return float(ms.value)
@@ -484,6 +515,14 @@ class AttentionDecode:
         """keys [begin, end) of piece `piece` of `pieces` for a sequence of `length` keys: the kernels' own function, on the host"""
         b, e = ctypes.c_uint32(0), ctypes.c_uint32(0)
         check(lib().mfa_attention_decode_piece_range(int(length), int(pieces), int(piece), ctypes.byref(b), ctypes.byref(e)))
+        return int(b.value), int(e.value)
+
+    @staticmethod
+    def windowPieceRange(length: int, rows: int, window: int, pieces: int, piece: int) -> Tuple[int, int]:
+        """keys [begin, end) of piece `piece` of `pieces` of a windowed launch (include/mfa_window.h): the kernels' own function"""
+        b, e = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        check(lib().mfa_attention_decode_window_piece_range(int(length), int(rows), int(window), int(pieces), int(piece), ctypes.byref(b),
+                                                            ctypes.byref(e)))
         return int(b.value), int(e.value)
 
 
@@ -512,6 +551,9 @@ class AttentionDecodeFP8(AttentionDecode):
         return quant, keep
 
     def workspaceSize(self, **shape) -> int:
+        if shape.get("window") is not None:
+            return super().workspaceSize(**shape)
+        shape.pop("window", None)
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape)
         out = ctypes.c_uint64(0)
@@ -519,6 +561,9 @@ class AttentionDecodeFP8(AttentionDecode):
         return int(out.value)
 
     def launchForm(self, **shape) -> str:
+        if shape.get("window") is not None:
+            return super().launchForm(**shape)
+        shape.pop("window", None)
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape)
         out = ctypes.create_string_buffer(512)
@@ -526,12 +571,18 @@ class AttentionDecodeFP8(AttentionDecode):
         return out.value.decode()
 
     def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        if shape.get("window") is not None:
+            return super().dispatch(q, k, v, o, l, stream=stream, **shape)
+        shape.pop("window", None)
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape)
         check(lib().mfa_attention_decode_fp8_launch(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
                                                     ctypes.byref(quant), ctypes.c_void_p(stream or 0)))
 
     def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        if shape.get("window") is not None:
+            return super().time(q, k, v, o, l, stream=stream, warmup=warmup, iterations=iterations, **shape)
+        shape.pop("window", None)
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape)
         ms = ctypes.c_float(0.0)
@@ -553,7 +604,8 @@ class AttentionPrefill:
     `strides`, pageSize / blockTable / blockTableStride / pageStrides, lStrides: as AttentionDecode.  cachePrecision=
     KVCachePrecision.E4M3 reads an e4m3 cache (the quantisation block is part of mfa_prefill_params, so one class serves both): the
     K / V strides then count bytes, and keyScale / valueScale (device FP32 [heads // headsPerKeyValue], None = 1.0) go with the shape
-    arguments.  The launch takes no workspace."""
+    arguments.  The launch takes no workspace.  window=W (launchForm, dispatch, time): sliding-window attention,
+    include/mfa_window.h; None: the plain launch; 0 goes through the window entries and is the plain launch."""
 
     OPERANDS = ("Q", "K", "V", "O")
 
@@ -593,22 +645,35 @@ class AttentionPrefill:
 
     def launchForm(self, **shape) -> str:
         """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name and the grid."""
+        window = shape.pop("window", None)
         p, _keep = self._params(**shape)
         out = ctypes.create_string_buffer(512)
-        check(lib().mfa_attention_prefill_launch_form(ctypes.byref(p), out, len(out)))
+        if window is not None:
+            check(lib().mfa_attention_prefill_window_launch_form(ctypes.byref(p), int(window), out, len(out)))
+        else:
+            check(lib().mfa_attention_prefill_launch_form(ctypes.byref(p), out, len(out)))
         return out.value.decode()
 
     def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        window = shape.pop("window", None)
         p, _keep = self._params(**shape)
-        check(lib().mfa_attention_prefill_launch(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
-                                                 ctypes.c_void_p(stream or 0)))
+        bufs = (_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l))
+        if window is not None:
+            check(lib().mfa_attention_prefill_window_launch(*bufs, ctypes.byref(p), int(window), ctypes.c_void_p(stream or 0)))
+        else:
+            check(lib().mfa_attention_prefill_launch(*bufs, ctypes.byref(p), ctypes.c_void_p(stream or 0)))
 
     def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
         """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
+        window = shape.pop("window", None)
         p, _keep = self._params(**shape)
         ms = ctypes.c_float(0.0)
-        check(lib().mfa_attention_prefill_time(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
-                                               ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
+        bufs = (_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l))
+        timing = (ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms))
+        if window is not None:
+            check(lib().mfa_attention_prefill_window_time(*bufs, ctypes.byref(p), int(window), *timing))
+        else:
+            check(lib().mfa_attention_prefill_time(*bufs, ctypes.byref(p), *timing))
         return float(ms.value)
 
     @staticmethod
@@ -619,6 +684,15 @@ class AttentionPrefill:
         check(lib().mfa_attention_prefill_tile_range(int(length), int(queryLength), int(firstRow), int(blockRows), int(bool(causal)),
                                                      ctypes.byref(f), ctypes.byref(e)))
         return int(f.value), int(e.value)
+
+    @staticmethod
+    def windowTileRange(length: int, queryLength: int, firstRow: int, blockRows: int, window: int) -> Tuple[int, int, int, int]:
+        """(begin, unmaskedBegin, unmaskedEnd, end) of the block of rows [firstRow, firstRow + blockRows) under a window of `window`
+        keys, in 64-key tiles (include/mfa_window.h): the kernels' own function, on the host"""
+        out = [ctypes.c_uint32(0) for _ in range(4)]
+        check(lib().mfa_attention_prefill_window_tile_range(int(length), int(queryLength), int(firstRow), int(blockRows), int(window),
+                                                            *(ctypes.byref(x) for x in out)))
+        return tuple(int(x.value) for x in out)
 
 
 class KVCacheAppend:

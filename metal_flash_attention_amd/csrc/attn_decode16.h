@@ -31,6 +31,15 @@
 //   * the scales are per K / V head: keyScale folds into the softmax scale, valueScale into the final normalisation (pieces: into
 //     the un-normalised O they publish, so that the combine kernel needs no change).  The 16-bit kernels read neither.
 //   * poison: rows at or past the piece's end are not loaded (zero bytes = +0.0), so a 0x7f beyond a length never reaches a product.
+//
+// WINDOW: the same body under a sliding window of a.window >= 1 keys (include/mfa_window.h): row r sees the keys
+// lo(r) <= c < lim(r), lo = max(f + 1, W) - W behind its causal frontier f.  What the parameter switches:
+//   * the keys the workgroup walks come from decode_window_piece_range, in the unsplit kernel too (one piece of one): they start at
+//     the tile of row 0's first key, and nothing below it is loaded -- no key, no page, no block-table entry (group_offsets is only
+//     ever asked for keys at or past `begin`).
+//   * the mask is one unsigned comparison c - lo < lim - lo in both places; a masked score is still replaced, never multiplied.
+//   * pieces may be empty: they publish m = -FLT_MAX, l = 0 and zeros, which the combine kernel already weighs with 0.
+// With W >= column + rows every lo is 0 and the ranges are decode_piece_range's: the plain kernel's arithmetic in the plain order.
 #pragma once
 #include "attn_fwd16_common.h"
 #include "kv_e4m3.h"
@@ -61,6 +70,7 @@ struct DecodeArgs {
   float scale2;                   // log2(e) / sqrt(D)
   float *wsO, *wsML;
   const float *keyScale, *valueScale;   // e4m3 caches, per K / V head; null: 1.0
+  uint32_t window;                      // the WINDOW kernels only (>= 1); last, so that no other field moves
 };
 
 // keys [*begin, *end) of piece `piece` of `pieces` for a sequence of `length` keys: an equal share of the sequence's whole 64-key
@@ -76,13 +86,30 @@ __host__ __device__ __forceinline__ void decode_piece_range(uint32_t length, uin
   *end = (uint32_t)e;
 }
 
+// keys [*begin, *end) of piece `piece` of `pieces` under a window of `window` >= 1 keys: with lo0 the first key row 0 sees, an equal
+// share, in whole tiles, of the tiles [lo0 / 64, ceil(length / 64)) -- the tiles that hold a key some row sees.  Device and host
+// (mfa_attention_decode_window_piece_range) run this one body.
+__host__ __device__ __forceinline__ void decode_window_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t pieces,
+                                                                   uint32_t piece, uint32_t *begin, uint32_t *end) {
+  const uint64_t f1 = (length > rows ? (uint64_t)length - rows : 0) + 1;   // row 0's frontier + 1
+  const uint64_t lo0 = (f1 > window ? f1 : (uint64_t)window) - window;
+  const uint64_t first = lo0 / DEC_KEY_TILE, last = ((uint64_t)length + DEC_KEY_TILE - 1) / DEC_KEY_TILE;
+  const uint64_t tiles = last > first ? last - first : 0;
+  const uint64_t t0 = first + (uint64_t)piece * tiles / pieces, t1 = first + ((uint64_t)piece + 1) * tiles / pieces;
+  uint64_t b = t0 * DEC_KEY_TILE, e = t1 * DEC_KEY_TILE;
+  if (e > length) e = length;
+  if (b > e) b = e;
+  *begin = (uint32_t)b;
+  *end = (uint32_t)e;
+}
+
 template <int D> constexpr int decode16_lds_bytes() {
   constexpr int images = DEC_WAVES * DEC_STEP * D * 2;
   constexpr int merge = DEC_WAVES * 32 * (D + 4) * 4 + 2 * DEC_WAVES * 32 * 4;
   return images > merge ? images : merge;
 }
 
-template <typename T, int D, bool SPLIT, bool FP8>
+template <typename T, int D, bool SPLIT, bool FP8, bool WINDOW = false>
 __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
@@ -105,7 +132,8 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
   const uint32_t R = a.R, M = a.G * R;
   const uint32_t len = min(a.lengths[batch], a.column);
   uint32_t begin = 0, end = len;
-  if constexpr (SPLIT) decode_piece_range(len, a.pieces, piece, &begin, &end);
+  if constexpr (WINDOW) decode_window_piece_range(len, R, a.window, SPLIT ? a.pieces : 1u, piece, &begin, &end);
+  else if constexpr (SPLIT) decode_piece_range(len, a.pieces, piece, &begin, &end);
   float kscale = a.scale2, vscale = 1.0f;   // (16-bit: scale2 as it stands, and vscale is never used)
   if constexpr (FP8) {
     kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
@@ -128,6 +156,13 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
   // keys this row sees: c < lim  (causal: c <= row + max(len - R, 0); always c < len, and inside this piece c < end)
   uint32_t lim = end;
   if (a.causal) lim = min(lim, qrow + (len > R ? len - R : 0u) + 1u);
+  // WINDOW: and c >= lo = max(f + 1, W) - W; `span` = lim - lo keys from lo on (none: 0), so that visible is c - lo < span, unsigned
+  uint32_t lo = 0, span = 0;
+  if constexpr (WINDOW) {
+    const uint32_t f1 = qrow + (len > R ? len - R : 0u) + 1u;
+    lo = max(f1, a.window) - a.window;
+    span = lim > lo ? lim - lo : 0u;
+  }
 
   // ---- addresses of a step's two 16-key groups (wave-uniform; element offsets from a.k / a.v, which are byte offsets under FP8)
   const int64_t khead = (int64_t)kvh * a.hsk, vhead = (int64_t)kvh * a.hsv;
@@ -229,7 +264,7 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     float mx = DEC_MINUS_HUGE;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const bool visible = cur + (uint32_t)crow(r, hi) < lim;
+      const bool visible = WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span : cur + (uint32_t)crow(r, hi) < lim;
       s[r] = visible ? s[r] * kscale : DEC_MINUS_HUGE;
       mx = fmaxf(mx, s[r]);
     }
@@ -247,7 +282,7 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     v8 pf[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const bool visible = cur + (uint32_t)crow(r, hi) < lim;
+      const bool visible = WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span : cur + (uint32_t)crow(r, hi) < lim;
       const float p = visible ? fast_exp2(s[r] - m) : 0.f;   // replaced, never multiplied
       psum += p;
       pf[r >> 3][r & 7] = (T)p;

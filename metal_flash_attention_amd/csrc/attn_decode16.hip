@@ -1,5 +1,6 @@
 // attn_decode16.hip -- decode attention over a KV cache, 16-bit or FP8 (e4m3): the kernels' code objects, the C ABI of
-// include/mfa_decode.h and the decode entries of include/mfa_kvcache.h.  One plan serves both: the launch over an e4m3 cache adds its
+// include/mfa_decode.h, the decode entries of include/mfa_kvcache.h and those of include/mfa_window.h (a sliding window: the same
+// plan with the piece count taken from the tiles a window can span, and the attn_decode16w_* / attn_decode8w_* kernels).  One plan serves both: the launch over an e4m3 cache adds its
 // own checks in front of the 16-bit launch's, starts the attn_decode8_* kernels in place of _single / _pieces, and shares the piece
 // count, the workspace formula and the combine kernel.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
@@ -12,6 +13,7 @@
 
 #include "../../include/mfa_decode.h"
 #include "../../include/mfa_kvcache.h"
+#include "../../include/mfa_window.h"
 #include "attn_decode16.h"
 #include "cache_launch.h"
 #include "launchers.h"
@@ -20,7 +22,8 @@
 using namespace mfa;
 
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_decode16_d<D>_<type>_{single,pieces,combine} and, over
-// an e4m3 cache, attn_decode8_d<D>_<type of Q>_{single,pieces}, whose pieces attn_decode16_d<D>_<type>_combine merges
+// an e4m3 cache, attn_decode8_d<D>_<type of Q>_{single,pieces}, whose pieces attn_decode16_d<D>_<type>_combine merges; under a
+// sliding window attn_decode16w_* / attn_decode8w_*, merged by the same combine kernel
 #define MFA_DECODE_KERNELS(TN, T, D)                                                                                                  \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16_d##D##_##TN##_single(const DecodeArgs a) {                       \
     decode_body<T, D, false, false>(a);                                                                                               \
@@ -33,6 +36,18 @@ using namespace mfa;
   }                                                                                                                                   \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8_d##D##_##TN##_pieces(const DecodeArgs a) {                        \
     decode_body<T, D, true, true>(a);                                                                                                 \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16w_d##D##_##TN##_single(const DecodeArgs a) {                      \
+    decode_body<T, D, false, false, true>(a);                                                                                         \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16w_d##D##_##TN##_pieces(const DecodeArgs a) {                      \
+    decode_body<T, D, true, false, true>(a);                                                                                          \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8w_d##D##_##TN##_single(const DecodeArgs a) {                       \
+    decode_body<T, D, false, true, true>(a);                                                                                          \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8w_d##D##_##TN##_pieces(const DecodeArgs a) {                       \
+    decode_body<T, D, true, true, true>(a);                                                                                           \
   }                                                                                                                                   \
   extern "C" __global__ __launch_bounds__(256) void attn_decode16_d##D##_##TN##_combine(const DecodeArgs a) {                         \
     decode16_combine_body<T, D>(a);                                                                                                   \
@@ -49,23 +64,37 @@ struct DecodeSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  DecodeKernel single[2], pieces[2], combine;   // [fp8]
-  const char *singleName[2], *piecesName[2], *combineName;
+  DecodeKernel single[2][2], pieces[2][2], combine;   // [window][fp8]
+  const char *singleName[2][2], *piecesName[2][2], *combineName;
 };
 #define MFA_DECODE_SET(TN, PREC, D)                                                                                                   \
   {D, PREC, (uint32_t)decode16_lds_bytes<D>(),                                                                                        \
-   {attn_decode16_d##D##_##TN##_single, attn_decode8_d##D##_##TN##_single},                                                           \
-   {attn_decode16_d##D##_##TN##_pieces, attn_decode8_d##D##_##TN##_pieces}, attn_decode16_d##D##_##TN##_combine,                      \
-   {"attn_decode16_d" #D "_" #TN "_single", "attn_decode8_d" #D "_" #TN "_single"},                                                   \
-   {"attn_decode16_d" #D "_" #TN "_pieces", "attn_decode8_d" #D "_" #TN "_pieces"}, "attn_decode16_d" #D "_" #TN "_combine"}
+   {{attn_decode16_d##D##_##TN##_single, attn_decode8_d##D##_##TN##_single},                                                          \
+    {attn_decode16w_d##D##_##TN##_single, attn_decode8w_d##D##_##TN##_single}},                                                       \
+   {{attn_decode16_d##D##_##TN##_pieces, attn_decode8_d##D##_##TN##_pieces},                                                          \
+    {attn_decode16w_d##D##_##TN##_pieces, attn_decode8w_d##D##_##TN##_pieces}},                                                       \
+   attn_decode16_d##D##_##TN##_combine,                                                                                               \
+   {{"attn_decode16_d" #D "_" #TN "_single", "attn_decode8_d" #D "_" #TN "_single"},                                                  \
+    {"attn_decode16w_d" #D "_" #TN "_single", "attn_decode8w_d" #D "_" #TN "_single"}},                                               \
+   {{"attn_decode16_d" #D "_" #TN "_pieces", "attn_decode8_d" #D "_" #TN "_pieces"},                                                  \
+    {"attn_decode16w_d" #D "_" #TN "_pieces", "attn_decode8w_d" #D "_" #TN "_pieces"}},                                               \
+   "attn_decode16_d" #D "_" #TN "_combine"}
 const DecodeSet kSets[] = {MFA_DECODE_SET(bf16, MFA_BF16, 64), MFA_DECODE_SET(bf16, MFA_BF16, 128), MFA_DECODE_SET(f16, MFA_FP16, 64),
                            MFA_DECODE_SET(f16, MFA_FP16, 128)};
 
 // Pieces of the keys: chosen from the workgroups the launch has without a split (batches x K/V heads) and `column` only -- the lengths
 // live on the device.  Aims at MFA_DECODE_WORKGROUP_TARGET workgroups (two per compute unit of a 256-CU chip, what choose_splits of
-// mfa_kernel.hip aims at), rounded down; a piece keeps at least four 64-key tiles (two steps for each of the workgroup's four waves)
-uint32_t choose_pieces(uint64_t blocks, uint32_t column) {
+// mfa_kernel.hip aims at), rounded down; a piece keeps at least four 64-key tiles (two steps for each of the workgroup's four waves).
+// Under a window of W keys a sequence walks the tiles of W + rows - 1 keys that need not start on a tile: at most
+// ceil((W + rows - 1) / 64) + 1, and never more than column's.
+uint64_t planned_tiles(uint32_t column, uint32_t rows, uint32_t window) {
   const uint64_t tiles = ((uint64_t)column + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE;
+  if (!window) return tiles;
+  const uint64_t spanned = ((uint64_t)window + rows - 1 + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE + 1;
+  return spanned < tiles ? spanned : tiles;
+}
+
+uint32_t choose_pieces(uint64_t blocks, uint64_t tiles) {
   if (blocks >= MFA_DECODE_WORKGROUP_TARGET) return 1;
   uint64_t s = MFA_DECODE_WORKGROUP_TARGET / blocks;
   if (s > tiles / 4) s = tiles / 4;
@@ -81,17 +110,22 @@ struct DecodePlan {
   DecodeArgs args;
   const DecodeSet *set;
   bool fp8;
+  uint32_t window;      // 0: none
+  uint64_t tiles;       // what the piece count was chosen from
   uint32_t pieces;      // as the launch runs: 1 without a workspace
   uint32_t planned;     // what the host would cut the keys into
   uint32_t blocks;      // batches x K/V heads
   // the kernel that reads the cache, and the name a HIP failure is reported under
-  const char *name() const { return pieces > 1 ? set->piecesName[fp8] : set->singleName[fp8]; }
+  const char *name() const { return pieces > 1 ? set->piecesName[window != 0][fp8] : set->singleName[window != 0][fp8]; }
 };
 
 // every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `quant` is null for a
-// 16-bit cache; an e4m3 cache puts its own checks first, then the 16-bit launch's
-mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, DecodePlan *plan) {
+// 16-bit cache; an e4m3 cache puts its own checks first, then the 16-bit launch's.  `window` 0: none
+mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32_t window, DecodePlan *plan) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (window && !p->causal)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "a sliding window needs causal: the window is the " + std::to_string(window) +
+                                              " keys that end at a row's causal frontier (window 0: no window)");
   if (quant) {
     bool e4m3;
     const mfa_status st = check_cache_precision(quant->cachePrecision, &e4m3);
@@ -141,7 +175,9 @@ mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, Decode
   plan->set = set;
   plan->fp8 = quant != nullptr;
   plan->blocks = p->batches * (p->heads / G);
-  plan->planned = choose_pieces(plan->blocks, p->column);
+  plan->window = window;
+  plan->tiles = planned_tiles(p->column, p->rows, window);
+  plan->planned = choose_pieces(plan->blocks, plan->tiles);
   plan->pieces = plan->planned;
   if (!p->workspace) plan->pieces = 1;   // no workspace: one kernel, unsplit
   if (plan->pieces > 1) {
@@ -171,6 +207,7 @@ mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, Decode
     a.wsML = a.wsO + (uint64_t)plan->pieces * p->batches * p->heads * p->rows * p->headDimension;
   }
   if (quant) { a.keyScale = quant->keyScale; a.valueScale = quant->valueScale; }
+  a.window = window;
   return MFA_OK;
 }
 
@@ -188,19 +225,19 @@ hipError_t run(const DecodePlan &plan, hipStream_t stream) {
   const DecodeSet &s = *plan.set;
   hipError_t err;
   if (plan.pieces > 1) {
-    err = launch_kernel(s.pieces[plan.fp8], dim3(plan.blocks * plan.pieces), dim3(256), s.lds, stream, plan.args);
+    err = launch_kernel(s.pieces[plan.window != 0][plan.fp8], dim3(plan.blocks * plan.pieces), dim3(256), s.lds, stream, plan.args);
     if (err != hipSuccess) return err;
     const uint64_t rows = (uint64_t)plan.args.batches * plan.args.Hq * plan.args.R;
     err = launch_kernel(s.combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, plan.args);
   } else {
-    err = launch_kernel(s.single[plan.fp8], dim3(plan.blocks), dim3(256), s.lds, stream, plan.args);
+    err = launch_kernel(s.single[plan.window != 0][plan.fp8], dim3(plan.blocks), dim3(256), s.lds, stream, plan.args);
   }
   if (err != hipSuccess) return err;
   return hipGetLastError();
 }
 
 // the bytes of the workspace the launch would split into: 0 for an unsplit plan, whatever workspace the caller may already have bound
-mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint64_t *bytes) {
+mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, uint64_t *bytes) {
   if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   *bytes = 0;
   if (!params) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
@@ -208,16 +245,16 @@ mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_q
   probe.workspace = nullptr;
   probe.workspaceBytes = 0;
   DecodePlan plan;
-  const mfa_status st = prepare(&probe, quant, &plan);
+  const mfa_status st = prepare(&probe, quant, window, &plan);
   if (st != MFA_OK) return st;
   if (plan.planned > 1) *bytes = pieces_workspace_bytes(plan.planned, params);
   return MFA_OK;
 }
 
 mfa_status decode_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params, const mfa_kv_quant *quant,
-                         void *stream) {
+                         uint32_t window, void *stream) {
   DecodePlan plan;
-  mfa_status st = prepare(params, quant, &plan);
+  mfa_status st = prepare(params, quant, window, &plan);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -226,31 +263,33 @@ mfa_status decode_launch(const void *q, const void *k, const void *v, void *o, f
   return MFA_OK;
 }
 
-mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, char *out, size_t capacity) {
+mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, char *out, size_t capacity) {
   if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   out[0] = '\0';
   DecodePlan plan;
-  const mfa_status st = prepare(params, quant, &plan);
+  const mfa_status st = prepare(params, quant, window, &plan);
   if (st != MFA_OK) return st;
   char text[512];
   const uint32_t M = plan.args.G * plan.args.R;
+  // (a windowed launch names its window and the tiles the piece count was chosen from)
+  const std::string layout = std::string(plan.args.paged ? "paged" : "contiguous") +
+                             (window ? ", window " + std::to_string(window) + ": planned from " + std::to_string(plan.tiles) + " tiles" : "");
   if (plan.pieces > 1)
     std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x K/V heads x %u pieces, %u packed rows, %s) + %s (grid %llu)", plan.name(),
-                  plan.blocks * plan.pieces, plan.blocks, plan.pieces, M, plan.args.paged ? "paged" : "contiguous", plan.set->combineName,
+                  plan.blocks * plan.pieces, plan.blocks, plan.pieces, M, layout.c_str(), plan.set->combineName,
                   (unsigned long long)(((uint64_t)plan.args.batches * plan.args.Hq * plan.args.R + 3) / 4));
   else
-    std::snprintf(text, sizeof(text), "%s (grid %u sequences x K/V heads, %u packed rows, %s%s)", plan.name(), plan.blocks, M,
-                  plan.args.paged ? "paged" : "contiguous",
+    std::snprintf(text, sizeof(text), "%s (grid %u sequences x K/V heads, %u packed rows, %s%s)", plan.name(), plan.blocks, M, layout.c_str(),
                   plan.planned > 1 ? (", unsplit without a workspace: the plan has " + std::to_string(plan.planned) + " pieces").c_str() : "");
   copy_text(out, capacity, text);
   return MFA_OK;
 }
 
 mfa_status decode_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params, const mfa_kv_quant *quant,
-                       void *stream, int warmup, int iterations, float *milliseconds) {
+                       uint32_t window, void *stream, int warmup, int iterations, float *milliseconds) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   DecodePlan plan;
-  mfa_status st = prepare(params, quant, &plan);
+  mfa_status st = prepare(params, quant, window, &plan);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -276,20 +315,20 @@ mfa_status mfa_attention_decode_piece_range(uint32_t length, uint32_t pieces, ui
   return MFA_OK;
 }
 
-mfa_status mfa_attention_decode_workspace_size(const mfa_decode_params *params, uint64_t *bytes) { return decode_workspace_size(params, nullptr, bytes); }
+mfa_status mfa_attention_decode_workspace_size(const mfa_decode_params *params, uint64_t *bytes) { return decode_workspace_size(params, nullptr, 0, bytes); }
 
 mfa_status mfa_attention_decode_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                        void *stream) {
-  return decode_launch(q, k, v, o, l, params, nullptr, stream);
+  return decode_launch(q, k, v, o, l, params, nullptr, 0, stream);
 }
 
 mfa_status mfa_attention_decode_launch_form(const mfa_decode_params *params, char *out, size_t capacity) {
-  return decode_launch_form(params, nullptr, out, capacity);
+  return decode_launch_form(params, nullptr, 0, out, capacity);
 }
 
 mfa_status mfa_attention_decode_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                      void *stream, int warmup, int iterations, float *milliseconds) {
-  return decode_time(q, k, v, o, l, params, nullptr, stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, nullptr, 0, stream, warmup, iterations, milliseconds);
 }
 
 // ---- over an e4m3 cache (include/mfa_kvcache.h): the same four with the cache's mfa_kv_quant, which is required
@@ -304,27 +343,61 @@ mfa_status mfa_attention_decode_fp8_workspace_size(const mfa_decode_params *para
   if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   *bytes = 0;
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_workspace_size(params, quant, bytes);
+  return decode_workspace_size(params, quant, 0, bytes);
 }
 
 mfa_status mfa_attention_decode_fp8_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                            const mfa_kv_quant *quant, void *stream) {
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_launch(q, k, v, o, l, params, quant, stream);
+  return decode_launch(q, k, v, o, l, params, quant, 0, stream);
 }
 
 mfa_status mfa_attention_decode_fp8_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, char *out, size_t capacity) {
   if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   out[0] = '\0';
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_launch_form(params, quant, out, capacity);
+  return decode_launch_form(params, quant, 0, out, capacity);
 }
 
 mfa_status mfa_attention_decode_fp8_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                          const mfa_kv_quant *quant, void *stream, int warmup, int iterations, float *milliseconds) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_time(q, k, v, o, l, params, quant, stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, quant, 0, stream, warmup, iterations, milliseconds);
+}
+
+// ---- under a sliding window (include/mfa_window.h): the same four with `window` after `quant`, which is null for a 16-bit cache.
+// window 0 is the launch without a window, whichever cache
+
+mfa_status mfa_attention_decode_window_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
+                                                      uint64_t *bytes) {
+  return decode_workspace_size(params, quant, window, bytes);
+}
+
+mfa_status mfa_attention_decode_window_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
+                                              const mfa_kv_quant *quant, uint32_t window, void *stream) {
+  return decode_launch(q, k, v, o, l, params, quant, window, stream);
+}
+
+mfa_status mfa_attention_decode_window_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, char *out,
+                                                   size_t capacity) {
+  return decode_launch_form(params, quant, window, out, capacity);
+}
+
+mfa_status mfa_attention_decode_window_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
+                                            const mfa_kv_quant *quant, uint32_t window, void *stream, int warmup, int iterations,
+                                            float *milliseconds) {
+  return decode_time(q, k, v, o, l, params, quant, window, stream, warmup, iterations, milliseconds);
+}
+
+mfa_status mfa_attention_decode_window_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t pieces, uint32_t piece,
+                                                   uint32_t *begin, uint32_t *end) {
+  if (!begin || !end) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (pieces == 0 || piece >= pieces) return fail(MFA_ERR_INVALID_ARGUMENT, "piece must be below pieces, pieces non-zero");
+  if (window == 0 || rows == 0)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "window and rows must be non-zero (no window: mfa_attention_decode_piece_range)");
+  decode_window_piece_range(length, rows, window, pieces, piece, begin, end);
+  return MFA_OK;
 }
 
 } // extern "C"

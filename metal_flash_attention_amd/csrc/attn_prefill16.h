@@ -23,6 +23,13 @@
 //     first_masked) run without the per-element mask, [first_masked, end) with it, tiles at or past end are never loaded.
 //   * what may hold poison is never loaded: key rows at or past n come in as zeros (K and V), a masked score is REPLACED (p = 0 exactly),
 //     and the running maximum only ever sees visible keys -- a row without a visible key keeps m = -FLT_MAX, l = 0.
+//
+// WINDOW: the same body under a sliding window of a.window >= 1 keys (include/mfa_window.h): row r sees the keys
+// lo(r) <= c < lim(r), lo = max(f + 1, W) - W.  prefill_window_tile_range gives the block four tile indices: [begin, unmaskedBegin)
+// runs with the per-element mask (a row's window starts inside), [unmaskedBegin, unmaskedEnd) without, [unmaskedEnd, end) with it
+// again (causal frontiers and n); tiles outside [begin, end) are never loaded -- no key, no page, no block-table entry.  The first
+// load is tile `begin`, the buffer of tile t is (t - begin) & 1.  The mask is one unsigned comparison c - lo < lim - lo.  With
+// W >= column + rows: begin = unmaskedBegin = 0, unmaskedEnd = first_masked -- the plain kernel's arithmetic in the plain order.
 #pragma once
 #include "attn_decode16.h"
 #include "kv_e4m3.h"
@@ -54,6 +61,7 @@ struct PrefillArgs {
   uint32_t paged, pageShift;      // pageSize = 1 << pageShift
   uint32_t causal, outF32;
   float scale2;                   // log2(e) / sqrt(D)
+  uint32_t window;                // the WINDOW kernels only (>= 1); last, so that no other field moves
 };
 
 // The tiles of the block of rows [r0, r0 + RB) of a sequence of n keys and qn rows.  Row r sees keys c < lim(r) = n, or with `causal`
@@ -82,9 +90,35 @@ __host__ __device__ __forceinline__ void prefill_tile_range(uint32_t n, uint32_t
   *end = (uint32_t)e;
 }
 
+// The same under a window of `window` >= 1 keys (causal): row r sees lo(r) <= c < lim(r) with f1 = r + max(n - qn, 0) + 1,
+// lim = min(n, f1), lo = max(f1, window) - window; both grow with r.  *begin = floor(lo(r0) / 64), *end = ceil(lim(last live row) / 64):
+// the tightest range that holds every visible key.  [*unmaskedBegin, *unmaskedEnd) = [ceil(lo(last) / 64), floor(lim(r0) / 64)): the
+// tiles whose every key every live row sees; empty: both = *begin.  A block without a live row or without a visible key: all 0.
+// Device and host (mfa_attention_prefill_window_tile_range) run this one body.
+__host__ __device__ __forceinline__ void prefill_window_tile_range(uint32_t n, uint32_t qn, uint32_t r0, uint32_t RB, uint32_t window,
+                                                                   uint32_t *begin, uint32_t *unmaskedBegin, uint32_t *unmaskedEnd,
+                                                                   uint32_t *end) {
+  *begin = *unmaskedBegin = *unmaskedEnd = *end = 0;
+  if (r0 >= qn || n == 0) return;
+  const uint64_t off = n > qn ? (uint64_t)n - qn : 0, W = window;
+  uint64_t last = (uint64_t)r0 + RB;
+  if (last > qn) last = qn;
+  const uint64_t f1First = (uint64_t)r0 + off + 1, f1Last = last + off;
+  const uint64_t loFirst = (f1First > W ? f1First : W) - W, loLast = (f1Last > W ? f1Last : W) - W;
+  if (loFirst >= n) return;   // (n < qn: the window of the block's first row, and of every later one, lies past the keys)
+  const uint64_t limFirst = f1First < n ? f1First : n, limLast = f1Last < n ? f1Last : n;
+  const uint64_t b = loFirst / PF_TILE, e = (limLast + PF_TILE - 1) / PF_TILE;
+  uint64_t u0 = (loLast + PF_TILE - 1) / PF_TILE, u1 = limFirst / PF_TILE;
+  if (u0 >= u1) u0 = u1 = b;
+  *begin = (uint32_t)b;
+  *unmaskedBegin = (uint32_t)u0;
+  *unmaskedEnd = (uint32_t)u1;
+  *end = (uint32_t)e;
+}
+
 template <int D> constexpr int prefill16_lds_bytes() { return 2 /*buffers*/ * 2 /*K, V*/ * PF_TILE * D * 2; }
 
-template <typename T, int D, bool FP8>
+template <typename T, int D, bool FP8, bool WINDOW = false>
 __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
@@ -112,8 +146,9 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   const uint32_t qn = a.qlengths ? min(a.qlengths[batch], a.rows) : a.rows;
   const uint32_t RB = a.RB, r0 = rb * RB;
   if (r0 >= qn) return;   // no live row: nothing is read or written
-  uint32_t firstMasked, endTile;
-  prefill_tile_range(n, qn, r0, RB, a.causal, &firstMasked, &endTile);
+  uint32_t firstMasked, endTile, beginTile = 0, unmaskedBegin = 0;   // (WINDOW: firstMasked is unmaskedEnd)
+  if constexpr (WINDOW) prefill_window_tile_range(n, qn, r0, RB, a.window, &beginTile, &unmaskedBegin, &firstMasked, &endTile);
+  else prefill_tile_range(n, qn, r0, RB, a.causal, &firstMasked, &endTile);
   const float kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
   const float vscale = a.valueScale ? a.valueScale[kvh] : 1.0f;
 
@@ -132,6 +167,13 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   // keys this row sees: c < lim
   uint32_t lim = n;
   if (a.causal) lim = min(lim, row + (n > qn ? n - qn : 0u) + 1u);
+  // WINDOW: and c >= lo = max(f + 1, W) - W; `span` = lim - lo keys from lo on (none: 0), so that visible is c - lo < span, unsigned
+  uint32_t lo = 0, span = 0;
+  if constexpr (WINDOW) {
+    const uint32_t f1 = row + (n > qn ? n - qn : 0u) + 1u;
+    lo = max(f1, a.window) - a.window;
+    span = lim > lo ? lim - lo : 0u;
+  }
 
   // ---- addresses of a 16-key group (wave-uniform; element offsets from a.k / a.v)
   const int64_t ldk = a.ldk, ldv = a.ldv, psk = a.psk, psv = a.psv;   // (values, not fields of `a`: hipcc otherwise selects between
@@ -233,7 +275,7 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
       float mx = DEC_MINUS_HUGE;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const bool visible = !MASK || cur + (uint32_t)crow(r, hi) < lim;
+        const bool visible = !MASK || (WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span : cur + (uint32_t)crow(r, hi) < lim);
         s[r] = visible ? s[r] * kscale : DEC_MINUS_HUGE;
         mx = fmaxf(mx, s[r]);
       }
@@ -251,7 +293,7 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
       v8 pf[2];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const bool visible = !MASK || cur + (uint32_t)crow(r, hi) < lim;
+        const bool visible = !MASK || (WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span : cur + (uint32_t)crow(r, hi) < lim);
         const float pr = visible ? fast_exp2(s[r] - m) : 0.f;   // replaced, never multiplied
         psum += pr;
         pf[r >> 3][r & 7] = (T)pr;
@@ -273,14 +315,14 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
 
   // ---- the tiles: the loads of tile t + 1 fly under the arithmetic of tile t and land in the other buffer behind it.  One barrier
   // per tile: the buffer written in iteration t was last read in iteration t - 1, which every wave left through that barrier.
-  if (endTile > 0) {
-    issue_loads(0u);
+  if (endTile > beginTile) {
+    issue_loads(beginTile * PF_TILE);
     write_lds(0);
   }
   __syncthreads();
   auto tile = [&](auto maskTag, uint32_t t) MFA_PREFILL_INLINE {
     const bool more = t + 1 < endTile;
-    const int buf = (int)(t & 1u);
+    const int buf = (int)((t - beginTile) & 1u);
     if (more) issue_loads((t + 1) * PF_TILE);
     compute(maskTag, t * PF_TILE, buf, 0);
     compute(maskTag, t * PF_TILE, buf, 1);
@@ -289,7 +331,9 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   };
   // (two loops, not one loop with the choice inside: with both forms of a step merging in one loop body hipcc spilled 6 .. 19 VGPRs
   // of the D = 128 kernels; like this the largest takes 232 of 256)
-  uint32_t t = 0;
+  uint32_t t = beginTile;
+  if constexpr (WINDOW)   // (a third loop in front: the tiles in which some row's window starts)
+    for (; t < unmaskedBegin; ++t) tile(std::true_type{}, t);
   for (; t < firstMasked; ++t) tile(std::false_type{}, t);
   for (; t < endTile; ++t) tile(std::true_type{}, t);
 

@@ -1,4 +1,5 @@
-// attn_prefill16.hip -- prefill attention over a KV cache: the kernels' code objects and the C ABI of include/mfa_prefill.h.
+// attn_prefill16.hip -- prefill attention over a KV cache: the kernels' code objects, the C ABI of include/mfa_prefill.h and the prefill
+// entries of include/mfa_window.h (a sliding window: the same checks and grid, the attn_prefill16w_* kernels).
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,7 @@
 #include <string>
 
 #include "../../include/mfa_prefill.h"
+#include "../../include/mfa_window.h"
 #include "attn_prefill16.h"
 #include "cache_launch.h"
 #include "launchers.h"
@@ -16,13 +18,20 @@
 
 using namespace mfa;
 
-// Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_prefill16_d<D>_<type>[_e4m3]
+// Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_prefill16_d<D>_<type>[_e4m3], and attn_prefill16w_*
+// under a sliding window
 #define MFA_PREFILL_KERNELS(TN, T, D)                                                                                                 \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16_d##D##_##TN(const PrefillArgs a) {                              \
     prefill16_body<T, D, false>(a);                                                                                                   \
   }                                                                                                                                   \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16_d##D##_##TN##_e4m3(const PrefillArgs a) {                       \
     prefill16_body<T, D, true>(a);                                                                                                    \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16w_d##D##_##TN(const PrefillArgs a) {                             \
+    prefill16_body<T, D, false, true>(a);                                                                                             \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16w_d##D##_##TN##_e4m3(const PrefillArgs a) {                      \
+    prefill16_body<T, D, true, true>(a);                                                                                              \
   }
 MFA_PREFILL_KERNELS(bf16, __bf16, 64)
 MFA_PREFILL_KERNELS(bf16, __bf16, 128)
@@ -36,12 +45,14 @@ struct PrefillSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  PrefillKernel plain, e4m3;
-  const char *plainName, *e4m3Name;
+  PrefillKernel kernel[2][2];   // [window][e4m3]
+  const char *name[2][2];
 };
 #define MFA_PREFILL_SET(TN, PREC, D)                                                                                                  \
-  {D, PREC, (uint32_t)prefill16_lds_bytes<D>(), attn_prefill16_d##D##_##TN, attn_prefill16_d##D##_##TN##_e4m3,                        \
-   "attn_prefill16_d" #D "_" #TN, "attn_prefill16_d" #D "_" #TN "_e4m3"}
+  {D, PREC, (uint32_t)prefill16_lds_bytes<D>(),                                                                                       \
+   {{attn_prefill16_d##D##_##TN, attn_prefill16_d##D##_##TN##_e4m3}, {attn_prefill16w_d##D##_##TN, attn_prefill16w_d##D##_##TN##_e4m3}}, \
+   {{"attn_prefill16_d" #D "_" #TN, "attn_prefill16_d" #D "_" #TN "_e4m3"},                                                           \
+    {"attn_prefill16w_d" #D "_" #TN, "attn_prefill16w_d" #D "_" #TN "_e4m3"}}}
 const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(f16, MFA_FP16, 64),
                             MFA_PREFILL_SET(f16, MFA_FP16, 128)};
 
@@ -49,14 +60,18 @@ struct PrefillPlan {
   PrefillArgs args;
   const PrefillSet *set;
   bool fp8;
+  uint32_t window;   // 0: none
   uint32_t blocks;   // batches x K/V heads x row blocks
-  PrefillKernel kernel() const { return fp8 ? set->e4m3 : set->plain; }
-  const char *name() const { return fp8 ? set->e4m3Name : set->plainName; }
+  PrefillKernel kernel() const { return set->kernel[window != 0][fp8]; }
+  const char *name() const { return set->name[window != 0][fp8]; }
 };
 
-// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind)
-mfa_status prepare(const mfa_prefill_params *p, PrefillPlan *plan) {
+// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `window` 0: none
+mfa_status prepare(const mfa_prefill_params *p, uint32_t window, PrefillPlan *plan) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (window && !p->causal)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "a sliding window needs causal: the window is the " + std::to_string(window) +
+                                              " keys that end at a row's causal frontier (window 0: no window)");
   if (p->precision == MFA_FP32)
     return fail(MFA_ERR_UNSUPPORTED, "prefill attention takes a 16-bit Q (precision MFA_BF16 or MFA_FP16); FP32 Q has no kernel");
   if (p->precision != MFA_BF16 && p->precision != MFA_FP16) return fail(MFA_ERR_INVALID_ARGUMENT, "precision must be MFA_FP16 or MFA_BF16");
@@ -102,6 +117,7 @@ mfa_status prepare(const mfa_prefill_params *p, PrefillPlan *plan) {
     return fail(MFA_ERR_UNSUPPORTED, "batches x K/V heads x row blocks = " + std::to_string(blocks) + " workgroups exceed one grid (2^31 - 1)");
   plan->set = set;
   plan->fp8 = fp8;
+  plan->window = window;
   plan->blocks = (uint32_t)blocks;
   PrefillArgs &a = plan->args;
   std::memset(&a, 0, sizeof(a));
@@ -121,6 +137,7 @@ mfa_status prepare(const mfa_prefill_params *p, PrefillPlan *plan) {
   a.paged = p->pageSize != 0; a.pageShift = pageShift;
   a.causal = p->causal != 0; a.outF32 = p->outputPrecision == MFA_FP32;
   a.scale2 = 1.44269504089f / std::sqrt((float)p->headDimension);
+  a.window = window;
   return MFA_OK;
 }
 
@@ -178,10 +195,10 @@ mfa_status mfa_attention_prefill_tile_range(uint32_t length, uint32_t queryLengt
   return MFA_OK;
 }
 
-mfa_status mfa_attention_prefill_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
-                                        void *stream) {
+static mfa_status prefill_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                 uint32_t window, void *stream) {
   PrefillPlan plan;
-  mfa_status st = prepare(params, &plan);
+  mfa_status st = prepare(params, window, &plan);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -190,29 +207,69 @@ mfa_status mfa_attention_prefill_launch(const void *q, const void *k, const void
   return MFA_OK;
 }
 
-mfa_status mfa_attention_prefill_launch_form(const mfa_prefill_params *params, char *out, size_t capacity) {
+static mfa_status prefill_launch_form(const mfa_prefill_params *params, uint32_t window, char *out, size_t capacity) {
   if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   out[0] = '\0';
   PrefillPlan plan;
-  const mfa_status st = prepare(params, &plan);
+  const mfa_status st = prepare(params, window, &plan);
   if (st != MFA_OK) return st;
   const PrefillArgs &a = plan.args;
   char text[512];
-  std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s)", plan.name(),
-                plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous");
+  std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s%s)", plan.name(),
+                plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous",
+                window ? (", window " + std::to_string(window)).c_str() : "");
   copy_text(out, capacity, text);
   return MFA_OK;
 }
 
-mfa_status mfa_attention_prefill_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
-                                      void *stream, int warmup, int iterations, float *milliseconds) {
+static mfa_status prefill_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                               uint32_t window, void *stream, int warmup, int iterations, float *milliseconds) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   PrefillPlan plan;
-  mfa_status st = prepare(params, &plan);
+  mfa_status st = prepare(params, window, &plan);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
   return time_launches((hipStream_t)stream, warmup, iterations, milliseconds, plan.name(), [&](hipStream_t s) { return run(plan, s); });
+}
+
+mfa_status mfa_attention_prefill_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                        void *stream) {
+  return prefill_launch(q, k, v, o, l, params, 0, stream);
+}
+
+mfa_status mfa_attention_prefill_launch_form(const mfa_prefill_params *params, char *out, size_t capacity) {
+  return prefill_launch_form(params, 0, out, capacity);
+}
+
+mfa_status mfa_attention_prefill_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                      void *stream, int warmup, int iterations, float *milliseconds) {
+  return prefill_time(q, k, v, o, l, params, 0, stream, warmup, iterations, milliseconds);
+}
+
+// ---- under a sliding window (include/mfa_window.h): the same three with `window` after `params`; window 0 is the launch without one
+
+mfa_status mfa_attention_prefill_window_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                               uint32_t window, void *stream) {
+  return prefill_launch(q, k, v, o, l, params, window, stream);
+}
+
+mfa_status mfa_attention_prefill_window_launch_form(const mfa_prefill_params *params, uint32_t window, char *out, size_t capacity) {
+  return prefill_launch_form(params, window, out, capacity);
+}
+
+mfa_status mfa_attention_prefill_window_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                             uint32_t window, void *stream, int warmup, int iterations, float *milliseconds) {
+  return prefill_time(q, k, v, o, l, params, window, stream, warmup, iterations, milliseconds);
+}
+
+mfa_status mfa_attention_prefill_window_tile_range(uint32_t length, uint32_t queryLength, uint32_t firstRow, uint32_t blockRows, uint32_t window,
+                                                   uint32_t *begin, uint32_t *unmaskedBegin, uint32_t *unmaskedEnd, uint32_t *end) {
+  if (!begin || !unmaskedBegin || !unmaskedEnd || !end) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (blockRows == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "blockRows must be non-zero");
+  if (window == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "window must be non-zero (no window: mfa_attention_prefill_tile_range)");
+  prefill_window_tile_range(length, queryLength, firstRow, blockRows, window, begin, unmaskedBegin, unmaskedEnd, end);
+  return MFA_OK;
 }
 
 } // extern "C"

@@ -298,7 +298,7 @@ def _cache_strides(t, paged):
     return (int(t.stride(2)) if t.shape[2] > 1 else int(t.shape[3]), int(t.stride(1)), 0 if paged else int(t.stride(0)))
 
 
-def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None):
+def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None):
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
         raise RuntimeError("flash_decode: tensors must live on the GPU (there is no CPU path)")
     if fp8:
@@ -347,6 +347,8 @@ def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=Fal
     kw.update(rows=R, column=column, heads=H, batches=B, headsPerKeyValue=H // Hkv, causal=bool(causal), cacheLengths=lengths,
               strides=dict(Q=(int(q.stride(2)) if R > 1 else D, int(q.stride(1)), int(q.stride(0))),
                            K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
+    if window is not None:
+        kw.update(window=int(window))
     need = dec.workspaceSize(**kw)
     ws = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
     with torch.cuda.device(q.device):
@@ -509,7 +511,7 @@ _HAVE_DECODE_OP = _register_decode_op()
 
 def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                  block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False,
-                 k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None):
+                 k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, window: Optional[int] = None):
     """Attention of the R new rows of every sequence (q [B, H, R, D]; R = 1, or a few speculative tokens; G R <= 32 with G = H / Hkv)
     against its KV cache.  cache_lengths [B] (GPU, int32): valid keys per sequence INCLUDING the R new tokens, which the caller has
     already written into the cache; with `causal` row r sees key c iff c <= r + max(len - R, 0).  Caches: [B, Hkv, C, D], or any view
@@ -520,13 +522,22 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     O = 0.  Goes through the torch.library op `mfa::attention_decode` where torch has custom ops, so it traces under torch.compile.
     FP8 caches (torch.float8_e4m3fn, written by kv_cache_append): k_scale / v_scale [Hkv] fp32 on the GPU (None = 1.0), a cache byte
     of head j stands for scale[j] x e4m3(byte); the launch goes through the op `mfa::attention_decode_fp8`.  Scales with a 16-bit
-    cache are an error."""
+    cache are an error.
+    window=W (an int >= 1; needs causal): sliding-window attention -- a row sees its frontier and the W - 1 keys before it; keys, pages
+    and block-table entries below the first 64-key tile a sequence's rows see are never read (include/mfa_window.h).  Goes through the
+    op `mfa::attention_decode_window`, for 16-bit and e4m3 caches alike.  None: no window."""
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
         raise RuntimeError("flash_decode: tensors must live on the GPU (there is no CPU path)")
     for t in (q, k_cache, v_cache):
         if t.requires_grad:
             raise RuntimeError("flash_decode is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
-    if k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES:
+    if window is not None:
+        _check_window("flash_decode", window, causal)
+        if _HAVE_WINDOW_OPS:
+            o, l = torch.ops.mfa.attention_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window)
+        else:
+            o, l = _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window)
+    elif k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES:
         if _HAVE_KVCACHE_OPS:
             o, l = torch.ops.mfa.attention_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale)
         else:
@@ -544,7 +555,7 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
 _PREFILLERS: Dict[Tuple, AttentionPrefill] = {}
 
 
-def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale):
+def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None):
     who = "flash_prefill"
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
         raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
@@ -601,6 +612,8 @@ def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, cau
               queryLengths=qlens,
               strides=dict(Q=(int(q.stride(2)) if R > 1 else D, int(q.stride(1)), int(q.stride(0))),
                            K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
+    if window is not None:
+        kw.update(window=int(window))
     with torch.cuda.device(q.device):
         pre.dispatch(q, k_cache, v_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
     return o, l
@@ -632,9 +645,64 @@ def _register_prefill_op():
 _HAVE_PREFILL_OP = _register_prefill_op()
 
 
+def _check_window(who, window, causal):
+    if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window < 2 ** 32:
+        raise ValueError(f"{who}: window must be an int from 1 to 2^32 - 1 (None: no window), not {window!r}")
+    if not causal:
+        raise ValueError(f"{who}: a sliding window needs causal=True (the window lies behind the row's causal frontier)")
+
+
+def _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window):
+    fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError("flash_decode: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache holds the values themselves")
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8, k_scale, v_scale, window)
+
+
+def _register_window_ops():
+    """mfa::attention_decode_window (16-bit and e4m3 caches: one op) and mfa::attention_prefill_window (include/mfa_window.h).  The
+    ops without a window keep their schemas."""
+    if not hasattr(torch.library, "custom_op"):
+        return False
+    try:
+        torch.ops.mfa.attention_decode_window  # noqa: B018 -- AttributeError when the op is not defined yet
+        torch.ops.mfa.attention_prefill_window  # noqa: B018
+        return True
+    except (AttributeError, RuntimeError):
+        pass
+
+    @torch.library.custom_op("mfa::attention_decode_window", mutates_args=(), device_types="cuda")
+    def _op_decode_window(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                          block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
+                          v_scale: Optional[torch.Tensor], window: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        return _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window)
+
+    @_op_decode_window.register_fake
+    def _op_decode_window_fake(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window):
+        B, H, R, D = q.shape
+        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
+
+    @torch.library.custom_op("mfa::attention_prefill_window", mutates_args=(), device_types="cuda")
+    def _op_prefill_window(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                           q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
+                           k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window)
+
+    @_op_prefill_window.register_fake
+    def _op_prefill_window_fake(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window):
+        B, H, R, D = q.shape
+        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
+
+    return True
+
+
+_HAVE_WINDOW_OPS = _register_window_ops()
+
+
 def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                   q_lengths: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None, causal: bool = True,
-                  k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, return_lse: bool = False):
+                  k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, return_lse: bool = False,
+                  window: Optional[int] = None):
     """Attention of a BLOCK of new rows of every sequence (q [B, H, R, D], any R: a chunk of a prompt, a reused prefix's tail, a long
     speculative block) against its KV cache, which already holds the new tokens (kv_cache_append first).  cache_lengths [B] (GPU):
     valid keys per sequence INCLUDING the new tokens; q_lengths [B] (GPU, None = R for every sequence): the new rows of sequence b,
@@ -644,13 +712,20 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     q, or torch.float8_e4m3fn with k_scale / v_scale [Hkv] fp32 on the GPU (None = 1.0; a byte of head j stands for scale[j] x
     e4m3(byte)).  The G = H / Hkv query heads of a K/V head share one workgroup (G <= 32), so K and V are read once per group.
     Forward only.  return_lse: also L [B, H, R] fp32 in natural units.  Goes through the torch.library op `mfa::attention_prefill`
-    where torch has custom ops, so it traces under torch.compile."""
+    where torch has custom ops, so it traces under torch.compile.  window=W (an int >= 1; needs causal): sliding-window attention as
+    flash_decode's, through the op `mfa::attention_prefill_window`; None: no window."""
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
         raise RuntimeError("flash_prefill: tensors must live on the GPU (there is no CPU path)")
     for t in (q, k_cache, v_cache):
         if t.requires_grad:
             raise RuntimeError("flash_prefill is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
-    if _HAVE_PREFILL_OP:
+    if window is not None:
+        _check_window("flash_prefill", window, causal)
+        if _HAVE_WINDOW_OPS:
+            o, l = torch.ops.mfa.attention_prefill_window(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window)
+        else:
+            o, l = _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window)
+    elif _HAVE_PREFILL_OP:
         o, l = torch.ops.mfa.attention_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
     else:
         o, l = _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
