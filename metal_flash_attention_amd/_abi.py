@@ -270,6 +270,30 @@ WINDOW_SYMBOLS = [   # include/mfa_window.h: `window` (uint32, 0 = none) after `
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U32P, _U32P, _U32P, _U32P]),
 ]
 
+class mfa_attention_sinks(ctypes.Structure):   # include/mfa_sink.h
+    _fields_ = [("sinkTokens", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("sinkLogits", ctypes.c_void_p)]
+
+
+_SINKS = ctypes.POINTER(mfa_attention_sinks)
+_U32x2 = ctypes.c_uint32 * 2
+
+SINK_SYMBOLS = [   # include/mfa_sink.h: `sinks` (required) after `window` (0 = none)
+    ("mfa_attention_sinks_init", None, [_SINKS]),
+    ("mfa_attention_sinks_size", ctypes.c_size_t, []),
+    ("mfa_attention_sinks_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
+    ("mfa_attention_decode_sink_workspace_size", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, ctypes.POINTER(ctypes.c_uint64)]),
+    ("mfa_attention_decode_sink_launch", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, ctypes.c_void_p]),
+    ("mfa_attention_decode_sink_launch_form", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_decode_sink_time", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, ctypes.c_void_p] + _TIMING),
+    ("mfa_attention_decode_sink_piece_range", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_U32x2),
+      ctypes.POINTER(_U32x2)]),
+    ("mfa_attention_prefill_sink_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, ctypes.c_void_p]),
+    ("mfa_attention_prefill_sink_launch_form", ctypes.c_int, [_PREFILL, ctypes.c_uint32, _SINKS, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_prefill_sink_time", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, ctypes.c_void_p] + _TIMING),
+    ("mfa_attention_prefill_sink_tile_range", ctypes.c_int, [ctypes.c_uint32] * 7 + [_U32P] * 5),
+]
+
 SYMBOLS = [
     ("mfa_precision_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mfa_precision_size", ctypes.c_int, [ctypes.c_int]),
@@ -345,7 +369,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -401,6 +401,24 @@ def deviceName(device: int = 0) -> str:
     return buf.value.decode()
 
 
+def _sinks_block(shape):
+    """pops sinkTokens= / sinkLogits= from a launch's keywords -> (mfa_attention_sinks, what it points to), or None when neither is
+    given (include/mfa_sink.h: the block is required by the sink entries, so None means the entries without sinks)"""
+    tokens, logits = shape.pop("sinkTokens", None), shape.pop("sinkLogits", None)
+    if tokens is None and logits is None:
+        return None
+    block = _abi.mfa_attention_sinks()
+    lib().mfa_attention_sinks_init(ctypes.byref(block))
+    block.sinkTokens = int(tokens or 0)
+    block.sinkLogits = _pointer(logits)
+    return block, logits
+
+
+def _extended(shape) -> bool:
+    """whether a launch's keywords ask for the window or sink entries"""
+    return any(shape.get(name) is not None for name in ("window", "sinkTokens", "sinkLogits"))
+
+
 class AttentionDecode:
     """Decode attention over a KV cache (include/mfa_decode.h; an extension, the reference has no such entry): `rows` new query rows
     per sequence against caches of `heads // headsPerKeyValue` K / V heads, per-sequence lengths on the device, contiguous or paged.
@@ -415,7 +433,11 @@ class AttentionDecode:
     pageStrides=(K, V); a cache operand's batchStride is then unused.
 
     window=W (workspaceSize, launchForm, dispatch, time): sliding-window attention, include/mfa_window.h -- row r sees its causal
-    frontier and the W - 1 keys before it.  None: the plain launch; 0 goes through the window entries and is the plain launch."""
+    frontier and the W - 1 keys before it.  None: the plain launch; 0 goes through the window entries and is the plain launch.
+
+    sinkTokens=S, sinkLogits=device FP32 [heads] (the same four methods): attention sinks, include/mfa_sink.h -- the keys [0, S) stay
+    visible under the window (needs window >= 1), and one logit per query head joins the softmax denominator (natural-log units,
+    any window).  Either keyword, even 0 / None beside the other, goes through the sink entries."""
 
     OPERANDS = ("Q", "K", "V", "O")
 
@@ -429,12 +451,16 @@ class AttentionDecode:
         """the mfa_kv_quant block of the window entries: none for a 16-bit cache"""
         return None, None
 
-    def _window(self, entry, window, shape, *head, tail=()):
-        """one of the four mfa_attention_decode_window_* entries: `head` arguments, params, quant, window, `tail` arguments"""
+    def _window(self, entry, window, shape, *head, tail=(), sinks=None):
+        """one of the four mfa_attention_decode_window_* entries: `head` arguments, params, quant, window, `tail` arguments; with a
+        `sinks` block the mfa_attention_decode_sink_* entry of the same name, which takes it after the window (None there: 0)"""
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape)
-        check(getattr(lib(), "mfa_attention_decode_window_" + entry)(*head, ctypes.byref(p), None if quant is None else ctypes.byref(quant),
-                                                                     int(window), *tail))
+        q = None if quant is None else ctypes.byref(quant)
+        if sinks is not None:
+            check(getattr(lib(), "mfa_attention_decode_sink_" + entry)(*head, ctypes.byref(p), q, int(window or 0), ctypes.byref(sinks[0]), *tail))
+        else:
+            check(getattr(lib(), "mfa_attention_decode_window_" + entry)(*head, ctypes.byref(p), q, int(window), *tail))
 
     def _params(self, *, rows: int, column: int, heads: int = 1, batches: int = 1, headsPerKeyValue: int = 1, causal: bool = True,
                 cacheLengths=None, pageSize: int = 0, blockTable=None, blockTableStride: int = 0, strides: Optional[Mapping] = None,
@@ -467,10 +493,10 @@ class AttentionDecode:
     def workspaceSize(self, **shape) -> int:
         """Bytes a launch of this shape wants to be cut along the keys (0: the plan has one piece).  Without a workspace the launch
         runs unsplit in one kernel."""
-        window = shape.pop("window", None)
+        window, sinks = shape.pop("window", None), _sinks_block(shape)
         out = ctypes.c_uint64(0)
-        if window is not None:
-            self._window("workspace_size", window, shape, tail=(ctypes.byref(out),))
+        if window is not None or sinks is not None:
+            self._window("workspace_size", window, shape, tail=(ctypes.byref(out),), sinks=sinks)
             return int(out.value)
         p, _keep = self._params(**shape)
         check(lib().mfa_attention_decode_workspace_size(ctypes.byref(p), ctypes.byref(out)))
@@ -479,31 +505,31 @@ class AttentionDecode:
     def launchForm(self, **shape) -> str:
         """What `dispatch` with the same arguments would run (nothing is launched): the pieces kernel, the piece count and the combine
         kernel, or the single kernel."""
-        window = shape.pop("window", None)
+        window, sinks = shape.pop("window", None), _sinks_block(shape)
         out = ctypes.create_string_buffer(512)
-        if window is not None:
-            self._window("launch_form", window, shape, tail=(out, len(out)))
+        if window is not None or sinks is not None:
+            self._window("launch_form", window, shape, tail=(out, len(out)), sinks=sinks)
             return out.value.decode()
         p, _keep = self._params(**shape)
         check(lib().mfa_attention_decode_launch_form(ctypes.byref(p), out, len(out)))
         return out.value.decode()
 
     def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
-        window = shape.pop("window", None)
-        if window is not None:
+        window, sinks = shape.pop("window", None), _sinks_block(shape)
+        if window is not None or sinks is not None:
             return self._window("launch", window, shape, _pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l),
-                                tail=(ctypes.c_void_p(stream or 0),))
+                                tail=(ctypes.c_void_p(stream or 0),), sinks=sinks)
         p, _keep = self._params(**shape)
         check(lib().mfa_attention_decode_launch(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
                                                 ctypes.c_void_p(stream or 0)))
 
     def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
         """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
-        window = shape.pop("window", None)
+        window, sinks = shape.pop("window", None), _sinks_block(shape)
         ms = ctypes.c_float(0.0)
-        if window is not None:
+        if window is not None or sinks is not None:
             self._window("time", window, shape, _pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l),
-                         tail=(ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
+                         tail=(ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)), sinks=sinks)
             return float(ms.value)
         p, _keep = self._params(**shape)
         check(lib().mfa_attention_decode_time(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
@@ -524,6 +550,15 @@ class AttentionDecode:
         check(lib().mfa_attention_decode_window_piece_range(int(length), int(rows), int(window), int(pieces), int(piece), ctypes.byref(b),
                                                             ctypes.byref(e)))
         return int(b.value), int(e.value)
+
+    @staticmethod
+    def sinkPieceRange(length: int, rows: int, window: int, sinkTokens: int, pieces: int, piece: int) -> Tuple[Tuple[int, int], Tuple[int, int]]:
+        """((begin, end) of the sink tiles, (begin, end) of the window's tiles) of piece `piece` of `pieces` of a launch with sink
+        tokens (include/mfa_sink.h): the kernels' own function, on the host"""
+        b, e = _abi._U32x2(0, 0), _abi._U32x2(0, 0)
+        check(lib().mfa_attention_decode_sink_piece_range(int(length), int(rows), int(window), int(sinkTokens), int(pieces), int(piece),
+                                                          ctypes.byref(b), ctypes.byref(e)))
+        return (int(b[0]), int(e[0])), (int(b[1]), int(e[1]))
 
 
 class KVCachePrecision(enum.IntEnum):
@@ -551,9 +586,10 @@ class AttentionDecodeFP8(AttentionDecode):
         return quant, keep
 
     def workspaceSize(self, **shape) -> int:
-        if shape.get("window") is not None:
+        if _extended(shape):
             return super().workspaceSize(**shape)
-        shape.pop("window", None)
+        for name in ("window", "sinkTokens", "sinkLogits"):
+            shape.pop(name, None)
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape)
         out = ctypes.c_uint64(0)
@@ -561,9 +597,10 @@ class AttentionDecodeFP8(AttentionDecode):
         return int(out.value)
 
     def launchForm(self, **shape) -> str:
-        if shape.get("window") is not None:
+        if _extended(shape):
             return super().launchForm(**shape)
-        shape.pop("window", None)
+        for name in ("window", "sinkTokens", "sinkLogits"):
+            shape.pop(name, None)
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape)
         out = ctypes.create_string_buffer(512)
@@ -571,18 +608,20 @@ class AttentionDecodeFP8(AttentionDecode):
         return out.value.decode()
 
     def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
-        if shape.get("window") is not None:
+        if _extended(shape):
             return super().dispatch(q, k, v, o, l, stream=stream, **shape)
-        shape.pop("window", None)
+        for name in ("window", "sinkTokens", "sinkLogits"):
+            shape.pop(name, None)
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape)
         check(lib().mfa_attention_decode_fp8_launch(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
                                                     ctypes.byref(quant), ctypes.c_void_p(stream or 0)))
 
     def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
-        if shape.get("window") is not None:
+        if _extended(shape):
             return super().time(q, k, v, o, l, stream=stream, warmup=warmup, iterations=iterations, **shape)
-        shape.pop("window", None)
+        for name in ("window", "sinkTokens", "sinkLogits"):
+            shape.pop(name, None)
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape)
         ms = ctypes.c_float(0.0)
@@ -605,7 +644,8 @@ class AttentionPrefill:
     KVCachePrecision.E4M3 reads an e4m3 cache (the quantisation block is part of mfa_prefill_params, so one class serves both): the
     K / V strides then count bytes, and keyScale / valueScale (device FP32 [heads // headsPerKeyValue], None = 1.0) go with the shape
     arguments.  The launch takes no workspace.  window=W (launchForm, dispatch, time): sliding-window attention,
-    include/mfa_window.h; None: the plain launch; 0 goes through the window entries and is the plain launch."""
+    include/mfa_window.h; None: the plain launch; 0 goes through the window entries and is the plain launch.  sinkTokens=S,
+    sinkLogits=device FP32 [heads] (the same three): attention sinks as AttentionDecode's, include/mfa_sink.h."""
 
     OPERANDS = ("Q", "K", "V", "O")
 
@@ -645,32 +685,39 @@ class AttentionPrefill:
 
     def launchForm(self, **shape) -> str:
         """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name and the grid."""
-        window = shape.pop("window", None)
+        window, sinks = shape.pop("window", None), _sinks_block(shape)
         p, _keep = self._params(**shape)
         out = ctypes.create_string_buffer(512)
-        if window is not None:
+        if sinks is not None:
+            check(lib().mfa_attention_prefill_sink_launch_form(ctypes.byref(p), int(window or 0), ctypes.byref(sinks[0]), out, len(out)))
+        elif window is not None:
             check(lib().mfa_attention_prefill_window_launch_form(ctypes.byref(p), int(window), out, len(out)))
         else:
             check(lib().mfa_attention_prefill_launch_form(ctypes.byref(p), out, len(out)))
         return out.value.decode()
 
     def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
-        window = shape.pop("window", None)
+        window, sinks = shape.pop("window", None), _sinks_block(shape)
         p, _keep = self._params(**shape)
         bufs = (_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l))
-        if window is not None:
+        if sinks is not None:
+            check(lib().mfa_attention_prefill_sink_launch(*bufs, ctypes.byref(p), int(window or 0), ctypes.byref(sinks[0]),
+                                                          ctypes.c_void_p(stream or 0)))
+        elif window is not None:
             check(lib().mfa_attention_prefill_window_launch(*bufs, ctypes.byref(p), int(window), ctypes.c_void_p(stream or 0)))
         else:
             check(lib().mfa_attention_prefill_launch(*bufs, ctypes.byref(p), ctypes.c_void_p(stream or 0)))
 
     def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
         """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
-        window = shape.pop("window", None)
+        window, sinks = shape.pop("window", None), _sinks_block(shape)
         p, _keep = self._params(**shape)
         ms = ctypes.c_float(0.0)
         bufs = (_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l))
         timing = (ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms))
-        if window is not None:
+        if sinks is not None:
+            check(lib().mfa_attention_prefill_sink_time(*bufs, ctypes.byref(p), int(window or 0), ctypes.byref(sinks[0]), *timing))
+        elif window is not None:
             check(lib().mfa_attention_prefill_window_time(*bufs, ctypes.byref(p), int(window), *timing))
         else:
             check(lib().mfa_attention_prefill_time(*bufs, ctypes.byref(p), *timing))
@@ -692,6 +739,17 @@ class AttentionPrefill:
         out = [ctypes.c_uint32(0) for _ in range(4)]
         check(lib().mfa_attention_prefill_window_tile_range(int(length), int(queryLength), int(firstRow), int(blockRows), int(window),
                                                             *(ctypes.byref(x) for x in out)))
+        return tuple(int(x.value) for x in out)
+
+    @staticmethod
+    def sinkTileRange(length: int, queryLength: int, firstRow: int, blockRows: int, window: int, sinkTokens: int,
+                      causal: bool = True) -> Tuple[int, int, int, int, int]:
+        """(begin, unmaskedBegin, unmaskedEnd, end, sinkEnd) of the block of rows [firstRow, firstRow + blockRows) under a window of
+        `window` keys (0: none) with `sinkTokens` sink keys, in 64-key tiles (include/mfa_sink.h): the tiles [0, sinkEnd) are walked
+        first, then [begin, end).  The kernels' own function, on the host"""
+        out = [ctypes.c_uint32(0) for _ in range(5)]
+        check(lib().mfa_attention_prefill_sink_tile_range(int(length), int(queryLength), int(firstRow), int(blockRows), int(bool(causal)),
+                                                          int(window), int(sinkTokens), *(ctypes.byref(x) for x in out)))
         return tuple(int(x.value) for x in out)
 
 

@@ -40,6 +40,18 @@
 //   * the mask is one unsigned comparison c - lo < lim - lo in both places; a masked score is still replaced, never multiplied.
 //   * pieces may be empty: they publish m = -FLT_MAX, l = 0 and zeros, which the combine kernel already weighs with 0.
 // With W >= column + rows every lo is 0 and the ranges are decode_piece_range's: the plain kernel's arithmetic in the plain order.
+//
+// SINK: the WINDOW body with attention sinks (include/mfa_sink.h); a.window = 0 is "lo = 0 everywhere".
+//   * sink TOKENS, a.sinkTokens = S: row r also sees the keys c < slim = min(S, lim).  The workgroup walks a piece of the tile LIST
+//     [0, sinkTiles) ++ [first, last) (decode_sink_piece_range): at most two key ranges.  The loop runs over the list's own key
+//     positions -- `key0` counts keys of the piece, sink range first -- and list_key() turns a position into the cache's key where
+//     one is addressed or masked; nothing between the two ranges is loaded, no key, no page, no block-table entry.
+//     The mask is (c - lo < span) || (c < slim) per lane.
+//   * sink LOGIT, a.sinkLogits[query head] (natural units; null: none): one more term of the denominator, s2 = sink log2(e),
+//     never scaled by 1 / sqrt(D) or keyScale.  The unsplit kernel adds it at the final normalisation; in the split kernels piece 0
+//     folds it into the (m, l) it publishes -- an empty piece 0 publishes m = s2, l = 1, O = 0 -- so the combine kernel is reused as
+//     it stands.  A row without a visible key: O = 0, L = s2.
+// With S = 0 and no logits the SINK kernels run the WINDOW kernels' arithmetic in their order.
 #pragma once
 #include "attn_fwd16_common.h"
 #include "kv_e4m3.h"
@@ -71,6 +83,8 @@ struct DecodeArgs {
   float *wsO, *wsML;
   const float *keyScale, *valueScale;   // e4m3 caches, per K / V head; null: 1.0
   uint32_t window;                      // the WINDOW kernels only (>= 1); last, so that no other field moves
+  uint32_t sinkTokens;                  // the SINK kernels only, which also take window = 0 (no window); behind `window` in turn
+  const float *sinkLogits;              // [Hq], natural units; null: none
 };
 
 // keys [*begin, *end) of piece `piece` of `pieces` for a sequence of `length` keys: an equal share of the sequence's whole 64-key
@@ -103,14 +117,40 @@ __host__ __device__ __forceinline__ void decode_window_piece_range(uint32_t leng
   *end = (uint32_t)e;
 }
 
+// The two key ranges of piece `piece` of `pieces` with `sinkTokens` sink keys under a window of `window` keys (0: no window, lo0 = 0):
+// with first, last as above and sinkTiles = min(ceil(min(S, length) / 64), first), an equal share, in whole tiles, of the LIST
+// [0, sinkTiles) ++ [first, last): [begin[0], end[0]) inside the sink tiles, [begin[1], end[1]) inside the window's; both clamped as
+// above.  Device and host (mfa_attention_decode_sink_piece_range) run this one body.
+__host__ __device__ __forceinline__ void decode_sink_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t sinkTokens,
+                                                                 uint32_t pieces, uint32_t piece, uint32_t *begin, uint32_t *end) {
+  const uint64_t f1 = (length > rows ? (uint64_t)length - rows : 0) + 1;   // row 0's frontier + 1
+  const uint64_t lo0 = window ? (f1 > window ? f1 : (uint64_t)window) - window : 0;
+  const uint64_t first = lo0 / DEC_KEY_TILE, last = ((uint64_t)length + DEC_KEY_TILE - 1) / DEC_KEY_TILE;
+  const uint64_t sunk = sinkTokens < length ? sinkTokens : length;
+  uint64_t sinkTiles = (sunk + DEC_KEY_TILE - 1) / DEC_KEY_TILE;
+  if (sinkTiles > first) sinkTiles = first;
+  const uint64_t tiles = sinkTiles + (last > first ? last - first : 0);
+  const uint64_t t0 = (uint64_t)piece * tiles / pieces, t1 = ((uint64_t)piece + 1) * tiles / pieces;   // positions in the list
+  const uint64_t tb[2] = {t0 < sinkTiles ? t0 : sinkTiles, first + (t0 > sinkTiles ? t0 - sinkTiles : 0)};
+  const uint64_t te[2] = {t1 < sinkTiles ? t1 : sinkTiles, first + (t1 > sinkTiles ? t1 - sinkTiles : 0)};
+  for (int i = 0; i < 2; ++i) {
+    uint64_t b = tb[i] * DEC_KEY_TILE, e = te[i] * DEC_KEY_TILE;
+    if (e > length) e = length;
+    if (b > e) b = e;
+    begin[i] = (uint32_t)b;
+    end[i] = (uint32_t)e;
+  }
+}
+
 template <int D> constexpr int decode16_lds_bytes() {
   constexpr int images = DEC_WAVES * DEC_STEP * D * 2;
   constexpr int merge = DEC_WAVES * 32 * (D + 4) * 4 + 2 * DEC_WAVES * 32 * 4;
   return images > merge ? images : merge;
 }
 
-template <typename T, int D, bool SPLIT, bool FP8, bool WINDOW = false>
+template <typename T, int D, bool SPLIT, bool FP8, bool WINDOW = false, bool SINK = false>
 __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
+  static_assert(!SINK || WINDOW, "the sink kernels are the window kernels plus SINK");
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -132,8 +172,18 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
   const uint32_t R = a.R, M = a.G * R;
   const uint32_t len = min(a.lengths[batch], a.column);
   uint32_t begin = 0, end = len;
-  if constexpr (WINDOW) decode_window_piece_range(len, R, a.window, SPLIT ? a.pieces : 1u, piece, &begin, &end);
+  // SINK: [begin, end) are positions in the piece's own key list -- `sunk` keys of the sink range from key sinkBegin, then the
+  // window range from key windowBegin -- and list_key() is the cache's key at a position
+  uint32_t sunk = 0, sinkBegin = 0, windowBegin = 0;
+  if constexpr (SINK) {
+    uint32_t rb[2], re[2];
+    decode_sink_piece_range(len, R, a.window, a.sinkTokens, SPLIT ? a.pieces : 1u, piece, rb, re);
+    sunk = re[0] - rb[0]; sinkBegin = rb[0]; windowBegin = rb[1];
+    end = sunk + (re[1] - rb[1]);
+  } else if constexpr (WINDOW) decode_window_piece_range(len, R, a.window, SPLIT ? a.pieces : 1u, piece, &begin, &end);
   else if constexpr (SPLIT) decode_piece_range(len, a.pieces, piece, &begin, &end);
+  auto list_key = [&](uint32_t at) { return SINK ? (at < sunk ? sinkBegin + at : windowBegin + (at - sunk)) : at; };
+  const uint32_t tableEnd = SINK ? len : end;   // block-table entries are read for keys below it
   float kscale = a.scale2, vscale = 1.0f;   // (16-bit: scale2 as it stands, and vscale is never used)
   if constexpr (FP8) {
     kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
@@ -154,15 +204,17 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     }
   }
   // keys this row sees: c < lim  (causal: c <= row + max(len - R, 0); always c < len, and inside this piece c < end)
-  uint32_t lim = end;
+  uint32_t lim = SINK ? len : end;
   if (a.causal) lim = min(lim, qrow + (len > R ? len - R : 0u) + 1u);
   // WINDOW: and c >= lo = max(f + 1, W) - W; `span` = lim - lo keys from lo on (none: 0), so that visible is c - lo < span, unsigned
   uint32_t lo = 0, span = 0;
   if constexpr (WINDOW) {
     const uint32_t f1 = qrow + (len > R ? len - R : 0u) + 1u;
     lo = max(f1, a.window) - a.window;
+    if constexpr (SINK) lo = a.window ? lo : 0u;
     span = lim > lo ? lim - lo : 0u;
   }
+  const uint32_t slim = SINK ? min(a.sinkTokens, lim) : 0u;   // SINK: and the keys c < slim
 
   // ---- addresses of a step's two 16-key groups (wave-uniform; element offsets from a.k / a.v, which are byte offsets under FP8)
   const int64_t khead = (int64_t)kvh * a.hsk, vhead = (int64_t)kvh * a.hsv;
@@ -173,7 +225,7 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
       const uint32_t key = key0 + 16u * u;
       if (a.paged) {
         // (entries past the sequence's last page are never read)
-        const int64_t page = key < end ? (int64_t)a.table[(int64_t)batch * a.tableStride + (key >> a.pageShift)] : 0;
+        const int64_t page = key < tableEnd ? (int64_t)a.table[(int64_t)batch * a.tableStride + (key >> a.pageShift)] : 0;
         const int64_t in = (int64_t)(key & pageMask);
         ko[u] = page * a.psk + khead + in * a.ldk;
         vo[u] = page * a.psv + vhead + in * a.ldv;
@@ -190,7 +242,7 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
   const int vrow0 = lane / CPR, vc = lane % CPR;
   auto issue_loads = [&](uint32_t key0) {
     int64_t ko[2], vo[2];
-    group_offsets(key0, ko, vo);
+    group_offsets(list_key(key0), ko, vo);
     const bool kvalid = key0 + (uint32_t)q < end;
     const char *kp;
     if constexpr (FP8) kp = a.k + (q >> 4 ? ko[1] : ko[0]) + (int64_t)(q & 15) * a.ldk + 16 * hi;
@@ -256,7 +308,7 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
       }
     }
     // ---- the registers are free: the next step's loads fly during the rest of this one
-    const uint32_t cur = key0;
+    const uint32_t cur = list_key(key0);
     key0 += DEC_WAVES * DEC_STEP;
     if (key0 < end) issue_loads(key0);
 
@@ -264,7 +316,9 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     float mx = DEC_MINUS_HUGE;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const bool visible = WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span : cur + (uint32_t)crow(r, hi) < lim;
+      const bool visible = SINK     ? (cur + (uint32_t)crow(r, hi) - lo < span) | (cur + (uint32_t)crow(r, hi) < slim)
+                           : WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span
+                                    : cur + (uint32_t)crow(r, hi) < lim;
       s[r] = visible ? s[r] * kscale : DEC_MINUS_HUGE;
       mx = fmaxf(mx, s[r]);
     }
@@ -282,7 +336,9 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     v8 pf[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const bool visible = WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span : cur + (uint32_t)crow(r, hi) < lim;
+      const bool visible = SINK     ? (cur + (uint32_t)crow(r, hi) - lo < span) | (cur + (uint32_t)crow(r, hi) < slim)
+                           : WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span
+                                    : cur + (uint32_t)crow(r, hi) < lim;
       const float p = visible ? fast_exp2(s[r] - m) : 0.f;   // replaced, never multiplied
       psum += p;
       pf[r >> 3][r & 7] = (T)p;
@@ -341,13 +397,26 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
       mrow = fmaxf(mrow, ms[w * 32 + p]);
     }
     const uint32_t head = kvh * a.G + p / R, row = p % R;
+    // SINK: the sink logit joins (m, l) -- piece 0's when the keys are split, the workgroup's otherwise; `fold` rescales O with l
+    float fold = 1.0f;
+    if constexpr (SINK) {
+      if (a.sinkLogits && piece == 0) {
+        float s2 = a.sinkLogits[head] * 1.44269504089f;
+        asm volatile("" : "+v"(s2));   // (s2 is the ROUNDED product in m and in both exponents: never fused into the subtractions below)
+        const float mnew = fmaxf(mrow, s2);
+        fold = fast_exp2(mrow - mnew);
+        lsum = lsum * fold + fast_exp2(s2 - mnew);
+        mrow = mnew;
+      }
+    }
     if constexpr (SPLIT) {
       const size_t slab = (((size_t)piece * a.batches + batch) * a.Hq + head) * R + row;
       if constexpr (FP8) { acc.x *= vscale; acc.y *= vscale; acc.z *= vscale; acc.w *= vscale; }
+      if constexpr (SINK) { acc.x *= fold; acc.y *= fold; acc.z *= fold; acc.w *= fold; }
       *reinterpret_cast<float4 *>(a.wsO + slab * D + 4 * c) = acc;
       if (c == 0) *reinterpret_cast<float2 *>(a.wsML + slab * 2) = make_float2(mrow, lsum);
     } else {
-      const float inv = lsum > 0.f ? (FP8 ? vscale : 1.0f) / lsum : 0.f;   // a sequence of length 0: O = 0
+      const float inv = lsum > 0.f ? (FP8 ? vscale : 1.0f) * fold / lsum : 0.f;   // a sequence of length 0: O = 0
       acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
       const int64_t at = (int64_t)batch * a.bso + (int64_t)head * a.hso + (int64_t)row * a.ldo + 4 * c;
       if (a.outF32) *reinterpret_cast<float4 *>(a.o + at * 4) = acc;

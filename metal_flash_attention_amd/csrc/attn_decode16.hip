@@ -1,18 +1,21 @@
 // attn_decode16.hip -- decode attention over a KV cache, 16-bit or FP8 (e4m3): the kernels' code objects, the C ABI of
 // include/mfa_decode.h, the decode entries of include/mfa_kvcache.h and those of include/mfa_window.h (a sliding window: the same
-// plan with the piece count taken from the tiles a window can span, and the attn_decode16w_* / attn_decode8w_* kernels).  One plan serves both: the launch over an e4m3 cache adds its
+// plan with the piece count taken from the tiles a window can span, and the attn_decode16w_* / attn_decode8w_* kernels) and those of
+// include/mfa_sink.h (attention sinks: the window's plan plus the sink tiles, and the attn_decode16s_* / attn_decode8s_* kernels).  One plan serves both: the launch over an e4m3 cache adds its
 // own checks in front of the 16-bit launch's, starts the attn_decode8_* kernels in place of _single / _pieces, and shares the piece
 // count, the workspace formula and the combine kernel.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <string>
 
 #include "../../include/mfa_decode.h"
 #include "../../include/mfa_kvcache.h"
+#include "../../include/mfa_sink.h"
 #include "../../include/mfa_window.h"
 #include "attn_decode16.h"
 #include "cache_launch.h"
@@ -23,7 +26,7 @@ using namespace mfa;
 
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_decode16_d<D>_<type>_{single,pieces,combine} and, over
 // an e4m3 cache, attn_decode8_d<D>_<type of Q>_{single,pieces}, whose pieces attn_decode16_d<D>_<type>_combine merges; under a
-// sliding window attn_decode16w_* / attn_decode8w_*, merged by the same combine kernel
+// sliding window attn_decode16w_* / attn_decode8w_*, with attention sinks attn_decode16s_* / attn_decode8s_*, merged by the same combine kernel
 #define MFA_DECODE_KERNELS(TN, T, D)                                                                                                  \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16_d##D##_##TN##_single(const DecodeArgs a) {                       \
     decode_body<T, D, false, false>(a);                                                                                               \
@@ -49,6 +52,18 @@ using namespace mfa;
   extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8w_d##D##_##TN##_pieces(const DecodeArgs a) {                       \
     decode_body<T, D, true, true, true>(a);                                                                                           \
   }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16s_d##D##_##TN##_single(const DecodeArgs a) {                      \
+    decode_body<T, D, false, false, true, true>(a);                                                                                   \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16s_d##D##_##TN##_pieces(const DecodeArgs a) {                      \
+    decode_body<T, D, true, false, true, true>(a);                                                                                    \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8s_d##D##_##TN##_single(const DecodeArgs a) {                       \
+    decode_body<T, D, false, true, true, true>(a);                                                                                    \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8s_d##D##_##TN##_pieces(const DecodeArgs a) {                       \
+    decode_body<T, D, true, true, true, true>(a);                                                                                     \
+  }                                                                                                                                   \
   extern "C" __global__ __launch_bounds__(256) void attn_decode16_d##D##_##TN##_combine(const DecodeArgs a) {                         \
     decode16_combine_body<T, D>(a);                                                                                                   \
   }
@@ -64,20 +79,24 @@ struct DecodeSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  DecodeKernel single[2][2], pieces[2][2], combine;   // [window][fp8]
-  const char *singleName[2][2], *piecesName[2][2], *combineName;
+  DecodeKernel single[3][2], pieces[3][2], combine;   // [0: plain, 1: window, 2: sinks][fp8]
+  const char *singleName[3][2], *piecesName[3][2], *combineName;
 };
 #define MFA_DECODE_SET(TN, PREC, D)                                                                                                   \
   {D, PREC, (uint32_t)decode16_lds_bytes<D>(),                                                                                        \
    {{attn_decode16_d##D##_##TN##_single, attn_decode8_d##D##_##TN##_single},                                                          \
-    {attn_decode16w_d##D##_##TN##_single, attn_decode8w_d##D##_##TN##_single}},                                                       \
+    {attn_decode16w_d##D##_##TN##_single, attn_decode8w_d##D##_##TN##_single},                                                        \
+    {attn_decode16s_d##D##_##TN##_single, attn_decode8s_d##D##_##TN##_single}},                                                       \
    {{attn_decode16_d##D##_##TN##_pieces, attn_decode8_d##D##_##TN##_pieces},                                                          \
-    {attn_decode16w_d##D##_##TN##_pieces, attn_decode8w_d##D##_##TN##_pieces}},                                                       \
+    {attn_decode16w_d##D##_##TN##_pieces, attn_decode8w_d##D##_##TN##_pieces},                                                        \
+    {attn_decode16s_d##D##_##TN##_pieces, attn_decode8s_d##D##_##TN##_pieces}},                                                       \
    attn_decode16_d##D##_##TN##_combine,                                                                                               \
    {{"attn_decode16_d" #D "_" #TN "_single", "attn_decode8_d" #D "_" #TN "_single"},                                                  \
-    {"attn_decode16w_d" #D "_" #TN "_single", "attn_decode8w_d" #D "_" #TN "_single"}},                                               \
+    {"attn_decode16w_d" #D "_" #TN "_single", "attn_decode8w_d" #D "_" #TN "_single"},                                                \
+    {"attn_decode16s_d" #D "_" #TN "_single", "attn_decode8s_d" #D "_" #TN "_single"}},                                               \
    {{"attn_decode16_d" #D "_" #TN "_pieces", "attn_decode8_d" #D "_" #TN "_pieces"},                                                  \
-    {"attn_decode16w_d" #D "_" #TN "_pieces", "attn_decode8w_d" #D "_" #TN "_pieces"}},                                               \
+    {"attn_decode16w_d" #D "_" #TN "_pieces", "attn_decode8w_d" #D "_" #TN "_pieces"},                                                \
+    {"attn_decode16s_d" #D "_" #TN "_pieces", "attn_decode8s_d" #D "_" #TN "_pieces"}},                                               \
    "attn_decode16_d" #D "_" #TN "_combine"}
 const DecodeSet kSets[] = {MFA_DECODE_SET(bf16, MFA_BF16, 64), MFA_DECODE_SET(bf16, MFA_BF16, 128), MFA_DECODE_SET(f16, MFA_FP16, 64),
                            MFA_DECODE_SET(f16, MFA_FP16, 128)};
@@ -86,13 +105,21 @@ const DecodeSet kSets[] = {MFA_DECODE_SET(bf16, MFA_BF16, 64), MFA_DECODE_SET(bf
 // live on the device.  Aims at MFA_DECODE_WORKGROUP_TARGET workgroups (two per compute unit of a 256-CU chip, what choose_splits of
 // mfa_kernel.hip aims at), rounded down; a piece keeps at least four 64-key tiles (two steps for each of the workgroup's four waves).
 // Under a window of W keys a sequence walks the tiles of W + rows - 1 keys that need not start on a tile: at most
-// ceil((W + rows - 1) / 64) + 1, and never more than column's.
-uint64_t planned_tiles(uint32_t column, uint32_t rows, uint32_t window) {
+// ceil((W + rows - 1) / 64) + 1, and never more than column's.  S sink tokens add at most their ceil(S / 64) tiles to the window's.
+uint64_t planned_tiles(uint32_t column, uint32_t rows, uint32_t window, uint32_t sinkTokens) {
   const uint64_t tiles = ((uint64_t)column + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE;
   if (!window) return tiles;
-  const uint64_t spanned = ((uint64_t)window + rows - 1 + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE + 1;
+  const uint64_t spanned = ((uint64_t)window + rows - 1 + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE + 1 +
+                           ((uint64_t)sinkTokens + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE;
   return spanned < tiles ? spanned : tiles;
 }
+
+// the sinks of a launch: none for the entries of the other headers
+struct Sinks {
+  uint32_t tokens = 0;
+  const float *logits = nullptr;
+  bool any() const { return tokens != 0 || logits != nullptr; }
+};
 
 uint32_t choose_pieces(uint64_t blocks, uint64_t tiles) {
   if (blocks >= MFA_DECODE_WORKGROUP_TARGET) return 1;
@@ -111,18 +138,27 @@ struct DecodePlan {
   const DecodeSet *set;
   bool fp8;
   uint32_t window;      // 0: none
+  Sinks sinks;
+  int family;           // 0: plain, 1: window, 2: sinks -- the kernels' first index
   uint64_t tiles;       // what the piece count was chosen from
   uint32_t pieces;      // as the launch runs: 1 without a workspace
   uint32_t planned;     // what the host would cut the keys into
   uint32_t blocks;      // batches x K/V heads
   // the kernel that reads the cache, and the name a HIP failure is reported under
-  const char *name() const { return pieces > 1 ? set->piecesName[window != 0][fp8] : set->singleName[window != 0][fp8]; }
+  const char *name() const { return pieces > 1 ? set->piecesName[family][fp8] : set->singleName[family][fp8]; }
 };
 
 // every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `quant` is null for a
-// 16-bit cache; an e4m3 cache puts its own checks first, then the 16-bit launch's.  `window` 0: none
-mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32_t window, DecodePlan *plan) {
+// 16-bit cache; an e4m3 cache puts its own checks first, then the 16-bit launch's.  `window` 0: none; `sinks`: include/mfa_sink.h
+mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, DecodePlan *plan) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (sinks.tokens && !window)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens = " + std::to_string(sinks.tokens) +
+                                              " keeps the first keys visible under a sliding window, and window is 0 (every key below "
+                                              "the frontier is visible already)");
+  if (sinks.tokens && !p->causal)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need causal: sinkTokens = " + std::to_string(sinks.tokens) +
+                                              " extends a sliding window, which ends at a row's causal frontier");
   if (window && !p->causal)
     return fail(MFA_ERR_INVALID_ARGUMENT, "a sliding window needs causal: the window is the " + std::to_string(window) +
                                               " keys that end at a row's causal frontier (window 0: no window)");
@@ -176,7 +212,9 @@ mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32
   plan->fp8 = quant != nullptr;
   plan->blocks = p->batches * (p->heads / G);
   plan->window = window;
-  plan->tiles = planned_tiles(p->column, p->rows, window);
+  plan->sinks = sinks;
+  plan->family = sinks.any() ? 2 : window != 0;
+  plan->tiles = planned_tiles(p->column, p->rows, window, sinks.tokens);
   plan->planned = choose_pieces(plan->blocks, plan->tiles);
   plan->pieces = plan->planned;
   if (!p->workspace) plan->pieces = 1;   // no workspace: one kernel, unsplit
@@ -208,6 +246,8 @@ mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32
   }
   if (quant) { a.keyScale = quant->keyScale; a.valueScale = quant->valueScale; }
   a.window = window;
+  a.sinkTokens = sinks.tokens;
+  a.sinkLogits = sinks.logits;
   return MFA_OK;
 }
 
@@ -215,6 +255,7 @@ mfa_status bind(DecodePlan *plan, const void *q, const void *k, const void *v, v
   mfa_status st = check_buffers({q, k, v, o}, "Q, K, V and O");
   if (st == MFA_OK) st = check_float_arrays({l}, "L");
   if (st == MFA_OK) st = check_float_arrays({plan->args.keyScale, plan->args.valueScale}, "keyScale and valueScale");
+  if (st == MFA_OK) st = check_float_arrays({plan->args.sinkLogits}, "sinkLogits");
   if (st != MFA_OK) return st;
   plan->args.q = (const char *)q; plan->args.k = (const char *)k; plan->args.v = (const char *)v;
   plan->args.o = (char *)o; plan->args.l = l;
@@ -225,19 +266,19 @@ hipError_t run(const DecodePlan &plan, hipStream_t stream) {
   const DecodeSet &s = *plan.set;
   hipError_t err;
   if (plan.pieces > 1) {
-    err = launch_kernel(s.pieces[plan.window != 0][plan.fp8], dim3(plan.blocks * plan.pieces), dim3(256), s.lds, stream, plan.args);
+    err = launch_kernel(s.pieces[plan.family][plan.fp8], dim3(plan.blocks * plan.pieces), dim3(256), s.lds, stream, plan.args);
     if (err != hipSuccess) return err;
     const uint64_t rows = (uint64_t)plan.args.batches * plan.args.Hq * plan.args.R;
     err = launch_kernel(s.combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, plan.args);
   } else {
-    err = launch_kernel(s.single[plan.window != 0][plan.fp8], dim3(plan.blocks), dim3(256), s.lds, stream, plan.args);
+    err = launch_kernel(s.single[plan.family][plan.fp8], dim3(plan.blocks), dim3(256), s.lds, stream, plan.args);
   }
   if (err != hipSuccess) return err;
   return hipGetLastError();
 }
 
 // the bytes of the workspace the launch would split into: 0 for an unsplit plan, whatever workspace the caller may already have bound
-mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, uint64_t *bytes) {
+mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, uint64_t *bytes) {
   if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   *bytes = 0;
   if (!params) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
@@ -245,16 +286,16 @@ mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_q
   probe.workspace = nullptr;
   probe.workspaceBytes = 0;
   DecodePlan plan;
-  const mfa_status st = prepare(&probe, quant, window, &plan);
+  const mfa_status st = prepare(&probe, quant, window, sinks, &plan);
   if (st != MFA_OK) return st;
   if (plan.planned > 1) *bytes = pieces_workspace_bytes(plan.planned, params);
   return MFA_OK;
 }
 
 mfa_status decode_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params, const mfa_kv_quant *quant,
-                         uint32_t window, void *stream) {
+                         uint32_t window, const Sinks &sinks, void *stream) {
   DecodePlan plan;
-  mfa_status st = prepare(params, quant, window, &plan);
+  mfa_status st = prepare(params, quant, window, sinks, &plan);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -263,17 +304,21 @@ mfa_status decode_launch(const void *q, const void *k, const void *v, void *o, f
   return MFA_OK;
 }
 
-mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, char *out, size_t capacity) {
+mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, char *out,
+                              size_t capacity) {
   if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   out[0] = '\0';
   DecodePlan plan;
-  const mfa_status st = prepare(params, quant, window, &plan);
+  const mfa_status st = prepare(params, quant, window, sinks, &plan);
   if (st != MFA_OK) return st;
   char text[512];
   const uint32_t M = plan.args.G * plan.args.R;
-  // (a windowed launch names its window and the tiles the piece count was chosen from)
+  // (a windowed launch names its window, its sink tokens and the tiles the piece count was chosen from; bound sink logits last)
   const std::string layout = std::string(plan.args.paged ? "paged" : "contiguous") +
-                             (window ? ", window " + std::to_string(window) + ": planned from " + std::to_string(plan.tiles) + " tiles" : "");
+                             (window ? ", window " + std::to_string(window) + (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : "") +
+                                           ": planned from " + std::to_string(plan.tiles) + " tiles"
+                                     : "") +
+                             (sinks.logits ? ", sink logits" : "");
   if (plan.pieces > 1)
     std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x K/V heads x %u pieces, %u packed rows, %s) + %s (grid %llu)", plan.name(),
                   plan.blocks * plan.pieces, plan.blocks, plan.pieces, M, layout.c_str(), plan.set->combineName,
@@ -286,10 +331,10 @@ mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quan
 }
 
 mfa_status decode_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params, const mfa_kv_quant *quant,
-                       uint32_t window, void *stream, int warmup, int iterations, float *milliseconds) {
+                       uint32_t window, const Sinks &sinks, void *stream, int warmup, int iterations, float *milliseconds) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   DecodePlan plan;
-  mfa_status st = prepare(params, quant, window, &plan);
+  mfa_status st = prepare(params, quant, window, sinks, &plan);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -315,20 +360,20 @@ mfa_status mfa_attention_decode_piece_range(uint32_t length, uint32_t pieces, ui
   return MFA_OK;
 }
 
-mfa_status mfa_attention_decode_workspace_size(const mfa_decode_params *params, uint64_t *bytes) { return decode_workspace_size(params, nullptr, 0, bytes); }
+mfa_status mfa_attention_decode_workspace_size(const mfa_decode_params *params, uint64_t *bytes) { return decode_workspace_size(params, nullptr, 0, Sinks(), bytes); }
 
 mfa_status mfa_attention_decode_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                        void *stream) {
-  return decode_launch(q, k, v, o, l, params, nullptr, 0, stream);
+  return decode_launch(q, k, v, o, l, params, nullptr, 0, Sinks(), stream);
 }
 
 mfa_status mfa_attention_decode_launch_form(const mfa_decode_params *params, char *out, size_t capacity) {
-  return decode_launch_form(params, nullptr, 0, out, capacity);
+  return decode_launch_form(params, nullptr, 0, Sinks(), out, capacity);
 }
 
 mfa_status mfa_attention_decode_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                      void *stream, int warmup, int iterations, float *milliseconds) {
-  return decode_time(q, k, v, o, l, params, nullptr, 0, stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, nullptr, 0, Sinks(), stream, warmup, iterations, milliseconds);
 }
 
 // ---- over an e4m3 cache (include/mfa_kvcache.h): the same four with the cache's mfa_kv_quant, which is required
@@ -343,27 +388,27 @@ mfa_status mfa_attention_decode_fp8_workspace_size(const mfa_decode_params *para
   if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   *bytes = 0;
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_workspace_size(params, quant, 0, bytes);
+  return decode_workspace_size(params, quant, 0, Sinks(), bytes);
 }
 
 mfa_status mfa_attention_decode_fp8_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                            const mfa_kv_quant *quant, void *stream) {
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_launch(q, k, v, o, l, params, quant, 0, stream);
+  return decode_launch(q, k, v, o, l, params, quant, 0, Sinks(), stream);
 }
 
 mfa_status mfa_attention_decode_fp8_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, char *out, size_t capacity) {
   if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   out[0] = '\0';
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_launch_form(params, quant, 0, out, capacity);
+  return decode_launch_form(params, quant, 0, Sinks(), out, capacity);
 }
 
 mfa_status mfa_attention_decode_fp8_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                          const mfa_kv_quant *quant, void *stream, int warmup, int iterations, float *milliseconds) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_time(q, k, v, o, l, params, quant, 0, stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, quant, 0, Sinks(), stream, warmup, iterations, milliseconds);
 }
 
 // ---- under a sliding window (include/mfa_window.h): the same four with `window` after `quant`, which is null for a 16-bit cache.
@@ -371,23 +416,23 @@ mfa_status mfa_attention_decode_fp8_time(const void *q, const void *k, const voi
 
 mfa_status mfa_attention_decode_window_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
                                                       uint64_t *bytes) {
-  return decode_workspace_size(params, quant, window, bytes);
+  return decode_workspace_size(params, quant, window, Sinks(), bytes);
 }
 
 mfa_status mfa_attention_decode_window_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                               const mfa_kv_quant *quant, uint32_t window, void *stream) {
-  return decode_launch(q, k, v, o, l, params, quant, window, stream);
+  return decode_launch(q, k, v, o, l, params, quant, window, Sinks(), stream);
 }
 
 mfa_status mfa_attention_decode_window_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, char *out,
                                                    size_t capacity) {
-  return decode_launch_form(params, quant, window, out, capacity);
+  return decode_launch_form(params, quant, window, Sinks(), out, capacity);
 }
 
 mfa_status mfa_attention_decode_window_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                             const mfa_kv_quant *quant, uint32_t window, void *stream, int warmup, int iterations,
                                             float *milliseconds) {
-  return decode_time(q, k, v, o, l, params, quant, window, stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, quant, window, Sinks(), stream, warmup, iterations, milliseconds);
 }
 
 mfa_status mfa_attention_decode_window_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t pieces, uint32_t piece,
@@ -397,6 +442,75 @@ mfa_status mfa_attention_decode_window_piece_range(uint32_t length, uint32_t row
   if (window == 0 || rows == 0)
     return fail(MFA_ERR_INVALID_ARGUMENT, "window and rows must be non-zero (no window: mfa_attention_decode_piece_range)");
   decode_window_piece_range(length, rows, window, pieces, piece, begin, end);
+  return MFA_OK;
+}
+
+// ---- with attention sinks (include/mfa_sink.h): the window entries with `sinks` after `window`.  The block is required; an all-zero
+// one is the window launch, whichever window
+
+void mfa_attention_sinks_init(mfa_attention_sinks *sinks) {
+  if (sinks) std::memset(sinks, 0, sizeof(*sinks));
+}
+
+size_t mfa_attention_sinks_size(void) { return sizeof(mfa_attention_sinks); }
+
+mfa_status mfa_attention_sinks_offsets(uint32_t *offsets, uint32_t capacity, uint32_t *count) {
+  if (!offsets || !count) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  static const uint32_t table[] = {(uint32_t)offsetof(mfa_attention_sinks, sinkTokens), (uint32_t)offsetof(mfa_attention_sinks, reserved),
+                                   (uint32_t)offsetof(mfa_attention_sinks, sinkLogits)};
+  const uint32_t total = (uint32_t)(sizeof(table) / sizeof(table[0]));
+  *count = total;
+  for (uint32_t i = 0; i < total && i < capacity; ++i) offsets[i] = table[i];
+  return MFA_OK;
+}
+
+static mfa_status sinks_of(const mfa_attention_sinks *block, Sinks *sinks) {
+  if (!block)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "null mfa_attention_sinks: the sink entries require the block (mfa_attention_sinks_init; a launch "
+                                          "without sinks: the mfa_window.h entries, or an all-zero block)");
+  sinks->tokens = block->sinkTokens;
+  sinks->logits = block->sinkLogits;
+  return MFA_OK;
+}
+
+mfa_status mfa_attention_decode_sink_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
+                                                    const mfa_attention_sinks *sinks, uint64_t *bytes) {
+  if (bytes) *bytes = 0;
+  Sinks s;
+  const mfa_status st = sinks_of(sinks, &s);
+  return st != MFA_OK ? st : decode_workspace_size(params, quant, window, s, bytes);
+}
+
+mfa_status mfa_attention_decode_sink_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
+                                            const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks, void *stream) {
+  Sinks s;
+  const mfa_status st = sinks_of(sinks, &s);
+  return st != MFA_OK ? st : decode_launch(q, k, v, o, l, params, quant, window, s, stream);
+}
+
+mfa_status mfa_attention_decode_sink_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
+                                                 const mfa_attention_sinks *sinks, char *out, size_t capacity) {
+  if (out && capacity) out[0] = '\0';
+  Sinks s;
+  const mfa_status st = sinks_of(sinks, &s);
+  return st != MFA_OK ? st : decode_launch_form(params, quant, window, s, out, capacity);
+}
+
+mfa_status mfa_attention_decode_sink_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
+                                          const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks, void *stream,
+                                          int warmup, int iterations, float *milliseconds) {
+  Sinks s;
+  const mfa_status st = sinks_of(sinks, &s);
+  return st != MFA_OK ? st : decode_time(q, k, v, o, l, params, quant, window, s, stream, warmup, iterations, milliseconds);
+}
+
+mfa_status mfa_attention_decode_sink_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t sinkTokens, uint32_t pieces,
+                                                 uint32_t piece, uint32_t begin[2], uint32_t end[2]) {
+  if (!begin || !end) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (pieces == 0 || piece >= pieces) return fail(MFA_ERR_INVALID_ARGUMENT, "piece must be below pieces, pieces non-zero");
+  if (rows == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "rows must be non-zero");
+  if (sinkTokens && !window) return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens must be 0 when window is 0");
+  decode_sink_piece_range(length, rows, window, sinkTokens, pieces, piece, begin, end);
   return MFA_OK;
 }
 

@@ -30,6 +30,16 @@
 // again (causal frontiers and n); tiles outside [begin, end) are never loaded -- no key, no page, no block-table entry.  The first
 // load is tile `begin`, the buffer of tile t is (t - begin) & 1.  The mask is one unsigned comparison c - lo < lim - lo.  With
 // W >= column + rows: begin = unmaskedBegin = 0, unmaskedEnd = first_masked -- the plain kernel's arithmetic in the plain order.
+//
+// SINK: the WINDOW body with attention sinks (include/mfa_sink.h); a.window = 0 is "lo = 0 everywhere".
+//   * sink TOKENS, a.sinkTokens = S: row r also sees the keys c < slim = min(S, lim).  prefill_sink_tile_range adds a fifth index: a
+//     fourth loop walks the tiles [0, sinkEnd) AHEAD of the three that exist, always with the per-element mask; sinkEnd <= begin, and
+//     the tiles between them are never loaded -- no key, no page, no block-table entry.  The buffer of a tile is its POSITION in
+//     the walked list [0, sinkEnd) ++ [begin, end), not t - begin.  Every masked tile tests (c - lo < span) || (c < slim), so sink
+//     keys inside the window's own masked tiles (S reaches `begin`: the zones touch) are seen as well.
+//   * sink LOGIT, a.sinkLogits[query head] (natural units; null: none): one more term of the denominator at the normalisation,
+//     s2 = sink log2(e), never scaled by 1 / sqrt(D) or keyScale; L includes it.  A live row without a visible key: O = 0, L = s2.
+// With S = 0 and no logits the SINK kernels run the WINDOW kernels' arithmetic in their order.
 #pragma once
 #include "attn_decode16.h"
 #include "kv_e4m3.h"
@@ -62,6 +72,8 @@ struct PrefillArgs {
   uint32_t causal, outF32;
   float scale2;                   // log2(e) / sqrt(D)
   uint32_t window;                // the WINDOW kernels only (>= 1); last, so that no other field moves
+  uint32_t sinkTokens;            // the SINK kernels only, which also take window = 0 (no window); behind `window` in turn
+  const float *sinkLogits;        // [heads], natural units; null: none
 };
 
 // The tiles of the block of rows [r0, r0 + RB) of a sequence of n keys and qn rows.  Row r sees keys c < lim(r) = n, or with `causal`
@@ -116,10 +128,42 @@ __host__ __device__ __forceinline__ void prefill_window_tile_range(uint32_t n, u
   *end = (uint32_t)e;
 }
 
+// The same with `sinkTokens` sink keys (window = 0: no window, and then no sink keys -- prefill_tile_range's two indices under `causal`
+// with begin = unmaskedBegin = 0).  *sinkEnd = min(ceil(min(S, lim(last live row)) / 64), *begin): the tiles [0, *sinkEnd) are walked
+// ahead of [*begin, *end), with the per-element mask.  A block whose rows all lie past their window's keys (n < qn) sees its sink keys
+// alone: all five = ceil(min(S, n) / 64).  Device and host (mfa_attention_prefill_sink_tile_range) run this one body.
+__host__ __device__ __forceinline__ void prefill_sink_tile_range(uint32_t n, uint32_t qn, uint32_t r0, uint32_t RB, uint32_t causal,
+                                                                 uint32_t window, uint32_t sinkTokens, uint32_t *begin,
+                                                                 uint32_t *unmaskedBegin, uint32_t *unmaskedEnd, uint32_t *end,
+                                                                 uint32_t *sinkEnd) {
+  *begin = *unmaskedBegin = *unmaskedEnd = *end = *sinkEnd = 0;
+  if (r0 >= qn || n == 0) return;
+  if (!window) {
+    prefill_tile_range(n, qn, r0, RB, causal, unmaskedEnd, end);
+    return;
+  }
+  prefill_window_tile_range(n, qn, r0, RB, window, begin, unmaskedBegin, unmaskedEnd, end);
+  if (!sinkTokens) return;
+  if (*end == 0) {   // no row of the block sees a key of its window: lim = n for every row
+    const uint64_t sunk = sinkTokens < n ? sinkTokens : n;
+    *begin = *unmaskedBegin = *unmaskedEnd = *end = *sinkEnd = (uint32_t)((sunk + PF_TILE - 1) / PF_TILE);
+    return;
+  }
+  const uint64_t off = n > qn ? (uint64_t)n - qn : 0;
+  uint64_t last = (uint64_t)r0 + RB;
+  if (last > qn) last = qn;
+  uint64_t limLast = last + off;
+  if (limLast > n) limLast = n;
+  const uint64_t sunk = sinkTokens < limLast ? sinkTokens : limLast;
+  const uint64_t tiles = (sunk + PF_TILE - 1) / PF_TILE;
+  *sinkEnd = tiles < *begin ? (uint32_t)tiles : *begin;
+}
+
 template <int D> constexpr int prefill16_lds_bytes() { return 2 /*buffers*/ * 2 /*K, V*/ * PF_TILE * D * 2; }
 
-template <typename T, int D, bool FP8, bool WINDOW = false>
+template <typename T, int D, bool FP8, bool WINDOW = false, bool SINK = false>
 __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
+  static_assert(!SINK || WINDOW, "the sink kernels are the window kernels plus SINK");
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -147,7 +191,9 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   const uint32_t RB = a.RB, r0 = rb * RB;
   if (r0 >= qn) return;   // no live row: nothing is read or written
   uint32_t firstMasked, endTile, beginTile = 0, unmaskedBegin = 0;   // (WINDOW: firstMasked is unmaskedEnd)
-  if constexpr (WINDOW) prefill_window_tile_range(n, qn, r0, RB, a.window, &beginTile, &unmaskedBegin, &firstMasked, &endTile);
+  uint32_t sinkEnd = 0;   // SINK: the tiles [0, sinkEnd) are walked ahead of [beginTile, endTile)
+  if constexpr (SINK) prefill_sink_tile_range(n, qn, r0, RB, a.causal, a.window, a.sinkTokens, &beginTile, &unmaskedBegin, &firstMasked, &endTile, &sinkEnd);
+  else if constexpr (WINDOW) prefill_window_tile_range(n, qn, r0, RB, a.window, &beginTile, &unmaskedBegin, &firstMasked, &endTile);
   else prefill_tile_range(n, qn, r0, RB, a.causal, &firstMasked, &endTile);
   const float kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
   const float vscale = a.valueScale ? a.valueScale[kvh] : 1.0f;
@@ -172,8 +218,10 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   if constexpr (WINDOW) {
     const uint32_t f1 = row + (n > qn ? n - qn : 0u) + 1u;
     lo = max(f1, a.window) - a.window;
+    if constexpr (SINK) lo = a.window ? lo : 0u;
     span = lim > lo ? lim - lo : 0u;
   }
+  const uint32_t slim = SINK ? min(a.sinkTokens, lim) : 0u;   // SINK: and the keys c < slim
 
   // ---- addresses of a 16-key group (wave-uniform; element offsets from a.k / a.v)
   const int64_t ldk = a.ldk, ldv = a.ldv, psk = a.psk, psv = a.psv;   // (values, not fields of `a`: hipcc otherwise selects between
@@ -275,7 +323,9 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
       float mx = DEC_MINUS_HUGE;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const bool visible = !MASK || (WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span : cur + (uint32_t)crow(r, hi) < lim);
+        const bool visible = !MASK || (SINK     ? (cur + (uint32_t)crow(r, hi) - lo < span) | (cur + (uint32_t)crow(r, hi) < slim)
+                                       : WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span
+                                                : cur + (uint32_t)crow(r, hi) < lim);
         s[r] = visible ? s[r] * kscale : DEC_MINUS_HUGE;
         mx = fmaxf(mx, s[r]);
       }
@@ -293,7 +343,9 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
       v8 pf[2];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const bool visible = !MASK || (WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span : cur + (uint32_t)crow(r, hi) < lim);
+        const bool visible = !MASK || (SINK     ? (cur + (uint32_t)crow(r, hi) - lo < span) | (cur + (uint32_t)crow(r, hi) < slim)
+                                       : WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span
+                                                : cur + (uint32_t)crow(r, hi) < lim);
         const float pr = visible ? fast_exp2(s[r] - m) : 0.f;   // replaced, never multiplied
         psum += pr;
         pf[r >> 3][r & 7] = (T)pr;
@@ -315,15 +367,31 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
 
   // ---- the tiles: the loads of tile t + 1 fly under the arithmetic of tile t and land in the other buffer behind it.  One barrier
   // per tile: the buffer written in iteration t was last read in iteration t - 1, which every wave left through that barrier.
-  if (endTile > beginTile) {
+  if constexpr (SINK) {
+    if (sinkEnd != 0 || endTile > beginTile) {
+      issue_loads((sinkEnd ? 0u : beginTile) * PF_TILE);
+      write_lds(0);
+    }
+  } else if (endTile > beginTile) {
     issue_loads(beginTile * PF_TILE);
     write_lds(0);
   }
   __syncthreads();
-  auto tile = [&](auto maskTag, uint32_t t) MFA_PREFILL_INLINE {
-    const bool more = t + 1 < endTile;
-    const int buf = (int)((t - beginTile) & 1u);
-    if (more) issue_loads((t + 1) * PF_TILE);
+  // (sinkZone: a tile of [0, sinkEnd); the tile walked after the last of them is beginTile, and a buffer is a position in the list)
+  auto tile = [&](auto maskTag, auto sinkZone, uint32_t t) MFA_PREFILL_INLINE {
+    bool more = t + 1 < endTile;
+    uint32_t next = t + 1;
+    int buf = (int)((t - beginTile) & 1u);
+    if constexpr (SINK) {
+      if constexpr (decltype(sinkZone)::value) {
+        more = t + 1 < sinkEnd || endTile > beginTile;
+        next = t + 1 < sinkEnd ? t + 1 : beginTile;
+        buf = (int)(t & 1u);
+      } else {
+        buf = (int)((t - beginTile + sinkEnd) & 1u);
+      }
+    }
+    if (more) issue_loads(next * PF_TILE);
     compute(maskTag, t * PF_TILE, buf, 0);
     compute(maskTag, t * PF_TILE, buf, 1);
     if (more) write_lds(buf ^ 1);
@@ -331,16 +399,30 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   };
   // (two loops, not one loop with the choice inside: with both forms of a step merging in one loop body hipcc spilled 6 .. 19 VGPRs
   // of the D = 128 kernels; like this the largest takes 232 of 256)
+  if constexpr (SINK)     // (a fourth loop ahead of them all: the sink tiles)
+    for (uint32_t ts = 0; ts < sinkEnd; ++ts) tile(std::true_type{}, std::true_type{}, ts);
   uint32_t t = beginTile;
   if constexpr (WINDOW)   // (a third loop in front: the tiles in which some row's window starts)
-    for (; t < unmaskedBegin; ++t) tile(std::true_type{}, t);
-  for (; t < firstMasked; ++t) tile(std::false_type{}, t);
-  for (; t < endTile; ++t) tile(std::true_type{}, t);
+    for (; t < unmaskedBegin; ++t) tile(std::true_type{}, std::false_type{}, t);
+  for (; t < firstMasked; ++t) tile(std::false_type{}, std::false_type{}, t);
+  for (; t < endTile; ++t) tile(std::true_type{}, std::false_type{}, t);
 
   // ---- normalise and store straight from the accumulators: o[db][4 g + i] is d = 32 db + 8 g + 4 hi + i of the lane's row
-  const float l_tot = l + __shfl_xor(l, 32);
+  float l_tot = l + __shfl_xor(l, 32);
   if (!live) return;
-  const float inv = l_tot > 0.f ? vscale / l_tot : 0.f;   // a row without a visible key: O = 0
+  // SINK: the sink logit joins (m, l); `fold` rescales O with l.  A row without a visible key ends with m = s2, l = 1
+  float fold = 1.0f;
+  if constexpr (SINK) {
+    if (a.sinkLogits) {
+      float s2 = a.sinkLogits[qhead] * 1.44269504089f;
+      asm volatile("" : "+v"(s2));   // (s2 is the ROUNDED product in m and in both exponents: never fused into the subtractions below)
+      const float mnew = fmaxf(m, s2);
+      fold = fast_exp2(m - mnew);
+      l_tot = l_tot * fold + fast_exp2(s2 - mnew);
+      m = mnew;
+    }
+  }
+  const float inv = l_tot > 0.f ? vscale * fold / l_tot : 0.f;   // a row without a visible key: O = 0
   const int64_t at = (int64_t)batch * a.bso + (int64_t)qhead * a.hso + (int64_t)rowt * a.ldo;
 #pragma unroll
   for (int db = 0; db < NDB; ++db)

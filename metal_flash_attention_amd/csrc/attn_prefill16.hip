@@ -1,5 +1,6 @@
 // attn_prefill16.hip -- prefill attention over a KV cache: the kernels' code objects, the C ABI of include/mfa_prefill.h and the prefill
-// entries of include/mfa_window.h (a sliding window: the same checks and grid, the attn_prefill16w_* kernels).
+// entries of include/mfa_window.h (a sliding window: the same checks and grid, the attn_prefill16w_* kernels) and of include/mfa_sink.h
+// (attention sinks: the attn_prefill16s_* kernels).
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include <string>
 
 #include "../../include/mfa_prefill.h"
+#include "../../include/mfa_sink.h"
 #include "../../include/mfa_window.h"
 #include "attn_prefill16.h"
 #include "cache_launch.h"
@@ -19,7 +21,7 @@
 using namespace mfa;
 
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_prefill16_d<D>_<type>[_e4m3], and attn_prefill16w_*
-// under a sliding window
+// under a sliding window, attn_prefill16s_* with attention sinks
 #define MFA_PREFILL_KERNELS(TN, T, D)                                                                                                 \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16_d##D##_##TN(const PrefillArgs a) {                              \
     prefill16_body<T, D, false>(a);                                                                                                   \
@@ -32,6 +34,12 @@ using namespace mfa;
   }                                                                                                                                   \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16w_d##D##_##TN##_e4m3(const PrefillArgs a) {                      \
     prefill16_body<T, D, true, true>(a);                                                                                              \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16s_d##D##_##TN(const PrefillArgs a) {                             \
+    prefill16_body<T, D, false, true, true>(a);                                                                                       \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16s_d##D##_##TN##_e4m3(const PrefillArgs a) {                      \
+    prefill16_body<T, D, true, true, true>(a);                                                                                        \
   }
 MFA_PREFILL_KERNELS(bf16, __bf16, 64)
 MFA_PREFILL_KERNELS(bf16, __bf16, 128)
@@ -45,30 +53,49 @@ struct PrefillSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  PrefillKernel kernel[2][2];   // [window][e4m3]
-  const char *name[2][2];
+  PrefillKernel kernel[3][2];   // [0: plain, 1: window, 2: sinks][e4m3]
+  const char *name[3][2];
 };
 #define MFA_PREFILL_SET(TN, PREC, D)                                                                                                  \
   {D, PREC, (uint32_t)prefill16_lds_bytes<D>(),                                                                                       \
-   {{attn_prefill16_d##D##_##TN, attn_prefill16_d##D##_##TN##_e4m3}, {attn_prefill16w_d##D##_##TN, attn_prefill16w_d##D##_##TN##_e4m3}}, \
+   {{attn_prefill16_d##D##_##TN, attn_prefill16_d##D##_##TN##_e4m3},                                                                  \
+    {attn_prefill16w_d##D##_##TN, attn_prefill16w_d##D##_##TN##_e4m3},                                                                \
+    {attn_prefill16s_d##D##_##TN, attn_prefill16s_d##D##_##TN##_e4m3}},                                                               \
    {{"attn_prefill16_d" #D "_" #TN, "attn_prefill16_d" #D "_" #TN "_e4m3"},                                                           \
-    {"attn_prefill16w_d" #D "_" #TN, "attn_prefill16w_d" #D "_" #TN "_e4m3"}}}
+    {"attn_prefill16w_d" #D "_" #TN, "attn_prefill16w_d" #D "_" #TN "_e4m3"},                                                         \
+    {"attn_prefill16s_d" #D "_" #TN, "attn_prefill16s_d" #D "_" #TN "_e4m3"}}}
 const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(f16, MFA_FP16, 64),
                             MFA_PREFILL_SET(f16, MFA_FP16, 128)};
+
+// the sinks of a launch: none for the entries of the other headers
+struct Sinks {
+  uint32_t tokens = 0;
+  const float *logits = nullptr;
+  bool any() const { return tokens != 0 || logits != nullptr; }
+};
 
 struct PrefillPlan {
   PrefillArgs args;
   const PrefillSet *set;
   bool fp8;
   uint32_t window;   // 0: none
+  int family;        // 0: plain, 1: window, 2: sinks -- the kernels' first index
   uint32_t blocks;   // batches x K/V heads x row blocks
-  PrefillKernel kernel() const { return set->kernel[window != 0][fp8]; }
-  const char *name() const { return set->name[window != 0][fp8]; }
+  PrefillKernel kernel() const { return set->kernel[family][fp8]; }
+  const char *name() const { return set->name[family][fp8]; }
 };
 
-// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `window` 0: none
-mfa_status prepare(const mfa_prefill_params *p, uint32_t window, PrefillPlan *plan) {
+// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `window` 0: none;
+// `sinks`: include/mfa_sink.h
+mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &sinks, PrefillPlan *plan) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (sinks.tokens && !window)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens = " + std::to_string(sinks.tokens) +
+                                              " keeps the first keys visible under a sliding window, and window is 0 (every key below "
+                                              "the frontier is visible already)");
+  if (sinks.tokens && !p->causal)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need causal: sinkTokens = " + std::to_string(sinks.tokens) +
+                                              " extends a sliding window, which ends at a row's causal frontier");
   if (window && !p->causal)
     return fail(MFA_ERR_INVALID_ARGUMENT, "a sliding window needs causal: the window is the " + std::to_string(window) +
                                               " keys that end at a row's causal frontier (window 0: no window)");
@@ -118,6 +145,7 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, PrefillPlan *pl
   plan->set = set;
   plan->fp8 = fp8;
   plan->window = window;
+  plan->family = sinks.any() ? 2 : window != 0;
   plan->blocks = (uint32_t)blocks;
   PrefillArgs &a = plan->args;
   std::memset(&a, 0, sizeof(a));
@@ -138,6 +166,8 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, PrefillPlan *pl
   a.causal = p->causal != 0; a.outF32 = p->outputPrecision == MFA_FP32;
   a.scale2 = 1.44269504089f / std::sqrt((float)p->headDimension);
   a.window = window;
+  a.sinkTokens = sinks.tokens;
+  a.sinkLogits = sinks.logits;
   return MFA_OK;
 }
 
@@ -145,6 +175,7 @@ mfa_status bind(PrefillPlan *plan, const void *q, const void *k, const void *v, 
   mfa_status st = check_buffers({q, k, v, o}, "Q, K, V and O");
   if (st == MFA_OK) st = check_float_arrays({l}, "L");
   if (st == MFA_OK) st = check_float_arrays({plan->args.keyScale, plan->args.valueScale}, "keyScale and valueScale");
+  if (st == MFA_OK) st = check_float_arrays({plan->args.sinkLogits}, "sinkLogits");
   if (st != MFA_OK) return st;
   plan->args.q = (const char *)q; plan->args.k = (const char *)k; plan->args.v = (const char *)v;
   plan->args.o = (char *)o; plan->args.l = l;
@@ -196,9 +227,9 @@ mfa_status mfa_attention_prefill_tile_range(uint32_t length, uint32_t queryLengt
 }
 
 static mfa_status prefill_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
-                                 uint32_t window, void *stream) {
+                                 uint32_t window, const Sinks &sinks, void *stream) {
   PrefillPlan plan;
-  mfa_status st = prepare(params, window, &plan);
+  mfa_status st = prepare(params, window, sinks, &plan);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -207,26 +238,28 @@ static mfa_status prefill_launch(const void *q, const void *k, const void *v, vo
   return MFA_OK;
 }
 
-static mfa_status prefill_launch_form(const mfa_prefill_params *params, uint32_t window, char *out, size_t capacity) {
+static mfa_status prefill_launch_form(const mfa_prefill_params *params, uint32_t window, const Sinks &sinks, char *out, size_t capacity) {
   if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   out[0] = '\0';
   PrefillPlan plan;
-  const mfa_status st = prepare(params, window, &plan);
+  const mfa_status st = prepare(params, window, sinks, &plan);
   if (st != MFA_OK) return st;
   const PrefillArgs &a = plan.args;
   char text[512];
+  // (a windowed launch names its window, then its sink tokens; bound sink logits last)
+  const std::string tail = (window ? ", window " + std::to_string(window) : std::string()) +
+                           (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : std::string()) + (sinks.logits ? ", sink logits" : "");
   std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s%s)", plan.name(),
-                plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous",
-                window ? (", window " + std::to_string(window)).c_str() : "");
+                plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous", tail.c_str());
   copy_text(out, capacity, text);
   return MFA_OK;
 }
 
 static mfa_status prefill_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
-                               uint32_t window, void *stream, int warmup, int iterations, float *milliseconds) {
+                               uint32_t window, const Sinks &sinks, void *stream, int warmup, int iterations, float *milliseconds) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   PrefillPlan plan;
-  mfa_status st = prepare(params, window, &plan);
+  mfa_status st = prepare(params, window, sinks, &plan);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -235,32 +268,32 @@ static mfa_status prefill_time(const void *q, const void *k, const void *v, void
 
 mfa_status mfa_attention_prefill_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                         void *stream) {
-  return prefill_launch(q, k, v, o, l, params, 0, stream);
+  return prefill_launch(q, k, v, o, l, params, 0, Sinks(), stream);
 }
 
 mfa_status mfa_attention_prefill_launch_form(const mfa_prefill_params *params, char *out, size_t capacity) {
-  return prefill_launch_form(params, 0, out, capacity);
+  return prefill_launch_form(params, 0, Sinks(), out, capacity);
 }
 
 mfa_status mfa_attention_prefill_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                       void *stream, int warmup, int iterations, float *milliseconds) {
-  return prefill_time(q, k, v, o, l, params, 0, stream, warmup, iterations, milliseconds);
+  return prefill_time(q, k, v, o, l, params, 0, Sinks(), stream, warmup, iterations, milliseconds);
 }
 
 // ---- under a sliding window (include/mfa_window.h): the same three with `window` after `params`; window 0 is the launch without one
 
 mfa_status mfa_attention_prefill_window_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                                uint32_t window, void *stream) {
-  return prefill_launch(q, k, v, o, l, params, window, stream);
+  return prefill_launch(q, k, v, o, l, params, window, Sinks(), stream);
 }
 
 mfa_status mfa_attention_prefill_window_launch_form(const mfa_prefill_params *params, uint32_t window, char *out, size_t capacity) {
-  return prefill_launch_form(params, window, out, capacity);
+  return prefill_launch_form(params, window, Sinks(), out, capacity);
 }
 
 mfa_status mfa_attention_prefill_window_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                              uint32_t window, void *stream, int warmup, int iterations, float *milliseconds) {
-  return prefill_time(q, k, v, o, l, params, window, stream, warmup, iterations, milliseconds);
+  return prefill_time(q, k, v, o, l, params, window, Sinks(), stream, warmup, iterations, milliseconds);
 }
 
 mfa_status mfa_attention_prefill_window_tile_range(uint32_t length, uint32_t queryLength, uint32_t firstRow, uint32_t blockRows, uint32_t window,
@@ -269,6 +302,52 @@ mfa_status mfa_attention_prefill_window_tile_range(uint32_t length, uint32_t que
   if (blockRows == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "blockRows must be non-zero");
   if (window == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "window must be non-zero (no window: mfa_attention_prefill_tile_range)");
   prefill_window_tile_range(length, queryLength, firstRow, blockRows, window, begin, unmaskedBegin, unmaskedEnd, end);
+  return MFA_OK;
+}
+
+// ---- with attention sinks (include/mfa_sink.h): the window entries with `sinks` after `window`.  The block is required; an all-zero
+// one is the window launch, whichever window
+
+static mfa_status sinks_of(const mfa_attention_sinks *block, Sinks *sinks) {
+  if (!block)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "null mfa_attention_sinks: the sink entries require the block (mfa_attention_sinks_init; a launch "
+                                          "without sinks: the mfa_window.h entries, or an all-zero block)");
+  sinks->tokens = block->sinkTokens;
+  sinks->logits = block->sinkLogits;
+  return MFA_OK;
+}
+
+mfa_status mfa_attention_prefill_sink_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                             uint32_t window, const mfa_attention_sinks *sinks, void *stream) {
+  Sinks s;
+  const mfa_status st = sinks_of(sinks, &s);
+  return st != MFA_OK ? st : prefill_launch(q, k, v, o, l, params, window, s, stream);
+}
+
+mfa_status mfa_attention_prefill_sink_launch_form(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks, char *out,
+                                                  size_t capacity) {
+  if (out && capacity) out[0] = '\0';
+  Sinks s;
+  const mfa_status st = sinks_of(sinks, &s);
+  return st != MFA_OK ? st : prefill_launch_form(params, window, s, out, capacity);
+}
+
+mfa_status mfa_attention_prefill_sink_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                           uint32_t window, const mfa_attention_sinks *sinks, void *stream, int warmup, int iterations,
+                                           float *milliseconds) {
+  Sinks s;
+  const mfa_status st = sinks_of(sinks, &s);
+  return st != MFA_OK ? st : prefill_time(q, k, v, o, l, params, window, s, stream, warmup, iterations, milliseconds);
+}
+
+mfa_status mfa_attention_prefill_sink_tile_range(uint32_t length, uint32_t queryLength, uint32_t firstRow, uint32_t blockRows, uint32_t causal,
+                                                 uint32_t window, uint32_t sinkTokens, uint32_t *begin, uint32_t *unmaskedBegin,
+                                                 uint32_t *unmaskedEnd, uint32_t *end, uint32_t *sinkEnd) {
+  if (!begin || !unmaskedBegin || !unmaskedEnd || !end || !sinkEnd) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (blockRows == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "blockRows must be non-zero");
+  if (window && !causal) return fail(MFA_ERR_INVALID_ARGUMENT, "a sliding window needs causal");
+  if (sinkTokens && !window) return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens must be 0 when window is 0");
+  prefill_sink_tile_range(length, queryLength, firstRow, blockRows, causal, window, sinkTokens, begin, unmaskedBegin, unmaskedEnd, end, sinkEnd);
   return MFA_OK;
 }
 

@@ -298,7 +298,7 @@ def _cache_strides(t, paged):
     return (int(t.stride(2)) if t.shape[2] > 1 else int(t.shape[3]), int(t.stride(1)), 0 if paged else int(t.stride(0)))
 
 
-def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None):
+def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None, sinks=None):
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
         raise RuntimeError("flash_decode: tensors must live on the GPU (there is no CPU path)")
     if fp8:
@@ -349,6 +349,8 @@ def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=Fal
                            K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
     if window is not None:
         kw.update(window=int(window))
+    if sinks is not None:   # (sink tokens or 0, sink logits or None): the entries of include/mfa_sink.h
+        kw.update(sinkTokens=int(sinks[0]), sinkLogits=sinks[1])
     need = dec.workspaceSize(**kw)
     ws = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
     with torch.cuda.device(q.device):
@@ -511,7 +513,8 @@ _HAVE_DECODE_OP = _register_decode_op()
 
 def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                  block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False,
-                 k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, window: Optional[int] = None):
+                 k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, window: Optional[int] = None,
+                 sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None):
     """Attention of the R new rows of every sequence (q [B, H, R, D]; R = 1, or a few speculative tokens; G R <= 32 with G = H / Hkv)
     against its KV cache.  cache_lengths [B] (GPU, int32): valid keys per sequence INCLUDING the R new tokens, which the caller has
     already written into the cache; with `causal` row r sees key c iff c <= r + max(len - R, 0).  Caches: [B, Hkv, C, D], or any view
@@ -525,13 +528,24 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     cache are an error.
     window=W (an int >= 1; needs causal): sliding-window attention -- a row sees its frontier and the W - 1 keys before it; keys, pages
     and block-table entries below the first 64-key tile a sequence's rows see are never read (include/mfa_window.h).  Goes through the
-    op `mfa::attention_decode_window`, for 16-bit and e4m3 caches alike.  None: no window."""
+    op `mfa::attention_decode_window`, for 16-bit and e4m3 caches alike.  None: no window.
+    sink_tokens=S (an int >= 1; needs window): the keys [0, S) stay visible under the window, and the keys, pages and block-table
+    entries between their tiles and the window's are never read.  sink_logits [H] fp32 on the GPU (any window, causal or not): one
+    learned logit per query head joins the softmax denominator and no value row -- natural-log units, not scaled by 1 / sqrt(D) or
+    k_scale; L includes it (include/mfa_sink.h).  Either goes through the op `mfa::attention_decode_sink`."""
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
         raise RuntimeError("flash_decode: tensors must live on the GPU (there is no CPU path)")
     for t in (q, k_cache, v_cache):
         if t.requires_grad:
             raise RuntimeError("flash_decode is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
-    if window is not None:
+    if sink_tokens is not None or sink_logits is not None:
+        _check_sinks("flash_decode", q, window, causal, sink_tokens, sink_logits)
+        if _HAVE_SINK_OPS:
+            o, l = torch.ops.mfa.attention_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale,
+                                                       window or 0, sink_tokens or 0, sink_logits)
+        else:
+            o, l = _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits)
+    elif window is not None:
         _check_window("flash_decode", window, causal)
         if _HAVE_WINDOW_OPS:
             o, l = torch.ops.mfa.attention_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window)
@@ -555,7 +569,7 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
 _PREFILLERS: Dict[Tuple, AttentionPrefill] = {}
 
 
-def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None):
+def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None, sinks=None):
     who = "flash_prefill"
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
         raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
@@ -614,6 +628,8 @@ def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, cau
                            K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
     if window is not None:
         kw.update(window=int(window))
+    if sinks is not None:
+        kw.update(sinkTokens=int(sinks[0]), sinkLogits=sinks[1])
     with torch.cuda.device(q.device):
         pre.dispatch(q, k_cache, v_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
     return o, l
@@ -699,10 +715,78 @@ def _register_window_ops():
 _HAVE_WINDOW_OPS = _register_window_ops()
 
 
+def _check_sinks(who, q, window, causal, sink_tokens, sink_logits):
+    if window is not None:
+        _check_window(who, window, causal)
+    if sink_tokens is not None:
+        if isinstance(sink_tokens, bool) or not isinstance(sink_tokens, int) or not 1 <= sink_tokens < 2 ** 32:
+            raise ValueError(f"{who}: sink_tokens must be an int from 1 to 2^32 - 1 (None: no sink tokens), not {sink_tokens!r}")
+        if window is None:
+            raise ValueError(f"{who}: sink_tokens needs window: the sink keys stay visible under a sliding window (without one every "
+                             "key below the frontier is visible already)")
+    if sink_logits is not None:
+        if not isinstance(sink_logits, torch.Tensor) or sink_logits.dtype != torch.float32 or q.dim() != 4 or \
+                tuple(sink_logits.shape) != (q.shape[1],) or not sink_logits.is_contiguous():
+            raise ValueError(f"{who}: sink_logits must be a contiguous float32 tensor [H] = [{q.shape[1] if q.dim() == 4 else '?'}], one logit "
+                             f"per query head (got {tuple(sink_logits.shape) if isinstance(sink_logits, torch.Tensor) else type(sink_logits).__name__}"
+                             f"{', ' + str(sink_logits.dtype) if isinstance(sink_logits, torch.Tensor) else ''})")
+        if sink_logits.device != q.device:
+            raise RuntimeError(f"{who}: sink_logits must live on q's device (the host never reads a logit)")
+
+
+def _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits):
+    fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError("flash_decode: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache holds the values themselves")
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8, k_scale, v_scale, window or None, (sink_tokens, sink_logits))
+
+
+def _register_sink_ops():
+    """mfa::attention_decode_sink and mfa::attention_prefill_sink (include/mfa_sink.h): the window ops with `sink_tokens` (0: none)
+    and `sink_logits` behind `window` (0: none).  The other ops keep their schemas."""
+    if not hasattr(torch.library, "custom_op"):
+        return False
+    try:
+        torch.ops.mfa.attention_decode_sink  # noqa: B018 -- AttributeError when the op is not defined yet
+        torch.ops.mfa.attention_prefill_sink  # noqa: B018
+        return True
+    except (AttributeError, RuntimeError):
+        pass
+
+    @torch.library.custom_op("mfa::attention_decode_sink", mutates_args=(), device_types="cuda")
+    def _op_decode_sink(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                        block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor],
+                        window: int, sink_tokens: int, sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        return _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits)
+
+    @_op_decode_sink.register_fake
+    def _op_decode_sink_fake(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits):
+        B, H, R, D = q.shape
+        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
+
+    @torch.library.custom_op("mfa::attention_prefill_sink", mutates_args=(), device_types="cuda")
+    def _op_prefill_sink(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                         q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
+                         k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
+                         sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window or None,
+                            (sink_tokens, sink_logits))
+
+    @_op_prefill_sink.register_fake
+    def _op_prefill_sink_fake(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits):
+        B, H, R, D = q.shape
+        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
+
+    return True
+
+
+_HAVE_SINK_OPS = _register_sink_ops()
+
+
 def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                   q_lengths: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None, causal: bool = True,
                   k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, return_lse: bool = False,
-                  window: Optional[int] = None):
+                  window: Optional[int] = None, sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None):
     """Attention of a BLOCK of new rows of every sequence (q [B, H, R, D], any R: a chunk of a prompt, a reused prefix's tail, a long
     speculative block) against its KV cache, which already holds the new tokens (kv_cache_append first).  cache_lengths [B] (GPU):
     valid keys per sequence INCLUDING the new tokens; q_lengths [B] (GPU, None = R for every sequence): the new rows of sequence b,
@@ -713,13 +797,23 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     e4m3(byte)).  The G = H / Hkv query heads of a K/V head share one workgroup (G <= 32), so K and V are read once per group.
     Forward only.  return_lse: also L [B, H, R] fp32 in natural units.  Goes through the torch.library op `mfa::attention_prefill`
     where torch has custom ops, so it traces under torch.compile.  window=W (an int >= 1; needs causal): sliding-window attention as
-    flash_decode's, through the op `mfa::attention_prefill_window`; None: no window."""
+    flash_decode's, through the op `mfa::attention_prefill_window`; None: no window.  sink_tokens / sink_logits: attention sinks as
+    flash_decode's (include/mfa_sink.h), through the op `mfa::attention_prefill_sink`; a live row without a visible key then gets
+    L = the head's sink logit."""
     if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
         raise RuntimeError("flash_prefill: tensors must live on the GPU (there is no CPU path)")
     for t in (q, k_cache, v_cache):
         if t.requires_grad:
             raise RuntimeError("flash_prefill is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
-    if window is not None:
+    if sink_tokens is not None or sink_logits is not None:
+        _check_sinks("flash_prefill", q, window, causal, sink_tokens, sink_logits)
+        if _HAVE_SINK_OPS:
+            o, l = torch.ops.mfa.attention_prefill_sink(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale,
+                                                        window or 0, sink_tokens or 0, sink_logits)
+        else:
+            o, l = _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window,
+                                (sink_tokens or 0, sink_logits))
+    elif window is not None:
         _check_window("flash_prefill", window, causal)
         if _HAVE_WINDOW_OPS:
             o, l = torch.ops.mfa.attention_prefill_window(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window)
