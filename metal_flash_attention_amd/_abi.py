@@ -294,6 +294,25 @@ SINK_SYMBOLS = [   # include/mfa_sink.h: `sinks` (required) after `window` (0 = 
     ("mfa_attention_prefill_sink_tile_range", ctypes.c_int, [ctypes.c_uint32] * 7 + [_U32P] * 5),
 ]
 
+class mfa_ragged_rows(ctypes.Structure):   # include/mfa_ragged.h
+    _fields_ = [("rowStarts", ctypes.c_void_p), ("totalRows", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+_RAGGED = ctypes.POINTER(mfa_ragged_rows)
+
+RAGGED_SYMBOLS = [   # include/mfa_ragged.h: `ragged` (required) after `sinks` (NULL = none)
+    ("mfa_ragged_rows_init", None, [_RAGGED]),
+    ("mfa_ragged_rows_size", ctypes.c_size_t, []),
+    ("mfa_ragged_rows_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
+    ("mfa_attention_prefill_ragged_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, ctypes.c_void_p]),
+    ("mfa_attention_prefill_ragged_launch_form", ctypes.c_int, [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_prefill_ragged_time", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, ctypes.c_void_p] + _TIMING),
+    ("mfa_attention_prefill_ragged_slots", ctypes.c_int, [ctypes.c_uint32] * 4 + [ctypes.POINTER(ctypes.c_uint64)]),
+    ("mfa_attention_prefill_ragged_block", ctypes.c_int, [_U32P] + [ctypes.c_uint32] * 5 + [_U32P, _U32P]),
+    ("mfa_kv_cache_append_ragged_launch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(mfa_kv_append_params), _RAGGED, ctypes.c_void_p]),
+]
+
 SYMBOLS = [
     ("mfa_precision_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mfa_precision_size", ctypes.c_int, [ctypes.c_int]),
@@ -369,7 +388,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -414,6 +414,19 @@ def _sinks_block(shape):
     return block, logits
 
 
+def _ragged_block(shape):
+    """pops rowStarts= / totalRows= from a launch's keywords -> (mfa_ragged_rows, what it points to), or None when neither is given
+    (include/mfa_ragged.h: packed rows, the block is required by the ragged entries)"""
+    starts, total = shape.pop("rowStarts", None), shape.pop("totalRows", None)
+    if starts is None and total is None:
+        return None
+    block = _abi.mfa_ragged_rows()
+    lib().mfa_ragged_rows_init(ctypes.byref(block))
+    block.rowStarts = _pointer(starts)
+    block.totalRows = int(total or 0)
+    return block, starts
+
+
 def _extended(shape) -> bool:
     """whether a launch's keywords ask for the window or sink entries"""
     return any(shape.get(name) is not None for name in ("window", "sinkTokens", "sinkLogits"))
@@ -645,7 +658,12 @@ class AttentionPrefill:
     K / V strides then count bytes, and keyScale / valueScale (device FP32 [heads // headsPerKeyValue], None = 1.0) go with the shape
     arguments.  The launch takes no workspace.  window=W (launchForm, dispatch, time): sliding-window attention,
     include/mfa_window.h; None: the plain launch; 0 goes through the window entries and is the plain launch.  sinkTokens=S,
-    sinkLogits=device FP32 [heads] (the same three): attention sinks as AttentionDecode's, include/mfa_sink.h."""
+    sinkLogits=device FP32 [heads] (the same three): attention sinks as AttentionDecode's, include/mfa_sink.h.
+
+    rowStarts=device uint32 [batches + 1], totalRows=T (the same three): a RAGGED batch, include/mfa_ragged.h -- q, o [T, heads, D] and
+    l [heads, T] packed along the rows, sequence b owning the rows rowStarts[b] .. rowStarts[b + 1]; `rows` is then the largest row
+    count of a sequence, queryLengths must stay None and Q / O / L have no batch stride (operands left out of `strides` are taken as
+    contiguous [T, heads, D]).  Goes through the ragged entries whichever window and sinks."""
 
     OPERANDS = ("Q", "K", "V", "O")
 
@@ -659,7 +677,7 @@ class AttentionPrefill:
     def _params(self, *, rows: int, column: int, heads: int = 1, batches: int = 1, headsPerKeyValue: int = 1, causal: bool = True,
                 cacheLengths=None, queryLengths=None, pageSize: int = 0, blockTable=None, blockTableStride: int = 0,
                 strides: Optional[Mapping] = None, pageStrides: Optional[Sequence[int]] = None, lStrides: Optional[Sequence[int]] = None,
-                keyScale=None, valueScale=None):
+                keyScale=None, valueScale=None, ragged=None):
         p = _abi.mfa_prefill_params()
         lib().mfa_prefill_params_init(ctypes.byref(p))
         p.rows, p.column, p.heads, p.batches = int(rows), int(column), int(heads), int(batches)
@@ -673,22 +691,35 @@ class AttentionPrefill:
         kvHeads = max(1, int(heads) // G)
         for i, name in enumerate(self.OPERANDS):
             seq, h = (int(rows), int(heads)) if name in ("Q", "O") else (int(pageSize) or int(column), kvHeads)
-            ld, hs, bs = (strides or {}).get(name, (D, seq * D, h * seq * D))
+            packed = (int(heads) * D, D, 0) if ragged and name in ("Q", "O") else (D, seq * D, h * seq * D)
+            ld, hs, bs = (strides or {}).get(name, packed)
             p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
         if pageStrides is not None:
             p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
         elif pageSize:
             p.pageStride[0] = p.pageStride[1] = kvHeads * int(pageSize) * D
-        p.lHeadStride, p.lBatchStride = (int(lStrides[0]), int(lStrides[1])) if lStrides is not None else (int(rows), int(heads) * int(rows))
+        if lStrides is not None:
+            p.lHeadStride, p.lBatchStride = int(lStrides[0]), int(lStrides[1])
+        elif ragged:
+            p.lHeadStride, p.lBatchStride = int(ragged[0].totalRows), 0
+        else:
+            p.lHeadStride, p.lBatchStride = int(rows), int(heads) * int(rows)
         p.keyScale, p.valueScale = _pointer(keyScale), _pointer(valueScale)
         return p, (cacheLengths, queryLengths, blockTable, keyScale, valueScale)
 
+    @staticmethod
+    def _sinks_pointer(sinks):
+        return ctypes.byref(sinks[0]) if sinks is not None else None
+
     def launchForm(self, **shape) -> str:
         """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name and the grid."""
-        window, sinks = shape.pop("window", None), _sinks_block(shape)
-        p, _keep = self._params(**shape)
+        window, sinks, ragged = shape.pop("window", None), _sinks_block(shape), _ragged_block(shape)
+        p, _keep = self._params(ragged=ragged, **shape)
         out = ctypes.create_string_buffer(512)
-        if sinks is not None:
+        if ragged is not None:
+            check(lib().mfa_attention_prefill_ragged_launch_form(ctypes.byref(p), int(window or 0), self._sinks_pointer(sinks),
+                                                                 ctypes.byref(ragged[0]), out, len(out)))
+        elif sinks is not None:
             check(lib().mfa_attention_prefill_sink_launch_form(ctypes.byref(p), int(window or 0), ctypes.byref(sinks[0]), out, len(out)))
         elif window is not None:
             check(lib().mfa_attention_prefill_window_launch_form(ctypes.byref(p), int(window), out, len(out)))
@@ -697,10 +728,13 @@ class AttentionPrefill:
         return out.value.decode()
 
     def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
-        window, sinks = shape.pop("window", None), _sinks_block(shape)
-        p, _keep = self._params(**shape)
+        window, sinks, ragged = shape.pop("window", None), _sinks_block(shape), _ragged_block(shape)
+        p, _keep = self._params(ragged=ragged, **shape)
         bufs = (_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l))
-        if sinks is not None:
+        if ragged is not None:
+            check(lib().mfa_attention_prefill_ragged_launch(*bufs, ctypes.byref(p), int(window or 0), self._sinks_pointer(sinks),
+                                                            ctypes.byref(ragged[0]), ctypes.c_void_p(stream or 0)))
+        elif sinks is not None:
             check(lib().mfa_attention_prefill_sink_launch(*bufs, ctypes.byref(p), int(window or 0), ctypes.byref(sinks[0]),
                                                           ctypes.c_void_p(stream or 0)))
         elif window is not None:
@@ -710,12 +744,15 @@ class AttentionPrefill:
 
     def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
         """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
-        window, sinks = shape.pop("window", None), _sinks_block(shape)
-        p, _keep = self._params(**shape)
+        window, sinks, ragged = shape.pop("window", None), _sinks_block(shape), _ragged_block(shape)
+        p, _keep = self._params(ragged=ragged, **shape)
         ms = ctypes.c_float(0.0)
         bufs = (_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l))
         timing = (ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms))
-        if sinks is not None:
+        if ragged is not None:
+            check(lib().mfa_attention_prefill_ragged_time(*bufs, ctypes.byref(p), int(window or 0), self._sinks_pointer(sinks),
+                                                          ctypes.byref(ragged[0]), *timing))
+        elif sinks is not None:
             check(lib().mfa_attention_prefill_sink_time(*bufs, ctypes.byref(p), int(window or 0), ctypes.byref(sinks[0]), *timing))
         elif window is not None:
             check(lib().mfa_attention_prefill_window_time(*bufs, ctypes.byref(p), int(window), *timing))
@@ -753,6 +790,25 @@ class AttentionPrefill:
         return tuple(int(x.value) for x in out)
 
 
+    @staticmethod
+    def raggedSlots(totalRows: int, batches: int, rows: int, blockRows: int) -> int:
+        """the slots of a ragged launch (include/mfa_ragged.h): min(totalRows // blockRows + batches, batches x ceil(rows / blockRows));
+        its grid is that many times the K/V heads"""
+        out = ctypes.c_uint64(0)
+        check(lib().mfa_attention_prefill_ragged_slots(int(totalRows), int(batches), int(rows), int(blockRows), ctypes.byref(out)))
+        return int(out.value)
+
+    @staticmethod
+    def raggedBlock(rowStarts: Sequence[int], totalRows: int, rows: int, blockRows: int, slot: int) -> Tuple[Optional[int], int]:
+        """(sequence, firstRow) of the row block that slot `slot` of a ragged launch serves, from HOST row starts [batches + 1]; (None, 0):
+        a slot past the last row block.  The kernels' own function, on the host"""
+        starts = (ctypes.c_uint32 * len(rowStarts))(*[int(x) for x in rowStarts])
+        seq, first = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        check(lib().mfa_attention_prefill_ragged_block(starts, len(rowStarts) - 1, int(totalRows), int(rows), int(blockRows), int(slot),
+                                                       ctypes.byref(seq), ctypes.byref(first)))
+        return (None if seq.value == 0xFFFFFFFF else int(seq.value)), int(first.value)
+
+
 class KVCacheAppend:
     """Appends the `rows` new key / value rows of every sequence to a KV cache (include/mfa_kvcache.h), quantising them to e4m3 when
     the cache is FP8 (cachePrecision=KVCachePrecision.E4M3) or copying their bits when it is the rows' 16-bit type (None).
@@ -762,7 +818,10 @@ class KVCacheAppend:
 
     cacheLengths already includes the new rows: row r of sequence b goes to key cacheLengths[b] - rows + r.  `strides`: operand name
     (kNew, vNew, kCache, vCache) -> (leadingDimension, headStride, batchStride) in elements; an operand left out is packed
-    ([batch][head][row or key][D]).  Paged caches: pageSize, blockTable, blockTableStride and pageStrides=(K, V)."""
+    ([batch][head][row or key][D]).  Paged caches: pageSize, blockTable, blockTableStride and pageStrides=(K, V).
+
+    rowStarts=device uint32 [batches + 1], totalRows=T: a RAGGED batch, include/mfa_ragged.h -- kNew, vNew [T, heads, D] packed along the
+    rows (left out of `strides`: contiguous), sequence b owning the rows rowStarts[b] .. rowStarts[b + 1], at most `rows` of them."""
 
     OPERANDS = ("kNew", "vNew", "kCache", "vCache")
 
@@ -773,7 +832,7 @@ class KVCacheAppend:
 
     def _params(self, *, rows: int, heads: int, batches: int = 1, column: int = 0, cacheLengths=None, pageSize: int = 0, blockTable=None,
                 blockTableStride: int = 0, strides: Optional[Mapping] = None, pageStrides: Optional[Sequence[int]] = None,
-                keyScale=None, valueScale=None):
+                keyScale=None, valueScale=None, ragged=None):
         p = _abi.mfa_kv_append_params()
         lib().mfa_kv_append_params_init(ctypes.byref(p))
         p.rows, p.heads, p.batches, p.column = int(rows), int(heads), int(batches), int(column)
@@ -783,7 +842,8 @@ class KVCacheAppend:
         D = self.headDimension
         for i, name in enumerate(self.OPERANDS):
             seq = int(rows) if i < 2 else (int(pageSize) or int(column))
-            ld, hs, bs = (strides or {}).get(name, (D, seq * D, int(heads) * seq * D))
+            packed = (int(heads) * D, D, 0) if ragged and i < 2 else (D, seq * D, int(heads) * seq * D)
+            ld, hs, bs = (strides or {}).get(name, packed)
             p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
         if pageStrides is not None:
             p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
@@ -791,7 +851,12 @@ class KVCacheAppend:
         return p
 
     def dispatch(self, kNew, vNew, kCache, vCache, *, stream: Optional[int] = None, **shape) -> None:
-        p = self._params(**shape)
+        ragged = _ragged_block(shape)
+        p = self._params(ragged=ragged, **shape)
+        if ragged is not None:
+            check(lib().mfa_kv_cache_append_ragged_launch(_pointer(kNew), _pointer(vNew), _pointer(kCache), _pointer(vCache), ctypes.byref(p),
+                                                          ctypes.byref(ragged[0]), ctypes.c_void_p(stream or 0)))
+            return
         check(lib().mfa_kv_cache_append_launch(_pointer(kNew), _pointer(vNew), _pointer(kCache), _pointer(vCache), ctypes.byref(p),
                                                ctypes.c_void_p(stream or 0)))
 

@@ -74,6 +74,8 @@ struct PrefillArgs {
   uint32_t window;                // the WINDOW kernels only (>= 1); last, so that no other field moves
   uint32_t sinkTokens;            // the SINK kernels only, which also take window = 0 (no window); behind `window` in turn
   const float *sinkLogits;        // [heads], natural units; null: none
+  const uint32_t *rowStarts;      // the RAGGED kernels only: [batches + 1], packed rows (include/mfa_ragged.h); behind the sinks in turn
+  uint32_t totalRows, slots;      // T; the slots of the grid (`rowBlocks` stays ceil(rows / RB))
 };
 
 // The tiles of the block of rows [r0, r0 + RB) of a sequence of n keys and qn rows.  Row r sees keys c < lim(r) = n, or with `causal`
@@ -159,11 +161,75 @@ __host__ __device__ __forceinline__ void prefill_sink_tile_range(uint32_t n, uin
   *sinkEnd = tiles < *begin ? (uint32_t)tiles : *begin;
 }
 
+// RAGGED (include/mfa_ragged.h): which row block slot `slot` of a launch over packed rows serves.  Sequence b owns the packed rows
+// [s_b, s_b + qn_b), s_b = min(starts[b], T), e_b = min(starts[b + 1], T), qn_b = min(max(e_b - s_b, 0), rows), in ceil(qn_b / RB) row
+// blocks; the slots count the row blocks of sequence 0, then those of sequence 1, ...  *sequence = UINT32_MAX: a slot past the total.
+// This scalar walk is the DEFINITION and what the host runs (mfa_attention_prefill_ragged_block); the kernels run
+// prefill_ragged_block_wave below, which returns its answer.  (sum_b ceil(qn_b / RB) <= batches x ceil(rows / RB) <= 2^31 - 1: the
+// host has checked it, nothing wraps.)
+__host__ __device__ __forceinline__ uint32_t prefill_ragged_count(uint32_t start, uint32_t next, uint32_t T, uint32_t rows, uint32_t *s) {
+  const uint32_t a = start < T ? start : T, e = next < T ? next : T;
+  *s = a;
+  const uint32_t span = e > a ? e - a : 0u;
+  return span < rows ? span : rows;
+}
+__host__ __device__ __forceinline__ void prefill_ragged_block(const uint32_t *starts, uint32_t batches, uint32_t T, uint32_t rows,
+                                                              uint32_t RB, uint32_t slot, uint32_t *sequence, uint32_t *firstRow,
+                                                              uint32_t *start, uint32_t *count) {
+  uint32_t before = 0;
+  for (uint32_t b = 0; b < batches; ++b) {
+    uint32_t s;
+    const uint32_t qn = prefill_ragged_count(starts[b], starts[b + 1], T, rows, &s);
+    const uint32_t nb = qn / RB + (qn % RB != 0);
+    if (slot - before < nb) {
+      *sequence = b; *firstRow = (slot - before) * RB; *start = s; *count = qn;
+      return;
+    }
+    before += nb;
+  }
+  *sequence = 0xffffffffu; *firstRow = 0; *start = 0; *count = 0;
+}
+
+#if defined(__HIPCC__)
+// The same answer, 64 sequences at a time: lane i of every wave takes sequence base + i, an inclusive prefix sum over the wave gives
+// the slots at or before each sequence, and the first lane whose sum passes `slot` holds the sequence.  All results wave-uniform.
+__device__ __forceinline__ void prefill_ragged_block_wave(const uint32_t *starts, uint32_t batches, uint32_t T, uint32_t rows, uint32_t RB,
+                                                          uint32_t slot, int lane, uint32_t *sequence, uint32_t *firstRow, uint32_t *start,
+                                                          uint32_t *count) {
+  uint32_t before = 0;
+  *sequence = 0xffffffffu; *firstRow = 0; *start = 0; *count = 0;
+  for (uint32_t base = 0; base < batches; base += 64u) {
+    const uint32_t b = base + (uint32_t)lane;
+    uint32_t s = 0, qn = 0;
+    if (b < batches) qn = prefill_ragged_count(starts[b], starts[b + 1], T, rows, &s);
+    const uint32_t nb = qn / RB + (qn % RB != 0);
+    uint32_t incl = nb;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+      if (lane >= d) incl += up;
+    }
+    const unsigned long long hit = __ballot(before + incl > slot);
+    if (hit) {
+      const int first = __builtin_ctzll(hit);
+      const uint32_t blocksBefore = before + (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)(incl - nb), first));
+      *sequence = base + (uint32_t)first;
+      *firstRow = (slot - blocksBefore) * RB;
+      *start = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)s, first));
+      *count = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)qn, first));
+      return;
+    }
+    before += (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)incl, 63));
+  }
+}
+#endif
+
 template <int D> constexpr int prefill16_lds_bytes() { return 2 /*buffers*/ * 2 /*K, V*/ * PF_TILE * D * 2; }
 
-template <typename T, int D, bool FP8, bool WINDOW = false, bool SINK = false>
+template <typename T, int D, bool FP8, bool WINDOW = false, bool SINK = false, bool RAGGED = false>
 __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   static_assert(!SINK || WINDOW, "the sink kernels are the window kernels plus SINK");
+  static_assert(!RAGGED || SINK, "the ragged kernels are the sink kernels plus RAGGED");
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -181,14 +247,23 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
 
   // ---- the block: (row block, K / V head, sequence); the blocks of one (sequence, K / V head) are neighbours on one XCD
   uint32_t rb, kvh, batch;
-  {
+  const uint32_t RB = a.RB;
+  uint32_t r0, qn, packed = 0;   // RAGGED: `packed` = s_b, the sequence's first packed row; Q, O and L have no batch axis
+  if constexpr (RAGGED) {
+    // the grid is slots x K / V heads: (slot, K / V head) come out of the same XCD-aware order, the slot gives (sequence, row block)
+    const Fwd16Grid g{a.slots, a.Hkv, 1u, 1u, nullptr, nullptr};
+    fwd16_decode_block(g, blockIdx.x, &rb, &kvh, &batch);
+    if (a.causal) rb = a.slots - 1 - rb;   // (the order of the slots is free: the last sequences' last row blocks start first)
+    prefill_ragged_block_wave(a.rowStarts, a.batches, a.totalRows, a.rows, RB, rb, lane, &batch, &r0, &packed, &qn);
+    if (batch == 0xffffffffu) return;      // a slot past the total: nothing is read or written
+  } else {
     const Fwd16Grid g{a.rowBlocks, a.Hkv, a.batches, 1u, nullptr, nullptr};
     fwd16_decode_block(g, blockIdx.x, &rb, &kvh, &batch);
+    if (a.causal) rb = a.rowBlocks - 1 - rb;   // later row blocks traverse more keys: start them first
+    qn = a.qlengths ? min(a.qlengths[batch], a.rows) : a.rows;
+    r0 = rb * RB;
   }
-  if (a.causal) rb = a.rowBlocks - 1 - rb;   // later row blocks traverse more keys: start them first
   const uint32_t n = min(a.lengths[batch], a.column);
-  const uint32_t qn = a.qlengths ? min(a.qlengths[batch], a.rows) : a.rows;
-  const uint32_t RB = a.RB, r0 = rb * RB;
   if (r0 >= qn) return;   // no live row: nothing is read or written
   uint32_t firstMasked, endTile, beginTile = 0, unmaskedBegin = 0;   // (WINDOW: firstMasked is unmaskedEnd)
   uint32_t sinkEnd = 0;   // SINK: the tiles [0, sinkEnd) are walked ahead of [beginTile, endTile)
@@ -206,7 +281,8 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   const uint32_t row = min(rowt, qn - 1);   // (rows at or past qn are not read: the lane repeats the last live one)
   v8 qf[NKS];
   {
-    const char *qp = a.q + ((int64_t)batch * a.bsq + (int64_t)qhead * a.hsq + (int64_t)row * a.ldq) * 2;
+    const int64_t qseq = RAGGED ? (int64_t)packed * a.ldq : (int64_t)batch * a.bsq;
+    const char *qp = a.q + (qseq + (int64_t)qhead * a.hsq + (int64_t)row * a.ldq) * 2;
 #pragma unroll
     for (int s = 0; s < NKS; ++s) qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + (16 * s + 8 * hi) * 2));
   }
@@ -423,7 +499,7 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
     }
   }
   const float inv = l_tot > 0.f ? vscale * fold / l_tot : 0.f;   // a row without a visible key: O = 0
-  const int64_t at = (int64_t)batch * a.bso + (int64_t)qhead * a.hso + (int64_t)rowt * a.ldo;
+  const int64_t at = (RAGGED ? (int64_t)packed * a.ldo : (int64_t)batch * a.bso) + (int64_t)qhead * a.hso + (int64_t)rowt * a.ldo;
 #pragma unroll
   for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -433,7 +509,7 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
       if (a.outF32) *reinterpret_cast<float4 *>(a.o + e * 4) = make_float4(x0, x1, x2, x3);
       else *reinterpret_cast<u32x2 *>(a.o + e * 2) = u32x2{pack16<T>(x0, x1), pack16<T>(x2, x3)};
     }
-  if (hi == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)qhead * a.lhs + rowt] = l_tot > 0.f ? m + log2f(l_tot) : DEC_MINUS_HUGE;
+  if (hi == 0 && a.l) a.l[(RAGGED ? (int64_t)packed : (int64_t)batch * a.lbs) + (int64_t)qhead * a.lhs + rowt] = l_tot > 0.f ? m + log2f(l_tot) : DEC_MINUS_HUGE;
 }
 
 } // namespace mfa

@@ -1,6 +1,6 @@
 // attn_prefill16.hip -- prefill attention over a KV cache: the kernels' code objects, the C ABI of include/mfa_prefill.h and the prefill
 // entries of include/mfa_window.h (a sliding window: the same checks and grid, the attn_prefill16w_* kernels) and of include/mfa_sink.h
-// (attention sinks: the attn_prefill16s_* kernels).
+// (attention sinks: the attn_prefill16s_* kernels), and the prefill entries of include/mfa_ragged.h (packed rows: attn_prefill16r_*).
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 #include <string>
 
 #include "../../include/mfa_prefill.h"
+#include "../../include/mfa_ragged.h"
 #include "../../include/mfa_sink.h"
 #include "../../include/mfa_window.h"
 #include "attn_prefill16.h"
@@ -21,7 +22,8 @@
 using namespace mfa;
 
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_prefill16_d<D>_<type>[_e4m3], and attn_prefill16w_*
-// under a sliding window, attn_prefill16s_* with attention sinks
+// under a sliding window, attn_prefill16s_* with attention sinks, attn_prefill16r_* over packed rows (the sink body: one ragged kernel
+// serves plain, window and sink launches)
 #define MFA_PREFILL_KERNELS(TN, T, D)                                                                                                 \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16_d##D##_##TN(const PrefillArgs a) {                              \
     prefill16_body<T, D, false>(a);                                                                                                   \
@@ -40,6 +42,12 @@ using namespace mfa;
   }                                                                                                                                   \
   extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16s_d##D##_##TN##_e4m3(const PrefillArgs a) {                      \
     prefill16_body<T, D, true, true, true>(a);                                                                                        \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16r_d##D##_##TN(const PrefillArgs a) {                             \
+    prefill16_body<T, D, false, true, true, true>(a);                                                                                 \
+  }                                                                                                                                   \
+  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16r_d##D##_##TN##_e4m3(const PrefillArgs a) {                      \
+    prefill16_body<T, D, true, true, true, true>(a);                                                                                  \
   }
 MFA_PREFILL_KERNELS(bf16, __bf16, 64)
 MFA_PREFILL_KERNELS(bf16, __bf16, 128)
@@ -53,19 +61,27 @@ struct PrefillSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  PrefillKernel kernel[3][2];   // [0: plain, 1: window, 2: sinks][e4m3]
-  const char *name[3][2];
+  PrefillKernel kernel[4][2];   // [0: plain, 1: window, 2: sinks, 3: ragged][e4m3]
+  const char *name[4][2];
 };
 #define MFA_PREFILL_SET(TN, PREC, D)                                                                                                  \
   {D, PREC, (uint32_t)prefill16_lds_bytes<D>(),                                                                                       \
    {{attn_prefill16_d##D##_##TN, attn_prefill16_d##D##_##TN##_e4m3},                                                                  \
     {attn_prefill16w_d##D##_##TN, attn_prefill16w_d##D##_##TN##_e4m3},                                                                \
-    {attn_prefill16s_d##D##_##TN, attn_prefill16s_d##D##_##TN##_e4m3}},                                                               \
+    {attn_prefill16s_d##D##_##TN, attn_prefill16s_d##D##_##TN##_e4m3},                                                                \
+    {attn_prefill16r_d##D##_##TN, attn_prefill16r_d##D##_##TN##_e4m3}},                                                               \
    {{"attn_prefill16_d" #D "_" #TN, "attn_prefill16_d" #D "_" #TN "_e4m3"},                                                           \
     {"attn_prefill16w_d" #D "_" #TN, "attn_prefill16w_d" #D "_" #TN "_e4m3"},                                                         \
-    {"attn_prefill16s_d" #D "_" #TN, "attn_prefill16s_d" #D "_" #TN "_e4m3"}}}
+    {"attn_prefill16s_d" #D "_" #TN, "attn_prefill16s_d" #D "_" #TN "_e4m3"},                                                         \
+    {"attn_prefill16r_d" #D "_" #TN, "attn_prefill16r_d" #D "_" #TN "_e4m3"}}}
 const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(f16, MFA_FP16, 64),
                             MFA_PREFILL_SET(f16, MFA_FP16, 128)};
+
+// min(T / RB + batches, batches x ceil(rows / RB)): never below sum_b ceil(qn_b / RB) for non-decreasing starts
+uint64_t ragged_slots(uint32_t totalRows, uint32_t batches, uint32_t rows, uint32_t RB) {
+  const uint64_t tight = (uint64_t)totalRows / RB + batches, padded = (uint64_t)batches * (((uint64_t)rows + RB - 1) / RB);
+  return tight < padded ? tight : padded;
+}
 
 // the sinks of a launch: none for the entries of the other headers
 struct Sinks {
@@ -79,16 +95,27 @@ struct PrefillPlan {
   const PrefillSet *set;
   bool fp8;
   uint32_t window;   // 0: none
-  int family;        // 0: plain, 1: window, 2: sinks -- the kernels' first index
-  uint32_t blocks;   // batches x K/V heads x row blocks
+  int family;        // 0: plain, 1: window, 2: sinks, 3: ragged -- the kernels' first index
+  uint32_t blocks;   // batches x K/V heads x row blocks; ragged: slots x K/V heads
   PrefillKernel kernel() const { return set->kernel[family][fp8]; }
   const char *name() const { return set->name[family][fp8]; }
 };
 
 // every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `window` 0: none;
-// `sinks`: include/mfa_sink.h
-mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &sinks, PrefillPlan *plan) {
+// `sinks`: include/mfa_sink.h; `ragged` non-null: packed rows, include/mfa_ragged.h
+mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &sinks, PrefillPlan *plan, const mfa_ragged_rows *ragged = nullptr) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (ragged) {
+    if (!ragged->rowStarts)
+      return fail(MFA_ERR_INVALID_ARGUMENT, "rowStarts is required (device array of batches + 1 uint32: the first packed row of every sequence, and the end of the last)");
+    if (ragged->totalRows == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "totalRows must be non-zero (the packed rows of Q, O and L)");
+    if (p->queryLengths)
+      return fail(MFA_ERR_INVALID_ARGUMENT, "queryLengths must be NULL for a ragged launch: rowStarts gives every sequence's row count");
+    if (p->batchStride[0] != 0 || p->batchStride[3] != 0)
+      return fail(MFA_ERR_INVALID_ARGUMENT, "batchStride of Q and O must be 0 for a ragged launch: the packed layout [totalRows][heads][D] has no batch axis");
+    if (p->lBatchStride != 0)
+      return fail(MFA_ERR_INVALID_ARGUMENT, "lBatchStride must be 0 for a ragged launch: the packed L [heads][totalRows] has no batch axis");
+  }
   if (sinks.tokens && !window)
     return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens = " + std::to_string(sinks.tokens) +
                                               " keeps the first keys visible under a sliding window, and window is 0 (every key below "
@@ -139,13 +166,21 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &si
   }
   const uint32_t RB = MFA_PREFILL_PACKED_ROWS / G;
   const uint64_t rowBlocks = ((uint64_t)p->rows + RB - 1) / RB;
-  const uint64_t blocks = (uint64_t)p->batches * (p->heads / G) * rowBlocks;
-  if (blocks > 0x7fffffffull)
+  uint64_t blocks = (uint64_t)p->batches * (p->heads / G) * rowBlocks, slots = 0;
+  if (ragged) {
+    if ((uint64_t)p->batches * rowBlocks > 0x7fffffffull)
+      return fail(MFA_ERR_UNSUPPORTED, "batches x ceil(rows / " + std::to_string(RB) + ") = " + std::to_string((uint64_t)p->batches * rowBlocks) +
+                                           " row blocks exceed 2^31 - 1: rows is the largest row count of a sequence, not totalRows");
+    slots = ragged_slots(ragged->totalRows, p->batches, p->rows, RB);
+    blocks = slots * (p->heads / G);
+    if (blocks > 0x7fffffffull)
+      return fail(MFA_ERR_UNSUPPORTED, "slots x K/V heads = " + std::to_string(blocks) + " workgroups exceed one grid (2^31 - 1)");
+  } else if (blocks > 0x7fffffffull)
     return fail(MFA_ERR_UNSUPPORTED, "batches x K/V heads x row blocks = " + std::to_string(blocks) + " workgroups exceed one grid (2^31 - 1)");
   plan->set = set;
   plan->fp8 = fp8;
   plan->window = window;
-  plan->family = sinks.any() ? 2 : window != 0;
+  plan->family = ragged ? 3 : sinks.any() ? 2 : window != 0;
   plan->blocks = (uint32_t)blocks;
   PrefillArgs &a = plan->args;
   std::memset(&a, 0, sizeof(a));
@@ -168,6 +203,11 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &si
   a.window = window;
   a.sinkTokens = sinks.tokens;
   a.sinkLogits = sinks.logits;
+  if (ragged) {
+    a.rowStarts = ragged->rowStarts;
+    a.totalRows = ragged->totalRows;
+    a.slots = (uint32_t)slots;
+  }
   return MFA_OK;
 }
 
@@ -227,9 +267,9 @@ mfa_status mfa_attention_prefill_tile_range(uint32_t length, uint32_t queryLengt
 }
 
 static mfa_status prefill_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
-                                 uint32_t window, const Sinks &sinks, void *stream) {
+                                 uint32_t window, const Sinks &sinks, void *stream, const mfa_ragged_rows *ragged = nullptr) {
   PrefillPlan plan;
-  mfa_status st = prepare(params, window, sinks, &plan);
+  mfa_status st = prepare(params, window, sinks, &plan, ragged);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -238,28 +278,34 @@ static mfa_status prefill_launch(const void *q, const void *k, const void *v, vo
   return MFA_OK;
 }
 
-static mfa_status prefill_launch_form(const mfa_prefill_params *params, uint32_t window, const Sinks &sinks, char *out, size_t capacity) {
+static mfa_status prefill_launch_form(const mfa_prefill_params *params, uint32_t window, const Sinks &sinks, char *out, size_t capacity,
+                                      const mfa_ragged_rows *ragged = nullptr) {
   if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   out[0] = '\0';
   PrefillPlan plan;
-  const mfa_status st = prepare(params, window, sinks, &plan);
+  const mfa_status st = prepare(params, window, sinks, &plan, ragged);
   if (st != MFA_OK) return st;
   const PrefillArgs &a = plan.args;
   char text[512];
   // (a windowed launch names its window, then its sink tokens; bound sink logits last)
   const std::string tail = (window ? ", window " + std::to_string(window) : std::string()) +
                            (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : std::string()) + (sinks.logits ? ", sink logits" : "");
-  std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s%s)", plan.name(),
-                plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous", tail.c_str());
+  if (ragged)
+    std::snprintf(text, sizeof(text), "%s (grid %u = %u slots x %u K/V heads, row blocks of %u rows x %u heads, %u packed rows of %u sequences, at most %u rows each, %s%s)",
+                  plan.name(), plan.blocks, a.slots, a.Hkv, a.RB, a.G, a.totalRows, a.batches, a.rows, a.paged ? "paged" : "contiguous", tail.c_str());
+  else
+    std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s%s)", plan.name(),
+                  plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous", tail.c_str());
   copy_text(out, capacity, text);
   return MFA_OK;
 }
 
 static mfa_status prefill_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
-                               uint32_t window, const Sinks &sinks, void *stream, int warmup, int iterations, float *milliseconds) {
+                               uint32_t window, const Sinks &sinks, void *stream, int warmup, int iterations, float *milliseconds,
+                               const mfa_ragged_rows *ragged = nullptr) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   PrefillPlan plan;
-  mfa_status st = prepare(params, window, sinks, &plan);
+  mfa_status st = prepare(params, window, sinks, &plan, ragged);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -348,6 +394,73 @@ mfa_status mfa_attention_prefill_sink_tile_range(uint32_t length, uint32_t query
   if (window && !causal) return fail(MFA_ERR_INVALID_ARGUMENT, "a sliding window needs causal");
   if (sinkTokens && !window) return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens must be 0 when window is 0");
   prefill_sink_tile_range(length, queryLength, firstRow, blockRows, causal, window, sinkTokens, begin, unmaskedBegin, unmaskedEnd, end, sinkEnd);
+  return MFA_OK;
+}
+
+// ---- over packed rows (include/mfa_ragged.h): the sink entries with `ragged` after `sinks`; a NULL `sinks` is no sinks
+
+void mfa_ragged_rows_init(mfa_ragged_rows *ragged) {
+  if (ragged) std::memset(ragged, 0, sizeof(*ragged));
+}
+
+size_t mfa_ragged_rows_size(void) { return sizeof(mfa_ragged_rows); }
+
+mfa_status mfa_ragged_rows_offsets(uint32_t *offsets, uint32_t capacity, uint32_t *count) {
+  if (!offsets || !count) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  static const uint32_t table[] = {(uint32_t)offsetof(mfa_ragged_rows, rowStarts), (uint32_t)offsetof(mfa_ragged_rows, totalRows),
+                                   (uint32_t)offsetof(mfa_ragged_rows, reserved)};
+  *count = 3;
+  for (uint32_t i = 0; i < 3 && i < capacity; ++i) offsets[i] = table[i];
+  return MFA_OK;
+}
+
+static mfa_status ragged_of(const mfa_ragged_rows *ragged, const mfa_attention_sinks *block, Sinks *sinks) {
+  if (!ragged)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "null mfa_ragged_rows: the ragged entries require the block (mfa_ragged_rows_init; a padded "
+                                          "launch: the mfa_prefill.h / mfa_window.h / mfa_sink.h entries)");
+  if (block) {
+    sinks->tokens = block->sinkTokens;
+    sinks->logits = block->sinkLogits;
+  }
+  return MFA_OK;
+}
+
+mfa_status mfa_attention_prefill_ragged_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                               uint32_t window, const mfa_attention_sinks *sinks, const mfa_ragged_rows *ragged, void *stream) {
+  Sinks s;
+  const mfa_status st = ragged_of(ragged, sinks, &s);
+  return st != MFA_OK ? st : prefill_launch(q, k, v, o, l, params, window, s, stream, ragged);
+}
+
+mfa_status mfa_attention_prefill_ragged_launch_form(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
+                                                    const mfa_ragged_rows *ragged, char *out, size_t capacity) {
+  if (out && capacity) out[0] = '\0';
+  Sinks s;
+  const mfa_status st = ragged_of(ragged, sinks, &s);
+  return st != MFA_OK ? st : prefill_launch_form(params, window, s, out, capacity, ragged);
+}
+
+mfa_status mfa_attention_prefill_ragged_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                             uint32_t window, const mfa_attention_sinks *sinks, const mfa_ragged_rows *ragged, void *stream,
+                                             int warmup, int iterations, float *milliseconds) {
+  Sinks s;
+  const mfa_status st = ragged_of(ragged, sinks, &s);
+  return st != MFA_OK ? st : prefill_time(q, k, v, o, l, params, window, s, stream, warmup, iterations, milliseconds, ragged);
+}
+
+mfa_status mfa_attention_prefill_ragged_slots(uint32_t totalRows, uint32_t batches, uint32_t rows, uint32_t blockRows, uint64_t *slots) {
+  if (!slots) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (blockRows == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "blockRows must be non-zero");
+  *slots = ragged_slots(totalRows, batches, rows, blockRows);
+  return MFA_OK;
+}
+
+mfa_status mfa_attention_prefill_ragged_block(const uint32_t *rowStarts, uint32_t batches, uint32_t totalRows, uint32_t rows, uint32_t blockRows,
+                                              uint32_t slot, uint32_t *sequence, uint32_t *firstRow) {
+  if (!rowStarts || !sequence || !firstRow) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (blockRows == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "blockRows must be non-zero");
+  uint32_t start, count;
+  prefill_ragged_block(rowStarts, batches, totalRows, rows, blockRows, slot, sequence, firstRow, &start, &count);
   return MFA_OK;
 }
 

@@ -824,3 +824,232 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     else:
         o, l = _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
     return (o, l * 0.6931471805599453) if return_lse else o
+
+
+# ---- ragged batches (include/mfa_ragged.h): packed query rows for prefill and append, one launch for a continuous-batching step
+def _check_row_starts(who, row_starts, cache_lengths, max_rows):
+    if not isinstance(row_starts, torch.Tensor) or not row_starts.is_cuda or row_starts.dim() != 1 or \
+            row_starts.shape[0] != cache_lengths.shape[0] + 1 or row_starts.dtype not in (torch.int32, torch.int64):
+        got = f"{tuple(row_starts.shape)}, {row_starts.dtype}" if isinstance(row_starts, torch.Tensor) else type(row_starts).__name__
+        raise ValueError(f"{who}: row_starts must be a GPU tensor [B + 1] = [{cache_lengths.shape[0] + 1}] int32 or int64: the first packed row "
+                         f"of every sequence and the end of the last (got {got})")
+    if isinstance(max_rows, bool) or not isinstance(max_rows, int) or not 1 <= max_rows < 2 ** 32:
+        raise ValueError(f"{who}: max_rows must be an int from 1 to 2^32 - 1, the largest row count of a sequence (the host never reads "
+                         f"row_starts), not {max_rows!r}")
+
+
+def _packed_operand(t):
+    """a packed [T, heads, D] operand as the kernels read it: any view with a contiguous last dimension and 16-byte rows is taken where
+    it lies (a slice of a fused QKV projection: strides, not a copy)"""
+    ok = t.stride(2) == 1 and all(st >= 0 for st in t.stride()) and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
+    return t if ok else t.contiguous()
+
+
+def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window, sinks):
+    who = "flash_prefill_ragged"
+    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{who}: q must be bfloat16 or float16")
+    if fp8:
+        if k_cache.dtype != v_cache.dtype or k_cache.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"{who}: an FP8 KV cache is torch.float8_e4m3fn for both K and V (got {k_cache.dtype}, {v_cache.dtype}); "
+                            "e5m2 and fnuz caches have no kernel")
+    elif k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise TypeError(f"{who}: q and the caches must share one of bfloat16 / float16 (or the caches are float8_e4m3fn)")
+    elif k_scale is not None or v_scale is not None:
+        raise ValueError(f"{who}: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache holds the values themselves")
+    paged = block_table is not None
+    if q.dim() != 3 or q.shape[0] == 0 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[2] != k_cache.shape[3] or \
+            k_cache.shape[1] == 0 or q.shape[1] % k_cache.shape[1] != 0:
+        raise ValueError(f"{who}: expected q [T, H, D] (packed rows) and caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) with H a "
+                         f"multiple of Hkv (got q {tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)})")
+    T, H, D = q.shape
+    Hkv = k_cache.shape[1]
+    if cache_lengths.dim() != 1 or cache_lengths.dtype not in (torch.int32, torch.int64) or (not paged and cache_lengths.shape[0] != k_cache.shape[0]):
+        raise ValueError(f"{who}: cache_lengths must be a GPU tensor [B] int32 or int64, B the caches' first dimension when they are "
+                         f"contiguous (got {tuple(cache_lengths.shape)}, {cache_lengths.dtype})")
+    B = int(cache_lengths.shape[0])
+    _check_row_starts(who, row_starts, cache_lengths, max_rows)
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
+            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is never copied)")
+    kw = {}
+    if paged:
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
+                not block_table.is_cuda:
+            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
+                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
+        page = int(k_cache.shape[2])
+        column = page * int(block_table.shape[1])
+        kw = dict(pageSize=page, blockTable=block_table, blockTableStride=int(block_table.stride(0)),
+                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
+    else:
+        column = int(k_cache.shape[2])
+    q = _packed_operand(q)
+    lengths, starts = cache_lengths.to(torch.int32), row_starts.to(torch.int32)   # (no copy when they already are; they stay on the device)
+    # (packed rows no sequence owns are not written by the launch: no memset is spent on them, they come back uninitialised)
+    o = torch.empty((T, H, D), dtype=q.dtype, device=q.device)
+    l = torch.empty((H, T), dtype=torch.float32, device=q.device)
+    key = (q.dtype, D, bool(fp8))
+    pre = _PREFILLERS.get(key)
+    if pre is None:
+        pre = _PREFILLERS[key] = AttentionPrefill(D, P.BF16 if q.dtype == torch.bfloat16 else P.FP16,
+                                                  cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
+    if fp8:
+        kw.update(keyScale=_scale_operand(who, "k_scale", k_scale, Hkv, q.device), valueScale=_scale_operand(who, "v_scale", v_scale, Hkv, q.device))
+    kw.update(rows=int(max_rows), column=column, heads=H, batches=B, headsPerKeyValue=H // Hkv, causal=bool(causal), cacheLengths=lengths,
+              rowStarts=starts, totalRows=T,
+              strides=dict(Q=(int(q.stride(0)) if T > 1 else H * D, int(q.stride(1)) if H > 1 else D, 0),
+                           K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
+    if window:
+        kw.update(window=int(window))
+    if sinks is not None and (sinks[0] or sinks[1] is not None):
+        kw.update(sinkTokens=int(sinks[0]), sinkLogits=sinks[1])
+    with torch.cuda.device(q.device):
+        pre.dispatch(q, k_cache, v_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
+    return o, l
+
+
+def _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale):
+    who = "kv_cache_append_ragged"
+    tensors = (k_new, v_new, k_cache, v_cache, cache_lengths)
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    if k_new.dtype not in (torch.bfloat16, torch.float16) or v_new.dtype != k_new.dtype:
+        raise TypeError(f"{who}: k_new and v_new must share one of bfloat16 / float16")
+    if k_cache.dtype != v_cache.dtype or k_cache.dtype not in (k_new.dtype, torch.float8_e4m3fn):
+        raise TypeError(f"{who}: the caches must both be torch.float8_e4m3fn or the new rows' {k_new.dtype} (got {k_cache.dtype}, "
+                        f"{v_cache.dtype}); e5m2 and fnuz caches have no kernel")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError(f"{who}: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache takes the rows' bits")
+    paged = block_table is not None
+    if k_new.dim() != 3 or k_new.shape[0] == 0 or v_new.shape != k_new.shape or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or \
+            k_cache.shape[1] != k_new.shape[1] or k_cache.shape[3] != k_new.shape[2]:
+        raise ValueError(f"{who}: expected k_new, v_new [T, Hkv, D] (packed rows) and caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) "
+                         f"(got {tuple(k_new.shape)}, {tuple(v_new.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
+    T, Hkv, D = k_new.shape
+    if cache_lengths.dim() != 1 or cache_lengths.dtype not in (torch.int32, torch.int64) or (not paged and cache_lengths.shape[0] != k_cache.shape[0]):
+        raise ValueError(f"{who}: cache_lengths must be a GPU tensor [B] int32 or int64, B the caches' first dimension when they are "
+                         f"contiguous (got {tuple(cache_lengths.shape)}, {cache_lengths.dtype})")
+    B = int(cache_lengths.shape[0])
+    _check_row_starts(who, row_starts, cache_lengths, max_rows)
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
+            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is written where it lies)")
+    if paged:
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
+                not block_table.is_cuda:
+            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
+                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
+        block_table = block_table.contiguous()   # (the row stride is the bound on the pages a sequence may name)
+        kw = dict(pageSize=int(k_cache.shape[2]), blockTable=block_table, blockTableStride=int(block_table.shape[1]),
+                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
+    else:
+        kw = dict(column=int(k_cache.shape[2]))
+    news = [_packed_operand(t) for t in (k_new, v_new)]
+    new_strides = lambda t: (int(t.stride(0)) if T > 1 else Hkv * D, int(t.stride(1)) if Hkv > 1 else D, 0)  # noqa: E731
+    key = (k_new.dtype, D, fp8)
+    app = _APPENDERS.get(key)
+    if app is None:
+        app = _APPENDERS[key] = KVCacheAppend(D, P.BF16 if k_new.dtype == torch.bfloat16 else P.FP16, KVCachePrecision.E4M3 if fp8 else None)
+    if fp8:
+        kw.update(keyScale=_scale_operand(who, "k_scale", k_scale, Hkv, k_new.device), valueScale=_scale_operand(who, "v_scale", v_scale, Hkv, k_new.device))
+    with torch.cuda.device(k_new.device):
+        app.dispatch(news[0], news[1], k_cache, v_cache, stream=torch.cuda.current_stream(k_new.device).cuda_stream, rows=int(max_rows),
+                     heads=Hkv, batches=B, cacheLengths=cache_lengths.to(torch.int32), rowStarts=row_starts.to(torch.int32), totalRows=T,
+                     strides=dict(kNew=new_strides(news[0]), vNew=new_strides(news[1]), kCache=_cache_strides(k_cache, paged),
+                                  vCache=_cache_strides(v_cache, paged)), **kw)
+
+
+def _register_ragged_ops():
+    """mfa::attention_prefill_ragged (`window`, `sink_tokens` 0: none) and mfa::kv_cache_append_ragged (include/mfa_ragged.h).  The other
+    ops keep their schemas."""
+    if not hasattr(torch.library, "custom_op"):
+        return False
+    try:
+        torch.ops.mfa.attention_prefill_ragged  # noqa: B018 -- AttributeError when the op is not defined yet
+        torch.ops.mfa.kv_cache_append_ragged  # noqa: B018
+        return True
+    except (AttributeError, RuntimeError):
+        pass
+
+    @torch.library.custom_op("mfa::attention_prefill_ragged", mutates_args=(), device_types="cuda")
+    def _op_prefill_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor, row_starts: torch.Tensor,
+                           max_rows: int, block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
+                           v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
+                           sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        return _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window,
+                                   (sink_tokens, sink_logits))
+
+    @_op_prefill_ragged.register_fake
+    def _op_prefill_ragged_fake(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window,
+                                sink_tokens, sink_logits):
+        T, H, D = q.shape
+        return q.new_empty((T, H, D)), q.new_empty((H, T), dtype=torch.float32)
+
+    @torch.library.custom_op("mfa::kv_cache_append_ragged", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+    def _op_append_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                          row_starts: torch.Tensor, max_rows: int, block_table: Optional[torch.Tensor], k_scale: Optional[torch.Tensor],
+                          v_scale: Optional[torch.Tensor]) -> None:
+        _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale)
+
+    @_op_append_ragged.register_fake
+    def _op_append_ragged_fake(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale):
+        return None
+
+    return True
+
+
+_HAVE_RAGGED_OPS = _register_ragged_ops()
+
+
+def flash_prefill_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor, row_starts: torch.Tensor,
+                         max_rows: int, block_table: Optional[torch.Tensor] = None, causal: bool = True,
+                         k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, return_lse: bool = False,
+                         window: Optional[int] = None, sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None):
+    """flash_prefill for a RAGGED batch (a continuous-batching step: sequences with one new token beside prompt chunks): q [T, H, D]
+    holds the new rows of all B sequences packed along the first axis, row_starts [B + 1] (GPU, int32 / int64, non-decreasing: the
+    engine's cu_seqlens_q / query_start_loc) says where each sequence's rows begin, and max_rows (a host int) is the largest row
+    count of any sequence -- rows of a sequence past it are not served.  q may be any view with a contiguous last dimension, a slice
+    of a fused QKV projection included: it is read where it lies.  Caches, cache_lengths [B], block_table, scales, causal, window,
+    sink_tokens and sink_logits: flash_prefill's.  Returns O [T, H, D], and with return_lse also L [H, T] fp32 in natural units; packed
+    rows that no sequence owns come back uninitialised.  The launch starts no workgroup for row blocks that do not exist and computes,
+    byte for byte, what flash_prefill computes for the same sequences padded to max_rows.  Forward only; goes through the op
+    `mfa::attention_prefill_ragged` where torch has custom ops, so it traces under torch.compile."""
+    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
+        raise RuntimeError("flash_prefill_ragged: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, k_cache, v_cache):
+        if t.requires_grad:
+            raise RuntimeError("flash_prefill_ragged is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
+    if window is not None or sink_tokens is not None or sink_logits is not None:
+        # (_check_sinks reads the heads off a [B, H, R, D] query: the packed q as such a view)
+        _check_sinks("flash_prefill_ragged", q.unsqueeze(0).transpose(1, 2) if q.dim() == 3 else q, window, causal, sink_tokens, sink_logits)
+    if _HAVE_RAGGED_OPS:
+        o, l = torch.ops.mfa.attention_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale,
+                                                      v_scale, window or 0, sink_tokens or 0, sink_logits)
+    else:
+        o, l = _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale,
+                                   window or 0, (sink_tokens or 0, sink_logits))
+    return (o, l * 0.6931471805599453) if return_lse else o
+
+
+def kv_cache_append_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                           row_starts: torch.Tensor, max_rows: int, block_table: Optional[torch.Tensor] = None,
+                           k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> None:
+    """kv_cache_append for a RAGGED batch, in ONE launch: k_new, v_new [T, Hkv, D] hold the new rows of all B sequences packed along
+    the first axis (any view with a contiguous last dimension: the K and V slices of a fused QKV projection are read where they lie),
+    row_starts [B + 1] and max_rows as flash_prefill_ragged's.  Row r of sequence b, which has qn_b = row_starts[b + 1] - row_starts[b]
+    rows, goes to key cache_lengths[b] - qn_b + r (cache_lengths ALREADY INCLUDES the new tokens); kv_cache_append's drop rules, caches,
+    quantisation and scales.  Goes through the op `mfa::kv_cache_append_ragged` (mutates_args) where torch has custom ops."""
+    for t in (k_new, v_new, k_cache, v_cache):
+        if t.requires_grad:
+            raise RuntimeError("kv_cache_append_ragged writes in place and has no autograd: detach the inputs")
+    if not all(t.is_cuda for t in (k_new, v_new, k_cache, v_cache, cache_lengths)):
+        raise RuntimeError("kv_cache_append_ragged: tensors must live on the GPU (there is no CPU path)")
+    if _HAVE_RAGGED_OPS:
+        torch.ops.mfa.kv_cache_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale)
+    else:
+        _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale)
