@@ -427,9 +427,31 @@ def _ragged_block(shape):
     return block, starts
 
 
-def _extended(shape) -> bool:
-    """whether a launch's keywords ask for the window or sink entries"""
-    return any(shape.get(name) is not None for name in ("window", "sinkTokens", "sinkLogits"))
+def _pointers(*buffers):
+    return tuple(_pointer(b) for b in buffers)
+
+
+def _packed(seq, heads, D):
+    """(leadingDimension, headStride, batchStride) of a packed [batch][head][row or key][D] operand"""
+    return D, int(seq) * D, int(heads) * int(seq) * D
+
+
+def _packed_rows(heads, D):
+    """the same of a ragged batch's packed [row][head][D] operand (include/mfa_ragged.h): no batch axis"""
+    return int(heads) * D, D, 0
+
+
+def _fill_shared(p, D, packed, *, rows, column, heads, batches, cacheLengths, pageSize, blockTable, blockTableStride, strides, pageStrides):
+    """the fields mfa_decode_params, mfa_prefill_params and mfa_kv_append_params share.  `packed`: operand name -> the strides of an
+    operand left out of `strides`, in the order of the struct's arrays"""
+    p.rows, p.column, p.heads, p.batches, p.headDimension = int(rows), int(column), int(heads), int(batches), D
+    p.pageSize, p.cacheLengths = int(pageSize), _pointer(cacheLengths)
+    p.blockTable, p.blockTableStride = _pointer(blockTable), int(blockTableStride)
+    for i, (name, default) in enumerate(packed.items()):
+        ld, hs, bs = (strides or {}).get(name, default)
+        p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
+    if pageStrides is not None:
+        p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
 
 
 class AttentionDecode:
@@ -461,41 +483,21 @@ class AttentionDecode:
         self.outputPrecision = self.precision if outputPrecision is None else GEMMOperandPrecision(outputPrecision)
 
     def _quant(self, shape):
-        """the mfa_kv_quant block of the window entries: none for a 16-bit cache"""
+        """the mfa_kv_quant block of a launch: none for a 16-bit cache"""
         return None, None
 
-    def _window(self, entry, window, shape, *head, tail=(), sinks=None):
-        """one of the four mfa_attention_decode_window_* entries: `head` arguments, params, quant, window, `tail` arguments; with a
-        `sinks` block the mfa_attention_decode_sink_* entry of the same name, which takes it after the window (None there: 0)"""
-        quant, _scales = self._quant(shape)
-        p, _keep = self._params(**shape)
-        q = None if quant is None else ctypes.byref(quant)
-        if sinks is not None:
-            check(getattr(lib(), "mfa_attention_decode_sink_" + entry)(*head, ctypes.byref(p), q, int(window or 0), ctypes.byref(sinks[0]), *tail))
-        else:
-            check(getattr(lib(), "mfa_attention_decode_window_" + entry)(*head, ctypes.byref(p), q, int(window), *tail))
-
     def _params(self, *, rows: int, column: int, heads: int = 1, batches: int = 1, headsPerKeyValue: int = 1, causal: bool = True,
-                cacheLengths=None, pageSize: int = 0, blockTable=None, blockTableStride: int = 0, strides: Optional[Mapping] = None,
-                pageStrides: Optional[Sequence[int]] = None, lStrides: Optional[Sequence[int]] = None, workspace=None,
-                workspaceBytes: Optional[int] = None):
+                lStrides: Optional[Sequence[int]] = None, workspace=None, workspaceBytes: Optional[int] = None, cacheLengths=None,
+                pageSize: int = 0, blockTable=None, blockTableStride: int = 0, strides: Optional[Mapping] = None,
+                pageStrides: Optional[Sequence[int]] = None):
         p = _abi.mfa_decode_params()
         lib().mfa_decode_params_init(ctypes.byref(p))
-        p.rows, p.column, p.heads, p.batches = int(rows), int(column), int(heads), int(batches)
+        D = self.headDimension
+        new, cache = _packed(rows, heads, D), _packed(column, max(1, int(heads) // max(1, int(headsPerKeyValue))), D)
+        _fill_shared(p, D, dict(zip(self.OPERANDS, (new, cache, cache, new))), rows=rows, column=column, heads=heads, batches=batches, cacheLengths=cacheLengths,
+                     pageSize=pageSize, blockTable=blockTable, blockTableStride=blockTableStride, strides=strides, pageStrides=pageStrides)
         p.headsPerKeyValue, p.causal = int(headsPerKeyValue), int(bool(causal))
-        p.headDimension, p.precision, p.outputPrecision = self.headDimension, int(self.precision), int(self.outputPrecision)
-        p.pageSize = int(pageSize)
-        p.cacheLengths = _pointer(cacheLengths)
-        p.blockTable = _pointer(blockTable)
-        p.blockTableStride = int(blockTableStride)
-        D, G = self.headDimension, max(1, int(headsPerKeyValue))
-        kvHeads = max(1, int(heads) // G)
-        for i, name in enumerate(self.OPERANDS):
-            seq, h = (int(rows), int(heads)) if name in ("Q", "O") else (int(column), kvHeads)
-            ld, hs, bs = (strides or {}).get(name, (D, seq * D, h * seq * D))
-            p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
-        if pageStrides is not None:
-            p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
+        p.precision, p.outputPrecision = int(self.precision), int(self.outputPrecision)
         p.lHeadStride, p.lBatchStride = (int(lStrides[0]), int(lStrides[1])) if lStrides is not None else (int(rows), int(heads) * int(rows))
         p.workspace = _pointer(workspace)
         if workspaceBytes is None:
@@ -503,50 +505,43 @@ class AttentionDecode:
         p.workspaceBytes = int(workspaceBytes)
         return p, (cacheLengths, blockTable, workspace)
 
+    def _call(self, suffix, shape, head=(), tail=()):
+        """mfa_attention_decode_<family><suffix>(*head, params, <the family's own arguments>, *tail).  The family, from the keywords:
+        sink_ (quant, window, sinks) with either sink keyword, else window_ (quant, window) with a window that is not None, else fp8_
+        (quant) over an e4m3 cache, else the plain entries"""
+        window, sinks = shape.pop("window", None), _sinks_block(shape)
+        quant, _scales = self._quant(shape)
+        p, _keep = self._params(**shape)
+        q = None if quant is None else ctypes.byref(quant)
+        if sinks is not None:
+            family, own = "sink_", (q, int(window or 0), ctypes.byref(sinks[0]))
+        elif window is not None:
+            family, own = "window_", (q, int(window))
+        else:
+            family, own = ("", ()) if quant is None else ("fp8_", (q,))
+        check(getattr(lib(), "mfa_attention_decode_" + family + suffix)(*head, ctypes.byref(p), *own, *tail))
+
     def workspaceSize(self, **shape) -> int:
         """Bytes a launch of this shape wants to be cut along the keys (0: the plan has one piece).  Without a workspace the launch
         runs unsplit in one kernel."""
-        window, sinks = shape.pop("window", None), _sinks_block(shape)
         out = ctypes.c_uint64(0)
-        if window is not None or sinks is not None:
-            self._window("workspace_size", window, shape, tail=(ctypes.byref(out),), sinks=sinks)
-            return int(out.value)
-        p, _keep = self._params(**shape)
-        check(lib().mfa_attention_decode_workspace_size(ctypes.byref(p), ctypes.byref(out)))
+        self._call("workspace_size", shape, tail=(ctypes.byref(out),))
         return int(out.value)
 
     def launchForm(self, **shape) -> str:
         """What `dispatch` with the same arguments would run (nothing is launched): the pieces kernel, the piece count and the combine
         kernel, or the single kernel."""
-        window, sinks = shape.pop("window", None), _sinks_block(shape)
         out = ctypes.create_string_buffer(512)
-        if window is not None or sinks is not None:
-            self._window("launch_form", window, shape, tail=(out, len(out)), sinks=sinks)
-            return out.value.decode()
-        p, _keep = self._params(**shape)
-        check(lib().mfa_attention_decode_launch_form(ctypes.byref(p), out, len(out)))
+        self._call("launch_form", shape, tail=(out, len(out)))
         return out.value.decode()
 
     def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
-        window, sinks = shape.pop("window", None), _sinks_block(shape)
-        if window is not None or sinks is not None:
-            return self._window("launch", window, shape, _pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l),
-                                tail=(ctypes.c_void_p(stream or 0),), sinks=sinks)
-        p, _keep = self._params(**shape)
-        check(lib().mfa_attention_decode_launch(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
-                                                ctypes.c_void_p(stream or 0)))
+        self._call("launch", shape, _pointers(q, k, v, o, l), (ctypes.c_void_p(stream or 0),))
 
     def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
         """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
-        window, sinks = shape.pop("window", None), _sinks_block(shape)
         ms = ctypes.c_float(0.0)
-        if window is not None or sinks is not None:
-            self._window("time", window, shape, _pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l),
-                         tail=(ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)), sinks=sinks)
-            return float(ms.value)
-        p, _keep = self._params(**shape)
-        check(lib().mfa_attention_decode_time(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
-                                              ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
+        self._call("time", shape, _pointers(q, k, v, o, l), (ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
         return float(ms.value)
 
     @staticmethod
@@ -598,51 +593,6 @@ class AttentionDecodeFP8(AttentionDecode):
         quant.keyScale, quant.valueScale = _pointer(keep[0]), _pointer(keep[1])
         return quant, keep
 
-    def workspaceSize(self, **shape) -> int:
-        if _extended(shape):
-            return super().workspaceSize(**shape)
-        for name in ("window", "sinkTokens", "sinkLogits"):
-            shape.pop(name, None)
-        quant, _scales = self._quant(shape)
-        p, _keep = self._params(**shape)
-        out = ctypes.c_uint64(0)
-        check(lib().mfa_attention_decode_fp8_workspace_size(ctypes.byref(p), ctypes.byref(quant), ctypes.byref(out)))
-        return int(out.value)
-
-    def launchForm(self, **shape) -> str:
-        if _extended(shape):
-            return super().launchForm(**shape)
-        for name in ("window", "sinkTokens", "sinkLogits"):
-            shape.pop(name, None)
-        quant, _scales = self._quant(shape)
-        p, _keep = self._params(**shape)
-        out = ctypes.create_string_buffer(512)
-        check(lib().mfa_attention_decode_fp8_launch_form(ctypes.byref(p), ctypes.byref(quant), out, len(out)))
-        return out.value.decode()
-
-    def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
-        if _extended(shape):
-            return super().dispatch(q, k, v, o, l, stream=stream, **shape)
-        for name in ("window", "sinkTokens", "sinkLogits"):
-            shape.pop(name, None)
-        quant, _scales = self._quant(shape)
-        p, _keep = self._params(**shape)
-        check(lib().mfa_attention_decode_fp8_launch(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
-                                                    ctypes.byref(quant), ctypes.c_void_p(stream or 0)))
-
-    def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
-        if _extended(shape):
-            return super().time(q, k, v, o, l, stream=stream, warmup=warmup, iterations=iterations, **shape)
-        for name in ("window", "sinkTokens", "sinkLogits"):
-            shape.pop(name, None)
-        quant, _scales = self._quant(shape)
-        p, _keep = self._params(**shape)
-        ms = ctypes.c_float(0.0)
-        check(lib().mfa_attention_decode_fp8_time(_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l), ctypes.byref(p),
-                                                  ctypes.byref(quant), ctypes.c_void_p(stream or 0), int(warmup), int(iterations),
-                                                  ctypes.byref(ms)))
-        return float(ms.value)
-
 
 class AttentionPrefill:
     """Prefill attention over a KV cache (include/mfa_prefill.h): a block of up to `rows` new query rows per sequence -- longer than a
@@ -675,29 +625,21 @@ class AttentionPrefill:
         self.cachePrecision = int(self.precision) if cachePrecision is None else int(cachePrecision)
 
     def _params(self, *, rows: int, column: int, heads: int = 1, batches: int = 1, headsPerKeyValue: int = 1, causal: bool = True,
-                cacheLengths=None, queryLengths=None, pageSize: int = 0, blockTable=None, blockTableStride: int = 0,
-                strides: Optional[Mapping] = None, pageStrides: Optional[Sequence[int]] = None, lStrides: Optional[Sequence[int]] = None,
-                keyScale=None, valueScale=None, ragged=None):
+                queryLengths=None, lStrides: Optional[Sequence[int]] = None, keyScale=None, valueScale=None, ragged=None, cacheLengths=None,
+                pageSize: int = 0, blockTable=None, blockTableStride: int = 0, strides: Optional[Mapping] = None,
+                pageStrides: Optional[Sequence[int]] = None):
         p = _abi.mfa_prefill_params()
         lib().mfa_prefill_params_init(ctypes.byref(p))
-        p.rows, p.column, p.heads, p.batches = int(rows), int(column), int(heads), int(batches)
+        D, kvHeads = self.headDimension, max(1, int(heads) // max(1, int(headsPerKeyValue)))
+        new, cache = _packed_rows(heads, D) if ragged else _packed(rows, heads, D), _packed(int(pageSize) or column, kvHeads, D)
+        if pageStrides is None and pageSize:
+            pageStrides = (kvHeads * int(pageSize) * D,) * 2
+        _fill_shared(p, D, dict(zip(self.OPERANDS, (new, cache, cache, new))), rows=rows, column=column, heads=heads, batches=batches,
+                     cacheLengths=cacheLengths, pageSize=pageSize, blockTable=blockTable, blockTableStride=blockTableStride, strides=strides,
+                     pageStrides=pageStrides)
         p.headsPerKeyValue, p.causal = int(headsPerKeyValue), int(bool(causal))
-        p.headDimension, p.precision, p.outputPrecision = self.headDimension, int(self.precision), int(self.outputPrecision)
-        p.cachePrecision = self.cachePrecision
-        p.pageSize = int(pageSize)
-        p.cacheLengths, p.queryLengths = _pointer(cacheLengths), _pointer(queryLengths)
-        p.blockTable, p.blockTableStride = _pointer(blockTable), int(blockTableStride)
-        D, G = self.headDimension, max(1, int(headsPerKeyValue))
-        kvHeads = max(1, int(heads) // G)
-        for i, name in enumerate(self.OPERANDS):
-            seq, h = (int(rows), int(heads)) if name in ("Q", "O") else (int(pageSize) or int(column), kvHeads)
-            packed = (int(heads) * D, D, 0) if ragged and name in ("Q", "O") else (D, seq * D, h * seq * D)
-            ld, hs, bs = (strides or {}).get(name, packed)
-            p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
-        if pageStrides is not None:
-            p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
-        elif pageSize:
-            p.pageStride[0] = p.pageStride[1] = kvHeads * int(pageSize) * D
+        p.precision, p.outputPrecision, p.cachePrecision = int(self.precision), int(self.outputPrecision), self.cachePrecision
+        p.queryLengths = _pointer(queryLengths)
         if lStrides is not None:
             p.lHeadStride, p.lBatchStride = int(lStrides[0]), int(lStrides[1])
         elif ragged:
@@ -707,57 +649,34 @@ class AttentionPrefill:
         p.keyScale, p.valueScale = _pointer(keyScale), _pointer(valueScale)
         return p, (cacheLengths, queryLengths, blockTable, keyScale, valueScale)
 
-    @staticmethod
-    def _sinks_pointer(sinks):
-        return ctypes.byref(sinks[0]) if sinks is not None else None
+    def _call(self, suffix, shape, head=(), tail=()):
+        """mfa_attention_prefill_<family><suffix>(*head, params, <the family's own arguments>, *tail).  The family, from the keywords:
+        ragged_ (window, sinks or NULL, ragged) with rowStarts / totalRows whichever window and sinks, else sink_ (window, sinks) with
+        either sink keyword, else window_ (window) with a window that is not None, else the plain entries"""
+        window, sinks, ragged = shape.pop("window", None), _sinks_block(shape), _ragged_block(shape)
+        p, _keep = self._params(ragged=ragged, **shape)
+        s = None if sinks is None else ctypes.byref(sinks[0])
+        if ragged is not None:
+            family, own = "ragged_", (int(window or 0), s, ctypes.byref(ragged[0]))
+        elif sinks is not None:
+            family, own = "sink_", (int(window or 0), s)
+        else:
+            family, own = ("", ()) if window is None else ("window_", (int(window),))
+        check(getattr(lib(), "mfa_attention_prefill_" + family + suffix)(*head, ctypes.byref(p), *own, *tail))
 
     def launchForm(self, **shape) -> str:
         """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name and the grid."""
-        window, sinks, ragged = shape.pop("window", None), _sinks_block(shape), _ragged_block(shape)
-        p, _keep = self._params(ragged=ragged, **shape)
         out = ctypes.create_string_buffer(512)
-        if ragged is not None:
-            check(lib().mfa_attention_prefill_ragged_launch_form(ctypes.byref(p), int(window or 0), self._sinks_pointer(sinks),
-                                                                 ctypes.byref(ragged[0]), out, len(out)))
-        elif sinks is not None:
-            check(lib().mfa_attention_prefill_sink_launch_form(ctypes.byref(p), int(window or 0), ctypes.byref(sinks[0]), out, len(out)))
-        elif window is not None:
-            check(lib().mfa_attention_prefill_window_launch_form(ctypes.byref(p), int(window), out, len(out)))
-        else:
-            check(lib().mfa_attention_prefill_launch_form(ctypes.byref(p), out, len(out)))
+        self._call("launch_form", shape, tail=(out, len(out)))
         return out.value.decode()
 
     def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
-        window, sinks, ragged = shape.pop("window", None), _sinks_block(shape), _ragged_block(shape)
-        p, _keep = self._params(ragged=ragged, **shape)
-        bufs = (_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l))
-        if ragged is not None:
-            check(lib().mfa_attention_prefill_ragged_launch(*bufs, ctypes.byref(p), int(window or 0), self._sinks_pointer(sinks),
-                                                            ctypes.byref(ragged[0]), ctypes.c_void_p(stream or 0)))
-        elif sinks is not None:
-            check(lib().mfa_attention_prefill_sink_launch(*bufs, ctypes.byref(p), int(window or 0), ctypes.byref(sinks[0]),
-                                                          ctypes.c_void_p(stream or 0)))
-        elif window is not None:
-            check(lib().mfa_attention_prefill_window_launch(*bufs, ctypes.byref(p), int(window), ctypes.c_void_p(stream or 0)))
-        else:
-            check(lib().mfa_attention_prefill_launch(*bufs, ctypes.byref(p), ctypes.c_void_p(stream or 0)))
+        self._call("launch", shape, _pointers(q, k, v, o, l), (ctypes.c_void_p(stream or 0),))
 
     def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
         """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
-        window, sinks, ragged = shape.pop("window", None), _sinks_block(shape), _ragged_block(shape)
-        p, _keep = self._params(ragged=ragged, **shape)
         ms = ctypes.c_float(0.0)
-        bufs = (_pointer(q), _pointer(k), _pointer(v), _pointer(o), _pointer(l))
-        timing = (ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms))
-        if ragged is not None:
-            check(lib().mfa_attention_prefill_ragged_time(*bufs, ctypes.byref(p), int(window or 0), self._sinks_pointer(sinks),
-                                                          ctypes.byref(ragged[0]), *timing))
-        elif sinks is not None:
-            check(lib().mfa_attention_prefill_sink_time(*bufs, ctypes.byref(p), int(window or 0), ctypes.byref(sinks[0]), *timing))
-        elif window is not None:
-            check(lib().mfa_attention_prefill_window_time(*bufs, ctypes.byref(p), int(window), *timing))
-        else:
-            check(lib().mfa_attention_prefill_time(*bufs, ctypes.byref(p), *timing))
+        self._call("time", shape, _pointers(q, k, v, o, l), (ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
         return float(ms.value)
 
     @staticmethod
@@ -830,35 +749,28 @@ class KVCacheAppend:
         self.precision = GEMMOperandPrecision(precision)
         self.cachePrecision = int(self.precision) if cachePrecision is None else int(cachePrecision)
 
-    def _params(self, *, rows: int, heads: int, batches: int = 1, column: int = 0, cacheLengths=None, pageSize: int = 0, blockTable=None,
-                blockTableStride: int = 0, strides: Optional[Mapping] = None, pageStrides: Optional[Sequence[int]] = None,
-                keyScale=None, valueScale=None, ragged=None):
+    def _params(self, *, rows: int, heads: int, batches: int = 1, column: int = 0, keyScale=None, valueScale=None, ragged=None,
+                cacheLengths=None, pageSize: int = 0, blockTable=None, blockTableStride: int = 0, strides: Optional[Mapping] = None,
+                pageStrides: Optional[Sequence[int]] = None):
         p = _abi.mfa_kv_append_params()
         lib().mfa_kv_append_params_init(ctypes.byref(p))
-        p.rows, p.heads, p.batches, p.column = int(rows), int(heads), int(batches), int(column)
-        p.headDimension, p.precision, p.cachePrecision = self.headDimension, int(self.precision), self.cachePrecision
-        p.pageSize = int(pageSize)
-        p.cacheLengths, p.blockTable, p.blockTableStride = _pointer(cacheLengths), _pointer(blockTable), int(blockTableStride)
         D = self.headDimension
-        for i, name in enumerate(self.OPERANDS):
-            seq = int(rows) if i < 2 else (int(pageSize) or int(column))
-            packed = (int(heads) * D, D, 0) if ragged and i < 2 else (D, seq * D, int(heads) * seq * D)
-            ld, hs, bs = (strides or {}).get(name, packed)
-            p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
-        if pageStrides is not None:
-            p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
+        new, cache = _packed_rows(heads, D) if ragged else _packed(rows, heads, D), _packed(int(pageSize) or column, heads, D)
+        _fill_shared(p, D, dict(zip(self.OPERANDS, (new, new, cache, cache))), rows=rows, column=column, heads=heads, batches=batches,
+                     cacheLengths=cacheLengths, pageSize=pageSize, blockTable=blockTable, blockTableStride=blockTableStride, strides=strides,
+                     pageStrides=pageStrides)
+        p.precision, p.cachePrecision = int(self.precision), self.cachePrecision
         p.keyScale, p.valueScale = _pointer(keyScale), _pointer(valueScale)
         return p
 
     def dispatch(self, kNew, vNew, kCache, vCache, *, stream: Optional[int] = None, **shape) -> None:
+        """mfa_kv_cache_append_launch, or with rowStarts / totalRows mfa_kv_cache_append_ragged_launch, which takes the ragged block
+        after the params"""
         ragged = _ragged_block(shape)
         p = self._params(ragged=ragged, **shape)
-        if ragged is not None:
-            check(lib().mfa_kv_cache_append_ragged_launch(_pointer(kNew), _pointer(vNew), _pointer(kCache), _pointer(vCache), ctypes.byref(p),
-                                                          ctypes.byref(ragged[0]), ctypes.c_void_p(stream or 0)))
-            return
-        check(lib().mfa_kv_cache_append_launch(_pointer(kNew), _pointer(vNew), _pointer(kCache), _pointer(vCache), ctypes.byref(p),
-                                               ctypes.c_void_p(stream or 0)))
+        family, own = ("", ()) if ragged is None else ("ragged_", (ctypes.byref(ragged[0]),))
+        check(getattr(lib(), "mfa_kv_cache_append_" + family + "launch")(*_pointers(kNew, vNew, kCache, vCache), ctypes.byref(p), *own,
+                                                                         ctypes.c_void_p(stream or 0)))
 
 
 def quantizeE4M3(x: float, scale: float = 1.0) -> int:

@@ -1,9 +1,10 @@
 // attn_decode16.hip -- decode attention over a KV cache, 16-bit or FP8 (e4m3): the kernels' code objects, the C ABI of
 // include/mfa_decode.h, the decode entries of include/mfa_kvcache.h and those of include/mfa_window.h (a sliding window: the same
 // plan with the piece count taken from the tiles a window can span, and the attn_decode16w_* / attn_decode8w_* kernels) and those of
-// include/mfa_sink.h (attention sinks: the window's plan plus the sink tiles, and the attn_decode16s_* / attn_decode8s_* kernels).  One plan serves both: the launch over an e4m3 cache adds its
-// own checks in front of the 16-bit launch's, starts the attn_decode8_* kernels in place of _single / _pieces, and shares the piece
-// count, the workspace formula and the combine kernel.
+// include/mfa_sink.h (attention sinks: the window's plan plus the sink tiles, and the attn_decode16s_* / attn_decode8s_* kernels).  One
+// plan serves both: the launch over an e4m3 cache adds its own checks in front of the 16-bit launch's, starts the attn_decode8_*
+// kernels in place of _single / _pieces, and shares the piece count, the workspace formula and the combine kernel.  The refusals of a
+// window and of sinks, and the Sinks of a launch, are cache_launch.h's, shared with attn_prefill16.hip.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
 
@@ -114,13 +115,6 @@ uint64_t planned_tiles(uint32_t column, uint32_t rows, uint32_t window, uint32_t
   return spanned < tiles ? spanned : tiles;
 }
 
-// the sinks of a launch: none for the entries of the other headers
-struct Sinks {
-  uint32_t tokens = 0;
-  const float *logits = nullptr;
-  bool any() const { return tokens != 0 || logits != nullptr; }
-};
-
 uint32_t choose_pieces(uint64_t blocks, uint64_t tiles) {
   if (blocks >= MFA_DECODE_WORKGROUP_TARGET) return 1;
   uint64_t s = MFA_DECODE_WORKGROUP_TARGET / blocks;
@@ -152,16 +146,8 @@ struct DecodePlan {
 // 16-bit cache; an e4m3 cache puts its own checks first, then the 16-bit launch's.  `window` 0: none; `sinks`: include/mfa_sink.h
 mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, DecodePlan *plan) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  if (sinks.tokens && !window)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens = " + std::to_string(sinks.tokens) +
-                                              " keeps the first keys visible under a sliding window, and window is 0 (every key below "
-                                              "the frontier is visible already)");
-  if (sinks.tokens && !p->causal)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need causal: sinkTokens = " + std::to_string(sinks.tokens) +
-                                              " extends a sliding window, which ends at a row's causal frontier");
-  if (window && !p->causal)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "a sliding window needs causal: the window is the " + std::to_string(window) +
-                                              " keys that end at a row's causal frontier (window 0: no window)");
+  const mfa_status allowed = check_window_and_sinks(window, sinks, p->causal != 0);
+  if (allowed != MFA_OK) return allowed;
   if (quant) {
     bool e4m3;
     const mfa_status st = check_cache_precision(quant->cachePrecision, &e4m3);
@@ -461,15 +447,6 @@ mfa_status mfa_attention_sinks_offsets(uint32_t *offsets, uint32_t capacity, uin
   const uint32_t total = (uint32_t)(sizeof(table) / sizeof(table[0]));
   *count = total;
   for (uint32_t i = 0; i < total && i < capacity; ++i) offsets[i] = table[i];
-  return MFA_OK;
-}
-
-static mfa_status sinks_of(const mfa_attention_sinks *block, Sinks *sinks) {
-  if (!block)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "null mfa_attention_sinks: the sink entries require the block (mfa_attention_sinks_init; a launch "
-                                          "without sinks: the mfa_window.h entries, or an all-zero block)");
-  sinks->tokens = block->sinkTokens;
-  sinks->logits = block->sinkLogits;
   return MFA_OK;
 }
 

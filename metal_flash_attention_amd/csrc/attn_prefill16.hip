@@ -1,6 +1,7 @@
 // attn_prefill16.hip -- prefill attention over a KV cache: the kernels' code objects, the C ABI of include/mfa_prefill.h and the prefill
 // entries of include/mfa_window.h (a sliding window: the same checks and grid, the attn_prefill16w_* kernels) and of include/mfa_sink.h
 // (attention sinks: the attn_prefill16s_* kernels), and the prefill entries of include/mfa_ragged.h (packed rows: attn_prefill16r_*).
+// The refusals of a window and of sinks, and the Sinks of a launch, are cache_launch.h's, shared with attn_decode16.hip.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
 
@@ -83,13 +84,6 @@ uint64_t ragged_slots(uint32_t totalRows, uint32_t batches, uint32_t rows, uint3
   return tight < padded ? tight : padded;
 }
 
-// the sinks of a launch: none for the entries of the other headers
-struct Sinks {
-  uint32_t tokens = 0;
-  const float *logits = nullptr;
-  bool any() const { return tokens != 0 || logits != nullptr; }
-};
-
 struct PrefillPlan {
   PrefillArgs args;
   const PrefillSet *set;
@@ -116,16 +110,8 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &si
     if (p->lBatchStride != 0)
       return fail(MFA_ERR_INVALID_ARGUMENT, "lBatchStride must be 0 for a ragged launch: the packed L [heads][totalRows] has no batch axis");
   }
-  if (sinks.tokens && !window)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens = " + std::to_string(sinks.tokens) +
-                                              " keeps the first keys visible under a sliding window, and window is 0 (every key below "
-                                              "the frontier is visible already)");
-  if (sinks.tokens && !p->causal)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need causal: sinkTokens = " + std::to_string(sinks.tokens) +
-                                              " extends a sliding window, which ends at a row's causal frontier");
-  if (window && !p->causal)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "a sliding window needs causal: the window is the " + std::to_string(window) +
-                                              " keys that end at a row's causal frontier (window 0: no window)");
+  const mfa_status allowed = check_window_and_sinks(window, sinks, p->causal != 0);
+  if (allowed != MFA_OK) return allowed;
   if (p->precision == MFA_FP32)
     return fail(MFA_ERR_UNSUPPORTED, "prefill attention takes a 16-bit Q (precision MFA_BF16 or MFA_FP16); FP32 Q has no kernel");
   if (p->precision != MFA_BF16 && p->precision != MFA_FP16) return fail(MFA_ERR_INVALID_ARGUMENT, "precision must be MFA_FP16 or MFA_BF16");
@@ -354,15 +340,6 @@ mfa_status mfa_attention_prefill_window_tile_range(uint32_t length, uint32_t que
 // ---- with attention sinks (include/mfa_sink.h): the window entries with `sinks` after `window`.  The block is required; an all-zero
 // one is the window launch, whichever window
 
-static mfa_status sinks_of(const mfa_attention_sinks *block, Sinks *sinks) {
-  if (!block)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "null mfa_attention_sinks: the sink entries require the block (mfa_attention_sinks_init; a launch "
-                                          "without sinks: the mfa_window.h entries, or an all-zero block)");
-  sinks->tokens = block->sinkTokens;
-  sinks->logits = block->sinkLogits;
-  return MFA_OK;
-}
-
 mfa_status mfa_attention_prefill_sink_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                              uint32_t window, const mfa_attention_sinks *sinks, void *stream) {
   Sinks s;
@@ -418,11 +395,7 @@ static mfa_status ragged_of(const mfa_ragged_rows *ragged, const mfa_attention_s
   if (!ragged)
     return fail(MFA_ERR_INVALID_ARGUMENT, "null mfa_ragged_rows: the ragged entries require the block (mfa_ragged_rows_init; a padded "
                                           "launch: the mfa_prefill.h / mfa_window.h / mfa_sink.h entries)");
-  if (block) {
-    sinks->tokens = block->sinkTokens;
-    sinks->logits = block->sinkLogits;
-  }
-  return MFA_OK;
+  return block ? sinks_of(block, sinks) : MFA_OK;
 }
 
 mfa_status mfa_attention_prefill_ragged_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,

@@ -68,4 +68,27 @@ mfa_status check_float_arrays(std::initializer_list<const void *> arrays, const 
   return MFA_OK;
 }
 
+mfa_status sinks_of(const mfa_attention_sinks *block, Sinks *sinks) {
+  if (!block)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "null mfa_attention_sinks: the sink entries require the block (mfa_attention_sinks_init; a launch "
+                                          "without sinks: the mfa_window.h entries, or an all-zero block)");
+  sinks->tokens = block->sinkTokens;
+  sinks->logits = block->sinkLogits;
+  return MFA_OK;
+}
+
+mfa_status check_window_and_sinks(uint32_t window, const Sinks &sinks, bool causal) {
+  if (sinks.tokens && !window)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens = " + std::to_string(sinks.tokens) +
+                                              " keeps the first keys visible under a sliding window, and window is 0 (every key below "
+                                              "the frontier is visible already)");
+  if (sinks.tokens && !causal)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need causal: sinkTokens = " + std::to_string(sinks.tokens) +
+                                              " extends a sliding window, which ends at a row's causal frontier");
+  if (window && !causal)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "a sliding window needs causal: the window is the " + std::to_string(window) +
+                                              " keys that end at a row's causal frontier (window 0: no window)");
+  return MFA_OK;
+}
+
 } // namespace mfa

@@ -1,13 +1,14 @@
 // cache_launch.h -- what the host sides of the launches over a KV cache share (attn_decode16.hip, attn_prefill16.hip,
-// kv_cache_append.hip): the checks of paging, operand strides, cache precision and buffer pointers, each with ONE wording, so that the
-// same mistake is refused in the same words whichever launch meets it.  hip_fail, copy_text and time_launches also serve
-// mfa_kernel.hip.  Internal, not part of the ABI.  Every check records its message (fail, mfa_internal.h) and returns the status.
+// kv_cache_append.hip): the checks of paging, operand strides, cache precision and buffer pointers, and of a sliding window and
+// attention sinks (Sinks, sinks_of, check_window_and_sinks: decode and prefill), each with ONE wording, so that the same mistake is
+// refused in the same words whichever launch meets it.  hip_fail, copy_text and time_launches also serve mfa_kernel.hip.  Internal, not part of the ABI.  Every check records its message (fail, mfa_internal.h) and returns the status.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <initializer_list>
 
+#include "../../include/mfa_sink.h"
 #include "mfa_internal.h"
 
 namespace mfa {
@@ -36,6 +37,17 @@ mfa_status check_cache_precision(uint32_t cachePrecision, bool *fp8);
 mfa_status check_buffers(std::initializer_list<const void *> buffers, const char *names);
 // optional FP32 arrays: null or 4-byte aligned
 mfa_status check_float_arrays(std::initializer_list<const void *> arrays, const char *names);
+
+// the sinks of a launch (include/mfa_sink.h): none for the entries of the other headers
+struct Sinks {
+  uint32_t tokens = 0;
+  const float *logits = nullptr;
+  bool any() const { return tokens != 0 || logits != nullptr; }
+};
+// the block of a sink entry, which requires it (null is refused)
+mfa_status sinks_of(const mfa_attention_sinks *block, Sinks *sinks);
+// sink tokens need a window and causal; a window (0: none) needs causal
+mfa_status check_window_and_sinks(uint32_t window, const Sinks &sinks, bool causal);
 
 // Times `iterations` calls of run(stream) between two events, after `warmup` untimed ones; nothing more is started after a call that
 // failed.  `name` is the kernel a HIP failure is reported under.

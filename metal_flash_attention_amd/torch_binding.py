@@ -289,73 +289,30 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
     return _FlashAttention.apply(q, k, v, causal, q_lengths, k_lengths, block_mask, fast_scale)
 
 
-# ---- decode attention over a KV cache (include/mfa_decode.h): forward only, per-sequence lengths on the device, contiguous or paged
-_DECODERS: Dict[Tuple, AttentionDecode] = {}
+# ---- launches over a KV cache (include/mfa_decode.h, mfa_kvcache.h, mfa_prefill.h, mfa_window.h, mfa_sink.h, mfa_ragged.h): decode and prefill
+# attention and the append that feeds them, forward only, per-sequence lengths on the device, contiguous or paged, 16-bit or e4m3
+_HOSTS: Dict[Tuple, object] = {}
+_FP8_DTYPES = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz") if hasattr(torch, n))
+_LN2 = 0.6931471805599453
+
+
+def _host(cls, dtype, D, fp8):
+    """the host object of a launch: one per (class, 16-bit type, head dimension, e4m3 cache or not), kept"""
+    key = (cls, dtype, D, bool(fp8))
+    host = _HOSTS.get(key)
+    if host is None:
+        precision = P.BF16 if dtype == torch.bfloat16 else P.FP16
+        if cls is AttentionDecode:
+            host = (AttentionDecodeFP8 if fp8 else AttentionDecode)(D, precision)
+        else:
+            host = cls(D, precision, cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
+        _HOSTS[key] = host
+    return host
 
 
 def _cache_strides(t, paged):
     """(leadingDimension, headStride, batchStride) of a [B or pages, Hkv, keys, D] cache view, passed through as they are"""
     return (int(t.stride(2)) if t.shape[2] > 1 else int(t.shape[3]), int(t.stride(1)), 0 if paged else int(t.stride(0)))
-
-
-def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None, sinks=None):
-    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
-        raise RuntimeError("flash_decode: tensors must live on the GPU (there is no CPU path)")
-    if fp8:
-        if k_cache.dtype != v_cache.dtype or k_cache.dtype != torch.float8_e4m3fn:
-            raise TypeError(f"flash_decode: an FP8 KV cache is torch.float8_e4m3fn for both K and V (got {k_cache.dtype}, {v_cache.dtype}); "
-                            "e5m2 and fnuz caches have no kernel")
-        if q.dtype not in (torch.bfloat16, torch.float16):
-            raise TypeError("flash_decode: q must be bfloat16 or float16")
-    elif q.dtype not in (torch.bfloat16, torch.float16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise TypeError("flash_decode: q and the caches must share one of bfloat16 / float16")
-    paged = block_table is not None
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[3] != k_cache.shape[3] or k_cache.shape[1] == 0 or \
-            q.shape[1] % k_cache.shape[1] != 0 or (not paged and k_cache.shape[0] != q.shape[0]):
-        raise ValueError("flash_decode: expected q [B, H, R, D] and caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) with H a "
-                         f"multiple of Hkv (got q {tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)})")
-    B, H, R, D = q.shape
-    Hkv = k_cache.shape[1]
-    if cache_lengths.shape != (B,) or cache_lengths.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"flash_decode: cache_lengths must be [B] = [{B}] int32 or int64 (got {tuple(cache_lengths.shape)}, {cache_lengths.dtype})")
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
-            raise ValueError(f"flash_decode: {name} must have a contiguous last dimension (a cache is never copied)")
-    kw = {}
-    if paged:
-        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
-                not block_table.is_cuda:
-            raise ValueError(f"flash_decode: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
-                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
-        page = int(k_cache.shape[2])
-        column = page * int(block_table.shape[1])
-        kw = dict(pageSize=page, blockTable=block_table, blockTableStride=int(block_table.stride(0)),
-                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
-    else:
-        column = int(k_cache.shape[2])
-    q = q if q.stride(3) == 1 and all(st >= 0 for st in q.stride()) else q.contiguous()
-    lengths = cache_lengths.to(torch.int32)   # (no copy when it already is; stays on the device)
-    o = torch.empty((B, H, R, D), dtype=q.dtype, device=q.device)
-    l = torch.empty((B, H, R), dtype=torch.float32, device=q.device)
-    key = (q.dtype, D, bool(fp8))
-    dec = _DECODERS.get(key)
-    if dec is None:
-        dec = _DECODERS[key] = (AttentionDecodeFP8 if fp8 else AttentionDecode)(D, P.BF16 if q.dtype == torch.bfloat16 else P.FP16)
-    if fp8:
-        kw.update(keyScale=_scale_operand("flash_decode", "k_scale", k_scale, Hkv, q.device),
-                  valueScale=_scale_operand("flash_decode", "v_scale", v_scale, Hkv, q.device))
-    kw.update(rows=R, column=column, heads=H, batches=B, headsPerKeyValue=H // Hkv, causal=bool(causal), cacheLengths=lengths,
-              strides=dict(Q=(int(q.stride(2)) if R > 1 else D, int(q.stride(1)), int(q.stride(0))),
-                           K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
-    if window is not None:
-        kw.update(window=int(window))
-    if sinks is not None:   # (sink tokens or 0, sink logits or None): the entries of include/mfa_sink.h
-        kw.update(sinkTokens=int(sinks[0]), sinkLogits=sinks[1])
-    need = dec.workspaceSize(**kw)
-    ws = torch.empty(need, dtype=torch.uint8, device=q.device) if need else None
-    with torch.cuda.device(q.device):
-        dec.dispatch(q, k_cache, v_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, workspace=ws, **kw)
-    return o, l
 
 
 def _scale_operand(who, name, t, heads, device):
@@ -369,99 +326,341 @@ def _scale_operand(who, name, t, heads, device):
     return t.contiguous()
 
 
-def _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale):
-    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, True, k_scale, v_scale)
-
-
-def _run_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale):
-    who = "kv_cache_append"
-    tensors = (k_new, v_new, k_cache, v_cache, cache_lengths)
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
-    if k_new.dtype not in (torch.bfloat16, torch.float16) or v_new.dtype != k_new.dtype:
-        raise TypeError(f"{who}: k_new and v_new must share one of bfloat16 / float16")
-    if k_cache.dtype != v_cache.dtype or k_cache.dtype not in (k_new.dtype, torch.float8_e4m3fn):
-        raise TypeError(f"{who}: the caches must both be torch.float8_e4m3fn or the new rows' {k_new.dtype} (got {k_cache.dtype}, "
-                        f"{v_cache.dtype}); e5m2 and fnuz caches have no kernel")
-    fp8 = k_cache.dtype == torch.float8_e4m3fn
+def _check_scales(who, fp8, k_scale, v_scale, write=False):
     if not fp8 and (k_scale is not None or v_scale is not None):
-        raise ValueError(f"{who}: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache takes the rows' bits")
+        raise ValueError(f"{who}: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache "
+                         + ("takes the rows' bits" if write else "holds the values themselves"))
+
+
+def _check_lengths(who, name, t, batches, tail=""):
+    """a per-sequence length array: [batches] (None: any count) int32 or int64 on the GPU"""
+    if not t.is_cuda or t.dim() != 1 or (batches is not None and t.shape[0] != batches) or t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{who}: {name} must be a GPU tensor [B]{'' if batches is None else f' = [{batches}]'} int32 or int64{tail} "
+                         f"(got {tuple(t.shape)}, {t.dtype})")
+
+
+def _cache_side(who, news, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, *, packed=False, write=False, fp8=None):
+    """Validates the cache side of a launch against its new operand(s) `news` -- q [B, H, R, D], or k_new and v_new [B, Hkv, R, D]; `packed`:
+    [T, H, D], a ragged batch -- and describes it -> (fp8, B, keywords of the host class's dispatch: the lengths, the paging, the scales,
+    `column`, and `strides` with the caches' entries, to which the caller adds its operands').  `write`: the launch writes the cache
+    (append) -- the rows' heads are the caches', the words say so, and the block table is handed over contiguous with its width as the
+    stride, the bound on the pages a sequence may name.  `fp8`: what the caller's op says the caches are (None: what they say)."""
+    new, names = news[0], "k_new, v_new" if write else "q"
+    if not all(t.is_cuda for t in (*news, k_cache, v_cache, cache_lengths)):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    if new.dtype not in (torch.bfloat16, torch.float16) or any(t.dtype != new.dtype for t in news):
+        raise TypeError(f"{who}: " + ("k_new and v_new must share one of bfloat16 / float16" if write else "q must be bfloat16 or float16"))
+    if fp8 is None:
+        fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
+    if k_cache.dtype != v_cache.dtype or k_cache.dtype != (torch.float8_e4m3fn if fp8 else new.dtype):
+        if write:
+            raise TypeError(f"{who}: the caches must both be torch.float8_e4m3fn or the new rows' {new.dtype} (got {k_cache.dtype}, "
+                            f"{v_cache.dtype}); e5m2 and fnuz caches have no kernel")
+        if fp8:
+            raise TypeError(f"{who}: an FP8 KV cache is torch.float8_e4m3fn for both K and V (got {k_cache.dtype}, {v_cache.dtype}); "
+                            "e5m2 and fnuz caches have no kernel")
+        raise TypeError(f"{who}: q and the caches must share one of bfloat16 / float16 (or the caches are float8_e4m3fn)")
+    _check_scales(who, fp8, k_scale, v_scale, write)
     paged = block_table is not None
-    if k_new.dim() != 4 or v_new.shape != k_new.shape or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or \
-            k_cache.shape[1] != k_new.shape[1] or k_cache.shape[3] != k_new.shape[3] or (not paged and k_cache.shape[0] != k_new.shape[0]):
-        raise ValueError(f"{who}: expected k_new, v_new [B, Hkv, R, D] and caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) "
-                         f"(got {tuple(k_new.shape)}, {tuple(v_new.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
-    B, Hkv, R, D = k_new.shape
-    if cache_lengths.shape != (B,) or cache_lengths.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{who}: cache_lengths must be [B] = [{B}] int32 or int64 (got {tuple(cache_lengths.shape)}, {cache_lengths.dtype})")
+    n = 3 if packed else 4
+    if any(t.dim() != n or t.shape != new.shape for t in news) or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or \
+            new.shape[-1] != k_cache.shape[3] or k_cache.shape[1] == 0 or \
+            (new.shape[1] != k_cache.shape[1] if write else new.shape[1] % k_cache.shape[1] != 0) or \
+            (new.shape[0] == 0 if packed else not paged and k_cache.shape[0] != new.shape[0]):
+        heads = "Hkv" if write else "H"
+        raise ValueError(f"{who}: expected {names} {f'[T, {heads}, D] (packed rows)' if packed else f'[B, {heads}, R, D]'} and caches "
+                         f"[B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]){'' if write else ' with H a multiple of Hkv'} "
+                         f"(got {', '.join(str(tuple(t.shape)) for t in (*news, k_cache, v_cache))})")
+    Hkv = k_cache.shape[1]
+    if packed:
+        _check_lengths(who, "cache_lengths", cache_lengths, None if paged else k_cache.shape[0], ", B the caches' first dimension when they are contiguous")
+    else:
+        _check_lengths(who, "cache_lengths", cache_lengths, new.shape[0])
+    B = int(cache_lengths.shape[0])
     for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
         if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
-            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is written where it lies)")
-    kw = {}
+            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is "
+                             f"{'written where it lies' if write else 'never copied'})")
+    kw = dict(cacheLengths=cache_lengths.to(torch.int32))   # (no copy when it already is; stays on the device)
     if paged:
         if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
                 not block_table.is_cuda:
             raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
                              f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
-        block_table = block_table.contiguous()   # (the row stride is the bound on the pages a sequence may name)
-        kw = dict(pageSize=int(k_cache.shape[2]), blockTable=block_table, blockTableStride=int(block_table.shape[1]),
+        kw.update(pageSize=int(k_cache.shape[2]), blockTable=block_table.contiguous() if write else block_table,
+                  blockTableStride=int(block_table.shape[1] if write else block_table.stride(0)),
                   pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
-    else:
-        kw = dict(column=int(k_cache.shape[2]))
-    news = [t if t.stride(3) == 1 and all(st >= 0 for st in t.stride()) else t.contiguous() for t in (k_new, v_new)]
-    new_strides = lambda t: (int(t.stride(2)) if R > 1 else D, int(t.stride(1)), int(t.stride(0)))  # noqa: E731
-    lengths = cache_lengths.to(torch.int32)
-    key = (k_new.dtype, D, fp8)
-    app = _APPENDERS.get(key)
-    if app is None:
-        app = _APPENDERS[key] = KVCacheAppend(D, P.BF16 if k_new.dtype == torch.bfloat16 else P.FP16, KVCachePrecision.E4M3 if fp8 else None)
+    if not (write and paged):   # (a paged append takes no column: its kernel drops a row whose page lies past the table's row)
+        kw.update(column=int(k_cache.shape[2]) * (int(block_table.shape[1]) if paged else 1))
     if fp8:
-        kw.update(keyScale=_scale_operand(who, "k_scale", k_scale, Hkv, k_new.device), valueScale=_scale_operand(who, "v_scale", v_scale, Hkv, k_new.device))
+        kw.update(keyScale=_scale_operand(who, "k_scale", k_scale, Hkv, new.device), valueScale=_scale_operand(who, "v_scale", v_scale, Hkv, new.device))
+    k_name, v_name = ("kCache", "vCache") if write else ("K", "V")
+    kw.update(strides={k_name: _cache_strides(k_cache, paged), v_name: _cache_strides(v_cache, paged)})
+    return fp8, B, kw
+
+
+def _new_operand(t):
+    """a [B, heads, R, D] operand as the kernels read it, and its strides: any view with a contiguous last dimension is taken where it lies"""
+    t = t if t.stride(3) == 1 and all(st >= 0 for st in t.stride()) else t.contiguous()
+    return t, (int(t.stride(2)) if t.shape[2] > 1 else int(t.shape[3]), int(t.stride(1)), int(t.stride(0)))
+
+
+def _packed_operand(t):
+    """the same of a packed [T, heads, D] operand: a view with a contiguous last dimension and 16-byte rows is taken where it lies (a slice
+    of a fused QKV projection: strides, not a copy)"""
+    ok = t.stride(2) == 1 and all(st >= 0 for st in t.stride()) and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
+    t = t if ok else t.contiguous()
+    T, heads, D = t.shape
+    return t, (int(t.stride(0)) if T > 1 else heads * D, int(t.stride(1)) if heads > 1 else D, 0)
+
+
+def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, workspace=False):
+    """the launch of a decode or prefill host object over `kw`, on q's device and torch's current stream -> (O, L).  (Rows the launch does
+    not own -- past q_lengths[b], or packed rows of no sequence -- are not written: no memset is spent on them, they come back uninitialised)"""
+    if window is not None:
+        kw.update(window=int(window))
+    if sinks is not None:   # (sink tokens or 0, sink logits or None): the entries of include/mfa_sink.h
+        kw.update(sinkTokens=int(sinks[0]), sinkLogits=sinks[1])
+    o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    l = torch.empty(l_shape, dtype=torch.float32, device=q.device)
+    if workspace:
+        need = host.workspaceSize(**kw)
+        kw.update(workspace=torch.empty(need, dtype=torch.uint8, device=q.device) if need else None)
+    with torch.cuda.device(q.device):
+        host.dispatch(q, k_cache, v_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
+    return o, l
+
+
+def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None, sinks=None):
+    fp8, B, kw = _cache_side("flash_decode", (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, fp8=bool(fp8))
+    q, kw["strides"]["Q"] = _new_operand(q)
+    _B, H, R, D = q.shape
+    kw.update(rows=R, heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal))
+    return _attend(_host(AttentionDecode, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, workspace=True)
+
+
+def _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale):
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, True, k_scale, v_scale)
+
+
+def _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sinks=None):
+    """over whichever cache the tensors say: the window and sink ops serve 16-bit and e4m3 caches alike"""
+    fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8, k_scale, v_scale, window, sinks)
+
+
+def _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits):
+    return _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window or None, (sink_tokens, sink_logits))
+
+
+def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None, sinks=None):
+    who = "flash_prefill"
+    fp8, B, kw = _cache_side(who, (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
+    if q_lengths is not None:
+        _check_lengths(who, "q_lengths", q_lengths, B)
+    q, kw["strides"]["Q"] = _new_operand(q)
+    _B, H, R, D = q.shape
+    kw.update(rows=R, heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal),
+              queryLengths=None if q_lengths is None else q_lengths.to(torch.int32))
+    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks)
+
+
+def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window, sinks):
+    who = "flash_prefill_ragged"
+    fp8, B, kw = _cache_side(who, (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, packed=True)
+    _check_row_starts(who, row_starts, cache_lengths, max_rows)
+    q, kw["strides"]["Q"] = _packed_operand(q)
+    T, H, D = q.shape
+    kw.update(rows=int(max_rows), heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal),
+              rowStarts=row_starts.to(torch.int32), totalRows=T)
+    sinks = sinks if sinks is not None and (sinks[0] or sinks[1] is not None) else None   # (the op's 0 and None: no sinks, as 0 is no window)
+    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (H, T), kw, window or None, sinks)
+
+
+def _append(who, operand, k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, row_starts=None, max_rows=None):
+    packed = operand is _packed_operand
+    fp8, B, kw = _cache_side(who, (k_new, v_new), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, packed=packed, write=True)
+    if packed:
+        _check_row_starts(who, row_starts, cache_lengths, max_rows)
+        kw.update(rows=int(max_rows), rowStarts=row_starts.to(torch.int32), totalRows=k_new.shape[0])
+    else:
+        kw.update(rows=k_new.shape[2])
+    (k_new, kw["strides"]["kNew"]), (v_new, kw["strides"]["vNew"]) = operand(k_new), operand(v_new)
     with torch.cuda.device(k_new.device):
-        app.dispatch(news[0], news[1], k_cache, v_cache, stream=torch.cuda.current_stream(k_new.device).cuda_stream, rows=R, heads=Hkv,
-                     batches=B, cacheLengths=lengths,
-                     strides=dict(kNew=new_strides(news[0]), vNew=new_strides(news[1]), kCache=_cache_strides(k_cache, paged),
-                                  vCache=_cache_strides(v_cache, paged)), **kw)
+        _host(KVCacheAppend, k_new.dtype, k_new.shape[-1], fp8).dispatch(
+            k_new, v_new, k_cache, v_cache, stream=torch.cuda.current_stream(k_new.device).cuda_stream, heads=k_new.shape[1], batches=B, **kw)
 
 
-_APPENDERS: Dict[Tuple, KVCacheAppend] = {}
-_FP8_DTYPES = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz") if hasattr(torch, n))
+def _run_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale):
+    _append("kv_cache_append", _new_operand, k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
 
 
-def _register_kvcache_ops():
+def _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale):
+    _append("kv_cache_append_ragged", _packed_operand, k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, row_starts, max_rows)
+
+
+def _check_window(who, window, causal):
+    if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window < 2 ** 32:
+        raise ValueError(f"{who}: window must be an int from 1 to 2^32 - 1 (None: no window), not {window!r}")
+    if not causal:
+        raise ValueError(f"{who}: a sliding window needs causal=True (the window lies behind the row's causal frontier)")
+
+
+def _check_sinks(who, q, window, causal, sink_tokens, sink_logits):
+    if window is not None:
+        _check_window(who, window, causal)
+    if sink_tokens is not None:
+        if isinstance(sink_tokens, bool) or not isinstance(sink_tokens, int) or not 1 <= sink_tokens < 2 ** 32:
+            raise ValueError(f"{who}: sink_tokens must be an int from 1 to 2^32 - 1 (None: no sink tokens), not {sink_tokens!r}")
+        if window is None:
+            raise ValueError(f"{who}: sink_tokens needs window: the sink keys stay visible under a sliding window (without one every "
+                             "key below the frontier is visible already)")
+    if sink_logits is not None:
+        if not isinstance(sink_logits, torch.Tensor) or sink_logits.dtype != torch.float32 or q.dim() != 4 or \
+                tuple(sink_logits.shape) != (q.shape[1],) or not sink_logits.is_contiguous():
+            raise ValueError(f"{who}: sink_logits must be a contiguous float32 tensor [H] = [{q.shape[1] if q.dim() == 4 else '?'}], one logit "
+                             f"per query head (got {tuple(sink_logits.shape) if isinstance(sink_logits, torch.Tensor) else type(sink_logits).__name__}"
+                             f"{', ' + str(sink_logits.dtype) if isinstance(sink_logits, torch.Tensor) else ''})")
+        if sink_logits.device != q.device:
+            raise RuntimeError(f"{who}: sink_logits must live on q's device (the host never reads a logit)")
+
+
+def _check_row_starts(who, row_starts, cache_lengths, max_rows):
+    if not isinstance(row_starts, torch.Tensor) or not row_starts.is_cuda or row_starts.dim() != 1 or \
+            row_starts.shape[0] != cache_lengths.shape[0] + 1 or row_starts.dtype not in (torch.int32, torch.int64):
+        got = f"{tuple(row_starts.shape)}, {row_starts.dtype}" if isinstance(row_starts, torch.Tensor) else type(row_starts).__name__
+        raise ValueError(f"{who}: row_starts must be a GPU tensor [B + 1] = [{cache_lengths.shape[0] + 1}] int32 or int64: the first packed row "
+                         f"of every sequence and the end of the last (got {got})")
+    if isinstance(max_rows, bool) or not isinstance(max_rows, int) or not 1 <= max_rows < 2 ** 32:
+        raise ValueError(f"{who}: max_rows must be an int from 1 to 2^32 - 1, the largest row count of a sequence (the host never reads "
+                         f"row_starts), not {max_rows!r}")
+
+
+# ---- the torch.library ops: what torch.compile traces.  Schemas are inferred from the annotated signatures
+def _op_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+               block_table: Optional[torch.Tensor], causal: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)
+
+
+def _op_decode_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                   block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
+                   v_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale)
+
+
+def _op_decode_window(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                      block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
+                      v_scale: Optional[torch.Tensor], window: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window)
+
+
+def _op_decode_sink(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                    block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor],
+                    window: int, sink_tokens: int, sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits)
+
+
+def _op_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
+                k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
+
+
+def _op_prefill_window(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                       q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
+                       k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window)
+
+
+def _op_prefill_sink(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                     q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
+                     k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
+                     sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window or None,
+                        (sink_tokens, sink_logits))
+
+
+def _op_prefill_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor, row_starts: torch.Tensor,
+                       max_rows: int, block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
+                       v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
+                       sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window,
+                               (sink_tokens, sink_logits))
+
+
+def _op_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+               block_table: Optional[torch.Tensor], k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor]) -> None:
+    _run_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
+
+
+def _op_append_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                      row_starts: torch.Tensor, max_rows: int, block_table: Optional[torch.Tensor], k_scale: Optional[torch.Tensor],
+                      v_scale: Optional[torch.Tensor]) -> None:
+    _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale)
+
+
+def _fake_padded(q, *args, **kwargs):
+    B, H, R, D = q.shape
+    return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
+
+
+def _fake_packed(q, *args, **kwargs):
+    T, H, D = q.shape
+    return q.new_empty((T, H, D)), q.new_empty((H, T), dtype=torch.float32)
+
+
+def _fake_none(*args, **kwargs):
+    return None
+
+
+_IMPLS = {}
+
+
+def _register_cache_op(name, impl, fake, mutates_args=()):
+    """defines the op mfa::<name> -- `impl` on the GPU, `fake` for tracing -- unless this torch has no custom ops (False) or an earlier import
+    defined it; either way `_call_op` finds `impl` under the name"""
+    _IMPLS[name] = impl
     if not hasattr(torch.library, "custom_op"):
         return False
     try:
-        torch.ops.mfa.attention_decode_fp8  # noqa: B018 -- AttributeError when the op is not defined yet
-        torch.ops.mfa.kv_cache_append  # noqa: B018
-        return True
+        getattr(torch.ops.mfa, name)   # AttributeError when the op is not defined yet
     except (AttributeError, RuntimeError):
-        pass
-
-    @torch.library.custom_op("mfa::attention_decode_fp8", mutates_args=(), device_types="cuda")
-    def _op_decode_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
-                       block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
-                       v_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        return _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale)
-
-    @_op_decode_fp8.register_fake
-    def _op_decode_fp8_fake(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale):
-        B, H, R, D = q.shape
-        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
-
-    @torch.library.custom_op("mfa::kv_cache_append", mutates_args=("k_cache", "v_cache"), device_types="cuda")
-    def _op_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
-                   block_table: Optional[torch.Tensor], k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor]) -> None:
-        _run_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
-
-    @_op_append.register_fake
-    def _op_append_fake(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale):
-        return None
-
+        torch.library.custom_op("mfa::" + name, mutates_args=mutates_args, device_types="cuda")(impl).register_fake(fake)
     return True
 
 
-_HAVE_KVCACHE_OPS = _register_kvcache_ops()
+def _call_op(have, name, *args):
+    """the op where torch has custom ops, else its implementation"""
+    return getattr(torch.ops.mfa, name)(*args) if have else _IMPLS[name](*args)
+
+
+_HAVE_DECODE_OP = _register_cache_op("attention_decode", _op_decode, _fake_padded)
+_HAVE_KVCACHE_OPS = all([_register_cache_op("attention_decode_fp8", _op_decode_fp8, _fake_padded),
+                         _register_cache_op("kv_cache_append", _op_append, _fake_none, ("k_cache", "v_cache"))])
+_HAVE_PREFILL_OP = _register_cache_op("attention_prefill", _op_prefill, _fake_padded)
+# (16-bit and e4m3 caches: one window op, one sink op; `window` 0 and `sink_tokens` 0: none.  The ops before them keep their schemas)
+_HAVE_WINDOW_OPS = all([_register_cache_op("attention_decode_window", _op_decode_window, _fake_padded),
+                        _register_cache_op("attention_prefill_window", _op_prefill_window, _fake_padded)])
+_HAVE_SINK_OPS = all([_register_cache_op("attention_decode_sink", _op_decode_sink, _fake_padded),
+                      _register_cache_op("attention_prefill_sink", _op_prefill_sink, _fake_padded)])
+_HAVE_RAGGED_OPS = all([_register_cache_op("attention_prefill_ragged", _op_prefill_ragged, _fake_packed),
+                        _register_cache_op("kv_cache_append_ragged", _op_append_ragged, _fake_none, ("k_cache", "v_cache"))])
+
+
+def _forward_only(who, q, k_cache, v_cache, cache_lengths):
+    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, k_cache, v_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
+
+
+def _in_place(who, k_new, v_new, k_cache, v_cache, cache_lengths):
+    for t in (k_new, v_new, k_cache, v_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} writes in place and has no autograd: detach the inputs")
+    if not all(t.is_cuda for t in (k_new, v_new, k_cache, v_cache, cache_lengths)):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
 
 
 def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
@@ -475,40 +674,8 @@ def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Ten
     quantised: byte = e4m3(x / scale[j]), round to nearest even, saturating at +-448; k_scale / v_scale fp32 [Hkv], None = 1.0) or
     the rows' own 16-bit type (bits copied; scales are an error).  Goes through the op `mfa::kv_cache_append` (mutates_args) where
     torch has custom ops."""
-    for t in (k_new, v_new, k_cache, v_cache):
-        if t.requires_grad:
-            raise RuntimeError("kv_cache_append writes in place and has no autograd: detach the inputs")
-    if not all(t.is_cuda for t in (k_new, v_new, k_cache, v_cache, cache_lengths)):
-        raise RuntimeError("kv_cache_append: tensors must live on the GPU (there is no CPU path)")
-    if _HAVE_KVCACHE_OPS:
-        torch.ops.mfa.kv_cache_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
-    else:
-        _run_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
-
-
-def _register_decode_op():
-    if not hasattr(torch.library, "custom_op"):
-        return False
-    try:
-        torch.ops.mfa.attention_decode  # noqa: B018 -- AttributeError when the op is not defined yet
-        return True
-    except (AttributeError, RuntimeError):
-        pass
-
-    @torch.library.custom_op("mfa::attention_decode", mutates_args=(), device_types="cuda")
-    def _op_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
-                   block_table: Optional[torch.Tensor], causal: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-        return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)
-
-    @_op_decode.register_fake
-    def _op_decode_fake(q, k_cache, v_cache, cache_lengths, block_table, causal):
-        B, H, R, D = q.shape
-        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
-
-    return True
-
-
-_HAVE_DECODE_OP = _register_decode_op()
+    _in_place("kv_cache_append", k_new, v_new, k_cache, v_cache, cache_lengths)
+    _call_op(_HAVE_KVCACHE_OPS, "kv_cache_append", k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
 
 
 def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
@@ -533,254 +700,21 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     entries between their tiles and the window's are never read.  sink_logits [H] fp32 on the GPU (any window, causal or not): one
     learned logit per query head joins the softmax denominator and no value row -- natural-log units, not scaled by 1 / sqrt(D) or
     k_scale; L includes it (include/mfa_sink.h).  Either goes through the op `mfa::attention_decode_sink`."""
-    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
-        raise RuntimeError("flash_decode: tensors must live on the GPU (there is no CPU path)")
-    for t in (q, k_cache, v_cache):
-        if t.requires_grad:
-            raise RuntimeError("flash_decode is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
+    _forward_only("flash_decode", q, k_cache, v_cache, cache_lengths)
+    args = (q, k_cache, v_cache, cache_lengths, block_table, causal)
     if sink_tokens is not None or sink_logits is not None:
         _check_sinks("flash_decode", q, window, causal, sink_tokens, sink_logits)
-        if _HAVE_SINK_OPS:
-            o, l = torch.ops.mfa.attention_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale,
-                                                       window or 0, sink_tokens or 0, sink_logits)
-        else:
-            o, l = _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits)
+        have, op, args = _HAVE_SINK_OPS, "attention_decode_sink", args + (k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits)
     elif window is not None:
         _check_window("flash_decode", window, causal)
-        if _HAVE_WINDOW_OPS:
-            o, l = torch.ops.mfa.attention_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window)
-        else:
-            o, l = _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window)
+        have, op, args = _HAVE_WINDOW_OPS, "attention_decode_window", args + (k_scale, v_scale, window)
     elif k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES:
-        if _HAVE_KVCACHE_OPS:
-            o, l = torch.ops.mfa.attention_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale)
-        else:
-            o, l = _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale)
-    elif k_scale is not None or v_scale is not None:
-        raise ValueError("flash_decode: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache holds the values themselves")
-    elif _HAVE_DECODE_OP:
-        o, l = torch.ops.mfa.attention_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)
-    else:
-        o, l = _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal)
-    return (o, l * 0.6931471805599453) if return_lse else o
-
-
-# ---- prefill attention over a KV cache (include/mfa_prefill.h): a block of new rows per sequence against a 16-bit or FP8 cache
-_PREFILLERS: Dict[Tuple, AttentionPrefill] = {}
-
-
-def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None, sinks=None):
-    who = "flash_prefill"
-    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
-        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
-    fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
-    if q.dtype not in (torch.bfloat16, torch.float16):
-        raise TypeError(f"{who}: q must be bfloat16 or float16")
-    if fp8:
-        if k_cache.dtype != v_cache.dtype or k_cache.dtype != torch.float8_e4m3fn:
-            raise TypeError(f"{who}: an FP8 KV cache is torch.float8_e4m3fn for both K and V (got {k_cache.dtype}, {v_cache.dtype}); "
-                            "e5m2 and fnuz caches have no kernel")
-    elif k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise TypeError(f"{who}: q and the caches must share one of bfloat16 / float16 (or the caches are float8_e4m3fn)")
-    elif k_scale is not None or v_scale is not None:
-        raise ValueError(f"{who}: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache holds the values themselves")
-    paged = block_table is not None
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[3] != k_cache.shape[3] or k_cache.shape[1] == 0 or \
-            q.shape[1] % k_cache.shape[1] != 0 or (not paged and k_cache.shape[0] != q.shape[0]):
-        raise ValueError(f"{who}: expected q [B, H, R, D] and caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) with H a "
-                         f"multiple of Hkv (got q {tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)})")
-    B, H, R, D = q.shape
-    Hkv = k_cache.shape[1]
-    for name, t in (("cache_lengths", cache_lengths), ("q_lengths", q_lengths)):
-        if t is not None and (not t.is_cuda or t.shape != (B,) or t.dtype not in (torch.int32, torch.int64)):
-            raise ValueError(f"{who}: {name} must be a GPU tensor [B] = [{B}] int32 or int64 (got {tuple(t.shape)}, {t.dtype})")
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
-            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is never copied)")
-    kw = {}
-    if paged:
-        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
-                not block_table.is_cuda:
-            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
-                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
-        page = int(k_cache.shape[2])
-        column = page * int(block_table.shape[1])
-        kw = dict(pageSize=page, blockTable=block_table, blockTableStride=int(block_table.stride(0)),
-                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
-    else:
-        column = int(k_cache.shape[2])
-    q = q if q.stride(3) == 1 and all(st >= 0 for st in q.stride()) else q.contiguous()
-    lengths = cache_lengths.to(torch.int32)   # (no copy when it already is; stays on the device)
-    qlens = None if q_lengths is None else q_lengths.to(torch.int32)
-    # (rows at or past q_lengths[b] are not written by the launch: no memset is spent on them, they come back uninitialised)
-    o = torch.empty((B, H, R, D), dtype=q.dtype, device=q.device)
-    l = torch.empty((B, H, R), dtype=torch.float32, device=q.device)
-    key = (q.dtype, D, bool(fp8))
-    pre = _PREFILLERS.get(key)
-    if pre is None:
-        pre = _PREFILLERS[key] = AttentionPrefill(D, P.BF16 if q.dtype == torch.bfloat16 else P.FP16,
-                                                  cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
-    if fp8:
-        kw.update(keyScale=_scale_operand(who, "k_scale", k_scale, Hkv, q.device), valueScale=_scale_operand(who, "v_scale", v_scale, Hkv, q.device))
-    kw.update(rows=R, column=column, heads=H, batches=B, headsPerKeyValue=H // Hkv, causal=bool(causal), cacheLengths=lengths,
-              queryLengths=qlens,
-              strides=dict(Q=(int(q.stride(2)) if R > 1 else D, int(q.stride(1)), int(q.stride(0))),
-                           K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
-    if window is not None:
-        kw.update(window=int(window))
-    if sinks is not None:
-        kw.update(sinkTokens=int(sinks[0]), sinkLogits=sinks[1])
-    with torch.cuda.device(q.device):
-        pre.dispatch(q, k_cache, v_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
-    return o, l
-
-
-def _register_prefill_op():
-    if not hasattr(torch.library, "custom_op"):
-        return False
-    try:
-        torch.ops.mfa.attention_prefill  # noqa: B018 -- AttributeError when the op is not defined yet
-        return True
-    except (AttributeError, RuntimeError):
-        pass
-
-    @torch.library.custom_op("mfa::attention_prefill", mutates_args=(), device_types="cuda")
-    def _op_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
-                    q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
-                    k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
-
-    @_op_prefill.register_fake
-    def _op_prefill_fake(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale):
-        B, H, R, D = q.shape
-        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
-
-    return True
-
-
-_HAVE_PREFILL_OP = _register_prefill_op()
-
-
-def _check_window(who, window, causal):
-    if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window < 2 ** 32:
-        raise ValueError(f"{who}: window must be an int from 1 to 2^32 - 1 (None: no window), not {window!r}")
-    if not causal:
-        raise ValueError(f"{who}: a sliding window needs causal=True (the window lies behind the row's causal frontier)")
-
-
-def _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window):
-    fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
-    if not fp8 and (k_scale is not None or v_scale is not None):
-        raise ValueError("flash_decode: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache holds the values themselves")
-    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8, k_scale, v_scale, window)
-
-
-def _register_window_ops():
-    """mfa::attention_decode_window (16-bit and e4m3 caches: one op) and mfa::attention_prefill_window (include/mfa_window.h).  The
-    ops without a window keep their schemas."""
-    if not hasattr(torch.library, "custom_op"):
-        return False
-    try:
-        torch.ops.mfa.attention_decode_window  # noqa: B018 -- AttributeError when the op is not defined yet
-        torch.ops.mfa.attention_prefill_window  # noqa: B018
-        return True
-    except (AttributeError, RuntimeError):
-        pass
-
-    @torch.library.custom_op("mfa::attention_decode_window", mutates_args=(), device_types="cuda")
-    def _op_decode_window(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
-                          block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
-                          v_scale: Optional[torch.Tensor], window: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        return _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window)
-
-    @_op_decode_window.register_fake
-    def _op_decode_window_fake(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window):
-        B, H, R, D = q.shape
-        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
-
-    @torch.library.custom_op("mfa::attention_prefill_window", mutates_args=(), device_types="cuda")
-    def _op_prefill_window(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
-                           q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
-                           k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window)
-
-    @_op_prefill_window.register_fake
-    def _op_prefill_window_fake(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window):
-        B, H, R, D = q.shape
-        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
-
-    return True
-
-
-_HAVE_WINDOW_OPS = _register_window_ops()
-
-
-def _check_sinks(who, q, window, causal, sink_tokens, sink_logits):
-    if window is not None:
-        _check_window(who, window, causal)
-    if sink_tokens is not None:
-        if isinstance(sink_tokens, bool) or not isinstance(sink_tokens, int) or not 1 <= sink_tokens < 2 ** 32:
-            raise ValueError(f"{who}: sink_tokens must be an int from 1 to 2^32 - 1 (None: no sink tokens), not {sink_tokens!r}")
-        if window is None:
-            raise ValueError(f"{who}: sink_tokens needs window: the sink keys stay visible under a sliding window (without one every "
-                             "key below the frontier is visible already)")
-    if sink_logits is not None:
-        if not isinstance(sink_logits, torch.Tensor) or sink_logits.dtype != torch.float32 or q.dim() != 4 or \
-                tuple(sink_logits.shape) != (q.shape[1],) or not sink_logits.is_contiguous():
-            raise ValueError(f"{who}: sink_logits must be a contiguous float32 tensor [H] = [{q.shape[1] if q.dim() == 4 else '?'}], one logit "
-                             f"per query head (got {tuple(sink_logits.shape) if isinstance(sink_logits, torch.Tensor) else type(sink_logits).__name__}"
-                             f"{', ' + str(sink_logits.dtype) if isinstance(sink_logits, torch.Tensor) else ''})")
-        if sink_logits.device != q.device:
-            raise RuntimeError(f"{who}: sink_logits must live on q's device (the host never reads a logit)")
-
-
-def _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits):
-    fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
-    if not fp8 and (k_scale is not None or v_scale is not None):
-        raise ValueError("flash_decode: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache holds the values themselves")
-    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8, k_scale, v_scale, window or None, (sink_tokens, sink_logits))
-
-
-def _register_sink_ops():
-    """mfa::attention_decode_sink and mfa::attention_prefill_sink (include/mfa_sink.h): the window ops with `sink_tokens` (0: none)
-    and `sink_logits` behind `window` (0: none).  The other ops keep their schemas."""
-    if not hasattr(torch.library, "custom_op"):
-        return False
-    try:
-        torch.ops.mfa.attention_decode_sink  # noqa: B018 -- AttributeError when the op is not defined yet
-        torch.ops.mfa.attention_prefill_sink  # noqa: B018
-        return True
-    except (AttributeError, RuntimeError):
-        pass
-
-    @torch.library.custom_op("mfa::attention_decode_sink", mutates_args=(), device_types="cuda")
-    def _op_decode_sink(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
-                        block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor],
-                        window: int, sink_tokens: int, sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        return _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits)
-
-    @_op_decode_sink.register_fake
-    def _op_decode_sink_fake(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits):
-        B, H, R, D = q.shape
-        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
-
-    @torch.library.custom_op("mfa::attention_prefill_sink", mutates_args=(), device_types="cuda")
-    def _op_prefill_sink(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
-                         q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
-                         k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
-                         sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window or None,
-                            (sink_tokens, sink_logits))
-
-    @_op_prefill_sink.register_fake
-    def _op_prefill_sink_fake(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits):
-        B, H, R, D = q.shape
-        return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
-
-    return True
-
-
-_HAVE_SINK_OPS = _register_sink_ops()
+        have, op, args = _HAVE_KVCACHE_OPS, "attention_decode_fp8", args + (k_scale, v_scale)
+    else:   # (the op of a 16-bit cache takes no scales)
+        _check_scales("flash_decode", False, k_scale, v_scale)
+        have, op = _HAVE_DECODE_OP, "attention_decode"
+    o, l = _call_op(have, op, *args)
+    return (o, l * _LN2) if return_lse else o
 
 
 def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
@@ -800,210 +734,18 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     flash_decode's, through the op `mfa::attention_prefill_window`; None: no window.  sink_tokens / sink_logits: attention sinks as
     flash_decode's (include/mfa_sink.h), through the op `mfa::attention_prefill_sink`; a live row without a visible key then gets
     L = the head's sink logit."""
-    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
-        raise RuntimeError("flash_prefill: tensors must live on the GPU (there is no CPU path)")
-    for t in (q, k_cache, v_cache):
-        if t.requires_grad:
-            raise RuntimeError("flash_prefill is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
+    _forward_only("flash_prefill", q, k_cache, v_cache, cache_lengths)
+    args = (q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
     if sink_tokens is not None or sink_logits is not None:
         _check_sinks("flash_prefill", q, window, causal, sink_tokens, sink_logits)
-        if _HAVE_SINK_OPS:
-            o, l = torch.ops.mfa.attention_prefill_sink(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale,
-                                                        window or 0, sink_tokens or 0, sink_logits)
-        else:
-            o, l = _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window,
-                                (sink_tokens or 0, sink_logits))
+        have, op, args = _HAVE_SINK_OPS, "attention_prefill_sink", args + (window or 0, sink_tokens or 0, sink_logits)
     elif window is not None:
         _check_window("flash_prefill", window, causal)
-        if _HAVE_WINDOW_OPS:
-            o, l = torch.ops.mfa.attention_prefill_window(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window)
-        else:
-            o, l = _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window)
-    elif _HAVE_PREFILL_OP:
-        o, l = torch.ops.mfa.attention_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
+        have, op, args = _HAVE_WINDOW_OPS, "attention_prefill_window", args + (window,)
     else:
-        o, l = _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
-    return (o, l * 0.6931471805599453) if return_lse else o
-
-
-# ---- ragged batches (include/mfa_ragged.h): packed query rows for prefill and append, one launch for a continuous-batching step
-def _check_row_starts(who, row_starts, cache_lengths, max_rows):
-    if not isinstance(row_starts, torch.Tensor) or not row_starts.is_cuda or row_starts.dim() != 1 or \
-            row_starts.shape[0] != cache_lengths.shape[0] + 1 or row_starts.dtype not in (torch.int32, torch.int64):
-        got = f"{tuple(row_starts.shape)}, {row_starts.dtype}" if isinstance(row_starts, torch.Tensor) else type(row_starts).__name__
-        raise ValueError(f"{who}: row_starts must be a GPU tensor [B + 1] = [{cache_lengths.shape[0] + 1}] int32 or int64: the first packed row "
-                         f"of every sequence and the end of the last (got {got})")
-    if isinstance(max_rows, bool) or not isinstance(max_rows, int) or not 1 <= max_rows < 2 ** 32:
-        raise ValueError(f"{who}: max_rows must be an int from 1 to 2^32 - 1, the largest row count of a sequence (the host never reads "
-                         f"row_starts), not {max_rows!r}")
-
-
-def _packed_operand(t):
-    """a packed [T, heads, D] operand as the kernels read it: any view with a contiguous last dimension and 16-byte rows is taken where
-    it lies (a slice of a fused QKV projection: strides, not a copy)"""
-    ok = t.stride(2) == 1 and all(st >= 0 for st in t.stride()) and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
-    return t if ok else t.contiguous()
-
-
-def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window, sinks):
-    who = "flash_prefill_ragged"
-    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
-        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
-    fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
-    if q.dtype not in (torch.bfloat16, torch.float16):
-        raise TypeError(f"{who}: q must be bfloat16 or float16")
-    if fp8:
-        if k_cache.dtype != v_cache.dtype or k_cache.dtype != torch.float8_e4m3fn:
-            raise TypeError(f"{who}: an FP8 KV cache is torch.float8_e4m3fn for both K and V (got {k_cache.dtype}, {v_cache.dtype}); "
-                            "e5m2 and fnuz caches have no kernel")
-    elif k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise TypeError(f"{who}: q and the caches must share one of bfloat16 / float16 (or the caches are float8_e4m3fn)")
-    elif k_scale is not None or v_scale is not None:
-        raise ValueError(f"{who}: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache holds the values themselves")
-    paged = block_table is not None
-    if q.dim() != 3 or q.shape[0] == 0 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or q.shape[2] != k_cache.shape[3] or \
-            k_cache.shape[1] == 0 or q.shape[1] % k_cache.shape[1] != 0:
-        raise ValueError(f"{who}: expected q [T, H, D] (packed rows) and caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) with H a "
-                         f"multiple of Hkv (got q {tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)})")
-    T, H, D = q.shape
-    Hkv = k_cache.shape[1]
-    if cache_lengths.dim() != 1 or cache_lengths.dtype not in (torch.int32, torch.int64) or (not paged and cache_lengths.shape[0] != k_cache.shape[0]):
-        raise ValueError(f"{who}: cache_lengths must be a GPU tensor [B] int32 or int64, B the caches' first dimension when they are "
-                         f"contiguous (got {tuple(cache_lengths.shape)}, {cache_lengths.dtype})")
-    B = int(cache_lengths.shape[0])
-    _check_row_starts(who, row_starts, cache_lengths, max_rows)
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
-            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is never copied)")
-    kw = {}
-    if paged:
-        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
-                not block_table.is_cuda:
-            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
-                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
-        page = int(k_cache.shape[2])
-        column = page * int(block_table.shape[1])
-        kw = dict(pageSize=page, blockTable=block_table, blockTableStride=int(block_table.stride(0)),
-                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
-    else:
-        column = int(k_cache.shape[2])
-    q = _packed_operand(q)
-    lengths, starts = cache_lengths.to(torch.int32), row_starts.to(torch.int32)   # (no copy when they already are; they stay on the device)
-    # (packed rows no sequence owns are not written by the launch: no memset is spent on them, they come back uninitialised)
-    o = torch.empty((T, H, D), dtype=q.dtype, device=q.device)
-    l = torch.empty((H, T), dtype=torch.float32, device=q.device)
-    key = (q.dtype, D, bool(fp8))
-    pre = _PREFILLERS.get(key)
-    if pre is None:
-        pre = _PREFILLERS[key] = AttentionPrefill(D, P.BF16 if q.dtype == torch.bfloat16 else P.FP16,
-                                                  cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
-    if fp8:
-        kw.update(keyScale=_scale_operand(who, "k_scale", k_scale, Hkv, q.device), valueScale=_scale_operand(who, "v_scale", v_scale, Hkv, q.device))
-    kw.update(rows=int(max_rows), column=column, heads=H, batches=B, headsPerKeyValue=H // Hkv, causal=bool(causal), cacheLengths=lengths,
-              rowStarts=starts, totalRows=T,
-              strides=dict(Q=(int(q.stride(0)) if T > 1 else H * D, int(q.stride(1)) if H > 1 else D, 0),
-                           K=_cache_strides(k_cache, paged), V=_cache_strides(v_cache, paged)))
-    if window:
-        kw.update(window=int(window))
-    if sinks is not None and (sinks[0] or sinks[1] is not None):
-        kw.update(sinkTokens=int(sinks[0]), sinkLogits=sinks[1])
-    with torch.cuda.device(q.device):
-        pre.dispatch(q, k_cache, v_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
-    return o, l
-
-
-def _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale):
-    who = "kv_cache_append_ragged"
-    tensors = (k_new, v_new, k_cache, v_cache, cache_lengths)
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
-    if k_new.dtype not in (torch.bfloat16, torch.float16) or v_new.dtype != k_new.dtype:
-        raise TypeError(f"{who}: k_new and v_new must share one of bfloat16 / float16")
-    if k_cache.dtype != v_cache.dtype or k_cache.dtype not in (k_new.dtype, torch.float8_e4m3fn):
-        raise TypeError(f"{who}: the caches must both be torch.float8_e4m3fn or the new rows' {k_new.dtype} (got {k_cache.dtype}, "
-                        f"{v_cache.dtype}); e5m2 and fnuz caches have no kernel")
-    fp8 = k_cache.dtype == torch.float8_e4m3fn
-    if not fp8 and (k_scale is not None or v_scale is not None):
-        raise ValueError(f"{who}: k_scale / v_scale go with a float8_e4m3fn cache; a 16-bit cache takes the rows' bits")
-    paged = block_table is not None
-    if k_new.dim() != 3 or k_new.shape[0] == 0 or v_new.shape != k_new.shape or k_cache.dim() != 4 or v_cache.shape != k_cache.shape or \
-            k_cache.shape[1] != k_new.shape[1] or k_cache.shape[3] != k_new.shape[2]:
-        raise ValueError(f"{who}: expected k_new, v_new [T, Hkv, D] (packed rows) and caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) "
-                         f"(got {tuple(k_new.shape)}, {tuple(v_new.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
-    T, Hkv, D = k_new.shape
-    if cache_lengths.dim() != 1 or cache_lengths.dtype not in (torch.int32, torch.int64) or (not paged and cache_lengths.shape[0] != k_cache.shape[0]):
-        raise ValueError(f"{who}: cache_lengths must be a GPU tensor [B] int32 or int64, B the caches' first dimension when they are "
-                         f"contiguous (got {tuple(cache_lengths.shape)}, {cache_lengths.dtype})")
-    B = int(cache_lengths.shape[0])
-    _check_row_starts(who, row_starts, cache_lengths, max_rows)
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
-            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is written where it lies)")
-    if paged:
-        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
-                not block_table.is_cuda:
-            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
-                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
-        block_table = block_table.contiguous()   # (the row stride is the bound on the pages a sequence may name)
-        kw = dict(pageSize=int(k_cache.shape[2]), blockTable=block_table, blockTableStride=int(block_table.shape[1]),
-                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
-    else:
-        kw = dict(column=int(k_cache.shape[2]))
-    news = [_packed_operand(t) for t in (k_new, v_new)]
-    new_strides = lambda t: (int(t.stride(0)) if T > 1 else Hkv * D, int(t.stride(1)) if Hkv > 1 else D, 0)  # noqa: E731
-    key = (k_new.dtype, D, fp8)
-    app = _APPENDERS.get(key)
-    if app is None:
-        app = _APPENDERS[key] = KVCacheAppend(D, P.BF16 if k_new.dtype == torch.bfloat16 else P.FP16, KVCachePrecision.E4M3 if fp8 else None)
-    if fp8:
-        kw.update(keyScale=_scale_operand(who, "k_scale", k_scale, Hkv, k_new.device), valueScale=_scale_operand(who, "v_scale", v_scale, Hkv, k_new.device))
-    with torch.cuda.device(k_new.device):
-        app.dispatch(news[0], news[1], k_cache, v_cache, stream=torch.cuda.current_stream(k_new.device).cuda_stream, rows=int(max_rows),
-                     heads=Hkv, batches=B, cacheLengths=cache_lengths.to(torch.int32), rowStarts=row_starts.to(torch.int32), totalRows=T,
-                     strides=dict(kNew=new_strides(news[0]), vNew=new_strides(news[1]), kCache=_cache_strides(k_cache, paged),
-                                  vCache=_cache_strides(v_cache, paged)), **kw)
-
-
-def _register_ragged_ops():
-    """mfa::attention_prefill_ragged (`window`, `sink_tokens` 0: none) and mfa::kv_cache_append_ragged (include/mfa_ragged.h).  The other
-    ops keep their schemas."""
-    if not hasattr(torch.library, "custom_op"):
-        return False
-    try:
-        torch.ops.mfa.attention_prefill_ragged  # noqa: B018 -- AttributeError when the op is not defined yet
-        torch.ops.mfa.kv_cache_append_ragged  # noqa: B018
-        return True
-    except (AttributeError, RuntimeError):
-        pass
-
-    @torch.library.custom_op("mfa::attention_prefill_ragged", mutates_args=(), device_types="cuda")
-    def _op_prefill_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor, row_starts: torch.Tensor,
-                           max_rows: int, block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
-                           v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
-                           sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        return _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window,
-                                   (sink_tokens, sink_logits))
-
-    @_op_prefill_ragged.register_fake
-    def _op_prefill_ragged_fake(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window,
-                                sink_tokens, sink_logits):
-        T, H, D = q.shape
-        return q.new_empty((T, H, D)), q.new_empty((H, T), dtype=torch.float32)
-
-    @torch.library.custom_op("mfa::kv_cache_append_ragged", mutates_args=("k_cache", "v_cache"), device_types="cuda")
-    def _op_append_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
-                          row_starts: torch.Tensor, max_rows: int, block_table: Optional[torch.Tensor], k_scale: Optional[torch.Tensor],
-                          v_scale: Optional[torch.Tensor]) -> None:
-        _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale)
-
-    @_op_append_ragged.register_fake
-    def _op_append_ragged_fake(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale):
-        return None
-
-    return True
-
-
-_HAVE_RAGGED_OPS = _register_ragged_ops()
+        have, op = _HAVE_PREFILL_OP, "attention_prefill"
+    o, l = _call_op(have, op, *args)
+    return (o, l * _LN2) if return_lse else o
 
 
 def flash_prefill_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor, row_starts: torch.Tensor,
@@ -1019,21 +761,13 @@ def flash_prefill_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.
     rows that no sequence owns come back uninitialised.  The launch starts no workgroup for row blocks that do not exist and computes,
     byte for byte, what flash_prefill computes for the same sequences padded to max_rows.  Forward only; goes through the op
     `mfa::attention_prefill_ragged` where torch has custom ops, so it traces under torch.compile."""
-    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_lengths.is_cuda):
-        raise RuntimeError("flash_prefill_ragged: tensors must live on the GPU (there is no CPU path)")
-    for t in (q, k_cache, v_cache):
-        if t.requires_grad:
-            raise RuntimeError("flash_prefill_ragged is forward only (no autograd): detach the inputs; flash_attention is the differentiable entry")
+    _forward_only("flash_prefill_ragged", q, k_cache, v_cache, cache_lengths)
     if window is not None or sink_tokens is not None or sink_logits is not None:
         # (_check_sinks reads the heads off a [B, H, R, D] query: the packed q as such a view)
         _check_sinks("flash_prefill_ragged", q.unsqueeze(0).transpose(1, 2) if q.dim() == 3 else q, window, causal, sink_tokens, sink_logits)
-    if _HAVE_RAGGED_OPS:
-        o, l = torch.ops.mfa.attention_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale,
-                                                      v_scale, window or 0, sink_tokens or 0, sink_logits)
-    else:
-        o, l = _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale,
-                                   window or 0, (sink_tokens or 0, sink_logits))
-    return (o, l * 0.6931471805599453) if return_lse else o
+    o, l = _call_op(_HAVE_RAGGED_OPS, "attention_prefill_ragged", q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal,
+                    k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits)
+    return (o, l * _LN2) if return_lse else o
 
 
 def kv_cache_append_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
@@ -1044,12 +778,6 @@ def kv_cache_append_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: to
     row_starts [B + 1] and max_rows as flash_prefill_ragged's.  Row r of sequence b, which has qn_b = row_starts[b + 1] - row_starts[b]
     rows, goes to key cache_lengths[b] - qn_b + r (cache_lengths ALREADY INCLUDES the new tokens); kv_cache_append's drop rules, caches,
     quantisation and scales.  Goes through the op `mfa::kv_cache_append_ragged` (mutates_args) where torch has custom ops."""
-    for t in (k_new, v_new, k_cache, v_cache):
-        if t.requires_grad:
-            raise RuntimeError("kv_cache_append_ragged writes in place and has no autograd: detach the inputs")
-    if not all(t.is_cuda for t in (k_new, v_new, k_cache, v_cache, cache_lengths)):
-        raise RuntimeError("kv_cache_append_ragged: tensors must live on the GPU (there is no CPU path)")
-    if _HAVE_RAGGED_OPS:
-        torch.ops.mfa.kv_cache_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale)
-    else:
-        _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale)
+    _in_place("kv_cache_append_ragged", k_new, v_new, k_cache, v_cache, cache_lengths)
+    _call_op(_HAVE_RAGGED_OPS, "kv_cache_append_ragged", k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale,
+             v_scale)
