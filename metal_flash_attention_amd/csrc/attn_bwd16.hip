@@ -5,6 +5,8 @@ namespace mfa {
 
 // precision: storage type of Q, K, V; gprecision: storage type of dO (equal, or BF16 next to FP16)
 bool dq16_variant(int precision, int gprecision, int D, VariantInfo *out) {
+  if (D == 160) return dq16_variant_d160(precision, gprecision, out);
+  if (D == 192) return dq16_variant_d192(precision, gprecision, out);
   if (precision == PREC_FP16 && gprecision == PREC_BF16) {
     if (D == 128) { fill_dq<_Float16, 128, 8, __bf16>(out, "attn_dq16_f16_dObf16_d128_w8x32"); return true; }
     if (D == 64) { fill_dq<_Float16, 64, 8, __bf16>(out, "attn_dq16_f16_dObf16_d64_w8x32"); return true; }

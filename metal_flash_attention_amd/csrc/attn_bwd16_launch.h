@@ -87,4 +87,8 @@ static void fill_dkv(VariantInfo *v, const char *name) {
   v->causal = v->own(&launch_dkv16_causal<T, D, NW, PRE, TG>);
 }
 
+// attn_dq16's buckets that have a translation unit each, behind dq16_variant (attn_bwd16.hip)
+bool dq16_variant_d160(int precision, int gprecision, VariantInfo *out);
+bool dq16_variant_d192(int precision, int gprecision, VariantInfo *out);
+
 } // namespace mfa

@@ -17,6 +17,9 @@ bool dkv16_rs_variant(int precision, int gprecision, int D, int impl, VariantInf
     return true;
   }
 #endif
+  if (D == 96) return dkv16_rs_variant_d96(precision, gprecision, out);
+  if (D == 160) return dkv16_rs_variant_d160(precision, gprecision, out);
+  if (D == 192) return dkv16_rs_variant_d192(precision, gprecision, out);
   if (precision == PREC_FP16 && gprecision == PREC_BF16) {
     if (D == 128) { fill<_Float16, 128, __bf16>(out, "attn_dkv16rs_f16_dObf16_d128_p4x32"); return true; }
     if (D == 64) { fill<_Float16, 64, __bf16>(out, "attn_dkv16rs_f16_dObf16_d64_p4x32"); return true; }

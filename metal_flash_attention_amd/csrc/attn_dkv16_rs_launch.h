@@ -53,4 +53,9 @@ static void fill(VariantInfo *v, const char *name) {
   v->split = v->splitCausal = v->own(&launch_rs_split<T, D, TG>);   // (the causal mask: a run-time flag of the pieces)
 }
 
+// the family's buckets that have a translation unit each, behind dkv16_rs_variant (attn_dkv16_rs.hip)
+bool dkv16_rs_variant_d96(int precision, int gprecision, VariantInfo *out);
+bool dkv16_rs_variant_d160(int precision, int gprecision, VariantInfo *out);
+bool dkv16_rs_variant_d192(int precision, int gprecision, VariantInfo *out);
+
 } // namespace mfa

@@ -51,7 +51,7 @@ template <typename T, int STREAM> static void attach(VariantInfo *v) {
   v->ldsBytes = v->ldsBytes > (uint32_t)p4::LDS_BYTES ? v->ldsBytes : (uint32_t)p4::LDS_BYTES;
 }
 
-// `out` arrives filled by fwd16_v3_tr_variant_d128 for `pattern` (bit 0 = K, bit 1 = V transposed; 0 = only Q / O: nothing to do):
+// `out` arrives filled by fwd16_v3_tr_variant at bucket 128 for `pattern` (bit 0 = K, bit 1 = V transposed; 0 = only Q / O: nothing to do):
 // launches the stream can take go to it, the others stay.  fold: Q pre-multiplied by the softmax scale in the 16-bit type
 // (mixed-precision descriptors).  The launches the stream does not take go to the 8 x 32 kernel in the same 256-row blocks
 bool fwd16_p4_tr_variant(int precision, int pattern, bool fold, VariantInfo *out) {

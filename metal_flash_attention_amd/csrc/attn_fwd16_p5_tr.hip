@@ -47,8 +47,7 @@ static const char *launch_p5_tr(const Launch &l) {
   constexpr int D = p5tr::stream_bucket(STREAM), PATTERN = p5tr::stream_pattern(STREAM);
   if (!p5_tr_takes(l.args, PATTERN)) {   // the dense route of the transposed code object `out` arrived with (attn_fwd16_v3_tr_dNNN.hip)
     VariantInfo tr;
-    (D == 160 ? fwd16_v3_tr_variant_d160 : D == 192 ? fwd16_v3_tr_variant_d192 : fwd16_v3_tr_variant_d256)(
-        std::is_same<T, __bf16>::value ? PREC_BF16 : PREC_FP16, D, PATTERN, &tr);
+    fwd16_v3_tr_variant(std::is_same<T, __bf16>::value ? PREC_BF16 : PREC_FP16, D, PATTERN, &tr);
     return tr.dense.launch(l);
   }
   // l.grid counts the transposed code object's 128-row blocks; this kernel's take 256 rows
@@ -68,7 +67,7 @@ template <typename T, int STREAM> static void attach(VariantInfo *v) {
   v->ldsBytes = v->ldsBytes > (uint32_t)p5::LDS_BYTES ? v->ldsBytes : (uint32_t)p5::LDS_BYTES;
 }
 
-// `out` arrives filled by fwd16_v3_tr_variant_d160 / _d192 / _d256 for `pattern` (bit 0 = K, bit 1 = V transposed; 0 = only Q / O:
+// `out` arrives filled by fwd16_v3_tr_variant of the bucket for `pattern` (bit 0 = K, bit 1 = V transposed; 0 = only Q / O:
 // nothing to do): launches the stream can take go to it, the others stay.  fold: Q pre-multiplied by the softmax scale in the 16-bit
 // type (mixed-precision descriptors)
 bool fwd16_p5_tr_variant(int precision, int bucket, int pattern, bool fold, VariantInfo *out) {

@@ -24,6 +24,8 @@ namespace mfa {
 // priority, packed-VALU softmax, K fragments requested one step ahead on top of LDS-DMA (+0.5 %); at D = 64, 64
 // rows per wave with two waves per SIMD (+-0).
 bool fwd16_v3_variant(int precision, int D, int impl, VariantInfo *out) {
+  if (D == 160) return impl == 0 && fwd16_v3_variant_d160(precision, out);
+  if (D == 192) return impl == 0 && fwd16_v3_variant_d192(precision, out);
   if (precision == PREC_BF16) {
     if (D == 128 && impl == 0) { fill_with_split<__bf16, 128, 8, 1, 8, 1, 3, 36>(out, "attn_fwd16v3_bf16_d128_w8x32_thr8_ldsdma"); return true; }
 #ifdef MFA_DEV_VARIANTS
@@ -71,6 +73,17 @@ bool fwd16_v3_variant(int precision, int D, int impl, VariantInfo *out) {
     if (D == 256 && impl == 0) { fill_with_split<_Float16, 256, 4, 1, 8, 1, 2, 12>(out, "attn_fwd16v3_f16_d256_w4x32_thr8_ring2_spread"); return true; }
   }
   return false;
+}
+
+bool fwd16_v3_tr_variant(int precision, int D, int pattern, VariantInfo *out) {
+  switch (D) {
+    case 32: case 64: return fwd16_v3_tr_variant_d64(precision, D, pattern, out);
+    case 128: return fwd16_v3_tr_variant_d128(precision, D, pattern, out);
+    case 160: return fwd16_v3_tr_variant_d160(precision, D, pattern, out);
+    case 192: return fwd16_v3_tr_variant_d192(precision, D, pattern, out);
+    case 256: return fwd16_v3_tr_variant_d256(precision, D, pattern, out);
+    default: return false;
+  }
 }
 
 // dense launches of the D = 64 bucket that the persistent kernel (attn_fwd16_p6.hip) does not serve

@@ -109,4 +109,13 @@ static void fill_tr(VariantInfo *v, const char *name) {
     default: return false;                                                                                                         \
   }
 
+// the family's buckets that have a translation unit each, behind fwd16_v3_variant / fwd16_v3_tr_variant (attn_fwd16_v3.hip)
+bool fwd16_v3_variant_d160(int precision, VariantInfo *out);
+bool fwd16_v3_variant_d192(int precision, VariantInfo *out);
+bool fwd16_v3_tr_variant_d64(int precision, int D, int pattern, VariantInfo *out);   // buckets 32, 64
+bool fwd16_v3_tr_variant_d128(int precision, int D, int pattern, VariantInfo *out);
+bool fwd16_v3_tr_variant_d160(int precision, int D, int pattern, VariantInfo *out);
+bool fwd16_v3_tr_variant_d192(int precision, int D, int pattern, VariantInfo *out);
+bool fwd16_v3_tr_variant_d256(int precision, int D, int pattern, VariantInfo *out);
+
 } // namespace mfa

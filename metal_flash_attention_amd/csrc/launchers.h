@@ -94,8 +94,12 @@ bool generic_dkv_variant(int DP, VariantInfo *out);
 bool fwd16_variant(int precision, int D, VariantInfo *out);
 // software-pipelined version; impl selects an experimental schedule (see attn_fwd16_v2.hip)
 bool fwd16_v2_variant(int precision, int D, int impl, VariantInfo *out);
-// one wave per SIMD, 64 query rows per wave, half-tile pipeline (see attn_fwd16_v3.h)
+// one wave per SIMD, 64 query rows per wave, half-tile pipeline (see attn_fwd16_v3.h); D = the head-dimension bucket: 32, 64, 128, 256
+// (attn_fwd16_v3.hip) and 160, 192 (a translation unit each).  Like every family entry: false = no code object for these arguments
 bool fwd16_v3_variant(int precision, int D, int impl, VariantInfo *out);
+// operands stored transposed, read in place (TR kernels of attn_fwd16_v3.h): pattern bit 0 = K, bit 1 = V transposed (Q / O: any);
+// buckets 32 .. 256
+bool fwd16_v3_tr_variant(int precision, int D, int pattern, VariantInfo *out);
 // four waves x 64 rows, one wave per SIMD, hand-placed instruction stream (attn_fwd16_p4.h); D <= 128 only
 bool fwd16_p4_variant(int precision, int D, int impl, VariantInfo *out);
 // D <= 64: four waves x 64 rows, persistent (attn_fwd16_p6.h; fold = the descriptor holds the attention matrix in 16-bit registers:
@@ -123,38 +127,25 @@ bool dq16_p4_variant(int precision, int gprecision, int D, int impl, VariantInfo
 // 8 waves x 32 rows, SIMD partners alternate matrix / vector segments (see attn_fwd16_v4.h)
 bool fwd16_v4_variant(int precision, int D, int impl, VariantInfo *out);
 
-// 16-bit MFMA backward kernels (Q, K, V, dO in one 16-bit type, row-major, D in {64, 128, 256})
-// (gprecision = storage type of dO: the same 16-bit type, or BF16 next to FP16 Q/K/V)
+// 16-bit MFMA backward kernels (Q, K, V, dO in one 16-bit type, row-major; gprecision = storage type of dO: the same 16-bit type,
+// or BF16 next to FP16 Q/K/V).  D = the head-dimension bucket: dQ 64, 128, 160, 192, 256; dK/dV one wave per key block 64, 128
 bool dq16_variant(int precision, int gprecision, int D, VariantInfo *out);
 bool dkv16_variant(int precision, int gprecision, int D, VariantInfo *out);
-// role-split wave pairs: one wave of a SIMD accumulates dV, its partner dK (see attn_dkv16_rs.h)
+// role-split wave pairs: one wave of a SIMD accumulates dV, its partner dK (see attn_dkv16_rs.h); buckets 64, 96, 128, 160, 192, 256.
+// The buckets 160 / 192 of the trio and 96 of this kernel have a translation unit each.  Measured at N = 4096, 64 heads
+// (profiles/r02_bucket_perf.txt): the 96-wide forward and dQ objects LOSE to the 128 objects run on zero-padded chunks (0.576 vs
+// 0.499 ms, 0.885 vs 0.781 ms) and are not built; dK/dV wins at 96 (1.02 vs 1.18 ms)
 bool dkv16_rs_variant(int precision, int gprecision, int D, int impl, VariantInfo *out);
 
-// head-dimension buckets 160 / 192 of the 16-bit trio and 96 of the dK/dV kernel (one translation unit per kernel type and
-// bucket).  Measured at N = 4096, 64 heads (profiles/r02_bucket_perf.txt): the 96-wide forward and dQ objects LOSE to the 128
-// objects run on zero-padded chunks (0.576 vs 0.499 ms, 0.885 vs 0.781 ms) and are not built; dK/dV wins at 96 (1.02 vs 1.18 ms)
-bool fwd16_v3_variant_d160(int precision, VariantInfo *out);
-bool fwd16_v3_variant_d192(int precision, VariantInfo *out);
-// operands stored transposed, read in place (TR kernels of attn_fwd16_v3.h): pattern bit 0 = K, bit 1 = V transposed (Q / O: any)
-bool fwd16_v3_tr_variant_d64(int precision, int D, int pattern, VariantInfo *out);   // buckets 32, 64
-bool fwd16_v3_tr_variant_d128(int precision, int D, int pattern, VariantInfo *out);
-bool fwd16_v3_tr_variant_d160(int precision, int D, int pattern, VariantInfo *out);
-bool fwd16_v3_tr_variant_d192(int precision, int D, int pattern, VariantInfo *out);
-bool fwd16_v3_tr_variant_d256(int precision, int D, int pattern, VariantInfo *out);
 // K and / or V transposed at D <= 128 (pattern: bit 0 = K, bit 1 = V): launches of whole chunks of aligned rows run the hand-placed
-// stream (attn_fwd16_p4_tr.h); `out` arrives filled by fwd16_v3_tr_variant_d128, whose kernel keeps the others
+// stream (attn_fwd16_p4_tr.h); `out` arrives filled by fwd16_v3_tr_variant at bucket 128, whose kernel keeps the others
 bool fwd16_p4_tr_variant(int precision, int pattern, bool fold, VariantInfo *out);
-bool dq16_variant_d160(int precision, int gprecision, VariantInfo *out);
-bool dq16_variant_d192(int precision, int gprecision, VariantInfo *out);
-bool dkv16_rs_variant_d96(int precision, int gprecision, VariantInfo *out);
-bool dkv16_rs_variant_d160(int precision, int gprecision, VariantInfo *out);
-bool dkv16_rs_variant_d192(int precision, int gprecision, VariantInfo *out);
 
 // backward kernels that read transposed operands in place (attn_bwd16_p4_tr.hip; l.grid = (row or column blocks, heads, batches)):
 // the launch form's text, nullptr = not a launch these kernels take (nothing is started then)
 const char *bwd16_p4_tr_launch(int type, bool fold, const Launch &l);
 // launches with K^T and / or V^T at the buckets 160 / 192 / 256 that are whole 32-key steps of aligned rows go
-// to the hand-placed stream (attn_fwd16_p5_tr.h); `out` arrives filled by fwd16_v3_tr_variant_dNN, whose kernel keeps the others
+// to the hand-placed stream (attn_fwd16_p5_tr.h); `out` arrives filled by fwd16_v3_tr_variant of the bucket, whose kernel keeps the others
 bool fwd16_p5_tr_variant(int precision, int bucket, int pattern, bool fold, VariantInfo *out);
 
 // grouped-query backwardKeyValue (attn_kv_group_sum.hip): dK / dV head j = sum over g < G, in order, of the fp32 slabs

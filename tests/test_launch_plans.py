@@ -31,7 +31,7 @@ Op = AttentionOperand
 P = GEMMOperandPrecision
 ROW_OPS = (Op.Q, Op.O, Op.dO, Op.dQ)
 MATRIX_OPS = (Op.Q, Op.K, Op.V, Op.O, Op.dO, Op.dQ, Op.dK, Op.dV)
-HEADS = (8, 32, 48, 64, 96, 128, 136, 160, 192, 256, 320, 384, 1000)
+HEADS = (8, 16, 30, 32, 48, 64, 96, 100, 128, 136, 160, 192, 256, 320, 384, 1000)
 
 
 def descriptors():
@@ -42,7 +42,7 @@ def descriptors():
     transposes = {"rm": (False,) * 4, "kv": (False, True, True, False), "k": (False, True, False, False),
                   "v": (False, False, True, False), "all": (True,) * 4}
     grid = [(D, sname, "rm") for D in HEADS for sname in storage]
-    grid += [(D, sname, tname) for D in (32, 64, 128, 192, 256, 320) for sname, tnames in
+    grid += [(D, sname, tname) for D in (32, 64, 128, 160, 192, 256, 320) for sname, tnames in
              (("bf16", ("kv", "k", "v", "all")), ("f16mid", ("kv", "all")), ("f32", ("all",))) for tname in tnames]
     for D, sname, tname in grid:
         d = AttentionDescriptor()
@@ -55,13 +55,19 @@ def descriptors():
             except MFAError as e:
                 yield key, ("E", e.status, str(e))
                 continue
-            if D not in (64, 128, 192) or sname not in ("f32", "bf16mid") or tname not in ("rm", "all"):
-                continue
-            variants = [("/strict", dict(strictBlockDimensions=True))]
-            if tname == "rm" and D != 192:   # non-default table rows: other block dimensions and cache states, strict and not
-                variants += [("/row%dx%dx%d%s" % (row + ("/strict" * s,)), dict(blockDimensions=row, strictBlockDimensions=s))
-                             for row in ((64, 32, 64), (32, 64, 128), (256, 64, 128)) for s in (False, True)]
-                variants.append(("/uncached", dict(cacheState="none")))
+            variants, rows = [], []
+            if D in (64, 128, 192) and sname in ("f32", "bf16mid") and tname in ("rm", "all"):
+                variants = [("/strict", dict(strictBlockDimensions=True))]
+                if tname == "rm" and D != 192:   # non-default table rows: other block dimensions and cache states, strict and not
+                    rows = [(64, 32, 64), (32, 64, 128), (256, 64, 128)]
+                    variants.append(("/uncached", dict(cacheState="none")))
+            if D in (32, 64, 96, 160, 256) and (sname, tname) == ("bf16mid", "rm"):
+                # the rows that select a sibling code object of the bucket: the 32-row dQ waves and 32-key dK/dV pairs in front of
+                # which a hand-placed kernel stands, the 96-wide dK/dV pairs, the eight-wave forward kernels of D <= 64.  Every
+                # row goes to every kernel type: one that matches nothing pins the nearest candidate and the strict error text
+                rows += [r for r in ((128, 64, D), (64, 32, D), (128, 32, 96), (256, 32, 64), (256, 64, 64)) if r not in rows]
+            variants += [("/row%dx%dx%d%s" % (row + ("/strict" * s,)), dict(blockDimensions=row, strictBlockDimensions=s))
+                         for row in rows for s in (False, True)]
             for suffix, change in variants:
                 k = d.kernelDescriptor(t)
                 for name, value in change.items():
