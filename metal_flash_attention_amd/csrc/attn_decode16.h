@@ -32,28 +32,18 @@
 //     the un-normalised O they publish, so that the combine kernel needs no change).  The 16-bit kernels read neither.
 //   * poison: rows at or past the piece's end are not loaded (zero bytes = +0.0), so a 0x7f beyond a length never reaches a product.
 //
-// WINDOW: the same body under a sliding window of a.window >= 1 keys (include/mfa_window.h): row r sees the keys
-// lo(r) <= c < lim(r), lo = max(f + 1, W) - W behind its causal frontier f.  What the parameter switches:
-//   * the keys the workgroup walks come from decode_window_piece_range, in the unsplit kernel too (one piece of one): they start at
-//     the tile of row 0's first key, and nothing below it is loaded -- no key, no page, no block-table entry (group_offsets is only
-//     ever asked for keys at or past `begin`).
-//   * the mask is one unsigned comparison c - lo < lim - lo in both places; a masked score is still replaced, never multiplied.
-//   * pieces may be empty: they publish m = -FLT_MAX, l = 0 and zeros, which the combine kernel already weighs with 0.
-// With W >= column + rows every lo is 0 and the ranges are decode_piece_range's: the plain kernel's arithmetic in the plain order.
-//
-// SINK: the WINDOW body with attention sinks (include/mfa_sink.h); a.window = 0 is "lo = 0 everywhere".
-//   * sink TOKENS, a.sinkTokens = S: row r also sees the keys c < slim = min(S, lim).  The workgroup walks a piece of the tile LIST
-//     [0, sinkTiles) ++ [first, last) (decode_sink_piece_range): at most two key ranges.  The loop runs over the list's own key
-//     positions -- `key0` counts keys of the piece, sink range first -- and list_key() turns a position into the cache's key where
-//     one is addressed or masked; nothing between the two ranges is loaded, no key, no page, no block-table entry.
-//     The mask is (c - lo < span) || (c < slim) per lane.
-//   * sink LOGIT, a.sinkLogits[query head] (natural units; null: none): one more term of the denominator, s2 = sink log2(e),
-//     never scaled by 1 / sqrt(D) or keyScale.  The unsplit kernel adds it at the final normalisation; in the split kernels piece 0
-//     folds it into the (m, l) it publishes -- an empty piece 0 publishes m = s2, l = 1, O = 0 -- so the combine kernel is reused as
-//     it stands.  A row without a visible key: O = 0, L = s2.
-// With S = 0 and no logits the SINK kernels run the WINDOW kernels' arithmetic in their order.
+// WINDOW, SINK: the rule of which keys a row sees, and the sink logit, are attn_cache_step.h's.  What is decode's own:
+//   * WINDOW: the keys the workgroup walks come from decode_window_piece_range, in the unsplit kernel too (one piece of one): they
+//     start at the tile of row 0's first key, and nothing below it is loaded -- no key, no page, no block-table entry (group_offsets
+//     is only ever asked for keys at or past `begin`).  Pieces may be empty: they publish m = -FLT_MAX, l = 0 and zeros, which the
+//     combine kernel already weighs with 0.  With W >= column + rows the ranges are decode_piece_range's.
+//   * SINK tokens: the workgroup walks a piece of the tile LIST [0, sinkTiles) ++ [first, last) (decode_sink_piece_range): at most two
+//     key ranges.  The loop runs over the list's own key positions -- `key0` counts keys of the piece, sink range first -- and
+//     list_key() turns a position into the cache's key where one is addressed or masked; nothing between the two ranges is loaded.
+//   * SINK logit: the unsplit kernel adds it at the final normalisation; in the split kernels piece 0 folds it into the (m, l) it
+//     publishes -- an empty piece 0 publishes m = s2, l = 1, O = 0 -- so the combine kernel is reused as it stands.
 #pragma once
-#include "attn_fwd16_common.h"
+#include "attn_cache_step.h"
 #include "kv_e4m3.h"
 
 namespace mfa {
@@ -61,7 +51,6 @@ namespace mfa {
 constexpr int DEC_KEY_TILE = 64;   // pieces are whole tiles of this many keys (MFA_DECODE_KEY_TILE)
 constexpr int DEC_STEP = 32;       // keys per wave step
 constexpr int DEC_WAVES = 4;
-constexpr float DEC_MINUS_HUGE = -3.402823466e+38f;
 
 struct DecodeArgs {
   const char *q, *k, *v;
@@ -87,44 +76,15 @@ struct DecodeArgs {
   const float *sinkLogits;              // [Hq], natural units; null: none
 };
 
-// keys [*begin, *end) of piece `piece` of `pieces` for a sequence of `length` keys: an equal share of the sequence's whole 64-key
-// tiles; only the last tile of the sequence may be partial.  Device and host (mfa_attention_decode_piece_range) run this one body.
-__host__ __device__ __forceinline__ void decode_piece_range(uint32_t length, uint32_t pieces, uint32_t piece, uint32_t *begin,
-                                                            uint32_t *end) {
-  const uint64_t tiles = ((uint64_t)length + DEC_KEY_TILE - 1) / DEC_KEY_TILE;
-  const uint64_t t0 = (uint64_t)piece * tiles / pieces, t1 = ((uint64_t)piece + 1) * tiles / pieces;
-  uint64_t b = t0 * DEC_KEY_TILE, e = t1 * DEC_KEY_TILE;
-  if (e > length) e = length;
-  if (b > e) b = e;
-  *begin = (uint32_t)b;
-  *end = (uint32_t)e;
-}
-
-// keys [*begin, *end) of piece `piece` of `pieces` under a window of `window` >= 1 keys: with lo0 the first key row 0 sees, an equal
-// share, in whole tiles, of the tiles [lo0 / 64, ceil(length / 64)) -- the tiles that hold a key some row sees.  Device and host
-// (mfa_attention_decode_window_piece_range) run this one body.
-__host__ __device__ __forceinline__ void decode_window_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t pieces,
-                                                                   uint32_t piece, uint32_t *begin, uint32_t *end) {
-  const uint64_t f1 = (length > rows ? (uint64_t)length - rows : 0) + 1;   // row 0's frontier + 1
-  const uint64_t lo0 = (f1 > window ? f1 : (uint64_t)window) - window;
-  const uint64_t first = lo0 / DEC_KEY_TILE, last = ((uint64_t)length + DEC_KEY_TILE - 1) / DEC_KEY_TILE;
-  const uint64_t tiles = last > first ? last - first : 0;
-  const uint64_t t0 = first + (uint64_t)piece * tiles / pieces, t1 = first + ((uint64_t)piece + 1) * tiles / pieces;
-  uint64_t b = t0 * DEC_KEY_TILE, e = t1 * DEC_KEY_TILE;
-  if (e > length) e = length;
-  if (b > e) b = e;
-  *begin = (uint32_t)b;
-  *end = (uint32_t)e;
-}
-
 // The two key ranges of piece `piece` of `pieces` with `sinkTokens` sink keys under a window of `window` keys (0: no window, lo0 = 0):
-// with first, last as above and sinkTiles = min(ceil(min(S, length) / 64), first), an equal share, in whole tiles, of the LIST
-// [0, sinkTiles) ++ [first, last): [begin[0], end[0]) inside the sink tiles, [begin[1], end[1]) inside the window's; both clamped as
-// above.  Device and host (mfa_attention_decode_sink_piece_range) run this one body.
+// with lo0 the first key row 0 sees, first = lo0 / 64, last = ceil(length / 64) -- [first, last) are the tiles that hold a key some row
+// sees through its window -- and sinkTiles = min(ceil(min(S, length) / 64), first), an equal share, in whole 64-key tiles, of the LIST
+// [0, sinkTiles) ++ [first, last): [begin[0], end[0]) inside the sink tiles, [begin[1], end[1]) inside the window's; only the last tile
+// of the sequence may be partial.  Device and host (mfa_attention_decode_sink_piece_range) run this one body.
 __host__ __device__ __forceinline__ void decode_sink_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t sinkTokens,
                                                                  uint32_t pieces, uint32_t piece, uint32_t *begin, uint32_t *end) {
   const uint64_t f1 = (length > rows ? (uint64_t)length - rows : 0) + 1;   // row 0's frontier + 1
-  const uint64_t lo0 = window ? (f1 > window ? f1 : (uint64_t)window) - window : 0;
+  const uint64_t lo0 = window ? window_lo<uint64_t>(f1, window) : 0;
   const uint64_t first = lo0 / DEC_KEY_TILE, last = ((uint64_t)length + DEC_KEY_TILE - 1) / DEC_KEY_TILE;
   const uint64_t sunk = sinkTokens < length ? sinkTokens : length;
   uint64_t sinkTiles = (sunk + DEC_KEY_TILE - 1) / DEC_KEY_TILE;
@@ -142,6 +102,25 @@ __host__ __device__ __forceinline__ void decode_sink_piece_range(uint32_t length
   }
 }
 
+// keys [*begin, *end) of a piece under a window of `window` >= 1 keys and no sink tokens: the list is [first, last) alone
+// (mfa_attention_decode_window_piece_range)
+__host__ __device__ __forceinline__ void decode_window_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t pieces,
+                                                                   uint32_t piece, uint32_t *begin, uint32_t *end) {
+  uint32_t b[2], e[2];
+  decode_sink_piece_range(length, rows, window, 0, pieces, piece, b, e);
+  *begin = b[1];
+  *end = e[1];
+}
+
+// keys [*begin, *end) of a piece without a window: an equal share of all the sequence's tiles (mfa_attention_decode_piece_range)
+__host__ __device__ __forceinline__ void decode_piece_range(uint32_t length, uint32_t pieces, uint32_t piece, uint32_t *begin,
+                                                            uint32_t *end) {
+  uint32_t b[2], e[2];
+  decode_sink_piece_range(length, 1, 0, 0, pieces, piece, b, e);
+  *begin = b[1];
+  *end = e[1];
+}
+
 template <int D> constexpr int decode16_lds_bytes() {
   constexpr int images = DEC_WAVES * DEC_STEP * D * 2;
   constexpr int merge = DEC_WAVES * 32 * (D + 4) * 4 + 2 * DEC_WAVES * 32 * 4;
@@ -150,7 +129,6 @@ template <int D> constexpr int decode16_lds_bytes() {
 
 template <typename T, int D, bool SPLIT, bool FP8, bool WINDOW = false, bool SINK = false>
 __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
-  static_assert(!SINK || WINDOW, "the sink kernels are the window kernels plus SINK");
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -203,18 +181,8 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
       qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + d0 * 2));
     }
   }
-  // keys this row sees: c < lim  (causal: c <= row + max(len - R, 0); always c < len, and inside this piece c < end)
-  uint32_t lim = SINK ? len : end;
-  if (a.causal) lim = min(lim, qrow + (len > R ? len - R : 0u) + 1u);
-  // WINDOW: and c >= lo = max(f + 1, W) - W; `span` = lim - lo keys from lo on (none: 0), so that visible is c - lo < span, unsigned
-  uint32_t lo = 0, span = 0;
-  if constexpr (WINDOW) {
-    const uint32_t f1 = qrow + (len > R ? len - R : 0u) + 1u;
-    lo = max(f1, a.window) - a.window;
-    if constexpr (SINK) lo = a.window ? lo : 0u;
-    span = lim > lo ? lim - lo : 0u;
-  }
-  const uint32_t slim = SINK ? min(a.sinkTokens, lim) : 0u;   // SINK: and the keys c < slim
+  // keys this row sees (causal: c <= row + max(len - R, 0); always c < len, and inside this piece c < end)
+  const VisibleKeys<WINDOW, SINK> keys(SINK ? len : end, qrow + (len > R ? len - R : 0u) + 1u, a.causal, a.window, a.sinkTokens);
 
   // ---- addresses of a step's two 16-key groups (wave-uniform; element offsets from a.k / a.v, which are byte offsets under FP8)
   const int64_t khead = (int64_t)kvh * a.hsk, vhead = (int64_t)kvh * a.hsv;
@@ -266,17 +234,14 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
   };
 
   f32x16 o[NDB];
-  float m = DEC_MINUS_HUGE, l = 0.f;
+  float m = STEP_MINUS_HUGE, l = 0.f;
 #pragma unroll
   for (int db = 0; db < NDB; ++db)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
 
   char *Vs = smem + wave * IMAGE;   // this wave's V image: [D/32][32 keys][32 d]
-  // tr read: lane n of a 16-lane group supplies row (n>>2), columns 4*(n&3)..+3 of a [4][16] block;
-  // group (lane>>4): bit0 = d half of the 32-wide d block, bit1 = hi   (dev/attn_fwd16.h)
-  const int n16 = lane & 15;
-  const int vtr_off = ((n16 >> 2) + 4 * hi) * 64 + (((lane >> 4) & 1) * 16 + 4 * (n16 & 3)) * 2;
+  const int vtr_off = vtr_lane_offset(lane, hi);
 
   uint32_t key0 = begin + (uint32_t)wave * DEC_STEP;
   if (key0 < end) issue_loads(key0);
@@ -313,50 +278,16 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     if (key0 < end) issue_loads(key0);
 
     // ---- online softmax over the visible keys only (FP8: the K scale rides on the softmax scale)
-    float mx = DEC_MINUS_HUGE;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const bool visible = SINK     ? (cur + (uint32_t)crow(r, hi) - lo < span) | (cur + (uint32_t)crow(r, hi) < slim)
-                           : WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span
-                                    : cur + (uint32_t)crow(r, hi) < lim;
-      s[r] = visible ? s[r] * kscale : DEC_MINUS_HUGE;
-      mx = fmaxf(mx, s[r]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    if (mx > m) {
-      const float corr = fast_exp2(m - mx);
-      m = mx;
-      l *= corr;
-#pragma unroll
-      for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] *= corr;
-    }
-    float psum = 0.f;
+    rescale_row(score_max<true>(s, keys, cur, hi, kscale), m, l, o);
     v8 pf[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const bool visible = SINK     ? (cur + (uint32_t)crow(r, hi) - lo < span) | (cur + (uint32_t)crow(r, hi) < slim)
-                           : WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span
-                                    : cur + (uint32_t)crow(r, hi) < lim;
-      const float p = visible ? fast_exp2(s[r] - m) : 0.f;   // replaced, never multiplied
-      psum += p;
-      pf[r >> 3][r & 7] = (T)p;
-    }
-    l += psum;
+    l += score_exp<T, true>(s, keys, cur, hi, m, pf);
 
     // ---- O^T += V^T P^T
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
-      for (int db = 0; db < NDB; ++db) {
-        const char *vp = Vs + (db * DEC_STEP + 16 * u) * 64 + vtr_off;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vp));
-        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vp + 8 * 64));
-        const s16x8 both = __builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-        o[db] = F::mfma(__builtin_bit_cast(v8, both), pf[u], o[db]);
-      }
+      for (int db = 0; db < NDB; ++db) o[db] = vt_mfma<T>(Vs + (db * DEC_STEP + 16 * u) * 64 + vtr_off, pf[u], o[db]);
   }
 
   // ---- merge the four waves through LDS: m* = max m_w, weights exp2(m_w - m*), sums of l and O (FP8: the V scale multiplies what
@@ -400,14 +331,7 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     // SINK: the sink logit joins (m, l) -- piece 0's when the keys are split, the workgroup's otherwise; `fold` rescales O with l
     float fold = 1.0f;
     if constexpr (SINK) {
-      if (a.sinkLogits && piece == 0) {
-        float s2 = a.sinkLogits[head] * 1.44269504089f;
-        asm volatile("" : "+v"(s2));   // (s2 is the ROUNDED product in m and in both exponents: never fused into the subtractions below)
-        const float mnew = fmaxf(mrow, s2);
-        fold = fast_exp2(mrow - mnew);
-        lsum = lsum * fold + fast_exp2(s2 - mnew);
-        mrow = mnew;
-      }
+      if (a.sinkLogits && piece == 0) fold = fold_sink_logit(a.sinkLogits[head], mrow, lsum);
     }
     if constexpr (SPLIT) {
       const size_t slab = (((size_t)piece * a.batches + batch) * a.Hq + head) * R + row;
@@ -419,9 +343,8 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
       const float inv = lsum > 0.f ? (FP8 ? vscale : 1.0f) * fold / lsum : 0.f;   // a sequence of length 0: O = 0
       acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
       const int64_t at = (int64_t)batch * a.bso + (int64_t)head * a.hso + (int64_t)row * a.ldo + 4 * c;
-      if (a.outF32) *reinterpret_cast<float4 *>(a.o + at * 4) = acc;
-      else *reinterpret_cast<u32x2 *>(a.o + at * 2) = u32x2{pack16<T>(acc.x, acc.y), pack16<T>(acc.z, acc.w)};
-      if (c == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)head * a.lhs + row] = lsum > 0.f ? mrow + log2f(lsum) : DEC_MINUS_HUGE;
+      store_o4<T>(a.o, at, a.outF32, acc);
+      if (c == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)head * a.lhs + row] = row_lse(mrow, lsum);
     }
   }
 }
@@ -438,7 +361,7 @@ __device__ __forceinline__ void decode16_combine_body(const DecodeArgs &a) {
   if (rowid >= rows) return;
   const uint32_t row = (uint32_t)(rowid % R), bh = (uint32_t)(rowid / R);
   const uint32_t head = bh % a.Hq, batch = bh / a.Hq;
-  float ms = DEC_MINUS_HUGE, ls = 0.f;
+  float ms = STEP_MINUS_HUGE, ls = 0.f;
   if ((uint32_t)lane < S) {
     const float2 ml = *reinterpret_cast<const float2 *>(a.wsML + ((uint64_t)lane * rows + rowid) * 2);
     ms = ml.x; ls = ml.y;
@@ -470,10 +393,9 @@ __device__ __forceinline__ void decode16_combine_body(const DecodeArgs &a) {
   if (g == 0) {
     acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
     const int64_t at = (int64_t)batch * a.bso + (int64_t)head * a.hso + (int64_t)row * a.ldo + 4 * c;
-    if (a.outF32) *reinterpret_cast<float4 *>(a.o + at * 4) = acc;
-    else *reinterpret_cast<u32x2 *>(a.o + at * 2) = u32x2{pack16<T>(acc.x, acc.y), pack16<T>(acc.z, acc.w)};
+    store_o4<T>(a.o, at, a.outF32, acc);
   }
-  if (lane == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)head * a.lhs + row] = lstar > 0.f ? mstar + log2f(lstar) : DEC_MINUS_HUGE;
+  if (lane == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)head * a.lhs + row] = row_lse(mstar, lstar);
 }
 
 } // namespace mfa

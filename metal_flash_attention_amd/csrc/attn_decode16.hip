@@ -28,43 +28,17 @@ using namespace mfa;
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_decode16_d<D>_<type>_{single,pieces,combine} and, over
 // an e4m3 cache, attn_decode8_d<D>_<type of Q>_{single,pieces}, whose pieces attn_decode16_d<D>_<type>_combine merges; under a
 // sliding window attn_decode16w_* / attn_decode8w_*, with attention sinks attn_decode16s_* / attn_decode8s_*, merged by the same combine kernel
+// One list of the kernel families, (infix, WINDOW, SINK): the kernels, the table that selects them and the names are generated from it
+#define MFA_DECODE_FAMILIES(X, TN, T, D) X(, false, false, TN, T, D) X(w, true, false, TN, T, D) X(s, true, true, TN, T, D)
+#define MFA_DECODE_KERNEL(NAME, ...)                                                                                                  \
+  extern "C" __global__ __launch_bounds__(256, 2) void NAME(const DecodeArgs a) { decode_body<__VA_ARGS__>(a); }
+#define MFA_DECODE_FAMILY(I, WINDOW, SINK, TN, T, D)                                                                                  \
+  MFA_DECODE_KERNEL(attn_decode16##I##_d##D##_##TN##_single, T, D, false, false, WINDOW, SINK)                                        \
+  MFA_DECODE_KERNEL(attn_decode16##I##_d##D##_##TN##_pieces, T, D, true, false, WINDOW, SINK)                                         \
+  MFA_DECODE_KERNEL(attn_decode8##I##_d##D##_##TN##_single, T, D, false, true, WINDOW, SINK)                                          \
+  MFA_DECODE_KERNEL(attn_decode8##I##_d##D##_##TN##_pieces, T, D, true, true, WINDOW, SINK)
 #define MFA_DECODE_KERNELS(TN, T, D)                                                                                                  \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16_d##D##_##TN##_single(const DecodeArgs a) {                       \
-    decode_body<T, D, false, false>(a);                                                                                               \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16_d##D##_##TN##_pieces(const DecodeArgs a) {                       \
-    decode_body<T, D, true, false>(a);                                                                                                \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8_d##D##_##TN##_single(const DecodeArgs a) {                        \
-    decode_body<T, D, false, true>(a);                                                                                                \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8_d##D##_##TN##_pieces(const DecodeArgs a) {                        \
-    decode_body<T, D, true, true>(a);                                                                                                 \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16w_d##D##_##TN##_single(const DecodeArgs a) {                      \
-    decode_body<T, D, false, false, true>(a);                                                                                         \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16w_d##D##_##TN##_pieces(const DecodeArgs a) {                      \
-    decode_body<T, D, true, false, true>(a);                                                                                          \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8w_d##D##_##TN##_single(const DecodeArgs a) {                       \
-    decode_body<T, D, false, true, true>(a);                                                                                          \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8w_d##D##_##TN##_pieces(const DecodeArgs a) {                       \
-    decode_body<T, D, true, true, true>(a);                                                                                           \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16s_d##D##_##TN##_single(const DecodeArgs a) {                      \
-    decode_body<T, D, false, false, true, true>(a);                                                                                   \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode16s_d##D##_##TN##_pieces(const DecodeArgs a) {                      \
-    decode_body<T, D, true, false, true, true>(a);                                                                                    \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8s_d##D##_##TN##_single(const DecodeArgs a) {                       \
-    decode_body<T, D, false, true, true, true>(a);                                                                                    \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_decode8s_d##D##_##TN##_pieces(const DecodeArgs a) {                       \
-    decode_body<T, D, true, true, true, true>(a);                                                                                     \
-  }                                                                                                                                   \
+  MFA_DECODE_FAMILIES(MFA_DECODE_FAMILY, TN, T, D)                                                                                    \
   extern "C" __global__ __launch_bounds__(256) void attn_decode16_d##D##_##TN##_combine(const DecodeArgs a) {                         \
     decode16_combine_body<T, D>(a);                                                                                                   \
   }
@@ -75,30 +49,24 @@ MFA_DECODE_KERNELS(f16, _Float16, 128)
 
 namespace {
 
-typedef void (*DecodeKernel)(const DecodeArgs);
+struct DecodeKernel {
+  void (*launch)(const DecodeArgs);
+  const char *name;
+};
 struct DecodeSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  DecodeKernel single[3][2], pieces[3][2], combine;   // [0: plain, 1: window, 2: sinks][fp8]
-  const char *singleName[3][2], *piecesName[3][2], *combineName;
+  DecodeKernel kernel[3][2][2];   // [0: plain, 1: window, 2: sinks][fp8][pieces]
+  DecodeKernel combine;
 };
+#define MFA_DECODE_ENTRY(NAME) {NAME, #NAME}
+#define MFA_DECODE_SET_FAMILY(I, WINDOW, SINK, TN, T, D)                                                                              \
+  {{MFA_DECODE_ENTRY(attn_decode16##I##_d##D##_##TN##_single), MFA_DECODE_ENTRY(attn_decode16##I##_d##D##_##TN##_pieces)},            \
+   {MFA_DECODE_ENTRY(attn_decode8##I##_d##D##_##TN##_single), MFA_DECODE_ENTRY(attn_decode8##I##_d##D##_##TN##_pieces)}},
 #define MFA_DECODE_SET(TN, PREC, D)                                                                                                   \
-  {D, PREC, (uint32_t)decode16_lds_bytes<D>(),                                                                                        \
-   {{attn_decode16_d##D##_##TN##_single, attn_decode8_d##D##_##TN##_single},                                                          \
-    {attn_decode16w_d##D##_##TN##_single, attn_decode8w_d##D##_##TN##_single},                                                        \
-    {attn_decode16s_d##D##_##TN##_single, attn_decode8s_d##D##_##TN##_single}},                                                       \
-   {{attn_decode16_d##D##_##TN##_pieces, attn_decode8_d##D##_##TN##_pieces},                                                          \
-    {attn_decode16w_d##D##_##TN##_pieces, attn_decode8w_d##D##_##TN##_pieces},                                                        \
-    {attn_decode16s_d##D##_##TN##_pieces, attn_decode8s_d##D##_##TN##_pieces}},                                                       \
-   attn_decode16_d##D##_##TN##_combine,                                                                                               \
-   {{"attn_decode16_d" #D "_" #TN "_single", "attn_decode8_d" #D "_" #TN "_single"},                                                  \
-    {"attn_decode16w_d" #D "_" #TN "_single", "attn_decode8w_d" #D "_" #TN "_single"},                                                \
-    {"attn_decode16s_d" #D "_" #TN "_single", "attn_decode8s_d" #D "_" #TN "_single"}},                                               \
-   {{"attn_decode16_d" #D "_" #TN "_pieces", "attn_decode8_d" #D "_" #TN "_pieces"},                                                  \
-    {"attn_decode16w_d" #D "_" #TN "_pieces", "attn_decode8w_d" #D "_" #TN "_pieces"},                                                \
-    {"attn_decode16s_d" #D "_" #TN "_pieces", "attn_decode8s_d" #D "_" #TN "_pieces"}},                                               \
-   "attn_decode16_d" #D "_" #TN "_combine"}
+  {D, PREC, (uint32_t)decode16_lds_bytes<D>(), {MFA_DECODE_FAMILIES(MFA_DECODE_SET_FAMILY, TN, , D)},                                 \
+   MFA_DECODE_ENTRY(attn_decode16_d##D##_##TN##_combine)}
 const DecodeSet kSets[] = {MFA_DECODE_SET(bf16, MFA_BF16, 64), MFA_DECODE_SET(bf16, MFA_BF16, 128), MFA_DECODE_SET(f16, MFA_FP16, 64),
                            MFA_DECODE_SET(f16, MFA_FP16, 128)};
 
@@ -138,8 +106,9 @@ struct DecodePlan {
   uint32_t pieces;      // as the launch runs: 1 without a workspace
   uint32_t planned;     // what the host would cut the keys into
   uint32_t blocks;      // batches x K/V heads
-  // the kernel that reads the cache, and the name a HIP failure is reported under
-  const char *name() const { return pieces > 1 ? set->piecesName[family][fp8] : set->singleName[family][fp8]; }
+  // the kernel that reads the cache; its name is what a HIP failure is reported under
+  const DecodeKernel &kernel() const { return set->kernel[family][fp8][pieces > 1]; }
+  const char *name() const { return kernel().name; }
 };
 
 // every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `quant` is null for a
@@ -252,12 +221,12 @@ hipError_t run(const DecodePlan &plan, hipStream_t stream) {
   const DecodeSet &s = *plan.set;
   hipError_t err;
   if (plan.pieces > 1) {
-    err = launch_kernel(s.pieces[plan.family][plan.fp8], dim3(plan.blocks * plan.pieces), dim3(256), s.lds, stream, plan.args);
+    err = launch_kernel(plan.kernel().launch, dim3(plan.blocks * plan.pieces), dim3(256), s.lds, stream, plan.args);
     if (err != hipSuccess) return err;
     const uint64_t rows = (uint64_t)plan.args.batches * plan.args.Hq * plan.args.R;
-    err = launch_kernel(s.combine, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, plan.args);
+    err = launch_kernel(s.combine.launch, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, plan.args);
   } else {
-    err = launch_kernel(s.single[plan.family][plan.fp8], dim3(plan.blocks), dim3(256), s.lds, stream, plan.args);
+    err = launch_kernel(plan.kernel().launch, dim3(plan.blocks), dim3(256), s.lds, stream, plan.args);
   }
   if (err != hipSuccess) return err;
   return hipGetLastError();
@@ -307,7 +276,7 @@ mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quan
                              (sinks.logits ? ", sink logits" : "");
   if (plan.pieces > 1)
     std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x K/V heads x %u pieces, %u packed rows, %s) + %s (grid %llu)", plan.name(),
-                  plan.blocks * plan.pieces, plan.blocks, plan.pieces, M, layout.c_str(), plan.set->combineName,
+                  plan.blocks * plan.pieces, plan.blocks, plan.pieces, M, layout.c_str(), plan.set->combine.name,
                   (unsigned long long)(((uint64_t)plan.args.batches * plan.args.Hq * plan.args.R + 3) / 4));
   else
     std::snprintf(text, sizeof(text), "%s (grid %u sequences x K/V heads, %u packed rows, %s%s)", plan.name(), plan.blocks, M, layout.c_str(),

@@ -24,24 +24,18 @@
 //   * what may hold poison is never loaded: key rows at or past n come in as zeros (K and V), a masked score is REPLACED (p = 0 exactly),
 //     and the running maximum only ever sees visible keys -- a row without a visible key keeps m = -FLT_MAX, l = 0.
 //
-// WINDOW: the same body under a sliding window of a.window >= 1 keys (include/mfa_window.h): row r sees the keys
-// lo(r) <= c < lim(r), lo = max(f + 1, W) - W.  prefill_window_tile_range gives the block four tile indices: [begin, unmaskedBegin)
-// runs with the per-element mask (a row's window starts inside), [unmaskedBegin, unmaskedEnd) without, [unmaskedEnd, end) with it
-// again (causal frontiers and n); tiles outside [begin, end) are never loaded -- no key, no page, no block-table entry.  The first
-// load is tile `begin`, the buffer of tile t is (t - begin) & 1.  The mask is one unsigned comparison c - lo < lim - lo.  With
-// W >= column + rows: begin = unmaskedBegin = 0, unmaskedEnd = first_masked -- the plain kernel's arithmetic in the plain order.
-//
-// SINK: the WINDOW body with attention sinks (include/mfa_sink.h); a.window = 0 is "lo = 0 everywhere".
-//   * sink TOKENS, a.sinkTokens = S: row r also sees the keys c < slim = min(S, lim).  prefill_sink_tile_range adds a fifth index: a
-//     fourth loop walks the tiles [0, sinkEnd) AHEAD of the three that exist, always with the per-element mask; sinkEnd <= begin, and
-//     the tiles between them are never loaded -- no key, no page, no block-table entry.  The buffer of a tile is its POSITION in
-//     the walked list [0, sinkEnd) ++ [begin, end), not t - begin.  Every masked tile tests (c - lo < span) || (c < slim), so sink
-//     keys inside the window's own masked tiles (S reaches `begin`: the zones touch) are seen as well.
-//   * sink LOGIT, a.sinkLogits[query head] (natural units; null: none): one more term of the denominator at the normalisation,
-//     s2 = sink log2(e), never scaled by 1 / sqrt(D) or keyScale; L includes it.  A live row without a visible key: O = 0, L = s2.
-// With S = 0 and no logits the SINK kernels run the WINDOW kernels' arithmetic in their order.
+// WINDOW, SINK: the rule of which keys a row sees, and the sink logit, are attn_cache_step.h's.  What is prefill's own:
+//   * WINDOW: prefill_window_tile_range gives the block four tile indices: [begin, unmaskedBegin) runs with the per-element mask (a
+//     row's window starts inside), [unmaskedBegin, unmaskedEnd) without, [unmaskedEnd, end) with it again (causal frontiers and n);
+//     tiles outside [begin, end) are never loaded -- no key, no page, no block-table entry.  The first load is tile `begin`, the
+//     buffer of tile t is (t - begin) & 1.  With W >= column + rows: begin = unmaskedBegin = 0, unmaskedEnd = first_masked.
+//   * SINK tokens: prefill_sink_tile_range adds a fifth index: a fourth loop walks the tiles [0, sinkEnd) AHEAD of the three that
+//     exist, always with the per-element mask; sinkEnd <= begin, and the tiles between them are never loaded.  The buffer of a tile
+//     is its POSITION in the walked list [0, sinkEnd) ++ [begin, end), not t - begin.  Every masked tile tests the whole rule, so
+//     sink keys inside the window's own masked tiles (S reaches `begin`: the zones touch) are seen as well.
+//   * SINK logit: joins (m, l) at the normalisation.
 #pragma once
-#include "attn_decode16.h"
+#include "attn_cache_step.h"
 #include "kv_e4m3.h"
 #include <type_traits>
 
@@ -118,7 +112,7 @@ __host__ __device__ __forceinline__ void prefill_window_tile_range(uint32_t n, u
   uint64_t last = (uint64_t)r0 + RB;
   if (last > qn) last = qn;
   const uint64_t f1First = (uint64_t)r0 + off + 1, f1Last = last + off;
-  const uint64_t loFirst = (f1First > W ? f1First : W) - W, loLast = (f1Last > W ? f1Last : W) - W;
+  const uint64_t loFirst = window_lo(f1First, W), loLast = window_lo(f1Last, W);
   if (loFirst >= n) return;   // (n < qn: the window of the block's first row, and of every later one, lies past the keys)
   const uint64_t limFirst = f1First < n ? f1First : n, limLast = f1Last < n ? f1Last : n;
   const uint64_t b = loFirst / PF_TILE, e = (limLast + PF_TILE - 1) / PF_TILE;
@@ -228,7 +222,6 @@ template <int D> constexpr int prefill16_lds_bytes() { return 2 /*buffers*/ * 2 
 
 template <typename T, int D, bool FP8, bool WINDOW = false, bool SINK = false, bool RAGGED = false>
 __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
-  static_assert(!SINK || WINDOW, "the sink kernels are the window kernels plus SINK");
   static_assert(!RAGGED || SINK, "the ragged kernels are the sink kernels plus RAGGED");
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
@@ -286,18 +279,8 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
 #pragma unroll
     for (int s = 0; s < NKS; ++s) qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + (16 * s + 8 * hi) * 2));
   }
-  // keys this row sees: c < lim
-  uint32_t lim = n;
-  if (a.causal) lim = min(lim, row + (n > qn ? n - qn : 0u) + 1u);
-  // WINDOW: and c >= lo = max(f + 1, W) - W; `span` = lim - lo keys from lo on (none: 0), so that visible is c - lo < span, unsigned
-  uint32_t lo = 0, span = 0;
-  if constexpr (WINDOW) {
-    const uint32_t f1 = row + (n > qn ? n - qn : 0u) + 1u;
-    lo = max(f1, a.window) - a.window;
-    if constexpr (SINK) lo = a.window ? lo : 0u;
-    span = lim > lo ? lim - lo : 0u;
-  }
-  const uint32_t slim = SINK ? min(a.sinkTokens, lim) : 0u;   // SINK: and the keys c < slim
+  // keys this row sees
+  const VisibleKeys<WINDOW, SINK> keys(n, row + (n > qn ? n - qn : 0u) + 1u, a.causal, a.window, a.sinkTokens);
 
   // ---- addresses of a 16-key group (wave-uniform; element offsets from a.k / a.v)
   const int64_t ldk = a.ldk, ldv = a.ldv, psk = a.psk, psv = a.psv;   // (values, not fields of `a`: hipcc otherwise selects between
@@ -363,16 +346,13 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   };
 
   f32x16 o[NDB];
-  float m = DEC_MINUS_HUGE, l = 0.f;
+  float m = STEP_MINUS_HUGE, l = 0.f;
 #pragma unroll
   for (int db = 0; db < NDB; ++db)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
 
-  // tr read: lane n of a 16-lane group supplies row (n>>2), columns 4*(n&3)..+3 of a [4][16] block;
-  // group (lane>>4): bit0 = d half of the 32-wide d block, bit1 = hi   (dev/attn_fwd16.h)
-  const int n16 = lane & 15;
-  const int vtr_off = ((n16 >> 2) + 4 * hi) * 64 + (((lane >> 4) & 1) * 16 + 4 * (n16 & 3)) * 2;
+  const int vtr_off = vtr_lane_offset(lane, hi);
 
   // A fragment t of key row kr = 32 half + q: chunk kswz(kr, 2 t + hi).  The swizzle XORs the chunk with bits of the row that 32 half
   // does not touch, 2 t + hi = 2 t ^ hi, and a row starts on a multiple of its own size (a power of two): the byte offset is
@@ -396,48 +376,14 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
         s = F::mfma(__builtin_bit_cast(v8, kf), qf[t], s);
       }
       // ---- online softmax over the visible keys only (the K scale rides on the softmax scale)
-      float mx = DEC_MINUS_HUGE;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const bool visible = !MASK || (SINK     ? (cur + (uint32_t)crow(r, hi) - lo < span) | (cur + (uint32_t)crow(r, hi) < slim)
-                                       : WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span
-                                                : cur + (uint32_t)crow(r, hi) < lim);
-        s[r] = visible ? s[r] * kscale : DEC_MINUS_HUGE;
-        mx = fmaxf(mx, s[r]);
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      if (mx > m) {
-        const float corr = fast_exp2(m - mx);
-        m = mx;
-        l *= corr;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[db][r] *= corr;
-      }
-      float psum = 0.f;
+      rescale_row(score_max<MASK>(s, keys, cur, hi, kscale), m, l, o);
       v8 pf[2];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const bool visible = !MASK || (SINK     ? (cur + (uint32_t)crow(r, hi) - lo < span) | (cur + (uint32_t)crow(r, hi) < slim)
-                                       : WINDOW ? cur + (uint32_t)crow(r, hi) - lo < span
-                                                : cur + (uint32_t)crow(r, hi) < lim);
-        const float pr = visible ? fast_exp2(s[r] - m) : 0.f;   // replaced, never multiplied
-        psum += pr;
-        pf[r >> 3][r & 7] = (T)pr;
-      }
-      l += psum;
+      l += score_exp<T, MASK>(s, keys, cur, hi, m, pf);
       // ---- O^T += V^T P^T
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int db = 0; db < NDB; ++db) {
-          const char *vp = Vs + (db * PF_TILE + 32 * half + 16 * u) * 64 + vtr_off;
-          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vp));
-          const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vp + 8 * 64));
-          const s16x8 both = __builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-          o[db] = F::mfma(__builtin_bit_cast(v8, both), pf[u], o[db]);
-        }
+        for (int db = 0; db < NDB; ++db) o[db] = vt_mfma<T>(Vs + (db * PF_TILE + 32 * half + 16 * u) * 64 + vtr_off, pf[u], o[db]);
     }
   };
 
@@ -489,14 +435,7 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   // SINK: the sink logit joins (m, l); `fold` rescales O with l.  A row without a visible key ends with m = s2, l = 1
   float fold = 1.0f;
   if constexpr (SINK) {
-    if (a.sinkLogits) {
-      float s2 = a.sinkLogits[qhead] * 1.44269504089f;
-      asm volatile("" : "+v"(s2));   // (s2 is the ROUNDED product in m and in both exponents: never fused into the subtractions below)
-      const float mnew = fmaxf(m, s2);
-      fold = fast_exp2(m - mnew);
-      l_tot = l_tot * fold + fast_exp2(s2 - mnew);
-      m = mnew;
-    }
+    if (a.sinkLogits) fold = fold_sink_logit(a.sinkLogits[qhead], m, l_tot);
   }
   const float inv = l_tot > 0.f ? vscale * fold / l_tot : 0.f;   // a row without a visible key: O = 0
   const int64_t at = (RAGGED ? (int64_t)packed * a.ldo : (int64_t)batch * a.bso) + (int64_t)qhead * a.hso + (int64_t)rowt * a.ldo;
@@ -504,12 +443,10 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   for (int db = 0; db < NDB; ++db)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const float x0 = o[db][4 * g] * inv, x1 = o[db][4 * g + 1] * inv, x2 = o[db][4 * g + 2] * inv, x3 = o[db][4 * g + 3] * inv;
-      const int64_t e = at + 32 * db + 8 * g + 4 * hi;
-      if (a.outF32) *reinterpret_cast<float4 *>(a.o + e * 4) = make_float4(x0, x1, x2, x3);
-      else *reinterpret_cast<u32x2 *>(a.o + e * 2) = u32x2{pack16<T>(x0, x1), pack16<T>(x2, x3)};
+      const float4 x = make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
+      store_o4<T>(a.o, at + 32 * db + 8 * g + 4 * hi, a.outF32, x);
     }
-  if (hi == 0 && a.l) a.l[(RAGGED ? (int64_t)packed : (int64_t)batch * a.lbs) + (int64_t)qhead * a.lhs + rowt] = l_tot > 0.f ? m + log2f(l_tot) : DEC_MINUS_HUGE;
+  if (hi == 0 && a.l) a.l[(RAGGED ? (int64_t)packed : (int64_t)batch * a.lbs) + (int64_t)qhead * a.lhs + rowt] = row_lse(m, l_tot);
 }
 
 } // namespace mfa

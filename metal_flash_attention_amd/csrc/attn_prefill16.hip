@@ -25,31 +25,16 @@ using namespace mfa;
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_prefill16_d<D>_<type>[_e4m3], and attn_prefill16w_*
 // under a sliding window, attn_prefill16s_* with attention sinks, attn_prefill16r_* over packed rows (the sink body: one ragged kernel
 // serves plain, window and sink launches)
-#define MFA_PREFILL_KERNELS(TN, T, D)                                                                                                 \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16_d##D##_##TN(const PrefillArgs a) {                              \
-    prefill16_body<T, D, false>(a);                                                                                                   \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16_d##D##_##TN##_e4m3(const PrefillArgs a) {                       \
-    prefill16_body<T, D, true>(a);                                                                                                    \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16w_d##D##_##TN(const PrefillArgs a) {                             \
-    prefill16_body<T, D, false, true>(a);                                                                                             \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16w_d##D##_##TN##_e4m3(const PrefillArgs a) {                      \
-    prefill16_body<T, D, true, true>(a);                                                                                              \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16s_d##D##_##TN(const PrefillArgs a) {                             \
-    prefill16_body<T, D, false, true, true>(a);                                                                                       \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16s_d##D##_##TN##_e4m3(const PrefillArgs a) {                      \
-    prefill16_body<T, D, true, true, true>(a);                                                                                        \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16r_d##D##_##TN(const PrefillArgs a) {                             \
-    prefill16_body<T, D, false, true, true, true>(a);                                                                                 \
-  }                                                                                                                                   \
-  extern "C" __global__ __launch_bounds__(256, 2) void attn_prefill16r_d##D##_##TN##_e4m3(const PrefillArgs a) {                      \
-    prefill16_body<T, D, true, true, true, true>(a);                                                                                  \
-  }
+// One list of the kernel families, (infix, WINDOW, SINK, RAGGED): the kernels, the table that selects them and the names are generated
+// from it
+#define MFA_PREFILL_FAMILIES(X, TN, T, D)                                                                                             \
+  X(, false, false, false, TN, T, D) X(w, true, false, false, TN, T, D) X(s, true, true, false, TN, T, D) X(r, true, true, true, TN, T, D)
+#define MFA_PREFILL_KERNEL(NAME, ...)                                                                                                 \
+  extern "C" __global__ __launch_bounds__(256, 2) void NAME(const PrefillArgs a) { prefill16_body<__VA_ARGS__>(a); }
+#define MFA_PREFILL_FAMILY(I, WINDOW, SINK, RAGGED, TN, T, D)                                                                         \
+  MFA_PREFILL_KERNEL(attn_prefill16##I##_d##D##_##TN, T, D, false, WINDOW, SINK, RAGGED)                                              \
+  MFA_PREFILL_KERNEL(attn_prefill16##I##_d##D##_##TN##_e4m3, T, D, true, WINDOW, SINK, RAGGED)
+#define MFA_PREFILL_KERNELS(TN, T, D) MFA_PREFILL_FAMILIES(MFA_PREFILL_FAMILY, TN, T, D)
 MFA_PREFILL_KERNELS(bf16, __bf16, 64)
 MFA_PREFILL_KERNELS(bf16, __bf16, 128)
 MFA_PREFILL_KERNELS(f16, _Float16, 64)
@@ -57,24 +42,20 @@ MFA_PREFILL_KERNELS(f16, _Float16, 128)
 
 namespace {
 
-typedef void (*PrefillKernel)(const PrefillArgs);
+struct PrefillKernel {
+  void (*launch)(const PrefillArgs);
+  const char *name;
+};
 struct PrefillSet {
   uint32_t D;
   int precision;
   uint32_t lds;
   PrefillKernel kernel[4][2];   // [0: plain, 1: window, 2: sinks, 3: ragged][e4m3]
-  const char *name[4][2];
 };
-#define MFA_PREFILL_SET(TN, PREC, D)                                                                                                  \
-  {D, PREC, (uint32_t)prefill16_lds_bytes<D>(),                                                                                       \
-   {{attn_prefill16_d##D##_##TN, attn_prefill16_d##D##_##TN##_e4m3},                                                                  \
-    {attn_prefill16w_d##D##_##TN, attn_prefill16w_d##D##_##TN##_e4m3},                                                                \
-    {attn_prefill16s_d##D##_##TN, attn_prefill16s_d##D##_##TN##_e4m3},                                                                \
-    {attn_prefill16r_d##D##_##TN, attn_prefill16r_d##D##_##TN##_e4m3}},                                                               \
-   {{"attn_prefill16_d" #D "_" #TN, "attn_prefill16_d" #D "_" #TN "_e4m3"},                                                           \
-    {"attn_prefill16w_d" #D "_" #TN, "attn_prefill16w_d" #D "_" #TN "_e4m3"},                                                         \
-    {"attn_prefill16s_d" #D "_" #TN, "attn_prefill16s_d" #D "_" #TN "_e4m3"},                                                         \
-    {"attn_prefill16r_d" #D "_" #TN, "attn_prefill16r_d" #D "_" #TN "_e4m3"}}}
+#define MFA_PREFILL_ENTRY(NAME) {NAME, #NAME}
+#define MFA_PREFILL_SET_FAMILY(I, WINDOW, SINK, RAGGED, TN, T, D)                                                                     \
+  {MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN), MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN##_e4m3)},
+#define MFA_PREFILL_SET(TN, PREC, D) {D, PREC, (uint32_t)prefill16_lds_bytes<D>(), {MFA_PREFILL_FAMILIES(MFA_PREFILL_SET_FAMILY, TN, , D)}}
 const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(f16, MFA_FP16, 64),
                             MFA_PREFILL_SET(f16, MFA_FP16, 128)};
 
@@ -91,8 +72,8 @@ struct PrefillPlan {
   uint32_t window;   // 0: none
   int family;        // 0: plain, 1: window, 2: sinks, 3: ragged -- the kernels' first index
   uint32_t blocks;   // batches x K/V heads x row blocks; ragged: slots x K/V heads
-  PrefillKernel kernel() const { return set->kernel[family][fp8]; }
-  const char *name() const { return set->name[family][fp8]; }
+  const PrefillKernel &kernel() const { return set->kernel[family][fp8]; }
+  const char *name() const { return kernel().name; }
 };
 
 // every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `window` 0: none;
@@ -209,7 +190,7 @@ mfa_status bind(PrefillPlan *plan, const void *q, const void *k, const void *v, 
 }
 
 hipError_t run(const PrefillPlan &plan, hipStream_t stream) {
-  const hipError_t err = launch_kernel(plan.kernel(), dim3(plan.blocks), dim3(PF_THREADS), plan.set->lds, stream, plan.args);
+  const hipError_t err = launch_kernel(plan.kernel().launch, dim3(plan.blocks), dim3(PF_THREADS), plan.set->lds, stream, plan.args);
   if (err != hipSuccess) return err;
   return hipGetLastError();
 }

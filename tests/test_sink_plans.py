@@ -214,6 +214,21 @@ def test_sink_piece_range_against_the_tile_list():
     assert AttentionDecode.sinkPieceRange(2 ** 32 - 1, 1, 2 ** 32 - 1, 2 ** 32 - 1, 64, 63)[1][1] == 2 ** 32 - 1
 
 
+def test_the_three_decode_piece_ranges_nest():
+    """the plain range is the window range of a window nothing falls out of; the window range is the sink range without sink tokens"""
+    for n in (0, 1, 63, 64, 65, 1000):
+        for pieces in (1, 3, 7):
+            for R in (1, 2, 32):
+                plain = [AttentionDecode.pieceRange(n, pieces, p) for p in range(pieces)]
+                for W in (n + R, n + R + 1, 2 ** 32 - 1):
+                    assert [AttentionDecode.windowPieceRange(n, R, W, pieces, p) for p in range(pieces)] == plain, (n, pieces, R, W)
+                for W in (1, 64, 100, n + R):
+                    windowed = [AttentionDecode.windowPieceRange(n, R, W, pieces, p) for p in range(pieces)]
+                    sunk = [AttentionDecode.sinkPieceRange(n, R, W, 0, pieces, p) for p in range(pieces)]
+                    assert [pair[0][0] == pair[0][1] for pair in sunk] == [True] * pieces, (n, pieces, R, W, sunk)
+                    assert [pair[1] for pair in sunk] == windowed, (n, pieces, R, W)
+
+
 def test_sink_tile_range_against_the_mask():
     for W in (1, 16, 64, 65, 129, 5000):
         for S in (0, 1, 4, 64, 70, 200):
