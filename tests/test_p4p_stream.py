@@ -225,23 +225,6 @@ def test_per_batch_lengths_long_entries_use_the_branch_free_loop():
     assert wg.waves[0].count.get("s_cmp_lg_u32", 0) > 0
 
 
-@pytest.mark.parametrize("C", [64, 128, 256, 449])
-def test_merged_block_switch_experiment(C):
-    """developer stream (slower on the GPU, kept as a record): the last tile's softmax finish beside the next block's first K Q^T.
-    The model found the hazard its first form had -- no barrier between a wave's wait for its own pieces of K'(1) and the other
-    waves' reads of them -- before any GPU run."""
-    _check(3, 256, C, cfg=p4pgen.VARIANTS["BF16_FOLD_L16_MERGE"], seed=13, dma_mode="late", order=(0, 1, 2, 3))
-    _check(2, 512, C, cfg=p4pgen.VARIANTS["BF16_FOLD_L16_MERGE"], seed=14, dma_mode="early", order=(3, 2, 1, 0))
-
-
-@pytest.mark.parametrize("C", [128, 449])
-def test_fused_tail_experiment(C):
-    """developer stream (no gain on the GPU, kept as a record): the epilogue's per-block work dealt out between the last tile's
-    P V products, which run in (head-dimension block, key step, row block) order"""
-    _check(3, 256, C, cfg=p4pgen.VARIANTS["BF16_FOLD_L16_FUSE"], seed=15)
-    _check(2, 300, C, cfg=p4pgen.VARIANTS["BF16_FOLD_L16_FUSE"], seed=16, dma_mode="early", stores="early", order=(3, 2, 1, 0))
-
-
 def test_stream_file_is_current(built_library):
     """csrc/attn_fwd16_p4p_stream.inc is what tools/p4pgen.py generates"""
     path = os.path.join(os.path.dirname(__file__), "..", "metal_flash_attention_amd", "csrc", "attn_fwd16_p4p_stream.inc")
@@ -279,24 +262,3 @@ def test_column_parallel_pieces(name, R, C, splits):
         Oref, Lref = p4psim.reference(q[h], k[h], v[h], causal=False, f16=f16)
         dO, dL = np.abs(O[h] - Oref).max(), np.abs(L[h] - Lref).max()
         assert dO < 6e-3 and dL < 6e-3, (h, dO, dL)
-
-
-# ---- round 6, developer streams: O = P V with lane = column (PCfg.orow) -- rows stored straight from the registers, no LDS trip.  Measured
-# equal to the product streams (profiles/r06_p4p_epilogue.txt: the epilogue is bound by the store path, not by LDS); kept as the record
-@pytest.mark.parametrize("name", ["BF16_FOLD_L16_OROW", "BF16_EXACT_OROW", "BF16_FOLD_L16_CAUSAL_OROW"])
-def test_row_major_accumulators_give_the_same_bytes(name):
-    """same instruction multiset inside the loop, the second products' operands exchanged: every byte of O and L equals the product
-    stream's -- also behind a deferred rescale (the row's factor per REGISTER, by ds_bpermute_b32) and with D < 128, ragged rows / keys"""
-    cfg = p4pgen.VARIANTS[name]
-    base = p4pgen.VARIANTS[name[:-5]]
-    assert cfg.orow and not base.orow and name not in p4pgen.PRODUCT_STREAMS
-    C = 448
-    for kw in (dict(spike=(17, 64 * 3 + 5, 3.0), tol_o=1.2e-2, stores="late", dma_mode="late", order=(3, 2, 1, 0)), dict(D=72, ld=128, R=300)):
-        R = kw.pop("R", 256)
-        a = _check(2, R, C, cfg=cfg, seed=31, **kw)
-        b = _check(2, R, C, cfg=base, seed=31, **kw)
-        assert (a[1][0] == b[1][0]).all() and (a[1][1] == b[1][1]).all()
-        if "spike" in kw:
-            wg = a[0]
-    assert wg.waves[0].count["buffer_store_dword"] >= 2 * 128 and not wg.waves[0].count.get("buffer_store_dwordx4")
-    assert wg.waves[0].count.get("ds_bpermute_b32", 0) >= 2 * 32 + 32      # two epilogues + at least one rescale

@@ -59,22 +59,18 @@ IN_S = ["kres", "vres", "nt", "wnt", "scale2", "kinc", "vinc", "ldsk", "ldsv", "
 
 
 class Cfg:
-    def __init__(self, dtype="bf16", thr=8.0, xe=0, order_a="kb", pad=0, prof=0, fold=0, xb=40, dma="b", abl=(), xf=64, tr=0, bal=0, cap=7, maxa=1, va0=0, fastdec=0, fdpos=0):
-        """tr: bit 0 = K, bit 1 = V stored transposed (attn_fwd16_p4_tr.h)"""
-        """fold: Q arrives pre-multiplied by log2(e)/sqrt(D) and the running maximum is subtracted INSIDE the matrix pipe (an
+    # timing-only ablations are retired: every stream is complete.  The empty set stays for code that filters on it
+    abl = frozenset()
+
+    def __init__(self, dtype="bf16", thr=8.0, xe=0, prof=0, fold=0, xb=40, tr=0, bal=0, cap=7, fastdec=0):
+        """tr: bit 0 = K, bit 1 = V stored transposed (attn_fwd16_p4_tr.h)
+        fold: Q arrives pre-multiplied by log2(e)/sqrt(D) and the running maximum is subtracted INSIDE the matrix pipe (an
         extra k-step whose A operand is -1.0 and whose B operand carries m as a bf16/f16 pair): no s * scale2 - m per
         score; xb = scores per tile exponentiated in phase B already (FOLD streams only)."""
-        self.dtype, self.thr, self.xe, self.order_a, self.pad, self.prof = dtype, float(thr), xe, order_a, pad, prof
+        self.dtype, self.thr, self.xe, self.prof = dtype, float(thr), xe, prof
         self.fold, self.xb = fold, (xb if fold else 0)
-        # exact-scale streams: scores e < xe are exponentiated in phase B (behind their s * scale2 - m), scores e >= xf get
-        # that multiply-subtract in phase A(j+1) in front of their exp2 instead of in phase B(j).  xe = xf = 32 keeps the
-        # filler COUNT of both phases and moves transcendentals to phase B, where they are cheaper (ablation table, DESIGN.md)
-        self.xf = xf
-        # dma = "b": K(j+2), V(j+1) requested in phase B(j) beside the K fragment reads; "a": K(j+1), V(j) requested in the
-        # first gaps of phase A(j), where only VALU work is placed (an LDS-DMA issue next to LDS reads costs 2-3x as much)
-        self.dma = dma
-        # timing-only ablations (WRONG RESULTS; developer builds): fillers left out of the steady-state phases
-        self.abl = frozenset(abl)
+        # exact-scale streams: scores e < xe are exponentiated in phase B (behind their s * scale2 - m), where transcendentals
+        # are cheaper (ablation table, DESIGN.md)
         # tr = 1: K and V stored TRANSPOSED ([D][keys], transposeState; attn_fwd16_p4_tr.h): the LDS images keep the orientation of
         # the source -- a 16-byte chunk is 8 consecutive KEYS of one head-dimension element -- and the two read recipes change
         # places.  K^T image: [2 blocks of 32 keys][128 elements][64 bytes], a fragment = two ds_read_b64_tr_b16 (rows 16 ks + 8 h
@@ -89,23 +85,24 @@ class Cfg:
         # in front of the step's first read (vta / vtb, operands of the statement).
         self.tr = tr
         self.kt, self.vt = tr & 1, (tr >> 1) & 1
-        # bal (round 5, FOLD streams): the fillers of both phases re-dealt by ISSUE SLOTS.  A wave alone on its SIMD issues one
+        # bal = 2 (round 5): the fillers of both phases re-dealt by ISSUE SLOTS.  A wave alone on its SIMD issues one
         # instruction per ~4 clocks, a matrix instruction holds the pipe for 32: eight slots per gap, of which the matrix
         # instruction takes one, a transcendental two, anything else one (SQ_ACTIVE_INST_VALU of the round-4 stream: 1429 clocks
         # per tile = 64 x 4 + 163 x 4 + 64 x 8).  The round-2 tables put 1029 clocks of issue into phase B's 1024 and 768 into
         # phase A's, with phase A's transcendentals bunched in its last twelve gaps (up to nine slots).  Here: the row maxima of
         # the first key block move to phase A of their own tile (its score blocks are complete after 16 matrix instructions),
         # the exponentials are dealt out one per gap over the whole of phase A and up to `cap` slots per gap in phase B, the V^T
-        # reads of phase A sit in its first sixteen gaps, the K fragment reads of phase B in front of the LDS-DMA pieces (which
-        # then sit in gaps without LDS reads), the scalar bookkeeping where slots are free.  No gap above `cap` slots.
-        self.bal, self.cap, self.maxa, self.va0 = bal, cap, maxa, va0
+        # reads of phase A sit in its first sixteen gaps, the LDS-DMA pieces lead phase B (phase_b_bal), the K fragment reads follow
+        # the rescale decision, the scalar bookkeeping sits where slots are free.  No gap above `cap` slots.
+        # bal = 0: the round-2 tables (the transposed streams and the R4 baselines)
+        assert bal in (0, 2)
+        self.bal, self.cap = bal, cap
         # fastdec (FOLD streams, bal = 2): the rescale decision from ONE half-wave exchange -- the two row blocks' partial maxima
         # swapped against each other give [row maxima of block 0 | of block 1] in the two half-waves, enough for the branch; the
         # per-lane maxima of both blocks are rebuilt in the out-of-line section only (7 issue slots instead of 14 per tile)
-        self.fastdec, self.fdpos = fastdec, fdpos   # fdpos: 0 = the gap behind the last row-maximum step, 1 = behind the LDS-DMA gaps, 2 = split over two gaps
+        self.fastdec = fastdec
         assert not (fastdec and not (fold and bal == 2))
-        assert not (bal and (tr or dma != "b")), "bal: row-major K / V"
-        assert not (bal == 1 and not fold)
+        assert not (bal and tr), "bal: row-major K / V"
         # number of scores per tile whose exponential phase B takes (the rest: phase A of the next tile)
         self.nexpb = (self.xb if fold else xe) if bal else None
         # ksplit: the second key block's K fragments are requested in the first gaps of phase A (they are first multiplied sixteen
@@ -138,7 +135,7 @@ def F(v):
     return ("f", float(v))
 
 
-VCC, M0, VCC_LO, VCC_HI = ("vcc",), ("m0",), ("vcc_lo",), ("vcc_hi",)
+VCC, M0, VCC_LO = ("vcc",), ("m0",), ("vcc_lo",)
 
 
 class Ins:
@@ -209,13 +206,7 @@ class Stream:
         # loop runs -- no mask-section test, no block-switch tests, no pending-rescale test; their rare rescale decision continues in
         # the ordinary copy of the same phase (slow_dec_back: parity -> the label behind that copy's decision)
         self.fast = False
-        # orow (round 6, persistent streams with fp32 O): the second products run as O = P V (operands exchanged: A = P, B = V^T fragment)
-        # -- lane = head-dimension column, register = row -- so that the epilogue stores rows straight from the registers
-        self.orow = bool(getattr(cfg, "orow", 0))
         self.slow_dec_back = {}
-        # second partial row sum per row block, mask value: module constants unless a stream re-maps them (p4pgen, pksum)
-        self.r_lb = [T_LB, T_LB + 1]
-        self.r_maskv = T_MASKV
 
     def emit(self, op, d=None, s=(), note="", **mod):
         self.ins.append(Ins(op, d, s, mod, note))
@@ -228,8 +219,8 @@ class Stream:
         return "%s_%d" % (stem, self.uid)
 
     # ---- LDS reads with exact wait counting (LDS returns in order)
-    def lds_read(self, op, d, addr, offset, note="", src=None):
-        self.emit(op, d, [addr] + ([src] if src is not None else []), note=note, offset=offset)
+    def lds_read(self, op, d, addr, offset, note=""):
+        self.emit(op, d, [addr], note=note, offset=offset)
         self.lds_issued += 1
         return self.lds_issued      # id = position in issue order (1-based)
 
@@ -265,16 +256,12 @@ class Stream:
         self.emit("v_mfma_f32_32x32x16_" + self.cfg.dtype, d, [a, b, c])
 
     def pv(self, rb, db, f, par, u):
-        """one second-product instruction: O^T(db, rb) += V^T P^T, or (orow) O(rb, db) += P V with the same registers"""
-        a, b = vf_frag(f), p_frag(par ^ 1, rb, u)
-        if self.orow:
-            a, b = b, a
-        self.mfma(o_acc(rb, db), a, b, o_acc(rb, db))
+        """one second-product instruction: O^T(db, rb) += V^T P^T"""
+        self.mfma(o_acc(rb, db), vf_frag(f), p_frag(par ^ 1, rb, u), o_acc(rb, db))
 
     def qk_order(self):
-        if self.cfg.order_a == "kb":      # kb-major: the kb = 0 blocks complete after 16 instructions
-            return [(g // 16, g % 2, (g % 16) // 2) for g in range(32)]          # (kb, rb, ks)
-        return [((g % 4) // 2, g % 2, g // 4) for g in range(32)]                # four accumulators in rotation
+        """(kb, rb, ks) of the 32 first products, kb-major: the kb = 0 blocks complete after 16 instructions"""
+        return [(g // 16, g % 2, (g % 16) // 2) for g in range(32)]
 
     # ------------------------------------------------------------ phase A
     def qk_list(self, par):
@@ -319,47 +306,27 @@ class Stream:
                     self.emit("v_accvgpr_write_b32", A(O_BASE + 4 * g + i), [I(0)])
             if softmax:
                 if pending_pack is not None:
-                    self.sum_pack(prev, pending_pack, mfma)
+                    self.sum_pack(prev, pending_pack)
                     pending_pack = None
                 i = g - g0
-                if not cfg.fold and 0 <= i + 1 < 32:      # s * scale2 - m of the pair exponentiated in the NEXT gap
-                    for e in (2 * i + 2, 2 * i + 3):
-                        if e >= cfg.xf:
-                            self.fma_only(prev, e)
                 if 0 <= i < 32:
                     for e in (2 * i, 2 * i + 1):
-                        if e >= max(cfg.xe, cfg.xb) and not (mfma and "expa" in cfg.abl):
+                        if e >= max(cfg.xe, cfg.xb):
                             rb_, kb_, r_ = elem(e)
                             x = s_elem(prev, rb_, kb_, r_)
                             self.emit("v_exp_f32", x, [x])
                     pending_pack = 2 * i
-                if v0 <= g < v0 + 16 and not (mfma and "vreada" in cfg.abl):
+                if v0 <= g < v0 + 16:
                     vids[g - v0] = self.v_read(g - v0)
-                elif v0 <= g < v0 + 16:
-                    vids[g - v0] = 0
-            if mfma and softmax and cfg.dma == "a":   # steady state only: K(j+1) -> K image (j+1) & 1, V(j) -> V image j % 3
-                if g == 0:
-                    self.vwr_update()
-                if 2 <= g < 6:
-                    self.dma_piece("k", par ^ 1, g - 2)
-                elif 6 <= g < 10:
-                    self.dma_piece("v", par, g - 6)
-                if 4 <= g < 8:
-                    self.emit("v_add_u32_e64", VN("koff%d" % (g - 4)), [VN("koff%d" % (g - 4)), SN("kinc")], clamp=1)
-                elif 8 <= g < 12:
-                    self.emit("v_add_u32_e64", VN("voff%d" % (g - 8)), [VN("voff%d" % (g - 8)), SN("vinc")], clamp=1)
         if softmax and pending_pack is not None:
-            self.sum_pack(prev, pending_pack, mfma)
+            self.sum_pack(prev, pending_pack)
         return vids
 
-    def sum_pack(self, prev, e, steady=False):
+    def sum_pack(self, prev, e):
         rb, kb, r = elem(e)
         x0, x1 = s_elem(prev, rb, kb, r), s_elem(prev, rb, kb, r + 1)
-        if not (steady and "sum" in self.cfg.abl):
-            self.emit("v_add_f32", VN("l%d" % rb), [x0, VN("l%d" % rb)])
-            self.emit("v_add_f32", V(self.r_lb[rb]), [x1, V(self.r_lb[rb])])
-        if steady and "pack" in self.cfg.abl:
-            return
+        self.emit("v_add_f32", VN("l%d" % rb), [x0, VN("l%d" % rb)])
+        self.emit("v_add_f32", V(T_LB + rb), [x1, V(T_LB + rb)])
         # MFMA step u (16 keys) of key block kb uses registers 8 (u & 1) .. + 7
         self.emit("v_cvt_pk_%s_f32" % self.cfg.dtype, p_word(prev, rb, 2 * kb + r // 8, (r % 8) // 2), [x0, x1])
 
@@ -396,15 +363,11 @@ class Stream:
             # V^T fragments 8..15: fragment f reuses the slot of f-8, free once the two MFMAs of f-8 (gaps 2(f-8), +1) are issued
             for f in range(8, 16):
                 g0 = 2 * (f - 8) + 2
-                if softmax and "vreadb" in cfg.abl:
-                    vids[2 * f] = vids[2 * f + 1] = 0
-                    continue
                 at(g0, lambda f=f: vids.__setitem__(2 * f, self.v_read(2 * f)))
                 at(g0 + 1, lambda f=f: vids.__setitem__(2 * f + 1, self.v_read(2 * f + 1)))
         if softmax:
             for i in range(32):                      # row maxima: gaps 0..7
-                if not (mfma and "max" in cfg.abl):
-                    at(i // 4, lambda i=i: self.max_op(par, i))
+                at(i // 4, lambda i=i: self.max_op(par, i))
             at(8, lambda: self.decide_1())
             at(9, lambda: self.decide_2())
             dec_lbl = self.newlabel("DEC")
@@ -412,8 +375,7 @@ class Stream:
             if cfg.fold:
                 at(10, lambda: self.decide_4_fold(dec_lbl, first))
                 for e in range(cfg.xb):          # exp2 of the first xb scores right here: S' needs no further arithmetic
-                    if not (mfma and "expb" in cfg.abl):
-                        at(12 + e // 2 if cfg.xb <= 40 else 11 + (e * 21) // cfg.xb, lambda e=e: self.exp_in_b(par, e))
+                    at(12 + e // 2 if cfg.xb <= 40 else 11 + (e * 21) // cfg.xb, lambda e=e: self.exp_in_b(par, e))
             else:
                 at(10, lambda: self.decide_3())
                 at(11, lambda: self.decide_4(dec_lbl))
@@ -428,18 +390,16 @@ class Stream:
                 assert e == 64
             # K(j+1) fragments -> a[192:255], one per gap 12..27 (transposed streams: key block 0 here, block 1 in phase A)
             for i in range(8 if cfg.ksplit else 16):
-                if not (mfma and "kread" in cfg.abl):
-                    at(12 + i, lambda i=i: self.k_read(par ^ 1, i))
+                at(12 + i, lambda i=i: self.k_read(par ^ 1, i))
             # LDS-DMA: K(j+2) pieces in gaps 20..23, V(j+1) pieces 24..27; their offsets advance in gaps 28..31
-            if cfg.vt and cfg.dma == "b":
+            if cfg.vt:
                 at(24, lambda: self.last_v_tile())
-            for i in range(4 if cfg.dma == "b" and not (mfma and "dma" in cfg.abl) else 0):
+            for i in range(4):
                 at(20 + i, lambda i=i: self.dma_piece("k", par, i))
                 at(24 + i, lambda i=i: self.dma_piece("v", par, i))
                 at(28 + i, lambda i=i: self.emit("v_add_u32_e64", VN("koff%d" % i), [VN("koff%d" % i), SN("kinc")], clamp=1))
                 at(28 + i, lambda i=i: self.emit("v_add_u32_e64", VN("voff%d" % i), [VN("voff%d" % i), SN("vinc")], clamp=1))
-            if cfg.dma == "b":
-                at(0, lambda: self.vwr_update())
+            at(0, lambda: self.vwr_update())
             at(1, lambda: self.vrd_advance())
             if cfg.tr == 3:
                 # the eight V^T chunk addresses of the tile phase A reads next (vrd has just advanced to it; the last V^T read of
@@ -477,13 +437,12 @@ class Stream:
         exponential of tile j-1 (the scores phase B(j-1) left), one V^T read (gaps 0..15), one row-maximum step of the FIRST
         key block of tile j (gaps 17..31: its score blocks are complete behind matrix instruction 15)"""
         cfg = self.cfg
-        abl = cfg.abl if (mfma and softmax) else frozenset()
         prev = par ^ 1
         vids = {}
         if softmax:
             self.emit("v_add_u32", V(T_VADDR), [SN("vrd"), VN("vbase")], note="V^T read base of tile j-1")
         mlist = self.qk_list(par)
-        assert len(mlist) == 32 and cfg.order_a == "kb"
+        assert len(mlist) == 32
         ea = list(range(cfg.nexpb, 64))                    # exponentials left to this phase, dealt evenly over the 32 gaps
         exp_gap = {e: (t * 32) // len(ea) for t, e in enumerate(ea)} if ea else {}
         pack_gap, g_prev = {}, 0                            # pair p = elements 2p, 2p + 1: one pair per gap, in order, once ready
@@ -491,7 +450,7 @@ class Stream:
             ready = max(exp_gap.get(2 * p, -1), exp_gap.get(2 * p + 1, -1))
             g_prev = min(32, max(g_prev + 1, ready + 1))
             pack_gap[p] = g_prev
-        maxa_gap = {k: min(17 + k, 31) for k in range(16 if cfg.maxa else 0)}  # row-maximum steps of score blocks (rb0, kb0), (rb1, kb0) of THIS tile
+        maxa_gap = {k: min(17 + k, 31) for k in range(16)}  # row-maximum steps of score blocks (rb0, kb0), (rb1, kb0) of THIS tile
         for g in range(33):
             if g < 32 and mfma:
                 self.mfma(*mlist[g])
@@ -501,42 +460,28 @@ class Stream:
             if softmax:
                 for p in range(32):
                     if pack_gap[p] == g:
-                        self.sum_pack_abl(prev, 2 * p, abl)
+                        self.sum_pack(prev, 2 * p)
                 for e in ea:
-                    if exp_gap[e] == g and "exp" not in abl:
+                    if exp_gap[e] == g:
                         rb_, kb_, r_ = elem(e)
                         x = s_elem(prev, rb_, kb_, r_)
                         self.emit("v_exp_f32", x, [x])
-                if cfg.va0 <= g < cfg.va0 + 16:
-                    vids[g - cfg.va0] = self.v_read(g - cfg.va0) if "lds" not in abl else 0
+                if g < 16:
+                    vids[g] = self.v_read(g)
             if mfma and g < 32:
                 for k in maxa_gap:
-                    if maxa_gap[k] == g and "max" not in abl:
+                    if maxa_gap[k] == g:
                         self.max_op(par, k)
         return vids
 
-    def sum_pack_abl(self, prev, e, abl):
-        rb, kb, r = elem(e)
-        x0, x1 = s_elem(prev, rb, kb, r), s_elem(prev, rb, kb, r + 1)
-        if "sum" not in abl and getattr(self.cfg, "pksum", 0):
-            # (l, second partial sum) are an aligned register pair: both additions in one packed instruction
-            lp = V(self.r_lb[rb] - 1, 2)
-            self.emit("v_pk_add_f32", lp, [V(x0[1], 2), lp])
-        elif "sum" not in abl:
-            self.emit("v_add_f32", VN("l%d" % rb), [x0, VN("l%d" % rb)])
-            self.emit("v_add_f32", V(self.r_lb[rb]), [x1, V(self.r_lb[rb])])
-        if "pack" not in abl:
-            self.emit("v_cvt_pk_%s_f32" % self.cfg.dtype, p_word(prev, rb, 2 * kb + r // 8, (r % 8) // 2), [x0, x1])
-
     def phase_b_bal(self, par, mfma, softmax, vids):
-        """B(j) dealt by issue slots: row maxima of the second key block (gaps 0..3), decision (4..6), exponentials from gap 7
-        wherever a gap has two slots left below `cap`, K(j+1) fragments in gaps 7..22, V^T fragments 8..15 as their ring slots
-        fall free, LDS-DMA of K(j+2) in gaps 23..26 and of V(j+1) in 27..30 (gaps without LDS reads)"""
+        """B(j) dealt by issue slots: LDS-DMA of K(j+2) in gaps 0..3 and of V(j+1) in 4..7, the row maxima of the second key block
+        and the decision behind them, K(j+1) fragments in the sixteen gaps behind the decision, exponentials wherever a gap has
+        two slots left below `cap`, V^T fragments 8..15 as their ring slots fall free"""
         cfg = self.cfg
-        abl = cfg.abl if (mfma and softmax) else frozenset()
         if not mfma and softmax:
             self.emit("s_nop", None, [I(15)], note="S(0) is still leaving the matrix pipe")
-        if softmax and "ctl" not in abl and not self.fast:
+        if softmax and not self.fast:
             self.mask_section(par, after_mfma=mfma)
         fill = [[] for _ in range(32)]
         slots = [1] * 32
@@ -548,105 +493,62 @@ class Stream:
         if mfma:
             for f in range(8, 16):   # fragment f reuses the slot of f - 8, free once the two products of f - 8 (gaps 2 (f - 8), + 1) are issued
                 g0 = 2 * (f - 8) + 2
-                if "lds" in abl:
-                    vids[2 * f] = vids[2 * f + 1] = 0
-                    continue
                 at(g0, lambda f=f: vids.__setitem__(2 * f, self.v_read(2 * f)))
                 at(g0 + 1, lambda f=f: vids.__setitem__(2 * f + 1, self.v_read(2 * f + 1)))
-        if softmax and cfg.bal == 1:
-            for i in range(16, 32):
-                if "max" not in abl:
-                    at((i - 16) // 4, lambda i=i: self.max_op(par, i))
-            at(4, lambda: self.decide_1(), 4)
-            at(5, lambda: self.decide_2(), 5)
-            dec_lbl = self.newlabel("DEC")
-            first = not mfma
-            at(6, lambda: self.decide_4_fold(dec_lbl, first), 5)
-            for i in range(16):
-                if "lds" not in abl:
-                    at(7 + i, lambda i=i: self.k_read(par ^ 1, i))
-            at(18, lambda: self.vrd_advance(), 3)
-            if getattr(self, "persistent", False):
-                self.b_hook(lambda g, fn: at(g, fn, 2), par, mfma)
-            if "dma" not in abl:
-                at(22, lambda: self.vwr_update(), 3)
-                for i in range(4):
-                    at(23 + i, lambda i=i: self.dma_piece("k", par, i), 4)
-                    at(27 + i, lambda i=i: self.dma_piece("v", par, i), 4)
-                    at(27 + i, lambda i=i: self.emit("v_add_u32_e64", VN("koff%d" % i), [VN("koff%d" % i), SN("kinc")], clamp=1))
-                    at(31, lambda i=i: self.emit("v_add_u32_e64", VN("voff%d" % i), [VN("voff%d" % i), SN("vinc")], clamp=1))
-            exp_from = 7
-        elif softmax:
-            # bal = 2: the LDS-DMA pieces of K(j+2) and V(j+1) FIRST.  Their images fell free at the barrier in front of this phase
+        if softmax:
+            # the LDS-DMA pieces of K(j+2) and V(j+1) FIRST.  Their images fell free at the barrier in front of this phase
             # (K(j) and V(j-2) were last read in phase B(j-1)) and their deadline is the next barrier: issued here they have two
             # phases of flight instead of one and a quarter.  On all-zero operands (2.4 GHz) the stream without the pieces ran
             # 19 % faster and without the wait + barrier 25 % faster (profiles/r05_p4p_bal_ablations.txt): the wait for pieces
             # issued in the last gaps of this phase was what the loop spent a fifth of its time in
             ksw_g, vsw_g = 0, 4
-            if getattr(self, "persistent", False) and "ctl" not in abl and not self.fast:
+            if getattr(self, "persistent", False) and not self.fast:
                 self.b_hook(lambda g, fn: at(g, fn, 2), par, mfma, gaps=(ksw_g, vsw_g))
             elif self.fast:   # (the same slot accounting as the ordinary copy: the two copies must agree gap by gap, see slow_dec_back)
                 slots[ksw_g] += 2
                 slots[vsw_g] += 2
-            if "dma" not in abl:
-                for n in range(4):
-                    at(n, lambda n=n: self.dma_piece("k", par, n), 2)
-                at(3, lambda: self.vwr_update(), 3)
-                for n in range(4):
-                    at(4 + n, lambda n=n: self.dma_piece("v", par, n), 2)
-            # row-maximum steps this phase owes (the second key block's, or all four blocks'), greedily under the cap from gap 0
+            for n in range(4):
+                at(n, lambda n=n: self.dma_piece("k", par, n), 2)
+            at(3, lambda: self.vwr_update(), 3)
+            for n in range(4):
+                at(4 + n, lambda n=n: self.dma_piece("v", par, n), 2)
+            # row-maximum steps this phase owes (the second key block's), greedily under the cap from gap 0
             gm = 0
-            for i in range(16 if cfg.maxa else 0, 32):
+            for i in range(16, 32):
                 while slots[gm] + 1 > cfg.cap:
                     gm += 1
-                if "max" not in abl:
-                    at(gm, lambda i=i: self.max_op(par, i))
-                else:
-                    slots[gm] += 1
+                at(gm, lambda i=i: self.max_op(par, i))
             dec_lbl = self.newlabel("DEC")
             first = not mfma
-            if not cfg.fastdec:
+            if cfg.fastdec:
+                at(gm + 1, lambda: self.decide_fast(dec_lbl, first), 7)
+                exp_from = gm + 2
+            else:
                 at(gm + 1, lambda: self.decide_1(), 4)
                 at(gm + 2, lambda: self.decide_2(), 5)
-            if cfg.fastdec and cfg.fdpos == 2:
-                at(gm + 1, lambda: self.decide_fast(dec_lbl, first, part=1), 5)
-                at(gm + 2, lambda: self.decide_fast(dec_lbl, first, part=2), 2)
-                exp_from = gm + 3
-            elif cfg.fastdec:
-                gd = max(gm + 1, 8) if cfg.fdpos == 1 else gm + 1
-                at(gd, lambda: self.decide_fast(dec_lbl, first), 7)
-                exp_from = gd + 1
-            elif cfg.fold:
-                at(gm + 3, lambda: self.decide_4_fold(dec_lbl, first), 5)
-                exp_from = gm + 4
-            else:
-                at(gm + 3, lambda: self.decide_3(), 4)
-                at(gm + 4, lambda: self.decide_4(dec_lbl), 5)
-                exp_from = gm + 5
+                if cfg.fold:
+                    at(gm + 3, lambda: self.decide_4_fold(dec_lbl, first), 5)
+                    exp_from = gm + 4
+                else:
+                    at(gm + 3, lambda: self.decide_3(), 4)
+                    at(gm + 4, lambda: self.decide_4(dec_lbl), 5)
+                    exp_from = gm + 5
             assert exp_from + 16 <= 32
             for n in range(16):
-                if "lds" not in abl:
-                    at(exp_from + n, lambda n=n: self.k_read(par ^ 1, n))
+                at(exp_from + n, lambda n=n: self.k_read(par ^ 1, n))
             at(26, lambda: self.vrd_advance(), 3)
-            if "dma" not in abl and "offs" not in abl and getattr(cfg, "soff", 0):
-                # round 6: the tile advance is the SCALAR offset of the loads (part of the range check on gfx950 like the vector offset,
-                # tools/probe_soffset.hip): two scalar additions per tile instead of eight vector ones
-                at(28, lambda: self.emit("s_add_u32", SN("ksoff"), [SN("ksoff"), SN("kinc")]))
-                at(29, lambda: self.emit("s_add_u32", SN("vsoff"), [SN("vsoff"), SN("vinc")]))
-            elif "dma" not in abl and "offs" not in abl:
-                for n in range(4):
-                    at(28 + n, lambda n=n: self.emit("v_add_u32_e64", VN("koff%d" % n), [VN("koff%d" % n), SN("kinc")], clamp=1))
-                    at(28 + n, lambda n=n: self.emit("v_add_u32_e64", VN("voff%d" % n), [VN("voff%d" % n), SN("vinc")], clamp=1))
-        if softmax:
+            for n in range(4):
+                at(28 + n, lambda n=n: self.emit("v_add_u32_e64", VN("koff%d" % n), [VN("koff%d" % n), SN("kinc")], clamp=1))
+                at(28 + n, lambda n=n: self.emit("v_add_u32_e64", VN("voff%d" % n), [VN("voff%d" % n), SN("vinc")], clamp=1))
             # exponentials of the scores e < xb: behind the decision, two slots each, greedily under the cap (then cap + 1, ...)
             if cfg.fold:
-                todo = [] if "exp" in abl else [(2, lambda e=e: self.exp_in_b(par, e)) for e in range(cfg.nexpb)]
+                todo = [(2, lambda e=e: self.exp_in_b(par, e)) for e in range(cfg.nexpb)]
             else:   # exact-scale streams: s * scale2 - m of every score, the exponential of the first nexpb two scores behind it
                 todo = []
                 for e in range(64 + 2):
                     if e < 64:
                         todo.append((1, lambda e=e: self.fma_plain(par, e)))
-                    if 0 <= e - 2 < cfg.nexpb and "exp" not in abl:
+                    if 0 <= e - 2 < cfg.nexpb:
                         todo.append((2, lambda e=e: self.exp_in_b(par, e - 2)))
             # in order (an exponential follows its own multiply-subtract), each gap filled up to the cap; the smallest cap >= cfg.cap
             # under which the whole list fits in front of the phase's end
@@ -686,9 +588,8 @@ class Stream:
             self.outofline.append(("dec", dec_lbl, None, par, False))
         elif softmax:
             resc, back = self.newlabel("RESC"), self.newlabel("RESCBACK")
-            if "ctl" not in abl:
-                self.emit("s_cmp_eq_u32", None, [SN("pend"), I(0)])
-                self.emit("s_cbranch_scc0", None, [], target=resc)
+            self.emit("s_cmp_eq_u32", None, [SN("pend"), I(0)])
+            self.emit("s_cbranch_scc0", None, [], target=resc)
             self.label(back)
             self.outofline.append(("resc", resc, back, par, False))
             self.outofline.append(("dec", dec_lbl, dec_lbl + "_BACK", par, not mfma))
@@ -720,15 +621,12 @@ class Stream:
         for rb in range(2):
             self.emit("v_max_f32", V(T_MN + rb), [V(T_SW + rb), V(T_MN + rb)])
 
-    def decide_fast(self, lbl, first, part=0):
-        if part in (0, 1):
-            for rb in range(2):
-                self.emit("v_max_f32", V(T_MN + rb), [V(T_MX + 2 * rb), V(T_MX + 2 * rb + 1)])
-            self.emit("s_nop", None, [I(1)], note="VALU write -> permlane read")
-            self.emit("v_permlane32_swap_b32", V(T_MN), [V(T_MN + 1)], swap=1)
-            self.emit("v_max_f32", V(T_SW), [V(T_MN), V(T_MN + 1)])    # [row maxima of row block 0 | of row block 1]
-        if part == 1:
-            return
+    def decide_fast(self, lbl, first):
+        for rb in range(2):
+            self.emit("v_max_f32", V(T_MN + rb), [V(T_MX + 2 * rb), V(T_MX + 2 * rb + 1)])
+        self.emit("s_nop", None, [I(1)], note="VALU write -> permlane read")
+        self.emit("v_permlane32_swap_b32", V(T_MN), [V(T_MN + 1)], swap=1)
+        self.emit("v_max_f32", V(T_SW), [V(T_MN), V(T_MN + 1)])    # [row maxima of row block 0 | of row block 1]
         if first:
             self.emit("s_branch", None, [], target=lbl)
         else:
@@ -771,14 +669,7 @@ class Stream:
         x = s_elem(par, rb, kb, r)
         self.emit("v_fma_f32", x, [x, SN("scale2"), VN("m%d" % rb)], neg2=1)
 
-    def fma_only(self, par, e):
-        rb, kb, r = elem(e)
-        x = s_elem(par, rb, kb, r)
-        self.emit("v_fma_f32", x, [x, SN("scale2"), VN("m%d" % rb)], neg2=1)
-
     def fma_op(self, par, e):
-        if e >= self.cfg.xf:
-            return          # done in phase A of the next tile
         rb, kb, r = elem(e)
         x = s_elem(par, rb, kb, r)
         self.emit("v_fma_f32", x, [x, SN("scale2"), VN("m%d" % rb)], neg2=1)
@@ -808,13 +699,12 @@ class Stream:
         self.emit("s_cselect_b32", SN("vwr"), [SN("ldsv"), SN("vwr")])
 
     def dma_piece(self, which, par, i):
-        so = getattr(self.cfg, "soff", 0)
         if which == "k":   # K(j+2) -> K image j & 1
             self.emit("s_add_u32", M0, [SN("ldsk"), I(par * KSLOT + i * 1024)])
-            self.emit("buffer_load_dwordx4_lds", None, [VN("koff%d" % i), SN("kres", 4)] + ([SN("ksoff")] if so else []), pol=getattr(self.cfg, "dmapol", ""))
+            self.emit("buffer_load_dwordx4_lds", None, [VN("koff%d" % i), SN("kres", 4)])
         else:              # V(j+1) -> V image (j + 1) % 3
             self.emit("s_add_u32", M0, [SN("vwr"), I(i * 1024)])
-            self.emit("buffer_load_dwordx4_lds", None, [VN("voff%d" % i), SN("vres", 4)] + ([SN("vsoff")] if so else []), pol=getattr(self.cfg, "dmapol", ""))
+            self.emit("buffer_load_dwordx4_lds", None, [VN("voff%d" % i), SN("vres", 4)])
 
     def last_v_tile(self):
         """transposed streams, in front of the pieces of V(j+1): the tile advances ALONG the rows of V^T, so the end of the
@@ -834,45 +724,17 @@ class Stream:
         if after_mfma:
             self.emit("s_nop", None, [I(15)], note="S(j) is still leaving the matrix pipe")
         self.emit("s_lshl_b32", SN("t0"), [SN("j"), I(6)])
-        if getattr(self.cfg, "causal", 0) and getattr(self.cfg, "diagmask", 0):
-            # round 6, causal streams: the tile ON the wave's diagonal with everything aligned (first row of the wave + C - R = first key
-            # of the tile, the tile inside the sequence -- every self-attention launch with N % 64 == 0): which lanes lose which key is
-            # a compile-time pattern.  Row block = key block: register r masks rows q < (r & 3) + 8 (r >> 2) (+ 4 in the upper half-wave)
-            # -- two scalar moves into vcc and ONE v_cndmask instead of a compare + v_cndmask per score; keys 32..63 against rows 0..31:
-            # all masked (a move); keys 0..31 against rows 32..63: all visible (nothing).  48 vector instructions instead of 256, and
-            # only one score block's row maxima to take again
-            general = self.newlabel("MASKGENERAL")
-            self.emit("s_cmp_eq_u32", None, [SN("t0"), SN("wdiag")])
-            self.emit("s_cbranch_scc0", None, [], target=general)
-            self.emit("s_add_u32", SN("t1x"), [SN("t0"), I(63)])
-            self.emit("s_cmp_gt_u32", None, [SN("t1x"), SN("cm1")])
-            self.emit("s_cbranch_scc1", None, [], target=general)
-            self.emit("v_mov_b32", V(self.r_maskv), [F(-(0.875 / 1.44269504089) * 3.402823466e+38)])
-            for rb in range(2):
-                for r in range(16):
-                    c0 = (r & 3) + 8 * (r >> 2)
-                    x = s_elem(par, rb, rb, r)
-                    self.emit("s_mov_b32", VCC_LO, [I((1 << c0) - 1)])
-                    self.emit("s_mov_b32", VCC_HI, [I((1 << (c0 + 4)) - 1)])
-                    self.emit("v_cndmask_b32", x, [x, V(self.r_maskv), VCC])
-            for r in range(16):
-                self.emit("v_mov_b32", s_elem(par, 0, 1, r), [V(self.r_maskv)])
-            if self.cfg.bal and self.cfg.maxa:
-                for i in range(8):     # (rb 0, kb 0) is the one first-key-block score block the mask touched
-                    self.max_op(par, i)
-            self.emit("s_branch", None, [], target=skip)
-            self.label(general)
         for rb in range(2):
             self.emit("v_subrev_u32", V(T_TL + rb), [SN("t0"), VN("lim%d" % rb)])   # lim - 4 hi - 64 j
-        self.emit("v_mov_b32", V(self.r_maskv), [F(-(0.875 / 1.44269504089) * 3.402823466e+38)])   # +Softmax.swift:242-243
+        self.emit("v_mov_b32", V(T_MASKV), [F(-(0.875 / 1.44269504089) * 3.402823466e+38)])   # +Softmax.swift:242-243
         for rb in range(2):
             for kb in range(2):
                 for r in range(16):
                     c = kb * 32 + (r & 3) + 8 * (r >> 2)
                     x = s_elem(par, rb, kb, r)
                     self.emit("v_cmp_gt_i32", VCC, [I(c), V(T_TL + rb)])
-                    self.emit("v_cndmask_b32", x, [x, V(self.r_maskv), VCC])
-        if self.cfg.bal and self.cfg.maxa:   # the first key block's row maxima were taken in phase A, from the unmasked scores
+                    self.emit("v_cndmask_b32", x, [x, V(T_MASKV), VCC])
+        if self.cfg.bal:   # the first key block's row maxima were taken in phase A, from the unmasked scores
             for i in range(16):
                 self.max_op(par, i)
         self.label(skip)
@@ -924,34 +786,7 @@ class Stream:
             else:               # O, l *= corr once every matrix instruction that accumulates P(j-1) has been issued
                 self.emit("s_nop", None, [I(15)])
                 self.emit("s_nop", None, [I(7)])
-                if self.orow:
-                    # register r of a lane belongs to row 8 (r >> 2) + 4 hi + (r & 3): the row's factor comes from the lane that owns the
-                    # row (ds_bpermute_b32: lane select = (address + offset) / 4, no LDS memory), four registers of the four blocks at a time
-                    self.emit("v_mbcnt_lo_u32_b32", V(rs), [I(-1), I(0)])
-                    self.emit("v_mbcnt_hi_u32_b32", V(rs), [I(-1), V(rs)])
-                    self.emit("v_lshrrev_b32", V(rs), [I(5), V(rs)])
-                    self.emit("v_lshlrev_b32", V(rs), [I(4), V(rs)])          # 16 hi
-                    for rb in range(2):
-                        for g in range(4):
-                            for i in range(3):
-                                self.emit("ds_bpermute_b32", V(rs + 1 + i), [V(rs), V(T_CORR + rb)], offset=4 * (8 * g + i))
-                            self.emit("ds_bpermute_b32", V(rs + 7), [V(rs), V(T_CORR + rb)], offset=4 * (8 * g + 3))
-                            self.emit("s_waitcnt", None, [], lgkmcnt=0)
-                            fac = [rs + 1, rs + 2, rs + 3, rs + 7]
-                            for db in range(4):
-                                for i in range(3):
-                                    self.emit("v_accvgpr_read_b32", V(rs + 4 + i), [A(O_BASE + 64 * rb + 16 * db + 4 * g + i)])
-                                for i in range(3):
-                                    self.emit("v_mul_f32", V(rs + 4 + i), [V(fac[i]), V(rs + 4 + i)])
-                                for i in range(3):
-                                    self.emit("v_accvgpr_write_b32", A(O_BASE + 64 * rb + 16 * db + 4 * g + i), [V(rs + 4 + i)])
-                                # (eight temporaries: the fourth register of the group goes through the fourth factor's register pair)
-                                self.emit("v_accvgpr_read_b32", V(rs + 4), [A(O_BASE + 64 * rb + 16 * db + 4 * g + 3)])
-                                self.emit("v_mul_f32", V(rs + 4), [V(fac[3]), V(rs + 4)])
-                                self.emit("v_accvgpr_write_b32", A(O_BASE + 64 * rb + 16 * db + 4 * g + 3), [V(rs + 4)])
-                        self.emit("v_mul_f32", VN("l%d" % rb), [V(T_CORR + rb), VN("l%d" % rb)])
-                        self.emit("v_mul_f32", V(self.r_lb[rb]), [V(T_CORR + rb), V(self.r_lb[rb])])
-                for rb in range(0 if self.orow else 2):
+                for rb in range(2):
                     for i0 in range(0, 64, 8):
                         for t in range(8):
                             self.emit("v_accvgpr_read_b32", V(rs + t), [A(O_BASE + 64 * rb + i0 + t)])
@@ -960,7 +795,7 @@ class Stream:
                         for t in range(8):
                             self.emit("v_accvgpr_write_b32", A(O_BASE + 64 * rb + i0 + t), [V(rs + t)])
                     self.emit("v_mul_f32", VN("l%d" % rb), [V(T_CORR + rb), VN("l%d" % rb)])
-                    self.emit("v_mul_f32", V(self.r_lb[rb]), [V(T_CORR + rb), V(self.r_lb[rb])])
+                    self.emit("v_mul_f32", V(T_LB + rb), [V(T_CORR + rb), V(T_LB + rb)])
                 self.emit("s_mov_b32", SN("pend"), [I(0)])
                 self.emit("s_nop", None, [I(4)], note="accvgpr write -> MFMA SrcC")
                 self.emit("s_branch", None, [], target=back)
@@ -975,8 +810,6 @@ class Stream:
     def build(self):
         self.outofline = []
         self.xe_pending = []
-        if self.cfg.pad:
-            self.emit("s_nop", None, [I(0)], note="code placement pad")
         # ---- prologue: K(0), V(0) landed (K(1) may be in flight): 12 DMA pieces were issued by the caller
         self.emit("s_waitcnt", None, [], vmcnt=4)
         self.emit("s_barrier")
@@ -984,7 +817,7 @@ class Stream:
             if not self.cfg.kt:
                 self.emit("v_xor_b32", V(T_KADDR + ks), [I(ks << 5), VN("kbase")])
         for rb in range(2):
-            self.emit("v_mov_b32", V(self.r_lb[rb]), [I(0)])
+            self.emit("v_mov_b32", V(T_LB + rb), [I(0)])
             self.emit("v_mov_b32", V(T_CORR + rb), [F(1.0)])
         if self.cfg.fold:
             for r in range(32):
@@ -1042,23 +875,22 @@ class Stream:
             self.emit("s_cbranch_scc1", None, [], target=done)
             self.emit("s_waitcnt", None, [], vmcnt=0)
             self.emit("s_barrier")
-            if self.cfg.dma == "b":
-                self.vwr_update()
-                for i in range(4):
-                    self.dma_piece("k", par, i)
-                if self.cfg.vt:
-                    self.last_v_tile()
-                for i in range(4):
-                    self.dma_piece("v", par, i)
-                for i in range(4):
-                    self.emit("v_add_u32_e64", VN("koff%d" % i), [VN("koff%d" % i), SN("kinc")], clamp=1)
-                    self.emit("v_add_u32_e64", VN("voff%d" % i), [VN("voff%d" % i), SN("vinc")], clamp=1)
+            self.vwr_update()
+            for i in range(4):
+                self.dma_piece("k", par, i)
+            if self.cfg.vt:
+                self.last_v_tile()
+            for i in range(4):
+                self.dma_piece("v", par, i)
+            for i in range(4):
+                self.emit("v_add_u32_e64", VN("koff%d" % i), [VN("koff%d" % i), SN("kinc")], clamp=1)
+                self.emit("v_add_u32_e64", VN("voff%d" % i), [VN("voff%d" % i), SN("vinc")], clamp=1)
             self.emit("s_add_u32", SN("j"), [SN("j"), I(1)])
             if par == 0:
                 self.emit("s_branch", None, [], target=skip_odd)
         self.label(done)
         for rb in range(2):
-            self.emit("v_add_f32", VN("l%d" % rb), [V(self.r_lb[rb]), VN("l%d" % rb)])
+            self.emit("v_add_f32", VN("l%d" % rb), [V(T_LB + rb), VN("l%d" % rb)])
         self.emit("s_branch", None, [], target=fin)
         self.emit_outofline()
         self.label(fin)
@@ -1078,8 +910,6 @@ def fmt(o):
         return "s%d" % o[1] if o[2] == 1 else "s[%d:%d]" % (o[1], o[1] + o[2] - 1)
     if k == "vcc_lo":
         return "vcc_lo"
-    if k == "vcc_hi":
-        return "vcc_hi"
     if k == "i":
         return str(o[1]) if -16 <= o[1] <= 64 else hex(o[1] & 0xFFFFFFFF)
     if k == "f":
@@ -1112,7 +942,7 @@ def render_one(ins, suffix="%="):
     if op in ("s_cbranch_scc0", "s_cbranch_scc1", "s_cbranch_vccnz", "s_branch"):
         return "%s %s_%s" % (op, m["target"], suffix)
     if op == "buffer_load_dwordx4_lds":
-        return "buffer_load_dwordx4 %s, %s, %s offen%s lds" % (fmt(ins.s[0]), fmt(ins.s[1]), fmt(ins.s[2]) if len(ins.s) > 2 else "0", m.get("pol", ""))
+        return "buffer_load_dwordx4 %s, %s, 0 offen lds" % (fmt(ins.s[0]), fmt(ins.s[1]))
     if op in ("buffer_load_dword", "buffer_load_ushort"):
         return "%s %s, %s, %s, 0 offen" % (op, fmt(ins.d), fmt(ins.s[0]), fmt(ins.s[1]))
     if op == "buffer_store_dwordx4":     # s = (four data registers, per-lane byte offset, buffer resource)
@@ -1124,8 +954,6 @@ def render_one(ins, suffix="%="):
         return "ds_write_b128 %s, %s offset:%d" % (fmt(ins.s[0]), fmt(ins.s[1]), m["offset"])
     if op in ("ds_read_b128", "ds_read_b64", "ds_read_b64_tr_b16"):
         return "%s %s, %s offset:%d" % (op, fmt(ins.d), fmt(ins.s[0]), m["offset"])
-    if op == "ds_bpermute_b32":         # d[lane] = s1[((s0[lane] + offset) >> 2) & 63]
-        return "ds_bpermute_b32 %s, %s, %s offset:%d" % (fmt(ins.d), fmt(ins.s[0]), fmt(ins.s[1]), m["offset"])
     if op == "v_fma_f32":
         return "v_fma_f32 %s, %s, %s, -%s" % (fmt(ins.d), fmt(ins.s[0]), fmt(ins.s[1]), fmt(ins.s[2]))
     if op == "v_add_u32_e64":
@@ -1184,8 +1012,8 @@ def write_inc(path):
         ins = st.build()
         txt = render(ins)
         n_mfma = sum(1 for i in ins if i.op.startswith("v_mfma"))
-        lines.append("// %s: dtype=%s thr=%g xe=%d xf=%d order_a=%s pad=%d prof=%d fold=%d xb=%d dma=%s%s -- %d instructions, %d matrix instructions"
-                     % (name, cfg.dtype, cfg.thr, cfg.xe, cfg.xf, cfg.order_a, cfg.pad, cfg.prof, cfg.fold, cfg.xb, cfg.dma,
+        lines.append("// %s: dtype=%s thr=%g xe=%d prof=%d fold=%d xb=%d bal=%d%s -- %d instructions, %d matrix instructions"
+                     % (name, cfg.dtype, cfg.thr, cfg.xe, cfg.prof, cfg.fold, cfg.xb, cfg.bal,
                         " tr=%d" % cfg.tr if cfg.tr else "", len(txt), n_mfma))
         lines.append("#define MFA_P4_STREAM_%s \\" % name)
         for t in txt:
@@ -1199,17 +1027,13 @@ def write_inc(path):
 VARIANTS = {
     # product streams: the round-5 schedule (bal = 2: LDS-DMA first in phase B, fillers dealt by issue slots)
     "BF16_THR8": Cfg("bf16", 8, xe=32, bal=2, cap=8),
-    "BF16_THR0": Cfg("bf16", 0, xe=32, bal=2, cap=8),
+    "BF16_THR0": Cfg("bf16", 0, xe=32, bal=2, cap=8),      # (index 1: tests/test_attention_gpu.py selects it as p4:1)
     "F16_THR8": Cfg("f16", 8, xe=32, bal=2, cap=8),
     "R4_BF16_THR8": Cfg("bf16", 8, 0),                 # the round-4 schedules (developer library, A/B baselines)
     "R4_BF16_FOLD": Cfg("bf16", 8, fold=1, xb=40),
-    "BF16_THR8_XE16": Cfg("bf16", 8, 16),
-    "BF16_THR8_ROT": Cfg("bf16", 8, 0, order_a="rot4"),
-    "BF16_THR8_PAD": Cfg("bf16", 8, 0, pad=1),
-    "BF16_THR8_PROF": Cfg("bf16", 8, 0, prof=1),
+    "BF16_THR8_PROF": Cfg("bf16", 8, 0, prof=1),       # developer library: phase times by shader clock (tools/p4_prof.py)
     "BF16_FOLD": Cfg("bf16", 8, fold=1, xb=48, bal=2, fastdec=1),
     "F16_FOLD": Cfg("f16", 8, fold=1, xb=48, bal=2, fastdec=1),
-    "BF16_FOLD_XB24": Cfg("bf16", 8, fold=1, xb=24),
     "BF16_FOLD_PROF": Cfg("bf16", 8, fold=1, xb=40, prof=1),
     "BF16_THR8_TR": Cfg("bf16", 8, 0, tr=3),
     "F16_THR8_TR": Cfg("f16", 8, 0, tr=3),
@@ -1223,16 +1047,6 @@ VARIANTS = {
     "F16_THR8_TRV": Cfg("f16", 8, 0, tr=2),
     "BF16_FOLD_TRV": Cfg("bf16", 8, fold=1, xb=40, tr=2),
     "F16_FOLD_TRV": Cfg("f16", 8, fold=1, xb=40, tr=2),
-    "ABL_EXPA": Cfg("bf16", 8, fold=1, prof=1, abl=("expa",)),
-    "ABL_SUMPACK": Cfg("bf16", 8, fold=1, prof=1, abl=("sum", "pack")),
-    "ABL_VREADA": Cfg("bf16", 8, fold=1, prof=1, abl=("vreada",)),
-    "ABL_VREADB": Cfg("bf16", 8, fold=1, prof=1, abl=("vreadb",)),
-    "ABL_KREAD": Cfg("bf16", 8, fold=1, prof=1, abl=("kread",)),
-    "ABL_MAX": Cfg("bf16", 8, fold=1, prof=1, abl=("max",)),
-    "ABL_EXPB": Cfg("bf16", 8, fold=1, prof=1, abl=("expb",)),
-    "ABL_DMA": Cfg("bf16", 8, fold=1, prof=1, abl=("dma",)),
-    "ABL_ALLB": Cfg("bf16", 8, fold=1, prof=1, abl=("vreadb", "kread", "max", "expb", "dma")),
-    "ABL_ALLA": Cfg("bf16", 8, fold=1, prof=1, abl=("expa", "sum", "pack", "vreada")),
 }
 
 PRODUCT_STREAMS = ("BF16_THR8", "F16_THR8", "BF16_THR0", "BF16_FOLD", "F16_FOLD")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""developer A/B (libmfa_hip_dev.so): the persistent forward kernel's developer streams (tools/p4pgen.py: slot-balanced schedules,
-code-placement pads, timing-only ablations) against the product stream -- headline shape, mixed mode, interleaved rounds in ONE
+"""developer A/B (libmfa_hip_dev.so): the persistent forward kernel's developer streams (tools/p4pgen.py: the round-4 and round-5
+schedules, the stamped schedules) against the product stream -- headline shape, mixed mode, interleaved rounds in ONE
 process, on N(0,1) and on all-zero operands (full clock: cycle efficiency).
 
   python tools/p4p_streams_ab.py [--streams A,B,...] [--fills normal,zero]
@@ -19,7 +19,7 @@ def main():
     import p4pgen
     V = p4pgen.VARIANTS
     dev = [n for n in V if n not in p4pgen.PRODUCT_STREAMS and V[n].fold and V[n].l16 and not V[n].o16 and not V[n].causal
-           and V[n].dtype == "bf16" and not V[n].merge and not V[n].fuse]
+           and V[n].dtype == "bf16"]
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=4096)
     ap.add_argument("--heads", type=int, default=256)

@@ -90,15 +90,6 @@ class PWorkgroup(Workgroup):
         scalar_kinds = ("sr",)
         if op == "align":
             return None
-        if op == "s_mov_b32" and d[0] in ("vcc_lo", "vcc_hi"):   # a scalar constant into one half of the lane mask
-            val = int(self.sval(w, s[0])) & 0xFFFFFFFF
-            bits = np.array([(val >> i) & 1 for i in range(32)], bool)
-            w.vcc = w.vcc.copy()
-            if d[0] == "vcc_lo":
-                w.vcc[:32] = bits
-            else:
-                w.vcc[32:] = bits
-            return None
         if op in ("s_mov_b32", "s_add_u32", "s_sub_u32", "s_and_b32", "s_or_b32", "s_lshl_b32", "s_lshr_b32", "s_mul_i32", "s_min_u32", "s_max_u32", "s_max_i32", "s_min_i32"):
             vals = [self.sval(w, x) for x in s]
             if op == "s_mov_b32":
@@ -119,15 +110,11 @@ class PWorkgroup(Workgroup):
             else:
                 w.swr(d, r)
             return None
-        if op == "s_bitcmp1_b32":
-            w.scc = (int(self.sval(w, s[0])) >> (int(self.sval(w, s[1])) & 31)) & 1
-            return None
-        if op in ("s_cmp_lt_i32", "s_cmp_ge_i32", "s_cmp_ge_u32", "s_cmp_eq_u32", "s_cmp_lt_u32", "s_cmp_lg_u32", "s_cmp_gt_u32"):
+        if op in ("s_cmp_lt_i32", "s_cmp_ge_i32", "s_cmp_ge_u32", "s_cmp_eq_u32", "s_cmp_lg_u32"):
             a, b = int(self.sval(w, s[0])) & 0xFFFFFFFF, int(self.sval(w, s[1])) & 0xFFFFFFFF
             if op.endswith("i32"):
                 a, b = int(np.int32(np.uint32(a))), int(np.int32(np.uint32(b)))
-            w.scc = int({"s_cmp_lt_i32": a < b, "s_cmp_ge_i32": a >= b, "s_cmp_ge_u32": a >= b, "s_cmp_eq_u32": a == b,
-                         "s_cmp_lt_u32": a < b, "s_cmp_lg_u32": a != b, "s_cmp_gt_u32": a > b}[op])
+            w.scc = int({"s_cmp_lt_i32": a < b, "s_cmp_ge_i32": a >= b, "s_cmp_ge_u32": a >= b, "s_cmp_eq_u32": a == b, "s_cmp_lg_u32": a != b}[op])
             return None
         if op == "s_cselect_b32":
             self.sset(w, d, self.sval(w, s[0]) if w.scc else self.sval(w, s[1]))
@@ -158,10 +145,9 @@ class PWorkgroup(Workgroup):
         if op == "buffer_load_dwordx4_lds" and s[1][0] == "sr":
             off = w.rd(s[0]).astype(np.int64)
             arr, base, nrec = self.resource(w, s[1])
-            soff = (int(self.sval(w, s[2])) & 0xFFFFFFFF) if len(s) > 2 else 0   # scalar offset: part of the range check, no 32-bit wrap (tools/probe_soffset.hip)
             data = np.zeros((64, 16), np.uint8)
             for l in range(64):
-                o = int(off[l]) + soff
+                o = int(off[l])
                 if o + 16 <= nrec:
                     data[l] = arr[base + o:base + o + 16]
             addrs = (w.m0 + 16 * np.arange(64)).astype(np.int64)
@@ -179,8 +165,6 @@ class PWorkgroup(Workgroup):
                     raise Poison("store of a register whose load is in flight")
             words = np.stack([(w.v if kind == "v" else w.a)[idx] for kind, idx in regs], axis=1).astype(np.uint32)   # [64][n]
             off = (w.rd(s[1]).astype(np.int64) + int(m.get("offset", 0))) & 0xFFFFFFFF   # the address adder wraps at 32 bits
-            if len(s) > 3:      # scalar offset: part of the range check, no 32-bit wrap (as for the loads)
-                off = off + (int(self.sval(w, s[3])) & 0xFFFFFFFF)
             arr, base, nrec = self.resource(w, s[2])
             writes = []
             for l in range(64):
@@ -193,20 +177,6 @@ class PWorkgroup(Workgroup):
                 w.vm_q.append((None, None))
             else:
                 w.vm_q.append((("store", arr, writes), None))
-            return None
-        if op == "ds_bpermute_b32":     # d[lane] = s1[((s0[lane] + offset) >> 2) & 63]; returns through the LDS queue like a read
-            sel = ((w.rd(s[0]).astype(np.int64) + int(m.get("offset", 0))) >> 2) & 63
-            data = w.rd(s[1])[sel].astype(np.uint32)
-            dests = w.regs(d)
-            for t in dests:
-                w.poison.add(t)
-            w.lds_q.append((dests, data.reshape(1, 64).copy()))
-            return None
-        if op in ("v_mbcnt_lo_u32_b32", "v_mbcnt_hi_u32_b32"):      # (mask -1: the lane's index, low 32 lanes / the rest)
-            assert s[0] == ("i", -1)
-            lanes = np.arange(64)
-            cnt = np.minimum(lanes, 32) if op.startswith("v_mbcnt_lo") else np.maximum(lanes - 32, 0)
-            w.wr(d, (cnt + self.vsrc(w, s[1]).astype(np.int64)).astype(np.uint32))
             return None
         if op == "ds_write_b128":
             addr = w.rd(s[0]).astype(np.int64) + int(m.get("offset", 0))
@@ -341,9 +311,6 @@ def run_workgroup(q, k, v, blocks, cfg, D=128, dma_mode="late", stores="late", o
         for db in range(4):
             col = 32 * db + 4 * (lane & 7)
             w.vn["ov%d" % db] = np.where(col < D, (lane >> 3) * ldo * osz + col * osz, p4pgen.OOB).astype(np.uint32)
-            if getattr(cfg, "orow", 0):     # lane = column 32 db + n of rows 4 hi + ...: one fp32 element per lane and store
-                ocol = 32 * db + qq
-                w.vn["ov%d" % db] = np.where(ocol < D, 4 * ocol + hi * 4 * ldo * 4, p4pgen.OOB).astype(np.uint32)
         for i in range(4):
             w.vn["kv%d" % i], w.vn["qv%d" % i] = kv[i], qv[i]
         w.sn.update({"nt": nt, "maskfrom": Ck // 64, "scale2": scale2, "kinc": 64 * ldk2, "vinc": 64 * ldv2,

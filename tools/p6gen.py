@@ -61,6 +61,7 @@ STAGE = TABLE + TABLE_ENTRIES * 64   # 112 KiB: O staging, 4 KiB per wave
 LDS_BYTES = STAGE + 4 * 4096
 NST = 18                         # buffer stores per wave and block: 16 x O, 2 x L
 NG_A, NG_B = 16, 24
+VLAST = 7                        # last gap of phase A with a V^T read: the wait in front of the barrier must not expose their latency
 UNROLL = 4                       # tiles per loop body = ring size: a block walks a multiple of UNROLL tiles
 
 PSGPR = dict(kres=(40, 4), vres=(44, 4), tres=(48, 4), lres=(52, 4),
@@ -81,12 +82,12 @@ IN_S = ["nt", "maskfrom", "scale2", "kinc", "vinc", "ldsk", "ldsv", "ldsq", "qre
 
 
 class Cfg6(p4gen.Cfg):
-    def __init__(self, dtype="bf16", thr=8.0, xb=56, o16=0, l16=1, lsum=1, abl=(), pad=0, vlast=7, kearly=1, fold=1, causal=0, split=0):
+    def __init__(self, dtype="bf16", thr=8.0, xb=56, o16=0, l16=1, lsum=1, fold=1, causal=0, split=0):
         """fold = 0: EXACT-SCALE streams (descriptors that keep the attention matrix in FP32 registers): Q stays as stored, the scale
         is applied in fp32 per score (s * scale2 - m, 64 more vector instructions per tile), the row sums are fp32 additions of
         the unrounded P (no `lsum`), L is stored in FP32.  xb = scores per tile whose exponential phase B takes (both kinds)"""
-        p4gen.Cfg.__init__(self, dtype=dtype, thr=thr, fold=fold, xb=xb, xe=0 if fold else xb, abl=abl, pad=pad, bal=2, maxa=1)
-        # (bal / maxa: p4gen's mask section then re-takes the first key block's row maxima, which phase A took from the unmasked scores)
+        p4gen.Cfg.__init__(self, dtype=dtype, thr=thr, fold=fold, xb=xb, xe=0 if fold else xb, bal=2)
+        # (bal: p4gen's mask section then re-takes the first key block's row maxima, which phase A took from the unmasked scores)
         self.xb = xb
         if not fold:
             lsum, l16 = 0, 0
@@ -104,10 +105,6 @@ class Cfg6(p4gen.Cfg):
         if split:
             self.o16, self.l16 = 0, 0
         assert not (split and causal)
-        # vlast: last gap of phase A with a V^T read; kearly: the K(j+1) fragment reads right behind the LDS-DMA pieces of phase B
-        # (else spread between its exponentials, the last one near the phase's end -- the first GPU runs lost ~250 clocks per tile
-        # to the two `lgkmcnt(0)` in front of the phase seams, profiles/r05_p6_ablations_first.txt)
-        self.vlast, self.kearly = vlast, kearly
 
 
 def s(name, cnt=None, off=0):
@@ -333,7 +330,6 @@ class Stream6(Stream):
         """A(j): S[par] = K(j) Q'^T - m  |  exponentials phase B left, packs (and row sums without `lsum`) of tile j - 1, all 16
         V^T(j-1) fragment reads, the row maxima of the first key block of tile j (complete behind matrix instruction 7); t = j mod 4"""
         cfg = self.cfg
-        abl = cfg.abl if (mfma and softmax) else frozenset()
         prev = par ^ 1
         fill = [[] for _ in range(NG_A + 1)]
         vids = {}
@@ -341,18 +337,15 @@ class Stream6(Stream):
             ea = list(range(cfg.xb, 64))
             exp_gap = {e: (t * NG_A) // len(ea) for t, e in enumerate(ea)} if ea else {}
             for e in ea:
-                if "exp" not in abl:
-                    fill[exp_gap[e]].append(lambda e=e: self.exp_op(prev, e))
+                fill[exp_gap[e]].append(lambda e=e: self.exp_op(prev, e))
             g_prev = 0
             for p in range(32):
                 ready = max(exp_gap.get(2 * p, -1), exp_gap.get(2 * p + 1, -1))
                 g_prev = min(NG_A, max(g_prev, p // 2, ready + 1))
-                if "pack" not in abl:
-                    fill[g_prev].append(lambda p=p: self.sum_pack6(prev, 2 * p))
-            for i in range(16):    # done by gap cfg.vlast: the wait in front of the barrier must not expose their latency
-                if "lds" not in abl:
-                    fill[(i * (cfg.vlast + 1)) // 16].append(lambda i=i: vids.__setitem__(i, self.v_read(i, (t + 3) % 4)))
-        if mfma and "max" not in abl:
+                fill[g_prev].append(lambda p=p: self.sum_pack6(prev, 2 * p))
+            for i in range(16):
+                fill[(i * (VLAST + 1)) // 16].append(lambda i=i: vids.__setitem__(i, self.v_read(i, (t + 3) % 4)))
+        if mfma:
             for k in range(16):    # (rb0, kb0) is complete behind matrix instruction 6, (rb1, kb0) behind 7: first steps from gap 9 / 12
                 fill[9 + (k * 7) // 16].append(lambda k=k: self.max_op(par, k))
         mlist = self.qk_list(par)
@@ -429,7 +422,6 @@ class Stream6(Stream):
         decision, the first xb exponentials, K(j+1) fragments; t = j mod 4: K(j+3) -> image t + 3, V(j+2) -> image t + 2, K(j+1) in
         image t + 1 (mod 4).  The next block's K switch (tile nt - 3) can only fall on t = 1, its V / Q switch (nt - 2) on t = 2"""
         cfg = self.cfg
-        abl = cfg.abl if (mfma and softmax) else frozenset()
         if not mfma and softmax:
             self.emit("s_nop", None, [I(15)], note="S(0) is still leaving the matrix pipe")
         if softmax:
@@ -447,19 +439,15 @@ class Stream6(Stream):
             first = not mfma
             if t == 1:
                 items.append((2, lambda: self.check("ntm3", ksw), None))
-            if "dma" not in abl:
-                items.append((4, lambda: self.dma_pieces("k", (t + 3) % 4), None))
+            items.append((4, lambda: self.dma_pieces("k", (t + 3) % 4), None))
             if t == 2:
                 items.append((2, lambda: self.check("ntm2", vsw), None))
-            if "dma" not in abl:
-                items.append((4, lambda: self.dma_pieces("v", (t + 2) % 4), None))
-            if cfg.kearly:
-                for i in range(8):
-                    if "lds" not in abl:
-                        items.append((1, lambda i=i: self.k_read(i, (t + 1) % 4), None))
+            items.append((4, lambda: self.dma_pieces("v", (t + 2) % 4), None))
+            for i in range(8):     # the K(j+1) fragment reads right behind the LDS-DMA pieces: spread between the exponentials (the last one near
+                # the phase's end) they cost ~250 clocks per tile at the `lgkmcnt(0)` in front of the seam (profiles/r05_p6_ablations_first.txt)
+                items.append((1, lambda i=i: self.k_read(i, (t + 1) % 4), None))
             for i in range(16, 32):
-                if "max" not in abl:
-                    items.append((1, lambda i=i: self.max_op(par, i), None))
+                items.append((1, lambda i=i: self.max_op(par, i), None))
             if cfg.fold:
                 items.append((7, lambda: self.decide_fast(dec_lbl, first), None))
             else:
@@ -467,25 +455,17 @@ class Stream6(Stream):
                 items.append((5, lambda: self.decide_2(), None))
                 items.append((4, lambda: self.decide_3(), None))
                 items.append((5, lambda: self.decide_4(dec_lbl), None))
-            nexp, nk = cfg.xb, 0
+            nexp = cfg.xb
             for e in range(64 if not cfg.fold else nexp):
                 if not cfg.fold:      # s * scale2 - m of every score; the exponential of the first xb two scores behind its own
                     items.append((1, lambda e=e: self.fma_plain(par, e), None))
                     e -= 2
                     if e < 0 or e >= nexp:
                         continue
-                if "exp" not in abl:
-                    items.append((2, lambda e=e: self.exp_in_b(par, e), None))
-                if not cfg.kearly and (e + 1) * 8 // nexp > nk:
-                    if "lds" not in abl:
-                        items.append((1, lambda i=nk: self.k_read(i, (t + 1) % 4), None))
-                    nk += 1
-            for i in range(nk, 8):
-                if not cfg.kearly and "lds" not in abl:
-                    items.append((1, lambda i=i: self.k_read(i, (t + 1) % 4), None))
+                items.append((2, lambda e=e: self.exp_in_b(par, e), None))
             if not cfg.fold:
                 for e in range(62, 64):
-                    if e < nexp and "exp" not in abl:
+                    if e < nexp:
                         items.append((2, lambda e=e: self.exp_in_b(par, e), None))
             for i in range(2):
                 items.append((1, lambda i=i: self.emit("v_add_u32_e64", VN("koff%d" % i), [VN("koff%d" % i), SN("kinc")], clamp=1), None))
@@ -753,8 +733,6 @@ class Stream6(Stream):
         self.outofline = []
         blk_lbl, loop, end_lbl, fin, nonext = (self.newlabel(x) for x in ("BLOCK", "LOOP", "END", "FIN", "NONEXT"))
         # ---- once per workgroup
-        if cfg.pad:
-            self.emit("s_nop", None, [I(0)], note="code placement pad")
         for ks in range(4):
             self.emit("v_xor_b32", V(T_KC + ks), [I(ks << 5), VN("kbase")])
         one = 0x3F803F80 if cfg.dtype == "bf16" else 0x3C003C00
@@ -810,10 +788,9 @@ class Stream6(Stream):
                 self.emit("s_cbranch_scc1", None, [], target=end_lbl)
             self.phase_a(par, mfma=True, softmax=True, zero_o=False, t=t)
             self.lds_flush()
-            if "bar" not in cfg.abl:
-                # K(j+1), V(j) were requested in phase B(j-2); only the four pieces of B(j-1) (K(j+2), V(j+1)) may still fly
-                self.emit("s_waitcnt", None, [], vmcnt=4)
-                self.emit("s_barrier")
+            # K(j+1), V(j) were requested in phase B(j-2); only the four pieces of B(j-1) (K(j+2), V(j+1)) may still fly
+            self.emit("s_waitcnt", None, [], vmcnt=4)
+            self.emit("s_barrier")
             self.phase_b(par, mfma=True, softmax=True, t=t)
             self.emit("s_add_u32", SN("j"), [SN("j"), I(1)])
         self.emit("s_branch", None, [], target=loop)
@@ -863,27 +840,12 @@ VARIANTS = {
     "BF16_EXACT_O16": Cfg6("bf16", 8, fold=0, xb=8, o16=1),
     "F16_EXACT": Cfg6("f16", 8, fold=0, xb=8),
     "F16_EXACT_O16": Cfg6("f16", 8, fold=0, xb=8, o16=1),
-    # developer streams (libmfa_hip_dev.so, tools/p6_ab.py): placements, and timing-only ablations (ABL_*, NOBAR: WRONG RESULTS)
-    "BF16_EXACT_XB24": Cfg6("bf16", 8, fold=0, xb=24),
-    "BF16_EXACT_XB40": Cfg6("bf16", 8, fold=0, xb=40),
+    # developer stream (libmfa_hip_dev.so, tools/p6_ab.py)
     "BF16_FOLD_L16_VSUM": Cfg6("bf16", 8, l16=1, lsum=0),        # row sums as 64 VALU additions per tile (A/B of `lsum`)
-    "BF16_FOLD_L16_XB32": Cfg6("bf16", 8, xb=32, l16=1),
-    "BF16_FOLD_L16_XB44": Cfg6("bf16", 8, xb=44, l16=1),
-    "BF16_FOLD_L16_XB60": Cfg6("bf16", 8, xb=60, l16=1),
-    "BF16_FOLD_L16_V5": Cfg6("bf16", 8, l16=1, vlast=5),
-    "BF16_FOLD_L16_V10": Cfg6("bf16", 8, l16=1, vlast=10),
-    "BF16_FOLD_L16_R5": Cfg6("bf16", 8, xb=44, l16=1, vlast=15, kearly=0),   # the first GPU version's read placement
-    "BF16_FOLD_L16_NOBAR": Cfg6("bf16", 8, l16=1, abl=("bar",)),
-    "ABL_DMA": Cfg6("bf16", 8, l16=1, abl=("dma",)),
-    "ABL_EXP": Cfg6("bf16", 8, l16=1, abl=("exp",)),
-    "ABL_MAX": Cfg6("bf16", 8, l16=1, abl=("max",)),
-    "ABL_PACK": Cfg6("bf16", 8, l16=1, abl=("pack",)),
-    "ABL_LDS": Cfg6("bf16", 8, l16=1, abl=("lds",)),
-    "ABL_ALL": Cfg6("bf16", 8, l16=1, abl=("dma", "exp", "max", "pack", "lds")),
-    "ABL_ALL_NOBAR": Cfg6("bf16", 8, l16=1, abl=("dma", "exp", "max", "pack", "lds", "bar")),
 }
-PRODUCT_STREAMS = tuple(n for n in VARIANTS if n.split("_")[0] in ("BF16", "F16") and n.split("_")[1] in ("FOLD", "EXACT") and
-                        all(t in ("BF16", "F16", "FOLD", "EXACT", "O16", "L16", "CAUSAL", "SPLIT") for t in n.split("_")))
+DEV_STREAMS = ("BF16_FOLD_L16_VSUM",)
+PRODUCT_STREAMS = tuple(n for n in VARIANTS if n not in DEV_STREAMS)
+assert len(PRODUCT_STREAMS) == 20
 
 
 def write_inc(path):
