@@ -28,8 +28,9 @@
  *
  * What the kernels need (anything else is MFA_ERR_INVALID_ARGUMENT naming the requirement; there is no slow fallback):
  *   Q, K, V 16-byte aligned with strides that are multiples of 8 elements; O 16-byte aligned with strides that are multiples
- *   of 4 elements; the workspace 16-byte aligned.  16-bit inputs only (FP32 caches: MFA_ERR_UNSUPPORTED); head dimensions 64
- *   and 128; packed rows M = G x R <= 32 (a longer block of rows is a prefill: mfa_attention_kernel_launch).
+ *   of 4 elements; the workspace 16-byte aligned.  16-bit inputs only (FP32 caches: MFA_ERR_UNSUPPORTED); head dimensions 64,
+ *   128 and 256 (anything else: MFA_ERR_UNSUPPORTED); packed rows M = G x R <= 32 (a longer block of rows is a prefill:
+ *   mfa_attention_kernel_launch).
  *
  * How a launch runs: one workgroup packs the G query heads x R rows of one K / V head as the rows of one matrix tile, so K and
  * V are read once per launch, not G times.  With a workspace the keys are cut into `pieces` (chosen on the host from

@@ -20,7 +20,7 @@
  * not written; no other byte of the cache is touched.  Cache layouts are decode's: contiguous with strides, or paged (pageSize a
  * power of two 16 .. 1024, K and V share the table).  The cache is the rows' 16-bit type (bits are copied) or E4M3.
  *   All four buffers 16-byte aligned; strides of the sources and of a 16-bit cache multiples of 8 elements, strides of an E4M3
- *   cache multiples of 16 elements; head dimensions 64 and 128.
+ *   cache multiples of 16 elements; head dimensions 64, 128 and 256.
  *
  * Decode over an E4M3 cache.  mfa_decode_params unchanged (precision = the 16-bit type of Q; K / V strides in elements = bytes,
  * multiples of 16) plus mfa_kv_quant.  Q, O, L, the mask, length, poison and piece rules, the piece plan and the workspace formula

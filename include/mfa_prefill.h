@@ -28,7 +28,7 @@
  * mfa_kvcache.h: MFA_KV_E4M3 only (MFA_KV_E5M2 is MFA_ERR_UNSUPPORTED), per-K/V-head FP32 scales on the device, NULL = 1.0, the key
  * scale folded into the softmax scale and the value scale into the final normalisation.  Scales with a 16-bit cache are refused.
  *
- * What the kernels need: 16-bit Q (FP32: MFA_ERR_UNSUPPORTED); head dimensions 64 and 128; Q, K, V, O 16-byte aligned; Q strides
+ * What the kernels need: 16-bit Q (FP32: MFA_ERR_UNSUPPORTED); head dimensions 64, 128 and 256; Q, K, V, O 16-byte aligned; Q strides
  * multiples of 8 elements, O strides of 4; K / V strides multiples of 8 elements for a 16-bit cache and of 16 elements (= bytes) for
  * an e4m3 cache; heads a multiple of headsPerKeyValue G, G <= 32.  No upper limit on rows (G x rows <= 32 included: the same math
  * as decode).  The launch takes no workspace: it is not cut along the keys.

@@ -17,6 +17,9 @@
 //     m = -FLT_MAX, l = 0.
 //   * SPLIT: piece p of sequence b takes decode_piece_range(len_b, pieces, p) -- the same function the host exports -- and publishes
 //     un-normalised O, m, l in FP32 (wsO [pieces][B Hq R][D], wsML [pieces][B Hq R][2]); attn_decode16_combine merges them.
+//   * D = 256: one workgroup per compute unit.  Over a 16-bit cache O^T, a step's K and V and the Q fragments do not
+//     fit the registers together: the Q fragments are parked once in LDS behind the four V images and re-read at their matrix
+//     instruction (QLDS below).  The e4m3 kernels, whose K and V take half the registers, keep them in registers as at every width.
 //
 // FP8: the same body over an FP8 (OCP e4m3) KV cache (include/mfa_kvcache.h), K and V read as bytes.  Everything above
 // holds, and so do decode_piece_range, the workspace slabs and the combine kernel.  What the parameter switches:
@@ -140,6 +143,11 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
   constexpr int NCH = DEC_STEP / RPI;          // V chunks per lane per step
   constexpr int IMAGE = DEC_STEP * D * 2;      // bytes of a wave's V image (16-bit values)
   static_assert(16 % RPI == 0, "a lane's V rows of one instruction stay inside a 16-key group");
+  // D = 256 over a 16-bit cache: K, V and O alone fill the registers, so the Q fragments are parked in LDS behind the four V images
+  // and re-read at their matrix instruction.  Everything else holds them in registers.
+  constexpr bool QLDS = D == 256 && !FP8;
+  constexpr int QPARK = DEC_WAVES * IMAGE;     // QLDS: fragment s of lane i at QPARK + (s 64 + i) 16, the same for every wave
+  static_assert(!QLDS || QPARK + NKS * 64 * 16 <= decode16_lds_bytes<D>(), "the parked Q fragments fit the workgroup's LDS");
 
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -172,13 +180,20 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
   // (FP8: its fragments in the permuted contraction order of the K bytes)
   const uint32_t pc = min((uint32_t)q, M - 1);
   const uint32_t qhead = kvh * a.G + pc / R, qrow = pc % R;
-  v8 qf[NKS];
+  v8 qf[QLDS ? 1 : NKS];
+  const char *qpark = smem + QPARK + lane * 16;
   {
     const char *qp = a.q + ((int64_t)batch * a.bsq + (int64_t)qhead * a.hsq + (int64_t)qrow * a.ldq) * 2;
+    if constexpr (QLDS) {   // wave w parks the fragments w, w + 4, ...: a lane's fragments do not depend on its wave
+      for (int s = wave; s < NKS; s += DEC_WAVES)
+        *reinterpret_cast<u32x4 *>(smem + QPARK + (s * 64 + lane) * 16) = *reinterpret_cast<const u32x4 *>(qp + (16 * s + 8 * hi) * 2);
+      __syncthreads();
+    } else {
 #pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-      const int d0 = FP8 ? 32 * (s >> 1) + 16 * hi + 8 * (s & 1) : 16 * s + 8 * hi;
-      qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + d0 * 2));
+      for (int s = 0; s < NKS; ++s) {
+        const int d0 = FP8 ? 32 * (s >> 1) + 16 * hi + 8 * (s & 1) : 16 * s + 8 * hi;
+        qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + d0 * 2));
+      }
     }
   }
   // keys this row sees (causal: c <= row + max(len - R, 0); always c < len, and inside this piece c < end)
@@ -256,6 +271,8 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
         const u32x4 kb = kreg[t >> 1];
         const u32x4 kf = (t & 1) ? cvt8_e4m3<T>(kb[2], kb[3]) : cvt8_e4m3<T>(kb[0], kb[1]);
         s = F::mfma(__builtin_bit_cast(v8, kf), qf[t], s);
+      } else if constexpr (QLDS) {
+        s = F::mfma(__builtin_bit_cast(v8, kreg[t]), __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qpark + t * 64 * 16)), s);
       } else {
         s = F::mfma(__builtin_bit_cast(v8, kreg[t]), qf[t], s);
       }
@@ -399,3 +416,19 @@ __device__ __forceinline__ void decode16_combine_body(const DecodeArgs &a) {
 }
 
 } // namespace mfa
+
+// One list of the kernel families, (infix, WINDOW, SINK): the kernels, the table that selects them (attn_decode16.hip) and the names
+// are generated from it.  MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, ...) is a set's code objects, in the translation unit that holds
+// them; (MFA_DECODE_DECLARE, ...) names the kernels of another unit for the table.  D = 256 runs one workgroup per compute unit.
+#define MFA_DECODE_FAMILIES(X, K, TN, T, D) X(K, , false, false, TN, T, D) X(K, w, true, false, TN, T, D) X(K, s, true, true, TN, T, D)
+#define MFA_DECODE_DEFINE(NAME, BOUNDS, BODY, ...)                                                                                    \
+  extern "C" __global__ BOUNDS void NAME(const mfa::DecodeArgs a) { mfa::BODY<__VA_ARGS__>(a); }
+#define MFA_DECODE_DECLARE(NAME, BOUNDS, BODY, ...) extern "C" __global__ void NAME(const mfa::DecodeArgs a);
+#define MFA_DECODE_FAMILY(K, I, WINDOW, SINK, TN, T, D)                                                                               \
+  K(attn_decode16##I##_d##D##_##TN##_single, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, false, false, WINDOW, SINK) \
+  K(attn_decode16##I##_d##D##_##TN##_pieces, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, true, false, WINDOW, SINK)  \
+  K(attn_decode8##I##_d##D##_##TN##_single, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, false, true, WINDOW, SINK)   \
+  K(attn_decode8##I##_d##D##_##TN##_pieces, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, true, true, WINDOW, SINK)
+#define MFA_DECODE_KERNELS(K, TN, T, D)                                                                                               \
+  MFA_DECODE_FAMILIES(MFA_DECODE_FAMILY, K, TN, T, D)                                                                                 \
+  K(attn_decode16_d##D##_##TN##_combine, __launch_bounds__(256), decode16_combine_body, T, D)

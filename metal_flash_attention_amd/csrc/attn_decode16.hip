@@ -28,24 +28,13 @@ using namespace mfa;
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_decode16_d<D>_<type>_{single,pieces,combine} and, over
 // an e4m3 cache, attn_decode8_d<D>_<type of Q>_{single,pieces}, whose pieces attn_decode16_d<D>_<type>_combine merges; under a
 // sliding window attn_decode16w_* / attn_decode8w_*, with attention sinks attn_decode16s_* / attn_decode8s_*, merged by the same combine kernel
-// One list of the kernel families, (infix, WINDOW, SINK): the kernels, the table that selects them and the names are generated from it
-#define MFA_DECODE_FAMILIES(X, TN, T, D) X(, false, false, TN, T, D) X(w, true, false, TN, T, D) X(s, true, true, TN, T, D)
-#define MFA_DECODE_KERNEL(NAME, ...)                                                                                                  \
-  extern "C" __global__ __launch_bounds__(256, 2) void NAME(const DecodeArgs a) { decode_body<__VA_ARGS__>(a); }
-#define MFA_DECODE_FAMILY(I, WINDOW, SINK, TN, T, D)                                                                                  \
-  MFA_DECODE_KERNEL(attn_decode16##I##_d##D##_##TN##_single, T, D, false, false, WINDOW, SINK)                                        \
-  MFA_DECODE_KERNEL(attn_decode16##I##_d##D##_##TN##_pieces, T, D, true, false, WINDOW, SINK)                                         \
-  MFA_DECODE_KERNEL(attn_decode8##I##_d##D##_##TN##_single, T, D, false, true, WINDOW, SINK)                                          \
-  MFA_DECODE_KERNEL(attn_decode8##I##_d##D##_##TN##_pieces, T, D, true, true, WINDOW, SINK)
-#define MFA_DECODE_KERNELS(TN, T, D)                                                                                                  \
-  MFA_DECODE_FAMILIES(MFA_DECODE_FAMILY, TN, T, D)                                                                                    \
-  extern "C" __global__ __launch_bounds__(256) void attn_decode16_d##D##_##TN##_combine(const DecodeArgs a) {                         \
-    decode16_combine_body<T, D>(a);                                                                                                   \
-  }
-MFA_DECODE_KERNELS(bf16, __bf16, 64)
-MFA_DECODE_KERNELS(bf16, __bf16, 128)
-MFA_DECODE_KERNELS(f16, _Float16, 64)
-MFA_DECODE_KERNELS(f16, _Float16, 128)
+// (the macros that generate them from one list of families: attn_decode16.h).  D = 256 lives in attn_decode16_d256.hip.
+MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, bf16, __bf16, 64)
+MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, bf16, __bf16, 128)
+MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, f16, _Float16, 64)
+MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, f16, _Float16, 128)
+MFA_DECODE_KERNELS(MFA_DECODE_DECLARE, bf16, __bf16, 256)
+MFA_DECODE_KERNELS(MFA_DECODE_DECLARE, f16, _Float16, 256)
 
 namespace {
 
@@ -61,14 +50,14 @@ struct DecodeSet {
   DecodeKernel combine;
 };
 #define MFA_DECODE_ENTRY(NAME) {NAME, #NAME}
-#define MFA_DECODE_SET_FAMILY(I, WINDOW, SINK, TN, T, D)                                                                              \
+#define MFA_DECODE_SET_FAMILY(K, I, WINDOW, SINK, TN, T, D)                                                                           \
   {{MFA_DECODE_ENTRY(attn_decode16##I##_d##D##_##TN##_single), MFA_DECODE_ENTRY(attn_decode16##I##_d##D##_##TN##_pieces)},            \
    {MFA_DECODE_ENTRY(attn_decode8##I##_d##D##_##TN##_single), MFA_DECODE_ENTRY(attn_decode8##I##_d##D##_##TN##_pieces)}},
 #define MFA_DECODE_SET(TN, PREC, D)                                                                                                   \
-  {D, PREC, (uint32_t)decode16_lds_bytes<D>(), {MFA_DECODE_FAMILIES(MFA_DECODE_SET_FAMILY, TN, , D)},                                 \
+  {D, PREC, (uint32_t)decode16_lds_bytes<D>(), {MFA_DECODE_FAMILIES(MFA_DECODE_SET_FAMILY, , TN, , D)},                               \
    MFA_DECODE_ENTRY(attn_decode16_d##D##_##TN##_combine)}
-const DecodeSet kSets[] = {MFA_DECODE_SET(bf16, MFA_BF16, 64), MFA_DECODE_SET(bf16, MFA_BF16, 128), MFA_DECODE_SET(f16, MFA_FP16, 64),
-                           MFA_DECODE_SET(f16, MFA_FP16, 128)};
+const DecodeSet kSets[] = {MFA_DECODE_SET(bf16, MFA_BF16, 64), MFA_DECODE_SET(bf16, MFA_BF16, 128), MFA_DECODE_SET(bf16, MFA_BF16, 256),
+                           MFA_DECODE_SET(f16, MFA_FP16, 64),  MFA_DECODE_SET(f16, MFA_FP16, 128),  MFA_DECODE_SET(f16, MFA_FP16, 256)};
 
 // Pieces of the keys: chosen from the workgroups the launch has without a split (batches x K/V heads) and `column` only -- the lengths
 // live on the device.  Aims at MFA_DECODE_WORKGROUP_TARGET workgroups (two per compute unit of a 256-CU chip, what choose_splits of
@@ -140,7 +129,7 @@ mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32
   for (const DecodeSet &s : kSets)
     if (s.D == p->headDimension && s.precision == p->precision) set = &s;
   if (!set)
-    return fail(MFA_ERR_UNSUPPORTED, "decode attention is compiled for head dimensions 64 and 128, not " + std::to_string(p->headDimension));
+    return fail(MFA_ERR_UNSUPPORTED, "decode attention is compiled for head dimensions 256, 64 and 128, not " + std::to_string(p->headDimension));
   if (p->rows == 0 || p->column == 0 || p->heads == 0 || p->batches == 0)
     return fail(MFA_ERR_INVALID_ARGUMENT, "rows, column, heads and batches must be non-zero");
   const uint32_t G = p->headsPerKeyValue > 1 ? p->headsPerKeyValue : 1;

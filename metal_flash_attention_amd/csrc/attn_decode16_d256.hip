@@ -1,0 +1,9 @@
+// attn_decode16_d256.hip -- the decode kernels of head dimension 256 (attn_decode16.h): a translation unit of their
+// own, so that the two units compile side by side; attn_decode16.hip's table selects them like the others.
+// (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
+#include <hip/hip_runtime.h>
+
+#include "attn_decode16.h"
+
+MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, bf16, __bf16, 256)
+MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, f16, _Float16, 256)

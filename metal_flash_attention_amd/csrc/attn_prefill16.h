@@ -23,6 +23,8 @@
 //     first_masked) run without the per-element mask, [first_masked, end) with it, tiles at or past end are never loaded.
 //   * what may hold poison is never loaded: key rows at or past n come in as zeros (K and V), a masked score is REPLACED (p = 0 exactly),
 //     and the running maximum only ever sees visible keys -- a row without a visible key keeps m = -FLT_MAX, l = 0.
+//   * D = 256: the same body at one workgroup per compute unit (128 KiB of LDS); over a 16-bit cache an instruction of
+//     the workgroup covers eight rows, half a 16-key group, and the staging addresses follow (RPI below).
 //
 // WINDOW, SINK: the rule of which keys a row sees, and the sink logit, are attn_cache_step.h's.  What is prefill's own:
 //   * WINDOW: prefill_window_tile_range gives the block four tile indices: [begin, unmaskedBegin) runs with the per-element mask (a
@@ -303,12 +305,16 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   };
 
   // ---- staging: instruction i of the workgroup covers rows i RPI .. + RPI - 1 of the tile whole; thread = (row lrow0, chunk lc).
-  // The rows of one wave-instruction lie inside one 16-key group (64 / CPR <= 16 consecutive rows, aligned), so its group is
-  // wave-uniform; a thread's row inside the group and its chunk do not depend on i.
-  static_assert(RPI % 16 == 0 && 64 / CPR <= 16, "the rows of a wave-instruction stay inside a 16-key group");
+  // The rows of one wave-instruction lie inside one 16-key group (64 / CPR consecutive rows, aligned, and 64 / CPR divides 16), so its
+  // group is wave-uniform.  A thread's chunk does not depend on i.  Its row inside the group, (i RPI + lrow0) & 15, does not either
+  // when an instruction covers whole groups (RPI % 16 == 0: D <= 128, and e4m3 at D = 256); a 16-bit cache at D = 256 has RPI = 8,
+  // lrow0 < 8, and the row is lrow0 + (i RPI & 15): `kstep` / `vstep`, the bytes of RPI rows, are added for odd i.
+  static_assert(16 % (64 / CPR) == 0 && (RPI % 16 == 0 || 16 % RPI == 0),
+                "the rows of a wave-instruction stay inside a 16-key group, and those of a workgroup-instruction tile the groups");
   u32x4 kreg[NCH], vreg[NCH];
   const int lrow0 = tid / CPR, lc = tid % CPR;
   const int64_t kin = (int64_t)(lrow0 & 15) * ldk * ESZ + lc * 16, vin = (int64_t)(lrow0 & 15) * ldv * ESZ + lc * 16;   // bytes
+  const int64_t kstep = (int64_t)RPI * ldk * ESZ, vstep = (int64_t)RPI * ldv * ESZ;   // (RPI < 16 only)
   auto issue_loads = [&](uint32_t key0) MFA_PREFILL_INLINE {
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
@@ -318,8 +324,14 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
       group_offsets(key0 + 16u * g, ko, vo);
       u32x4 zk = {0u, 0u, 0u, 0u}, zv = {0u, 0u, 0u, 0u};
       if (key0 + (uint32_t)r < n) {   // rows at or past n are never loaded: zeros
-        zk = *reinterpret_cast<const u32x4 *>(a.k + ko * ESZ + kin);
-        zv = *reinterpret_cast<const u32x4 *>(a.v + vo * ESZ + vin);
+        if constexpr (RPI % 16 == 0) {
+          zk = *reinterpret_cast<const u32x4 *>(a.k + ko * ESZ + kin);
+          zv = *reinterpret_cast<const u32x4 *>(a.v + vo * ESZ + vin);
+        } else {
+          const int into = (j * RPI & 15) / RPI;   // whole instructions into the group: a constant of the unrolled loop
+          zk = *reinterpret_cast<const u32x4 *>(a.k + ko * ESZ + kin + into * kstep);
+          zv = *reinterpret_cast<const u32x4 *>(a.v + vo * ESZ + vin + into * vstep);
+        }
       }
       kreg[j] = zk;
       vreg[j] = zv;
@@ -450,3 +462,17 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
 }
 
 } // namespace mfa
+
+// One list of the kernel families, (infix, WINDOW, SINK, RAGGED): the kernels, the table that selects them (attn_prefill16.hip) and the
+// names are generated from it.  MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, ...) is a set's code objects, in the translation unit that
+// holds them; (MFA_PREFILL_DECLARE, ...) names the kernels of another unit for the table.  D = 256 runs one workgroup per compute unit.
+#define MFA_PREFILL_FAMILIES(X, K, TN, T, D)                                                                                          \
+  X(K, , false, false, false, TN, T, D) X(K, w, true, false, false, TN, T, D) X(K, s, true, true, false, TN, T, D)                    \
+  X(K, r, true, true, true, TN, T, D)
+#define MFA_PREFILL_DEFINE(NAME, D, ...)                                                                                              \
+  extern "C" __global__ __launch_bounds__(256, D == 256 ? 1 : 2) void NAME(const mfa::PrefillArgs a) { mfa::prefill16_body<__VA_ARGS__>(a); }
+#define MFA_PREFILL_DECLARE(NAME, D, ...) extern "C" __global__ void NAME(const mfa::PrefillArgs a);
+#define MFA_PREFILL_FAMILY(K, I, WINDOW, SINK, RAGGED, TN, T, D)                                                                      \
+  K(attn_prefill16##I##_d##D##_##TN, D, T, D, false, WINDOW, SINK, RAGGED)                                                            \
+  K(attn_prefill16##I##_d##D##_##TN##_e4m3, D, T, D, true, WINDOW, SINK, RAGGED)
+#define MFA_PREFILL_KERNELS(K, TN, T, D) MFA_PREFILL_FAMILIES(MFA_PREFILL_FAMILY, K, TN, T, D)

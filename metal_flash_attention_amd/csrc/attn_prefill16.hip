@@ -25,20 +25,13 @@ using namespace mfa;
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_prefill16_d<D>_<type>[_e4m3], and attn_prefill16w_*
 // under a sliding window, attn_prefill16s_* with attention sinks, attn_prefill16r_* over packed rows (the sink body: one ragged kernel
 // serves plain, window and sink launches)
-// One list of the kernel families, (infix, WINDOW, SINK, RAGGED): the kernels, the table that selects them and the names are generated
-// from it
-#define MFA_PREFILL_FAMILIES(X, TN, T, D)                                                                                             \
-  X(, false, false, false, TN, T, D) X(w, true, false, false, TN, T, D) X(s, true, true, false, TN, T, D) X(r, true, true, true, TN, T, D)
-#define MFA_PREFILL_KERNEL(NAME, ...)                                                                                                 \
-  extern "C" __global__ __launch_bounds__(256, 2) void NAME(const PrefillArgs a) { prefill16_body<__VA_ARGS__>(a); }
-#define MFA_PREFILL_FAMILY(I, WINDOW, SINK, RAGGED, TN, T, D)                                                                         \
-  MFA_PREFILL_KERNEL(attn_prefill16##I##_d##D##_##TN, T, D, false, WINDOW, SINK, RAGGED)                                              \
-  MFA_PREFILL_KERNEL(attn_prefill16##I##_d##D##_##TN##_e4m3, T, D, true, WINDOW, SINK, RAGGED)
-#define MFA_PREFILL_KERNELS(TN, T, D) MFA_PREFILL_FAMILIES(MFA_PREFILL_FAMILY, TN, T, D)
-MFA_PREFILL_KERNELS(bf16, __bf16, 64)
-MFA_PREFILL_KERNELS(bf16, __bf16, 128)
-MFA_PREFILL_KERNELS(f16, _Float16, 64)
-MFA_PREFILL_KERNELS(f16, _Float16, 128)
+// (the macros that generate them from one list of families: attn_prefill16.h).  D = 256 lives in attn_prefill16_d256.hip.
+MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, bf16, __bf16, 64)
+MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, bf16, __bf16, 128)
+MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, f16, _Float16, 64)
+MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, f16, _Float16, 128)
+MFA_PREFILL_KERNELS(MFA_PREFILL_DECLARE, bf16, __bf16, 256)
+MFA_PREFILL_KERNELS(MFA_PREFILL_DECLARE, f16, _Float16, 256)
 
 namespace {
 
@@ -53,11 +46,11 @@ struct PrefillSet {
   PrefillKernel kernel[4][2];   // [0: plain, 1: window, 2: sinks, 3: ragged][e4m3]
 };
 #define MFA_PREFILL_ENTRY(NAME) {NAME, #NAME}
-#define MFA_PREFILL_SET_FAMILY(I, WINDOW, SINK, RAGGED, TN, T, D)                                                                     \
+#define MFA_PREFILL_SET_FAMILY(K, I, WINDOW, SINK, RAGGED, TN, T, D)                                                                  \
   {MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN), MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN##_e4m3)},
-#define MFA_PREFILL_SET(TN, PREC, D) {D, PREC, (uint32_t)prefill16_lds_bytes<D>(), {MFA_PREFILL_FAMILIES(MFA_PREFILL_SET_FAMILY, TN, , D)}}
-const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(f16, MFA_FP16, 64),
-                            MFA_PREFILL_SET(f16, MFA_FP16, 128)};
+#define MFA_PREFILL_SET(TN, PREC, D) {D, PREC, (uint32_t)prefill16_lds_bytes<D>(), {MFA_PREFILL_FAMILIES(MFA_PREFILL_SET_FAMILY, , TN, , D)}}
+const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(bf16, MFA_BF16, 256),
+                            MFA_PREFILL_SET(f16, MFA_FP16, 64),  MFA_PREFILL_SET(f16, MFA_FP16, 128),  MFA_PREFILL_SET(f16, MFA_FP16, 256)};
 
 // min(T / RB + batches, batches x ceil(rows / RB)): never below sum_b ceil(qn_b / RB) for non-decreasing starts
 uint64_t ragged_slots(uint32_t totalRows, uint32_t batches, uint32_t rows, uint32_t RB) {
@@ -109,7 +102,7 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &si
   for (const PrefillSet &s : kSets)
     if (s.D == p->headDimension && s.precision == p->precision) set = &s;
   if (!set)
-    return fail(MFA_ERR_UNSUPPORTED, "prefill attention is compiled for head dimensions 64 and 128, not " + std::to_string(p->headDimension));
+    return fail(MFA_ERR_UNSUPPORTED, "prefill attention is compiled for head dimensions 256, 64 and 128, not " + std::to_string(p->headDimension));
   if (p->rows == 0 || p->column == 0 || p->heads == 0 || p->batches == 0)
     return fail(MFA_ERR_INVALID_ARGUMENT, "rows, column, heads and batches must be non-zero");
   const uint32_t G = p->headsPerKeyValue > 1 ? p->headsPerKeyValue : 1;

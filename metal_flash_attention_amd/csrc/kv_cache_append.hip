@@ -117,17 +117,39 @@ __device__ __forceinline__ void kv_append_ragged_body(const AppendArgs &a) {
   }
 MFA_KV_APPEND_KERNELS(bf16, __bf16, 64)
 MFA_KV_APPEND_KERNELS(bf16, __bf16, 128)
+MFA_KV_APPEND_KERNELS(bf16, __bf16, 256)
 MFA_KV_APPEND_KERNELS(f16, _Float16, 64)
 MFA_KV_APPEND_KERNELS(f16, _Float16, 128)
+MFA_KV_APPEND_KERNELS(f16, _Float16, 256)
 // a 16-bit cache takes the bits as they are: one kernel per head dimension serves both types
-extern "C" __global__ __launch_bounds__(256) void kv_cache_append_d64_copy16(const AppendArgs a) { kv_append_body<__bf16, 64, false>(a); }
-extern "C" __global__ __launch_bounds__(256) void kv_cache_append_d128_copy16(const AppendArgs a) { kv_append_body<__bf16, 128, false>(a); }
-extern "C" __global__ __launch_bounds__(256) void kv_cache_append_ragged_d64_copy16(const AppendArgs a) { kv_append_ragged_body<__bf16, 64, false>(a); }
-extern "C" __global__ __launch_bounds__(256) void kv_cache_append_ragged_d128_copy16(const AppendArgs a) { kv_append_ragged_body<__bf16, 128, false>(a); }
+#define MFA_KV_COPY_KERNELS(D)                                                                                                        \
+  extern "C" __global__ __launch_bounds__(256) void kv_cache_append_d##D##_copy16(const AppendArgs a) { kv_append_body<__bf16, D, false>(a); } \
+  extern "C" __global__ __launch_bounds__(256) void kv_cache_append_ragged_d##D##_copy16(const AppendArgs a) {                        \
+    kv_append_ragged_body<__bf16, D, false>(a);                                                                                       \
+  }
+MFA_KV_COPY_KERNELS(64)
+MFA_KV_COPY_KERNELS(128)
+MFA_KV_COPY_KERNELS(256)
 
 namespace {
 
 typedef void (*AppendKernel)(const AppendArgs);
+struct AppendEntry {
+  AppendKernel launch;
+  const char *name;
+};
+struct AppendSet {
+  uint32_t D;
+  AppendEntry kernel[2][3];   // [ragged][0: a 16-bit cache, 1: bf16 rows into e4m3, 2: f16 rows into e4m3]
+};
+#define MFA_KV_APPEND_ENTRY(NAME) {NAME, #NAME}
+#define MFA_KV_APPEND_SET(D)                                                                                                          \
+  {D,                                                                                                                                 \
+   {{MFA_KV_APPEND_ENTRY(kv_cache_append_d##D##_copy16), MFA_KV_APPEND_ENTRY(kv_cache_append_d##D##_bf16_e4m3),                       \
+     MFA_KV_APPEND_ENTRY(kv_cache_append_d##D##_f16_e4m3)},                                                                           \
+    {MFA_KV_APPEND_ENTRY(kv_cache_append_ragged_d##D##_copy16), MFA_KV_APPEND_ENTRY(kv_cache_append_ragged_d##D##_bf16_e4m3),         \
+     MFA_KV_APPEND_ENTRY(kv_cache_append_ragged_d##D##_f16_e4m3)}}}
+const AppendSet kSets[] = {MFA_KV_APPEND_SET(64), MFA_KV_APPEND_SET(128), MFA_KV_APPEND_SET(256)};
 
 mfa_status prepare(const mfa_kv_append_params *p, AppendArgs *a, AppendKernel *kernel, const char **name, const mfa_ragged_rows *ragged = nullptr) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
@@ -147,8 +169,11 @@ mfa_status prepare(const mfa_kv_append_params *p, AppendArgs *a, AppendKernel *k
   if (st != MFA_OK) return st;
   if (!fp8 && p->cachePrecision != p->precision)
     return fail(MFA_ERR_INVALID_ARGUMENT, "cachePrecision must be the rows' 16-bit type (`precision`) or MFA_KV_E4M3");
-  if (p->headDimension != 64 && p->headDimension != 128)
-    return fail(MFA_ERR_UNSUPPORTED, "the KV cache append is compiled for head dimensions 64 and 128, not " + std::to_string(p->headDimension));
+  const AppendSet *set = nullptr;
+  for (const AppendSet &s : kSets)
+    if (s.D == p->headDimension) set = &s;
+  if (!set)
+    return fail(MFA_ERR_UNSUPPORTED, "the KV cache append is compiled for head dimensions 256, 64 and 128, not " + std::to_string(p->headDimension));
   if (p->rows == 0 || p->heads == 0 || p->batches == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "rows, heads and batches must be non-zero");
   if (!ragged && (uint64_t)p->rows * p->batches > 0x7FFFFFFFull) return fail(MFA_ERR_INVALID_ARGUMENT, "rows x batches must fit a grid of 2^31 - 1 workgroups");
   if (!p->cacheLengths) return fail(MFA_ERR_INVALID_ARGUMENT, "cacheLengths is required (device array of `batches` uint32)");
@@ -178,29 +203,12 @@ mfa_status prepare(const mfa_kv_append_params *p, AppendArgs *a, AppendKernel *k
   }
   a->R = p->rows; a->H = p->heads; a->column = p->column;
   a->paged = p->pageSize != 0; a->pageShift = pageShift;
-  const bool d128 = p->headDimension == 128, bf = p->precision == MFA_BF16;
   if (ragged) {
     a->rowStarts = ragged->rowStarts; a->totalRows = ragged->totalRows; a->batches = p->batches;
-    if (!fp8) {
-      *kernel = d128 ? kv_cache_append_ragged_d128_copy16 : kv_cache_append_ragged_d64_copy16;
-      *name = d128 ? "kv_cache_append_ragged_d128_copy16" : "kv_cache_append_ragged_d64_copy16";
-    } else if (bf) {
-      *kernel = d128 ? kv_cache_append_ragged_d128_bf16_e4m3 : kv_cache_append_ragged_d64_bf16_e4m3;
-      *name = d128 ? "kv_cache_append_ragged_d128_bf16_e4m3" : "kv_cache_append_ragged_d64_bf16_e4m3";
-    } else {
-      *kernel = d128 ? kv_cache_append_ragged_d128_f16_e4m3 : kv_cache_append_ragged_d64_f16_e4m3;
-      *name = d128 ? "kv_cache_append_ragged_d128_f16_e4m3" : "kv_cache_append_ragged_d64_f16_e4m3";
-    }
-  } else if (!fp8) {
-    *kernel = d128 ? kv_cache_append_d128_copy16 : kv_cache_append_d64_copy16;
-    *name = d128 ? "kv_cache_append_d128_copy16" : "kv_cache_append_d64_copy16";
-  } else if (bf) {
-    *kernel = d128 ? kv_cache_append_d128_bf16_e4m3 : kv_cache_append_d64_bf16_e4m3;
-    *name = d128 ? "kv_cache_append_d128_bf16_e4m3" : "kv_cache_append_d64_bf16_e4m3";
-  } else {
-    *kernel = d128 ? kv_cache_append_d128_f16_e4m3 : kv_cache_append_d64_f16_e4m3;
-    *name = d128 ? "kv_cache_append_d128_f16_e4m3" : "kv_cache_append_d64_f16_e4m3";
   }
+  const AppendEntry &entry = set->kernel[ragged != nullptr][!fp8 ? 0 : p->precision == MFA_BF16 ? 1 : 2];
+  *kernel = entry.launch;
+  *name = entry.name;
   return MFA_OK;
 }
 

@@ -1,7 +1,7 @@
 """Decode attention over a KV cache (include/mfa_decode.h) against the only route the library had before it: the ordinary forward
 launch with headsPerKeyValue + columnLengths + causal.  Both arms run from one library, in one process.
 
-Shapes: bf16, D = 128, Hq = 64 query heads over Hkv = 8 K / V heads (G = 8); R = 1 and 4 new rows; B = 1, 8, 64 sequences; caches of
+Shapes: bf16, D = 128 or 256 (--head-dim, default 128), Hq = 64 query heads over Hkv = 8 K / V heads (G = 8); R = 1 and 4 new rows; B = 1, 8, 64 sequences; caches of
 4096 and 32768 keys, all full or with seeded mixed lengths (uniform between a quarter and the whole of the cache); the B = 8 rows
 also with a paged cache (page sizes 16 and 256, shuffled pages) -- the forward launch cannot read pages, so their arm (b) is the
 contiguous launch of the same shape.
@@ -15,6 +15,7 @@ launch).  TB/s = algorithmic bytes (sum_b len_b x Hkv x D x 2 operands x 2 bytes
 
     python tools/decode_perf.py                  # the table
     python tools/decode_perf.py --trace-only     # a few launches of each arm, nothing timed: for rocprofv3 --kernel-trace --stats
+    python tools/decode_perf.py --head-dim 256   # the same table at D = 256 (both arms; the forward launch is D = 256's only other route)
     python tools/decode_perf.py --fp8            # another table: decode over an e4m3 cache (include/mfa_kvcache.h) against the 16-bit
                                                  # decode launch, R = 1, same method; plus the append launch at B = 64
 """
@@ -32,11 +33,11 @@ import torch  # noqa: E402
 from metal_flash_attention_amd import (AttentionDecode, AttentionDecodeFP8, KVCacheAppend, KVCachePrecision, AttentionDescriptor, AttentionKernel, AttentionKernelType, AttentionOperand as Op,  # noqa: E402
                                        GEMMOperandPrecision as P, _abi)
 
-HQ, HKV, D = 64, 8, 128
+HQ, HKV = 64, 8
 G = HQ // HKV
 
 
-def forward_kernel(R, C):
+def forward_kernel(R, C, D):
     d = AttentionDescriptor()
     d.lowPrecisionInputs, d.lowPrecisionIntermediates = True, False
     d.lowPrecisionInputType, d.lowPrecisionOutputs = P.BF16, True
@@ -45,8 +46,8 @@ def forward_kernel(R, C):
 
 
 class Row:
-    def __init__(self, B, C, R, mixed, page, rotate_bytes):
-        self.B, self.C, self.R, self.mixed, self.page = B, C, R, mixed, page
+    def __init__(self, B, C, R, mixed, page, rotate_bytes, D):
+        self.B, self.C, self.R, self.mixed, self.page, self.D = B, C, R, mixed, page, D
         g = torch.Generator().manual_seed(B * 131 + C + R)
         lens = torch.randint(C // 4, C + 1, (B,), generator=g, dtype=torch.int32) if mixed else torch.full((B,), C, dtype=torch.int32)
         self.keys = int(lens.sum())
@@ -74,7 +75,7 @@ class Row:
         need = self.decode.workspaceSize(**self.kw)
         self.ws = torch.empty(need, dtype=torch.uint8, device="cuda") if need else None
         self.form = self.decode.launchForm(workspace=self.ws, **self.kw)
-        self.forward = forward_kernel(R, C)
+        self.forward = forward_kernel(R, C, D)
         self.hs = {Op.Q: R * D, Op.K: C * D, Op.V: C * D, Op.O: R * D, Op.L: R}
         self.bs = {Op.Q: HQ * R * D, Op.K: HKV * C * D, Op.V: HKV * C * D, Op.O: HQ * R * D, Op.L: HQ * R}
 
@@ -133,8 +134,8 @@ class RowFP8:
     """R = 1: the FP8 decode launch (arm "fp8") and the 16-bit decode launch (arm "bf16") of the same shape, each rotating over its own
     cache copies whose sum is >= rotate_bytes; "append": the append launch that precedes a decode step (e4m3 cache)"""
 
-    def __init__(self, B, C, mixed, rotate_bytes):
-        self.B, self.C, self.R, self.mixed = B, C, 1, mixed
+    def __init__(self, B, C, mixed, rotate_bytes, D):
+        self.B, self.C, self.R, self.mixed, self.D = B, C, 1, mixed, D
         g = torch.Generator().manual_seed(B * 131 + C + 1)
         lens = torch.randint(C // 4, C + 1, (B,), generator=g, dtype=torch.int32) if mixed else torch.full((B,), C, dtype=torch.int32)
         self.keys = int(lens.sum())
@@ -203,13 +204,13 @@ def measure_arms(row, arms, rounds, window_ms):
 def main_fp8(a):
     print("bf16 Q, D %d, Hq %d, Hkv %d (G %d), causal, R 1; arm (a) = decode over an e4m3 cache with per-head scales, arm (b) = the 16-bit decode "
           "launch; us per launch: median (min .. max) of %d rounds; TB/s = each arm's own algorithmic bytes over its time; achievable HBM "
-          "rate 6.0-6.3 TB/s" % (D, HQ, HKV, G, a.rounds))
+          "rate 6.0-6.3 TB/s" % (a.head_dim, HQ, HKV, G, a.rounds))
     for B in (1, 8, 64):
         for C in (4096, 32768):
             if a.quick and (B == 64 or C != 4096):
                 continue
             for mixed in (False, True):
-                row = RowFP8(B, C, mixed, a.rotate_bytes)
+                row = RowFP8(B, C, mixed, a.rotate_bytes, a.head_dim)
                 arms = ("bf16", "fp8") + (("append",) if B == 64 else ())
                 r = measure_arms(row, arms, a.rounds, a.window_ms)
                 (fa, flo, fhi, fn), (ba, blo, bhi, bn) = r["fp8"], r["bf16"]
@@ -228,6 +229,7 @@ def main_fp8(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fp8", action="store_true", help="the e4m3-cache decode launch against the 16-bit decode launch (another table)")
+    ap.add_argument("--head-dim", type=int, default=128, choices=(128, 256), help="the head dimension of every row (both arms)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--window-ms", type=float, default=150.0, help="device time one timed replay aims at")
     ap.add_argument("--rotate-bytes", type=int, default=1 << 30)
@@ -240,7 +242,7 @@ def main():
     if a.fp8:
         return main_fp8(a)
     print("bf16, D %d, Hq %d, Hkv %d (G %d), causal; arm (a) = decode launch, arm (b) = forward launch with headsPerKeyValue + "
-          "columnLengths + causal; us per launch: median (min .. max) of %d rounds; achievable HBM rate 6.0-6.3 TB/s" % (D, HQ, HKV, G, a.rounds))
+          "columnLengths + causal; us per launch: median (min .. max) of %d rounds; achievable HBM rate 6.0-6.3 TB/s" % (a.head_dim, HQ, HKV, G, a.rounds))
     rows = []
     for R in (1, 4):
         for B in (1, 8, 64):
@@ -251,7 +253,7 @@ def main():
                     for page in ((0, 16, 256) if B == 8 else (0,)):
                         rows.append((B, C, R, mixed, page))
     for B, C, R, mixed, page in rows:
-        row = Row(B, C, R, mixed, page, a.rotate_bytes)
+        row = Row(B, C, R, mixed, page, a.rotate_bytes, a.head_dim)
         if a.trace_only:
             s = torch.cuda.current_stream().cuda_stream
             for i in range(3):

@@ -3,7 +3,7 @@ headsPerKeyValue + rowLengths + columnLengths + causal on a contiguous 16-bit ca
 launch cannot read -- a torch gather (and dequantise) of the pages into a contiguous 16-bit buffer followed by that forward launch.
 All arms run from one library, in one process.
 
-Shapes: bf16, D = 128, Hq = 64 query heads, G = 8 and G = 1, causal; a chunk of R = 512 and 2048 new rows against n = 4096 / 32768
+Shapes: bf16, D = 128 or 256 (--head-dim, default 128), Hq = 64 query heads, G = 8 and G = 1, causal; a chunk of R = 512 and 2048 new rows against n = 4096 / 32768
 cached keys (the chunk's own keys included), B = 1 and 8 sequences, every sequence full.  Arms:
   (a16) (a256)  the prefill launch on a paged cache, page sizes 16 and 256, shuffled tables
   (a')          the prefill launch on the contiguous cache
@@ -20,6 +20,7 @@ spread (min .. max) of --rounds rounds after a warm-up replay of each.  roof = 4
 as a fraction of 2500 TFLOP/s (the bf16 matrix peak bench.py uses).
 
     python tools/prefill_perf.py                 # the table
+    python tools/prefill_perf.py --head-dim 256  # the same table at D = 256 (every arm)
     python tools/prefill_perf.py --quick         # B = 1, n = 4096 only (a rehearsal)
     python tools/prefill_perf.py --trace-only    # a few launches of each arm of the largest shape, nothing timed: for a kernel trace
 """
@@ -37,12 +38,12 @@ import torch  # noqa: E402
 from metal_flash_attention_amd import (AttentionDescriptor, AttentionKernel, AttentionKernelType, AttentionOperand as Op, AttentionPrefill,  # noqa: E402
                                        GEMMOperandPrecision as P, KVCachePrecision, _abi)
 
-HQ, D = 64, 128
+HQ = 64
 PEAK = 2500e12
 ARMS = ("a16", "a256", "a'", "a8", "b", "b'", "b'8")
 
 
-def forward_kernel(R, C):
+def forward_kernel(R, C, D):
     d = AttentionDescriptor()
     d.lowPrecisionInputs, d.lowPrecisionIntermediates = True, False
     d.lowPrecisionInputType, d.lowPrecisionOutputs = P.BF16, True
@@ -51,8 +52,8 @@ def forward_kernel(R, C):
 
 
 class Row:
-    def __init__(self, B, C, R, G, rotate_bytes):
-        self.B, self.C, self.R, self.G = B, C, R, G
+    def __init__(self, B, C, R, G, rotate_bytes, D):
+        self.B, self.C, self.R, self.G, self.D = B, C, R, G, D
         Hkv = self.Hkv = HQ // G
         g = torch.Generator().manual_seed(B * 131 + C + R + G)
         self.lens = torch.full((B,), C, dtype=torch.int32, device="cuda")
@@ -79,13 +80,13 @@ class Row:
                                             strides=dict(K=(D, page * D, 0), V=(D, page * D, 0))))
         self.index = self.paged[16][0].view(-1).long()
         self.form = self.pre.launchForm(**self.kw)
-        self.forward = forward_kernel(R, C)
+        self.forward = forward_kernel(R, C, D)
         self.hs = {Op.Q: R * D, Op.K: C * D, Op.V: C * D, Op.O: R * D, Op.L: R}
         self.bs = {Op.Q: HQ * R * D, Op.K: Hkv * C * D, Op.V: Hkv * C * D, Op.O: HQ * R * D, Op.L: HQ * R}
 
     def gather(self, pool, dst):
         """the pages of every sequence, in order, into the contiguous [B][Hkv][C][D] buffer (converting when the pool is e4m3)"""
-        B, Hkv, per = self.B, self.Hkv, self.C // 16
+        B, Hkv, per, D = self.B, self.Hkv, self.C // 16, self.D
         pages = pool.view(B * per, Hkv, 16, D).index_select(0, self.index)
         dst.view(B, Hkv, per, 16, D).copy_(pages.view(B, per, Hkv, 16, D).permute(0, 2, 1, 3, 4))
 
@@ -152,6 +153,7 @@ def measure(row, rounds, window_ms):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--head-dim", type=int, default=128, choices=(128, 256), help="the head dimension of every row (every arm)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--window-ms", type=float, default=60.0, help="device time one timed replay aims at")
     ap.add_argument("--rotate-bytes", type=int, default=1 << 30)
@@ -161,7 +163,7 @@ def main():
     assert torch.cuda.is_available(), "prefill_perf.py measures on the GPU: there is nothing to report without one"
     print("library sha256 %s" % hashlib.sha256(open(_abi.library_path(), "rb").read()).hexdigest())
     if a.trace_only:
-        row = Row(8, 32768, 2048, 8, a.rotate_bytes)
+        row = Row(8, 32768, 2048, 8, a.rotate_bytes, a.head_dim)
         s = torch.cuda.current_stream().cuda_stream
         for i in range(3):
             for arm in ARMS:
@@ -169,14 +171,14 @@ def main():
         torch.cuda.synchronize()
         return
     print("bf16, D %d, Hq %d, causal, full sequences; us per launch: median (min .. max) of %d rounds, launches per replay after x; "
-          "roof = fraction of %.0f TFLOP/s" % (D, HQ, a.rounds, PEAK / 1e12))
+          "roof = fraction of %.0f TFLOP/s" % (a.head_dim, HQ, a.rounds, PEAK / 1e12))
     for G in (8, 1):
         for R in (512, 2048):
             for C in (4096, 32768):
                 for B in (1, 8):
                     if a.quick and (B != 1 or C != 4096):
                         continue
-                    row = Row(B, C, R, G, a.rotate_bytes)
+                    row = Row(B, C, R, G, a.rotate_bytes, a.head_dim)
                     r = measure(row, a.rounds, a.window_ms)
                     print("G %d  R %4d  n %5d  B %d  copies %2d  %s" % (G, R, C, B, row.copies, row.form), flush=True)
                     for arm in ARMS:
