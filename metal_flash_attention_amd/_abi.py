@@ -313,6 +313,23 @@ RAGGED_SYMBOLS = [   # include/mfa_ragged.h: `ragged` (required) after `sinks` (
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(mfa_kv_append_params), _RAGGED, ctypes.c_void_p]),
 ]
 
+_CAP = ctypes.c_float
+
+SOFTCAP_SYMBOLS = [   # include/mfa_softcap.h: `softcap` (float, 0 = none) after `sinks` (NULL = none) / after `ragged`
+    ("mfa_attention_decode_softcap_workspace_size", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, _CAP, ctypes.POINTER(ctypes.c_uint64)]),
+    ("mfa_attention_decode_softcap_launch", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_void_p]),
+    ("mfa_attention_decode_softcap_launch_form", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_decode_softcap_time", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_void_p] + _TIMING),
+    ("mfa_attention_prefill_softcap_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_void_p]),
+    ("mfa_attention_prefill_softcap_launch_form", ctypes.c_int, [_PREFILL, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_prefill_softcap_time", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_void_p] + _TIMING),
+    ("mfa_attention_prefill_ragged_softcap_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, _CAP, ctypes.c_void_p]),
+    ("mfa_attention_prefill_ragged_softcap_launch_form", ctypes.c_int,
+     [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, _CAP, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_prefill_ragged_softcap_time", ctypes.c_int,
+     _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, _CAP, ctypes.c_void_p] + _TIMING),
+]
+
 SYMBOLS = [
     ("mfa_precision_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mfa_precision_size", ctypes.c_int, [ctypes.c_int]),
@@ -388,7 +405,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

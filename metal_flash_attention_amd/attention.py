@@ -427,6 +427,13 @@ def _ragged_block(shape):
     return block, starts
 
 
+def _softcap(shape):
+    """pops softcap= from a launch's keywords -> ctypes.c_float, or None when it is not given (include/mfa_softcap.h: 0 goes through the
+    soft-cap entries and is the launch without a cap; what the value may be is the library's to say)"""
+    cap = shape.pop("softcap", None)
+    return None if cap is None else ctypes.c_float(cap)
+
+
 def _pointers(*buffers):
     return tuple(_pointer(b) for b in buffers)
 
@@ -472,7 +479,10 @@ class AttentionDecode:
 
     sinkTokens=S, sinkLogits=device FP32 [heads] (the same four methods): attention sinks, include/mfa_sink.h -- the keys [0, S) stay
     visible under the window (needs window >= 1), and one logit per query head joins the softmax denominator (natural-log units,
-    any window).  Either keyword, even 0 / None beside the other, goes through the sink entries."""
+    any window).  Either keyword, even 0 / None beside the other, goes through the sink entries.
+
+    softcap=cap (the same four methods): logit soft-capping, include/mfa_softcap.h -- the softmax sees cap tanh(score / cap), cap > 0 in
+    natural-log units (Gemma 2: 50).  None: no cap; 0 goes through the soft-cap entries and is the launch without a cap."""
 
     OPERANDS = ("Q", "K", "V", "O")
 
@@ -507,13 +517,16 @@ class AttentionDecode:
 
     def _call(self, suffix, shape, head=(), tail=()):
         """mfa_attention_decode_<family><suffix>(*head, params, <the family's own arguments>, *tail).  The family, from the keywords:
-        sink_ (quant, window, sinks) with either sink keyword, else window_ (quant, window) with a window that is not None, else fp8_
-        (quant) over an e4m3 cache, else the plain entries"""
-        window, sinks = shape.pop("window", None), _sinks_block(shape)
+        softcap_ (quant, window, sinks or NULL, softcap) with a softcap that is not None whichever window and sinks, else sink_ (quant,
+        window, sinks) with either sink keyword, else window_ (quant, window) with a window that is not None, else fp8_ (quant) over an
+        e4m3 cache, else the plain entries"""
+        window, sinks, cap = shape.pop("window", None), _sinks_block(shape), _softcap(shape)
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape)
         q = None if quant is None else ctypes.byref(quant)
-        if sinks is not None:
+        if cap is not None:
+            family, own = "softcap_", (q, int(window or 0), None if sinks is None else ctypes.byref(sinks[0]), cap)
+        elif sinks is not None:
             family, own = "sink_", (q, int(window or 0), ctypes.byref(sinks[0]))
         elif window is not None:
             family, own = "window_", (q, int(window))
@@ -613,7 +626,9 @@ class AttentionPrefill:
     rowStarts=device uint32 [batches + 1], totalRows=T (the same three): a RAGGED batch, include/mfa_ragged.h -- q, o [T, heads, D] and
     l [heads, T] packed along the rows, sequence b owning the rows rowStarts[b] .. rowStarts[b + 1]; `rows` is then the largest row
     count of a sequence, queryLengths must stay None and Q / O / L have no batch stride (operands left out of `strides` are taken as
-    contiguous [T, heads, D]).  Goes through the ragged entries whichever window and sinks."""
+    contiguous [T, heads, D]).  Goes through the ragged entries whichever window and sinks.
+
+    softcap=cap (the same three, ragged included): logit soft-capping as AttentionDecode's, include/mfa_softcap.h."""
 
     OPERANDS = ("Q", "K", "V", "O")
 
@@ -652,11 +667,15 @@ class AttentionPrefill:
     def _call(self, suffix, shape, head=(), tail=()):
         """mfa_attention_prefill_<family><suffix>(*head, params, <the family's own arguments>, *tail).  The family, from the keywords:
         ragged_ (window, sinks or NULL, ragged) with rowStarts / totalRows whichever window and sinks, else sink_ (window, sinks) with
-        either sink keyword, else window_ (window) with a window that is not None, else the plain entries"""
-        window, sinks, ragged = shape.pop("window", None), _sinks_block(shape), _ragged_block(shape)
+        either sink keyword, else window_ (window) with a window that is not None, else the plain entries; a softcap that is not None
+        takes ragged_softcap_ (window, sinks or NULL, ragged, softcap) or softcap_ (window, sinks or NULL, softcap) in their place"""
+        window, sinks, ragged, cap = shape.pop("window", None), _sinks_block(shape), _ragged_block(shape), _softcap(shape)
         p, _keep = self._params(ragged=ragged, **shape)
         s = None if sinks is None else ctypes.byref(sinks[0])
-        if ragged is not None:
+        if cap is not None:
+            family = "softcap_" if ragged is None else "ragged_softcap_"
+            own = (int(window or 0), s) + (() if ragged is None else (ctypes.byref(ragged[0]),)) + (cap,)
+        elif ragged is not None:
             family, own = "ragged_", (int(window or 0), s, ctypes.byref(ragged[0]))
         elif sinks is not None:
             family, own = "sink_", (int(window or 0), s)

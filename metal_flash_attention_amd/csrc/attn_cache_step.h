@@ -14,6 +14,17 @@
 //     With S = 0 and no logits the SINK kernels run the WINDOW kernels' arithmetic in their order.
 // A masked score is REPLACED, never multiplied (p = 0 exactly), and the running maximum only ever sees visible keys: a step without
 // a visible key keeps m = -FLT_MAX, l = 0, and what a masked key holds -- poison past a length -- never reaches a product.
+//
+// The rule of the soft cap (CAP; include/mfa_softcap.h).  With raw = q . k and s = raw keyScale / sqrt(D) the natural-unit
+// score the softmax sees without a cap (keyScale = 1 for 16-bit caches), a cap > 0 makes it see s' = cap tanh(s / cap) instead.
+//   * VISIBLE scores only: a masked score is still replaced, never computed from, so poison past a length never reaches the tanh.
+//   * the sink logit is not capped and not scaled; L = log2 of the denominator of the CAPPED scores plus the sink term.
+//   * which keys are visible, which tiles are walked, the pieces, the workspace and the O = 0 / L rules of a blind row do not change.
+//   * the arithmetic, on the base-2 score the kernels form anyway: with c1 = 2 / cap folded into kscale and c2 = cap log2(e),
+//       s2' = c2 (1 - 2 / (1 + exp2(c1 kscale raw))),    exp2(c1 kscale raw) = e^(2 s / cap)
+//     -- tanh(x) = 1 - 2 / (1 + e^(2x)) is right at both ends: e^(2x) = +inf gives +c2, 0 gives -c2, never NaN (the form
+//     (e^(2x) - 1) / (e^(2x) + 1) is inf / inf there).  One v_exp_f32, one v_rcp_f32 and four plain instructions per score; the
+//     cancellation near 0 costs absolute error of the order of c2 2^-24, far below the rounding of P.
 #pragma once
 #include "attn_fwd16_common.h"
 
@@ -25,7 +36,9 @@ constexpr float STEP_MINUS_HUGE = -3.402823466e+38f;   // m of a row that has se
 template <typename U> __host__ __device__ __forceinline__ U window_lo(U f1, U W) { return (f1 > W ? f1 : W) - W; }
 
 // The keys one query row sees, by the rule above.  `bound`: the keys the launch holds for the row's sequence (decode pieces: their end).
-template <bool WINDOW, bool SINK> struct VisibleKeys {
+// (CAP changes nothing here: it keeps the capped kernels' instantiations of the step apart from the sink kernels', whose code hipcc
+// otherwise orders differently once they share them)
+template <bool WINDOW, bool SINK, bool CAP = false> struct VisibleKeys {
   static_assert(!SINK || WINDOW, "the sink kernels are the window kernels plus SINK");
   uint32_t lim, lo = 0, span = 0, slim = 0;
   __device__ __forceinline__ VisibleKeys(uint32_t bound, uint32_t f1, uint32_t causal, uint32_t window, uint32_t sinkTokens) {
@@ -52,14 +65,21 @@ template <bool WINDOW, bool SINK> struct VisibleKeys {
 //   l += score_exp<T, MASK>(s, keys, cur, hi, m, pf);
 // MASK false: every key of the step is visible to every row (prefill's unmasked tiles).
 
-// scales the visible scores (the K scale rides on the softmax scale), replaces the others; returns the row's maximum over the step
-template <bool MASK, typename Keys>
-__device__ __forceinline__ float score_max(f32x16 &s, const Keys &keys, uint32_t cur, int hi, float kscale) {
+// the soft cap of one score: `x` = c1 kscale raw, returns c2 tanh(s / cap) in base-2 units (the rule above)
+__device__ __forceinline__ float soft_cap(float x, float c2) {
+  return c2 * (1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + fast_exp2(x)));
+}
+
+// scales the visible scores (the K scale rides on the softmax scale), replaces the others; returns the row's maximum over the step.
+// CAP: `kscale` carries c1 = 2 / cap as well, and the visible scores pass through soft_cap with c2 = `cap2` -- unmasked tiles too
+template <bool MASK, bool CAP = false, typename Keys>
+__device__ __forceinline__ float score_max(f32x16 &s, const Keys &keys, uint32_t cur, int hi, float kscale, float cap2 = 0.f) {
   float mx = STEP_MINUS_HUGE;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const bool visible = !MASK || keys.visible(cur + (uint32_t)crow(r, hi));
-    s[r] = visible ? s[r] * kscale : STEP_MINUS_HUGE;
+    if constexpr (CAP) s[r] = visible ? soft_cap(s[r] * kscale, cap2) : STEP_MINUS_HUGE;
+    else s[r] = visible ? s[r] * kscale : STEP_MINUS_HUGE;
     mx = fmaxf(mx, s[r]);
   }
   return fmaxf(mx, __shfl_xor(mx, 32));
@@ -112,7 +132,7 @@ template <typename T> __device__ __forceinline__ f32x16 vt_mfma(const char *vp, 
 
 // The sink logit joins a row's (m, l); returns `fold`, the factor that rescales the row's O with l.  A row without a visible key
 // (m = -FLT_MAX, l = 0) ends with m = s2, l = 1.
-__device__ __forceinline__ float fold_sink_logit(float logit, float &m, float &l) {
+template <bool CAP = false> __device__ __forceinline__ float fold_sink_logit(float logit, float &m, float &l) {
   float s2 = logit * 1.44269504089f;
   asm volatile("" : "+v"(s2));   // (s2 is the ROUNDED product in m and in both exponents: never fused into the subtractions below)
   const float mnew = fmaxf(m, s2);

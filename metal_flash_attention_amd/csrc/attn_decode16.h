@@ -45,6 +45,9 @@
 //     list_key() turns a position into the cache's key where one is addressed or masked; nothing between the two ranges is loaded.
 //   * SINK logit: the unsplit kernel adds it at the final normalisation; in the split kernels piece 0 folds it into the (m, l) it
 //     publishes -- an empty piece 0 publishes m = s2, l = 1, O = 0 -- so the combine kernel is reused as it stands.
+//
+// CAP: the soft cap of attn_cache_step.h on the visible scores, the SINK body otherwise (any window and sinks, none included): c1 rides
+// on kscale, c2 goes to score_max.  Pieces, workspace and the combine kernel are untouched -- the pieces publish capped (m, l).
 #pragma once
 #include "attn_cache_step.h"
 #include "kv_e4m3.h"
@@ -77,6 +80,7 @@ struct DecodeArgs {
   uint32_t window;                      // the WINDOW kernels only (>= 1); last, so that no other field moves
   uint32_t sinkTokens;                  // the SINK kernels only, which also take window = 0 (no window); behind `window` in turn
   const float *sinkLogits;              // [Hq], natural units; null: none
+  float capIn, capOut;                  // the CAP kernels only: c1 = 2 / cap and c2 = cap log2(e) (attn_cache_step.h); behind the sinks in turn
 };
 
 // The two key ranges of piece `piece` of `pieces` with `sinkTokens` sink keys under a window of `window` keys (0: no window, lo0 = 0):
@@ -130,8 +134,9 @@ template <int D> constexpr int decode16_lds_bytes() {
   return images > merge ? images : merge;
 }
 
-template <typename T, int D, bool SPLIT, bool FP8, bool WINDOW = false, bool SINK = false>
+template <typename T, int D, bool SPLIT, bool FP8, bool WINDOW = false, bool SINK = false, bool CAP = false>
 __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
+  static_assert(!CAP || SINK, "the capped kernels are the sink kernels plus CAP");
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -175,6 +180,7 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
     vscale = a.valueScale ? a.valueScale[kvh] : 1.0f;
   }
+  if constexpr (CAP) kscale *= a.capIn;   // (after the K scale: the cap is on the score the softmax would see)
 
   // ---- the lane's packed query row: p = (query head within the group) R + row; columns >= M repeat the last one and are not stored
   // (FP8: its fragments in the permuted contraction order of the K bytes)
@@ -197,7 +203,7 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     }
   }
   // keys this row sees (causal: c <= row + max(len - R, 0); always c < len, and inside this piece c < end)
-  const VisibleKeys<WINDOW, SINK> keys(SINK ? len : end, qrow + (len > R ? len - R : 0u) + 1u, a.causal, a.window, a.sinkTokens);
+  const VisibleKeys<WINDOW, SINK, CAP> keys(SINK ? len : end, qrow + (len > R ? len - R : 0u) + 1u, a.causal, a.window, a.sinkTokens);
 
   // ---- addresses of a step's two 16-key groups (wave-uniform; element offsets from a.k / a.v, which are byte offsets under FP8)
   const int64_t khead = (int64_t)kvh * a.hsk, vhead = (int64_t)kvh * a.hsv;
@@ -295,7 +301,8 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     if (key0 < end) issue_loads(key0);
 
     // ---- online softmax over the visible keys only (FP8: the K scale rides on the softmax scale)
-    rescale_row(score_max<true>(s, keys, cur, hi, kscale), m, l, o);
+    if constexpr (CAP) rescale_row(score_max<true, true>(s, keys, cur, hi, kscale, a.capOut), m, l, o);
+    else rescale_row(score_max<true>(s, keys, cur, hi, kscale), m, l, o);
     v8 pf[2];
     l += score_exp<T, true>(s, keys, cur, hi, m, pf);
 
@@ -348,7 +355,7 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     // SINK: the sink logit joins (m, l) -- piece 0's when the keys are split, the workgroup's otherwise; `fold` rescales O with l
     float fold = 1.0f;
     if constexpr (SINK) {
-      if (a.sinkLogits && piece == 0) fold = fold_sink_logit(a.sinkLogits[head], mrow, lsum);
+      if (a.sinkLogits && piece == 0) fold = fold_sink_logit<CAP>(a.sinkLogits[head], mrow, lsum);
     }
     if constexpr (SPLIT) {
       const size_t slab = (((size_t)piece * a.batches + batch) * a.Hq + head) * R + row;
@@ -417,18 +424,20 @@ __device__ __forceinline__ void decode16_combine_body(const DecodeArgs &a) {
 
 } // namespace mfa
 
-// One list of the kernel families, (infix, WINDOW, SINK): the kernels, the table that selects them (attn_decode16.hip) and the names
+// One list of the kernel families, (infix, WINDOW, SINK, CAP): the kernels, the table that selects them (attn_decode16.hip) and the names
 // are generated from it.  MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, ...) is a set's code objects, in the translation unit that holds
 // them; (MFA_DECODE_DECLARE, ...) names the kernels of another unit for the table.  D = 256 runs one workgroup per compute unit.
-#define MFA_DECODE_FAMILIES(X, K, TN, T, D) X(K, , false, false, TN, T, D) X(K, w, true, false, TN, T, D) X(K, s, true, true, TN, T, D)
+#define MFA_DECODE_FAMILIES(X, K, TN, T, D)                                                                                           \
+  X(K, , false, false, false, TN, T, D) X(K, w, true, false, false, TN, T, D) X(K, s, true, true, false, TN, T, D)                    \
+  X(K, c, true, true, true, TN, T, D)
 #define MFA_DECODE_DEFINE(NAME, BOUNDS, BODY, ...)                                                                                    \
   extern "C" __global__ BOUNDS void NAME(const mfa::DecodeArgs a) { mfa::BODY<__VA_ARGS__>(a); }
 #define MFA_DECODE_DECLARE(NAME, BOUNDS, BODY, ...) extern "C" __global__ void NAME(const mfa::DecodeArgs a);
-#define MFA_DECODE_FAMILY(K, I, WINDOW, SINK, TN, T, D)                                                                               \
-  K(attn_decode16##I##_d##D##_##TN##_single, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, false, false, WINDOW, SINK) \
-  K(attn_decode16##I##_d##D##_##TN##_pieces, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, true, false, WINDOW, SINK)  \
-  K(attn_decode8##I##_d##D##_##TN##_single, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, false, true, WINDOW, SINK)   \
-  K(attn_decode8##I##_d##D##_##TN##_pieces, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, true, true, WINDOW, SINK)
+#define MFA_DECODE_FAMILY(K, I, WINDOW, SINK, CAP, TN, T, D)                                                                          \
+  K(attn_decode16##I##_d##D##_##TN##_single, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, false, false, WINDOW, SINK, CAP) \
+  K(attn_decode16##I##_d##D##_##TN##_pieces, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, true, false, WINDOW, SINK, CAP)  \
+  K(attn_decode8##I##_d##D##_##TN##_single, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, false, true, WINDOW, SINK, CAP)   \
+  K(attn_decode8##I##_d##D##_##TN##_pieces, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, true, true, WINDOW, SINK, CAP)
 #define MFA_DECODE_KERNELS(K, TN, T, D)                                                                                               \
   MFA_DECODE_FAMILIES(MFA_DECODE_FAMILY, K, TN, T, D)                                                                                 \
   K(attn_decode16_d##D##_##TN##_combine, __launch_bounds__(256), decode16_combine_body, T, D)

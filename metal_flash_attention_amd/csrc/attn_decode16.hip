@@ -1,7 +1,8 @@
 // attn_decode16.hip -- decode attention over a KV cache, 16-bit or FP8 (e4m3): the kernels' code objects, the C ABI of
 // include/mfa_decode.h, the decode entries of include/mfa_kvcache.h and those of include/mfa_window.h (a sliding window: the same
 // plan with the piece count taken from the tiles a window can span, and the attn_decode16w_* / attn_decode8w_* kernels) and those of
-// include/mfa_sink.h (attention sinks: the window's plan plus the sink tiles, and the attn_decode16s_* / attn_decode8s_* kernels).  One
+// include/mfa_sink.h (attention sinks: the window's plan plus the sink tiles, and the attn_decode16s_* / attn_decode8s_* kernels) and
+// those of include/mfa_softcap.h (a soft cap on the scores: the sink launch's plan, and the attn_decode16c_* / attn_decode8c_* kernels).  One
 // plan serves both: the launch over an e4m3 cache adds its own checks in front of the 16-bit launch's, starts the attn_decode8_*
 // kernels in place of _single / _pieces, and shares the piece count, the workspace formula and the combine kernel.  The refusals of a
 // window and of sinks, and the Sinks of a launch, are cache_launch.h's, shared with attn_prefill16.hip.
@@ -17,6 +18,7 @@
 #include "../../include/mfa_decode.h"
 #include "../../include/mfa_kvcache.h"
 #include "../../include/mfa_sink.h"
+#include "../../include/mfa_softcap.h"
 #include "../../include/mfa_window.h"
 #include "attn_decode16.h"
 #include "cache_launch.h"
@@ -27,7 +29,8 @@ using namespace mfa;
 
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_decode16_d<D>_<type>_{single,pieces,combine} and, over
 // an e4m3 cache, attn_decode8_d<D>_<type of Q>_{single,pieces}, whose pieces attn_decode16_d<D>_<type>_combine merges; under a
-// sliding window attn_decode16w_* / attn_decode8w_*, with attention sinks attn_decode16s_* / attn_decode8s_*, merged by the same combine kernel
+// sliding window attn_decode16w_* / attn_decode8w_*, with attention sinks attn_decode16s_* / attn_decode8s_*, with a soft cap (whatever
+// the window and sinks) attn_decode16c_* / attn_decode8c_*, merged by the same combine kernel
 // (the macros that generate them from one list of families: attn_decode16.h).  D = 256 lives in attn_decode16_d256.hip.
 MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, bf16, __bf16, 64)
 MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, bf16, __bf16, 128)
@@ -46,11 +49,11 @@ struct DecodeSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  DecodeKernel kernel[3][2][2];   // [0: plain, 1: window, 2: sinks][fp8][pieces]
+  DecodeKernel kernel[4][2][2];   // [0: plain, 1: window, 2: sinks, 3: soft cap][fp8][pieces]
   DecodeKernel combine;
 };
 #define MFA_DECODE_ENTRY(NAME) {NAME, #NAME}
-#define MFA_DECODE_SET_FAMILY(K, I, WINDOW, SINK, TN, T, D)                                                                           \
+#define MFA_DECODE_SET_FAMILY(K, I, WINDOW, SINK, CAP, TN, T, D)                                                                      \
   {{MFA_DECODE_ENTRY(attn_decode16##I##_d##D##_##TN##_single), MFA_DECODE_ENTRY(attn_decode16##I##_d##D##_##TN##_pieces)},            \
    {MFA_DECODE_ENTRY(attn_decode8##I##_d##D##_##TN##_single), MFA_DECODE_ENTRY(attn_decode8##I##_d##D##_##TN##_pieces)}},
 #define MFA_DECODE_SET(TN, PREC, D)                                                                                                   \
@@ -90,7 +93,8 @@ struct DecodePlan {
   bool fp8;
   uint32_t window;      // 0: none
   Sinks sinks;
-  int family;           // 0: plain, 1: window, 2: sinks -- the kernels' first index
+  float softcap;        // 0: none
+  int family;           // 0: plain, 1: window, 2: sinks, 3: soft cap (whatever the window and sinks) -- the kernels' first index
   uint64_t tiles;       // what the piece count was chosen from
   uint32_t pieces;      // as the launch runs: 1 without a workspace
   uint32_t planned;     // what the host would cut the keys into
@@ -101,10 +105,12 @@ struct DecodePlan {
 };
 
 // every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `quant` is null for a
-// 16-bit cache; an e4m3 cache puts its own checks first, then the 16-bit launch's.  `window` 0: none; `sinks`: include/mfa_sink.h
-mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, DecodePlan *plan) {
+// 16-bit cache; an e4m3 cache puts its own checks first, then the 16-bit launch's.  `window` 0: none; `sinks`: include/mfa_sink.h;
+// `softcap` 0: none, include/mfa_softcap.h
+mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, float softcap, DecodePlan *plan) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  const mfa_status allowed = check_window_and_sinks(window, sinks, p->causal != 0);
+  mfa_status allowed = check_window_and_sinks(window, sinks, p->causal != 0);
+  if (allowed == MFA_OK) allowed = check_softcap(softcap);
   if (allowed != MFA_OK) return allowed;
   if (quant) {
     bool e4m3;
@@ -157,7 +163,8 @@ mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32
   plan->blocks = p->batches * (p->heads / G);
   plan->window = window;
   plan->sinks = sinks;
-  plan->family = sinks.any() ? 2 : window != 0;
+  plan->softcap = softcap;
+  plan->family = softcap != 0.0f ? 3 : sinks.any() ? 2 : window != 0;
   plan->tiles = planned_tiles(p->column, p->rows, window, sinks.tokens);
   plan->planned = choose_pieces(plan->blocks, plan->tiles);
   plan->pieces = plan->planned;
@@ -192,6 +199,10 @@ mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32
   a.window = window;
   a.sinkTokens = sinks.tokens;
   a.sinkLogits = sinks.logits;
+  if (softcap != 0.0f) {
+    a.capIn = 2.0f / softcap;
+    a.capOut = softcap * 1.44269504089f;
+  }
   return MFA_OK;
 }
 
@@ -222,7 +233,7 @@ hipError_t run(const DecodePlan &plan, hipStream_t stream) {
 }
 
 // the bytes of the workspace the launch would split into: 0 for an unsplit plan, whatever workspace the caller may already have bound
-mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, uint64_t *bytes) {
+mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, float softcap, uint64_t *bytes) {
   if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   *bytes = 0;
   if (!params) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
@@ -230,16 +241,16 @@ mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_q
   probe.workspace = nullptr;
   probe.workspaceBytes = 0;
   DecodePlan plan;
-  const mfa_status st = prepare(&probe, quant, window, sinks, &plan);
+  const mfa_status st = prepare(&probe, quant, window, sinks, softcap, &plan);
   if (st != MFA_OK) return st;
   if (plan.planned > 1) *bytes = pieces_workspace_bytes(plan.planned, params);
   return MFA_OK;
 }
 
 mfa_status decode_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params, const mfa_kv_quant *quant,
-                         uint32_t window, const Sinks &sinks, void *stream) {
+                         uint32_t window, const Sinks &sinks, float softcap, void *stream) {
   DecodePlan plan;
-  mfa_status st = prepare(params, quant, window, sinks, &plan);
+  mfa_status st = prepare(params, quant, window, sinks, softcap, &plan);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -248,21 +259,24 @@ mfa_status decode_launch(const void *q, const void *k, const void *v, void *o, f
   return MFA_OK;
 }
 
-mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, char *out,
-                              size_t capacity) {
+mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, float softcap,
+                              char *out, size_t capacity) {
   if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   out[0] = '\0';
   DecodePlan plan;
-  const mfa_status st = prepare(params, quant, window, sinks, &plan);
+  const mfa_status st = prepare(params, quant, window, sinks, softcap, &plan);
   if (st != MFA_OK) return st;
   char text[512];
   const uint32_t M = plan.args.G * plan.args.R;
-  // (a windowed launch names its window, its sink tokens and the tiles the piece count was chosen from; bound sink logits last)
+  // (a windowed launch names its window, its sink tokens and the tiles the piece count was chosen from; bound sink logits, then the
+  // soft cap, last)
+  char cap[48] = "";
+  if (softcap != 0.0f) std::snprintf(cap, sizeof(cap), ", softcap %g", (double)softcap);
   const std::string layout = std::string(plan.args.paged ? "paged" : "contiguous") +
                              (window ? ", window " + std::to_string(window) + (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : "") +
                                            ": planned from " + std::to_string(plan.tiles) + " tiles"
                                      : "") +
-                             (sinks.logits ? ", sink logits" : "");
+                             (sinks.logits ? ", sink logits" : "") + cap;
   if (plan.pieces > 1)
     std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x K/V heads x %u pieces, %u packed rows, %s) + %s (grid %llu)", plan.name(),
                   plan.blocks * plan.pieces, plan.blocks, plan.pieces, M, layout.c_str(), plan.set->combine.name,
@@ -275,10 +289,10 @@ mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quan
 }
 
 mfa_status decode_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params, const mfa_kv_quant *quant,
-                       uint32_t window, const Sinks &sinks, void *stream, int warmup, int iterations, float *milliseconds) {
+                       uint32_t window, const Sinks &sinks, float softcap, void *stream, int warmup, int iterations, float *milliseconds) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   DecodePlan plan;
-  mfa_status st = prepare(params, quant, window, sinks, &plan);
+  mfa_status st = prepare(params, quant, window, sinks, softcap, &plan);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -304,20 +318,20 @@ mfa_status mfa_attention_decode_piece_range(uint32_t length, uint32_t pieces, ui
   return MFA_OK;
 }
 
-mfa_status mfa_attention_decode_workspace_size(const mfa_decode_params *params, uint64_t *bytes) { return decode_workspace_size(params, nullptr, 0, Sinks(), bytes); }
+mfa_status mfa_attention_decode_workspace_size(const mfa_decode_params *params, uint64_t *bytes) { return decode_workspace_size(params, nullptr, 0, Sinks(), 0.0f, bytes); }
 
 mfa_status mfa_attention_decode_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                        void *stream) {
-  return decode_launch(q, k, v, o, l, params, nullptr, 0, Sinks(), stream);
+  return decode_launch(q, k, v, o, l, params, nullptr, 0, Sinks(), 0.0f, stream);
 }
 
 mfa_status mfa_attention_decode_launch_form(const mfa_decode_params *params, char *out, size_t capacity) {
-  return decode_launch_form(params, nullptr, 0, Sinks(), out, capacity);
+  return decode_launch_form(params, nullptr, 0, Sinks(), 0.0f, out, capacity);
 }
 
 mfa_status mfa_attention_decode_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                      void *stream, int warmup, int iterations, float *milliseconds) {
-  return decode_time(q, k, v, o, l, params, nullptr, 0, Sinks(), stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, nullptr, 0, Sinks(), 0.0f, stream, warmup, iterations, milliseconds);
 }
 
 // ---- over an e4m3 cache (include/mfa_kvcache.h): the same four with the cache's mfa_kv_quant, which is required
@@ -332,27 +346,27 @@ mfa_status mfa_attention_decode_fp8_workspace_size(const mfa_decode_params *para
   if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   *bytes = 0;
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_workspace_size(params, quant, 0, Sinks(), bytes);
+  return decode_workspace_size(params, quant, 0, Sinks(), 0.0f, bytes);
 }
 
 mfa_status mfa_attention_decode_fp8_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                            const mfa_kv_quant *quant, void *stream) {
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_launch(q, k, v, o, l, params, quant, 0, Sinks(), stream);
+  return decode_launch(q, k, v, o, l, params, quant, 0, Sinks(), 0.0f, stream);
 }
 
 mfa_status mfa_attention_decode_fp8_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, char *out, size_t capacity) {
   if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   out[0] = '\0';
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_launch_form(params, quant, 0, Sinks(), out, capacity);
+  return decode_launch_form(params, quant, 0, Sinks(), 0.0f, out, capacity);
 }
 
 mfa_status mfa_attention_decode_fp8_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                          const mfa_kv_quant *quant, void *stream, int warmup, int iterations, float *milliseconds) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_time(q, k, v, o, l, params, quant, 0, Sinks(), stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, quant, 0, Sinks(), 0.0f, stream, warmup, iterations, milliseconds);
 }
 
 // ---- under a sliding window (include/mfa_window.h): the same four with `window` after `quant`, which is null for a 16-bit cache.
@@ -360,23 +374,23 @@ mfa_status mfa_attention_decode_fp8_time(const void *q, const void *k, const voi
 
 mfa_status mfa_attention_decode_window_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
                                                       uint64_t *bytes) {
-  return decode_workspace_size(params, quant, window, Sinks(), bytes);
+  return decode_workspace_size(params, quant, window, Sinks(), 0.0f, bytes);
 }
 
 mfa_status mfa_attention_decode_window_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                               const mfa_kv_quant *quant, uint32_t window, void *stream) {
-  return decode_launch(q, k, v, o, l, params, quant, window, Sinks(), stream);
+  return decode_launch(q, k, v, o, l, params, quant, window, Sinks(), 0.0f, stream);
 }
 
 mfa_status mfa_attention_decode_window_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, char *out,
                                                    size_t capacity) {
-  return decode_launch_form(params, quant, window, Sinks(), out, capacity);
+  return decode_launch_form(params, quant, window, Sinks(), 0.0f, out, capacity);
 }
 
 mfa_status mfa_attention_decode_window_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                             const mfa_kv_quant *quant, uint32_t window, void *stream, int warmup, int iterations,
                                             float *milliseconds) {
-  return decode_time(q, k, v, o, l, params, quant, window, Sinks(), stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, quant, window, Sinks(), 0.0f, stream, warmup, iterations, milliseconds);
 }
 
 mfa_status mfa_attention_decode_window_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t pieces, uint32_t piece,
@@ -413,14 +427,14 @@ mfa_status mfa_attention_decode_sink_workspace_size(const mfa_decode_params *par
   if (bytes) *bytes = 0;
   Sinks s;
   const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : decode_workspace_size(params, quant, window, s, bytes);
+  return st != MFA_OK ? st : decode_workspace_size(params, quant, window, s, 0.0f, bytes);
 }
 
 mfa_status mfa_attention_decode_sink_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                             const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks, void *stream) {
   Sinks s;
   const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : decode_launch(q, k, v, o, l, params, quant, window, s, stream);
+  return st != MFA_OK ? st : decode_launch(q, k, v, o, l, params, quant, window, s, 0.0f, stream);
 }
 
 mfa_status mfa_attention_decode_sink_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
@@ -428,7 +442,7 @@ mfa_status mfa_attention_decode_sink_launch_form(const mfa_decode_params *params
   if (out && capacity) out[0] = '\0';
   Sinks s;
   const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : decode_launch_form(params, quant, window, s, out, capacity);
+  return st != MFA_OK ? st : decode_launch_form(params, quant, window, s, 0.0f, out, capacity);
 }
 
 mfa_status mfa_attention_decode_sink_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
@@ -436,7 +450,7 @@ mfa_status mfa_attention_decode_sink_time(const void *q, const void *k, const vo
                                           int warmup, int iterations, float *milliseconds) {
   Sinks s;
   const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : decode_time(q, k, v, o, l, params, quant, window, s, stream, warmup, iterations, milliseconds);
+  return st != MFA_OK ? st : decode_time(q, k, v, o, l, params, quant, window, s, 0.0f, stream, warmup, iterations, milliseconds);
 }
 
 mfa_status mfa_attention_decode_sink_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t sinkTokens, uint32_t pieces,
@@ -447,6 +461,43 @@ mfa_status mfa_attention_decode_sink_piece_range(uint32_t length, uint32_t rows,
   if (sinkTokens && !window) return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens must be 0 when window is 0");
   decode_sink_piece_range(length, rows, window, sinkTokens, pieces, piece, begin, end);
   return MFA_OK;
+}
+
+// ---- with a soft cap (include/mfa_softcap.h): the sink entries with `softcap` after `sinks`, which may be NULL here (no sinks).
+// softcap 0 is the launch of the headers below, whichever window and sinks
+
+static mfa_status optional_sinks(const mfa_attention_sinks *block, Sinks *sinks) { return block ? sinks_of(block, sinks) : MFA_OK; }
+
+mfa_status mfa_attention_decode_softcap_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
+                                                       const mfa_attention_sinks *sinks, float softcap, uint64_t *bytes) {
+  if (bytes) *bytes = 0;
+  Sinks s;
+  const mfa_status st = optional_sinks(sinks, &s);
+  return st != MFA_OK ? st : decode_workspace_size(params, quant, window, s, softcap, bytes);
+}
+
+mfa_status mfa_attention_decode_softcap_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
+                                               const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks, float softcap,
+                                               void *stream) {
+  Sinks s;
+  const mfa_status st = optional_sinks(sinks, &s);
+  return st != MFA_OK ? st : decode_launch(q, k, v, o, l, params, quant, window, s, softcap, stream);
+}
+
+mfa_status mfa_attention_decode_softcap_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
+                                                    const mfa_attention_sinks *sinks, float softcap, char *out, size_t capacity) {
+  if (out && capacity) out[0] = '\0';
+  Sinks s;
+  const mfa_status st = optional_sinks(sinks, &s);
+  return st != MFA_OK ? st : decode_launch_form(params, quant, window, s, softcap, out, capacity);
+}
+
+mfa_status mfa_attention_decode_softcap_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
+                                             const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks, float softcap,
+                                             void *stream, int warmup, int iterations, float *milliseconds) {
+  Sinks s;
+  const mfa_status st = optional_sinks(sinks, &s);
+  return st != MFA_OK ? st : decode_time(q, k, v, o, l, params, quant, window, s, softcap, stream, warmup, iterations, milliseconds);
 }
 
 } // extern "C"

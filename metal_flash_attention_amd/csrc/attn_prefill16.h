@@ -36,6 +36,9 @@
 //     is its POSITION in the walked list [0, sinkEnd) ++ [begin, end), not t - begin.  Every masked tile tests the whole rule, so
 //     sink keys inside the window's own masked tiles (S reaches `begin`: the zones touch) are seen as well.
 //   * SINK logit: joins (m, l) at the normalisation.
+//
+// CAP: the soft cap of attn_cache_step.h on the visible scores of every tile, the unmasked ones included; the SINK body otherwise (any
+// window and sinks, none included; RAGGED or not): c1 rides on kscale, c2 goes to score_max.
 #pragma once
 #include "attn_cache_step.h"
 #include "kv_e4m3.h"
@@ -72,6 +75,7 @@ struct PrefillArgs {
   const float *sinkLogits;        // [heads], natural units; null: none
   const uint32_t *rowStarts;      // the RAGGED kernels only: [batches + 1], packed rows (include/mfa_ragged.h); behind the sinks in turn
   uint32_t totalRows, slots;      // T; the slots of the grid (`rowBlocks` stays ceil(rows / RB))
+  float capIn, capOut;            // the CAP kernels only: c1 = 2 / cap and c2 = cap log2(e) (attn_cache_step.h); last in turn
 };
 
 // The tiles of the block of rows [r0, r0 + RB) of a sequence of n keys and qn rows.  Row r sees keys c < lim(r) = n, or with `causal`
@@ -222,9 +226,10 @@ __device__ __forceinline__ void prefill_ragged_block_wave(const uint32_t *starts
 
 template <int D> constexpr int prefill16_lds_bytes() { return 2 /*buffers*/ * 2 /*K, V*/ * PF_TILE * D * 2; }
 
-template <typename T, int D, bool FP8, bool WINDOW = false, bool SINK = false, bool RAGGED = false>
+template <typename T, int D, bool FP8, bool WINDOW = false, bool SINK = false, bool RAGGED = false, bool CAP = false>
 __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   static_assert(!RAGGED || SINK, "the ragged kernels are the sink kernels plus RAGGED");
+  static_assert(!CAP || SINK, "the capped kernels are the sink kernels plus CAP");
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -265,7 +270,8 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   if constexpr (SINK) prefill_sink_tile_range(n, qn, r0, RB, a.causal, a.window, a.sinkTokens, &beginTile, &unmaskedBegin, &firstMasked, &endTile, &sinkEnd);
   else if constexpr (WINDOW) prefill_window_tile_range(n, qn, r0, RB, a.window, &beginTile, &unmaskedBegin, &firstMasked, &endTile);
   else prefill_tile_range(n, qn, r0, RB, a.causal, &firstMasked, &endTile);
-  const float kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
+  float kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
+  if constexpr (CAP) kscale *= a.capIn;   // (after the K scale: the cap is on the score the softmax would see)
   const float vscale = a.valueScale ? a.valueScale[kvh] : 1.0f;
 
   // ---- the lane's packed row
@@ -282,7 +288,7 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
     for (int s = 0; s < NKS; ++s) qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + (16 * s + 8 * hi) * 2));
   }
   // keys this row sees
-  const VisibleKeys<WINDOW, SINK> keys(n, row + (n > qn ? n - qn : 0u) + 1u, a.causal, a.window, a.sinkTokens);
+  const VisibleKeys<WINDOW, SINK, CAP> keys(n, row + (n > qn ? n - qn : 0u) + 1u, a.causal, a.window, a.sinkTokens);
 
   // ---- addresses of a 16-key group (wave-uniform; element offsets from a.k / a.v)
   const int64_t ldk = a.ldk, ldv = a.ldv, psk = a.psk, psv = a.psv;   // (values, not fields of `a`: hipcc otherwise selects between
@@ -388,7 +394,8 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
         s = F::mfma(__builtin_bit_cast(v8, kf), qf[t], s);
       }
       // ---- online softmax over the visible keys only (the K scale rides on the softmax scale)
-      rescale_row(score_max<MASK>(s, keys, cur, hi, kscale), m, l, o);
+      if constexpr (CAP) rescale_row(score_max<MASK, true>(s, keys, cur, hi, kscale, a.capOut), m, l, o);
+      else rescale_row(score_max<MASK>(s, keys, cur, hi, kscale), m, l, o);
       v8 pf[2];
       l += score_exp<T, MASK>(s, keys, cur, hi, m, pf);
       // ---- O^T += V^T P^T
@@ -447,7 +454,7 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   // SINK: the sink logit joins (m, l); `fold` rescales O with l.  A row without a visible key ends with m = s2, l = 1
   float fold = 1.0f;
   if constexpr (SINK) {
-    if (a.sinkLogits) fold = fold_sink_logit(a.sinkLogits[qhead], m, l_tot);
+    if (a.sinkLogits) fold = fold_sink_logit<CAP>(a.sinkLogits[qhead], m, l_tot);
   }
   const float inv = l_tot > 0.f ? vscale * fold / l_tot : 0.f;   // a row without a visible key: O = 0
   const int64_t at = (RAGGED ? (int64_t)packed * a.ldo : (int64_t)batch * a.bso) + (int64_t)qhead * a.hso + (int64_t)rowt * a.ldo;
@@ -463,16 +470,16 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
 
 } // namespace mfa
 
-// One list of the kernel families, (infix, WINDOW, SINK, RAGGED): the kernels, the table that selects them (attn_prefill16.hip) and the
+// One list of the kernel families, (infix, WINDOW, SINK, RAGGED, CAP): the kernels, the table that selects them (attn_prefill16.hip) and the
 // names are generated from it.  MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, ...) is a set's code objects, in the translation unit that
 // holds them; (MFA_PREFILL_DECLARE, ...) names the kernels of another unit for the table.  D = 256 runs one workgroup per compute unit.
 #define MFA_PREFILL_FAMILIES(X, K, TN, T, D)                                                                                          \
-  X(K, , false, false, false, TN, T, D) X(K, w, true, false, false, TN, T, D) X(K, s, true, true, false, TN, T, D)                    \
-  X(K, r, true, true, true, TN, T, D)
+  X(K, , false, false, false, false, TN, T, D) X(K, w, true, false, false, false, TN, T, D) X(K, s, true, true, false, false, TN, T, D) \
+  X(K, r, true, true, true, false, TN, T, D) X(K, c, true, true, false, true, TN, T, D) X(K, rc, true, true, true, true, TN, T, D)
 #define MFA_PREFILL_DEFINE(NAME, D, ...)                                                                                              \
   extern "C" __global__ __launch_bounds__(256, D == 256 ? 1 : 2) void NAME(const mfa::PrefillArgs a) { mfa::prefill16_body<__VA_ARGS__>(a); }
 #define MFA_PREFILL_DECLARE(NAME, D, ...) extern "C" __global__ void NAME(const mfa::PrefillArgs a);
-#define MFA_PREFILL_FAMILY(K, I, WINDOW, SINK, RAGGED, TN, T, D)                                                                      \
-  K(attn_prefill16##I##_d##D##_##TN, D, T, D, false, WINDOW, SINK, RAGGED)                                                            \
-  K(attn_prefill16##I##_d##D##_##TN##_e4m3, D, T, D, true, WINDOW, SINK, RAGGED)
+#define MFA_PREFILL_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TN, T, D)                                                                 \
+  K(attn_prefill16##I##_d##D##_##TN, D, T, D, false, WINDOW, SINK, RAGGED, CAP)                                                       \
+  K(attn_prefill16##I##_d##D##_##TN##_e4m3, D, T, D, true, WINDOW, SINK, RAGGED, CAP)
 #define MFA_PREFILL_KERNELS(K, TN, T, D) MFA_PREFILL_FAMILIES(MFA_PREFILL_FAMILY, K, TN, T, D)

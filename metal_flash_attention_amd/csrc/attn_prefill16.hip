@@ -1,6 +1,7 @@
 // attn_prefill16.hip -- prefill attention over a KV cache: the kernels' code objects, the C ABI of include/mfa_prefill.h and the prefill
 // entries of include/mfa_window.h (a sliding window: the same checks and grid, the attn_prefill16w_* kernels) and of include/mfa_sink.h
-// (attention sinks: the attn_prefill16s_* kernels), and the prefill entries of include/mfa_ragged.h (packed rows: attn_prefill16r_*).
+// (attention sinks: the attn_prefill16s_* kernels), the prefill entries of include/mfa_ragged.h (packed rows: attn_prefill16r_*) and
+// those of include/mfa_softcap.h (a soft cap on the scores: attn_prefill16c_*, over packed rows attn_prefill16rc_*).
 // The refusals of a window and of sinks, and the Sinks of a launch, are cache_launch.h's, shared with attn_decode16.hip.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 #include "../../include/mfa_prefill.h"
 #include "../../include/mfa_ragged.h"
 #include "../../include/mfa_sink.h"
+#include "../../include/mfa_softcap.h"
 #include "../../include/mfa_window.h"
 #include "attn_prefill16.h"
 #include "cache_launch.h"
@@ -24,7 +26,7 @@ using namespace mfa;
 
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_prefill16_d<D>_<type>[_e4m3], and attn_prefill16w_*
 // under a sliding window, attn_prefill16s_* with attention sinks, attn_prefill16r_* over packed rows (the sink body: one ragged kernel
-// serves plain, window and sink launches)
+// serves plain, window and sink launches), attn_prefill16c_* / attn_prefill16rc_* with a soft cap (the sink body and the ragged one)
 // (the macros that generate them from one list of families: attn_prefill16.h).  D = 256 lives in attn_prefill16_d256.hip.
 MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, bf16, __bf16, 64)
 MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, bf16, __bf16, 128)
@@ -43,10 +45,10 @@ struct PrefillSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  PrefillKernel kernel[4][2];   // [0: plain, 1: window, 2: sinks, 3: ragged][e4m3]
+  PrefillKernel kernel[6][2];   // [0: plain, 1: window, 2: sinks, 3: ragged, 4: soft cap, 5: ragged with a soft cap][e4m3]
 };
 #define MFA_PREFILL_ENTRY(NAME) {NAME, #NAME}
-#define MFA_PREFILL_SET_FAMILY(K, I, WINDOW, SINK, RAGGED, TN, T, D)                                                                  \
+#define MFA_PREFILL_SET_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TN, T, D)                                                             \
   {MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN), MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN##_e4m3)},
 #define MFA_PREFILL_SET(TN, PREC, D) {D, PREC, (uint32_t)prefill16_lds_bytes<D>(), {MFA_PREFILL_FAMILIES(MFA_PREFILL_SET_FAMILY, , TN, , D)}}
 const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(bf16, MFA_BF16, 256),
@@ -63,15 +65,17 @@ struct PrefillPlan {
   const PrefillSet *set;
   bool fp8;
   uint32_t window;   // 0: none
-  int family;        // 0: plain, 1: window, 2: sinks, 3: ragged -- the kernels' first index
+  float softcap;     // 0: none
+  int family;        // 0: plain, 1: window, 2: sinks, 3: ragged, 4 / 5: padded / ragged with a soft cap -- the kernels' first index
   uint32_t blocks;   // batches x K/V heads x row blocks; ragged: slots x K/V heads
   const PrefillKernel &kernel() const { return set->kernel[family][fp8]; }
   const char *name() const { return kernel().name; }
 };
 
 // every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `window` 0: none;
-// `sinks`: include/mfa_sink.h; `ragged` non-null: packed rows, include/mfa_ragged.h
-mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &sinks, PrefillPlan *plan, const mfa_ragged_rows *ragged = nullptr) {
+// `sinks`: include/mfa_sink.h; `ragged` non-null: packed rows, include/mfa_ragged.h; `softcap` 0: none, include/mfa_softcap.h
+mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &sinks, PrefillPlan *plan, const mfa_ragged_rows *ragged = nullptr,
+                   float softcap = 0.0f) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   if (ragged) {
     if (!ragged->rowStarts)
@@ -84,7 +88,8 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &si
     if (p->lBatchStride != 0)
       return fail(MFA_ERR_INVALID_ARGUMENT, "lBatchStride must be 0 for a ragged launch: the packed L [heads][totalRows] has no batch axis");
   }
-  const mfa_status allowed = check_window_and_sinks(window, sinks, p->causal != 0);
+  mfa_status allowed = check_window_and_sinks(window, sinks, p->causal != 0);
+  if (allowed == MFA_OK) allowed = check_softcap(softcap);
   if (allowed != MFA_OK) return allowed;
   if (p->precision == MFA_FP32)
     return fail(MFA_ERR_UNSUPPORTED, "prefill attention takes a 16-bit Q (precision MFA_BF16 or MFA_FP16); FP32 Q has no kernel");
@@ -140,7 +145,8 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &si
   plan->set = set;
   plan->fp8 = fp8;
   plan->window = window;
-  plan->family = ragged ? 3 : sinks.any() ? 2 : window != 0;
+  plan->softcap = softcap;
+  plan->family = softcap != 0.0f ? (ragged ? 5 : 4) : ragged ? 3 : sinks.any() ? 2 : window != 0;
   plan->blocks = (uint32_t)blocks;
   PrefillArgs &a = plan->args;
   std::memset(&a, 0, sizeof(a));
@@ -167,6 +173,10 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &si
     a.rowStarts = ragged->rowStarts;
     a.totalRows = ragged->totalRows;
     a.slots = (uint32_t)slots;
+  }
+  if (softcap != 0.0f) {
+    a.capIn = 2.0f / softcap;
+    a.capOut = softcap * 1.44269504089f;
   }
   return MFA_OK;
 }
@@ -227,9 +237,10 @@ mfa_status mfa_attention_prefill_tile_range(uint32_t length, uint32_t queryLengt
 }
 
 static mfa_status prefill_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
-                                 uint32_t window, const Sinks &sinks, void *stream, const mfa_ragged_rows *ragged = nullptr) {
+                                 uint32_t window, const Sinks &sinks, void *stream, const mfa_ragged_rows *ragged = nullptr,
+                                 float softcap = 0.0f) {
   PrefillPlan plan;
-  mfa_status st = prepare(params, window, sinks, &plan, ragged);
+  mfa_status st = prepare(params, window, sinks, &plan, ragged, softcap);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -239,17 +250,19 @@ static mfa_status prefill_launch(const void *q, const void *k, const void *v, vo
 }
 
 static mfa_status prefill_launch_form(const mfa_prefill_params *params, uint32_t window, const Sinks &sinks, char *out, size_t capacity,
-                                      const mfa_ragged_rows *ragged = nullptr) {
+                                      const mfa_ragged_rows *ragged = nullptr, float softcap = 0.0f) {
   if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   out[0] = '\0';
   PrefillPlan plan;
-  const mfa_status st = prepare(params, window, sinks, &plan, ragged);
+  const mfa_status st = prepare(params, window, sinks, &plan, ragged, softcap);
   if (st != MFA_OK) return st;
   const PrefillArgs &a = plan.args;
   char text[512];
-  // (a windowed launch names its window, then its sink tokens; bound sink logits last)
+  // (a windowed launch names its window, then its sink tokens; bound sink logits, then the soft cap, last)
+  char cap[48] = "";
+  if (softcap != 0.0f) std::snprintf(cap, sizeof(cap), ", softcap %g", (double)softcap);
   const std::string tail = (window ? ", window " + std::to_string(window) : std::string()) +
-                           (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : std::string()) + (sinks.logits ? ", sink logits" : "");
+                           (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : std::string()) + (sinks.logits ? ", sink logits" : "") + cap;
   if (ragged)
     std::snprintf(text, sizeof(text), "%s (grid %u = %u slots x %u K/V heads, row blocks of %u rows x %u heads, %u packed rows of %u sequences, at most %u rows each, %s%s)",
                   plan.name(), plan.blocks, a.slots, a.Hkv, a.RB, a.G, a.totalRows, a.batches, a.rows, a.paged ? "paged" : "contiguous", tail.c_str());
@@ -262,10 +275,10 @@ static mfa_status prefill_launch_form(const mfa_prefill_params *params, uint32_t
 
 static mfa_status prefill_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                uint32_t window, const Sinks &sinks, void *stream, int warmup, int iterations, float *milliseconds,
-                               const mfa_ragged_rows *ragged = nullptr) {
+                               const mfa_ragged_rows *ragged = nullptr, float softcap = 0.0f) {
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   PrefillPlan plan;
-  mfa_status st = prepare(params, window, sinks, &plan, ragged);
+  mfa_status st = prepare(params, window, sinks, &plan, ragged, softcap);
   if (st != MFA_OK) return st;
   st = bind(&plan, q, k, v, o, l);
   if (st != MFA_OK) return st;
@@ -409,6 +422,59 @@ mfa_status mfa_attention_prefill_ragged_block(const uint32_t *rowStarts, uint32_
   uint32_t start, count;
   prefill_ragged_block(rowStarts, batches, totalRows, rows, blockRows, slot, sequence, firstRow, &start, &count);
   return MFA_OK;
+}
+
+// ---- with a soft cap (include/mfa_softcap.h): the sink entries with `softcap` after `sinks`, the ragged entries with it after
+// `ragged`; a NULL `sinks` is no sinks.  softcap 0 is the launch of the headers below, whichever window, sinks and rows
+
+static mfa_status optional_sinks(const mfa_attention_sinks *block, Sinks *sinks) { return block ? sinks_of(block, sinks) : MFA_OK; }
+
+mfa_status mfa_attention_prefill_softcap_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                                uint32_t window, const mfa_attention_sinks *sinks, float softcap, void *stream) {
+  Sinks s;
+  const mfa_status st = optional_sinks(sinks, &s);
+  return st != MFA_OK ? st : prefill_launch(q, k, v, o, l, params, window, s, stream, nullptr, softcap);
+}
+
+mfa_status mfa_attention_prefill_softcap_launch_form(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
+                                                     float softcap, char *out, size_t capacity) {
+  if (out && capacity) out[0] = '\0';
+  Sinks s;
+  const mfa_status st = optional_sinks(sinks, &s);
+  return st != MFA_OK ? st : prefill_launch_form(params, window, s, out, capacity, nullptr, softcap);
+}
+
+mfa_status mfa_attention_prefill_softcap_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                              uint32_t window, const mfa_attention_sinks *sinks, float softcap, void *stream, int warmup,
+                                              int iterations, float *milliseconds) {
+  Sinks s;
+  const mfa_status st = optional_sinks(sinks, &s);
+  return st != MFA_OK ? st : prefill_time(q, k, v, o, l, params, window, s, stream, warmup, iterations, milliseconds, nullptr, softcap);
+}
+
+mfa_status mfa_attention_prefill_ragged_softcap_launch(const void *q, const void *k, const void *v, void *o, float *l,
+                                                       const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
+                                                       const mfa_ragged_rows *ragged, float softcap, void *stream) {
+  Sinks s;
+  const mfa_status st = ragged_of(ragged, sinks, &s);
+  return st != MFA_OK ? st : prefill_launch(q, k, v, o, l, params, window, s, stream, ragged, softcap);
+}
+
+mfa_status mfa_attention_prefill_ragged_softcap_launch_form(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
+                                                            const mfa_ragged_rows *ragged, float softcap, char *out, size_t capacity) {
+  if (out && capacity) out[0] = '\0';
+  Sinks s;
+  const mfa_status st = ragged_of(ragged, sinks, &s);
+  return st != MFA_OK ? st : prefill_launch_form(params, window, s, out, capacity, ragged, softcap);
+}
+
+mfa_status mfa_attention_prefill_ragged_softcap_time(const void *q, const void *k, const void *v, void *o, float *l,
+                                                     const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
+                                                     const mfa_ragged_rows *ragged, float softcap, void *stream, int warmup, int iterations,
+                                                     float *milliseconds) {
+  Sinks s;
+  const mfa_status st = ragged_of(ragged, sinks, &s);
+  return st != MFA_OK ? st : prefill_time(q, k, v, o, l, params, window, s, stream, warmup, iterations, milliseconds, ragged, softcap);
 }
 
 } // extern "C"

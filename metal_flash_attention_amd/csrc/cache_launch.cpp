@@ -2,6 +2,7 @@
 #include "cache_launch.h"
 
 #include <cstring>
+#include <cmath>
 #include <string>
 
 #include "../../include/mfa_kvcache.h"
@@ -88,6 +89,13 @@ mfa_status check_window_and_sinks(uint32_t window, const Sinks &sinks, bool caus
   if (window && !causal)
     return fail(MFA_ERR_INVALID_ARGUMENT, "a sliding window needs causal: the window is the " + std::to_string(window) +
                                               " keys that end at a row's causal frontier (window 0: no window)");
+  return MFA_OK;
+}
+
+mfa_status check_softcap(float softcap) {
+  if (!(softcap >= 0.0f) || std::isinf(softcap))   // (a NaN fails the comparison)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "softcap must be 0 (no cap) or a finite positive number, the cap of cap x tanh(score / cap) in "
+                                          "natural-log units (a checkpoint's attn_logit_softcapping), not " + std::to_string(softcap));
   return MFA_OK;
 }
 

@@ -1,6 +1,6 @@
 // cache_launch.h -- what the host sides of the launches over a KV cache share (attn_decode16.hip, attn_prefill16.hip,
 // kv_cache_append.hip): the checks of paging, operand strides, cache precision and buffer pointers, and of a sliding window and
-// attention sinks (Sinks, sinks_of, check_window_and_sinks: decode and prefill), each with ONE wording, so that the same mistake is
+// attention sinks (Sinks, sinks_of, check_window_and_sinks: decode and prefill) and of a soft cap (check_softcap), each with ONE wording, so that the same mistake is
 // refused in the same words whichever launch meets it.  hip_fail, copy_text and time_launches also serve mfa_kernel.hip.  Internal, not part of the ABI.  Every check records its message (fail, mfa_internal.h) and returns the status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,6 +48,8 @@ struct Sinks {
 mfa_status sinks_of(const mfa_attention_sinks *block, Sinks *sinks);
 // sink tokens need a window and causal; a window (0: none) needs causal
 mfa_status check_window_and_sinks(uint32_t window, const Sinks &sinks, bool causal);
+// the soft cap of a launch (include/mfa_softcap.h): 0 is none, anything but a finite positive number is refused
+mfa_status check_softcap(float softcap);
 
 // Times `iterations` calls of run(stream) between two events, after `warmup` untimed ones; nothing more is started after a call that
 // failed.  `name` is the kernel a HIP failure is reported under.

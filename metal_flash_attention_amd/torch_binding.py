@@ -24,6 +24,7 @@ library or a CPU tensor raises).
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -414,13 +415,15 @@ def _packed_operand(t):
     return t, (int(t.stride(0)) if T > 1 else heads * D, int(t.stride(1)) if heads > 1 else D, 0)
 
 
-def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, workspace=False):
+def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, workspace=False, softcap=None):
     """the launch of a decode or prefill host object over `kw`, on q's device and torch's current stream -> (O, L).  (Rows the launch does
     not own -- past q_lengths[b], or packed rows of no sequence -- are not written: no memset is spent on them, they come back uninitialised)"""
     if window is not None:
         kw.update(window=int(window))
     if sinks is not None:   # (sink tokens or 0, sink logits or None): the entries of include/mfa_sink.h
         kw.update(sinkTokens=int(sinks[0]), sinkLogits=sinks[1])
+    if softcap is not None:   # the entries of include/mfa_softcap.h
+        kw.update(softcap=float(softcap))
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     l = torch.empty(l_shape, dtype=torch.float32, device=q.device)
     if workspace:
@@ -431,29 +434,35 @@ def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, workspace=Fal
     return o, l
 
 
-def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None, sinks=None):
+def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None, sinks=None,
+                softcap=None):
     fp8, B, kw = _cache_side("flash_decode", (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, fp8=bool(fp8))
     q, kw["strides"]["Q"] = _new_operand(q)
     _B, H, R, D = q.shape
     kw.update(rows=R, heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal))
-    return _attend(_host(AttentionDecode, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, workspace=True)
+    return _attend(_host(AttentionDecode, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, workspace=True, softcap=softcap)
 
 
 def _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale):
     return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, True, k_scale, v_scale)
 
 
-def _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sinks=None):
-    """over whichever cache the tensors say: the window and sink ops serve 16-bit and e4m3 caches alike"""
+def _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sinks=None, softcap=None):
+    """over whichever cache the tensors say: the window, sink and soft-cap ops serve 16-bit and e4m3 caches alike"""
     fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
-    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8, k_scale, v_scale, window, sinks)
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8, k_scale, v_scale, window, sinks, softcap)
 
 
 def _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits):
     return _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window or None, (sink_tokens, sink_logits))
 
 
-def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None, sinks=None):
+def _no_sinks(sinks):
+    """the ops' 0 and None are no sinks, as 0 is no window"""
+    return sinks if sinks is not None and (sinks[0] or sinks[1] is not None) else None
+
+
+def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None, sinks=None, softcap=None):
     who = "flash_prefill"
     fp8, B, kw = _cache_side(who, (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
     if q_lengths is not None:
@@ -462,10 +471,11 @@ def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, cau
     _B, H, R, D = q.shape
     kw.update(rows=R, heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal),
               queryLengths=None if q_lengths is None else q_lengths.to(torch.int32))
-    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks)
+    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, softcap=softcap)
 
 
-def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window, sinks):
+def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window, sinks,
+                        softcap=None):
     who = "flash_prefill_ragged"
     fp8, B, kw = _cache_side(who, (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, packed=True)
     _check_row_starts(who, row_starts, cache_lengths, max_rows)
@@ -473,8 +483,7 @@ def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows
     T, H, D = q.shape
     kw.update(rows=int(max_rows), heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal),
               rowStarts=row_starts.to(torch.int32), totalRows=T)
-    sinks = sinks if sinks is not None and (sinks[0] or sinks[1] is not None) else None   # (the op's 0 and None: no sinks, as 0 is no window)
-    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (H, T), kw, window or None, sinks)
+    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (H, T), kw, window or None, _no_sinks(sinks), softcap=softcap)
 
 
 def _append(who, operand, k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, row_starts=None, max_rows=None):
@@ -504,6 +513,12 @@ def _check_window(who, window, causal):
         raise ValueError(f"{who}: window must be an int from 1 to 2^32 - 1 (None: no window), not {window!r}")
     if not causal:
         raise ValueError(f"{who}: a sliding window needs causal=True (the window lies behind the row's causal frontier)")
+
+
+def _check_softcap(who, softcap):
+    if isinstance(softcap, bool) or not isinstance(softcap, (int, float)) or not math.isfinite(softcap) or not softcap > 0:
+        raise ValueError(f"{who}: softcap must be a finite number > 0, the cap of cap * tanh(score / cap) in natural-log units (None: no "
+                         f"cap), not {softcap!r}")
 
 
 def _check_sinks(who, q, window, causal, sink_tokens, sink_logits):
@@ -560,6 +575,13 @@ def _op_decode_sink(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
     return _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits)
 
 
+def _op_decode_softcap(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                       block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor],
+                       window: int, sink_tokens: int, sink_logits: Optional[torch.Tensor], softcap: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window or None,
+                              _no_sinks((sink_tokens, sink_logits)), softcap)
+
+
 def _op_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                 q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
                 k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -586,6 +608,22 @@ def _op_prefill_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
                        sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     return _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window,
                                (sink_tokens, sink_logits))
+
+
+def _op_prefill_softcap(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                        q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
+                        k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
+                        sink_logits: Optional[torch.Tensor], softcap: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window or None,
+                        _no_sinks((sink_tokens, sink_logits)), softcap)
+
+
+def _op_prefill_ragged_softcap(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                               row_starts: torch.Tensor, max_rows: int, block_table: Optional[torch.Tensor], causal: bool,
+                               k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
+                               sink_logits: Optional[torch.Tensor], softcap: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window,
+                               (sink_tokens, sink_logits), softcap)
 
 
 def _op_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
@@ -645,6 +683,10 @@ _HAVE_SINK_OPS = all([_register_cache_op("attention_decode_sink", _op_decode_sin
                       _register_cache_op("attention_prefill_sink", _op_prefill_sink, _fake_padded)])
 _HAVE_RAGGED_OPS = all([_register_cache_op("attention_prefill_ragged", _op_prefill_ragged, _fake_packed),
                         _register_cache_op("kv_cache_append_ragged", _op_append_ragged, _fake_none, ("k_cache", "v_cache"))])
+# (a soft cap, whatever the window and sinks: one op per launch kind, `softcap` > 0 last)
+_HAVE_SOFTCAP_OPS = all([_register_cache_op("attention_decode_softcap", _op_decode_softcap, _fake_padded),
+                         _register_cache_op("attention_prefill_softcap", _op_prefill_softcap, _fake_padded),
+                         _register_cache_op("attention_prefill_ragged_softcap", _op_prefill_ragged_softcap, _fake_packed)])
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -681,7 +723,7 @@ def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Ten
 def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                  block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False,
                  k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, window: Optional[int] = None,
-                 sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None):
+                 sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None, softcap: Optional[float] = None):
     """Attention of the R new rows of every sequence (q [B, H, R, D]; R = 1, or a few speculative tokens; G R <= 32 with G = H / Hkv)
     against its KV cache.  cache_lengths [B] (GPU, int32): valid keys per sequence INCLUDING the R new tokens, which the caller has
     already written into the cache; with `causal` row r sees key c iff c <= r + max(len - R, 0).  Caches: [B, Hkv, C, D], or any view
@@ -699,10 +741,20 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     sink_tokens=S (an int >= 1; needs window): the keys [0, S) stay visible under the window, and the keys, pages and block-table
     entries between their tiles and the window's are never read.  sink_logits [H] fp32 on the GPU (any window, causal or not): one
     learned logit per query head joins the softmax denominator and no value row -- natural-log units, not scaled by 1 / sqrt(D) or
-    k_scale; L includes it (include/mfa_sink.h).  Either goes through the op `mfa::attention_decode_sink`."""
+    k_scale; L includes it (include/mfa_sink.h).  Either goes through the op `mfa::attention_decode_sink`.
+    softcap=cap (a finite number > 0, natural-log units: a checkpoint's attn_logit_softcapping, 50 in Gemma 2): the softmax sees
+    cap tanh(score / cap), the score with 1 / sqrt(D) and k_scale applied; masked keys stay masked, the sink logit is not capped, L is
+    that of the capped scores (include/mfa_softcap.h).  With any window and sinks, through the op `mfa::attention_decode_softcap`.
+    None: no cap."""
     _forward_only("flash_decode", q, k_cache, v_cache, cache_lengths)
     args = (q, k_cache, v_cache, cache_lengths, block_table, causal)
-    if sink_tokens is not None or sink_logits is not None:
+    if softcap is not None:
+        _check_softcap("flash_decode", softcap)
+        if window is not None or sink_tokens is not None or sink_logits is not None:
+            _check_sinks("flash_decode", q, window, causal, sink_tokens, sink_logits)
+        have, op = _HAVE_SOFTCAP_OPS, "attention_decode_softcap"
+        args = args + (k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits, float(softcap))
+    elif sink_tokens is not None or sink_logits is not None:
         _check_sinks("flash_decode", q, window, causal, sink_tokens, sink_logits)
         have, op, args = _HAVE_SINK_OPS, "attention_decode_sink", args + (k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits)
     elif window is not None:
@@ -720,7 +772,8 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
 def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                   q_lengths: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None, causal: bool = True,
                   k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, return_lse: bool = False,
-                  window: Optional[int] = None, sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None):
+                  window: Optional[int] = None, sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None,
+                  softcap: Optional[float] = None):
     """Attention of a BLOCK of new rows of every sequence (q [B, H, R, D], any R: a chunk of a prompt, a reused prefix's tail, a long
     speculative block) against its KV cache, which already holds the new tokens (kv_cache_append first).  cache_lengths [B] (GPU):
     valid keys per sequence INCLUDING the new tokens; q_lengths [B] (GPU, None = R for every sequence): the new rows of sequence b,
@@ -733,10 +786,16 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     where torch has custom ops, so it traces under torch.compile.  window=W (an int >= 1; needs causal): sliding-window attention as
     flash_decode's, through the op `mfa::attention_prefill_window`; None: no window.  sink_tokens / sink_logits: attention sinks as
     flash_decode's (include/mfa_sink.h), through the op `mfa::attention_prefill_sink`; a live row without a visible key then gets
-    L = the head's sink logit."""
+    L = the head's sink logit.  softcap=cap: logit soft-capping as flash_decode's (include/mfa_softcap.h), with any window and sinks,
+    through the op `mfa::attention_prefill_softcap`; None: no cap."""
     _forward_only("flash_prefill", q, k_cache, v_cache, cache_lengths)
     args = (q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
-    if sink_tokens is not None or sink_logits is not None:
+    if softcap is not None:
+        _check_softcap("flash_prefill", softcap)
+        if window is not None or sink_tokens is not None or sink_logits is not None:
+            _check_sinks("flash_prefill", q, window, causal, sink_tokens, sink_logits)
+        have, op, args = _HAVE_SOFTCAP_OPS, "attention_prefill_softcap", args + (window or 0, sink_tokens or 0, sink_logits, float(softcap))
+    elif sink_tokens is not None or sink_logits is not None:
         _check_sinks("flash_prefill", q, window, causal, sink_tokens, sink_logits)
         have, op, args = _HAVE_SINK_OPS, "attention_prefill_sink", args + (window or 0, sink_tokens or 0, sink_logits)
     elif window is not None:
@@ -751,7 +810,8 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
 def flash_prefill_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor, row_starts: torch.Tensor,
                          max_rows: int, block_table: Optional[torch.Tensor] = None, causal: bool = True,
                          k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, return_lse: bool = False,
-                         window: Optional[int] = None, sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None):
+                         window: Optional[int] = None, sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None,
+                         softcap: Optional[float] = None):
     """flash_prefill for a RAGGED batch (a continuous-batching step: sequences with one new token beside prompt chunks): q [T, H, D]
     holds the new rows of all B sequences packed along the first axis, row_starts [B + 1] (GPU, int32 / int64, non-decreasing: the
     engine's cu_seqlens_q / query_start_loc) says where each sequence's rows begin, and max_rows (a host int) is the largest row
@@ -760,13 +820,19 @@ def flash_prefill_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.
     sink_tokens and sink_logits: flash_prefill's.  Returns O [T, H, D], and with return_lse also L [H, T] fp32 in natural units; packed
     rows that no sequence owns come back uninitialised.  The launch starts no workgroup for row blocks that do not exist and computes,
     byte for byte, what flash_prefill computes for the same sequences padded to max_rows.  Forward only; goes through the op
-    `mfa::attention_prefill_ragged` where torch has custom ops, so it traces under torch.compile."""
+    `mfa::attention_prefill_ragged` where torch has custom ops, so it traces under torch.compile.  softcap=cap: logit soft-capping as
+    flash_decode's, through the op `mfa::attention_prefill_ragged_softcap`; None: no cap."""
     _forward_only("flash_prefill_ragged", q, k_cache, v_cache, cache_lengths)
+    if softcap is not None:
+        _check_softcap("flash_prefill_ragged", softcap)
     if window is not None or sink_tokens is not None or sink_logits is not None:
         # (_check_sinks reads the heads off a [B, H, R, D] query: the packed q as such a view)
         _check_sinks("flash_prefill_ragged", q.unsqueeze(0).transpose(1, 2) if q.dim() == 3 else q, window, causal, sink_tokens, sink_logits)
-    o, l = _call_op(_HAVE_RAGGED_OPS, "attention_prefill_ragged", q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal,
-                    k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits)
+    args = (q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits)
+    if softcap is not None:
+        o, l = _call_op(_HAVE_SOFTCAP_OPS, "attention_prefill_ragged_softcap", *args, float(softcap))
+    else:
+        o, l = _call_op(_HAVE_RAGGED_OPS, "attention_prefill_ragged", *args)
     return (o, l * _LN2) if return_lse else o
 
 
