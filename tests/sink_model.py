@@ -144,61 +144,25 @@ def compare(got_o, got_l, ref, fmt, out, lens, qlens, *, margin=MARGIN, info=Non
 
 
 # ------------------------------------------------------------------------------------------------- the rounding-emulated reference
-def _fold(part, s2):
-    """the sink logit (base-2 units, [rows]) joins a state (m, l, o): what piece 0 publishes, and what the final normalisation does"""
-    m, l, o = part
-    mn = np.maximum(m, s2)
-    c = np.where(np.isfinite(m), np.exp2(np.where(np.isfinite(m), m, 0.0) - mn), 0.0)
-    return mn, l * c + np.exp2(s2 - mn), o * c[:, None]
-
-
 def emulated(q, k, v, lens, qlens, G, W, S, logits, fmt, *, causal=True, pieces=None, kscale=None, vscale=None, piece_range=None,
-             tile_range=None):
-    """-> (O before the store's rounding [B, Hq, R, D], L natural): the kernels' roundings and order of sums (see the module's text)"""
-    q, k, v = dm.f64(q), dm.f64(k), dm.f64(v)
-    B, Hq, R, D = q.shape
-    Hkv = Hq // G
-    kind = "decode" if qlens is None else "prefill"
-    ks = np.ones(Hkv) if kscale is None else np.asarray(kscale, dtype=np.float64)
-    vs = np.ones(Hkv) if vscale is None else np.asarray(vscale, dtype=np.float64)
-    tr = tile_range or library_tile_range
-    O = np.zeros((B, Hq, R, D))
-    L = np.full((B, Hq, R), -np.inf)
-    for b in range(B):
-        n, qn = int(lens[b]), R if qlens is None else min(int(qlens[b]), R)
-        if qn == 0:
-            continue
-        npad = (-(-max(n, 1) // TILE)) * TILE
+             tile_range=None, score=None):
+    """-> (O before the store's rounding [B, Hq, R, D], L natural): window_model.emulated_walk over the sink tiles, then the window's
+    (see the module's text).  score: another score function than the uncapped kernels' (softcap_model's)"""
+    R = q.shape[2]
+
+    def visible(n, qn, rows, npad):
+        lo, lim = frontiers(n, qn, rows, W, causal)
         cols = np.arange(npad)[None, :]
-        for r0, r1 in wm.blocks_of(kind, qn, G):
-            lo, lim = frontiers(n, qn, np.arange(r0, r1), W, causal)
-            vis = (cols < lim[:, None]) & ((cols >= lo[:, None]) | (cols < S))
-            if kind == "decode":
-                waves = []
-                for pair in piece_ranges(n, R, W, S, pieces, piece_range):
-                    steps = steps_of(pair)
-                    waves.append([steps[w::WAVES] for w in range(WAVES)])
-            else:
-                bt, _u0, _u1, et, se = tr(n, qn, r0, ROWS // G, causal, W, S)
-                waves = [[list(range(0, se * TILE, STEP)) + list(range(bt * TILE, et * TILE, STEP))]]
-            for h in range(Hq):
-                j = h // G
-                K, V = np.zeros((npad, D)), np.zeros((npad, D))
-                K[:n], V[:n] = k[b, j, :n], v[b, j, :n]
-                S2 = np.where(vis, (q[b, h, r0:r1] @ K.T) * (ks[j] * dm.LOG2E / math.sqrt(D)), -np.inf)
-                published = [wm._merge([wm._walk(S2, V, steps, fmt) for steps in piece]) if len(piece) > 1 else wm._walk(S2, V, piece[0], fmt)
-                             for piece in waves]
-                s2 = None if logits is None else np.full(r1 - r0, float(logits[h]) * dm.LOG2E)
-                if s2 is not None and len(published) > 1:
-                    published[0] = _fold(published[0], s2)
-                mstar, lt, ot = wm._merge(published) if len(published) > 1 else published[0]
-                if s2 is not None and len(published) == 1:
-                    mstar, lt, ot = _fold((mstar, lt, ot), s2)
-                seen = lt > 0
-                l0 = np.where(seen, lt, 1.0)
-                O[b, h, r0:r1] = np.where(seen[:, None], ot * vs[j] / l0[:, None], 0.0)
-                L[b, h, r0:r1] = np.where(seen, (np.where(seen, mstar, 0.0) + np.log2(l0)) / dm.LOG2E, -np.inf)
-    return O, L
+        return (cols < lim[:, None]) & ((cols >= lo[:, None]) | (cols < S))
+
+    def steps(n, qn, r0):
+        if qlens is None:
+            return [[steps_of(pair)[w::WAVES] for w in range(WAVES)] for pair in piece_ranges(n, R, W, S, pieces, piece_range)]
+        bt, _u0, _u1, et, se = (tile_range or library_tile_range)(n, qn, r0, ROWS // G, causal, W, S)
+        return [[list(range(0, se * TILE, STEP)) + list(range(bt * TILE, et * TILE, STEP))]]
+
+    return wm.emulated_walk(q, k, v, lens, qlens, G, fmt, visible, steps, score or wm.scaled_scores(kscale, G, q.shape[3]), logits=logits,
+                            vscale=vscale)
 
 
 # ------------------------------------------------------------------------------------------------------------------ needle inputs

@@ -159,51 +159,19 @@ def emulated(q, k, v, lens, qlens, G, W, S, logits, cap, fmt, *, causal=True, pi
     if cap is None:
         return sm.emulated(q, k, v, lens, qlens, G, W, S, logits, fmt, causal=causal, pieces=pieces, kscale=kscale, vscale=vscale,
                            piece_range=piece_range, tile_range=tile_range)
-    q, k, v = dm.f64(q), dm.f64(k), dm.f64(v)
     B, Hq, R, D = q.shape
-    Hkv = Hq // G
-    kind = "decode" if qlens is None else "prefill"
-    ks = np.ones(Hkv) if kscale is None else np.asarray(kscale, dtype=np.float64)
-    vs = np.ones(Hkv) if vscale is None else np.asarray(vscale, dtype=np.float64)
-    tr = tile_range or sm.library_tile_range
+    ks = np.ones(Hq // G) if kscale is None else np.asarray(kscale, dtype=np.float64)
     scale2 = np.float32(1.44269504089) / np.sqrt(np.float32(D))
-    O = np.zeros((B, Hq, R, D))
-    L = np.full((B, Hq, R), -np.inf)
-    for b in range(B):
-        n, qn = int(lens[b]), R if qlens is None else min(int(qlens[b]), R)
-        if qn == 0:
-            continue
-        npad = (-(-max(n, 1) // TILE)) * TILE
-        for r0, r1 in wm.blocks_of(kind, qn, G):
-            vis = _visible(n, qn, np.arange(r0, r1), W, S, causal, npad)
-            if kind == "decode":
-                waves = []
-                for pair in sm.piece_ranges(n, R, W, S, pieces, piece_range):
-                    steps = sm.steps_of(pair)
-                    waves.append([steps[w::WAVES] for w in range(WAVES)])
-            else:
-                bt, _u0, _u1, et, se = tr(n, qn, r0, ROWS // G, causal, W, S)
-                waves = [[list(range(0, se * TILE, STEP)) + list(range(bt * TILE, et * TILE, STEP))]]
-            for h in range(Hq):
-                j = h // G
-                K, V = np.zeros((npad, D)), np.zeros((npad, D))
-                K[:n], V[:n] = k[b, j, :n], v[b, j, :n]
-                S2 = np.where(vis, capped_fp32(q[b, h, r0:r1] @ K.T, scale2, ks[j], cap, naive), -np.inf)
-                bad = np.isnan(S2).any(axis=1)   # (naive only.  fmaxf drops a NaN score, its exp2 does not: P, l and O of the row are NaN)
-                S2 = np.where(np.isnan(S2), -np.inf, S2)
-                published = [wm._merge([wm._walk(S2, V, steps, fmt) for steps in piece]) if len(piece) > 1 else wm._walk(S2, V, piece[0], fmt)
-                             for piece in waves]
-                s2 = None if logits is None else np.full(r1 - r0, float(logits[h]) * dm.LOG2E)
-                if s2 is not None and len(published) > 1:
-                    published[0] = sm._fold(published[0], s2)
-                mstar, lt, ot = wm._merge(published) if len(published) > 1 else published[0]
-                if s2 is not None and len(published) == 1:
-                    mstar, lt, ot = sm._fold((mstar, lt, ot), s2)
-                seen = lt > 0
-                l0 = np.where(seen, lt, 1.0)
-                O[b, h, r0:r1] = np.where(bad[:, None], np.nan, np.where(seen[:, None], ot * vs[j] / l0[:, None], 0.0))
-                L[b, h, r0:r1] = np.where(bad, np.nan, np.where(seen, (np.where(seen, mstar, 0.0) + np.log2(l0)) / dm.LOG2E, -np.inf))
-    return O, L
+    bad = np.zeros((B, Hq, R), dtype=bool)   # (naive only.  fmaxf drops a NaN score, its exp2 does not: P, l and O of the row are NaN)
+
+    def score(raw, vis, b, h, rows):
+        S2 = np.where(vis, capped_fp32(raw, scale2, ks[h // G], cap, naive), -np.inf)
+        bad[b, h, rows] = np.isnan(S2).any(axis=1)
+        return np.where(np.isnan(S2), -np.inf, S2)
+
+    O, L = sm.emulated(q, k, v, lens, qlens, G, W, S, logits, fmt, causal=causal, pieces=pieces, vscale=vscale, piece_range=piece_range,
+                       tile_range=tile_range, score=score)
+    return np.where(bad[..., None], np.nan, O), np.where(bad, np.nan, L)
 
 
 # ------------------------------------------------------------------------------------------------------------------ needle inputs

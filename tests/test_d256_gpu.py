@@ -3,8 +3,8 @@ strided, a window with and without sinks, split and unsplit), prefill (row block
 with and without sinks, ragged) and append.
 
 Every comparison with a model goes through decode_model.compare / prefill_model.compare / sink_model.compare at the committed MARGIN,
-with the test's own queries and with the needle queries of those modules; the runners and caches are those of tests/test_decode_gpu.py,
-tests/test_kvcache_gpu.py and tests/test_prefill_gpu.py: NaN (16-bit) or 0x7f (e4m3) at and past every length, in page tails and in
+with the test's own queries and with the needle queries of those modules; the runners and caches are those of tests/decode_kit.py and
+tests/cache_kit.py (the decode, the e4m3 and the prefill file's): NaN (16-bit) or 0x7f (e4m3) at and past every length, in page tails and in
 pages nobody names; canaries or sentinels around O, L and the workspace.  The shapes are the smallest that reach every path of the
 D = 256 kernels: 129 keys give wave 0 a second step and every wave a first, 33 a partial second step, 0 the empty sequence; (700, 513,
 65) against column 1024 plan four pieces; a prefill of (5, 70) rows over (150, 70) keys is one row block at G = 1 and several, the last
@@ -17,14 +17,12 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import cache_kit as ck  # noqa: E402  (prefill_launch, prefill_hold, prefill_pool: prefill's runners; the ragged append)
+import decode_kit as dk  # noqa: E402  (Cache, run, check_against_model: the 16-bit launch's runner and its bounds; Cache8, run8, check: the e4m3 launch's)
 import decode_model as dm  # noqa: E402
 import prefill_model as pm  # noqa: E402
 import ragged_model as rm  # noqa: E402
 import sink_model as sm  # noqa: E402
-import test_decode_gpu as t16  # noqa: E402  (Cache, run, check_against_model, both_inputs: the 16-bit launch's runner and its bounds)
-import test_kvcache_gpu as t8  # noqa: E402  (Cache8, run8, check: the e4m3 launch's)
-import test_prefill_gpu as tp  # noqa: E402  (launch, hold, paged_pool: prefill's)
-import test_ragged_gpu as trg  # noqa: E402
 from metal_flash_attention_amd import (AttentionDecode, AttentionDecodeFP8, AttentionPrefill, GEMMOperandPrecision as P, KVCacheAppend,  # noqa: E402
                                        KVCachePrecision)
 
@@ -34,6 +32,7 @@ DTYPE = {P.FP16: torch.float16, P.BF16: torch.bfloat16}
 SHORT, C_SHORT = np.array([129, 33, 0], dtype=np.uint32), 192        # unsplit: three tiles plan one piece
 LONG, C_LONG = np.array([700, 513, 65], dtype=np.uint32), 1024       # sixteen tiles over at most 24 workgroups: four pieces
 GROUPS = [(8, 1, 1), (8, 1, 4), (8, 4, 1), (8, 4, 4), (8, 8, 1), (8, 8, 4), (6, 3, 1)]   # (Hq, G, R): G R = 32, and G R odd
+SEEN = {}
 W, S = 130, 4                                                        # the window and sink tokens of tests/test_sink_gpu.py
 
 
@@ -42,6 +41,8 @@ def _gpu():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     yield
+    if SEEN:
+        print("\nD = 256 prefill worst err / bound at margin 1:", {k: round(v, 4) for k, v in SEEN.items()})
 
 
 def launches():
@@ -55,16 +56,16 @@ def launches():
 def test_decode_parity_with_the_float64_model(prec, Hq, G, R):
     tn = "bf16" if prec == P.BF16 else "f16"
     for index, (lens, C, workspace, kernel) in enumerate(launches()):
-        q, k, v = t16.make_values(3, Hq, G, R, C, D, DTYPE[prec], seed=256 + 8 * Hq + G + R)
-        cache = t16.Cache(k, v, lens, "packed")
+        q, k, v = dk.make_values(3, Hq, G, R, C, D, DTYPE[prec], seed=256 + 8 * Hq + G + R)
+        cache = dk.Cache(k, v, lens, "packed")
         for causal in (True, False):
             out32 = bool((index + causal + R) & 1)
-            for name, qq, info in t16.both_inputs(q, k, lens, G, causal, cache, C, workspace):
-                o, l, _bits, text = t16.run(qq, cache, G, C, causal=causal, workspace=workspace, out32=out32)
+            for name, qq, info in dk.both_inputs(q, k, lens, G, causal, cache, C, workspace):
+                o, l, _bits, text = dk.run(qq, cache, G, C, causal=causal, workspace=workspace, out32=out32)
                 assert text.startswith("attn_decode16_d256_%s%s (" % (tn, kernel)), text
                 assert ("x 4 pieces" in text and "attn_decode16_d256_%s_combine" % tn in text) == (kernel == "_pieces"), text
-                t16.check_against_model(f"D=256 {prec.name} Hq={Hq} G={G} R={R} causal={causal} {kernel[1:]} lens={lens.tolist()}{name}", o, l,
-                                        qq, k, v, lens, G, causal, out32=out32, pieces=t16.pieces_of(text), info=info)
+                dk.check_against_model(f"D=256 {prec.name} Hq={Hq} G={G} R={R} causal={causal} {kernel[1:]} lens={lens.tolist()}{name}", o, l,
+                                        qq, k, v, lens, G, causal, out32=out32, pieces=dk.pieces_of(text), info=info)
 
 
 @pytest.mark.parametrize("Hq,G,R", [(8, 1, 4), (8, 4, 1), (8, 8, 4)])
@@ -72,14 +73,14 @@ def test_decode_parity_with_the_float64_model(prec, Hq, G, R):
 def test_decode_over_an_e4m3_cache_with_per_head_scales(prec, Hq, G, R):
     tn = "bf16" if prec == P.BF16 else "f16"
     for index, (lens, C, workspace, kernel) in enumerate(launches()):
-        q, kb, vb, ks, vs = t8.make_case(3, Hq, G, R, C, D, DTYPE[prec], seed=512 + G + R)
-        cache = t8.Cache8(kb, vb, lens, "packed")
+        q, kb, vb, ks, vs = dk.make_case(3, Hq, G, R, C, D, DTYPE[prec], seed=512 + G + R)
+        cache = dk.Cache8(kb, vb, lens, "packed")
         out32 = bool((index + R) & 1)
-        for name, qq, info in t8.both_inputs(q, kb, ks, lens, G, True, cache, C, workspace):
-            o, l, _bits, text = t8.run8(qq, cache, G, C, ks, vs, workspace=workspace, out32=out32)
+        for name, qq, info in dk.both_inputs8(q, kb, ks, lens, G, True, cache, C, workspace):
+            o, l, _bits, text = dk.run8(qq, cache, G, C, ks, vs, workspace=workspace, out32=out32)
             assert text.startswith("attn_decode8_d256_%s%s (" % (tn, kernel)), text
-            t8.check(f"D=256 e4m3 {prec.name} G={G} R={R} {kernel[1:]} lens={lens.tolist()}{name}", o, l, qq, kb, vb, ks, vs, lens, G, True,
-                     out32=out32, pieces=t16.pieces_of(text), info=info)
+            dk.check(f"D=256 e4m3 {prec.name} G={G} R={R} {kernel[1:]} lens={lens.tolist()}{name}", o, l, qq, kb, vb, ks, vs, lens, G, True,
+                     out32=out32, pieces=dk.pieces_of(text), info=info)
 
 
 @pytest.mark.parametrize("layout", ["paged:16", "paged:64", "token_major", "fused"])
@@ -89,15 +90,15 @@ def test_decode_layouts_are_byte_identical_to_packed(fp8, layout):
     Hq, G, R, prec = 8, 4, 4, P.FP16 if fp8 else P.BF16
     page = int(layout.split(":")[1]) if layout.startswith("paged") else None
     if fp8:
-        q, k, v, ks, vs = t8.make_case(3, Hq, G, R, C_LONG, D, DTYPE[prec], seed=77)
-        caches = [t8.Cache8(k, v, LONG, how, seed=5) for how in ("packed", layout)]
-        inputs = t8.both_inputs(q, k, ks, LONG, G, True, caches[1], C_LONG, True, page=page)
-        run = lambda qq, cache, workspace: t8.run8(qq, cache, G, C_LONG, ks, vs, workspace=workspace)  # noqa: E731
+        q, k, v, ks, vs = dk.make_case(3, Hq, G, R, C_LONG, D, DTYPE[prec], seed=77)
+        caches = [dk.Cache8(k, v, LONG, how, seed=5) for how in ("packed", layout)]
+        inputs = dk.both_inputs8(q, k, ks, LONG, G, True, caches[1], C_LONG, True, page=page)
+        run = lambda qq, cache, workspace: dk.run8(qq, cache, G, C_LONG, ks, vs, workspace=workspace)  # noqa: E731
     else:
-        q, k, v = t16.make_values(3, Hq, G, R, C_LONG, D, DTYPE[prec], seed=78)
-        caches = [t16.Cache(k, v, LONG, how, seed=5) for how in ("packed", layout)]
-        inputs = t16.both_inputs(q, k, LONG, G, True, caches[1], C_LONG, True, page=page)
-        run = lambda qq, cache, workspace: t16.run(qq, cache, G, C_LONG, workspace=workspace)  # noqa: E731
+        q, k, v = dk.make_values(3, Hq, G, R, C_LONG, D, DTYPE[prec], seed=78)
+        caches = [dk.Cache(k, v, LONG, how, seed=5) for how in ("packed", layout)]
+        inputs = dk.both_inputs(q, k, LONG, G, True, caches[1], C_LONG, True, page=page)
+        run = lambda qq, cache, workspace: dk.run(qq, cache, G, C_LONG, workspace=workspace)  # noqa: E731
     for workspace in (True, False):
         for name, qq, info in inputs:
             _o0, l0, b0, t0 = run(qq, caches[0], workspace)
@@ -107,9 +108,9 @@ def test_decode_layouts_are_byte_identical_to_packed(fp8, layout):
             assert torch.equal(b0, b1), f"O differs between the {layout} and the packed cache"
             assert torch.equal(l0.view(torch.int32), l1.view(torch.int32)), f"L differs between the {layout} and the packed cache"
             if workspace and fp8:
-                t8.check(f"D=256 e4m3 {layout}{name}", o1, l1, qq, k, v, ks, vs, LONG, G, True, pieces=4, page=page, info=info)
+                dk.check(f"D=256 e4m3 {layout}{name}", o1, l1, qq, k, v, ks, vs, LONG, G, True, pieces=4, page=page, info=info)
             elif workspace:
-                t16.check_against_model(f"D=256 {layout}{name}", o1, l1, qq, k, v, LONG, G, True, pieces=4, page=page, info=info)
+                dk.check_against_model(f"D=256 {layout}{name}", o1, l1, qq, k, v, LONG, G, True, pieces=4, page=page, info=info)
 
 
 # (window, sink tokens, logits, the family's infix, the kernel the plan gives at column 1024 with a workspace): W = 130 spans five tiles
@@ -122,35 +123,35 @@ SETTINGS = [(W, S, True, "s", "_single"), (640, S, True, "s", "_pieces"), (640, 
 @pytest.mark.parametrize("fp8", [False, True])
 @pytest.mark.parametrize("dtype,G,R", [(torch.bfloat16, 8, 4), (torch.float16, 1, 1)])
 def test_decode_under_a_window_with_and_without_sinks(dtype, G, R, fp8, setting):
-    """on the split lengths, with the workspace the plan asks for, through the runners of tests/test_decode_gpu.py and
-    tests/test_kvcache_gpu.py (poison past every length; canaries around O, L and the workspace): the window, the sink tokens and the
+    """on the split lengths, with the workspace the plan asks for, through the runners of tests/decode_kit.py
+    (poison past every length; canaries around O, L and the workspace): the window, the sink tokens and the
     logits ride in the cache's launch keywords"""
     Wd, Sd, with_logits, infix, kernel = SETTINGS[setting]
     Hkv = 2
     Hq, fmt, lens = Hkv * G, dm.fmt_of(dtype), [int(n) for n in LONG]
     if fp8:
-        _q, kb, vb, ks, vs = t8.make_case(3, Hq, G, R, C_LONG, D, dtype, seed=31 + G + setting)
-        cache = t8.Cache8(kb, vb, LONG, "packed")
-        kvals, vvals = t8.dequantise(kb, t8.ONES(kb)), t8.dequantise(vb, t8.ONES(vb))
+        _q, kb, vb, ks, vs = dk.make_case(3, Hq, G, R, C_LONG, D, dtype, seed=31 + G + setting)
+        cache = dk.Cache8(kb, vb, LONG, "packed")
+        kvals, vvals = dk.dequantise(kb, dk.ONES(kb)), dk.dequantise(vb, dk.ONES(vb))
         seen = kvals.numpy() * ks.astype(np.float64)[None, :, None, None]
     else:
-        _q, kvals, vvals = t16.make_values(3, Hq, G, R, C_LONG, D, dtype, seed=31 + G + setting)
-        cache, ks, vs = t16.Cache(kvals, vvals, LONG, "packed"), None, None
+        _q, kvals, vvals = dk.make_values(3, Hq, G, R, C_LONG, D, dtype, seed=31 + G + setting)
+        cache, ks, vs = dk.Cache(kvals, vvals, LONG, "packed"), None, None
         seen = kvals.double().numpy()
     logits = np.random.default_rng(40 + setting).uniform(1.0, 4.0, Hq).astype(np.float32) if with_logits else None
     cache.kw.update(window=Wd)
     if infix == "s":
         cache.kw.update(sinkTokens=Sd, sinkLogits=torch.from_numpy(logits).cuda())
-    pieces = t16.planned_pieces((3, Hq, R, D), dtype, cache, G, C_LONG, True, True, AttentionDecodeFP8 if fp8 else AttentionDecode)
+    pieces = dk.planned_pieces((3, Hq, R, D), dtype, cache, G, C_LONG, True, True, AttentionDecodeFP8 if fp8 else AttentionDecode)
     assert (pieces is not None) == (kernel == "_pieces"), pieces
     q64, info = sm.needle_queries(seen, lens, None, Hq, G, R, Wd, Sd or 0, fmt, pieces=pieces, page=16)
     q = torch.from_numpy(q64).to(dtype)
     assert torch.equal(q.to(torch.float64), torch.from_numpy(q64))
     ref = sm.model(q, kvals, vvals, lens, None, G, Wd, Sd or 0, logits, pieces=pieces, kscale=ks, vscale=vs)
     if fp8:
-        o, l, _bits, text = t8.run8(q, cache, G, C_LONG, ks, vs, workspace=True)
+        o, l, _bits, text = dk.run8(q, cache, G, C_LONG, ks, vs, workspace=True)
     else:
-        o, l, _bits, text = t16.run(q, cache, G, C_LONG, workspace=True)
+        o, l, _bits, text = dk.run(q, cache, G, C_LONG, workspace=True)
     assert text.startswith("attn_decode%s%s_d256_%s%s (" % ("8" if fp8 else "16", infix, fmt, kernel)), text
     if pieces:
         assert "x %d pieces" % pieces in text and "+ attn_decode16_d256_%s_combine (" % fmt in text, text
@@ -164,7 +165,7 @@ def test_decode_under_a_window_with_and_without_sinks(dtype, G, R, fp8, setting)
 def test_decode_agrees_with_the_forward_kernel(prec, Hq, G, R, causal):
     """the parent's only route at this width, on the same buffers; both sides are held to the model's bound and to no number of their own
     beyond what tests/test_decode_gpu.py holds them to"""
-    t16.test_agrees_with_the_forward_kernel(prec, D, Hq, G, R, causal)
+    dk.agrees_with_the_forward_kernel(prec, D, Hq, G, R, causal)
 
 
 # --------------------------------------------------------------------------------------------------------------------- prefill
@@ -197,10 +198,6 @@ def prefill_values(dtype, G, fp8, seed=0):
     return q, kc, vc, kf, vf, scales
 
 
-def dev_scales(scales):
-    return tuple(None if s is None else torch.from_numpy(s).cuda() for s in scales)
-
-
 @pytest.mark.parametrize("causal", [True, False])
 @pytest.mark.parametrize("fp8", [False, True])
 @pytest.mark.parametrize("G", [1, 8])
@@ -208,8 +205,8 @@ def dev_scales(scales):
 def test_prefill_parity_contiguous_and_paged_16(dtype, G, fp8, causal):
     fmt, Hq = dm.fmt_of(dtype), HKV * G
     q, kc, vc, kf, vf, (ks, vs) = prefill_values(dtype, G, fp8)
-    form = AttentionPrefill(D, tp.PREC[dtype], cachePrecision=KVCachePrecision.E4M3 if fp8 else None).launchForm(
-        rows=PR, column=PC, heads=Hq, batches=PB, headsPerKeyValue=G, causal=causal, cacheLengths=tp.lengths(LENS))
+    form = AttentionPrefill(D, ck.PREC[dtype], cachePrecision=KVCachePrecision.E4M3 if fp8 else None).launchForm(
+        rows=PR, column=PC, heads=Hq, batches=PB, headsPerKeyValue=G, causal=causal, cacheLengths=ck.lengths(LENS))
     blocks = -(-PR // (128 // G))
     assert form.startswith("attn_prefill16_d256_%s%s (" % (fmt, "_e4m3" if fp8 else "")) and "x %d row blocks of %d rows" % (blocks, 128 // G) in form, form
     seen = kf.double().numpy() * (ks[None, :, None, None] if fp8 else 1.0)
@@ -224,18 +221,17 @@ def test_prefill_parity_contiguous_and_paged_16(dtype, G, fp8, causal):
         for b, n in enumerate(QLENS):
             qn[b, :, n:] = float("nan")   # rows nobody owns are never read
         for out in (None, torch.float32):
-            o, l = tp.launch(qn, tp.dev(kc), tp.dev(vc), G, causal, out=out, lens=LENS, qlens=QLENS, fp8=fp8, scales=dev_scales((ks, vs)))
-            tp.check_dead_and_empty(o, l, LENS, QLENS)
-            tp.hold(o, l, ref, dtype, out or dtype, info, "D=256 %s %s cache O%s" % (fmt, "e4m3" if fp8 else "16-bit", "32" if out else "16"), LENS, QLENS)
+            o, l = ck.prefill_launch(qn, ck.dev(kc), ck.dev(vc), G, causal, out=out, lens=LENS, qlens=QLENS, fp8=fp8, scales=ck.dev_scales((ks, vs)))
+            ck.check_dead_and_empty(o, l, LENS, QLENS)
+            ck.prefill_hold(o, l, ref, dtype, out or dtype, info, "D=256 %s %s cache O%s" % (fmt, "e4m3" if fp8 else "16-bit", "32" if out else "16"), LENS, QLENS, SEEN)
             if out is None:
                 base = (o, l)
         # paged 16, a shuffled pool: a row of a 16-key group that is read eight rows too low comes from another page's place
-        raw = (lambda t: t.view(torch.uint8)) if fp8 else (lambda t: t)
-        pk, pv, kw = tp.paged_pool(raw(kc), raw(vc), 16, LENS, 3 + G, 0x7F if fp8 else float("nan"))
+        pk, pv, kw = ck.prefill_pool(ck.raw(kc), ck.raw(vc), 16, LENS, 3 + G, 0x7F if fp8 else float("nan"))
         if fp8:
             pk, pv = pk.view(torch.float8_e4m3fn), pv.view(torch.float8_e4m3fn)
-        o, l = tp.launch(qn, pk, pv, G, causal, lens=LENS, qlens=QLENS, fp8=fp8, scales=dev_scales((ks, vs)), cache_kw=kw)
-        tp.check_dead_and_empty(o, l, LENS, QLENS)
+        o, l = ck.prefill_launch(qn, pk, pv, G, causal, lens=LENS, qlens=QLENS, fp8=fp8, scales=ck.dev_scales((ks, vs)), cache_kw=kw)
+        ck.check_dead_and_empty(o, l, LENS, QLENS)
         assert torch.equal(o.view(torch.int16), base[0].view(torch.int16)) and torch.equal(l, base[1]), "paged 16 differs from the contiguous launch"
 
 
@@ -250,15 +246,14 @@ def sink_and_ragged_case(dtype, G, fp8, paged, sinks):
     for b, n in enumerate(QLENS):
         q[b, :, n:] = float("nan")
     ref = sm.model(torch.nan_to_num(q.float(), nan=0.0), kf, vf, LENS, QLENS, G, W, Sp, logits, kscale=ks, vscale=vs)
-    kw = dict(rows=PR, column=PC, heads=Hq, batches=PB, headsPerKeyValue=G, causal=True, cacheLengths=tp.lengths(LENS), window=W)
+    kw = dict(rows=PR, column=PC, heads=Hq, batches=PB, headsPerKeyValue=G, causal=True, cacheLengths=ck.lengths(LENS), window=W)
     if sinks:
         kw.update(sinkTokens=S, sinkLogits=torch.from_numpy(logits).cuda())
     if fp8:
         kw.update(keyScale=torch.from_numpy(ks).cuda(), valueScale=torch.from_numpy(vs).cuda())
-    kd, vd = tp.dev(kc), tp.dev(vc)
+    kd, vd = ck.dev(kc), ck.dev(vc)
     if paged:
-        raw = (lambda t: t.view(torch.uint8)) if fp8 else (lambda t: t)
-        kd, vd, pkw = tp.paged_pool(raw(kc), raw(vc), 16, LENS, 17, 0x7F if fp8 else float("nan"))
+        kd, vd, pkw = ck.prefill_pool(ck.raw(kc), ck.raw(vc), 16, LENS, 17, 0x7F if fp8 else float("nan"))
         kw.update(pkw)
     return q, kd, vd, kw, ref, info, fmt
 
@@ -273,16 +268,16 @@ def test_prefill_under_a_window_with_sinks_and_the_ragged_identity(dtype, G, fp8
     padded launch's byte for byte, with NaN in the Q rows nobody owns"""
     Hq = HKV * G
     q, kd, vd, kw, ref, info, fmt = sink_and_ragged_case(dtype, G, fp8, paged, sinks)
-    op = AttentionPrefill(D, tp.PREC[dtype], cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
+    op = AttentionPrefill(D, ck.PREC[dtype], cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
     stream = torch.cuda.current_stream().cuda_stream
-    o = torch.full((PB, Hq, PR, D), tp.SENT_O, dtype=dtype, device="cuda")
-    l = torch.full((PB, Hq, PR), tp.SENT_L, dtype=torch.float32, device="cuda")
-    padded = dict(kw, queryLengths=tp.lengths(QLENS))
+    o = torch.full((PB, Hq, PR, D), ck.SENT_O, dtype=dtype, device="cuda")
+    l = torch.full((PB, Hq, PR), ck.SENT_L, dtype=torch.float32, device="cuda")
+    padded = dict(kw, queryLengths=ck.lengths(QLENS))
     assert op.launchForm(**padded).startswith("attn_prefill16%s_d256_%s%s (" % ("s" if sinks else "w", fmt, "_e4m3" if fp8 else ""))
     op.dispatch(q.cuda(), kd, vd, o, l, stream=stream, **padded)
     torch.cuda.synchronize()
     o, l = o.cpu(), l.cpu()
-    tp.check_dead_and_empty(o, l, LENS, QLENS)
+    ck.check_dead_and_empty(o, l, LENS, QLENS)
     wo, wl, where = sm.compare(o, l / LOG2E, ref, fmt, fmt, LENS, QLENS, margin=1, info=info)
     print("RATIO %s O16 needles | D=256 prefill window %d sinks %s%s G=%d | err / bound at margin 1: O %.3f L %.3f" % (
         fmt, W, S if sinks else None, " e4m3" if fp8 else "", G, wo, wl))
@@ -292,8 +287,8 @@ def test_prefill_under_a_window_with_sinks_and_the_ragged_identity(dtype, G, fp8
     qp = torch.full((T, Hq, D), float("nan"), dtype=dtype)
     for b, qn in enumerate(QLENS):
         qp[starts[b]:starts[b] + qn] = q[b, :, :qn].permute(1, 0, 2)
-    op_ = torch.full((T, Hq, D), tp.SENT_O, dtype=dtype, device="cuda")
-    lp = torch.full((Hq, T), tp.SENT_L, dtype=torch.float32, device="cuda")
+    op_ = torch.full((T, Hq, D), ck.SENT_O, dtype=dtype, device="cuda")
+    lp = torch.full((Hq, T), ck.SENT_L, dtype=torch.float32, device="cuda")
     ragged = dict(kw, rowStarts=torch.tensor(starts, dtype=torch.int32, device="cuda"), totalRows=T)
     assert op.launchForm(**ragged).startswith("attn_prefill16r_d256_%s%s (" % (fmt, "_e4m3" if fp8 else ""))
     op.dispatch(qp.cuda(), kd, vd, op_, lp, stream=stream, **ragged)
@@ -303,7 +298,7 @@ def test_prefill_under_a_window_with_sinks_and_the_ragged_identity(dtype, G, fp8
         got_o, got_l = op_[starts[b]:starts[b] + qn].permute(1, 0, 2), lp[:, starts[b]:starts[b] + qn]
         assert torch.equal(got_o.contiguous().view(torch.int16), o[b, :, :qn].contiguous().view(torch.int16)), f"sequence {b}: O differs from the padded launch"
         assert torch.equal(got_l.contiguous().view(torch.int32), l[b, :, :qn].contiguous().view(torch.int32)), f"sequence {b}: L differs from the padded launch"
-    assert bool((op_[sum(QLENS):].float() == tp.SENT_O).all()) and bool((lp[:, sum(QLENS):] == tp.SENT_L).all()), "a packed row nobody owns was written"
+    assert bool((op_[sum(QLENS):].float() == ck.SENT_O).all()) and bool((lp[:, sum(QLENS):] == ck.SENT_L).all()), "a packed row nobody owns was written"
 
 
 # ---------------------------------------------------------------------------------------------------------------------- append
@@ -311,13 +306,13 @@ def test_prefill_under_a_window_with_sinks_and_the_ragged_identity(dtype, G, fp8
                                                (P.FP16, 4, "contiguous", False)])
 def test_append_writes_exactly_the_named_positions(prec, R, layout, fp8):
     """e4m3: against mfa_kv_quantize_e4m3, the exported contract, element by element; a 16-bit cache: the rows' bits"""
-    t8.test_append_writes_exactly_the_named_positions(prec, D, R, layout, fp8)
+    dk.append_writes_exactly_the_named_positions(prec, D, R, layout, fp8)
 
 
 @pytest.mark.parametrize("dtype,fp8,paged", [(torch.bfloat16, True, True), (torch.float16, True, False), (torch.float16, False, False),
                                              (torch.bfloat16, False, True)])
 def test_ragged_append_is_the_per_sequence_append(dtype, fp8, paged):
-    trg.test_append_is_the_per_sequence_append_byte_for_byte(D, dtype, fp8, paged)
+    ck.append_is_the_per_sequence_append(ck.RAGGED_BATCH, D, dtype, fp8, paged)
 
 
 @pytest.mark.parametrize("fp8", [False, True])
@@ -332,8 +327,8 @@ def test_append_then_decode_over_the_appended_cache(fp8):
     hist_k, hist_v = ((torch.randn(B, Hkv, C, D, generator=g)).to(dtype) for _ in range(2))
     rng = np.random.default_rng(12)
     ks, vs = (dm.spread_scales(rng, Hkv), dm.spread_scales(rng, Hkv)) if fp8 else (None, None)
-    stored_k = t8.quantise(hist_k, ks) if fp8 else hist_k    # what a cache of this type holds for those rows
-    stored_v = t8.quantise(hist_v, vs) if fp8 else hist_v
+    stored_k = dk.quantise(hist_k, ks) if fp8 else hist_k    # what a cache of this type holds for those rows
+    stored_v = dk.quantise(hist_v, vs) if fp8 else hist_v
     pages = B * per + 2
     table = torch.from_numpy(rng.permutation(pages)[:B * per].reshape(B, per).astype(np.int32))
     poison = 0x7F if fp8 else float("nan")
@@ -352,8 +347,8 @@ def test_append_then_decode_over_the_appended_cache(fp8):
     KVCacheAppend(D, P.BF16, KVCachePrecision.E4M3 if fp8 else None).dispatch(
         knew.cuda(), vnew.cuda(), poolk, poolv, rows=R, heads=Hkv, batches=B, cacheLengths=lensd, pageSize=ps, blockTable=tabled, blockTableStride=per,
         pageStrides=(Hkv * ps * D, Hkv * ps * D), stream=stream, **scales)
-    seen_k = t8.dequantise(stored_k, ks) if fp8 else stored_k
-    q, info = t16.needle_q(seen_k, lens, Hq, G, R, dtype, True, page=ps)
+    seen_k = dk.dequantise(stored_k, ks) if fp8 else stored_k
+    q, info = dk.needle_q(seen_k, lens, Hq, G, R, dtype, True, page=ps)
     assert all(min(r + max(int(lens[b]) - R, 0), int(lens[b]) - 1) in info[(b, h, r)][0] for b in range(B) for h in range(Hq) for r in range(R))
     o = torch.full((B, Hq, R, D), float("nan"), dtype=dtype, device="cuda")
     l = torch.full((B, Hq, R), float("nan"), dtype=torch.float32, device="cuda")
@@ -363,6 +358,6 @@ def test_append_then_decode_over_the_appended_cache(fp8):
         pageStrides=(Hkv * ps * D, Hkv * ps * D), strides=dict(K=(D, ps * D, 0), V=(D, ps * D, 0)), stream=stream, **scales)
     torch.cuda.synchronize()
     if fp8:
-        t8.check("D=256 append then decode, e4m3", o.float().cpu(), l.cpu(), q, stored_k, stored_v, ks, vs, lens, G, True, page=ps, info=info)
+        dk.check("D=256 append then decode, e4m3", o.float().cpu(), l.cpu(), q, stored_k, stored_v, ks, vs, lens, G, True, page=ps, info=info)
     else:
-        t16.check_against_model("D=256 append then decode, 16-bit", o.float().cpu(), l.cpu(), q, hist_k, hist_v, lens, G, True, page=ps, info=info)
+        dk.check_against_model("D=256 append then decode, 16-bit", o.float().cpu(), l.cpu(), q, hist_k, hist_v, lens, G, True, page=ps, info=info)

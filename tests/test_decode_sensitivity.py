@@ -1,4 +1,4 @@
-"""CPU test (no GPU call): the checks of tests/test_decode_gpu.py and tests/test_kvcache_gpu.py can see a wrong key.
+"""CPU test (no GPU call): the checks of tests/test_decode_gpu.py and tests/test_kvcache_gpu.py (tests/decode_kit.py) can see a wrong key.
 
 For both input families of the GPU files (16-bit caches with K, V ~ U(-1, 1); e4m3 caches with K, V ~ N(0, 1) under per-head scales),
 at 1, 31, 33, 65, 600, 4096 and 32768 keys, causal or not, split or not, paged or not, with the needle queries of
@@ -219,15 +219,16 @@ def test_the_former_inputs_and_bounds_missed_what_the_new_ones_flag():
 # ------------------------------------------------------------------------------------------------------------------------- (d)
 def test_the_gpu_files_use_the_proven_bound():
     pytest.importorskip("torch")
+    import decode_kit
     import test_decode_gpu
     import test_kvcache_gpu
-    for module in (test_decode_gpu, test_kvcache_gpu):
+    for module in (test_decode_gpu, test_kvcache_gpu, decode_kit):   # (decode_kit: the runners and the model check both files share)
         assert module.decode_model is dm
         assert module.MARGIN is dm.MARGIN and module.bounds is dm.bounds and module.compare is dm.compare, module.__name__
         source = open(module.__file__).read()
         for own in ("MARGIN =", "def bounds", "def compare", "margin="):
             assert own not in source, "%s must not define or pass its own %r" % (module.__name__, own)
-    assert test_decode_gpu.model is dm.model and test_kvcache_gpu.ref16.model is dm.model
+    assert test_decode_gpu.model is dm.model and decode_kit.model is dm.model and test_kvcache_gpu.dk is decode_kit
 
 
 def test_needles_cover_the_geometry_of_the_long_case():

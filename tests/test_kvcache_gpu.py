@@ -1,7 +1,7 @@
 """GPU test: the FP8 KV cache through the C ABI of include/mfa_kvcache.h -- the append launch (exact, whole buffers compared) and
 decode attention over an e4m3 cache.
 
-Decode: expected values are the float64 numpy model of tests/test_decode_gpu.py applied to the DEQUANTISED cache,
+Decode: expected values are the float64 numpy model of tests/test_decode_gpu.py (tests/decode_kit.py holds both files' runners) applied to the DEQUANTISED cache,
 scale[j] x e4m3(byte), with that file's bounds (tests/harness.py TOL_MIXED: O 5e-2, L 7e-3 after dividing by log2 e): the kernel
 converts the bytes exactly to the launch's 16-bit type, the arithmetic after that is the 16-bit kernel's.  K, V ~ N(0, 1), scales per
 head in [0.5, 2].  Every decode launch runs on poisoned caches (0x7f = NaN in every byte at or past a length, in the rest of a last
@@ -21,17 +21,11 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import decode_kit as dk  # noqa: E402  (the float64 model's check, the runners of both launches and their caches)
 import decode_model  # noqa: E402
-import harness  # noqa: E402
+from decode_kit import DTYPE, LOG2E, NAN8, TOL_L, TOL_O, Cache8, both_inputs8 as both_inputs, check, dequantise, make_case, quantise, run8  # noqa: E402
 from decode_model import MARGIN, bounds, compare  # noqa: E402,F401  (the bound proven by tests/test_decode_sensitivity.py)
-import test_decode_gpu as ref16  # noqa: E402  (the float64 model, the 16-bit launch's runner and its bounds)
-from metal_flash_attention_amd import (AttentionDecodeFP8, GEMMOperandPrecision as P, KVCacheAppend, KVCachePrecision, _abi)  # noqa: E402
-
-DTYPE = {P.FP16: torch.float16, P.BF16: torch.bfloat16}
-LOG2E = ref16.LOG2E
-TOL_O, TOL_L = harness.TOL_MIXED["O"], harness.TOL_MIXED["L"]
-CANARY16, CANARY32, PAD, GUARD = ref16.CANARY16, ref16.CANARY32, ref16.PAD, ref16.GUARD
-NAN8 = 0x7F
+from metal_flash_attention_amd import GEMMOperandPrecision as P  # noqa: E402
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -39,150 +33,6 @@ def _gpu():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     yield
-
-
-def quantise(x, scales):
-    """[B, Hkv, C, D] 16-bit values -> e4m3 bytes (uint8) under per-head scales: torch's conversion, which tests/test_kvcache_plans.py
-    shows to be mfa_kv_quantize_e4m3 for every 16-bit pattern"""
-    s = torch.from_numpy(np.asarray(scales, dtype=np.float32))[None, :, None, None]
-    return (x.float() / s).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
-
-
-def dequantise(b, scales):
-    """bytes -> float64 scale[j] x e4m3(byte)"""
-    s = torch.from_numpy(np.asarray(scales, dtype=np.float64))[None, :, None, None]
-    return b.view(torch.float8_e4m3fn).to(torch.float64) * s
-
-
-def make_case(B, Hq, G, R, C, D, dtype, seed, shared=False):
-    g = torch.Generator().manual_seed(seed)
-    Hkv = Hq // G
-    q = torch.randn(B, Hq, R, D, generator=g).to(dtype)
-    k, v = (torch.randn(1 if shared else B, Hkv, C, D, generator=g).to(dtype) for _ in range(2))
-    if shared:
-        k, v = k.expand(B, -1, -1, -1).contiguous(), v.expand(B, -1, -1, -1).contiguous()
-    rng = np.random.default_rng(seed)
-    ks, vs = decode_model.spread_scales(rng, Hkv), decode_model.spread_scales(rng, Hkv)
-    return q, quantise(k, ks), quantise(v, vs), ks, vs
-
-
-class Cache8:
-    """K and V bytes on the device in one of the layouts of tests/test_decode_gpu.py, `poison` in every byte a launch must not load"""
-
-    def __init__(self, k, v, lens, layout, seed=0, poison=NAN8):
-        B, Hkv, C, D = k.shape
-        dev = "cuda"
-        kk, vv = k.clone(), v.clone()
-        if layout != "shared":
-            for b in range(B):
-                kk[b, :, int(lens[b]):] = poison
-                vv[b, :, int(lens[b]):] = poison
-        kw = {}
-        if layout == "packed":
-            self.k, self.v = kk.to(dev), vv.to(dev)
-        elif layout == "token_major":
-            self.k, self.v = kk.permute(0, 2, 1, 3).contiguous().to(dev), vv.permute(0, 2, 1, 3).contiguous().to(dev)
-            st = (Hkv * D, D, C * Hkv * D)
-            kw["strides"] = dict(K=st, V=st)
-        elif layout == "fused":
-            self.both = torch.stack([kk, vv], dim=3).contiguous().to(dev)
-            self.k, self.v = self.both[:, :, :, 0], self.both[:, :, :, 1]
-            st = (2 * D, C * 2 * D, Hkv * C * 2 * D)
-            kw["strides"] = dict(K=st, V=st)
-        elif layout == "shared":
-            n = int(max(lens))
-            kk[:, :, n:] = poison
-            vv[:, :, n:] = poison
-            self.k, self.v = kk[0].contiguous().to(dev), vv[0].contiguous().to(dev)
-            st = (D, C * D, 0)
-            kw["strides"] = dict(K=st, V=st)
-        else:   # "paged:<page size>": a shuffled pool with three pages nobody names and a guard page behind it
-            ps = int(layout.split(":")[1])
-            per = (C + ps - 1) // ps
-            rng = np.random.default_rng(seed)
-            used = [(b, i) for b in range(B) for i in range((int(lens[b]) + ps - 1) // ps)]
-            pages = len(used) + 3
-            order = rng.permutation(pages)
-            poolk = torch.full((pages + 1, Hkv, ps, D), poison, dtype=torch.uint8)
-            poolv = torch.full((pages + 1, Hkv, ps, D), poison, dtype=torch.uint8)
-            table = np.full((B, per + 2), int(order[len(used)]), dtype=np.int32)
-            for slot, (b, i) in enumerate(used):
-                pg = int(order[slot])
-                n = min(ps, C - i * ps)
-                poolk[pg, :, :n] = kk[b, :, i * ps:i * ps + n]
-                poolv[pg, :, :n] = vv[b, :, i * ps:i * ps + n]
-                table[b, i] = pg
-            self.poolk, self.poolv = poolk.to(dev), poolv.to(dev)
-            self.k, self.v = self.poolk, self.poolv
-            self.table = torch.from_numpy(table).to(dev)
-            kw.update(pageSize=ps, blockTable=self.table, blockTableStride=per + 2, pageStrides=(Hkv * ps * D, Hkv * ps * D),
-                      strides=dict(K=(D, ps * D, 0), V=(D, ps * D, 0)))
-        self.kw = kw
-        self.lens = torch.from_numpy(lens.astype(np.int64)).to(torch.int32).to(dev)
-        holders = [getattr(self, n) for n in ("both", "poolk", "poolv", "table") if hasattr(self, n)] or [self.k, self.v]
-        self.holders = holders + [self.lens]
-        self.before = [h.clone() for h in self.holders]
-
-    def unchanged(self):
-        return all(torch.equal(a, b) for a, b in zip(self.holders, self.before))
-
-
-def run8(q, cache, G, C, ks=None, vs=None, causal=True, workspace=True, out32=False, want_l=True):
-    """one FP8 launch -> (O fp32, L fp32 or None, O's stored bits, the launch form); checks NaN, canaries and that the cache is intact"""
-    B, Hq, R, D = q.shape
-    prec = P.BF16 if q.dtype == torch.bfloat16 else P.FP16
-    dec = AttentionDecodeFP8(D, prec, P.FP32 if out32 else prec)
-    dev = "cuda"
-    odt, ibits, ocan = (torch.float32, torch.int32, CANARY32) if out32 else (q.dtype, torch.int16, CANARY16)
-    o = torch.empty((B, Hq, R, D + PAD), dtype=odt, device=dev)
-    o.view(ibits).fill_(ocan)
-    l = torch.empty((B, Hq, R + 3), dtype=torch.float32, device=dev)
-    l.view(torch.int32).fill_(CANARY32)
-    strides = dict(cache.kw.get("strides", {}))
-    strides["O"] = (D + PAD, R * (D + PAD), Hq * R * (D + PAD))
-    ksd = None if ks is None else torch.from_numpy(ks).to(dev)
-    vsd = None if vs is None else torch.from_numpy(vs).to(dev)
-    kw = dict(cache.kw, rows=R, column=C, heads=Hq, batches=B, headsPerKeyValue=G, causal=causal, cacheLengths=cache.lens,
-              strides=strides, lStrides=(R + 3, Hq * (R + 3)), keyScale=ksd, valueScale=vsd)
-    need = dec.workspaceSize(**kw)
-    ws = None
-    if workspace and need:
-        ws = torch.empty(need + 2 * GUARD, dtype=torch.uint8, device=dev)
-        ws.view(torch.int16).fill_(CANARY16)
-        ws[GUARD:GUARD + need].view(torch.float32).fill_(float("nan"))
-        kw.update(workspace=int(ws.data_ptr()) + GUARD, workspaceBytes=need)
-    text = dec.launchForm(**kw)
-    dec.dispatch(q.to(dev), cache.k, cache.v, o, l if want_l else None, stream=torch.cuda.current_stream().cuda_stream, **kw)
-    torch.cuda.synchronize()
-    assert cache.unchanged(), "the launch wrote K, V, the table or the lengths"
-    assert bool((o.view(ibits)[..., D:] == ocan).all()), "O padding overwritten"
-    assert bool((l.view(torch.int32)[..., R:] == CANARY32).all()), "L padding overwritten"
-    if not want_l:
-        assert bool((l.view(torch.int32) == CANARY32).all()), "L written although NULL was passed"
-    if ws is not None:
-        assert bool((ws[:GUARD].view(torch.int16) == CANARY16).all()) and bool((ws[GUARD + need:].view(torch.int16) == CANARY16).all()), \
-            "workspace written beyond the reported size"
-    ov = o[..., :D]
-    assert bool(torch.isfinite(ov.float()).all()), "O is not finite"
-    lv = l[..., :R].cpu() if want_l else None
-    if want_l:
-        assert not bool(torch.isnan(lv).any()), "NaN in L"
-    return ov.float().cpu(), lv, ov.contiguous().view(ibits).cpu(), text
-
-
-ONES = lambda b: np.ones(b.shape[1], dtype=np.float32)  # noqa: E731
-
-
-def check(tag, o, l, q, kb, vb, ks, vs, lens, G, causal, **how):
-    """the model sees the bytes' own values and the scales apart, as the kernel does (how: out32, pieces, page, info)"""
-    return ref16.check_against_model(tag, o, l, q, dequantise(kb, ONES(kb)), dequantise(vb, ONES(vb)), lens, G, causal,
-                                     kscale=None if ks is None else ks, vscale=None if vs is None else vs, **how)
-
-
-def both_inputs(q, kb, ks, lens, G, causal, cache, C, workspace, page=None):
-    """the test's own queries and the needle queries for the dequantised K: [(name, q, info)]"""
-    return ref16.both_inputs(q, dequantise(kb, ONES(kb) if ks is None else ks), lens, G, causal, cache, C, workspace, page=page,
-                             decode=AttentionDecodeFP8)
 
 
 # ---------------------------------------------------------------------------------------------------------------- decode parity
@@ -203,7 +53,7 @@ def test_parity_with_the_float64_model_on_the_dequantised_cache(index, case):
             o, l, _bits, text = run8(qq, cache, G, C, ks, vs, causal=causal, workspace=workspace, out32=out32, want_l=want_l)
             assert ("_pieces" in text) == workspace and "attn_decode8_" in text, text
             check(f"fp8 {prec.name} D={D} G={G} R={R} causal={causal} split={workspace} O32={out32}{name}", o, l, qq, kb, vb, ks, vs, LENGTHS,
-                  G, causal, out32=out32, pieces=ref16.pieces_of(text), info=info)
+                  G, causal, out32=out32, pieces=dk.pieces_of(text), info=info)
 
 
 def test_one_long_sequence_in_64_pieces():
@@ -232,7 +82,7 @@ def test_fewer_keys_than_rows_and_packed_groups_at_the_tile_edges(prec, D, Hq, G
             for name, qq, info in both_inputs(q, kb, ks, lens, G, causal, cache, C, workspace):
                 o, l, _bits, text = run8(qq, cache, G, C, ks, vs, causal=causal, workspace=workspace, out32=causal)
                 check(f"fp8 n < R {prec.name} D={D} G={G} R={R} causal={causal} split={workspace}{name}", o, l, qq, kb, vb, ks, vs, lens, G,
-                      causal, out32=causal, pieces=ref16.pieces_of(text), info=info)
+                      causal, out32=causal, pieces=dk.pieces_of(text), info=info)
 
 
 # ------------------------------------------------------------------------------------------------- same inputs, the 16-bit route
@@ -247,17 +97,17 @@ def test_same_values_through_the_16_bit_launch(prec, D, G, R):
     k16, v16 = (b.view(torch.float8_e4m3fn).to(DTYPE[prec]) for b in (kb, vb))
     assert torch.equal(k16.to(torch.float64), kb.view(torch.float8_e4m3fn).to(torch.float64))   # the conversion is exact
     for workspace in (False, True):
-        c8, c16 = Cache8(kb, vb, lens, "packed"), ref16.Cache(k16, v16, lens, "packed")
+        c8, c16 = Cache8(kb, vb, lens, "packed"), dk.Cache(k16, v16, lens, "packed")
         for name, qq, info in both_inputs(q, kb, None, lens, G, True, c8, C, workspace):
             o8, l8, _b, t8 = run8(qq, c8, G, C, None, None, workspace=workspace, out32=True)
-            o16, l16, _b, t16 = ref16.run(qq, c16, G, C, workspace=workspace, out32=True)
+            o16, l16, _b, t16 = dk.run(qq, c16, G, C, workspace=workspace, out32=True)
             assert t8.replace("attn_decode8_", "attn_decode16_") == t16, (t8, t16)
             do, dl = float((o8 - o16).abs().max()), float((l8 - l16).abs().max())
             print(f"fp8 against the 16-bit launch {prec.name} D={D} G={G} R={R} split={workspace}{name}: max |dO| = {do:.3e} (fp32 O), "
                   f"max |dL| = {dl:.3e}")
             assert do <= TOL_O and dl / LOG2E <= TOL_L
             # each side on its own against the model: with FP32 O this is what gives the comparison a meaning
-            how = dict(out32=True, pieces=ref16.pieces_of(t8), info=info)
+            how = dict(out32=True, pieces=dk.pieces_of(t8), info=info)
             check(f"fp8 side {prec.name} D={D} G={G} R={R} split={workspace}{name}", o8, l8, qq, kb, vb, None, None, lens, G, True, **how)
             check(f"16-bit side {prec.name} D={D} G={G} R={R} split={workspace}{name}", o16, l16, qq, kb, vb, None, None, lens, G, True, **how)
 
@@ -268,7 +118,7 @@ def test_same_values_through_the_16_bit_launch(prec, D, G, R):
 def test_layouts_are_bit_identical_to_packed(prec, D, Hq, G, R, layout):
     C, B = 1000, 9
     q, kb, vb, ks, vs = make_case(B, Hq, G, R, C, D, DTYPE[prec], seed=21 + D, shared=layout == "shared")
-    lens = ref16.lengths_for(B, C, R, seed=4, page=int(layout.split(":")[1]) if ":" in layout else 64)
+    lens = dk.lengths_for(B, C, R, seed=4, page=int(layout.split(":")[1]) if ":" in layout else 64)
     page = int(layout.split(":")[1]) if ":" in layout else None
     for workspace in (False, True):
         packed, other = Cache8(kb, vb, lens, "packed"), Cache8(kb, vb, lens, layout, seed=5)
@@ -279,7 +129,7 @@ def test_layouts_are_bit_identical_to_packed(prec, D, Hq, G, R, layout):
             assert torch.equal(b0, b1), f"O differs between the {layout} and the packed cache"
             assert torch.equal(l0.view(torch.int32), l1.view(torch.int32)), f"L differs between the {layout} and the packed cache"
             check(f"fp8 {layout} {prec.name} D={D} split={workspace}{name}", o1, l1, qq, kb, vb, ks, vs, lens, G, True,
-                  pieces=ref16.pieces_of(t1), page=page, info=info)
+                  pieces=dk.pieces_of(t1), page=page, info=info)
 
 
 # ------------------------------------------------------------------------------------------------------------------- poison
@@ -288,7 +138,7 @@ def test_layouts_are_bit_identical_to_packed(prec, D, Hq, G, R, layout):
 def test_bytes_past_a_length_never_reach_a_product(prec, D, G, R, layout):
     C, B, Hq = 1000, 9, 2 * G
     q, kb, vb, ks, vs = make_case(B, Hq, G, R, C, D, DTYPE[prec], seed=55)
-    lens = ref16.lengths_for(B, C, R, seed=6, page=64)
+    lens = dk.lengths_for(B, C, R, seed=6, page=64)
     for workspace in (False, True):
         for causal in (True, False):
             on, ln, bn, _t = run8(q, Cache8(kb, vb, lens, layout, seed=8, poison=NAN8), G, C, ks, vs, causal=causal, workspace=workspace)
@@ -298,89 +148,13 @@ def test_bytes_past_a_length_never_reach_a_product(prec, D, G, R, layout):
 
 
 # ------------------------------------------------------------------------------------------------------------------- append
-def contract_bytes(x, scales):
-    """mfa_kv_quantize_e4m3 itself, element by element: [B, Hkv, R, D] 16-bit values -> uint8"""
-    quantize = _abi.lib().mfa_kv_quantize_e4m3
-    xf = x.float().numpy()
-    out = np.empty(xf.shape, dtype=np.uint8)
-    for j in range(xf.shape[1]):
-        s = float(scales[j])
-        flat = xf[:, j].reshape(-1)
-        out[:, j] = np.fromiter((quantize(float(t), s) for t in flat), dtype=np.uint8, count=flat.size).reshape(xf[:, j].shape)
-    return torch.from_numpy(out)
-
-
 APPEND = [(prec, D, R, layout, fp8) for prec in (P.BF16, P.FP16) for D in (64, 128) for R in (1, 4)
           for layout in ("contiguous", "token_major", "paged:16", "paged:64", "paged:256") for fp8 in (True, False)]
 
 
 @pytest.mark.parametrize("prec,D,R,layout,fp8", APPEND)
 def test_append_writes_exactly_the_named_positions(prec, D, R, layout, fp8):
-    dtype, dev = DTYPE[prec], "cuda"
-    Hkv = 3
-    paged = layout.startswith("paged")
-    ps = int(layout.split(":")[1]) if paged else 0
-    column = 3 * ps if paged else 200            # capacity of one sequence
-    per = column // ps if paged else 0
-    # none; fewer than R (for R = 4: the first row falls before key 0); exactly the capacity; a last page partly full; past the
-    # capacity (the rows behind it are dropped); an ordinary one
-    lens = np.array([0, R - 1, column, (2 * ps + 5) if paged else 77, column + 2, max(R, 9)], dtype=np.int64)
-    B = len(lens)
-    g = torch.Generator().manual_seed(D + R + len(layout))
-    knew, vnew = (torch.randn(B, Hkv, R, D, generator=g) * 3).to(dtype), (torch.randn(B, Hkv, R, D, generator=g) * 3).to(dtype)
-    knew[0, 0, 0, :4] = torch.tensor([1000.0, -1000.0, -0.0, 2.0 ** -10]).to(dtype)   # (sequence 0 is not written; 5 is)
-    knew[5, 0, 0, :4] = torch.tensor([1000.0, -1000.0, -0.0, 2.0 ** -10]).to(dtype)
-    ks, vs = (0.5 + 1.5 * torch.rand(Hkv, generator=g).numpy().astype(np.float32) for _ in range(2))
-    edt = torch.uint8 if fp8 else torch.int16
-    if fp8:
-        wk, wv = contract_bytes(knew, ks), contract_bytes(vnew, vs)
-    else:
-        wk, wv = knew.view(torch.int16), vnew.view(torch.int16)
-    # the caches, pre-filled with a byte pattern, as [slot][Hkv][keys][D] views of their buffers
-    rng = np.random.default_rng(7)
-    if paged:
-        pages = B * per + 2
-        shape_, perm = (pages, Hkv, ps, D), (0, 1, 2, 3)
-        order = rng.permutation(pages)
-        table = torch.from_numpy(order[:B * per].reshape(B, per).astype(np.int32))
-    elif layout == "token_major":
-        shape_, perm = (B, column, Hkv, D), (0, 2, 1, 3)
-    else:
-        shape_, perm = (B, Hkv, column, D), (0, 1, 2, 3)
-    esz = 1 if fp8 else 2
-    bufs = [torch.from_numpy(rng.integers(0, 256, size=int(np.prod(shape_)) * esz + 64, dtype=np.uint8)) for _ in range(2)]   # 64 guard bytes
-    expect = [b.clone() for b in bufs]
-    views = [e[:int(np.prod(shape_)) * esz].view(edt).view(shape_).permute(perm) for e in expect]
-    for b in range(B):
-        for r in range(R):
-            pos = int(lens[b]) - R + r
-            if pos < 0 or pos >= column:
-                continue
-            slot, at = (int(table[b, pos // ps]), pos % ps) if paged else (b, pos)
-            views[0][slot, :, at] = wk[b, :, r]
-            views[1][slot, :, at] = wv[b, :, r]
-    dbufs = [b.to(dev) for b in bufs]
-    kw = dict(rows=R, heads=Hkv, batches=B, cacheLengths=torch.from_numpy(lens).to(torch.int32).to(dev))
-    if paged:
-        kw.update(pageSize=ps, blockTable=table.to(dev), blockTableStride=per, pageStrides=(Hkv * ps * D, Hkv * ps * D))
-    else:
-        kw.update(column=column)
-        if layout == "token_major":
-            st = (Hkv * D, D, column * Hkv * D)
-            kw.update(strides=dict(kCache=st, vCache=st))
-    if fp8:
-        kw.update(keyScale=torch.from_numpy(ks).to(dev), valueScale=torch.from_numpy(vs).to(dev))
-    hold = kw.get("blockTable")
-    KVCacheAppend(D, prec, KVCachePrecision.E4M3 if fp8 else None).dispatch(knew.to(dev), vnew.to(dev), dbufs[0], dbufs[1],
-                                                                            stream=torch.cuda.current_stream().cuda_stream, **kw)
-    torch.cuda.synchronize()
-    for name, got, want in zip("KV", dbufs, expect):
-        got = got.cpu()
-        wrong = torch.nonzero(got != want).flatten()
-        assert wrong.numel() == 0, f"{name} cache: {wrong.numel()} bytes differ from the model, first at {wrong[:4].tolist()}"
-    written = sum(1 for b in range(B) for r in range(R) if 0 <= int(lens[b]) - R + r < column)
-    assert written >= 3 and not torch.equal(expect[0], bufs[0])   # the case does write something
-    del hold
+    dk.append_writes_exactly_the_named_positions(prec, D, R, layout, fp8)
 
 
 # ---------------------------------------------------------------------------------------------------------------- round trip
@@ -423,7 +197,7 @@ def test_eight_generation_steps_append_then_decode():
             vb[b, :, :int(n[b])] = quantise(history_v[b][None], vs.numpy())[0]
         # the step's query: the row just appended (key n - 1, the row's frontier) and the one before it are among its needles, so
         # an append that went to another position, page or head, or stale bytes there, move O far outside the bound
-        q, info = ref16.needle_q(dequantise(kb, ks.numpy()), n, Hq, G, 1, dtype, True, page=ps)
+        q, info = dk.needle_q(dequantise(kb, ks.numpy()), n, Hq, G, 1, dtype, True, page=ps)
         assert all(int(n[b]) - 1 in info[(b, h, 0)][0] for b in range(B) for h in range(Hq))
         lens += 1                                            # on the device
         assert kv_cache_append(kn.to(dev), vn.to(dev), poolk, poolv, lens, block_table=table, k_scale=ksd, v_scale=vsd) is None

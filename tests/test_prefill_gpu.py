@@ -16,19 +16,21 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import cache_kit as ck  # noqa: E402
 import decode_model as dm  # noqa: E402
 import prefill_model as pm  # noqa: E402
-from metal_flash_attention_amd import (AttentionDecode, AttentionDescriptor, AttentionKernel, AttentionKernelType, AttentionOperand as Op,  # noqa: E402
-                                       AttentionPrefill, GEMMOperandPrecision as P, KVCachePrecision)
+from cache_kit import LOG2E, PREC, SENT_L, SENT_O, dev, lengths, strides_of  # noqa: E402
+from metal_flash_attention_amd import AttentionDecode, AttentionDescriptor, AttentionKernel, AttentionKernelType, AttentionOperand as Op  # noqa: E402
 
-LOG2E = 1.4426950408889634
-FLT_MAX = float(np.finfo(np.float32).max)
 SEQS = [(1, 1), (33, 33), (128, 128), (129, 300), (40, 1500), (200, 777), (5, 2049), (70, 65), (0, 50), (64, 0)]
 QLENS, LENS = [s[0] for s in SEQS], [s[1] for s in SEQS]
 B, R, C, HKV = len(SEQS), 200, 2112, 2
-PREC = {torch.bfloat16: P.BF16, torch.float16: P.FP16}
-SENT_O, SENT_L = -7.25, 12345.5
 SEEN = {}
+# the runners of tests/cache_kit.py on this file's batch
+launch = functools.partial(ck.prefill_launch, lens=LENS, qlens=QLENS)
+check_dead_and_empty = functools.partial(ck.check_dead_and_empty, lens=LENS, qlens=QLENS)
+hold = functools.partial(ck.prefill_hold, lens=LENS, qlens=QLENS, seen=SEEN)
+paged_pool = ck.prefill_pool
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -38,18 +40,6 @@ def _gpu():
     yield
     if SEEN:
         print("\nprefill worst err / bound at margin 1:", {k: round(v, 4) for k, v in SEEN.items()})
-
-
-def dev(t):
-    return t.cuda() if t is not None else None
-
-
-def lengths(values):
-    return torch.tensor(values, dtype=torch.int32, device="cuda")
-
-
-def strides_of(t):
-    return (int(t.stride(2)), int(t.stride(1)), int(t.stride(0)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -79,58 +69,6 @@ def reference(D, dtype, G, causal, kind):
     return q, pm.model(q, clean(k), clean(v), LENS, QLENS, G, causal), info
 
 
-def launch(q, k, v, G, causal, *, out=None, lens=LENS, qlens=QLENS, cache_kw=None, q_strided=False, fp8=False, scales=(None, None)):
-    """-> (O [B, Hq, R, D], L [B, Hq, R] base-2) as the launch left them on sentinel-filled buffers"""
-    Bq, Hq, Rq, D = q.shape
-    pre = AttentionPrefill(D, PREC[q.dtype], out and PREC.get(out, P.FP32), cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
-    odt = out or q.dtype
-    qd = dev(q)
-    strides = {}
-    if q_strided:   # rows D + 8 apart, heads and batches padded: the operand is a window of a larger allocation
-        buf = torch.full((Bq, Hq + 1, Rq + 3, D + 8), float("nan"), dtype=q.dtype, device="cuda")
-        buf[:, :Hq, :Rq, :D] = qd
-        qd = buf[:, :Hq, :Rq, :D]
-        obuf = torch.full((Bq, Hq + 2, Rq + 1, D + 4), SENT_O, dtype=odt, device="cuda")
-        o = obuf[:, :Hq, :Rq, :D]
-        strides.update(Q=strides_of(qd), O=strides_of(o))
-    else:
-        obuf = o = torch.full((Bq, Hq, Rq, D), SENT_O, dtype=odt, device="cuda")
-    l = torch.full((Bq, Hq, Rq), SENT_L, dtype=torch.float32, device="cuda")
-    kw = dict(cache_kw or {})
-    strides.update(kw.pop("strides", {}))
-    column = kw.pop("column", k.shape[2])
-    if fp8:
-        kw.update(keyScale=scales[0], valueScale=scales[1])
-    pre.dispatch(qd, k, v, o, l, rows=Rq, column=column, heads=Hq, batches=Bq, headsPerKeyValue=G, causal=causal,
-                 cacheLengths=lengths(lens), queryLengths=None if qlens is None else lengths(qlens), strides=strides,
-                 stream=torch.cuda.current_stream().cuda_stream, **kw)
-    torch.cuda.synchronize()
-    if q_strided:
-        inside = torch.zeros_like(obuf, dtype=torch.bool)
-        inside[:, :Hq, :Rq, :D] = True
-        assert bool((obuf[~inside] == SENT_O).all()), "the launch wrote outside O's window"
-    return o.cpu(), l.cpu()
-
-
-def check_dead_and_empty(o, l, lens=LENS, qlens=QLENS):
-    """rows at or past qn keep the sentinel bit for bit; live rows of an empty sequence hold O = 0, L = -FLT_MAX; no live NaN"""
-    for b, (qn, n) in enumerate(zip(qlens, lens)):
-        qn = min(qn, o.shape[2])
-        assert bool((o[b, :, qn:].float() == SENT_O).all()) and bool((l[b, :, qn:] == SENT_L).all()), f"sequence {b}: rows at or past {qn} were written"
-        assert bool(torch.isfinite(o[b, :, :qn].float()).all()) and bool(torch.isfinite(l[b, :, :qn]).all()), f"sequence {b}: poison reached a live row"
-        if n == 0:
-            assert not o[b, :, :qn].float().any() and bool((l[b, :, :qn] == -FLT_MAX).all()), f"sequence {b}: empty"
-
-
-def hold(o, l, ref, dtype, out, info, tag, lens=LENS, qlens=QLENS):
-    fmt = dm.fmt_of(dtype)
-    outf = "f32" if out == torch.float32 else fmt
-    wo, wl, text = pm.compare(o, l / LOG2E, ref, fmt, outf, lens, qlens, margin=1, info=info)
-    SEEN[tag] = max(SEEN.get(tag, 0.0), wo, wl)
-    print("%s: worst |dO| / bound %.3f, |dL| / bound %.3f at margin 1" % (tag, wo, wl))
-    assert wo <= pm.MARGIN and wl <= pm.MARGIN, text
-
-
 @pytest.mark.parametrize("kind", ["uniform", "needle"])
 @pytest.mark.parametrize("causal", [True, False])
 @pytest.mark.parametrize("G", [1, 4, 8, 3])
@@ -144,30 +82,6 @@ def test_parity_with_the_model(D, dtype, G, causal, kind):
         o, l = launch(q, kd, vd, G, causal, out=out)
         check_dead_and_empty(o, l)
         hold(o, l, ref, dtype, out or dtype, info, "16-bit cache")
-
-
-def paged_pool(k, v, page, lens, seed, poison, fill_dtype=None):
-    """a shuffled pool [pages, HKV, page, D] holding keys < n only (the rest poison), and the table with garbage past the last page"""
-    rng = np.random.default_rng(seed)
-    Bk, Hkv, Ck, D = k.shape
-    pps = -(-Ck // page)
-    total = Bk * pps + 3
-    perm = rng.permutation(total)
-    pk = torch.full((total, Hkv, page, D), poison, dtype=k.dtype if fill_dtype is None else fill_dtype)
-    pv = pk.clone()
-    if fill_dtype is not None:
-        pk, pv = pk.view(k.dtype), pv.view(k.dtype)
-    table = np.full((Bk, pps + 2), -7, dtype=np.int32)
-    table[:, 1::2] = 2 ** 30
-    for b, n in enumerate(lens):
-        for i in range(-(-n // page)):
-            pg, cnt = int(perm[b * pps + i]), min(page, n - i * page)
-            table[b, i] = pg
-            pk[pg, :, :cnt] = k[b, :, i * page:i * page + cnt]
-            pv[pg, :, :cnt] = v[b, :, i * page:i * page + cnt]
-    kw = dict(pageSize=page, blockTable=torch.from_numpy(table).cuda(), blockTableStride=table.shape[1],
-              pageStrides=(Hkv * page * D, Hkv * page * D), strides=dict(K=(D, page * D, 0), V=(D, page * D, 0)), column=pps * page)
-    return pk.cuda(), pv.cuda(), kw
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

@@ -9,7 +9,8 @@ distinct caches, so a row served with another sequence's start, length, block-ta
 Batches (n keys, qn rows).  G = 8 (RB = 16) and G = 3 (RB = 42): (700, 40), (200, 17), (65, 1), (0, 0), (30, 16), (10, 33) -- fewer keys
 than rows -- and (0, 3), rows without any key.  G = 1 (RB = 128): qn = 130, 0, 1, 128.  Caches hold NaN / 0x7f at and past every length;
 the packed Q holds NaN in every row no sequence owns; O and L are pre-filled with sentinels and carry 64 sentinel rows before and
-after.  Parity with the float64 model runs on the batch, the poisoned caches and the needle queries of tests/test_sink_gpu.py, packed.
+after.  Parity with the float64 model runs on the batch, the poisoned caches and the needle queries of tests/test_sink_gpu.py
+(tests/cache_kit.py holds them), packed.
 Maxima seen on an MI355X: DESIGN.md 4.14."""
 import functools
 
@@ -21,21 +22,21 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import decode_model as dm  # noqa: E402
+import cache_kit as ck  # noqa: E402  (the sink batch, its poisoned caches, needle queries and bounds: the parity cases run on them)
 import ragged_model as rm  # noqa: E402
-import test_sink_gpu as tsg  # noqa: E402  (its batch, poisoned caches, needle queries and bounds: the parity cases run on them)
-from metal_flash_attention_amd import AttentionPrefill, GEMMOperandPrecision as P, KVCacheAppend, KVCachePrecision  # noqa: E402
+import sink_model as sm  # noqa: E402
+from cache_kit import FLT_MAX, PREC, SENT_L, SENT_O, bits, lengths  # noqa: E402
+from metal_flash_attention_amd import AttentionPrefill, KVCacheAppend, KVCachePrecision  # noqa: E402
 
-FLT_MAX = float(np.finfo(np.float32).max)
-BATCH = [(700, 40), (200, 17), (65, 1), (0, 0), (30, 16), (10, 33), (0, 3)]
+BATCH = list(ck.RAGGED_BATCH.SEQS)
 BATCH_G1 = [(700, 130), (200, 0), (65, 1), (300, 128)]
-C, HKV, PAGE, PADROWS = 768, 2, 16, 64
-PREC = {torch.bfloat16: P.BF16, torch.float16: P.FP16}
-SENT_O, SENT_L = -7.25, 12345.5
+C, HKV, PAGE, PADROWS = ck.RAGGED_BATCH.C, ck.RAGGED_BATCH.HKV, 16, 64
 SETTINGS = [(0, 0, False), (130, 0, False), (130, 4, True), (0, 0, True)]        # (W, S, logits)
 # (D, dtype, G, e4m3 cache, paged 16): every value of every dimension, both caches and both layouts under every G
 VARIANTS = [(64, torch.bfloat16, 8, False, False), (128, torch.float16, 8, False, True), (128, torch.bfloat16, 8, True, True),
             (64, torch.float16, 8, True, False), (64, torch.float16, 3, True, True), (128, torch.bfloat16, 3, False, False),
             (64, torch.bfloat16, 1, False, True), (128, torch.float16, 1, True, False)]
+SEEN = {}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -43,64 +44,34 @@ def _gpu():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     yield
-    if tsg.SEEN:
-        print("\nragged parity, worst err / bound at margin 1:", {k: round(v, 4) for k, v in tsg.SEEN.items() if k.startswith("ragged")})
+    if SEEN:
+        print("\nragged parity, worst err / bound at margin 1:", {k: round(v, 4) for k, v in SEEN.items()})
 
 
 def batch_of(G):
     return BATCH_G1 if G == 1 else BATCH
 
 
-def u32(values):
-    return torch.tensor([int(x) for x in values], dtype=torch.int32, device="cuda")
-
-
-def raw(t):
-    return t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t
-
-
 @functools.lru_cache(maxsize=None)
 def caches(D, dtype, fp8, G, paged):
     """device K, V of the batch with poison at and past every length, the launch keywords of the layout, and the per-head scales"""
-    lens = [n for n, _ in batch_of(G)]
-    B = len(lens)
+    batch = ck.Batch(tuple(batch_of(G)), C, HKV, None)
     g = torch.Generator().manual_seed(D + 3 * G + 11 * fp8)
-    rnd = lambda: torch.rand(B, HKV, C, D, generator=g) * 2 - 1  # noqa: E731
+    rnd = lambda: torch.rand(batch.B, HKV, C, D, generator=g) * 2 - 1  # noqa: E731
     if fp8:
         k, v = (rnd() * 3).to(torch.float8_e4m3fn), (rnd() * 3).to(torch.float8_e4m3fn)
         rng = np.random.default_rng(D + G)
         scales = tuple(torch.from_numpy(dm.spread_scales(rng, HKV)).cuda() for _ in range(2))
     else:
         k, v, scales = rnd().to(dtype), rnd().to(dtype), (None, None)
-    poison = 0x7F if fp8 else float("nan")
-    k, v = raw(k.clone()), raw(v.clone())
-    for b, n in enumerate(lens):
-        k[b, :, n:] = poison
-        v[b, :, n:] = poison
-    kw = {}
     if paged:   # a shuffled pool that holds the pages below each length only; every other table entry names an all-poison page
-        pps = C // PAGE
-        total = B * pps + 1
-        perm = np.random.default_rng(D + G + fp8).permutation(total - 1)
-        pk = torch.empty((total, HKV, PAGE, D), dtype=k.dtype)
-        pk[:] = poison
-        pv = pk.clone()
-        table = np.full((B, pps), total - 1, dtype=np.int32)
-        for b, n in enumerate(lens):
-            for i in range(-(-n // PAGE)):
-                pg = int(perm[b * pps + i])
-                table[b, i] = pg
-                pk[pg], pv[pg] = k[b, :, i * PAGE:(i + 1) * PAGE], v[b, :, i * PAGE:(i + 1) * PAGE]
-        k, v = pk, pv
-        kw = dict(pageSize=PAGE, blockTable=torch.from_numpy(table).cuda(), blockTableStride=pps, pageStrides=(HKV * PAGE * D, HKV * PAGE * D),
-                  strides=dict(K=(D, PAGE * D, 0), V=(D, PAGE * D, 0)))
-    view = (lambda t: t.view(torch.float8_e4m3fn)) if fp8 else (lambda t: t)
-    return view(k).cuda(), view(v).cuda(), kw, scales
+        return ck.paged_pool(k, v, PAGE, batch.keep(), seed=D + G + fp8) + (scales,)
+    return ck.poisoned(k, batch.keep()).cuda(), ck.poisoned(v, batch.keep()).cuda(), {}, scales
 
 
 def extras(W, S, logits, Hq, padded_entry):
     """the window / sink keywords of a launch; the padded launch goes through the sink entries iff any of them is set"""
-    lg = torch.from_numpy(tsg.sink_logits(Hq, W + S)).cuda() if logits else None
+    lg = torch.from_numpy(ck.sink_logits(Hq, W + S)).cuda() if logits else None
     if padded_entry and not (W or S or logits):
         return {}, lg
     kw = {}
@@ -123,7 +94,7 @@ def padded_launch(q, k, v, lens, qlens, G, fp8, scales, cache_kw, ext):
     o = torch.full((B, Hq, R, D), SENT_O, dtype=q.dtype, device="cuda")
     l = torch.full((B, Hq, R), SENT_L, dtype=torch.float32, device="cuda")
     kw = dict(cache_kw)
-    kw.update(rows=R, column=C, heads=Hq, batches=B, headsPerKeyValue=G, cacheLengths=u32(lens), queryLengths=u32(qlens), **ext)
+    kw.update(rows=R, column=C, heads=Hq, batches=B, headsPerKeyValue=G, cacheLengths=lengths(lens), queryLengths=lengths(qlens), **ext)
     if fp8:
         kw.update(keyScale=scales[0], valueScale=scales[1])
     op_of(D, q.dtype, fp8).dispatch(q.cuda(), k, v, o, l, stream=torch.cuda.current_stream().cuda_stream, **kw)
@@ -139,7 +110,7 @@ def ragged_launch(qp, k, v, lens, starts, T, cap, G, fp8, scales, cache_kw, ext,
     ob = torch.full((Tq + 2 * PADROWS, Hq, D), SENT_O, dtype=qp.dtype, device="cuda")
     lb = torch.full((Hq, Tq + 2 * PADROWS), SENT_L, dtype=torch.float32, device="cuda")
     kw = dict(cache_kw)
-    kw.update(rows=cap, column=column, heads=Hq, batches=len(lens), headsPerKeyValue=G, cacheLengths=u32(lens), rowStarts=u32(starts), totalRows=T,
+    kw.update(rows=cap, column=column, heads=Hq, batches=len(lens), headsPerKeyValue=G, cacheLengths=lengths(lens), rowStarts=lengths(starts), totalRows=T,
               lStrides=(Tq + 2 * PADROWS, 0), **ext)
     if fp8:
         kw.update(keyScale=scales[0], valueScale=scales[1])
@@ -148,10 +119,6 @@ def ragged_launch(qp, k, v, lens, starts, T, cap, G, fp8, scales, cache_kw, ext,
     op.dispatch(qb[PADROWS:], k, v, ob[PADROWS:], lb[:, PADROWS:], stream=torch.cuda.current_stream().cuda_stream, **kw)
     torch.cuda.synchronize()
     return ob, lb
-
-
-def bits(t):
-    return t.view(torch.int16) if t.dtype in (torch.bfloat16, torch.float16) else t.view(torch.int32)
 
 
 def identity_case(variant, setting, *, total=None, cap=None):
@@ -217,103 +184,45 @@ def test_rows_at_or_past_total_rows_and_past_the_cap_keep_their_sentinels(varian
     assert max(qn for _s, qn in owned) == cap < max(counts)
 
 
-@pytest.mark.parametrize("variant", range(len(tsg.VARIANTS)))
+@pytest.mark.parametrize("variant", range(len(ck.SINK_VARIANTS)))
 def test_parity_with_the_float64_model_on_poisoned_caches(variant):
     """the batch of tests/test_sink_gpu.py, packed, under W = 130 with S = 4 and a sink logit per head: one configuration per D and
     type, at the committed bounds and margin of sink_model.compare, on caches poisoned in every tile no workgroup walks"""
-    (W, S), (D, dtype, G, _Rd, fp8) = tsg.SETTINGS[0], tsg.VARIANTS[variant]
-    R = tsg.RP
-    k, v, scales = tsg.base(D, dtype, fp8)
-    sd = (tsg.dev(scales[0]), tsg.dev(scales[1]))
-    tiles = [tsg.walked("prefill", n, qn, G, R, W, S) for n, qn in tsg.SEQS]
-    q, sink, ref, info = tsg.reference("prefill", D, dtype, G, R, W, S, fp8)
-    counts = [min(qn, R) for qn in tsg.QLENS]
+    batch, (W, S), (D, dtype, G, _Rd, fp8) = ck.SINK_BATCH, (130, 4), ck.SINK_VARIANTS[variant]
+    R = batch.RP
+    k, v, scales = ck.base(batch, D, dtype, fp8)
+    sd = (ck.dev(scales[0]), ck.dev(scales[1]))
+    keep = batch.keep(tiles=ck.walked(batch, "prefill", G, R, W, S))
+    q, sink, ref, info = ck.sink_reference(batch, "prefill", D, dtype, G, R, W, S, fp8)
+    counts = [min(qn, R) for qn in batch.QLENS]
     starts = rm.row_starts(counts)
     T = starts[-1]
     qp = torch.from_numpy(rm.pack(q.view(torch.int16).numpy(), starts, T, R)).view(dtype)
-    ext = dict(window=W, sinkTokens=S, sinkLogits=tsg.dev(sink))
+    ext = dict(window=W, sinkTokens=S, sinkLogits=ck.dev(sink))
     results = []
     for paged in (False, True):
         if paged:
-            kd, vd, kw = tsg.paged_pool(k, v, 16, tiles, seed=variant)
+            kd, vd, kw = ck.paged_pool(k, v, 16, keep, seed=variant)
         else:
-            kd, vd, kw = tsg.poisoned(k, tiles).cuda(), tsg.poisoned(v, tiles).cuda(), {}
-        ob, lb = ragged_launch(qp, kd, vd, tsg.LENS, starts, T, R, G, fp8, sd, kw, ext, column=tsg.C)
+            kd, vd, kw = ck.poisoned(k, keep).cuda(), ck.poisoned(v, keep).cuda(), {}
+        ob, lb = ragged_launch(qp, kd, vd, batch.LENS, starts, T, R, G, fp8, sd, kw, ext, column=batch.C)
         ob, lb = ob.cpu()[PADROWS:PADROWS + T], lb.cpu()[:, PADROWS:PADROWS + T]
         o = torch.from_numpy(rm.unpack(ob.view(torch.int16).numpy(), starts, T, R, R, fill=0)).view(dtype)
         l = torch.from_numpy(rm.unpack_l(lb.numpy(), starts, T, R, R, fill=SENT_L))
-        for b, qn in enumerate(counts):               # (tsg.hold wants its own sentinels at and past qn)
-            o[b, :, qn:] = tsg.SENT_O
-            l[b, :, qn:] = tsg.SENT_L
-        tsg.hold("prefill", o, l, ref, dtype, dtype, info, "ragged" + (" e4m3 cache" if fp8 else " 16-bit cache"), sink, W, S)
+        for b, qn in enumerate(counts):               # (cache_kit.hold wants its sentinels at and past qn)
+            o[b, :, qn:] = SENT_O
+            l[b, :, qn:] = SENT_L
+        ck.hold(batch, "prefill", o, l, ref, dtype, dtype, info, "ragged" + (" e4m3 cache" if fp8 else " 16-bit cache"), sm, SEEN, ck.sink_blind(W, S), sink)
         results.append((ob, lb))
     assert torch.equal(bits(results[0][0]), bits(results[1][0])) and torch.equal(results[0][1], results[1][1]), "paged 16 differs from the contiguous launch"
 
 
 # ---------------------------------------------------------------------------------------------------------------------- the append
-def append_case(D, dtype, fp8, paged, seed):
-    """(packed sources, lens, starts, cap, sentinel-filled caches, keywords, scales)"""
-    batch = BATCH
-    lens, counts = [n for n, _ in batch], [qn for _, qn in batch]
-    B = len(batch)
-    starts = rm.row_starts(counts)
-    T = starts[-1]
-    g = torch.Generator().manual_seed(seed)
-    kn, vn = ((torch.rand(T, HKV, D, generator=g) * 6 - 3).to(dtype).cuda() for _ in range(2))
-    cdt = torch.uint8 if fp8 else dtype
-    sent = 0x5A if fp8 else 3.5
-    kw, scales = {}, (None, None)
-    if paged:
-        pps = C // PAGE
-        table = torch.from_numpy(np.random.default_rng(seed).permutation(B * pps).astype(np.int32).reshape(B, pps)).cuda()
-        kc, vc = (torch.full((B * pps, HKV, PAGE, D), sent, dtype=cdt, device="cuda") for _ in range(2))
-        kw = dict(pageSize=PAGE, blockTable=table, blockTableStride=pps, pageStrides=(HKV * PAGE * D, HKV * PAGE * D),
-                  strides=dict(kCache=(D, PAGE * D, 0), vCache=(D, PAGE * D, 0)))
-    else:
-        kc, vc = (torch.full((B, HKV, C, D), sent, dtype=cdt, device="cuda") for _ in range(2))
-        kw = dict(column=C)
-    if fp8:
-        rng = np.random.default_rng(seed)
-        scales = tuple(torch.from_numpy(dm.spread_scales(rng, HKV)).cuda() for _ in range(2))
-        kw.update(keyScale=scales[0], valueScale=scales[1])
-    return kn, vn, lens, counts, starts, T, kc, vc, kw
-
-
 @pytest.mark.parametrize("paged", [False, True])
 @pytest.mark.parametrize("fp8", [False, True])
 @pytest.mark.parametrize("D,dtype", [(64, torch.float16), (128, torch.bfloat16)])
 def test_append_is_the_per_sequence_append_byte_for_byte(D, dtype, fp8, paged):
-    kn, vn, lens, counts, starts, T, kc, vc, kw = append_case(D, dtype, fp8, paged, D + fp8)
-    app = KVCacheAppend(D, PREC[dtype], KVCachePrecision.E4M3 if fp8 else None)
-    stream = torch.cuda.current_stream().cuda_stream
-    want_k, want_v = kc.clone(), vc.clone()
-    dlens = u32(lens)
-    for b, qn in enumerate(counts):                   # the launch that exists, once per sequence with batches = 1
-        if qn == 0:
-            continue
-        s = starts[b]
-        one = dict(kw)
-        ks, vs = kn[s:s + qn].transpose(0, 1).contiguous(), vn[s:s + qn].transpose(0, 1).contiguous()   # [Hkv, qn, D]
-        if paged:
-            one.update(blockTable=kw["blockTable"][b:])
-            app.dispatch(ks, vs, want_k, want_v, stream=stream, rows=qn, heads=HKV, batches=1, cacheLengths=dlens[b:], **one)
-        else:
-            app.dispatch(ks, vs, want_k[b], want_v[b], stream=stream, rows=qn, heads=HKV, batches=1, cacheLengths=dlens[b:], **one)
-    app.dispatch(kn, vn, kc, vc, stream=stream, rows=max(counts), heads=HKV, batches=len(lens), cacheLengths=dlens, rowStarts=u32(starts),
-                 totalRows=T, **kw)
-    torch.cuda.synchronize()
-    assert torch.equal(bits(kc) if not fp8 else kc, bits(want_k) if not fp8 else want_k), "K cache differs from the per-sequence appends"
-    assert torch.equal(bits(vc) if not fp8 else vc, bits(want_v) if not fp8 else want_v), "V cache differs from the per-sequence appends"
-    sent = 0x5A if fp8 else 3.5
-    assert int((kc != sent).sum()) > 0 and int((want_k != sent).sum()) == int((kc != sent).sum())
-    # the cap and T: rows past them are not appended, and the sequence's rows land qn_b below its length, not its full count
-    kc2, vc2 = torch.full_like(kc, sent), torch.full_like(vc, sent)
-    cap = 20
-    app.dispatch(kn, vn, kc2, vc2, stream=stream, rows=cap, heads=HKV, batches=len(lens), cacheLengths=dlens, rowStarts=u32(starts),
-                 totalRows=starts[-2] + 1, **kw)
-    torch.cuda.synchronize()
-    written = sum(min(n, qn) for n, (_s, qn) in zip(lens, rm.counts_of(starts, starts[-2] + 1, cap)))   # (keys below 0 are dropped)
-    assert int((kc2 != sent).any(dim=-1).sum()) == written * HKV
+    ck.append_is_the_per_sequence_append(ck.RAGGED_BATCH, D, dtype, fp8, paged)
 
 
 def test_append_then_ragged_prefill_in_one_graph():
@@ -321,13 +230,13 @@ def test_append_then_ragged_prefill_in_one_graph():
     to the host and read the starts and lengths on the device"""
     D, dtype, G, fp8 = 128, torch.bfloat16, 8, True
     Hq = HKV * G
-    kn, vn, lens, counts, starts, T, kc, vc, kw = append_case(D, dtype, fp8, True, 5)
+    kn, vn, lens, counts, starts, T, kc, vc, kw = ck.append_case(ck.RAGGED_BATCH, D, dtype, fp8, True, 5)
     fill = kc.clone()
     g = torch.Generator().manual_seed(9)
     q = (torch.rand(T, Hq, D, generator=g) * 2 - 1).to(dtype).cuda()
-    dlens, dstarts = u32(lens), u32(starts)
+    dlens, dstarts = lengths(lens), lengths(starts)
     app, pre = KVCacheAppend(D, PREC[dtype], KVCachePrecision.E4M3), op_of(D, dtype, True)
-    logits = torch.from_numpy(tsg.sink_logits(Hq)).cuda()
+    logits = torch.from_numpy(ck.sink_logits(Hq)).cuda()
     pkw = dict(kw)
     pkw["strides"] = dict(K=kw["strides"]["kCache"], V=kw["strides"]["vCache"])
 

@@ -22,20 +22,19 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import cache_kit as ck  # noqa: E402
 import decode_model as dm  # noqa: E402
 import sink_model as sm  # noqa: E402
-from metal_flash_attention_amd import AttentionDecode, AttentionDecodeFP8, AttentionPrefill, GEMMOperandPrecision as P, KVCachePrecision  # noqa: E402
+from cache_kit import LOG2E, TILE, dev, poisoned  # noqa: E402
+from metal_flash_attention_amd import AttentionDecode  # noqa: E402
 
-LOG2E = 1.4426950408889634
-FLT_MAX = float(np.finfo(np.float32).max)
-SEQS = [(700, 40), (200, 40), (100, 130), (5, 5), (0, 3), (1500, 129)]
-LENS, QLENS = [s[0] for s in SEQS], [s[1] for s in SEQS]
-B, C, RP, HKV, TILE = len(SEQS), 1536, 130, 2, 64
-PREC = {torch.bfloat16: P.BF16, torch.float16: P.FP16}
-SENT_O, SENT_L = -7.25, 12345.5
+BATCH = ck.SINK_BATCH
+SEQS, C, HKV, RP = list(BATCH.SEQS), BATCH.C, BATCH.HKV, BATCH.RP
+LENS, QLENS, B = BATCH.LENS, BATCH.QLENS, BATCH.B
 SETTINGS = [(130, 4), (130, 70), (130, 2000)]                       # (W, S)
-# (D, dtype, G, decode R, e4m3 cache): every value of every dimension with both caches
-VARIANTS = [(64, torch.bfloat16, 1, 1, False), (128, torch.float16, 8, 4, False), (128, torch.bfloat16, 8, 1, True), (64, torch.float16, 1, 4, True)]
+VARIANTS = ck.SINK_VARIANTS                                          # (D, dtype, G, decode R, e4m3 cache)
+base = functools.partial(ck.base, BATCH)
+walked, reference = functools.partial(ck.walked, BATCH), functools.partial(ck.sink_reference, BATCH)
 SEEN = {}
 
 
@@ -48,167 +47,23 @@ def _gpu():
         print("\nsink worst err / bound at margin 1:", {k: round(v, 4) for k, v in SEEN.items()})
 
 
-def lengths(values):
-    return torch.tensor(values, dtype=torch.int32, device="cuda")
-
-
-@functools.lru_cache(maxsize=None)
-def base(D, dtype, fp8, seed=0):
-    """k, v [B, HKV, C, D] (CPU) of the 16-bit type or e4m3, every key a value; per-head scales (float32 numpy) for e4m3, else None"""
-    g = torch.Generator().manual_seed(seed + D + 7 * fp8)
-    rnd = lambda: (torch.rand(B, HKV, C, D, generator=g) * 2 - 1)  # noqa: E731
-    if fp8:
-        rng = np.random.default_rng(seed + D)
-        return (rnd() * 3).to(torch.float8_e4m3fn), (rnd() * 3).to(torch.float8_e4m3fn), (dm.spread_scales(rng, HKV), dm.spread_scales(rng, HKV))
-    return rnd().to(dtype), rnd().to(dtype), (None, None)
-
-
-def sink_logits(Hq, seed=0):
-    """one logit per query head, natural units: a share of the softmax mass of the order of the needles'"""
-    return np.random.default_rng(40 + seed).uniform(1.0, 4.0, Hq).astype(np.float32)
-
-
-def walked(kind, n, qn, G, R, W, S):
-    """[C // 64] bool: the 64-key tiles some workgroup of the sequence walks (from the host's range functions)"""
-    out = np.zeros(C // TILE, dtype=bool)
-    if kind == "decode":
-        ranges = AttentionDecode.sinkPieceRange(n, R, W, S, 1, 0)
-    else:
-        RB, ranges = 128 // G, []
-        for r0 in range(0, min(qn, R), RB):
-            b, _u0, _u1, e, se = AttentionPrefill.sinkTileRange(n, min(qn, R), r0, RB, W, S)
-            ranges += [(0, se * TILE), (b * TILE, e * TILE)]
-    for b, e in ranges:
-        out[b // TILE:-(-min(e, n) // TILE)] = True
-    return out
-
-
-def poison_of(t):
-    return 0x7F if t.dtype == torch.float8_e4m3fn else float("nan")
-
-
-def raw(t):
-    return t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t
-
-
-def poisoned(t, tiles):
-    """a copy with poison in every tile that is not walked (tiles[b]) and at or past LENS[b]"""
-    out = raw(t.clone())
-    for b, n in enumerate(LENS):
-        keep = torch.from_numpy(np.repeat(tiles[b], TILE) & (np.arange(C) < n))
-        out[b][:, ~keep] = poison_of(t)
-    return out.view(t.dtype)
-
-
-def paged_pool(k, v, page, tiles, seed):
-    """shuffled pools [pages, HKV, page, D] that hold the keys of the walked tiles below n_b only, poison everywhere else, and the block
-    table: an entry whose page holds no such key names page `spare`, a page of the pool that is all poison"""
-    rng = np.random.default_rng(seed)
-    D, pps = k.shape[3], C // page
-    total = B * pps + 1
-    spare = total - 1
-    perm = rng.permutation(total - 1)
-    pk = raw(torch.empty((total, HKV, page, D), dtype=k.dtype))
-    pk[:] = poison_of(k)
-    pv = pk.clone()
-    table = np.full((B, pps), spare, dtype=np.int32)
-    for b, n in enumerate(LENS):
-        for i in range(pps):
-            a, e = i * page, min((i + 1) * page, n)
-            if e > a and tiles[b][a // TILE]:
-                pg = int(perm[b * pps + i])
-                table[b, i] = pg
-                pk[pg, :, :e - a] = raw(k)[b, :, a:e]
-                pv[pg, :, :e - a] = raw(v)[b, :, a:e]
-    kw = dict(pageSize=page, blockTable=torch.from_numpy(table).cuda(), blockTableStride=pps, pageStrides=(HKV * page * D, HKV * page * D),
-              strides=dict(K=(D, page * D, 0), V=(D, page * D, 0)))
-    return pk.view(k.dtype).cuda(), pv.view(k.dtype).cuda(), kw
-
-
-def launch(kind, q, k, v, G, *, W=None, S=None, logits=None, out=None, workspace=False, cache_kw=None, scales=(None, None), want_pieces=None,
-           causal=True, entry="sink"):
-    """-> (O, L base-2) (CPU) as the launch left them on sentinel-filled buffers.  entry "sink": the sink entries (W None: window 0);
-    "window": the window entries; "plain": the entries without a window.  k, v on the device"""
-    Bq, Hq, R, D = q.shape
-    fp8 = k.dtype == torch.float8_e4m3fn
-    odt = out or q.dtype
-    o = torch.full((Bq, Hq, R, D), SENT_O, dtype=odt, device="cuda")
-    l = torch.full((Bq, Hq, R), SENT_L, dtype=torch.float32, device="cuda")
-    kw = dict(cache_kw or {})
-    kw.update(rows=R, column=C, heads=Hq, batches=Bq, headsPerKeyValue=G, causal=causal, cacheLengths=lengths(LENS))
+def launch(kind, q, k, v, G, *, W=None, S=None, logits=None, entry="sink", **how):
+    """entry "sink": the sink entries (W None: window 0); "window": the window entries; "plain": the entries without a window"""
+    named = {}
     if entry != "plain" and W is not None:
-        kw.update(window=W)
+        named.update(window=W)
     if entry == "sink":
-        kw.update(sinkTokens=S or 0, sinkLogits=logits)
-    outp = None if out is None else PREC.get(out, P.FP32)
-    if kind == "decode":
-        op = (AttentionDecodeFP8 if fp8 else AttentionDecode)(D, PREC[q.dtype], outp)
-        if fp8:
-            kw.update(keyScale=scales[0], valueScale=scales[1])
-        if workspace:
-            need = op.workspaceSize(**kw)
-            if want_pieces is not None:
-                assert need == want_pieces * Bq * Hq * R * (D + 2) * 4
-                assert want_pieces == 0 or ("x %d pieces" % want_pieces) in op.launchForm(workspace=0x1000, workspaceBytes=need, **kw)
-            if need:
-                kw.update(workspace=torch.empty(need, dtype=torch.uint8, device="cuda"))
-    else:
-        op = AttentionPrefill(D, PREC[q.dtype], outp, cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
-        kw.update(queryLengths=lengths(QLENS))
-        if fp8:
-            kw.update(keyScale=scales[0], valueScale=scales[1])
-    op.dispatch(q.cuda(), k, v, o, l, stream=torch.cuda.current_stream().cuda_stream, **kw)
-    torch.cuda.synchronize()
-    return o.cpu(), l.cpu()
+        named.update(sinkTokens=S or 0, sinkLogits=logits)
+    return ck.launch(BATCH, kind, q, k, v, G, **named, **how)
 
 
 def qlens_of(kind):
     return None if kind == "decode" else QLENS
 
 
-@functools.lru_cache(maxsize=None)
-def reference(kind, D, dtype, G, R, W, S, fp8, with_logits=True, pieces=None, causal=True, qkind="needle"):
-    """(q, sink logits, model, needle info), computed once per case and shared; the model reads the values a cache stands for"""
-    k, v, (ks, vs) = base(D, dtype, fp8)
-    fmt, Hq = dm.fmt_of(dtype), HKV * G
-    sink = sink_logits(Hq, D + G) if with_logits else None
-    info = None
-    if qkind == "needle":
-        seen = k.float().numpy().astype(np.float64) * (ks[None, :, None, None] if fp8 else 1.0)
-        q64, info = sm.needle_queries(seen, LENS, qlens_of(kind), Hq, G, R, W, S, fmt, pieces=pieces, page=16)
-        q = torch.from_numpy(q64).to(dtype)
-        assert torch.equal(q.to(torch.float64), torch.from_numpy(q64))
-    else:
-        q = (torch.rand(B, Hq, R, D, generator=torch.Generator().manual_seed(D + G + W)) * 2 - 1).to(dtype)
-    ref = sm.model(q, k.float(), v.float(), LENS, qlens_of(kind), G, W, S, sink, causal=causal, pieces=pieces, kscale=ks, vscale=vs)
-    return q, sink, ref, info
-
-
-def dev(x):
-    return None if x is None else torch.from_numpy(x).cuda()
-
-
 def hold(kind, o, l, ref, dtype, out, info, tag, sink, W, S, causal=True):
-    """sentinels kept at and past qn; live rows finite; a live row without a visible key holds O = 0 and L = its sink logit (base 2), or
-    -FLT_MAX without logits; every live row inside the bounds"""
-    R = o.shape[2]
-    for b, (n, qn) in enumerate(SEQS):
-        qn = R if kind == "decode" else min(qn, R)
-        assert bool((o[b, :, qn:].float() == SENT_O).all()) and bool((l[b, :, qn:] == SENT_L).all()), f"sequence {b}: rows at or past {qn} were written"
-        assert bool(torch.isfinite(o[b, :, :qn].float()).all()) and bool(torch.isfinite(l[b, :, :qn]).all()), f"sequence {b}: poison reached a live row"
-        lo, lim = sm.frontiers(n, qn, np.arange(qn), W, causal)
-        blind = torch.from_numpy(np.array([sm.visible_keys(int(a), int(e), S).size == 0 for a, e in zip(lo, lim)]))[None, :].expand(o.shape[1], -1)
-        assert not o[b, :, :qn][blind].float().any(), f"sequence {b}: a row without a visible key"
-        if sink is None:
-            assert bool((l[b, :, :qn][blind] == -FLT_MAX).all()), f"sequence {b}: a row without a visible key"
-        else:
-            want = torch.from_numpy(sink)[:, None].expand(-1, qn)[blind] * np.float32(LOG2E)
-            assert torch.allclose(l[b, :, :qn][blind], want, rtol=1e-6, atol=0), f"sequence {b}: a row without a visible key must hold L = its sink logit"
-    fmt = dm.fmt_of(dtype)
-    wo, wl, text = sm.compare(o, l / LOG2E, ref, fmt, "f32" if out == torch.float32 else fmt, LENS, qlens_of(kind), margin=1, info=info)
-    SEEN[tag] = max(SEEN.get(tag, 0.0), wo, wl)
-    print("%s: worst |dO| / bound %.3f, |dL| / bound %.3f at margin 1" % (tag, wo, wl))
-    assert wo <= sm.MARGIN and wl <= sm.MARGIN, text
+    """cache_kit.hold with the blind rows of the frontiers under (W, S): O = 0 and L = the sink logit (base 2), or -FLT_MAX without logits"""
+    ck.hold(BATCH, kind, o, l, ref, dtype, out, info, tag, sm, SEEN, ck.sink_blind(W, S, causal), sink)
 
 
 @pytest.mark.parametrize("variant", range(len(VARIANTS)))
@@ -219,19 +74,20 @@ def test_parity_with_the_model_on_poisoned_caches(kind, setting, variant):
     R = Rd if kind == "decode" else RP
     k, v, scales = base(D, dtype, fp8)
     sd = (dev(scales[0]), dev(scales[1]))
-    tiles = [walked(kind, n, qn, G, R, W, S) for n, qn in SEQS]
+    tiles = walked(kind, G, R, W, S)
+    keep = BATCH.keep(tiles=tiles)
     if (W, S) == (130, 4):
         assert tiles[0][0] and not tiles[0][1:8].any() and tiles[0][8:11].all()   # n = 700: sink tile 0, tiles 1-7 poisoned, the window from tile 8
     if (W, S) == (130, 70):
         assert tiles[0][:2].all() and not tiles[0][2:8].any() and tiles[1][:4].all()   # two sink tiles over a gap; n = 200: the zones touch
     q, sink, ref, info = reference(kind, D, dtype, G, R, W, S, fp8)
     tag = kind + (" e4m3 cache" if fp8 else " 16-bit cache")
-    kd, vd = poisoned(k, tiles).cuda(), poisoned(v, tiles).cuda()
+    kd, vd = poisoned(k, keep).cuda(), poisoned(v, keep).cuda()
     o, l = launch(kind, q, kd, vd, G, W=W, S=S, logits=dev(sink), scales=sd)
     hold(kind, o, l, ref, dtype, dtype, info, tag, sink, W, S)
     o32, l32 = launch(kind, q, kd, vd, G, W=W, S=S, logits=dev(sink), scales=sd, out=torch.float32)   # (unsplit: no workspace is offered)
     hold(kind, o32, l32, ref, dtype, torch.float32, info, tag, sink, W, S)
-    kp, vp, kw = paged_pool(k, v, 16, tiles, seed=setting + 3 * variant)
+    kp, vp, kw = ck.paged_pool(k, v, 16, keep, seed=setting + 3 * variant)
     o2, l2 = launch(kind, q, kp, vp, G, W=W, S=S, logits=dev(sink), scales=sd, cache_kw=kw)
     assert torch.equal(o2.view(torch.int16), o.view(torch.int16)) and torch.equal(l2, l), "paged 16 differs from the contiguous launch"
 
@@ -246,11 +102,12 @@ def test_decode_pieces_one_straddles_the_gap_and_one_is_empty(fp8, R):
     pairs = [AttentionDecode.sinkPieceRange(1500, R, W, S, 3, p) for p in range(3)]
     assert pairs[0][0] == (0, 64) and pairs[0][1][1] > pairs[0][1][0] >= 832, pairs          # piece 0 straddles the gap
     assert AttentionDecode.sinkPieceRange(100, R, W, S, 3, 0) == ((0, 0), (0, 0))               # an empty piece 0
-    tiles = [walked("decode", n, qn, G, R, W, S) for n, qn in SEQS]
+    tiles = walked("decode", G, R, W, S)
+    keep = BATCH.keep(tiles=tiles)
     assert tiles[5][0] and not tiles[5][1:13].any()
     q, sink, ref, info = reference("decode", D, dtype, G, R, W, S, fp8, True, 3)
     for out in (None, torch.float32):
-        o, l = launch("decode", q, poisoned(k, tiles).cuda(), poisoned(v, tiles).cuda(), G, W=W, S=S, logits=dev(sink), out=out, workspace=True,
+        o, l = launch("decode", q, poisoned(k, keep).cuda(), poisoned(v, keep).cuda(), G, W=W, S=S, logits=dev(sink), out=out, workspace=True,
                       want_pieces=3, scales=(dev(scales[0]), dev(scales[1])))
         hold("decode", o, l, ref, dtype, out or dtype, info, "decode pieces" + (" e4m3" if fp8 else ""), sink, W, S)
 
@@ -266,7 +123,7 @@ def test_byte_identities(kind, fp8):
     sd = (dev(scales[0]), dev(scales[1]))
     q = reference(kind, D, dtype, G, R, 130, 4, fp8, qkind="uniform")[0]
     zeros = [np.ones(C // TILE, dtype=bool)] * B
-    kd, vd = poisoned(k, zeros).cuda(), poisoned(v, zeros).cuda()
+    kd, vd = poisoned(k, BATCH.keep(tiles=zeros)).cuda(), poisoned(v, BATCH.keep(tiles=zeros)).cuda()
     never = torch.full((HKV * G,), -1e30, dtype=torch.float32, device="cuda")
     sees = torch.zeros((B, HKV * G, R), dtype=torch.bool)
     for b, (n, qn) in enumerate(SEQS):
@@ -296,7 +153,8 @@ def test_the_fused_logit_against_what_a_caller_could_do_from_l(kind, causal):
     k, v, _ = base(D, dtype, False)
     q, sink, ref, _info = reference(kind, D, dtype, G, R, 0, 0, False, True, None, causal, "uniform")
     tiles = [np.ones(C // TILE, dtype=bool)] * B
-    kd, vd = poisoned(k, tiles).cuda(), poisoned(v, tiles).cuda()
+    keep = BATCH.keep(tiles=tiles)
+    kd, vd = poisoned(k, keep).cuda(), poisoned(v, keep).cuda()
     o, l = launch(kind, q, kd, vd, G, logits=dev(sink), out=torch.float32, causal=causal)
     hold(kind, o, l, ref, dtype, torch.float32, None, kind + " logits only", sink, 0, 0, causal)
     po, pl = launch(kind, q, kd, vd, G, out=torch.float32, causal=causal, entry="plain")

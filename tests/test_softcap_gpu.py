@@ -1,7 +1,7 @@
 """GPU test: logit soft-capping over a KV cache through the C ABI of include/mfa_softcap.h (the softcap= keyword of AttentionDecode,
 AttentionDecodeFP8 and AttentionPrefill, ragged included).
 
-The batch, the caches and the poison are tests/test_sink_gpu.py's (its helpers are imported, not copied): sequences (n, qn) = (700, 40),
+The batch is tests/test_sink_gpu.py's, the caches, the poison, the launch and the check tests/cache_kit.py's: sequences (n, qn) = (700, 40),
 (200, 40), (100, 130), (5, 5), (0, 3), (1500, 129) in caches of 1536 keys; NaN (16-bit) or 0x7f (e4m3) in every key and value at or
 past each length and in every 64-key tile no workgroup walks; paged pools of page 16 whose spare entries name an all-poison page.
 Settings (cap, W, S, sink logits): (30, none, 0, no), (50, 130, 4, yes) and (1, 130, 70, yes) -- the last saturates: the needle keys
@@ -19,21 +19,20 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import cache_kit as ck  # noqa: E402
 import decode_model as dm  # noqa: E402
 import sink_model as sm  # noqa: E402
 import softcap_model as cm  # noqa: E402
-import test_sink_gpu as tsg  # noqa: E402
-from metal_flash_attention_amd import AttentionDecode, AttentionDecodeFP8, AttentionPrefill, GEMMOperandPrecision as P, KVCachePrecision  # noqa: E402
+from cache_kit import LOG2E, dev, poisoned, same, token_major  # noqa: E402
 
-LOG2E, FLT_MAX = tsg.LOG2E, tsg.FLT_MAX
-SEQS, LENS, QLENS, B, C, RP, HKV, TILE = tsg.SEQS, tsg.LENS, tsg.QLENS, tsg.B, tsg.C, tsg.RP, tsg.HKV, tsg.TILE
-PREC, SENT_O, SENT_L = tsg.PREC, tsg.SENT_O, tsg.SENT_L
+BATCH = ck.SINK_BATCH
+SEQS, LENS, QLENS, B, RP, HKV = list(BATCH.SEQS), BATCH.LENS, BATCH.QLENS, BATCH.B, BATCH.RP, BATCH.HKV
 SETTINGS = [(30.0, 0, 0, False), (50.0, 130, 4, True), (1.0, 130, 70, True)]      # (cap, W (0: none), S, sink logits)
 # (D, dtype, G, decode R, e4m3 cache): every value of every dimension with both caches
 VARIANTS = [(64, torch.bfloat16, 1, 1, False), (128, torch.float16, 8, 4, False), (256, torch.bfloat16, 8, 1, True),
             (256, torch.float16, 1, 4, False), (64, torch.float16, 8, 4, True), (128, torch.bfloat16, 1, 1, True)]
+base = functools.partial(ck.base, BATCH)
 SEEN = {}
-base, poisoned, paged_pool, walked, lengths, dev, qlens_of = tsg.base, tsg.poisoned, tsg.paged_pool, tsg.walked, tsg.lengths, tsg.dev, tsg.qlens_of
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -45,58 +44,22 @@ def _gpu():
         print("\nsoftcap worst err / bound at margin 1:", {k: round(v, 4) for k, v in SEEN.items()})
 
 
+def qlens_of(kind):
+    return None if kind == "decode" else QLENS
+
+
 def sink_logits(Hq, cap, seed=0):
     """one logit per query head, natural units, of the order of the cap: beside needles at cap tanh(3) a share of the mass"""
     return (cap * np.random.default_rng(50 + seed).uniform(0.8, 1.1, Hq)).astype(np.float32)
 
 
-def token_major(t):
-    """[B, HKV, C, D] -> the same values in a [B, C, HKV, D] allocation, and the (leadingDimension, headStride, batchStride) of the view"""
-    D = t.shape[3]
-    return t.permute(0, 2, 1, 3).contiguous(), (HKV * D, D, C * HKV * D)
-
-
-def launch(kind, q, k, v, G, *, cap=None, W=0, S=0, logits=None, out=None, workspace=False, cache_kw=None, scales=(None, None), want_pieces=None,
-           ragged=None):
-    """-> (O, L base-2) (CPU) as the launch left them on sentinel-filled buffers.  cap None: the sink entries (the uncapped sibling).
-    ragged (row starts, T): q is packed [T, Hq, D]"""
-    Hq, D = q.shape[-3 if ragged is None else -2], q.shape[-1]
-    fp8 = k.dtype == torch.float8_e4m3fn
-    odt = out or q.dtype
-    if ragged is None:
-        Bq, _Hq, R, _D = q.shape
-        o = torch.full((Bq, Hq, R, D), SENT_O, dtype=odt, device="cuda")
-        l = torch.full((Bq, Hq, R), SENT_L, dtype=torch.float32, device="cuda")
-    else:
-        R, T = RP, q.shape[0]
-        o = torch.full((T, Hq, D), SENT_O, dtype=odt, device="cuda")
-        l = torch.full((Hq, T), SENT_L, dtype=torch.float32, device="cuda")
-    kw = dict(cache_kw or {})
-    kw.update(rows=R, column=C, heads=Hq, batches=B, headsPerKeyValue=G, causal=True, cacheLengths=lengths(LENS))
-    kw.update(window=W, sinkTokens=S, sinkLogits=logits)
+def launch(kind, q, k, v, G, *, cap=None, W=0, S=0, logits=None, want_pieces=None, **how):
+    """cap None: the sink entries (the uncapped sibling).  In pieces, the launch form must name the capped kernels"""
+    named = dict(window=W, sinkTokens=S, sinkLogits=logits)
     if cap is not None:
-        kw.update(softcap=cap)
-    outp = None if out is None else PREC.get(out, P.FP32)
-    if fp8:
-        kw.update(keyScale=scales[0], valueScale=scales[1])
-    if kind == "decode":
-        op = (AttentionDecodeFP8 if fp8 else AttentionDecode)(D, PREC[q.dtype], outp)
-        if workspace:
-            need = op.workspaceSize(**kw)
-            if want_pieces is not None:
-                assert need == want_pieces * B * Hq * R * (D + 2) * 4
-                form = op.launchForm(workspace=0x1000, workspaceBytes=need, **kw)
-                assert ("x %d pieces" % want_pieces) in form and form.startswith("attn_decode%sc_d%d_" % ("8" if fp8 else "16", D)) and "_pieces (" in form
-            kw.update(workspace=torch.empty(need, dtype=torch.uint8, device="cuda"))
-    else:
-        op = AttentionPrefill(D, PREC[q.dtype], outp, cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
-        if ragged is None:
-            kw.update(queryLengths=lengths(QLENS))
-        else:
-            kw.update(rowStarts=lengths(ragged[0]), totalRows=ragged[1])
-    op.dispatch(q.cuda(), k, v, o, l, stream=torch.cuda.current_stream().cuda_stream, **kw)
-    torch.cuda.synchronize()
-    return o.cpu(), l.cpu()
+        named.update(softcap=cap)
+    form = r"attn_decode%sc_d%d_.*_pieces \(" % ("8" if k.dtype == torch.float8_e4m3fn else "16", q.shape[-1])
+    return ck.launch(BATCH, kind, q, k, v, G, want_pieces=want_pieces, want_form=None if want_pieces is None else form, **named, **how)
 
 
 @functools.lru_cache(maxsize=None)
@@ -115,30 +78,8 @@ def reference(kind, D, dtype, G, R, cap, W, S, with_logits, fp8, pieces=None):
 
 
 def hold(kind, o, l, ref, dtype, out, info, tag, sink, W, S):
-    """sentinels kept at and past qn; live rows finite; a live row without a visible key holds O = 0 and L = its sink logit (base 2), or
-    -FLT_MAX without logits; every element of every live row inside the bounds"""
-    R = o.shape[2]
-    for b, (n, qn) in enumerate(SEQS):
-        qn = R if kind == "decode" else min(qn, R)
-        assert bool((o[b, :, qn:].float() == SENT_O).all()) and bool((l[b, :, qn:] == SENT_L).all()), f"sequence {b}: rows at or past {qn} were written"
-        assert bool(torch.isfinite(o[b, :, :qn].float()).all()) and bool(torch.isfinite(l[b, :, :qn]).all()), f"sequence {b}: poison reached a live row"
-        lo, lim = sm.frontiers(n, qn, np.arange(qn), W)
-        blind = torch.from_numpy(np.array([sm.visible_keys(int(a), int(e), S).size == 0 for a, e in zip(lo, lim)]))[None, :].expand(o.shape[1], -1)
-        assert not o[b, :, :qn][blind].float().any(), f"sequence {b}: a row without a visible key"
-        if sink is None:
-            assert bool((l[b, :, :qn][blind] == -FLT_MAX).all()), f"sequence {b}: a row without a visible key"
-        else:
-            want = torch.from_numpy(sink)[:, None].expand(-1, qn)[blind] * np.float32(LOG2E)
-            assert torch.allclose(l[b, :, :qn][blind], want, rtol=1e-6, atol=0), f"sequence {b}: a row without a visible key must hold L = its sink logit"
-    fmt = dm.fmt_of(dtype)
-    wo, wl, text = cm.compare(o, l / LOG2E, ref, fmt, "f32" if out == torch.float32 else fmt, LENS, qlens_of(kind), margin=1, info=info)
-    SEEN[tag] = max(SEEN.get(tag, 0.0), wo, wl)
-    print("%s: worst |dO| / bound %.3f, |dL| / bound %.3f at margin 1" % (tag, wo, wl))
-    assert wo <= cm.MARGIN and wl <= cm.MARGIN, text
-
-
-def same(a, b):
-    return torch.equal(a[0].view(torch.int16), b[0].view(torch.int16)) and torch.equal(a[1], b[1])
+    """cache_kit.hold with the blind rows of the frontiers under (W, S), at this model's bounds"""
+    ck.hold(BATCH, kind, o, l, ref, dtype, out, info, tag, cm, SEEN, ck.sink_blind(W, S), sink)
 
 
 @pytest.mark.parametrize("variant", range(len(VARIANTS)))
@@ -149,12 +90,13 @@ def test_parity_with_the_model_on_poisoned_caches(kind, setting, variant):
     R = Rd if kind == "decode" else RP
     k, v, scales = base(D, dtype, fp8)
     sd = (dev(scales[0]), dev(scales[1]))
-    tiles = [walked(kind, n, qn, G, R, W, S) for n, qn in SEQS]
+    tiles = ck.walked(BATCH, kind, G, R, W, S)
+    keep = BATCH.keep(tiles=tiles)
     if W:
         assert tiles[0][0] and not tiles[0][2:8].any() and tiles[0][8:11].all()   # n = 700: the sink tiles, a poisoned gap, the window from tile 8
     q, sink, ref, info = reference(kind, D, dtype, G, R, cap, W, S, with_logits, fp8)
     tag = "%s %s cache cap %g" % (kind, "e4m3" if fp8 else "16-bit", cap)
-    kd, vd = poisoned(k, tiles), poisoned(v, tiles)
+    kd, vd = poisoned(k, keep), poisoned(v, keep)
     common = dict(cap=cap, W=W, S=S, logits=dev(sink), scales=sd)
     o, l = launch(kind, q, kd.cuda(), vd.cuda(), G, **common)
     hold(kind, o, l, ref, dtype, dtype, info, tag, sink, W, S)
@@ -163,7 +105,7 @@ def test_parity_with_the_model_on_poisoned_caches(kind, setting, variant):
     (kt, strides), (vt, _) = token_major(kd), token_major(vd)
     assert same(launch(kind, q, kt.cuda(), vt.cuda(), G, cache_kw=dict(strides=dict(K=strides, V=strides)), **common), (o, l)), \
         "the token-major strided layout differs from the contiguous launch"
-    kp, vp, kw = paged_pool(k, v, 16, tiles, seed=setting + 3 * variant)
+    kp, vp, kw = ck.paged_pool(k, v, 16, keep, seed=setting + 3 * variant)
     assert same(launch(kind, q, kp, vp, G, cache_kw=kw, **common), (o, l)), "paged 16 differs from the contiguous launch"
 
 
@@ -175,10 +117,11 @@ def test_decode_in_pieces(case):
     cap, W, S, with_logits = SETTINGS[setting]
     W = 640 if W else 0
     k, v, scales = base(D, dtype, fp8)
-    tiles = [walked("decode", n, qn, G, R, W, S) for n, qn in SEQS]
+    tiles = ck.walked(BATCH, "decode", G, R, W, S)
+    keep = BATCH.keep(tiles=tiles)
     q, sink, ref, info = reference("decode", D, dtype, G, R, cap, W, S, with_logits, fp8, pieces)
     for out in (None, torch.float32):
-        o, l = launch("decode", q, poisoned(k, tiles).cuda(), poisoned(v, tiles).cuda(), G, cap=cap, W=W, S=S, logits=dev(sink), out=out, workspace=True,
+        o, l = launch("decode", q, poisoned(k, keep).cuda(), poisoned(v, keep).cuda(), G, cap=cap, W=W, S=S, logits=dev(sink), out=out, workspace=True,
                       want_pieces=pieces, scales=(dev(scales[0]), dev(scales[1])))
         hold("decode", o, l, ref, dtype, out or dtype, info, "decode pieces%s cap %g" % (" e4m3" if fp8 else "", cap), sink, W, S)
 
@@ -189,9 +132,10 @@ def test_ragged_prefill_is_the_padded_capped_launch_byte_for_byte(case):
     cap, W, S, with_logits = SETTINGS[setting]
     k, v, scales = base(D, dtype, fp8)
     sd = (dev(scales[0]), dev(scales[1]))
-    tiles = [walked("prefill", n, qn, G, RP, W, S) for n, qn in SEQS]
+    tiles = ck.walked(BATCH, "prefill", G, RP, W, S)
+    keep = BATCH.keep(tiles=tiles)
     q, sink, _ref, _info = reference("prefill", D, dtype, G, RP, cap, W, S, with_logits, fp8)
-    kd, vd = poisoned(k, tiles).cuda(), poisoned(v, tiles).cuda()
+    kd, vd = poisoned(k, keep).cuda(), poisoned(v, keep).cuda()
     common = dict(cap=cap, W=W, S=S, logits=dev(sink), scales=sd)
     o, l = launch("prefill", q, kd, vd, G, **common)
     counts = [min(qn, RP) for qn in QLENS]
@@ -212,9 +156,10 @@ def test_the_capped_kernels_run(kind):
     cap, W, S, with_logits = SETTINGS[1]
     R = 1 if kind == "decode" else RP
     k, v, _scales = base(D, dtype, fp8)
-    tiles = [walked(kind, n, qn, G, R, W, S) for n, qn in SEQS]
+    tiles = ck.walked(BATCH, kind, G, R, W, S)
+    keep = BATCH.keep(tiles=tiles)
     q, sink, ref, info = reference(kind, D, dtype, G, R, cap, W, S, with_logits, fp8)
-    kd, vd = poisoned(k, tiles).cuda(), poisoned(v, tiles).cuda()
+    kd, vd = poisoned(k, keep).cuda(), poisoned(v, keep).cuda()
     o, l = launch(kind, q, kd, vd, G, cap=cap, W=W, S=S, logits=dev(sink), out=torch.float32)
     uo, ul = launch(kind, q, kd, vd, G, cap=None, W=W, S=S, logits=dev(sink), out=torch.float32)
     bo, bl = cm.bounds(ref, dm.fmt_of(dtype), "f32")

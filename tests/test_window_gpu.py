@@ -24,18 +24,18 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import cache_kit as ck  # noqa: E402
 import decode_model as dm  # noqa: E402
 import window_model as wm  # noqa: E402
-from metal_flash_attention_amd import AttentionDecode, AttentionDecodeFP8, AttentionPrefill, GEMMOperandPrecision as P, KVCachePrecision  # noqa: E402
+from cache_kit import LOG2E, PREC, SENT_L, SENT_O, lengths, poison_of, poisoned, raw, token_major  # noqa: E402
+from metal_flash_attention_amd import AttentionDecode, AttentionDecodeFP8, AttentionPrefill  # noqa: E402
 
-LOG2E = 1.4426950408889634
-FLT_MAX = float(np.finfo(np.float32).max)
 SEQS = [(0, 1), (2, 3), (5, 5), (64, 1), (65, 4), (300, 129), (1500, 40), (100, 200)]
 LENS, QLENS = [s[0] for s in SEQS], [s[1] for s in SEQS]
 B, C, RP, HKV = len(SEQS), 1536, 200, 2
-PREC = {torch.bfloat16: P.BF16, torch.float16: P.FP16}
-SENT_O, SENT_L = -7.25, 12345.5
+BATCH = ck.Batch(tuple(SEQS), C, HKV, RP)
 WINDOWS = [1, 16, 64, 65, 200]
+base = functools.partial(ck.base, BATCH)
 SEEN = {}
 
 
@@ -48,21 +48,6 @@ def _gpu():
         print("\nwindow worst err / bound at margin 1:", {k: round(v, 4) for k, v in SEEN.items()})
 
 
-def lengths(values):
-    return torch.tensor(values, dtype=torch.int32, device="cuda")
-
-
-@functools.lru_cache(maxsize=None)
-def base(D, dtype, fp8, seed=0):
-    """k, v [B, HKV, C, D] (CPU) of the 16-bit type or e4m3, every key a value; per-head scales (float32 numpy) for e4m3, else None"""
-    g = torch.Generator().manual_seed(seed + D + 7 * fp8)
-    rnd = lambda: (torch.rand(B, HKV, C, D, generator=g) * 2 - 1)  # noqa: E731
-    if fp8:
-        rng = np.random.default_rng(seed + D)
-        return (rnd() * 3).to(torch.float8_e4m3fn), (rnd() * 3).to(torch.float8_e4m3fn), (dm.spread_scales(rng, HKV), dm.spread_scales(rng, HKV))
-    return rnd().to(dtype), rnd().to(dtype), (None, None)
-
-
 def first_loaded(kind, n, qn, G, W):
     """the first key any workgroup of the sequence may load under window W (None: no window)"""
     if W is None or n == 0 or qn == 0:
@@ -72,79 +57,9 @@ def first_loaded(kind, n, qn, G, W):
     return AttentionPrefill.windowTileRange(n, qn, 0, 128 // G, W)[0] * 64
 
 
-def poison_of(t):
-    return 0x7F if t.dtype == torch.float8_e4m3fn else float("nan")
-
-
-def raw(t):
-    return t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t
-
-
-def poisoned(t, firsts):
-    """a copy with poison below firsts[b] and at or past LENS[b]"""
-    out = raw(t.clone())
-    for b, n in enumerate(LENS):
-        out[b, :, :firsts[b]] = poison_of(t)
-        out[b, :, n:] = poison_of(t)
-    return out.view(t.dtype)
-
-
-def paged_pool(k, v, page, firsts, seed):
-    """shuffled pools [pages, HKV, page, D] that hold the keys [firsts[b], n_b) only, poison everywhere else, and the block table: an
-    entry whose page holds no such key names page `spare`, a page of the pool that is all poison"""
-    rng = np.random.default_rng(seed)
-    D, pps = k.shape[3], C // page
-    total = B * pps + 1
-    spare = total - 1
-    perm = rng.permutation(total - 1)
-    pk = raw(torch.empty((total, HKV, page, D), dtype=k.dtype))
-    pk[:] = poison_of(k)
-    pv = pk.clone()
-    table = np.full((B, pps), spare, dtype=np.int32)
-    for b, n in enumerate(LENS):
-        for i in range(pps):
-            a, e = max(i * page, firsts[b]), min((i + 1) * page, n)
-            if e > a:
-                pg = int(perm[b * pps + i])
-                table[b, i] = pg
-                pk[pg, :, a - i * page:e - i * page] = raw(k)[b, :, a:e]
-                pv[pg, :, a - i * page:e - i * page] = raw(v)[b, :, a:e]
-    kw = dict(pageSize=page, blockTable=torch.from_numpy(table).cuda(), blockTableStride=pps, pageStrides=(HKV * page * D, HKV * page * D),
-              strides=dict(K=(D, page * D, 0), V=(D, page * D, 0)))
-    return pk.view(k.dtype).cuda(), pv.view(k.dtype).cuda(), kw
-
-
-def launch(kind, q, k, v, G, W, *, out=None, workspace=False, cache_kw=None, scales=(None, None), want_pieces=None):
-    """-> (O, L base-2) (CPU) as the launch left them on sentinel-filled buffers.  W None: the plain launch.  k, v on the device"""
-    Bq, Hq, R, D = q.shape
-    fp8 = k.dtype == torch.float8_e4m3fn
-    odt = out or q.dtype
-    o = torch.full((Bq, Hq, R, D), SENT_O, dtype=odt, device="cuda")
-    l = torch.full((Bq, Hq, R), SENT_L, dtype=torch.float32, device="cuda")
-    kw = dict(cache_kw or {})
-    kw.update(rows=R, column=C, heads=Hq, batches=Bq, headsPerKeyValue=G, causal=True, cacheLengths=lengths(LENS))
-    if W is not None:
-        kw.update(window=W)
-    outp = None if out is None else PREC.get(out, P.FP32)
-    if kind == "decode":
-        op = (AttentionDecodeFP8 if fp8 else AttentionDecode)(D, PREC[q.dtype], outp)
-        if fp8:
-            kw.update(keyScale=scales[0], valueScale=scales[1])
-        if workspace:
-            need = op.workspaceSize(**kw)
-            if want_pieces is not None:
-                assert need == want_pieces * Bq * Hq * R * (D + 2) * 4
-                assert want_pieces == 0 or ("x %d pieces" % want_pieces) in op.launchForm(workspace=0x1000, workspaceBytes=need, **kw)
-            if need:
-                kw.update(workspace=torch.empty(need, dtype=torch.uint8, device="cuda"))
-    else:
-        op = AttentionPrefill(D, PREC[q.dtype], outp, cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
-        kw.update(queryLengths=lengths(QLENS))
-        if fp8:
-            kw.update(keyScale=scales[0], valueScale=scales[1])
-    op.dispatch(q.cuda(), k, v, o, l, stream=torch.cuda.current_stream().cuda_stream, **kw)
-    torch.cuda.synchronize()
-    return o.cpu(), l.cpu()
+def launch(kind, q, k, v, G, W, **how):
+    """W None: the plain launch (no window= keyword)"""
+    return ck.launch(BATCH, kind, q, k, v, G, **({} if W is None else dict(window=W)), **how)
 
 
 def qlens_of(kind):
@@ -173,24 +88,9 @@ def firsts_of(kind, R, G, W):
     return [first_loaded(kind, n, R if kind == "decode" else min(qn, R), G, W) for n, qn in SEQS]
 
 
-def dev_scales(scales):
-    return tuple(None if s is None else torch.from_numpy(s).cuda() for s in scales)
-
-
 def hold(kind, o, l, ref, dtype, out, info, tag):
-    """sentinels kept at and past qn; live rows finite; a live row without a visible key holds O = 0, L = -FLT_MAX; the rest inside the bounds"""
-    R = o.shape[2]
-    for b, (n, qn) in enumerate(SEQS):
-        qn = R if kind == "decode" else min(qn, R)
-        assert bool((o[b, :, qn:].float() == SENT_O).all()) and bool((l[b, :, qn:] == SENT_L).all()), f"sequence {b}: rows at or past {qn} were written"
-        assert bool(torch.isfinite(o[b, :, :qn].float()).all()) and bool(torch.isfinite(l[b, :, :qn]).all()), f"sequence {b}: poison reached a live row"
-        blind = torch.from_numpy(~np.isfinite(ref.L[b, :, :qn]))
-        assert not o[b, :, :qn][blind].float().any() and bool((l[b, :, :qn][blind] == -FLT_MAX).all()), f"sequence {b}: a row without a visible key"
-    fmt = dm.fmt_of(dtype)
-    wo, wl, text = wm.compare(o, l / LOG2E, ref, fmt, "f32" if out == torch.float32 else fmt, LENS, qlens_of(kind), margin=1, info=info)
-    SEEN[tag] = max(SEEN.get(tag, 0.0), wo, wl)
-    print("%s: worst |dO| / bound %.3f, |dL| / bound %.3f at margin 1" % (tag, wo, wl))
-    assert wo <= wm.MARGIN and wl <= wm.MARGIN, text
+    """cache_kit.hold with this file's rule: a live row without a visible key (the model's L is not finite) holds O = 0, L = -FLT_MAX"""
+    ck.hold(BATCH, kind, o, l, ref, dtype, out, info, tag, wm, SEEN, lambda b, n, qn: ~np.isfinite(ref.L[b, :, :qn]))
 
 
 @pytest.mark.parametrize("W", WINDOWS)
@@ -202,7 +102,8 @@ def test_parity_with_the_model_on_poisoned_caches(kind, D, dtype, G, W):
     R = 4 if kind == "decode" else RP
     k, v, _ = base(D, dtype, False)
     firsts = firsts_of(kind, R, G, W)
-    kd, vd = poisoned(k, firsts).cuda(), poisoned(v, firsts).cuda()
+    keep = BATCH.keep(firsts)
+    kd, vd = poisoned(k, keep).cuda(), poisoned(v, keep).cuda()
     for qkind in ("needle", "uniform"):
         q, ref, info = reference(kind, D, dtype, G, R, W, qkind, False)
         for out, ws in ((None, False), (torch.float32, True)):
@@ -220,20 +121,20 @@ def test_layouts_and_e4m3_caches(fp8, kind, case):
     D, dtype, G = (64, 128)[i % 2], (torch.bfloat16, torch.float16)[(i // 2) % 2], (1, 4, 3)[i % 3]
     R = 4 if kind == "decode" else RP
     k, v, scales = base(D, dtype, fp8)
-    sd = dev_scales(scales)
+    sd = ck.dev_scales(scales)
     firsts = firsts_of(kind, R, G, W)
+    keep = BATCH.keep(firsts)
     q, ref, info = reference(kind, D, dtype, G, R, W, "needle", fp8)
-    pk, pv = poisoned(k, firsts), poisoned(v, firsts)
+    pk, pv = poisoned(k, keep), poisoned(v, keep)
     o, l = launch(kind, q, pk.cuda(), pv.cuda(), G, W, scales=sd)
     hold(kind, o, l, ref, dtype, dtype, info, kind + (" e4m3 cache" if fp8 else " 16-bit cache"))
     for page in (16, 256):
-        kp, vp, kw = paged_pool(k, v, page, firsts, seed=page + i)
+        kp, vp, kw = ck.paged_pool(k, v, page, keep, seed=page + i)
         o2, l2 = launch(kind, q, kp, vp, G, W, scales=sd, cache_kw=kw)
         assert torch.equal(o2.view(torch.int16), o.view(torch.int16)) and torch.equal(l2, l), f"paged {page} differs from the packed launch"
     # token-major [B, C, HKV, D] (poisoned like the packed one), passed by its strides
-    kt, vt = (raw(t).permute(0, 2, 1, 3).contiguous().cuda().view(t.dtype) for t in (pk, pv))
-    tm = dict(strides=dict(K=(HKV * D, D, C * HKV * D), V=(HKV * D, D, C * HKV * D)))
-    o3, l3 = launch(kind, q, kt, vt, G, W, scales=sd, cache_kw=tm)
+    (kt, st), (vt, _) = token_major(pk), token_major(pv)
+    o3, l3 = launch(kind, q, kt.cuda(), vt.cuda(), G, W, scales=sd, cache_kw=dict(strides=dict(K=st, V=st)))
     assert torch.equal(o3.view(torch.int16), o.view(torch.int16)) and torch.equal(l3, l), "token-major differs from the packed launch"
 
 
@@ -244,7 +145,7 @@ def test_zero_batch_stride_is_the_packed_launch(fp8, kind):
     D, dtype, G, W = 128, torch.bfloat16, 4, 65
     R = 4 if kind == "decode" else RP
     k, v, scales = base(D, dtype, fp8)
-    sd = dev_scales(scales)
+    sd = ck.dev_scales(scales)
     q, _ref, _info = reference(kind, D, dtype, G, R, W, "uniform", fp8)
     one = [raw(t)[6:7].clone() for t in (k, v)]
     for t in one:
@@ -266,13 +167,12 @@ def test_a_window_past_every_key_is_the_plain_launch_byte_for_byte(kind, fp8, pa
     R = 4 if kind == "decode" else RP
     W = C + R
     k, v, scales = base(D, dtype, fp8)
-    sd = dev_scales(scales)
+    sd = ck.dev_scales(scales)
     q, _ref, _info = reference(kind, D, dtype, G, R, 65, "uniform", fp8)
-    zeros = [0] * B
     if paged:
-        kd, vd, kw = paged_pool(k, v, 16, zeros, seed=3)
+        kd, vd, kw = ck.paged_pool(k, v, 16, BATCH.keep(), seed=3)
     else:
-        kd, vd, kw = poisoned(k, zeros).cuda(), poisoned(v, zeros).cuda(), None
+        kd, vd, kw = poisoned(k, BATCH.keep()).cuda(), poisoned(v, BATCH.keep()).cuda(), None
     op = (AttentionDecodeFP8 if fp8 else AttentionDecode)(D, PREC[dtype]) if kind == "decode" else AttentionPrefill(D, PREC[dtype])
     form = op.launchForm(window=W, rows=R, column=C, heads=HKV * G, batches=B, headsPerKeyValue=G, cacheLengths=0x1000)
     assert form.split(" ")[0] in ("attn_decode16w_d128_f16_single", "attn_decode8w_d128_f16_single", "attn_prefill16w_d128_f16"), form
@@ -289,11 +189,12 @@ def test_decode_pieces_some_of_them_empty(fp8, R):
     D, dtype, G, W = (128, torch.bfloat16, 4, 700) if R == 4 else (64, torch.float16, 3, 700)
     k, v, scales = base(D, dtype, fp8)
     firsts = firsts_of("decode", R, G, W)
+    keep = BATCH.keep(firsts)
     assert any(AttentionDecode.windowPieceRange(n, R, W, 3, p)[0] == AttentionDecode.windowPieceRange(n, R, W, 3, p)[1] for n in LENS[1:] for p in range(3))
     assert firsts[6] == 768   # 1500 keys: the window starts in tile 12
     q, ref, info = reference("decode", D, dtype, G, R, W, "needle", fp8, 3)
     for out in (None, torch.float32):
-        o, l = launch("decode", q, poisoned(k, firsts).cuda(), poisoned(v, firsts).cuda(), G, W, out=out, workspace=True, want_pieces=3, scales=dev_scales(scales))
+        o, l = launch("decode", q, poisoned(k, keep).cuda(), poisoned(v, keep).cuda(), G, W, out=out, workspace=True, want_pieces=3, scales=ck.dev_scales(scales))
         hold("decode", o, l, ref, dtype, out or dtype, info, "decode pieces" + (" e4m3" if fp8 else ""))
 
 
@@ -303,7 +204,8 @@ def test_decode_and_prefill_agree_on_the_same_buffers():
     D, dtype, G, R, W = 128, torch.bfloat16, 4, 4, 65
     k, v, _ = base(D, dtype, False)
     firsts = [min(a, b) for a, b in zip(firsts_of("decode", R, G, W), [first_loaded("prefill", n, R, G, W) for n in LENS])]
-    kd, vd = poisoned(k, firsts).cuda(), poisoned(v, firsts).cuda()
+    keep = BATCH.keep(firsts)
+    kd, vd = poisoned(k, keep).cuda(), poisoned(v, keep).cuda()
     q, ref, info = reference("decode", D, dtype, G, R, W, "needle", False)
     o, l = launch("decode", q, kd, vd, G, W)
     hold("decode", o, l, ref, dtype, dtype, info, "decode 16-bit cache")

@@ -146,46 +146,78 @@ def _merge(parts):
     return mstar, lt, ot
 
 
-def emulated(q, k, v, lens, qlens, G, W, fmt, *, pieces=None, kscale=None, vscale=None, piece_range=None, tile_range=None):
-    """the windowed attention with the kernels' roundings and order of sums -> (O before the store's rounding [B, Hq, R, D], L natural).
-    decode: per piece of the window range the four waves take its 32-key steps in turn, merge, and the pieces are combined.  prefill:
-    one wave walks every step of the block's tiles [begin, end) in order.  P is rounded to the 16-bit type against the running maximum,
-    l sums the unrounded p, the maximum sees visible keys only."""
+def _fold(part, s2):
+    """the sink logit (base-2 units, [rows]) joins a state (m, l, o): what piece 0 publishes, and what the final normalisation does"""
+    m, l, o = part
+    mn = np.maximum(m, s2)
+    c = np.where(np.isfinite(m), np.exp2(np.where(np.isfinite(m), m, 0.0) - mn), 0.0)
+    return mn, l * c + np.exp2(s2 - mn), o * c[:, None]
+
+
+def scaled_scores(kscale, G, D):
+    """the score function of the uncapped kernels: raw dot products x keyScale log2(e) / sqrt(D), -inf where masked"""
+    return lambda raw, vis, b, h, rows: np.where(vis, raw * ((1.0 if kscale is None else float(kscale[h // G])) * dm.LOG2E / math.sqrt(D)), -np.inf)
+
+
+def emulated_walk(q, k, v, lens, qlens, G, fmt, visible, steps, score, *, logits=None, vscale=None):
+    """the one walk of the window, sink and soft-cap emulations -> (O before the store's rounding [B, Hq, R, D], L natural).  Per
+    workgroup (wm.blocks_of) and query head: visible(n, qn, rows, npad) is the mask [rows, npad]; steps(n, qn, r0) the 32-key steps
+    [piece][wave][key0]; score(raw, vis, b, h, rows) the base-2 scores, -inf where masked.  A piece's waves merge, the pieces are
+    combined; piece 0 folds the sink logit in, unsplit launches apply it at the final normalisation.  P is rounded to the 16-bit type
+    against the running maximum, l sums the unrounded p, the maximum sees visible keys only."""
     q, k, v = dm.f64(q), dm.f64(k), dm.f64(v)
     B, Hq, R, D = q.shape
-    Hkv = Hq // G
     kind = "decode" if qlens is None else "prefill"
-    ks = np.ones(Hkv) if kscale is None else np.asarray(kscale, dtype=np.float64)
-    vs = np.ones(Hkv) if vscale is None else np.asarray(vscale, dtype=np.float64)
-    tr = tile_range or library_tile_range
+    vs = np.ones(Hq // G) if vscale is None else np.asarray(vscale, dtype=np.float64)
     O = np.zeros((B, Hq, R, D))
     L = np.full((B, Hq, R), -np.inf)
     for b in range(B):
         n, qn = int(lens[b]), R if qlens is None else min(int(qlens[b]), R)
-        if n == 0 or qn == 0:
+        if qn == 0:
             continue
-        npad = (-(-n // TILE)) * TILE
-        cols = np.arange(npad)[None, :]
+        npad = (-(-max(n, 1) // TILE)) * TILE
         for r0, r1 in blocks_of(kind, qn, G):
-            lo, lim = frontiers(n, qn, np.arange(r0, r1), W)
-            vis = (cols >= lo[:, None]) & (cols < lim[:, None])
-            if kind == "decode":
-                waves = [[list(range(pb + w * STEP, pe, WAVES * STEP)) for w in range(WAVES)] for pb, pe in piece_ranges(n, R, W, pieces, piece_range)]
-            else:
-                bt, _u0, _u1, et = tr(n, qn, r0, ROWS // G, W)
-                waves = [[list(range(bt * TILE, et * TILE, STEP))]]
+            vis = visible(n, qn, np.arange(r0, r1), npad)
+            waves = steps(n, qn, r0)
             for h in range(Hq):
                 j = h // G
                 K, V = np.zeros((npad, D)), np.zeros((npad, D))
                 K[:n], V[:n] = k[b, j, :n], v[b, j, :n]
-                S2 = np.where(vis, (q[b, h, r0:r1] @ K.T) * (ks[j] * dm.LOG2E / math.sqrt(D)), -np.inf)
-                published = [_merge([_walk(S2, V, steps, fmt) for steps in piece]) if len(piece) > 1 else _walk(S2, V, piece[0], fmt) for piece in waves]
+                S2 = score(q[b, h, r0:r1] @ K.T, vis, b, h, slice(r0, r1))
+                published = [_merge([_walk(S2, V, w, fmt) for w in piece]) if len(piece) > 1 else _walk(S2, V, piece[0], fmt) for piece in waves]
+                s2 = None if logits is None else np.full(r1 - r0, float(logits[h]) * dm.LOG2E)
+                if s2 is not None and len(published) > 1:
+                    published[0] = _fold(published[0], s2)
                 mstar, lt, ot = _merge(published) if len(published) > 1 else published[0]
+                if s2 is not None and len(published) == 1:
+                    mstar, lt, ot = _fold((mstar, lt, ot), s2)
                 seen = lt > 0
                 l0 = np.where(seen, lt, 1.0)
                 O[b, h, r0:r1] = np.where(seen[:, None], ot * vs[j] / l0[:, None], 0.0)
                 L[b, h, r0:r1] = np.where(seen, (np.where(seen, mstar, 0.0) + np.log2(l0)) / dm.LOG2E, -np.inf)
     return O, L
+
+
+def emulated(q, k, v, lens, qlens, G, W, fmt, *, pieces=None, kscale=None, vscale=None, piece_range=None, tile_range=None):
+    """the windowed attention with the kernels' roundings and order of sums: emulated_walk over the window's ranges.  decode: per piece
+    of the window range the four waves take its 32-key steps in turn.  prefill: one wave walks every step of the block's tiles
+    [begin, end) in order"""
+    R = q.shape[2]
+
+    def visible(n, qn, rows, npad):
+        lo, lim = frontiers(n, qn, rows, W)
+        cols = np.arange(npad)[None, :]
+        return (cols >= lo[:, None]) & (cols < lim[:, None])
+
+    def steps(n, qn, r0):
+        if n == 0:
+            return [[[]]]
+        if qlens is None:
+            return [[list(range(pb + w * STEP, pe, WAVES * STEP)) for w in range(WAVES)] for pb, pe in piece_ranges(n, R, W, pieces, piece_range)]
+        bt, _u0, _u1, et = (tile_range or library_tile_range)(n, qn, r0, ROWS // G, W)
+        return [[list(range(bt * TILE, et * TILE, STEP))]]
+
+    return emulated_walk(q, k, v, lens, qlens, G, fmt, visible, steps, scaled_scores(kscale, G, q.shape[3]), vscale=vscale)
 
 
 # ------------------------------------------------------------------------------------------------------------------ needle inputs
