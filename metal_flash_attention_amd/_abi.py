@@ -177,13 +177,8 @@ class mfa_decode_params(ctypes.Structure):   # include/mfa_decode.h
 MFA_DECODE_KEY_TILE, MFA_DECODE_MAX_PACKED_ROWS, MFA_DECODE_WORKGROUP_TARGET, MFA_DECODE_MAX_PIECES = 64, 32, 512, 64
 _DECODE_BUFS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
 
-DECODE_SYMBOLS = [
+DECODE_SYMBOLS = [   # + its mfa_attention_*_{workspace_size,launch,launch_form,time} rows: the CACHE_FAMILIES loop below
     ("mfa_decode_params_init", None, [ctypes.POINTER(mfa_decode_params)]),
-    ("mfa_attention_decode_workspace_size", ctypes.c_int, [ctypes.POINTER(mfa_decode_params), ctypes.POINTER(ctypes.c_uint64)]),
-    ("mfa_attention_decode_launch", ctypes.c_int, _DECODE_BUFS + [ctypes.POINTER(mfa_decode_params), ctypes.c_void_p]),
-    ("mfa_attention_decode_launch_form", ctypes.c_int, [ctypes.POINTER(mfa_decode_params), ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_decode_time", ctypes.c_int,
-     _DECODE_BUFS + [ctypes.POINTER(mfa_decode_params), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     ("mfa_attention_decode_piece_range", ctypes.c_int,
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
 ]
@@ -207,18 +202,13 @@ class mfa_kv_quant(ctypes.Structure):   # include/mfa_kvcache.h
 MFA_KV_E4M3, MFA_KV_E5M2 = 16, 17
 _QUANT = ctypes.POINTER(mfa_kv_quant)
 
-KVCACHE_SYMBOLS = [
+KVCACHE_SYMBOLS = [   # + its mfa_attention_*_{workspace_size,launch,launch_form,time} rows: the CACHE_FAMILIES loop below
     ("mfa_kv_quantize_e4m3", ctypes.c_uint8, [ctypes.c_float, ctypes.c_float]),
     ("mfa_kv_dequantize_e4m3", ctypes.c_float, [ctypes.c_uint8]),
     ("mfa_kv_append_params_init", None, [ctypes.POINTER(mfa_kv_append_params)]),
     ("mfa_kv_cache_append_launch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(mfa_kv_append_params), ctypes.c_void_p]),
     ("mfa_kv_quant_init", None, [_QUANT]),
-    ("mfa_attention_decode_fp8_workspace_size", ctypes.c_int, [ctypes.POINTER(mfa_decode_params), _QUANT, ctypes.POINTER(ctypes.c_uint64)]),
-    ("mfa_attention_decode_fp8_launch", ctypes.c_int, _DECODE_BUFS + [ctypes.POINTER(mfa_decode_params), _QUANT, ctypes.c_void_p]),
-    ("mfa_attention_decode_fp8_launch_form", ctypes.c_int, [ctypes.POINTER(mfa_decode_params), _QUANT, ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_decode_fp8_time", ctypes.c_int,
-     _DECODE_BUFS + [ctypes.POINTER(mfa_decode_params), _QUANT, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
 ]
 
 class mfa_prefill_params(ctypes.Structure):   # include/mfa_prefill.h
@@ -241,14 +231,10 @@ MFA_PREFILL_KEY_TILE, MFA_PREFILL_PACKED_ROWS, MFA_PREFILL_MAX_GROUP = 64, 128, 
 _PREFILL = ctypes.POINTER(mfa_prefill_params)
 _U32P = ctypes.POINTER(ctypes.c_uint32)
 
-PREFILL_SYMBOLS = [
+PREFILL_SYMBOLS = [   # + its mfa_attention_*_{workspace_size,launch,launch_form,time} rows: the CACHE_FAMILIES loop below
     ("mfa_prefill_params_init", None, [_PREFILL]),
     ("mfa_prefill_params_size", ctypes.c_size_t, []),
     ("mfa_prefill_params_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
-    ("mfa_attention_prefill_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_void_p]),
-    ("mfa_attention_prefill_launch_form", ctypes.c_int, [_PREFILL, ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_prefill_time", ctypes.c_int,
-     _DECODE_BUFS + [_PREFILL, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     ("mfa_attention_prefill_tile_range", ctypes.c_int,
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U32P, _U32P]),
 ]
@@ -257,15 +243,9 @@ _DECODE = ctypes.POINTER(mfa_decode_params)
 _TIMING = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
 
 WINDOW_SYMBOLS = [   # include/mfa_window.h: `window` (uint32, 0 = none) after `quant` (decode; NULL: a 16-bit cache) / `params` (prefill)
-    ("mfa_attention_decode_window_workspace_size", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),
-    ("mfa_attention_decode_window_launch", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, ctypes.c_void_p]),
-    ("mfa_attention_decode_window_launch_form", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_decode_window_time", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, ctypes.c_void_p] + _TIMING),
+    # + its mfa_attention_*_{workspace_size,launch,launch_form,time} rows: the CACHE_FAMILIES loop below
     ("mfa_attention_decode_window_piece_range", ctypes.c_int,
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U32P, _U32P]),
-    ("mfa_attention_prefill_window_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, ctypes.c_void_p]),
-    ("mfa_attention_prefill_window_launch_form", ctypes.c_int, [_PREFILL, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_prefill_window_time", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, ctypes.c_void_p] + _TIMING),
     ("mfa_attention_prefill_window_tile_range", ctypes.c_int,
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U32P, _U32P, _U32P, _U32P]),
 ]
@@ -278,19 +258,13 @@ _SINKS = ctypes.POINTER(mfa_attention_sinks)
 _U32x2 = ctypes.c_uint32 * 2
 
 SINK_SYMBOLS = [   # include/mfa_sink.h: `sinks` (required) after `window` (0 = none)
+    # + its mfa_attention_*_{workspace_size,launch,launch_form,time} rows: the CACHE_FAMILIES loop below
     ("mfa_attention_sinks_init", None, [_SINKS]),
     ("mfa_attention_sinks_size", ctypes.c_size_t, []),
     ("mfa_attention_sinks_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
-    ("mfa_attention_decode_sink_workspace_size", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, ctypes.POINTER(ctypes.c_uint64)]),
-    ("mfa_attention_decode_sink_launch", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, ctypes.c_void_p]),
-    ("mfa_attention_decode_sink_launch_form", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_decode_sink_time", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, ctypes.c_void_p] + _TIMING),
     ("mfa_attention_decode_sink_piece_range", ctypes.c_int,
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_U32x2),
       ctypes.POINTER(_U32x2)]),
-    ("mfa_attention_prefill_sink_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, ctypes.c_void_p]),
-    ("mfa_attention_prefill_sink_launch_form", ctypes.c_int, [_PREFILL, ctypes.c_uint32, _SINKS, ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_prefill_sink_time", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, ctypes.c_void_p] + _TIMING),
     ("mfa_attention_prefill_sink_tile_range", ctypes.c_int, [ctypes.c_uint32] * 7 + [_U32P] * 5),
 ]
 
@@ -301,34 +275,44 @@ class mfa_ragged_rows(ctypes.Structure):   # include/mfa_ragged.h
 _RAGGED = ctypes.POINTER(mfa_ragged_rows)
 
 RAGGED_SYMBOLS = [   # include/mfa_ragged.h: `ragged` (required) after `sinks` (NULL = none)
+    # + its mfa_attention_*_{workspace_size,launch,launch_form,time} rows: the CACHE_FAMILIES loop below
     ("mfa_ragged_rows_init", None, [_RAGGED]),
     ("mfa_ragged_rows_size", ctypes.c_size_t, []),
     ("mfa_ragged_rows_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
-    ("mfa_attention_prefill_ragged_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, ctypes.c_void_p]),
-    ("mfa_attention_prefill_ragged_launch_form", ctypes.c_int, [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_prefill_ragged_time", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, ctypes.c_void_p] + _TIMING),
     ("mfa_attention_prefill_ragged_slots", ctypes.c_int, [ctypes.c_uint32] * 4 + [ctypes.POINTER(ctypes.c_uint64)]),
     ("mfa_attention_prefill_ragged_block", ctypes.c_int, [_U32P] + [ctypes.c_uint32] * 5 + [_U32P, _U32P]),
     ("mfa_kv_cache_append_ragged_launch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(mfa_kv_append_params), _RAGGED, ctypes.c_void_p]),
 ]
 
-_CAP = ctypes.c_float
+SOFTCAP_SYMBOLS = []   # include/mfa_softcap.h: `softcap` (float, 0 = none) after `sinks` (NULL = none) / after `ragged`
+   #    all of it mfa_attention_*_{workspace_size,launch,launch_form,time} rows: the CACHE_FAMILIES loop below
 
-SOFTCAP_SYMBOLS = [   # include/mfa_softcap.h: `softcap` (float, 0 = none) after `sinks` (NULL = none) / after `ragged`
-    ("mfa_attention_decode_softcap_workspace_size", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, _CAP, ctypes.POINTER(ctypes.c_uint64)]),
-    ("mfa_attention_decode_softcap_launch", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_void_p]),
-    ("mfa_attention_decode_softcap_launch_form", ctypes.c_int, [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_decode_softcap_time", ctypes.c_int, _DECODE_BUFS + [_DECODE, _QUANT, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_void_p] + _TIMING),
-    ("mfa_attention_prefill_softcap_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_void_p]),
-    ("mfa_attention_prefill_softcap_launch_form", ctypes.c_int, [_PREFILL, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_prefill_softcap_time", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _CAP, ctypes.c_void_p] + _TIMING),
-    ("mfa_attention_prefill_ragged_softcap_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, _CAP, ctypes.c_void_p]),
-    ("mfa_attention_prefill_ragged_softcap_launch_form", ctypes.c_int,
-     [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, _CAP, ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_prefill_ragged_softcap_time", ctypes.c_int,
-     _DECODE_BUFS + [_PREFILL, ctypes.c_uint32, _SINKS, _RAGGED, _CAP, ctypes.c_void_p] + _TIMING),
-]
+# ---- the laddered entries of the launches over a KV cache, described once:
+#     mfa_attention_<launch>_<family><verb>(*<the verb's head>, params, *<the options the family owns>, *<the verb's tail>)
+# CACHE_FAMILIES: launch -> family -> the options its entries take, in the order of their signatures (each family is an earlier one plus an
+# argument; attention._route picks the first that owns every option a call gives).  CACHE_VERBS: launch -> verb -> (head, tail).
+CACHE_OPTION_TYPES = {"quant": _QUANT, "window": ctypes.c_uint32, "sinks": _SINKS, "ragged": _RAGGED, "softcap": ctypes.c_float}
+CACHE_FAMILIES = {
+    "decode": {"": (), "fp8_": ("quant",), "window_": ("quant", "window"), "sink_": ("quant", "window", "sinks"),
+               "softcap_": ("quant", "window", "sinks", "softcap")},
+    "prefill": {"": (), "window_": ("window",), "sink_": ("window", "sinks"), "ragged_": ("window", "sinks", "ragged"),
+                "softcap_": ("window", "sinks", "softcap"), "ragged_softcap_": ("window", "sinks", "ragged", "softcap")},
+}
+_VERBS = {"workspace_size": ([], [ctypes.POINTER(ctypes.c_uint64)]), "launch": (_DECODE_BUFS, [ctypes.c_void_p]),
+          "launch_form": ([], [ctypes.c_char_p, ctypes.c_size_t]), "time": (_DECODE_BUFS, [ctypes.c_void_p] + _TIMING)}
+CACHE_VERBS = {"decode": _VERBS, "prefill": {verb: _VERBS[verb] for verb in ("launch", "launch_form", "time")}}
+_CACHE_PARAMS = {"decode": _DECODE, "prefill": _PREFILL}
+
+# (the list of the header that declares each family's entries)
+for _symbols, _launch, _family in ((DECODE_SYMBOLS, "decode", ""), (KVCACHE_SYMBOLS, "decode", "fp8_"), (PREFILL_SYMBOLS, "prefill", ""),
+                                   (WINDOW_SYMBOLS, "decode", "window_"), (WINDOW_SYMBOLS, "prefill", "window_"),
+                                   (SINK_SYMBOLS, "decode", "sink_"), (SINK_SYMBOLS, "prefill", "sink_"), (RAGGED_SYMBOLS, "prefill", "ragged_"),
+                                   (SOFTCAP_SYMBOLS, "decode", "softcap_"), (SOFTCAP_SYMBOLS, "prefill", "softcap_"),
+                                   (SOFTCAP_SYMBOLS, "prefill", "ragged_softcap_")):
+    _own = [CACHE_OPTION_TYPES[option] for option in CACHE_FAMILIES[_launch][_family]]
+    _symbols += [(f"mfa_attention_{_launch}_{_family}{verb}", ctypes.c_int, head + [_CACHE_PARAMS[_launch]] + _own + tail)
+                 for verb, (head, tail) in CACHE_VERBS[_launch].items()]
 
 SYMBOLS = [
     ("mfa_precision_name", ctypes.c_char_p, [ctypes.c_int]),

@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import ctypes
 import enum
+import itertools
 from typing import Dict, Iterable, Mapping, Optional, Sequence, Tuple, Union
 
 from . import _abi
@@ -448,20 +449,88 @@ def _packed_rows(heads, D):
     return int(heads) * D, D, 0
 
 
-def _fill_shared(p, D, packed, *, rows, column, heads, batches, cacheLengths, pageSize, blockTable, blockTableStride, strides, pageStrides):
-    """the fields mfa_decode_params, mfa_prefill_params and mfa_kv_append_params share.  `packed`: operand name -> the strides of an
-    operand left out of `strides`, in the order of the struct's arrays"""
+def _fill_shared(p, D, operands, packed, *, rows, column, heads, batches, cacheLengths, pageSize, blockTable, blockTableStride, strides, pageStrides):
+    """the fields mfa_decode_params, mfa_prefill_params and mfa_kv_append_params share.  `operands`: their names in the order of the
+    struct's arrays; `packed`: in the same order, the strides of an operand left out of `strides`"""
     p.rows, p.column, p.heads, p.batches, p.headDimension = int(rows), int(column), int(heads), int(batches), D
     p.pageSize, p.cacheLengths = int(pageSize), _pointer(cacheLengths)
     p.blockTable, p.blockTableStride = _pointer(blockTable), int(blockTableStride)
-    for i, (name, default) in enumerate(packed.items()):
-        ld, hs, bs = (strides or {}).get(name, default)
-        p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
+    lds, hss, bss = p.leadingDimension, p.headStride, p.batchStride
+    for i, name in enumerate(operands):
+        ld, hs, bs = strides.get(name, packed[i]) if strides else packed[i]
+        lds[i], hss[i], bss[i] = int(ld), int(hs), int(bs)
     if pageStrides is not None:
         p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
 
 
-class AttentionDecode:
+_OPTIONS = tuple(_abi.CACHE_OPTION_TYPES)   # quant, window, sinks, ragged, softcap: the order every family's signature keeps
+
+
+def _routes(launch):
+    """which options a call gives (a bool per name of _OPTIONS) -> (the entries' name up to the verb, which of _OPTIONS they take; None: none), of the
+    first family of _abi.CACHE_FAMILIES[launch] that owns every given option (each family is an earlier one plus an argument); nothing
+    for options no family of the launch owns"""
+    table = {}
+    for given in itertools.product((False, True), repeat=len(_OPTIONS)):
+        names = {name for name, g in zip(_OPTIONS, given) if g}
+        owners = [(family, own) for family, own in _abi.CACHE_FAMILIES[launch].items() if names <= set(own)]
+        if owners:
+            family, own = owners[0]
+            assert own == tuple(name for name in _OPTIONS if name in own), "a family's arguments keep the order of _OPTIONS"
+            table[given] = ("mfa_attention_" + launch + "_" + family, tuple(name in own for name in _OPTIONS) if own else None)
+    return table
+
+
+def _route(routes, quant, window, sinks, ragged, softcap):
+    """The entries a launch's options reach (`routes`: _routes of the launch) -> (their name up to the verb, the arguments the family owns).
+    Each option is its ctypes argument, or None when the keywords leave it out (window: a number; a window that IS given may be 0).  An
+    option that is given needs a family that owns it: a cap wins over all, ragged over window and sinks, either sink keyword reaches the
+    sink entries, a window -- 0 too -- the window entries, an e4m3 decode with nothing else fp8_.  What the family owns beyond the given
+    options is passed as none: window 0, a NULL block"""
+    entries, owned = routes[(quant is not None, window is not None, sinks is not None, ragged is not None, softcap is not None)]
+    return entries, itertools.compress((quant, int(window or 0), sinks, ragged, softcap), owned) if owned else ()
+
+
+class _CacheAttention:
+    """what AttentionDecode and AttentionPrefill share: the call of an entry mfa_attention_<LAUNCH>_<family><verb>, and the methods over it"""
+
+    LAUNCH, ROUTES = None, None   # "decode" / "prefill", and its _routes
+    OPERANDS = ("Q", "K", "V", "O")
+
+    def _quant(self, shape):
+        """the mfa_kv_quant block of a launch, by reference, and what it points to: none but for decode over an e4m3 cache"""
+        return None, None
+
+    def _call(self, verb, shape, head=(), tail=()):
+        """mfa_attention_<LAUNCH>_<family><verb>(*head, params, <the family's own arguments>, *tail), the family from the keywords (_route)"""
+        # (a launch without options, the common one, pays three membership tests for them)
+        window = shape.pop("window", None)
+        sinks = _sinks_block(shape) if "sinkTokens" in shape or "sinkLogits" in shape else None
+        cap = _softcap(shape) if "softcap" in shape else None
+        ragged = _ragged_block(shape) if self.LAUNCH == "prefill" and ("rowStarts" in shape or "totalRows" in shape) else None
+        quant, _scales = self._quant(shape)
+        p, _keep = self._params(**shape) if ragged is None else self._params(ragged=ragged, **shape)
+        entries, own = _route(self.ROUTES, quant, window, sinks and ctypes.byref(sinks[0]), ragged and ctypes.byref(ragged[0]), cap)
+        check(getattr(lib(), entries + verb)(*head, ctypes.byref(p), *own, *tail))
+
+    def launchForm(self, **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name and the grid; decode: the pieces
+        kernel, the piece count and the combine kernel, or the single kernel."""
+        out = ctypes.create_string_buffer(512)
+        self._call("launch_form", shape, tail=(out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        self._call("launch", shape, _pointers(q, k, v, o, l), (ctypes.c_void_p(stream or 0),))
+
+    def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
+        ms = ctypes.c_float(0.0)
+        self._call("time", shape, _pointers(q, k, v, o, l), (ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
+        return float(ms.value)
+
+
+class AttentionDecode(_CacheAttention):
     """Decode attention over a KV cache (include/mfa_decode.h; an extension, the reference has no such entry): `rows` new query rows
     per sequence against caches of `heads // headsPerKeyValue` K / V heads, per-sequence lengths on the device, contiguous or paged.
 
@@ -484,17 +553,13 @@ class AttentionDecode:
     softcap=cap (the same four methods): logit soft-capping, include/mfa_softcap.h -- the softmax sees cap tanh(score / cap), cap > 0 in
     natural-log units (Gemma 2: 50).  None: no cap; 0 goes through the soft-cap entries and is the launch without a cap."""
 
-    OPERANDS = ("Q", "K", "V", "O")
+    LAUNCH, ROUTES = "decode", _routes("decode")
 
     def __init__(self, headDimension: int, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16,
                  outputPrecision: Optional[GEMMOperandPrecision] = None):
         self.headDimension = int(headDimension)
         self.precision = GEMMOperandPrecision(precision)
         self.outputPrecision = self.precision if outputPrecision is None else GEMMOperandPrecision(outputPrecision)
-
-    def _quant(self, shape):
-        """the mfa_kv_quant block of a launch: none for a 16-bit cache"""
-        return None, None
 
     def _params(self, *, rows: int, column: int, heads: int = 1, batches: int = 1, headsPerKeyValue: int = 1, causal: bool = True,
                 lStrides: Optional[Sequence[int]] = None, workspace=None, workspaceBytes: Optional[int] = None, cacheLengths=None,
@@ -504,7 +569,7 @@ class AttentionDecode:
         lib().mfa_decode_params_init(ctypes.byref(p))
         D = self.headDimension
         new, cache = _packed(rows, heads, D), _packed(column, max(1, int(heads) // max(1, int(headsPerKeyValue))), D)
-        _fill_shared(p, D, dict(zip(self.OPERANDS, (new, cache, cache, new))), rows=rows, column=column, heads=heads, batches=batches, cacheLengths=cacheLengths,
+        _fill_shared(p, D, self.OPERANDS, (new, cache, cache, new), rows=rows, column=column, heads=heads, batches=batches, cacheLengths=cacheLengths,
                      pageSize=pageSize, blockTable=blockTable, blockTableStride=blockTableStride, strides=strides, pageStrides=pageStrides)
         p.headsPerKeyValue, p.causal = int(headsPerKeyValue), int(bool(causal))
         p.precision, p.outputPrecision = int(self.precision), int(self.outputPrecision)
@@ -515,47 +580,12 @@ class AttentionDecode:
         p.workspaceBytes = int(workspaceBytes)
         return p, (cacheLengths, blockTable, workspace)
 
-    def _call(self, suffix, shape, head=(), tail=()):
-        """mfa_attention_decode_<family><suffix>(*head, params, <the family's own arguments>, *tail).  The family, from the keywords:
-        softcap_ (quant, window, sinks or NULL, softcap) with a softcap that is not None whichever window and sinks, else sink_ (quant,
-        window, sinks) with either sink keyword, else window_ (quant, window) with a window that is not None, else fp8_ (quant) over an
-        e4m3 cache, else the plain entries"""
-        window, sinks, cap = shape.pop("window", None), _sinks_block(shape), _softcap(shape)
-        quant, _scales = self._quant(shape)
-        p, _keep = self._params(**shape)
-        q = None if quant is None else ctypes.byref(quant)
-        if cap is not None:
-            family, own = "softcap_", (q, int(window or 0), None if sinks is None else ctypes.byref(sinks[0]), cap)
-        elif sinks is not None:
-            family, own = "sink_", (q, int(window or 0), ctypes.byref(sinks[0]))
-        elif window is not None:
-            family, own = "window_", (q, int(window))
-        else:
-            family, own = ("", ()) if quant is None else ("fp8_", (q,))
-        check(getattr(lib(), "mfa_attention_decode_" + family + suffix)(*head, ctypes.byref(p), *own, *tail))
-
     def workspaceSize(self, **shape) -> int:
         """Bytes a launch of this shape wants to be cut along the keys (0: the plan has one piece).  Without a workspace the launch
         runs unsplit in one kernel."""
         out = ctypes.c_uint64(0)
         self._call("workspace_size", shape, tail=(ctypes.byref(out),))
         return int(out.value)
-
-    def launchForm(self, **shape) -> str:
-        """What `dispatch` with the same arguments would run (nothing is launched): the pieces kernel, the piece count and the combine
-        kernel, or the single kernel."""
-        out = ctypes.create_string_buffer(512)
-        self._call("launch_form", shape, tail=(out, len(out)))
-        return out.value.decode()
-
-    def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
-        self._call("launch", shape, _pointers(q, k, v, o, l), (ctypes.c_void_p(stream or 0),))
-
-    def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
-        """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
-        ms = ctypes.c_float(0.0)
-        self._call("time", shape, _pointers(q, k, v, o, l), (ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
-        return float(ms.value)
 
     @staticmethod
     def pieceRange(length: int, pieces: int, piece: int) -> Tuple[int, int]:
@@ -604,10 +634,10 @@ class AttentionDecodeFP8(AttentionDecode):
         quant.cachePrecision = self.cachePrecision
         keep = (shape.pop("keyScale", None), shape.pop("valueScale", None))
         quant.keyScale, quant.valueScale = _pointer(keep[0]), _pointer(keep[1])
-        return quant, keep
+        return ctypes.byref(quant), keep
 
 
-class AttentionPrefill:
+class AttentionPrefill(_CacheAttention):
     """Prefill attention over a KV cache (include/mfa_prefill.h): a block of up to `rows` new query rows per sequence -- longer than a
     decode step -- against caches of `heads // headsPerKeyValue` K / V heads that already hold the new tokens; per-sequence cache and
     query lengths on the device, contiguous or paged, 16-bit or FP8.
@@ -630,7 +660,7 @@ class AttentionPrefill:
 
     softcap=cap (the same three, ragged included): logit soft-capping as AttentionDecode's, include/mfa_softcap.h."""
 
-    OPERANDS = ("Q", "K", "V", "O")
+    LAUNCH, ROUTES = "prefill", _routes("prefill")
 
     def __init__(self, headDimension: int, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16,
                  outputPrecision: Optional[GEMMOperandPrecision] = None, cachePrecision: Optional[int] = None):
@@ -649,7 +679,7 @@ class AttentionPrefill:
         new, cache = _packed_rows(heads, D) if ragged else _packed(rows, heads, D), _packed(int(pageSize) or column, kvHeads, D)
         if pageStrides is None and pageSize:
             pageStrides = (kvHeads * int(pageSize) * D,) * 2
-        _fill_shared(p, D, dict(zip(self.OPERANDS, (new, cache, cache, new))), rows=rows, column=column, heads=heads, batches=batches,
+        _fill_shared(p, D, self.OPERANDS, (new, cache, cache, new), rows=rows, column=column, heads=heads, batches=batches,
                      cacheLengths=cacheLengths, pageSize=pageSize, blockTable=blockTable, blockTableStride=blockTableStride, strides=strides,
                      pageStrides=pageStrides)
         p.headsPerKeyValue, p.causal = int(headsPerKeyValue), int(bool(causal))
@@ -663,40 +693,6 @@ class AttentionPrefill:
             p.lHeadStride, p.lBatchStride = int(rows), int(heads) * int(rows)
         p.keyScale, p.valueScale = _pointer(keyScale), _pointer(valueScale)
         return p, (cacheLengths, queryLengths, blockTable, keyScale, valueScale)
-
-    def _call(self, suffix, shape, head=(), tail=()):
-        """mfa_attention_prefill_<family><suffix>(*head, params, <the family's own arguments>, *tail).  The family, from the keywords:
-        ragged_ (window, sinks or NULL, ragged) with rowStarts / totalRows whichever window and sinks, else sink_ (window, sinks) with
-        either sink keyword, else window_ (window) with a window that is not None, else the plain entries; a softcap that is not None
-        takes ragged_softcap_ (window, sinks or NULL, ragged, softcap) or softcap_ (window, sinks or NULL, softcap) in their place"""
-        window, sinks, ragged, cap = shape.pop("window", None), _sinks_block(shape), _ragged_block(shape), _softcap(shape)
-        p, _keep = self._params(ragged=ragged, **shape)
-        s = None if sinks is None else ctypes.byref(sinks[0])
-        if cap is not None:
-            family = "softcap_" if ragged is None else "ragged_softcap_"
-            own = (int(window or 0), s) + (() if ragged is None else (ctypes.byref(ragged[0]),)) + (cap,)
-        elif ragged is not None:
-            family, own = "ragged_", (int(window or 0), s, ctypes.byref(ragged[0]))
-        elif sinks is not None:
-            family, own = "sink_", (int(window or 0), s)
-        else:
-            family, own = ("", ()) if window is None else ("window_", (int(window),))
-        check(getattr(lib(), "mfa_attention_prefill_" + family + suffix)(*head, ctypes.byref(p), *own, *tail))
-
-    def launchForm(self, **shape) -> str:
-        """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name and the grid."""
-        out = ctypes.create_string_buffer(512)
-        self._call("launch_form", shape, tail=(out, len(out)))
-        return out.value.decode()
-
-    def dispatch(self, q, k, v, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
-        self._call("launch", shape, _pointers(q, k, v, o, l), (ctypes.c_void_p(stream or 0),))
-
-    def time(self, q, k, v, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
-        """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
-        ms = ctypes.c_float(0.0)
-        self._call("time", shape, _pointers(q, k, v, o, l), (ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
-        return float(ms.value)
 
     @staticmethod
     def tileRange(length: int, queryLength: int, firstRow: int, blockRows: int, causal: bool = True) -> Tuple[int, int]:
@@ -775,7 +771,7 @@ class KVCacheAppend:
         lib().mfa_kv_append_params_init(ctypes.byref(p))
         D = self.headDimension
         new, cache = _packed_rows(heads, D) if ragged else _packed(rows, heads, D), _packed(int(pageSize) or column, heads, D)
-        _fill_shared(p, D, dict(zip(self.OPERANDS, (new, new, cache, cache))), rows=rows, column=column, heads=heads, batches=batches,
+        _fill_shared(p, D, self.OPERANDS, (new, new, cache, cache), rows=rows, column=column, heads=heads, batches=batches,
                      cacheLengths=cacheLengths, pageSize=pageSize, blockTable=blockTable, blockTableStride=blockTableStride, strides=strides,
                      pageStrides=pageStrides)
         p.precision, p.cachePrecision = int(self.precision), self.cachePrecision

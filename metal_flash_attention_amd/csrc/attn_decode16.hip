@@ -91,9 +91,6 @@ struct DecodePlan {
   DecodeArgs args;
   const DecodeSet *set;
   bool fp8;
-  uint32_t window;      // 0: none
-  Sinks sinks;
-  float softcap;        // 0: none
   int family;           // 0: plain, 1: window, 2: sinks, 3: soft cap (whatever the window and sinks) -- the kernels' first index
   uint64_t tiles;       // what the piece count was chosen from
   uint32_t pieces;      // as the launch runs: 1 without a workspace
@@ -102,12 +99,17 @@ struct DecodePlan {
   // the kernel that reads the cache; its name is what a HIP failure is reported under
   const DecodeKernel &kernel() const { return set->kernel[family][fp8][pieces > 1]; }
   const char *name() const { return kernel().name; }
+  mfa_status prepare(const mfa_decode_params *p, const LaunchOptions &options);
+  hipError_t run(hipStream_t stream) const;
 };
 
-// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `quant` is null for a
-// 16-bit cache; an e4m3 cache puts its own checks first, then the 16-bit launch's.  `window` 0: none; `sinks`: include/mfa_sink.h;
-// `softcap` 0: none, include/mfa_softcap.h
-mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, float softcap, DecodePlan *plan) {
+// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  options.quant is null for
+// a 16-bit cache; an e4m3 cache puts its own checks first, then the 16-bit launch's
+mfa_status DecodePlan::prepare(const mfa_decode_params *p, const LaunchOptions &options) {
+  const mfa_kv_quant *quant = options.quant;
+  const uint32_t window = options.window;
+  const Sinks &sinks = options.sinks;
+  const float softcap = options.softcap;
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   mfa_status allowed = check_window_and_sinks(window, sinks, p->causal != 0);
   if (allowed == MFA_OK) allowed = check_softcap(softcap);
@@ -128,150 +130,94 @@ mfa_status prepare(const mfa_decode_params *p, const mfa_kv_quant *quant, uint32
   }
   if (p->precision == MFA_FP32)
     return fail(MFA_ERR_UNSUPPORTED, "decode attention reads 16-bit caches (MFA_BF16 or MFA_FP16); an FP32 cache has no kernel");
-  if (p->precision != MFA_BF16 && p->precision != MFA_FP16) return fail(MFA_ERR_INVALID_ARGUMENT, "precision must be MFA_FP16 or MFA_BF16");
-  if (p->outputPrecision != p->precision && p->outputPrecision != MFA_FP32)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "outputPrecision must be the inputs' 16-bit type or MFA_FP32");
+  mfa_status st = check_precisions(p->precision, p->outputPrecision);
+  if (st != MFA_OK) return st;
   const DecodeSet *set = nullptr;
   for (const DecodeSet &s : kSets)
     if (s.D == p->headDimension && s.precision == p->precision) set = &s;
   if (!set)
     return fail(MFA_ERR_UNSUPPORTED, "decode attention is compiled for head dimensions 256, 64 and 128, not " + std::to_string(p->headDimension));
-  if (p->rows == 0 || p->column == 0 || p->heads == 0 || p->batches == 0)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "rows, column, heads and batches must be non-zero");
+  if ((st = check_sizes(p)) != MFA_OK) return st;
   const uint32_t G = p->headsPerKeyValue > 1 ? p->headsPerKeyValue : 1;
-  if (p->heads % G != 0)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "heads (" + std::to_string(p->heads) + ") must be a multiple of headsPerKeyValue (" + std::to_string(G) + ")");
+  if ((st = check_group(p->heads, G)) != MFA_OK) return st;
   if ((uint64_t)G * p->rows > MFA_DECODE_MAX_PACKED_ROWS)
     return fail(MFA_ERR_UNSUPPORTED, "decode attention packs headsPerKeyValue x rows = " + std::to_string((uint64_t)G * p->rows) +
                                          " rows into one tile of at most 32; a longer block of query rows is a prefill: use "
                                          "mfa_attention_kernel_launch with headsPerKeyValue, columnLengths and causal");
-  if (!p->cacheLengths) return fail(MFA_ERR_INVALID_ARGUMENT, "cacheLengths is required (device array of `batches` uint32)");
   uint32_t pageShift = 0;
-  mfa_status st = check_paging(p->pageSize, p->blockTable, p->blockTableStride, p->column, &pageShift);
-  if (st != MFA_OK) return st;
-  static const char *names[4] = {"Q", "K", "V", "O"};
-  for (int i = 0; i < 4; ++i) {
-    const int64_t need = (i == 3) ? 4 : 8;   // 16-byte rows of Q, K, V; 8- or 16-byte stores of O
-    const bool kv = i == 1 || i == 2;
-    st = check_operand_strides(names[i], p->headDimension, p->leadingDimension[i], p->headStride[i],
-                               kv && p->pageSize ? p->pageStride[i - 1] : p->batchStride[i], need,
-                               "(16-byte rows for Q, K, V; whole 4-element stores for O)");
-    if (st != MFA_OK) return st;
-  }
-  plan->set = set;
-  plan->fp8 = quant != nullptr;
-  plan->blocks = p->batches * (p->heads / G);
-  plan->window = window;
-  plan->sinks = sinks;
-  plan->softcap = softcap;
-  plan->family = softcap != 0.0f ? 3 : sinks.any() ? 2 : window != 0;
-  plan->tiles = planned_tiles(p->column, p->rows, window, sinks.tokens);
-  plan->planned = choose_pieces(plan->blocks, plan->tiles);
-  plan->pieces = plan->planned;
-  if (!p->workspace) plan->pieces = 1;   // no workspace: one kernel, unsplit
-  if (plan->pieces > 1) {
-    const uint64_t need = pieces_workspace_bytes(plan->pieces, p);
+  if ((st = check_cache_and_strides(p, false, &pageShift)) != MFA_OK) return st;
+  this->set = set;
+  fp8 = quant != nullptr;
+  blocks = p->batches * (p->heads / G);
+  family = softcap != 0.0f ? 3 : sinks.any() ? 2 : window != 0;
+  tiles = planned_tiles(p->column, p->rows, window, sinks.tokens);
+  planned = choose_pieces(blocks, tiles);
+  pieces = planned;
+  if (!p->workspace) pieces = 1;   // no workspace: one kernel, unsplit
+  if (pieces > 1) {
+    const uint64_t need = pieces_workspace_bytes(pieces, p);
     if (p->workspaceBytes < need)
       return fail(MFA_ERR_INVALID_ARGUMENT, "workspace too small: " + std::to_string(p->workspaceBytes) + " bytes, the launch needs " +
                                                 std::to_string(need) + " (mfa_attention_decode_workspace_size)");
     if ((uintptr_t)p->workspace % 16 != 0) return fail(MFA_ERR_INVALID_ARGUMENT, "workspace must be 16-byte aligned");
   }
-  DecodeArgs &a = plan->args;
-  std::memset(&a, 0, sizeof(a));
-  a.lengths = p->cacheLengths;
-  a.table = p->blockTable;
-  a.tableStride = p->blockTableStride;
-  a.ldq = p->leadingDimension[0]; a.hsq = p->headStride[0]; a.bsq = p->batchStride[0];
-  a.ldk = p->leadingDimension[1]; a.hsk = p->headStride[1]; a.bsk = p->batchStride[1]; a.psk = p->pageStride[0];
-  a.ldv = p->leadingDimension[2]; a.hsv = p->headStride[2]; a.bsv = p->batchStride[2]; a.psv = p->pageStride[1];
-  a.ldo = p->leadingDimension[3]; a.hso = p->headStride[3]; a.bso = p->batchStride[3];
-  a.lhs = p->lHeadStride; a.lbs = p->lBatchStride;
-  a.R = p->rows; a.G = G; a.Hq = p->heads; a.Hkv = p->heads / G; a.batches = p->batches; a.column = p->column;
-  a.paged = p->pageSize != 0; a.pageShift = pageShift;
-  a.causal = p->causal != 0; a.outF32 = p->outputPrecision == MFA_FP32;
-  a.pieces = plan->pieces;
-  a.scale2 = 1.44269504089f / std::sqrt((float)p->headDimension);
-  if (plan->pieces > 1) {
+  DecodeArgs &a = args;
+  set_shared_args(a, p, G, pageShift, options);
+  a.R = p->rows; a.Hq = p->heads;
+  a.pieces = pieces;
+  if (pieces > 1) {
     a.wsO = (float *)p->workspace;
-    a.wsML = a.wsO + (uint64_t)plan->pieces * p->batches * p->heads * p->rows * p->headDimension;
+    a.wsML = a.wsO + (uint64_t)pieces * p->batches * p->heads * p->rows * p->headDimension;
   }
   if (quant) { a.keyScale = quant->keyScale; a.valueScale = quant->valueScale; }
-  a.window = window;
-  a.sinkTokens = sinks.tokens;
-  a.sinkLogits = sinks.logits;
-  if (softcap != 0.0f) {
-    a.capIn = 2.0f / softcap;
-    a.capOut = softcap * 1.44269504089f;
-  }
   return MFA_OK;
 }
 
-mfa_status bind(DecodePlan *plan, const void *q, const void *k, const void *v, void *o, float *l) {
-  mfa_status st = check_buffers({q, k, v, o}, "Q, K, V and O");
-  if (st == MFA_OK) st = check_float_arrays({l}, "L");
-  if (st == MFA_OK) st = check_float_arrays({plan->args.keyScale, plan->args.valueScale}, "keyScale and valueScale");
-  if (st == MFA_OK) st = check_float_arrays({plan->args.sinkLogits}, "sinkLogits");
-  if (st != MFA_OK) return st;
-  plan->args.q = (const char *)q; plan->args.k = (const char *)k; plan->args.v = (const char *)v;
-  plan->args.o = (char *)o; plan->args.l = l;
-  return MFA_OK;
-}
-
-hipError_t run(const DecodePlan &plan, hipStream_t stream) {
-  const DecodeSet &s = *plan.set;
+hipError_t DecodePlan::run(hipStream_t stream) const {
+  const DecodeSet &s = *set;
   hipError_t err;
-  if (plan.pieces > 1) {
-    err = launch_kernel(plan.kernel().launch, dim3(plan.blocks * plan.pieces), dim3(256), s.lds, stream, plan.args);
+  if (pieces > 1) {
+    err = launch_kernel(kernel().launch, dim3(blocks * pieces), dim3(256), s.lds, stream, args);
     if (err != hipSuccess) return err;
-    const uint64_t rows = (uint64_t)plan.args.batches * plan.args.Hq * plan.args.R;
-    err = launch_kernel(s.combine.launch, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, plan.args);
+    const uint64_t rows = (uint64_t)args.batches * args.Hq * args.R;
+    err = launch_kernel(s.combine.launch, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args);
   } else {
-    err = launch_kernel(plan.kernel().launch, dim3(plan.blocks), dim3(256), s.lds, stream, plan.args);
+    err = launch_kernel(kernel().launch, dim3(blocks), dim3(256), s.lds, stream, args);
   }
   if (err != hipSuccess) return err;
   return hipGetLastError();
 }
 
 // the bytes of the workspace the launch would split into: 0 for an unsplit plan, whatever workspace the caller may already have bound
-mfa_status decode_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, float softcap, uint64_t *bytes) {
-  if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  *bytes = 0;
+mfa_status decode_workspace_size(const mfa_decode_params *params, const LaunchOptions &options, uint64_t *bytes) {
+  if (bytes) *bytes = 0;
+  const mfa_status refused = entry_check(options, !bytes ? "null argument" : nullptr);
+  if (refused != MFA_OK) return refused;
   if (!params) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   mfa_decode_params probe = *params;
   probe.workspace = nullptr;
   probe.workspaceBytes = 0;
   DecodePlan plan;
-  const mfa_status st = prepare(&probe, quant, window, sinks, softcap, &plan);
+  const mfa_status st = plan.prepare(&probe, options);
   if (st != MFA_OK) return st;
   if (plan.planned > 1) *bytes = pieces_workspace_bytes(plan.planned, params);
   return MFA_OK;
 }
 
-mfa_status decode_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params, const mfa_kv_quant *quant,
-                         uint32_t window, const Sinks &sinks, float softcap, void *stream) {
+mfa_status decode_launch_form(const mfa_decode_params *params, const LaunchOptions &options, char *out, size_t capacity) {
+  if (out && capacity) out[0] = '\0';
   DecodePlan plan;
-  mfa_status st = prepare(params, quant, window, sinks, softcap, &plan);
+  mfa_status st = entry_check(options, !out || capacity == 0 ? "null argument" : nullptr);
+  if (st == MFA_OK) st = plan.prepare(params, options);
   if (st != MFA_OK) return st;
-  st = bind(&plan, q, k, v, o, l);
-  if (st != MFA_OK) return st;
-  const hipError_t err = run(plan, (hipStream_t)stream);
-  if (err != hipSuccess) return hip_fail(err, plan.name());
-  return MFA_OK;
-}
-
-mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, const Sinks &sinks, float softcap,
-                              char *out, size_t capacity) {
-  if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  out[0] = '\0';
-  DecodePlan plan;
-  const mfa_status st = prepare(params, quant, window, sinks, softcap, &plan);
-  if (st != MFA_OK) return st;
+  const uint32_t window = options.window;
+  const Sinks &sinks = options.sinks;
   char text[512];
   const uint32_t M = plan.args.G * plan.args.R;
   // (a windowed launch names its window, its sink tokens and the tiles the piece count was chosen from; bound sink logits, then the
   // soft cap, last)
   char cap[48] = "";
-  if (softcap != 0.0f) std::snprintf(cap, sizeof(cap), ", softcap %g", (double)softcap);
+  if (options.softcap != 0.0f) std::snprintf(cap, sizeof(cap), ", softcap %g", (double)options.softcap);
   const std::string layout = std::string(plan.args.paged ? "paged" : "contiguous") +
                              (window ? ", window " + std::to_string(window) + (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : "") +
                                            ": planned from " + std::to_string(plan.tiles) + " tiles"
@@ -288,16 +234,8 @@ mfa_status decode_launch_form(const mfa_decode_params *params, const mfa_kv_quan
   return MFA_OK;
 }
 
-mfa_status decode_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params, const mfa_kv_quant *quant,
-                       uint32_t window, const Sinks &sinks, float softcap, void *stream, int warmup, int iterations, float *milliseconds) {
-  if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
-  DecodePlan plan;
-  mfa_status st = prepare(params, quant, window, sinks, softcap, &plan);
-  if (st != MFA_OK) return st;
-  st = bind(&plan, q, k, v, o, l);
-  if (st != MFA_OK) return st;
-  return time_launches((hipStream_t)stream, warmup, iterations, milliseconds, plan.name(), [&](hipStream_t s) { return run(plan, s); });
-}
+constexpr auto decode_launch = cache_launch<DecodePlan, mfa_decode_params>;
+constexpr auto decode_time = cache_time<DecodePlan, mfa_decode_params>;
 
 } // namespace
 
@@ -318,20 +256,22 @@ mfa_status mfa_attention_decode_piece_range(uint32_t length, uint32_t pieces, ui
   return MFA_OK;
 }
 
-mfa_status mfa_attention_decode_workspace_size(const mfa_decode_params *params, uint64_t *bytes) { return decode_workspace_size(params, nullptr, 0, Sinks(), 0.0f, bytes); }
+mfa_status mfa_attention_decode_workspace_size(const mfa_decode_params *params, uint64_t *bytes) {
+  return decode_workspace_size(params, LaunchOptions(), bytes);
+}
 
 mfa_status mfa_attention_decode_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                        void *stream) {
-  return decode_launch(q, k, v, o, l, params, nullptr, 0, Sinks(), 0.0f, stream);
+  return decode_launch(q, k, v, o, l, params, LaunchOptions(), stream);
 }
 
 mfa_status mfa_attention_decode_launch_form(const mfa_decode_params *params, char *out, size_t capacity) {
-  return decode_launch_form(params, nullptr, 0, Sinks(), 0.0f, out, capacity);
+  return decode_launch_form(params, LaunchOptions(), out, capacity);
 }
 
 mfa_status mfa_attention_decode_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                      void *stream, int warmup, int iterations, float *milliseconds) {
-  return decode_time(q, k, v, o, l, params, nullptr, 0, Sinks(), 0.0f, stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, LaunchOptions(), stream, warmup, iterations, milliseconds);
 }
 
 // ---- over an e4m3 cache (include/mfa_kvcache.h): the same four with the cache's mfa_kv_quant, which is required
@@ -343,30 +283,21 @@ void mfa_kv_quant_init(mfa_kv_quant *quant) {
 }
 
 mfa_status mfa_attention_decode_fp8_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint64_t *bytes) {
-  if (!bytes) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  *bytes = 0;
-  if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_workspace_size(params, quant, 0, Sinks(), 0.0f, bytes);
+  return decode_workspace_size(params, LaunchOptions().e4m3(quant), bytes);
 }
 
 mfa_status mfa_attention_decode_fp8_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                            const mfa_kv_quant *quant, void *stream) {
-  if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_launch(q, k, v, o, l, params, quant, 0, Sinks(), 0.0f, stream);
+  return decode_launch(q, k, v, o, l, params, LaunchOptions().e4m3(quant), stream);
 }
 
 mfa_status mfa_attention_decode_fp8_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, char *out, size_t capacity) {
-  if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  out[0] = '\0';
-  if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_launch_form(params, quant, 0, Sinks(), 0.0f, out, capacity);
+  return decode_launch_form(params, LaunchOptions().e4m3(quant), out, capacity);
 }
 
 mfa_status mfa_attention_decode_fp8_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                          const mfa_kv_quant *quant, void *stream, int warmup, int iterations, float *milliseconds) {
-  if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
-  if (!quant) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  return decode_time(q, k, v, o, l, params, quant, 0, Sinks(), 0.0f, stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, LaunchOptions().e4m3(quant), stream, warmup, iterations, milliseconds);
 }
 
 // ---- under a sliding window (include/mfa_window.h): the same four with `window` after `quant`, which is null for a 16-bit cache.
@@ -374,23 +305,23 @@ mfa_status mfa_attention_decode_fp8_time(const void *q, const void *k, const voi
 
 mfa_status mfa_attention_decode_window_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
                                                       uint64_t *bytes) {
-  return decode_workspace_size(params, quant, window, Sinks(), 0.0f, bytes);
+  return decode_workspace_size(params, LaunchOptions().cache(quant).within(window), bytes);
 }
 
 mfa_status mfa_attention_decode_window_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                               const mfa_kv_quant *quant, uint32_t window, void *stream) {
-  return decode_launch(q, k, v, o, l, params, quant, window, Sinks(), 0.0f, stream);
+  return decode_launch(q, k, v, o, l, params, LaunchOptions().cache(quant).within(window), stream);
 }
 
 mfa_status mfa_attention_decode_window_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window, char *out,
                                                    size_t capacity) {
-  return decode_launch_form(params, quant, window, Sinks(), 0.0f, out, capacity);
+  return decode_launch_form(params, LaunchOptions().cache(quant).within(window), out, capacity);
 }
 
 mfa_status mfa_attention_decode_window_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                             const mfa_kv_quant *quant, uint32_t window, void *stream, int warmup, int iterations,
                                             float *milliseconds) {
-  return decode_time(q, k, v, o, l, params, quant, window, Sinks(), 0.0f, stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, LaunchOptions().cache(quant).within(window), stream, warmup, iterations, milliseconds);
 }
 
 mfa_status mfa_attention_decode_window_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t pieces, uint32_t piece,
@@ -424,33 +355,23 @@ mfa_status mfa_attention_sinks_offsets(uint32_t *offsets, uint32_t capacity, uin
 
 mfa_status mfa_attention_decode_sink_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
                                                     const mfa_attention_sinks *sinks, uint64_t *bytes) {
-  if (bytes) *bytes = 0;
-  Sinks s;
-  const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : decode_workspace_size(params, quant, window, s, 0.0f, bytes);
+  return decode_workspace_size(params, LaunchOptions().cache(quant).within(window).required_sinks(sinks), bytes);
 }
 
 mfa_status mfa_attention_decode_sink_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                             const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks, void *stream) {
-  Sinks s;
-  const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : decode_launch(q, k, v, o, l, params, quant, window, s, 0.0f, stream);
+  return decode_launch(q, k, v, o, l, params, LaunchOptions().cache(quant).within(window).required_sinks(sinks), stream);
 }
 
 mfa_status mfa_attention_decode_sink_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
                                                  const mfa_attention_sinks *sinks, char *out, size_t capacity) {
-  if (out && capacity) out[0] = '\0';
-  Sinks s;
-  const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : decode_launch_form(params, quant, window, s, 0.0f, out, capacity);
+  return decode_launch_form(params, LaunchOptions().cache(quant).within(window).required_sinks(sinks), out, capacity);
 }
 
 mfa_status mfa_attention_decode_sink_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                           const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks, void *stream,
                                           int warmup, int iterations, float *milliseconds) {
-  Sinks s;
-  const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : decode_time(q, k, v, o, l, params, quant, window, s, 0.0f, stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, LaunchOptions().cache(quant).within(window).required_sinks(sinks), stream, warmup, iterations, milliseconds);
 }
 
 mfa_status mfa_attention_decode_sink_piece_range(uint32_t length, uint32_t rows, uint32_t window, uint32_t sinkTokens, uint32_t pieces,
@@ -466,38 +387,26 @@ mfa_status mfa_attention_decode_sink_piece_range(uint32_t length, uint32_t rows,
 // ---- with a soft cap (include/mfa_softcap.h): the sink entries with `softcap` after `sinks`, which may be NULL here (no sinks).
 // softcap 0 is the launch of the headers below, whichever window and sinks
 
-static mfa_status optional_sinks(const mfa_attention_sinks *block, Sinks *sinks) { return block ? sinks_of(block, sinks) : MFA_OK; }
-
 mfa_status mfa_attention_decode_softcap_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
                                                        const mfa_attention_sinks *sinks, float softcap, uint64_t *bytes) {
-  if (bytes) *bytes = 0;
-  Sinks s;
-  const mfa_status st = optional_sinks(sinks, &s);
-  return st != MFA_OK ? st : decode_workspace_size(params, quant, window, s, softcap, bytes);
+  return decode_workspace_size(params, LaunchOptions().cache(quant).within(window).optional_sinks(sinks).capped(softcap), bytes);
 }
 
 mfa_status mfa_attention_decode_softcap_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                                const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks, float softcap,
                                                void *stream) {
-  Sinks s;
-  const mfa_status st = optional_sinks(sinks, &s);
-  return st != MFA_OK ? st : decode_launch(q, k, v, o, l, params, quant, window, s, softcap, stream);
+  return decode_launch(q, k, v, o, l, params, LaunchOptions().cache(quant).within(window).optional_sinks(sinks).capped(softcap), stream);
 }
 
 mfa_status mfa_attention_decode_softcap_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
                                                     const mfa_attention_sinks *sinks, float softcap, char *out, size_t capacity) {
-  if (out && capacity) out[0] = '\0';
-  Sinks s;
-  const mfa_status st = optional_sinks(sinks, &s);
-  return st != MFA_OK ? st : decode_launch_form(params, quant, window, s, softcap, out, capacity);
+  return decode_launch_form(params, LaunchOptions().cache(quant).within(window).optional_sinks(sinks).capped(softcap), out, capacity);
 }
 
 mfa_status mfa_attention_decode_softcap_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
                                              const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks, float softcap,
                                              void *stream, int warmup, int iterations, float *milliseconds) {
-  Sinks s;
-  const mfa_status st = optional_sinks(sinks, &s);
-  return st != MFA_OK ? st : decode_time(q, k, v, o, l, params, quant, window, s, softcap, stream, warmup, iterations, milliseconds);
+  return decode_time(q, k, v, o, l, params, LaunchOptions().cache(quant).within(window).optional_sinks(sinks).capped(softcap), stream, warmup, iterations, milliseconds);
 }
 
 } // extern "C"

@@ -64,18 +64,18 @@ struct PrefillPlan {
   PrefillArgs args;
   const PrefillSet *set;
   bool fp8;
-  uint32_t window;   // 0: none
-  float softcap;     // 0: none
   int family;        // 0: plain, 1: window, 2: sinks, 3: ragged, 4 / 5: padded / ragged with a soft cap -- the kernels' first index
   uint32_t blocks;   // batches x K/V heads x row blocks; ragged: slots x K/V heads
   const PrefillKernel &kernel() const { return set->kernel[family][fp8]; }
   const char *name() const { return kernel().name; }
+  mfa_status prepare(const mfa_prefill_params *p, const LaunchOptions &options);
+  hipError_t run(hipStream_t stream) const;
 };
 
-// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  `window` 0: none;
-// `sinks`: include/mfa_sink.h; `ragged` non-null: packed rows, include/mfa_ragged.h; `softcap` 0: none, include/mfa_softcap.h
-mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &sinks, PrefillPlan *plan, const mfa_ragged_rows *ragged = nullptr,
-                   float softcap = 0.0f) {
+// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by bind).  options.ragged non-null:
+// packed rows, include/mfa_ragged.h
+mfa_status PrefillPlan::prepare(const mfa_prefill_params *p, const LaunchOptions &options) {
+  const mfa_ragged_rows *ragged = options.ragged;
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   if (ragged) {
     if (!ragged->rowStarts)
@@ -88,16 +88,13 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &si
     if (p->lBatchStride != 0)
       return fail(MFA_ERR_INVALID_ARGUMENT, "lBatchStride must be 0 for a ragged launch: the packed L [heads][totalRows] has no batch axis");
   }
-  mfa_status allowed = check_window_and_sinks(window, sinks, p->causal != 0);
-  if (allowed == MFA_OK) allowed = check_softcap(softcap);
+  mfa_status allowed = check_window_and_sinks(options.window, options.sinks, p->causal != 0);
+  if (allowed == MFA_OK) allowed = check_softcap(options.softcap);
   if (allowed != MFA_OK) return allowed;
   if (p->precision == MFA_FP32)
     return fail(MFA_ERR_UNSUPPORTED, "prefill attention takes a 16-bit Q (precision MFA_BF16 or MFA_FP16); FP32 Q has no kernel");
-  if (p->precision != MFA_BF16 && p->precision != MFA_FP16) return fail(MFA_ERR_INVALID_ARGUMENT, "precision must be MFA_FP16 or MFA_BF16");
-  if (p->outputPrecision != p->precision && p->outputPrecision != MFA_FP32)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "outputPrecision must be the inputs' 16-bit type or MFA_FP32");
-  bool fp8;
-  mfa_status st = check_cache_precision(p->cachePrecision, &fp8);
+  mfa_status st = check_precisions(p->precision, p->outputPrecision);
+  if (st == MFA_OK) st = check_cache_precision(p->cachePrecision, &fp8);
   if (st != MFA_OK) return st;
   if (!fp8 && p->cachePrecision != p->precision)
     return fail(MFA_ERR_INVALID_ARGUMENT, "cachePrecision must be `precision` (a 16-bit cache of Q's type) or MFA_KV_E4M3");
@@ -108,27 +105,13 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &si
     if (s.D == p->headDimension && s.precision == p->precision) set = &s;
   if (!set)
     return fail(MFA_ERR_UNSUPPORTED, "prefill attention is compiled for head dimensions 256, 64 and 128, not " + std::to_string(p->headDimension));
-  if (p->rows == 0 || p->column == 0 || p->heads == 0 || p->batches == 0)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "rows, column, heads and batches must be non-zero");
+  if ((st = check_sizes(p)) != MFA_OK) return st;
   const uint32_t G = p->headsPerKeyValue > 1 ? p->headsPerKeyValue : 1;
   if (G > MFA_PREFILL_MAX_GROUP)
     return fail(MFA_ERR_UNSUPPORTED, "prefill attention packs the headsPerKeyValue query heads of a K/V head into one workgroup: headsPerKeyValue must be "
                                      "at most 32, not " + std::to_string(G));
-  if (p->heads % G != 0)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "heads (" + std::to_string(p->heads) + ") must be a multiple of headsPerKeyValue (" + std::to_string(G) + ")");
-  if (!p->cacheLengths) return fail(MFA_ERR_INVALID_ARGUMENT, "cacheLengths is required (device array of `batches` uint32)");
   uint32_t pageShift = 0;
-  st = check_paging(p->pageSize, p->blockTable, p->blockTableStride, p->column, &pageShift);
-  if (st != MFA_OK) return st;
-  static const char *names[4] = {"Q", "K", "V", "O"};
-  for (int i = 0; i < 4; ++i) {
-    const bool kv = i == 1 || i == 2;
-    const int64_t need = (i == 3) ? 4 : (kv && fp8) ? 16 : 8;   // 16-byte rows of Q, K, V; 8- or 16-byte stores of O
-    st = check_operand_strides(names[i], p->headDimension, p->leadingDimension[i], p->headStride[i],
-                               kv && p->pageSize ? p->pageStride[i - 1] : p->batchStride[i], need,
-                               kv && fp8 ? "(16-byte rows of an e4m3 cache)" : "(16-byte rows for Q, K, V; whole 4-element stores for O)");
-    if (st != MFA_OK) return st;
-  }
+  if ((st = check_group(p->heads, G)) != MFA_OK || (st = check_cache_and_strides(p, fp8, &pageShift)) != MFA_OK) return st;
   const uint32_t RB = MFA_PREFILL_PACKED_ROWS / G;
   const uint64_t rowBlocks = ((uint64_t)p->rows + RB - 1) / RB;
   uint64_t blocks = (uint64_t)p->batches * (p->heads / G) * rowBlocks, slots = 0;
@@ -142,61 +125,55 @@ mfa_status prepare(const mfa_prefill_params *p, uint32_t window, const Sinks &si
       return fail(MFA_ERR_UNSUPPORTED, "slots x K/V heads = " + std::to_string(blocks) + " workgroups exceed one grid (2^31 - 1)");
   } else if (blocks > 0x7fffffffull)
     return fail(MFA_ERR_UNSUPPORTED, "batches x K/V heads x row blocks = " + std::to_string(blocks) + " workgroups exceed one grid (2^31 - 1)");
-  plan->set = set;
-  plan->fp8 = fp8;
-  plan->window = window;
-  plan->softcap = softcap;
-  plan->family = softcap != 0.0f ? (ragged ? 5 : 4) : ragged ? 3 : sinks.any() ? 2 : window != 0;
-  plan->blocks = (uint32_t)blocks;
-  PrefillArgs &a = plan->args;
-  std::memset(&a, 0, sizeof(a));
-  a.lengths = p->cacheLengths;
+  this->set = set;
+  family = options.softcap != 0.0f ? (ragged ? 5 : 4) : ragged ? 3 : options.sinks.any() ? 2 : options.window != 0;
+  this->blocks = (uint32_t)blocks;
+  PrefillArgs &a = args;
+  set_shared_args(a, p, G, pageShift, options);
   a.qlengths = p->queryLengths;
-  a.table = p->blockTable;
-  a.tableStride = p->blockTableStride;
-  a.ldq = p->leadingDimension[0]; a.hsq = p->headStride[0]; a.bsq = p->batchStride[0];
-  a.ldk = p->leadingDimension[1]; a.hsk = p->headStride[1]; a.bsk = p->batchStride[1]; a.psk = p->pageStride[0];
-  a.ldv = p->leadingDimension[2]; a.hsv = p->headStride[2]; a.bsv = p->batchStride[2]; a.psv = p->pageStride[1];
-  a.ldo = p->leadingDimension[3]; a.hso = p->headStride[3]; a.bso = p->batchStride[3];
-  a.lhs = p->lHeadStride; a.lbs = p->lBatchStride;
   a.keyScale = fp8 ? p->keyScale : nullptr;
   a.valueScale = fp8 ? p->valueScale : nullptr;
-  a.rows = p->rows; a.G = G; a.RB = RB; a.rowBlocks = (uint32_t)rowBlocks; a.Hkv = p->heads / G; a.batches = p->batches;
-  a.column = p->column;
-  a.paged = p->pageSize != 0; a.pageShift = pageShift;
-  a.causal = p->causal != 0; a.outF32 = p->outputPrecision == MFA_FP32;
-  a.scale2 = 1.44269504089f / std::sqrt((float)p->headDimension);
-  a.window = window;
-  a.sinkTokens = sinks.tokens;
-  a.sinkLogits = sinks.logits;
+  a.rows = p->rows; a.RB = RB; a.rowBlocks = (uint32_t)rowBlocks;
   if (ragged) {
     a.rowStarts = ragged->rowStarts;
     a.totalRows = ragged->totalRows;
     a.slots = (uint32_t)slots;
   }
-  if (softcap != 0.0f) {
-    a.capIn = 2.0f / softcap;
-    a.capOut = softcap * 1.44269504089f;
-  }
   return MFA_OK;
 }
 
-mfa_status bind(PrefillPlan *plan, const void *q, const void *k, const void *v, void *o, float *l) {
-  mfa_status st = check_buffers({q, k, v, o}, "Q, K, V and O");
-  if (st == MFA_OK) st = check_float_arrays({l}, "L");
-  if (st == MFA_OK) st = check_float_arrays({plan->args.keyScale, plan->args.valueScale}, "keyScale and valueScale");
-  if (st == MFA_OK) st = check_float_arrays({plan->args.sinkLogits}, "sinkLogits");
-  if (st != MFA_OK) return st;
-  plan->args.q = (const char *)q; plan->args.k = (const char *)k; plan->args.v = (const char *)v;
-  plan->args.o = (char *)o; plan->args.l = l;
-  return MFA_OK;
-}
-
-hipError_t run(const PrefillPlan &plan, hipStream_t stream) {
-  const hipError_t err = launch_kernel(plan.kernel().launch, dim3(plan.blocks), dim3(PF_THREADS), plan.set->lds, stream, plan.args);
+hipError_t PrefillPlan::run(hipStream_t stream) const {
+  const hipError_t err = launch_kernel(kernel().launch, dim3(blocks), dim3(PF_THREADS), set->lds, stream, args);
   if (err != hipSuccess) return err;
   return hipGetLastError();
 }
+
+mfa_status prefill_launch_form(const mfa_prefill_params *params, const LaunchOptions &options, char *out, size_t capacity) {
+  if (out && capacity) out[0] = '\0';
+  PrefillPlan plan;
+  mfa_status st = entry_check(options, !out || capacity == 0 ? "null argument" : nullptr);
+  if (st == MFA_OK) st = plan.prepare(params, options);
+  if (st != MFA_OK) return st;
+  const PrefillArgs &a = plan.args;
+  const Sinks &sinks = options.sinks;
+  char text[512];
+  // (a windowed launch names its window, then its sink tokens; bound sink logits, then the soft cap, last)
+  char cap[48] = "";
+  if (options.softcap != 0.0f) std::snprintf(cap, sizeof(cap), ", softcap %g", (double)options.softcap);
+  const std::string tail = (options.window ? ", window " + std::to_string(options.window) : std::string()) +
+                           (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : std::string()) + (sinks.logits ? ", sink logits" : "") + cap;
+  if (options.ragged)
+    std::snprintf(text, sizeof(text), "%s (grid %u = %u slots x %u K/V heads, row blocks of %u rows x %u heads, %u packed rows of %u sequences, at most %u rows each, %s%s)",
+                  plan.name(), plan.blocks, a.slots, a.Hkv, a.RB, a.G, a.totalRows, a.batches, a.rows, a.paged ? "paged" : "contiguous", tail.c_str());
+  else
+    std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s%s)", plan.name(),
+                  plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous", tail.c_str());
+  copy_text(out, capacity, text);
+  return MFA_OK;
+}
+
+constexpr auto prefill_launch = cache_launch<PrefillPlan, mfa_prefill_params>;
+constexpr auto prefill_time = cache_time<PrefillPlan, mfa_prefill_params>;
 
 } // namespace
 
@@ -236,83 +213,34 @@ mfa_status mfa_attention_prefill_tile_range(uint32_t length, uint32_t queryLengt
   return MFA_OK;
 }
 
-static mfa_status prefill_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
-                                 uint32_t window, const Sinks &sinks, void *stream, const mfa_ragged_rows *ragged = nullptr,
-                                 float softcap = 0.0f) {
-  PrefillPlan plan;
-  mfa_status st = prepare(params, window, sinks, &plan, ragged, softcap);
-  if (st != MFA_OK) return st;
-  st = bind(&plan, q, k, v, o, l);
-  if (st != MFA_OK) return st;
-  const hipError_t err = run(plan, (hipStream_t)stream);
-  if (err != hipSuccess) return hip_fail(err, plan.name());
-  return MFA_OK;
-}
-
-static mfa_status prefill_launch_form(const mfa_prefill_params *params, uint32_t window, const Sinks &sinks, char *out, size_t capacity,
-                                      const mfa_ragged_rows *ragged = nullptr, float softcap = 0.0f) {
-  if (!out || capacity == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  out[0] = '\0';
-  PrefillPlan plan;
-  const mfa_status st = prepare(params, window, sinks, &plan, ragged, softcap);
-  if (st != MFA_OK) return st;
-  const PrefillArgs &a = plan.args;
-  char text[512];
-  // (a windowed launch names its window, then its sink tokens; bound sink logits, then the soft cap, last)
-  char cap[48] = "";
-  if (softcap != 0.0f) std::snprintf(cap, sizeof(cap), ", softcap %g", (double)softcap);
-  const std::string tail = (window ? ", window " + std::to_string(window) : std::string()) +
-                           (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : std::string()) + (sinks.logits ? ", sink logits" : "") + cap;
-  if (ragged)
-    std::snprintf(text, sizeof(text), "%s (grid %u = %u slots x %u K/V heads, row blocks of %u rows x %u heads, %u packed rows of %u sequences, at most %u rows each, %s%s)",
-                  plan.name(), plan.blocks, a.slots, a.Hkv, a.RB, a.G, a.totalRows, a.batches, a.rows, a.paged ? "paged" : "contiguous", tail.c_str());
-  else
-    std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s%s)", plan.name(),
-                  plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous", tail.c_str());
-  copy_text(out, capacity, text);
-  return MFA_OK;
-}
-
-static mfa_status prefill_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
-                               uint32_t window, const Sinks &sinks, void *stream, int warmup, int iterations, float *milliseconds,
-                               const mfa_ragged_rows *ragged = nullptr, float softcap = 0.0f) {
-  if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
-  PrefillPlan plan;
-  mfa_status st = prepare(params, window, sinks, &plan, ragged, softcap);
-  if (st != MFA_OK) return st;
-  st = bind(&plan, q, k, v, o, l);
-  if (st != MFA_OK) return st;
-  return time_launches((hipStream_t)stream, warmup, iterations, milliseconds, plan.name(), [&](hipStream_t s) { return run(plan, s); });
-}
-
 mfa_status mfa_attention_prefill_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                         void *stream) {
-  return prefill_launch(q, k, v, o, l, params, 0, Sinks(), stream);
+  return prefill_launch(q, k, v, o, l, params, LaunchOptions(), stream);
 }
 
 mfa_status mfa_attention_prefill_launch_form(const mfa_prefill_params *params, char *out, size_t capacity) {
-  return prefill_launch_form(params, 0, Sinks(), out, capacity);
+  return prefill_launch_form(params, LaunchOptions(), out, capacity);
 }
 
 mfa_status mfa_attention_prefill_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                       void *stream, int warmup, int iterations, float *milliseconds) {
-  return prefill_time(q, k, v, o, l, params, 0, Sinks(), stream, warmup, iterations, milliseconds);
+  return prefill_time(q, k, v, o, l, params, LaunchOptions(), stream, warmup, iterations, milliseconds);
 }
 
 // ---- under a sliding window (include/mfa_window.h): the same three with `window` after `params`; window 0 is the launch without one
 
 mfa_status mfa_attention_prefill_window_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                                uint32_t window, void *stream) {
-  return prefill_launch(q, k, v, o, l, params, window, Sinks(), stream);
+  return prefill_launch(q, k, v, o, l, params, LaunchOptions().within(window), stream);
 }
 
 mfa_status mfa_attention_prefill_window_launch_form(const mfa_prefill_params *params, uint32_t window, char *out, size_t capacity) {
-  return prefill_launch_form(params, window, Sinks(), out, capacity);
+  return prefill_launch_form(params, LaunchOptions().within(window), out, capacity);
 }
 
 mfa_status mfa_attention_prefill_window_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                              uint32_t window, void *stream, int warmup, int iterations, float *milliseconds) {
-  return prefill_time(q, k, v, o, l, params, window, Sinks(), stream, warmup, iterations, milliseconds);
+  return prefill_time(q, k, v, o, l, params, LaunchOptions().within(window), stream, warmup, iterations, milliseconds);
 }
 
 mfa_status mfa_attention_prefill_window_tile_range(uint32_t length, uint32_t queryLength, uint32_t firstRow, uint32_t blockRows, uint32_t window,
@@ -329,25 +257,18 @@ mfa_status mfa_attention_prefill_window_tile_range(uint32_t length, uint32_t que
 
 mfa_status mfa_attention_prefill_sink_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                              uint32_t window, const mfa_attention_sinks *sinks, void *stream) {
-  Sinks s;
-  const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : prefill_launch(q, k, v, o, l, params, window, s, stream);
+  return prefill_launch(q, k, v, o, l, params, LaunchOptions().within(window).required_sinks(sinks), stream);
 }
 
 mfa_status mfa_attention_prefill_sink_launch_form(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks, char *out,
                                                   size_t capacity) {
-  if (out && capacity) out[0] = '\0';
-  Sinks s;
-  const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : prefill_launch_form(params, window, s, out, capacity);
+  return prefill_launch_form(params, LaunchOptions().within(window).required_sinks(sinks), out, capacity);
 }
 
 mfa_status mfa_attention_prefill_sink_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                            uint32_t window, const mfa_attention_sinks *sinks, void *stream, int warmup, int iterations,
                                            float *milliseconds) {
-  Sinks s;
-  const mfa_status st = sinks_of(sinks, &s);
-  return st != MFA_OK ? st : prefill_time(q, k, v, o, l, params, window, s, stream, warmup, iterations, milliseconds);
+  return prefill_time(q, k, v, o, l, params, LaunchOptions().within(window).required_sinks(sinks), stream, warmup, iterations, milliseconds);
 }
 
 mfa_status mfa_attention_prefill_sink_tile_range(uint32_t length, uint32_t queryLength, uint32_t firstRow, uint32_t blockRows, uint32_t causal,
@@ -378,34 +299,20 @@ mfa_status mfa_ragged_rows_offsets(uint32_t *offsets, uint32_t capacity, uint32_
   return MFA_OK;
 }
 
-static mfa_status ragged_of(const mfa_ragged_rows *ragged, const mfa_attention_sinks *block, Sinks *sinks) {
-  if (!ragged)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "null mfa_ragged_rows: the ragged entries require the block (mfa_ragged_rows_init; a padded "
-                                          "launch: the mfa_prefill.h / mfa_window.h / mfa_sink.h entries)");
-  return block ? sinks_of(block, sinks) : MFA_OK;
-}
-
 mfa_status mfa_attention_prefill_ragged_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                                uint32_t window, const mfa_attention_sinks *sinks, const mfa_ragged_rows *ragged, void *stream) {
-  Sinks s;
-  const mfa_status st = ragged_of(ragged, sinks, &s);
-  return st != MFA_OK ? st : prefill_launch(q, k, v, o, l, params, window, s, stream, ragged);
+  return prefill_launch(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).ragged_of(ragged), stream);
 }
 
 mfa_status mfa_attention_prefill_ragged_launch_form(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
                                                     const mfa_ragged_rows *ragged, char *out, size_t capacity) {
-  if (out && capacity) out[0] = '\0';
-  Sinks s;
-  const mfa_status st = ragged_of(ragged, sinks, &s);
-  return st != MFA_OK ? st : prefill_launch_form(params, window, s, out, capacity, ragged);
+  return prefill_launch_form(params, LaunchOptions().within(window).optional_sinks(sinks).ragged_of(ragged), out, capacity);
 }
 
 mfa_status mfa_attention_prefill_ragged_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                              uint32_t window, const mfa_attention_sinks *sinks, const mfa_ragged_rows *ragged, void *stream,
                                              int warmup, int iterations, float *milliseconds) {
-  Sinks s;
-  const mfa_status st = ragged_of(ragged, sinks, &s);
-  return st != MFA_OK ? st : prefill_time(q, k, v, o, l, params, window, s, stream, warmup, iterations, milliseconds, ragged);
+  return prefill_time(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).ragged_of(ragged), stream, warmup, iterations, milliseconds);
 }
 
 mfa_status mfa_attention_prefill_ragged_slots(uint32_t totalRows, uint32_t batches, uint32_t rows, uint32_t blockRows, uint64_t *slots) {
@@ -427,54 +334,38 @@ mfa_status mfa_attention_prefill_ragged_block(const uint32_t *rowStarts, uint32_
 // ---- with a soft cap (include/mfa_softcap.h): the sink entries with `softcap` after `sinks`, the ragged entries with it after
 // `ragged`; a NULL `sinks` is no sinks.  softcap 0 is the launch of the headers below, whichever window, sinks and rows
 
-static mfa_status optional_sinks(const mfa_attention_sinks *block, Sinks *sinks) { return block ? sinks_of(block, sinks) : MFA_OK; }
-
 mfa_status mfa_attention_prefill_softcap_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                                 uint32_t window, const mfa_attention_sinks *sinks, float softcap, void *stream) {
-  Sinks s;
-  const mfa_status st = optional_sinks(sinks, &s);
-  return st != MFA_OK ? st : prefill_launch(q, k, v, o, l, params, window, s, stream, nullptr, softcap);
+  return prefill_launch(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).capped(softcap), stream);
 }
 
 mfa_status mfa_attention_prefill_softcap_launch_form(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
                                                      float softcap, char *out, size_t capacity) {
-  if (out && capacity) out[0] = '\0';
-  Sinks s;
-  const mfa_status st = optional_sinks(sinks, &s);
-  return st != MFA_OK ? st : prefill_launch_form(params, window, s, out, capacity, nullptr, softcap);
+  return prefill_launch_form(params, LaunchOptions().within(window).optional_sinks(sinks).capped(softcap), out, capacity);
 }
 
 mfa_status mfa_attention_prefill_softcap_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
                                               uint32_t window, const mfa_attention_sinks *sinks, float softcap, void *stream, int warmup,
                                               int iterations, float *milliseconds) {
-  Sinks s;
-  const mfa_status st = optional_sinks(sinks, &s);
-  return st != MFA_OK ? st : prefill_time(q, k, v, o, l, params, window, s, stream, warmup, iterations, milliseconds, nullptr, softcap);
+  return prefill_time(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).capped(softcap), stream, warmup, iterations, milliseconds);
 }
 
 mfa_status mfa_attention_prefill_ragged_softcap_launch(const void *q, const void *k, const void *v, void *o, float *l,
                                                        const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
                                                        const mfa_ragged_rows *ragged, float softcap, void *stream) {
-  Sinks s;
-  const mfa_status st = ragged_of(ragged, sinks, &s);
-  return st != MFA_OK ? st : prefill_launch(q, k, v, o, l, params, window, s, stream, ragged, softcap);
+  return prefill_launch(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).ragged_of(ragged).capped(softcap), stream);
 }
 
 mfa_status mfa_attention_prefill_ragged_softcap_launch_form(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
                                                             const mfa_ragged_rows *ragged, float softcap, char *out, size_t capacity) {
-  if (out && capacity) out[0] = '\0';
-  Sinks s;
-  const mfa_status st = ragged_of(ragged, sinks, &s);
-  return st != MFA_OK ? st : prefill_launch_form(params, window, s, out, capacity, ragged, softcap);
+  return prefill_launch_form(params, LaunchOptions().within(window).optional_sinks(sinks).ragged_of(ragged).capped(softcap), out, capacity);
 }
 
 mfa_status mfa_attention_prefill_ragged_softcap_time(const void *q, const void *k, const void *v, void *o, float *l,
                                                      const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
                                                      const mfa_ragged_rows *ragged, float softcap, void *stream, int warmup, int iterations,
                                                      float *milliseconds) {
-  Sinks s;
-  const mfa_status st = ragged_of(ragged, sinks, &s);
-  return st != MFA_OK ? st : prefill_time(q, k, v, o, l, params, window, s, stream, warmup, iterations, milliseconds, ragged, softcap);
+  return prefill_time(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).ragged_of(ragged).capped(softcap), stream, warmup, iterations, milliseconds);
 }
 
 } // extern "C"

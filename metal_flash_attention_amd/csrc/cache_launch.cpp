@@ -48,6 +48,19 @@ mfa_status check_operand_strides(const char *name, uint32_t headDimension, int64
   return check_stride_multiples(name, leadingDimension, headStride, outer, need, why);
 }
 
+mfa_status check_precisions(int precision, int outputPrecision) {
+  if (precision != MFA_BF16 && precision != MFA_FP16) return fail(MFA_ERR_INVALID_ARGUMENT, "precision must be MFA_FP16 or MFA_BF16");
+  if (outputPrecision != precision && outputPrecision != MFA_FP32)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "outputPrecision must be the inputs' 16-bit type or MFA_FP32");
+  return MFA_OK;
+}
+
+mfa_status check_group(uint32_t heads, uint32_t G) {
+  if (heads % G != 0)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "heads (" + std::to_string(heads) + ") must be a multiple of headsPerKeyValue (" + std::to_string(G) + ")");
+  return MFA_OK;
+}
+
 mfa_status check_cache_precision(uint32_t cachePrecision, bool *fp8) {
   if (cachePrecision == MFA_KV_E5M2)
     return fail(MFA_ERR_UNSUPPORTED, "an FP8 KV cache is e4m3 (MFA_KV_E4M3, OCP e4m3fn); e5m2 caches have no kernel");
@@ -69,13 +82,35 @@ mfa_status check_float_arrays(std::initializer_list<const void *> arrays, const 
   return MFA_OK;
 }
 
-mfa_status sinks_of(const mfa_attention_sinks *block, Sinks *sinks) {
-  if (!block)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "null mfa_attention_sinks: the sink entries require the block (mfa_attention_sinks_init; a launch "
-                                          "without sinks: the mfa_window.h entries, or an all-zero block)");
-  sinks->tokens = block->sinkTokens;
-  sinks->logits = block->sinkLogits;
-  return MFA_OK;
+LaunchOptions &LaunchOptions::e4m3(const mfa_kv_quant *block) {
+  quant = block;
+  if (!block && !refusal) refusal = "null argument", refusalFirst = false;
+  return *this;
+}
+
+LaunchOptions &LaunchOptions::required_sinks(const mfa_attention_sinks *block) {
+  if (!block && !refusal)
+    refusal = "null mfa_attention_sinks: the sink entries require the block (mfa_attention_sinks_init; a launch "
+              "without sinks: the mfa_window.h entries, or an all-zero block)";
+  return optional_sinks(block);
+}
+
+LaunchOptions &LaunchOptions::optional_sinks(const mfa_attention_sinks *block) {
+  if (block) sinks.tokens = block->sinkTokens, sinks.logits = block->sinkLogits;
+  return *this;
+}
+
+LaunchOptions &LaunchOptions::ragged_of(const mfa_ragged_rows *block) {
+  ragged = block;
+  if (!block && !refusal)
+    refusal = "null mfa_ragged_rows: the ragged entries require the block (mfa_ragged_rows_init; a padded "
+              "launch: the mfa_prefill.h / mfa_window.h / mfa_sink.h entries)";
+  return *this;
+}
+
+mfa_status entry_check(const LaunchOptions &options, const char *bad) {
+  if (options.refusal && (options.refusalFirst || !bad)) return fail(MFA_ERR_INVALID_ARGUMENT, options.refusal);
+  return bad ? fail(MFA_ERR_INVALID_ARGUMENT, bad) : MFA_OK;
 }
 
 mfa_status check_window_and_sinks(uint32_t window, const Sinks &sinks, bool causal) {

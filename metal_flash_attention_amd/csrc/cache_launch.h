@@ -1,13 +1,21 @@
 // cache_launch.h -- what the host sides of the launches over a KV cache share (attn_decode16.hip, attn_prefill16.hip,
 // kv_cache_append.hip): the checks of paging, operand strides, cache precision and buffer pointers, and of a sliding window and
-// attention sinks (Sinks, sinks_of, check_window_and_sinks: decode and prefill) and of a soft cap (check_softcap), each with ONE wording, so that the same mistake is
-// refused in the same words whichever launch meets it.  hip_fail, copy_text and time_launches also serve mfa_kernel.hip.  Internal, not part of the ABI.  Every check records its message (fail, mfa_internal.h) and returns the status.
+// attention sinks (Sinks, check_window_and_sinks: decode and prefill) and of a soft cap (check_softcap), each with ONE wording, so that
+// the same mistake is refused in the same words whichever launch meets it; the options of a launch as one value (LaunchOptions), and the
+// path every decode and prefill entry takes from it: the checks both launches word alike (check_precisions ... check_cache_and_strides), bind, and the bodies
+// of the launch and time entries (cache_launch, cache_time).  hip_fail, copy_text and time_launches also serve mfa_kernel.hip.
+// Internal, not part of the ABI.  Every check records its message (fail, mfa_internal.h) and returns the status.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <initializer_list>
+#include <string>
 
+#include "../../include/mfa_kvcache.h"
+#include "../../include/mfa_ragged.h"
 #include "../../include/mfa_sink.h"
 #include "mfa_internal.h"
 
@@ -44,12 +52,103 @@ struct Sinks {
   const float *logits = nullptr;
   bool any() const { return tokens != 0 || logits != nullptr; }
 };
-// the block of a sink entry, which requires it (null is refused)
-mfa_status sinks_of(const mfa_attention_sinks *block, Sinks *sinks);
 // sink tokens need a window and causal; a window (0: none) needs causal
 mfa_status check_window_and_sinks(uint32_t window, const Sinks &sinks, bool causal);
 // the soft cap of a launch (include/mfa_softcap.h): 0 is none, anything but a finite positive number is refused
 mfa_status check_softcap(float softcap);
+
+// The options of a launch beside its params: what the entry families of mfa_kvcache.h (fp8_), mfa_window.h, mfa_sink.h, mfa_ragged.h and
+// mfa_softcap.h add to the plain entries, as ONE value that every function below an entry takes.  An entry builds it in one statement
+// from the setters, each of which carries its argument's NULL rule in that family's words; a new option is a member, a setter and the
+// places that read it.
+struct LaunchOptions {
+  const mfa_kv_quant *quant = nullptr;       // decode over an e4m3 cache (prefill says it in its params); null: a 16-bit cache
+  uint32_t window = 0;                       // 0: none
+  Sinks sinks;
+  const mfa_ragged_rows *ragged = nullptr;   // prefill over packed rows; null: padded
+  float softcap = 0.0f;                      // 0: none
+  const char *refusal = nullptr;             // a block the family requires is NULL: what entry_check answers
+  bool refusalFirst = true;                  // ... before the entry's own arguments are looked at (fp8_: after)
+
+  LaunchOptions &e4m3(const mfa_kv_quant *block);                  // the fp8_ entries: required
+  LaunchOptions &cache(const mfa_kv_quant *block) { quant = block; return *this; }   // the later decode entries: NULL is a 16-bit cache
+  LaunchOptions &within(uint32_t keys) { window = keys; return *this; }
+  LaunchOptions &required_sinks(const mfa_attention_sinks *block);   // the sink_ entries
+  LaunchOptions &optional_sinks(const mfa_attention_sinks *block);   // the ragged_ and softcap_ entries: NULL is no sinks
+  LaunchOptions &ragged_of(const mfa_ragged_rows *block);            // the ragged_ entries: required
+  LaunchOptions &capped(float cap) { softcap = cap; return *this; }
+};
+// what an entry answers before its launch is prepared: the options' refusal and `bad`, what is wrong with the entry's own arguments
+// (null: nothing), in the family's order
+mfa_status entry_check(const LaunchOptions &options, const char *bad);
+
+// The checks mfa_decode_params and mfa_prefill_params are put to in the same words.  Each prepare calls them in this order, with its own
+// checks (its kernel table, prefill's cache precision, the limits of its packing) between them where they have always stood: the order
+// in which two mistakes are reported is pinned by tests/golden/cache_refusals.json.
+mfa_status check_precisions(int precision, int outputPrecision);
+template <typename Params>
+mfa_status check_sizes(const Params *p) {
+  if (p->rows == 0 || p->column == 0 || p->heads == 0 || p->batches == 0)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "rows, column, heads and batches must be non-zero");
+  return MFA_OK;
+}
+mfa_status check_group(uint32_t heads, uint32_t G);
+// cacheLengths, the paging (*pageShift: out) and the strides of Q, K, V and O; `e4m3Rows`: K and V rows of bytes, strides in multiples of 16
+template <typename Params>
+mfa_status check_cache_and_strides(const Params *p, bool e4m3Rows, uint32_t *pageShift) {
+  if (!p->cacheLengths) return fail(MFA_ERR_INVALID_ARGUMENT, "cacheLengths is required (device array of `batches` uint32)");
+  mfa_status st = check_paging(p->pageSize, p->blockTable, p->blockTableStride, p->column, pageShift);
+  if (st != MFA_OK) return st;
+  static const char *names[4] = {"Q", "K", "V", "O"};
+  for (int i = 0; i < 4; ++i) {
+    const bool kv = i == 1 || i == 2;
+    const int64_t need = (i == 3) ? 4 : (kv && e4m3Rows) ? 16 : 8;   // 16-byte rows of Q, K, V; 8- or 16-byte stores of O
+    st = check_operand_strides(names[i], p->headDimension, p->leadingDimension[i], p->headStride[i],
+                               kv && p->pageSize ? p->pageStride[i - 1] : p->batchStride[i], need,
+                               kv && e4m3Rows ? "(16-byte rows of an e4m3 cache)" : "(16-byte rows for Q, K, V; whole 4-element stores for O)");
+    if (st != MFA_OK) return st;
+  }
+  return MFA_OK;
+}
+
+// what DecodeArgs and PrefillArgs (attn_decode16.h, attn_prefill16.h) share, from the params and options of a checked launch; the rest
+// of the block is zero
+template <typename Args, typename Params>
+void set_shared_args(Args &a, const Params *p, uint32_t G, uint32_t pageShift, const LaunchOptions &options) {
+  std::memset(&a, 0, sizeof(a));
+  a.lengths = p->cacheLengths;
+  a.table = p->blockTable;
+  a.tableStride = p->blockTableStride;
+  a.ldq = p->leadingDimension[0]; a.hsq = p->headStride[0]; a.bsq = p->batchStride[0];
+  a.ldk = p->leadingDimension[1]; a.hsk = p->headStride[1]; a.bsk = p->batchStride[1]; a.psk = p->pageStride[0];
+  a.ldv = p->leadingDimension[2]; a.hsv = p->headStride[2]; a.bsv = p->batchStride[2]; a.psv = p->pageStride[1];
+  a.ldo = p->leadingDimension[3]; a.hso = p->headStride[3]; a.bso = p->batchStride[3];
+  a.lhs = p->lHeadStride; a.lbs = p->lBatchStride;
+  a.G = G; a.Hkv = p->heads / G; a.batches = p->batches; a.column = p->column;
+  a.paged = p->pageSize != 0; a.pageShift = pageShift;
+  a.causal = p->causal != 0; a.outF32 = p->outputPrecision == MFA_FP32;
+  a.scale2 = 1.44269504089f / std::sqrt((float)p->headDimension);
+  a.window = options.window;
+  a.sinkTokens = options.sinks.tokens;
+  a.sinkLogits = options.sinks.logits;
+  if (options.softcap != 0.0f) {   // cap x tanh(s / cap) in the kernels' log2 units
+    a.capIn = 2.0f / options.softcap;
+    a.capOut = options.softcap * 1.44269504089f;
+  }
+}
+
+// the buffers of a launch into a plan's argument block
+template <typename Plan>
+mfa_status bind(Plan *plan, const void *q, const void *k, const void *v, void *o, float *l) {
+  mfa_status st = check_buffers({q, k, v, o}, "Q, K, V and O");
+  if (st == MFA_OK) st = check_float_arrays({l}, "L");
+  if (st == MFA_OK) st = check_float_arrays({plan->args.keyScale, plan->args.valueScale}, "keyScale and valueScale");
+  if (st == MFA_OK) st = check_float_arrays({plan->args.sinkLogits}, "sinkLogits");
+  if (st != MFA_OK) return st;
+  plan->args.q = (const char *)q; plan->args.k = (const char *)k; plan->args.v = (const char *)v;
+  plan->args.o = (char *)o; plan->args.l = l;
+  return MFA_OK;
+}
 
 // Times `iterations` calls of run(stream) between two events, after `warmup` untimed ones; nothing more is started after a call that
 // failed.  `name` is the kernel a HIP failure is reported under.
@@ -71,6 +170,32 @@ mfa_status time_launches(hipStream_t stream, int warmup, int iterations, float *
   (void)hipEventDestroy(stop);
   if (err != hipSuccess) return hip_fail(err, name);
   return MFA_OK;
+}
+
+// The bodies of every decode and prefill `_launch` and `_time` entry.  Plan: DecodePlan / PrefillPlan, with prepare(params, options),
+// run(stream) and name() -- the kernel a HIP failure is reported under.
+template <typename Plan, typename Params>
+mfa_status cache_launch(const void *q, const void *k, const void *v, void *o, float *l, const Params *params, const LaunchOptions &options,
+                        void *stream) {
+  Plan plan;
+  mfa_status st = entry_check(options, nullptr);
+  if (st == MFA_OK) st = plan.prepare(params, options);
+  if (st == MFA_OK) st = bind(&plan, q, k, v, o, l);
+  if (st != MFA_OK) return st;
+  const hipError_t err = plan.run((hipStream_t)stream);
+  if (err != hipSuccess) return hip_fail(err, plan.name());
+  return MFA_OK;
+}
+
+template <typename Plan, typename Params>
+mfa_status cache_time(const void *q, const void *k, const void *v, void *o, float *l, const Params *params, const LaunchOptions &options,
+                      void *stream, int warmup, int iterations, float *milliseconds) {
+  Plan plan;
+  mfa_status st = entry_check(options, !milliseconds || iterations <= 0 || warmup < 0 ? "bad timing arguments" : nullptr);
+  if (st == MFA_OK) st = plan.prepare(params, options);
+  if (st == MFA_OK) st = bind(&plan, q, k, v, o, l);
+  if (st != MFA_OK) return st;
+  return time_launches((hipStream_t)stream, warmup, iterations, milliseconds, plan.name(), [&](hipStream_t s) { return plan.run(s); });
 }
 
 } // namespace mfa

@@ -151,7 +151,7 @@ struct AppendSet {
      MFA_KV_APPEND_ENTRY(kv_cache_append_ragged_d##D##_f16_e4m3)}}}
 const AppendSet kSets[] = {MFA_KV_APPEND_SET(64), MFA_KV_APPEND_SET(128), MFA_KV_APPEND_SET(256)};
 
-mfa_status prepare(const mfa_kv_append_params *p, AppendArgs *a, AppendKernel *kernel, const char **name, const mfa_ragged_rows *ragged = nullptr) {
+mfa_status prepare(const mfa_kv_append_params *p, AppendArgs *a, AppendKernel *kernel, const char **name, const mfa_ragged_rows *ragged) {
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   if (ragged) {
     if (!ragged->rowStarts)

@@ -415,15 +415,17 @@ def _packed_operand(t):
     return t, (int(t.stride(0)) if T > 1 else heads * D, int(t.stride(1)) if heads > 1 else D, 0)
 
 
-def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, workspace=False, softcap=None):
-    """the launch of a decode or prefill host object over `kw`, on q's device and torch's current stream -> (O, L).  (Rows the launch does
-    not own -- past q_lengths[b], or packed rows of no sequence -- are not written: no memset is spent on them, they come back uninitialised)"""
+def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, softcap, workspace=False):
+    """the launch of a decode or prefill host object over `kw`, on q's device and torch's current stream -> (O, L).  window, sinks -- (sink
+    tokens or 0, sink logits or None) -- and softcap: None is none, and anything else reaches the entries of its header, a window 0 and
+    sinks (0, None) too.  (Rows the launch does not own -- past q_lengths[b], or packed rows of no sequence -- are not written: no memset
+    is spent on them, they come back uninitialised)"""
     if window is not None:
-        kw.update(window=int(window))
+        kw["window"] = int(window)
     if sinks is not None:   # (sink tokens or 0, sink logits or None): the entries of include/mfa_sink.h
-        kw.update(sinkTokens=int(sinks[0]), sinkLogits=sinks[1])
+        kw["sinkTokens"], kw["sinkLogits"] = int(sinks[0]), sinks[1]
     if softcap is not None:   # the entries of include/mfa_softcap.h
-        kw.update(softcap=float(softcap))
+        kw["softcap"] = float(softcap)
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     l = torch.empty(l_shape, dtype=torch.float32, device=q.device)
     if workspace:
@@ -434,32 +436,20 @@ def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, workspace=Fal
     return o, l
 
 
-def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None, sinks=None,
-                softcap=None):
-    fp8, B, kw = _cache_side("flash_decode", (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, fp8=bool(fp8))
+def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None, sinks=None, softcap=None):
+    """`fp8`: what the op says the caches are (None: what they say themselves -- the window, sink and soft-cap ops serve 16-bit and e4m3 caches alike)"""
+    if fp8 is None:
+        fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
+    fp8, B, kw = _cache_side("flash_decode", (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, fp8=fp8)
     q, kw["strides"]["Q"] = _new_operand(q)
     _B, H, R, D = q.shape
     kw.update(rows=R, heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal))
-    return _attend(_host(AttentionDecode, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, workspace=True, softcap=softcap)
+    return _attend(_host(AttentionDecode, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, softcap, workspace=True)
 
 
-def _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale):
-    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, True, k_scale, v_scale)
-
-
-def _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sinks=None, softcap=None):
-    """over whichever cache the tensors say: the window, sink and soft-cap ops serve 16-bit and e4m3 caches alike"""
-    fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
-    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8, k_scale, v_scale, window, sinks, softcap)
-
-
-def _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits):
-    return _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window or None, (sink_tokens, sink_logits))
-
-
-def _no_sinks(sinks):
-    """the ops' 0 and None are no sinks, as 0 is no window"""
-    return sinks if sinks is not None and (sinks[0] or sinks[1] is not None) else None
+def _sinks_or_none(sink_tokens, sink_logits):
+    """the op boundary: an op's 0 sink tokens and None logits are no sinks (None inside this module), as its window 0 is no window"""
+    return (sink_tokens, sink_logits) if sink_tokens or sink_logits is not None else None
 
 
 def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None, sinks=None, softcap=None):
@@ -471,11 +461,11 @@ def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, cau
     _B, H, R, D = q.shape
     kw.update(rows=R, heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal),
               queryLengths=None if q_lengths is None else q_lengths.to(torch.int32))
-    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, softcap=softcap)
+    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, softcap)
 
 
-def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window, sinks,
-                        softcap=None):
+def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window, sinks, softcap=None):
+    """the body of the two ragged ops, in their spelling: `window` 0 and `sinks` None or (0, None) are none, translated here for both"""
     who = "flash_prefill_ragged"
     fp8, B, kw = _cache_side(who, (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, packed=True)
     _check_row_starts(who, row_starts, cache_lengths, max_rows)
@@ -483,7 +473,7 @@ def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows
     T, H, D = q.shape
     kw.update(rows=int(max_rows), heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal),
               rowStarts=row_starts.to(torch.int32), totalRows=T)
-    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (H, T), kw, window or None, _no_sinks(sinks), softcap=softcap)
+    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (H, T), kw, window or None, sinks and _sinks_or_none(*sinks), softcap)
 
 
 def _append(who, operand, k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, row_starts=None, max_rows=None):
@@ -560,26 +550,26 @@ def _op_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, ca
 def _op_decode_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                    block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
                    v_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-    return _run_decode_fp8(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale)
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, True, k_scale, v_scale)
 
 
 def _op_decode_window(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                       block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor],
                       v_scale: Optional[torch.Tensor], window: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    return _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window)
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, None, k_scale, v_scale, window)
 
 
 def _op_decode_sink(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                     block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor],
                     window: int, sink_tokens: int, sink_logits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-    return _run_decode_sink(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window, sink_tokens, sink_logits)
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, None, k_scale, v_scale, window or None, (sink_tokens, sink_logits))
 
 
 def _op_decode_softcap(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                        block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor],
                        window: int, sink_tokens: int, sink_logits: Optional[torch.Tensor], softcap: float) -> Tuple[torch.Tensor, torch.Tensor]:
-    return _run_decode_window(q, k_cache, v_cache, cache_lengths, block_table, causal, k_scale, v_scale, window or None,
-                              _no_sinks((sink_tokens, sink_logits)), softcap)
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, None, k_scale, v_scale, window or None,
+                       _sinks_or_none(sink_tokens, sink_logits), softcap)
 
 
 def _op_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
@@ -615,7 +605,7 @@ def _op_prefill_softcap(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.T
                         k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
                         sink_logits: Optional[torch.Tensor], softcap: float) -> Tuple[torch.Tensor, torch.Tensor]:
     return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window or None,
-                        _no_sinks((sink_tokens, sink_logits)), softcap)
+                        _sinks_or_none(sink_tokens, sink_logits), softcap)
 
 
 def _op_prefill_ragged_softcap(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
@@ -672,21 +662,31 @@ def _call_op(have, name, *args):
     return getattr(torch.ops.mfa, name)(*args) if have else _IMPLS[name](*args)
 
 
-_HAVE_DECODE_OP = _register_cache_op("attention_decode", _op_decode, _fake_padded)
-_HAVE_KVCACHE_OPS = all([_register_cache_op("attention_decode_fp8", _op_decode_fp8, _fake_padded),
-                         _register_cache_op("kv_cache_append", _op_append, _fake_none, ("k_cache", "v_cache"))])
-_HAVE_PREFILL_OP = _register_cache_op("attention_prefill", _op_prefill, _fake_padded)
-# (16-bit and e4m3 caches: one window op, one sink op; `window` 0 and `sink_tokens` 0: none.  The ops before them keep their schemas)
-_HAVE_WINDOW_OPS = all([_register_cache_op("attention_decode_window", _op_decode_window, _fake_padded),
-                        _register_cache_op("attention_prefill_window", _op_prefill_window, _fake_padded)])
-_HAVE_SINK_OPS = all([_register_cache_op("attention_decode_sink", _op_decode_sink, _fake_padded),
-                      _register_cache_op("attention_prefill_sink", _op_prefill_sink, _fake_padded)])
-_HAVE_RAGGED_OPS = all([_register_cache_op("attention_prefill_ragged", _op_prefill_ragged, _fake_packed),
-                        _register_cache_op("kv_cache_append_ragged", _op_append_ragged, _fake_none, ("k_cache", "v_cache"))])
-# (a soft cap, whatever the window and sinks: one op per launch kind, `softcap` > 0 last)
-_HAVE_SOFTCAP_OPS = all([_register_cache_op("attention_decode_softcap", _op_decode_softcap, _fake_padded),
-                         _register_cache_op("attention_prefill_softcap", _op_prefill_softcap, _fake_padded),
-                         _register_cache_op("attention_prefill_ragged_softcap", _op_prefill_ragged_softcap, _fake_packed)])
+# the ops: (name, implementation, fake, mutated arguments).  16-bit and e4m3 caches share one window op, one sink op and one soft-cap op
+# per launch kind (`window` 0 and `sink_tokens` 0: none; `softcap` > 0 last); the ops before them keep their schemas
+_CACHE_OPS = [
+    ("attention_decode", _op_decode, _fake_padded, ()),
+    ("attention_decode_fp8", _op_decode_fp8, _fake_padded, ()),
+    ("kv_cache_append", _op_append, _fake_none, ("k_cache", "v_cache")),
+    ("attention_prefill", _op_prefill, _fake_padded, ()),
+    ("attention_decode_window", _op_decode_window, _fake_padded, ()),
+    ("attention_prefill_window", _op_prefill_window, _fake_padded, ()),
+    ("attention_decode_sink", _op_decode_sink, _fake_padded, ()),
+    ("attention_prefill_sink", _op_prefill_sink, _fake_padded, ()),
+    ("attention_prefill_ragged", _op_prefill_ragged, _fake_packed, ()),
+    ("kv_cache_append_ragged", _op_append_ragged, _fake_none, ("k_cache", "v_cache")),
+    ("attention_decode_softcap", _op_decode_softcap, _fake_padded, ()),
+    ("attention_prefill_softcap", _op_prefill_softcap, _fake_padded, ()),
+    ("attention_prefill_ragged_softcap", _op_prefill_ragged_softcap, _fake_packed, ()),
+]
+_HAVE = {_op[0]: _register_cache_op(*_op) for _op in _CACHE_OPS}   # op name -> whether torch has it as a custom op
+_HAVE_DECODE_OP = _HAVE["attention_decode"]
+_HAVE_KVCACHE_OPS = _HAVE["attention_decode_fp8"] and _HAVE["kv_cache_append"]
+_HAVE_PREFILL_OP = _HAVE["attention_prefill"]
+_HAVE_WINDOW_OPS = _HAVE["attention_decode_window"] and _HAVE["attention_prefill_window"]
+_HAVE_SINK_OPS = _HAVE["attention_decode_sink"] and _HAVE["attention_prefill_sink"]
+_HAVE_RAGGED_OPS = _HAVE["attention_prefill_ragged"] and _HAVE["kv_cache_append_ragged"]
+_HAVE_SOFTCAP_OPS = _HAVE["attention_decode_softcap"] and _HAVE["attention_prefill_softcap"] and _HAVE["attention_prefill_ragged_softcap"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -703,6 +703,45 @@ def _in_place(who, k_new, v_new, k_cache, v_cache, cache_lengths):
             raise RuntimeError(f"{who} writes in place and has no autograd: detach the inputs")
     if not all(t.is_cuda for t in (k_new, v_new, k_cache, v_cache, cache_lengths)):
         raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+
+
+class _Public:
+    """what _route knows of a public function: its name in messages, the op of each rung (none: the function has no such rung and its
+    plain op takes the rung's arguments), whether the scales go in front of a rung's arguments (prefill's ops all take them earlier)"""
+
+    def __init__(self, who, plain, fp8=None, window=None, sink=None, softcap=None, scales=False, packed=False):
+        self.who, self.plain, self.fp8, self.window, self.sink, self.softcap, self.scales, self.packed = who, plain, fp8, window, sink, softcap, scales, packed
+
+
+_DECODE = _Public("flash_decode", "attention_decode", "attention_decode_fp8", "attention_decode_window", "attention_decode_sink",
+                  "attention_decode_softcap", scales=True)
+_PREFILL = _Public("flash_prefill", "attention_prefill", None, "attention_prefill_window", "attention_prefill_sink", "attention_prefill_softcap")
+_PREFILL_RAGGED = _Public("flash_prefill_ragged", "attention_prefill_ragged", softcap="attention_prefill_ragged_softcap", packed=True)
+
+
+def _route(f, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap):
+    """The keywords of the public function `f` (a _Public), checked in one order -- the cap, then the window, the sink tokens and the sink
+    logits -- and the op they reach -> (op, the arguments it takes after causal, or after the scales where they come earlier), in the ops'
+    spelling: 0 for no window and no sink tokens.  A cap wins over all, either sink keyword reaches the sink op, a window the window op"""
+    who = f.who
+    if softcap is not None:
+        _check_softcap(who, softcap)
+    sinks = sink_tokens is not None or sink_logits is not None
+    if window is not None or sinks:
+        # (_check_sinks reads the heads off a [B, H, R, D] query: the packed q of a ragged batch as such a view)
+        _check_sinks(who, q.unsqueeze(0).transpose(1, 2) if f.packed and q.dim() == 3 else q, window, causal, sink_tokens, sink_logits)
+    scales = (k_scale, v_scale) if f.scales else ()
+    if softcap is not None:
+        return f.softcap, (*scales, window or 0, sink_tokens or 0, sink_logits, float(softcap))
+    if f.sink is None or sinks:   # (a function without a sink op: its plain op takes the window and the sinks)
+        return f.sink or f.plain, (*scales, window or 0, sink_tokens or 0, sink_logits)
+    if window is not None:
+        return f.window, (*scales, window)
+    if f.fp8 is not None:
+        if k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES:
+            return f.fp8, scales
+        _check_scales(who, False, k_scale, v_scale)   # (the op of a 16-bit cache takes no scales)
+    return f.plain, ()
 
 
 def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
@@ -747,25 +786,8 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     that of the capped scores (include/mfa_softcap.h).  With any window and sinks, through the op `mfa::attention_decode_softcap`.
     None: no cap."""
     _forward_only("flash_decode", q, k_cache, v_cache, cache_lengths)
-    args = (q, k_cache, v_cache, cache_lengths, block_table, causal)
-    if softcap is not None:
-        _check_softcap("flash_decode", softcap)
-        if window is not None or sink_tokens is not None or sink_logits is not None:
-            _check_sinks("flash_decode", q, window, causal, sink_tokens, sink_logits)
-        have, op = _HAVE_SOFTCAP_OPS, "attention_decode_softcap"
-        args = args + (k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits, float(softcap))
-    elif sink_tokens is not None or sink_logits is not None:
-        _check_sinks("flash_decode", q, window, causal, sink_tokens, sink_logits)
-        have, op, args = _HAVE_SINK_OPS, "attention_decode_sink", args + (k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits)
-    elif window is not None:
-        _check_window("flash_decode", window, causal)
-        have, op, args = _HAVE_WINDOW_OPS, "attention_decode_window", args + (k_scale, v_scale, window)
-    elif k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES:
-        have, op, args = _HAVE_KVCACHE_OPS, "attention_decode_fp8", args + (k_scale, v_scale)
-    else:   # (the op of a 16-bit cache takes no scales)
-        _check_scales("flash_decode", False, k_scale, v_scale)
-        have, op = _HAVE_DECODE_OP, "attention_decode"
-    o, l = _call_op(have, op, *args)
+    op, own = _route(_DECODE, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap)
+    o, l = _call_op(_HAVE[op], op, q, k_cache, v_cache, cache_lengths, block_table, causal, *own)
     return (o, l * _LN2) if return_lse else o
 
 
@@ -789,21 +811,8 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     L = the head's sink logit.  softcap=cap: logit soft-capping as flash_decode's (include/mfa_softcap.h), with any window and sinks,
     through the op `mfa::attention_prefill_softcap`; None: no cap."""
     _forward_only("flash_prefill", q, k_cache, v_cache, cache_lengths)
-    args = (q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale)
-    if softcap is not None:
-        _check_softcap("flash_prefill", softcap)
-        if window is not None or sink_tokens is not None or sink_logits is not None:
-            _check_sinks("flash_prefill", q, window, causal, sink_tokens, sink_logits)
-        have, op, args = _HAVE_SOFTCAP_OPS, "attention_prefill_softcap", args + (window or 0, sink_tokens or 0, sink_logits, float(softcap))
-    elif sink_tokens is not None or sink_logits is not None:
-        _check_sinks("flash_prefill", q, window, causal, sink_tokens, sink_logits)
-        have, op, args = _HAVE_SINK_OPS, "attention_prefill_sink", args + (window or 0, sink_tokens or 0, sink_logits)
-    elif window is not None:
-        _check_window("flash_prefill", window, causal)
-        have, op, args = _HAVE_WINDOW_OPS, "attention_prefill_window", args + (window,)
-    else:
-        have, op = _HAVE_PREFILL_OP, "attention_prefill"
-    o, l = _call_op(have, op, *args)
+    op, own = _route(_PREFILL, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap)
+    o, l = _call_op(_HAVE[op], op, q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, *own)
     return (o, l * _LN2) if return_lse else o
 
 
@@ -823,16 +832,8 @@ def flash_prefill_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.
     `mfa::attention_prefill_ragged` where torch has custom ops, so it traces under torch.compile.  softcap=cap: logit soft-capping as
     flash_decode's, through the op `mfa::attention_prefill_ragged_softcap`; None: no cap."""
     _forward_only("flash_prefill_ragged", q, k_cache, v_cache, cache_lengths)
-    if softcap is not None:
-        _check_softcap("flash_prefill_ragged", softcap)
-    if window is not None or sink_tokens is not None or sink_logits is not None:
-        # (_check_sinks reads the heads off a [B, H, R, D] query: the packed q as such a view)
-        _check_sinks("flash_prefill_ragged", q.unsqueeze(0).transpose(1, 2) if q.dim() == 3 else q, window, causal, sink_tokens, sink_logits)
-    args = (q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window or 0, sink_tokens or 0, sink_logits)
-    if softcap is not None:
-        o, l = _call_op(_HAVE_SOFTCAP_OPS, "attention_prefill_ragged_softcap", *args, float(softcap))
-    else:
-        o, l = _call_op(_HAVE_RAGGED_OPS, "attention_prefill_ragged", *args)
+    op, own = _route(_PREFILL_RAGGED, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap)
+    o, l = _call_op(_HAVE[op], op, q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, *own)
     return (o, l * _LN2) if return_lse else o
 
 

@@ -4,11 +4,12 @@ Host classes (AttentionDecode, AttentionDecodeFP8, AttentionPrefill, KVCacheAppe
 Entries ending in `_launch` / `_time` are not called (the proxy answers 0); everything else is called through.  Per call the proxy
 records the symbol, the bytes of every ctypes.Structure passed by reference and the integer arguments; the `*_init` helpers run but
 are not recorded (the bytes they leave behind are).  The entry each case must reach is a literal here; the recorded calls are the
-fixture tests/golden/cache_launch_marshalling.json, written by this module's own recorder:
+fixture tests/golden/cache_launch_marshalling.json (the soft cap's cases: cache_launch_marshalling_softcap.json), written by this module's own recorder:
 
     PYTHONPATH=. python tests/test_cache_launch_marshalling.py        # rewrites the fixture from the sources as they are
 
-Torch layer (the five _run_* functions of torch_binding): FakeTensorMode tensors, the host classes' dispatch / workspaceSize replaced
+Torch layer (the five _run_* functions of torch_binding, and the implementations of the decode ops, which hold the translation of the
+ops' spelling of none -- window 0, sink_tokens 0 -- to the None the module uses inside): FakeTensorMode tensors, the host classes' dispatch / workspaceSize replaced
 by recorders of their keywords, torch.cuda.device / current_stream stubbed in torch_binding's namespace.
 """
 import ctypes
@@ -21,6 +22,10 @@ from metal_flash_attention_amd import GEMMOperandPrecision as P, MFAError, atten
 from metal_flash_attention_amd.attention import AttentionDecode, AttentionDecodeFP8, AttentionPrefill, KVCacheAppend, KVCachePrecision
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cache_launch_marshalling.json")
+# The cases of the soft cap (every keyword set and torch case with "softcap" in its name) are a fixture of their own, in the same form.
+# GOLDEN is one line of 83 kB: adding to it would rewrite that line, and the bytes recorded before the soft cap existed would no longer
+# stand in the history as the proof that the older cases did not move
+GOLDEN_SOFTCAP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cache_launch_marshalling_softcap.json")
 
 # fake device pointers: the host never reads what they point to
 Q, K, V, O, L = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000
@@ -53,6 +58,8 @@ class _Recorder:
             return a.value
         if isinstance(a, ctypes.Array):
             return "buffer"
+        if isinstance(a, ctypes.c_float):
+            return a.value
         assert a is None or isinstance(a, int), a
         return a
 
@@ -81,6 +88,11 @@ ATTENTION_SETS = {
     "strides_q_window": (dict(strides=dict(Q=(256, 128 * 80, 4 * 128 * 80)), window=65), "window_"),
     "l_strides": (dict(lStrides=(96, 4 * 96)), ""),
     "not_causal": (dict(causal=False, sinkLogits=LOGITS), "sink_"),
+    "softcap_50": (dict(softcap=50.0), "softcap_"),
+    "softcap_0": (dict(softcap=0), "softcap_"),
+    "softcap_window": (dict(softcap=50.0, window=65), "softcap_"),
+    "softcap_sink_logits": (dict(softcap=50.0, sinkLogits=LOGITS), "softcap_"),
+    "softcap_window_sinks": (dict(softcap=50.0, window=65, sinkTokens=4, sinkLogits=LOGITS), "softcap_"),
 }
 DECODE_ONLY_SETS = {
     "workspace_int": (dict(workspace=WORKSPACE, workspaceBytes=1 << 20), ""),
@@ -95,11 +107,14 @@ PREFILL_ONLY_SETS = {
     "ragged_window_0_sink_0": (dict(RAGGED, window=0, sinkTokens=0), "ragged_"),
     "ragged_total_rows_only": (dict(totalRows=100), "ragged_"),
     "ragged_paged_l_strides": (dict(RAGGED, **PAGED, lStrides=(104, 0), strides=dict(O=(4 * 128 + 64, 128, 0))), "ragged_"),
+    "ragged_softcap": (dict(RAGGED, softcap=50.0), "ragged_softcap_"),
+    "ragged_softcap_window_sinks": (dict(RAGGED, softcap=50.0, window=65, sinkTokens=4, sinkLogits=LOGITS), "ragged_softcap_"),
 }
 FP8_SETS = {
     "scales": (dict(keyScale=KSCALE, valueScale=VSCALE), ""),
     "key_scale_window": (dict(keyScale=KSCALE, window=65), "window_"),
     "scales_sinks": (dict(keyScale=KSCALE, valueScale=VSCALE, sinkLogits=LOGITS), "sink_"),
+    "scales_softcap": (dict(keyScale=KSCALE, valueScale=VSCALE, softcap=50.0), "softcap_"),
 }
 APPEND_SETS = {
     "nothing": ({}, ""),
@@ -162,10 +177,13 @@ def _run_host_case(obj, keywords, method):
     return {"calls": recorder.calls, "result": result}
 
 
-def record_host():
-    """{class: {keyword set: {method: [the entry's arguments, the method's result]}}}, equal structs stored once: {"struct": index}"""
+def record_host(softcap):
+    """{class: {keyword set: {method: [the entry's arguments, the method's result]}}}, equal structs stored once: {"struct": index}.
+    `softcap`: the cases of GOLDEN_SOFTCAP, else those of GOLDEN"""
     structs, cases = [], {}
     for case, obj, keywords, method, entry in _host_cases():
+        if ("softcap" in case) != softcap:
+            continue
         got = _run_host_case(obj, keywords, method)
         assert [call[0] for call in got["calls"]] == [entry], (case, got["calls"])
         args = got["calls"][0][1:]
@@ -181,15 +199,25 @@ def record_host():
 
 @pytest.fixture(scope="module")
 def golden():
-    with open(GOLDEN) as f:
-        return json.load(f)
+    """both fixtures as one, the structs of the host cases put back in place of their indices"""
+    merged = {"host": {}, "torch": {}}
+    for path in (GOLDEN, GOLDEN_SOFTCAP):
+        with open(path) as f:
+            part = json.load(f)
+        for cls, sets in part["host"]["cases"].items():
+            for set_name, methods in sets.items():
+                for method, (args, result) in methods.items():
+                    args = [{"struct": part["host"]["structs"][a["struct"]]} if isinstance(a, dict) else a for a in args]
+                    merged["host"].setdefault(cls, {}).setdefault(set_name, {})[method] = [args, result]
+        merged["torch"].update(part["torch"])
+    return merged
 
 
 _HOST_CASES = list(_host_cases())
 
 
 def test_the_fixture_holds_exactly_the_cases(golden):
-    cases = golden["host"]["cases"]
+    cases = golden["host"]
     assert sorted(f"{c}/{s}/{m}" for c in cases for s in cases[c] for m in cases[c][s]) == sorted(case for case, *_ in _HOST_CASES)
     assert sorted(golden["torch"]) == sorted(_TORCH_CASES)
 
@@ -199,8 +227,7 @@ def test_host_class_reaches_the_entry_with_the_bytes(case, obj, keywords, method
     got = _run_host_case(obj, keywords, method)
     assert [call[0] for call in got["calls"]] == [entry], "one call, to the entry the keywords choose"
     cls, set_name, _method = case.split("/")
-    args, result = golden["host"]["cases"][cls][set_name][method]
-    args = [{"struct": golden["host"]["structs"][a["struct"]]} if isinstance(a, dict) else a for a in args]
+    args, result = golden["host"][cls][set_name][method]
     assert json.loads(json.dumps([got["calls"][0][1:], got["result"]])) == [args, result]
 
 
@@ -239,7 +266,7 @@ def _describe_value(v):
         return {k: _describe_value(x) for k, x in v.items()}
     if isinstance(v, (tuple, list)):
         return [_describe_value(x) for x in v]
-    assert v is None or isinstance(v, (bool, int)), v
+    assert v is None or isinstance(v, (bool, int, float)), v
     return v
 
 
@@ -336,12 +363,14 @@ _TORCH_CASES = {
     "decode/paged_wide_table": ("_run_decode", 0, ("q1", "pool_k", "pool_v", "lens", "table", True)),
     "decode/fp8_scales": ("_run_decode", 0, ("q1", "k8", "v8", "lens", None, True, True, "ks", "vs")),
     "decode/fp8_no_scales_f16_d64": ("_run_decode", 0, ("q1_f16_d64", "k8_d64", "v8_d64", "lens", None, True, True, None, None)),
-    "decode/fp8_wrapper": ("_run_decode_fp8", 0, ("q1", "pool_k8", "pool_v8", "lens", "table", True, "ks", None)),
+    "decode/fp8_wrapper": ("op:attention_decode_fp8", 0, ("q1", "pool_k8", "pool_v8", "lens", "table", True, "ks", None)),
     "decode/window": ("_run_decode", 0, ("q1", "k", "v", "lens", None, True, False, None, None, 65)),
     "decode/window_and_sinks": ("_run_decode", 512, ("q3", "k", "v", "lens", None, True, False, None, None, 65, (4, "logits"))),
     "decode/sinks_zero": ("_run_decode", 0, ("q1", "k", "v", "lens", None, True, False, None, None, None, (0, None))),
-    "decode/window_wrapper_fp8": ("_run_decode_window", 0, ("q1", "k8", "v8", "lens", None, True, "ks", "vs", 65)),
-    "decode/sink_wrapper_window_0": ("_run_decode_sink", 0, ("q1", "k", "v", "lens", None, True, None, None, 0, 0, "logits")),
+    "decode/window_wrapper_fp8": ("op:attention_decode_window", 0, ("q1", "k8", "v8", "lens", None, True, "ks", "vs", 65)),
+    "decode/sink_wrapper_window_0": ("op:attention_decode_sink", 0, ("q1", "k", "v", "lens", None, True, None, None, 0, 0, "logits")),
+    "decode/window_wrapper_softcap": ("op:attention_decode_softcap", 0, ("q1", "k", "v", "lens", None, True, None, None, 0, 0, None, 50.0)),
+    "decode/window_wrapper_fp8_window_sinks_softcap": ("op:attention_decode_softcap", 512, ("q3", "k8", "v8", "lens", None, True, "ks", "vs", 65, 4, "logits", 30.0)),
     "prefill/contiguous": ("_run_prefill", 0, ("q70", "k", "v", "lens", None, None, True, None, None)),
     "prefill/r1_query_lengths_view_caches": ("_run_prefill", 0, ("q1", "k_view", "v_view", "lens64", "qlens", None, False, None, None)),
     "prefill/q_copied": ("_run_prefill", 0, ("q3_t", "k", "v", "lens", None, None, True, None, None)),
@@ -350,6 +379,10 @@ _TORCH_CASES = {
     "prefill/window_and_sinks": ("_run_prefill", 0, ("q70", "k", "v", "lens", None, None, True, None, None, 65, (4, "logits"))),
     "prefill/window": ("_run_prefill", 0, ("q3_view", "k", "v", "lens", None, None, True, None, None, 65)),
     "prefill/sinks_zero": ("_run_prefill", 0, ("q70", "k", "v", "lens", None, None, True, None, None, None, (0, None))),
+    "prefill/softcap": ("_run_prefill", 0, ("q70", "k", "v", "lens", None, None, True, None, None, None, None, 50.0)),
+    "prefill/softcap_window_sinks_fp8": ("_run_prefill", 0, ("q70", "k8", "v8", "lens", "qlens", None, True, "ks", None, 65, (4, "logits"), 30.0)),
+    "prefill_ragged/softcap": ("_run_prefill_ragged", 0, ("qp", "k", "v", "lens", "starts", 70, None, True, None, None, 0, (0, None), 50.0)),
+    "prefill_ragged/softcap_window_sinks": ("_run_prefill_ragged", 0, ("qp", "k", "v", "lens", "starts", 70, None, True, None, None, 65, (4, "logits"), 30.0)),
     "prefill_ragged/contiguous": ("_run_prefill_ragged", 0, ("qp", "k", "v", "lens", "starts", 70, None, True, None, None, 0, (0, None))),
     "prefill_ragged/t1": ("_run_prefill_ragged", 0, ("qp_t1", "k", "v", "lens64", "starts", 1, None, True, None, None, 65, (4, "logits"))),
     "prefill_ragged/h1_view_caches": ("_run_prefill_ragged", 0, ("qp_h1", "k_h1", "v_h1", "lens", "starts", 70, None, False, None, None, 0, (0, "logits_h1"))),
@@ -373,15 +406,21 @@ def _resolve(arg, t):
     return tuple(_resolve(a, t) for a in arg) if isinstance(arg, tuple) else arg
 
 
+def _function(name):
+    """a function of torch_binding, or with "op:" the implementation of a torch op: what the op runs on the GPU, with the op's spelling
+    of none (window 0, sink_tokens 0)"""
+    return tb._IMPLS[name[3:]] if name.startswith("op:") else getattr(tb, name)
+
+
 def _run_torch_case(case, log):
     function, need, args = _TORCH_CASES[case]
     del log[:]
     log.need = need
     with FakeTensorMode():
         t = _operands()
-        result = getattr(tb, function)(*(_resolve(a, t) for a in args))
+        result = _function(function)(*(_resolve(a, t) for a in args))
     launches = list(log)
-    if function.startswith("_run_decode"):   # workspaceSize sees dispatch's keywords without the workspace and the stream: kept once
+    if "decode" in function:   # workspaceSize sees dispatch's keywords without the workspace and the stream: kept once
         assert [x["method"] for x in launches] == ["workspaceSize", "dispatch"] and launches[0]["buffers"] == []
         sized, run = ({k: v for k, v in x.items() if k not in ("method", "buffers", "keywords")} for x in launches)
         assert sized == run and launches[0]["keywords"] == {k: v for k, v in launches[1]["keywords"].items() if k not in ("workspace", "stream")}
@@ -393,7 +432,7 @@ def test_torch_layer_hands_the_host_classes_these_keywords(case, launches, golde
     got = _run_torch_case(case, launches)
     methods = [(x["class"], x["method"]) for x in got["launches"]]
     function, need, args = _TORCH_CASES[case]
-    if function.startswith("_run_decode"):
+    if "decode" in function:
         cls = "AttentionDecodeFP8" if any(isinstance(a, str) and "8" in a for a in args[1:3]) else "AttentionDecode"
         assert methods == [(cls, "dispatch")]
         workspace = got["launches"][0]["keywords"]["workspace"]
@@ -426,8 +465,8 @@ _REFUSALS = {
     "decode/block_table": ("_run_decode", ("q1", "pool_k", "pool_v", "lens", "table64", True), ValueError, "block_table must be an int32 GPU tensor"),
     "decode/scale_shape": ("_run_decode", ("q1", "k8", "v8", "lens", None, True, True, "logits", None), ValueError, "k_scale must be float32 [Hkv]"),
     "decode/scale_device": ("_run_decode", ("q1", "k8", "v8", "lens", None, True, True, None, "ks_cpu"), RuntimeError, "v_scale must live on the GPU of the cache"),
-    "decode_window/scales_16bit": ("_run_decode_window", ("q1", "k", "v", "lens", None, True, "ks", None, 65), ValueError, "go with a float8_e4m3fn cache"),
-    "decode_sink/scales_16bit": ("_run_decode_sink", ("q1", "k", "v", "lens", None, True, None, "ks", 65, 4, None), ValueError, "go with a float8_e4m3fn cache"),
+    "decode_window/scales_16bit": ("op:attention_decode_window", ("q1", "k", "v", "lens", None, True, "ks", None, 65), ValueError, "go with a float8_e4m3fn cache"),
+    "decode_sink/scales_16bit": ("op:attention_decode_sink", ("q1", "k", "v", "lens", None, True, None, "ks", 65, 4, None), ValueError, "go with a float8_e4m3fn cache"),
     "prefill/cpu_tensor": ("_run_prefill", ("q70", "k", "v", "lens_cpu", None, None, True, None, None), RuntimeError, "must live on the GPU"),
     "prefill/dtype": ("_run_prefill", ("q1_f16", "k", "v", "lens", None, None, True, None, None), TypeError, "must share one of bfloat16 / float16"),
     "prefill/q_dtype": ("_run_prefill", ("q1_f32", "k", "v", "lens", None, None, True, None, None), TypeError, "q must be bfloat16 or float16"),
@@ -487,29 +526,31 @@ def _bad_operands(t):
 @pytest.mark.parametrize("case", sorted(_REFUSALS))
 def test_torch_layer_refusals(case, launches):
     function, args, exception, needle = _REFUSALS[case]
-    who = {"_run_decode": "flash_decode", "_run_decode_window": "flash_decode", "_run_decode_sink": "flash_decode", "_run_prefill": "flash_prefill",
+    who = {"_run_decode": "flash_decode", "op:attention_decode_window": "flash_decode", "op:attention_decode_sink": "flash_decode", "_run_prefill": "flash_prefill",
            "_run_prefill_ragged": "flash_prefill_ragged", "_run_append": "kv_cache_append", "_run_append_ragged": "kv_cache_append_ragged"}[function]
     with FakeTensorMode():
         t = _bad_operands(_operands())
         with pytest.raises(exception) as raised:
-            getattr(tb, function)(*(_resolve(a, t) for a in args))
+            _function(function)(*(_resolve(a, t) for a in args))
     message = str(raised.value)
     assert type(raised.value) is exception and message.startswith(who + ": ") and needle in message, message
     assert not launches, "nothing is dispatched after a refusal"
 
 
-def record_torch():
+def record_torch(softcap):
     mp = pytest.MonkeyPatch()
     try:
         log = _record_launches(mp)
-        return {case: json.loads(json.dumps(_run_torch_case(case, log))) for case in sorted(_TORCH_CASES)}
+        return {case: json.loads(json.dumps(_run_torch_case(case, log))) for case in sorted(_TORCH_CASES) if ("softcap" in case) == softcap}
     finally:
         mp.undo()
 
 
 if __name__ == "__main__":
-    fixture = {"host": json.loads(json.dumps(record_host())), "torch": record_torch()}
-    with open(GOLDEN, "w") as f:
-        json.dump(fixture, f, indent=None, separators=(",", ":"), sort_keys=True)
-        f.write("\n")
-    print(f"wrote {GOLDEN}: {len(_HOST_CASES)} host cases, {len(fixture['torch'])} torch cases, {os.path.getsize(GOLDEN)} bytes")
+    for path, softcap in ((GOLDEN, False), (GOLDEN_SOFTCAP, True)):
+        fixture = {"host": json.loads(json.dumps(record_host(softcap))), "torch": record_torch(softcap)}
+        with open(path, "w") as f:
+            json.dump(fixture, f, indent=None, separators=(",", ":"), sort_keys=True)
+            f.write("\n")
+        print(f"wrote {path}: {sum(len(m) for c in fixture['host']['cases'].values() for m in c.values())} host cases, "
+              f"{len(fixture['torch'])} torch cases, {os.path.getsize(path)} bytes")
