@@ -288,16 +288,33 @@ RAGGED_SYMBOLS = [   # include/mfa_ragged.h: `ragged` (required) after `sinks` (
 SOFTCAP_SYMBOLS = []   # include/mfa_softcap.h: `softcap` (float, 0 = none) after `sinks` (NULL = none) / after `ragged`
    #    all of it mfa_attention_*_{workspace_size,launch,launch_form,time} rows: the CACHE_FAMILIES loop below
 
+class mfa_attention_tree(ctypes.Structure):   # include/mfa_tree.h
+    _fields_ = [("masks", ctypes.c_void_p), ("batchStride", ctypes.c_int64), ("reserved", ctypes.c_uint64)]
+
+
+_TREE = ctypes.POINTER(mfa_attention_tree)
+MFA_TREE_MAX_NODES = 64
+
+TREE_SYMBOLS = [   # include/mfa_tree.h: `tree` (required) after `sinks` (NULL = none)
+    # + its mfa_attention_*_{workspace_size,launch,launch_form,time} rows: the CACHE_FAMILIES loop below
+    ("mfa_attention_tree_init", None, [_TREE]),
+    ("mfa_attention_tree_size", ctypes.c_size_t, []),
+    ("mfa_attention_tree_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
+    ("mfa_attention_prefill_tree_tile_range", ctypes.c_int, [ctypes.c_uint32] * 4 + [_U32P] * 5),
+]
+
 # ---- the laddered entries of the launches over a KV cache, described once:
 #     mfa_attention_<launch>_<family><verb>(*<the verb's head>, params, *<the options the family owns>, *<the verb's tail>)
 # CACHE_FAMILIES: launch -> family -> the options its entries take, in the order of their signatures (each family is an earlier one plus an
 # argument; attention._route picks the first that owns every option a call gives).  CACHE_VERBS: launch -> verb -> (head, tail).
-CACHE_OPTION_TYPES = {"quant": _QUANT, "window": ctypes.c_uint32, "sinks": _SINKS, "ragged": _RAGGED, "softcap": ctypes.c_float}
+CACHE_OPTION_TYPES = {"quant": _QUANT, "window": ctypes.c_uint32, "sinks": _SINKS, "ragged": _RAGGED, "softcap": ctypes.c_float,
+                      "tree": _TREE}
 CACHE_FAMILIES = {
     "decode": {"": (), "fp8_": ("quant",), "window_": ("quant", "window"), "sink_": ("quant", "window", "sinks"),
-               "softcap_": ("quant", "window", "sinks", "softcap")},
+               "softcap_": ("quant", "window", "sinks", "softcap"), "tree_": ("quant", "window", "sinks", "tree")},
     "prefill": {"": (), "window_": ("window",), "sink_": ("window", "sinks"), "ragged_": ("window", "sinks", "ragged"),
-                "softcap_": ("window", "sinks", "softcap"), "ragged_softcap_": ("window", "sinks", "ragged", "softcap")},
+                "softcap_": ("window", "sinks", "softcap"), "ragged_softcap_": ("window", "sinks", "ragged", "softcap"),
+                "tree_": ("window", "sinks", "tree")},
 }
 _VERBS = {"workspace_size": ([], [ctypes.POINTER(ctypes.c_uint64)]), "launch": (_DECODE_BUFS, [ctypes.c_void_p]),
           "launch_form": ([], [ctypes.c_char_p, ctypes.c_size_t]), "time": (_DECODE_BUFS, [ctypes.c_void_p] + _TIMING)}
@@ -309,7 +326,8 @@ for _symbols, _launch, _family in ((DECODE_SYMBOLS, "decode", ""), (KVCACHE_SYMB
                                    (WINDOW_SYMBOLS, "decode", "window_"), (WINDOW_SYMBOLS, "prefill", "window_"),
                                    (SINK_SYMBOLS, "decode", "sink_"), (SINK_SYMBOLS, "prefill", "sink_"), (RAGGED_SYMBOLS, "prefill", "ragged_"),
                                    (SOFTCAP_SYMBOLS, "decode", "softcap_"), (SOFTCAP_SYMBOLS, "prefill", "softcap_"),
-                                   (SOFTCAP_SYMBOLS, "prefill", "ragged_softcap_")):
+                                   (SOFTCAP_SYMBOLS, "prefill", "ragged_softcap_"), (TREE_SYMBOLS, "decode", "tree_"),
+                                   (TREE_SYMBOLS, "prefill", "tree_")):
     _own = [CACHE_OPTION_TYPES[option] for option in CACHE_FAMILIES[_launch][_family]]
     _symbols += [(f"mfa_attention_{_launch}_{_family}{verb}", ctypes.c_int, head + [_CACHE_PARAMS[_launch]] + _own + tail)
                  for verb, (head, tail) in CACHE_VERBS[_launch].items()]
@@ -389,7 +407,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

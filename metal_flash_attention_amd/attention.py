@@ -435,6 +435,19 @@ def _softcap(shape):
     return None if cap is None else ctypes.c_float(cap)
 
 
+def _tree_block(shape):
+    """pops treeMasks= / treeBatchStride= from a launch's keywords -> (mfa_attention_tree, what it points to), or None when neither is
+    given (include/mfa_tree.h: a speculation tree among the new rows, the block is required by the tree entries)"""
+    masks, stride = shape.pop("treeMasks", None), shape.pop("treeBatchStride", None)
+    if masks is None and stride is None:
+        return None
+    block = _abi.mfa_attention_tree()
+    lib().mfa_attention_tree_init(ctypes.byref(block))
+    block.masks = _pointer(masks)
+    block.batchStride = int(stride or 0)
+    return block, masks
+
+
 def _pointers(*buffers):
     return tuple(_pointer(b) for b in buffers)
 
@@ -463,7 +476,7 @@ def _fill_shared(p, D, operands, packed, *, rows, column, heads, batches, cacheL
         p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
 
 
-_OPTIONS = tuple(_abi.CACHE_OPTION_TYPES)   # quant, window, sinks, ragged, softcap: the order every family's signature keeps
+_OPTIONS = tuple(_abi.CACHE_OPTION_TYPES)   # quant, window, sinks, ragged, softcap, tree: the order every family's signature keeps
 
 
 def _routes(launch):
@@ -481,14 +494,17 @@ def _routes(launch):
     return table
 
 
-def _route(routes, quant, window, sinks, ragged, softcap):
+def _route(routes, quant, window, sinks, ragged, softcap, tree=None):
     """The entries a launch's options reach (`routes`: _routes of the launch) -> (their name up to the verb, the arguments the family owns).
     Each option is its ctypes argument, or None when the keywords leave it out (window: a number; a window that IS given may be 0).  An
     option that is given needs a family that owns it: a cap wins over all, ragged over window and sinks, either sink keyword reaches the
-    sink entries, a window -- 0 too -- the window entries, an e4m3 decode with nothing else fp8_.  What the family owns beyond the given
-    options is passed as none: window 0, a NULL block"""
-    entries, owned = routes[(quant is not None, window is not None, sinks is not None, ragged is not None, softcap is not None)]
-    return entries, itertools.compress((quant, int(window or 0), sinks, ragged, softcap), owned) if owned else ()
+    sink entries, a window -- 0 too -- the window entries, an e4m3 decode with nothing else fp8_; a tree reaches the tree entries, which
+    own neither a cap nor ragged rows.  What the family owns beyond the given options is passed as none: window 0, a NULL block"""
+    if tree is not None and (softcap is not None or ragged is not None):   # (no family owns both: said here, not by the table's KeyError)
+        raise ValueError("a speculation tree (treeMasks=) goes with neither " + ("softcap=" if softcap is not None else "rowStarts= / totalRows=") +
+                         ": a soft cap or ragged rows together with a tree have no kernel (include/mfa_tree.h)")
+    entries, owned = routes[(quant is not None, window is not None, sinks is not None, ragged is not None, softcap is not None, tree is not None)]
+    return entries, itertools.compress((quant, int(window or 0), sinks, ragged, softcap, tree), owned) if owned else ()
 
 
 class _CacheAttention:
@@ -508,9 +524,11 @@ class _CacheAttention:
         sinks = _sinks_block(shape) if "sinkTokens" in shape or "sinkLogits" in shape else None
         cap = _softcap(shape) if "softcap" in shape else None
         ragged = _ragged_block(shape) if self.LAUNCH == "prefill" and ("rowStarts" in shape or "totalRows" in shape) else None
+        tree = _tree_block(shape) if "treeMasks" in shape or "treeBatchStride" in shape else None
         quant, _scales = self._quant(shape)
         p, _keep = self._params(**shape) if ragged is None else self._params(ragged=ragged, **shape)
-        entries, own = _route(self.ROUTES, quant, window, sinks and ctypes.byref(sinks[0]), ragged and ctypes.byref(ragged[0]), cap)
+        entries, own = _route(self.ROUTES, quant, window, sinks and ctypes.byref(sinks[0]), ragged and ctypes.byref(ragged[0]), cap,
+                              tree and ctypes.byref(tree[0]))
         check(getattr(lib(), entries + verb)(*head, ctypes.byref(p), *own, *tail))
 
     def launchForm(self, **shape) -> str:
@@ -551,7 +569,11 @@ class AttentionDecode(_CacheAttention):
     any window).  Either keyword, even 0 / None beside the other, goes through the sink entries.
 
     softcap=cap (the same four methods): logit soft-capping, include/mfa_softcap.h -- the softmax sees cap tanh(score / cap), cap > 0 in
-    natural-log units (Gemma 2: 50).  None: no cap; 0 goes through the soft-cap entries and is the launch without a cap."""
+    natural-log units (Gemma 2: 50).  None: no cap; 0 goes through the soft-cap entries and is the launch without a cap.
+
+    treeMasks=device uint64 [batches][rows] (or [rows] with treeBatchStride=0, one tree for every sequence), treeBatchStride=elements
+    (the same four methods): a speculation tree among the new rows, include/mfa_tree.h -- bit j of row r's mask says that the row sees
+    new token j; the prefix is seen through the window at the row's depth.  Goes with a window and sinks, not with softcap=."""
 
     LAUNCH, ROUTES = "decode", _routes("decode")
 
@@ -658,7 +680,10 @@ class AttentionPrefill(_CacheAttention):
     count of a sequence, queryLengths must stay None and Q / O / L have no batch stride (operands left out of `strides` are taken as
     contiguous [T, heads, D]).  Goes through the ragged entries whichever window and sinks.
 
-    softcap=cap (the same three, ragged included): logit soft-capping as AttentionDecode's, include/mfa_softcap.h."""
+    softcap=cap (the same three, ragged included): logit soft-capping as AttentionDecode's, include/mfa_softcap.h.
+
+    treeMasks= / treeBatchStride= (the same three; rows <= 64, not ragged, no softcap): a speculation tree as AttentionDecode's,
+    include/mfa_tree.h; treeTileRange gives the tiles every row block of a sequence then walks."""
 
     LAUNCH, ROUTES = "prefill", _routes("prefill")
 
@@ -723,6 +748,15 @@ class AttentionPrefill(_CacheAttention):
                                                           int(window), int(sinkTokens), *(ctypes.byref(x) for x in out)))
         return tuple(int(x.value) for x in out)
 
+
+    @staticmethod
+    def treeTileRange(length: int, queryLength: int, window: int = 0, sinkTokens: int = 0) -> Tuple[int, int, int, int, int]:
+        """(begin, unmaskedBegin, unmaskedEnd, end, sinkEnd) of EVERY row block of a sequence of `length` keys and `queryLength` rows under
+        a speculation tree (include/mfa_tree.h), in 64-key tiles: the kernels' own function, on the host"""
+        out = [ctypes.c_uint32(0) for _ in range(5)]
+        check(lib().mfa_attention_prefill_tree_tile_range(int(length), int(queryLength), int(window), int(sinkTokens),
+                                                          *(ctypes.byref(x) for x in out)))
+        return tuple(int(x.value) for x in out)
 
     @staticmethod
     def raggedSlots(totalRows: int, batches: int, rows: int, blockRows: int) -> int:

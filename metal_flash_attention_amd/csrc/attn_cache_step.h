@@ -25,8 +25,20 @@
 //     -- tanh(x) = 1 - 2 / (1 + e^(2x)) is right at both ends: e^(2x) = +inf gives +c2, 0 gives -c2, never NaN (the form
 //     (e^(2x) - 1) / (e^(2x) + 1) is inf / inf there).  One v_exp_f32, one v_rcp_f32 and four plain instructions per score; the
 //     cancellation near 0 costs absolute error of the order of c2 2^-24, far below the rounding of P.
+//
+// The rule of the tree (TREE; include/mfa_tree.h): the new rows of a sequence are the nodes of a speculation tree and see
+// their ancestors, not their neighbours in the cache.  With n the keys of the sequence and qn its new rows, P = max(n - qn, 0) is the
+// prefix length, node j is key P + j, live = min(qn, n), and row r carries mask_r = masks[b batchStride + r] & (2^live - 1) -- bit j: the
+// row sees node j; bits at or past `live` are ignored -- and d_r = max(popcount(mask_r), 1), its depth + 1.  Row r sees key c iff
+//   * PREFIX key, c < P: the SINK rule above with the row's frontier at its POSITION P + d_r - 1, not at its index: no window, or
+//     c >= lo = window_lo(P + d_r, W), or c < S.
+//   * NEW-TOKEN key, P <= c < n: bit c - P of mask_r is set.  The mask alone decides: no causal test and no window test among the new
+//     tokens (the host refuses 0 < W < rows, so an ancestor never leaves a descendant's window), and bits j > r are honoured.
+//   * everything else is the SINK rule's: a masked score is replaced, a blind row keeps O = 0 / L = -FLT_MAX or the sink logit, the
+//     scales and what is never loaded do not change.  The chain mask_r = 2^(r + 1) - 1 is today's causal launch, key for key.
 #pragma once
 #include "attn_fwd16_common.h"
+#include <type_traits>
 
 namespace mfa {
 
@@ -38,9 +50,27 @@ template <typename U> __host__ __device__ __forceinline__ U window_lo(U f1, U W)
 // The keys one query row sees, by the rule above.  `bound`: the keys the launch holds for the row's sequence (decode pieces: their end).
 // (CAP changes nothing here: it keeps the capped kernels' instantiations of the step apart from the sink kernels', whose code hipcc
 // otherwise orders differently once they share them)
-template <bool WINDOW, bool SINK, bool CAP = false> struct VisibleKeys {
+// TREE = 32 / 64: the tree side, with the row's mask in that many bits (decode: M <= 32 rows, the low word; prefill: up to 64 rows);
+// `lim` is then the prefix length P, so that the SINK test answers for the prefix keys alone and the mask for the keys from P on.
+template <int TREE> struct TreeSide {
+  typename std::conditional<TREE == 64, uint64_t, uint32_t>::type mask;
+};
+template <> struct TreeSide<0> {};
+struct TreeRow { uint32_t prefix; uint64_t mask; };   // what the tree kernels construct a row's keys from
+template <bool WINDOW, bool SINK, bool CAP = false, int TREE = 0> struct VisibleKeys : TreeSide<TREE> {
   static_assert(!SINK || WINDOW, "the sink kernels are the window kernels plus SINK");
+  static_assert(!TREE || (SINK && !CAP && (TREE == 32 || TREE == 64)), "the tree kernels are the sink kernels plus TREE");
   uint32_t lim, lo = 0, span = 0, slim = 0;
+  // TREE: row.prefix = P <= bound, row.mask = mask_r (bits at or past `live` already cleared); the frontier is P + d_r
+  __device__ __forceinline__ VisibleKeys(uint32_t bound, TreeRow row, uint32_t window, uint32_t sinkTokens) {
+    static_assert(TREE != 0, "the constructor of the tree kernels");
+    this->mask = (decltype(this->mask))row.mask;
+    const uint32_t d = max((uint32_t)__builtin_popcountll(row.mask), 1u);
+    lim = min(bound, row.prefix);
+    lo = window ? window_lo(row.prefix + d, window) : 0u;
+    span = lim > lo ? lim - lo : 0u;
+    slim = min(sinkTokens, lim);
+  }
   __device__ __forceinline__ VisibleKeys(uint32_t bound, uint32_t f1, uint32_t causal, uint32_t window, uint32_t sinkTokens) {
     lim = bound;
     if (causal) lim = min(lim, f1);
@@ -52,7 +82,10 @@ template <bool WINDOW, bool SINK, bool CAP = false> struct VisibleKeys {
     if constexpr (SINK) slim = min(sinkTokens, lim);
   }
   __device__ __forceinline__ bool visible(uint32_t c) const {
-    if constexpr (SINK) return (c - lo < span) | (c < slim);
+    if constexpr (TREE != 0) {   // (c < P: j wraps past TREE; c >= P: both prefix tests fail, lim = P)
+      const uint32_t j = c - lim;
+      return (c - lo < span) | (c < slim) | ((j < (uint32_t)TREE) & (uint32_t)((this->mask >> (j & (uint32_t)(TREE - 1))) & 1u));
+    } else if constexpr (SINK) return (c - lo < span) | (c < slim);
     else if constexpr (WINDOW) return c - lo < span;
     else return c < lim;
   }

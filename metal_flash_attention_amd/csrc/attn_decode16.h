@@ -48,6 +48,11 @@
 //
 // CAP: the soft cap of attn_cache_step.h on the visible scores, the SINK body otherwise (any window and sinks, none included): c1 rides
 // on kscale, c2 goes to score_max.  Pieces, workspace and the combine kernel are untouched -- the pieces publish capped (m, l).
+//
+// TREE: the tree rule of attn_cache_step.h, the SINK body otherwise (any window and sinks, none included).  The lane's mask is that of
+// its ROW, pc % R, never of its packed index; R <= 32, so the low word of the uint64 is all a lane keeps.  Nothing else moves: row 0's
+// frontier P + 1 is the smallest a node can have, so decode_sink_piece_range with `rows` already starts at the conservative tile, and
+// the pieces, the workspace and the combine kernel are the sink launch's.
 #pragma once
 #include "attn_cache_step.h"
 #include "kv_e4m3.h"
@@ -81,6 +86,8 @@ struct DecodeArgs {
   uint32_t sinkTokens;                  // the SINK kernels only, which also take window = 0 (no window); behind `window` in turn
   const float *sinkLogits;              // [Hq], natural units; null: none
   float capIn, capOut;                  // the CAP kernels only: c1 = 2 / cap and c2 = cap log2(e) (attn_cache_step.h); behind the sinks in turn
+  const uint64_t *masks;                // the TREE kernels only: [batches][R] row masks (include/mfa_tree.h); last in turn
+  int64_t maskStride;                   // elements between two sequences' masks; 0: one tree for all
 };
 
 // The two key ranges of piece `piece` of `pieces` with `sinkTokens` sink keys under a window of `window` keys (0: no window, lo0 = 0):
@@ -134,9 +141,10 @@ template <int D> constexpr int decode16_lds_bytes() {
   return images > merge ? images : merge;
 }
 
-template <typename T, int D, bool SPLIT, bool FP8, bool WINDOW = false, bool SINK = false, bool CAP = false>
+template <typename T, int D, bool SPLIT, bool FP8, bool WINDOW = false, bool SINK = false, bool CAP = false, bool TREE = false>
 __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
   static_assert(!CAP || SINK, "the capped kernels are the sink kernels plus CAP");
+  static_assert(!TREE || (SINK && !CAP), "the tree kernels are the sink kernels plus TREE");
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -203,7 +211,17 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
     }
   }
   // keys this row sees (causal: c <= row + max(len - R, 0); always c < len, and inside this piece c < end)
-  const VisibleKeys<WINDOW, SINK, CAP> keys(SINK ? len : end, qrow + (len > R ? len - R : 0u) + 1u, a.causal, a.window, a.sinkTokens);
+  // (TREE: the row's mask, cut to the live nodes -- with len < R new tokens the rows from `len` on have no key of their own)
+  const auto keys = [&] {
+    if constexpr (TREE) {
+      const uint32_t live = min(R, len);
+      const uint32_t word = *reinterpret_cast<const uint32_t *>(a.masks + ((int64_t)batch * a.maskStride + qrow));   // the low word
+      const uint32_t mask = live < 32u ? word & ((1u << live) - 1u) : word;
+      return VisibleKeys<true, true, false, 32>(len, TreeRow{len > R ? len - R : 0u, mask}, a.window, a.sinkTokens);
+    } else {
+      return VisibleKeys<WINDOW, SINK, CAP>(SINK ? len : end, qrow + (len > R ? len - R : 0u) + 1u, a.causal, a.window, a.sinkTokens);
+    }
+  }();
 
   // ---- addresses of a step's two 16-key groups (wave-uniform; element offsets from a.k / a.v, which are byte offsets under FP8)
   const int64_t khead = (int64_t)kvh * a.hsk, vhead = (int64_t)kvh * a.hsv;
@@ -424,20 +442,20 @@ __device__ __forceinline__ void decode16_combine_body(const DecodeArgs &a) {
 
 } // namespace mfa
 
-// One list of the kernel families, (infix, WINDOW, SINK, CAP): the kernels, the table that selects them (attn_decode16.hip) and the names
-// are generated from it.  MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, ...) is a set's code objects, in the translation unit that holds
+// One list of the kernel families, (infix, WINDOW, SINK, CAP, TREE): the kernels, the table that selects them (attn_decode16.hip) and the
+// names are generated from it.  MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, ...) is a set's code objects, in the translation unit that holds
 // them; (MFA_DECODE_DECLARE, ...) names the kernels of another unit for the table.  D = 256 runs one workgroup per compute unit.
 #define MFA_DECODE_FAMILIES(X, K, TN, T, D)                                                                                           \
-  X(K, , false, false, false, TN, T, D) X(K, w, true, false, false, TN, T, D) X(K, s, true, true, false, TN, T, D)                    \
-  X(K, c, true, true, true, TN, T, D)
+  X(K, , false, false, false, false, TN, T, D) X(K, w, true, false, false, false, TN, T, D) X(K, s, true, true, false, false, TN, T, D) \
+  X(K, c, true, true, true, false, TN, T, D) X(K, t, true, true, false, true, TN, T, D)
 #define MFA_DECODE_DEFINE(NAME, BOUNDS, BODY, ...)                                                                                    \
   extern "C" __global__ BOUNDS void NAME(const mfa::DecodeArgs a) { mfa::BODY<__VA_ARGS__>(a); }
 #define MFA_DECODE_DECLARE(NAME, BOUNDS, BODY, ...) extern "C" __global__ void NAME(const mfa::DecodeArgs a);
-#define MFA_DECODE_FAMILY(K, I, WINDOW, SINK, CAP, TN, T, D)                                                                          \
-  K(attn_decode16##I##_d##D##_##TN##_single, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, false, false, WINDOW, SINK, CAP) \
-  K(attn_decode16##I##_d##D##_##TN##_pieces, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, true, false, WINDOW, SINK, CAP)  \
-  K(attn_decode8##I##_d##D##_##TN##_single, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, false, true, WINDOW, SINK, CAP)   \
-  K(attn_decode8##I##_d##D##_##TN##_pieces, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, true, true, WINDOW, SINK, CAP)
+#define MFA_DECODE_FAMILY(K, I, WINDOW, SINK, CAP, TREE, TN, T, D)                                                                    \
+  K(attn_decode16##I##_d##D##_##TN##_single, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, false, false, WINDOW, SINK, CAP, TREE) \
+  K(attn_decode16##I##_d##D##_##TN##_pieces, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, true, false, WINDOW, SINK, CAP, TREE)  \
+  K(attn_decode8##I##_d##D##_##TN##_single, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, false, true, WINDOW, SINK, CAP, TREE)   \
+  K(attn_decode8##I##_d##D##_##TN##_pieces, __launch_bounds__(256, D == 256 ? 1 : 2), decode_body, T, D, true, true, WINDOW, SINK, CAP, TREE)
 #define MFA_DECODE_KERNELS(K, TN, T, D)                                                                                               \
   MFA_DECODE_FAMILIES(MFA_DECODE_FAMILY, K, TN, T, D)                                                                                 \
   K(attn_decode16_d##D##_##TN##_combine, __launch_bounds__(256), decode16_combine_body, T, D)

@@ -2,7 +2,8 @@
 // include/mfa_decode.h, the decode entries of include/mfa_kvcache.h and those of include/mfa_window.h (a sliding window: the same
 // plan with the piece count taken from the tiles a window can span, and the attn_decode16w_* / attn_decode8w_* kernels) and those of
 // include/mfa_sink.h (attention sinks: the window's plan plus the sink tiles, and the attn_decode16s_* / attn_decode8s_* kernels) and
-// those of include/mfa_softcap.h (a soft cap on the scores: the sink launch's plan, and the attn_decode16c_* / attn_decode8c_* kernels).  One
+// those of include/mfa_softcap.h (a soft cap on the scores: the sink launch's plan, and the attn_decode16c_* / attn_decode8c_* kernels) and
+// those of include/mfa_tree.h (a speculation tree among the new rows: the sink launch's plan again, and attn_decode16t_* / attn_decode8t_*).  One
 // plan serves both: the launch over an e4m3 cache adds its own checks in front of the 16-bit launch's, starts the attn_decode8_*
 // kernels in place of _single / _pieces, and shares the piece count, the workspace formula and the combine kernel.  The refusals of a
 // window and of sinks, and the Sinks of a launch, are cache_launch.h's, shared with attn_prefill16.hip.
@@ -19,6 +20,7 @@
 #include "../../include/mfa_kvcache.h"
 #include "../../include/mfa_sink.h"
 #include "../../include/mfa_softcap.h"
+#include "../../include/mfa_tree.h"
 #include "../../include/mfa_window.h"
 #include "attn_decode16.h"
 #include "cache_launch.h"
@@ -30,7 +32,8 @@ using namespace mfa;
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_decode16_d<D>_<type>_{single,pieces,combine} and, over
 // an e4m3 cache, attn_decode8_d<D>_<type of Q>_{single,pieces}, whose pieces attn_decode16_d<D>_<type>_combine merges; under a
 // sliding window attn_decode16w_* / attn_decode8w_*, with attention sinks attn_decode16s_* / attn_decode8s_*, with a soft cap (whatever
-// the window and sinks) attn_decode16c_* / attn_decode8c_*, merged by the same combine kernel
+// the window and sinks) attn_decode16c_* / attn_decode8c_*, with a speculation tree attn_decode16t_* / attn_decode8t_*, merged by the same
+// combine kernel
 // (the macros that generate them from one list of families: attn_decode16.h).  D = 256 lives in attn_decode16_d256.hip.
 MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, bf16, __bf16, 64)
 MFA_DECODE_KERNELS(MFA_DECODE_DEFINE, bf16, __bf16, 128)
@@ -49,11 +52,11 @@ struct DecodeSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  DecodeKernel kernel[4][2][2];   // [0: plain, 1: window, 2: sinks, 3: soft cap][fp8][pieces]
+  DecodeKernel kernel[5][2][2];   // [0: plain, 1: window, 2: sinks, 3: soft cap, 4: tree][fp8][pieces]
   DecodeKernel combine;
 };
 #define MFA_DECODE_ENTRY(NAME) {NAME, #NAME}
-#define MFA_DECODE_SET_FAMILY(K, I, WINDOW, SINK, CAP, TN, T, D)                                                                      \
+#define MFA_DECODE_SET_FAMILY(K, I, WINDOW, SINK, CAP, TREE, TN, T, D)                                                                     \
   {{MFA_DECODE_ENTRY(attn_decode16##I##_d##D##_##TN##_single), MFA_DECODE_ENTRY(attn_decode16##I##_d##D##_##TN##_pieces)},            \
    {MFA_DECODE_ENTRY(attn_decode8##I##_d##D##_##TN##_single), MFA_DECODE_ENTRY(attn_decode8##I##_d##D##_##TN##_pieces)}},
 #define MFA_DECODE_SET(TN, PREC, D)                                                                                                   \
@@ -91,7 +94,7 @@ struct DecodePlan {
   DecodeArgs args;
   const DecodeSet *set;
   bool fp8;
-  int family;           // 0: plain, 1: window, 2: sinks, 3: soft cap (whatever the window and sinks) -- the kernels' first index
+  int family;           // 0: plain, 1: window, 2: sinks, 3: soft cap, 4: tree (both whatever the window and sinks) -- the kernels' first index
   uint64_t tiles;       // what the piece count was chosen from
   uint32_t pieces;      // as the launch runs: 1 without a workspace
   uint32_t planned;     // what the host would cut the keys into
@@ -113,6 +116,7 @@ mfa_status DecodePlan::prepare(const mfa_decode_params *p, const LaunchOptions &
   if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   mfa_status allowed = check_window_and_sinks(window, sinks, p->causal != 0);
   if (allowed == MFA_OK) allowed = check_softcap(softcap);
+  if (allowed == MFA_OK) allowed = check_tree(options, p->causal != 0, p->rows, 0);   // (rows: G x rows <= 32 below)
   if (allowed != MFA_OK) return allowed;
   if (quant) {
     bool e4m3;
@@ -149,7 +153,7 @@ mfa_status DecodePlan::prepare(const mfa_decode_params *p, const LaunchOptions &
   this->set = set;
   fp8 = quant != nullptr;
   blocks = p->batches * (p->heads / G);
-  family = softcap != 0.0f ? 3 : sinks.any() ? 2 : window != 0;
+  family = options.tree ? 4 : softcap != 0.0f ? 3 : sinks.any() ? 2 : window != 0;
   tiles = planned_tiles(p->column, p->rows, window, sinks.tokens);
   planned = choose_pieces(blocks, tiles);
   pieces = planned;
@@ -215,14 +219,14 @@ mfa_status decode_launch_form(const mfa_decode_params *params, const LaunchOptio
   char text[512];
   const uint32_t M = plan.args.G * plan.args.R;
   // (a windowed launch names its window, its sink tokens and the tiles the piece count was chosen from; bound sink logits, then the
-  // soft cap, last)
+  // soft cap, then the tree, last)
   char cap[48] = "";
   if (options.softcap != 0.0f) std::snprintf(cap, sizeof(cap), ", softcap %g", (double)options.softcap);
   const std::string layout = std::string(plan.args.paged ? "paged" : "contiguous") +
                              (window ? ", window " + std::to_string(window) + (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : "") +
                                            ": planned from " + std::to_string(plan.tiles) + " tiles"
                                      : "") +
-                             (sinks.logits ? ", sink logits" : "") + cap;
+                             (sinks.logits ? ", sink logits" : "") + cap + tree_form(options);
   if (plan.pieces > 1)
     std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x K/V heads x %u pieces, %u packed rows, %s) + %s (grid %llu)", plan.name(),
                   plan.blocks * plan.pieces, plan.blocks, plan.pieces, M, layout.c_str(), plan.set->combine.name,
@@ -407,6 +411,46 @@ mfa_status mfa_attention_decode_softcap_time(const void *q, const void *k, const
                                              const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks, float softcap,
                                              void *stream, int warmup, int iterations, float *milliseconds) {
   return decode_time(q, k, v, o, l, params, LaunchOptions().cache(quant).within(window).optional_sinks(sinks).capped(softcap), stream, warmup, iterations, milliseconds);
+}
+
+// ---- with a speculation tree (include/mfa_tree.h): the sink entries with `tree` after `sinks`, which may be NULL here (no sinks).  The
+// tree block is required
+
+void mfa_attention_tree_init(mfa_attention_tree *tree) {
+  if (tree) std::memset(tree, 0, sizeof(*tree));
+}
+
+size_t mfa_attention_tree_size(void) { return sizeof(mfa_attention_tree); }
+
+mfa_status mfa_attention_tree_offsets(uint32_t *offsets, uint32_t capacity, uint32_t *count) {
+  if (!offsets || !count) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  static const uint32_t table[] = {(uint32_t)offsetof(mfa_attention_tree, masks), (uint32_t)offsetof(mfa_attention_tree, batchStride),
+                                   (uint32_t)offsetof(mfa_attention_tree, reserved)};
+  *count = 3;
+  for (uint32_t i = 0; i < 3 && i < capacity; ++i) offsets[i] = table[i];
+  return MFA_OK;
+}
+
+mfa_status mfa_attention_decode_tree_workspace_size(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
+                                                    const mfa_attention_sinks *sinks, const mfa_attention_tree *tree, uint64_t *bytes) {
+  return decode_workspace_size(params, LaunchOptions().cache(quant).within(window).optional_sinks(sinks).tree_of(tree), bytes);
+}
+
+mfa_status mfa_attention_decode_tree_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
+                                            const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks,
+                                            const mfa_attention_tree *tree, void *stream) {
+  return decode_launch(q, k, v, o, l, params, LaunchOptions().cache(quant).within(window).optional_sinks(sinks).tree_of(tree), stream);
+}
+
+mfa_status mfa_attention_decode_tree_launch_form(const mfa_decode_params *params, const mfa_kv_quant *quant, uint32_t window,
+                                                 const mfa_attention_sinks *sinks, const mfa_attention_tree *tree, char *out, size_t capacity) {
+  return decode_launch_form(params, LaunchOptions().cache(quant).within(window).optional_sinks(sinks).tree_of(tree), out, capacity);
+}
+
+mfa_status mfa_attention_decode_tree_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_decode_params *params,
+                                          const mfa_kv_quant *quant, uint32_t window, const mfa_attention_sinks *sinks,
+                                          const mfa_attention_tree *tree, void *stream, int warmup, int iterations, float *milliseconds) {
+  return decode_time(q, k, v, o, l, params, LaunchOptions().cache(quant).within(window).optional_sinks(sinks).tree_of(tree), stream, warmup, iterations, milliseconds);
 }
 
 } // extern "C"

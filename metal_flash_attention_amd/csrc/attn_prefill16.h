@@ -39,6 +39,12 @@
 //
 // CAP: the soft cap of attn_cache_step.h on the visible scores of every tile, the unmasked ones included; the SINK body otherwise (any
 // window and sinks, none included; RAGGED or not): c1 rides on kscale, c2 goes to score_max.
+//
+// TREE: the tree rule of attn_cache_step.h, the SINK body otherwise (any window and sinks, none included; not RAGGED, no CAP).  The lane's
+// mask is that of its ROW `row` -- never of its packed index; lanes that repeat the last live row read that row's mask, rows at or past qn
+// are never read.  A row's mask may name any new token and its depth is not its index, so every row block of a sequence walks the SAME
+// tiles, prefill_tree_tile_range's, through the four loops that exist: the tiles an earlier row block walks beyond its causal end are
+// fully masked for a chain (p = 0, the row maximum untouched, +0 added) and change no bit.
 #pragma once
 #include "attn_cache_step.h"
 #include "kv_e4m3.h"
@@ -75,7 +81,9 @@ struct PrefillArgs {
   const float *sinkLogits;        // [heads], natural units; null: none
   const uint32_t *rowStarts;      // the RAGGED kernels only: [batches + 1], packed rows (include/mfa_ragged.h); behind the sinks in turn
   uint32_t totalRows, slots;      // T; the slots of the grid (`rowBlocks` stays ceil(rows / RB))
-  float capIn, capOut;            // the CAP kernels only: c1 = 2 / cap and c2 = cap log2(e) (attn_cache_step.h); last in turn
+  float capIn, capOut;            // the CAP kernels only: c1 = 2 / cap and c2 = cap log2(e) (attn_cache_step.h); behind the ragged fields in turn
+  const uint64_t *masks;          // the TREE kernels only: [batches][rows] row masks (include/mfa_tree.h); last in turn
+  int64_t maskStride;             // elements between two sequences' masks; 0: one tree for all
 };
 
 // The tiles of the block of rows [r0, r0 + RB) of a sequence of n keys and qn rows.  Row r sees keys c < lim(r) = n, or with `causal`
@@ -161,6 +169,31 @@ __host__ __device__ __forceinline__ void prefill_sink_tile_range(uint32_t n, uin
   *sinkEnd = tiles < *begin ? (uint32_t)tiles : *begin;
 }
 
+// TREE (include/mfa_tree.h): the tiles EVERY row block of a sequence of n keys and qn rows walks under a speculation tree.  With P =
+// max(n - qn, 0), live = min(qn, n) and lo(f) = window ? max(f, window) - window : 0, a node's frontier lies in [P + 1, P + live]:
+//   *begin = floor(lo(P + 1) / 64), *end = ceil(n / 64): the tightest range that holds every key any row can see through its window;
+//   [*unmaskedBegin, *unmaskedEnd) = [ceil(lo(P + live) / 64), floor(P / 64)): the tiles whose every key is a prefix key inside every
+//   row's window -- key P itself is a tree key and masked; empty: both = *begin;
+//   *sinkEnd = min(ceil(min(S, P) / 64), *begin): the sink tiles walked ahead, with the per-element mask.
+// n = 0 or qn = 0: all 0.  Device and host (mfa_attention_prefill_tree_tile_range) run this one body.
+__host__ __device__ __forceinline__ void prefill_tree_tile_range(uint32_t n, uint32_t qn, uint32_t window, uint32_t sinkTokens, uint32_t *begin,
+                                                                 uint32_t *unmaskedBegin, uint32_t *unmaskedEnd, uint32_t *end, uint32_t *sinkEnd) {
+  *begin = *unmaskedBegin = *unmaskedEnd = *end = *sinkEnd = 0;
+  if (n == 0 || qn == 0) return;
+  const uint64_t P = n > qn ? (uint64_t)n - qn : 0, live = qn < n ? qn : n, W = window;
+  const uint64_t loFirst = W ? window_lo(P + 1, W) : 0, loLast = W ? window_lo(P + live, W) : 0;
+  const uint64_t b = loFirst / PF_TILE, e = ((uint64_t)n + PF_TILE - 1) / PF_TILE;
+  uint64_t u0 = (loLast + PF_TILE - 1) / PF_TILE, u1 = P / PF_TILE;
+  if (u0 >= u1) u0 = u1 = b;
+  const uint64_t sunk = sinkTokens < P ? sinkTokens : P;
+  const uint64_t tiles = (sunk + PF_TILE - 1) / PF_TILE;
+  *begin = (uint32_t)b;
+  *unmaskedBegin = (uint32_t)u0;
+  *unmaskedEnd = (uint32_t)u1;
+  *end = (uint32_t)e;
+  *sinkEnd = (uint32_t)(tiles < b ? tiles : b);
+}
+
 // RAGGED (include/mfa_ragged.h): which row block slot `slot` of a launch over packed rows serves.  Sequence b owns the packed rows
 // [s_b, s_b + qn_b), s_b = min(starts[b], T), e_b = min(starts[b + 1], T), qn_b = min(max(e_b - s_b, 0), rows), in ceil(qn_b / RB) row
 // blocks; the slots count the row blocks of sequence 0, then those of sequence 1, ...  *sequence = UINT32_MAX: a slot past the total.
@@ -226,8 +259,9 @@ __device__ __forceinline__ void prefill_ragged_block_wave(const uint32_t *starts
 
 template <int D> constexpr int prefill16_lds_bytes() { return 2 /*buffers*/ * 2 /*K, V*/ * PF_TILE * D * 2; }
 
-template <typename T, int D, bool FP8, bool WINDOW = false, bool SINK = false, bool RAGGED = false, bool CAP = false>
+template <typename T, int D, bool FP8, bool WINDOW = false, bool SINK = false, bool RAGGED = false, bool CAP = false, bool TREE = false>
 __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
+  static_assert(!TREE || (SINK && !RAGGED && !CAP), "the tree kernels are the sink kernels plus TREE");
   static_assert(!RAGGED || SINK, "the ragged kernels are the sink kernels plus RAGGED");
   static_assert(!CAP || SINK, "the capped kernels are the sink kernels plus CAP");
   typedef Frag16<T> F;
@@ -267,7 +301,8 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   if (r0 >= qn) return;   // no live row: nothing is read or written
   uint32_t firstMasked, endTile, beginTile = 0, unmaskedBegin = 0;   // (WINDOW: firstMasked is unmaskedEnd)
   uint32_t sinkEnd = 0;   // SINK: the tiles [0, sinkEnd) are walked ahead of [beginTile, endTile)
-  if constexpr (SINK) prefill_sink_tile_range(n, qn, r0, RB, a.causal, a.window, a.sinkTokens, &beginTile, &unmaskedBegin, &firstMasked, &endTile, &sinkEnd);
+  if constexpr (TREE) prefill_tree_tile_range(n, qn, a.window, a.sinkTokens, &beginTile, &unmaskedBegin, &firstMasked, &endTile, &sinkEnd);
+  else if constexpr (SINK) prefill_sink_tile_range(n, qn, r0, RB, a.causal, a.window, a.sinkTokens, &beginTile, &unmaskedBegin, &firstMasked, &endTile, &sinkEnd);
   else if constexpr (WINDOW) prefill_window_tile_range(n, qn, r0, RB, a.window, &beginTile, &unmaskedBegin, &firstMasked, &endTile);
   else prefill_tile_range(n, qn, r0, RB, a.causal, &firstMasked, &endTile);
   float kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
@@ -288,7 +323,17 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
     for (int s = 0; s < NKS; ++s) qf[s] = __builtin_bit_cast(v8, *reinterpret_cast<const u32x4 *>(qp + (16 * s + 8 * hi) * 2));
   }
   // keys this row sees
-  const VisibleKeys<WINDOW, SINK, CAP> keys(n, row + (n > qn ? n - qn : 0u) + 1u, a.causal, a.window, a.sinkTokens);
+  // (TREE: the row's mask, cut to the live nodes -- with n < qn keys the rows from n on have no key of their own)
+  const auto keys = [&]() MFA_PREFILL_INLINE {
+    if constexpr (TREE) {
+      const uint32_t liveNodes = min(qn, n);
+      const uint64_t word = a.masks[(int64_t)batch * a.maskStride + row];
+      const uint64_t mask = liveNodes < 64u ? word & ((1ull << liveNodes) - 1ull) : word;
+      return VisibleKeys<true, true, false, 64>(n, TreeRow{n > qn ? n - qn : 0u, mask}, a.window, a.sinkTokens);
+    } else {
+      return VisibleKeys<WINDOW, SINK, CAP>(n, row + (n > qn ? n - qn : 0u) + 1u, a.causal, a.window, a.sinkTokens);
+    }
+  }();
 
   // ---- addresses of a 16-key group (wave-uniform; element offsets from a.k / a.v)
   const int64_t ldk = a.ldk, ldv = a.ldv, psk = a.psk, psv = a.psv;   // (values, not fields of `a`: hipcc otherwise selects between
@@ -470,16 +515,18 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
 
 } // namespace mfa
 
-// One list of the kernel families, (infix, WINDOW, SINK, RAGGED, CAP): the kernels, the table that selects them (attn_prefill16.hip) and the
+// One list of the kernel families, (infix, WINDOW, SINK, RAGGED, CAP, TREE): the kernels, the table that selects them (attn_prefill16.hip) and the
 // names are generated from it.  MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, ...) is a set's code objects, in the translation unit that
 // holds them; (MFA_PREFILL_DECLARE, ...) names the kernels of another unit for the table.  D = 256 runs one workgroup per compute unit.
 #define MFA_PREFILL_FAMILIES(X, K, TN, T, D)                                                                                          \
-  X(K, , false, false, false, false, TN, T, D) X(K, w, true, false, false, false, TN, T, D) X(K, s, true, true, false, false, TN, T, D) \
-  X(K, r, true, true, true, false, TN, T, D) X(K, c, true, true, false, true, TN, T, D) X(K, rc, true, true, true, true, TN, T, D)
+  X(K, , false, false, false, false, false, TN, T, D) X(K, w, true, false, false, false, false, TN, T, D)                             \
+  X(K, s, true, true, false, false, false, TN, T, D) X(K, r, true, true, true, false, false, TN, T, D)                                \
+  X(K, c, true, true, false, true, false, TN, T, D) X(K, rc, true, true, true, true, false, TN, T, D)                                 \
+  X(K, t, true, true, false, false, true, TN, T, D)
 #define MFA_PREFILL_DEFINE(NAME, D, ...)                                                                                              \
   extern "C" __global__ __launch_bounds__(256, D == 256 ? 1 : 2) void NAME(const mfa::PrefillArgs a) { mfa::prefill16_body<__VA_ARGS__>(a); }
 #define MFA_PREFILL_DECLARE(NAME, D, ...) extern "C" __global__ void NAME(const mfa::PrefillArgs a);
-#define MFA_PREFILL_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TN, T, D)                                                                 \
-  K(attn_prefill16##I##_d##D##_##TN, D, T, D, false, WINDOW, SINK, RAGGED, CAP)                                                       \
-  K(attn_prefill16##I##_d##D##_##TN##_e4m3, D, T, D, true, WINDOW, SINK, RAGGED, CAP)
+#define MFA_PREFILL_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TREE, TN, T, D)                                                           \
+  K(attn_prefill16##I##_d##D##_##TN, D, T, D, false, WINDOW, SINK, RAGGED, CAP, TREE)                                                 \
+  K(attn_prefill16##I##_d##D##_##TN##_e4m3, D, T, D, true, WINDOW, SINK, RAGGED, CAP, TREE)
 #define MFA_PREFILL_KERNELS(K, TN, T, D) MFA_PREFILL_FAMILIES(MFA_PREFILL_FAMILY, K, TN, T, D)

@@ -1,7 +1,8 @@
 // attn_prefill16.hip -- prefill attention over a KV cache: the kernels' code objects, the C ABI of include/mfa_prefill.h and the prefill
 // entries of include/mfa_window.h (a sliding window: the same checks and grid, the attn_prefill16w_* kernels) and of include/mfa_sink.h
 // (attention sinks: the attn_prefill16s_* kernels), the prefill entries of include/mfa_ragged.h (packed rows: attn_prefill16r_*) and
-// those of include/mfa_softcap.h (a soft cap on the scores: attn_prefill16c_*, over packed rows attn_prefill16rc_*).
+// those of include/mfa_softcap.h (a soft cap on the scores: attn_prefill16c_*, over packed rows attn_prefill16rc_*) and those of
+// include/mfa_tree.h (a speculation tree among the new rows: attn_prefill16t_*).
 // The refusals of a window and of sinks, and the Sinks of a launch, are cache_launch.h's, shared with attn_decode16.hip.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 #include "../../include/mfa_ragged.h"
 #include "../../include/mfa_sink.h"
 #include "../../include/mfa_softcap.h"
+#include "../../include/mfa_tree.h"
 #include "../../include/mfa_window.h"
 #include "attn_prefill16.h"
 #include "cache_launch.h"
@@ -26,7 +28,8 @@ using namespace mfa;
 
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_prefill16_d<D>_<type>[_e4m3], and attn_prefill16w_*
 // under a sliding window, attn_prefill16s_* with attention sinks, attn_prefill16r_* over packed rows (the sink body: one ragged kernel
-// serves plain, window and sink launches), attn_prefill16c_* / attn_prefill16rc_* with a soft cap (the sink body and the ragged one)
+// serves plain, window and sink launches), attn_prefill16c_* / attn_prefill16rc_* with a soft cap (the sink body and the ragged one),
+// attn_prefill16t_* with a speculation tree (the sink body)
 // (the macros that generate them from one list of families: attn_prefill16.h).  D = 256 lives in attn_prefill16_d256.hip.
 MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, bf16, __bf16, 64)
 MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, bf16, __bf16, 128)
@@ -45,10 +48,10 @@ struct PrefillSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  PrefillKernel kernel[6][2];   // [0: plain, 1: window, 2: sinks, 3: ragged, 4: soft cap, 5: ragged with a soft cap][e4m3]
+  PrefillKernel kernel[7][2];   // [0: plain, 1: window, 2: sinks, 3: ragged, 4: soft cap, 5: ragged with a soft cap, 6: tree][e4m3]
 };
 #define MFA_PREFILL_ENTRY(NAME) {NAME, #NAME}
-#define MFA_PREFILL_SET_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TN, T, D)                                                             \
+#define MFA_PREFILL_SET_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TREE, TN, T, D)                                                           \
   {MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN), MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN##_e4m3)},
 #define MFA_PREFILL_SET(TN, PREC, D) {D, PREC, (uint32_t)prefill16_lds_bytes<D>(), {MFA_PREFILL_FAMILIES(MFA_PREFILL_SET_FAMILY, , TN, , D)}}
 const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(bf16, MFA_BF16, 256),
@@ -64,7 +67,7 @@ struct PrefillPlan {
   PrefillArgs args;
   const PrefillSet *set;
   bool fp8;
-  int family;        // 0: plain, 1: window, 2: sinks, 3: ragged, 4 / 5: padded / ragged with a soft cap -- the kernels' first index
+  int family;        // 0: plain, 1: window, 2: sinks, 3: ragged, 4 / 5: padded / ragged with a soft cap, 6: tree -- the kernels' first index
   uint32_t blocks;   // batches x K/V heads x row blocks; ragged: slots x K/V heads
   const PrefillKernel &kernel() const { return set->kernel[family][fp8]; }
   const char *name() const { return kernel().name; }
@@ -90,6 +93,7 @@ mfa_status PrefillPlan::prepare(const mfa_prefill_params *p, const LaunchOptions
   }
   mfa_status allowed = check_window_and_sinks(options.window, options.sinks, p->causal != 0);
   if (allowed == MFA_OK) allowed = check_softcap(options.softcap);
+  if (allowed == MFA_OK) allowed = check_tree(options, p->causal != 0, p->rows, MFA_TREE_MAX_NODES);
   if (allowed != MFA_OK) return allowed;
   if (p->precision == MFA_FP32)
     return fail(MFA_ERR_UNSUPPORTED, "prefill attention takes a 16-bit Q (precision MFA_BF16 or MFA_FP16); FP32 Q has no kernel");
@@ -126,7 +130,7 @@ mfa_status PrefillPlan::prepare(const mfa_prefill_params *p, const LaunchOptions
   } else if (blocks > 0x7fffffffull)
     return fail(MFA_ERR_UNSUPPORTED, "batches x K/V heads x row blocks = " + std::to_string(blocks) + " workgroups exceed one grid (2^31 - 1)");
   this->set = set;
-  family = options.softcap != 0.0f ? (ragged ? 5 : 4) : ragged ? 3 : options.sinks.any() ? 2 : options.window != 0;
+  family = options.tree ? 6 : options.softcap != 0.0f ? (ragged ? 5 : 4) : ragged ? 3 : options.sinks.any() ? 2 : options.window != 0;
   this->blocks = (uint32_t)blocks;
   PrefillArgs &a = args;
   set_shared_args(a, p, G, pageShift, options);
@@ -157,11 +161,12 @@ mfa_status prefill_launch_form(const mfa_prefill_params *params, const LaunchOpt
   const PrefillArgs &a = plan.args;
   const Sinks &sinks = options.sinks;
   char text[512];
-  // (a windowed launch names its window, then its sink tokens; bound sink logits, then the soft cap, last)
+  // (a windowed launch names its window, then its sink tokens; bound sink logits, then the soft cap, then the tree, last)
   char cap[48] = "";
   if (options.softcap != 0.0f) std::snprintf(cap, sizeof(cap), ", softcap %g", (double)options.softcap);
   const std::string tail = (options.window ? ", window " + std::to_string(options.window) : std::string()) +
-                           (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : std::string()) + (sinks.logits ? ", sink logits" : "") + cap;
+                           (sinks.tokens ? ", sink tokens " + std::to_string(sinks.tokens) : std::string()) + (sinks.logits ? ", sink logits" : "") + cap +
+                           tree_form(options);
   if (options.ragged)
     std::snprintf(text, sizeof(text), "%s (grid %u = %u slots x %u K/V heads, row blocks of %u rows x %u heads, %u packed rows of %u sequences, at most %u rows each, %s%s)",
                   plan.name(), plan.blocks, a.slots, a.Hkv, a.RB, a.G, a.totalRows, a.batches, a.rows, a.paged ? "paged" : "contiguous", tail.c_str());
@@ -366,6 +371,33 @@ mfa_status mfa_attention_prefill_ragged_softcap_time(const void *q, const void *
                                                      const mfa_ragged_rows *ragged, float softcap, void *stream, int warmup, int iterations,
                                                      float *milliseconds) {
   return prefill_time(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).ragged_of(ragged).capped(softcap), stream, warmup, iterations, milliseconds);
+}
+
+// ---- with a speculation tree (include/mfa_tree.h): the sink entries with `tree` after `sinks`; a NULL `sinks` is no sinks, the tree
+// block is required (mfa_attention_tree_init and its size / offsets: attn_decode16.hip)
+
+mfa_status mfa_attention_prefill_tree_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                             uint32_t window, const mfa_attention_sinks *sinks, const mfa_attention_tree *tree, void *stream) {
+  return prefill_launch(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).tree_of(tree), stream);
+}
+
+mfa_status mfa_attention_prefill_tree_launch_form(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
+                                                  const mfa_attention_tree *tree, char *out, size_t capacity) {
+  return prefill_launch_form(params, LaunchOptions().within(window).optional_sinks(sinks).tree_of(tree), out, capacity);
+}
+
+mfa_status mfa_attention_prefill_tree_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                           uint32_t window, const mfa_attention_sinks *sinks, const mfa_attention_tree *tree, void *stream,
+                                           int warmup, int iterations, float *milliseconds) {
+  return prefill_time(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).tree_of(tree), stream, warmup, iterations, milliseconds);
+}
+
+mfa_status mfa_attention_prefill_tree_tile_range(uint32_t length, uint32_t queryLength, uint32_t window, uint32_t sinkTokens, uint32_t *begin,
+                                                 uint32_t *unmaskedBegin, uint32_t *unmaskedEnd, uint32_t *end, uint32_t *sinkEnd) {
+  if (!begin || !unmaskedBegin || !unmaskedEnd || !end || !sinkEnd) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (sinkTokens && !window) return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens must be 0 when window is 0");
+  prefill_tree_tile_range(length, queryLength, window, sinkTokens, begin, unmaskedBegin, unmaskedEnd, end, sinkEnd);
+  return MFA_OK;
 }
 
 } // extern "C"

@@ -108,6 +108,14 @@ LaunchOptions &LaunchOptions::ragged_of(const mfa_ragged_rows *block) {
   return *this;
 }
 
+LaunchOptions &LaunchOptions::tree_of(const mfa_attention_tree *block) {
+  tree = block;
+  if (!block && !refusal)
+    refusal = "null mfa_attention_tree: the tree entries require the block (mfa_attention_tree_init; a launch "
+              "whose new rows see each other causally: the mfa_sink.h entries)";
+  return *this;
+}
+
 mfa_status entry_check(const LaunchOptions &options, const char *bad) {
   if (options.refusal && (options.refusalFirst || !bad)) return fail(MFA_ERR_INVALID_ARGUMENT, options.refusal);
   return bad ? fail(MFA_ERR_INVALID_ARGUMENT, bad) : MFA_OK;
@@ -132,6 +140,36 @@ mfa_status check_softcap(float softcap) {
     return fail(MFA_ERR_INVALID_ARGUMENT, "softcap must be 0 (no cap) or a finite positive number, the cap of cap x tanh(score / cap) in "
                                           "natural-log units (a checkpoint's attn_logit_softcapping), not " + std::to_string(softcap));
   return MFA_OK;
+}
+
+mfa_status check_tree(const LaunchOptions &options, bool causal, uint32_t rows, uint32_t rowLimit) {
+  const mfa_attention_tree *tree = options.tree;
+  if (!tree) return MFA_OK;
+  if (!causal)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "a speculation tree needs causal: the tree replaces the causal rule among the new rows, which "
+                                          "sit behind the cached prefix");
+  if (options.window && options.window < rows)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "a speculation tree needs a window of at least `rows` keys (or 0: none): window = " +
+                                              std::to_string(options.window) + " < rows = " + std::to_string(rows) +
+                                              " could leave an ancestor outside a descendant's window");
+  if (rowLimit && rows > rowLimit)
+    return fail(MFA_ERR_UNSUPPORTED, "a speculation tree holds at most " + std::to_string(rowLimit) +
+                                         " nodes, one bit of a uint64 mask each: rows = " + std::to_string(rows));
+  if (!tree->masks)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_attention_tree.masks is required (device array of uint64, [batches][rows], one mask per new row)");
+  if ((uintptr_t)tree->masks % 8) return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_attention_tree.masks must be 8-byte aligned");
+  if (tree->batchStride < 0 || (tree->batchStride != 0 && (uint64_t)tree->batchStride < rows))
+    return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_attention_tree.batchStride must be 0 (one tree shared by every sequence) or at least `rows` elements");
+  if (options.softcap != 0.0f)
+    return fail(MFA_ERR_UNSUPPORTED, "a soft cap together with a speculation tree has no kernel: softcap must be 0 with a tree");
+  if (options.ragged)
+    return fail(MFA_ERR_UNSUPPORTED, "a ragged launch together with a speculation tree has no kernel: a tree needs padded rows (queryLengths)");
+  return MFA_OK;
+}
+
+std::string tree_form(const LaunchOptions &options) {
+  if (!options.tree) return std::string();
+  return options.tree->batchStride ? ", tree masks per sequence" : ", tree masks shared";
 }
 
 } // namespace mfa

@@ -1,7 +1,7 @@
 // cache_launch.h -- what the host sides of the launches over a KV cache share (attn_decode16.hip, attn_prefill16.hip,
 // kv_cache_append.hip): the checks of paging, operand strides, cache precision and buffer pointers, and of a sliding window and
-// attention sinks (Sinks, check_window_and_sinks: decode and prefill) and of a soft cap (check_softcap), each with ONE wording, so that
-// the same mistake is refused in the same words whichever launch meets it; the options of a launch as one value (LaunchOptions), and the
+// attention sinks (Sinks, check_window_and_sinks: decode and prefill), of a soft cap (check_softcap) and of a speculation tree
+// (check_tree), each with ONE wording, so that the same mistake is refused in the same words whichever launch meets it; the options of a launch as one value (LaunchOptions), and the
 // path every decode and prefill entry takes from it: the checks both launches word alike (check_precisions ... check_cache_and_strides), bind, and the bodies
 // of the launch and time entries (cache_launch, cache_time).  hip_fail, copy_text and time_launches also serve mfa_kernel.hip.
 // Internal, not part of the ABI.  Every check records its message (fail, mfa_internal.h) and returns the status.
@@ -17,6 +17,7 @@
 #include "../../include/mfa_kvcache.h"
 #include "../../include/mfa_ragged.h"
 #include "../../include/mfa_sink.h"
+#include "../../include/mfa_tree.h"
 #include "mfa_internal.h"
 
 namespace mfa {
@@ -56,9 +57,15 @@ struct Sinks {
 mfa_status check_window_and_sinks(uint32_t window, const Sinks &sinks, bool causal);
 // the soft cap of a launch (include/mfa_softcap.h): 0 is none, anything but a finite positive number is refused
 mfa_status check_softcap(float softcap);
+struct LaunchOptions;
+// the tree of a launch (include/mfa_tree.h; none: MFA_OK): it needs causal, a window of 0 or at least `rows` keys, at most `rowLimit`
+// rows (0: the launch has its own limit), masks that are bound and 8-byte aligned, and neither a soft cap nor packed rows -- in this order
+mfa_status check_tree(const LaunchOptions &options, bool causal, uint32_t rows, uint32_t rowLimit);
+// ", tree masks" and how they are shared, for a launch form; empty without a tree
+std::string tree_form(const LaunchOptions &options);
 
-// The options of a launch beside its params: what the entry families of mfa_kvcache.h (fp8_), mfa_window.h, mfa_sink.h, mfa_ragged.h and
-// mfa_softcap.h add to the plain entries, as ONE value that every function below an entry takes.  An entry builds it in one statement
+// The options of a launch beside its params: what the entry families of mfa_kvcache.h (fp8_), mfa_window.h, mfa_sink.h, mfa_ragged.h,
+// mfa_softcap.h and mfa_tree.h add to the plain entries, as ONE value that every function below an entry takes.  An entry builds it in one statement
 // from the setters, each of which carries its argument's NULL rule in that family's words; a new option is a member, a setter and the
 // places that read it.
 struct LaunchOptions {
@@ -67,6 +74,7 @@ struct LaunchOptions {
   Sinks sinks;
   const mfa_ragged_rows *ragged = nullptr;   // prefill over packed rows; null: padded
   float softcap = 0.0f;                      // 0: none
+  const mfa_attention_tree *tree = nullptr;  // a speculation tree among the new rows; null: the causal rule
   const char *refusal = nullptr;             // a block the family requires is NULL: what entry_check answers
   bool refusalFirst = true;                  // ... before the entry's own arguments are looked at (fp8_: after)
 
@@ -77,6 +85,7 @@ struct LaunchOptions {
   LaunchOptions &optional_sinks(const mfa_attention_sinks *block);   // the ragged_ and softcap_ entries: NULL is no sinks
   LaunchOptions &ragged_of(const mfa_ragged_rows *block);            // the ragged_ entries: required
   LaunchOptions &capped(float cap) { softcap = cap; return *this; }
+  LaunchOptions &tree_of(const mfa_attention_tree *block);           // the tree_ entries: required
 };
 // what an entry answers before its launch is prepared: the options' refusal and `bad`, what is wrong with the entry's own arguments
 // (null: nothing), in the family's order
@@ -134,6 +143,10 @@ void set_shared_args(Args &a, const Params *p, uint32_t G, uint32_t pageShift, c
   if (options.softcap != 0.0f) {   // cap x tanh(s / cap) in the kernels' log2 units
     a.capIn = 2.0f / options.softcap;
     a.capOut = options.softcap * 1.44269504089f;
+  }
+  if (options.tree) {
+    a.masks = options.tree->masks;
+    a.maskStride = options.tree->batchStride;
   }
 }
 

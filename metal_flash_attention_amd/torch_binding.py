@@ -277,6 +277,16 @@ def pack_block_mask(bits: torch.Tensor) -> torch.Tensor:
     return torch.where(packed >= 2 ** 31, packed - 2 ** 32, packed).to(torch.int32)
 
 
+def pack_tree_mask(bits: torch.Tensor) -> torch.Tensor:
+    """bool [..., R, R] (row r sees new token j: bits[..., r, j]; R <= 64) -> int64 [..., R], the bit pattern of the uint64 row masks
+    flash_decode and flash_prefill take as tree_mask= (include/mfa_tree.h): bit j of entry r is bits[..., r, j]."""
+    if bits.dim() < 2 or bits.shape[-1] != bits.shape[-2] or not 1 <= bits.shape[-1] <= 64:
+        raise ValueError(f"pack_tree_mask: expected bool [..., R, R] with R from 1 to 64 (got {tuple(bits.shape)})")
+    R = bits.shape[-1]
+    weights = torch.tensor([(1 << j) if j < 63 else -(1 << 63) for j in range(R)], dtype=torch.int64, device=bits.device)
+    return (bits.to(torch.int64) * weights).sum(-1)   # (distinct bits: the sum is their OR, bit 63 the sign)
+
+
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False,
                     q_lengths: torch.Tensor = None, k_lengths: torch.Tensor = None,
                     block_mask: torch.Tensor = None, fast_scale: bool = False) -> torch.Tensor:
@@ -415,7 +425,7 @@ def _packed_operand(t):
     return t, (int(t.stride(0)) if T > 1 else heads * D, int(t.stride(1)) if heads > 1 else D, 0)
 
 
-def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, softcap, workspace=False):
+def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, softcap, workspace=False, tree=None):
     """the launch of a decode or prefill host object over `kw`, on q's device and torch's current stream -> (O, L).  window, sinks -- (sink
     tokens or 0, sink logits or None) -- and softcap: None is none, and anything else reaches the entries of its header, a window 0 and
     sinks (0, None) too.  (Rows the launch does not own -- past q_lengths[b], or packed rows of no sequence -- are not written: no memset
@@ -426,6 +436,8 @@ def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, softcap, work
         kw["sinkTokens"], kw["sinkLogits"] = int(sinks[0]), sinks[1]
     if softcap is not None:   # the entries of include/mfa_softcap.h
         kw["softcap"] = float(softcap)
+    if tree is not None:   # [R] or [B, R] int64 on the GPU: the entries of include/mfa_tree.h
+        kw["treeMasks"], kw["treeBatchStride"] = tree, int(tree.stride(0)) if tree.dim() == 2 else 0
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     l = torch.empty(l_shape, dtype=torch.float32, device=q.device)
     if workspace:
@@ -436,7 +448,8 @@ def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, softcap, work
     return o, l
 
 
-def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None, sinks=None, softcap=None):
+def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=False, k_scale=None, v_scale=None, window=None, sinks=None, softcap=None,
+                tree=None):
     """`fp8`: what the op says the caches are (None: what they say themselves -- the window, sink and soft-cap ops serve 16-bit and e4m3 caches alike)"""
     if fp8 is None:
         fp8 = k_cache.dtype in _FP8_DTYPES or v_cache.dtype in _FP8_DTYPES
@@ -444,7 +457,8 @@ def _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, fp8=Fal
     q, kw["strides"]["Q"] = _new_operand(q)
     _B, H, R, D = q.shape
     kw.update(rows=R, heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal))
-    return _attend(_host(AttentionDecode, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, softcap, workspace=True)
+    return _attend(_host(AttentionDecode, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, softcap, workspace=True,
+                   tree=None if tree is None else _tree_operand("flash_decode", tree, B, R))
 
 
 def _sinks_or_none(sink_tokens, sink_logits):
@@ -452,7 +466,8 @@ def _sinks_or_none(sink_tokens, sink_logits):
     return (sink_tokens, sink_logits) if sink_tokens or sink_logits is not None else None
 
 
-def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None, sinks=None, softcap=None):
+def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None, sinks=None, softcap=None,
+                 tree=None):
     who = "flash_prefill"
     fp8, B, kw = _cache_side(who, (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
     if q_lengths is not None:
@@ -461,7 +476,8 @@ def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, cau
     _B, H, R, D = q.shape
     kw.update(rows=R, heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal),
               queryLengths=None if q_lengths is None else q_lengths.to(torch.int32))
-    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, softcap)
+    return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, softcap,
+                   tree=None if tree is None else _tree_operand(who, tree, B, R))
 
 
 def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window, sinks, softcap=None):
@@ -496,6 +512,30 @@ def _run_append(k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_sc
 
 def _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale):
     _append("kv_cache_append_ragged", _packed_operand, k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, row_starts, max_rows)
+
+
+def _check_tree(who, q, tree_mask, causal, window, softcap):
+    """tree_mask= of a public function: an int64 tensor [R] or [B, R] on q's device; causal, no cap, a window of at least R"""
+    R, B = (q.shape[2], q.shape[0]) if q.dim() == 4 else (None, None)
+    if not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype != torch.int64 or R is None or tuple(tree_mask.shape) not in ((R,), (B, R)):
+        got = f"{tuple(tree_mask.shape)}, {tree_mask.dtype}" if isinstance(tree_mask, torch.Tensor) else type(tree_mask).__name__
+        raise ValueError(f"{who}: tree_mask must be an int64 tensor [R] = [{R}] (one tree for every sequence) or [B, R] = [{B}, {R}], the bit "
+                         f"patterns of uint64 row masks (pack_tree_mask; got {got})")
+    if tree_mask.device != q.device:
+        raise RuntimeError(f"{who}: tree_mask must live on q's device (the host never reads a mask)")
+    if not causal:
+        raise ValueError(f"{who}: tree_mask needs causal=True (the tree replaces the causal rule among the new rows)")
+    if softcap is not None:
+        raise ValueError(f"{who}: tree_mask and softcap together have no kernel (include/mfa_tree.h)")
+    if window is not None and isinstance(window, int) and window < R:
+        raise ValueError(f"{who}: tree_mask needs a window of at least R = {R} keys (an ancestor could fall outside a descendant's window), not {window}")
+
+
+def _tree_operand(who, tree, B, R):
+    """the masks as the kernels read them: rows of R contiguous uint64"""
+    if tuple(tree.shape) not in ((R,), (B, R)) or tree.dtype != torch.int64:
+        raise ValueError(f"{who}: tree_mask must be int64 [R] = [{R}] or [B, R] = [{B}, {R}] (got {tuple(tree.shape)}, {tree.dtype})")
+    return tree if tree.stride(-1) == 1 and (tree.dim() == 1 or tree.stride(0) >= R) else tree.contiguous()
 
 
 def _check_window(who, window, causal):
@@ -572,6 +612,13 @@ def _op_decode_softcap(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
                        _sinks_or_none(sink_tokens, sink_logits), softcap)
 
 
+def _op_decode_tree(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                    block_table: Optional[torch.Tensor], causal: bool, k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor],
+                    window: int, sink_tokens: int, sink_logits: Optional[torch.Tensor], tree_mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_decode(q, k_cache, v_cache, cache_lengths, block_table, causal, None, k_scale, v_scale, window or None,
+                       _sinks_or_none(sink_tokens, sink_logits), None, tree_mask)
+
+
 def _op_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                 q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
                 k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -606,6 +653,14 @@ def _op_prefill_softcap(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.T
                         sink_logits: Optional[torch.Tensor], softcap: float) -> Tuple[torch.Tensor, torch.Tensor]:
     return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window or None,
                         _sinks_or_none(sink_tokens, sink_logits), softcap)
+
+
+def _op_prefill_tree(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                     q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
+                     k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
+                     sink_logits: Optional[torch.Tensor], tree_mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window or None,
+                        _sinks_or_none(sink_tokens, sink_logits), None, tree_mask)
 
 
 def _op_prefill_ragged_softcap(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
@@ -663,7 +718,8 @@ def _call_op(have, name, *args):
 
 
 # the ops: (name, implementation, fake, mutated arguments).  16-bit and e4m3 caches share one window op, one sink op and one soft-cap op
-# per launch kind (`window` 0 and `sink_tokens` 0: none; `softcap` > 0 last); the ops before them keep their schemas
+# per launch kind (`window` 0 and `sink_tokens` 0: none; `softcap` > 0 last), and one tree op (`tree_mask` last); the ops before them keep
+# their schemas
 _CACHE_OPS = [
     ("attention_decode", _op_decode, _fake_padded, ()),
     ("attention_decode_fp8", _op_decode_fp8, _fake_padded, ()),
@@ -678,6 +734,8 @@ _CACHE_OPS = [
     ("attention_decode_softcap", _op_decode_softcap, _fake_padded, ()),
     ("attention_prefill_softcap", _op_prefill_softcap, _fake_padded, ()),
     ("attention_prefill_ragged_softcap", _op_prefill_ragged_softcap, _fake_packed, ()),
+    ("attention_decode_tree", _op_decode_tree, _fake_padded, ()),
+    ("attention_prefill_tree", _op_prefill_tree, _fake_padded, ()),
 ]
 _HAVE = {_op[0]: _register_cache_op(*_op) for _op in _CACHE_OPS}   # op name -> whether torch has it as a custom op
 _HAVE_DECODE_OP = _HAVE["attention_decode"]
@@ -687,6 +745,7 @@ _HAVE_WINDOW_OPS = _HAVE["attention_decode_window"] and _HAVE["attention_prefill
 _HAVE_SINK_OPS = _HAVE["attention_decode_sink"] and _HAVE["attention_prefill_sink"]
 _HAVE_RAGGED_OPS = _HAVE["attention_prefill_ragged"] and _HAVE["kv_cache_append_ragged"]
 _HAVE_SOFTCAP_OPS = _HAVE["attention_decode_softcap"] and _HAVE["attention_prefill_softcap"] and _HAVE["attention_prefill_ragged_softcap"]
+_HAVE_TREE_OPS = _HAVE["attention_decode_tree"] and _HAVE["attention_prefill_tree"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -709,19 +768,21 @@ class _Public:
     """what _route knows of a public function: its name in messages, the op of each rung (none: the function has no such rung and its
     plain op takes the rung's arguments), whether the scales go in front of a rung's arguments (prefill's ops all take them earlier)"""
 
-    def __init__(self, who, plain, fp8=None, window=None, sink=None, softcap=None, scales=False, packed=False):
+    def __init__(self, who, plain, fp8=None, window=None, sink=None, softcap=None, scales=False, packed=False, tree=None):
         self.who, self.plain, self.fp8, self.window, self.sink, self.softcap, self.scales, self.packed = who, plain, fp8, window, sink, softcap, scales, packed
+        self.tree = tree
 
 
 _DECODE = _Public("flash_decode", "attention_decode", "attention_decode_fp8", "attention_decode_window", "attention_decode_sink",
-                  "attention_decode_softcap", scales=True)
-_PREFILL = _Public("flash_prefill", "attention_prefill", None, "attention_prefill_window", "attention_prefill_sink", "attention_prefill_softcap")
+                  "attention_decode_softcap", scales=True, tree="attention_decode_tree")
+_PREFILL = _Public("flash_prefill", "attention_prefill", None, "attention_prefill_window", "attention_prefill_sink", "attention_prefill_softcap",
+                   tree="attention_prefill_tree")
 _PREFILL_RAGGED = _Public("flash_prefill_ragged", "attention_prefill_ragged", softcap="attention_prefill_ragged_softcap", packed=True)
 
 
-def _route(f, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap):
+def _route(f, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap, tree_mask=None):
     """The keywords of the public function `f` (a _Public), checked in one order -- the cap, then the window, the sink tokens and the sink
-    logits -- and the op they reach -> (op, the arguments it takes after causal, or after the scales where they come earlier), in the ops'
+    logits, then the tree, which reaches the tree op with any window and sinks -- and the op they reach -> (op, the arguments it takes after causal, or after the scales where they come earlier), in the ops'
     spelling: 0 for no window and no sink tokens.  A cap wins over all, either sink keyword reaches the sink op, a window the window op"""
     who = f.who
     if softcap is not None:
@@ -731,6 +792,9 @@ def _route(f, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens
         # (_check_sinks reads the heads off a [B, H, R, D] query: the packed q of a ragged batch as such a view)
         _check_sinks(who, q.unsqueeze(0).transpose(1, 2) if f.packed and q.dim() == 3 else q, window, causal, sink_tokens, sink_logits)
     scales = (k_scale, v_scale) if f.scales else ()
+    if tree_mask is not None:
+        _check_tree(who, q, tree_mask, causal, window, softcap)
+        return f.tree, (*scales, window or 0, sink_tokens or 0, sink_logits, tree_mask)
     if softcap is not None:
         return f.softcap, (*scales, window or 0, sink_tokens or 0, sink_logits, float(softcap))
     if f.sink is None or sinks:   # (a function without a sink op: its plain op takes the window and the sinks)
@@ -762,7 +826,8 @@ def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Ten
 def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                  block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False,
                  k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, window: Optional[int] = None,
-                 sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None, softcap: Optional[float] = None):
+                 sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None, softcap: Optional[float] = None,
+                 tree_mask: Optional[torch.Tensor] = None):
     """Attention of the R new rows of every sequence (q [B, H, R, D]; R = 1, or a few speculative tokens; G R <= 32 with G = H / Hkv)
     against its KV cache.  cache_lengths [B] (GPU, int32): valid keys per sequence INCLUDING the R new tokens, which the caller has
     already written into the cache; with `causal` row r sees key c iff c <= r + max(len - R, 0).  Caches: [B, Hkv, C, D], or any view
@@ -784,9 +849,14 @@ def flash_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     softcap=cap (a finite number > 0, natural-log units: a checkpoint's attn_logit_softcapping, 50 in Gemma 2): the softmax sees
     cap tanh(score / cap), the score with 1 / sqrt(D) and k_scale applied; masked keys stay masked, the sink logit is not capped, L is
     that of the capped scores (include/mfa_softcap.h).  With any window and sinks, through the op `mfa::attention_decode_softcap`.
-    None: no cap."""
+    None: no cap.
+    tree_mask=int64 [R] (one tree for every sequence) or [B, R] on the GPU, the bit patterns of uint64 row masks (pack_tree_mask): the R new
+    rows are the nodes of a speculation TREE, node j at key len - R + j -- row r sees new token j iff bit j of its mask is set, whatever r
+    and j, and sees the cached prefix through the window at its depth, popcount(mask) - 1, not at its index (include/mfa_tree.h).  Needs
+    causal and, with a window, window >= R; not with softcap.  The chain mask 2^(r + 1) - 1 is the launch without a tree, bit for bit.
+    Through the op `mfa::attention_decode_tree`, with any window and sinks.  None: the causal rule."""
     _forward_only("flash_decode", q, k_cache, v_cache, cache_lengths)
-    op, own = _route(_DECODE, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap)
+    op, own = _route(_DECODE, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap, tree_mask)
     o, l = _call_op(_HAVE[op], op, q, k_cache, v_cache, cache_lengths, block_table, causal, *own)
     return (o, l * _LN2) if return_lse else o
 
@@ -795,7 +865,7 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                   q_lengths: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None, causal: bool = True,
                   k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, return_lse: bool = False,
                   window: Optional[int] = None, sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None,
-                  softcap: Optional[float] = None):
+                  softcap: Optional[float] = None, tree_mask: Optional[torch.Tensor] = None):
     """Attention of a BLOCK of new rows of every sequence (q [B, H, R, D], any R: a chunk of a prompt, a reused prefix's tail, a long
     speculative block) against its KV cache, which already holds the new tokens (kv_cache_append first).  cache_lengths [B] (GPU):
     valid keys per sequence INCLUDING the new tokens; q_lengths [B] (GPU, None = R for every sequence): the new rows of sequence b,
@@ -809,9 +879,11 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     flash_decode's, through the op `mfa::attention_prefill_window`; None: no window.  sink_tokens / sink_logits: attention sinks as
     flash_decode's (include/mfa_sink.h), through the op `mfa::attention_prefill_sink`; a live row without a visible key then gets
     L = the head's sink logit.  softcap=cap: logit soft-capping as flash_decode's (include/mfa_softcap.h), with any window and sinks,
-    through the op `mfa::attention_prefill_softcap`; None: no cap."""
+    through the op `mfa::attention_prefill_softcap`; None: no cap.  tree_mask=int64 [R] or [B, R]: a speculation tree among the new rows as
+    flash_decode's (include/mfa_tree.h; R <= 64, trees of different sizes through q_lengths), through the op `mfa::attention_prefill_tree`;
+    None: the causal rule."""
     _forward_only("flash_prefill", q, k_cache, v_cache, cache_lengths)
-    op, own = _route(_PREFILL, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap)
+    op, own = _route(_PREFILL, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap, tree_mask)
     o, l = _call_op(_HAVE[op], op, q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, *own)
     return (o, l * _LN2) if return_lse else o
 
