@@ -1,0 +1,704 @@
+"""The float64 model of training attention (forward, dQ, dK/dV) on a [B, H, R | C, D] grid, its per-element error bounds, the needle
+inputs and the named mutants (a plain module, as tests/decode_model.py, whose rounding helpers and constants it reuses; numpy only).
+
+  model()           float64 O, L (natural units), D = rowsum(dO O), dV, dK, dQ under the library's causal rule and per-batch length
+                    rule (include/mfa.h: row r of entry b sees column c iff c < columnLengths[b] and, causal, c <= r +
+                    max(columnLengths[b] - rowLengths[b], 0)), the magnitude sums of the bounds and the bounds' error terms.
+                    mutant= computes a named WRONG attention instead (MUTANTS).  No wrong kernel is ever run.
+  bounds()          per-element bounds on all six outputs (derivation below).
+  emulated()        the same computation with the kernels' roundings and summation orders: what a correct kernel may give.
+  needle_inputs()   Q, K, V and dO in which individual keys and individual rows matter.
+  compare()         got against model under the bounds: worst err / bound per output and where; padding must keep the buffer's value.
+  split_ranges()    the ranges of a traversal cut into pieces as the kernels cut it (piece i takes the units
+                    [i n / s, (i + 1) n / s) of 64 keys or 32 rows: attn_dq16_p4.h `tile_lo`, attn_dkv16_p4.h `lo`, `up`);
+                    library_piece_count() reads the piece count s from the library's own plan (mfa_attention_kernel_workspace_size).
+
+The bound.  Write u = 2^-8 (bf16) or 2^-11 (f16) for half a unit in the last place of the inputs' 16-bit type (round-to-nearest:
+`v_cvt_pk_*_f32` in every stream generator), u32 = 2^-24, scale = 1 / sqrt(D), p_ij the model's softmax weights,
+T_ij = scale sum_d |q_id k_jd|.  Every term is a worst case and errors add up linearly.
+
+  Scores.  Exact mode (lowPrecisionIntermediates = 0): a score is D exact products summed in FP32 and scaled in FP32, p_ij carries
+  the relative error rho_ij = ln 2 ((D + 3) u32 log2e T_ij + 3 u32 spread_i) + 4 u32 (decode_model's term).  Mixed mode: one operand
+  of S = Q K^T is multiplied by log2e / sqrt(D) and rounded to the 16-bit type once (forward and backwardQuery: Q'; backwardKeyValue:
+  K'; include/mfa.h), every product then moves by u: rho_ij += u T_ij.  This is the term that grows with a needle's score.
+  Forward.  P enters P V in the 16-bit type: u A_O, A_O = sum_j p_ij |v_jd|.  Exact mode: l sums the unrounded P.  Mixed mode (FOLD
+  streams): l sums the ROUNDED P: u |O| more.  p~ = p (1 + rho) moves the numerator by sum_j rho_ij p_ij |v_jd|
+  and, through l, O by |O| sum_j rho_ij p_ij.  FP32 chains (per 16- or 32-deep matrix instruction, per deferred rescale, per wave,
+  per piece, the combine, the normalisation): chain = C / 8 + pieces + 16 roundings on A_O + |O|.  The store: U_OUT |O|.
+    E_O = u A_O + [mixed] u |O| + sum_j rho p |v| + |O| sum_j rho p + chain u32 (A_O + |O|)
+  L = m + log2 l in log2 units, stored in FP32 (exact mode) or FP16 (mixed mode: half an ulp is 2^-11 |L|, the same in natural units):
+    E_L = sum_j rho_ij p_ij + [mixed] u + chain u32 + 4 u32 (|m| + |ln l| + |L|) + (2^-11 [mixed] or 2^-23) |L|
+  D = sum_d dO_id O_id from the FP32 O the forward launch stored, in FP32.  An error eps_j p_ij of the forward weights moves O_d by
+  sum_j eps_j p_ij (v_jd - O_d) where l sums the same rounded P (mixed mode), by sum_j eps_j p_ij v_jd where it does not (exact mode),
+  hence D by sum_j eps_j p_ij (dP_ij - D_i) or sum_j eps_j p_ij dP_ij, dP_ij = sum_d dO_id v_jd: a sum over KEYS, far below the sum
+  over d of the O bounds.  D is stored in FP32 (exact mode) or in BF16 by truncation (mixed mode: up to 2^-7 |D_i|);
+  backwardKeyValue reads the stored value back:
+    E_D = sum_j p_ij (u (|dP_ij - D_i| [mixed] or |dP_ij|) + rho_ij |dP_ij - D_i|) + chain u32 (sum_j p_ij |dP_ij| + |D_i|)
+          + ((D + 2) u32 + 2^-23) sum_d |dO_id O_id| + (2^-7 [mixed] or 2^-23) |D_i|
+  Backward.  P_ij = exp2(s'_ij - L_i) with the STORED L: rho^b_ij = rho_ij + E_L_i (an FP16 L is one common relative error on a whole
+  row of P).  P is rounded to 16 bits for dV (u); dP_ij = sum_d dO_id v_jd in FP32 (e_dP = (D + 3) u32 sum_d |dO v|);
+  dS_ij = P (dP - D) is formed from the ROUNDED P in the role-split kernels (u, charged to every kernel) and rounded to 16 bits (u):
+    e_dS_ij = p_ij ((rho^b_ij + u) |dP_ij - D_i| + e_dP_ij + E_D_i) + u |dS_ij|
+    E_dV = sum_i p_ij (rho^b_ij + u) |dO_id| + chain_r u32 A_dV,          A_dV = sum_i p_ij |dO_id|
+    E_dQ = scale sum_j e_dS_ij |k_jd| + chain u32 A_dQ,                   A_dQ = scale sum_j |dS_ij| |k_jd|
+    E_dK = scale sum_i e_dS_ij |q_id| + chain_r u32 A_dK,                 A_dK = scale sum_i |dS_ij| |q_id|
+  (the last products read K and Q as stored and the softmax scale multiplies the FP32 result: attn_dq16_p4.h `dQ = scale * dS' K`,
+  attn_dkv16_p4.h `dK = scale * dS'^T Q`; the scaled, rounded K' of the mixed mode feeds S only.)  An error dL of a row's L moves dQ
+  by dL A_dQ, dK and dV by dL times the row's share of A_dK and A_dV; an error dD of a row's D moves dQ by dD scale sum_j p_ij |k_jd|
+  (Reference.PK) and dK by dD scale p_ij |q_id|.
+  What the mixed bf16 bound does NOT resolve: a relative defect of 2^-5 on dQ.  E_dQ holds three half-ulps of its own (the rounded P,
+  the rounded dS, l summed from the rounded P through E_L) and a fourth through E_D: the forward's rounded P moves D_i by up to
+  u sum_j |dS_ij|, and the truncated store by 2^-7 |D_i| more (D_i is about 1.4 by needle_inputs' choice of dO; the smaller |D_i|, the
+  smaller this share, but the u sum_j |dS_ij| part stays).  4 x 2^-8 of A_dQ >= |dQ| is 2^-5 exactly at margin 2, before the FP16 L
+  and the D store are added: "dQ scaled by 1 - 2^-5" sits at 0.85 to 0.9 of the bound there, at 1.6 under bf16 exact, at 4 to 5 under
+  f16 mixed (tests/test_train_sensitivity.py BOUND_OF).
+  FP16 inputs: P (at most 2^8 against the running maximum, at most 1 in the backward pass) and dS lose their relative accuracy below
+  2^-14: every visible (i, j) adds the absolute error f = 2^-25 to p_ij and f (|dP_ij - D_i| + sqrt(D)) to dS_ij (BF16 has FP32's
+  exponent range: f = 0).  The sqrt(D): the role-split and wide dK / dV kernels round dS' = scale P (dP - D) -- the scale folded in
+  BEFORE the 16-bit rounding, as the reference does (attn_dkv16_rs.h `(T)(p4[i] * (x[r] * a.scale - d4[i]))`, attn_dkv16_wide.h the
+  same line) -- so FP16's floor f sits on scale dS.  Found by tests/test_train_parity_gpu.py: attn_dkv16w_f16_d320 and
+  attn_dkv16rs_f16_d256 left dK elements of 1.5e-6 at 1.1 times a bound that had the floor on dS itself.
+  bound_X = margin (E_X + U_OUT[out] |X|) + tiny,   tiny = 2^-24.
+
+MARGIN is the smallest power of two, at most 4, with at least 2 x headroom over the worst err / bound at margin 1 of emulated() on
+every case of tests/test_train_sensitivity.py and of the kernels on every case of tests/test_train_parity_gpu.py (DESIGN.md 4.18
+records both maxima).
+"""
+import math
+from typing import NamedTuple
+
+import numpy as np
+
+from decode_model import LN2, LOG2E, TINY, U32, U_OUT, U_P, f64, fmt_of, round_to, store  # noqa: F401 -- one set of rounding helpers
+
+TILE, STEP, WAVE_ROWS, BLOCK_ROWS = 64, 32, 64, 256   # keys per tile, keys / rows per step, rows per wave, rows per row block
+RESCALE_THRESHOLD = 8.0                               # log2 units: the deferred rescale of the forward streams (include/mfa.h)
+MARGIN = 2
+F16_FLOOR = 2.0 ** -25                                # half the spacing of FP16's subnormals: P and dS below 2^-14 in that type
+OUTPUTS = ("O", "L", "D", "dV", "dK", "dQ")
+OLD_TOL = dict(O=5e-2, L=7e-3, D=1e-1, dV=5e-2, dK=5e-2, dQ=5e-2)   # tests/harness.py TOL_MIXED
+
+
+class Reference(NamedTuple):
+    O: np.ndarray; L: np.ndarray; D: np.ndarray; dV: np.ndarray; dK: np.ndarray; dQ: np.ndarray   # noqa: E702
+    A: dict          # the magnitude sums: O, dV, dQ, dK
+    E: dict          # per output, every term of the bound except the store's, at margin 1
+    PK: np.ndarray   # [B, H, R, D] scale sum_j p_ij |k_jd|: what a unit error of the row's D moves in dQ (an error of L moves A["dQ"])
+    row_live: np.ndarray   # [B, R] rows below the entry's row length
+    key_live: np.ndarray   # [B, C]
+
+
+# ---------------------------------------------------------------------------------------------------------------------- mutants
+# name -> (what the defect is, where it changes nothing).  `case` has R, C, H, B, causal, pieces (bool), spike (bool), all_whole_tiles,
+# row_lengths_differ, row_padding, key_padding (case_flags)
+_no_split = lambda c: not c["pieces"]          # noqa: E731
+MUTANTS = {
+    # forward
+    "o_zero": ("O = 0 everywhere", lambda c: False),
+    "key0_dropped": ("key 0 never seen", lambda c: False),
+    "last_key_dropped": ("the last key never seen", lambda c: False),
+    "partial_last_tile_dropped": ("the partial last 64-key tile is not run", lambda c: c["all_whole_tiles"]),
+    "tile_skipped_in_one_row_block": ("keys 64..127 skipped in the LAST row block only", lambda c: c["C"] <= TILE),
+    "causal_plus_1": ("forward: causal frontier one key too far", lambda c: not c["causal"] or c["R"] == 1),
+    "causal_minus_1": ("forward: causal frontier one key short", lambda c: not c["causal"]),
+    "wave_groups_exchanged": ("rows 0..63 and 64..127 of row block 0 exchanged in O and L", lambda c: c["R"] <= WAVE_ROWS),
+    "row_block_next_head_kv": ("row block 0 served from the next head's K / V", lambda c: c["H"] == 1),
+    "v_rows_exchanged": ("two V rows of one 16-key group exchanged", lambda c: c["C"] < 2),
+    "v_dblocks_exchanged": ("the first two 32-wide d blocks of V exchanged", lambda c: False),
+    "rescale_o_not_l": ("the deferred rescale (threshold 8) applied to O but not to l", lambda c: not c["spike"]),
+    "l_without_key0": ("l without key 0: wrong in L only", lambda c: False),
+    "row_length_next_batch": ("the row length of batch b + 1 used for batch b", lambda c: not c["row_lengths_differ"]),
+    "piece_loses_last_tile": ("forward: every piece stops one 64-key tile early", _no_split),
+    "piece_overlaps": ("forward: every piece starts one tile early, inside its neighbour", _no_split),
+    "combine_ignores_maxima": ("the forward combine adds the pieces without exp2(m_s - m*)", _no_split),
+    # backward
+    "dq_last_tile_dropped": ("dQ without its last key tile", lambda c: c["C"] == 1),
+    "dq_tile_skipped_in_one_row_block": ("dQ without keys 64..127 in the LAST row block only", lambda c: c["C"] <= TILE),
+    "dkv_last_step_dropped": ("dK / dV without the last 32-row step", lambda c: False),
+    "dkv_row_block_dropped": ("dK / dV without the last 256-row block", lambda c: False),
+    "d_zero": ("D term = 0", lambda c: False),
+    "d_wrong": ("D wrong by 2^-4", lambda c: False),
+    "d_neighbour_row": ("D of the neighbouring row", lambda c: c["R"] == 1),
+    "d_next_head": ("D of the next head", lambda c: c["H"] == 1),
+    "l_neighbour_row": ("L of the neighbouring row in the backward pass", lambda c: c["R"] == 1),
+    "ds_scale_missing": ("the softmax scale left out of dS", lambda c: c["C"] == 1),
+    "ds_scale_twice": ("the softmax scale applied twice to dS", lambda c: c["C"] == 1),
+    "dq_scaled": ("dQ scaled by 1 - 2^-5", lambda c: c["C"] == 1),
+    "dk_dv_exchanged": ("dK and dV exchanged", lambda c: False),
+    "bwd_causal_plus_1": ("backward only: causal frontier one key too far", lambda c: not c["causal"] or c["R"] == 1),
+    "bwd_causal_minus_1": ("backward only: causal frontier one key short", lambda c: not c["causal"]),
+    "dq_reads_padding_keys": ("the key AT the key length contributes to dQ", lambda c: not c["key_padding"]),
+    "dkv_reads_padding_rows": ("the row AT the row length contributes to dK / dV", lambda c: not c["row_padding"]),
+    "bwd_combine_drops_slab": ("attn_bwd_combine drops the second piece's slab", _no_split),
+    "bwd_combine_adds_slab_twice": ("attn_bwd_combine adds the second piece's slab twice", _no_split),
+}
+
+
+def case_flags(R, C, row_lengths=None, key_lengths=None):
+    """the fields of a case the predicates read that follow from its lengths"""
+    rl, cl = list(row_lengths or [R]), list(key_lengths or [C])
+    return dict(all_whole_tiles=all(n % TILE == 0 for n in cl), row_lengths_differ=len(set(rl)) > 1, row_padding=any(n < R for n in rl),
+                key_padding=any(n < C for n in cl))
+
+
+def split_ranges(n, count, unit):
+    """[(begin, end)] of a traversal of n keys (unit 64: dQ, forward) or rows (unit 32: dK / dV) cut into `count` pieces"""
+    units = -(-int(n) // unit)
+    return [(min(n, unit * (i * units // count)), min(n, unit * ((i + 1) * units // count))) for i in range(count)]
+
+
+KERNEL_TYPES = ("fwd", "dq", "dkv")          # in the order of AttentionKernelType: forward, backwardQuery, backwardKeyValue
+
+
+def piece_count(kernel, kernel_type, R, C, D, heads, batches):
+    """pieces of the library's own plan for a launch of `kernel` given a workspace (1: not split): the workspace it asks for
+    (mfa_attention_kernel_workspace_size) over one piece's slabs (mfa_kernel.hip split_workspace_bytes)"""
+    need = kernel.workspaceSize(row=R, column=C, heads=heads, batches=batches)
+    per = heads * batches * {"fwd": R * (D + 2) * 4, "dq": R * D * 4, "dkv": 2 * C * D * 4}[kernel_type]
+    assert need % per == 0, (kernel_type, need, per)
+    return max(1, need // per)
+
+
+def pieces_of(counts, R, C):
+    """{"fwd": key ranges, "dq": key ranges, "dkv": row ranges} for the kernel types that are split, or None"""
+    res = {t: split_ranges(R if t == "dkv" else C, n, STEP if t == "dkv" else TILE) for t, n in counts.items() if n > 1}
+    return res or None
+
+
+def library_piece_count(kernel_type, R, C, D, heads, batches, fmt="bf16", mixed=True):
+    """piece_count() of the kernel the default tables select for this shape, type and mode"""
+    from metal_flash_attention_amd import AttentionDescriptor, AttentionKernel, AttentionKernelType, GEMMOperandPrecision
+    d = AttentionDescriptor()
+    d.lowPrecisionInputs, d.lowPrecisionIntermediates = True, mixed
+    d.matrixDimensions = (R, C, D)
+    d.transposeState = (False,) * 4
+    d.lowPrecisionInputType = GEMMOperandPrecision.BF16 if fmt == "bf16" else GEMMOperandPrecision.FP16
+    t = list(AttentionKernelType)[KERNEL_TYPES.index(kernel_type)]
+    return piece_count(AttentionKernel(d.kernelDescriptor(t)), kernel_type, R, C, D, heads, batches)
+
+
+def library_pieces(R, C, D, heads, batches, fmt="bf16", mixed=True):
+    """{"fwd": key ranges, "dq": key ranges, "dkv": row ranges} of the library's plan, or None where no kernel type is split"""
+    return pieces_of({t: library_piece_count(t, R, C, D, heads, batches, fmt, mixed) for t in KERNEL_TYPES}, R, C)
+
+
+def _lengths(lens, B, full):
+    return np.full(B, full, dtype=np.int64) if lens is None else np.minimum(np.asarray(lens, dtype=np.int64), full)
+
+
+def _visible(R, C, rlen, clen, causal, shift=0):
+    rows, cols = np.arange(R)[:, None], np.arange(C)[None, :]
+    vis = np.broadcast_to(cols < clen, (R, C)).copy()
+    if causal:
+        vis &= cols <= rows + max(clen - rlen, 0) + shift
+    return vis
+
+
+def _softmax(S, vis, mult=None):
+    Sm = np.where(vis, S, -np.inf)
+    m = Sm.max(axis=1, keepdims=True)
+    m0 = np.where(np.isfinite(m), m, 0.0)
+    pw = np.exp(Sm - m0)
+    if mult is not None:
+        pw = pw * mult
+    l = pw.sum(axis=1, keepdims=True)
+    l0 = np.where(l > 0, l, 1.0)
+    return pw / l0, m0[:, 0], l0[:, 0]
+
+
+def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, pieces=None, mutant=None, fmt="bf16", mixed=True, with_bounds=True):
+    """-> Reference (with_bounds=False: A, E and PK stay zero).  pieces: None or {"fwd": [(key begin, end)], "dq": [(key begin, end)], "dkv": [(row begin, end)]} (they change the
+    bound's chain and what the mutants do, never the unmutated values).  A mutated run leaves NaN where its launch writes nothing."""
+    assert mutant is None or mutant in MUTANTS, mutant
+    q, k, v, dO = f64(q), f64(k), f64(v), f64(dO)
+    B, H, R, Dh = q.shape
+    C = k.shape[2]
+    scale = 1.0 / math.sqrt(Dh)
+    u = U_P[fmt]
+    fl = F16_FLOOR if fmt == "f16" else 0.0
+    rl, cl = _lengths(row_lengths, B, R), _lengths(key_lengths, B, C)
+    rl_used = np.roll(rl, -1) if mutant == "row_length_next_batch" else rl
+    pieces = pieces or {}
+    npieces = max(len(pieces.get("fwd", ())), len(pieces.get("dq", ())), len(pieces.get("dkv", ())), 1)
+    chain, chain_r = (C / 8 + npieces + 16) * U32, (R / 8 + npieces + 16) * U32
+    out = {n: np.full((B, H, R if n in ("O", "dQ") else C, Dh), np.nan) for n in ("O", "dV", "dK", "dQ")}
+    out["L"], out["D"] = np.full((B, H, R), np.nan), np.full((B, H, R), np.nan)
+    A = {n: np.zeros_like(out[n]) for n in ("O", "dV", "dK", "dQ")}
+    E = {n: np.zeros_like(out[n]) for n in OUTPUTS}
+    PK = np.zeros((B, H, R, Dh))
+    want_bounds = mutant is None and with_bounds
+    fwd = {}
+    for b in range(B):
+        rlen, clen = int(rl_used[b]), int(cl[b])
+        vis = _visible(R, C, rlen, clen, causal)
+        for h in range(H):
+            hk = (h + 1) % H if mutant == "row_block_next_head_kv" else h
+            K, V = k[b, h], v[b, h]
+            S = (q[b, h] @ K.T) * scale
+            visF, mult = vis, None
+            if mutant == "causal_plus_1":
+                visF = _visible(R, C, rlen, clen, causal, +1)
+            elif mutant == "causal_minus_1":
+                visF = _visible(R, C, rlen, clen, causal, -1)
+            elif mutant in ("key0_dropped", "last_key_dropped", "partial_last_tile_dropped", "tile_skipped_in_one_row_block"):
+                visF = vis.copy()
+                if mutant == "key0_dropped":
+                    visF[:, 0] = False
+                elif mutant == "last_key_dropped":
+                    visF[:, clen - 1] = False
+                elif mutant == "partial_last_tile_dropped" and clen % TILE:
+                    visF[:, clen // TILE * TILE:] = False
+                elif mutant == "tile_skipped_in_one_row_block":
+                    visF[(rlen - 1) // BLOCK_ROWS * BLOCK_ROWS:, TILE:2 * TILE] = False
+            Vf = V
+            if mutant == "v_rows_exchanged" and clen >= 2:
+                src = np.arange(C)
+                x = 30 if clen >= 32 else 0
+                src[x], src[x + 1] = x + 1, x
+                Vf = V[src]
+            if mutant == "piece_loses_last_tile" and len(pieces.get("fwd", ())) > 1:
+                visF = visF.copy()
+                for pb, pe in pieces["fwd"]:
+                    pe = min(pe, clen)
+                    if pe > pb:
+                        visF[:, max(pb, (pe - 1) // TILE * TILE):pe] = False
+            if mutant == "piece_overlaps" and len(pieces.get("fwd", ())) > 1:
+                mult = np.ones(C)
+                for pb, pe in pieces["fwd"]:
+                    if min(pe, clen) > pb and pb >= TILE:
+                        mult[pb - TILE:pb] += 1.0
+            P, m, l = _softmax(S, visF, mult)
+            O = P @ Vf
+            L = m + np.log(l)
+            if mutant == "row_block_next_head_kv":     # rows of block 0 from head h + 1's K / V
+                S1 = (q[b, h] @ k[b, hk].T) * scale
+                P1, m1, l1 = _softmax(S1, visF)
+                blk = slice(0, BLOCK_ROWS)
+                O[blk], L[blk] = (P1 @ v[b, hk])[blk], (m1 + np.log(l1))[blk]
+            if mutant == "combine_ignores_maxima" and len(pieces.get("fwd", ())) > 1:
+                num, den = np.zeros((R, Dh)), np.zeros(R)
+                Sm = np.where(visF, S, -np.inf)
+                for pb, pe in pieces["fwd"]:
+                    pe = min(pe, clen)
+                    if pe <= pb:
+                        continue
+                    pm = Sm[:, pb:pe].max(axis=1)
+                    ok = np.isfinite(pm)
+                    e = np.where(ok[:, None], np.exp(Sm[:, pb:pe] - np.where(ok, pm, 0.0)[:, None]), 0.0)
+                    num += e @ Vf[pb:pe]
+                    den += e.sum(axis=1)
+                O = num / den[:, None]
+                L = m + np.log(den)
+            if mutant == "rescale_o_not_l":
+                S2 = np.where(visF, S, -np.inf) * LOG2E
+                run, lm, fired = np.full(R, -1e30), np.zeros(R), np.zeros(R, dtype=bool)
+                for t0 in range(0, clen, TILE):
+                    tm = S2[:, t0:t0 + TILE].max(axis=1)
+                    fired |= (tm > run + RESCALE_THRESHOLD) & (lm > 0)
+                    run = np.where(tm > run + RESCALE_THRESHOLD, tm, run)     # O is rescaled here; l is not
+                    lm = lm + np.exp2(S2[:, t0:t0 + TILE] - run[:, None]).sum(axis=1)
+                ltrue = np.exp2(S2 - run[:, None]).sum(axis=1)
+                O = np.where(fired[:, None], O * (ltrue / lm)[:, None], O)
+                L = np.where(fired, (run + np.log2(lm)) / LOG2E, L)
+            if mutant == "l_without_key0":
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    L = L + np.log1p(-P[:, 0])
+            if mutant == "wave_groups_exchanged":
+                n = max(0, min(WAVE_ROWS, rlen - WAVE_ROWS))
+                O, L = O.copy(), L.copy()
+                O[:n], O[WAVE_ROWS:WAVE_ROWS + n] = O[WAVE_ROWS:WAVE_ROWS + n].copy(), O[:n].copy()
+                L[:n], L[WAVE_ROWS:WAVE_ROWS + n] = L[WAVE_ROWS:WAVE_ROWS + n].copy(), L[:n].copy()
+            if mutant == "v_dblocks_exchanged" and Dh >= 64:
+                O = np.concatenate([O[:, 32:64], O[:, :32], O[:, 64:]], axis=1)
+            if mutant == "o_zero":
+                O = np.zeros_like(O)
+            fwd[(b, h)] = (S, P, m, l, O, L, (dO[b, h] * O).sum(axis=1))
+    for b in range(B):
+        rlen, clen = int(rl_used[b]), int(cl[b])
+        vis = _visible(R, C, rlen, clen, causal)
+        live_r = np.arange(R) < rlen
+        live_c = np.arange(C) < clen
+        for h in range(H):
+            S, P0, m, l, O, L, Dv = fwd[(b, h)]
+            K, V, Q, G = k[b, h], v[b, h], q[b, h], dO[b, h]
+            if mutant == "d_zero":
+                Dv = np.zeros(R)
+            elif mutant == "d_wrong":
+                Dv = Dv * (1.0 + 2.0 ** -4)
+            elif mutant == "d_neighbour_row":
+                Dv = np.concatenate([Dv[1:rlen], Dv[:1], Dv[rlen:]])
+            elif mutant == "d_next_head":
+                Dv = fwd[(b, (h + 1) % H)][6]
+            Lb = np.concatenate([L[1:rlen], L[:1], L[rlen:]]) if mutant == "l_neighbour_row" else L
+            visB = vis
+            if mutant == "bwd_causal_plus_1":
+                visB = _visible(R, C, rlen, clen, causal, +1)
+            elif mutant == "bwd_causal_minus_1":
+                visB = _visible(R, C, rlen, clen, causal, -1)
+            with np.errstate(over="ignore", invalid="ignore"):
+                Pall = np.exp(S - Lb[:, None])          # the backward kernels' P = exp(s - L), for every (row, key) of the buffers
+            Pb = np.where(visB, Pall, 0.0)
+            dP = G @ V.T
+            dS = Pb * (dP - Dv[:, None])
+            # ---- dQ: rows below the row length, keys the pass reads
+            Pq, dSq = Pb, dS
+            if mutant in ("dq_last_tile_dropped", "dq_tile_skipped_in_one_row_block", "dq_reads_padding_keys"):
+                keep = np.ones((R, C), dtype=bool)
+                if mutant == "dq_last_tile_dropped":
+                    keep[:, (clen - 1) // TILE * TILE:] = False
+                elif mutant == "dq_tile_skipped_in_one_row_block":
+                    keep[(rlen - 1) // BLOCK_ROWS * BLOCK_ROWS:, TILE:2 * TILE] = False
+                dSq = np.where(keep, dS, 0.0)
+                if mutant == "dq_reads_padding_keys" and clen < C:
+                    dSq = dSq.copy()
+                    dSq[:, clen] = Pall[:, clen] * (dP[:, clen] - Dv)
+            dq_scale = {"ds_scale_missing": 1.0, "ds_scale_twice": scale * scale}.get(mutant, scale)
+            dQ = dq_scale * (dSq @ K)
+            if mutant == "dq_scaled":
+                dQ = dQ * (1.0 - 2.0 ** -5)
+            if mutant in ("bwd_combine_drops_slab", "bwd_combine_adds_slab_twice") and len(pieces.get("dq", ())) > 1:
+                pb, pe = pieces["dq"][1]
+                slab = dq_scale * (dSq[:, pb:pe] @ K[pb:pe])
+                dQ = dQ - slab if mutant == "bwd_combine_drops_slab" else dQ + slab
+            # ---- dK / dV: keys below the key length, rows the pass reads
+            rows_in = live_r.copy()
+            if mutant == "dkv_last_step_dropped":
+                rows_in[(rlen - 1) // STEP * STEP:] = False
+            elif mutant == "dkv_row_block_dropped":
+                rows_in[(rlen - 1) // BLOCK_ROWS * BLOCK_ROWS:] = False
+            Pk, dSk = Pb[rows_in], dS[rows_in]
+            Gk, Qk = G[rows_in], Q[rows_in]
+            if mutant == "dkv_reads_padding_rows" and rlen < R:
+                prow = np.where(live_c, Pall[rlen], 0.0)[None, :]
+                Pk, dSk = np.concatenate([Pk, prow]), np.concatenate([dSk, prow * (dP[rlen] - Dv[rlen])[None, :]])
+                Gk, Qk = np.concatenate([Gk, G[rlen:rlen + 1]]), np.concatenate([Qk, Q[rlen:rlen + 1]])
+            dV = Pk.T @ Gk
+            dK = dq_scale * (dSk.T @ Qk)
+            if mutant in ("bwd_combine_drops_slab", "bwd_combine_adds_slab_twice") and len(pieces.get("dkv", ())) > 1:
+                pb, pe = pieces["dkv"][1]
+                sel = np.zeros(R, dtype=bool)
+                sel[pb:pe] = True
+                sel &= live_r
+                sv, sk = Pb[sel].T @ G[sel], dq_scale * (dS[sel].T @ Q[sel])
+                sign = -1.0 if mutant == "bwd_combine_drops_slab" else 1.0
+                dV, dK = dV + sign * sv, dK + sign * sk
+            if mutant == "dk_dv_exchanged":
+                dV, dK = dK, dV
+            Dout = Dv
+            for name, val, live in (("O", O, live_r), ("L", L, live_r), ("D", Dout, live_r), ("dQ", dQ, live_r), ("dV", dV, live_c), ("dK", dK, live_c)):
+                out[name][b, h][live] = val[live]
+            if not want_bounds:
+                continue
+            # ---- the magnitude sums and the error terms (margin 1, without the stores)
+            P = np.where(live_r[:, None], P0, 0.0)
+            aK, aV, aQ, aG = np.abs(K), np.abs(V), np.abs(Q), np.abs(G)
+            T = scale * (aQ @ aK.T)
+            smin = np.where(vis, S, np.inf).min(axis=1)
+            spread2 = np.where(np.isfinite(smin), (m - np.where(np.isfinite(smin), smin, m)) * LOG2E, 0.0)
+            rho = LN2 * ((Dh + 3) * U32 * LOG2E * T + 3 * U32 * spread2[:, None]) + 4 * U32
+            visl = (vis & live_r[:, None]).astype(np.float64)
+            if mixed:
+                rho = rho + u * T
+            rp = rho * P
+            relp = rp.sum(axis=1) + fl * visl.sum(axis=1)
+            AO = P @ aV
+            absO = np.abs(np.where(live_r[:, None], O, 0.0))
+            EO = u * AO + (u * absO if mixed else 0.0) + fl * (visl @ aV) + rp @ aV + absO * relp[:, None] + chain * (AO + absO)
+            Lf = np.where(live_r, L, 0.0)
+            EL = relp + (u if mixed else 0.0) + chain + 4 * U32 * (np.abs(m) + np.abs(np.log(l)) + np.abs(Lf)) + (2.0 ** -11 if mixed else 2.0 ** -23) * np.abs(Lf)
+            Df = np.where(live_r, Dv, 0.0)
+            dP = np.where(live_r[:, None], dP, 0.0)
+            dev = np.abs(dP - Df[:, None])
+            ED = (P * (u * (dev if mixed else np.abs(dP)) + rho * dev)).sum(axis=1) + fl * (visl * np.abs(dP)).sum(axis=1) \
+                + chain * ((P * np.abs(dP)).sum(axis=1) + np.abs(Df)) + ((Dh + 2) * U32 + U_OUT["f32"]) * (aG * absO).sum(axis=1) \
+                + (2.0 ** -7 if mixed else 2.0 ** -23) * np.abs(Df)
+            rhob = rho + EL[:, None]
+            dSl = np.where(live_r[:, None], dS, 0.0)
+            edP = (Dh + 3) * U32 * (aG @ aV.T)
+            eds = P * ((rhob + u) * dev + edP + ED[:, None]) + u * np.abs(dSl) + fl * visl * (dev + math.sqrt(Dh))
+            A["O"][b, h], A["dV"][b, h] = AO, P.T @ aG
+            A["dQ"][b, h], A["dK"][b, h] = scale * (np.abs(dSl) @ aK), scale * (np.abs(dSl).T @ aQ)
+            PK[b, h] = scale * (P @ aK)
+            E["O"][b, h], E["L"][b, h], E["D"][b, h] = EO, EL, ED
+            E["dV"][b, h] = (P * (rhob + u) + fl * visl).T @ aG + chain_r * A["dV"][b, h]
+            E["dQ"][b, h] = scale * (eds @ aK) + chain * A["dQ"][b, h]
+            E["dK"][b, h] = scale * (eds.T @ aQ) + chain_r * A["dK"][b, h]
+    row_live = np.arange(R)[None, :] < rl[:, None]
+    key_live = np.arange(C)[None, :] < cl[:, None]
+    return Reference(out["O"], out["L"], out["D"], out["dV"], out["dK"], out["dQ"], A, E, PK, row_live, key_live)
+
+
+def bounds(ref, out="f32", margin=MARGIN):
+    """{output: per-element bound}: see the module's docstring.  `out`: the type O, dQ, dK, dV are stored in (L and D: their own
+    store is part of E, the mode decides it)"""
+    res = {}
+    for name in OUTPUTS:
+        x = np.nan_to_num(getattr(ref, name), nan=0.0)
+        st = 0.0 if name in ("L", "D") else U_OUT[out] * np.abs(x)
+        res[name] = margin * (ref.E[name] + st) + TINY
+    return res
+
+
+# ------------------------------------------------------------------------------------------------- the rounding-emulated reference
+def _f32(x):
+    return np.asarray(x, dtype=np.float32).astype(np.float64)
+
+
+def emulated(q, k, v, dO, fmt, mixed, *, causal=False, row_lengths=None, key_lengths=None, pieces=None, out="f32"):
+    """the model with the kernels' roundings and order of sums -> {output: array}, NaN where nothing is written: Q' (K' in
+    backwardKeyValue) rounded once in the mixed mode, 64-key tiles under the deferred rescale, P and dS rounded to the 16-bit type,
+    l from the rounded P in the mixed mode, pieces merged, L in FP16 and D in truncated BF16 in the mixed mode, the stores"""
+    q, k, v, dO = f64(q), f64(k), f64(v), f64(dO)
+    B, H, R, Dh = q.shape
+    C = k.shape[2]
+    scale = 1.0 / math.sqrt(Dh)
+    s2c = float(np.float32(LOG2E * scale))
+    rl, cl = _lengths(row_lengths, B, R), _lengths(key_lengths, B, C)
+    pieces = pieces or {}
+    res = {n: np.full((B, H, R if n in ("O", "dQ") else C, Dh), np.nan) for n in ("O", "dV", "dK", "dQ")}
+    res["L"], res["D"] = np.full((B, H, R), np.nan), np.full((B, H, R), np.nan)
+    for b in range(B):
+        rlen, clen = int(rl[b]), int(cl[b])
+        vis = _visible(R, C, rlen, clen, causal)[:rlen, :clen]
+        for h in range(H):
+            Q, K, V, G = q[b, h, :rlen], k[b, h, :clen], v[b, h, :clen], dO[b, h, :rlen]
+            if mixed:
+                S2q = _f32(round_to(Q * s2c, fmt) @ K.T)
+                S2k = _f32(Q @ round_to(K * s2c, fmt).T)
+            else:
+                S2q = S2k = _f32(_f32(Q @ K.T) * s2c)
+            S2 = np.where(vis, S2q, -np.inf)
+            parts = []
+            for pb, pe in (pieces.get("fwd") or [(0, clen)]):
+                pe = min(pe, clen)
+                run, l, o = np.full(rlen, -1e30), np.zeros(rlen), np.zeros((rlen, Dh))
+                for t0 in range(pb, pe, TILE):
+                    s = S2[:, t0:min(t0 + TILE, pe)]
+                    tm = s.max(axis=1)
+                    new = np.where(tm > run + RESCALE_THRESHOLD, tm, run)
+                    corr = _f32(np.exp2(run - new))
+                    p = _f32(np.exp2(s - new[:, None]))
+                    pr = round_to(p, fmt)
+                    l = _f32(l * corr + (pr if mixed else p).sum(axis=1))
+                    o = _f32(o * corr[:, None] + pr @ V[t0:min(t0 + TILE, pe)])
+                    run = new
+                parts.append((run, l, o))
+            mstar = np.max([p[0] for p in parts], axis=0)
+            lt = sum(_f32(np.exp2(m_ - mstar)) * l_ for m_, l_, _o in parts)
+            ot = sum(_f32(np.exp2(m_ - mstar))[:, None] * o_ for m_, _l, o_ in parts)
+            O = store(_f32(ot / lt[:, None]), out)
+            L2 = _f32(mstar + np.log2(lt))
+            L2 = round_to(L2, "f16") if mixed else L2
+            Dv = _f32((G * O).sum(axis=1))
+            Dst = round_to(Dv * scale, "bf16", trunc=True) / scale if mixed else Dv
+            dP = _f32(G @ V.T)
+            Pq = np.where(vis, _f32(np.exp2(S2q - L2[:, None])), 0.0)
+            Pk = np.where(vis, _f32(np.exp2(S2k - L2[:, None])), 0.0)
+            dSq = round_to(round_to(Pq, fmt) * (dP - Dv[:, None]), fmt)
+            dSk = round_to(scale * round_to(Pk, fmt) * (dP - Dst[:, None]), fmt)      # dS' = scale dS: attn_dkv16_rs.h
+            dQ = sum(_f32(dSq[:, pb:pe] @ K[pb:pe]) for pb, pe in (pieces.get("dq") or [(0, clen)])) * scale
+            rr = [(pb, min(pe, rlen)) for pb, pe in (pieces.get("dkv") or [(0, rlen)])]
+            dV = sum(_f32(round_to(Pk[pb:pe], fmt).T @ G[pb:pe]) for pb, pe in rr if pe > pb)
+            dK = sum(_f32(dSk[pb:pe].T @ Q[pb:pe]) for pb, pe in rr if pe > pb)
+            res["O"][b, h, :rlen], res["L"][b, h, :rlen], res["D"][b, h, :rlen] = O, L2 / LOG2E, Dst
+            res["dQ"][b, h, :rlen] = store(_f32(dQ), out)
+            res["dV"][b, h, :clen], res["dK"][b, h, :clen] = store(_f32(dV), out), store(_f32(dK), out)
+    return res
+
+
+# ------------------------------------------------------------------------------------------------------------------ needle inputs
+def key_pool(clen, pieces=None):
+    """the keys whose handling the kernels' geometry makes special, most important first: key 0, the last key, the first and last key
+    of every piece, both sides of every 64-key tile edge, both sides of every 32-key step edge"""
+    pool = [0, clen - 1]
+    for name in ("fwd", "dq"):
+        for pb, pe in (pieces or {}).get(name, ()):
+            pool += [pb, min(pe, clen) - 1]
+    pool += [t for e in range(TILE, clen, TILE) for t in (e - 1, e)]
+    pool += [t for e in range(STEP, clen, TILE) for t in (e - 1, e)]
+    seen, res = set(), []
+    for t in pool:
+        if 0 <= t < clen and t not in seen:
+            seen.add(t)
+            res.append(t)
+    return res
+
+
+def edge_rows(rlen, pieces=None):
+    """{class: rows}: the first and the last row of every 32-row step, of every wave's 64 rows and of every 256-row block (a ragged
+    last one ends at the last live row), and of every row piece of a split dK / dV launch"""
+    res = {}
+    for name, n in (("step", STEP), ("wave", WAVE_ROWS), ("block", BLOCK_ROWS)):
+        res[name + "_first"] = list(range(0, rlen, n))
+        res[name + "_last"] = [min(r + n, rlen) - 1 for r in range(0, rlen, n)]
+    for pb, pe in (pieces or {}).get("dkv", ()):
+        if min(pe, rlen) > pb:
+            res.setdefault("piece_first", []).append(pb)
+            res.setdefault("piece_last", []).append(min(pe, rlen) - 1)
+    return res
+
+
+PER_ROW, CAPACITY = 3, 12    # pool keys of an ordinary row; most needles a row may carry
+
+
+def needle_plan(R, C, rlen, clen, causal, pieces, salt, spike=False):
+    """-> [set of needle keys per row r < R], [forbidden key or None per row].  Every row: key 0 (so that no later needle fires the
+    deferred rescale; a spike case keeps it for its spiked rows only), its causal frontier and the key before it, PER_ROW pool keys in rotation (`salt`: heads
+    and batch entries differ); the last row of every 256-row block also key 64 (a tile skipped in one block only shows in that block).  Transposed property: every pool key, in the pool's order of importance, is handed to one row of each
+    class of edge_rows() that sees it and still has room (CAPACITY needles).  The step and wave classes hold every pool key.  The block
+    and piece classes have few rows (R = 513: three first rows of a block, two of a piece, 66 pool keys): each head and batch entry
+    starts its walk of the pool 2 (CAPACITY - 2) keys further on, so a grid of several heads covers between them what one head's
+    rows cannot hold (tests/test_train_sensitivity.py asserts the counts).
+    Forbidden: the key after the frontier (causal), else the key AT the key length (padding): a row that reads it is taken over."""
+    off = max(clen - rlen, 0)
+    pool = key_pool(clen, pieces)
+    rows = [set() for _ in range(R)]
+    front = [min(r + off, clen - 1) if causal else clen - 1 for r in range(R)]
+    classes = edge_rows(min(rlen, R), pieces)
+    edges = {r for members in classes.values() for r in members}
+    for r in range(R):
+        if not spike:
+            rows[r].add(0)
+        if causal:
+            rows[r] |= {front[r]} | ({front[r] - 1} if front[r] >= 1 else set())
+        for i in range(0 if r in edges else PER_ROW):      # (an edge row's room goes to the keys its classes hand it)
+            t = pool[(r * PER_ROW + i + salt * 5) % len(pool)]
+            if t <= front[r]:
+                rows[r].add(t)
+    for r in classes["block_last"]:                        # a ragged last block may be ONE row: every block sees keys 64..127 dropped
+        if TILE <= front[r]:
+            rows[r].add(TILE)
+    for kind in ("piece", "block", "wave", "step"):        # (a piece's edge rows are mostly block edge rows too: what they hold counts twice)
+        start = (salt * 2 * (CAPACITY - 2)) % len(pool) if kind in ("piece", "block") else 0
+        for side in ("_first", "_last"):
+            members = classes.get(kind + side, [])
+            for i, t in enumerate(pool[start:] + pool[:start] if members else ()):
+                for j in range(len(members)):
+                    r = members[(i + salt + j) % len(members)]
+                    if t in rows[r]:
+                        break
+                    if t <= front[r] and len(rows[r]) < CAPACITY:
+                        rows[r].add(t)
+                        break
+    for r in range(R):
+        for t in (front[r], front[r] - 1, 0):              # never a one-needle row where there is a second key: dS would vanish
+            if len(rows[r]) < 2 and t >= 0:
+                rows[r].add(t)
+    forbidden = [(front[r] + 1 if causal else clen) for r in range(R)]
+    return rows, [f if f < C else None for f in forbidden]
+
+
+def code_layout(C, Dh, h=0):
+    """(mA, mB, dims): key j carries the code (j % mA, (j // mA) % mB) as a 1 on dimension dims[j % mA] and a 1 on dimension
+    dims[mA + (j // mA) % mB]; mA mB >= C where D has room for mA + mB dimensions (else codes repeat every mA mB keys); `dims`
+    spreads the code over all 32-wide d blocks and differs between heads.  The other D - mA - mB dimensions are free."""
+    mA = int(math.ceil(math.sqrt(C)))
+    mB = -(-C // mA)
+    if mA + mB > Dh:
+        mA = Dh // 2
+        mB = Dh - mA
+    stride = next(s for s in (7, 11, 13, 1) if math.gcd(s, Dh) == 1)
+    return mA, mB, (np.arange(Dh) * stride + 5 * h) % Dh
+
+
+SUPPRESSED = 9.0    # nats below the needles: the score of a key that shares one code half with no needle of the row (18: neither half)
+
+
+def needle_inputs(B, H, R, C, Dh, fmt, *, causal=False, row_lengths=None, key_lengths=None, pieces=None, spike=False, seed=0):
+    """-> q, k, v, dO (float64 values of the 16-bit type, asserted exact) and info {(b, h, r): (needle keys, forbidden key)}.
+
+    The tension: in the mixed mode a score moves by u T_ij, T_ij = scale sum_d |q_d k_jd| >= |s_ij|, so a needle that stands
+    ln(keys) + c ABOVE a background at 0 carries a relative error of u (ln(keys) + c) -- 3 % at 257 keys in bf16, which would hide
+    every defect below that.  Softmax is shift invariant and T is not: here the needles score about 0 and the background is pushed
+    DOWN.  Key j carries a two-part one-hot code (code_layout) and U(-1, 1) on the free dimensions; V, dO ~ U(-1, 1), dense.  Row r
+    with needles T: q = -SUPPRESSED sqrt(D) on every code dimension that no key of T uses, +-sqrt(D) / 8 or / 16 on those T uses and on two
+    free dimensions (few-hot: a score spread of +-0.5 at T_ij <= 0.5).  A key scores 0 +- 0.5 where both halves of its code are used by T --
+    T itself and at most |T|^2 - |T| further keys, needles by the same right -- and -9 or -18 otherwise: the needles have T_ij < 1,
+    the background's large T_ij multiplies weights of e^-9.  The forbidden key (needle_plan) is one more key the row does not
+    suppress: a row that reads it gains a needle.  dP_ij - D_i = dO_i . (v_j - O_i) is of the order of |dO| sqrt(D) / 3 on every needle.
+    spike: row 40 of every 64 keeps key 0 and its last visible key t* only and adds +9 sqrt(D) on the second
+    code dimension of t*: t* scores +9, the keys of its code run (its neighbours, all late) 0: the late dominant key that fires the
+    deferred rescale.  Rows at and past the row length are built like live rows (a kernel that reads them moves dK / dV)."""
+    rng = np.random.default_rng(seed)
+    k = round_to(rng.uniform(-1, 1, (B, H, C, Dh)), fmt)
+    v = round_to(rng.uniform(-1, 1, (B, H, C, Dh)), fmt)
+    dO = round_to(rng.uniform(-1, 1, (B, H, R, Dh)), fmt)
+    q = np.zeros((B, H, R, Dh))
+    rl, cl = _lengths(row_lengths, B, R), _lengths(key_lengths, B, C)
+    info = {}
+    gamma = float(round_to(np.array([SUPPRESSED * math.sqrt(Dh)]), fmt)[0])
+    keys = np.arange(C)
+    for h in range(H):
+        mA, mB, dims = code_layout(C, Dh, h)
+        free = dims[mA + mB:]
+        ka, kb = keys % mA, (keys // mA) % mB
+        for b in range(B):
+            k[b, h][:, dims[:mA + mB]] = 0.0
+            k[b, h, keys, dims[ka]] = 1.0
+            k[b, h, keys, dims[mA + kb]] = 1.0
+            rows, forbidden = needle_plan(R, C, int(rl[b]), int(cl[b]), causal, pieces, b * H + h, spike)
+            off = max(int(cl[b]) - int(rl[b]), 0)
+            for r in range(R):
+                T = set(rows[r])
+                last = min(r + off, int(cl[b]) - 1) if causal else int(cl[b]) - 1
+                spiked = spike and r % TILE == 40 and last >= mA
+                if spiked:
+                    T = {0, last}
+                U = sorted(T | ({forbidden[r]} if forbidden[r] is not None else set()))
+                row = np.zeros(Dh)
+                row[dims[:mA + mB]] = -gamma
+                lifted = np.unique(np.concatenate([dims[ka[U]], dims[mA + kb[U]]]))
+                row[lifted] = rng.choice([-1.0, -0.5, 0.5, 1.0], len(lifted)) * 0.125 * math.sqrt(Dh)     # few-hot: +-0.125 per code half
+                if spiked:
+                    row[dims[mA + kb[last]]] = gamma
+                if len(free):                      # and two free dimensions: T_ij = scale sum_d |q_d k_jd| <= 0.5 on a needle
+                    row[free[(r * 2 + np.arange(2)) % len(free)]] = rng.choice([-1.0, 1.0], 2) * 0.125 * math.sqrt(Dh)
+                q[b, h, r] = row
+                info[(b, h, r)] = (sorted(T), forbidden[r])
+    q = round_to(q, fmt)
+    for b in range(B):          # dO = U(-1, 1) + 8 / D units along the row's O: D_i = dO_i . O_i is then about 1.4 + noise in every row
+        vis = _visible(R, C, int(rl[b]), int(cl[b]), causal)
+        for h in range(H):
+            P, _m, _l = _softmax((q[b, h] @ k[b, h].T) / math.sqrt(Dh), vis)
+            O = P @ v[b, h]
+            dO[b, h] = round_to(dO[b, h] + (8.0 / Dh) * O / np.sqrt((O * O).mean(axis=1, keepdims=True)), fmt)
+    for x in (q, k, v, dO):
+        assert np.array_equal(round_to(x, fmt), x) and np.isfinite(x).all(), "the inputs must survive the cast to the 16-bit type"
+    return q, k, v, dO, info
+
+
+def needle_keys(info):
+    """{(b, h): {key: [rows that hold it as a needle]}}"""
+    res = {}
+    for (b, h, r), (needles, _f) in info.items():
+        for t in needles:
+            res.setdefault((b, h), {}).setdefault(t, []).append(r)
+    return res
+
+
+# ----------------------------------------------------------------------------------------------------------------------- checker
+def compare(got, ref, *, out="f32", margin=MARGIN, info=None, outputs=OUTPUTS):
+    """got {output: array, NaN (the buffer's sentinel) where the launch wrote nothing} against the model -> ({output: worst err /
+    bound over EVERY element of every live row or key}, {output: True where the padding kept the sentinel}, text naming the worst
+    elements)."""
+    bd = bounds(ref, out, margin)
+    worst, padding, lines = {}, {}, []
+    for name in outputs:
+        g = f64(got[name])
+        want = getattr(ref, name)
+        live = ref.key_live if name in ("dV", "dK") else ref.row_live      # [B, n]
+        mask = np.broadcast_to(live[:, None, :] if g.ndim == 3 else live[:, None, :, None], g.shape)
+        with np.errstate(invalid="ignore"):
+            ratio = np.abs(g - want) / bd[name]
+        ratio = np.where(mask, np.where(np.isnan(ratio), np.inf, ratio), 0.0)
+        at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+        worst[name] = float(ratio[at])
+        padding[name] = bool(np.isnan(g[~mask]).all())
+        text = "%s worst at %s: got %.6g, model %.6g, |d| / bound = %.3g" % (name, tuple(int(x) for x in at), g[at], want[at], worst[name])
+        if info is not None and name in ("O", "L", "D", "dQ") and tuple(int(x) for x in at[:3]) in info:
+            needles, f = info[tuple(int(x) for x in at[:3])]
+            text += " (the row's needles: keys %s%s)" % (needles, "; forbidden key %d" % f if f is not None else "")
+        if not padding[name]:
+            text += "; PADDING WRITTEN"
+        lines.append(text)
+    return worst, padding, "\n".join(lines)
