@@ -1558,6 +1558,69 @@ def test_block_sparse_mask(shape, causal, empty, low):
     assert all(run.tails_ok.values())
 
 
+@pytest.mark.parametrize("shape,B,H", [((513, 1030, 64), 2, 3), ((257, 4224, 128), 1, 2)], ids=["per-head-per-batch", "two-words"])
+def test_block_sparse_mask_fp32_per_head_and_two_words(shape, B, H):
+    """FP32 operands under a mask per head and per batch entry (non-zero blockMaskStrides, pairwise different masks, a poisoned word
+    before the first mask, between the heads' masks and behind the last) and under a mask of two words per row block (33 column
+    blocks, bits b and b + 32 opposite): a wrong mask word or a wrong stride is a gross error at the FP32 constants of
+    test_block_sparse_mask.  The 16-bit kernels are held to per-element bounds in tests/test_train_parity_mask_gpu.py."""
+    import torch
+    from oracle.network_np import attention_f64, block_mask_to_dense
+    R, C, D = shape
+    rng = np.random.default_rng(R + C + B)
+    rb, cb = (R + 255) // 256, (C + 127) // 128
+    words = (cb + 31) // 32
+    bits = np.zeros((B, H, rb, cb), bool)
+    for b in range(B):
+        for h in range(H):
+            while True:
+                m = _random_block_mask(R, C, 0.4, rng)[0]
+                if cb > 32:
+                    m[:, 32:] = ~m[:, :cb - 32]
+                if not any(np.array_equal(m, bits[i, j]) for i in range(B) for j in range(H) if (i, j) < (b, h)):
+                    break
+            bits[b, h] = m
+    hstride, bstride = rb * words + 3, H * (rb * words + 3) + 5
+    packed = np.full(1 + B * bstride + 4, 0xA5C3965A, np.uint32)
+    for b in range(B):
+        for h in range(H):
+            for i in range(rb):
+                for j in range(cb):
+                    at = 1 + b * bstride + h * hstride + i * words + j // 32
+                    if j % 32 == 0:
+                        packed[at] = 0
+                    if bits[b, h, i, j]:
+                        packed[at] |= np.uint32(1) << np.uint32(j % 32)
+    mask_dev = torch.from_numpy(packed.view(np.int32)).cuda()
+    host = {n: rng.standard_normal((B, H, R if n in ("Q", "dO") else C, D)).astype(np.float32) for n in ("Q", "K", "V", "dO")}
+    ops = {"Q": Op.Q, "K": Op.K, "V": Op.V, "dO": Op.dO}
+    bufs = {ops[n]: torch.from_numpy(x).cuda() for n, x in host.items()}
+    outs = {"O": (Op.O, R, D), "L": (Op.L, R, 1), "D": (Op.D, R, 1), "dQ": (Op.dQ, R, D), "dK": (Op.dK, C, D), "dV": (Op.dV, C, D)}
+    for name, (op, n, d) in outs.items():     # one spare batch entry behind each output: the canary
+        bufs[op] = torch.full((B + 1, H, n, d) if d > 1 else (B + 1, H, n), float("nan"), device="cuda")
+    hs = {Op.Q: R * D, Op.K: C * D, Op.V: C * D, Op.O: R * D, Op.L: R, Op.D: R, Op.dO: R * D, Op.dV: C * D, Op.dK: C * D, Op.dQ: R * D}
+    bs = {op: v * H for op, v in hs.items()}
+    desc = make_desc(R, C, D)
+    stream = torch.cuda.current_stream().cuda_stream
+    for t in (AttentionKernelType.forward, AttentionKernelType.backwardQuery, AttentionKernelType.backwardKeyValue):
+        AttentionKernel(desc.kernelDescriptor(t)).dispatch(bufs, row=R, column=C, heads=H, batches=B, headStrides=hs, batchStrides=bs, stream=stream,
+                                                           blockMask=mask_dev[1:], blockMaskWords=words, blockMaskStrides=(hstride, bstride))
+    torch.cuda.synchronize()
+    assert np.array_equal(mask_dev.cpu().numpy(), packed.view(np.int32))
+    got = {name: bufs[op].cpu().numpy() for name, (op, n, d) in outs.items()}
+    for name, x in got.items():
+        assert np.isnan(x[B]).all(), (name, "the canary entry behind the buffer was written")
+    tol = dict(O=2e-5, D=2e-5, dV=3e-5, dK=3e-5, dQ=3e-5)
+    for b in range(B):
+        for h in range(H):
+            ref = attention_f64(host["Q"][b, h], host["K"][b, h], host["V"][b, h], host["dO"][b, h], mask=block_mask_to_dense(bits[b, h], R, C))
+            assert np.isfinite(ref["L"]).all()
+            for name, bound in tol.items():
+                x = got[name][b, h] * (np.sqrt(np.float32(D)) if name == "D" else 1)
+                assert np.abs(x - ref[name]).max() < bound, (name, b, h, float(np.abs(x - ref[name]).max()))
+            assert np.abs(got["L"][b, h] / np.float32(harness.LOG2E) - ref["L"]).max() < 2e-5, (b, h)
+
+
 # ---- traversal-parallel backward launches through a caller-provided workspace ------------------------
 @pytest.mark.parametrize("shape,causal", [((4096, 4096, 64), False), ((2048, 4096, 128), False), ((3000, 3000, 128), True),
                                           ((1024, 2048, 256), False), ((2100, 1500, 192), False), ((1500, 2100, 256), True),

@@ -58,7 +58,7 @@ def _inputs(B, Hq, Hkv, R, C, D, seed):
     return {Op.Q: rnd(B, Hq, R, D), Op.K: rnd(B, Hkv, C, D), Op.V: rnd(B, Hkv, C, D), Op.dO: rnd(B, Hq, R, D)}
 
 
-def _run(desc, x, B, Hq, Hkv, R, C, D, causal=False, lengths=None, mask=None, fwd_workspace=False, repeat=1):
+def _run(desc, x, B, Hq, Hkv, R, C, D, causal=False, lengths=None, mask=None, fwd_workspace=False, repeat=1, mask_strides=(0, 0)):
     """one forward + backwardQuery + backwardKeyValue pass with Hkv declared K / V heads (G = Hq / Hkv) -> (values, launch forms, canary
     intact).  Values are fp32 CPU tensors [B, heads, seq, D] / [B, heads, seq] of what the device stored."""
     G = Hq // Hkv
@@ -85,7 +85,7 @@ def _run(desc, x, B, Hq, Hkv, R, C, D, causal=False, lengths=None, mask=None, fw
     if lengths is not None:
         kw.update(rowLengths=lengths[0].to(dev), columnLengths=lengths[1].to(dev))
     if mask is not None:
-        kw.update(blockMask=mask.to(dev), blockMaskWords=int(mask.shape[1]))
+        kw.update(blockMask=mask.to(dev), blockMaskWords=int(mask.shape[-1]), blockMaskStrides=mask_strides)
     before = {op: bufs[op].clone() for op in (Op.K, Op.V, Op.dK, Op.dV)}
     forms, runs = {}, []
     for _ in range(repeat):
@@ -158,11 +158,11 @@ def _stored(x, desc):
 
 
 def _case(storage, D, Hq, G, B=1, R=200, C=264, causal=False, lengths=None, mask=None, transposed_kv=False, outputs16=False,
-          oracle=True, fwd_workspace=False, seed=0, expect_split=False):
+          oracle=True, fwd_workspace=False, seed=0, expect_split=False, mask_strides=(0, 0)):
     Hkv = Hq // G
     desc = _descriptor(storage, R, C, D, transposed_kv, outputs16)
     x = _inputs(B, Hq, Hkv, R, C, D, seed)
-    (got, again), forms, intact = _run(desc, x, B, Hq, Hkv, R, C, D, causal, lengths, mask, fwd_workspace, repeat=2)
+    (got, again), forms, intact = _run(desc, x, B, Hq, Hkv, R, C, D, causal, lengths, mask, fwd_workspace, repeat=2, mask_strides=mask_strides)
     assert forms[T.backwardKeyValue].endswith(" + attn_kv_group_sum x%d" % G), forms[T.backwardKeyValue]
     if expect_split:
         assert "column-parallel" in forms[T.forward], forms[T.forward]
@@ -172,7 +172,7 @@ def _case(storage, D, Hq, G, B=1, R=200, C=264, causal=False, lengths=None, mask
     # the same launch on K / V materialised per query head
     xm = dict(x)
     xm[Op.K], xm[Op.V] = (x[op].repeat_interleave(G, dim=1) for op in (Op.K, Op.V))
-    (mat,), mforms, _ = _run(desc, xm, B, Hq, Hq, R, C, D, causal, lengths, mask, fwd_workspace)
+    (mat,), mforms, _ = _run(desc, xm, B, Hq, Hq, R, C, D, causal, lengths, mask, fwd_workspace, mask_strides=mask_strides)
     assert mforms[T.forward] == forms[T.forward] and mforms[T.backwardQuery] == forms[T.backwardQuery], (mforms, forms)
     for op in (Op.O, Op.L, Op.dQ, Op.D):
         assert _bits_equal(got[op], mat[op]), (op.name, forms, (got[op].float() - mat[op].float()).abs().max())
@@ -228,6 +228,25 @@ def test_per_batch_lengths(storage, D, Hq, G):
 def test_block_mask_with_an_unattended_column_block(storage, D, Hq, G):
     bits = torch.tensor([[True, False, True], [True, False, False]])   # 2 row blocks x 3 column blocks; column block 1 never attended
     _case(storage, D, Hq, G, R=300, C=384, mask=pack_block_mask(bits))
+
+
+@pytest.mark.parametrize("storage,D", [("bf16", 128), ("f16", 64), ("f32", 128)])
+def test_block_mask_per_query_head(storage, D):
+    """a mask per QUERY head (blockMaskHeadStride counts query heads, include/mfa.h) and per batch entry, Hq = 4, G = 2: the two query
+    heads of one K / V head attend different blocks.  Bit-identical to the materialised launch with the same masks and strides, which
+    tests/test_train_parity_mask_gpu.py holds to the per-element bounds; a launch that took head h's mask at h / G would differ."""
+    B, Hq, G = 2, 4, 2
+    patterns = ([[1, 0, 1], [0, 1, 1]], [[0, 1, 0], [1, 1, 0]], [[1, 1, 0], [0, 0, 1]], [[0, 0, 1], [1, 0, 0]],
+                [[1, 0, 0], [0, 1, 0]], [[0, 1, 1], [1, 0, 1]], [[1, 1, 1], [0, 1, 0]], [[0, 1, 0], [0, 0, 1]])
+    bits = torch.tensor(patterns, dtype=torch.bool).view(B, Hq, 2, 3)           # 2 row blocks x 3 column blocks, all eight different
+    mask = torch.stack([pack_block_mask(m) for m in bits.view(-1, 2, 3)]).view(B, Hq, 2, 1)
+    _case(storage, D, Hq, G, B=B, R=300, C=384, mask=mask.reshape(-1, 1), mask_strides=(2, 2 * Hq))
+    # (the masks matter: with head 0's mask for every head the result is another one)
+    desc = _descriptor(storage, 300, 384, D)
+    x = _inputs(B, Hq, Hq // G, 300, 384, D, 0)
+    (own,), _f, _i = _run(desc, x, B, Hq, Hq // G, 300, 384, D, mask=mask.reshape(-1, 1), mask_strides=(2, 2 * Hq))
+    (shared,), _f, _i = _run(desc, x, B, Hq, Hq // G, 300, 384, D, mask=mask.reshape(-1, 1))
+    assert not _bits_equal(own[Op.O], shared[Op.O]) and _bits_equal(own[Op.O][0, 0], shared[Op.O][0, 0])
 
 
 @pytest.mark.parametrize("storage,D,Hq,G", [("bf16", 128, 8, 2), ("f16", 64, 28, 7), ("bf16", 256, 8, 4), ("f32", 128, 8, 8),

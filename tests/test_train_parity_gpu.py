@@ -6,6 +6,10 @@ every live row and key under the bound at the committed margin, the padding and 
 worst err / bound at margin 1.  Each case asserts the `variant` and the `launchForm` it means to test, so that a shape cannot slide
 onto another kernel unnoticed.  tests/test_train_sensitivity.py proves on the CPU that this check sees each named wrong kernel.
 
+run_case() is the one runner: tests/test_train_parity_mask_gpu.py (block masks: the model and the inputs take the mask, the mask
+buffer is poisoned around every head's words) and tests/test_train_parity_transposed_gpu.py (transposed operands: only the buffers'
+layout changes; the padding of every leading dimension is NaN before and after) build their cases with case() and run them here.
+
 FP16 cases store dO in FP16 next to FP16 Q / K / V (the model's one 16-bit type); the reference's own FP16 / BF16-dO mix keeps the
 checks of tests/test_attention_gpu.py.
 """
@@ -28,11 +32,19 @@ MODES = {"bf16-mixed": ("bf16", True), "bf16-exact": ("bf16", False), "f16-mixed
 _MODELS = {}
 
 
-def case(name, R, C, D, modes, *, B=1, H=1, causal=False, rl=None, cl=None, workspace=False, rows=(), spike=False, variant=None, form=None):
+def case(name, R, C, D, modes, *, B=1, H=1, causal=False, rl=None, cl=None, workspace=False, rows=(), spike=False, variant=None, form=None,
+         mask=None, tr=None, ld=None, only=None):
     """variant / form: {kernel type: text the kernel's variant / the launch's form must contain; form: several joined by |, a leading !
-    for text it must not contain}"""
+    for text it must not contain, a leading ^ for text it must start with}.
+    mask: None or dict(per="shared" | "head" | "batch" | "both", seed=, empty_last=, need_blocks=): a block mask of
+    train_model.needle_mask, one for the grid or one per head / batch entry / both (pairwise different), passed with non-zero
+    blockMaskStrides wherever it is not shared.
+    tr: transposeState (Q, K, V, O): operand X^T lies [D][leading dimension] per head (dQ follows Q, dK K, dV V, dO O).
+    ld: {operand: leading dimension} (default: the sequence length of a transposed operand, D of a row-major one); the padding columns
+    hold NaN, in inputs and outputs.  only: the kernel types to run (default all three)."""
     return [pytest.param(dict(R=R, C=C, D=D, B=B, H=H, causal=causal, rl=rl, cl=cl, workspace=workspace, rows=rows, spike=spike,
-                              variant=variant or {}, form=form or {}, mode=m), id="%s-%dx%dx%d-%s" % (name, R, C, D, m)) for m in modes]
+                              variant=variant or {}, form=form or {}, mode=m, mask=mask, tr=tuple(tr or (False,) * 4), ld=ld or {},
+                              only=tuple(only or (FWD, DQ, DKV))), id="%s-%dx%dx%d-%s" % (name, R, C, D, m)) for m in modes]
 
 
 L3R, L3C = [300, 77, 1], [333, 100, 64]          # per-batch lengths: an entry shorter than a workgroup, a one-row entry
@@ -98,11 +110,11 @@ def _kernels(c, fmt, mixed):
     desc = AttentionDescriptor()
     desc.lowPrecisionInputs, desc.lowPrecisionIntermediates = True, mixed
     desc.matrixDimensions = (c["R"], c["C"], c["D"])
-    desc.transposeState = (False,) * 4
+    desc.transposeState = c["tr"]
     desc.lowPrecisionInputType = P.BF16 if fmt == "bf16" else P.FP16
     kernels, precisions = {}, {}
     with parameter_rows(*c["rows"]):
-        for t in (FWD, DQ, DKV):
+        for t in c["only"]:
             kdesc = desc.kernelDescriptor(t)
             if fmt == "f16" and Op.dO in kdesc.memoryPrecisions:
                 kdesc.memoryPrecisions[Op.dO] = P.FP16
@@ -119,69 +131,164 @@ def _pieces(c, kernels):
     return train_model.pieces_of(named, c["R"], c["C"]), counts
 
 
-def _problem(c, fmt, mixed, pieces):
+def block_mask_of(c):
+    """None, or the case's mask as bool [B, H, row blocks, column blocks] (what the model takes)"""
+    m = c["mask"]
+    if m is None:
+        return None
+    B, H = c["B"], c["H"]
+    kw = dict(causal=c["causal"], empty_last=m.get("empty_last", False), need_blocks=m.get("need_blocks", ()))
+    distinct = {"shared": 1, "head": H, "batch": B, "both": B * H}[m["per"]]
+    masks, seed = [], m.get("seed", 0)
+    while len(masks) < distinct:                             # (a small mask has few admissible patterns: draw until all differ)
+        one = train_model.needle_mask(c["R"], c["C"], seed, **kw)
+        seed += 1
+        if not any(np.array_equal(one, x) for x in masks):
+            masks.append(one)
+    grid = {"shared": lambda b, h: 0, "head": lambda b, h: h, "batch": lambda b, h: b, "both": lambda b, h: b * H + h}[m["per"]]
+    bits = np.array([[masks[grid(b, h)] for h in range(H)] for b in range(B)])
+    assert len({x.tobytes() for x in bits.reshape((-1,) + bits.shape[2:])}) == distinct, "the masks of the grid are pairwise different"
+    return bits
+
+
+POISON = 0xA5C3965A          # mask words no launch may read: one before the first mask, between the heads' masks, behind the last
+
+
+def mask_buffer(c, bits):
+    """-> int32 array (the first word is poison: the launch gets the address of word 1), words per row block, (head, batch) strides"""
+    B, H = c["B"], c["H"]
+    packed = train_model.pack_mask(bits)                     # [B, H, row blocks, words]
+    nrb, words = packed.shape[2:]
+    per_head, per_batch = c["mask"]["per"] in ("head", "both"), c["mask"]["per"] in ("batch", "both")
+    hs = nrb * words + 3 if per_head else 0
+    bs = ((H * hs if per_head else nrb * words) + 5) if per_batch else 0
+    nb, nh = (B if per_batch else 1), (H if per_head else 1)
+    buf = np.full(1 + (nb - 1) * bs + (nh - 1) * hs + nrb * words + 4, POISON, dtype=np.uint32)
+    for b in range(nb):
+        for h in range(nh):
+            at = 1 + b * bs + h * hs
+            buf[at:at + nrb * words] = packed[b, h].reshape(-1)
+    return buf.view(np.int32), words, (hs, bs)
+
+
+def _problem(c, fmt, mixed, pieces, block_mask=None):
     """needle inputs and the float64 model of a case, computed once per (case, type, mode)"""
-    key = (c["R"], c["C"], c["D"], c["B"], c["H"], c["causal"], str(c["rl"]), str(c["cl"]), c["spike"], fmt, mixed, str(pieces))
+    key = (c["R"], c["C"], c["D"], c["B"], c["H"], c["causal"], str(c["rl"]), str(c["cl"]), c["spike"], fmt, mixed, str(pieces),
+           None if block_mask is None else block_mask.tobytes())
     if key not in _MODELS:
         geo = dict(causal=c["causal"], row_lengths=c["rl"], key_lengths=c["cl"], pieces=pieces)
+        if block_mask is not None:
+            geo["block_mask"] = block_mask
         q, k, v, dO, info = train_model.needle_inputs(c["B"], c["H"], c["R"], c["C"], c["D"], fmt, spike=c["spike"], seed=c["R"] + c["D"], **geo)
         _MODELS[key] = (q, k, v, dO, info, train_model.model(q, k, v, dO, fmt=fmt, mixed=mixed, **geo))
     return _MODELS[key]
 
 
 TORCH_TYPE = {P.FP32: "float32", P.FP16: "float16", P.BF16: "bfloat16"}
+SEQ = {Op.Q: "R", Op.O: "R", Op.dO: "R", Op.dQ: "R", Op.K: "C", Op.V: "C", Op.dK: "C", Op.dV: "C"}
 
 
-@pytest.mark.parametrize("c", CASES)
-def test_training_kernels_inside_the_per_element_bounds(c):
+def run_case(c, device="cuda", launch=True):
+    """launch the case's kernels and hold all their outputs to the model's bounds (see the module's docstring) -> the launch forms.
+    launch=False (any device): the forms only, nothing is started"""
+    import time
     import torch
     fmt, mixed = MODES[c["mode"]]
     R, C, D, B, H = c["R"], c["C"], c["D"], c["B"], c["H"]
     kernels, prec = _kernels(c, fmt, mixed)
     for t, text in c["variant"].items():
         assert text in kernels[t].variant, (t.name, kernels[t].variant, text)
-    pieces, counts = _pieces(c, kernels) if c["workspace"] else (None, {})
-    q, k, v, dO, info, ref = _problem(c, fmt, mixed, pieces)
+    transposed = any(c["tr"])
+    pieces, counts = _pieces(c, kernels) if c["workspace"] and not transposed else (None, {})
+    bits = block_mask_of(c)
+    q, k, v, dO, info, ref = _problem(c, fmt, mixed, pieces, bits)
+    tq, tk, tv, to = c["tr"]
+    tr_of = {Op.Q: tq, Op.dQ: tq, Op.K: tk, Op.dK: tk, Op.V: tv, Op.dV: tv, Op.O: to, Op.dO: to}
+    ld_of = {op: c["ld"].get(op, c[SEQ[op]] if tr_of[op] else D) for op in SEQ}
+
+    def shape_of(op):            # [rows][leading dimension] per head: X^T is [D][ld], X is [sequence][ld]
+        return (H, D if tr_of[op] else c[SEQ[op]], ld_of[op])
+
+    def view(x, op):             # the [.., sequence, D] view of a buffer laid out by shape_of
+        return x[..., :c[SEQ[op]]].swapaxes(-1, -2) if tr_of[op] else x[..., :D]
+
+    def pad(x, op):
+        return x[..., (c[SEQ[op]] if tr_of[op] else D):]
 
     def dev_in(x, op):
-        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(getattr(torch, TORCH_TYPE[prec[op]])).cuda()
+        host = np.full((B,) + shape_of(op), np.nan, dtype=np.float32)
+        view(host, op)[...] = x
+        return torch.from_numpy(host).to(getattr(torch, TORCH_TYPE[prec[op]])).to(device)
 
     def dev_out(op, *shape):     # B live entries and one spare entry, the canary: all NaN
-        return torch.full((B + 1,) + shape, float("nan"), device="cuda", dtype=getattr(torch, TORCH_TYPE[prec[op]]))
+        return torch.full((B + 1,) + (shape or shape_of(op)), float("nan"), device=device, dtype=getattr(torch, TORCH_TYPE[prec[op]]))
 
     bufs = {Op.Q: dev_in(q, Op.Q), Op.K: dev_in(k, Op.K), Op.V: dev_in(v, Op.V), Op.dO: dev_in(dO, Op.dO),
-            Op.O: dev_out(Op.O, H, R, D), Op.L: dev_out(Op.L, H, R), Op.D: dev_out(Op.D, H, R),
-            Op.dQ: dev_out(Op.dQ, H, R, D), Op.dK: dev_out(Op.dK, H, C, D), Op.dV: dev_out(Op.dV, H, C, D)}
+            Op.O: dev_out(Op.O), Op.L: dev_out(Op.L, H, R), Op.D: dev_out(Op.D, H, R),
+            Op.dQ: dev_out(Op.dQ), Op.dK: dev_out(Op.dK), Op.dV: dev_out(Op.dV)}
     for op, x in ((Op.Q, q), (Op.K, k), (Op.V, v), (Op.dO, dO)):
-        assert np.array_equal(bufs[op].double().cpu().numpy(), x), "the inputs must reach the device exactly"
-    hs = {Op.Q: R * D, Op.K: C * D, Op.V: C * D, Op.O: R * D, Op.L: R, Op.D: R, Op.dO: R * D, Op.dV: C * D, Op.dK: C * D, Op.dQ: R * D}
+        assert np.array_equal(view(bufs[op].double().cpu().numpy(), op), x), "the inputs must reach the device exactly"
+    hs = {op: int(np.prod(shape_of(op)[1:])) for op in SEQ}
+    hs.update({Op.L: R, Op.D: R})
     bs = {op: s * H for op, s in hs.items()}
     kw = dict(row=R, column=C, heads=H, batches=B, headStrides=hs, batchStrides=bs, causal=c["causal"])
+    if transposed or c["ld"]:
+        kw["leadingDimensions"] = {op: n for op, n in ld_of.items() if tr_of[op] or op in c["ld"]}
     if c["rl"] is not None:
-        kw["rowLengths"] = torch.tensor(c["rl"], dtype=torch.int32, device="cuda")
-        kw["columnLengths"] = torch.tensor(c["cl"], dtype=torch.int32, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    forms = {}
-    for t in (FWD, DQ, DKV):
+        kw["rowLengths"] = torch.tensor(c["rl"], dtype=torch.int32, device=device)
+        kw["columnLengths"] = torch.tensor(c["cl"], dtype=torch.int32, device=device)
+    if bits is not None:
+        words_host, words, strides = mask_buffer(c, bits)
+        mask_dev = torch.from_numpy(words_host).to(device)
+        kw.update(blockMask=mask_dev[1:], blockMaskWords=words, blockMaskStrides=strides)
+    stream = torch.cuda.current_stream().cuda_stream if launch else None
+    forms, spaces = {}, {}
+    began = time.perf_counter()
+    for t in c["only"]:
         ws = None
         if c["workspace"]:
             need = kernels[t].workspaceSize(row=R, column=C, heads=H, batches=B)
-            ws = torch.empty(need + 256, dtype=torch.uint8, device="cuda") if need else None
+            ws = torch.full((need + 256,), 0xFF, dtype=torch.uint8, device=device) if need else None     # NaN in every type; 256 canary bytes
+            spaces[t] = (ws, need)
         forms[t] = kernels[t].launchForm(bufs, workspace=ws, **kw)
         for text in c["form"].get(t, "").split("|") if t in c["form"] else ():
-            assert (text[1:] not in forms[t]) if text.startswith("!") else (text in forms[t]), (t.name, forms[t], text)
-        kernels[t].dispatch(bufs, stream=stream, workspace=ws, **kw)
+            ok = (text[1:] not in forms[t]) if text.startswith("!") else forms[t].startswith(text[1:]) if text.startswith("^") else (text in forms[t])
+            assert ok, (t.name, forms[t], text)
+        if launch:
+            kernels[t].dispatch(bufs, stream=stream, workspace=ws, **kw)
+    if not launch:
+        return forms
     torch.cuda.synchronize()
-    raw = {op.description: bufs[op].double().cpu().numpy() for op in (Op.O, Op.L, Op.D, Op.dQ, Op.dK, Op.dV)}
+    spent = time.perf_counter() - began
+    for t, (ws, need) in spaces.items():
+        assert ws is None or bool((ws[need:] == 0xFF).all()), "%s: the canary behind the workspace was written" % t.name
+    if bits is not None:
+        assert np.array_equal(mask_dev.cpu().numpy(), words_host), "the mask buffer was written"
+    outputs = tuple(n for n, t in (("O", FWD), ("L", FWD), ("D", DQ), ("dV", DKV), ("dK", DKV), ("dQ", DQ)) if t in c["only"])
+    ops = {op.description: op for op in (Op.O, Op.L, Op.D, Op.dQ, Op.dK, Op.dV)}
+    raw = {name: bufs[ops[name]].double().cpu().numpy() for name in outputs}
+    got = {}
     for name, x in raw.items():
         assert np.isnan(x[B]).all(), "%s: the canary entry behind the buffer was written" % name
-    got = {name: x[:B] for name, x in raw.items()}
-    got["L"] = got["L"] / train_model.LOG2E                 # stored in log2 units
-    got["D"] = got["D"] * math.sqrt(D)                      # stored times the softmax scale
-    at_one, _padding, _text = compare(got, ref, margin=1, info=info)
-    worst, padding, text = compare(got, ref, info=info)
-    print("train parity %s %s: err / bound at margin 1: %s; pieces %s; %s" % (
+        if ops[name] in SEQ:
+            assert np.isnan(pad(x[:B], ops[name])).all(), "%s: the padding of the leading dimension was written" % name
+            got[name] = np.ascontiguousarray(view(x[:B], ops[name]))
+        else:
+            got[name] = x[:B]
+    if "L" in got:
+        got["L"] = got["L"] / train_model.LOG2E                 # stored in log2 units
+    if "D" in got:
+        got["D"] = got["D"] * math.sqrt(D)                      # stored times the softmax scale
+    at_one, _padding, _text = compare(got, ref, margin=1, info=info, outputs=outputs)
+    worst, padding, text = compare(got, ref, info=info, outputs=outputs)
+    print("train parity %s %s: err / bound at margin 1: %s; pieces %s; %s; %.3f s" % (
         c["mode"], (R, C, D, B, H), " ".join("%s %.3f" % kv for kv in at_one.items()), {t.name: n for t, n in counts.items()},
-        " | ".join(forms[t].split(" (")[0] for t in (FWD, DQ, DKV))))
+        " | ".join(forms[t].split(" (")[0] for t in c["only"]), spent))
     assert all(padding.values()), "rows or keys past a per-batch length were written:\n" + text
     assert max(worst.values()) <= 1.0, "outside the bound at margin %d (%s):\n%s" % (MARGIN, [kernels[t].variant for t in kernels], text)
+    return forms
+
+
+@pytest.mark.parametrize("c", CASES)
+def test_training_kernels_inside_the_per_element_bounds(c):
+    run_case(c)

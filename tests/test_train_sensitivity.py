@@ -15,6 +15,15 @@ per-batch lengths, with and without the library's split plan, at D = 64, 128 and
       `python tests/test_train_sensitivity.py` (it adds (4096, 4096, 128), dense and causal);
   (d) the GPU file takes its bound, margin and checker from train_model.
 
+Block masks (MASKED: eight more cases of (a) and (b)): (513, 1030) -- three row blocks of the mask, the last of one row, nine column
+blocks, the last of six keys -- shared, per head and per batch entry, causal (and (600, 600)), with per-batch lengths, with an empty
+last row block (dead rows), and (257, 4224) at D = 128: two mask words, bits b and b + 32 opposite, codes that repeat every 4096
+keys.  The 18 mutants of train_model.MASK_MUTANTS misread the mask (a word, a stride, a bit, a run's edge key, the causal rule or the
+key length inside a run, the list of row blocks, a dead row); each is exercised by at least two cases and flagged under bf16 mixed on
+every case on which it changes anything, with no exception.  The former mutants run on the masked cases too: where a defect drops
+keys or rows no live row sees, it changes nothing (train_model._seen).  test_needles_cover_the_geometry_of_a_mask: every run edge of
+every row block has a needle on its visible and a trap on its hidden side.
+
 The 26 cases of (b) are a covering set, not the full product: every shape meets dense and causal, lengths and none; (a) runs both
 types and both modes on each and on four more (D = 256 at the two large shapes and under the split plan, the 1024-key split of the
 persistent forwards); the (b) cost of the product (288 cases x 36 mutants of float64 attention) buys no geometry the set lacks.
@@ -77,9 +86,45 @@ def cases():
     return out, extra
 
 
+def masked_cases():
+    """block-masked cases (256 x 128 blocks): (513, 1030) has three row blocks, the last of one row, and nine column blocks, the last
+    of six keys; (257, 4224) at D = 128 has 33 column blocks -- two mask words -- and codes that repeat every 4096 keys, so that key j
+    of block 0 and key j + 4096 of block 32, whose bits are opposite, score alike.  Shared and per-head / per-batch masks (pairwise
+    different), causal, per-batch lengths (a key length inside an active block), an empty last row block (dead rows)."""
+    nm = tm.needle_mask
+    out = []
+
+    def add(name, R, C, D, B, H, mask, causal=False, rl=None, cl=None):
+        c = dict(R=R, C=C, D=D, B=B, H=H, causal=causal, lengths=rl is not None, pieces=False, spike=False, rl=rl, cl=cl, mask_name=name,
+                 block_mask=np.asarray(mask, dtype=bool))
+        c.update(tm.case_flags(R, C, rl, cl))
+        out.append(c)
+
+    add("shared", 513, 1030, 64, 1, 2, nm(513, 1030, 1))
+    grid = np.array([[nm(513, 1030, 10 + 4 * b + h, empty_last=(b, h) == (1, 3)) for h in range(4)] for b in range(2)])
+    add("per-head-per-batch", 513, 1030, 128, 2, 4, grid)
+    add("shared", 513, 1030, 64, 1, 2, nm(513, 1030, 2, causal=True), causal=True)
+    add("shared", 600, 600, 128, 1, 1, nm(600, 600, 3, causal=True), causal=True)
+    add("shared", 513, 1030, 64, 2, 1, nm(513, 1030, 4, need_blocks=(6, 8)), rl=[513, 383], cl=[1030, 821])      # key 821: inside block 6
+    add("per-head-empty-last", 513, 1030, 128, 1, 2, np.array([[nm(513, 1030, 20 + h, empty_last=True) for h in range(2)]]))
+    add("per-head-two-words", 257, 4224, 128, 1, 2, np.array([[nm(257, 4224, 30 + h) for h in range(2)]]))
+    # (entry 0: block 0 active in the 256-row block, so that its rows hold needles among keys 0 .. 127)
+    two = np.array([[next(m for m in (nm(257, 4224, s) for s in range(40, 140)) if m[0, 0])], [nm(257, 4224, 41)]])
+    two[1, 0, 0, 32], two[1, 0, 0, 0] = True, False                                                             # key length 4100: inside block 32
+    add("per-batch-two-words", 257, 4224, 128, 2, 1, two, rl=[257, 200], cl=[4224, 4100])
+    for c in out:
+        m = c["block_mask"].reshape((-1,) + c["block_mask"].shape[-2:])
+        assert len({x.tobytes() for x in m}) == len(m), "the masks of one grid are pairwise different"
+    return out
+
+
 CASES, EMULATED_ONLY = cases()
-case_id = lambda c: "%dx%dx%d-%s-%s-%s%s" % (c["R"], c["C"], c["D"], "causal" if c["causal"] else "dense", "lengths" if c["lengths"] else "full",  # noqa: E731
-                                             "split" if c["pieces"] else "unsplit", "-spike" if c["spike"] else "")
+MASKED = masked_cases()
+case_id = lambda c: "%dx%dx%d-%s-%s-%s%s%s" % (c["R"], c["C"], c["D"], "causal" if c["causal"] else "dense", "lengths" if c["lengths"] else "full",  # noqa: E731
+                                               "split" if c["pieces"] else "unsplit", "-spike" if c["spike"] else "",
+                                               "-mask-" + c["mask_name"] if c.get("mask_name") else "")
+_IDS = [case_id(c) for c in CASES + EMULATED_ONLY + MASKED]
+assert len(set(_IDS)) == len(_IDS)
 
 _PROBLEMS = {}
 
@@ -95,8 +140,10 @@ def problem(case, fmt="bf16", mixed=True):
             pieces = tm.library_pieces(case["R"], case["C"], case["D"], case["H"], case["B"], fmt, mixed)
             assert pieces and all(len(pieces[t]) > 1 for t in ("fwd", "dq", "dkv")), (case_id(case), pieces)
         geo = dict(causal=case["causal"], row_lengths=case["rl"], key_lengths=case["cl"], pieces=pieces)
+        if case.get("block_mask") is not None:
+            geo["block_mask"] = case["block_mask"]
         q, k, v, dO, info = tm.needle_inputs(case["B"], case["H"], case["R"], case["C"], case["D"], fmt, spike=case["spike"],
-                                             seed=(CASES + EMULATED_ONLY).index(case), **geo)
+                                             seed=_IDS.index(case_id(case)), **geo)
         _PROBLEMS[key] = (q, k, v, dO, geo, info, tm.model(q, k, v, dO, fmt=fmt, mixed=mixed, **geo))
     return _PROBLEMS[key]
 
@@ -108,7 +155,7 @@ def emulated_ratios(case, fmt, mixed):
     return tm.compare(got, ref, margin=1, info=info)
 
 
-@pytest.mark.parametrize("case", CASES + EMULATED_ONLY, ids=case_id)
+@pytest.mark.parametrize("case", CASES + EMULATED_ONLY + MASKED, ids=case_id)
 def test_the_rounding_emulated_reference_is_inside_the_bounds(case):
     for fmt in ("bf16", "f16"):
         for mixed in (False, True):
@@ -162,7 +209,7 @@ def test_each_mutant_is_flagged_wherever_it_changes_anything(mutant):
         pytest.skip("a mutant of the split plan: needs the library")
     for fmt, mixed in BOUND_OF.get(mutant, (("bf16", True),)):
         exercised, missed = 0, []
-        for case in CASES:
+        for case in CASES + MASKED:
             if case["pieces"] and not HAVE_LIBRARY:
                 continue
             if noop(case):
@@ -174,7 +221,7 @@ def test_each_mutant_is_flagged_wherever_it_changes_anything(mutant):
             exercised += 1
             if not seen:
                 missed.append(case_id(case))
-        assert exercised >= 1, "%s is exercised by no case" % mutant
+        assert exercised >= (2 if mutant in tm.MASK_MUTANTS else 1), "%s is exercised by %d cases" % (mutant, exercised)
         assert not missed, "%s goes unnoticed on %d of %d cases (%s %s): %s" % (mutant, len(missed), exercised, fmt, "mixed" if mixed else "exact", missed)
 
 
@@ -263,6 +310,59 @@ def test_the_former_inputs_and_bounds_missed_what_the_new_ones_flag():
             mutant, shape, "causal" if causal else "dense", "every former check" if both else "TOL_MIXED", seen)
 
 
+# the former checks of block-masked launches: test_block_sparse_mask of tests/test_attention_gpu.py -- N(0, 1) operands, ONE mask shared
+# by the grid (drawn as that test draws it: density 0.4, seeded by R + C), one mask word, and these constants on the maximum error
+OLD_MASK_TOL = dict(O=1.5e-2, L=1e-3, D=5e-2, dV=2e-2, dK=2e-2, dQ=2e-2)
+OLD_MASK_SHAPES = (((600, 900, 64), False, False), ((1024, 1024, 128), True, False), ((700, 1300, 128), False, True), ((520, 1100, 256), False, False))
+
+
+def old_mask(R, C, empty):
+    rng = np.random.default_rng(R + C)
+    rb, cb = (R + 255) // 256, (C + 127) // 128
+    bits = rng.random((rb, cb)) < 0.4
+    for i in range(rb):
+        if not bits[i].any() and not (empty and i == rb - 1):
+            bits[i, rng.integers(0, cb)] = True
+    if empty:
+        bits[rb - 1, :] = False
+    return bits
+
+
+def old_mask_check_sees(shape, causal, empty, mutant):
+    """None: the mutant changes nothing there; else (seen under OLD_MASK_TOL, {output: maximum absolute error}).  A dead row's L is
+    compared where the model's is finite only, as that test does; its O and dQ must be 0 and its L below -1e30"""
+    R, C, D = shape
+    bits = old_mask(R, C, empty)
+    case = dict(R=R, C=C, D=D, H=1, B=1, causal=causal, pieces=False, spike=False, block_mask=bits, rl=None, cl=None, **tm.case_flags(R, C))
+    if tm.MUTANTS[mutant][1](case):
+        return None
+    key = ("old mask", shape, causal, empty)
+    if key not in _PROBLEMS:
+        q, k, v, dO = network_inputs(*shape)
+        _PROBLEMS[key] = (q, k, v, dO, tm.model(q, k, v, dO, causal=causal, block_mask=bits, with_bounds=False))
+    q, k, v, dO, ref = _PROBLEMS[key]
+    with np.errstate(all="ignore"):
+        bad = tm.model(q, k, v, dO, causal=causal, block_mask=bits, mutant=mutant)
+        alive = ~ref.dead
+        diff = {n: np.abs(getattr(bad, n) - getattr(ref, n)) for n in tm.OUTPUTS}
+        diff["L"] = diff["L"][alive]
+        err = {n: float(np.max(np.where(np.isnan(x), np.inf, x), initial=0.0)) for n, x in diff.items()}
+        dead_ok = (bad.O[ref.dead] == 0).all() and (bad.dQ[ref.dead] == 0).all() and (bad.L[ref.dead] < -1e30).all()
+    return (any(not err[n] < OLD_MASK_TOL[n] for n in tm.OUTPUTS) or not dead_ok, err)
+
+
+def test_what_the_former_mask_check_never_ran():
+    """the table the script prints: on its own shapes the former check sees every misreading of a mask it can
+    exercise -- N(0, 1) scores at these sizes leave rows in which one key carries much of the weight, and the exact mode's FP32 L at
+    1e-3 resolves one key among a few hundred -- but its one shared mask of one
+    word exercises neither a second mask word nor a mask stride, and it has no per-batch key length"""
+    for mutant in ("mask_word0_for_every_block", "mask_row_stride_one_word", "mask_head0_for_all", "mask_batch0_for_all", "mask_head_is_kv_head",
+                   "mask_drops_key_length"):
+        assert all(old_mask_check_sees(*shape, mutant) is None for shape in OLD_MASK_SHAPES), "%s was exercised" % mutant
+    for mutant in ("run_starts_one_key_late", "run_ends_one_key_early", "run_reads_one_key_past"):
+        assert old_mask_check_sees(*OLD_MASK_SHAPES[0], mutant)[0]
+
+
 # ------------------------------------------------------------------------------------------------------------------------- (d)
 def test_the_gpu_file_uses_the_proven_bound():
     pytest.importorskip("torch")
@@ -273,6 +373,12 @@ def test_the_gpu_file_uses_the_proven_bound():
     for own in ("MARGIN =", "def bounds", "def compare"):
         assert own not in source, "test_train_parity_gpu must not define its own %r" % own
     assert source.count("margin=") == source.count("margin=1") , "the only margin the GPU file may pass is 1, for the figure it prints"
+    import test_train_parity_mask_gpu as masked
+    import test_train_parity_transposed_gpu as transposed
+    for sibling in (masked, transposed):      # the masked and the transposed cases go through the same runner and define no check
+        assert sibling.run_case is gpu.run_case and sibling.case is gpu.case
+        text = open(sibling.__file__).read()
+        assert not any(own in text for own in ("MARGIN", "margin=", "def bounds", "def compare", "compare(")), sibling.__name__
 
 
 def test_needles_cover_the_geometry():
@@ -298,6 +404,50 @@ def test_needles_cover_the_geometry():
     assert max(len(w) for w, _f in info.values()) <= tm.CAPACITY
 
 
+@pytest.mark.parametrize("causal", [False, True], ids=["dense", "causal"])
+def test_needles_cover_the_geometry_of_a_mask(causal):
+    """under a block mask, over a grid of four heads, with no (row block, run edge) pair left out: every run of active column blocks of
+    every row block has its first and its last key as a needle of a row of that row block, and, where an inactive block lies before /
+    behind it, that block's last / first key as a trap of a row of that row block; every first and last row of a 256-row block holds,
+    in every head, a needle in a column block that is active for its row block and inactive for the adjacent one, and a trap in a block
+    with the opposite pattern; needles are keys the row sees, traps keys it does not see; dead rows hold traps only."""
+    R, C, D, H = 513, 1030, 64, 4
+    bits = tm.needle_mask(R, C, 7, causal=causal)
+    _q, _k, _v, _dO, info = tm.needle_inputs(1, H, R, C, D, "bf16", causal=causal, block_mask=bits)
+    vis = tm.mask_views(bits, 0, 0, R, C, R, C, causal)[0]
+    block = lambda t: t // tm.MASK_COLUMNS    # noqa: E731
+    for (b, h, r), (needles, traps) in info.items():
+        assert all(vis[r, t] for t in needles) and not any(vis[r, t] for t in traps), (h, r, needles, traps)
+        assert len(needles) <= tm.CAPACITY and (len(needles) >= 2 or vis[r].sum() < 2), (h, r, needles)
+    nrb = bits.shape[0]
+    pairs = 0
+    for i in range(nrb):
+        rows = range(i * tm.BLOCK_ROWS, min((i + 1) * tm.BLOCK_ROWS, R))
+        held = {t for h in range(H) for r in rows for t in info[(0, h, r)][0]}
+        trapped = {t for h in range(H) for r in rows for t in info[(0, h, r)][1]}
+        for s, e in tm.mask_runs(bits[i]):
+            first, last = s * tm.MASK_COLUMNS, min((e + 1) * tm.MASK_COLUMNS, C) - 1
+            reach = rows[-1] + C - R if causal else C - 1                           # the frontier of the row block's last row
+            for key, hidden in ((first, first - 1 if s > 0 else None), (last, last + 1 if last + 1 < C else None)):
+                if key > reach:
+                    continue          # causal: no row of the row block sees as far
+                pairs += 1
+                assert key in held, ("no needle on the visible side", i, (s, e), key)
+                if hidden is not None and hidden <= reach:
+                    assert hidden in trapped, ("no trap on the hidden side", i, (s, e), hidden)
+        for r, j in ((rows[0], i - 1), (rows[-1], i + 1)):
+            if not 0 <= j < nrb:
+                continue
+            for h in range(H):
+                needles, traps = info[(0, h, r)]
+                seen = [c for c in range(bits.shape[1]) if vis[r, c * tm.MASK_COLUMNS]]
+                if any(bits[i, c] and not bits[j, c] for c in seen):
+                    assert any(bits[i, block(t)] and not bits[j, block(t)] for t in needles), ("no needle the adjacent row block must not see", h, r)
+                if any(bits[j, c] and not bits[i, c] and c * tm.MASK_COLUMNS <= r + (C - R if causal else C) for c in range(bits.shape[1])):
+                    assert any(bits[j, block(t)] and not bits[i, block(t)] for t in traps), ("no trap in a block of the adjacent row block", h, r)
+    assert pairs >= 2 * nrb
+
+
 if __name__ == "__main__":
     import __graft_entry__ as entry
     entry.build()
@@ -314,4 +464,17 @@ if __name__ == "__main__":
                 worst = max((n for n in tm.OUTPUTS), key=lambda n: seen[2][n] / tm.OLD_TOL[n])
                 what = "caught" if seen[0] else "tighter constants only" if seen[1] else "**missed**"
                 cells.append("%s (%s %.2g)" % (what, worst, seen[2][worst]))
+        print("| %s | %s |" % (mutant, " | ".join(cells)))
+    print()
+    print("| mask mutant | " + " | ".join("%s %s%s" % (s, "causal" if c else "dense", ", empty last row block" if e else "") for s, c, e in OLD_MASK_SHAPES) + " |")
+    print("|---|" + "---|" * len(OLD_MASK_SHAPES))
+    for mutant in tm.MASK_MUTANTS:
+        cells = []
+        for shape, causal, empty in OLD_MASK_SHAPES:
+            seen = old_mask_check_sees(shape, causal, empty, mutant)
+            if seen is None:
+                cells.append("-")
+                continue
+            worst = max((n for n in tm.OUTPUTS), key=lambda n: (seen[1][n] if np.isfinite(seen[1][n]) else 1e30) / OLD_MASK_TOL[n])
+            cells.append("%s (%s %.2g)" % ("caught" if seen[0] else "**missed**", worst, seen[1][worst]))
         print("| %s | %s |" % (mutant, " | ".join(cells)))
