@@ -89,6 +89,13 @@ const char *mfa_gemm_kernel_variant(const mfa_gemm_kernel *kernel);
  * if a leading dimension is smaller than the row it must hold ("Leading block dimension was too small."). */
 mfa_status mfa_gemm_kernel_launch(const mfa_gemm_kernel *kernel, const void *A, const void *B, void *C,
                                   const mfa_gemm_launch_params *params, void *stream);
+/* Name of the code object mfa_gemm_kernel_launch would run for exactly these arguments: the decision depends on
+ * K, the leading dimensions, the batch strides and the alignment of A and B, not on the kernel alone (e.g.
+ * "gemm_f32mfma_128x128x16_w2x2", "gemm_16_bf16_256x256x64_w2x4_dma_akm_bxm": type, block, LDS-DMA staging,
+ * k-major / x-major image of A and of B).  Launches nothing and reads no buffer.  "" with the last error set
+ * where the launch would be refused.  The string lives as long as the library. */
+const char *mfa_gemm_kernel_launch_form(const mfa_gemm_kernel *kernel, const void *A, const void *B, const void *C,
+                                        const mfa_gemm_launch_params *params);
 /* `iterations` back-to-back launches between two HIP events on `stream` (LaplacianTest.swift:181-228) */
 mfa_status mfa_gemm_kernel_time(const mfa_gemm_kernel *kernel, const void *A, const void *B, void *C,
                                 const mfa_gemm_launch_params *params, void *stream, int warmup, int iterations,

@@ -155,6 +155,8 @@ GEMM_SYMBOLS = [
     ("mfa_gemm_kernel_variant", ctypes.c_char_p, [_GEMM]),
     ("mfa_gemm_kernel_launch", ctypes.c_int,
      [_GEMM, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(mfa_gemm_launch_params), ctypes.c_void_p]),
+    ("mfa_gemm_kernel_launch_form", ctypes.c_char_p,
+     [_GEMM, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(mfa_gemm_launch_params)]),
     ("mfa_gemm_kernel_time", ctypes.c_int,
      [_GEMM, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(mfa_gemm_launch_params), ctypes.c_void_p,
       ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),

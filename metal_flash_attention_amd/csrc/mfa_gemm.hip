@@ -123,8 +123,17 @@ extern "C" uint32_t mfa_gemm_kernel_threadgroup_memory_allocation(const mfa_gemm
 }
 extern "C" const char *mfa_gemm_kernel_variant(const mfa_gemm_kernel *k) { return k ? k->name.c_str() : ""; }
 
-static mfa_status prepare(const mfa_gemm_kernel *k, const void *A, const void *B, void *C, const mfa_gemm_launch_params *p,
-                          GemmArgs *g, dim3 *grid, bool *use16) {
+// which code object a launch runs: decided once, in prepare, for launch, timing and mfa_gemm_kernel_launch_form
+enum GemmForm { FORM_F32 = 0, FORM_16_SMALL, FORM_16_BIG, FORM_16_BIG_DMA };
+
+struct GemmLaunch {
+  GemmArgs g;
+  dim3 grid;
+  GemmForm form;
+};
+
+static mfa_status prepare(const mfa_gemm_kernel *k, const void *A, const void *B, const void *C, const mfa_gemm_launch_params *p,
+                          GemmLaunch *out) {
   if (!k || !p) return fail(MFA_ERR_INVALID_ARGUMENT, "null pointer");
   if (p->M == 0 || p->N == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "matrix dimensions must be positive");
   if (!A || !B || !C) return fail(MFA_ERR_INVALID_ARGUMENT, "null operand buffer");
@@ -136,12 +145,25 @@ static mfa_status prepare(const mfa_gemm_kernel *k, const void *A, const void *B
   const uint32_t ldC = p->leadingDimensionC ? p->leadingDimensionC : expC;
   if (ldA < expA || ldB < expB || ldC < expC) return fail(MFA_ERR_INVALID_ARGUMENT, "Leading block dimension was too small.");
   const uint32_t batch = p->batchDimension ? p->batchDimension : 1;
-  *g = GemmArgs{A, B, C, p->M, p->N, p->K, ldA, ldB, ldC, k->desc.memoryPrecisionA, k->desc.memoryPrecisionB,
-                k->desc.memoryPrecisionC, tA, tB, p->loadPreviousC ? 1 : 0, p->batchStrideA, p->batchStrideB, p->batchStrideC};
-  *grid = dim3((p->N + GEMM_BN - 1) / GEMM_BN, (p->M + GEMM_BM - 1) / GEMM_BM, batch);   // general / small block
-  // 32-bit byte offsets must cover the operands (buffer addressing); alignment is not required
+  GemmArgs &g = out->g;
+  g = GemmArgs{A, B, const_cast<void *>(C), p->M, p->N, p->K, ldA, ldB, ldC, k->desc.memoryPrecisionA, k->desc.memoryPrecisionB,
+               k->desc.memoryPrecisionC, tA, tB, p->loadPreviousC ? 1 : 0, p->batchStrideA, p->batchStrideB, p->batchStrideC};
+  // 32-bit byte offsets must cover the operands (buffer addressing); alignment is not required.  Larger operands
+  // take the general kernel, whose offsets are 64-bit.
   const uint64_t bytesA = (uint64_t)(tA ? p->K : p->M) * ldA * 2, bytesB = (uint64_t)(tB ? p->N : p->K) * ldB * 2;
-  *use16 = k->fast16 && bytesA < 0xFFFFFF00ull && bytesB < 0xFFFFFF00ull;
+  const bool use16 = k->fast16 && bytesA < 0xFFFFFF00ull && bytesB < 0xFFFFFF00ull;
+  // LDS-DMA staging for launches made of whole, 16-byte aligned chunks (MFA_GEMM_IMPL=vgpr: developer knob that
+  // forces the register-staged kernel, which also serves every other launch)
+#ifdef MFA_DEV_VARIANTS
+  static const bool dmaKnob = !(std::getenv("MFA_GEMM_IMPL") && std::strcmp(std::getenv("MFA_GEMM_IMPL"), "vgpr") == 0);
+#else
+  constexpr bool dmaKnob = true;
+#endif
+  const bool aligned = (g.K & 7) == 0 && (g.ldA & 7) == 0 && (g.ldB & 7) == 0 && (g.bsA & 7) == 0 && (g.bsB & 7) == 0 &&
+                       ((uintptr_t)g.A & 15) == 0 && ((uintptr_t)g.B & 15) == 0;
+  out->form = !use16 ? FORM_F32 : !k->big ? FORM_16_SMALL : (dmaKnob && aligned) ? FORM_16_BIG_DMA : FORM_16_BIG;
+  const uint32_t bm = out->form >= FORM_16_BIG ? 256 : GEMM_BM, bn = out->form >= FORM_16_BIG ? 256 : GEMM_BN;
+  out->grid = dim3((p->N + bn - 1) / bn, (p->M + bm - 1) / bm, batch);
   return MFA_OK;
 }
 
@@ -152,22 +174,13 @@ template <typename K> static hipError_t enable_lds(K kernel, int bytes) {
 }
 
 template <typename T, bool AKM, bool BKM>
-static hipError_t launch16(bool big, const GemmArgs &g, dim3 grid, hipStream_t s) {
+static hipError_t launch16(GemmForm form, const GemmArgs &g, dim3 grid, hipStream_t s) {
   hipError_t e;
-  // LDS-DMA staging for launches made of whole, 16-byte aligned chunks (MFA_GEMM_IMPL=vgpr: developer knob that
-  // forces the register-staged kernel, which also serves every other launch)
-#ifdef MFA_DEV_VARIANTS
-  static const bool dmaKnob = !(std::getenv("MFA_GEMM_IMPL") && std::strcmp(std::getenv("MFA_GEMM_IMPL"), "vgpr") == 0);
-#else
-  constexpr bool dmaKnob = true;
-#endif
-  const bool aligned = (g.K & 7) == 0 && (g.ldA & 7) == 0 && (g.ldB & 7) == 0 && (g.bsA & 7) == 0 && (g.bsB & 7) == 0 &&
-                       ((uintptr_t)g.A & 15) == 0 && ((uintptr_t)g.B & 15) == 0;
-  if (big && dmaKnob && aligned) {
+  if (form == FORM_16_BIG_DMA) {
     constexpr int LDS = gemm16_lds_bytes<2, 4, 4, 2>();
     e = enable_lds(gemm_16<T, 2, 4, 4, 2, AKM, BKM, true>, LDS);
     if (e == hipSuccess) hipLaunchKernelGGL((gemm_16<T, 2, 4, 4, 2, AKM, BKM, true>), grid, dim3(512), LDS, s, g);
-  } else if (big) {
+  } else if (form == FORM_16_BIG) {
     constexpr int LDS = gemm16_lds_bytes<2, 4, 4, 2>();
     e = enable_lds(gemm_16<T, 2, 4, 4, 2, AKM, BKM>, LDS);
     if (e == hipSuccess) hipLaunchKernelGGL((gemm_16<T, 2, 4, 4, 2, AKM, BKM>), grid, dim3(512), LDS, s, g);
@@ -181,29 +194,52 @@ static hipError_t launch16(bool big, const GemmArgs &g, dim3 grid, hipStream_t s
 
 // image kinds of the two operands: k-major rows when the memory order has k contiguous (A not transposed, B transposed)
 template <typename T>
-static hipError_t launch16_images(bool big, bool akm, bool bkm, const GemmArgs &g, dim3 grid, hipStream_t s) {
-  if (akm) return bkm ? launch16<T, true, true>(big, g, grid, s) : launch16<T, true, false>(big, g, grid, s);
-  return bkm ? launch16<T, false, true>(big, g, grid, s) : launch16<T, false, false>(big, g, grid, s);
+static hipError_t launch16_images(GemmForm form, bool akm, bool bkm, const GemmArgs &g, dim3 grid, hipStream_t s) {
+  if (akm) return bkm ? launch16<T, true, true>(form, g, grid, s) : launch16<T, true, false>(form, g, grid, s);
+  return bkm ? launch16<T, false, true>(form, g, grid, s) : launch16<T, false, false>(form, g, grid, s);
 }
 
-static hipError_t launch_one(const mfa_gemm_kernel *k, const GemmArgs &g, dim3 grid, bool use16, hipStream_t s) {
-  if (!use16) {
-    hipLaunchKernelGGL(gemm_f32mfma, grid, dim3(256), 0, s, g);
+static hipError_t launch_one(const GemmLaunch &l, hipStream_t s) {
+  const GemmArgs &g = l.g;
+  if (l.form == FORM_F32) {
+    hipLaunchKernelGGL(gemm_f32mfma, l.grid, dim3(256), 0, s, g);
     return hipSuccess;
   }
-  const dim3 gb((g.N + 255) / 256, (g.M + 255) / 256, grid.z);
-  return (g.precA == PREC_BF16) ? launch16_images<__bf16>(k->big, !g.transA, g.transB, g, k->big ? gb : grid, s)
-                                : launch16_images<_Float16>(k->big, !g.transA, g.transB, g, k->big ? gb : grid, s);
+  return (g.precA == PREC_BF16) ? launch16_images<__bf16>(l.form, !g.transA, g.transB, g, l.grid, s)
+                                : launch16_images<_Float16>(l.form, !g.transA, g.transB, g, l.grid, s);
+}
+
+// name of the code object launch_one runs for `l`: the general kernel, or gemm_16 by type, form and image pair
+static const char *form_name(const GemmLaunch &l) {
+  struct Names {
+    std::string n[2][3][2][2];
+    Names() {
+      const char *const forms[3] = {"128x128x64_w2x2", "256x256x64_w2x4", "256x256x64_w2x4_dma"};
+      for (int t = 0; t < 2; ++t)
+        for (int f = 0; f < 3; ++f)
+          for (int a = 0; a < 2; ++a)
+            for (int b = 0; b < 2; ++b)
+              n[t][f][a][b] = std::string("gemm_16_") + (t ? "bf16_" : "f16_") + forms[f] + (a ? "_akm" : "_axm") + (b ? "_bkm" : "_bxm");
+    }
+  };
+  static const Names names;
+  if (l.form == FORM_F32) return "gemm_f32mfma_128x128x16_w2x2";
+  return names.n[l.g.precA == PREC_BF16][l.form - FORM_16_SMALL][!l.g.transA][l.g.transB ? 1 : 0].c_str();
+}
+
+extern "C" const char *mfa_gemm_kernel_launch_form(const mfa_gemm_kernel *k, const void *A, const void *B, const void *C,
+                                                   const mfa_gemm_launch_params *p) {
+  GemmLaunch l;
+  if (prepare(k, A, B, C, p, &l) != MFA_OK) return "";
+  return form_name(l);
 }
 
 extern "C" mfa_status mfa_gemm_kernel_launch(const mfa_gemm_kernel *k, const void *A, const void *B, void *C,
                                              const mfa_gemm_launch_params *p, void *stream) {
-  GemmArgs g;
-  dim3 grid;
-  bool use16;
-  const mfa_status st = prepare(k, A, B, C, p, &g, &grid, &use16);
+  GemmLaunch l;
+  const mfa_status st = prepare(k, A, B, C, p, &l);
   if (st != MFA_OK) return st;
-  hipError_t e = launch_one(k, g, grid, use16, (hipStream_t)stream);
+  hipError_t e = launch_one(l, (hipStream_t)stream);
   if (e == hipSuccess) e = hipGetLastError();
   if (e != hipSuccess) return fail(MFA_ERR_HIP, std::string("gemm launch: ") + hipGetErrorString(e));
   return MFA_OK;
@@ -212,17 +248,15 @@ extern "C" mfa_status mfa_gemm_kernel_launch(const mfa_gemm_kernel *k, const voi
 extern "C" mfa_status mfa_gemm_kernel_time(const mfa_gemm_kernel *k, const void *A, const void *B, void *C,
                                            const mfa_gemm_launch_params *p, void *stream, int warmup, int iterations, float *ms) {
   if (!ms || iterations <= 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
-  GemmArgs g;
-  dim3 grid;
-  bool use16;
-  const mfa_status st = prepare(k, A, B, C, p, &g, &grid, &use16);
+  GemmLaunch l;
+  const mfa_status st = prepare(k, A, B, C, p, &l);
   if (st != MFA_OK) return st;
   hipStream_t s = (hipStream_t)stream;
   hipEvent_t e0, e1;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(MFA_ERR_HIP, "hipEventCreate failed");
-  for (int i = 0; i < warmup; ++i) (void)launch_one(k, g, grid, use16, s);
+  for (int i = 0; i < warmup; ++i) (void)launch_one(l, s);
   (void)hipEventRecord(e0, s);
-  for (int i = 0; i < iterations; ++i) (void)launch_one(k, g, grid, use16, s);
+  for (int i = 0; i < iterations; ++i) (void)launch_one(l, s);
   (void)hipEventRecord(e1, s);
   hipError_t e = hipEventSynchronize(e1);
   if (e == hipSuccess) e = hipEventElapsedTime(ms, e0, e1);

@@ -134,6 +134,15 @@ class GEMMKernel:
         check(lib().mfa_gemm_kernel_launch(self._handle, _device_pointer(A), _device_pointer(B), _device_pointer(C),
                                            ctypes.byref(p), ctypes.c_void_p(stream or 0)))
 
+    def launch_form(self, A, B, C, *, descriptor: GEMMDescriptor, batchStrides=None) -> str:
+        """Name of the code object `dispatch` would run for exactly these arguments (launches nothing)."""
+        p = self._params(descriptor, batchStrides)
+        form = lib().mfa_gemm_kernel_launch_form(self._handle, _device_pointer(A), _device_pointer(B), _device_pointer(C),
+                                                 ctypes.byref(p)).decode()
+        if not form:
+            raise _abi.MFAError(2, lib().mfa_last_error_string().decode())
+        return form
+
     def time(self, A, B, C, *, descriptor: GEMMDescriptor, batchStrides=None, stream: Optional[int] = None,
              warmup: int = 1, iterations: int = 20) -> float:
         p = self._params(descriptor, batchStrides)
