@@ -12,6 +12,8 @@ inputs and the named mutants (a plain module, as tests/decode_model.py, whose ro
                     dK / dV, L hugely negative (include/mfa.h; the model says -inf, compare() asks for < -1e30 and for exact zeros).
                     The bound needs no new term: every sum runs over the visible (i, j) with the model's p, and the FP32 chain
                     keeps C / 8, an upper bound on the matrix instructions of the blocks that are run.
+                    out= (the type O, dQ, dK, dV are stored in), dO_fmt= / dO_path= (the FP16 + BF16-dO mix), heads_per_kv= (K, V,
+                    dK, dV of H / G heads): the launch forms of the torch binding, derived at the end of the bound below.
   bounds()          per-element bounds on all six outputs (derivation below).
   emulated()        the same computation with the kernels' roundings and summation orders: what a correct kernel may give.
   needle_inputs()   Q, K, V and dO in which individual keys and individual rows matter; under a mask the needles are keys the row
@@ -69,9 +71,38 @@ T_ij = scale sum_d |q_id k_jd|.  Every term is a worst case and errors add up li
   attn_dkv16rs_f16_d256 left dK elements of 1.5e-6 at 1.1 times a bound that had the floor on dS itself.
   bound_X = margin (E_X + U_OUT[out] |X|) + tiny,   tiny = 2^-24.
 
+The launch forms of the torch binding (out=, dO_fmt= / dO_path=, heads_per_kv=; FORM_MUTANTS are their named defects).
+  16-bit outputs (out = "bf16" | "f16": lowPrecisionOutputs).  backwardQuery reads the O the forward STORED (attn_dq16_p4.h `o32`,
+  attn_dq16_p5.h, attn_bwd16.h): D~_i = sum_d dO_id st(O~_id), O~ the computed O (|O~ - O| <= E_O) and st its rounding to `out`.
+  st(x) - x = -delta x with 0 <= delta < 2^-7 where the BF16 store truncates (one sign per element: every product moves towards 0), and
+  |delta| <= 2^-8 (BF16) or 2^-11 (FP16) where it rounds to nearest (STORE_ROUNDING: the hand-placed persistent forwards do, every other
+  store truncates).  With x_d = dO_id O_id, pos = sum of the positive x_d, neg = sum of the |negative x_d|:
+    truncation  D~ - D = -sum_d delta_d x_d lies in [-2^-7 pos, +2^-7 neg]:  at most 2^-7 max(pos, neg);
+    nearest     at most 2^-8 (pos + neg) <= 2^-7 max(pos, neg): the one term covers both roundings with decode_model.U_OUT;
+    where O~_id and O_id differ in sign |O~_id| <= E_O_id, and elsewhere |O~_id| <= |O_id| + E_O_id:  U_OUT sum_d |dO_id| E_O_id more;
+    FP16: no sign rule, U_OUT (pos + neg), and FP16's subnormal floor 2^-25 sum_d |dO_id| for elements of O below 2^-14.
+    E_D += U_OUT[out] (max(pos, neg) [bf16] or pos + neg [f16]) + U_OUT[out] sum_d |dO_id| E_O_id + [f16] 2^-25 sum_d |dO_id|
+  in place of the 2^-23 sum_d |dO_id O_id| of an FP32 O.  It reaches e_dS, E_dQ and E_dK through E_D as every other term of it does.
+  On the needle inputs (bf16 mixed, (255, 257, 64) causal and (300, 333, 128)) E_D grows 2.1 to 2.6 fold, a truncating store moves D
+  by at most 0.46 to 0.70 of the new term, "D wrong by 2^-4" falls from 3.2 - 3.7 to 1.3 - 1.7 times the bound and stays flagged.
+  The FP16 + BF16-dO mix (fmt = "f16", dO_fmt = "bf16": the reference's memoryPrecisions).  Every backwardQuery kernel, and the
+  backwardKeyValue kernels of MIX_PATH's "convert_dO" rows, convert dO to FP16 element by element through `(T)(float)`
+  (attn_bwd16.h convert_chunk).  BF16's 8 significant bits fit FP16's 11: the conversion is exact down to 2^-14; below, the result is
+  an FP16 subnormal, a multiple of 2^-24: an absolute error of at most 2^-25 per element (above 65504 it is infinite: out of the
+  contract).  Charged wherever dO enters a product:
+    convert_dO     e_dP_ij += 2^-25 sum_d |v_jd|,   E_D_i += 2^-25 sum_d |O_id|,   E_dV_jd += 2^-25 sum_i p_ij
+  "bf16_products" (the mix streams of attn_dkv16_p4 / _p5: attn_dkv16_p4.h `stream_mix`): backwardKeyValue reads dO as stored and runs
+  its two products in BF16 -- V converted to BF16 once (half an ulp: 2^-8 relative on every product of dP), P packed to BF16 for
+  dV (u = 2^-8 in E_dV in place of 2^-11); S, dS and dK keep FP16's u.  D and dQ come from backwardQuery, which converts:
+    bf16_products  e_dP_ij (dK side) += 2^-8 sum_d |dO_id v_jd|,   E_dV: u -> 2^-8,   E_D and E_dQ as under convert_dO
+  Two variants, never their maximum: the union would loosen dV eightfold on the families that convert.
+  Grouped K / V heads (heads_per_kv = G; K, V [B, H / G, C, D], query head h reads head h // G).  backwardKeyValue leaves every query
+  head's FP32 dK / dV in a slab; attn_kv_group_sum adds the G slabs of a group in the order g = 0 .. G - 1 in FP32 and stores once:
+    E_dV (group) = sum_g E_dV (member g) + G u32 sum_g A_dV (member g)        (dK alike); the store term U_OUT |dV| once, on the sum.
+
 MARGIN is the smallest power of two, at most 4, with at least 2 x headroom over the worst err / bound at margin 1 of emulated() on
-every case of tests/test_train_sensitivity.py and of the kernels on every case of tests/test_train_parity_gpu.py (DESIGN.md 4.18
-records both maxima).
+every case of tests/test_train_sensitivity.py and of the kernels on every case of tests/test_train_parity_gpu.py and of the files
+that run their cases through it (DESIGN.md 4.18 records both maxima).
 """
 import math
 from typing import NamedTuple
@@ -165,6 +196,27 @@ MUTANTS = {
     "bwd_combine_drops_slab": ("attn_bwd_combine drops the second piece's slab", _no_split),
     "bwd_combine_adds_slab_twice": ("attn_bwd_combine adds the second piece's slab twice", _no_split),
 }
+# the launch forms of the torch binding (16-bit outputs, the FP16 + BF16-dO mix, grouped K / V heads).  `case` also has out ("f32" |
+# "bf16" | "f16"), mix (dO_fmt differs from fmt), small_dO (a block of dO rows scaled by 2^-12) and G (heads_per_kv)
+_out32 = lambda c: c.get("out", "f32") == "f32"      # noqa: E731
+_no_mix = lambda c: not c.get("mix")                 # noqa: E731
+_no_group = lambda c: c.get("G", 1) == 1             # noqa: E731
+FORM_MUTANTS = {
+    "d_from_unstored_o_next_head": ("16-bit outputs: D formed from the O of head h + 1", lambda c: _out32(c) or c["H"] == 1),
+    "o16_row_pairs_exchanged": ("16-bit outputs: rows 0 and 1 exchanged in the O store only (D from the right rows)", lambda c: _out32(c) or c["R"] < 2),
+    "out16_last_chunk_dropped": ("16-bit outputs: the last 8 elements of row 0 of O, dQ and dK keep the sentinel", _out32),
+    "out16_piece_rounded_before_combine": ("16-bit outputs under a split plan: every piece's partial rounded to 16 bits before the sum",
+                                           lambda c: _out32(c) or not c["pieces"]),
+    "dO_bits_as_input_type": ("the mix: dO's BF16 bits read as FP16", _no_mix),
+    "dO_small_flushed": ("the mix: dO elements below 2^-14 read as zero (the code converts them to FP16 subnormals)",
+                         lambda c: _no_mix(c) or not c.get("small_dO")),
+    "dO_converted_in_dv_only": ("the mix: backwardKeyValue's dP reads dO's unconverted bits", _no_mix),
+    "group_slab_dropped": ("attn_kv_group_sum without the slab of the group's second member", _no_group),
+    "group_slab_twice": ("attn_kv_group_sum adds the slab of the group's second member twice", _no_group),
+    "group_sum_head_is_query_head": ("query head h's slab added to K / V head h instead of h // G", _no_group),
+    "group_store_rounds_each_slab": ("16-bit outputs: every slab of a group rounded to 16 bits before the sum", lambda c: _no_group(c) or _out32(c)),
+}
+MUTANTS.update(FORM_MUTANTS)
 # block-mask mutants: each misreads the mask (mask_views); "changes nothing" where the misread visibility of every live row equals the
 # true one, which follows from the case's mask, its words, whether it is shared, causal and the lengths -- never from a result
 MASK_MUTANTS = {
@@ -423,24 +475,81 @@ def _softmax(S, vis, mult=None):
     return pw / l0, m0[:, 0], l0[:, 0]
 
 
+DO_PATHS = ("convert_dO", "bf16_products")             # how a backwardKeyValue kernel of the FP16 + BF16-dO mix reads dO (docstring)
+# backwardKeyValue variant prefix -> its path in the mix, with the source line it was read from (the first matching prefix holds).
+# Every backwardQuery kernel converts (attn_dq16_p4.h:148, attn_dq16_p5.h:189, attn_bwd16.h:114 `convert_chunk<T, TG>`).
+MIX_PATH = (
+    ("attn_dkv16p4", "bf16_products"),    # attn_dkv16_p4.h:129 `if constexpr (stream_mix(STREAM)) ... convert_chunk<__bf16, T>(vx)`, P packed by the stream
+    ("attn_dkv16p5", "bf16_products"),    # attn_dkv16_p5.h:142-144, the same conversion of V; first_is_bf16 (:210)
+    ("attn_dkv16rs", "convert_dO"),       # attn_dkv16_rs.h:176 `convert_chunk<T, TG>(greg[i])`
+    ("attn_dkv16w_", "convert_dO"),       # attn_dkv16_wide.h:121, the same line
+    ("attn_dkv16_", "convert_dO"),        # attn_bwd16.h:491, the same line (the one-wave kernel)
+)
+# the rounding of the 16-bit stores, per family: FP16 always rounds to nearest (`(_Float16)x`, `v_cvt_pk_f16_f32`); BF16:
+STORE_ROUNDING = (
+    ("attn_fwd16_p4p", "nearest"),        # tools/p4pgen.py:449 `v_cvt_pk_bf16_f32` under cfg.o16 (the hand-placed persistent streams)
+    ("attn_fwd16_p6", "nearest"),         # tools/p6gen.py:612, the same instruction under cfg.o16
+    ("", "trunc"),                        # every other store: attn_fwd16_common.h:32 pack16 (store_block_rows; attn_fwd16_v3.h:877, attn_fwd16_wide.h:338),
+)                                         # attn_common.h:71 f32_to_bf16_trunc (store_elem: the combine kernels; attn_kv_group_sum.hip:74)
+
+
+U_BF16 = U_P["bf16"]
+SMALL_DO = 2.0 ** -14                                 # FP16's smallest normal number
+
+
+def mix_path(variant):
+    return next(path for prefix, path in MIX_PATH if variant.startswith(prefix))
+
+
+def store_rounding(form):
+    """the BF16 rounding of the store of a launch whose form (launchForm) is `form`: STORE_ROUNDING's first matching prefix"""
+    return next(rounding for prefix, rounding in STORE_ROUNDING if form.startswith(prefix))
+
+
+def off_grid_grad(dO):
+    """BF16 values -> FP16 values three quarters of a BF16 ulp further from zero (six FP16 ulps: exact above 2^-14): round-to-nearest
+    takes every element one BF16 ulp up in magnitude, truncation gives dO back -- a grad_out on which the two roundings differ everywhere"""
+    _m, e = np.frexp(dO)                              # |dO| = m 2^e, m in [0.5, 1): the BF16 ulp is 2^(e - 8)
+    grad = dO + np.sign(dO) * 0.75 * np.exp2(e - 8.0)
+    assert np.array_equal(round_to(grad, "f16"), grad) and (np.abs(dO) >= SMALL_DO).all() and (dO != 0).all()
+    return grad
+
+
+def _bits_as_f16(x):
+    """BF16 values -> the FP16 values of the same 16 bits"""
+    bits = (np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) >> np.uint32(16)).astype(np.uint16)
+    with np.errstate(all="ignore"):
+        return bits.view(np.float16).astype(np.float64)
+
+
 def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, pieces=None, block_mask=None, mutant=None, fmt="bf16", mixed=True,
-          with_bounds=True):
+          with_bounds=True, out="f32", dO_fmt=None, dO_path=None, heads_per_kv=1):
     """-> Reference (with_bounds=False: A, E and PK stay zero).  pieces: None or {"fwd": [(key begin, end)], "dq": [(key begin, end)], "dkv": [(row begin, end)]} (they change the
     bound's chain and what the mutants do, never the unmutated values).  A mutated run leaves NaN where its launch writes nothing."""
     assert mutant is None or mutant in MUTANTS, mutant
     q, k, v, dO = f64(q), f64(k), f64(v), f64(dO)
     B, H, R, Dh = q.shape
     C = k.shape[2]
+    Gq = int(heads_per_kv)
+    Hkv = H // Gq
+    assert H == Hkv * Gq and k.shape[1] == Hkv and v.shape[1] == Hkv, (q.shape, k.shape, Gq)
+    mix = dO_fmt is not None and dO_fmt != fmt
+    assert not mix or ((fmt, dO_fmt) == ("f16", "bf16") and dO_path in DO_PATHS), (fmt, dO_fmt, dO_path)
+    ofmt = out                                        # (`out` names the outputs below)
+    out16 = ofmt != "f32"
     scale = 1.0 / math.sqrt(Dh)
     u = U_P[fmt]
     fl = F16_FLOOR if fmt == "f16" else 0.0
+    cf = F16_FLOOR if mix else 0.0                    # dO converted to FP16: exact mantissa, FP16's subnormal floor
+    products = mix and dO_path == "bf16_products"     # backwardKeyValue: V and P rounded to BF16 for dP and dV
     rl, cl = _lengths(row_lengths, B, R), _lengths(key_lengths, B, C)
     rl_used = np.roll(rl, -1) if mutant == "row_length_next_batch" else rl
     pieces = pieces or {}
     npieces = max(len(pieces.get("fwd", ())), len(pieces.get("dq", ())), len(pieces.get("dkv", ())), 1)
     chain, chain_r = (C / 8 + npieces + 16) * U32, (R / 8 + npieces + 16) * U32
-    out = {n: np.full((B, H, R if n in ("O", "dQ") else C, Dh), np.nan) for n in ("O", "dV", "dK", "dQ")}
+    out = {n: np.full((B, H, R, Dh) if n in ("O", "dQ") else (B, Hkv, C, Dh), np.nan) for n in ("O", "dV", "dK", "dQ")}
     out["L"], out["D"] = np.full((B, H, R), np.nan), np.full((B, H, R), np.nan)
+    slabs = {}                                        # (b, h) -> a query head's dV, dK and their E and A: summed per group below
     A = {n: np.zeros_like(out[n]) for n in ("O", "dV", "dK", "dQ")}
     E = {n: np.zeros_like(out[n]) for n in OUTPUTS}
     PK = np.zeros((B, H, R, Dh))
@@ -451,7 +560,7 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
         rlen, clen = int(rl_used[b]), int(cl[b])
         for h in range(H):
             hk = (h + 1) % H if mutant == "row_block_next_head_kv" else h
-            K, V = k[b, h], v[b, h]
+            K, V = k[b, h // Gq], v[b, h // Gq]
             S = (q[b, h] @ K.T) * scale
             vis, visF, visQ, visK = mask_views(block_mask, b, h, R, C, rlen, clen, causal, mutant)
             md = True if block_mask is None else mask_dense(mask_bits(block_mask, b, h), R, C)
@@ -496,10 +605,10 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
             else:
                 L = np.where(unseeing, -np.inf, L)
             if mutant == "row_block_next_head_kv":     # rows of block 0 from head h + 1's K / V
-                S1 = (q[b, h] @ k[b, hk].T) * scale
+                S1 = (q[b, h] @ k[b, hk // Gq].T) * scale
                 P1, m1, l1 = _softmax(S1, visF)
                 blk = slice(0, BLOCK_ROWS)
-                O[blk], L[blk] = (P1 @ v[b, hk])[blk], (m1 + np.log(l1))[blk]
+                O[blk], L[blk] = (P1 @ v[b, hk // Gq])[blk], (m1 + np.log(l1))[blk]
             if mutant == "combine_ignores_maxima" and len(pieces.get("fwd", ())) > 1:
                 num, den = np.zeros((R, Dh)), np.zeros(R)
                 Sm = np.where(visF, S, -np.inf)
@@ -537,6 +646,8 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
                 O = np.concatenate([O[:, 32:64], O[:, :32], O[:, 64:]], axis=1)
             if mutant == "o_zero":
                 O = np.zeros_like(O)
+            if mutant == "out16_piece_rounded_before_combine" and out16 and len(pieces.get("fwd", ())) > 1:
+                O = sum(store(P[:, pb:min(pe, clen)] @ Vf[pb:min(pe, clen)], ofmt) for pb, pe in pieces["fwd"] if min(pe, clen) > pb)
             fwd[(b, h)] = (S, P, m, l, O, L, (dO[b, h] * O).sum(axis=1), vis, visQ, visK, md)
     for b in range(B):
         rlen, clen = int(rl_used[b]), int(cl[b])
@@ -545,7 +656,19 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
         for h in range(H):
             S, P0, m, l, O, L, Dv, vis, visQ, visK, md = fwd[(b, h)]
             dead_rows[b, h] = live_r & ~vis.any(axis=1)
-            K, V, Q, G = k[b, h], v[b, h], q[b, h], dO[b, h]
+            K, V, Q, G = k[b, h // Gq], v[b, h // Gq], q[b, h], dO[b, h]
+            Gk_all = G                                 # dO as backwardKeyValue's dP product reads it
+            if mix and mutant == "dO_bits_as_input_type":
+                G = Gk_all = _bits_as_f16(G)
+            elif mix and mutant == "dO_small_flushed":
+                G = Gk_all = np.where(np.abs(G) < SMALL_DO, 0.0, G)
+            elif mix and mutant == "dO_converted_in_dv_only":
+                Gk_all = _bits_as_f16(G)
+            if G is not dO[b, h]:
+                with np.errstate(all="ignore"):
+                    Dv = (G * O).sum(axis=1)
+            if mutant == "d_from_unstored_o_next_head" and out16:
+                Dv = (G * fwd[(b, (h + 1) % H)][4]).sum(axis=1)
             if mutant == "d_zero":
                 Dv = np.zeros(R)
             elif mutant == "d_wrong":
@@ -565,7 +688,8 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
                 Pb = np.where(visB, Pall, 0.0)
                 dP = G @ V.T
                 dS = Pb * (dP - Dv[:, None])
-                PbK, dSK = (Pb, dS) if visK is visB else (np.where(visK, Pall, 0.0), np.where(visK, Pall, 0.0) * (dP - Dv[:, None]))
+                dPk = dP if Gk_all is G else Gk_all @ V.T
+                PbK, dSK = (Pb, dS) if visK is visB and dPk is dP else (np.where(visK, Pall, 0.0), np.where(visK, Pall, 0.0) * (dPk - Dv[:, None]))
             # ---- dQ: rows below the row length, keys the pass reads
             Pq, dSq = Pb, dS
             if mutant in ("dq_last_tile_dropped", "dq_tile_skipped_in_one_row_block", "dq_reads_padding_keys"):
@@ -610,9 +734,22 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
                 dV, dK = dV + sign * sv, dK + sign * sk
             if mutant == "dk_dv_exchanged":
                 dV, dK = dK, dV
+            if mutant == "out16_piece_rounded_before_combine" and out16:
+                if len(pieces.get("dq", ())) > 1:
+                    dQ = sum(store(dq_scale * (dSq[:, pb:min(pe, clen)] @ K[pb:min(pe, clen)]), ofmt) for pb, pe in pieces["dq"] if min(pe, clen) > pb)
+                if len(pieces.get("dkv", ())) > 1:
+                    sel = [live_r & (np.arange(R) >= pb) & (np.arange(R) < pe) for pb, pe in pieces["dkv"]]
+                    dV = sum(store(PbK[x].T @ G[x], ofmt) for x in sel if x.any())
+                    dK = sum(store(dq_scale * (dSK[x].T @ Q[x]), ofmt) for x in sel if x.any())
             Dout = Dv
-            for name, val, live in (("O", O, live_r), ("L", L, live_r), ("D", Dout, live_r), ("dQ", dQ, live_r), ("dV", dV, live_c), ("dK", dK, live_c)):
+            Oout = O
+            if mutant == "o16_row_pairs_exchanged" and out16 and rlen >= 2:
+                Oout = np.concatenate([O[1:2], O[:1], O[2:]])
+            for name, val, live in (("O", Oout, live_r), ("L", L, live_r), ("D", Dout, live_r), ("dQ", dQ, live_r)):
                 out[name][b, h][live] = val[live]
+            if mutant == "out16_last_chunk_dropped" and out16:
+                out["O"][b, h, 0, -8:], out["dQ"][b, h, 0, -8:] = np.nan, np.nan
+            slabs[(b, h)] = [dV, dK, None, None, None, None, live_c]
             if not want_bounds:
                 continue
             # ---- the magnitude sums and the error terms (margin 1, without the stores)
@@ -630,6 +767,13 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
             AO = P @ aV
             absO = np.abs(np.where(live_r[:, None], O, 0.0))
             EO = u * AO + (u * absO if mixed else 0.0) + fl * (visl @ aV) + rp @ aV + absO * relp[:, None] + chain * (AO + absO)
+            GO = np.where(live_r[:, None], G * O, 0.0)
+            if ofmt == "f32":
+                stored = U_OUT["f32"] * np.abs(GO).sum(axis=1)
+            elif ofmt == "bf16":   # one sign per element: the positive and the negative products move D in opposite directions
+                stored = U_OUT[ofmt] * (np.maximum(np.maximum(GO, 0.0).sum(axis=1), np.maximum(-GO, 0.0).sum(axis=1)) + (aG * EO).sum(axis=1))
+            else:
+                stored = U_OUT[ofmt] * (np.abs(GO).sum(axis=1) + (aG * EO).sum(axis=1)) + F16_FLOOR * np.where(live_r, aG.sum(axis=1), 0.0)
             L = np.where(np.isfinite(L), L, 0.0)          # (a dead row: every term of its bounds is 0 but the constants)
             Lf = np.where(live_r, L, 0.0)
             EL = relp + (u if mixed else 0.0) + chain + 4 * U32 * (np.abs(m) + np.abs(np.log(l)) + np.abs(Lf)) + (2.0 ** -11 if mixed else 2.0 ** -23) * np.abs(Lf)
@@ -637,19 +781,43 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
             dP = np.where(live_r[:, None], dP, 0.0)
             dev = np.abs(dP - Df[:, None])
             ED = (P * (u * (dev if mixed else np.abs(dP)) + rho * dev)).sum(axis=1) + fl * (visl * np.abs(dP)).sum(axis=1) \
-                + chain * ((P * np.abs(dP)).sum(axis=1) + np.abs(Df)) + ((Dh + 2) * U32 + U_OUT["f32"]) * (aG * absO).sum(axis=1) \
-                + (2.0 ** -7 if mixed else 2.0 ** -23) * np.abs(Df)
+                + chain * ((P * np.abs(dP)).sum(axis=1) + np.abs(Df)) + (Dh + 2) * U32 * (aG * absO).sum(axis=1) + stored \
+                + cf * absO.sum(axis=1) + (2.0 ** -7 if mixed else 2.0 ** -23) * np.abs(Df)
             rhob = rho + EL[:, None]
             dSl = np.where(live_r[:, None], dS, 0.0)
             edP = (Dh + 3) * U32 * (aG @ aV.T)
-            eds = P * ((rhob + u) * dev + edP + ED[:, None]) + u * np.abs(dSl) + fl * visl * (dev + math.sqrt(Dh))
-            A["O"][b, h], A["dV"][b, h] = AO, P.T @ aG
-            A["dQ"][b, h], A["dK"][b, h] = scale * (np.abs(dSl) @ aK), scale * (np.abs(dSl).T @ aQ)
+            eds = P * ((rhob + u) * dev + edP + cf * aV.sum(axis=1)[None, :] + ED[:, None]) + u * np.abs(dSl) + fl * visl * (dev + math.sqrt(Dh))
+            # backwardKeyValue of the mix: dO converted as in backwardQuery, or (bf16_products) V rounded to BF16 and dO as stored
+            eds_k = eds + P * (U_BF16 * (aG @ aV.T) - cf * aV.sum(axis=1)[None, :]) if products else eds
+            u_dv = U_BF16 if products else u
+            A["O"][b, h] = AO
+            A["dQ"][b, h] = scale * (np.abs(dSl) @ aK)
             PK[b, h] = scale * (P @ aK)
             E["O"][b, h], E["L"][b, h], E["D"][b, h] = EO, EL, ED
-            E["dV"][b, h] = (P * (rhob + u) + fl * visl).T @ aG + chain_r * A["dV"][b, h]
+            AdV, AdK = P.T @ aG, scale * (np.abs(dSl).T @ aQ)
+            EdV = (P * (rhob + u_dv) + fl * visl).T @ aG + (0.0 if products else cf) * P.sum(axis=0)[:, None] + chain_r * AdV
             E["dQ"][b, h] = scale * (eds @ aK) + chain * A["dQ"][b, h]
-            E["dK"][b, h] = scale * (eds.T @ aQ) + chain_r * A["dK"][b, h]
+            slabs[(b, h)][2:6] = EdV, scale * (eds_k.T @ aQ) + chain_r * AdK, AdV, AdK
+    for b in range(B):            # dK / dV of K / V head j: the slabs of its G query heads, in the order g = 0 .. G - 1 (attn_kv_group_sum)
+        for j in range(Hkv):
+            members = [slabs[(b, j * Gq + g)] for g in range(Gq)]
+            if mutant == "group_slab_dropped" and Gq > 1:
+                members = members[:1] + members[2:]
+            elif mutant == "group_slab_twice" and Gq > 1:
+                members = members[:2] + members[1:]
+            elif mutant == "group_sum_head_is_query_head" and Gq > 1:
+                members = [slabs[(b, j)]]
+            each = (lambda x: store(x, ofmt)) if mutant == "group_store_rounds_each_slab" and out16 and Gq > 1 else (lambda x: x)
+            live = members[0][6]
+            out["dV"][b, j][live] = sum(each(m_[0]) for m_ in members)[live]
+            out["dK"][b, j][live] = sum(each(m_[1]) for m_ in members)[live]
+            if mutant == "out16_last_chunk_dropped" and out16:
+                out["dK"][b, j, 0, -8:] = np.nan
+            if want_bounds:
+                more = Gq * U32 if Gq > 1 else 0.0       # the group sum's FP32 additions, on the summed magnitudes
+                A["dV"][b, j], A["dK"][b, j] = sum(m_[4] for m_ in members), sum(m_[5] for m_ in members)
+                E["dV"][b, j] = sum(m_[2] for m_ in members) + more * A["dV"][b, j]
+                E["dK"][b, j] = sum(m_[3] for m_ in members) + more * A["dK"][b, j]
     row_live = np.arange(R)[None, :] < rl[:, None]
     key_live = np.arange(C)[None, :] < cl[:, None]
     return Reference(out["O"], out["L"], out["D"], out["dV"], out["dK"], out["dQ"], A, E, PK, row_live, key_live, dead_rows)
@@ -671,25 +839,37 @@ def _f32(x):
     return np.asarray(x, dtype=np.float32).astype(np.float64)
 
 
-def emulated(q, k, v, dO, fmt, mixed, *, causal=False, row_lengths=None, key_lengths=None, pieces=None, block_mask=None, out="f32"):
+def emulated(q, k, v, dO, fmt, mixed, *, causal=False, row_lengths=None, key_lengths=None, pieces=None, block_mask=None, out="f32",
+             o_rounding="trunc", dO_fmt=None, dO_path=None, heads_per_kv=1):
     """the model with the kernels' roundings and order of sums -> {output: array}, NaN where nothing is written: Q' (K' in
     backwardKeyValue) rounded once in the mixed mode, 64-key tiles under the deferred rescale, P and dS rounded to the 16-bit type,
-    l from the rounded P in the mixed mode, pieces merged, L in FP16 and D in truncated BF16 in the mixed mode, the stores"""
+    l from the rounded P in the mixed mode, pieces merged, L in FP16 and D in truncated BF16 in the mixed mode, the stores.
+    out: O, dQ, dK, dV are stored in that type and D is formed from the STORED O; o_rounding ("trunc" | "nearest"): the rounding of
+    the forward's BF16 O store (STORE_ROUNDING; FP16 always rounds to nearest, the gradients' BF16 stores always truncate).  dO_fmt /
+    dO_path: the FP16 + BF16-dO mix (model()).  heads_per_kv: the FP32 slabs of a group are added in the order g = 0 .. G - 1 and the sum is
+    stored once"""
     q, k, v, dO = f64(q), f64(k), f64(v), f64(dO)
     B, H, R, Dh = q.shape
     C = k.shape[2]
+    Gq = int(heads_per_kv)
+    mix = dO_fmt is not None and dO_fmt != fmt
+    assert not mix or dO_path in DO_PATHS
+    products = mix and dO_path == "bf16_products"
     scale = 1.0 / math.sqrt(Dh)
     s2c = float(np.float32(LOG2E * scale))
     rl, cl = _lengths(row_lengths, B, R), _lengths(key_lengths, B, C)
     pieces = pieces or {}
-    res = {n: np.full((B, H, R if n in ("O", "dQ") else C, Dh), np.nan) for n in ("O", "dV", "dK", "dQ")}
+    res = {n: np.full((B, H, R, Dh) if n in ("O", "dQ") else (B, H // Gq, C, Dh), np.nan) for n in ("O", "dV", "dK", "dQ")}
     res["L"], res["D"] = np.full((B, H, R), np.nan), np.full((B, H, R), np.nan)
     for b in range(B):
         rlen, clen = int(rl[b]), int(cl[b])
         for h in range(H):
             vis = mask_views(block_mask, b, h, R, C, rlen, clen, causal)[0][:rlen, :clen]
             dead = ~vis.any(axis=1)                       # (a dead row: no tile is run, l = 0; O = 0 and L hugely negative by rule)
-            Q, K, V, G = q[b, h, :rlen], k[b, h, :clen], v[b, h, :clen], dO[b, h, :rlen]
+            Q, K, V, G = q[b, h, :rlen], k[b, h // Gq, :clen], v[b, h // Gq, :clen], dO[b, h, :rlen]
+            if mix:                                       # (T)(float): attn_bwd16.h convert_chunk
+                G = round_to(G, fmt)
+            Gk, Vk, pfmt = (dO[b, h, :rlen], round_to(V, "bf16"), "bf16") if products else (G, V, fmt)
             if mixed:
                 S2q = _f32(round_to(Q * s2c, fmt) @ K.T)
                 S2k = _f32(Q @ round_to(K * s2c, fmt).T)
@@ -715,7 +895,7 @@ def emulated(q, k, v, dO, fmt, mixed, *, causal=False, row_lengths=None, key_len
             lt = sum(_f32(np.exp2(m_ - mstar)) * l_ for m_, l_, _o in parts)
             ot = sum(_f32(np.exp2(m_ - mstar))[:, None] * o_ for m_, _l, o_ in parts)
             lt = np.where(dead, 1.0, lt)
-            O = store(_f32(ot / lt[:, None]), out)
+            O = round_to(_f32(ot / lt[:, None]), out, trunc=out == "bf16" and o_rounding == "trunc")
             L2 = np.where(dead, -np.inf, _f32(mstar + np.log2(lt)))
             L2 = round_to(L2, "f16") if mixed else L2
             Dv = _f32((G * O).sum(axis=1))
@@ -725,14 +905,20 @@ def emulated(q, k, v, dO, fmt, mixed, *, causal=False, row_lengths=None, key_len
                 Pq = np.where(vis, _f32(np.exp2(S2q - L2[:, None])), 0.0)
                 Pk = np.where(vis, _f32(np.exp2(S2k - L2[:, None])), 0.0)
             dSq = round_to(round_to(Pq, fmt) * (dP - Dv[:, None]), fmt)
-            dSk = round_to(scale * round_to(Pk, fmt) * (dP - Dst[:, None]), fmt)      # dS' = scale dS: attn_dkv16_rs.h
+            dPk = _f32(Gk @ Vk.T) if products else dP
+            dSk = round_to(scale * round_to(Pk, fmt) * (dPk - Dst[:, None]), fmt)     # dS' = scale dS: attn_dkv16_rs.h
             dQ = sum(_f32(dSq[:, pb:pe] @ K[pb:pe]) for pb, pe in (pieces.get("dq") or [(0, clen)])) * scale
             rr = [(pb, min(pe, rlen)) for pb, pe in (pieces.get("dkv") or [(0, rlen)])]
-            dV = sum(_f32(round_to(Pk[pb:pe], fmt).T @ G[pb:pe]) for pb, pe in rr if pe > pb)
+            dV = sum(_f32(round_to(Pk[pb:pe], pfmt).T @ Gk[pb:pe]) for pb, pe in rr if pe > pb)
             dK = sum(_f32(dSk[pb:pe].T @ Q[pb:pe]) for pb, pe in rr if pe > pb)
             res["O"][b, h, :rlen], res["L"][b, h, :rlen], res["D"][b, h, :rlen] = O, L2 / LOG2E, Dst
             res["dQ"][b, h, :rlen] = store(_f32(dQ), out)
-            res["dV"][b, h, :clen], res["dK"][b, h, :clen] = store(_f32(dV), out), store(_f32(dK), out)
+            if h % Gq == 0:
+                sv, sk = _f32(dV), _f32(dK)
+            else:
+                sv, sk = _f32(sv + _f32(dV)), _f32(sk + _f32(dK))
+            if h % Gq == Gq - 1:
+                res["dV"][b, h // Gq, :clen], res["dK"][b, h // Gq, :clen] = store(sv, out), store(sk, out)
     return res
 
 
@@ -927,7 +1113,8 @@ def code_layout(C, Dh, h=0):
 SUPPRESSED = 9.0    # nats below the needles: the score of a key that shares one code half with no needle of the row (18: neither half)
 
 
-def needle_inputs(B, H, R, C, Dh, fmt, *, causal=False, row_lengths=None, key_lengths=None, pieces=None, block_mask=None, spike=False, seed=0):
+def needle_inputs(B, H, R, C, Dh, fmt, *, causal=False, row_lengths=None, key_lengths=None, pieces=None, block_mask=None, spike=False, seed=0,
+                  dO_fmt=None, small_dO_rows=None, heads_per_kv=1):
     """-> q, k, v, dO (float64 values of the 16-bit type, asserted exact) and info {(b, h, r): (needle keys, trap keys)}.
 
     The tension: in the mixed mode a score moves by u T_ij, T_ij = scale sum_d |q_d k_jd| >= |s_ij|, so a needle that stands
@@ -942,10 +1129,17 @@ def needle_inputs(B, H, R, C, Dh, fmt, *, causal=False, row_lengths=None, key_le
     needle in a block the row's mask hides is a trap by itself, the alias of a trap in a visible block a needle; the model stays the truth.  dP_ij - D_i = dO_i . (v_j - O_i) is of the order of |dO| sqrt(D) / 3 on every needle.
     spike: row 40 of every 64 keeps key 0 and its last visible key t* only and adds +9 sqrt(D) on the second
     code dimension of t*: t* scores +9, the keys of its code run (its neighbours, all late) 0: the late dominant key that fires the
-    deferred rescale.  Rows at and past the row length are built like live rows (a kernel that reads them moves dK / dV)."""
+    deferred rescale.  Rows at and past the row length are built like live rows (a kernel that reads them moves dK / dV).
+    dO_fmt (default fmt): the type dO is built in and must survive the cast to ("bf16" beside fmt = "f16": the reference's mix); in the
+    mix no dO element lies below 2^-14 in magnitude (FP16's smallest normal number) except in small_dO_rows (a slice of rows), whose dO
+    is scaled by 2^-12 as a whole -- Q, K, V and with them every needle stay as they are.  heads_per_kv = G: K and V are [B, H / G, C,
+    D], query head h reads head h // G and takes that head's code layout; the members of a group draw their needles with different
+    salts, so their needle keys differ."""
     rng = np.random.default_rng(seed)
-    k = round_to(rng.uniform(-1, 1, (B, H, C, Dh)), fmt)
-    v = round_to(rng.uniform(-1, 1, (B, H, C, Dh)), fmt)
+    Gq = int(heads_per_kv)
+    dO_fmt = dO_fmt or fmt
+    k = round_to(rng.uniform(-1, 1, (B, H // Gq, C, Dh)), fmt)
+    v = round_to(rng.uniform(-1, 1, (B, H // Gq, C, Dh)), fmt)
     dO = round_to(rng.uniform(-1, 1, (B, H, R, Dh)), fmt)
     q = np.zeros((B, H, R, Dh))
     rl, cl = _lengths(row_lengths, B, R), _lengths(key_lengths, B, C)
@@ -953,13 +1147,13 @@ def needle_inputs(B, H, R, C, Dh, fmt, *, causal=False, row_lengths=None, key_le
     gamma = float(round_to(np.array([SUPPRESSED * math.sqrt(Dh)]), fmt)[0])
     keys = np.arange(C)
     for h in range(H):
-        mA, mB, dims = code_layout(C, Dh, h)
+        mA, mB, dims = code_layout(C, Dh, h // Gq)
         free = dims[mA + mB:]
         ka, kb = keys % mA, (keys // mA) % mB
         for b in range(B):
-            k[b, h][:, dims[:mA + mB]] = 0.0
-            k[b, h, keys, dims[ka]] = 1.0
-            k[b, h, keys, dims[mA + kb]] = 1.0
+            k[b, h // Gq][:, dims[:mA + mB]] = 0.0
+            k[b, h // Gq, keys, dims[ka]] = 1.0
+            k[b, h // Gq, keys, dims[mA + kb]] = 1.0
             assert block_mask is None or not spike
             rows, traps = needle_plan(R, C, int(rl[b]), int(cl[b]), causal, pieces, b * H + h, spike,
                                       None if block_mask is None else mask_bits(block_mask, b, h))
@@ -985,12 +1179,16 @@ def needle_inputs(B, H, R, C, Dh, fmt, *, causal=False, row_lengths=None, key_le
     for b in range(B):          # dO = U(-1, 1) + 8 / D units along the row's O: D_i = dO_i . O_i is then about 1.4 + noise in every row
         for h in range(H):
             vis = mask_views(block_mask, b, h, R, C, int(rl[b]), int(cl[b]), causal)[0]
-            P, _m, _l = _softmax((q[b, h] @ k[b, h].T) / math.sqrt(Dh), vis)
-            O = P @ v[b, h]
+            P, _m, _l = _softmax((q[b, h] @ k[b, h // Gq].T) / math.sqrt(Dh), vis)
+            O = P @ v[b, h // Gq]
             rms = np.sqrt((O * O).mean(axis=1, keepdims=True))
-            dO[b, h] = round_to(dO[b, h] + (8.0 / Dh) * O / np.where(rms > 0, rms, 1.0), fmt)
-    for x in (q, k, v, dO):
-        assert np.array_equal(round_to(x, fmt), x) and np.isfinite(x).all(), "the inputs must survive the cast to the 16-bit type"
+            dO[b, h] = round_to(dO[b, h] + (8.0 / Dh) * O / np.where(rms > 0, rms, 1.0), dO_fmt)
+    if dO_fmt != fmt:
+        dO = np.where(np.abs(dO) < SMALL_DO, np.where(dO < 0, -SMALL_DO, SMALL_DO), dO)
+    if small_dO_rows is not None:
+        dO[:, :, small_dO_rows] *= 2.0 ** -12
+    for x, f in ((q, fmt), (k, fmt), (v, fmt), (dO, dO_fmt)):
+        assert np.array_equal(round_to(x, f), x) and np.isfinite(x).all(), "the inputs must survive the cast to the 16-bit type"
     return q, k, v, dO, info
 
 
