@@ -15,6 +15,7 @@ from .attention import (  # noqa: F401
     AttentionPrefill,
     GEMMOperandPrecision,
     KVCacheAppend,
+    KVCacheCompact,
     KVCachePrecision,
     deviceCount,
     deviceName,
@@ -26,3 +27,11 @@ from .attention import (  # noqa: F401
     setParameterFile,
 )
 from .gemm import GEMMDescriptor, GEMMKernel, GEMMKernelDescriptor  # noqa: F401,E402
+
+
+def __getattr__(name):
+    # the torch functions of the KV-cache loop, on first use: torch stays optional for everything above
+    if name in ("kv_cache_compact", "tree_path"):
+        from . import torch_binding
+        return getattr(torch_binding, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

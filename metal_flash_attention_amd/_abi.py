@@ -305,6 +305,28 @@ TREE_SYMBOLS = [   # include/mfa_tree.h: `tree` (required) after `sinks` (NULL =
     ("mfa_attention_prefill_tree_tile_range", ctypes.c_int, [ctypes.c_uint32] * 4 + [_U32P] * 5),
 ]
 
+class mfa_kv_compact_params(ctypes.Structure):   # include/mfa_compact.h
+    _fields_ = [
+        ("rows", ctypes.c_uint32), ("heads", ctypes.c_uint32), ("batches", ctypes.c_uint32), ("column", ctypes.c_uint32),
+        ("headDimension", ctypes.c_uint16), ("cachePrecision", ctypes.c_uint8), ("reserved", ctypes.c_uint8),
+        ("pageSize", ctypes.c_uint32),
+        ("cacheLengths", ctypes.c_void_p), ("queryLengths", ctypes.c_void_p), ("blockTable", ctypes.c_void_p), ("blockTableStride", ctypes.c_int64),
+        ("accepted", ctypes.c_void_p), ("acceptedStride", ctypes.c_int64), ("acceptedCounts", ctypes.c_void_p),
+        ("maxAccepted", ctypes.c_uint32), ("reserved2", ctypes.c_uint32), ("newLengths", ctypes.c_void_p),
+        ("leadingDimension", ctypes.c_int64 * 2), ("headStride", ctypes.c_int64 * 2), ("batchStride", ctypes.c_int64 * 2),
+        ("pageStride", ctypes.c_int64 * 2),
+    ]
+
+
+_COMPACT = ctypes.POINTER(mfa_kv_compact_params)
+
+COMPACT_SYMBOLS = [   # include/mfa_compact.h: the accepted path of a speculation tree moved to the front of the tree's slots
+    ("mfa_kv_compact_params_init", None, [_COMPACT]),
+    ("mfa_kv_compact_params_size", ctypes.c_size_t, []),
+    ("mfa_kv_compact_params_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
+    ("mfa_kv_cache_compact_launch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _COMPACT, ctypes.c_void_p]),
+]
+
 # ---- the laddered entries of the launches over a KV cache, described once:
 #     mfa_attention_<launch>_<family><verb>(*<the verb's head>, params, *<the options the family owns>, *<the verb's tail>)
 # CACHE_FAMILIES: launch -> family -> the options its entries take, in the order of their signatures (each family is an earlier one plus an
@@ -409,7 +431,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

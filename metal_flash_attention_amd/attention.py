@@ -463,7 +463,7 @@ def _packed_rows(heads, D):
 
 
 def _fill_shared(p, D, operands, packed, *, rows, column, heads, batches, cacheLengths, pageSize, blockTable, blockTableStride, strides, pageStrides):
-    """the fields mfa_decode_params, mfa_prefill_params and mfa_kv_append_params share.  `operands`: their names in the order of the
+    """the fields mfa_decode_params, mfa_prefill_params, mfa_kv_append_params and mfa_kv_compact_params share.  `operands`: their names in the order of the
     struct's arrays; `packed`: in the same order, the strides of an operand left out of `strides`"""
     p.rows, p.column, p.heads, p.batches, p.headDimension = int(rows), int(column), int(heads), int(batches), D
     p.pageSize, p.cacheLengths = int(pageSize), _pointer(cacheLengths)
@@ -820,6 +820,48 @@ class KVCacheAppend:
         family, own = ("", ()) if ragged is None else ("ragged_", (ctypes.byref(ragged[0]),))
         check(getattr(lib(), "mfa_kv_cache_append_" + family + "launch")(*_pointers(kNew, vNew, kCache, vCache), ctypes.byref(p), *own,
                                                                          ctypes.c_void_p(stream or 0)))
+
+
+class KVCacheCompact:
+    """Moves the K and V rows of the accepted path of a speculation tree to the front of the tree's slots, in place, and writes the
+    lengths the sequences then have (include/mfa_compact.h): what follows a tree launch, before the next append.
+
+        compact = KVCacheCompact(128, KVCachePrecision.E4M3)
+        compact.dispatch(k_cache, v_cache, rows=R, heads=8, batches=B, column=C, cacheLengths=lengths, accepted=path, acceptedStride=R,
+                         acceptedCounts=counts, maxAccepted=R, newLengths=new_lengths)
+
+    cachePrecision: the cache's 16-bit type (GEMMOperandPrecision) or KVCachePrecision.E4M3 -- only the bytes of a row matter.
+    cacheLengths includes the `rows` tree rows, as the append and the tree launch took it; node j sits at key cacheLengths[b] - rows + j.
+    accepted: device int32 [batches][acceptedStride], node indices in path order; acceptedCounts: device uint32 [batches]; newLengths:
+    device uint32 [batches] or None.  `strides`: operand name (kCache, vCache) -> (leadingDimension, headStride, batchStride) in
+    elements; an operand left out is packed ([batch][head][key][D]).  Paged caches: pageSize, blockTable, blockTableStride and
+    pageStrides=(K, V)."""
+
+    OPERANDS = ("kCache", "vCache")
+
+    def __init__(self, headDimension: int, cachePrecision: int = GEMMOperandPrecision.BF16):
+        self.headDimension = int(headDimension)
+        self.cachePrecision = int(cachePrecision)
+
+    def _params(self, *, rows: int, heads: int, batches: int = 1, column: int = 0, cacheLengths=None, queryLengths=None, accepted=None,
+                acceptedStride: Optional[int] = None, acceptedCounts=None, maxAccepted: Optional[int] = None, newLengths=None, pageSize: int = 0,
+                blockTable=None, blockTableStride: int = 0, strides: Optional[Mapping] = None, pageStrides: Optional[Sequence[int]] = None):
+        p = _abi.mfa_kv_compact_params()
+        lib().mfa_kv_compact_params_init(ctypes.byref(p))
+        D = self.headDimension
+        cache = _packed(int(pageSize) or column, heads, D)
+        _fill_shared(p, D, self.OPERANDS, (cache, cache), rows=rows, column=column, heads=heads, batches=batches, cacheLengths=cacheLengths,
+                     pageSize=pageSize, blockTable=blockTable, blockTableStride=blockTableStride, strides=strides, pageStrides=pageStrides)
+        p.cachePrecision, p.queryLengths = self.cachePrecision, _pointer(queryLengths)
+        p.maxAccepted = int(rows if maxAccepted is None else maxAccepted)
+        p.accepted, p.acceptedStride = _pointer(accepted), int(p.maxAccepted if acceptedStride is None else acceptedStride)
+        p.acceptedCounts, p.newLengths = _pointer(acceptedCounts), _pointer(newLengths)
+        return p
+
+    def dispatch(self, kCache, vCache, *, stream: Optional[int] = None, **shape) -> None:
+        """mfa_kv_cache_compact_launch"""
+        p = self._params(**shape)
+        check(lib().mfa_kv_cache_compact_launch(*_pointers(kCache, vCache), ctypes.byref(p), ctypes.c_void_p(stream or 0)))
 
 
 def quantizeE4M3(x: float, scale: float = 1.0) -> int:

@@ -35,6 +35,19 @@ mfa_status check_paging(uint32_t pageSize, const void *blockTable, int64_t block
   return MFA_OK;
 }
 
+mfa_status check_written_cache(uint32_t pageSize, const void *blockTable, int64_t blockTableStride, uint32_t column, uint32_t *pageShift) {
+  const mfa_status st = check_paging(pageSize, blockTable, blockTableStride, 0, pageShift);   // (0: the kernel drops a row past the stride)
+  if (st != MFA_OK) return st;
+  if (!pageSize && column == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "column (the capacity of a contiguous cache) must be non-zero");
+  return MFA_OK;
+}
+
+const char *const kWrittenCacheStridesWhy = "(16-byte rows of 16-bit operands; an e4m3 cache: multiples of 16 elements)";
+
+mfa_status check_written_cache_strides(const char *name, uint32_t headDimension, int64_t leadingDimension, int64_t headStride, int64_t outer, bool fp8) {
+  return check_operand_strides(name, headDimension, leadingDimension, headStride, outer, fp8 ? 16 : 8, kWrittenCacheStridesWhy);
+}
+
 mfa_status check_stride_multiples(const char *name, int64_t leadingDimension, int64_t headStride, int64_t outer, int64_t need, const char *why) {
   if (leadingDimension % need || headStride % need || outer % need)
     return fail(MFA_ERR_INVALID_ARGUMENT, std::string("strides of ") + name + " must be multiples of " + std::to_string(need) + " elements " + why);

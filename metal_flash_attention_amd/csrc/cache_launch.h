@@ -1,5 +1,5 @@
 // cache_launch.h -- what the host sides of the launches over a KV cache share (attn_decode16.hip, attn_prefill16.hip,
-// kv_cache_append.hip): the checks of paging, operand strides, cache precision and buffer pointers, and of a sliding window and
+// kv_cache_append.hip, kv_cache_compact.hip): the checks of paging, operand strides, cache precision and buffer pointers, and of a sliding window and
 // attention sinks (Sinks, check_window_and_sinks: decode and prefill), of a soft cap (check_softcap) and of a speculation tree
 // (check_tree), each with ONE wording, so that the same mistake is refused in the same words whichever launch meets it; the options of a launch as one value (LaunchOptions), and the
 // path every decode and prefill entry takes from it: the checks both launches word alike (check_precisions ... check_cache_and_strides), bind, and the bodies
@@ -32,6 +32,13 @@ void copy_text(char *out, size_t capacity, const char *text);
 // logarithm.  `column` != 0: a sequence's row of the table must hold the pages of that many keys (decode, prefill).  0: any positive
 // stride (append, whose kernel drops a row whose page lies past the stride).
 mfa_status check_paging(uint32_t pageSize, const void *blockTable, int64_t blockTableStride, uint32_t column, uint32_t *pageShift);
+
+// the cache of a launch that WRITES it (append, compact): check_paging without a column bound -- the kernels drop a row whose page lies
+// past the stride (kv_cache_slot.h) -- and, for a contiguous cache, a non-zero `column`
+mfa_status check_written_cache(uint32_t pageSize, const void *blockTable, int64_t blockTableStride, uint32_t column, uint32_t *pageShift);
+// ... and the strides of its kCache / vCache (`name`), in check_operand_strides' words: multiples of 8 elements, an e4m3 cache of 16
+mfa_status check_written_cache_strides(const char *name, uint32_t headDimension, int64_t leadingDimension, int64_t headStride, int64_t outer, bool fp8);
+extern const char *const kWrittenCacheStridesWhy;
 
 // one operand's strides, in elements: leadingDimension, headStride and `outer` (the batch stride, or the page stride of a paged cache)
 // are multiples of `need`; `why` ends the message.  check_operand_strides first wants rows of at least headDimension elements.

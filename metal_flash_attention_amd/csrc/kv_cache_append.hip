@@ -12,6 +12,7 @@
 #include "../../include/mfa_ragged.h"
 #include "attn_common.h"
 #include "cache_launch.h"
+#include "kv_cache_slot.h"
 #include "kv_e4m3.h"
 #include "launchers.h"
 #include "mfa_internal.h"
@@ -43,21 +44,10 @@ template <> __device__ __forceinline__ float to_float<_Float16>(uint16_t bits) {
 template <typename T, int D, bool FP8>
 __device__ __forceinline__ void kv_append_row(const AppendArgs &a, uint32_t batch, uint32_t sbatch, uint32_t row, int64_t pos) {
   constexpr uint32_t CPR = D / 8;   // 16-byte source chunks per row
-  if (pos < 0) return;
-  int64_t base[2];
-  if (a.paged) {
-    const int64_t pageIndex = pos >> a.pageShift;
-    if (pageIndex >= a.tableStride) return;
-    const int64_t page = (int64_t)a.table[(int64_t)batch * a.tableStride + pageIndex];
-    if (page < 0) return;
-    const int64_t in = pos & (((int64_t)1 << a.pageShift) - 1);
+  int64_t base[2], outer, in;
+  if (!kv_cache_slot(a.table, a.tableStride, a.paged, a.pageShift, a.column, batch, pos, &outer, &in)) return;
 #pragma unroll
-    for (int o = 0; o < 2; ++o) base[o] = page * a.psc[o] + in * a.ldc[o];
-  } else {
-    if (pos >= (int64_t)a.column) return;
-#pragma unroll
-    for (int o = 0; o < 2; ++o) base[o] = (int64_t)batch * a.bsc[o] + pos * a.ldc[o];
-  }
+  for (int o = 0; o < 2; ++o) base[o] = outer * (a.paged ? a.psc[o] : a.bsc[o]) + in * a.ldc[o];
   const uint32_t items = 2u * a.H * CPR;
   for (uint32_t idx = threadIdx.x; idx < items; idx += blockDim.x) {
     const uint32_t c = idx % CPR, head = (idx / CPR) % a.H, o = idx / (CPR * a.H);
@@ -180,15 +170,15 @@ mfa_status prepare(const mfa_kv_append_params *p, AppendArgs *a, AppendKernel *k
   if (!fp8 && (p->keyScale || p->valueScale))
     return fail(MFA_ERR_INVALID_ARGUMENT, "keyScale / valueScale go with an e4m3 cache (MFA_KV_E4M3); a 16-bit cache takes the rows' bits unscaled");
   uint32_t pageShift = 0;
-  st = check_paging(p->pageSize, p->blockTable, p->blockTableStride, 0, &pageShift);   // (0: the kernel drops a row past the stride)
+  st = check_written_cache(p->pageSize, p->blockTable, p->blockTableStride, p->column, &pageShift);
   if (st != MFA_OK) return st;
-  if (!p->pageSize && p->column == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "column (the capacity of a contiguous cache) must be non-zero");
   static const char *names[4] = {"kNew", "vNew", "kCache", "vCache"};
   for (int i = 0; i < 4; ++i) {
-    const bool cache = i >= 2;
-    st = check_operand_strides(names[i], p->headDimension, p->leadingDimension[i], p->headStride[i],
-                               cache && p->pageSize ? p->pageStride[i - 2] : p->batchStride[i], (cache && fp8) ? 16 : 8,
-                               "(16-byte rows of 16-bit operands; an e4m3 cache: multiples of 16 elements)");
+    if (i >= 2)
+      st = check_written_cache_strides(names[i], p->headDimension, p->leadingDimension[i], p->headStride[i],
+                                       p->pageSize ? p->pageStride[i - 2] : p->batchStride[i], fp8);
+    else
+      st = check_operand_strides(names[i], p->headDimension, p->leadingDimension[i], p->headStride[i], p->batchStride[i], 8, kWrittenCacheStridesWhy);
     if (st != MFA_OK) return st;
   }
   std::memset(a, 0, sizeof(*a));

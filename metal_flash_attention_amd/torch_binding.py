@@ -15,6 +15,10 @@ reference does not have -- only its tests call the kernels, Tests/FlashAttention
     kv_cache_append(k_new, v_new, k_cache, v_cache, cache_lengths, k_scale=ks, v_scale=vs)   # float8_e4m3fn or 16-bit caches
     o = flash_decode(q, k_cache, v_cache, cache_lengths, k_scale=ks, v_scale=vs)
 
+    from metal_flash_attention_amd.torch_binding import kv_cache_compact, tree_path   # after a tree launch (tree_mask=): keep the accepted path
+    accepted, counts = tree_path(tree_bits, leaf)                                      # bool [B, R, R] and a leaf per sequence
+    cache_lengths = kv_cache_compact(k_cache, v_cache, cache_lengths, accepted, counts, rows=R)
+
 forward  = AttentionKernelType.forward           -> O (the inputs' dtype, fused cast), L (fp32), both saved
 backward = AttentionKernelType.backwardQuery     -> D, dQ      (needs O, dO, L)
            AttentionKernelType.backwardKeyValue  -> dK, dV     (needs L, D)
@@ -30,7 +34,8 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
-                        AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCachePrecision)
+                        AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
+                        KVCachePrecision)
 
 _KERNELS: Dict[Tuple, AttentionKernel] = {}
 
@@ -287,6 +292,29 @@ def pack_tree_mask(bits: torch.Tensor) -> torch.Tensor:
     return (bits.to(torch.int64) * weights).sum(-1)   # (distinct bits: the sum is their OR, bit 63 the sign)
 
 
+def tree_path(tree_bits: torch.Tensor, leaf) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The accepted path of a speculation tree as kv_cache_compact takes it: tree_bits bool [..., R, R] (what pack_tree_mask takes; [R, R]
+    with a leaf per sequence: one tree shared) and `leaf`, the index of the accepted leaf per sequence (an integer tensor [...], or an
+    int) -> (accepted int32 [..., R] padded with -1, counts int32 [...]).  The path is the set bits of the leaf's row -- its ancestors and
+    itself -- ordered by the popcount of each node's own row: depth order, root first, whatever the index order (a child may have a
+    smaller index than its parent).  Computed where tree_bits lives; nothing is read back."""
+    if tree_bits.dim() < 2 or tree_bits.shape[-1] != tree_bits.shape[-2] or not 1 <= tree_bits.shape[-1] <= 64:
+        raise ValueError(f"tree_path: expected bool [..., R, R] with R from 1 to 64 (got {tuple(tree_bits.shape)})")
+    R = tree_bits.shape[-1]
+    leaf = torch.as_tensor(leaf, device=tree_bits.device).to(torch.int64)
+    bits = tree_bits.to(torch.bool)
+    if bits.dim() - 2 < leaf.dim():
+        bits = bits.expand(*leaf.shape, R, R)
+    if leaf.shape != bits.shape[:-2]:
+        raise ValueError(f"tree_path: leaf must hold one index per tree, {tuple(bits.shape[:-2])} (got {tuple(leaf.shape)})")
+    row = torch.gather(bits, -2, leaf[..., None, None].expand(*leaf.shape, 1, R)).squeeze(-2)   # [..., R]: the leaf's ancestors and itself
+    depth = bits.sum(-1)                                                                        # [..., R]: each node's own popcount
+    order = torch.argsort(torch.where(row, depth, R + 1), dim=-1, stable=True)                  # (nodes off the path sort last)
+    counts = row.sum(-1)
+    on_path = torch.arange(R, device=bits.device) < counts[..., None]
+    return torch.where(on_path, order, -1).to(torch.int32), counts.to(torch.int32)
+
+
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False,
                     q_lengths: torch.Tensor = None, k_lengths: torch.Tensor = None,
                     block_mask: torch.Tensor = None, fast_scale: bool = False) -> torch.Tensor:
@@ -514,6 +542,65 @@ def _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts
     _append("kv_cache_append_ragged", _packed_operand, k_new, v_new, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, row_starts, max_rows)
 
 
+def _run_compact(k_cache, v_cache, cache_lengths, accepted, accepted_counts, rows, q_lengths, block_table):
+    """kv_cache_compact's launch (include/mfa_compact.h) on the caches' device and torch's current stream -> new lengths int32 [B]"""
+    who = "kv_cache_compact"
+    if not all(t.is_cuda for t in (k_cache, v_cache, cache_lengths, accepted, accepted_counts)):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for name, t in (("v_cache", v_cache), ("cache_lengths", cache_lengths), ("accepted", accepted), ("accepted_counts", accepted_counts),
+                    ("q_lengths", q_lengths), ("block_table", block_table)):
+        if t is not None and (not t.is_cuda or t.device != k_cache.device):
+            raise RuntimeError(f"{who}: {name} must live on the GPU of the cache (the host never reads it)")
+    if k_cache.dtype != v_cache.dtype or k_cache.dtype not in (torch.bfloat16, torch.float16, torch.float8_e4m3fn):
+        raise TypeError(f"{who}: the caches must both be bfloat16, float16 or torch.float8_e4m3fn (got {k_cache.dtype}, {v_cache.dtype}); "
+                        "e5m2 and fnuz caches have no kernel")
+    paged = block_table is not None
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or k_cache.shape[1] == 0:
+        raise ValueError(f"{who}: expected caches [B, Hkv, C, D] (paged: [pages, Hkv, pageSize, D]) of one shape "
+                         f"(got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
+    _check_lengths(who, "cache_lengths", cache_lengths, None if paged else k_cache.shape[0], ", B the caches' first dimension when they are contiguous")
+    B = int(cache_lengths.shape[0])
+    if isinstance(rows, bool) or not isinstance(rows, int) or not 1 <= rows <= 64:
+        raise ValueError(f"{who}: rows must be an int from 1 to 64, the rows of the tree launch (the host never reads a length), not {rows!r}")
+    if accepted.dim() != 2 or accepted.shape[0] != B or accepted.dtype != torch.int32 or accepted.shape[1] == 0 or accepted.stride(1) != 1:
+        raise ValueError(f"{who}: accepted must be an int32 GPU tensor [B, A] = [{B}, A] with a contiguous last dimension, the node indices of "
+                         f"every sequence's path in path order (tree_path; got {tuple(accepted.shape)}, {accepted.dtype})")
+    if accepted.shape[1] > 64:
+        raise ValueError(f"{who}: accepted holds at most 64 nodes per sequence, one bit of a uint64 tree mask each (got {tuple(accepted.shape)})")
+    _check_lengths(who, "accepted_counts", accepted_counts, B)
+    if q_lengths is not None:
+        _check_lengths(who, "q_lengths", q_lengths, B)
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
+            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is written where it lies)")
+    if accepted.stride(0) < accepted.shape[1]:   # (an expanded row: one path shared is given a row per sequence)
+        accepted = accepted.contiguous()
+    kw = dict(cacheLengths=cache_lengths.to(torch.int32), acceptedCounts=accepted_counts.to(torch.int32), accepted=accepted,
+              acceptedStride=int(accepted.stride(0)), maxAccepted=int(accepted.shape[1]),
+              queryLengths=None if q_lengths is None else q_lengths.to(torch.int32))
+    if paged:
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
+                not block_table.is_cuda:
+            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
+                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
+        table = block_table.contiguous()
+        kw.update(pageSize=int(k_cache.shape[2]), blockTable=table, blockTableStride=int(table.shape[1]),
+                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
+    else:
+        kw.update(column=int(k_cache.shape[2]))
+    kw.update(strides=dict(kCache=_cache_strides(k_cache, paged), vCache=_cache_strides(v_cache, paged)))
+    new_lengths = torch.empty((B,), dtype=torch.int32, device=k_cache.device)
+    key = (KVCacheCompact, k_cache.dtype, int(k_cache.shape[3]))
+    host = _HOSTS.get(key)
+    if host is None:
+        precision = {torch.bfloat16: P.BF16, torch.float16: P.FP16}.get(k_cache.dtype, KVCachePrecision.E4M3)
+        host = _HOSTS[key] = KVCacheCompact(int(k_cache.shape[3]), precision)
+    with torch.cuda.device(k_cache.device):
+        host.dispatch(k_cache, v_cache, stream=torch.cuda.current_stream(k_cache.device).cuda_stream, rows=rows, heads=int(k_cache.shape[1]),
+                      batches=B, newLengths=new_lengths, **kw)
+    return new_lengths
+
+
 def _check_tree(who, q, tree_mask, causal, window, softcap):
     """tree_mask= of a public function: an int64 tensor [R] or [B, R] on q's device; causal, no cap, a window of at least R"""
     R, B = (q.shape[2], q.shape[0]) if q.dim() == 4 else (None, None)
@@ -682,6 +769,15 @@ def _op_append_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.T
     _run_append_ragged(k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale, v_scale)
 
 
+def _op_compact(k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor, accepted: torch.Tensor, accepted_counts: torch.Tensor,
+                rows: int, q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor]) -> torch.Tensor:
+    return _run_compact(k_cache, v_cache, cache_lengths, accepted, accepted_counts, rows, q_lengths, block_table)
+
+
+def _fake_lengths(k_cache, v_cache, cache_lengths, *args, **kwargs):
+    return cache_lengths.new_empty((cache_lengths.shape[0],), dtype=torch.int32)
+
+
 def _fake_padded(q, *args, **kwargs):
     B, H, R, D = q.shape
     return q.new_empty((B, H, R, D)), q.new_empty((B, H, R), dtype=torch.float32)
@@ -736,6 +832,7 @@ _CACHE_OPS = [
     ("attention_prefill_ragged_softcap", _op_prefill_ragged_softcap, _fake_packed, ()),
     ("attention_decode_tree", _op_decode_tree, _fake_padded, ()),
     ("attention_prefill_tree", _op_prefill_tree, _fake_padded, ()),
+    ("kv_cache_compact", _op_compact, _fake_lengths, ("k_cache", "v_cache")),
 ]
 _HAVE = {_op[0]: _register_cache_op(*_op) for _op in _CACHE_OPS}   # op name -> whether torch has it as a custom op
 _HAVE_DECODE_OP = _HAVE["attention_decode"]
@@ -746,6 +843,7 @@ _HAVE_SINK_OPS = _HAVE["attention_decode_sink"] and _HAVE["attention_prefill_sin
 _HAVE_RAGGED_OPS = _HAVE["attention_prefill_ragged"] and _HAVE["kv_cache_append_ragged"]
 _HAVE_SOFTCAP_OPS = _HAVE["attention_decode_softcap"] and _HAVE["attention_prefill_softcap"] and _HAVE["attention_prefill_ragged_softcap"]
 _HAVE_TREE_OPS = _HAVE["attention_decode_tree"] and _HAVE["attention_prefill_tree"]
+_HAVE_COMPACT_OP = _HAVE["kv_cache_compact"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -920,3 +1018,25 @@ def kv_cache_append_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: to
     _in_place("kv_cache_append_ragged", k_new, v_new, k_cache, v_cache, cache_lengths)
     _call_op(_HAVE_RAGGED_OPS, "kv_cache_append_ragged", k_new, v_new, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, k_scale,
              v_scale)
+
+
+def kv_cache_compact(k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor, accepted: torch.Tensor,
+                     accepted_counts: torch.Tensor, rows: int, q_lengths: Optional[torch.Tensor] = None,
+                     block_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """What follows a tree launch (tree_mask= on flash_decode / flash_prefill): moves the K and V rows of the ACCEPTED path of every
+    sequence's speculation tree to the front of the tree's slots IN PLACE and returns the lengths the sequences then have, int32 [B] on
+    the GPU -- the tensor the next kv_cache_append takes once the new tokens are counted in.  cache_lengths [B] (GPU) is the tensor the
+    tree launch took: it INCLUDES the `rows` tree rows (q_lengths [B]: the rows of sequence b, as flash_prefill's), node j of sequence b
+    at key P + j with P = cache_lengths[b] - rows.  accepted int32 [B, A] (A <= 64) holds each path's node indices in path order, root
+    first, accepted_counts [B] how many of them count (tree_path gives both): the row at key P + i becomes the row that stood at key
+    P + accepted[b, i] BEFORE the call, for every K/V head, in K and in V -- every source is read before any destination is written, so
+    indices may decrease or repeat; an index < 0 or past the tree's live rows moves nothing.  Returns P + min(accepted_counts[b], A,
+    live rows).  Caches: kv_cache_append's -- [B, Hkv, C, D] or a strided view with a contiguous last dimension, or with block_table
+    [B, n] int32 page pools [pages, Hkv, pageSize, D]; bfloat16, float16 or torch.float8_e4m3fn (bytes are moved, scales do not enter).
+    No other byte of the caches changes.  Goes through the op `mfa::kv_cache_compact` (mutates_args) where torch has custom ops."""
+    for t in (k_cache, v_cache):
+        if t.requires_grad:
+            raise RuntimeError("kv_cache_compact writes in place and has no autograd: detach the inputs")
+    if not all(t.is_cuda for t in (k_cache, v_cache, cache_lengths, accepted, accepted_counts)):
+        raise RuntimeError("kv_cache_compact: tensors must live on the GPU (there is no CPU path)")
+    return _call_op(_HAVE_COMPACT_OP, "kv_cache_compact", k_cache, v_cache, cache_lengths, accepted, accepted_counts, rows, q_lengths, block_table)
