@@ -31,7 +31,8 @@
  * What the kernels need: 16-bit Q (FP32: MFA_ERR_UNSUPPORTED); head dimensions 64, 128 and 256; Q, K, V, O 16-byte aligned; Q strides
  * multiples of 8 elements, O strides of 4; K / V strides multiples of 8 elements for a 16-bit cache and of 16 elements (= bytes) for
  * an e4m3 cache; heads a multiple of headsPerKeyValue G, G <= 32.  No upper limit on rows (G x rows <= 32 included: the same math
- * as decode).  The launch takes no workspace: it is not cut along the keys.
+ * as decode).  The launch of these entries takes no workspace: it is not cut along the keys.  The entries of mfa_split.h are: a launch of
+ * few row blocks over a long cache, cut into pieces of every row block's tiles with a workspace and a combine kernel.
  *
  * How a launch runs: one workgroup owns 128 packed rows of ONE K / V head of one sequence -- RB = 128 / G consecutive query rows
  * for each of the G query heads of the group -- so K and V are read once per group, not G times.  Grid = batches x K/V heads x

@@ -305,6 +305,26 @@ TREE_SYMBOLS = [   # include/mfa_tree.h: `tree` (required) after `sinks` (NULL =
     ("mfa_attention_prefill_tree_tile_range", ctypes.c_int, [ctypes.c_uint32] * 4 + [_U32P] * 5),
 ]
 
+class mfa_key_split(ctypes.Structure):   # include/mfa_split.h
+    _fields_ = [("workspace", ctypes.c_void_p), ("workspaceBytes", ctypes.c_uint64), ("pieces", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+_SPLIT = ctypes.POINTER(mfa_key_split)
+MFA_PREFILL_SPLIT_MAX_PIECES, MFA_PREFILL_SPLIT_MIN_TILES, MFA_PREFILL_SPLIT_COMPUTE_UNITS = 64, 8, 256
+_SPLIT_OWN = [ctypes.c_uint32, _SINKS, _TREE, _SPLIT]   # window (0 = none), sinks (NULL = none), tree (NULL = none), split (required)
+
+SPLIT_SYMBOLS = [   # include/mfa_split.h: prefill cut along the keys -- one family of entries with `split` (required) after `tree`, written out
+    # here: it owns a window, sinks AND a tree, which no family of CACHE_FAMILIES does, and its workspace_size has a second result
+    ("mfa_key_split_init", None, [_SPLIT]),
+    ("mfa_key_split_size", ctypes.c_size_t, []),
+    ("mfa_key_split_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
+    ("mfa_attention_prefill_split_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL] + _SPLIT_OWN + [ctypes.c_void_p]),
+    ("mfa_attention_prefill_split_launch_form", ctypes.c_int, [_PREFILL] + _SPLIT_OWN + [ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_prefill_split_time", ctypes.c_int, _DECODE_BUFS + [_PREFILL] + _SPLIT_OWN + [ctypes.c_void_p] + _TIMING),
+    ("mfa_attention_prefill_split_workspace_size", ctypes.c_int, [_PREFILL] + _SPLIT_OWN + [ctypes.POINTER(ctypes.c_uint64), _U32P]),
+    ("mfa_attention_prefill_split_piece_range", ctypes.c_int, [ctypes.c_uint32] * 5 + [ctypes.POINTER(_U32x2), ctypes.POINTER(_U32x2)]),
+]
+
 class mfa_kv_compact_params(ctypes.Structure):   # include/mfa_compact.h
     _fields_ = [
         ("rows", ctypes.c_uint32), ("heads", ctypes.c_uint32), ("batches", ctypes.c_uint32), ("column", ctypes.c_uint32),
@@ -431,7 +451,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -448,6 +448,19 @@ def _tree_block(shape):
     return block, masks
 
 
+def _split_block(shape):
+    """pops workspace= / workspaceBytes= / pieces= from a prefill launch's keywords -> (mfa_key_split, what it points to) (include/mfa_split.h:
+    the launch cut along the keys; pieces None or 0: the host's plan, 1: unsplit; no workspace: the unsplit launch)"""
+    workspace, nbytes, pieces = shape.pop("workspace", None), shape.pop("workspaceBytes", None), shape.pop("pieces", None)
+    block = _abi.mfa_key_split()
+    lib().mfa_key_split_init(ctypes.byref(block))
+    block.workspace = _pointer(workspace)
+    if nbytes is None:
+        nbytes = int(workspace.numel() * workspace.element_size()) if hasattr(workspace, "numel") else 0
+    block.workspaceBytes, block.pieces = int(nbytes), int(pieces or 0)
+    return block, workspace
+
+
 def _pointers(*buffers):
     return tuple(_pointer(b) for b in buffers)
 
@@ -526,6 +539,15 @@ class _CacheAttention:
         ragged = _ragged_block(shape) if self.LAUNCH == "prefill" and ("rowStarts" in shape or "totalRows" in shape) else None
         tree = _tree_block(shape) if "treeMasks" in shape or "treeBatchStride" in shape else None
         quant, _scales = self._quant(shape)
+        if self.LAUNCH == "prefill" and ("workspace" in shape or "pieces" in shape):   # cut along the keys: the entries of include/mfa_split.h
+            split = _split_block(shape)
+            if cap is not None or ragged is not None:   # (no split kernel and no entry: said here)
+                raise ValueError("a key split (workspace= / pieces=) goes with neither " + ("softcap=" if cap is not None else "rowStarts= / totalRows=") +
+                                 ": a soft cap or ragged rows together with a split have no kernel (include/mfa_split.h)")
+            p, _keep = self._params(**shape)
+            own = (int(window or 0), sinks and ctypes.byref(sinks[0]), tree and ctypes.byref(tree[0]), ctypes.byref(split[0]))
+            check(getattr(lib(), "mfa_attention_prefill_split_" + verb)(*head, ctypes.byref(p), *own, *tail))
+            return
         p, _keep = self._params(**shape) if ragged is None else self._params(ragged=ragged, **shape)
         entries, own = _route(self.ROUTES, quant, window, sinks and ctypes.byref(sinks[0]), ragged and ctypes.byref(ragged[0]), cap,
                               tree and ctypes.byref(tree[0]))
@@ -671,7 +693,7 @@ class AttentionPrefill(_CacheAttention):
     `strides`, pageSize / blockTable / blockTableStride / pageStrides, lStrides: as AttentionDecode.  cachePrecision=
     KVCachePrecision.E4M3 reads an e4m3 cache (the quantisation block is part of mfa_prefill_params, so one class serves both): the
     K / V strides then count bytes, and keyScale / valueScale (device FP32 [heads // headsPerKeyValue], None = 1.0) go with the shape
-    arguments.  The launch takes no workspace.  window=W (launchForm, dispatch, time): sliding-window attention,
+    arguments.  The launch takes no workspace unless it is cut along the keys (below).  window=W (launchForm, dispatch, time): sliding-window attention,
     include/mfa_window.h; None: the plain launch; 0 goes through the window entries and is the plain launch.  sinkTokens=S,
     sinkLogits=device FP32 [heads] (the same three): attention sinks as AttentionDecode's, include/mfa_sink.h.
 
@@ -683,7 +705,13 @@ class AttentionPrefill(_CacheAttention):
     softcap=cap (the same three, ragged included): logit soft-capping as AttentionDecode's, include/mfa_softcap.h.
 
     treeMasks= / treeBatchStride= (the same three; rows <= 64, not ragged, no softcap): a speculation tree as AttentionDecode's,
-    include/mfa_tree.h; treeTileRange gives the tiles every row block of a sequence then walks."""
+    include/mfa_tree.h; treeTileRange gives the tiles every row block of a sequence then walks.
+
+    workspace=device buffer / pieces=P (the same three, and workspaceSize; not ragged, no softcap): the launch CUT ALONG THE KEYS,
+    include/mfa_split.h -- each row block's tiles in P pieces (None or 0: the host's plan; 1: unsplit; 2 .. 64: as given) that publish
+    partial results to the workspace, and a combine kernel.  Either keyword goes through the split entries, with any window, sinks and
+    tree; without a workspace the launch runs unsplit.  workspaceSize(pieces=...) gives the bytes, plannedSplit the piece count too,
+    pieceRange the tiles of a piece.  A launch that gives neither keyword is the launch it always was."""
 
     LAUNCH, ROUTES = "prefill", _routes("prefill")
 
@@ -757,6 +785,28 @@ class AttentionPrefill(_CacheAttention):
         check(lib().mfa_attention_prefill_tree_tile_range(int(length), int(queryLength), int(window), int(sinkTokens),
                                                           *(ctypes.byref(x) for x in out)))
         return tuple(int(x.value) for x in out)
+
+    def workspaceSize(self, **shape) -> int:
+        """Bytes a launch of this shape needs to run cut along the keys in `pieces` pieces (None or 0: the host's plan); 0: one piece
+        (include/mfa_split.h).  Without a workspace the launch runs unsplit in one kernel."""
+        return self.plannedSplit(**shape)[0]
+
+    def plannedSplit(self, **shape) -> Tuple[int, int]:
+        """(workspace bytes, pieces) of workspaceSize's launch: the piece count the host planned, or the one given"""
+        shape.setdefault("pieces", None)
+        nbytes, pieces = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        self._call("workspace_size", shape, tail=(ctypes.byref(nbytes), ctypes.byref(pieces)))
+        return int(nbytes.value), int(pieces.value)
+
+    @staticmethod
+    def pieceRange(beginTile: int, endTile: int, sinkEnd: int, pieces: int, piece: int) -> Tuple[Tuple[int, int], Tuple[int, int]]:
+        """((begin, end) inside the sink tiles, (begin, end) inside [beginTile, endTile)) of piece `piece` of `pieces` of a row block whose
+        walked list is the tiles [0, sinkEnd) ++ [beginTile, endTile) -- three of the five indices of sinkTileRange / treeTileRange
+        (include/mfa_split.h): the kernels' own function, on the host"""
+        b, e = _abi._U32x2(0, 0), _abi._U32x2(0, 0)
+        check(lib().mfa_attention_prefill_split_piece_range(int(beginTile), int(endTile), int(sinkEnd), int(pieces), int(piece),
+                                                            ctypes.byref(b), ctypes.byref(e)))
+        return (int(b[0]), int(e[0])), (int(b[1]), int(e[1]))
 
     @staticmethod
     def raggedSlots(totalRows: int, batches: int, rows: int, blockRows: int) -> int:

@@ -68,15 +68,7 @@ const DecodeSet kSets[] = {MFA_DECODE_SET(bf16, MFA_BF16, 64), MFA_DECODE_SET(bf
 // Pieces of the keys: chosen from the workgroups the launch has without a split (batches x K/V heads) and `column` only -- the lengths
 // live on the device.  Aims at MFA_DECODE_WORKGROUP_TARGET workgroups (two per compute unit of a 256-CU chip, what choose_splits of
 // mfa_kernel.hip aims at), rounded down; a piece keeps at least four 64-key tiles (two steps for each of the workgroup's four waves).
-// Under a window of W keys a sequence walks the tiles of W + rows - 1 keys that need not start on a tile: at most
-// ceil((W + rows - 1) / 64) + 1, and never more than column's.  S sink tokens add at most their ceil(S / 64) tiles to the window's.
-uint64_t planned_tiles(uint32_t column, uint32_t rows, uint32_t window, uint32_t sinkTokens) {
-  const uint64_t tiles = ((uint64_t)column + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE;
-  if (!window) return tiles;
-  const uint64_t spanned = ((uint64_t)window + rows - 1 + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE + 1 +
-                           ((uint64_t)sinkTokens + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE;
-  return spanned < tiles ? spanned : tiles;
-}
+// The tile count is planned_tiles' (cache_launch.h, shared with the split prefill launch).
 
 uint32_t choose_pieces(uint64_t blocks, uint64_t tiles) {
   if (blocks >= MFA_DECODE_WORKGROUP_TARGET) return 1;

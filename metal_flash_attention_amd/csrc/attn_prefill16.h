@@ -45,6 +45,19 @@
 // are never read.  A row's mask may name any new token and its depth is not its index, so every row block of a sequence walks the SAME
 // tiles, prefill_tree_tile_range's, through the four loops that exist: the tiles an earlier row block walks beyond its causal end are
 // fully masked for a chain (p = 0, the row maximum untouched, +0 added) and change no bit.
+//
+// SPLIT (include/mfa_split.h): the launch cut along the keys, the SINK or the TREE body otherwise (any window and sinks,
+// none included; not RAGGED, no CAP).  The grid gains a piece index, the fastest: the pieces of one block are neighbours and share Q.
+//   * piece i of P of a block takes the positions [i W / P, (i + 1) W / P) of THAT BLOCK'S OWN walked list [0, sinkEnd) ++ [beginTile,
+//     endTile): prefill_split_piece_range -- one function, device and host (mfa_attention_prefill_split_piece_range) -- NARROWS the
+//     block's five indices to the piece, and the four loops, the first load and the buffer of a tile (its position inside the piece) are
+//     the unsplit body's on the narrowed indices.  Whether a tile runs with the per-element mask stays a property of the tile.
+//   * a live row publishes its un-normalised O (FP32, 16 bytes per lane straight from the accumulators) and (m, l) to the piece's slab
+//     wsO[piece][b][head][row][D], wsML[piece][b][head][row][2]; a piece that walked no tile still publishes (-FLT_MAX, 0), and a row
+//     whose l is 0 leaves its O slab alone.  Rows at or past queryLengths[b] and blocks without a live row write nothing.
+//   * the sink logit and the value scale are NOT the pieces' business: prefill16_combine_body, which has the head index, merges a row's
+//     pieces by the weights exp2(m_s - m*), reads a piece's O only where its l > 0, and THEN folds the sink logit and applies the value
+//     scale -- each exactly once per row, also when piece 0 is empty.  (Decode's "piece 0 folds" was the alternative.)
 #pragma once
 #include "attn_cache_step.h"
 #include "kv_e4m3.h"
@@ -84,6 +97,8 @@ struct PrefillArgs {
   float capIn, capOut;            // the CAP kernels only: c1 = 2 / cap and c2 = cap log2(e) (attn_cache_step.h); behind the ragged fields in turn
   const uint64_t *masks;          // the TREE kernels only: [batches][rows] row masks (include/mfa_tree.h); last in turn
   int64_t maskStride;             // elements between two sequences' masks; 0: one tree for all
+  uint32_t pieces, heads;         // the SPLIT kernels and the combine kernel only: P >= 2, and Hq = Hkv G; last in turn
+  float *wsO, *wsML;              // the slabs of include/mfa_split.h
 };
 
 // The tiles of the block of rows [r0, r0 + RB) of a sequence of n keys and qn rows.  Row r sees keys c < lim(r) = n, or with `causal`
@@ -194,6 +209,20 @@ __host__ __device__ __forceinline__ void prefill_tree_tile_range(uint32_t n, uin
   *sinkEnd = (uint32_t)(tiles < b ? tiles : b);
 }
 
+// SPLIT (include/mfa_split.h): piece `piece` of `pieces` of the walked list [0, sinkEnd) ++ [beginTile, endTile) of W tiles takes the
+// positions [piece W / pieces, (piece + 1) W / pieces): the tiles [begin[0], end[0]) inside the sink tiles, then [begin[1], end[1])
+// inside [beginTile, endTile) -- decode_sink_piece_range's arithmetic, on tiles.  sinkEnd <= beginTile <= endTile.  Device and host
+// (mfa_attention_prefill_split_piece_range) run this one body.
+__host__ __device__ __forceinline__ void prefill_split_piece_range(uint32_t beginTile, uint32_t endTile, uint32_t sinkEnd, uint32_t pieces,
+                                                                   uint32_t piece, uint32_t *begin, uint32_t *end) {
+  const uint32_t tiles = sinkEnd + (endTile - beginTile);
+  const uint32_t t0 = (uint32_t)((uint64_t)piece * tiles / pieces), t1 = (uint32_t)(((uint64_t)piece + 1) * tiles / pieces);   // positions in the list
+  begin[0] = t0 < sinkEnd ? t0 : sinkEnd;
+  end[0] = t1 < sinkEnd ? t1 : sinkEnd;
+  begin[1] = beginTile + (t0 > sinkEnd ? t0 - sinkEnd : 0u);
+  end[1] = beginTile + (t1 > sinkEnd ? t1 - sinkEnd : 0u);
+}
+
 // RAGGED (include/mfa_ragged.h): which row block slot `slot` of a launch over packed rows serves.  Sequence b owns the packed rows
 // [s_b, s_b + qn_b), s_b = min(starts[b], T), e_b = min(starts[b + 1], T), qn_b = min(max(e_b - s_b, 0), rows), in ceil(qn_b / RB) row
 // blocks; the slots count the row blocks of sequence 0, then those of sequence 1, ...  *sequence = UINT32_MAX: a slot past the total.
@@ -259,9 +288,11 @@ __device__ __forceinline__ void prefill_ragged_block_wave(const uint32_t *starts
 
 template <int D> constexpr int prefill16_lds_bytes() { return 2 /*buffers*/ * 2 /*K, V*/ * PF_TILE * D * 2; }
 
-template <typename T, int D, bool FP8, bool WINDOW = false, bool SINK = false, bool RAGGED = false, bool CAP = false, bool TREE = false>
+template <typename T, int D, bool FP8, bool WINDOW = false, bool SINK = false, bool RAGGED = false, bool CAP = false, bool TREE = false,
+          bool SPLIT = false>
 __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   static_assert(!TREE || (SINK && !RAGGED && !CAP), "the tree kernels are the sink kernels plus TREE");
+  static_assert(!SPLIT || (SINK && !RAGGED && !CAP), "the split kernels are the sink or the tree kernels plus SPLIT");
   static_assert(!RAGGED || SINK, "the ragged kernels are the sink kernels plus RAGGED");
   static_assert(!CAP || SINK, "the capped kernels are the sink kernels plus CAP");
   typedef Frag16<T> F;
@@ -292,7 +323,7 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
     if (batch == 0xffffffffu) return;      // a slot past the total: nothing is read or written
   } else {
     const Fwd16Grid g{a.rowBlocks, a.Hkv, a.batches, 1u, nullptr, nullptr};
-    fwd16_decode_block(g, blockIdx.x, &rb, &kvh, &batch);
+    fwd16_decode_block(g, SPLIT ? blockIdx.x / a.pieces : blockIdx.x, &rb, &kvh, &batch);   // (SPLIT: the piece is the fastest index)
     if (a.causal) rb = a.rowBlocks - 1 - rb;   // later row blocks traverse more keys: start them first
     qn = a.qlengths ? min(a.qlengths[batch], a.rows) : a.rows;
     r0 = rb * RB;
@@ -305,6 +336,19 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   else if constexpr (SINK) prefill_sink_tile_range(n, qn, r0, RB, a.causal, a.window, a.sinkTokens, &beginTile, &unmaskedBegin, &firstMasked, &endTile, &sinkEnd);
   else if constexpr (WINDOW) prefill_window_tile_range(n, qn, r0, RB, a.window, &beginTile, &unmaskedBegin, &firstMasked, &endTile);
   else prefill_tile_range(n, qn, r0, RB, a.causal, &firstMasked, &endTile);
+  // SPLIT: the five indices narrowed to the piece -- its sink tiles are [sinkBegin, sinkEnd), its other tiles [beginTile, endTile), of
+  // which [unmaskedBegin, firstMasked) run without the per-element mask; all wave-uniform, kept in scalar registers
+  uint32_t sinkBegin = 0;
+  if constexpr (SPLIT) {
+    uint32_t pb[2], pe[2];
+    prefill_split_piece_range(beginTile, endTile, sinkEnd, a.pieces, blockIdx.x % a.pieces, pb, pe);
+    sinkBegin = (uint32_t)__builtin_amdgcn_readfirstlane((int)pb[0]);
+    sinkEnd = (uint32_t)__builtin_amdgcn_readfirstlane((int)pe[0]);
+    beginTile = (uint32_t)__builtin_amdgcn_readfirstlane((int)pb[1]);
+    endTile = (uint32_t)__builtin_amdgcn_readfirstlane((int)pe[1]);
+    unmaskedBegin = min(max(unmaskedBegin, beginTile), endTile);
+    firstMasked = min(max(firstMasked, beginTile), endTile);
+  }
   float kscale = a.scale2 * (a.keyScale ? a.keyScale[kvh] : 1.0f);
   if constexpr (CAP) kscale *= a.capIn;   // (after the K scale: the cap is on the score the softmax would see)
   const float vscale = a.valueScale ? a.valueScale[kvh] : 1.0f;
@@ -453,7 +497,12 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
 
   // ---- the tiles: the loads of tile t + 1 fly under the arithmetic of tile t and land in the other buffer behind it.  One barrier
   // per tile: the buffer written in iteration t was last read in iteration t - 1, which every wave left through that barrier.
-  if constexpr (SINK) {
+  if constexpr (SPLIT) {   // (the piece's first tile)
+    if (sinkEnd > sinkBegin || endTile > beginTile) {
+      issue_loads((sinkEnd > sinkBegin ? sinkBegin : beginTile) * PF_TILE);
+      write_lds(0);
+    }
+  } else if constexpr (SINK) {
     if (sinkEnd != 0 || endTile > beginTile) {
       issue_loads((sinkEnd ? 0u : beginTile) * PF_TILE);
       write_lds(0);
@@ -472,9 +521,9 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
       if constexpr (decltype(sinkZone)::value) {
         more = t + 1 < sinkEnd || endTile > beginTile;
         next = t + 1 < sinkEnd ? t + 1 : beginTile;
-        buf = (int)(t & 1u);
+        buf = (int)((SPLIT ? t - sinkBegin : t) & 1u);   // (SPLIT: a buffer is a position inside the piece)
       } else {
-        buf = (int)((t - beginTile + sinkEnd) & 1u);
+        buf = (int)((t - beginTile + (SPLIT ? sinkEnd - sinkBegin : sinkEnd)) & 1u);
       }
     }
     if (more) issue_loads(next * PF_TILE);
@@ -486,7 +535,7 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   // (two loops, not one loop with the choice inside: with both forms of a step merging in one loop body hipcc spilled 6 .. 19 VGPRs
   // of the D = 128 kernels; like this the largest takes 232 of 256)
   if constexpr (SINK)     // (a fourth loop ahead of them all: the sink tiles)
-    for (uint32_t ts = 0; ts < sinkEnd; ++ts) tile(std::true_type{}, std::true_type{}, ts);
+    for (uint32_t ts = SPLIT ? sinkBegin : 0u; ts < sinkEnd; ++ts) tile(std::true_type{}, std::true_type{}, ts);
   uint32_t t = beginTile;
   if constexpr (WINDOW)   // (a third loop in front: the tiles in which some row's window starts)
     for (; t < unmaskedBegin; ++t) tile(std::true_type{}, std::false_type{}, t);
@@ -496,6 +545,20 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   // ---- normalise and store straight from the accumulators: o[db][4 g + i] is d = 32 db + 8 g + 4 hi + i of the lane's row
   float l_tot = l + __shfl_xor(l, 32);
   if (!live) return;
+  if constexpr (SPLIT) {
+    // the piece's slab: (m, l) always, O where the row saw a key (the combine kernel reads O only where l > 0); no scale, no sink logit
+    const uint64_t slab = (((uint64_t)(blockIdx.x % a.pieces) * a.batches + batch) * a.heads + qhead) * a.rows + rowt;
+    if (hi == 0) *reinterpret_cast<float2 *>(a.wsML + slab * 2) = make_float2(m, l_tot);
+    if (l_tot > 0.f) {
+      float *dst = a.wsO + slab * D + 4 * hi;
+#pragma unroll
+      for (int db = 0; db < NDB; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          *reinterpret_cast<float4 *>(dst + 32 * db + 8 * g) = make_float4(o[db][4 * g], o[db][4 * g + 1], o[db][4 * g + 2], o[db][4 * g + 3]);
+    }
+    return;
+  }
   // SINK: the sink logit joins (m, l); `fold` rescales O with l.  A row without a visible key ends with m = s2, l = 1
   float fold = 1.0f;
   if constexpr (SINK) {
@@ -513,20 +576,84 @@ __device__ __forceinline__ void prefill16_body(const PrefillArgs &a) {
   if (hi == 0 && a.l) a.l[(RAGGED ? (int64_t)packed : (int64_t)batch * a.lbs) + (int64_t)qhead * a.lhs + rowt] = row_lse(m, l_tot);
 }
 
+// SPLIT: merges the pieces of a row (the online-softmax merge of decode16_combine_body, attn_decode16.h).  One wave per (sequence, head,
+// row) of the capacity: lane s holds (m_s, l_s) of piece s (pieces <= 64); for O the wave is D / 4 column lanes x 64 / (D / 4) piece
+// groups.  A piece's weight is exp2(m_s - m*) where its l > 0 and 0 elsewhere, and its O slab is read only where the weight is not 0:
+// nothing is read that the launch did not write.  Rows at or past queryLengths[b] are skipped whole.  The sink logit joins the merged
+// (m*, l*) and the value scale the normalisation, HERE and nowhere else: once per row.  A row without a visible key in any piece:
+// O = 0, L = -FLT_MAX or the sink logit.
+template <typename T, int D>
+__device__ __forceinline__ void prefill16_combine_body(const PrefillArgs &a) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t R = a.rows, S = a.pieces;
+  const uint64_t rows = (uint64_t)a.batches * a.heads * R;
+  const uint64_t rowid = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (rowid >= rows) return;
+  const uint32_t row = (uint32_t)(rowid % R), bh = (uint32_t)(rowid / R);
+  const uint32_t head = bh % a.heads, batch = bh / a.heads;
+  const uint32_t qn = a.qlengths ? min(a.qlengths[batch], R) : R;
+  if (row >= qn) return;   // (its slabs were never written)
+  float ms = STEP_MINUS_HUGE, ls = 0.f;
+  if ((uint32_t)lane < S) {
+    const float2 ml = *reinterpret_cast<const float2 *>(a.wsML + ((uint64_t)lane * rows + rowid) * 2);
+    ms = ml.x; ls = ml.y;
+  }
+  float mstar = ms;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) mstar = fmaxf(mstar, __shfl_xor(mstar, off, 64));
+  const float w = ((uint32_t)lane < S && ls > 0.f) ? fast_exp2(ms - mstar) : 0.f;
+  float lstar = w * ls;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) lstar += __shfl_xor(lstar, off, 64);
+  constexpr uint32_t CL = D / 4, GR = 64 / CL;
+  const uint32_t c = (uint32_t)lane % CL, g = (uint32_t)lane / CL;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (uint32_t s0 = 0; s0 < S; s0 += GR) {
+    const uint32_t s_ = s0 + g;
+    const float ws = __shfl(w, (int)(s_ < 64 ? s_ : 63), 64);   // (every lane takes part in the exchange)
+    if (s_ < S && ws > 0.f) {
+      const float4 x = *reinterpret_cast<const float4 *>(a.wsO + ((uint64_t)s_ * rows + rowid) * D + c * 4);
+      acc.x += ws * x.x; acc.y += ws * x.y; acc.z += ws * x.z; acc.w += ws * x.w;
+    }
+  }
+#pragma unroll
+  for (uint32_t off = CL; off < 64; off <<= 1) {
+    acc.x += __shfl_xor(acc.x, (int)off, 64); acc.y += __shfl_xor(acc.y, (int)off, 64);
+    acc.z += __shfl_xor(acc.z, (int)off, 64); acc.w += __shfl_xor(acc.w, (int)off, 64);
+  }
+  float fold = 1.0f;
+  if (a.sinkLogits) fold = fold_sink_logit(a.sinkLogits[head], mstar, lstar);
+  const float vscale = a.valueScale ? a.valueScale[head / a.G] : 1.0f;
+  const float inv = lstar > 0.f ? vscale * fold / lstar : 0.f;
+  if (g == 0) {
+    acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
+    const int64_t at = (int64_t)batch * a.bso + (int64_t)head * a.hso + (int64_t)row * a.ldo + 4 * c;
+    store_o4<T>(a.o, at, a.outF32, acc);
+  }
+  if (lane == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)head * a.lhs + row] = row_lse(mstar, lstar);
+}
+
 } // namespace mfa
 
-// One list of the kernel families, (infix, WINDOW, SINK, RAGGED, CAP, TREE): the kernels, the table that selects them (attn_prefill16.hip) and the
+// One list of the kernel families, (infix, WINDOW, SINK, RAGGED, CAP, TREE, SPLIT): the kernels, the table that selects them (attn_prefill16.hip) and the
 // names are generated from it.  MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, ...) is a set's code objects, in the translation unit that
 // holds them; (MFA_PREFILL_DECLARE, ...) names the kernels of another unit for the table.  D = 256 runs one workgroup per compute unit.
 #define MFA_PREFILL_FAMILIES(X, K, TN, T, D)                                                                                          \
-  X(K, , false, false, false, false, false, TN, T, D) X(K, w, true, false, false, false, false, TN, T, D)                             \
-  X(K, s, true, true, false, false, false, TN, T, D) X(K, r, true, true, true, false, false, TN, T, D)                                \
-  X(K, c, true, true, false, true, false, TN, T, D) X(K, rc, true, true, true, true, false, TN, T, D)                                 \
-  X(K, t, true, true, false, false, true, TN, T, D)
+  X(K, , false, false, false, false, false, false, TN, T, D) X(K, w, true, false, false, false, false, false, TN, T, D)               \
+  X(K, s, true, true, false, false, false, false, TN, T, D) X(K, r, true, true, true, false, false, false, TN, T, D)                  \
+  X(K, c, true, true, false, true, false, false, TN, T, D) X(K, rc, true, true, true, true, false, false, TN, T, D)                   \
+  X(K, t, true, true, false, false, true, false, TN, T, D) X(K, sk, true, true, false, false, false, true, TN, T, D)                  \
+  X(K, tk, true, true, false, false, true, true, TN, T, D)
 #define MFA_PREFILL_DEFINE(NAME, D, ...)                                                                                              \
   extern "C" __global__ __launch_bounds__(256, D == 256 ? 1 : 2) void NAME(const mfa::PrefillArgs a) { mfa::prefill16_body<__VA_ARGS__>(a); }
 #define MFA_PREFILL_DECLARE(NAME, D, ...) extern "C" __global__ void NAME(const mfa::PrefillArgs a);
-#define MFA_PREFILL_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TREE, TN, T, D)                                                           \
-  K(attn_prefill16##I##_d##D##_##TN, D, T, D, false, WINDOW, SINK, RAGGED, CAP, TREE)                                                 \
-  K(attn_prefill16##I##_d##D##_##TN##_e4m3, D, T, D, true, WINDOW, SINK, RAGGED, CAP, TREE)
+#define MFA_PREFILL_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TREE, SPLIT, TN, T, D)                                                    \
+  K(attn_prefill16##I##_d##D##_##TN, D, T, D, false, WINDOW, SINK, RAGGED, CAP, TREE, SPLIT)                                          \
+  K(attn_prefill16##I##_d##D##_##TN##_e4m3, D, T, D, true, WINDOW, SINK, RAGGED, CAP, TREE, SPLIT)
 #define MFA_PREFILL_KERNELS(K, TN, T, D) MFA_PREFILL_FAMILIES(MFA_PREFILL_FAMILY, K, TN, T, D)
+// the combine kernel of a (D, type), in the translation unit of the set: the e4m3 launches share it (the slabs hold FP32 whatever the cache)
+#define MFA_PREFILL_COMBINE_DEFINE(TN, T, D)                                                                                          \
+  extern "C" __global__ __launch_bounds__(256) void attn_prefill16_combine_d##D##_##TN(const mfa::PrefillArgs a) {                    \
+    mfa::prefill16_combine_body<T, D>(a);                                                                                             \
+  }
+#define MFA_PREFILL_COMBINE_DECLARE(TN, T, D) extern "C" __global__ void attn_prefill16_combine_d##D##_##TN(const mfa::PrefillArgs a);

@@ -2,7 +2,8 @@
 // entries of include/mfa_window.h (a sliding window: the same checks and grid, the attn_prefill16w_* kernels) and of include/mfa_sink.h
 // (attention sinks: the attn_prefill16s_* kernels), the prefill entries of include/mfa_ragged.h (packed rows: attn_prefill16r_*) and
 // those of include/mfa_softcap.h (a soft cap on the scores: attn_prefill16c_*, over packed rows attn_prefill16rc_*) and those of
-// include/mfa_tree.h (a speculation tree among the new rows: attn_prefill16t_*).
+// include/mfa_tree.h (a speculation tree among the new rows: attn_prefill16t_*) and those of include/mfa_split.h (the launch cut along
+// the keys: attn_prefill16sk_* / attn_prefill16tk_* and the combine kernels attn_prefill16_combine_*).
 // The refusals of a window and of sinks, and the Sinks of a launch, are cache_launch.h's, shared with attn_decode16.hip.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 #include "../../include/mfa_ragged.h"
 #include "../../include/mfa_sink.h"
 #include "../../include/mfa_softcap.h"
+#include "../../include/mfa_split.h"
 #include "../../include/mfa_tree.h"
 #include "../../include/mfa_window.h"
 #include "attn_prefill16.h"
@@ -29,7 +31,8 @@ using namespace mfa;
 // Kernel names are plain C symbols, stable for a profiler's kernel trace: attn_prefill16_d<D>_<type>[_e4m3], and attn_prefill16w_*
 // under a sliding window, attn_prefill16s_* with attention sinks, attn_prefill16r_* over packed rows (the sink body: one ragged kernel
 // serves plain, window and sink launches), attn_prefill16c_* / attn_prefill16rc_* with a soft cap (the sink body and the ragged one),
-// attn_prefill16t_* with a speculation tree (the sink body)
+// attn_prefill16t_* with a speculation tree (the sink body), attn_prefill16sk_* / attn_prefill16tk_* cut along the keys (the sink and the
+// tree body), whose pieces attn_prefill16_combine_d<D>_<type> merges
 // (the macros that generate them from one list of families: attn_prefill16.h).  D = 256 lives in attn_prefill16_d256.hip.
 MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, bf16, __bf16, 64)
 MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, bf16, __bf16, 128)
@@ -37,6 +40,12 @@ MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, f16, _Float16, 64)
 MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, f16, _Float16, 128)
 MFA_PREFILL_KERNELS(MFA_PREFILL_DECLARE, bf16, __bf16, 256)
 MFA_PREFILL_KERNELS(MFA_PREFILL_DECLARE, f16, _Float16, 256)
+MFA_PREFILL_COMBINE_DEFINE(bf16, __bf16, 64)
+MFA_PREFILL_COMBINE_DEFINE(bf16, __bf16, 128)
+MFA_PREFILL_COMBINE_DEFINE(f16, _Float16, 64)
+MFA_PREFILL_COMBINE_DEFINE(f16, _Float16, 128)
+MFA_PREFILL_COMBINE_DECLARE(bf16, __bf16, 256)
+MFA_PREFILL_COMBINE_DECLARE(f16, _Float16, 256)
 
 namespace {
 
@@ -48,12 +57,16 @@ struct PrefillSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  PrefillKernel kernel[7][2];   // [0: plain, 1: window, 2: sinks, 3: ragged, 4: soft cap, 5: ragged with a soft cap, 6: tree][e4m3]
+  PrefillKernel kernel[9][2];   // [0: plain, 1: window, 2: sinks, 3: ragged, 4: soft cap, 5: ragged with a soft cap, 6: tree,
+                                //  7: sinks cut along the keys, 8: tree cut along the keys][e4m3]
+  PrefillKernel combine;        // merges the pieces of families 7 and 8
 };
 #define MFA_PREFILL_ENTRY(NAME) {NAME, #NAME}
-#define MFA_PREFILL_SET_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TREE, TN, T, D)                                                           \
+#define MFA_PREFILL_SET_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TREE, SPLIT, TN, T, D)                                                          \
   {MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN), MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN##_e4m3)},
-#define MFA_PREFILL_SET(TN, PREC, D) {D, PREC, (uint32_t)prefill16_lds_bytes<D>(), {MFA_PREFILL_FAMILIES(MFA_PREFILL_SET_FAMILY, , TN, , D)}}
+#define MFA_PREFILL_SET(TN, PREC, D)                                                                                                  \
+  {D, PREC, (uint32_t)prefill16_lds_bytes<D>(), {MFA_PREFILL_FAMILIES(MFA_PREFILL_SET_FAMILY, , TN, , D)},                            \
+   MFA_PREFILL_ENTRY(attn_prefill16_combine_d##D##_##TN)}
 const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(bf16, MFA_BF16, 256),
                             MFA_PREFILL_SET(f16, MFA_FP16, 64),  MFA_PREFILL_SET(f16, MFA_FP16, 128),  MFA_PREFILL_SET(f16, MFA_FP16, 256)};
 
@@ -63,13 +76,33 @@ uint64_t ragged_slots(uint32_t totalRows, uint32_t batches, uint32_t rows, uint3
   return tight < padded ? tight : padded;
 }
 
+// Pieces of the keys (include/mfa_split.h): chosen from the workgroups the launch has without a split and the tiles a sequence can walk
+// (planned_tiles, cache_launch.h) only -- the lengths live on the device.  Aims at MFA_PREFILL_SPLIT_COMPUTE_UNITS x the workgroups per
+// compute unit the kernel's LDS allows (2 at D <= 128, 1 at D = 256), rounded down; a piece keeps at least MFA_PREFILL_SPLIT_MIN_TILES.
+uint32_t choose_prefill_pieces(uint64_t blocks, uint64_t tiles, uint32_t D) {
+  const uint64_t target = (uint64_t)MFA_PREFILL_SPLIT_COMPUTE_UNITS * (D == 256 ? 1 : 2);
+  if (blocks >= target) return 1;
+  uint64_t s = target / blocks;
+  if (s > tiles / MFA_PREFILL_SPLIT_MIN_TILES) s = tiles / MFA_PREFILL_SPLIT_MIN_TILES;
+  if (s > MFA_PREFILL_SPLIT_MAX_PIECES) s = MFA_PREFILL_SPLIT_MAX_PIECES;
+  return s < 2 ? 1 : (uint32_t)s;
+}
+
+uint64_t prefill_workspace_bytes(uint32_t pieces, const mfa_prefill_params *p) {
+  return (uint64_t)pieces * p->batches * p->heads * p->rows * (p->headDimension + 2) * sizeof(float);
+}
+
 struct PrefillPlan {
   PrefillArgs args;
   const PrefillSet *set;
   bool fp8;
-  int family;        // 0: plain, 1: window, 2: sinks, 3: ragged, 4 / 5: padded / ragged with a soft cap, 6: tree -- the kernels' first index
+  int family;        // 0: plain, 1: window, 2: sinks, 3: ragged, 4 / 5: padded / ragged with a soft cap, 6: tree, 7 / 8: sinks / tree cut
+                     // along the keys -- the kernels' first index
   uint32_t blocks;   // batches x K/V heads x row blocks; ragged: slots x K/V heads
+  uint32_t pieces;   // as the launch runs: 1 without a split block, without a workspace, or when one piece is asked for or planned
+  uint32_t planned;  // what the split block asks for (pieces = 0: the host's plan); 1 without one
   const PrefillKernel &kernel() const { return set->kernel[family][fp8]; }
+  uint32_t combine_blocks() const { return (uint32_t)(((uint64_t)args.batches * args.heads * args.rows + 3) / 4); }   // a wave per row
   const char *name() const { return kernel().name; }
   mfa_status prepare(const mfa_prefill_params *p, const LaunchOptions &options);
   hipError_t run(hipStream_t stream) const;
@@ -95,6 +128,12 @@ mfa_status PrefillPlan::prepare(const mfa_prefill_params *p, const LaunchOptions
   if (allowed == MFA_OK) allowed = check_softcap(options.softcap);
   if (allowed == MFA_OK) allowed = check_tree(options, p->causal != 0, p->rows, MFA_TREE_MAX_NODES);
   if (allowed != MFA_OK) return allowed;
+  const mfa_key_split *split = options.split;
+  if (split && split->pieces > MFA_PREFILL_SPLIT_MAX_PIECES)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_key_split.pieces must be 0 (the host's plan), 1 (unsplit) or 2 .. 64 (a lane of the combine kernel's "
+                                          "wave per piece), not " + std::to_string(split->pieces));
+  if (split && (ragged || options.softcap != 0.0f))
+    return fail(MFA_ERR_UNSUPPORTED, "a key split goes with neither packed rows nor a soft cap: they have no split kernel (include/mfa_split.h)");
   if (p->precision == MFA_FP32)
     return fail(MFA_ERR_UNSUPPORTED, "prefill attention takes a 16-bit Q (precision MFA_BF16 or MFA_FP16); FP32 Q has no kernel");
   mfa_status st = check_precisions(p->precision, p->outputPrecision);
@@ -132,8 +171,28 @@ mfa_status PrefillPlan::prepare(const mfa_prefill_params *p, const LaunchOptions
   this->set = set;
   family = options.tree ? 6 : options.softcap != 0.0f ? (ragged ? 5 : 4) : ragged ? 3 : options.sinks.any() ? 2 : options.window != 0;
   this->blocks = (uint32_t)blocks;
+  planned = pieces = 1;
+  if (split) {
+    planned = split->pieces ? split->pieces : choose_prefill_pieces(blocks, planned_tiles(p->column, p->rows, options.window, options.sinks.tokens), set->D);
+    pieces = split->workspace ? planned : 1;   // no workspace: one kernel, unsplit
+    if (pieces > 1) {
+      const uint64_t need = prefill_workspace_bytes(pieces, p);
+      if (split->workspaceBytes < need)
+        return fail(MFA_ERR_INVALID_ARGUMENT, "workspace too small: " + std::to_string(split->workspaceBytes) + " bytes, the launch needs " +
+                                                  std::to_string(need) + " (mfa_attention_prefill_split_workspace_size)");
+      if ((uintptr_t)split->workspace % 16 != 0) return fail(MFA_ERR_INVALID_ARGUMENT, "workspace must be 16-byte aligned");
+      if (blocks * pieces > 0x7fffffffull)
+        return fail(MFA_ERR_UNSUPPORTED, "batches x K/V heads x row blocks x pieces = " + std::to_string(blocks * pieces) + " workgroups exceed one grid (2^31 - 1)");
+      family = options.tree ? 8 : 7;
+    }
+  }
   PrefillArgs &a = args;
   set_shared_args(a, p, G, pageShift, options);
+  if (pieces > 1) {
+    a.pieces = pieces; a.heads = p->heads;
+    a.wsO = (float *)split->workspace;
+    a.wsML = a.wsO + (uint64_t)pieces * p->batches * p->heads * p->rows * p->headDimension;
+  }
   a.qlengths = p->queryLengths;
   a.keyScale = fp8 ? p->keyScale : nullptr;
   a.valueScale = fp8 ? p->valueScale : nullptr;
@@ -146,9 +205,14 @@ mfa_status PrefillPlan::prepare(const mfa_prefill_params *p, const LaunchOptions
   return MFA_OK;
 }
 
+// (split: two kernels on the caller's stream, the pieces and their merge; nothing synchronises)
 hipError_t PrefillPlan::run(hipStream_t stream) const {
-  const hipError_t err = launch_kernel(kernel().launch, dim3(blocks), dim3(PF_THREADS), set->lds, stream, args);
+  hipError_t err = launch_kernel(kernel().launch, dim3(blocks * pieces), dim3(PF_THREADS), set->lds, stream, args);
   if (err != hipSuccess) return err;
+  if (pieces > 1) {
+    err = launch_kernel(set->combine.launch, dim3(combine_blocks()), dim3(256), 0, stream, args);
+    if (err != hipSuccess) return err;
+  }
   return hipGetLastError();
 }
 
@@ -170,10 +234,35 @@ mfa_status prefill_launch_form(const mfa_prefill_params *params, const LaunchOpt
   if (options.ragged)
     std::snprintf(text, sizeof(text), "%s (grid %u = %u slots x %u K/V heads, row blocks of %u rows x %u heads, %u packed rows of %u sequences, at most %u rows each, %s%s)",
                   plan.name(), plan.blocks, a.slots, a.Hkv, a.RB, a.G, a.totalRows, a.batches, a.rows, a.paged ? "paged" : "contiguous", tail.c_str());
+  else if (plan.pieces > 1)
+    std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads x %u pieces%s, %s%s) + %s (grid %u)",
+                  plan.name(), plan.blocks * plan.pieces, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, plan.pieces,
+                  options.split->pieces ? " as given" : "", a.paged ? "paged" : "contiguous", tail.c_str(), plan.set->combine.name, plan.combine_blocks());
   else
-    std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s%s)", plan.name(),
-                  plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous", tail.c_str());
+    std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s%s%s)", plan.name(),
+                  plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous", tail.c_str(),
+                  plan.planned > 1 ? (", unsplit without a workspace: the plan has " + std::to_string(plan.planned) + " pieces").c_str() : "");
   copy_text(out, capacity, text);
+  return MFA_OK;
+}
+
+// the bytes of the workspace the launch would split into and the piece count: 0 and 1 for an unsplit plan, whatever workspace the
+// block may already name
+mfa_status prefill_split_workspace_size(const mfa_prefill_params *params, const LaunchOptions &options, uint64_t *bytes, uint32_t *pieces) {
+  if (bytes) *bytes = 0;
+  if (pieces) *pieces = 1;
+  const mfa_status refused = entry_check(options, !bytes ? "null argument" : nullptr);
+  if (refused != MFA_OK) return refused;
+  mfa_key_split probe = *options.split;
+  probe.workspace = nullptr;
+  probe.workspaceBytes = 0;
+  LaunchOptions probed = options;
+  probed.split = &probe;
+  PrefillPlan plan;
+  const mfa_status st = plan.prepare(params, probed);
+  if (st != MFA_OK) return st;
+  if (plan.planned > 1) *bytes = prefill_workspace_bytes(plan.planned, params);
+  if (pieces) *pieces = plan.planned;
   return MFA_OK;
 }
 
@@ -397,6 +486,58 @@ mfa_status mfa_attention_prefill_tree_tile_range(uint32_t length, uint32_t query
   if (!begin || !unmaskedBegin || !unmaskedEnd || !end || !sinkEnd) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   if (sinkTokens && !window) return fail(MFA_ERR_INVALID_ARGUMENT, "sink tokens need a window: sinkTokens must be 0 when window is 0");
   prefill_tree_tile_range(length, queryLength, window, sinkTokens, begin, unmaskedBegin, unmaskedEnd, end, sinkEnd);
+  return MFA_OK;
+}
+
+// ---- cut along the keys (include/mfa_split.h): the tree entries with `split` after `tree`; NULL `sinks` and NULL `tree` are none, the
+// split block is required
+
+void mfa_key_split_init(mfa_key_split *split) {
+  if (split) std::memset(split, 0, sizeof(*split));
+}
+
+size_t mfa_key_split_size(void) { return sizeof(mfa_key_split); }
+
+mfa_status mfa_key_split_offsets(uint32_t *offsets, uint32_t capacity, uint32_t *count) {
+  if (!offsets || !count) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  static const uint32_t table[] = {(uint32_t)offsetof(mfa_key_split, workspace), (uint32_t)offsetof(mfa_key_split, workspaceBytes),
+                                   (uint32_t)offsetof(mfa_key_split, pieces), (uint32_t)offsetof(mfa_key_split, reserved)};
+  *count = 4;
+  for (uint32_t i = 0; i < 4 && i < capacity; ++i) offsets[i] = table[i];
+  return MFA_OK;
+}
+
+mfa_status mfa_attention_prefill_split_launch(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                              uint32_t window, const mfa_attention_sinks *sinks, const mfa_attention_tree *tree,
+                                              const mfa_key_split *split, void *stream) {
+  return prefill_launch(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).optional_tree(tree).split_of(split), stream);
+}
+
+mfa_status mfa_attention_prefill_split_launch_form(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
+                                                   const mfa_attention_tree *tree, const mfa_key_split *split, char *out, size_t capacity) {
+  return prefill_launch_form(params, LaunchOptions().within(window).optional_sinks(sinks).optional_tree(tree).split_of(split), out, capacity);
+}
+
+mfa_status mfa_attention_prefill_split_time(const void *q, const void *k, const void *v, void *o, float *l, const mfa_prefill_params *params,
+                                            uint32_t window, const mfa_attention_sinks *sinks, const mfa_attention_tree *tree,
+                                            const mfa_key_split *split, void *stream, int warmup, int iterations, float *milliseconds) {
+  return prefill_time(q, k, v, o, l, params, LaunchOptions().within(window).optional_sinks(sinks).optional_tree(tree).split_of(split), stream, warmup,
+                      iterations, milliseconds);
+}
+
+mfa_status mfa_attention_prefill_split_workspace_size(const mfa_prefill_params *params, uint32_t window, const mfa_attention_sinks *sinks,
+                                                      const mfa_attention_tree *tree, const mfa_key_split *split, uint64_t *bytes,
+                                                      uint32_t *pieces) {
+  return prefill_split_workspace_size(params, LaunchOptions().within(window).optional_sinks(sinks).optional_tree(tree).split_of(split), bytes, pieces);
+}
+
+mfa_status mfa_attention_prefill_split_piece_range(uint32_t beginTile, uint32_t endTile, uint32_t sinkEnd, uint32_t pieces, uint32_t piece,
+                                                   uint32_t begin[2], uint32_t end[2]) {
+  if (!begin || !end) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  if (pieces == 0 || piece >= pieces) return fail(MFA_ERR_INVALID_ARGUMENT, "piece must be below pieces, pieces non-zero");
+  if (sinkEnd > beginTile || beginTile > endTile)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "the walked list is [0, sinkEnd) ++ [beginTile, endTile): sinkEnd <= beginTile <= endTile");
+  prefill_split_piece_range(beginTile, endTile, sinkEnd, pieces, piece, begin, end);
   return MFA_OK;
 }
 

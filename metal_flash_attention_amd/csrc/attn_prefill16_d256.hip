@@ -7,3 +7,5 @@
 
 MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, bf16, __bf16, 256)
 MFA_PREFILL_KERNELS(MFA_PREFILL_DEFINE, f16, _Float16, 256)
+MFA_PREFILL_COMBINE_DEFINE(bf16, __bf16, 256)
+MFA_PREFILL_COMBINE_DEFINE(f16, _Float16, 256)

@@ -129,6 +129,14 @@ LaunchOptions &LaunchOptions::tree_of(const mfa_attention_tree *block) {
   return *this;
 }
 
+LaunchOptions &LaunchOptions::split_of(const mfa_key_split *block) {
+  split = block;
+  if (!block && !refusal)
+    refusal = "null mfa_key_split: the split entries require the block (mfa_key_split_init; a launch that is "
+              "not cut along the keys: the mfa_prefill.h / mfa_window.h / mfa_sink.h / mfa_tree.h entries, or pieces = 1)";
+  return *this;
+}
+
 mfa_status entry_check(const LaunchOptions &options, const char *bad) {
   if (options.refusal && (options.refusalFirst || !bad)) return fail(MFA_ERR_INVALID_ARGUMENT, options.refusal);
   return bad ? fail(MFA_ERR_INVALID_ARGUMENT, bad) : MFA_OK;

@@ -17,6 +17,7 @@
 #include "../../include/mfa_kvcache.h"
 #include "../../include/mfa_ragged.h"
 #include "../../include/mfa_sink.h"
+#include "../../include/mfa_split.h"
 #include "../../include/mfa_tree.h"
 #include "mfa_internal.h"
 
@@ -64,6 +65,17 @@ struct Sinks {
 mfa_status check_window_and_sinks(uint32_t window, const Sinks &sinks, bool causal);
 // the soft cap of a launch (include/mfa_softcap.h): 0 is none, anything but a finite positive number is refused
 mfa_status check_softcap(float softcap);
+// The 64-key tiles a sequence can walk, from what the host knows (the lengths live on the device): what decode's piece count and the
+// split prefill launch's are chosen from.  Under a window of W keys a sequence walks the tiles of W + rows - 1 keys that need not start
+// on a tile: at most ceil((W + rows - 1) / 64) + 1, and never more than column's.  S sink tokens add at most their ceil(S / 64) tiles
+// to the window's.
+inline uint64_t planned_tiles(uint32_t column, uint32_t rows, uint32_t window, uint32_t sinkTokens) {
+  const uint64_t tiles = ((uint64_t)column + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE;
+  if (!window) return tiles;
+  const uint64_t spanned = ((uint64_t)window + rows - 1 + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE + 1 +
+                           ((uint64_t)sinkTokens + MFA_DECODE_KEY_TILE - 1) / MFA_DECODE_KEY_TILE;
+  return spanned < tiles ? spanned : tiles;
+}
 struct LaunchOptions;
 // the tree of a launch (include/mfa_tree.h; none: MFA_OK): it needs causal, a window of 0 or at least `rows` keys, at most `rowLimit`
 // rows (0: the launch has its own limit), masks that are bound and 8-byte aligned, and neither a soft cap nor packed rows -- in this order
@@ -82,6 +94,7 @@ struct LaunchOptions {
   const mfa_ragged_rows *ragged = nullptr;   // prefill over packed rows; null: padded
   float softcap = 0.0f;                      // 0: none
   const mfa_attention_tree *tree = nullptr;  // a speculation tree among the new rows; null: the causal rule
+  const mfa_key_split *split = nullptr;      // prefill cut along the keys (include/mfa_split.h); null: the launch of the other headers
   const char *refusal = nullptr;             // a block the family requires is NULL: what entry_check answers
   bool refusalFirst = true;                  // ... before the entry's own arguments are looked at (fp8_: after)
 
@@ -93,6 +106,8 @@ struct LaunchOptions {
   LaunchOptions &ragged_of(const mfa_ragged_rows *block);            // the ragged_ entries: required
   LaunchOptions &capped(float cap) { softcap = cap; return *this; }
   LaunchOptions &tree_of(const mfa_attention_tree *block);           // the tree_ entries: required
+  LaunchOptions &optional_tree(const mfa_attention_tree *block) { tree = block; return *this; }   // the split_ entries: NULL is no tree
+  LaunchOptions &split_of(const mfa_key_split *block);               // the split_ entries: required
 };
 // what an entry answers before its launch is prepared: the options' refusal and `bad`, what is wrong with the entry's own arguments
 // (null: nothing), in the family's order

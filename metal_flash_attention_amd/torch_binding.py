@@ -453,7 +453,7 @@ def _packed_operand(t):
     return t, (int(t.stride(0)) if T > 1 else heads * D, int(t.stride(1)) if heads > 1 else D, 0)
 
 
-def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, softcap, workspace=False, tree=None):
+def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, softcap, workspace=False, tree=None, pieces=None):
     """the launch of a decode or prefill host object over `kw`, on q's device and torch's current stream -> (O, L).  window, sinks -- (sink
     tokens or 0, sink logits or None) -- and softcap: None is none, and anything else reaches the entries of its header, a window 0 and
     sinks (0, None) too.  (Rows the launch does not own -- past q_lengths[b], or packed rows of no sequence -- are not written: no memset
@@ -466,6 +466,8 @@ def _attend(host, q, k_cache, v_cache, l_shape, kw, window, sinks, softcap, work
         kw["softcap"] = float(softcap)
     if tree is not None:   # [R] or [B, R] int64 on the GPU: the entries of include/mfa_tree.h
         kw["treeMasks"], kw["treeBatchStride"] = tree, int(tree.stride(0)) if tree.dim() == 2 else 0
+    if pieces is not None:   # prefill cut along the keys (0: the host's plan): the entries of include/mfa_split.h
+        kw["pieces"] = int(pieces)
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     l = torch.empty(l_shape, dtype=torch.float32, device=q.device)
     if workspace:
@@ -495,7 +497,8 @@ def _sinks_or_none(sink_tokens, sink_logits):
 
 
 def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window=None, sinks=None, softcap=None,
-                 tree=None):
+                 tree=None, pieces=None):
+    """`pieces`: None is the launch that is not cut along the keys; 0 the host's plan, 2 .. 64 as given -- the workspace is allocated here"""
     who = "flash_prefill"
     fp8, B, kw = _cache_side(who, (q,), k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale)
     if q_lengths is not None:
@@ -505,7 +508,7 @@ def _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, cau
     kw.update(rows=R, heads=H, batches=B, headsPerKeyValue=H // k_cache.shape[1], causal=bool(causal),
               queryLengths=None if q_lengths is None else q_lengths.to(torch.int32))
     return _attend(_host(AttentionPrefill, q.dtype, D, fp8), q, k_cache, v_cache, (B, H, R), kw, window, sinks, softcap,
-                   tree=None if tree is None else _tree_operand(who, tree, B, R))
+                   workspace=pieces is not None, tree=None if tree is None else _tree_operand(who, tree, B, R), pieces=pieces)
 
 
 def _run_prefill_ragged(q, k_cache, v_cache, cache_lengths, row_starts, max_rows, block_table, causal, k_scale, v_scale, window, sinks, softcap=None):
@@ -750,6 +753,15 @@ def _op_prefill_tree(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
                         _sinks_or_none(sink_tokens, sink_logits), None, tree_mask)
 
 
+def _op_prefill_split(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                      q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
+                      k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
+                      sink_logits: Optional[torch.Tensor], tree: Optional[torch.Tensor], key_pieces: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(`tree`: flash_prefill's tree_mask, None for none -- the ops of include/mfa_tree.h alone spell it tree_mask)"""
+    return _run_prefill(q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, window or None,
+                        _sinks_or_none(sink_tokens, sink_logits), None, tree, key_pieces)
+
+
 def _op_prefill_ragged_softcap(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: torch.Tensor,
                                row_starts: torch.Tensor, max_rows: int, block_table: Optional[torch.Tensor], causal: bool,
                                k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor], window: int, sink_tokens: int,
@@ -833,6 +845,7 @@ _CACHE_OPS = [
     ("attention_decode_tree", _op_decode_tree, _fake_padded, ()),
     ("attention_prefill_tree", _op_prefill_tree, _fake_padded, ()),
     ("kv_cache_compact", _op_compact, _fake_lengths, ("k_cache", "v_cache")),
+    ("attention_prefill_split", _op_prefill_split, _fake_padded, ()),
 ]
 _HAVE = {_op[0]: _register_cache_op(*_op) for _op in _CACHE_OPS}   # op name -> whether torch has it as a custom op
 _HAVE_DECODE_OP = _HAVE["attention_decode"]
@@ -844,6 +857,7 @@ _HAVE_RAGGED_OPS = _HAVE["attention_prefill_ragged"] and _HAVE["kv_cache_append_
 _HAVE_SOFTCAP_OPS = _HAVE["attention_decode_softcap"] and _HAVE["attention_prefill_softcap"] and _HAVE["attention_prefill_ragged_softcap"]
 _HAVE_TREE_OPS = _HAVE["attention_decode_tree"] and _HAVE["attention_prefill_tree"]
 _HAVE_COMPACT_OP = _HAVE["kv_cache_compact"]
+_HAVE_SPLIT_OP = _HAVE["attention_prefill_split"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -963,7 +977,7 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                   q_lengths: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None, causal: bool = True,
                   k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None, return_lse: bool = False,
                   window: Optional[int] = None, sink_tokens: Optional[int] = None, sink_logits: Optional[torch.Tensor] = None,
-                  softcap: Optional[float] = None, tree_mask: Optional[torch.Tensor] = None):
+                  softcap: Optional[float] = None, tree_mask: Optional[torch.Tensor] = None, key_pieces: Optional[int] = None):
     """Attention of a BLOCK of new rows of every sequence (q [B, H, R, D], any R: a chunk of a prompt, a reused prefix's tail, a long
     speculative block) against its KV cache, which already holds the new tokens (kv_cache_append first).  cache_lengths [B] (GPU):
     valid keys per sequence INCLUDING the new tokens; q_lengths [B] (GPU, None = R for every sequence): the new rows of sequence b,
@@ -979,8 +993,21 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     L = the head's sink logit.  softcap=cap: logit soft-capping as flash_decode's (include/mfa_softcap.h), with any window and sinks,
     through the op `mfa::attention_prefill_softcap`; None: no cap.  tree_mask=int64 [R] or [B, R]: a speculation tree among the new rows as
     flash_decode's (include/mfa_tree.h; R <= 64, trees of different sizes through q_lengths), through the op `mfa::attention_prefill_tree`;
-    None: the causal rule."""
+    None: the causal rule.  key_pieces=P: the launch CUT ALONG THE KEYS (include/mfa_split.h) -- for few row blocks over a long cache (one
+    sequence, a speculation tree, a short chunk), which unsplit are a handful of workgroups that each walk the whole cache: 0 lets the host
+    plan the pieces from the shapes, 2 .. 64 forces them, 1 is the unsplit launch; the workspace is allocated here.  With any window, sinks
+    and tree_mask, not with softcap; through the op `mfa::attention_prefill_split`.  None: the launch is not cut, as before."""
     _forward_only("flash_prefill", q, k_cache, v_cache, cache_lengths)
+    if key_pieces is not None:
+        who = "flash_prefill"
+        if softcap is not None:
+            raise ValueError(f"{who}: key_pieces and softcap together have no kernel (include/mfa_split.h)")
+        if isinstance(key_pieces, bool) or not isinstance(key_pieces, int) or not 0 <= key_pieces <= 64:
+            raise ValueError(f"{who}: key_pieces must be an int from 0 (the host's plan) to 64 (None: the launch is not cut along the keys), not {key_pieces!r}")
+        _op, own = _route(_PREFILL, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, None, tree_mask)   # (the checks)
+        o, l = _call_op(_HAVE_SPLIT_OP, "attention_prefill_split", q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale,
+                        window or 0, sink_tokens or 0, sink_logits, tree_mask, key_pieces)
+        return (o, l * _LN2) if return_lse else o
     op, own = _route(_PREFILL, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap, tree_mask)
     o, l = _call_op(_HAVE[op], op, q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, *own)
     return (o, l * _LN2) if return_lse else o
