@@ -311,17 +311,12 @@ class mfa_key_split(ctypes.Structure):   # include/mfa_split.h
 
 _SPLIT = ctypes.POINTER(mfa_key_split)
 MFA_PREFILL_SPLIT_MAX_PIECES, MFA_PREFILL_SPLIT_MIN_TILES, MFA_PREFILL_SPLIT_COMPUTE_UNITS = 64, 8, 256
-_SPLIT_OWN = [ctypes.c_uint32, _SINKS, _TREE, _SPLIT]   # window (0 = none), sinks (NULL = none), tree (NULL = none), split (required)
 
-SPLIT_SYMBOLS = [   # include/mfa_split.h: prefill cut along the keys -- one family of entries with `split` (required) after `tree`, written out
-    # here: it owns a window, sinks AND a tree, which no family of CACHE_FAMILIES does, and its workspace_size has a second result
+SPLIT_SYMBOLS = [   # include/mfa_split.h: prefill cut along the keys -- `split` (required) after `tree` (NULL = none): the tree family plus an argument
+    # + its mfa_attention_*_{launch,launch_form,time} rows and, this family's alone, workspace_size with its second result: the CACHE_FAMILIES loop below
     ("mfa_key_split_init", None, [_SPLIT]),
     ("mfa_key_split_size", ctypes.c_size_t, []),
     ("mfa_key_split_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
-    ("mfa_attention_prefill_split_launch", ctypes.c_int, _DECODE_BUFS + [_PREFILL] + _SPLIT_OWN + [ctypes.c_void_p]),
-    ("mfa_attention_prefill_split_launch_form", ctypes.c_int, [_PREFILL] + _SPLIT_OWN + [ctypes.c_char_p, ctypes.c_size_t]),
-    ("mfa_attention_prefill_split_time", ctypes.c_int, _DECODE_BUFS + [_PREFILL] + _SPLIT_OWN + [ctypes.c_void_p] + _TIMING),
-    ("mfa_attention_prefill_split_workspace_size", ctypes.c_int, [_PREFILL] + _SPLIT_OWN + [ctypes.POINTER(ctypes.c_uint64), _U32P]),
     ("mfa_attention_prefill_split_piece_range", ctypes.c_int, [ctypes.c_uint32] * 5 + [ctypes.POINTER(_U32x2), ctypes.POINTER(_U32x2)]),
 ]
 
@@ -350,19 +345,21 @@ COMPACT_SYMBOLS = [   # include/mfa_compact.h: the accepted path of a speculatio
 # ---- the laddered entries of the launches over a KV cache, described once:
 #     mfa_attention_<launch>_<family><verb>(*<the verb's head>, params, *<the options the family owns>, *<the verb's tail>)
 # CACHE_FAMILIES: launch -> family -> the options its entries take, in the order of their signatures (each family is an earlier one plus an
-# argument; attention._route picks the first that owns every option a call gives).  CACHE_VERBS: launch -> verb -> (head, tail).
+# argument; attention._route picks the first that owns every option a call gives).  CACHE_VERBS: launch -> verb -> (head, tail);
+# CACHE_FAMILY_VERBS: (launch, family) -> the verbs that family alone adds.
 CACHE_OPTION_TYPES = {"quant": _QUANT, "window": ctypes.c_uint32, "sinks": _SINKS, "ragged": _RAGGED, "softcap": ctypes.c_float,
-                      "tree": _TREE}
+                      "tree": _TREE, "split": _SPLIT}
 CACHE_FAMILIES = {
     "decode": {"": (), "fp8_": ("quant",), "window_": ("quant", "window"), "sink_": ("quant", "window", "sinks"),
                "softcap_": ("quant", "window", "sinks", "softcap"), "tree_": ("quant", "window", "sinks", "tree")},
     "prefill": {"": (), "window_": ("window",), "sink_": ("window", "sinks"), "ragged_": ("window", "sinks", "ragged"),
                 "softcap_": ("window", "sinks", "softcap"), "ragged_softcap_": ("window", "sinks", "ragged", "softcap"),
-                "tree_": ("window", "sinks", "tree")},
+                "tree_": ("window", "sinks", "tree"), "split_": ("window", "sinks", "tree", "split")},
 }
 _VERBS = {"workspace_size": ([], [ctypes.POINTER(ctypes.c_uint64)]), "launch": (_DECODE_BUFS, [ctypes.c_void_p]),
           "launch_form": ([], [ctypes.c_char_p, ctypes.c_size_t]), "time": (_DECODE_BUFS, [ctypes.c_void_p] + _TIMING)}
 CACHE_VERBS = {"decode": _VERBS, "prefill": {verb: _VERBS[verb] for verb in ("launch", "launch_form", "time")}}
+CACHE_FAMILY_VERBS = {("prefill", "split_"): {"workspace_size": ([], [ctypes.POINTER(ctypes.c_uint64), _U32P])}}   # (bytes, pieces)
 _CACHE_PARAMS = {"decode": _DECODE, "prefill": _PREFILL}
 
 # (the list of the header that declares each family's entries)
@@ -371,10 +368,10 @@ for _symbols, _launch, _family in ((DECODE_SYMBOLS, "decode", ""), (KVCACHE_SYMB
                                    (SINK_SYMBOLS, "decode", "sink_"), (SINK_SYMBOLS, "prefill", "sink_"), (RAGGED_SYMBOLS, "prefill", "ragged_"),
                                    (SOFTCAP_SYMBOLS, "decode", "softcap_"), (SOFTCAP_SYMBOLS, "prefill", "softcap_"),
                                    (SOFTCAP_SYMBOLS, "prefill", "ragged_softcap_"), (TREE_SYMBOLS, "decode", "tree_"),
-                                   (TREE_SYMBOLS, "prefill", "tree_")):
+                                   (TREE_SYMBOLS, "prefill", "tree_"), (SPLIT_SYMBOLS, "prefill", "split_")):
     _own = [CACHE_OPTION_TYPES[option] for option in CACHE_FAMILIES[_launch][_family]]
     _symbols += [(f"mfa_attention_{_launch}_{_family}{verb}", ctypes.c_int, head + [_CACHE_PARAMS[_launch]] + _own + tail)
-                 for verb, (head, tail) in CACHE_VERBS[_launch].items()]
+                 for verb, (head, tail) in dict(CACHE_VERBS[_launch], **CACHE_FAMILY_VERBS.get((_launch, _family), {})).items()]
 
 SYMBOLS = [
     ("mfa_precision_name", ctypes.c_char_p, [ctypes.c_int]),

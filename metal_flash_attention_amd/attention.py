@@ -489,7 +489,7 @@ def _fill_shared(p, D, operands, packed, *, rows, column, heads, batches, cacheL
         p.pageStride[0], p.pageStride[1] = int(pageStrides[0]), int(pageStrides[1])
 
 
-_OPTIONS = tuple(_abi.CACHE_OPTION_TYPES)   # quant, window, sinks, ragged, softcap, tree: the order every family's signature keeps
+_OPTIONS = tuple(_abi.CACHE_OPTION_TYPES)   # quant, window, sinks, ragged, softcap, tree, split: the order every family's signature keeps
 
 
 def _routes(launch):
@@ -507,17 +507,22 @@ def _routes(launch):
     return table
 
 
-def _route(routes, quant, window, sinks, ragged, softcap, tree=None):
+def _route(routes, quant, window, sinks, ragged, softcap, tree=None, split=None):
     """The entries a launch's options reach (`routes`: _routes of the launch) -> (their name up to the verb, the arguments the family owns).
     Each option is its ctypes argument, or None when the keywords leave it out (window: a number; a window that IS given may be 0).  An
     option that is given needs a family that owns it: a cap wins over all, ragged over window and sinks, either sink keyword reaches the
     sink entries, a window -- 0 too -- the window entries, an e4m3 decode with nothing else fp8_; a tree reaches the tree entries, which
-    own neither a cap nor ragged rows.  What the family owns beyond the given options is passed as none: window 0, a NULL block"""
+    own neither a cap nor ragged rows; a split block (prefill's workspace= / pieces=) reaches the split entries, which own a window, sinks
+    and a tree and neither of those two either.  What the family owns beyond the given options is passed as none: window 0, a NULL block"""
+    if split is not None and (softcap is not None or ragged is not None):   # (no split kernel and no entry: said here)
+        raise ValueError("a key split (workspace= / pieces=) goes with neither " + ("softcap=" if softcap is not None else "rowStarts= / totalRows=") +
+                         ": a soft cap or ragged rows together with a split have no kernel (include/mfa_split.h)")
     if tree is not None and (softcap is not None or ragged is not None):   # (no family owns both: said here, not by the table's KeyError)
         raise ValueError("a speculation tree (treeMasks=) goes with neither " + ("softcap=" if softcap is not None else "rowStarts= / totalRows=") +
                          ": a soft cap or ragged rows together with a tree have no kernel (include/mfa_tree.h)")
-    entries, owned = routes[(quant is not None, window is not None, sinks is not None, ragged is not None, softcap is not None, tree is not None)]
-    return entries, itertools.compress((quant, int(window or 0), sinks, ragged, softcap, tree), owned) if owned else ()
+    given = (quant, window, sinks, ragged, softcap, tree, split)
+    entries, owned = routes[tuple(option is not None for option in given)]
+    return entries, itertools.compress((quant, int(window or 0)) + given[2:], owned) if owned else ()
 
 
 class _CacheAttention:
@@ -538,19 +543,12 @@ class _CacheAttention:
         cap = _softcap(shape) if "softcap" in shape else None
         ragged = _ragged_block(shape) if self.LAUNCH == "prefill" and ("rowStarts" in shape or "totalRows" in shape) else None
         tree = _tree_block(shape) if "treeMasks" in shape or "treeBatchStride" in shape else None
+        # (prefill's workspace= / pieces=: the launch cut along the keys, include/mfa_split.h; decode's workspace is part of its params)
+        split = _split_block(shape) if self.LAUNCH == "prefill" and ("workspace" in shape or "pieces" in shape) else None
         quant, _scales = self._quant(shape)
-        if self.LAUNCH == "prefill" and ("workspace" in shape or "pieces" in shape):   # cut along the keys: the entries of include/mfa_split.h
-            split = _split_block(shape)
-            if cap is not None or ragged is not None:   # (no split kernel and no entry: said here)
-                raise ValueError("a key split (workspace= / pieces=) goes with neither " + ("softcap=" if cap is not None else "rowStarts= / totalRows=") +
-                                 ": a soft cap or ragged rows together with a split have no kernel (include/mfa_split.h)")
-            p, _keep = self._params(**shape)
-            own = (int(window or 0), sinks and ctypes.byref(sinks[0]), tree and ctypes.byref(tree[0]), ctypes.byref(split[0]))
-            check(getattr(lib(), "mfa_attention_prefill_split_" + verb)(*head, ctypes.byref(p), *own, *tail))
-            return
         p, _keep = self._params(**shape) if ragged is None else self._params(ragged=ragged, **shape)
         entries, own = _route(self.ROUTES, quant, window, sinks and ctypes.byref(sinks[0]), ragged and ctypes.byref(ragged[0]), cap,
-                              tree and ctypes.byref(tree[0]))
+                              tree and ctypes.byref(tree[0]), split and ctypes.byref(split[0]))
         check(getattr(lib(), entries + verb)(*head, ctypes.byref(p), *own, *tail))
 
     def launchForm(self, **shape) -> str:

@@ -6,7 +6,8 @@
 // those of include/mfa_tree.h (a speculation tree among the new rows: the sink launch's plan again, and attn_decode16t_* / attn_decode8t_*).  One
 // plan serves both: the launch over an e4m3 cache adds its own checks in front of the 16-bit launch's, starts the attn_decode8_*
 // kernels in place of _single / _pieces, and shares the piece count, the workspace formula and the combine kernel.  The refusals of a
-// window and of sinks, and the Sinks of a launch, are cache_launch.h's, shared with attn_prefill16.hip.
+// window and of sinks, the Sinks of a launch and the host side of the cut along the keys (the piece count's formula, the workspace, its
+// check and slabs, the two kernels of a run) are cache_launch.h's, shared with attn_prefill16.hip.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
 
@@ -44,53 +45,40 @@ MFA_DECODE_KERNELS(MFA_DECODE_DECLARE, f16, _Float16, 256)
 
 namespace {
 
-struct DecodeKernel {
-  void (*launch)(const DecodeArgs);
-  const char *name;
-};
+// the families of MFA_DECODE_FAMILIES by their kernels' infix -- F_: plain, F_w: window, F_s: sinks, F_c: soft cap, F_t: tree (both
+// whatever the window and sinks) -- and their count: the kernels' first index, generated from the list that generates the kernels
+#define MFA_DECODE_FAMILY_ID(K, I, ...) F_##I,
+enum Family { MFA_DECODE_FAMILIES(MFA_DECODE_FAMILY_ID, , , , ) FAMILIES };
+typedef CacheKernel<DecodeArgs> DecodeKernel;
 struct DecodeSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  DecodeKernel kernel[5][2][2];   // [0: plain, 1: window, 2: sinks, 3: soft cap, 4: tree][fp8][pieces]
+  DecodeKernel kernel[FAMILIES][2][2];   // [family][fp8][pieces]
   DecodeKernel combine;
 };
-#define MFA_DECODE_ENTRY(NAME) {NAME, #NAME}
 #define MFA_DECODE_SET_FAMILY(K, I, WINDOW, SINK, CAP, TREE, TN, T, D)                                                                     \
-  {{MFA_DECODE_ENTRY(attn_decode16##I##_d##D##_##TN##_single), MFA_DECODE_ENTRY(attn_decode16##I##_d##D##_##TN##_pieces)},            \
-   {MFA_DECODE_ENTRY(attn_decode8##I##_d##D##_##TN##_single), MFA_DECODE_ENTRY(attn_decode8##I##_d##D##_##TN##_pieces)}},
+  {{MFA_CACHE_KERNEL(attn_decode16##I##_d##D##_##TN##_single), MFA_CACHE_KERNEL(attn_decode16##I##_d##D##_##TN##_pieces)},            \
+   {MFA_CACHE_KERNEL(attn_decode8##I##_d##D##_##TN##_single), MFA_CACHE_KERNEL(attn_decode8##I##_d##D##_##TN##_pieces)}},
 #define MFA_DECODE_SET(TN, PREC, D)                                                                                                   \
   {D, PREC, (uint32_t)decode16_lds_bytes<D>(), {MFA_DECODE_FAMILIES(MFA_DECODE_SET_FAMILY, , TN, , D)},                               \
-   MFA_DECODE_ENTRY(attn_decode16_d##D##_##TN##_combine)}
+   MFA_CACHE_KERNEL(attn_decode16_d##D##_##TN##_combine)}
 const DecodeSet kSets[] = {MFA_DECODE_SET(bf16, MFA_BF16, 64), MFA_DECODE_SET(bf16, MFA_BF16, 128), MFA_DECODE_SET(bf16, MFA_BF16, 256),
                            MFA_DECODE_SET(f16, MFA_FP16, 64),  MFA_DECODE_SET(f16, MFA_FP16, 128),  MFA_DECODE_SET(f16, MFA_FP16, 256)};
 
-// Pieces of the keys: chosen from the workgroups the launch has without a split (batches x K/V heads) and `column` only -- the lengths
-// live on the device.  Aims at MFA_DECODE_WORKGROUP_TARGET workgroups (two per compute unit of a 256-CU chip, what choose_splits of
-// mfa_kernel.hip aims at), rounded down; a piece keeps at least four 64-key tiles (two steps for each of the workgroup's four waves).
-// The tile count is planned_tiles' (cache_launch.h, shared with the split prefill launch).
-
-uint32_t choose_pieces(uint64_t blocks, uint64_t tiles) {
-  if (blocks >= MFA_DECODE_WORKGROUP_TARGET) return 1;
-  uint64_t s = MFA_DECODE_WORKGROUP_TARGET / blocks;
-  if (s > tiles / 4) s = tiles / 4;
-  if (s > MFA_DECODE_MAX_PIECES) s = MFA_DECODE_MAX_PIECES;
-  return s < 2 ? 1 : (uint32_t)s;
-}
-
-uint64_t pieces_workspace_bytes(uint32_t pieces, const mfa_decode_params *p) {
-  return (uint64_t)pieces * p->batches * p->heads * p->rows * (p->headDimension + 2) * sizeof(float);
-}
-
+// Pieces of the keys (choose_pieces, cache_launch.h): chosen from the workgroups the launch has without a split (batches x K/V heads) and
+// planned_tiles of `column`.  Aims at MFA_DECODE_WORKGROUP_TARGET workgroups (two per compute unit of a 256-CU chip, what choose_splits
+// of mfa_kernel.hip aims at); a piece keeps at least four 64-key tiles (two steps for each of the workgroup's four waves).
 struct DecodePlan {
   DecodeArgs args;
   const DecodeSet *set;
   bool fp8;
-  int family;           // 0: plain, 1: window, 2: sinks, 3: soft cap, 4: tree (both whatever the window and sinks) -- the kernels' first index
+  Family family;        // the kernels' first index
   uint64_t tiles;       // what the piece count was chosen from
   uint32_t pieces;      // as the launch runs: 1 without a workspace
   uint32_t planned;     // what the host would cut the keys into
   uint32_t blocks;      // batches x K/V heads
+  uint64_t rows;        // batches x query heads x rows: the rows of a workspace slab, a wave of the combine kernel each
   // the kernel that reads the cache; its name is what a HIP failure is reported under
   const DecodeKernel &kernel() const { return set->kernel[family][fp8][pieces > 1]; }
   const char *name() const { return kernel().name; }
@@ -145,43 +133,27 @@ mfa_status DecodePlan::prepare(const mfa_decode_params *p, const LaunchOptions &
   this->set = set;
   fp8 = quant != nullptr;
   blocks = p->batches * (p->heads / G);
-  family = options.tree ? 4 : softcap != 0.0f ? 3 : sinks.any() ? 2 : window != 0;
+  rows = (uint64_t)p->batches * p->heads * p->rows;
+  family = options.tree ? F_t : softcap != 0.0f ? F_c : sinks.any() ? F_s : window != 0 ? F_w : F_;
   tiles = planned_tiles(p->column, p->rows, window, sinks.tokens);
-  planned = choose_pieces(blocks, tiles);
+  planned = choose_pieces(blocks, tiles, MFA_DECODE_WORKGROUP_TARGET, 4, MFA_DECODE_MAX_PIECES);
   pieces = planned;
   if (!p->workspace) pieces = 1;   // no workspace: one kernel, unsplit
   if (pieces > 1) {
-    const uint64_t need = pieces_workspace_bytes(pieces, p);
-    if (p->workspaceBytes < need)
-      return fail(MFA_ERR_INVALID_ARGUMENT, "workspace too small: " + std::to_string(p->workspaceBytes) + " bytes, the launch needs " +
-                                                std::to_string(need) + " (mfa_attention_decode_workspace_size)");
-    if ((uintptr_t)p->workspace % 16 != 0) return fail(MFA_ERR_INVALID_ARGUMENT, "workspace must be 16-byte aligned");
+    st = check_split_workspace(p->workspace, p->workspaceBytes, split_workspace_bytes(pieces, rows, set->D), "mfa_attention_decode_workspace_size");
+    if (st != MFA_OK) return st;
   }
   DecodeArgs &a = args;
   set_shared_args(a, p, G, pageShift, options);
   a.R = p->rows; a.Hq = p->heads;
   a.pieces = pieces;
-  if (pieces > 1) {
-    a.wsO = (float *)p->workspace;
-    a.wsML = a.wsO + (uint64_t)pieces * p->batches * p->heads * p->rows * p->headDimension;
-  }
+  if (pieces > 1) set_split_slabs(a, p->workspace, pieces, rows, set->D);
   if (quant) { a.keyScale = quant->keyScale; a.valueScale = quant->valueScale; }
   return MFA_OK;
 }
 
 hipError_t DecodePlan::run(hipStream_t stream) const {
-  const DecodeSet &s = *set;
-  hipError_t err;
-  if (pieces > 1) {
-    err = launch_kernel(kernel().launch, dim3(blocks * pieces), dim3(256), s.lds, stream, args);
-    if (err != hipSuccess) return err;
-    const uint64_t rows = (uint64_t)args.batches * args.Hq * args.R;
-    err = launch_kernel(s.combine.launch, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, stream, args);
-  } else {
-    err = launch_kernel(kernel().launch, dim3(blocks), dim3(256), s.lds, stream, args);
-  }
-  if (err != hipSuccess) return err;
-  return hipGetLastError();
+  return run_pieces(kernel(), blocks, pieces, set->lds, set->combine, rows, stream, args);
 }
 
 // the bytes of the workspace the launch would split into: 0 for an unsplit plan, whatever workspace the caller may already have bound
@@ -196,7 +168,7 @@ mfa_status decode_workspace_size(const mfa_decode_params *params, const LaunchOp
   DecodePlan plan;
   const mfa_status st = plan.prepare(&probe, options);
   if (st != MFA_OK) return st;
-  if (plan.planned > 1) *bytes = pieces_workspace_bytes(plan.planned, params);
+  if (plan.planned > 1) *bytes = split_workspace_bytes(plan.planned, plan.rows, plan.set->D);
   return MFA_OK;
 }
 
@@ -222,7 +194,7 @@ mfa_status decode_launch_form(const mfa_decode_params *params, const LaunchOptio
   if (plan.pieces > 1)
     std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x K/V heads x %u pieces, %u packed rows, %s) + %s (grid %llu)", plan.name(),
                   plan.blocks * plan.pieces, plan.blocks, plan.pieces, M, layout.c_str(), plan.set->combine.name,
-                  (unsigned long long)(((uint64_t)plan.args.batches * plan.args.Hq * plan.args.R + 3) / 4));
+                  (unsigned long long)combine_grid(plan.rows));
   else
     std::snprintf(text, sizeof(text), "%s (grid %u sequences x K/V heads, %u packed rows, %s%s)", plan.name(), plan.blocks, M, layout.c_str(),
                   plan.planned > 1 ? (", unsplit without a workspace: the plan has " + std::to_string(plan.planned) + " pieces").c_str() : "");

@@ -4,7 +4,8 @@
 // those of include/mfa_softcap.h (a soft cap on the scores: attn_prefill16c_*, over packed rows attn_prefill16rc_*) and those of
 // include/mfa_tree.h (a speculation tree among the new rows: attn_prefill16t_*) and those of include/mfa_split.h (the launch cut along
 // the keys: attn_prefill16sk_* / attn_prefill16tk_* and the combine kernels attn_prefill16_combine_*).
-// The refusals of a window and of sinks, and the Sinks of a launch, are cache_launch.h's, shared with attn_decode16.hip.
+// The refusals of a window and of sinks, the Sinks of a launch and the host side of the cut along the keys (the piece count's formula, the
+// workspace, its check and slabs, the two kernels of a run) are cache_launch.h's, shared with attn_decode16.hip.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
 
@@ -49,24 +50,24 @@ MFA_PREFILL_COMBINE_DECLARE(f16, _Float16, 256)
 
 namespace {
 
-struct PrefillKernel {
-  void (*launch)(const PrefillArgs);
-  const char *name;
-};
+// the families of MFA_PREFILL_FAMILIES by their kernels' infix -- F_: plain, F_w: window, F_s: sinks, F_r: ragged, F_c / F_rc: padded /
+// ragged with a soft cap, F_t: tree, F_sk / F_tk: sinks / tree cut along the keys -- and their count: the kernels' first index, generated
+// from the list that generates the kernels
+#define MFA_PREFILL_FAMILY_ID(K, I, ...) F_##I,
+enum Family { MFA_PREFILL_FAMILIES(MFA_PREFILL_FAMILY_ID, , , , ) FAMILIES };
+typedef CacheKernel<PrefillArgs> PrefillKernel;
 struct PrefillSet {
   uint32_t D;
   int precision;
   uint32_t lds;
-  PrefillKernel kernel[9][2];   // [0: plain, 1: window, 2: sinks, 3: ragged, 4: soft cap, 5: ragged with a soft cap, 6: tree,
-                                //  7: sinks cut along the keys, 8: tree cut along the keys][e4m3]
-  PrefillKernel combine;        // merges the pieces of families 7 and 8
+  PrefillKernel kernel[FAMILIES][2];   // [family][e4m3]
+  PrefillKernel combine;               // merges the pieces of F_sk and F_tk
 };
-#define MFA_PREFILL_ENTRY(NAME) {NAME, #NAME}
 #define MFA_PREFILL_SET_FAMILY(K, I, WINDOW, SINK, RAGGED, CAP, TREE, SPLIT, TN, T, D)                                                          \
-  {MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN), MFA_PREFILL_ENTRY(attn_prefill16##I##_d##D##_##TN##_e4m3)},
+  {MFA_CACHE_KERNEL(attn_prefill16##I##_d##D##_##TN), MFA_CACHE_KERNEL(attn_prefill16##I##_d##D##_##TN##_e4m3)},
 #define MFA_PREFILL_SET(TN, PREC, D)                                                                                                  \
   {D, PREC, (uint32_t)prefill16_lds_bytes<D>(), {MFA_PREFILL_FAMILIES(MFA_PREFILL_SET_FAMILY, , TN, , D)},                            \
-   MFA_PREFILL_ENTRY(attn_prefill16_combine_d##D##_##TN)}
+   MFA_CACHE_KERNEL(attn_prefill16_combine_d##D##_##TN)}
 const PrefillSet kSets[] = {MFA_PREFILL_SET(bf16, MFA_BF16, 64), MFA_PREFILL_SET(bf16, MFA_BF16, 128), MFA_PREFILL_SET(bf16, MFA_BF16, 256),
                             MFA_PREFILL_SET(f16, MFA_FP16, 64),  MFA_PREFILL_SET(f16, MFA_FP16, 128),  MFA_PREFILL_SET(f16, MFA_FP16, 256)};
 
@@ -76,33 +77,19 @@ uint64_t ragged_slots(uint32_t totalRows, uint32_t batches, uint32_t rows, uint3
   return tight < padded ? tight : padded;
 }
 
-// Pieces of the keys (include/mfa_split.h): chosen from the workgroups the launch has without a split and the tiles a sequence can walk
-// (planned_tiles, cache_launch.h) only -- the lengths live on the device.  Aims at MFA_PREFILL_SPLIT_COMPUTE_UNITS x the workgroups per
-// compute unit the kernel's LDS allows (2 at D <= 128, 1 at D = 256), rounded down; a piece keeps at least MFA_PREFILL_SPLIT_MIN_TILES.
-uint32_t choose_prefill_pieces(uint64_t blocks, uint64_t tiles, uint32_t D) {
-  const uint64_t target = (uint64_t)MFA_PREFILL_SPLIT_COMPUTE_UNITS * (D == 256 ? 1 : 2);
-  if (blocks >= target) return 1;
-  uint64_t s = target / blocks;
-  if (s > tiles / MFA_PREFILL_SPLIT_MIN_TILES) s = tiles / MFA_PREFILL_SPLIT_MIN_TILES;
-  if (s > MFA_PREFILL_SPLIT_MAX_PIECES) s = MFA_PREFILL_SPLIT_MAX_PIECES;
-  return s < 2 ? 1 : (uint32_t)s;
-}
-
-uint64_t prefill_workspace_bytes(uint32_t pieces, const mfa_prefill_params *p) {
-  return (uint64_t)pieces * p->batches * p->heads * p->rows * (p->headDimension + 2) * sizeof(float);
-}
-
+// Pieces of the keys (include/mfa_split.h; choose_pieces, cache_launch.h): chosen from the workgroups the launch has without a split and
+// planned_tiles.  Aims at MFA_PREFILL_SPLIT_COMPUTE_UNITS x the workgroups per compute unit the kernel's LDS allows (2 at D <= 128, 1 at
+// D = 256); a piece keeps at least MFA_PREFILL_SPLIT_MIN_TILES.
 struct PrefillPlan {
   PrefillArgs args;
   const PrefillSet *set;
   bool fp8;
-  int family;        // 0: plain, 1: window, 2: sinks, 3: ragged, 4 / 5: padded / ragged with a soft cap, 6: tree, 7 / 8: sinks / tree cut
-                     // along the keys -- the kernels' first index
+  Family family;     // the kernels' first index
   uint32_t blocks;   // batches x K/V heads x row blocks; ragged: slots x K/V heads
   uint32_t pieces;   // as the launch runs: 1 without a split block, without a workspace, or when one piece is asked for or planned
   uint32_t planned;  // what the split block asks for (pieces = 0: the host's plan); 1 without one
+  uint64_t rows;     // batches x heads x rows: the rows of a workspace slab, a wave of the combine kernel each
   const PrefillKernel &kernel() const { return set->kernel[family][fp8]; }
-  uint32_t combine_blocks() const { return (uint32_t)(((uint64_t)args.batches * args.heads * args.rows + 3) / 4); }   // a wave per row
   const char *name() const { return kernel().name; }
   mfa_status prepare(const mfa_prefill_params *p, const LaunchOptions &options);
   hipError_t run(hipStream_t stream) const;
@@ -169,29 +156,29 @@ mfa_status PrefillPlan::prepare(const mfa_prefill_params *p, const LaunchOptions
   } else if (blocks > 0x7fffffffull)
     return fail(MFA_ERR_UNSUPPORTED, "batches x K/V heads x row blocks = " + std::to_string(blocks) + " workgroups exceed one grid (2^31 - 1)");
   this->set = set;
-  family = options.tree ? 6 : options.softcap != 0.0f ? (ragged ? 5 : 4) : ragged ? 3 : options.sinks.any() ? 2 : options.window != 0;
+  family = options.tree ? F_t : options.softcap != 0.0f ? (ragged ? F_rc : F_c) : ragged ? F_r : options.sinks.any() ? F_s : options.window != 0 ? F_w : F_;
   this->blocks = (uint32_t)blocks;
+  rows = (uint64_t)p->batches * p->heads * p->rows;
   planned = pieces = 1;
   if (split) {
-    planned = split->pieces ? split->pieces : choose_prefill_pieces(blocks, planned_tiles(p->column, p->rows, options.window, options.sinks.tokens), set->D);
+    planned = split->pieces ? split->pieces
+                            : choose_pieces(blocks, planned_tiles(p->column, p->rows, options.window, options.sinks.tokens),
+                                            (uint64_t)MFA_PREFILL_SPLIT_COMPUTE_UNITS * (set->D == 256 ? 1 : 2), MFA_PREFILL_SPLIT_MIN_TILES,
+                                            MFA_PREFILL_SPLIT_MAX_PIECES);
     pieces = split->workspace ? planned : 1;   // no workspace: one kernel, unsplit
     if (pieces > 1) {
-      const uint64_t need = prefill_workspace_bytes(pieces, p);
-      if (split->workspaceBytes < need)
-        return fail(MFA_ERR_INVALID_ARGUMENT, "workspace too small: " + std::to_string(split->workspaceBytes) + " bytes, the launch needs " +
-                                                  std::to_string(need) + " (mfa_attention_prefill_split_workspace_size)");
-      if ((uintptr_t)split->workspace % 16 != 0) return fail(MFA_ERR_INVALID_ARGUMENT, "workspace must be 16-byte aligned");
+      st = check_split_workspace(split->workspace, split->workspaceBytes, split_workspace_bytes(pieces, rows, set->D), "mfa_attention_prefill_split_workspace_size");
+      if (st != MFA_OK) return st;
       if (blocks * pieces > 0x7fffffffull)
         return fail(MFA_ERR_UNSUPPORTED, "batches x K/V heads x row blocks x pieces = " + std::to_string(blocks * pieces) + " workgroups exceed one grid (2^31 - 1)");
-      family = options.tree ? 8 : 7;
+      family = options.tree ? F_tk : F_sk;
     }
   }
   PrefillArgs &a = args;
   set_shared_args(a, p, G, pageShift, options);
   if (pieces > 1) {
-    a.pieces = pieces; a.heads = p->heads;
-    a.wsO = (float *)split->workspace;
-    a.wsML = a.wsO + (uint64_t)pieces * p->batches * p->heads * p->rows * p->headDimension;
+    a.heads = p->heads;
+    set_split_slabs(a, split->workspace, pieces, rows, set->D);
   }
   a.qlengths = p->queryLengths;
   a.keyScale = fp8 ? p->keyScale : nullptr;
@@ -205,15 +192,9 @@ mfa_status PrefillPlan::prepare(const mfa_prefill_params *p, const LaunchOptions
   return MFA_OK;
 }
 
-// (split: two kernels on the caller's stream, the pieces and their merge; nothing synchronises)
 hipError_t PrefillPlan::run(hipStream_t stream) const {
-  hipError_t err = launch_kernel(kernel().launch, dim3(blocks * pieces), dim3(PF_THREADS), set->lds, stream, args);
-  if (err != hipSuccess) return err;
-  if (pieces > 1) {
-    err = launch_kernel(set->combine.launch, dim3(combine_blocks()), dim3(256), 0, stream, args);
-    if (err != hipSuccess) return err;
-  }
-  return hipGetLastError();
+  static_assert(PF_THREADS == 256, "run_pieces starts workgroups of 256 threads");
+  return run_pieces(kernel(), blocks, pieces, set->lds, set->combine, rows, stream, args);
 }
 
 mfa_status prefill_launch_form(const mfa_prefill_params *params, const LaunchOptions &options, char *out, size_t capacity) {
@@ -237,7 +218,7 @@ mfa_status prefill_launch_form(const mfa_prefill_params *params, const LaunchOpt
   else if (plan.pieces > 1)
     std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads x %u pieces%s, %s%s) + %s (grid %u)",
                   plan.name(), plan.blocks * plan.pieces, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, plan.pieces,
-                  options.split->pieces ? " as given" : "", a.paged ? "paged" : "contiguous", tail.c_str(), plan.set->combine.name, plan.combine_blocks());
+                  options.split->pieces ? " as given" : "", a.paged ? "paged" : "contiguous", tail.c_str(), plan.set->combine.name, (uint32_t)combine_grid(plan.rows));
   else
     std::snprintf(text, sizeof(text), "%s (grid %u = %u sequences x %u K/V heads x %u row blocks of %u rows x %u heads, %s%s%s)", plan.name(),
                   plan.blocks, a.batches, a.Hkv, a.rowBlocks, a.RB, a.G, a.paged ? "paged" : "contiguous", tail.c_str(),
@@ -261,7 +242,7 @@ mfa_status prefill_split_workspace_size(const mfa_prefill_params *params, const 
   PrefillPlan plan;
   const mfa_status st = plan.prepare(params, probed);
   if (st != MFA_OK) return st;
-  if (plan.planned > 1) *bytes = prefill_workspace_bytes(plan.planned, params);
+  if (plan.planned > 1) *bytes = split_workspace_bytes(plan.planned, plan.rows, plan.set->D);
   if (pieces) *pieces = plan.planned;
   return MFA_OK;
 }

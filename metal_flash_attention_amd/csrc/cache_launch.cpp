@@ -81,6 +81,22 @@ mfa_status check_cache_precision(uint32_t cachePrecision, bool *fp8) {
   return MFA_OK;
 }
 
+uint32_t choose_pieces(uint64_t blocks, uint64_t tiles, uint64_t target, uint64_t minTiles, uint64_t maxPieces) {
+  if (blocks >= target) return 1;
+  uint64_t s = target / blocks;
+  if (s > tiles / minTiles) s = tiles / minTiles;
+  if (s > maxPieces) s = maxPieces;
+  return s < 2 ? 1 : (uint32_t)s;
+}
+
+mfa_status check_split_workspace(const void *workspace, uint64_t bytes, uint64_t need, const char *sizeEntry) {
+  if (bytes < need)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "workspace too small: " + std::to_string(bytes) + " bytes, the launch needs " + std::to_string(need) +
+                                              " (" + sizeEntry + ")");
+  if ((uintptr_t)workspace % 16 != 0) return fail(MFA_ERR_INVALID_ARGUMENT, "workspace must be 16-byte aligned");
+  return MFA_OK;
+}
+
 mfa_status check_buffers(std::initializer_list<const void *> buffers, const char *names) {
   for (const void *b : buffers)
     if (!b) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");

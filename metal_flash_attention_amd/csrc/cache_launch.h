@@ -2,8 +2,9 @@
 // kv_cache_append.hip, kv_cache_compact.hip): the checks of paging, operand strides, cache precision and buffer pointers, and of a sliding window and
 // attention sinks (Sinks, check_window_and_sinks: decode and prefill), of a soft cap (check_softcap) and of a speculation tree
 // (check_tree), each with ONE wording, so that the same mistake is refused in the same words whichever launch meets it; the options of a launch as one value (LaunchOptions), and the
-// path every decode and prefill entry takes from it: the checks both launches word alike (check_precisions ... check_cache_and_strides), bind, and the bodies
-// of the launch and time entries (cache_launch, cache_time).  hip_fail, copy_text and time_launches also serve mfa_kernel.hip.
+// path every decode and prefill entry takes from it: the checks both launches word alike (check_precisions ... check_cache_and_strides), bind, the
+// launch cut along the keys (choose_pieces ... run_pieces: the piece count, the workspace and its check, the slabs, the two kernels of a
+// run) and the bodies of the launch and time entries (cache_launch, cache_time).  hip_fail, copy_text and time_launches also serve mfa_kernel.hip.
 // Internal, not part of the ABI.  Every check records its message (fail, mfa_internal.h) and returns the status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +20,7 @@
 #include "../../include/mfa_sink.h"
 #include "../../include/mfa_split.h"
 #include "../../include/mfa_tree.h"
+#include "launchers.h"
 #include "mfa_internal.h"
 
 namespace mfa {
@@ -183,6 +185,40 @@ mfa_status bind(Plan *plan, const void *q, const void *k, const void *v, void *o
   plan->args.q = (const char *)q; plan->args.k = (const char *)k; plan->args.v = (const char *)v;
   plan->args.o = (char *)o; plan->args.l = l;
   return MFA_OK;
+}
+
+// ---- The launch cut along the keys, as DecodePlan and PrefillPlan (include/mfa_split.h) run it: every block's keys go to `pieces`
+// workgroups that publish un-normalised O and (m, l) in FP32 to the caller's workspace -- wsO [pieces][rows][D], then wsML
+// [pieces][rows][2], rows = batches x query heads x rows -- and a combine kernel, one wave per row, merges them.
+
+// a kernel of a plan's table: the function and its name, which a launch form and a HIP failure are reported under
+template <typename Args> struct CacheKernel {
+  void (*launch)(const Args);
+  const char *name;
+};
+#define MFA_CACHE_KERNEL(NAME) {NAME, #NAME}
+
+// The piece count, from the workgroups the launch has without a split and planned_tiles only -- the lengths live on the device.  Aims
+// at `target` workgroups, rounded down; a piece keeps at least `minTiles` tiles; at most `maxPieces`; below 2: 1.
+uint32_t choose_pieces(uint64_t blocks, uint64_t tiles, uint64_t target, uint64_t minTiles, uint64_t maxPieces);
+// the project's one workspace formula, in bytes
+inline uint64_t split_workspace_bytes(uint32_t pieces, uint64_t rows, uint32_t D) { return (uint64_t)pieces * rows * (D + 2) * sizeof(float); }
+// the workspace of a launch in more than one piece: at least `need` bytes -- `sizeEntry` is the entry that says how many -- and 16-byte aligned
+mfa_status check_split_workspace(const void *workspace, uint64_t bytes, uint64_t need, const char *sizeEntry);
+template <typename Args> void set_split_slabs(Args &a, void *workspace, uint32_t pieces, uint64_t rows, uint32_t D) {
+  a.pieces = pieces;
+  a.wsO = (float *)workspace;
+  a.wsML = a.wsO + (uint64_t)pieces * rows * D;
+}
+inline uint64_t combine_grid(uint64_t rows) { return (rows + 3) / 4; }   // a wave per row, four to a workgroup
+// the body of a plan's run(): the kernel that reads the cache on blocks x pieces workgroups, then -- more than one piece -- the combine
+// kernel over the slabs' `rows`, both on the caller's stream; nothing synchronises
+template <typename Args>
+hipError_t run_pieces(const CacheKernel<Args> &kernel, uint32_t blocks, uint32_t pieces, uint32_t lds, const CacheKernel<Args> &combine,
+                      uint64_t rows, hipStream_t stream, const Args &args) {
+  hipError_t err = launch_kernel(kernel.launch, dim3(blocks * pieces), dim3(256), lds, stream, args);
+  if (err == hipSuccess && pieces > 1) err = launch_kernel(combine.launch, dim3((uint32_t)combine_grid(rows)), dim3(256), 0, stream, args);
+  return err != hipSuccess ? err : hipGetLastError();
 }
 
 // Times `iterations` calls of run(stream) between two events, after `warmup` untimed ones; nothing more is started after a call that

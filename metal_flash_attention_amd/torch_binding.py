@@ -343,6 +343,8 @@ def _host(cls, dtype, D, fp8):
         precision = P.BF16 if dtype == torch.bfloat16 else P.FP16
         if cls is AttentionDecode:
             host = (AttentionDecodeFP8 if fp8 else AttentionDecode)(D, precision)
+        elif cls is KVCacheCompact:   # (no new rows: the cache's own type is all it takes)
+            host = cls(D, KVCachePrecision.E4M3 if fp8 else precision)
         else:
             host = cls(D, precision, cachePrecision=KVCachePrecision.E4M3 if fp8 else None)
         _HOSTS[key] = host
@@ -378,12 +380,38 @@ def _check_lengths(who, name, t, batches, tail=""):
                          f"(got {tuple(t.shape)}, {t.dtype})")
 
 
+def _cache_layout(who, k_cache, v_cache, block_table, B, write):
+    """The caches [B or pages, Hkv, keys, D] of a launch over `B` sequences as they lie, checked -- a contiguous last dimension, the block
+    table -- and described -> keywords of a host class's dispatch: the paging, `column`, and `strides` with the caches' entries.  `write`:
+    the launch writes the cache (append, compact) -- the words and the operand names say so, and the block table is handed over contiguous
+    with its width as the stride, the bound on the pages a sequence may name."""
+    paged = block_table is not None
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
+            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is "
+                             f"{'written where it lies' if write else 'never copied'})")
+    kw = {}
+    if paged:
+        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
+                not block_table.is_cuda:
+            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
+                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
+        kw.update(pageSize=int(k_cache.shape[2]), blockTable=block_table.contiguous() if write else block_table,
+                  blockTableStride=int(block_table.shape[1] if write else block_table.stride(0)),
+                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
+    if not (write and paged):   # (a paged write takes no column: its kernel drops a row whose page lies past the table's row)
+        kw.update(column=int(k_cache.shape[2]) * (int(block_table.shape[1]) if paged else 1))
+    k_name, v_name = ("kCache", "vCache") if write else ("K", "V")
+    kw.update(strides={k_name: _cache_strides(k_cache, paged), v_name: _cache_strides(v_cache, paged)})
+    return kw
+
+
 def _cache_side(who, news, k_cache, v_cache, cache_lengths, block_table, k_scale, v_scale, *, packed=False, write=False, fp8=None):
     """Validates the cache side of a launch against its new operand(s) `news` -- q [B, H, R, D], or k_new and v_new [B, Hkv, R, D]; `packed`:
     [T, H, D], a ragged batch -- and describes it -> (fp8, B, keywords of the host class's dispatch: the lengths, the paging, the scales,
-    `column`, and `strides` with the caches' entries, to which the caller adds its operands').  `write`: the launch writes the cache
-    (append) -- the rows' heads are the caches', the words say so, and the block table is handed over contiguous with its width as the
-    stride, the bound on the pages a sequence may name.  `fp8`: what the caller's op says the caches are (None: what they say)."""
+    `column`, and `strides` with the caches' entries (_cache_layout), to which the caller adds its operands').  `write`: the launch writes
+    the cache (append) -- the rows' heads are the caches' and the words say so.  `fp8`: what the caller's op says the caches are (None:
+    what they say)."""
     new, names = news[0], "k_new, v_new" if write else "q"
     if not all(t.is_cuda for t in (*news, k_cache, v_cache, cache_lengths)):
         raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
@@ -416,25 +444,10 @@ def _cache_side(who, news, k_cache, v_cache, cache_lengths, block_table, k_scale
     else:
         _check_lengths(who, "cache_lengths", cache_lengths, new.shape[0])
     B = int(cache_lengths.shape[0])
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
-            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is "
-                             f"{'written where it lies' if write else 'never copied'})")
-    kw = dict(cacheLengths=cache_lengths.to(torch.int32))   # (no copy when it already is; stays on the device)
-    if paged:
-        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
-                not block_table.is_cuda:
-            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
-                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
-        kw.update(pageSize=int(k_cache.shape[2]), blockTable=block_table.contiguous() if write else block_table,
-                  blockTableStride=int(block_table.shape[1] if write else block_table.stride(0)),
-                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
-    if not (write and paged):   # (a paged append takes no column: its kernel drops a row whose page lies past the table's row)
-        kw.update(column=int(k_cache.shape[2]) * (int(block_table.shape[1]) if paged else 1))
+    kw = _cache_layout(who, k_cache, v_cache, block_table, B, write)
+    kw.update(cacheLengths=cache_lengths.to(torch.int32))   # (no copy when it already is; stays on the device)
     if fp8:
         kw.update(keyScale=_scale_operand(who, "k_scale", k_scale, Hkv, new.device), valueScale=_scale_operand(who, "v_scale", v_scale, Hkv, new.device))
-    k_name, v_name = ("kCache", "vCache") if write else ("K", "V")
-    kw.update(strides={k_name: _cache_strides(k_cache, paged), v_name: _cache_strides(v_cache, paged)})
     return fp8, B, kw
 
 
@@ -573,31 +586,14 @@ def _run_compact(k_cache, v_cache, cache_lengths, accepted, accepted_counts, row
     _check_lengths(who, "accepted_counts", accepted_counts, B)
     if q_lengths is not None:
         _check_lengths(who, "q_lengths", q_lengths, B)
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.stride(3) != 1 or any(st < 0 for st in t.stride()):
-            raise ValueError(f"{who}: {name} must have a contiguous last dimension (a cache is written where it lies)")
+    kw = _cache_layout(who, k_cache, v_cache, block_table, B, True)
     if accepted.stride(0) < accepted.shape[1]:   # (an expanded row: one path shared is given a row per sequence)
         accepted = accepted.contiguous()
-    kw = dict(cacheLengths=cache_lengths.to(torch.int32), acceptedCounts=accepted_counts.to(torch.int32), accepted=accepted,
+    kw.update(cacheLengths=cache_lengths.to(torch.int32), acceptedCounts=accepted_counts.to(torch.int32), accepted=accepted,
               acceptedStride=int(accepted.stride(0)), maxAccepted=int(accepted.shape[1]),
               queryLengths=None if q_lengths is None else q_lengths.to(torch.int32))
-    if paged:
-        if block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1 or \
-                not block_table.is_cuda:
-            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous "
-                             f"last dimension (got {tuple(block_table.shape)}, {block_table.dtype})")
-        table = block_table.contiguous()
-        kw.update(pageSize=int(k_cache.shape[2]), blockTable=table, blockTableStride=int(table.shape[1]),
-                  pageStrides=(int(k_cache.stride(0)), int(v_cache.stride(0))))
-    else:
-        kw.update(column=int(k_cache.shape[2]))
-    kw.update(strides=dict(kCache=_cache_strides(k_cache, paged), vCache=_cache_strides(v_cache, paged)))
     new_lengths = torch.empty((B,), dtype=torch.int32, device=k_cache.device)
-    key = (KVCacheCompact, k_cache.dtype, int(k_cache.shape[3]))
-    host = _HOSTS.get(key)
-    if host is None:
-        precision = {torch.bfloat16: P.BF16, torch.float16: P.FP16}.get(k_cache.dtype, KVCachePrecision.E4M3)
-        host = _HOSTS[key] = KVCacheCompact(int(k_cache.shape[3]), precision)
+    host = _host(KVCacheCompact, k_cache.dtype, int(k_cache.shape[3]), k_cache.dtype == torch.float8_e4m3fn)
     with torch.cuda.device(k_cache.device):
         host.dispatch(k_cache, v_cache, stream=torch.cuda.current_stream(k_cache.device).cuda_stream, rows=rows, heads=int(k_cache.shape[1]),
                       batches=B, newLengths=new_lengths, **kw)
@@ -880,23 +876,30 @@ class _Public:
     """what _route knows of a public function: its name in messages, the op of each rung (none: the function has no such rung and its
     plain op takes the rung's arguments), whether the scales go in front of a rung's arguments (prefill's ops all take them earlier)"""
 
-    def __init__(self, who, plain, fp8=None, window=None, sink=None, softcap=None, scales=False, packed=False, tree=None):
+    def __init__(self, who, plain, fp8=None, window=None, sink=None, softcap=None, scales=False, packed=False, tree=None, split=None):
         self.who, self.plain, self.fp8, self.window, self.sink, self.softcap, self.scales, self.packed = who, plain, fp8, window, sink, softcap, scales, packed
-        self.tree = tree
+        self.tree, self.split = tree, split
 
 
 _DECODE = _Public("flash_decode", "attention_decode", "attention_decode_fp8", "attention_decode_window", "attention_decode_sink",
                   "attention_decode_softcap", scales=True, tree="attention_decode_tree")
 _PREFILL = _Public("flash_prefill", "attention_prefill", None, "attention_prefill_window", "attention_prefill_sink", "attention_prefill_softcap",
-                   tree="attention_prefill_tree")
+                   tree="attention_prefill_tree", split="attention_prefill_split")
 _PREFILL_RAGGED = _Public("flash_prefill_ragged", "attention_prefill_ragged", softcap="attention_prefill_ragged_softcap", packed=True)
 
 
-def _route(f, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap, tree_mask=None):
-    """The keywords of the public function `f` (a _Public), checked in one order -- the cap, then the window, the sink tokens and the sink
-    logits, then the tree, which reaches the tree op with any window and sinks -- and the op they reach -> (op, the arguments it takes after causal, or after the scales where they come earlier), in the ops'
-    spelling: 0 for no window and no sink tokens.  A cap wins over all, either sink keyword reaches the sink op, a window the window op"""
+def _route(f, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap, tree_mask=None, key_pieces=None):
+    """The keywords of the public function `f` (a _Public), checked in one order -- the key pieces, the cap, then the window, the sink tokens
+    and the sink logits, then the tree, which reaches the tree op with any window and sinks -- and the op they reach -> (op, the arguments
+    it takes after causal, or after the scales where they come earlier), in the ops' spelling: 0 for no window and no sink tokens, None for
+    no tree.  Key pieces reach the split op with any window, sinks and tree and no cap; a cap wins over all else, either sink keyword
+    reaches the sink op, a window the window op"""
     who = f.who
+    if key_pieces is not None:
+        if softcap is not None:
+            raise ValueError(f"{who}: key_pieces and softcap together have no kernel (include/mfa_split.h)")
+        if isinstance(key_pieces, bool) or not isinstance(key_pieces, int) or not 0 <= key_pieces <= 64:
+            raise ValueError(f"{who}: key_pieces must be an int from 0 (the host's plan) to 64 (None: the launch is not cut along the keys), not {key_pieces!r}")
     if softcap is not None:
         _check_softcap(who, softcap)
     sinks = sink_tokens is not None or sink_logits is not None
@@ -906,6 +909,9 @@ def _route(f, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens
     scales = (k_scale, v_scale) if f.scales else ()
     if tree_mask is not None:
         _check_tree(who, q, tree_mask, causal, window, softcap)
+    if key_pieces is not None:
+        return f.split, (*scales, window or 0, sink_tokens or 0, sink_logits, tree_mask, key_pieces)
+    if tree_mask is not None:
         return f.tree, (*scales, window or 0, sink_tokens or 0, sink_logits, tree_mask)
     if softcap is not None:
         return f.softcap, (*scales, window or 0, sink_tokens or 0, sink_logits, float(softcap))
@@ -998,17 +1004,7 @@ def flash_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     plan the pieces from the shapes, 2 .. 64 forces them, 1 is the unsplit launch; the workspace is allocated here.  With any window, sinks
     and tree_mask, not with softcap; through the op `mfa::attention_prefill_split`.  None: the launch is not cut, as before."""
     _forward_only("flash_prefill", q, k_cache, v_cache, cache_lengths)
-    if key_pieces is not None:
-        who = "flash_prefill"
-        if softcap is not None:
-            raise ValueError(f"{who}: key_pieces and softcap together have no kernel (include/mfa_split.h)")
-        if isinstance(key_pieces, bool) or not isinstance(key_pieces, int) or not 0 <= key_pieces <= 64:
-            raise ValueError(f"{who}: key_pieces must be an int from 0 (the host's plan) to 64 (None: the launch is not cut along the keys), not {key_pieces!r}")
-        _op, own = _route(_PREFILL, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, None, tree_mask)   # (the checks)
-        o, l = _call_op(_HAVE_SPLIT_OP, "attention_prefill_split", q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale,
-                        window or 0, sink_tokens or 0, sink_logits, tree_mask, key_pieces)
-        return (o, l * _LN2) if return_lse else o
-    op, own = _route(_PREFILL, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap, tree_mask)
+    op, own = _route(_PREFILL, q, k_cache, v_cache, causal, k_scale, v_scale, window, sink_tokens, sink_logits, softcap, tree_mask, key_pieces)
     o, l = _call_op(_HAVE[op], op, q, k_cache, v_cache, cache_lengths, q_lengths, block_table, causal, k_scale, v_scale, *own)
     return (o, l * _LN2) if return_lse else o
 

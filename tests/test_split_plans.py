@@ -4,6 +4,7 @@ count against the rule as the header states it, the launch-form texts of split, 
 head dimension, type, cache and with a tree, every refusal by status and message, and the torch binding's routes on fake tensors."""
 import ctypes
 import inspect
+import itertools
 import os
 import re
 
@@ -42,6 +43,21 @@ def test_header_symbols_exported_and_the_ctypes_mirror():
         if name.endswith(("_launch", "_launch_form", "_time", "_workspace_size")):   # `split` follows `tree`, which follows `sinks`
             at = argtypes.index(_abi._SPLIT)
             assert argtypes.count(_abi._SPLIT) == 1 and argtypes[at - 1] is _abi._TREE and argtypes[at - 2] is _abi._SINKS
+    # the five entries' signatures written out, as include/mfa_split.h declares them: the table that generates four of them is not its own witness
+    void, u32, u32p = ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)
+    bufs, params = [void] * 5, [ctypes.POINTER(_abi.mfa_prefill_params)]
+    own = [u32, ctypes.POINTER(_abi.mfa_attention_sinks), ctypes.POINTER(_abi.mfa_attention_tree), ctypes.POINTER(_abi.mfa_key_split)]
+    pair = ctypes.POINTER(ctypes.c_uint32 * 2)
+    written_out = {
+        "launch": bufs + params + own + [void],
+        "launch_form": params + own + [ctypes.c_char_p, ctypes.c_size_t],
+        "time": bufs + params + own + [void, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)],
+        "workspace_size": params + own + [ctypes.POINTER(ctypes.c_uint64), u32p],
+        "piece_range": [u32] * 5 + [pair, pair],
+    }
+    for verb, argtypes in written_out.items():
+        fn = getattr(handle, "mfa_attention_prefill_split_" + verb)
+        assert fn.restype is ctypes.c_int and list(fn.argtypes) == argtypes, verb
     assert int(handle.mfa_abi_version()) == 6   # mfa.h did not change
     for name in ("MAX_PIECES", "MIN_TILES", "COMPUTE_UNITS"):
         assert getattr(_abi, "MFA_PREFILL_SPLIT_" + name) == int(re.search(r"#define MFA_PREFILL_SPLIT_%s (\d+)u" % name, header).group(1))
@@ -224,6 +240,36 @@ def test_every_refusal_by_status_and_message():
     handle.mfa_key_split_init(ctypes.byref(split))
     assert handle.mfa_attention_prefill_split_launch_form(ctypes.byref(pp), 0, None, None, ctypes.byref(split), out, len(out)) == 0
     assert out.value.decode() == pre.launchForm(pieces=0, **pshape())
+
+
+def test_every_split_call_reaches_the_split_family_of_the_table():
+    """the split block is one more option of attention._route: with any of a window, sinks and a tree it reaches mfa_attention_prefill_split_,
+    which is handed window 0 and NULL blocks for what the call leaves out; decode has no such family"""
+    from metal_flash_attention_amd import attention as at
+    assert at._OPTIONS == ("quant", "window", "sinks", "ragged", "softcap", "tree", "split")
+    assert _abi.CACHE_FAMILIES["prefill"]["split_"] == ("window", "sinks", "tree", "split")
+    routes = at._routes("prefill")
+    assert routes is not at.AttentionPrefill.ROUTES and routes == at.AttentionPrefill.ROUTES
+    sinks, tree, split = object(), object(), object()   # (whatever the caller passes by reference goes through as it is)
+    for given in itertools.product((False, True), repeat=3):
+        w, s, t = (value if g else None for value, g in zip((130, sinks, tree), given))
+        entries, own = at._route(routes, None, w, s, None, None, t, split)
+        assert entries == "mfa_attention_prefill_split_" and tuple(own) == (130 if given[0] else 0, s, t, split), given
+        assert routes[(False, given[0], given[1], False, False, given[2], True)] == (entries, (False, True, True, False, False, True, True))
+    assert tuple(at._route(routes, None, 0, None, None, None, None, split)[1]) == (0, None, None, split)   # a window that is given as 0
+    assert at._route(routes, None, 130, sinks, None, None, tree)[0] == "mfa_attention_prefill_tree_"      # no split block: the family it always was
+    assert not any(given[0] or given[6] for given in routes if given[3] or given[4]) and not any(given[6] for given in at._routes("decode"))
+    text = "a key split (workspace= / pieces=) goes with neither %s: a soft cap or ragged rows together with a split have no kernel (include/mfa_split.h)"
+    for softcap, ragged, t, said in ((ctypes.c_float(50.0), None, None, "softcap="), (None, object(), None, "rowStarts= / totalRows="),
+                                     (ctypes.c_float(50.0), object(), None, "softcap="), (ctypes.c_float(50.0), None, tree, "softcap=")):
+        with pytest.raises(ValueError) as refused:
+            at._route(routes, None, None, None, ragged, softcap, t, split)
+        assert str(refused.value) == text % said
+    pre = AttentionPrefill(128, P.BF16)
+    for kw, said in ((dict(pieces=3, softcap=50.0), "softcap="), (dict(workspace=WS, rowStarts=STARTS, totalRows=100), "rowStarts= / totalRows="),
+                     (dict(pieces=0, softcap=50.0, **TREE), "softcap=")):
+        for call in (pre.launchForm, pre.workspaceSize, pre.plannedSplit):
+            assert outcome(call, **kw, **pshape()) == ["ValueError", text % said]
 
 
 # ------------------------------------------------------------------------------------------------ the torch binding, on fake tensors
