@@ -11,6 +11,7 @@ from .attention import (  # noqa: F401
     AttentionKernel,
     AttentionKernelDescriptor,
     AttentionKernelType,
+    AttentionMLADecode,
     AttentionOperand,
     AttentionPrefill,
     GEMMOperandPrecision,
@@ -31,7 +32,7 @@ from .gemm import GEMMDescriptor, GEMMKernel, GEMMKernelDescriptor  # noqa: F401
 
 def __getattr__(name):
     # the torch functions of the KV-cache loop, on first use: torch stays optional for everything above
-    if name in ("kv_cache_compact", "tree_path"):
+    if name in ("kv_cache_compact", "tree_path", "flash_mla_decode"):
         from . import torch_binding
         return getattr(torch_binding, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

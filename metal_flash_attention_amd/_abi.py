@@ -342,6 +342,35 @@ COMPACT_SYMBOLS = [   # include/mfa_compact.h: the accepted path of a speculatio
     ("mfa_kv_cache_compact_launch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _COMPACT, ctypes.c_void_p]),
 ]
 
+class mfa_mla_decode_params(ctypes.Structure):   # include/mfa_mla.h
+    _fields_ = [
+        ("rows", ctypes.c_uint32), ("column", ctypes.c_uint32), ("heads", ctypes.c_uint32), ("batches", ctypes.c_uint32),
+        ("causal", ctypes.c_uint32),
+        ("headDimension", ctypes.c_uint16), ("valueDimension", ctypes.c_uint16),
+        ("precision", ctypes.c_uint8), ("outputPrecision", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
+        ("scale", ctypes.c_float), ("pageSize", ctypes.c_uint32), ("pieces", ctypes.c_uint32),
+        ("cacheLengths", ctypes.c_void_p), ("blockTable", ctypes.c_void_p), ("blockTableStride", ctypes.c_int64),
+        ("leadingDimension", ctypes.c_int64 * 3), ("headStride", ctypes.c_int64 * 3), ("batchStride", ctypes.c_int64 * 3),
+        ("pageStride", ctypes.c_int64),
+        ("lHeadStride", ctypes.c_int64), ("lBatchStride", ctypes.c_int64),
+        ("workspace", ctypes.c_void_p), ("workspaceBytes", ctypes.c_uint64),
+    ]
+
+
+_MLA = ctypes.POINTER(mfa_mla_decode_params)
+MFA_MLA_HEAD_DIMENSION, MFA_MLA_VALUE_DIMENSION, MFA_MLA_PACKED_ROWS = 576, 512, 32
+_MLA_BUFS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]   # q, kv, o, l
+
+MLA_SYMBOLS = [   # include/mfa_mla.h: multi-head latent attention decode over a compressed KV cache; an entry of its own, no family
+    ("mfa_mla_decode_params_init", None, [_MLA]),
+    ("mfa_mla_decode_params_size", ctypes.c_size_t, []),
+    ("mfa_mla_decode_params_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
+    ("mfa_attention_mla_decode_workspace_size", ctypes.c_int, [_MLA, ctypes.POINTER(ctypes.c_uint64), _U32P]),
+    ("mfa_attention_mla_decode_launch", ctypes.c_int, _MLA_BUFS + [_MLA, ctypes.c_void_p]),
+    ("mfa_attention_mla_decode_launch_form", ctypes.c_int, [_MLA, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_mla_decode_time", ctypes.c_int, _MLA_BUFS + [_MLA, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+]
+
 # ---- the laddered entries of the launches over a KV cache, described once:
 #     mfa_attention_<launch>_<family><verb>(*<the verb's head>, params, *<the options the family owns>, *<the verb's tail>)
 # CACHE_FAMILIES: launch -> family -> the options its entries take, in the order of their signatures (each family is an earlier one plus an
@@ -448,7 +477,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -912,6 +912,85 @@ class KVCacheCompact:
         check(lib().mfa_kv_cache_compact_launch(*_pointers(kCache, vCache), ctypes.byref(p), ctypes.c_void_p(stream or 0)))
 
 
+class AttentionMLADecode:
+    """Multi-head latent attention decode over a compressed KV cache (include/mfa_mla.h): `rows` new query rows per sequence and head,
+    q [batches][heads][rows][576], against ONE cache row of 576 values per key -- all of them the key, the first 512 the value --
+    shared by every head; o [batches][heads][rows][512].  The softmax scale is the model's own and must be given.
+
+        mla = AttentionMLADecode(GEMMOperandPrecision.BF16)
+        need, pieces = mla.plannedSplit(rows=1, column=C, heads=128, batches=B, scale=s)
+        mla.dispatch(q, kv, o, l, cacheLengths=lengths, rows=1, column=C, heads=128, batches=B, scale=s, workspace=ws)
+
+    `strides`: operand name (Q, KV, O) -> (leadingDimension, headStride, batchStride) in elements; an operand left out is packed (the
+    cache: [batch][key][576], head stride unused).  Paged caches: pageSize, blockTable (device int32 [batches][blockTableStride]) and
+    pageStride (default pageSize x the cache's leadingDimension).  pieces: None or 0 is the host's plan, 1 unsplit, 2 .. 64 as given;
+    without a workspace the launch runs unsplit.  Stands alone, as KVCacheCompact: no option families."""
+
+    OPERANDS = ("Q", "KV", "O")
+    HEAD_DIMENSION, VALUE_DIMENSION = _abi.MFA_MLA_HEAD_DIMENSION, _abi.MFA_MLA_VALUE_DIMENSION
+
+    def __init__(self, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16, outputPrecision: Optional[GEMMOperandPrecision] = None,
+                 headDimension: int = _abi.MFA_MLA_HEAD_DIMENSION, valueDimension: int = _abi.MFA_MLA_VALUE_DIMENSION):
+        self.precision = GEMMOperandPrecision(precision)
+        self.outputPrecision = self.precision if outputPrecision is None else GEMMOperandPrecision(outputPrecision)
+        self.headDimension, self.valueDimension = int(headDimension), int(valueDimension)
+
+    def _params(self, *, rows: int, column: int, scale: float, heads: int = 1, batches: int = 1, causal: bool = True, pieces: Optional[int] = None,
+                lStrides: Optional[Sequence[int]] = None, workspace=None, workspaceBytes: Optional[int] = None, cacheLengths=None,
+                pageSize: int = 0, blockTable=None, blockTableStride: int = 0, strides: Optional[Mapping] = None,
+                pageStride: Optional[int] = None):
+        p = _abi.mfa_mla_decode_params()
+        lib().mfa_mla_decode_params_init(ctypes.byref(p))
+        Dk, Dv = self.headDimension, self.valueDimension
+        p.rows, p.column, p.heads, p.batches = int(rows), int(column), int(heads), int(batches)
+        p.headDimension, p.valueDimension, p.causal, p.scale, p.pieces = Dk, Dv, int(bool(causal)), float(scale), int(pieces or 0)
+        p.precision, p.outputPrecision = int(self.precision), int(self.outputPrecision)
+        p.pageSize, p.cacheLengths = int(pageSize), _pointer(cacheLengths)
+        p.blockTable, p.blockTableStride = _pointer(blockTable), int(blockTableStride)
+        packed = (_packed(rows, heads, Dk), (Dk, 0, int(column) * Dk), _packed(rows, heads, Dv))
+        for i, name in enumerate(self.OPERANDS):
+            ld, hs, bs = strides.get(name, packed[i]) if strides else packed[i]
+            p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
+        p.pageStride = int(pageStride) if pageStride is not None else int(pageSize) * int(p.leadingDimension[1])
+        p.lHeadStride, p.lBatchStride = (int(lStrides[0]), int(lStrides[1])) if lStrides is not None else (int(rows), int(heads) * int(rows))
+        p.workspace = _pointer(workspace)
+        if workspaceBytes is None:
+            workspaceBytes = int(workspace.numel() * workspace.element_size()) if hasattr(workspace, "numel") else 0
+        p.workspaceBytes = int(workspaceBytes)
+        return p, (cacheLengths, blockTable, workspace)
+
+    def plannedSplit(self, **shape) -> Tuple[int, int]:
+        """(workspace bytes, pieces) of a launch of this shape: the piece count the host planned, or the one given; 0 bytes: one piece"""
+        p, _keep = self._params(**shape)
+        nbytes, pieces = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        check(lib().mfa_attention_mla_decode_workspace_size(ctypes.byref(p), ctypes.byref(nbytes), ctypes.byref(pieces)))
+        return int(nbytes.value), int(pieces.value)
+
+    def workspaceSize(self, **shape) -> int:
+        """Bytes a launch of this shape wants to be cut along the keys (0: one piece).  Without a workspace the launch runs unsplit."""
+        return self.plannedSplit(**shape)[0]
+
+    def launchForm(self, **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the kernels' names, the grid, the piece count"""
+        p, _keep = self._params(**shape)
+        out = ctypes.create_string_buffer(512)
+        check(lib().mfa_attention_mla_decode_launch_form(ctypes.byref(p), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, kv, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        """mfa_attention_mla_decode_launch"""
+        p, _keep = self._params(**shape)
+        check(lib().mfa_attention_mla_decode_launch(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.c_void_p(stream or 0)))
+
+    def time(self, q, kv, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
+        p, _keep = self._params(**shape)
+        ms = ctypes.c_float(0.0)
+        check(lib().mfa_attention_mla_decode_time(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.c_void_p(stream or 0), int(warmup),
+                                                  int(iterations), ctypes.byref(ms)))
+        return float(ms.value)
+
+
 def quantizeE4M3(x: float, scale: float = 1.0) -> int:
     """the cache byte of `x` under `scale`: mfa_kv_quantize_e4m3, the contract of writer and reader"""
     return int(lib().mfa_kv_quantize_e4m3(float(x), float(scale)))

@@ -33,7 +33,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
                         KVCachePrecision)
 
@@ -600,6 +600,62 @@ def _run_compact(k_cache, v_cache, cache_lengths, accepted, accepted_counts, row
     return new_lengths
 
 
+def _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces):
+    """the operands of flash_mla_decode (include/mfa_mla.h), checked where the public function and the op both pass: shapes, types, devices"""
+    Dk = AttentionMLADecode.HEAD_DIMENSION
+    if not all(t.is_cuda for t in (q, kv_cache, cache_lengths)) or (block_table is not None and not block_table.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{who}: q must be bfloat16 or float16 (got {q.dtype})")
+    if kv_cache.dtype != q.dtype:
+        raise TypeError(f"{who}: q and the latent cache must share one of bfloat16 / float16 (got {q.dtype}, {kv_cache.dtype}); e4m3 latent "
+                        "caches have no kernel")
+    paged = block_table is not None
+    if q.dim() != 4 or kv_cache.dim() != 3 or q.shape[3] != Dk or kv_cache.shape[2] != Dk or (not paged and kv_cache.shape[0] != q.shape[0]):
+        raise ValueError(f"{who}: expected q [B, H, R, {Dk}] and kv_cache [B, C, {Dk}] (paged: [pages, pageSize, {Dk}]): one row of the 512-wide "
+                         f"latent and the 64-wide rotary part per key (got {tuple(q.shape)}, {tuple(kv_cache.shape)})")
+    if kv_cache.stride(2) != 1 or any(st < 0 for st in kv_cache.stride()):
+        raise ValueError(f"{who}: kv_cache must have a contiguous last dimension (a cache is never copied)")
+    B = int(q.shape[0])
+    _check_lengths(who, "cache_lengths", cache_lengths, B)
+    if paged and (block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1):
+        raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous last dimension "
+                         f"(got {tuple(block_table.shape)}, {block_table.dtype})")
+    if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)) or not math.isfinite(softmax_scale) or not softmax_scale > 0:
+        raise ValueError(f"{who}: softmax_scale must be a finite number > 0, the model's own softmax scale in natural units (it is not "
+                         f"1 / sqrt(576) and has no default), not {softmax_scale!r}")
+    if isinstance(pieces, bool) or not isinstance(pieces, int) or not 0 <= pieces <= 64:
+        raise ValueError(f"{who}: pieces must be an int from 0 to 64 (None or 0: the host's plan, 1: unsplit), not {pieces!r}")
+
+
+def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces):
+    """flash_mla_decode's launch (include/mfa_mla.h) on q's device and torch's current stream -> (O [B, H, R, 512], L [B, H, R] base 2);
+    the workspace of a launch cut along the keys is allocated here"""
+    who = "flash_mla_decode"
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces)
+    paged = block_table is not None
+    q, q_strides = _new_operand(q)
+    B, H, R, _Dk = q.shape
+    Dv = AttentionMLADecode.VALUE_DIMENSION
+    ld = int(kv_cache.stride(1)) if kv_cache.shape[1] > 1 else int(kv_cache.shape[2])
+    kw = dict(rows=R, heads=H, batches=B, causal=bool(causal), scale=float(softmax_scale), pieces=int(pieces),
+              cacheLengths=cache_lengths.to(torch.int32), strides={"Q": q_strides, "KV": (ld, 0, 0 if paged else int(kv_cache.stride(0)))},
+              column=int(kv_cache.shape[1]) * (int(block_table.shape[1]) if paged else 1))
+    if paged:
+        kw.update(pageSize=int(kv_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)), pageStride=int(kv_cache.stride(0)))
+    key = (AttentionMLADecode, q.dtype)
+    host = _HOSTS.get(key)
+    if host is None:
+        host = _HOSTS[key] = AttentionMLADecode(P.BF16 if q.dtype == torch.bfloat16 else P.FP16)
+    o = torch.empty((B, H, R, Dv), dtype=q.dtype, device=q.device)
+    l = torch.empty((B, H, R), dtype=torch.float32, device=q.device)
+    need = host.workspaceSize(**kw)
+    kw.update(workspace=torch.empty(need, dtype=torch.uint8, device=q.device) if need else None)
+    with torch.cuda.device(q.device):
+        host.dispatch(q, kv_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
+    return o, l
+
+
 def _check_tree(who, q, tree_mask, causal, window, softcap):
     """tree_mask= of a public function: an int64 tensor [R] or [B, R] on q's device; causal, no cap, a window of at least R"""
     R, B = (q.shape[2], q.shape[0]) if q.dim() == 4 else (None, None)
@@ -782,6 +838,17 @@ def _op_compact(k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths: tor
     return _run_compact(k_cache, v_cache, cache_lengths, accepted, accepted_counts, rows, q_lengths, block_table)
 
 
+def _op_mla_decode(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, block_table: Optional[torch.Tensor], causal: bool,
+                   softmax_scale: float, pieces: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(`pieces`: 0 is the host's plan, 1 unsplit, 2 .. 64 as given)"""
+    return _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces)
+
+
+def _fake_mla(q, *args, **kwargs):
+    B, H, R, _Dk = q.shape
+    return q.new_empty((B, H, R, AttentionMLADecode.VALUE_DIMENSION)), q.new_empty((B, H, R), dtype=torch.float32)
+
+
 def _fake_lengths(k_cache, v_cache, cache_lengths, *args, **kwargs):
     return cache_lengths.new_empty((cache_lengths.shape[0],), dtype=torch.int32)
 
@@ -842,6 +909,7 @@ _CACHE_OPS = [
     ("attention_prefill_tree", _op_prefill_tree, _fake_padded, ()),
     ("kv_cache_compact", _op_compact, _fake_lengths, ("k_cache", "v_cache")),
     ("attention_prefill_split", _op_prefill_split, _fake_padded, ()),
+    ("attention_mla_decode", _op_mla_decode, _fake_mla, ()),
 ]
 _HAVE = {_op[0]: _register_cache_op(*_op) for _op in _CACHE_OPS}   # op name -> whether torch has it as a custom op
 _HAVE_DECODE_OP = _HAVE["attention_decode"]
@@ -854,6 +922,7 @@ _HAVE_SOFTCAP_OPS = _HAVE["attention_decode_softcap"] and _HAVE["attention_prefi
 _HAVE_TREE_OPS = _HAVE["attention_decode_tree"] and _HAVE["attention_prefill_tree"]
 _HAVE_COMPACT_OP = _HAVE["kv_cache_compact"]
 _HAVE_SPLIT_OP = _HAVE["attention_prefill_split"]
+_HAVE_MLA_OP = _HAVE["attention_mla_decode"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1063,3 +1132,29 @@ def kv_cache_compact(k_cache: torch.Tensor, v_cache: torch.Tensor, cache_lengths
     if not all(t.is_cuda for t in (k_cache, v_cache, cache_lengths, accepted, accepted_counts)):
         raise RuntimeError("kv_cache_compact: tensors must live on the GPU (there is no CPU path)")
     return _call_op(_HAVE_COMPACT_OP, "kv_cache_compact", k_cache, v_cache, cache_lengths, accepted, accepted_counts, rows, q_lengths, block_table)
+
+
+def flash_mla_decode(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, *, softmax_scale: float,
+                     block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False, pieces: Optional[int] = None):
+    """Multi-head latent attention decode in its absorbed form (DeepSeek-V2 / V3 / R1, Kimi K2; include/mfa_mla.h): the R new rows of every
+    sequence and head, q [B, H, R, 576] (R <= 32), against a COMPRESSED cache kv_cache [B, C, 576] that holds one row per key -- a 512-wide
+    latent followed by a 64-wide rotary part -- shared by every head: all 576 columns are the key, the first 512 the value.  Returns
+    O [B, H, R, 512] (the caller applies the value up-projection), and with return_lse also L [B, H, R] fp32 in natural units.
+    softmax_scale is the model's own scale on q . k (1 / sqrt(192) times a YaRN factor in those checkpoints) and is required.
+    cache_lengths [B] (GPU): valid keys per sequence INCLUDING the R new tokens, which the caller has already written into the cache (with
+    torch: there is no append kernel for the latent cache yet); with `causal` row r sees key c iff c <= r + max(len - R, 0).  kv_cache may
+    be any view of that shape with a contiguous last dimension and a row stride that is a multiple of 8 (nothing is copied); with
+    block_table [B, n] int32 it is a page pool [pages, pageSize, 576].  pieces: None lets the host cut the keys into pieces from the
+    shapes, 1 is the unsplit launch, 2 .. 64 forces them; the workspace is allocated here.  Forward only, GPU only.  A sequence of length
+    0 gets O = 0.  Goes through the torch.library op `mfa::attention_mla_decode` where torch has custom ops, so it traces under
+    torch.compile."""
+    who = "flash_mla_decode"
+    if not (q.is_cuda and kv_cache.is_cuda and cache_lengths.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, kv_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} is forward only (no autograd): detach the inputs")
+    pieces = 0 if pieces is None else pieces
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces)
+    o, l = _call_op(_HAVE_MLA_OP, "attention_mla_decode", q, kv_cache, cache_lengths, block_table, bool(causal), float(softmax_scale), int(pieces))
+    return (o, l * _LN2) if return_lse else o
