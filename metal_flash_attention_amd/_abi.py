@@ -371,6 +371,38 @@ MLA_SYMBOLS = [   # include/mfa_mla.h: multi-head latent attention decode over a
     ("mfa_attention_mla_decode_time", ctypes.c_int, _MLA_BUFS + [_MLA, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
 ]
 
+class mfa_mla_append_params(ctypes.Structure):   # include/mfa_mla_cache.h
+    _fields_ = [
+        ("rows", ctypes.c_uint32), ("batches", ctypes.c_uint32), ("column", ctypes.c_uint32), ("pageSize", ctypes.c_uint32),
+        ("latentDimension", ctypes.c_uint16), ("ropeDimension", ctypes.c_uint16),
+        ("precision", ctypes.c_uint8), ("cachePrecision", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
+        ("cacheLengths", ctypes.c_void_p), ("blockTable", ctypes.c_void_p), ("blockTableStride", ctypes.c_int64),
+        ("leadingDimension", ctypes.c_int64 * 3), ("batchStride", ctypes.c_int64 * 3),
+        ("pageStride", ctypes.c_int64),
+        ("kvScale", ctypes.c_void_p),
+    ]
+
+
+class mfa_mla_quant(ctypes.Structure):   # include/mfa_mla_cache.h
+    _fields_ = [("cachePrecision", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("kvScale", ctypes.c_void_p)]
+
+
+_MLA_APPEND, _MLA_QUANT = ctypes.POINTER(mfa_mla_append_params), ctypes.POINTER(mfa_mla_quant)
+MFA_MLA_LATENT_DIMENSION, MFA_MLA_ROPE_DIMENSION = 512, 64
+
+MLA_CACHE_SYMBOLS = [   # include/mfa_mla_cache.h: the latent cache's append, and MLA decode over an e4m3 latent cache (`quant` after `params`)
+    ("mfa_mla_append_params_init", None, [_MLA_APPEND]),
+    ("mfa_mla_append_params_size", ctypes.c_size_t, []),
+    ("mfa_mla_append_params_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
+    ("mfa_mla_cache_append_launch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _MLA_APPEND, ctypes.c_void_p]),
+    ("mfa_mla_quant_init", None, [_MLA_QUANT]),
+    ("mfa_attention_mla_decode_fp8_workspace_size", ctypes.c_int, [_MLA, _MLA_QUANT, ctypes.POINTER(ctypes.c_uint64), _U32P]),
+    ("mfa_attention_mla_decode_fp8_launch", ctypes.c_int, _MLA_BUFS + [_MLA, _MLA_QUANT, ctypes.c_void_p]),
+    ("mfa_attention_mla_decode_fp8_launch_form", ctypes.c_int, [_MLA, _MLA_QUANT, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_mla_decode_fp8_time", ctypes.c_int,
+     _MLA_BUFS + [_MLA, _MLA_QUANT, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+]
+
 # ---- the laddered entries of the launches over a KV cache, described once:
 #     mfa_attention_<launch>_<family><verb>(*<the verb's head>, params, *<the options the family owns>, *<the verb's tail>)
 # CACHE_FAMILIES: launch -> family -> the options its entries take, in the order of their signatures (each family is an earlier one plus an
@@ -477,7 +509,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -959,11 +959,21 @@ class AttentionMLADecode:
         p.workspaceBytes = int(workspaceBytes)
         return p, (cacheLengths, blockTable, workspace)
 
+    _FAMILY = ""   # the entries are mfa_attention_mla_decode_<family><verb>
+
+    def _own(self, shape):
+        """what the family's entries take after the params, taken out of `shape` -> (ctypes arguments, what they point to)"""
+        return (), None
+
+    def _entry(self, verb):
+        return getattr(lib(), "mfa_attention_mla_decode_" + self._FAMILY + verb)
+
     def plannedSplit(self, **shape) -> Tuple[int, int]:
         """(workspace bytes, pieces) of a launch of this shape: the piece count the host planned, or the one given; 0 bytes: one piece"""
+        own, _kept = self._own(shape)
         p, _keep = self._params(**shape)
         nbytes, pieces = ctypes.c_uint64(0), ctypes.c_uint32(0)
-        check(lib().mfa_attention_mla_decode_workspace_size(ctypes.byref(p), ctypes.byref(nbytes), ctypes.byref(pieces)))
+        check(self._entry("workspace_size")(ctypes.byref(p), *own, ctypes.byref(nbytes), ctypes.byref(pieces)))
         return int(nbytes.value), int(pieces.value)
 
     def workspaceSize(self, **shape) -> int:
@@ -972,23 +982,92 @@ class AttentionMLADecode:
 
     def launchForm(self, **shape) -> str:
         """What `dispatch` with the same arguments would run (nothing is launched): the kernels' names, the grid, the piece count"""
+        own, _kept = self._own(shape)
         p, _keep = self._params(**shape)
         out = ctypes.create_string_buffer(512)
-        check(lib().mfa_attention_mla_decode_launch_form(ctypes.byref(p), out, len(out)))
+        check(self._entry("launch_form")(ctypes.byref(p), *own, out, len(out)))
         return out.value.decode()
 
     def dispatch(self, q, kv, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
         """mfa_attention_mla_decode_launch"""
+        own, _kept = self._own(shape)
         p, _keep = self._params(**shape)
-        check(lib().mfa_attention_mla_decode_launch(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.c_void_p(stream or 0)))
+        check(self._entry("launch")(*_pointers(q, kv, o, l), ctypes.byref(p), *own, ctypes.c_void_p(stream or 0)))
 
     def time(self, q, kv, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
         """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
+        own, _kept = self._own(shape)
         p, _keep = self._params(**shape)
         ms = ctypes.c_float(0.0)
-        check(lib().mfa_attention_mla_decode_time(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.c_void_p(stream or 0), int(warmup),
-                                                  int(iterations), ctypes.byref(ms)))
+        check(self._entry("time")(*_pointers(q, kv, o, l), ctypes.byref(p), *own, ctypes.c_void_p(stream or 0), int(warmup), int(iterations),
+                                  ctypes.byref(ms)))
         return float(ms.value)
+
+
+class AttentionMLADecodeFP8(AttentionMLADecode):
+    """MLA decode over an FP8 (OCP e4m3) latent cache (include/mfa_mla_cache.h): AttentionMLADecode's methods and arguments -- the KV
+    strides count bytes, multiples of 16 -- plus kvScale (device FP32, one entry, None = 1.0): a cache byte stands for
+    kvScale[0] x e4m3(byte), latent and rotary part alike.  `precision` is the 16-bit type of Q.  The workspace and the piece plan are
+    AttentionMLADecode's."""
+
+    _FAMILY = "fp8_"
+
+    def __init__(self, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16, outputPrecision: Optional[GEMMOperandPrecision] = None,
+                 cachePrecision: int = KVCachePrecision.E4M3, **widths):
+        super().__init__(precision, outputPrecision, **widths)
+        self.cachePrecision = int(cachePrecision)
+
+    def _own(self, shape):
+        quant = _abi.mfa_mla_quant()
+        lib().mfa_mla_quant_init(ctypes.byref(quant))
+        quant.cachePrecision = self.cachePrecision
+        keep = shape.pop("kvScale", None)
+        quant.kvScale = _pointer(keep)
+        return (ctypes.byref(quant),), (quant, keep)
+
+
+class MLACacheAppend:
+    """Appends the `rows` new rows of every sequence to the latent cache of MLA decode (include/mfa_mla_cache.h) -- latentNew
+    [batches][rows][512] and ropeNew [batches][rows][64] become one cache row of 576 -- quantising them to e4m3 when the cache is FP8
+    (cachePrecision=KVCachePrecision.E4M3, kvScale: device FP32, one entry, None = 1.0) or copying their bits when it is the rows'
+    16-bit type (None).
+
+        append = MLACacheAppend(GEMMOperandPrecision.BF16, KVCachePrecision.E4M3)
+        append.dispatch(latent_new, rope_new, kv_cache, rows=1, batches=B, column=C, cacheLengths=lengths, kvScale=scale)
+
+    cacheLengths already includes the new rows: row r of sequence b goes to key cacheLengths[b] - rows + r.  `strides`: operand name
+    (latentNew, ropeNew, kvCache) -> (leadingDimension, batchStride) in elements; an operand left out is packed.  Paged caches:
+    pageSize, blockTable, blockTableStride and pageStride (default pageSize x the cache's leadingDimension)."""
+
+    OPERANDS = ("latentNew", "ropeNew", "kvCache")
+    LATENT_DIMENSION, ROPE_DIMENSION = _abi.MFA_MLA_LATENT_DIMENSION, _abi.MFA_MLA_ROPE_DIMENSION
+
+    def __init__(self, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16, cachePrecision: Optional[int] = None,
+                 latentDimension: int = _abi.MFA_MLA_LATENT_DIMENSION, ropeDimension: int = _abi.MFA_MLA_ROPE_DIMENSION):
+        self.precision = GEMMOperandPrecision(precision)
+        self.cachePrecision = int(self.precision) if cachePrecision is None else int(cachePrecision)
+        self.latentDimension, self.ropeDimension = int(latentDimension), int(ropeDimension)
+
+    def _params(self, *, rows: int, batches: int = 1, column: int = 0, kvScale=None, cacheLengths=None, pageSize: int = 0, blockTable=None,
+                blockTableStride: int = 0, strides: Optional[Mapping] = None, pageStride: Optional[int] = None):
+        p = _abi.mfa_mla_append_params()
+        lib().mfa_mla_append_params_init(ctypes.byref(p))
+        Dl, Dr = self.latentDimension, self.ropeDimension
+        p.rows, p.batches, p.column, p.pageSize = int(rows), int(batches), int(column), int(pageSize)
+        p.latentDimension, p.ropeDimension, p.precision, p.cachePrecision = Dl, Dr, int(self.precision), self.cachePrecision
+        p.cacheLengths, p.blockTable, p.blockTableStride = _pointer(cacheLengths), _pointer(blockTable), int(blockTableStride)
+        packed = ((Dl, int(rows) * Dl), (Dr, int(rows) * Dr), (Dl + Dr, int(column) * (Dl + Dr)))
+        for i, name in enumerate(self.OPERANDS):
+            ld, bs = strides.get(name, packed[i]) if strides else packed[i]
+            p.leadingDimension[i], p.batchStride[i] = int(ld), int(bs)
+        p.pageStride = int(pageStride) if pageStride is not None else int(pageSize) * int(p.leadingDimension[2])
+        p.kvScale = _pointer(kvScale)
+        return p
+
+    def dispatch(self, latentNew, ropeNew, kvCache, *, stream: Optional[int] = None, **shape) -> None:
+        """mfa_mla_cache_append_launch"""
+        p = self._params(**shape)
+        check(lib().mfa_mla_cache_append_launch(*_pointers(latentNew, ropeNew, kvCache), ctypes.byref(p), ctypes.c_void_p(stream or 0)))
 
 
 def quantizeE4M3(x: float, scale: float = 1.0) -> int:

@@ -59,6 +59,7 @@ struct MlaArgs {
   uint32_t pieces;
   float scale2;                   // fl(scale x log2 e)
   float *wsO, *wsML;
+  const float *kvScale;           // the e4m3 kernels only (attn_mla8.h), one entry; null: 1.0.  Last, so that no other field moves
 };
 
 template <typename T, bool SPLIT>

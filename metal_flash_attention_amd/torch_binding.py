@@ -33,9 +33,9 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
-                        KVCachePrecision)
+                        KVCachePrecision, MLACacheAppend)
 
 _KERNELS: Dict[Tuple, AttentionKernel] = {}
 
@@ -600,16 +600,20 @@ def _run_compact(k_cache, v_cache, cache_lengths, accepted, accepted_counts, row
     return new_lengths
 
 
-def _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces):
-    """the operands of flash_mla_decode (include/mfa_mla.h), checked where the public function and the op both pass: shapes, types, devices"""
+def _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces, fp8=False):
+    """the operands of flash_mla_decode (include/mfa_mla.h) and, `fp8`, of flash_mla_decode_fp8 (include/mfa_mla_cache.h), checked where
+    the public function and the op both pass: shapes, types, devices"""
     Dk = AttentionMLADecode.HEAD_DIMENSION
     if not all(t.is_cuda for t in (q, kv_cache, cache_lengths)) or (block_table is not None and not block_table.is_cuda):
         raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
     if q.dtype not in (torch.bfloat16, torch.float16):
         raise TypeError(f"{who}: q must be bfloat16 or float16 (got {q.dtype})")
-    if kv_cache.dtype != q.dtype:
+    if fp8 and kv_cache.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"{who}: the latent cache must be torch.float8_e4m3fn (got {kv_cache.dtype}); a 16-bit latent cache is flash_mla_decode's, "
+                        "and e5m2 and fnuz caches have no kernel")
+    if not fp8 and kv_cache.dtype != q.dtype:
         raise TypeError(f"{who}: q and the latent cache must share one of bfloat16 / float16 (got {q.dtype}, {kv_cache.dtype}); e4m3 latent "
-                        "caches have no kernel")
+                        "caches have no kernel in this function: flash_mla_decode_fp8 reads them")
     paged = block_table is not None
     if q.dim() != 4 or kv_cache.dim() != 3 or q.shape[3] != Dk or kv_cache.shape[2] != Dk or (not paged and kv_cache.shape[0] != q.shape[0]):
         raise ValueError(f"{who}: expected q [B, H, R, {Dk}] and kv_cache [B, C, {Dk}] (paged: [pages, pageSize, {Dk}]): one row of the 512-wide "
@@ -628,11 +632,12 @@ def _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, piec
         raise ValueError(f"{who}: pieces must be an int from 0 to 64 (None or 0: the host's plan, 1: unsplit), not {pieces!r}")
 
 
-def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces):
+def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces, fp8=False, kv_scale=None):
     """flash_mla_decode's launch (include/mfa_mla.h) on q's device and torch's current stream -> (O [B, H, R, 512], L [B, H, R] base 2);
-    the workspace of a launch cut along the keys is allocated here"""
-    who = "flash_mla_decode"
-    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces)
+    the workspace of a launch cut along the keys is allocated here.  `fp8`: flash_mla_decode_fp8's, over an e4m3 latent cache with
+    `kv_scale` (include/mfa_mla_cache.h) -- the strides of such a cache count bytes, which are its elements"""
+    who = "flash_mla_decode_fp8" if fp8 else "flash_mla_decode"
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces, fp8)
     paged = block_table is not None
     q, q_strides = _new_operand(q)
     B, H, R, _Dk = q.shape
@@ -643,10 +648,13 @@ def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_sca
               column=int(kv_cache.shape[1]) * (int(block_table.shape[1]) if paged else 1))
     if paged:
         kw.update(pageSize=int(kv_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)), pageStride=int(kv_cache.stride(0)))
-    key = (AttentionMLADecode, q.dtype)
+    cls = AttentionMLADecodeFP8 if fp8 else AttentionMLADecode
+    if fp8:
+        kw.update(kvScale=_latent_scale(who, kv_scale, kv_cache.device))
+    key = (cls, q.dtype)
     host = _HOSTS.get(key)
     if host is None:
-        host = _HOSTS[key] = AttentionMLADecode(P.BF16 if q.dtype == torch.bfloat16 else P.FP16)
+        host = _HOSTS[key] = cls(P.BF16 if q.dtype == torch.bfloat16 else P.FP16)
     o = torch.empty((B, H, R, Dv), dtype=q.dtype, device=q.device)
     l = torch.empty((B, H, R), dtype=torch.float32, device=q.device)
     need = host.workspaceSize(**kw)
@@ -654,6 +662,78 @@ def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_sca
     with torch.cuda.device(q.device):
         host.dispatch(q, kv_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
     return o, l
+
+
+def _latent_scale(who, t, device):
+    """kv_scale as the kernels read it: fp32 [1] on the cache's device; None stays None (1.0)"""
+    if t is None:
+        return None
+    if not t.is_cuda or t.device != device:
+        raise RuntimeError(f"{who}: kv_scale must live on the GPU of the cache (the host never reads a scale)")
+    if t.shape != (1,) or t.dtype != torch.float32:
+        raise ValueError(f"{who}: kv_scale must be float32 [1], one scale for the whole cache row (got {tuple(t.shape)}, {t.dtype})")
+    return t
+
+
+def _check_mla_append(who, latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale):
+    """the operands of mla_cache_append (include/mfa_mla_cache.h), checked where the public function and the op both pass -> the cache is e4m3"""
+    Dl, Dr = MLACacheAppend.LATENT_DIMENSION, MLACacheAppend.ROPE_DIMENSION
+    if not all(t.is_cuda for t in (latent_new, rope_new, kv_cache, cache_lengths)) or (block_table is not None and not block_table.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    if latent_new.dtype not in (torch.bfloat16, torch.float16) or rope_new.dtype != latent_new.dtype:
+        raise TypeError(f"{who}: latent_new and rope_new must share one of bfloat16 / float16 (got {latent_new.dtype}, {rope_new.dtype})")
+    fp8 = kv_cache.dtype == torch.float8_e4m3fn
+    if not fp8 and kv_cache.dtype != latent_new.dtype:
+        raise TypeError(f"{who}: the latent cache must be the rows' 16-bit type or torch.float8_e4m3fn (got {kv_cache.dtype} beside "
+                        f"{latent_new.dtype}); e5m2 and fnuz caches have no kernel")
+    paged = block_table is not None
+    if (latent_new.dim() != 3 or rope_new.dim() != 3 or kv_cache.dim() != 3 or latent_new.shape[2] != Dl or rope_new.shape[2] != Dr
+            or rope_new.shape[:2] != latent_new.shape[:2] or latent_new.shape[1] == 0 or kv_cache.shape[2] != Dl + Dr
+            or (not paged and kv_cache.shape[0] != latent_new.shape[0])):
+        raise ValueError(f"{who}: expected latent_new [B, R, {Dl}], rope_new [B, R, {Dr}] and kv_cache [B, C, {Dl + Dr}] (paged: [pages, pageSize, "
+                         f"{Dl + Dr}]) (got {tuple(latent_new.shape)}, {tuple(rope_new.shape)}, {tuple(kv_cache.shape)})")
+    if kv_cache.stride(2) != 1 or any(st < 0 for st in kv_cache.stride()):
+        raise ValueError(f"{who}: kv_cache must have a contiguous last dimension (a cache is written where it lies)")
+    B = int(latent_new.shape[0])
+    _check_lengths(who, "cache_lengths", cache_lengths, B)
+    if paged and (block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.shape[1] == 0):
+        raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] "
+                         f"(got {tuple(block_table.shape)}, {block_table.dtype})")
+    if not fp8 and kv_scale is not None:
+        raise ValueError(f"{who}: kv_scale goes with a float8_e4m3fn cache; a 16-bit cache takes the rows' bits")
+    _latent_scale(who, kv_scale, kv_cache.device)
+    return fp8
+
+
+def _latent_rows(t):
+    """a [B, R, width] source as the kernel reads it, and its (leadingDimension, batchStride): a view with a contiguous last dimension and
+    16-byte rows is taken where it lies (a slice of a fused projection: strides, not a copy)"""
+    ok = t.stride(2) == 1 and all(st >= 0 for st in t.stride()) and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
+    t = t if ok else t.contiguous()
+    return t, (int(t.stride(1)) if t.shape[1] > 1 else int(t.shape[2]), int(t.stride(0)))
+
+
+def _run_mla_append(latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale):
+    """mla_cache_append's launch (include/mfa_mla_cache.h) on the cache's device and torch's current stream"""
+    who = "mla_cache_append"
+    fp8 = _check_mla_append(who, latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale)
+    paged = block_table is not None
+    (latent_new, latent_strides), (rope_new, rope_strides) = _latent_rows(latent_new), _latent_rows(rope_new)
+    B, R, _Dl = latent_new.shape
+    ld = int(kv_cache.stride(1)) if kv_cache.shape[1] > 1 else int(kv_cache.shape[2])
+    kw = dict(rows=R, batches=B, cacheLengths=cache_lengths.to(torch.int32), column=0 if paged else int(kv_cache.shape[1]),
+              strides={"latentNew": latent_strides, "ropeNew": rope_strides, "kvCache": (ld, 0 if paged else int(kv_cache.stride(0)))})
+    if paged:   # the table contiguous, its width the bound on the pages a sequence may name
+        block_table = block_table.contiguous()
+        kw.update(pageSize=int(kv_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.shape[1]), pageStride=int(kv_cache.stride(0)))
+    if fp8:
+        kw.update(kvScale=_latent_scale(who, kv_scale, kv_cache.device))
+    key = (MLACacheAppend, latent_new.dtype, fp8)
+    host = _HOSTS.get(key)
+    if host is None:
+        host = _HOSTS[key] = MLACacheAppend(P.BF16 if latent_new.dtype == torch.bfloat16 else P.FP16, KVCachePrecision.E4M3 if fp8 else None)
+    with torch.cuda.device(kv_cache.device):
+        host.dispatch(latent_new, rope_new, kv_cache, stream=torch.cuda.current_stream(kv_cache.device).cuda_stream, **kw)
 
 
 def _check_tree(who, q, tree_mask, causal, window, softcap):
@@ -844,6 +924,17 @@ def _op_mla_decode(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch
     return _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces)
 
 
+def _op_mla_decode_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, block_table: Optional[torch.Tensor], causal: bool,
+                       softmax_scale: float, pieces: int, kv_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(`pieces` as attention_mla_decode's; `kv_scale` last)"""
+    return _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces, True, kv_scale)
+
+
+def _op_mla_append(latent_new: torch.Tensor, rope_new: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                   block_table: Optional[torch.Tensor], kv_scale: Optional[torch.Tensor]) -> None:
+    _run_mla_append(latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale)
+
+
 def _fake_mla(q, *args, **kwargs):
     B, H, R, _Dk = q.shape
     return q.new_empty((B, H, R, AttentionMLADecode.VALUE_DIMENSION)), q.new_empty((B, H, R), dtype=torch.float32)
@@ -923,6 +1014,13 @@ _HAVE_TREE_OPS = _HAVE["attention_decode_tree"] and _HAVE["attention_prefill_tre
 _HAVE_COMPACT_OP = _HAVE["kv_cache_compact"]
 _HAVE_SPLIT_OP = _HAVE["attention_prefill_split"]
 _HAVE_MLA_OP = _HAVE["attention_mla_decode"]
+# the ops of include/mfa_mla_cache.h, a list of their own: the append of the latent cache and MLA decode over an e4m3 latent cache
+_MLA_CACHE_OPS = [
+    ("mla_cache_append", _op_mla_append, _fake_none, ("kv_cache",)),
+    ("attention_mla_decode_fp8", _op_mla_decode_fp8, _fake_mla, ()),
+]
+_HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_CACHE_OPS})
+_HAVE_MLA_CACHE_OPS = _HAVE["mla_cache_append"] and _HAVE["attention_mla_decode_fp8"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1141,8 +1239,8 @@ def flash_mla_decode(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: tor
     latent followed by a 64-wide rotary part -- shared by every head: all 576 columns are the key, the first 512 the value.  Returns
     O [B, H, R, 512] (the caller applies the value up-projection), and with return_lse also L [B, H, R] fp32 in natural units.
     softmax_scale is the model's own scale on q . k (1 / sqrt(192) times a YaRN factor in those checkpoints) and is required.
-    cache_lengths [B] (GPU): valid keys per sequence INCLUDING the R new tokens, which the caller has already written into the cache (with
-    torch: there is no append kernel for the latent cache yet); with `causal` row r sees key c iff c <= r + max(len - R, 0).  kv_cache may
+    cache_lengths [B] (GPU): valid keys per sequence INCLUDING the R new tokens, which the caller has already written into the cache
+    (mla_cache_append, with the same lengths); with `causal` row r sees key c iff c <= r + max(len - R, 0).  kv_cache may
     be any view of that shape with a contiguous last dimension and a row stride that is a multiple of 8 (nothing is copied); with
     block_table [B, n] int32 it is a page pool [pages, pageSize, 576].  pieces: None lets the host cut the keys into pieces from the
     shapes, 1 is the unsplit launch, 2 .. 64 forces them; the workspace is allocated here.  Forward only, GPU only.  A sequence of length
@@ -1157,4 +1255,51 @@ def flash_mla_decode(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: tor
     pieces = 0 if pieces is None else pieces
     _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces)
     o, l = _call_op(_HAVE_MLA_OP, "attention_mla_decode", q, kv_cache, cache_lengths, block_table, bool(causal), float(softmax_scale), int(pieces))
+    return (o, l * _LN2) if return_lse else o
+
+
+def mla_cache_append(latent_new: torch.Tensor, rope_new: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, *,
+                     block_table: Optional[torch.Tensor] = None, kv_scale: Optional[torch.Tensor] = None) -> None:
+    """Writes the R new rows of every sequence into the latent cache of flash_mla_decode IN PLACE and returns nothing
+    (include/mfa_mla_cache.h): latent_new [B, R, 512] (the normalised latent) and rope_new [B, R, 64] (the rotated key part), bf16 or
+    fp16, become one cache row of 576.  Either may be any view with a contiguous last dimension and 16-byte rows -- the two slices of a
+    fused row of 576 are read where they lie.  cache_lengths [B] (GPU) ALREADY INCLUDES the new tokens -- the tensor the decode takes
+    next: row r of sequence b goes to key cache_lengths[b] - R + r; rows that fall before key 0, past the cache's capacity or past the
+    block table's row are not written, and no other byte of the cache is touched.  kv_cache: [B, C, 576] (or a strided view with a
+    contiguous last dimension) or, with block_table [B, n] int32, a page pool [pages, pageSize, 576]; the rows' own 16-bit type (bits
+    copied; kv_scale is an error) or torch.float8_e4m3fn (the rows are quantised: byte = e4m3(x / kv_scale[0]), round to nearest even,
+    saturating at +-448; kv_scale fp32 [1] on the GPU, None = 1.0 -- one scale for the latent and the rotary part alike).  R has no limit:
+    a prompt's rows go in one launch.  Goes through the op `mfa::mla_cache_append` (mutates_args) where torch has custom ops."""
+    who = "mla_cache_append"
+    if not all(t.is_cuda for t in (latent_new, rope_new, kv_cache, cache_lengths)):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (latent_new, rope_new, kv_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} writes in place and has no autograd: detach the inputs")
+    _check_mla_append(who, latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale)
+    _call_op(_HAVE_MLA_CACHE_OPS, "mla_cache_append", latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale)
+
+
+def flash_mla_decode_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, *, softmax_scale: float,
+                         kv_scale: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None, causal: bool = True,
+                         return_lse: bool = False, pieces: Optional[int] = None):
+    """flash_mla_decode over an FP8 latent cache (include/mfa_mla_cache.h): kv_cache [B, C, 576] torch.float8_e4m3fn (or, with
+    block_table, a page pool [pages, pageSize, 576]), as mla_cache_append writes it -- one row of 576 bytes per key, half the traffic and
+    half the memory of a 16-bit cache.  kv_scale fp32 [1] on the GPU (None = 1.0): a cache byte stands for kv_scale[0] x e4m3(byte),
+    latent and rotary part alike; it folds into the softmax scale and the final normalisation.  q [B, H, R, 576] bf16 or fp16 (R <= 32);
+    everything else -- softmax_scale (required), cache_lengths, causal, return_lse, pieces, O [B, H, R, 512] in q's type -- is
+    flash_mla_decode's.  kv_cache may be any view with a contiguous last dimension and strides that are multiples of 16 (nothing is
+    copied).  Forward only, GPU only.  Goes through the torch.library op `mfa::attention_mla_decode_fp8` where torch has custom ops, so it
+    traces under torch.compile."""
+    who = "flash_mla_decode_fp8"
+    if not (q.is_cuda and kv_cache.is_cuda and cache_lengths.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, kv_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} is forward only (no autograd): detach the inputs")
+    pieces = 0 if pieces is None else pieces
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces, True)
+    _latent_scale(who, kv_scale, kv_cache.device)
+    o, l = _call_op(_HAVE_MLA_CACHE_OPS, "attention_mla_decode_fp8", q, kv_cache, cache_lengths, block_table, bool(causal), float(softmax_scale),
+                    int(pieces), kv_scale)
     return (o, l * _LN2) if return_lse else o
