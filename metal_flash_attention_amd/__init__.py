@@ -13,6 +13,7 @@ from .attention import (  # noqa: F401
     AttentionKernelType,
     AttentionMLADecode,
     AttentionMLADecodeFP8,
+    AttentionMLASparseDecode,
     AttentionOperand,
     AttentionPrefill,
     GEMMOperandPrecision,
@@ -34,7 +35,7 @@ from .gemm import GEMMDescriptor, GEMMKernel, GEMMKernelDescriptor  # noqa: F401
 
 def __getattr__(name):
     # the torch functions of the KV-cache loop, on first use: torch stays optional for everything above
-    if name in ("kv_cache_compact", "tree_path", "flash_mla_decode", "flash_mla_decode_fp8", "mla_cache_append"):
+    if name in ("kv_cache_compact", "tree_path", "flash_mla_decode", "flash_mla_decode_fp8", "mla_cache_append", "flash_mla_sparse_decode"):
         from . import torch_binding
         return getattr(torch_binding, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1026,6 +1026,36 @@ class AttentionMLADecodeFP8(AttentionMLADecode):
         return (ctypes.byref(quant),), (quant, keep)
 
 
+class AttentionMLASparseDecode(AttentionMLADecode):
+    """Sparse MLA decode (include/mfa_mla_sparse.h): AttentionMLADecode's methods and arguments plus `indices`, device int32
+    [batches][rows][topk] -- the key POSITIONS row r of sequence b attends to, shared by all heads -- and `topk`.  -1, a position at or
+    past the length and a position past the causal frontier are holes: never loaded, never scored.  indexStrides: (row, batch) in
+    entries, default (topk, rows x topk).  The workspace formula is AttentionMLADecode's; the pieces are pieces of the list's slots, and
+    plannedSplit / workspaceSize plan over `topk`, not over `column`.
+
+        mla = AttentionMLASparseDecode(GEMMOperandPrecision.BF16)
+        need, pieces = mla.plannedSplit(rows=1, column=C, heads=128, batches=B, scale=s, indices=idx, topk=2048)
+        mla.dispatch(q, kv, o, l, cacheLengths=lengths, rows=1, column=C, heads=128, batches=B, scale=s, indices=idx, topk=2048, workspace=ws)
+    """
+
+    def _own(self, shape):
+        sparse = _abi.mfa_mla_sparse()
+        lib().mfa_mla_sparse_init(ctypes.byref(sparse))
+        keep = shape.pop("indices", None)
+        topk = int(shape.pop("topk", 0))
+        strides = shape.pop("indexStrides", None)
+        sparse.indices, sparse.topk = _pointer(keep), topk
+        sparse.indexRowStride, sparse.indexBatchStride = (int(strides[0]), int(strides[1])) if strides is not None else (topk, int(shape.get("rows", 0)) * topk)
+        return (ctypes.byref(sparse),), (sparse, keep)
+
+    def _entry(self, verb):
+        return getattr(lib(), "mfa_attention_mla_sparse_decode_" + verb)
+
+    def launch(self, q, kv, o, l=None, **shape) -> None:
+        """mfa_attention_mla_sparse_decode_launch (`dispatch` under the name the header uses)"""
+        self.dispatch(q, kv, o, l, **shape)
+
+
 class MLACacheAppend:
     """Appends the `rows` new rows of every sequence to the latent cache of MLA decode (include/mfa_mla_cache.h) -- latentNew
     [batches][rows][512] and ropeNew [batches][rows][64] become one cache row of 576 -- quantising them to e4m3 when the cache is FP8

@@ -33,7 +33,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLASparseDecode, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
                         KVCachePrecision, MLACacheAppend)
 
@@ -632,12 +632,27 @@ def _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, piec
         raise ValueError(f"{who}: pieces must be an int from 0 to 64 (None or 0: the host's plan, 1: unsplit), not {pieces!r}")
 
 
-def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces, fp8=False, kv_scale=None):
+def _check_mla_indices(who, q, indices):
+    """the lists of flash_mla_sparse_decode (include/mfa_mla_sparse.h): int32 [B, R, topk] on q's GPU, read where they lie"""
+    if not indices.is_cuda or indices.device != q.device:
+        raise RuntimeError(f"{who}: indices must live on the GPU of q (the host never reads a list)")
+    if indices.dtype != torch.int32:
+        raise TypeError(f"{who}: indices must be int32 key positions (got {indices.dtype})")
+    if indices.dim() != 3 or tuple(indices.shape[:2]) != (int(q.shape[0]), int(q.shape[2])) or indices.shape[2] < 1:
+        raise ValueError(f"{who}: indices must be [B, R, topk] = [{int(q.shape[0])}, {int(q.shape[2])}, topk >= 1], one list per sequence and row, "
+                         f"shared by all heads (got {tuple(indices.shape)})")
+    if indices.stride(2) != 1 or any(st < 0 for st in indices.stride()):
+        raise ValueError(f"{who}: indices must have a contiguous last dimension (a list is never copied)")
+
+
+def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces, fp8=False, kv_scale=None, indices=None):
     """flash_mla_decode's launch (include/mfa_mla.h) on q's device and torch's current stream -> (O [B, H, R, 512], L [B, H, R] base 2);
     the workspace of a launch cut along the keys is allocated here.  `fp8`: flash_mla_decode_fp8's, over an e4m3 latent cache with
     `kv_scale` (include/mfa_mla_cache.h) -- the strides of such a cache count bytes, which are its elements"""
-    who = "flash_mla_decode_fp8" if fp8 else "flash_mla_decode"
+    who = "flash_mla_sparse_decode" if indices is not None else "flash_mla_decode_fp8" if fp8 else "flash_mla_decode"
     _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces, fp8)
+    if indices is not None:
+        _check_mla_indices(who, q, indices)
     paged = block_table is not None
     q, q_strides = _new_operand(q)
     B, H, R, _Dk = q.shape
@@ -648,9 +663,12 @@ def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_sca
               column=int(kv_cache.shape[1]) * (int(block_table.shape[1]) if paged else 1))
     if paged:
         kw.update(pageSize=int(kv_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)), pageStride=int(kv_cache.stride(0)))
-    cls = AttentionMLADecodeFP8 if fp8 else AttentionMLADecode
+    cls = AttentionMLASparseDecode if indices is not None else AttentionMLADecodeFP8 if fp8 else AttentionMLADecode
     if fp8:
         kw.update(kvScale=_latent_scale(who, kv_scale, kv_cache.device))
+    if indices is not None:   # `indices`: flash_mla_sparse_decode's lists (include/mfa_mla_sparse.h), passed where they lie
+        topk = int(indices.shape[2])
+        kw.update(indices=indices, topk=topk, indexStrides=(int(indices.stride(1)) if R > 1 else topk, int(indices.stride(0)) if B > 1 else R * topk))
     key = (cls, q.dtype)
     host = _HOSTS.get(key)
     if host is None:
@@ -930,6 +948,12 @@ def _op_mla_decode_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: t
     return _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces, True, kv_scale)
 
 
+def _op_mla_sparse_decode(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, indices: torch.Tensor,
+                          block_table: Optional[torch.Tensor], causal: bool, softmax_scale: float, pieces: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(`pieces` as attention_mla_decode's, over the slots of a list; `indices` after the lengths)"""
+    return _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces, indices=indices)
+
+
 def _op_mla_append(latent_new: torch.Tensor, rope_new: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor,
                    block_table: Optional[torch.Tensor], kv_scale: Optional[torch.Tensor]) -> None:
     _run_mla_append(latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale)
@@ -1021,6 +1045,12 @@ _MLA_CACHE_OPS = [
 ]
 _HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_CACHE_OPS})
 _HAVE_MLA_CACHE_OPS = _HAVE["mla_cache_append"] and _HAVE["attention_mla_decode_fp8"]
+# the op of include/mfa_mla_sparse.h, in a list of its own
+_MLA_SPARSE_OPS = [
+    ("attention_mla_sparse_decode", _op_mla_sparse_decode, _fake_mla, ()),
+]
+_HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_SPARSE_OPS})
+_HAVE_MLA_SPARSE_OP = _HAVE["attention_mla_sparse_decode"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1302,4 +1332,30 @@ def flash_mla_decode_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths:
     _latent_scale(who, kv_scale, kv_cache.device)
     o, l = _call_op(_HAVE_MLA_CACHE_OPS, "attention_mla_decode_fp8", q, kv_cache, cache_lengths, block_table, bool(causal), float(softmax_scale),
                     int(pieces), kv_scale)
+    return (o, l * _LN2) if return_lse else o
+
+
+def flash_mla_sparse_decode(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, indices: torch.Tensor, *, softmax_scale: float,
+                            block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False,
+                            pieces: Optional[int] = None):
+    """flash_mla_decode over per-row lists of selected keys (DeepSeek-V3.2's sparse attention; include/mfa_mla_sparse.h): q [B, H, R, 576]
+    and indices [B, R, topk] int32 on the GPU, the key POSITIONS row r of sequence b attends to, shared by all H heads.  A position is
+    logical -- with block_table it is translated through the table as flash_mla_decode does.  -1, a position at or past
+    cache_lengths[b] and, with `causal`, a position past r + max(len - R, 0) are holes: their cache rows are never loaded.  A position
+    that appears twice counts twice; the order of a list is free.  A row without a visible entry gets O = 0.  indices may be any view
+    with a contiguous last dimension (nothing is copied).  kv_cache (bf16 or fp16, q's type), cache_lengths, softmax_scale (required),
+    return_lse and O [B, H, R, 512] are flash_mla_decode's; pieces cuts the SLOTS of a list (None: the host's plan from topk).  Forward
+    only, GPU only.  Goes through the torch.library op `mfa::attention_mla_sparse_decode` where torch has custom ops, so it traces under
+    torch.compile."""
+    who = "flash_mla_sparse_decode"
+    if not (q.is_cuda and kv_cache.is_cuda and cache_lengths.is_cuda and indices.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, kv_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} is forward only (no autograd): detach the inputs")
+    pieces = 0 if pieces is None else pieces
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces)
+    _check_mla_indices(who, q, indices)
+    o, l = _call_op(_HAVE_MLA_SPARSE_OP, "attention_mla_sparse_decode", q, kv_cache, cache_lengths, indices, block_table, bool(causal),
+                    float(softmax_scale), int(pieces))
     return (o, l * _LN2) if return_lse else o
