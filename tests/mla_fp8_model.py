@@ -9,7 +9,8 @@ quantisation error is no part of the bound.  The launch computes exactly mla_mod
                    that applies, and this kernel's own.  No wrong kernel is ever run.
   emulated()       the attention with the roundings and the order of sums of attn_mla8.h: what a correct kernel may give.
   CASES, inputs()  mla_model.CASES -- its lengths (700, 200, 100, 5, 0, 1500) in 1536 keys -- restated over byte caches, each with a
-                   kvScale of (None, 0.37, 3.0) in turn: non-powers of two make a missing or doubled scale visible.
+                   kvScale of (None, 0.37, 3.0) in turn: non-powers of two make a missing or doubled scale visible.  SEAM_CASES are
+                   mla_model.SEAM_CASES -- the lengths on the step, page, tile and column seams -- restated the same way.
 
 The bound is mla_model's (its docstring) with what attn_mla8.h adds.  The kernel contracts the same 576 exact products per score -- the
 conversion e4m3 -> 16-bit is exact, and a permuted contraction order is one more order of the same sum, which the (Dk + 3) u worst case
@@ -21,7 +22,7 @@ over ONE chain already covers -- and runs the same steps, exchange, softmax and 
     chain + 1 roundings on a sum of magnitude A + |O|.  chain >= 34 + 2 + 12 = 48, so u (A + |O|) <= E / 48.  L never meets it.
   E' = E (1 + 1 / (Dk + 3) + 1 / 48),  EL' = EL (1 + 1 / (Dk + 3)); bounds() and compare() are decode_model's over them.
 MARGIN is fixed by tests/test_mla_fp8_sensitivity.py alone, before any device run: the smallest power of two with at least 2 x headroom
-over emulated()'s worst err / bound at margin 1 on CASES.
+over emulated()'s worst err / bound at margin 1 on CASES and SEAM_CASES together.
 """
 import functools
 
@@ -30,7 +31,7 @@ import numpy as np
 import decode_model as dm
 import mla_model as mm
 from decode_model import Reference, bounds, compare, piece_ranges, round_to, store  # noqa: F401
-from mla_model import C, DK, DV, LENS, ROWS, SCALE, STEP, TILE  # noqa: F401
+from mla_model import C, DK, DV, LENS, ROWS, SCALE, SEAM_C, SEAM_LENS, SEAM_MUTANTS, STEP, TILE, facts_of, seen_lens  # noqa: F401
 
 MARGIN = 2
 KV_SCALES = (0.37, 3.0, None)
@@ -94,7 +95,7 @@ def model(q, kvb, kvscale, lens, causal, scale, mutant=None, *, pieces=None, pag
         return mm.model(q, kv[..., _ROPE_DOUBLED], lens, causal, scale, **kw)
     if mutant == "kv_scale_per_sequence":
         B = len(lens)
-        per = np.array([kvs] + [float(np.float32(s)) for s in SCALE_TAIL])[:B]
+        per = np.array([kvs] + [float(np.float32(s)) for s in (SCALE_TAIL * B)[:B - 1]])
         seen = np.broadcast_to(deq[:1], (B,) + deq.shape[1:]) if shared else deq
         return mm.model(q, seen * per[:, None, None], lens, causal, scale, **dict(kw, shared=False))
     ref = mm.model(q, kv, lens, causal, scale, **kw)
@@ -123,7 +124,7 @@ def emulated(q, kvb, kvscale, lens, causal, scale, fmt, *, pieces=None, shared=F
     NEG = -np.inf
     scale2 = f32(np.float32(np.float32(scale) * np.float32(1.44269504089)) * np.float32(kvs))
     for b in range(B):
-        n = int(lens[b])
+        n = min(int(lens[b]), deq.shape[1])
         if n == 0:
             continue
         ranges = piece_ranges(n, pieces, piece_range)
@@ -169,25 +170,29 @@ def emulated(q, kvb, kvscale, lens, causal, scale, fmt, *, pieces=None, shared=F
 # ---------------------------------------------------------------------------------------------------------------------- the cases
 # mla_model's launches, each over a byte cache with one of KV_SCALES in turn; "ld640": rows 640 BYTES apart
 CASES = {name: dict(case, kvscale=KV_SCALES[i % len(KV_SCALES)]) for i, (name, case) in enumerate(mm.CASES.items())}
+SEAM_CASES = {name: dict(case, kvscale=KV_SCALES[i % len(KV_SCALES)]) for i, (name, case) in enumerate(mm.SEAM_CASES.items())}
+ALL_CASES = dict(CASES, **SEAM_CASES)
 planned_pieces = mm.planned_pieces   # (the plan of the e4m3 launch is the 16-bit launch's: tests/test_mla_cache_plans.py)
 
 
 @functools.lru_cache(maxsize=None)
-def cache_bytes(seed=0):
+def cache_bytes(seed=0, batches=len(LENS), column=C):
     """kv [B, C, 576] uint8: e4m3 bytes of magnitude <= 1.0 (codes 0x00 .. 0x38) with a random sign, every key a value -- never 0x7f / 0xff"""
-    rng = np.random.default_rng(2000 + seed)
-    shape = (len(LENS), C, DK)
+    rng = np.random.default_rng(2000 + seed + (0 if (batches, column) == (len(LENS), C) else 7 * column))
+    shape = (batches, column, DK)
     return (rng.integers(0, 0x39, shape) | (rng.integers(0, 2, shape) << 7)).astype(np.uint8)
 
 
 @functools.lru_cache(maxsize=None)
 def inputs(name):
-    """(case, pieces, q, kv bytes, Reference, needle info) of a case, computed once and shared"""
-    case = CASES[name]
+    """(case, pieces, q, kv bytes, Reference, needle info) of a case of CASES or SEAM_CASES, computed once and shared; the lengths are
+    the case's own (mla_model.inputs)"""
+    case = ALL_CASES[name]
     pieces = planned_pieces(case)
-    kvb = cache_bytes()
+    lens = case["lens"]
+    kvb = cache_bytes(0, len(lens), case["C"])
     shared = case["layout"] == "shared"
-    q, info = mm.needle_queries(values_of(kvb, case["kvscale"]), LENS, case["H"], case["R"], case["causal"], case["fmt"], SCALE, pieces=pieces,
+    q, info = mm.needle_queries(values_of(kvb, case["kvscale"]), lens, case["H"], case["R"], case["causal"], case["fmt"], SCALE, pieces=pieces,
                                 page=case["page"], shared=shared)
-    ref = model(q, kvb, case["kvscale"], LENS, case["causal"], SCALE, pieces=pieces, page=case["page"], shared=shared)
+    ref = model(q, kvb, case["kvscale"], lens, case["causal"], SCALE, pieces=pieces, page=case["page"], shared=shared)
     return case, pieces, q, kvb, ref, info

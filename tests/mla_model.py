@@ -22,7 +22,12 @@ The bound is decode_model's, term for term (its docstring), with what the kernel
     chain = 34 steps + 2 pieces + 12 covers both (pieces = 1 unsplit), on a sum of magnitude A (numerator) and 1 (l).
   * P is rounded to the 16-bit type against the row's one running maximum (u_P A); the store rounds as decode's (u_out |O|).
 MARGIN is fixed by tests/test_mla_sensitivity.py alone, before any GPU run: the smallest power of two with at least 2 x headroom over
-emulated()'s worst err / bound at margin 1 on CASES.
+emulated()'s worst err / bound at margin 1 on CASES and SEAM_CASES together.
+
+Two batches.  LENS in a cache of C keys is the batch of CASES.  SEAM_LENS in a cache of SEAM_C keys is the batch of SEAM_CASES: lengths ON
+the seams a serving loop meets every few tokens -- full last steps, full last pages, whole piece tiles, n == column and n > column (the
+launch is handed 400; the header clamps it to the column, and so do model() and emulated(): a length past the cache's rows is read as
+the cache's rows).  A case carries its batch (lens, C); inputs() serves both dicts.
 """
 import functools
 import math
@@ -38,6 +43,10 @@ SLICE = 128                         # latent columns of a wave; its rotary colum
 MARGIN = 2
 SCALE = 0.1352337788608801          # 1 / sqrt(192) x (0.1 ln 40 + 1)^2: DeepSeek-V3's softmax scale under YaRN
 LENS, C = (700, 200, 100, 5, 0, 1500), 1536
+# the seam batch: one, two and three steps exactly (32, 64, 96), one key, n < R and n == R for R = 8, one past a step, full last pages for
+# every page size from 16 to 64, one and four whole tiles, n == column and n > column.  The sequence of 400 is followed by the empty one:
+# a kernel that does not clamp walks into that sequence's rows, which a launch fills with poison.
+SEAM_LENS, SEAM_C = (1, 8, 16, 32, 33, 64, 96, 256, 320, 400, 0), 320
 
 
 def chain_length(n, pieces):
@@ -47,7 +56,8 @@ def chain_length(n, pieces):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- mutants
-# name -> (what the defect is, where it changes nothing).  `case` has n, R, H, B, causal, pieces, page.
+# name -> (what the defect is, where it changes nothing).  `case` has n (the clamped length), raw (the length the launch is handed), C,
+# R, H, B, causal, pieces, page.
 MUTANTS = {
     "len_minus_2": ("c < len replaced by c <= len - 2", lambda c: False),
     "causal_plus_1": ("causal frontier one key too far", lambda c: not c["causal"] or c["R"] == 1 or c["n"] < 2),
@@ -55,6 +65,11 @@ MUTANTS = {
     "max_dropped": ("max(n - R, 0) replaced by n - R", lambda c: not c["causal"] or c["n"] >= c["R"]),
     "wave_partial_dropped": ("one wave's partial score left out of the sum of the step before the sequence's last", lambda c: c["n"] <= STEP),
     "final_partial_step_dropped": ("the partial last step is not run", lambda c: c["n"] % STEP == 0),
+    "full_last_step_dropped": ("the last step is not run when it is full", lambda c: c["n"] % STEP != 0),
+    "length_not_clamped": ("cacheLengths[b] not clamped to column: the keys column .. n - 1 are walked, in a packed cache the first rows "
+                           "of sequence b + 1", lambda c: c["raw"] <= c["C"]),
+    "page_boundary_key_from_next_page": ("a key on the last slot of a page read from slot 0 of the page after it",
+                                         lambda c: not c["page"] or c["n"] <= c["page"]),
     "piece_loses_last_tile": ("every piece stops one 64-key tile early", lambda c: not c["pieces"]),
     "piece_overlaps": ("every piece starts one tile early, inside its neighbour", lambda c: not c["pieces"] or c["n"] <= TILE),
     "combine_ignores_maxima": ("the combine adds the pieces without exp2(m_s - m*)", lambda c: not c["pieces"] or c["n"] <= TILE),
@@ -72,6 +87,15 @@ MUTANTS = {
 }
 
 
+SEAM_MUTANTS = ("full_last_step_dropped", "length_not_clamped")   # invisible on LENS by their own rule: only SEAM_CASES show them
+
+
+def facts_of(case, pieces, n):
+    """what a mutant's `harmless` rule is asked about: the case's launch and ONE sequence, n as the launch is handed it"""
+    return dict(R=case["R"], H=case["H"], B=len(case["lens"]), causal=case["causal"], pieces=pieces, page=case["page"], C=case["C"], raw=n,
+                n=min(n, case["C"]))
+
+
 def _query_of(mutant, h, r, H, R):
     """(head, row) whose q a (mutated) kernel reads for packed row p = h R + r"""
     p = h * R + r
@@ -85,7 +109,7 @@ def _query_of(mutant, h, r, H, R):
 def model(q, kv, lens, causal, scale, mutant=None, *, pieces=None, page=None, shared=False, piece_range=None):
     """float64 attention -> Reference(O, L, A, E, EL).  q [B, H, R, 576], kv [B, C, 576] (shared: sequence b reads kv[0], a launch with
     batchStride 0).  pieces / page: the launch's geometry (they change the bound's chain length and what the mutants do, never the
-    unmutated values)."""
+    unmutated values).  A length past the cache's C rows is clamped to C, as the launch clamps it to `column`."""
     assert mutant is None or mutant in MUTANTS, mutant
     q, kv = dm.f64(q), dm.f64(kv)
     B, H, R, _ = q.shape
@@ -94,7 +118,9 @@ def model(q, kv, lens, causal, scale, mutant=None, *, pieces=None, page=None, sh
     EL = np.zeros((B, H, R))
     sc = 1.0 / math.sqrt(DK) if mutant == "scale_sqrt_dk" else float(scale)
     for b in range(B):
-        n = int(lens[b])
+        n = min(int(lens[b]), kv.shape[1])
+        if mutant == "length_not_clamped":
+            n = int(lens[b])
         if n == 0:
             continue
         ranges = piece_ranges(n, pieces, piece_range)
@@ -105,10 +131,15 @@ def model(q, kv, lens, causal, scale, mutant=None, *, pieces=None, page=None, sh
         if mutant == "page_table_neighbour" and page:
             src_b = (b + 1) % B
         K = kv[src_b, :n]
+        if n > kv.shape[1]:                     # (length_not_clamped alone: the rows behind the cache's last are the next sequence's)
+            K = np.concatenate([kv[src_b], kv[(src_b + 1) % B]])[:n]
         if mutant == "page_off_by_one" and page:
             src = np.arange(n)
             first = (src >= page) & (src % page < 16)
             K = kv[src_b][np.where(first, src - page, src)]
+        if mutant == "page_boundary_key_from_next_page" and page:
+            src = np.arange(n)
+            K = kv[src_b][np.where((src % page == page - 1) & (src + 1 < n), src + 1, src)]
         V = K[:, 64:DK] if mutant == "v_from_tail" else K[:, :DV]
         Ks = K[:, :DV] if mutant == "rope_left_out" else K
         absV = np.abs(V)
@@ -131,6 +162,8 @@ def model(q, kv, lens, causal, scale, mutant=None, *, pieces=None, page=None, sh
                 vis &= cols <= qrow + base + off
             if mutant == "final_partial_step_dropped" and n % STEP:
                 vis[:, n // STEP * STEP:] = False
+            if mutant == "full_last_step_dropped" and n % STEP == 0:
+                vis[:, n - STEP:] = False
             mult = np.ones(n)
             if split and mutant == "piece_loses_last_tile":
                 for (pb, pe) in ranges:
@@ -206,7 +239,7 @@ def emulated(q, kv, lens, causal, scale, fmt, *, pieces=None, shared=False, piec
     NEG = -np.inf
     scale2 = float(np.float32(np.float32(scale) * np.float32(1.44269504089)))
     for b in range(B):
-        n = int(lens[b])
+        n = min(int(lens[b]), kv.shape[1])
         if n == 0:
             continue
         ranges = piece_ranges(n, pieces, piece_range)
@@ -254,6 +287,7 @@ def needle_queries(kv, lens, H, R, causal, fmt, scale, *, pieces=None, page=None
     1 / sqrt(Dk) to the caller's scale, so that a needle scores what it scores there"""
     kv = dm.f64(kv)
     B = len(lens)
+    lens = [min(int(n), kv.shape[1]) for n in lens]
     seen = np.broadcast_to(kv[:1], (B,) + kv.shape[1:]) if shared else kv
     q, info = dm.needle_queries(seen[:, None], lens, H, H, R, causal, fmt, pieces=pieces, page=page, piece_range=piece_range, seed=seed)
     return round_to(q / (scale * math.sqrt(DK)), fmt), info
@@ -261,9 +295,14 @@ def needle_queries(kv, lens, H, R, causal, fmt, scale, *, pieces=None, page=None
 
 # ---------------------------------------------------------------------------------------------------------------------- the cases
 # name -> the launch: fmt, H, R, causal, pieces (None: no workspace; "plan": the host's; a number: forced), page, layout ("packed",
-# "ld640": rows 640 elements apart in a larger allocation, "shared": batchStride 0, every sequence reads sequence 0's cache), out
-def _case(fmt, H, R, causal=True, pieces=None, page=None, layout="packed", out=None):
-    return dict(fmt=fmt, H=H, R=R, causal=causal, pieces=pieces, page=page, layout=layout, out=out or fmt)
+# "ld640": rows 640 elements apart in a larger allocation, "shared": batchStride 0, every sequence reads sequence 0's cache), out, and
+# the batch it runs on: lens as the launch is handed them, in a cache of C keys
+def _case(fmt, H, R, causal=True, pieces=None, page=None, layout="packed", out=None, lens=LENS, C=C):
+    return dict(fmt=fmt, H=H, R=R, causal=causal, pieces=pieces, page=page, layout=layout, out=out or fmt, lens=tuple(lens), C=C)
+
+
+def _seam(fmt, H, R, **kw):
+    return _case(fmt, H, R, lens=SEAM_LENS, C=SEAM_C, **kw)
 
 
 CASES = {
@@ -284,6 +323,31 @@ CASES = {
 }
 
 
+# the seam batch: the column is five 64-key tiles; n = 64 has one tile, n = 256 exactly four, so forced pieces leave pieces without a
+# tile (64 pieces), a last piece of one tile (2: 3 + 2) and one tile a piece (5).  Pages of 512 hold the whole column in ONE page: the
+# table has one entry a sequence
+SEAM_CASES = {
+    "s1 seam inside a head, unsplit": _seam("f16", 11, 3),
+    "s2 eight rows": _seam("bf16", 4, 8),
+    "s3 two groups, not causal": _seam("bf16", 40, 1, causal=False),
+    "s4 two pieces": _seam("bf16", 16, 1, pieces=2),
+    "s4 five pieces": _seam("f16", 11, 3, pieces=5),
+    "s4 sixty-four pieces, fp32 out": _seam("bf16", 4, 8, pieces=64, out="f32"),
+    "s5 pages of 16": _seam("f16", 16, 4, page=16),
+    "s5 pages of 32, two pieces": _seam("bf16", 16, 2, pieces=2, page=32),
+    "s5 pages of 64": _seam("f16", 11, 3, page=64),
+    "s5 pages of 64, five pieces": _seam("bf16", 16, 1, pieces=5, page=64),
+    "s6 pages of 512, one a sequence": _seam("bf16", 16, 2, page=512),
+    "s6 pages of 512, two pieces": _seam("f16", 16, 1, pieces=2, page=512),
+}
+ALL_CASES = dict(CASES, **SEAM_CASES)
+
+
+def seen_lens(case):
+    """the lengths the launch of a case reads: the case's, clamped to its column"""
+    return tuple(min(n, case["C"]) for n in case["lens"])
+
+
 def planned_pieces(case):
     """the piece count the launch of a case runs in (None: unsplit), from the library's own plan"""
     if case["pieces"] is None:
@@ -291,25 +355,28 @@ def planned_pieces(case):
     if case["pieces"] != "plan":
         return int(case["pieces"])
     from metal_flash_attention_amd import AttentionMLADecode
-    _bytes, pieces = AttentionMLADecode().plannedSplit(rows=case["R"], column=C, heads=case["H"], batches=len(LENS), scale=SCALE,
+    _bytes, pieces = AttentionMLADecode().plannedSplit(rows=case["R"], column=case["C"], heads=case["H"], batches=len(case["lens"]), scale=SCALE,
                                                        cacheLengths=0x1000)   # (the host never reads the lengths)
     return pieces if pieces > 1 else None
 
 
 @functools.lru_cache(maxsize=None)
-def cache_values(fmt, seed=0):
-    """kv [B, C, 576] float64 values of the 16-bit type, every key a value"""
-    rng = np.random.default_rng(1000 + seed + (fmt == "f16"))
-    return round_to(rng.uniform(-1.0, 1.0, (len(LENS), C, DK)), fmt)
+def cache_values(fmt, seed=0, batches=len(LENS), column=C):
+    """kv [B, C, 576] float64 values of the 16-bit type, every key a value (the empty sequence's and those past a length too: what a
+    mutant reads there is finite)"""
+    rng = np.random.default_rng(1000 + seed + (fmt == "f16") + (0 if (batches, column) == (len(LENS), C) else 7 * column))
+    return round_to(rng.uniform(-1.0, 1.0, (batches, column, DK)), fmt)
 
 
 @functools.lru_cache(maxsize=None)
 def inputs(name):
-    """(case, pieces, q, kv, Reference, needle info) of a case, computed once and shared"""
-    case = CASES[name]
+    """(case, pieces, q, kv, Reference, needle info) of a case of CASES or SEAM_CASES, computed once and shared; the lengths are the
+    case's own (case["lens"] as the launch is handed them, seen_lens(case) as it reads them)"""
+    case = ALL_CASES[name]
     pieces = planned_pieces(case)
-    kv = cache_values(case["fmt"])
+    lens = case["lens"]
+    kv = cache_values(case["fmt"], 0, len(lens), case["C"])
     shared = case["layout"] == "shared"
-    q, info = needle_queries(kv, LENS, case["H"], case["R"], case["causal"], case["fmt"], SCALE, pieces=pieces, page=case["page"], shared=shared)
-    ref = model(q, kv, LENS, case["causal"], SCALE, pieces=pieces, page=case["page"], shared=shared)
+    q, info = needle_queries(kv, lens, case["H"], case["R"], case["causal"], case["fmt"], SCALE, pieces=pieces, page=case["page"], shared=shared)
+    ref = model(q, kv, lens, case["causal"], SCALE, pieces=pieces, page=case["page"], shared=shared)
     return case, pieces, q, kv, ref, info

@@ -11,13 +11,16 @@ cache was gathered.
   emulated()       the kernel's roundings and order of sums: 32-SLOT steps with the holes kept in their slots (a step of holes changes
                    nothing), pieces of slots, the pieces combined in order.
   needle_queries() mla_model's needle rows over the gathered caches: the last two visible slots and the geometry's special slots.
-  CASES, inputs()  the launches of tests/test_mla_sparse_gpu.py, which tests/test_mla_sparse_sensitivity.py walks on the CPU.
+  CASES, inputs()  the launches of tests/test_mla_sparse_gpu.py, which tests/test_mla_sparse_sensitivity.py walks on the CPU.  SEAM_CASES
+                   run on mla_model's seam batch (SEAM_LENS in SEAM_C keys) with lists that sit ON the rule's seams: n - 1, n, 0, the
+                   frontier and the key after it, column - 1 and the positions in [column, cacheLengths[b]) of the sequence handed a
+                   length past the column, entries below -1.  A case carries its batch (lens, C).
 
 Mutants.  Those of mla_model that are statements about columns survive the reduction unchanged and are passed through (DENSE_MUTANTS).
 Its mutants about lengths, the causal frontier, steps, pieces, pages and packing are statements about the dense walk over key ranges;
 their counterparts over a list are this module's own (MUTANTS), each a change of which slots are visible or of what a slot reads.
 MARGIN is fixed by tests/test_mla_sparse_sensitivity.py alone, before any GPU run: the smallest power of two with at least 2 x headroom
-over emulated()'s worst err / bound at margin 1 on CASES.
+over emulated()'s worst err / bound at margin 1 on CASES and SEAM_CASES together.
 """
 import functools
 
@@ -26,14 +29,16 @@ import numpy as np
 import decode_model as dm
 import mla_model as mm
 from decode_model import LOG2E, U32, Reference, piece_ranges, round_to
-from mla_model import DK, DV, LENS, SCALE, STEP, C, bounds, chain_length, compare, store  # noqa: F401
+from mla_model import DK, DV, LENS, SCALE, SEAM_C, SEAM_LENS, STEP, C, bounds, chain_length, compare, seen_lens, store  # noqa: F401
 
 MARGIN = 2
 HOLE = -1
 B = len(LENS)
+PAD = 96             # rows of poison a seam launch keeps in front of and behind every sequence: where an entry in [-PAD, C + PAD) lands
 
 DENSE_MUTANTS = ("v_from_tail", "rope_left_out", "scale_sqrt_dk", "o_blocks_exchanged")
-# name -> (what the defect is, where it changes nothing).  `case` has R, H, causal, pieces (None: unsplit), page, topk
+# name -> (what the defect is, where it changes nothing).  `case` has R, H, causal, pieces (None: unsplit), page, topk, n (the clamped
+# length), raw (the length the launch is handed), C and negatives (the lists hold an entry below -1)
 MUTANTS = {
     "list_of_next_row": ("the list of row r + 1", lambda c: c["R"] == 1),
     "list_of_next_sequence": ("the list of sequence b + 1", lambda c: False),
@@ -49,7 +54,13 @@ MUTANTS = {
     "holes_step_resets_m": ("a step of 32 holes resets the running maximum", lambda c: False),
     "head_mod_32": ("head 32 group + q taken modulo 32", lambda c: c["H"] <= 32),
     "rows_swapped": ("the R rows of a head swapped", lambda c: c["R"] == 1),
+    "length_not_clamped": ("cacheLengths[b] not clamped to column: a listed position in [column, cacheLengths[b]) is visible and reads "
+                           "the row of sequence b + 1 that lies there in a packed cache", lambda c: c["raw"] <= c["C"]),
+    "only_minus_one_is_a_hole": ("only -1 is a hole: an entry below -1 is scored, with the row of key 0", lambda c: not c["negatives"]),
+    "last_key_of_the_column_hidden": ("the length clamped to column - 1: the last key a full cache holds is a hole",
+                                      lambda c: c["n"] < c["C"]),
 }
+SEAM_MUTANTS = ("length_not_clamped", "only_minus_one_is_a_hole", "last_key_of_the_column_hidden")   # only SEAM_CASES show them
 MUTANTS.update({name: mm.MUTANTS[name] for name in DENSE_MUTANTS})
 
 
@@ -62,10 +73,16 @@ def visible(c, n, r, R, causal):
     return ok
 
 
-def page_table(page, seed=None):
-    """the permuted block table [B, C // page] of the paged cases (numpy; the GPU file lays its pool out by it)"""
-    pps = C // page
-    return np.random.default_rng(page if seed is None else seed).permutation(B * pps).reshape(B, pps).astype(np.int32)
+def facts_of(case, pieces, n, idx):
+    """what a mutant's `harmless` rule is asked about: the case's launch, its lists and ONE sequence, n as the launch is handed it"""
+    return dict(R=case["R"], H=case["H"], B=len(case["lens"]), causal=case["causal"], pieces=pieces, page=case["page"], topk=case["topk"],
+                C=case["C"], raw=n, n=min(n, case["C"]), negatives=bool((np.asarray(idx) < HOLE).any()))
+
+
+def page_table(page, seed=None, batches=B, column=C):
+    """the permuted block table [B, ceil(C / page)] of the paged cases (numpy; the GPU file lays its pool out by it)"""
+    pps = -(-column // page)
+    return np.random.default_rng(page if seed is None else seed).permutation(batches * pps).reshape(batches, pps).astype(np.int32)
 
 
 def gathered(kv, lens, idx, R, causal, mutant=None, *, pieces=None, page=None, shared=False, piece_range=None):
@@ -73,13 +90,18 @@ def gathered(kv, lens, idx, R, causal, mutant=None, *, pieces=None, page=None, s
     a (mutated) kernel scores without having loaded a row reads zeros: score 0, value 0."""
     kv = dm.f64(kv)
     idx = np.asarray(idx, dtype=np.int64)
+    B, C = len(lens), kv.shape[1]                                # (the batch is the caller's: a length past the cache's C rows is clamped)
     topk = idx.shape[2]
     flat = idx.reshape(-1)
     ranges = piece_ranges(topk, pieces, piece_range)
-    table = page_table(page) if page else None
+    table = page_table(page, None, B, C) if page else None
     out = []
     for b in range(B):
-        n = int(lens[b])
+        n = min(int(lens[b]), C)
+        if mutant == "length_not_clamped":
+            n = int(lens[b])
+        if mutant == "last_key_of_the_column_hidden":
+            n = min(n, C - 1)
         src = 0 if shared else b
         for r in range(R):
             lb, lr = b, r
@@ -96,6 +118,8 @@ def gathered(kv, lens, idx, R, causal, mutant=None, *, pieces=None, page=None, s
                 c = np.concatenate([c, np.full(steps - topk, HOLE, dtype=np.int64)])
             if mutant == "minus_one_reads_key_0":
                 c = np.where(c == HOLE, 0, c)
+            if mutant == "only_minus_one_is_a_hole" and n:
+                c = np.where(c < HOLE, 0, c)
             ok = visible(c, n if mutant != "length_not_masked" else C, r, R, causal and mutant not in ("causal_dropped", "length_not_masked"))
             if mutant == "length_not_masked" and causal:   # (the frontier still holds for the keys below the length)
                 ok &= (c >= n) | (c <= r + max(n - R, 0))
@@ -126,6 +150,8 @@ def gathered(kv, lens, idx, R, causal, mutant=None, *, pieces=None, page=None, s
                 if mutant == "position_as_physical_slot" and page:   # physical slot c of the pool: the key that lives there, or poison
                     hit = np.argwhere(table == c[s] // page)
                     rows[i] = kv[0 if shared else hit[0][0], hit[0][1] * page + c[s] % page] if len(hit) else np.nan
+                elif c[s] >= C:                                     # (length_not_clamped alone: behind the cache's last row lies the next sequence)
+                    rows[i] = kv[(src + 1) % B, c[s] - C]
                 else:
                     rows[i] = kv[src, c[s]]
             out.append((rows, slots))
@@ -183,7 +209,7 @@ def emulated(q, kv, lens, idx, causal, scale, fmt, *, pieces=None, shared=False,
     scale2 = float(np.float32(np.float32(scale) * np.float32(1.44269504089)))
     ranges = piece_ranges(topk, pieces, piece_range)
     for b in range(B_):
-        n = int(lens[b])
+        n = min(int(lens[b]), kv.shape[1])
         for r in range(R):
             c = idx[b, r]
             ok = visible(c, n, r, R, causal)
@@ -223,6 +249,7 @@ def needle_queries(kv, lens, idx, H, R, causal, fmt, scale, *, pieces=None, shar
     the gathered cache -- from mla_model.needle_queries over the gathered caches (not causal there: no forbidden key; a hole's row is
     not in the cache at all, and the mutants of the list are what shows a hole that was read)"""
     parts = gathered(kv, lens, idx, R, causal, shared=shared)
+    B = len(lens)
     width = max(1, max(len(rows) for rows, _s in parts))
     kvg = np.zeros((B * R, width, DK))
     for i, (rows, _s) in enumerate(parts):
@@ -233,8 +260,16 @@ def needle_queries(kv, lens, idx, H, R, causal, fmt, scale, *, pieces=None, shar
 
 
 # ---------------------------------------------------------------------------------------------------------------------- the cases
-def _case(fmt, H, R, topk, lists, causal=True, pieces=None, page=None, layout="packed", out=None):
-    return dict(fmt=fmt, H=H, R=R, topk=topk, lists=lists, causal=causal, pieces=pieces, page=page, layout=layout, out=out or fmt)
+def _case(fmt, H, R, topk, lists, causal=True, pieces=None, page=None, layout="packed", out=None, lens=LENS, C=C):
+    return dict(fmt=fmt, H=H, R=R, topk=topk, lists=lists, causal=causal, pieces=pieces, page=page, layout=layout, out=out or fmt,
+                lens=tuple(lens), C=C)
+
+
+def _seam(fmt, H, R, topk, **kw):
+    """a case on the seam batch.  Contiguous ("padded": PAD rows of poison around every sequence) its lists hold entries below -1; paged
+    they hold none, and positions up to C + PAD instead, which a widened block table sends to the page of poison"""
+    kw.setdefault("layout", "packed" if kw.get("page") else "padded")
+    return _case(fmt, H, R, topk, "seam, paged" if kw.get("page") else "seam", lens=SEAM_LENS, C=SEAM_C, **kw)
 
 
 # lists: how the lists are drawn (lists_of).  pieces: None runs without a workspace; "plan" is the host's; a number is forced
@@ -257,10 +292,60 @@ CASES = {
 }
 
 
+# topk 32, 64 and 96 are whole steps (no slot past topk pads the last one), 33 is one slot more.  96 slots are two 64-slot tiles: two pieces
+SEAM_CASES = {
+    "s thirty-two slots, a seam inside a head": _seam("f16", 11, 3, 32),
+    "s sixty-four slots, eight rows": _seam("bf16", 4, 8, 64),
+    "s ninety-six slots, two groups, not causal": _seam("bf16", 40, 1, 96, causal=False),
+    "s ninety-six slots, two pieces": _seam("f16", 16, 2, 96, pieces=2),
+    "s thirty-three slots": _seam("f16", 8, 2, 33),
+    "s pages of 16, thirty-two slots": _seam("bf16", 16, 1, 32, page=16),
+    "s pages of 32, ninety-six slots, two pieces": _seam("f16", 11, 3, 96, pieces=2, page=32),
+    "s pages of 64, thirty-three slots": _seam("bf16", 4, 8, 33, page=64),
+    "s pages of 512, sixty-four slots": _seam("f16", 16, 2, 64, page=512),
+}
+ALL_CASES = dict(CASES, **SEAM_CASES)
+
+
+def seam_lists_of(case, rng):
+    """idx [B, R, topk] on the seams of the rule `0 <= c < min(len, column)` and, causal, `c <= frontier`: every list of a live
+    sequence holds n - 1, n, 0 and, causal, the row's frontier and the key after it; where the launch is handed n > column also
+    column - 1 (visible), column, column + 1 and n - 1 (holes); then entries below -1 (-2, -17, -PAD; contiguous caches only) or, paged,
+    positions up to column + PAD - 1; the rest are visible positions and -1, shuffled"""
+    R, topk, lens, C_, paged = case["R"], case["topk"], case["lens"], case["C"], bool(case["page"])
+    idx = np.full((len(lens), R, topk), HOLE, dtype=np.int64)
+    for b, raw in enumerate(lens):
+        n = min(raw, C_)
+        if n == 0:
+            idx[b] = rng.integers(0, C_, (R, topk))                  # the empty sequence: every position is a hole
+            continue
+        for r in range(R):
+            fr = r + max(n - R, 0)
+            must = [raw - 1, raw, 0] + ([fr, fr + 1] if case["causal"] else [])
+            if raw > C_:
+                must += [C_ - 1, C_, C_ + 1]
+            must += [C_ + PAD - 1, C_ + 5] if paged else [-2, -17, -PAD]
+            must = list(dict.fromkeys(must))
+            limit = min(n, fr + 1) if case["causal"] else n
+            free = np.setdiff1d(np.arange(limit), must)
+            take = min(len(free), (3 * (topk - len(must))) // 4)
+            row = np.full(topk, HOLE, dtype=np.int64)
+            row[:len(must)] = must
+            row[len(must):len(must) + take] = rng.choice(free, size=take, replace=False)
+            rng.shuffle(row)
+            idx[b, r] = row
+    lo, hi = (0, C_ + PAD) if paged else (-PAD, C_ + PAD)
+    assert ((idx == HOLE) | ((idx >= lo) & (idx < hi))).all()
+    return idx
+
+
 def lists_of(case, seed=0):
-    """idx [B, R, topk] int64: every entry is -1 or a position in [0, C)"""
+    """idx [B, R, topk] int64: every entry is -1 or a position in [0, C) -- on the seam batch (seam_lists_of) in [-PAD, C + PAD)"""
     R, topk, kind = case["R"], case["topk"], case["lists"]
+    LENS, C, B = case["lens"], case["C"], len(case["lens"])
     rng = np.random.default_rng(4000 + seed + topk + 7 * R)
+    if kind.startswith("seam"):
+        return seam_lists_of(case, rng)
     idx = np.full((B, R, topk), HOLE, dtype=np.int64)
     for b, n in enumerate(LENS):
         for r in range(R):
@@ -303,28 +388,31 @@ def planned_pieces(case):
     if case["pieces"] != "plan":
         return int(case["pieces"])
     from metal_flash_attention_amd import AttentionMLASparseDecode
-    _bytes, pieces = AttentionMLASparseDecode().plannedSplit(rows=case["R"], column=C, heads=case["H"], batches=B, scale=SCALE, cacheLengths=0x1000,
+    _bytes, pieces = AttentionMLASparseDecode().plannedSplit(rows=case["R"], column=case["C"], heads=case["H"], batches=len(case["lens"]), scale=SCALE, cacheLengths=0x1000,
                                                              indices=0x2000, topk=case["topk"])   # (the host reads neither)
     return pieces if pieces > 1 else None
 
 
 @functools.lru_cache(maxsize=None)
 def inputs(name):
-    """(case, pieces, q, kv, idx, Reference, needle info) of a case, computed once and shared"""
-    case = CASES[name]
+    """(case, pieces, q, kv, idx, Reference, needle info) of a case of CASES or SEAM_CASES, computed once and shared; the lengths are
+    the case's own (case["lens"] as the launch is handed them, seen_lens(case) as it reads them)"""
+    case = ALL_CASES[name]
     pieces = planned_pieces(case)
-    kv = mm.cache_values(case["fmt"])
+    lens = case["lens"]
+    kv = mm.cache_values(case["fmt"], 0, len(lens), case["C"])
     idx = lists_of(case)
     shared = case["layout"] == "shared"
-    q, info = needle_queries(kv, LENS, idx, case["H"], case["R"], case["causal"], case["fmt"], SCALE, pieces=pieces, shared=shared)
-    ref = model(q, kv, LENS, idx, case["causal"], SCALE, pieces=pieces, page=case["page"], shared=shared)
+    q, info = needle_queries(kv, lens, idx, case["H"], case["R"], case["causal"], case["fmt"], SCALE, pieces=pieces, shared=shared)
+    ref = model(q, kv, lens, idx, case["causal"], SCALE, pieces=pieces, page=case["page"], shared=shared)
     return case, pieces, q, kv, idx, ref, info
 
 
-def keep_mask(idx, causal, R):
+def keep_mask(idx, causal, R, lens=LENS, column=C):
     """[B][C]: the cache rows some list of the launch makes visible -- everything else may hold poison"""
-    keep = np.zeros((B, C), dtype=bool)
-    for b, n in enumerate(LENS):
+    keep = np.zeros((len(lens), column), dtype=bool)
+    for b, n in enumerate(lens):
+        n = min(n, column)
         for r in range(R):
             c = idx[b, r]
             keep[b, c[visible(c, n, r, R, causal)]] = True

@@ -1,4 +1,5 @@
-"""CPU test of the oracle of tests/test_mla_gpu.py (tests/mla_model.py): on that file's cases, a correct kernel -- emulated(), the model
+"""CPU test of the oracle of tests/test_mla_gpu.py (tests/mla_model.py): on that file's cases -- CASES on the batch LENS and SEAM_CASES
+on the batch SEAM_LENS, whose lengths lie on the step, page, tile and column seams -- a correct kernel -- emulated(), the model
 with the kernel's roundings and order of sums -- lies inside bounds(), and every named mutant, what a defect of the kernels or of the
 host plan would compute, lies outside on at least one case where its defect can show.  MARGIN is fixed HERE, before any GPU run: the
 smallest power of two with at least 2 x headroom over emulated()'s worst err / bound at margin 1.  No wrong kernel is ever run; the
@@ -25,9 +26,9 @@ def _ratio(o, l, ref, fmt, out):
 def worst():
     """name -> (worst O ratio, worst L ratio) of emulated() on every case, once"""
     out = {}
-    for name in mm.CASES:
+    for name in mm.ALL_CASES:
         case, pieces, q, kv, ref, _info = mm.inputs(name)
-        o, l = mm.emulated(q, kv, mm.LENS, case["causal"], mm.SCALE, case["fmt"], pieces=pieces, shared=case["layout"] == "shared")
+        o, l = mm.emulated(q, kv, case["lens"], case["causal"], mm.SCALE, case["fmt"], pieces=pieces, shared=case["layout"] == "shared")
         out[name] = _ratio(o, l, ref, case["fmt"], case["out"])
         print("%s: emulated worst |dO| / bound %.3f, |dL| / bound %.3f at margin 1" % ((name,) + out[name]))
     return out
@@ -55,6 +56,46 @@ def test_the_cases_meet_what_they_are_for():
     assert mm.planned_pieces(mm.CASES["2 seam inside a head, planned"]) == 6  # 12 workgroups: 42, and 6 again
     assert 0 in mm.LENS and 5 in mm.LENS and max(mm.LENS) // mm.TILE >= 16 and any(n % mm.STEP for n in mm.LENS)
     assert any(0 < -(-n // mm.TILE) < 7 for n in mm.LENS)                    # sequences with fewer tiles than pieces
+    assert all(c["lens"] == mm.LENS and c["C"] == mm.C for c in mm.CASES.values())
+    the_seam_cases_meet_what_they_are_for()
+
+
+def the_seam_cases_meet_what_they_are_for():
+    """(the second half of test_the_cases_meet_what_they_are_for)"""
+    lens, C, cases = mm.SEAM_LENS, mm.SEAM_C, mm.SEAM_CASES
+    assert all(c["lens"] == lens and c["C"] == C for c in cases.values()) and not set(cases) & set(mm.CASES)
+    seen = mm.seen_lens(next(iter(cases.values())))
+    assert any(n and n % mm.STEP == 0 for n in lens) and any(n % mm.STEP for n in lens)          # a full last step, and a partial one
+    pages = sorted({c["page"] for c in cases.values() if c["page"]})
+    assert pages == [16, 32, 64, 512]
+    for page in (16, 32, 64):                                                 # a full last page of one and of several pages, a partial one
+        assert page in seen and any(n > page and n % page == 0 for n in seen) and any(n > page and n % page for n in seen), page
+    assert 512 > C                                                            # one page holds the column: blockTableStride 1
+    assert C in lens and max(lens) > C and seen[lens.index(max(lens))] == C   # n == C, and n > C read as C
+    assert lens[lens.index(max(lens)) + 1] == 0 and lens[-1] == 0             # the empty sequence's rows follow the one past the column
+    assert {mm.STEP, 2 * mm.STEP, 3 * mm.STEP} <= set(lens)                   # exactly one, two and three steps
+    assert {mm.TILE, 4 * mm.TILE, C} <= set(lens) and C == 5 * mm.TILE        # whole piece tiles: one, four, five
+    eight = cases["s2 eight rows"]
+    assert eight["R"] == 8 and eight["causal"] and 8 in lens and any(0 < n < 8 for n in lens)   # n == R and n < R
+    assert sorted(c["pieces"] for c in cases.values() if c["pieces"] and not c["page"]) == [2, 5, 64]
+    assert any(c["pieces"] and c["page"] for c in cases.values()) and any(not c["pieces"] and c["page"] for c in cases.values())
+    groups = lambda c: -(-c["H"] * c["R"] // mm.ROWS)  # noqa: E731
+    assert groups(cases["s1 seam inside a head, unsplit"]) == 2 and groups(cases["s3 two groups, not causal"]) == 2
+    assert not cases["s3 two groups, not causal"]["causal"]
+
+
+@pytest.mark.parametrize("mutant", mm.SEAM_MUTANTS)
+def test_a_seam_mutant_is_invisible_to_the_old_batch(mutant):
+    """the gap the seam batch closes: by its own rule the defect changes nothing on any sequence of any case of LENS (and on the
+    cheapest of them the mutated model IS the model), while some sequence of SEAM_LENS lets it show"""
+    _what, harmless = mm.MUTANTS[mutant]
+    for name, case in mm.CASES.items():
+        assert all(harmless(mm.facts_of(case, mm.planned_pieces(case), n)) for n in case["lens"] if n), name
+    case, pieces, q, kv, ref, _info = mm.inputs("4 one row")
+    bad = mm.model(q, kv, case["lens"], case["causal"], mm.SCALE, mutant, pieces=pieces, page=case["page"])
+    assert np.array_equal(bad.O, ref.O) and np.array_equal(bad.L, ref.L)
+    for name, case in mm.SEAM_CASES.items():
+        assert any(not harmless(mm.facts_of(case, mm.planned_pieces(case), n)) for n in case["lens"] if n), name
 
 
 @pytest.mark.parametrize("mutant", sorted(mm.MUTANTS))
@@ -63,12 +104,12 @@ def test_every_mutant_lies_outside(mutant):
     walk; a mutant that shows nowhere fails"""
     _what, harmless = mm.MUTANTS[mutant]
     tried = []
-    for name in mm.CASES:
-        case, pieces, q, kv, ref, _info = mm.inputs(name)
-        facts = dict(R=case["R"], H=case["H"], B=len(mm.LENS), causal=case["causal"], pieces=pieces, page=case["page"])
-        if all(harmless(dict(facts, n=n)) for n in mm.LENS if n):
+    for name in mm.ALL_CASES:
+        case, pieces = mm.ALL_CASES[name], mm.planned_pieces(mm.ALL_CASES[name])
+        if all(harmless(mm.facts_of(case, pieces, n)) for n in case["lens"] if n):
             continue
-        bad = mm.model(q, kv, mm.LENS, case["causal"], mm.SCALE, mutant, pieces=pieces, page=case["page"], shared=case["layout"] == "shared")
+        case, pieces, q, kv, ref, _info = mm.inputs(name)
+        bad = mm.model(q, kv, case["lens"], case["causal"], mm.SCALE, mutant, pieces=pieces, page=case["page"], shared=case["layout"] == "shared")
         fmt, out = case["fmt"], case["out"]
         bo, bl = mm.bounds(ref, fmt, out)
         wo = float((np.abs(mm.store(bad.O, out) - ref.O) / bo).max())          # (err / bound at MARGIN: outside is > 1)
@@ -80,4 +121,5 @@ def test_every_mutant_lies_outside(mutant):
         if max(wo, wl) > 1.0:
             return
     assert tried, "no case lets %s show" % mutant
+    assert np.isfinite(bad.O).all(), "a mutant computes finite wrong values"
     pytest.fail("%s stays inside the bounds on every case where it can show: %r" % (mutant, tried))

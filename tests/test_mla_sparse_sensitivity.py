@@ -1,4 +1,5 @@
-"""CPU test of the oracle of tests/test_mla_sparse_gpu.py (tests/mla_sparse_model.py): on that file's cases, a correct kernel --
+"""CPU test of the oracle of tests/test_mla_sparse_gpu.py (tests/mla_sparse_model.py): on that file's cases -- CASES and, on the seam
+batch of tests/mla_model.py with lists on the seams of the visibility rule, SEAM_CASES -- a correct kernel --
 emulated(), the model with the kernel's roundings, its 32-slot steps with the holes in their slots and its pieces of slots -- lies inside
 the bounds, and every named mutant, what a defect of the kernels or of the host plan would compute, lies outside on at least one case
 where its defect can show.  MARGIN is fixed HERE, before any GPU run: the smallest power of two with at least 2 x headroom over
@@ -26,9 +27,9 @@ def _ratio(o, l, ref, fmt, out):
 def worst():
     """name -> (worst O ratio, worst L ratio) of emulated() on every case, once"""
     out = {}
-    for name in sm.CASES:
+    for name in sm.ALL_CASES:
         case, pieces, q, kv, idx, ref, _info = sm.inputs(name)
-        o, l = sm.emulated(q, kv, sm.LENS, idx, case["causal"], sm.SCALE, case["fmt"], pieces=pieces, shared=case["layout"] == "shared")
+        o, l = sm.emulated(q, kv, case["lens"], idx, case["causal"], sm.SCALE, case["fmt"], pieces=pieces, shared=case["layout"] == "shared")
         out[name] = _ratio(o, l, ref, case["fmt"], case["out"])
         print("%s: emulated worst |dO| / bound %.3f, |dL| / bound %.3f at margin 1" % ((name,) + out[name]))
     return out
@@ -71,6 +72,53 @@ def test_the_cases_meet_what_they_are_for():
     for name in cases:
         idx = sm.inputs(name)[4]
         assert ((idx == sm.HOLE) | ((idx >= 0) & (idx < sm.C))).all(), name
+    the_seam_cases_meet_what_they_are_for()
+
+
+def the_seam_cases_meet_what_they_are_for():
+    """(the second half of test_the_cases_meet_what_they_are_for)"""
+    cases, lens, C = sm.SEAM_CASES, sm.SEAM_LENS, sm.SEAM_C
+    assert all(c["lens"] == lens and c["C"] == C for c in cases.values()) and not set(cases) & set(sm.CASES)
+    assert sorted({c["topk"] for c in cases.values()}) == [32, 33, 64, 96] and sorted({c["page"] for c in cases.values() if c["page"]}) == [16, 32, 64, 512]
+    assert any(c["pieces"] and c["page"] for c in cases.values()) and any(c["pieces"] and not c["page"] for c in cases.values())
+    assert C in lens and max(lens) > C and max(lens) < C + sm.PAD
+    for name, case in cases.items():
+        idx, R, causal, paged = sm.inputs(name)[4], case["R"], case["causal"], bool(case["page"])
+        assert idx.shape == (len(lens), R, case["topk"])
+        assert ((idx >= (0 if paged else -sm.PAD)) | (idx == sm.HOLE)).all() and (idx < C + sm.PAD).all(), name   # inside what the launch poisons
+        assert paged == (case["layout"] == "packed") and (paged or case["layout"] == "padded")
+        for b, raw in enumerate(lens):
+            n = min(raw, C)
+            for r in range(R if n else 0):
+                row, vis = idx[b, r], sm.visible(idx[b, r], n, r, R, causal)
+                fr = r + max(n - R, 0)
+                assert {raw - 1, raw, 0} <= set(row) and (not causal or {fr, fr + 1} <= set(row)), (name, b, r)
+                assert vis[row == 0].all() and vis[row == min(fr, n - 1) if causal else row == n - 1].all(), (name, b, r)   # the first and the last visible key
+                assert not vis[row == n].any() and not vis[row < 0].any() and not vis[row >= C].any()
+                if causal and fr + 1 < n:
+                    assert not vis[row == fr + 1].any()
+                if raw >= C and (not causal or r == R - 1):
+                    assert vis[row == C - 1].all() and (row == C - 1).any(), (name, b, r)                # the column's last key is visible
+                if raw > C:
+                    assert ((row >= C) & (row < raw)).sum() >= 3 and {C, raw - 1} <= set(row)            # positions in [C, n): holes
+                if paged:
+                    assert (row >= C).any() and (row[row != sm.HOLE] >= 0).all()
+                else:
+                    assert {-2, -17, -sm.PAD} <= set(row)
+
+
+@pytest.mark.parametrize("mutant", sm.SEAM_MUTANTS)
+def test_a_seam_mutant_is_invisible_to_the_old_batch(mutant):
+    """by its own rule the defect changes nothing on any sequence of any case of LENS -- no length reaches the column, no list holds an
+    entry below -1 -- and on one of them the mutated model IS the model; some seam case lets it show"""
+    _what, harmless = sm.MUTANTS[mutant]
+    for name, case in sm.CASES.items():
+        idx = sm.lists_of(case)
+        assert all(harmless(sm.facts_of(case, sm.planned_pieces(case), n, idx)) for n in case["lens"] if n), name
+    case, pieces, q, kv, idx, ref, _info = sm.inputs("b thirty-three slots")
+    bad = sm.model(q, kv, case["lens"], idx, case["causal"], sm.SCALE, mutant, pieces=pieces, page=case["page"])
+    assert np.array_equal(bad.O, ref.O) and np.array_equal(bad.L, ref.L)
+    assert any(not harmless(sm.facts_of(case, sm.planned_pieces(case), n, sm.lists_of(case))) for case in sm.SEAM_CASES.values() for n in case["lens"] if n)
 
 
 @pytest.mark.parametrize("mutant", sorted(sm.MUTANTS))
@@ -79,12 +127,11 @@ def test_every_mutant_lies_outside(mutant):
     walk; a mutant that shows nowhere fails"""
     _what, harmless = sm.MUTANTS[mutant]
     tried = []
-    for name in sm.CASES:
+    for name in sm.ALL_CASES:
         case, pieces, q, kv, idx, ref, _info = sm.inputs(name)
-        facts = dict(R=case["R"], H=case["H"], B=sm.B, causal=case["causal"], pieces=pieces, page=case["page"], topk=case["topk"])
-        if all(harmless(dict(facts, n=n)) for n in sm.LENS if n):
+        if all(harmless(sm.facts_of(case, pieces, n, idx)) for n in case["lens"] if n):
             continue
-        bad = sm.model(q, kv, sm.LENS, idx, case["causal"], sm.SCALE, mutant, pieces=pieces, page=case["page"], shared=case["layout"] == "shared")
+        bad = sm.model(q, kv, case["lens"], idx, case["causal"], sm.SCALE, mutant, pieces=pieces, page=case["page"], shared=case["layout"] == "shared")
         fmt, out = case["fmt"], case["out"]
         bo, bl = sm.bounds(ref, fmt, out, sm.MARGIN)
         wo = (np.abs(sm.store(bad.O, out) - ref.O) / bo)
@@ -97,4 +144,5 @@ def test_every_mutant_lies_outside(mutant):
         if max(wo, wl) > 1.0:
             return
     assert tried, "no case lets %s show" % mutant
+    assert mutant not in sm.SEAM_MUTANTS or np.isfinite(bad.O).all(), "a seam mutant computes finite wrong values"
     pytest.fail("%s stays inside the bounds on every case where it can show: %r" % (mutant, tried))
