@@ -10,6 +10,8 @@ run_case() is the one runner: tests/test_train_parity_mask_gpu.py (block masks: 
 buffer is poisoned around every head's words) and tests/test_train_parity_transposed_gpu.py (transposed operands: only the buffers'
 layout changes; the padding of every leading dimension is NaN before and after) build their cases with case() and run them here.
 
+The mode "f32" (tests/test_train_parity_f32_gpu.py) runs FP32 operands under the model's FP32 bound and margin; a spike case of it
+proves on the CPU, before the launch, that its inputs take the FP32 forward's re-base branch (train_model.rebase_proof).
 FP16 cases store dO in FP16 next to FP16 Q / K / V (the model's one 16-bit type).  The launch forms of the torch binding
 (tests/test_train_parity_binding_forms_gpu.py): out16= stores O, dQ, dK, dV in the inputs' type (lowPrecisionOutputs; D is then formed
 from the stored O, and the model's bound says so); the modes "f16mix-mixed" / "f16mix-exact" store dO in BF16 next to FP16 Q / K / V, as
@@ -37,13 +39,14 @@ T = AttentionKernelType
 FWD, DQ, DKV = T.forward, T.backwardQuery, T.backwardKeyValue
 MODES = {"bf16-mixed": ("bf16", True), "bf16-exact": ("bf16", False), "f16-mixed": ("f16", True), "f16-exact": ("f16", False)}
 MIX_MODES = {"f16mix-mixed": ("f16", True), "f16mix-exact": ("f16", False)}      # dO in BF16 next to FP16 Q / K / V
+F32_MODES = {"f32": ("f32", False)}          # FP32 operands (tests/test_train_parity_f32_gpu.py): lowPrecisionInputs = False
 KV_CANARY = -3.0             # K / V heads behind the live ones of a grouped grid: finite, so that a launch that reads them computes wrong values
 SMALL_ROWS = slice(64, 128)  # small=True: the dO of these rows is scaled by 2^-12 (below FP16's normal range in part)
 _MODELS = {}
 
 
 def case(name, R, C, D, modes, *, B=1, H=1, causal=False, rl=None, cl=None, workspace=False, rows=(), spike=False, variant=None, form=None,
-         mask=None, tr=None, ld=None, only=None, out16=False, G=1, path=None, small=False):
+         mask=None, tr=None, ld=None, only=None, out16=False, G=1, path=None, small=False, shift=None):
     """variant / form: {kernel type: text the kernel's variant / the launch's form must contain; form: several joined by |, a leading !
     for text it must not contain, a leading ^ for text it must start with}.
     mask: None or dict(per="shared" | "head" | "batch" | "both", seed=, empty_last=, need_blocks=): a block mask of
@@ -53,10 +56,11 @@ def case(name, R, C, D, modes, *, B=1, H=1, causal=False, rl=None, cl=None, work
     ld: {operand: leading dimension} (default: the sequence length of a transposed operand, D of a row-major one); the padding columns
     hold NaN, in inputs and outputs.  only: the kernel types to run (default all three).
     out16: O, dQ, dK, dV in the inputs' type.  G: headsPerKeyValue (H query heads over H / G K / V heads).  path: the f16mix modes' path of
-    the backwardKeyValue kernel ("convert_dO" | "bf16_products"), asserted against train_model.MIX_PATH.  small: SMALL_ROWS of dO x 2^-12."""
+    the backwardKeyValue kernel ("convert_dO" | "bf16_products"), asserted against train_model.MIX_PATH.  small: SMALL_ROWS of dO x 2^-12.
+    spike: True or, FP32, a member of train_model.SPIKES; shift (FP32): nats, train_model.needle_inputs."""
     return [pytest.param(dict(R=R, C=C, D=D, B=B, H=H, causal=causal, rl=rl, cl=cl, workspace=workspace, rows=rows, spike=spike,
                               variant=variant or {}, form=form or {}, mode=m, mask=mask, tr=tuple(tr or (False,) * 4), ld=ld or {},
-                              only=tuple(only or (FWD, DQ, DKV)), out16=out16, G=G, path=path, small=small),
+                              only=tuple(only or (FWD, DQ, DKV)), out16=out16, G=G, path=path, small=small, shift=shift),
                          id="%s-%dx%dx%d-%s" % (name, R, C, D, m)) for m in modes]
 
 
@@ -123,10 +127,11 @@ def _kernels(c, fmt, mixed, fp32=None):
     """-> {kernel type: kernel}, {operand: precision}.  fp32: {kernel type: its outputs kept in FP32} on the case's descriptor (the by-bits
     launches: every input keeps its type, backwardQuery's 16-bit O too)"""
     desc = AttentionDescriptor()
-    desc.lowPrecisionInputs, desc.lowPrecisionIntermediates = True, mixed
+    desc.lowPrecisionInputs, desc.lowPrecisionIntermediates = fmt != "f32", mixed
     desc.matrixDimensions = (c["R"], c["C"], c["D"])
     desc.transposeState = c["tr"]
-    desc.lowPrecisionInputType = P.BF16 if fmt == "bf16" else P.FP16
+    if fmt != "f32":
+        desc.lowPrecisionInputType = P.BF16 if fmt == "bf16" else P.FP16
     desc.lowPrecisionOutputs = bool(c.get("out16"))
     kernels, precisions = {}, {}
     with parameter_rows(*c["rows"]):
@@ -195,17 +200,18 @@ def _problem(c, fmt, mixed, pieces, block_mask=None):
     mix = c["mode"].startswith("f16mix")
     out = fmt if c.get("out16") else "f32"
     form = (out, mix, c.get("path"), c.get("G", 1), bool(c.get("small")))
-    key = (c["R"], c["C"], c["D"], c["B"], c["H"], c["causal"], str(c["rl"]), str(c["cl"]), c["spike"], fmt, mixed, str(pieces),
+    key = (c["R"], c["C"], c["D"], c["B"], c["H"], c["causal"], str(c["rl"]), str(c["cl"]), c["spike"], c.get("shift"), fmt, mixed, str(pieces),
            None if block_mask is None else block_mask.tobytes(), form)
     if key not in _MODELS:
         geo = dict(causal=c["causal"], row_lengths=c["rl"], key_lengths=c["cl"], pieces=pieces)
         if block_mask is not None:
             geo["block_mask"] = block_mask
         extra = {}
+        shifted = {} if c.get("shift") is None else dict(shift=c["shift"])
         if form != ("f32", False, None, 1, False):             # (the former cases call exactly what they called)
             extra = dict(dO_fmt="bf16" if mix else None, heads_per_kv=c.get("G", 1))
         q, k, v, dO, info = train_model.needle_inputs(c["B"], c["H"], c["R"], c["C"], c["D"], fmt, spike=c["spike"], seed=c["R"] + c["D"],
-                                                      **(dict(extra, small_dO_rows=SMALL_ROWS if c.get("small") else None) if extra else {}), **geo)
+                                                      **(dict(extra, small_dO_rows=SMALL_ROWS if c.get("small") else None) if extra else {}), **shifted, **geo)
         if extra:
             extra.update(out=out, dO_path=c.get("path") if mix else None)
         _MODELS[key] = (q, k, v, dO, info, train_model.model(q, k, v, dO, fmt=fmt, mixed=mixed, **extra, **geo))
@@ -221,7 +227,7 @@ def run_case(c, device="cuda", launch=True):
     launch=False (any device): the forms only, nothing is started"""
     import time
     import torch
-    fmt, mixed = {**MODES, **MIX_MODES}[c["mode"]]
+    fmt, mixed = {**MODES, **MIX_MODES, **F32_MODES}[c["mode"]]
     R, C, D, B, H = c["R"], c["C"], c["D"], c["B"], c["H"]
     G, out16, mix = c.get("G", 1), bool(c.get("out16")), c["mode"].startswith("f16mix")
     Hkv = H // G
@@ -237,6 +243,9 @@ def run_case(c, device="cuda", launch=True):
     bits = block_mask_of(c)
     if launch:
         q, k, v, dO, info, ref = _problem(c, fmt, mixed, pieces, bits)
+        if fmt == "f32" and c["spike"]:      # before anything is launched: the inputs do take the forward's re-base branch (train_model.rebase_proof)
+            proof = train_model.rebase_proof(q, k, v, dO, causal=c["causal"], row_lengths=c["rl"], key_lengths=c["cl"], heads_per_kv=G)
+            train_model.check_rebase_proof(proof, c["spike"], c.get("shift"), C, whole=c["rl"] is None)
     else:                        # the forms only: they depend on the buffers' shapes, types and strides, not on their values
         q, dO = np.zeros((B, H, R, D)), np.zeros((B, H, R, D))
         k, v = np.zeros((B, Hkv, C, D)), np.zeros((B, Hkv, C, D))
@@ -366,14 +375,14 @@ def run_case(c, device="cuda", launch=True):
     if "D" in got:
         got["D"] = got["D"] * math.sqrt(D)                      # stored times the softmax scale
     out = fmt if out16 else "f32"
-    at_one, _padding, _text = compare(got, ref, out=out, margin=1, info=info, outputs=outputs)
-    worst, padding, text = compare(got, ref, out=out, info=info, outputs=outputs)
+    at_one, _padding, _text = compare(got, ref, out=out, margin=1, info=info, outputs=outputs, fmt=fmt)
+    worst, padding, text = compare(got, ref, out=out, info=info, outputs=outputs, fmt=fmt)
     print("train parity %s %s%s: err / bound at margin 1: %s; pieces %s; %s; %.3f s" % (
         c["mode"], (R, C, D, B, H), "".join((" out16" if out16 else "", " G=%d" % G if G > 1 else "", " " + c["path"] if mix else "")),
         " ".join("%s %.3f" % kv for kv in at_one.items()), {t.name: n for t, n in counts.items()},
         " | ".join(forms[t].split(" (")[0] for t in c["only"]), spent))
     assert all(padding.values()), "rows or keys past a per-batch length were written:\n" + text
-    assert max(worst.values()) <= 1.0, "outside the bound at margin %d (%s):\n%s" % (MARGIN, [kernels[t].variant for t in kernels], text)
+    assert max(worst.values()) <= 1.0, "outside the bound at margin %d (%s):\n%s" % (train_model.margin_of(fmt), [kernels[t].variant for t in kernels], text)
     return forms
 
 

@@ -36,6 +36,13 @@ outputs is flagged with its 16-bit outputs, on all 14 cases, the grouped ones to
 outputs (FORM_LOST: the arithmetic, asserted; flagged under every FP16-output case).  test_the_binding_form_cases_name_their_kernels: every case of tests/test_train_parity_binding_forms_gpu.py
 selects the variant, form and mix path it asserts, without a GPU.
 
+(f) FP32 operands (F32_CASES: 18 cases, one per geometry class of tests/test_train_parity_f32_gpu.py, the spike family (a) .. (f), the
+shift of 60 nats and one of 100 among them): emulated(fmt="f32") -- the walk of attn_f32_fwd, re-base rule included -- is inside the
+FP32 bound at margin 1 with 2 x headroom; every spike case proves from that walk that the re-base branch fires behind tile 0 in some
+but not all rows of a wave; every mutant that can act on an FP32 launch, the six of the re-base branch (train_model.F32_MUTANTS)
+included, is outside the bound at MARGIN_F32 wherever it changes anything; five of those six change NOTHING on the former check's
+inputs at any of its shapes; the model's outputs under the shift are those without it.
+
 The 26 cases of (b) are a covering set, not the full product: every shape meets dense and causal, lengths and none; (a) runs both
 types and both modes on each and on four more (D = 256 at the two large shapes and under the split plan, the 1024-key split of the
 persistent forwards); the (b) cost of the product (288 cases x 36 mutants of float64 attention) buys no geometry the set lacks.
@@ -214,7 +221,7 @@ def flagged(case, mutant, fmt="bf16", mixed=True):
 BOUND_OF = {"dq_scaled": (("bf16", False), ("f16", True))}
 
 
-@pytest.mark.parametrize("mutant", sorted(set(tm.MUTANTS) - set(tm.FORM_MUTANTS)))     # (the launch-form mutants: part (e))
+@pytest.mark.parametrize("mutant", sorted(set(tm.MUTANTS) - set(tm.FORM_MUTANTS) - set(tm.F32_MUTANTS)))     # (the launch-form mutants: part (e); attn_f32_fwd's: part (f))
 def test_each_mutant_is_flagged_wherever_it_changes_anything(mutant):
     _what, noop = tm.MUTANTS[mutant]
     if not HAVE_LIBRARY and noop is tm._no_split:
@@ -538,7 +545,7 @@ def test_sixteen_bit_outputs_lose_no_mutant_the_fp32_outputs_flag(case):
     if case["pieces"] and not HAVE_LIBRARY:
         pytest.skip("split cases need the library's plan")
     lost = []
-    for mutant in sorted(set(tm.MUTANTS) - set(tm.FORM_MUTANTS)):
+    for mutant in sorted(set(tm.MUTANTS) - set(tm.FORM_MUTANTS) - set(tm.F32_MUTANTS)):
         if tm.MUTANTS[mutant][1](case):
             continue
         before = form_flagged(case, mutant, "f32")
@@ -624,6 +631,234 @@ def test_a_truncated_grad_out_is_outside_the_bound_of_the_rounded_one():
         worst = tm.compare({n: getattr(bad, n) for n in outputs}, ref, out="f16", outputs=outputs)[0]
         print("a truncated grad_out, %s mode: err / bound at margin %d: %s" % ("mixed" if mixed else "exact", tm.MARGIN, worst))
         assert (max(worst.values()) > 1.0) == resolved and (not resolved or worst["dQ"] > 1.5), (mixed, worst)
+
+
+# ------------------------------------------------------------------------------------------------------------------------- (f)
+# FP32 operands (csrc/attn_f32.h and the general FP32 kernels): one case per geometry class of tests/test_train_parity_f32_gpu.py, the
+# spike family (a) .. (f) and the shift among them.  (i) every mutant of (b) and of the launch forms that can act on an FP32 launch,
+# and the six mutants of the re-base branch (train_model.F32_MUTANTS), is outside the bound at MARGIN_F32 on every FP32 case on which
+# it changes anything, and on at least one; (ii) what the former check (harness.TOL_FP32 on the oracle Network's N(0, 1) operands at
+# the shapes of tests/test_f32_kernels_gpu.py) saw of the re-base mutants; (iii) emulated(fmt="f32") is inside the bound at margin 1
+# with 2 x headroom on every case.
+L3R, L3C = [300, 77, 1], [333, 100, 64]
+
+
+def f32_cases():
+    out = []
+
+    def add(R, C, D, *, B=1, H=2, causal=False, rl=None, cl=None, spike=False, shift=None, G=1):
+        c = dict(R=R, C=C, D=D, B=B, H=H, causal=causal, lengths=rl is not None, rl=rl, cl=cl, pieces=False, spike=spike, shift=shift, G=G)
+        c.update(tm.case_flags(R, C, rl, cl))
+        out.append(c)
+
+    add(300, 333, 128)                                           # D = 128, dense: 11 forward tiles, 10 row tiles, three workgroups
+    add(300, 333, 64, causal=True)
+    add(129, 131, 100, H=1)                                      # below the head block; a row block of one row; 5 tiles
+    add(64, 64, 4, H=1)
+    add(1, 97, 64, H=1)                                          # one row
+    add(33, 1, 64, H=1)                                          # one key
+    add(160, 225, 128, causal=True, H=1)                         # C > R: a positive offset; five row tiles, two workgroups of keys
+    add(300, 333, 128, B=3, causal=True, rl=L3R, cl=L3C)         # an entry shorter than a workgroup, a one-row entry, fewer keys than rows
+    add(300, 333, 64, B=3, rl=L3R, cl=L3C)
+    add(255, 257, 64, H=8, G=4)                                  # grouped K / V heads: kv_head and the group sum
+    add(300, 333, 128, spike="a")
+    add(300, 333, 64, spike="b", causal=True)
+    add(300, 333, 128, spike="c")
+    add(300, 333, 64, spike="d", causal=True)
+    add(300, 333, 128, B=3, spike="e", causal=True, rl=L3R, cl=L3C)
+    add(300, 333, 64, spike="f")
+    add(300, 333, 64, spike="a", shift=tm.SHIFT, causal=True)
+    add(300, 333, 128, spike="a", shift=tm.SHIFT_DEEP)           # beyond FP32's exponent range: what first_tile_keeps_m0 needs
+    return out
+
+
+F32_CASES = f32_cases()
+f32_id = lambda c: "f32-%dx%dx%d-B%dH%d%s-%s-%s%s%s" % (  # noqa: E731
+    c["R"], c["C"], c["D"], c["B"], c["H"], "-G%d" % c["G"] if c["G"] > 1 else "", "causal" if c["causal"] else "dense",
+    "lengths" if c["lengths"] else "full", "-spike-%s" % c["spike"] if c["spike"] else "", "-shift%g" % c["shift"] if c["shift"] else "")
+_F32_IDS = [f32_id(c) for c in F32_CASES]
+assert len(set(_F32_IDS)) == len(_F32_IDS)
+F32_RUN = sorted(set(tm.MUTANTS) - set(tm.MASK_MUTANTS))         # (no FP32 launch of these kernels takes a block mask)
+
+
+def f32_problem(case):
+    key = f32_id(case)
+    if key not in _PROBLEMS:
+        geo = dict(causal=case["causal"], row_lengths=case["rl"], key_lengths=case["cl"], heads_per_kv=case["G"])
+        q, k, v, dO, info = tm.needle_inputs(case["B"], case["H"], case["R"], case["C"], case["D"], "f32", spike=case["spike"], shift=case["shift"],
+                                             seed=200 + _F32_IDS.index(key), **geo)
+        geo.update(fmt="f32", mixed=False)
+        _PROBLEMS[key] = (q, k, v, dO, geo, info, tm.model(q, k, v, dO, **geo))
+    return _PROBLEMS[key]
+
+
+def f32_flagged(case, mutant):
+    """None where the mutant computes the model's own values; else (flagged at MARGIN_F32, the worst err / bound)"""
+    key = (f32_id(case), mutant)
+    if key not in _FLAGGED:
+        q, k, v, dO, geo, info, ref = f32_problem(case)
+        with np.errstate(all="ignore"):
+            bad = tm.model(q, k, v, dO, mutant=mutant, with_bounds=False, **geo)
+        if all(np.array_equal(getattr(bad, n), getattr(ref, n), equal_nan=True) for n in tm.OUTPUTS):
+            _FLAGGED[key] = None
+        else:
+            worst, padding, _text = tm.compare({n: getattr(bad, n) for n in tm.OUTPUTS}, ref, info=info, fmt="f32")
+            _FLAGGED[key] = (max(worst.values()) > 1.0 or not all(padding.values()), max(worst.values()))
+    return _FLAGGED[key]
+
+
+@pytest.mark.parametrize("case", F32_CASES, ids=f32_id)
+def test_fp32_emulated_reference_is_inside_the_bounds(case):
+    """(iii), and what a spike or shift case must prove of the re-base branch before it may stand for it (train_model.check_rebase_proof)"""
+    q, k, v, dO, geo, info, ref = f32_problem(case)
+    kw = {n: x for n, x in geo.items() if n not in ("fmt", "mixed")}
+    worst, padding, text = tm.compare(tm.emulated(q, k, v, dO, "f32", False, **kw), ref, margin=1, info=info, fmt="f32")
+    print("%s: emulated reference at margin 1: %s" % (f32_id(case), " ".join("%s %.3f" % kv for kv in worst.items())))
+    assert max(worst.values()) <= tm.MARGIN_F32 / 2.0 and all(padding.values()), text
+    assert float(np.nanmax(np.abs(ref.O))) >= 0.05 and float(np.nanmax(np.abs(ref.dV))) >= 0.05, "O and dV must stay of the order of V and dO"
+    if case["spike"]:
+        proof = tm.rebase_proof(q, k, v, dO, **kw)
+        print("%s: the re-base branch: %s" % (f32_id(case), {n: len(x) if n == "residues" else x for n, x in proof.items()}))
+        tm.check_rebase_proof(proof, case["spike"], case["shift"], case["C"], whole=not case["lengths"])
+    else:      # no tile behind tile 0 fires on plain needle inputs: every row holds key 0
+        assert case["shift"] is None and not tm.rebase_proof(q, k, v, dO, **kw)["rows"]
+
+
+def test_the_fp32_margin_is_a_power_of_two_and_at_most_four():
+    assert tm.MARGIN_F32 in (1, 2, 4) and tm.margin_of("f32") == tm.MARGIN_F32 and tm.margin_of("bf16") == tm.MARGIN
+    with pytest.raises(AssertionError):
+        tm.model(*f32_problem(F32_CASES[3])[:4], fmt="f32", mixed=True)
+
+
+@pytest.mark.parametrize("mutant", F32_RUN)
+def test_each_mutant_is_flagged_on_the_fp32_cases(mutant):
+    """(i)"""
+    _what, noop = tm.MUTANTS[mutant]
+    exercised, missed = 0, []
+    for case in F32_CASES:
+        if noop(case):      # (the model's own values, or -- one key: dS = P (dP - D) is 0 up to float64 rounding -- 1e-6 of the bound at the most)
+            assert f32_flagged(case, mutant) is None or f32_flagged(case, mutant)[1] < 1e-6, (mutant, f32_id(case))
+            continue
+        seen = f32_flagged(case, mutant)
+        assert seen is not None, "%s changes nothing on %s, which it does not name" % (mutant, f32_id(case))
+        exercised += 1
+        if not seen[0]:
+            missed.append((f32_id(case), round(seen[1], 3)))
+    group = ("group_slab_dropped", "group_slab_twice", "group_sum_head_is_query_head")
+    if not (noop is tm._no_split or (mutant in tm.FORM_MUTANTS and mutant not in group)):     # (no FP32 case is split, stores 16 bits or mixes types)
+        assert exercised >= 1, "%s is exercised by no FP32 case" % mutant
+    assert not missed, "%s goes unnoticed on %s" % (mutant, missed)
+
+
+def test_the_shift_changes_no_output_of_the_model():
+    """softmax cancels the shift: the model under shift = 60 nats gives the outputs of shift = 0 (the same inputs with a_i = 0) to
+    float64 rounding -- 1e-6 of the bound; what the shift changes is the bound itself, through T and the |m| term: it grows"""
+    case = next(c for c in F32_CASES if c["shift"] == tm.SHIFT)
+    q, k, v, dO, geo, info, ref = f32_problem(case)
+    form = {n: x for n, x in geo.items() if n not in ("fmt", "mixed")}
+    q0, k0, v0, dO0, _info = tm.needle_inputs(case["B"], case["H"], case["R"], case["C"], case["D"], "f32", spike=case["spike"], shift=0.0,
+                                              seed=200 + _F32_IDS.index(f32_id(case)), **form)
+    assert np.array_equal(k0, k) and np.array_equal(v0, v) and np.array_equal(dO0, dO)
+    assert ((q0 != q).any(axis=(0, 2)).sum(axis=-1) == 1).all(), "the shift lives in one spare head dimension per head"
+    rows = np.arange(case["R"])
+    moved = ((q - q0) * k[:, :, :1]).sum(axis=-1) / np.sqrt(case["D"])                 # a_i b scale per row
+    assert np.allclose(moved, tm.shift_of(tm.SHIFT, rows)[None, None, :], atol=1e-5)
+    wave = tm.shift_of(tm.SHIFT, rows[:32])
+    assert wave.min() == -tm.SHIFT and wave.max() >= tm.SHIFT - 4.0 and len(set(wave)) == 32
+    ref0 = tm.model(q0, k0, v0, dO0, **geo)
+    bd, bd0 = tm.bounds(ref, fmt="f32"), tm.bounds(ref0, fmt="f32")
+    spare = [int(np.flatnonzero((q0 != q)[:, h].any(axis=(0, 1)))[0]) for h in range(case["H"])]
+    for name in tm.OUTPUTS:
+        a, b = getattr(ref, name).copy(), getattr(ref0, name).copy()
+        if name == "L":                       # every score of row i moved by its shift: so did L
+            a -= moved
+        if name == "dK":                      # dK = scale dS^T Q: its spare column holds scale sum_i dS_ij a_i, the others are untouched
+            for h in range(case["H"]):
+                assert np.nanmax(np.abs(a[:, h, :, spare[h]])) > 0 and np.nanmax(np.abs(b[:, h, :, spare[h]])) == 0
+                a[:, h, :, spare[h]] = 0.0
+        live = ~np.isnan(b)
+        assert np.array_equal(np.isnan(a), np.isnan(b)) and (np.abs(a - b)[live] <= 1e-6 * bd[name][live]).all(), name
+        assert bd[name][live].sum() > 1.5 * bd0[name][live].sum(), name
+
+
+# (ii) the former check of the FP32 kernels: test_fp32_kernels_match_the_oracle -- one head of the oracle Network's N(0, 1) operands,
+# harness.TOL_FP32 (2e-5; 5e-5 where R or C exceeds 777) on the maximum absolute error of each output
+OLD_F32_SHAPES = [(128, 128, 128), (300, 555, 64), (257, 600, 128), (129, 131, 100), (64, 64, 4), (1, 50, 8), (1000, 900, 72),
+                  (160, 96, 128), (33, 1, 64), (640, 640, 60), (96, 1024, 128)]
+REBASE_UNSEEN = ("rebase_l_not_o", "rebase_scores_not_shifted", "rebase_bias_stale", "first_tile_keeps_m0", "rebase_only_first_db")
+
+
+def old_f32_check_sees(shape, causal, mutant):
+    """None where the mutant changes nothing on the former inputs; else (seen under TOL_FP32, {output: maximum absolute error})"""
+    from oracle import Network, NetworkDescriptor
+    R, C, D = shape
+    key = ("old f32", shape, causal)
+    if key not in _PROBLEMS:
+        net = Network(NetworkDescriptor(R, C, D), seed=R * 7 + C)
+        q, k, v, dO = (tm.round_to(x, "f32")[None, None] for x in (net.Q, net.K, net.V, net.dO))
+        _PROBLEMS[key] = (q, k, v, dO, tm.model(q, k, v, dO, causal=causal, fmt="f32", mixed=False, with_bounds=False))
+    q, k, v, dO, ref = _PROBLEMS[key]
+    with np.errstate(all="ignore"):
+        bad = tm.model(q, k, v, dO, causal=causal, fmt="f32", mixed=False, mutant=mutant, with_bounds=False)
+        err = {n: float(np.max(np.where(np.isnan(getattr(bad, n)), np.inf, np.abs(getattr(bad, n) - getattr(ref, n))))) for n in tm.OUTPUTS}
+    if max(err.values()) == 0.0:
+        return None
+    tol = tm.OLD_TOL_FP32 if max(R, C) <= 777 else 5e-5
+    return any(e > tol for e in err.values()), err
+
+
+def test_what_the_former_fp32_check_saw_of_the_rebase_branch():
+    """on N(0, 1) operands no tile behind tile 0 beats the reference maximum by 8 log2 units and no exponent leaves FP32's range: the
+    five mutants that live there change NOTHING at any shape of tests/test_f32_kernels_gpu.py, dense or causal -- the branch and its
+    five pieces of code never ran.  The sixth (the lost half-wave exchange) acts in tile 0 too, which every launch runs: caught."""
+    import harness
+    assert harness.TOL_FP32 == {n: tm.OLD_TOL_FP32 for n in harness.TOL_FP32}
+    assert set(REBASE_UNSEEN) | {"rebase_other_half"} == set(tm.F32_MUTANTS)
+    for shape in OLD_F32_SHAPES:
+        for causal in (False, True):
+            if causal and shape[1] < shape[0]:
+                continue
+            for mutant in REBASE_UNSEEN:
+                assert old_f32_check_sees(shape, causal, mutant) is None, (mutant, shape, causal)
+    assert old_f32_check_sees((300, 555, 64), False, "rebase_other_half")[0]
+    for mutant in REBASE_UNSEEN:      # ... and each is flagged by a case of the new file
+        assert any(not tm.MUTANTS[mutant][1](c) and f32_flagged(c, mutant)[0] for c in F32_CASES), mutant
+
+
+F32_TABLE_SHAPES = ((300, 555, 64), (257, 600, 128), (1000, 900, 72), (4096, 4096, 128))    # the last: config 3's, at 5e-5 like every shape beyond 777
+F32_TABLE_MUTANTS = tuple(tm.F32_MUTANTS) + ("key0_dropped", "last_key_dropped", "partial_last_tile_dropped", "l_without_key0", "dq_scaled", "d_wrong")
+
+
+def print_fp32_table():
+    """what harness.TOL_FP32 on N(0, 1) operands saw of FP32 defects; the script's alone, for the cost of 4096 keys"""
+    columns = [(s, c) for s in F32_TABLE_SHAPES for c in (False, True) if not (c and s[1] < s[0])]
+    print("| FP32 mutant | " + " | ".join("%s %s" % (s, "causal" if c else "dense") for s, c in columns) + " | new cases: worst err / bound where it is weakest |")
+    print("|---|" + "---|" * (len(columns) + 1))
+    for mutant in F32_TABLE_MUTANTS:
+        cells = []
+        for shape, causal in columns:
+            seen = old_f32_check_sees(shape, causal, mutant)
+            if seen is None:
+                cells.append("changes nothing")
+                continue
+            worst = max(tm.OUTPUTS, key=lambda n: seen[1][n] if np.isfinite(seen[1][n]) else 1e30)
+            cells.append("%s (%s %.2g)" % ("caught" if seen[0] else "**missed**", worst, seen[1][worst]))
+        new = [f32_flagged(c, mutant)[1] for c in F32_CASES if not tm.MUTANTS[mutant][1](c)]
+        print("| %s | %s | %.3g over %d cases |" % (mutant, " | ".join(cells), min(new), len(new)))
+
+
+def test_the_fp32_gpu_file_runs_every_case_of_the_proof():
+    """every FP32 case above is a case of tests/test_train_parity_f32_gpu.py (same grid, lengths, spike, shift and group), which
+    goes through run_case and defines no bound, margin or checker of its own"""
+    pytest.importorskip("torch")
+    import test_train_parity_f32_gpu as f32gpu
+    import test_train_parity_gpu as gpu
+    assert f32gpu.run_case is gpu.run_case and f32gpu.case is gpu.case
+    text = open(f32gpu.__file__).read()
+    assert not any(own in text for own in ("MARGIN", "margin=", "def bounds", "def compare", "compare("))
+    have = {tuple(str(p.values[0].get(n)) for n in ("R", "C", "D", "B", "H", "causal", "rl", "cl", "spike", "shift", "G")) for p in f32gpu.CASES}
+    for c in F32_CASES:
+        assert tuple(str(c[n]) for n in ("R", "C", "D", "B", "H", "causal", "rl", "cl", "spike", "shift", "G")) in have, f32_id(c)
 
 
 # ------------------------------------------------------------------------------------------------------------------------- (d)
@@ -744,6 +979,8 @@ if __name__ == "__main__":
                 what = "caught" if seen[0] else "tighter constants only" if seen[1] else "**missed**"
                 cells.append("%s (%s %.2g)" % (what, worst, seen[2][worst]))
         print("| %s | %s |" % (mutant, " | ".join(cells)))
+    print()
+    print_fp32_table()
     print()
     print("| launch-form mutant | case | err / bound (margin %d) | the former constants on N(0, 1) operands |" % tm.MARGIN)
     print("|---|---|---|---|")

@@ -20,6 +20,9 @@ inputs and the named mutants (a plain module, as tests/decode_model.py, whose ro
                     sees and a small set of TRAP keys it must not see is left unsuppressed (needle_plan).
   needle_mask()     a random mask with what the needle plan asks for (neighbouring row blocks that differ both ways, run edges).
   compare()         got against model under the bounds: worst err / bound per output and where; padding must keep the buffer's value.
+  fmt = "f32"       model(), bounds(), emulated(), needle_inputs() and compare() take FP32 operands (the bound: the end of this text);
+                    needle_inputs(spike= "a" .. "f", shift= nats) drive the re-base branch of attn_f32_fwd, rebase_proof() shows from
+                    emulated()'s walk that they do, F32_MUTANTS are that branch's named defects (_rebase_walk).
   split_ranges()    the ranges of a traversal cut into pieces as the kernels cut it (piece i takes the units
                     [i n / s, (i + 1) n / s) of 64 keys or 32 rows: attn_dq16_p4.h `tile_lo`, attn_dkv16_p4.h `lo`, `up`);
                     library_piece_count() reads the piece count s from the library's own plan (mfa_attention_kernel_workspace_size).
@@ -103,6 +106,52 @@ The launch forms of the torch binding (out=, dO_fmt= / dO_path=, heads_per_kv=; 
 MARGIN is the smallest power of two, at most 4, with at least 2 x headroom over the worst err / bound at margin 1 of emulated() on
 every case of tests/test_train_sensitivity.py and of the kernels on every case of tests/test_train_parity_gpu.py and of the files
 that run their cases through it (DESIGN.md 4.18 records both maxima).
+
+FP32 operands (fmt = "f32": csrc/attn_f32.h; `mixed` is meaningless and refused; the outputs are always FP32).  u = 0: no operand, P
+or dS is rounded to 16 bits, and FP16's floor f is 0.  What remains is the rho term and the FP32 chains, re-derived from the kernels
+as read.  s2 = log2e s are the scores in log2 units, T2_ij = log2e T_ij, m the kernel's REFERENCE maximum in log2 units.
+  Scores (attn_f32_fwd).  Q is multiplied by scale2 = fl(log2e / sqrt(D)) once (pin_fragments: one rounding per element, u32 T2 on a
+  score).  A score is an FP32 chain on v_mfma_f32_32x32x2_f32: one instruction contracts two head dimensions (d = 8 T + i from the
+  hi = 0 lanes, 8 T + 4 + i from the hi = 1 lanes; two roundings at the most), D / 2 instructions, D roundings.  The accumulator
+  STARTS at -m (mfma_bias: ones . (-m), exact), so every partial sum is bounded by |m| + T2 and each rounding by u32 (|m| + T2): the
+  cancellation term in |m|.  A firing tile subtracts delta (`s[r] -= delta`: one rounding of the same size) and adds it to m
+  (`m += delta`: u32 |m|, which every later tile starts from).  In all (D + 3) u32 (T2_ij + M_ij) in log2 units, M_ij = the larger of
+  |m| before and after the tile of key j.  m follows the kernel's rule (32-key tiles; tile 0 sets m to its maximum; a later tile
+  re-bases iff its maximum exceeds m by more than 8), walked in float64 (_rebase_walk).  A tile whose maximum lies within 2^-8 of the
+  threshold may go either way in FP32; m then differs by about 8: such a row carries M + 8 on every key.
+  fast_exp2 is __builtin_amdgcn_exp2f, one v_exp_f32: 1 ulp = 2 u32 (the CDNA ISA's stated accuracy of the transcendental unit);
+  the sum `psum += s[r]` adds 1, the product with V or dP one more:
+    rho_ij = ln 2 u32 ((D + 3) (T2_ij + M_ij) + 2 (max_j M_ij + 8)) + 4 u32
+  (the last bracket: the general kernels of attn_generic.h start a score at 0, scale it and subtract the RUNNING maximum in one fma,
+  `s[r] * a.scale2 - m`, and re-base at every growth: two roundings on |m_run|, which lies between tile 0's maximum and the row's,
+  hence within 8 of an M of the row.)
+  Forward chains.  O^T += V^T P^T on the same instruction: two keys per instruction, C roundings on A_O + |O|.  l: 16 additions per
+  half-wave and tile, one `l += psum` per tile, half_add once (C / 32 + 17); one re-base per firing tile multiplies l and O by
+  corr = fast_exp2(-delta) (the same factor on both: its own error cancels in O; one rounding each: 2 per tile at the most);
+  half_max is exact; 1 / l_tot (v_rcp_f32, 1 ulp = 2) and the product with it (1).  chain = C + 3 ceil(C / 32) + pieces + 24.
+    E_O = sum_j rho p |v| + |O| sum_j rho p + chain u32 (A_O + |O|)
+  L = m + log2f(l_tot): log2f is one v_log_f32 under the library's fast-math build or OCML's log2f, both within 1 ulp = 2 u32 |log2 l|;
+  the kernel's m and l are the reference's, not the row maximum's: |m_ref| <= |m| + 8 and |log2 l_ref| <= |log2 l| + 8 in log2 units:
+    E_L = sum_j rho p + chain u32 + 4 u32 (|m| + |ln l| + |L| + 16 ln 2) + 2^-23 |L|
+  D = scale sum_d dO O (attn_f32_dq: D / 2 fma per half-wave, half_add, the product with scale, the FP32 store): the terms of the
+  exact mode above, with this chain.
+  Backward.  attn_f32_dq: S' - L and dP - D / scale leave the matrix pipe from accumulators started at -L and -sum(dO o O): D
+  roundings each on |L2| + T2 and on |D_i| + sum_d |dO v|; P = fast_exp2 (2 u32), dS = P (dP - D) (1):
+    rho^b_ij = ln 2 (D + 3) u32 (T2_ij + |L2_i|) + 4 u32 + E_L_i,      e_dP_ij = (D + 3) u32 (sum_d |dO_id v_jd| + |D_i|)
+  dQ^T += K^T dS^T over 32-KEY tiles, two keys per instruction: chain (C roundings) on A_dQ.  attn_f32_dkv: K is multiplied by
+  -scale2 and V by -scale once (one rounding per element, inside the D + 3), the accumulators start at the stored L and D of the
+  tile's 32 ROWS; dV^T += dO^T P and dK^T += Q^T dS over 32-row tiles, two rows per instruction: chain_r = R + 3 ceil(R / 32) +
+  pieces + 24 roundings on A_dV and A_dK.  The group sum is as above.
+  The general FP32 kernels (attn_generic.h: the 32 and 256 head blocks, transposed operands, unaligned leading dimensions, the 384
+  row and the paged route beyond it) run the same arithmetic on the same instruction with the same tiles of 32 keys or rows
+  (attn_f32.h's header says so; `BT = 32` there, `BC = 32` and 32-row steps here), and attn_paged.h (D > 384: `BR = 32, BC = 32`)
+  adds its scores and outputs up in plain fma chains, one rounding per product, over 32-key and 32-row tiles: the chain counts one
+  rounding per product and three per 32-wide tile, and so holds for every FP32 launch form.
+  emulated(fmt="f32") walks the forward as the kernel does: Q' once, the chain of a score in the kernel's order of d from -m, 32-key
+  tiles, the re-base rule (threshold 8; tile 0 always sets m; corr = exp2(-delta) on O and l; the firing tile's scores shifted;
+  later tiles start from the new m), l per half-wave, the P V sum in the kernel's order of keys.  trace= receives, per grid entry,
+  the per-tile maxima relative to m and which rows fired in which tile (rebase_proof reads it).
+MARGIN_F32 is measured the same way (DESIGN.md 4.25 records the maxima of emulated() and of the kernels).
 """
 import math
 from typing import NamedTuple
@@ -116,6 +165,12 @@ RESCALE_THRESHOLD = 8.0                               # log2 units: the deferred
 MARGIN = 2
 F16_FLOOR = 2.0 ** -25                                # half the spacing of FP16's subnormals: P and dS below 2^-14 in that type
 OUTPUTS = ("O", "L", "D", "dV", "dK", "dQ")
+U_OF = dict(U_P, f32=0.0)                             # u of the bound: half an ulp of the operands' 16-bit type; FP32 operands round nothing to 16 bits
+MARGIN_F32 = 1                                        # fmt = "f32": measured like MARGIN
+F32_TILE, F32_THRESHOLD = 32, 8.0                     # attn_f32.h BT, RESCALE_ABOVE (log2 units)
+SPIKES = ("a", "b", "c", "d", "e", "f")               # needle_inputs(spike=): the family of late dominant keys (spike_keys)
+SHIFT, SHIFT_DEEP = 60.0, 100.0                       # needle_inputs(shift=), nats: inside and beyond FP32's exponent range (87 nats)
+OLD_TOL_FP32 = 2e-5                                   # tests/harness.py TOL_FP32
 OLD_TOL = dict(O=5e-2, L=7e-3, D=1e-1, dV=5e-2, dK=5e-2, dQ=5e-2)   # tests/harness.py TOL_MIXED
 
 
@@ -167,7 +222,7 @@ MUTANTS = {
     "row_block_next_head_kv": ("row block 0 served from the next head's K / V", lambda c: c["H"] == 1),
     "v_rows_exchanged": ("two V rows of one 16-key group exchanged",
                          lambda c: c["C"] < 2 or not _seen(c, None, lambda n: slice(30, 32) if n >= 32 else slice(0, 2))),
-    "v_dblocks_exchanged": ("the first two 32-wide d blocks of V exchanged", lambda c: False),
+    "v_dblocks_exchanged": ("the first two 32-wide d blocks of V exchanged", lambda c: c.get("D", 64) < 64),
     "rescale_o_not_l": ("the deferred rescale (threshold 8) applied to O but not to l", lambda c: not c["spike"]),
     "l_without_key0": ("l without key 0: wrong in L only", lambda c: not _seen(c, None, lambda n: slice(0, 1))),
     "row_length_next_batch": ("the row length of batch b + 1 used for batch b", lambda c: not c["row_lengths_differ"]),
@@ -217,6 +272,20 @@ FORM_MUTANTS = {
     "group_store_rounds_each_slab": ("16-bit outputs: every slab of a group rounded to 16 bits before the sum", lambda c: _no_group(c) or _out32(c)),
 }
 MUTANTS.update(FORM_MUTANTS)
+# the re-base branch of attn_f32_fwd (attn_f32.h `if (__builtin_amdgcn_ballot_w64(grow) != 0)`), walked by _rebase_walk.  `case` also
+# has D, spike (False | True | "a" .. "f": SPIKES) and shift (None or nats).  A spike case leaves key 0 out of its unspiked rows'
+# needles, so rows of every kind fire behind tile 0; FP32's exponent range is +-126 log2 units = +-87 nats: a first tile that keeps
+# m = 0 computes the same softmax until a shift takes exp2 out of that range (SHIFT_DEEP)
+F32_MUTANTS = {
+    "rebase_l_not_o": ("FP32 forward: a re-base after tile 0 corrects l but not O", lambda c: not c["spike"]),
+    "rebase_scores_not_shifted": ("FP32 forward: the firing tile (after tile 0) keeps s instead of s - delta", lambda c: not c["spike"]),
+    "rebase_bias_stale": ("FP32 forward: tiles after a re-base still start from the old -m", lambda c: not c["spike"]),
+    "first_tile_keeps_m0": ("FP32 forward: tile 0 re-bases only if mx > 8", lambda c: (c.get("shift") or 0.0) < SHIFT_DEEP),
+    "rebase_only_first_db": ("FP32 forward: the correction reaches the first accumulator block of O only (d = NDB i + 0)", lambda c: not c["spike"]),
+    # (D = 4: the keys' codes repeat every four keys, both halves of a tile hold every code and so the same maximum)
+    "rebase_other_half": ("FP32 forward: the hi = 1 lanes re-base by their own half's maximum (half_max lost)", lambda c: c["D"] == 4),
+}
+MUTANTS.update(F32_MUTANTS)
 # block-mask mutants: each misreads the mask (mask_views); "changes nothing" where the misread visibility of every live row equals the
 # true one, which follows from the case's mask, its words, whether it is shared, causal and the lengths -- never from a result
 MASK_MUTANTS = {
@@ -475,6 +544,67 @@ def _softmax(S, vis, mult=None):
     return pw / l0, m0[:, 0], l0[:, 0]
 
 
+def crow(r, hi):
+    """the key (forward, dQ) or row (dK / dV) of a 32-wide tile that register r of half-wave hi holds (attn_common.h crow)"""
+    return (r & 3) + 8 * (r >> 2) + 4 * hi
+
+
+def _fp32_range(p):
+    """float64 weights as fast_exp2 returns them: infinite from 2^128 on, zero below 2^-126 (v_exp_f32 flushes subnormal results:
+    LLVM's own exp2 lowering for AMDGPU scales its argument for that reason; __builtin_amdgcn_exp2f is the bare instruction)"""
+    with np.errstate(all="ignore"):
+        return np.where(p >= 2.0 ** 128, np.inf, np.where(p < 2.0 ** -126, 0.0, p))
+
+
+def _rebase_walk(S2, V, mutant=None):
+    """attn_f32_fwd's online softmax around a reference maximum, in float64: S2 [R, C] scores in log2 units (-inf: not seen), V [C, D]
+    -> O, L in log2 units, trace {before, after: m a tile's scores start from / m behind the tile, mx: the tile's maximum relative to
+    `before` ([R, tiles]), fired: rows that took the re-base branch in a tile after tile 0}.  Per half-wave hi: its reference m, its
+    l, the columns d = NDB crow(r, hi) + db of O; the scores of a tile start from the hi = 0 lanes' bias.  Unmutated this is softmax."""
+    R, C = S2.shape
+    Dh = V.shape[1]
+    ndb = 2 if Dh <= 64 else 4
+    tiles = -(-C // F32_TILE)
+    S2 = np.concatenate([S2, np.full((R, tiles * F32_TILE - C), -np.inf)], axis=1)
+    V = np.concatenate([V, np.zeros((tiles * F32_TILE - C, Dh))])
+    half = np.arange(F32_TILE) % 8 >= 4                 # keys of a tile the hi = 1 lanes hold (crow)
+    cols = (np.arange(Dh) // ndb) % 8 >= 4              # columns of O the hi = 1 lanes hold
+    first_db = np.arange(Dh) % ndb == 0
+    m, l, o, bias = np.zeros((2, R)), np.zeros((2, R)), np.zeros((R, Dh)), np.zeros(R)
+    tr = {n: np.zeros((R, tiles)) for n in ("before", "after", "mx")}
+    tr["fired"] = np.zeros((R, tiles), dtype=bool)
+    with np.errstate(all="ignore"):
+        for j in range(tiles):
+            s = S2[:, j * F32_TILE:(j + 1) * F32_TILE] - bias[:, None]
+            whole = s.max(axis=1)
+            p = np.zeros_like(s)
+            for h in (0, 1):
+                mine = half == bool(h)
+                mx = s[:, mine].max(axis=1) if mutant == "rebase_other_half" and h == 1 else whole
+                grow = mx > F32_THRESHOLD if j > 0 or mutant == "first_tile_keeps_m0" else np.ones(R, dtype=bool)
+                delta = np.where(grow, mx, 0.0)
+                lost = np.isneginf(delta)               # (rebase_other_half, tile 0, no key in the half: s - mask_value = 0 on its 16 slots)
+                delta = np.where(lost, 0.0, delta)
+                corr = np.ones(R) if j == 0 else np.exp2(-delta)
+                m[h] += delta
+                l[h] *= corr
+                reach = (cols == bool(h)) & (first_db if mutant == "rebase_only_first_db" and j > 0 else True)
+                if not (mutant == "rebase_l_not_o" and j > 0):
+                    o[:, reach] *= corr[:, None]
+                kept = mutant == "rebase_scores_not_shifted" and j > 0
+                ph = np.where(lost[:, None], 1.0, np.exp2(s[:, mine] - (0.0 if kept else delta[:, None])))
+                p[:, mine] = _fp32_range(ph)
+                l[h] += p[:, mine].sum(axis=1)
+                if h == 0:
+                    tr["before"][:, j], tr["mx"][:, j], tr["fired"][:, j] = bias, whole, grow & (j > 0)
+            o += np.where(p > 0, p, 0.0) @ V[j * F32_TILE:(j + 1) * F32_TILE]
+            if not (mutant == "rebase_bias_stale" and j > 0):
+                bias = m[0].copy()
+            tr["after"][:, j] = m[0]
+        ltot = l[0] + l[1]
+        return o / ltot[:, None], m[0] + np.log2(ltot), tr
+
+
 DO_PATHS = ("convert_dO", "bf16_products")             # how a backwardKeyValue kernel of the FP16 + BF16-dO mix reads dO (docstring)
 # backwardKeyValue variant prefix -> its path in the mix, with the source line it was read from (the first matching prefix holds).
 # Every backwardQuery kernel converts (attn_dq16_p4.h:148, attn_dq16_p5.h:189, attn_bwd16.h:114 `convert_chunk<T, TG>`).
@@ -538,7 +668,10 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
     ofmt = out                                        # (`out` names the outputs below)
     out16 = ofmt != "f32"
     scale = 1.0 / math.sqrt(Dh)
-    u = U_P[fmt]
+    f32 = fmt == "f32"
+    assert not f32 or (not mixed and not mix and ofmt == "f32" and block_mask is None), "FP32 operands: exact mode, FP32 outputs, no mask"
+    assert mutant not in F32_MUTANTS or f32, "the re-base mutants are attn_f32_fwd's"
+    u = U_OF[fmt]
     fl = F16_FLOOR if fmt == "f16" else 0.0
     cf = F16_FLOOR if mix else 0.0                    # dO converted to FP16: exact mantissa, FP16's subnormal floor
     products = mix and dO_path == "bf16_products"     # backwardKeyValue: V and P rounded to BF16 for dP and dV
@@ -547,6 +680,8 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
     pieces = pieces or {}
     npieces = max(len(pieces.get("fwd", ())), len(pieces.get("dq", ())), len(pieces.get("dkv", ())), 1)
     chain, chain_r = (C / 8 + npieces + 16) * U32, (R / 8 + npieces + 16) * U32
+    if f32:      # two keys (rows) per matrix instruction, one rounding each; 32-wide tiles: the sums of l, one re-base on l and O
+        chain, chain_r = (C + 3 * -(-C // F32_TILE) + npieces + 24) * U32, (R + 3 * -(-R // F32_TILE) + npieces + 24) * U32
     out = {n: np.full((B, H, R, Dh) if n in ("O", "dQ") else (B, Hkv, C, Dh), np.nan) for n in ("O", "dV", "dK", "dQ")}
     out["L"], out["D"] = np.full((B, H, R), np.nan), np.full((B, H, R), np.nan)
     slabs = {}                                        # (b, h) -> a query head's dV, dK and their E and A: summed per group below
@@ -634,6 +769,13 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
                 ltrue = np.exp2(S2 - run[:, None]).sum(axis=1)
                 O = np.where(fired[:, None], O * (ltrue / lm)[:, None], O)
                 L = np.where(fired, (run + np.log2(lm)) / LOG2E, L)
+            if mutant in F32_MUTANTS:      # rows on which the mutated walk gives the unmutated walk's values keep the model's own
+                S2w = np.where(visF, S, -np.inf) * LOG2E
+                Ow, Lw, _tr = _rebase_walk(S2w, Vf)
+                Om, Lm, _tr = _rebase_walk(S2w, Vf, mutant)
+                with np.errstate(all="ignore"):
+                    same = np.isclose(Om, Ow, rtol=1e-9, atol=1e-12).all(axis=1) & np.isclose(Lm, Lw, rtol=1e-9, atol=1e-9)
+                O, L = np.where(same[:, None], O, Om), np.where(same, L, Lm / LOG2E)
             if mutant == "l_without_key0":
                 with np.errstate(divide="ignore", invalid="ignore"):
                     L = L + np.log1p(-P[:, 0])
@@ -759,6 +901,13 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
             smin = np.where(vis, S, np.inf).min(axis=1)
             spread2 = np.where(np.isfinite(smin), (m - np.where(np.isfinite(smin), smin, m)) * LOG2E, 0.0)
             rho = LN2 * ((Dh + 3) * U32 * LOG2E * T + 3 * U32 * spread2[:, None]) + 4 * U32
+            if f32:     # the chain of a score starts at -m: M, the kernel's reference maximum around every key's tile (docstring)
+                _o, _l2, walk = _rebase_walk(np.where(vis, S, -np.inf) * LOG2E, V)
+                Mt = np.maximum(np.abs(walk["before"]), np.abs(walk["after"]))
+                with np.errstate(invalid="ignore"):
+                    Mt = Mt + 8.0 * (np.abs(walk["mx"] - F32_THRESHOLD) < 2.0 ** -8)[:, 1:].any(axis=1)[:, None]
+                Mkey = np.repeat(Mt, F32_TILE, axis=1)[:, :C]
+                rho = LN2 * U32 * ((Dh + 3) * (LOG2E * T + Mkey) + 2 * (Mt.max(axis=1)[:, None] + 8.0)) + 4 * U32
             visl = (vis & live_r[:, None]).astype(np.float64)
             if mixed:
                 rho = rho + u * T
@@ -777,6 +926,8 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
             L = np.where(np.isfinite(L), L, 0.0)          # (a dead row: every term of its bounds is 0 but the constants)
             Lf = np.where(live_r, L, 0.0)
             EL = relp + (u if mixed else 0.0) + chain + 4 * U32 * (np.abs(m) + np.abs(np.log(l)) + np.abs(Lf)) + (2.0 ** -11 if mixed else 2.0 ** -23) * np.abs(Lf)
+            if f32:
+                EL = EL + 4 * U32 * 16 * LN2
             Df = np.where(live_r, Dv, 0.0)
             dP = np.where(live_r[:, None], dP, 0.0)
             dev = np.abs(dP - Df[:, None])
@@ -786,6 +937,9 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
             rhob = rho + EL[:, None]
             dSl = np.where(live_r[:, None], dS, 0.0)
             edP = (Dh + 3) * U32 * (aG @ aV.T)
+            if f32:     # the backward accumulators start at -L and -D (dQ) or at L and D (dK / dV)
+                rhob = LN2 * U32 * (Dh + 3) * LOG2E * (T + np.abs(Lf)[:, None]) + 4 * U32 + EL[:, None]
+                edP = edP + (Dh + 3) * U32 * np.abs(Df)[:, None]
             eds = P * ((rhob + u) * dev + edP + cf * aV.sum(axis=1)[None, :] + ED[:, None]) + u * np.abs(dSl) + fl * visl * (dev + math.sqrt(Dh))
             # backwardKeyValue of the mix: dO converted as in backwardQuery, or (bf16_products) V rounded to BF16 and dO as stored
             eds_k = eds + P * (U_BF16 * (aG @ aV.T) - cf * aV.sum(axis=1)[None, :]) if products else eds
@@ -823,9 +977,15 @@ def model(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, piec
     return Reference(out["O"], out["L"], out["D"], out["dV"], out["dK"], out["dQ"], A, E, PK, row_live, key_live, dead_rows)
 
 
-def bounds(ref, out="f32", margin=MARGIN):
+def margin_of(fmt=None):
+    return MARGIN_F32 if fmt == "f32" else MARGIN
+
+
+def bounds(ref, out="f32", margin=None, fmt=None):
     """{output: per-element bound}: see the module's docstring.  `out`: the type O, dQ, dK, dV are stored in (L and D: their own
-    store is part of E, the mode decides it)"""
+    store is part of E, the mode decides it).  fmt: the operands' type the Reference was built for (it decides the default margin)"""
+    margin = margin_of(fmt) if margin is None else margin
+    assert fmt != "f32" or out == "f32"
     res = {}
     for name in OUTPUTS:
         x = np.nan_to_num(getattr(ref, name), nan=0.0)
@@ -840,14 +1000,18 @@ def _f32(x):
 
 
 def emulated(q, k, v, dO, fmt, mixed, *, causal=False, row_lengths=None, key_lengths=None, pieces=None, block_mask=None, out="f32",
-             o_rounding="trunc", dO_fmt=None, dO_path=None, heads_per_kv=1):
+             o_rounding="trunc", dO_fmt=None, dO_path=None, heads_per_kv=1, trace=None, forward_only=False):
     """the model with the kernels' roundings and order of sums -> {output: array}, NaN where nothing is written: Q' (K' in
     backwardKeyValue) rounded once in the mixed mode, 64-key tiles under the deferred rescale, P and dS rounded to the 16-bit type,
     l from the rounded P in the mixed mode, pieces merged, L in FP16 and D in truncated BF16 in the mixed mode, the stores.
     out: O, dQ, dK, dV are stored in that type and D is formed from the STORED O; o_rounding ("trunc" | "nearest"): the rounding of
     the forward's BF16 O store (STORE_ROUNDING; FP16 always rounds to nearest, the gradients' BF16 stores always truncate).  dO_fmt /
     dO_path: the FP16 + BF16-dO mix (model()).  heads_per_kv: the FP32 slabs of a group are added in the order g = 0 .. G - 1 and the sum is
-    stored once"""
+    stored once.  fmt = "f32": the walk of attn_f32.h (docstring; _emulated_f32); trace (a dict) receives {(b, h): the walk's per-tile
+    record}, forward_only leaves the gradients and D unwritten"""
+    if fmt == "f32":
+        assert not mixed and out == "f32" and block_mask is None and not pieces and (dO_fmt or fmt) == fmt
+        return _emulated_f32(f64(q), f64(k), f64(v), f64(dO), causal, row_lengths, key_lengths, int(heads_per_kv), trace, forward_only)
     q, k, v, dO = f64(q), f64(k), f64(v), f64(dO)
     B, H, R, Dh = q.shape
     C = k.shape[2]
@@ -919,6 +1083,107 @@ def emulated(q, k, v, dO, fmt, mixed, *, causal=False, row_lengths=None, key_len
                 sv, sk = _f32(sv + _f32(dV)), _f32(sk + _f32(dK))
             if h % Gq == Gq - 1:
                 res["dV"][b, h // Gq, :clen], res["dK"][b, h // Gq, :clen] = store(sv, out), store(sk, out)
+    return res
+
+
+def _chain32(init, A, B):
+    """init [n, m] + A [n, D] B [m, D]^T as one first product of attn_f32.h adds it up: one FP32 rounding per matrix instruction, which
+    contracts d = 8 T + i (hi = 0) and 8 T + 4 + i (hi = 1)"""
+    Dh = A.shape[1]
+    pad = -Dh % 8
+    A, B = np.pad(A, ((0, 0), (0, pad))), np.pad(B, ((0, 0), (0, pad)))
+    acc = np.array(init, dtype=np.float64)
+    for T in range((Dh + pad) // 8):
+        for i in range(4):
+            d0, d1 = 8 * T + i, 8 * T + 4 + i
+            acc = _f32(acc + A[:, d0:d0 + 1] * B[None, :, d0] + A[:, d1:d1 + 1] * B[None, :, d1])
+    return acc
+
+
+def _accum32(acc, W, X):
+    """acc [n, D] + W [n, 32] X [32, D] as one second product adds a 32-wide tile up: step t contracts crow(t, 0) and crow(t, 1)"""
+    for t in range(16):
+        a, b = crow(t, 0), crow(t, 1)
+        acc = _f32(acc + W[:, a:a + 1] * X[a] + W[:, b:b + 1] * X[b])
+    return acc
+
+
+def _emulated_f32(q, k, v, dO, causal, row_lengths, key_lengths, Gq, trace, forward_only):
+    B, H, R, Dh = q.shape
+    C = k.shape[2]
+    sc = float(np.float32(1.0 / math.sqrt(Dh)))
+    s2c = float(np.float32(LOG2E / math.sqrt(Dh)))
+    rl, cl = _lengths(row_lengths, B, R), _lengths(key_lengths, B, C)
+    res = {n: np.full((B, H, R, Dh) if n in ("O", "dQ") else (B, H // Gq, C, Dh), np.nan) for n in ("O", "dV", "dK", "dQ")}
+    res["L"], res["D"] = np.full((B, H, R), np.nan), np.full((B, H, R), np.nan)
+    half = np.arange(F32_TILE) % 8 >= 4
+    order = [[crow(r, hi) for r in range(16)] for hi in (0, 1)]
+    for b in range(B):
+        rlen, clen = int(rl[b]), int(cl[b])
+        tiles, rtiles = -(-clen // F32_TILE), -(-rlen // F32_TILE)
+        vis = np.pad(_visible(R, C, rlen, clen, causal)[:rlen, :clen], ((0, rtiles * F32_TILE - rlen), (0, tiles * F32_TILE - clen)))
+        for h in range(H):
+            padk, padr = ((0, tiles * F32_TILE - clen), (0, 0)), ((0, rtiles * F32_TILE - rlen), (0, 0))
+            Q, G = np.pad(q[b, h, :rlen], padr), np.pad(dO[b, h, :rlen], padr)          # (the bounds-checked resources fill with zeros)
+            K, V = np.pad(k[b, h // Gq, :clen], padk), np.pad(v[b, h // Gq, :clen], padk)
+            Q2 = _f32(Q * s2c)
+            n = Q.shape[0]
+            # ---- forward: 32-key tiles around the reference maximum m
+            m, l, o = np.zeros(n), np.zeros((2, n)), np.zeros((n, Dh))
+            rec = {name: np.zeros((n, tiles)) for name in ("before", "mx", "at")}
+            rec["fired"] = np.zeros((n, tiles), dtype=bool)
+            with np.errstate(all="ignore"):
+                for j in range(tiles):
+                    t = slice(j * F32_TILE, (j + 1) * F32_TILE)
+                    s = np.where(vis[:, t], _chain32(np.repeat(-m[:, None], F32_TILE, axis=1), Q2, K[t]), -np.inf)
+                    mx = s.max(axis=1)
+                    grow = (mx > F32_THRESHOLD) if j else np.ones(n, dtype=bool)
+                    rec["before"][:, j], rec["mx"][:, j], rec["fired"][:, j], rec["at"][:, j] = m, mx, grow & (j > 0), s.argmax(axis=1)
+                    delta = np.where(grow, mx, 0.0)
+                    corr = _f32(np.exp2(-delta)) if j else np.ones(n)
+                    m = _f32(m + delta)
+                    l, o = _f32(l * corr), _f32(o * corr[:, None])
+                    p = _f32(np.exp2(_f32(s - delta[:, None])))
+                    for hi in (0, 1):
+                        psum = np.zeros(n)
+                        for r in order[hi]:
+                            psum = _f32(psum + p[:, r])
+                        l[hi] = _f32(l[hi] + psum)
+                    o = _accum32(o, p, V[t])
+                ltot = _f32(l[0] + l[1])
+                live = np.arange(n) < rlen                  # (rows past the length: Q, dO, L and D read as zeros, nothing is stored)
+                O = np.where(live[:, None], _f32(o * _f32(1.0 / ltot)[:, None]), 0.0)
+                L2 = np.where(live, _f32(m + _f32(np.log2(ltot))), 0.0)
+            if trace is not None:
+                trace[(b, h)] = {name: x[:rlen] for name, x in rec.items()}
+            res["O"][b, h, :rlen], res["L"][b, h, :rlen] = O[:rlen], L2[:rlen] / LOG2E
+            if forward_only:
+                continue
+            # ---- backwardQuery: accumulators started at -L and -sum(dO o O), three stages of 32-key tiles
+            dsum = _f32((G * O).sum(axis=1))
+            Dst = _f32(dsum * sc)
+            with np.errstate(all="ignore"):
+                P = _f32(np.exp2(_chain32(np.repeat(-L2[:, None], K.shape[0], axis=1), Q2, K)))
+                dS = np.where(vis, _f32(P * _chain32(np.repeat(-dsum[:, None], K.shape[0], axis=1), G, V)), 0.0)
+            acc = np.zeros((n, Dh))
+            for j in range(tiles):
+                acc = _accum32(acc, dS[:, j * F32_TILE:(j + 1) * F32_TILE], K[j * F32_TILE:(j + 1) * F32_TILE])
+            res["dQ"][b, h, :rlen], res["D"][b, h, :rlen] = _f32(acc * sc)[:rlen], Dst[:rlen] / sc
+            # ---- backwardKeyValue: K and V pre-multiplied, accumulators started at the stored L and D of a 32-row tile
+            with np.errstate(all="ignore"):
+                Pk = np.where(vis.T, _f32(np.exp2(-_chain32(np.repeat(L2[None, :], K.shape[0], axis=0), _f32(-s2c * K), Q))), 0.0)
+                X = np.where(vis.T, _f32(Pk * _chain32(np.repeat(Dst[None, :], K.shape[0], axis=0), _f32(-sc * V), G)), 0.0)   # = -dS'
+            dV, dK = np.zeros((K.shape[0], Dh)), np.zeros((K.shape[0], Dh))
+            for j in range(rtiles):
+                t = slice(j * F32_TILE, (j + 1) * F32_TILE)
+                dV, dK = _accum32(dV, Pk[:, t], G[t]), _accum32(dK, X[:, t], Q[t])
+            dV, dK = dV[:clen], -dK[:clen]
+            if h % Gq == 0:
+                sv, sk = dV, dK
+            else:
+                sv, sk = _f32(sv + dV), _f32(sk + dK)
+            if h % Gq == Gq - 1:
+                res["dV"][b, h // Gq, :clen], res["dK"][b, h // Gq, :clen] = sv, sk
     return res
 
 
@@ -1113,8 +1378,52 @@ def code_layout(C, Dh, h=0):
 SUPPRESSED = 9.0    # nats below the needles: the score of a key that shares one code half with no needle of the row (18: neither half)
 
 
+def spike_keys(spike, r, salt, last, clen):
+    """[(key, nats above the row's other keys)] of row r whose last visible key is `last`, or [] (the row is not spiked).  True: the
+    single late key of the 16-bit cases (row 40 of every 64: its last visible key).  The family for 32-key tiles (SPIKES), every
+    spike behind tile 0; rows 3 mod 4 stay unspiked ("f": every other row), so that spiked and unspiked lanes share every wave:
+      a  one key 9 nats up in a whole tile 1 .., at residue (5 r + salt) mod 32: 32 consecutive rows walk every residue, both
+         half-waves (crow) and, with the tile index (r / 2 + salt), both LDS stages
+      b  the tile's parity follows the row's: odd rows in odd tiles, even rows in even tiles
+      c  a key of the partial last tile (rows that see it)
+      d  a key of the row's diagonal tile: its last visible key or one of the two before it
+      e  a staircase: three (even rows) or four (odd rows) successive tiles, 9, 15, 21, 27 nats: each tops the one before by 6 nats
+         (8.66 log2 units), so the branch fires tile after tile and the bias is rewritten each time
+      f  as a, every other row"""
+    if not spike:
+        return []
+    if spike is True:
+        return [(last, SUPPRESSED)] if r % TILE == 40 else []
+    assert spike in SPIKES, spike
+    if r % 2 == 0 if spike == "f" else r % 4 == 3:
+        return []
+    full, at = (last + 1) // F32_TILE, (5 * r + salt) % F32_TILE           # whole tiles the row sees
+    if spike in ("a", "f"):
+        return [((1 + (r // 2 + salt) % (full - 1)) * F32_TILE + at, SUPPRESSED)] if full >= 2 else []
+    if spike == "b":
+        if full < 3:
+            return []
+        tile = 1 + 2 * ((r // 2 + salt) % (full // 2)) if r % 2 else 2 + 2 * ((r // 2 + salt) % ((full - 1) // 2))
+        return [(tile * F32_TILE + at, SUPPRESSED)]
+    if spike == "c":
+        t0 = clen // F32_TILE * F32_TILE
+        return [(t0 + (r + salt) % (last - t0 + 1), SUPPRESSED)] if clen % F32_TILE and t0 and last >= t0 else []
+    if spike == "d":
+        return [(last - (r + salt) % 3, SUPPRESSED)] if last - 2 >= F32_TILE else []
+    n = 3 + r % 2
+    if full < n + 1:
+        return []
+    first = 1 + (r // 4 + salt) % (full - n)
+    return [((first + i) * F32_TILE + at, SUPPRESSED + 6.0 * i) for i in range(n)]
+
+
+def shift_of(shift, r):
+    """the per-row score shift of needle_inputs(shift=) in nats: 32 consecutive rows walk +-shift in 32 steps"""
+    return shift * ((7 * r) % 32 / 15.5 - 1.0)
+
+
 def needle_inputs(B, H, R, C, Dh, fmt, *, causal=False, row_lengths=None, key_lengths=None, pieces=None, block_mask=None, spike=False, seed=0,
-                  dO_fmt=None, small_dO_rows=None, heads_per_kv=1):
+                  dO_fmt=None, small_dO_rows=None, heads_per_kv=1, shift=None):
     """-> q, k, v, dO (float64 values of the 16-bit type, asserted exact) and info {(b, h, r): (needle keys, trap keys)}.
 
     The tension: in the mixed mode a score moves by u T_ij, T_ij = scale sum_d |q_d k_jd| >= |s_ij|, so a needle that stands
@@ -1134,8 +1443,14 @@ def needle_inputs(B, H, R, C, Dh, fmt, *, causal=False, row_lengths=None, key_le
     mix no dO element lies below 2^-14 in magnitude (FP16's smallest normal number) except in small_dO_rows (a slice of rows), whose dO
     is scaled by 2^-12 as a whole -- Q, K, V and with them every needle stay as they are.  heads_per_kv = G: K and V are [B, H / G, C,
     D], query head h reads head h // G and takes that head's code layout; the members of a group draw their needles with different
-    salts, so their needle keys differ."""
+    salts, so their needle keys differ.
+    fmt = "f32": FP32 values.  spike may name a member of SPIKES (spike_keys): a spiked row keeps one key of tile 0 -- the key whose
+    first code half is the first spike's own, so that no other key of the spike's code run is lifted -- and its spike keys only.
+    shift (nats; FP32 only): the last free dimension is taken out of the draw and carries a per-row constant a_i in Q and b = 1 in
+    K: every score of row i moves by shift_of(shift, i) -- +-shift inside every 32-row wave --, which softmax cancels exactly
+    (shift = 0.0: the same inputs with a_i = 0, the comparison case; dO is drawn along the unshifted O either way)."""
     rng = np.random.default_rng(seed)
+    assert shift is None or (fmt == "f32" and block_mask is None)
     Gq = int(heads_per_kv)
     dO_fmt = dO_fmt or fmt
     k = round_to(rng.uniform(-1, 1, (B, H // Gq, C, Dh)), fmt)
@@ -1149,28 +1464,36 @@ def needle_inputs(B, H, R, C, Dh, fmt, *, causal=False, row_lengths=None, key_le
     for h in range(H):
         mA, mB, dims = code_layout(C, Dh, h // Gq)
         free = dims[mA + mB:]
+        if shift is not None:
+            assert len(free) >= 3, "the shift needs a spare head dimension"
+            free, spare = free[:-1], free[-1]
         ka, kb = keys % mA, (keys // mA) % mB
         for b in range(B):
             k[b, h // Gq][:, dims[:mA + mB]] = 0.0
             k[b, h // Gq, keys, dims[ka]] = 1.0
             k[b, h // Gq, keys, dims[mA + kb]] = 1.0
+            if shift is not None:
+                k[b, h // Gq, :, spare] = 1.0
             assert block_mask is None or not spike
-            rows, traps = needle_plan(R, C, int(rl[b]), int(cl[b]), causal, pieces, b * H + h, spike,
+            rows, traps = needle_plan(R, C, int(rl[b]), int(cl[b]), causal, pieces, b * H + h, bool(spike),
                                       None if block_mask is None else mask_bits(block_mask, b, h))
             off = max(int(cl[b]) - int(rl[b]), 0)
             for r in range(R):
                 T = set(rows[r])
                 last = min(r + off, int(cl[b]) - 1) if causal else int(cl[b]) - 1
-                spiked = spike and r % TILE == 40 and last >= mA
+                spikes = [(t, nats) for t, nats in spike_keys(spike, r, b * H + h, last, int(cl[b])) if t >= mA]
+                if len({int(kb[t]) for t, _n in spikes}) < len(spikes):       # (two spikes in one code run: C > 1024)
+                    spikes = []
+                spiked = bool(spikes)
                 if spiked:
-                    T = {0, last}
+                    T = {0 if spike is True else spikes[0][0] % mA} | {t for t, _n in spikes}
                 U = sorted(T | set(traps[r]))
                 row = np.zeros(Dh)
                 row[dims[:mA + mB]] = -gamma
                 lifted = np.unique(np.concatenate([dims[ka[U]], dims[mA + kb[U]]]))
                 row[lifted] = rng.choice([-1.0, -0.5, 0.5, 1.0], len(lifted)) * 0.125 * math.sqrt(Dh)     # few-hot: +-0.125 per code half
-                if spiked:
-                    row[dims[mA + kb[last]]] = gamma
+                for t, nats in spikes:
+                    row[dims[mA + kb[t]]] = gamma if nats == SUPPRESSED else float(round_to(np.array([nats * math.sqrt(Dh)]), fmt)[0])
                 if len(free):                      # and two free dimensions: T_ij = scale sum_d |q_d k_jd| <= 0.5 on a needle
                     row[free[(r * 2 + np.arange(2)) % len(free)]] = rng.choice([-1.0, 1.0], 2) * 0.125 * math.sqrt(Dh)
                 q[b, h, r] = row
@@ -1183,6 +1506,10 @@ def needle_inputs(B, H, R, C, Dh, fmt, *, causal=False, row_lengths=None, key_le
             O = P @ v[b, h // Gq]
             rms = np.sqrt((O * O).mean(axis=1, keepdims=True))
             dO[b, h] = round_to(dO[b, h] + (8.0 / Dh) * O / np.where(rms > 0, rms, 1.0), dO_fmt)
+    if shift:
+        for h in range(H):
+            spare = code_layout(C, Dh, h // Gq)[2][-1]
+            q[:, h, :, spare] = round_to(shift_of(shift, np.arange(R)) * math.sqrt(Dh), fmt)[None, :]
     if dO_fmt != fmt:
         dO = np.where(np.abs(dO) < SMALL_DO, np.where(dO < 0, -SMALL_DO, SMALL_DO), dO)
     if small_dO_rows is not None:
@@ -1201,12 +1528,55 @@ def needle_keys(info):
     return res
 
 
+def rebase_proof(q, k, v, dO, *, causal=False, row_lengths=None, key_lengths=None, heads_per_kv=1):
+    """what the FP32 forward's re-base branch does on these inputs, from emulated()'s walk and with nothing launched: the kernel's
+    rule (j > 0 and the tile's maximum relative to m above 8 log2 units) applied to the walk's per-tile maxima ->
+    dict(mixed: (wave, tile) pairs in which some but not all live rows of a 32-row wave take the branch, residues: the positions mod 32
+    of the keys that fired it, parities: the tile indices mod 2, last_tile: fires in a row's last visible tile, longest: the longest run of
+    successive firing tiles of one row, rows: rows that fire at all, far_first: the largest |m| tile 0 sets, in log2 units)"""
+    trace = {}
+    emulated(q, k, v, dO, "f32", False, causal=causal, row_lengths=row_lengths, key_lengths=key_lengths, heads_per_kv=heads_per_kv,
+             trace=trace, forward_only=True)
+    res = dict(mixed=0, residues=set(), parities=set(), last_tile=0, longest=0, rows=0, far_first=0.0)
+    for rec in trace.values():
+        fired = rec["mx"] > F32_THRESHOLD
+        fired[:, 0] = False
+        assert np.array_equal(fired, rec["fired"])
+        for w in range(0, fired.shape[0], 32):
+            res["mixed"] += int((fired[w:w + 32].any(axis=0) & ~fired[w:w + 32].all(axis=0)).sum())
+        res["residues"] |= {int(x) for x in rec["at"][fired]}
+        res["parities"] |= {int(j) % 2 for j in np.nonzero(fired)[1]}
+        seen = np.isfinite(rec["mx"])                                  # tiles in which the row sees a key
+        res["last_tile"] += int((fired & seen & ~np.concatenate([seen[:, 1:], np.zeros((len(seen), 1), dtype=bool)], axis=1)).sum())
+        run = np.zeros(fired.shape[0], dtype=int)
+        for j in range(fired.shape[1]):
+            run = np.where(fired[:, j], run + 1, 0)
+            res["longest"] = max(res["longest"], int(run.max(initial=0)))
+        res["rows"] += int(fired.any(axis=1).sum())
+        res["far_first"] = max(res["far_first"], float(np.abs(rec["before"][:, 1]).max()) if fired.shape[1] > 1 else 0.0)
+    return res
+
+
+def check_rebase_proof(proof, spike, shift=None, C=None, whole=True):
+    """what a spike (and shift) case of the FP32 forward must show before anything is launched: the branch fires behind tile 0 in some
+    but not all rows of a wave, in tiles of both parities (both LDS stages); the keys that fire it take every residue mod 32 -- "c":
+    every position of the partial last tile of C keys (whole: no per-batch length shortens it), and the fire is in the row's last
+    tile; "d": also in the last visible tile; "e": some row fires in three successive tiles or more; shift: tile 0 sets an m as far
+    from 0 as the shift reaches (0.9 shift log2e)"""
+    assert spike in SPIKES and proof["mixed"] >= 1 and proof["parities"] == {0, 1}, (spike, proof)
+    want = set(range(C % F32_TILE)) if spike == "c" and whole else set() if spike == "c" else set(range(F32_TILE))
+    assert want <= proof["residues"], (spike, sorted(want - proof["residues"]))
+    assert proof["last_tile"] >= 1 or spike not in ("c", "d"), (spike, proof)
+    assert proof["longest"] >= 3 or spike != "e", (spike, proof)
+    assert not shift or proof["far_first"] >= 0.9 * shift * LOG2E, (shift, proof)
+
+
 # ----------------------------------------------------------------------------------------------------------------------- checker
-def compare(got, ref, *, out="f32", margin=MARGIN, info=None, outputs=OUTPUTS):
+def compare(got, ref, *, out="f32", margin=None, info=None, outputs=OUTPUTS, fmt=None):
     """got {output: array, NaN (the buffer's sentinel) where the launch wrote nothing} against the model -> ({output: worst err /
     bound over EVERY element of every live row or key}, {output: True where the padding kept the sentinel}, text naming the worst
-    elements)."""
-    bd = bounds(ref, out, margin)
+    elements).  fmt: as in bounds()."""
+    bd = bounds(ref, out, margin, fmt)
     worst, padding, lines = {}, {}, []
     for name in outputs:
         g = f64(got[name])
