@@ -14,6 +14,7 @@ from .attention import (  # noqa: F401
     AttentionMLADecode,
     AttentionMLADecodeFP8,
     AttentionMLASparseDecode,
+    AttentionMLASparseDecodeFP8,
     AttentionOperand,
     AttentionPrefill,
     GEMMOperandPrecision,
@@ -35,7 +36,8 @@ from .gemm import GEMMDescriptor, GEMMKernel, GEMMKernelDescriptor  # noqa: F401
 
 def __getattr__(name):
     # the torch functions of the KV-cache loop, on first use: torch stays optional for everything above
-    if name in ("kv_cache_compact", "tree_path", "flash_mla_decode", "flash_mla_decode_fp8", "mla_cache_append", "flash_mla_sparse_decode"):
+    if name in ("kv_cache_compact", "tree_path", "flash_mla_decode", "flash_mla_decode_fp8", "mla_cache_append", "flash_mla_sparse_decode",
+                "flash_mla_sparse_decode_fp8"):
         from . import torch_binding
         return getattr(torch_binding, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

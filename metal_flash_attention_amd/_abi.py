@@ -421,6 +421,14 @@ MLA_SPARSE_SYMBOLS = [   # include/mfa_mla_sparse.h: MLA decode over per-row lis
      _MLA_BUFS + [_MLA, _MLA_SPARSE, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
 ]
 
+MLA_SPARSE_FP8_SYMBOLS = [   # include/mfa_mla_sparse_fp8.h: the sparse entries over an e4m3 latent cache (`sparse`, then `quant`, after `params`)
+    ("mfa_attention_mla_sparse_decode_fp8_workspace_size", ctypes.c_int, [_MLA, _MLA_SPARSE, _MLA_QUANT, ctypes.POINTER(ctypes.c_uint64), _U32P]),
+    ("mfa_attention_mla_sparse_decode_fp8_launch", ctypes.c_int, _MLA_BUFS + [_MLA, _MLA_SPARSE, _MLA_QUANT, ctypes.c_void_p]),
+    ("mfa_attention_mla_sparse_decode_fp8_launch_form", ctypes.c_int, [_MLA, _MLA_SPARSE, _MLA_QUANT, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_mla_sparse_decode_fp8_time", ctypes.c_int,
+     _MLA_BUFS + [_MLA, _MLA_SPARSE, _MLA_QUANT, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+]
+
 # ---- the laddered entries of the launches over a KV cache, described once:
 #     mfa_attention_<launch>_<family><verb>(*<the verb's head>, params, *<the options the family owns>, *<the verb's tail>)
 # CACHE_FAMILIES: launch -> family -> the options its entries take, in the order of their signatures (each family is an earlier one plus an
@@ -527,7 +535,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS + MLA_SPARSE_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS + MLA_SPARSE_SYMBOLS + MLA_SPARSE_FP8_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -1056,6 +1056,34 @@ class AttentionMLASparseDecode(AttentionMLADecode):
         self.dispatch(q, kv, o, l, **shape)
 
 
+class AttentionMLASparseDecodeFP8(AttentionMLASparseDecode):
+    """Sparse MLA decode over an FP8 (OCP e4m3) latent cache (include/mfa_mla_sparse_fp8.h): AttentionMLASparseDecode's methods and
+    arguments -- the KV strides count bytes, multiples of 16 -- plus kvScale (device FP32, one entry, None = 1.0): a cache byte stands
+    for kvScale[0] x e4m3(byte).  `precision` is the 16-bit type of Q.  The workspace and the piece plan are AttentionMLASparseDecode's.
+
+        mla = AttentionMLASparseDecodeFP8(GEMMOperandPrecision.BF16)
+        mla.dispatch(q, kv8, o, l, cacheLengths=lengths, rows=1, column=C, heads=128, batches=B, scale=s, indices=idx, topk=2048,
+                     kvScale=kv_scale, workspace=ws)
+    """
+
+    def __init__(self, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16, outputPrecision: Optional[GEMMOperandPrecision] = None,
+                 cachePrecision: int = KVCachePrecision.E4M3, **widths):
+        super().__init__(precision, outputPrecision, **widths)
+        self.cachePrecision = int(cachePrecision)
+
+    def _own(self, shape):
+        sparse, keptSparse = super()._own(shape)
+        quant = _abi.mfa_mla_quant()
+        lib().mfa_mla_quant_init(ctypes.byref(quant))
+        quant.cachePrecision = self.cachePrecision
+        keep = shape.pop("kvScale", None)
+        quant.kvScale = _pointer(keep)
+        return sparse + (ctypes.byref(quant),), (keptSparse, quant, keep)
+
+    def _entry(self, verb):
+        return getattr(lib(), "mfa_attention_mla_sparse_decode_fp8_" + verb)
+
+
 class MLACacheAppend:
     """Appends the `rows` new rows of every sequence to the latent cache of MLA decode (include/mfa_mla_cache.h) -- latentNew
     [batches][rows][512] and ropeNew [batches][rows][64] become one cache row of 576 -- quantising them to e4m3 when the cache is FP8

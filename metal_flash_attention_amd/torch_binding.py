@@ -33,7 +33,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLASparseDecode, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
                         KVCachePrecision, MLACacheAppend)
 
@@ -649,7 +649,7 @@ def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_sca
     """flash_mla_decode's launch (include/mfa_mla.h) on q's device and torch's current stream -> (O [B, H, R, 512], L [B, H, R] base 2);
     the workspace of a launch cut along the keys is allocated here.  `fp8`: flash_mla_decode_fp8's, over an e4m3 latent cache with
     `kv_scale` (include/mfa_mla_cache.h) -- the strides of such a cache count bytes, which are its elements"""
-    who = "flash_mla_sparse_decode" if indices is not None else "flash_mla_decode_fp8" if fp8 else "flash_mla_decode"
+    who = ("flash_mla_sparse_decode_fp8" if fp8 else "flash_mla_sparse_decode") if indices is not None else "flash_mla_decode_fp8" if fp8 else "flash_mla_decode"
     _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces, fp8)
     if indices is not None:
         _check_mla_indices(who, q, indices)
@@ -663,7 +663,7 @@ def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_sca
               column=int(kv_cache.shape[1]) * (int(block_table.shape[1]) if paged else 1))
     if paged:
         kw.update(pageSize=int(kv_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)), pageStride=int(kv_cache.stride(0)))
-    cls = AttentionMLASparseDecode if indices is not None else AttentionMLADecodeFP8 if fp8 else AttentionMLADecode
+    cls = (AttentionMLASparseDecodeFP8 if fp8 else AttentionMLASparseDecode) if indices is not None else AttentionMLADecodeFP8 if fp8 else AttentionMLADecode
     if fp8:
         kw.update(kvScale=_latent_scale(who, kv_scale, kv_cache.device))
     if indices is not None:   # `indices`: flash_mla_sparse_decode's lists (include/mfa_mla_sparse.h), passed where they lie
@@ -954,6 +954,13 @@ def _op_mla_sparse_decode(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths
     return _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces, indices=indices)
 
 
+def _op_mla_sparse_decode_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, indices: torch.Tensor,
+                              block_table: Optional[torch.Tensor], causal: bool, softmax_scale: float, pieces: int,
+                              kv_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(attention_mla_sparse_decode's arguments; `kv_scale` last, as attention_mla_decode_fp8's)"""
+    return _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces, True, kv_scale, indices=indices)
+
+
 def _op_mla_append(latent_new: torch.Tensor, rope_new: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor,
                    block_table: Optional[torch.Tensor], kv_scale: Optional[torch.Tensor]) -> None:
     _run_mla_append(latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale)
@@ -1051,6 +1058,12 @@ _MLA_SPARSE_OPS = [
 ]
 _HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_SPARSE_OPS})
 _HAVE_MLA_SPARSE_OP = _HAVE["attention_mla_sparse_decode"]
+# the op of include/mfa_mla_sparse_fp8.h, in a list of its own
+_MLA_SPARSE_FP8_OPS = [
+    ("attention_mla_sparse_decode_fp8", _op_mla_sparse_decode_fp8, _fake_mla, ()),
+]
+_HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_SPARSE_FP8_OPS})
+_HAVE_MLA_SPARSE_FP8_OP = _HAVE["attention_mla_sparse_decode_fp8"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1358,4 +1371,31 @@ def flash_mla_sparse_decode(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengt
     _check_mla_indices(who, q, indices)
     o, l = _call_op(_HAVE_MLA_SPARSE_OP, "attention_mla_sparse_decode", q, kv_cache, cache_lengths, indices, block_table, bool(causal),
                     float(softmax_scale), int(pieces))
+    return (o, l * _LN2) if return_lse else o
+
+
+def flash_mla_sparse_decode_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, indices: torch.Tensor, *,
+                                softmax_scale: float, kv_scale: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None,
+                                causal: bool = True, return_lse: bool = False, pieces: Optional[int] = None):
+    """flash_mla_sparse_decode over an FP8 latent cache (DeepSeek-V3.2 as it is served; include/mfa_mla_sparse_fp8.h): kv_cache
+    [B, C, 576] torch.float8_e4m3fn (or, with block_table, a page pool [pages, pageSize, 576]) as mla_cache_append writes it, kv_scale
+    fp32 [1] on the GPU (None = 1.0) as flash_mla_decode_fp8 takes it, and indices [B, R, topk] int32 on the GPU as
+    flash_mla_sparse_decode takes them: logical key positions, shared by all heads; -1, a position at or past cache_lengths[b] and, with
+    `causal`, a position past r + max(len - R, 0) are holes, whose 576 bytes are never loaded -- nor is any key that no list names, so
+    such rows may hold the NaN bytes 0x7f / 0xff.  No temporary is gathered: the kernel reads the listed rows where they lie.
+    q [B, H, R, 576] bf16 or fp16 (R <= 32), softmax_scale (required), cache_lengths, return_lse and O [B, H, R, 512] in q's type are
+    flash_mla_decode's; pieces cuts the SLOTS of a list.  Forward only, GPU only.  Goes through the torch.library op
+    `mfa::attention_mla_sparse_decode_fp8` where torch has custom ops, so it traces under torch.compile."""
+    who = "flash_mla_sparse_decode_fp8"
+    if not (q.is_cuda and kv_cache.is_cuda and cache_lengths.is_cuda and indices.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, kv_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} is forward only (no autograd): detach the inputs")
+    pieces = 0 if pieces is None else pieces
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces, True)
+    _check_mla_indices(who, q, indices)
+    _latent_scale(who, kv_scale, kv_cache.device)
+    o, l = _call_op(_HAVE_MLA_SPARSE_FP8_OP, "attention_mla_sparse_decode_fp8", q, kv_cache, cache_lengths, indices, block_table, bool(causal),
+                    float(softmax_scale), int(pieces), kv_scale)
     return (o, l * _LN2) if return_lse else o
