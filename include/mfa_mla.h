@@ -48,9 +48,10 @@
  *
  * Kernels: attn_mla16_d576_<bf16|f16> (unsplit), attn_mla16_d576_<type>_k (a piece of the keys), attn_mla16_d576_<type>_combine.
  *
- * Deliberately not here: a window, sinks, a soft cap or trees on this entry; prefill over the latent cache (rows > 32); more than 32
- * packed rows per workgroup (at heads = 128 a sequence's four groups each walk the cache); other (Dk, Dv) pairs.  In mfa_mla_cache.h,
- * beside this header: the append kernel for the latent cache, and decode over e4m3 latent caches.
+ * Deliberately not here: a window, sinks, a soft cap or trees on this entry; more than 32 packed rows per workgroup (at heads = 128 a
+ * sequence's four groups each walk the cache); other (Dk, Dv) pairs.  In mfa_mla_cache.h, beside this header: the append kernel for the
+ * latent cache, and decode over e4m3 latent caches.  In mfa_mla_prefill.h: prefill over the latent cache, blocks of rows of any length
+ * (this entry still refuses rows > 32).
  */
 #ifndef MFA_MLA_H
 #define MFA_MLA_H

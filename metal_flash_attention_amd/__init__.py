@@ -13,6 +13,7 @@ from .attention import (  # noqa: F401
     AttentionKernelType,
     AttentionMLADecode,
     AttentionMLADecodeFP8,
+    AttentionMLAPrefill,
     AttentionMLASparseDecode,
     AttentionMLASparseDecodeFP8,
     AttentionOperand,
@@ -37,7 +38,7 @@ from .gemm import GEMMDescriptor, GEMMKernel, GEMMKernelDescriptor  # noqa: F401
 def __getattr__(name):
     # the torch functions of the KV-cache loop, on first use: torch stays optional for everything above
     if name in ("kv_cache_compact", "tree_path", "flash_mla_decode", "flash_mla_decode_fp8", "mla_cache_append", "flash_mla_sparse_decode",
-                "flash_mla_sparse_decode_fp8"):
+                "flash_mla_sparse_decode_fp8", "flash_mla_prefill"):
         from . import torch_binding
         return getattr(torch_binding, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -429,6 +429,35 @@ MLA_SPARSE_FP8_SYMBOLS = [   # include/mfa_mla_sparse_fp8.h: the sparse entries 
      _MLA_BUFS + [_MLA, _MLA_SPARSE, _MLA_QUANT, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
 ]
 
+class mfa_mla_prefill_params(ctypes.Structure):   # include/mfa_mla_prefill.h
+    _fields_ = [
+        ("rows", ctypes.c_uint32), ("column", ctypes.c_uint32), ("heads", ctypes.c_uint32), ("batches", ctypes.c_uint32),
+        ("causal", ctypes.c_uint32),
+        ("headDimension", ctypes.c_uint16), ("valueDimension", ctypes.c_uint16),
+        ("precision", ctypes.c_uint8), ("outputPrecision", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
+        ("scale", ctypes.c_float), ("pageSize", ctypes.c_uint32),
+        ("cacheLengths", ctypes.c_void_p), ("queryLengths", ctypes.c_void_p), ("blockTable", ctypes.c_void_p),
+        ("blockTableStride", ctypes.c_int64),
+        ("leadingDimension", ctypes.c_int64 * 3), ("headStride", ctypes.c_int64 * 3), ("batchStride", ctypes.c_int64 * 3),
+        ("pageStride", ctypes.c_int64),
+        ("lHeadStride", ctypes.c_int64), ("lBatchStride", ctypes.c_int64),
+    ]
+
+
+_MLA_PREFILL = ctypes.POINTER(mfa_mla_prefill_params)
+MFA_MLA_PREFILL_PACKED_ROWS, MFA_MLA_PREFILL_KEY_STEP = 64, 32
+
+MLA_PREFILL_SYMBOLS = [   # include/mfa_mla_prefill.h: MLA prefill over the latent cache, row blocks of any length; an entry of its own, no family
+    ("mfa_mla_prefill_params_init", None, [_MLA_PREFILL]),
+    ("mfa_mla_prefill_params_size", ctypes.c_size_t, []),
+    ("mfa_mla_prefill_params_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
+    ("mfa_attention_mla_prefill_launch", ctypes.c_int, _MLA_BUFS + [_MLA_PREFILL, ctypes.c_void_p]),
+    ("mfa_attention_mla_prefill_launch_form", ctypes.c_int, [_MLA_PREFILL, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_mla_prefill_time", ctypes.c_int,
+     _MLA_BUFS + [_MLA_PREFILL, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    ("mfa_attention_mla_prefill_step_range", ctypes.c_int, [ctypes.c_uint32] * 5 + [_U32P, _U32P]),
+]
+
 # ---- the laddered entries of the launches over a KV cache, described once:
 #     mfa_attention_<launch>_<family><verb>(*<the verb's head>, params, *<the options the family owns>, *<the verb's tail>)
 # CACHE_FAMILIES: launch -> family -> the options its entries take, in the order of their signatures (each family is an earlier one plus an
@@ -535,7 +564,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS + MLA_SPARSE_SYMBOLS + MLA_SPARSE_FP8_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS + MLA_SPARSE_SYMBOLS + MLA_SPARSE_FP8_SYMBOLS + MLA_PREFILL_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

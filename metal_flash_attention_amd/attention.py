@@ -1084,6 +1084,77 @@ class AttentionMLASparseDecodeFP8(AttentionMLASparseDecode):
         return getattr(lib(), "mfa_attention_mla_sparse_decode_fp8_" + verb)
 
 
+class AttentionMLAPrefill:
+    """Multi-head latent attention prefill over the compressed KV cache (include/mfa_mla_prefill.h): a block of `rows` new query rows per
+    sequence and head, of any length, q [batches][heads][rows][576], against the cache rows AttentionMLADecode reads;
+    o [batches][heads][rows][512].  Sequence b uses its first queryLengths[b] rows (device uint32, None: `rows`); the others are neither
+    read nor written.  The softmax scale is the model's own and must be given.
+
+        mla = AttentionMLAPrefill(GEMMOperandPrecision.BF16)
+        mla.dispatch(q, kv, o, l, cacheLengths=lengths, queryLengths=new, rows=512, column=C, heads=128, batches=B, scale=s)
+
+    `strides`, pageSize, blockTable and pageStride as AttentionMLADecode takes them: a token-major q / o is a plain launch.  The launch
+    is not cut along the keys: no pieces, no workspace, no plannedSplit."""
+
+    OPERANDS = ("Q", "KV", "O")
+    HEAD_DIMENSION, VALUE_DIMENSION = _abi.MFA_MLA_HEAD_DIMENSION, _abi.MFA_MLA_VALUE_DIMENSION
+    PACKED_ROWS, KEY_STEP = _abi.MFA_MLA_PREFILL_PACKED_ROWS, _abi.MFA_MLA_PREFILL_KEY_STEP
+
+    def __init__(self, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16, outputPrecision: Optional[GEMMOperandPrecision] = None,
+                 headDimension: int = _abi.MFA_MLA_HEAD_DIMENSION, valueDimension: int = _abi.MFA_MLA_VALUE_DIMENSION):
+        self.precision = GEMMOperandPrecision(precision)
+        self.outputPrecision = self.precision if outputPrecision is None else GEMMOperandPrecision(outputPrecision)
+        self.headDimension, self.valueDimension = int(headDimension), int(valueDimension)
+
+    def _params(self, *, rows: int, column: int, scale: float, heads: int = 1, batches: int = 1, causal: bool = True,
+                lStrides: Optional[Sequence[int]] = None, cacheLengths=None, queryLengths=None, pageSize: int = 0, blockTable=None,
+                blockTableStride: int = 0, strides: Optional[Mapping] = None, pageStride: Optional[int] = None):
+        p = _abi.mfa_mla_prefill_params()
+        lib().mfa_mla_prefill_params_init(ctypes.byref(p))
+        Dk, Dv = self.headDimension, self.valueDimension
+        p.rows, p.column, p.heads, p.batches = int(rows), int(column), int(heads), int(batches)
+        p.headDimension, p.valueDimension, p.causal, p.scale = Dk, Dv, int(bool(causal)), float(scale)
+        p.precision, p.outputPrecision = int(self.precision), int(self.outputPrecision)
+        p.pageSize, p.cacheLengths, p.queryLengths = int(pageSize), _pointer(cacheLengths), _pointer(queryLengths)
+        p.blockTable, p.blockTableStride = _pointer(blockTable), int(blockTableStride)
+        packed = (_packed(rows, heads, Dk), (Dk, 0, int(column) * Dk), _packed(rows, heads, Dv))
+        for i, name in enumerate(self.OPERANDS):
+            ld, hs, bs = strides.get(name, packed[i]) if strides else packed[i]
+            p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
+        p.pageStride = int(pageStride) if pageStride is not None else int(pageSize) * int(p.leadingDimension[1])
+        p.lHeadStride, p.lBatchStride = (int(lStrides[0]), int(lStrides[1])) if lStrides is not None else (int(rows), int(heads) * int(rows))
+        return p, (cacheLengths, queryLengths, blockTable)
+
+    def launchForm(self, **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name and the grid"""
+        p, _keep = self._params(**shape)
+        out = ctypes.create_string_buffer(512)
+        check(lib().mfa_attention_mla_prefill_launch_form(ctypes.byref(p), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, kv, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        """mfa_attention_mla_prefill_launch"""
+        p, _keep = self._params(**shape)
+        check(lib().mfa_attention_mla_prefill_launch(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.c_void_p(stream or 0)))
+
+    def time(self, q, kv, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
+        p, _keep = self._params(**shape)
+        ms = ctypes.c_float(0.0)
+        check(lib().mfa_attention_mla_prefill_time(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.c_void_p(stream or 0), int(warmup),
+                                                   int(iterations), ctypes.byref(ms)))
+        return float(ms.value)
+
+    @staticmethod
+    def stepRange(length: int, queryLength: int, firstPacked: int, heads: int, causal: bool = True) -> Tuple[int, int]:
+        """mfa_attention_mla_prefill_step_range -> (firstMasked, end), in 32-key steps: the kernels' own range function for the block of
+        the 64 packed rows from `firstPacked` (p = row x heads + head)"""
+        first, end = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        check(lib().mfa_attention_mla_prefill_step_range(int(length), int(queryLength), int(firstPacked), int(heads), int(bool(causal)),
+                                                         ctypes.byref(first), ctypes.byref(end)))
+        return int(first.value), int(end.value)
+
+
 class MLACacheAppend:
     """Appends the `rows` new rows of every sequence to the latent cache of MLA decode (include/mfa_mla_cache.h) -- latentNew
     [batches][rows][512] and ropeNew [batches][rows][64] become one cache row of 576 -- quantising them to e4m3 when the cache is FP8

@@ -33,7 +33,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAPrefill, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
                         KVCachePrecision, MLACacheAppend)
 
@@ -682,6 +682,36 @@ def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_sca
     return o, l
 
 
+def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale):
+    """flash_mla_prefill's launch (include/mfa_mla_prefill.h) on q's device and torch's current stream -> (O [B, H, R, 512], L [B, H, R]
+    base 2).  (Rows past q_lengths[b] are not written: no memset is spent on them, they come back uninitialised)"""
+    who = "flash_mla_prefill"
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, 0)
+    B = int(q.shape[0])
+    if q_lengths is not None:
+        _check_lengths(who, "q_lengths", q_lengths, B)
+    paged = block_table is not None
+    q, q_strides = _new_operand(q)
+    _B, H, R, _Dk = q.shape
+    Dv = AttentionMLAPrefill.VALUE_DIMENSION
+    ld = int(kv_cache.stride(1)) if kv_cache.shape[1] > 1 else int(kv_cache.shape[2])
+    kw = dict(rows=R, heads=H, batches=B, causal=bool(causal), scale=float(softmax_scale), cacheLengths=cache_lengths.to(torch.int32),
+              queryLengths=None if q_lengths is None else q_lengths.to(torch.int32),
+              strides={"Q": q_strides, "KV": (ld, 0, 0 if paged else int(kv_cache.stride(0)))},
+              column=int(kv_cache.shape[1]) * (int(block_table.shape[1]) if paged else 1))
+    if paged:
+        kw.update(pageSize=int(kv_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)), pageStride=int(kv_cache.stride(0)))
+    key = (AttentionMLAPrefill, q.dtype)
+    host = _HOSTS.get(key)
+    if host is None:
+        host = _HOSTS[key] = AttentionMLAPrefill(P.BF16 if q.dtype == torch.bfloat16 else P.FP16)
+    o = torch.empty((B, H, R, Dv), dtype=q.dtype, device=q.device)
+    l = torch.empty((B, H, R), dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        host.dispatch(q, kv_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
+    return o, l
+
+
 def _latent_scale(who, t, device):
     """kv_scale as the kernels read it: fp32 [1] on the cache's device; None stays None (1.0)"""
     if t is None:
@@ -961,6 +991,12 @@ def _op_mla_sparse_decode_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_len
     return _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_scale, pieces, True, kv_scale, indices=indices)
 
 
+def _op_mla_prefill(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, q_lengths: Optional[torch.Tensor],
+                    block_table: Optional[torch.Tensor], causal: bool, softmax_scale: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(`q_lengths` after the cache's lengths, as attention_prefill's; no pieces: the launch is not cut along the keys)"""
+    return _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale)
+
+
 def _op_mla_append(latent_new: torch.Tensor, rope_new: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor,
                    block_table: Optional[torch.Tensor], kv_scale: Optional[torch.Tensor]) -> None:
     _run_mla_append(latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale)
@@ -1064,6 +1100,13 @@ _MLA_SPARSE_FP8_OPS = [
 ]
 _HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_SPARSE_FP8_OPS})
 _HAVE_MLA_SPARSE_FP8_OP = _HAVE["attention_mla_sparse_decode_fp8"]
+
+# the op of include/mfa_mla_prefill.h, in a list of its own
+_MLA_PREFILL_OPS = [
+    ("attention_mla_prefill", _op_mla_prefill, _fake_mla, ()),
+]
+_HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_PREFILL_OPS})
+_HAVE_MLA_PREFILL_OP = _HAVE["attention_mla_prefill"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1298,6 +1341,32 @@ def flash_mla_decode(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: tor
     pieces = 0 if pieces is None else pieces
     _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, pieces)
     o, l = _call_op(_HAVE_MLA_OP, "attention_mla_decode", q, kv_cache, cache_lengths, block_table, bool(causal), float(softmax_scale), int(pieces))
+    return (o, l * _LN2) if return_lse else o
+
+
+def flash_mla_prefill(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, *, softmax_scale: float,
+                      q_lengths: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None, causal: bool = True,
+                      return_lse: bool = False):
+    """Multi-head latent attention prefill in its absorbed form over the compressed cache of flash_mla_decode (include/mfa_mla_prefill.h): a
+    block of R new rows per sequence and head, of ANY length, q [B, H, R, 576], against kv_cache [B, C, 576] (with block_table [B, n] int32:
+    a page pool [pages, pageSize, 576]) -- chunked prefill, prefix reuse, the extend step after a cache hit, a long draft block.  Returns
+    O [B, H, R, 512], and with return_lse also L [B, H, R] fp32 in natural units.  softmax_scale is the model's own scale and is required.
+    cache_lengths [B] (GPU): valid keys per sequence INCLUDING the new tokens, which the caller has already written (mla_cache_append).
+    q_lengths [B] (GPU; None: every sequence has R): the new rows of each sequence; with `causal` row r < q_lengths[b] sees key c iff
+    c <= r + max(len - q_lengths[b], 0).  Rows at or past q_lengths[b] are neither read nor written: they come back uninitialised.  A row
+    without a visible key gets O = 0.  q may be any view with a contiguous last dimension and strides that are multiples of 8 -- a
+    transposed token-major [B, R, H, 576] is read where it lies.  Forward only, GPU only.  Goes through the torch.library op
+    `mfa::attention_mla_prefill` where torch has custom ops, so it traces under torch.compile."""
+    who = "flash_mla_prefill"
+    if not (q.is_cuda and kv_cache.is_cuda and cache_lengths.is_cuda) or (q_lengths is not None and not q_lengths.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, kv_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} is forward only (no autograd): detach the inputs")
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, 0)
+    if q_lengths is not None:
+        _check_lengths(who, "q_lengths", q_lengths, int(q.shape[0]))
+    o, l = _call_op(_HAVE_MLA_PREFILL_OP, "attention_mla_prefill", q, kv_cache, cache_lengths, q_lengths, block_table, bool(causal), float(softmax_scale))
     return (o, l * _LN2) if return_lse else o
 
 
