@@ -1155,6 +1155,60 @@ class AttentionMLAPrefill:
         return int(first.value), int(end.value)
 
 
+class AttentionMLAPrefillSplit(AttentionMLAPrefill):
+    """AttentionMLAPrefill CUT ALONG THE KEYS (include/mfa_mla_prefill_split.h): few row blocks over a long latent cache -- a chunk of a
+    chunked prefill behind a long prefix -- run as `pieces` workgroups a block and a combine kernel.  The keywords of AttentionMLAPrefill
+    plus pieces= (None or 0: the host's plan, 1: unsplit, 2 .. 64: as given), workspace= (device, 16-byte aligned; None: the unsplit
+    launch) and workspaceBytes= (default: the workspace tensor's size).
+
+        mla = AttentionMLAPrefillSplit(GEMMOperandPrecision.BF16)
+        nbytes, pieces = mla.plannedSplit(rows=64, column=C, heads=16, batches=1, scale=s)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        mla.dispatch(q, kv, o, l, cacheLengths=lengths, rows=64, column=C, heads=16, batches=1, scale=s, workspace=ws)"""
+
+    MAX_PIECES = _abi.MFA_MLA_PREFILL_SPLIT_MAX_PIECES
+
+    def _split_params(self, shape):
+        split, kept = _split_block(shape)
+        p, keep = self._params(**shape)
+        return p, split, (keep, kept)
+
+    def plannedSplit(self, **shape) -> Tuple[int, int]:
+        """mfa_attention_mla_prefill_split_workspace_size -> (bytes of the workspace the launch needs, its pieces); (0, 1): not cut"""
+        p, split, _keep = self._split_params(shape)
+        nbytes, pieces = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        check(lib().mfa_attention_mla_prefill_split_workspace_size(ctypes.byref(p), ctypes.byref(split), ctypes.byref(nbytes), ctypes.byref(pieces)))
+        return int(nbytes.value), int(pieces.value)
+
+    def launchForm(self, **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the kernels' names and their grids"""
+        p, split, _keep = self._split_params(shape)
+        out = ctypes.create_string_buffer(512)
+        check(lib().mfa_attention_mla_prefill_split_launch_form(ctypes.byref(p), ctypes.byref(split), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, kv, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        """mfa_attention_mla_prefill_split_launch"""
+        p, split, _keep = self._split_params(shape)
+        check(lib().mfa_attention_mla_prefill_split_launch(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.byref(split), ctypes.c_void_p(stream or 0)))
+
+    def time(self, q, kv, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches, both kernels of a cut launch (HIP events on `stream`)."""
+        p, split, _keep = self._split_params(shape)
+        ms = ctypes.c_float(0.0)
+        check(lib().mfa_attention_mla_prefill_split_time(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.byref(split), ctypes.c_void_p(stream or 0),
+                                                         int(warmup), int(iterations), ctypes.byref(ms)))
+        return float(ms.value)
+
+    @staticmethod
+    def pieceRange(end: int, pieces: int, piece: int) -> Tuple[int, int]:
+        """mfa_attention_mla_prefill_split_piece_range -> (beginStep, endStep): the steps of piece `piece` of `pieces` of a block whose
+        walk is the steps [0, end) -- the kernels' own function"""
+        begin, stop = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        check(lib().mfa_attention_mla_prefill_split_piece_range(int(end), int(pieces), int(piece), ctypes.byref(begin), ctypes.byref(stop)))
+        return int(begin.value), int(stop.value)
+
+
 class MLACacheAppend:
     """Appends the `rows` new rows of every sequence to the latent cache of MLA decode (include/mfa_mla_cache.h) -- latentNew
     [batches][rows][512] and ropeNew [batches][rows][64] become one cache row of 576 -- quantising them to e4m3 when the cache is FP8

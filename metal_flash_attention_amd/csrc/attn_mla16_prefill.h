@@ -19,6 +19,10 @@
 //   * what may hold poison is never loaded: key rows at or past n come in as zeros, block-table entries past the last page are not
 //     read, lanes at or past the last live packed row repeat it and store nothing, rows at or past qn are never read.
 //   * LDS: 4 x 8 KiB images + 2 x 32 KiB exchange buffers = 96 KiB; one workgroup a compute unit, up to 512 registers a lane.
+//   * SPLIT (include/mfa_mla_prefill_split.h): the grid gains the pieces, fastest; piece s of a block walks the steps
+//     mla_prefill_split_piece_range gives it of the block's OWN [0, end) and publishes un-normalised O and (m, l) in FP32 (wsO
+//     [pieces][B][packed p][Dv], wsML [pieces][B][packed p][2]); mla_prefill_combine_body, one wave a packed row, merges them.  The step
+//     is the same step; only the walk's bounds and the epilogue differ.
 #pragma once
 #include "attn_mla16.h"
 
@@ -45,6 +49,8 @@ struct MlaPrefillArgs {
   uint32_t paged, pageShift;      // pageSize = 1 << pageShift
   uint32_t causal, outF32;
   float scale2;                   // fl(scale x log2 e)
+  uint32_t pieces;                // the split launch only (attn_mla16_prefill_split.hip); last, so that no other field moves
+  float *wsO, *wsML;
 };
 
 // The 32-key steps of the block of the 64 packed rows from p0 (p = row x H + head) of a sequence of n keys and qn rows: row r sees the
@@ -75,6 +81,15 @@ __host__ __device__ __forceinline__ void mla_prefill_step_range(uint32_t n, uint
   *end = (uint32_t)e;
 }
 
+// Piece `piece` of `pieces` of a block's steps [0, end): [piece x end / pieces, (piece + 1) x end / pieces).  The pieces are ordered,
+// disjoint, cover [0, end) and differ by at most one step; with more pieces than steps some are empty.  Device and host run this one
+// body (mfa_attention_mla_prefill_split_piece_range).
+__host__ __device__ __forceinline__ void mla_prefill_split_piece_range(uint32_t end, uint32_t pieces, uint32_t piece, uint32_t *beginStep,
+                                                                       uint32_t *endStep) {
+  *beginStep = (uint32_t)((uint64_t)piece * end / pieces);
+  *endStep = (uint32_t)(((uint64_t)piece + 1) * end / pieces);
+}
+
 // rescale_row (attn_cache_step.h) behind a WAVE-uniform test: a lane whose maximum does not rise multiplies by 1.0f, which changes no
 // bit, so the row's arithmetic is rescale_row's.  (With 128 accumulators a lane the per-lane branch made hipcc spill them.)
 template <int NDB> __device__ __forceinline__ void rescale_row_uniform(float mx, float &m, float &l, f32x16 (&o)[NDB]) {
@@ -90,7 +105,7 @@ template <int NDB> __device__ __forceinline__ void rescale_row_uniform(float mx,
   }
 }
 
-template <typename T>
+template <typename T, bool SPLIT = false>
 __device__ __forceinline__ void mla_prefill_body(const MlaPrefillArgs &a) {
   typedef Frag16<T> F;
   typedef typename F::v8 v8;
@@ -99,7 +114,9 @@ __device__ __forceinline__ void mla_prefill_body(const MlaPrefillArgs &a) {
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, q = lane & 31, hi = lane >> 5;
-  const uint32_t block = blockIdx.x % a.blocks, batch = blockIdx.x / a.blocks;
+  const uint32_t piece = SPLIT ? blockIdx.x % a.pieces : 0u;   // (fastest: a block's pieces are neighbours)
+  const uint32_t bb = SPLIT ? blockIdx.x / a.pieces : blockIdx.x;
+  const uint32_t block = bb % a.blocks, batch = bb / a.blocks;
   const uint32_t H = a.H;
   const uint32_t n = min(a.lengths[batch], a.column);
   const uint32_t qn = a.qlengths ? min(a.qlengths[batch], a.R) : a.R;
@@ -108,6 +125,16 @@ __device__ __forceinline__ void mla_prefill_body(const MlaPrefillArgs &a) {
   uint32_t firstMasked, stepEnd;
   mla_prefill_step_range(n, qn, p0, H, a.causal, &firstMasked, &stepEnd);
   const uint32_t live = qn * H;   // packed rows of the sequence
+  uint32_t stepBegin = 0;
+  if constexpr (SPLIT) {
+    mla_prefill_split_piece_range(stepEnd, a.pieces, piece, &stepBegin, &stepEnd);
+    if (stepBegin >= stepEnd) {   // a piece without a step: (m, l) = (-FLT_MAX, 0) for the live rows, no O (the whole workgroup, ahead
+      const uint32_t p = p0 + (uint32_t)tid;   // of every barrier)
+      if (tid < MLAP_ROWS && p < live)
+        *reinterpret_cast<float2 *>(a.wsML + (((size_t)piece * a.batches + batch) * ((size_t)a.R * H) + p) * 2) = make_float2(STEP_MINUS_HUGE, 0.f);
+      return;
+    }
+  }
 
   // ---- the lane's packed query row of each tile; rows at or past `live` repeat the last live one and are not stored
   const int col0 = MLA_LATENT * wave + 8 * hi, colR = MLA_DV + MLA_ROPE * wave + 8 * hi;
@@ -176,7 +203,7 @@ __device__ __forceinline__ void mla_prefill_body(const MlaPrefillArgs &a) {
   const int vtr_off = vtr_lane_offset(lane, hi);
 
   const uint32_t keyEnd = stepEnd * (uint32_t)MLA_STEP, unmaskedEnd = firstMasked * (uint32_t)MLA_STEP;
-  uint32_t key0 = 0, buf = 0;
+  uint32_t key0 = stepBegin * (uint32_t)MLA_STEP, buf = 0;
   if (key0 < keyEnd) issue_loads(key0);
   while (key0 < keyEnd) {   // (the same trips for every wave: the barrier below is met by all)
     // ---- the wave's partial S^T = K Q^T over its 144 columns, one per tile: s[t][r] = key key0 + crow(r, hi), packed row q of tile t
@@ -243,23 +270,80 @@ __device__ __forceinline__ void mla_prefill_body(const MlaPrefillArgs &a) {
   }
 
   // ---- every wave holds the rows' (m, l) and its own columns of O^T: no merge.  o[t][db][4 g + i] is d = 128 w + 32 db + 8 g + 4 hi + i
-  // (no barrier follows)
+  // (no barrier follows).  SPLIT: un-normalised, to the piece's slab
 #pragma unroll
   for (int t = 0; t < MLAP_TILES; ++t) {
     const float l_tot = l[t] + __shfl_xor(l[t], 32);
-    if (p0 + (uint32_t)(MLA_ROWS * t + q) >= live) continue;
-    const float mult = l_tot > 0.f ? 1.0f / l_tot : 0.f;   // a row without a visible key: O = 0
+    const uint32_t p = p0 + (uint32_t)(MLA_ROWS * t + q);
+    if (p >= live) continue;
+    float mult = 1.0f;
+    if constexpr (!SPLIT) mult = l_tot > 0.f ? 1.0f / l_tot : 0.f;   // a row without a visible key: O = 0
+    const size_t slab = SPLIT ? ((size_t)piece * a.batches + batch) * ((size_t)a.R * H) + p : 0;
     const int64_t at0 = (int64_t)batch * a.bso + (int64_t)head[t] * a.hso + (int64_t)qrow[t] * a.ldo;
 #pragma unroll
     for (int db = 0; db < MLA_NDB; ++db)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int d = MLA_LATENT * wave + 32 * db + 8 * g + 4 * hi;
-        store_o4<T>(a.o, at0 + d, a.outF32,
-                    make_float4(o[t][db][4 * g] * mult, o[t][db][4 * g + 1] * mult, o[t][db][4 * g + 2] * mult, o[t][db][4 * g + 3] * mult));
+        const float4 x = make_float4(o[t][db][4 * g] * mult, o[t][db][4 * g + 1] * mult, o[t][db][4 * g + 2] * mult, o[t][db][4 * g + 3] * mult);
+        if constexpr (SPLIT) *reinterpret_cast<float4 *>(a.wsO + slab * MLA_DV + d) = x;
+        else store_o4<T>(a.o, at0 + d, a.outF32, x);
       }
-    if (wave == 0 && hi == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)head[t] * a.lhs + qrow[t]] = row_lse(m[t], l_tot);
+    if (wave == 0 && hi == 0) {
+      if constexpr (SPLIT) *reinterpret_cast<float2 *>(a.wsML + slab * 2) = make_float2(m[t], l_tot);
+      else if (a.l) a.l[(int64_t)batch * a.lbs + (int64_t)head[t] * a.lhs + qrow[t]] = row_lse(m[t], l_tot);
+    }
   }
+}
+
+// Merge the pieces: mla_combine_body's arithmetic in its order (attn_mla16.h), for prefill's packing.  One wave per packed row of the
+// capacity, p = row x H + head; lane s holds (m_s, l_s) of piece s; for O a lane owns the float4 columns lane and lane + 64 and walks
+// the pieces in order.  A row at or past queryLengths[b] returns before it reads anything: its block may not have run, and nothing of
+// the workspace is read that this launch did not write.  A piece without a visible key has l = 0: weight 0, its slab is not read.
+template <typename T>
+__device__ __forceinline__ void mla_prefill_combine_body(const MlaPrefillArgs &a) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t S = a.pieces;
+  const uint64_t M = (uint64_t)a.R * a.H, rows = (uint64_t)a.batches * M;
+  const uint64_t rowid = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (rowid >= rows) return;
+  const uint32_t pr = (uint32_t)(rowid % M), batch = (uint32_t)(rowid / M);
+  const uint32_t row = pr / a.H, head = pr % a.H;
+  const uint32_t qn = a.qlengths ? min(a.qlengths[batch], a.R) : a.R;
+  if (row >= qn) return;
+  float ms = STEP_MINUS_HUGE, ls = 0.f;
+  if ((uint32_t)lane < S) {
+    const float2 ml = *reinterpret_cast<const float2 *>(a.wsML + ((uint64_t)lane * rows + rowid) * 2);
+    ms = ml.x; ls = ml.y;
+  }
+  if (!(ls > 0.f)) ms = STEP_MINUS_HUGE;   // (an empty piece never sets the maximum)
+  float mstar = ms;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) mstar = fmaxf(mstar, __shfl_xor(mstar, off, 64));
+  const float w = ((uint32_t)lane < S && ls > 0.f) ? fast_exp2(ms - mstar) : 0.f;
+  float lstar = w * ls;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) lstar += __shfl_xor(lstar, off, 64);
+  float4 acc[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+  for (uint32_t s_ = 0; s_ < S; ++s_) {
+    const float ws = __shfl(w, (int)s_, 64);
+    if (ws > 0.f) {   // (wave-uniform)
+      const float *src = a.wsO + ((uint64_t)s_ * rows + rowid) * MLA_DV;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const float4 x = *reinterpret_cast<const float4 *>(src + (lane + 64 * j) * 4);
+        acc[j].x += ws * x.x; acc[j].y += ws * x.y; acc[j].z += ws * x.z; acc[j].w += ws * x.w;
+      }
+    }
+  }
+  const float inv = lstar > 0.f ? 1.0f / lstar : 0.f;
+  const int64_t at = (int64_t)batch * a.bso + (int64_t)head * a.hso + (int64_t)row * a.ldo;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    acc[j].x *= inv; acc[j].y *= inv; acc[j].z *= inv; acc[j].w *= inv;
+    store_o4<T>(a.o, at + (lane + 64 * j) * 4, a.outF32, acc[j]);
+  }
+  if (lane == 0 && a.l) a.l[(int64_t)batch * a.lbs + (int64_t)head * a.lhs + row] = row_lse(mstar, lstar);
 }
 
 } // namespace mfa

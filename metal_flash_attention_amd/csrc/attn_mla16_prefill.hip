@@ -14,6 +14,7 @@
 
 #include "../../include/mfa_mla_prefill.h"
 #include "attn_mla16_prefill.h"
+#include "attn_mla16_prefill_launch.h"
 #include "cache_launch.h"
 #include "launchers.h"
 #include "mfa_internal.h"
@@ -105,6 +106,14 @@ mfa_status bind_mla_prefill(MlaPrefillPlan *plan, const void *q, const void *kv,
 }
 
 } // namespace
+
+// what the split entries (attn_mla16_prefill_split.hip) take from this plan: its checks in its words, and its argument block
+mfa_status mfa::mla_prefill_prepare_args(const mfa_mla_prefill_params *p, MlaPrefillArgs *args) {
+  MlaPrefillPlan plan;
+  const mfa_status st = plan.prepare(p);
+  if (st == MFA_OK) *args = plan.args;
+  return st;
+}
 
 extern "C" {
 

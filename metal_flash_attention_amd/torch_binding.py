@@ -33,7 +33,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAPrefill, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAPrefill, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
                         KVCachePrecision, MLACacheAppend)
 
@@ -682,11 +682,13 @@ def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_sca
     return o, l
 
 
-def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale):
+def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces=None):
     """flash_mla_prefill's launch (include/mfa_mla_prefill.h) on q's device and torch's current stream -> (O [B, H, R, 512], L [B, H, R]
-    base 2).  (Rows past q_lengths[b] are not written: no memset is spent on them, they come back uninitialised)"""
-    who = "flash_mla_prefill"
-    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, 0)
+    base 2).  (Rows past q_lengths[b] are not written: no memset is spent on them, they come back uninitialised.)  key_pieces not None:
+    flash_mla_prefill_split's launch, cut along the keys (include/mfa_mla_prefill_split.h); its workspace is allocated here"""
+    split = key_pieces is not None
+    who = "flash_mla_prefill_split" if split else "flash_mla_prefill"
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, key_pieces if split else 0)
     B = int(q.shape[0])
     if q_lengths is not None:
         _check_lengths(who, "q_lengths", q_lengths, B)
@@ -701,12 +703,16 @@ def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal,
               column=int(kv_cache.shape[1]) * (int(block_table.shape[1]) if paged else 1))
     if paged:
         kw.update(pageSize=int(kv_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)), pageStride=int(kv_cache.stride(0)))
-    key = (AttentionMLAPrefill, q.dtype)
+    cls = AttentionMLAPrefillSplit if split else AttentionMLAPrefill
+    key = (cls, q.dtype)
     host = _HOSTS.get(key)
     if host is None:
-        host = _HOSTS[key] = AttentionMLAPrefill(P.BF16 if q.dtype == torch.bfloat16 else P.FP16)
+        host = _HOSTS[key] = cls(P.BF16 if q.dtype == torch.bfloat16 else P.FP16)
     o = torch.empty((B, H, R, Dv), dtype=q.dtype, device=q.device)
     l = torch.empty((B, H, R), dtype=torch.float32, device=q.device)
+    if split:
+        need, _pieces = host.plannedSplit(pieces=int(key_pieces), **kw)
+        kw.update(pieces=int(key_pieces), workspace=torch.empty(need, dtype=torch.uint8, device=q.device) if need else None)
     with torch.cuda.device(q.device):
         host.dispatch(q, kv_cache, o, l, stream=torch.cuda.current_stream(q.device).cuda_stream, **kw)
     return o, l
@@ -997,6 +1003,12 @@ def _op_mla_prefill(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torc
     return _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale)
 
 
+def _op_mla_prefill_split(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, q_lengths: Optional[torch.Tensor],
+                          block_table: Optional[torch.Tensor], causal: bool, softmax_scale: float, key_pieces: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(attention_mla_prefill's arguments; `key_pieces` last: 0 the host's plan, 1 unsplit, 2 .. 64 as given)"""
+    return _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces)
+
+
 def _op_mla_append(latent_new: torch.Tensor, rope_new: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor,
                    block_table: Optional[torch.Tensor], kv_scale: Optional[torch.Tensor]) -> None:
     _run_mla_append(latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale)
@@ -1107,6 +1119,12 @@ _MLA_PREFILL_OPS = [
 ]
 _HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_PREFILL_OPS})
 _HAVE_MLA_PREFILL_OP = _HAVE["attention_mla_prefill"]
+# the op of include/mfa_mla_prefill_split.h, in a list of its own
+_MLA_PREFILL_SPLIT_OPS = [
+    ("attention_mla_prefill_split", _op_mla_prefill_split, _fake_mla, ()),
+]
+_HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_PREFILL_SPLIT_OPS})
+_HAVE_MLA_PREFILL_SPLIT_OP = _HAVE["attention_mla_prefill_split"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1367,6 +1385,32 @@ def flash_mla_prefill(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: to
     if q_lengths is not None:
         _check_lengths(who, "q_lengths", q_lengths, int(q.shape[0]))
     o, l = _call_op(_HAVE_MLA_PREFILL_OP, "attention_mla_prefill", q, kv_cache, cache_lengths, q_lengths, block_table, bool(causal), float(softmax_scale))
+    return (o, l * _LN2) if return_lse else o
+
+
+def flash_mla_prefill_split(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, *, softmax_scale: float,
+                            q_lengths: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None, causal: bool = True,
+                            return_lse: bool = False, key_pieces: Optional[int] = None):
+    """flash_mla_prefill CUT ALONG THE KEYS (include/mfa_mla_prefill_split.h): for few row blocks over a long latent cache -- a chunk of a
+    chunked prefill, the rows behind a reused prefix of one long conversation -- where flash_mla_prefill's one workgroup per 64 packed
+    rows leaves most of the chip idle.  Every block's keys go to `key_pieces` workgroups and a combine kernel merges them: a straight
+    chain of two kernels that reads the lengths on the device, so one capture in a graph serves changed cache_lengths / q_lengths.
+    key_pieces: None or 0 the host's plan (from B, H, R and the cache's capacity alone; 1 where the launch fills the chip already), 1 the
+    unsplit launch (flash_mla_prefill bit for bit), 2 .. 64 as given.  The FP32 workspace, key_pieces x B x H x R x 514 x 4 bytes, is
+    allocated here.  Everything else -- operands, mask, q_lengths, rows that are not written, the results -- is flash_mla_prefill's.
+    Goes through the torch.library op `mfa::attention_mla_prefill_split` where torch has custom ops."""
+    who = "flash_mla_prefill_split"
+    if not (q.is_cuda and kv_cache.is_cuda and cache_lengths.is_cuda) or (q_lengths is not None and not q_lengths.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, kv_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} is forward only (no autograd): detach the inputs")
+    key_pieces = 0 if key_pieces is None else key_pieces
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, key_pieces)
+    if q_lengths is not None:
+        _check_lengths(who, "q_lengths", q_lengths, int(q.shape[0]))
+    o, l = _call_op(_HAVE_MLA_PREFILL_SPLIT_OP, "attention_mla_prefill_split", q, kv_cache, cache_lengths, q_lengths, block_table, bool(causal),
+                    float(softmax_scale), int(key_pieces))
     return (o, l * _LN2) if return_lse else o
 
 
