@@ -1209,6 +1209,97 @@ class AttentionMLAPrefillSplit(AttentionMLAPrefill):
         return int(begin.value), int(stop.value)
 
 
+def _mla_quant_block(cachePrecision: int, shape):
+    """mfa_mla_quant for the fp8 prefill entries, `kvScale` taken out of `shape` -> (the block, what it points to)"""
+    quant = _abi.mfa_mla_quant()
+    lib().mfa_mla_quant_init(ctypes.byref(quant))
+    quant.cachePrecision = int(cachePrecision)
+    keep = shape.pop("kvScale", None)
+    quant.kvScale = _pointer(keep)
+    return quant, keep
+
+
+class AttentionMLAPrefillFP8(AttentionMLAPrefill):
+    """MLA prefill over an FP8 (OCP e4m3) latent cache (include/mfa_mla_prefill_fp8.h): AttentionMLAPrefill's methods and arguments --
+    the KV strides count bytes, multiples of 16 -- plus kvScale (device FP32, one entry, None = 1.0): a cache byte stands for
+    kvScale[0] x e4m3(byte), latent and rotary part alike.  `precision` is the 16-bit type of Q.
+
+        mla = AttentionMLAPrefillFP8(GEMMOperandPrecision.BF16)
+        mla.dispatch(q, kv8, o, l, cacheLengths=lengths, queryLengths=new, rows=512, column=C, heads=128, batches=B, scale=s, kvScale=kv_scale)"""
+
+    def __init__(self, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16, outputPrecision: Optional[GEMMOperandPrecision] = None,
+                 cachePrecision: int = KVCachePrecision.E4M3, **widths):
+        super().__init__(precision, outputPrecision, **widths)
+        self.cachePrecision = int(cachePrecision)
+
+    def launchForm(self, **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name and the grid"""
+        quant, _kept = _mla_quant_block(self.cachePrecision, shape)
+        p, _keep = self._params(**shape)
+        out = ctypes.create_string_buffer(512)
+        check(lib().mfa_attention_mla_prefill_fp8_launch_form(ctypes.byref(p), ctypes.byref(quant), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, kv, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        """mfa_attention_mla_prefill_fp8_launch"""
+        quant, _kept = _mla_quant_block(self.cachePrecision, shape)
+        p, _keep = self._params(**shape)
+        check(lib().mfa_attention_mla_prefill_fp8_launch(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.byref(quant), ctypes.c_void_p(stream or 0)))
+
+    def time(self, q, kv, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
+        quant, _kept = _mla_quant_block(self.cachePrecision, shape)
+        p, _keep = self._params(**shape)
+        ms = ctypes.c_float(0.0)
+        check(lib().mfa_attention_mla_prefill_fp8_time(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.byref(quant), ctypes.c_void_p(stream or 0),
+                                                       int(warmup), int(iterations), ctypes.byref(ms)))
+        return float(ms.value)
+
+
+class AttentionMLAPrefillFP8Split(AttentionMLAPrefillSplit):
+    """AttentionMLAPrefillFP8 CUT ALONG THE KEYS (include/mfa_mla_prefill_fp8.h): AttentionMLAPrefillSplit's methods and arguments
+    (pieces=, workspace=, workspaceBytes=) over an e4m3 latent cache, plus kvScale.  The piece plan and the workspace size are
+    AttentionMLAPrefillSplit's; without a workspace, or at one piece, the launch is AttentionMLAPrefillFP8's."""
+
+    def __init__(self, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16, outputPrecision: Optional[GEMMOperandPrecision] = None,
+                 cachePrecision: int = KVCachePrecision.E4M3, **widths):
+        super().__init__(precision, outputPrecision, **widths)
+        self.cachePrecision = int(cachePrecision)
+
+    def plannedSplit(self, **shape) -> Tuple[int, int]:
+        """mfa_attention_mla_prefill_fp8_split_workspace_size -> (bytes of the workspace the launch needs, its pieces); (0, 1): not cut"""
+        quant, _kept = _mla_quant_block(self.cachePrecision, shape)
+        p, split, _keep = self._split_params(shape)
+        nbytes, pieces = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        check(lib().mfa_attention_mla_prefill_fp8_split_workspace_size(ctypes.byref(p), ctypes.byref(split), ctypes.byref(quant), ctypes.byref(nbytes),
+                                                                       ctypes.byref(pieces)))
+        return int(nbytes.value), int(pieces.value)
+
+    def launchForm(self, **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the kernels' names and their grids"""
+        quant, _kept = _mla_quant_block(self.cachePrecision, shape)
+        p, split, _keep = self._split_params(shape)
+        out = ctypes.create_string_buffer(512)
+        check(lib().mfa_attention_mla_prefill_fp8_split_launch_form(ctypes.byref(p), ctypes.byref(split), ctypes.byref(quant), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, kv, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        """mfa_attention_mla_prefill_fp8_split_launch"""
+        quant, _kept = _mla_quant_block(self.cachePrecision, shape)
+        p, split, _keep = self._split_params(shape)
+        check(lib().mfa_attention_mla_prefill_fp8_split_launch(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.byref(split), ctypes.byref(quant),
+                                                               ctypes.c_void_p(stream or 0)))
+
+    def time(self, q, kv, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches, both kernels of a cut launch (HIP events on `stream`)."""
+        quant, _kept = _mla_quant_block(self.cachePrecision, shape)
+        p, split, _keep = self._split_params(shape)
+        ms = ctypes.c_float(0.0)
+        check(lib().mfa_attention_mla_prefill_fp8_split_time(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.byref(split), ctypes.byref(quant),
+                                                             ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
+        return float(ms.value)
+
+
 class MLACacheAppend:
     """Appends the `rows` new rows of every sequence to the latent cache of MLA decode (include/mfa_mla_cache.h) -- latentNew
     [batches][rows][512] and ropeNew [batches][rows][64] become one cache row of 576 -- quantising them to e4m3 when the cache is FP8

@@ -33,7 +33,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAPrefill, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAPrefill, AttentionMLAPrefillFP8Split, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
                         KVCachePrecision, MLACacheAppend)
 
@@ -682,13 +682,18 @@ def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_sca
     return o, l
 
 
-def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces=None):
+def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces=None, fp8=False, kv_scale=None):
     """flash_mla_prefill's launch (include/mfa_mla_prefill.h) on q's device and torch's current stream -> (O [B, H, R, 512], L [B, H, R]
     base 2).  (Rows past q_lengths[b] are not written: no memset is spent on them, they come back uninitialised.)  key_pieces not None:
-    flash_mla_prefill_split's launch, cut along the keys (include/mfa_mla_prefill_split.h); its workspace is allocated here"""
+    flash_mla_prefill_split's launch, cut along the keys (include/mfa_mla_prefill_split.h); its workspace is allocated here.  `fp8`:
+    flash_mla_prefill_fp8's, over an e4m3 latent cache with `kv_scale` (include/mfa_mla_prefill_fp8.h; always its cut entries, which at
+    one piece run the unsplit kernel) -- the strides of such a cache count bytes, which are its elements"""
     split = key_pieces is not None
-    who = "flash_mla_prefill_split" if split else "flash_mla_prefill"
-    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, key_pieces if split else 0)
+    who = "flash_mla_prefill_fp8" if fp8 else "flash_mla_prefill_split" if split else "flash_mla_prefill"
+    if fp8 and kv_cache.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"{who}: the latent cache must be torch.float8_e4m3fn (got {kv_cache.dtype}); a 16-bit latent cache is flash_mla_prefill's, "
+                        "and e5m2 and fnuz caches have no kernel")
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, key_pieces if split else 0, fp8)
     B = int(q.shape[0])
     if q_lengths is not None:
         _check_lengths(who, "q_lengths", q_lengths, B)
@@ -703,7 +708,9 @@ def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal,
               column=int(kv_cache.shape[1]) * (int(block_table.shape[1]) if paged else 1))
     if paged:
         kw.update(pageSize=int(kv_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)), pageStride=int(kv_cache.stride(0)))
-    cls = AttentionMLAPrefillSplit if split else AttentionMLAPrefill
+    cls = AttentionMLAPrefillFP8Split if fp8 else AttentionMLAPrefillSplit if split else AttentionMLAPrefill
+    if fp8:
+        kw.update(kvScale=_latent_scale(who, kv_scale, kv_cache.device))
     key = (cls, q.dtype)
     host = _HOSTS.get(key)
     if host is None:
@@ -1009,6 +1016,13 @@ def _op_mla_prefill_split(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths
     return _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces)
 
 
+def _op_mla_prefill_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, q_lengths: Optional[torch.Tensor],
+                        block_table: Optional[torch.Tensor], causal: bool, softmax_scale: float, key_pieces: int,
+                        kv_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(attention_mla_prefill_split's arguments; `kv_scale` last, as attention_mla_decode_fp8's)"""
+    return _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces, True, kv_scale)
+
+
 def _op_mla_append(latent_new: torch.Tensor, rope_new: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor,
                    block_table: Optional[torch.Tensor], kv_scale: Optional[torch.Tensor]) -> None:
     _run_mla_append(latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale)
@@ -1125,6 +1139,12 @@ _MLA_PREFILL_SPLIT_OPS = [
 ]
 _HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_PREFILL_SPLIT_OPS})
 _HAVE_MLA_PREFILL_SPLIT_OP = _HAVE["attention_mla_prefill_split"]
+# the op of include/mfa_mla_prefill_fp8.h, in a list of its own
+_MLA_PREFILL_FP8_OPS = [
+    ("attention_mla_prefill_fp8", _op_mla_prefill_fp8, _fake_mla, ()),
+]
+_HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_PREFILL_FP8_OPS})
+_HAVE_MLA_PREFILL_FP8_OP = _HAVE["attention_mla_prefill_fp8"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1411,6 +1431,38 @@ def flash_mla_prefill_split(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengt
         _check_lengths(who, "q_lengths", q_lengths, int(q.shape[0]))
     o, l = _call_op(_HAVE_MLA_PREFILL_SPLIT_OP, "attention_mla_prefill_split", q, kv_cache, cache_lengths, q_lengths, block_table, bool(causal),
                     float(softmax_scale), int(key_pieces))
+    return (o, l * _LN2) if return_lse else o
+
+
+def flash_mla_prefill_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, *, softmax_scale: float,
+                          kv_scale: Optional[torch.Tensor] = None, q_lengths: Optional[torch.Tensor] = None,
+                          block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False,
+                          key_pieces: Optional[int] = 1):
+    """flash_mla_prefill over an FP8 latent cache (include/mfa_mla_prefill_fp8.h): kv_cache is torch.float8_e4m3fn, [B, C, 576] or a page
+    pool [pages, pageSize, 576] -- the cache mla_cache_append writes and flash_mla_decode_fp8 reads, so that an FP8 latent cache serves
+    append -> prefill -> decode without a 16-bit copy.  kv_scale (float32 [1] on the GPU; None: 1.0) is the cache's one scale: a byte b
+    stands for kv_scale x e4m3(b); the host never reads it.  q is bfloat16 or float16; everything else -- the mask, q_lengths, rows that
+    are not written, the results -- is flash_mla_prefill's.  Keys at or past a length, a last page's tail and pages no table names are
+    never loaded.  For every row the arithmetic is flash_mla_decode_fp8's at one piece, bit for bit: the result does not depend on how a
+    prompt is cut into chunks.  key_pieces: 1 (the default) the unsplit launch; None or 0 the host's plan, 2 .. 64 as given -- the cut
+    launch of flash_mla_prefill_split, its FP32 workspace allocated here.  Nothing is read on the host: one capture in a graph serves
+    changed cache_lengths / q_lengths.  Goes through the torch.library op `mfa::attention_mla_prefill_fp8` where torch has custom ops."""
+    who = "flash_mla_prefill_fp8"
+    if not (q.is_cuda and kv_cache.is_cuda and cache_lengths.is_cuda) or (q_lengths is not None and not q_lengths.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, kv_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} is forward only (no autograd): detach the inputs")
+    if kv_cache.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"{who}: the latent cache must be torch.float8_e4m3fn (got {kv_cache.dtype}); a 16-bit latent cache is flash_mla_prefill's, "
+                        "and e5m2 and fnuz caches have no kernel")
+    key_pieces = 0 if key_pieces is None else key_pieces
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, key_pieces, True)
+    if q_lengths is not None:
+        _check_lengths(who, "q_lengths", q_lengths, int(q.shape[0]))
+    _latent_scale(who, kv_scale, kv_cache.device)
+    o, l = _call_op(_HAVE_MLA_PREFILL_FP8_OP, "attention_mla_prefill_fp8", q, kv_cache, cache_lengths, q_lengths, block_table, bool(causal),
+                    float(softmax_scale), int(key_pieces), kv_scale)
     return (o, l * _LN2) if return_lse else o
 
 
