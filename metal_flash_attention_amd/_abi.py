@@ -481,6 +481,39 @@ MLA_PREFILL_FP8_SYMBOLS = [   # include/mfa_mla_prefill_fp8.h: both prefill fami
     ("mfa_attention_mla_prefill_fp8_split_workspace_size", ctypes.c_int, [_MLA_PREFILL, _SPLIT, _MLA_QUANT, ctypes.POINTER(ctypes.c_uint64), _U32P]),
 ]
 
+class mfa_mla_index_params(ctypes.Structure):   # include/mfa_mla_index.h
+    _fields_ = [
+        ("rows", ctypes.c_uint32), ("column", ctypes.c_uint32), ("indexHeads", ctypes.c_uint32), ("batches", ctypes.c_uint32),
+        ("causal", ctypes.c_uint32),
+        ("indexDimension", ctypes.c_uint16), ("precision", ctypes.c_uint8), ("reserved", ctypes.c_uint8),
+        ("pageSize", ctypes.c_uint32), ("topk", ctypes.c_uint32),
+        ("cacheLengths", ctypes.c_void_p), ("blockTable", ctypes.c_void_p), ("blockTableStride", ctypes.c_int64),
+        ("leadingDimension", ctypes.c_int64 * 2), ("headStride", ctypes.c_int64 * 2), ("batchStride", ctypes.c_int64 * 2),
+        ("pageStride", ctypes.c_int64),
+        ("weightRowStride", ctypes.c_int64), ("weightBatchStride", ctypes.c_int64),
+        ("logitRowStride", ctypes.c_int64), ("logitBatchStride", ctypes.c_int64),
+        ("indexRowStride", ctypes.c_int64), ("indexBatchStride", ctypes.c_int64),
+        ("workspace", ctypes.c_void_p), ("workspaceBytes", ctypes.c_uint64),
+    ]
+
+
+_MLA_INDEX = ctypes.POINTER(mfa_mla_index_params)
+MFA_MLA_INDEX_DIMENSION, MFA_MLA_INDEX_MAX_HEADS, MFA_MLA_INDEX_KEY_STEP = 128, 64, 32
+_TIMED = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]   # stream, warmup, iterations, milliseconds
+# the buffers of each of the three launches: logits (qi, w, ki, logits), select (logits, indices), topk (qi, w, ki, indices)
+MLA_INDEX_BUFS = {"logits": [ctypes.c_void_p] * 4, "select": [ctypes.c_void_p] * 2, "topk": [ctypes.c_void_p] * 4}
+
+MLA_INDEX_SYMBOLS = [   # include/mfa_mla_index.h: the MLA sparse indexer -- index logits, top-k selection and their chain
+    ("mfa_mla_index_params_init", None, [_MLA_INDEX]),
+    ("mfa_mla_index_params_size", ctypes.c_size_t, []),
+    ("mfa_mla_index_params_offsets", ctypes.c_int, [_U32P, ctypes.c_uint32, _U32P]),
+    ("mfa_mla_index_workspace_size", ctypes.c_int, [_MLA_INDEX, ctypes.POINTER(ctypes.c_uint64)]),
+]
+for _stage, _bufs in MLA_INDEX_BUFS.items():
+    MLA_INDEX_SYMBOLS += [(f"mfa_mla_index_{_stage}_launch", ctypes.c_int, _bufs + [_MLA_INDEX, ctypes.c_void_p]),
+                          (f"mfa_mla_index_{_stage}_launch_form", ctypes.c_int, [_MLA_INDEX, ctypes.c_char_p, ctypes.c_size_t]),
+                          (f"mfa_mla_index_{_stage}_time", ctypes.c_int, _bufs + [_MLA_INDEX] + _TIMED)]
+
 # ---- the laddered entries of the launches over a KV cache, described once:
 #     mfa_attention_<launch>_<family><verb>(*<the verb's head>, params, *<the options the family owns>, *<the verb's tail>)
 # CACHE_FAMILIES: launch -> family -> the options its entries take, in the order of their signatures (each family is an earlier one plus an
@@ -587,7 +620,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS + MLA_SPARSE_SYMBOLS + MLA_SPARSE_FP8_SYMBOLS + MLA_PREFILL_SYMBOLS + MLA_PREFILL_SPLIT_SYMBOLS + MLA_PREFILL_FP8_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS + MLA_SPARSE_SYMBOLS + MLA_SPARSE_FP8_SYMBOLS + MLA_PREFILL_SYMBOLS + MLA_PREFILL_SPLIT_SYMBOLS + MLA_PREFILL_FP8_SYMBOLS + MLA_INDEX_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -1300,6 +1300,86 @@ class AttentionMLAPrefillFP8Split(AttentionMLAPrefillSplit):
         return float(ms.value)
 
 
+class AttentionMLAIndex:
+    """The MLA sparse indexer (include/mfa_mla_index.h), the producer of AttentionMLASparseDecode's `indices`: three launches chosen by
+    `stage` -- "logits": logits[b][r][c] = sum_h w[b][r][h] max(qi[b][h][r] . ki[b][c], 0) at every visible key; "select": the topk
+    largest logits of every row as a list of positions, ascending, then -1; "topk" (the default): both back to back, the logits in
+    `workspace`.  qi [batches][indexHeads][rows][128], w FP32 [batches][rows][indexHeads], ki one row of 128 values per key.
+
+        index = AttentionMLAIndex(GEMMOperandPrecision.BF16)
+        ws = torch.empty(index.workspaceSize(rows=1, column=C, indexHeads=64, batches=B, topk=2048), dtype=torch.uint8, device="cuda")
+        index.dispatch(qi, w, ki, indices, cacheLengths=lengths, rows=1, column=C, indexHeads=64, batches=B, topk=2048, workspace=ws)
+
+    The buffers of a stage, in order: logits (qi, w, ki, logits), select (logits, indices), topk (qi, w, ki, indices).  `strides`: operand
+    name (QI, KI) -> (leadingDimension, headStride, batchStride) in elements, an operand left out is packed; weightStrides, logitStrides,
+    indexStrides: (row, batch), packed when left out.  Paged caches as AttentionMLADecode takes them."""
+
+    OPERANDS = ("QI", "KI")
+    STAGES = ("logits", "select", "topk")
+    INDEX_DIMENSION = _abi.MFA_MLA_INDEX_DIMENSION
+
+    def __init__(self, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16, indexDimension: int = _abi.MFA_MLA_INDEX_DIMENSION):
+        self.precision, self.indexDimension = GEMMOperandPrecision(precision), int(indexDimension)
+
+    def _params(self, *, rows: int, column: int, batches: int = 1, indexHeads: int = 64, topk: int = 0, causal: bool = True, cacheLengths=None,
+                pageSize: int = 0, blockTable=None, blockTableStride: int = 0, strides: Optional[Mapping] = None, pageStride: Optional[int] = None,
+                weightStrides: Optional[Sequence[int]] = None, logitStrides: Optional[Sequence[int]] = None,
+                indexStrides: Optional[Sequence[int]] = None, workspace=None, workspaceBytes: Optional[int] = None):
+        p = _abi.mfa_mla_index_params()
+        lib().mfa_mla_index_params_init(ctypes.byref(p))
+        Di = self.indexDimension
+        p.rows, p.column, p.indexHeads, p.batches, p.topk = int(rows), int(column), int(indexHeads), int(batches), int(topk)
+        p.indexDimension, p.precision, p.causal = Di, int(self.precision), int(bool(causal))
+        p.pageSize, p.cacheLengths = int(pageSize), _pointer(cacheLengths)
+        p.blockTable, p.blockTableStride = _pointer(blockTable), int(blockTableStride)
+        packed = (_packed(rows, indexHeads, Di), (Di, 0, int(column) * Di))
+        for i, name in enumerate(self.OPERANDS):
+            ld, hs, bs = strides.get(name, packed[i]) if strides else packed[i]
+            p.leadingDimension[i], p.headStride[i], p.batchStride[i] = int(ld), int(hs), int(bs)
+        p.pageStride = int(pageStride) if pageStride is not None else int(pageSize) * int(p.leadingDimension[1])
+        for field, given, width in (("weight", weightStrides, indexHeads), ("logit", logitStrides, column), ("index", indexStrides, topk)):
+            row, batch = given if given is not None else (int(width), int(rows) * int(width))
+            setattr(p, field + "RowStride", int(row))
+            setattr(p, field + "BatchStride", int(batch))
+        p.workspace = _pointer(workspace)
+        if workspaceBytes is None:
+            workspaceBytes = int(workspace.numel() * workspace.element_size()) if hasattr(workspace, "numel") else 0
+        p.workspaceBytes = int(workspaceBytes)
+        return p, (cacheLengths, blockTable, workspace)
+
+    def _entry(self, stage, verb):
+        if stage not in self.STAGES:
+            raise ValueError(f"stage must be one of {self.STAGES}, not {stage!r}")
+        return getattr(lib(), f"mfa_mla_index_{stage}_{verb}")
+
+    def workspaceSize(self, **shape) -> int:
+        """Bytes of the logits the "topk" stage keeps in `workspace`: batches x rows x (column rounded up to 4) x 4"""
+        p, _keep = self._params(**shape)
+        nbytes = ctypes.c_uint64(0)
+        check(lib().mfa_mla_index_workspace_size(ctypes.byref(p), ctypes.byref(nbytes)))
+        return int(nbytes.value)
+
+    def launchForm(self, *, stage: str = "topk", **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the kernels' names and their grids"""
+        p, _keep = self._params(**shape)
+        out = ctypes.create_string_buffer(512)
+        check(self._entry(stage, "launch_form")(ctypes.byref(p), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, *buffers, stage: str = "topk", stream: Optional[int] = None, **shape) -> None:
+        """mfa_mla_index_<stage>_launch over the stage's buffers"""
+        p, _keep = self._params(**shape)
+        check(self._entry(stage, "launch")(*_pointers(*buffers), ctypes.byref(p), ctypes.c_void_p(stream or 0)))
+
+    def time(self, *buffers, stage: str = "topk", stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches of the stage (HIP events on `stream`)."""
+        p, _keep = self._params(**shape)
+        ms = ctypes.c_float(0.0)
+        check(self._entry(stage, "time")(*_pointers(*buffers), ctypes.byref(p), ctypes.c_void_p(stream or 0), int(warmup), int(iterations),
+                                         ctypes.byref(ms)))
+        return float(ms.value)
+
+
 class MLACacheAppend:
     """Appends the `rows` new rows of every sequence to the latent cache of MLA decode (include/mfa_mla_cache.h) -- latentNew
     [batches][rows][512] and ropeNew [batches][rows][64] become one cache row of 576 -- quantising them to e4m3 when the cache is FP8

@@ -33,7 +33,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAPrefill, AttentionMLAPrefillFP8Split, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAIndex, AttentionMLAPrefill, AttentionMLAPrefillFP8Split, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
                         KVCachePrecision, MLACacheAppend)
 
@@ -682,6 +682,90 @@ def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_sca
     return o, l
 
 
+def _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, logits, topk):
+    """the operands of mla_index_logits / mla_index_select / mla_index_topk (include/mfa_mla_index.h), checked where the public function
+    and the op both pass: shapes, types, devices.  What a function does not take is None"""
+    Di = AttentionMLAIndex.INDEX_DIMENSION
+    given = [t for t in (q_index, weights, index_cache, cache_lengths, block_table, logits) if t is not None]
+    if not all(t.is_cuda and t.device == given[0].device for t in given):
+        raise RuntimeError(f"{who}: tensors must live on one GPU (there is no CPU path, and the host never reads a length)")
+    if q_index is not None:
+        if q_index.dtype not in (torch.bfloat16, torch.float16) or index_cache.dtype != q_index.dtype:
+            raise TypeError(f"{who}: q_index and the index cache must share one of bfloat16 / float16 (got {q_index.dtype}, {index_cache.dtype}); "
+                            "e4m3 index caches have no kernel")
+        paged = block_table is not None
+        if q_index.dim() != 4 or index_cache.dim() != 3 or q_index.shape[3] != Di or index_cache.shape[2] != Di or \
+                (not paged and index_cache.shape[0] != q_index.shape[0]):
+            raise ValueError(f"{who}: expected q_index [B, Hi, R, {Di}] and index_cache [B, C, {Di}] (paged: [pages, pageSize, {Di}]): one row of "
+                             f"{Di} values per key (got {tuple(q_index.shape)}, {tuple(index_cache.shape)})")
+        B, Hi, R, _Di = (int(n) for n in q_index.shape)
+        if not 1 <= Hi <= 64 or not 1 <= R <= 32:
+            raise ValueError(f"{who}: q_index [B, Hi, R, {Di}] takes 1 .. 64 index heads and 1 .. 32 rows (got Hi = {Hi}, R = {R})")
+        if index_cache.stride(2) != 1 or any(st < 0 for st in index_cache.stride()):
+            raise ValueError(f"{who}: index_cache must have a contiguous last dimension (a cache is never copied)")
+        if weights.dtype != torch.float32 or tuple(weights.shape) != (B, R, Hi):
+            raise ValueError(f"{who}: weights must be float32 [B, R, Hi] = [{B}, {R}, {Hi}], the model's per-row, per-head weights with every "
+                             f"scale folded in (got {tuple(weights.shape)}, {weights.dtype})")
+        if paged and (block_table.dim() != 2 or block_table.shape[0] != B or block_table.dtype != torch.int32 or block_table.stride(1) != 1):
+            raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous last dimension "
+                             f"(got {tuple(block_table.shape)}, {block_table.dtype})")
+    else:
+        if logits.dtype != torch.float32 or logits.dim() != 3 or logits.shape[2] < 1 or not 1 <= logits.shape[1] <= 32:
+            raise ValueError(f"{who}: logits must be float32 [B, R, C] with R <= 32, as mla_index_logits returns them (got {tuple(logits.shape)}, "
+                             f"{logits.dtype})")
+        B = int(logits.shape[0])
+    _check_lengths(who, "cache_lengths", cache_lengths, B)
+    if topk is not None and (isinstance(topk, bool) or not isinstance(topk, int) or topk < 1):
+        raise ValueError(f"{who}: topk must be an int >= 1, the slots of a row's list, not {topk!r}")
+
+
+def _rows_view(t):
+    """a [B, R, n] operand read through its (row, batch) strides where it lies; only a last dimension that is not contiguous is copied"""
+    t = t if t.stride(2) == 1 and all(st >= 0 for st in t.stride()) else t.contiguous()
+    return t, (int(t.stride(1)) if t.shape[1] > 1 else int(t.shape[2]), int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]) * int(t.shape[2]))
+
+
+def _run_mla_index(stage, q_index, weights, index_cache, cache_lengths, block_table, causal, logits=None, topk=None):
+    """the launches of include/mfa_mla_index.h on the operands' device and torch's current stream.  "logits" -> FP32 [B, R, column], -inf
+    where the kernel writes nothing; "select" and "topk" -> int32 [B, R, topk]; the logits of "topk" live in a workspace allocated here"""
+    who = "mla_index_" + stage
+    _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, logits, topk)
+    kw = dict(causal=bool(causal), cacheLengths=cache_lengths.to(torch.int32))
+    if stage == "select":
+        logits, kw["logitStrides"] = _rows_view(logits)
+        (B, R, column), device, dtype = logits.shape, logits.device, torch.bfloat16
+    else:
+        paged = block_table is not None
+        q_index, q_strides = _new_operand(q_index)
+        weights, kw["weightStrides"] = _rows_view(weights)
+        B, Hi, R, _Di = q_index.shape
+        device, dtype = q_index.device, q_index.dtype
+        ld = int(index_cache.stride(1)) if index_cache.shape[1] > 1 else int(index_cache.shape[2])
+        column = int(index_cache.shape[1]) * (int(block_table.shape[1]) if paged else 1)
+        kw.update(indexHeads=Hi, strides={"QI": q_strides, "KI": (ld, 0, 0 if paged else int(index_cache.stride(0)))})
+        if paged:
+            kw.update(pageSize=int(index_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)),
+                      pageStride=int(index_cache.stride(0)))
+    kw.update(rows=int(R), batches=int(B), column=int(column))
+    key = (AttentionMLAIndex, dtype)
+    host = _HOSTS.get(key)
+    if host is None:
+        host = _HOSTS[key] = AttentionMLAIndex(P.BF16 if dtype == torch.bfloat16 else P.FP16)
+    if stage == "logits":
+        out = torch.full((B, R, column), float("-inf"), dtype=torch.float32, device=device)
+        buffers = (q_index, weights, index_cache, out)
+    else:
+        out = torch.empty((B, R, topk), dtype=torch.int32, device=device)
+        kw.update(topk=int(topk))
+        buffers = (logits, out)
+        if stage == "topk":
+            kw.update(workspace=torch.empty(host.workspaceSize(**kw), dtype=torch.uint8, device=device))
+            buffers = (q_index, weights, index_cache, out)
+    with torch.cuda.device(device):
+        host.dispatch(*buffers, stage=stage, stream=torch.cuda.current_stream(device).cuda_stream, **kw)
+    return out
+
+
 def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces=None, fp8=False, kv_scale=None):
     """flash_mla_prefill's launch (include/mfa_mla_prefill.h) on q's device and torch's current stream -> (O [B, H, R, 512], L [B, H, R]
     base 2).  (Rows past q_lengths[b] are not written: no memset is spent on them, they come back uninitialised.)  key_pieces not None:
@@ -1023,6 +1107,34 @@ def _op_mla_prefill_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: 
     return _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces, True, kv_scale)
 
 
+def _op_mla_index_logits(q_index: torch.Tensor, weights: torch.Tensor, index_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                         block_table: Optional[torch.Tensor], causal: bool) -> torch.Tensor:
+    return _run_mla_index("logits", q_index, weights, index_cache, cache_lengths, block_table, causal)
+
+
+def _op_mla_index_select(logits: torch.Tensor, cache_lengths: torch.Tensor, topk: int, causal: bool) -> torch.Tensor:
+    return _run_mla_index("select", None, None, None, cache_lengths, None, causal, logits, topk)
+
+
+def _op_mla_index_topk(q_index: torch.Tensor, weights: torch.Tensor, index_cache: torch.Tensor, cache_lengths: torch.Tensor, topk: int,
+                       block_table: Optional[torch.Tensor], causal: bool) -> torch.Tensor:
+    """(mla_index_logits' arguments; `topk` after the lengths)"""
+    return _run_mla_index("topk", q_index, weights, index_cache, cache_lengths, block_table, causal, None, topk)
+
+
+def _fake_mla_index_logits(q_index, weights, index_cache, cache_lengths, block_table, causal):
+    column = index_cache.shape[1] * (block_table.shape[1] if block_table is not None else 1)
+    return q_index.new_empty((q_index.shape[0], q_index.shape[2], column), dtype=torch.float32)
+
+
+def _fake_mla_index_select(logits, cache_lengths, topk, causal):
+    return logits.new_empty((logits.shape[0], logits.shape[1], topk), dtype=torch.int32)
+
+
+def _fake_mla_index_topk(q_index, weights, index_cache, cache_lengths, topk, *args, **kwargs):
+    return q_index.new_empty((q_index.shape[0], q_index.shape[2], topk), dtype=torch.int32)
+
+
 def _op_mla_append(latent_new: torch.Tensor, rope_new: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor,
                    block_table: Optional[torch.Tensor], kv_scale: Optional[torch.Tensor]) -> None:
     _run_mla_append(latent_new, rope_new, kv_cache, cache_lengths, block_table, kv_scale)
@@ -1145,6 +1257,14 @@ _MLA_PREFILL_FP8_OPS = [
 ]
 _HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_PREFILL_FP8_OPS})
 _HAVE_MLA_PREFILL_FP8_OP = _HAVE["attention_mla_prefill_fp8"]
+# the ops of include/mfa_mla_index.h, in a list of their own
+_MLA_INDEX_OPS = [
+    ("mla_index_logits", _op_mla_index_logits, _fake_mla_index_logits, ()),
+    ("mla_index_select", _op_mla_index_select, _fake_mla_index_select, ()),
+    ("mla_index_topk", _op_mla_index_topk, _fake_mla_index_topk, ()),
+]
+_HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_INDEX_OPS})
+_HAVE_MLA_INDEX_OPS = all(_HAVE[_op[0]] for _op in _MLA_INDEX_OPS)
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1564,3 +1684,38 @@ def flash_mla_sparse_decode_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_l
     o, l = _call_op(_HAVE_MLA_SPARSE_FP8_OP, "attention_mla_sparse_decode_fp8", q, kv_cache, cache_lengths, indices, block_table, bool(causal),
                     float(softmax_scale), int(pieces), kv_scale)
     return (o, l * _LN2) if return_lse else o
+
+
+def mla_index_logits(q_index: torch.Tensor, weights: torch.Tensor, index_cache: torch.Tensor, cache_lengths: torch.Tensor, *,
+                     block_table: Optional[torch.Tensor] = None, causal: bool = True) -> torch.Tensor:
+    """The index logits of DeepSeek-V3.2's sparse-attention indexer (include/mfa_mla_index.h): q_index [B, Hi, R, 128] bf16 or fp16
+    (Hi <= 64 index heads, R <= 32), weights float32 [B, R, Hi] -- the model's own, every scale folded in, either sign -- and index_cache
+    [B, C, 128] in q_index's type (or, with block_table, a page pool [pages, pageSize, 128]), one row per key, laid out and paged as
+    flash_mla_decode's cache.  Returns float32 [B, R, column]: sum_h weights[b, r, h] x relu(q_index[b, h, r] . index_cache[b, c]) at every
+    position row r sees -- flash_mla_decode's rule from cache_lengths and `causal` -- and -inf elsewhere (the allocation's fill: the kernel
+    writes visible positions only, and never loads a key at or past a length).  Operands are read where they lie, through strides.
+    Forward only, GPU only; the torch.library op is `mfa::mla_index_logits`."""
+    who = "mla_index_logits"
+    _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, None, None)
+    return _call_op(_HAVE_MLA_INDEX_OPS, who, q_index, weights, index_cache, cache_lengths, block_table, bool(causal))
+
+
+def mla_index_select(logits: torch.Tensor, cache_lengths: torch.Tensor, topk: int, *, causal: bool = True) -> torch.Tensor:
+    """The top-k selection of the indexer (include/mfa_mla_index.h): logits float32 [B, R, C] as mla_index_logits returns them -> int32
+    [B, R, topk], the lists flash_mla_sparse_decode takes.  Row r's list holds the min(topk, v) visible positions with the largest logits
+    (v from cache_lengths and `causal`, flash_mla_decode's rule; ties go to the lower position; logits compare by their FP32 bit patterns,
+    so -0 < +0) in ASCENDING POSITION order, then -1.  Only logits[b, r, :v] is read.  Deterministic: a pure function of its inputs.
+    The torch.library op is `mfa::mla_index_select`."""
+    who = "mla_index_select"
+    _check_mla_index(who, None, None, None, cache_lengths, None, logits, topk)
+    return _call_op(_HAVE_MLA_INDEX_OPS, who, logits, cache_lengths, int(topk), bool(causal))
+
+
+def mla_index_topk(q_index: torch.Tensor, weights: torch.Tensor, index_cache: torch.Tensor, cache_lengths: torch.Tensor, topk: int, *,
+                   block_table: Optional[torch.Tensor] = None, causal: bool = True) -> torch.Tensor:
+    """mla_index_select(mla_index_logits(...), cache_lengths, topk) as two kernels back to back, bit for bit the same lists, the logits
+    in a workspace that is never filled with -inf or returned: int32 [B, R, topk], ready for flash_mla_sparse_decode(q, kv_cache,
+    cache_lengths, indices).  The torch.library op is `mfa::mla_index_topk`."""
+    who = "mla_index_topk"
+    _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, None, topk)
+    return _call_op(_HAVE_MLA_INDEX_OPS, who, q_index, weights, index_cache, cache_lengths, int(topk), block_table, bool(causal))
