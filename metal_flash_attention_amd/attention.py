@@ -1300,6 +1300,57 @@ class AttentionMLAPrefillFP8Split(AttentionMLAPrefillSplit):
         return float(ms.value)
 
 
+def _mla_sparse_block(shape):
+    """mfa_mla_sparse for the prefill entries, `indices`, `topk` and `indexStrides` taken out of `shape` -> (the block, what it points to)"""
+    sparse = _abi.mfa_mla_sparse()
+    lib().mfa_mla_sparse_init(ctypes.byref(sparse))
+    keep = shape.pop("indices", None)
+    topk = int(shape.pop("topk", 0))
+    strides = shape.pop("indexStrides", None)
+    sparse.indices, sparse.topk = _pointer(keep), topk
+    sparse.indexRowStride, sparse.indexBatchStride = (int(strides[0]), int(strides[1])) if strides is not None else (topk, int(shape.get("rows", 0)) * topk)
+    return sparse, keep
+
+
+class AttentionMLAPrefillSparse(AttentionMLAPrefill):
+    """Sparse MLA prefill (include/mfa_mla_prefill_sparse.h): AttentionMLAPrefill's methods and arguments plus `indices`, device int32
+    [batches][rows][topk] -- the key POSITIONS row r of sequence b attends to, shared by all heads -- and `topk`, as
+    AttentionMLASparseDecode takes them (indexStrides: (row, batch) in entries, default (topk, rows x topk)).  -1, a position at or past
+    the length and a position past the row's causal frontier (prefill's, from queryLengths) are holes: never loaded, never scored.  Any
+    number of rows in one launch; a workgroup serves 32 heads of one row.
+
+        mla = AttentionMLAPrefillSparse(GEMMOperandPrecision.BF16)
+        mla.launch(q, kv, o, l, cacheLengths=lengths, queryLengths=new, rows=512, column=C, heads=128, batches=B, scale=s, indices=idx, topk=2048)
+    """
+
+    def launchForm(self, **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name, the grid's factors and topk"""
+        sparse, _kept = _mla_sparse_block(shape)
+        p, _keep = self._params(**shape)
+        out = ctypes.create_string_buffer(512)
+        check(lib().mfa_attention_mla_prefill_sparse_launch_form(ctypes.byref(p), ctypes.byref(sparse), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, kv, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        """mfa_attention_mla_prefill_sparse_launch"""
+        sparse, _kept = _mla_sparse_block(shape)
+        p, _keep = self._params(**shape)
+        check(lib().mfa_attention_mla_prefill_sparse_launch(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.byref(sparse), ctypes.c_void_p(stream or 0)))
+
+    def launch(self, q, kv, o, l=None, **shape) -> None:
+        """mfa_attention_mla_prefill_sparse_launch (`dispatch` under the name the header uses)"""
+        self.dispatch(q, kv, o, l, **shape)
+
+    def time(self, q, kv, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
+        sparse, _kept = _mla_sparse_block(shape)
+        p, _keep = self._params(**shape)
+        ms = ctypes.c_float(0.0)
+        check(lib().mfa_attention_mla_prefill_sparse_time(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.byref(sparse), ctypes.c_void_p(stream or 0),
+                                                          int(warmup), int(iterations), ctypes.byref(ms)))
+        return float(ms.value)
+
+
 class AttentionMLAIndex:
     """The MLA sparse indexer (include/mfa_mla_index.h), the producer of AttentionMLASparseDecode's `indices`: three launches chosen by
     `stage` -- "logits": logits[b][r][c] = sum_h w[b][r][h] max(qi[b][h][r] . ki[b][c], 0) at every visible key; "select": the topk

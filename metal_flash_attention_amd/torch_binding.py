@@ -33,7 +33,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAIndex, AttentionMLAPrefill, AttentionMLAPrefillFP8Split, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAIndex, AttentionMLAPrefill, AttentionMLAPrefillFP8Split, AttentionMLAPrefillSparse, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
                         KVCachePrecision, MLACacheAppend)
 
@@ -766,18 +766,21 @@ def _run_mla_index(stage, q_index, weights, index_cache, cache_lengths, block_ta
     return out
 
 
-def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces=None, fp8=False, kv_scale=None):
+def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces=None, fp8=False, kv_scale=None, indices=None):
     """flash_mla_prefill's launch (include/mfa_mla_prefill.h) on q's device and torch's current stream -> (O [B, H, R, 512], L [B, H, R]
     base 2).  (Rows past q_lengths[b] are not written: no memset is spent on them, they come back uninitialised.)  key_pieces not None:
     flash_mla_prefill_split's launch, cut along the keys (include/mfa_mla_prefill_split.h); its workspace is allocated here.  `fp8`:
     flash_mla_prefill_fp8's, over an e4m3 latent cache with `kv_scale` (include/mfa_mla_prefill_fp8.h; always its cut entries, which at
-    one piece run the unsplit kernel) -- the strides of such a cache count bytes, which are its elements"""
+    one piece run the unsplit kernel) -- the strides of such a cache count bytes, which are its elements.  `indices`:
+    flash_mla_sparse_prefill's lists (include/mfa_mla_prefill_sparse.h), passed where they lie; a 16-bit cache, no pieces"""
     split = key_pieces is not None
-    who = "flash_mla_prefill_fp8" if fp8 else "flash_mla_prefill_split" if split else "flash_mla_prefill"
+    who = "flash_mla_sparse_prefill" if indices is not None else "flash_mla_prefill_fp8" if fp8 else "flash_mla_prefill_split" if split else "flash_mla_prefill"
     if fp8 and kv_cache.dtype != torch.float8_e4m3fn:
         raise TypeError(f"{who}: the latent cache must be torch.float8_e4m3fn (got {kv_cache.dtype}); a 16-bit latent cache is flash_mla_prefill's, "
                         "and e5m2 and fnuz caches have no kernel")
     _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, key_pieces if split else 0, fp8)
+    if indices is not None:
+        _check_mla_indices(who, q, indices)
     B = int(q.shape[0])
     if q_lengths is not None:
         _check_lengths(who, "q_lengths", q_lengths, B)
@@ -792,9 +795,12 @@ def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal,
               column=int(kv_cache.shape[1]) * (int(block_table.shape[1]) if paged else 1))
     if paged:
         kw.update(pageSize=int(kv_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)), pageStride=int(kv_cache.stride(0)))
-    cls = AttentionMLAPrefillFP8Split if fp8 else AttentionMLAPrefillSplit if split else AttentionMLAPrefill
+    cls = AttentionMLAPrefillSparse if indices is not None else AttentionMLAPrefillFP8Split if fp8 else AttentionMLAPrefillSplit if split else AttentionMLAPrefill
     if fp8:
         kw.update(kvScale=_latent_scale(who, kv_scale, kv_cache.device))
+    if indices is not None:
+        topk = int(indices.shape[2])
+        kw.update(indices=indices, topk=topk, indexStrides=(int(indices.stride(1)) if R > 1 else topk, int(indices.stride(0)) if B > 1 else R * topk))
     key = (cls, q.dtype)
     host = _HOSTS.get(key)
     if host is None:
@@ -1107,6 +1113,13 @@ def _op_mla_prefill_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: 
     return _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, key_pieces, True, kv_scale)
 
 
+def _op_mla_sparse_prefill(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, indices: torch.Tensor,
+                           q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool,
+                           softmax_scale: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(attention_mla_prefill's arguments; `indices` after the cache's lengths, as attention_mla_sparse_decode's)"""
+    return _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, indices=indices)
+
+
 def _op_mla_index_logits(q_index: torch.Tensor, weights: torch.Tensor, index_cache: torch.Tensor, cache_lengths: torch.Tensor,
                          block_table: Optional[torch.Tensor], causal: bool) -> torch.Tensor:
     return _run_mla_index("logits", q_index, weights, index_cache, cache_lengths, block_table, causal)
@@ -1265,6 +1278,12 @@ _MLA_INDEX_OPS = [
 ]
 _HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_INDEX_OPS})
 _HAVE_MLA_INDEX_OPS = all(_HAVE[_op[0]] for _op in _MLA_INDEX_OPS)
+# the op of include/mfa_mla_prefill_sparse.h, in a list of its own
+_MLA_SPARSE_PREFILL_OPS = [
+    ("attention_mla_sparse_prefill", _op_mla_sparse_prefill, _fake_mla, ()),
+]
+_HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_SPARSE_PREFILL_OPS})
+_HAVE_MLA_SPARSE_PREFILL_OP = _HAVE["attention_mla_sparse_prefill"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1683,6 +1702,36 @@ def flash_mla_sparse_decode_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_l
     _latent_scale(who, kv_scale, kv_cache.device)
     o, l = _call_op(_HAVE_MLA_SPARSE_FP8_OP, "attention_mla_sparse_decode_fp8", q, kv_cache, cache_lengths, indices, block_table, bool(causal),
                     float(softmax_scale), int(pieces), kv_scale)
+    return (o, l * _LN2) if return_lse else o
+
+
+def flash_mla_sparse_prefill(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, indices: torch.Tensor, *, softmax_scale: float,
+                             q_lengths: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None, causal: bool = True,
+                             return_lse: bool = False):
+    """flash_mla_prefill over per-row lists of selected keys (a prompt chunk of DeepSeek-V3.2's sparse attention;
+    include/mfa_mla_prefill_sparse.h): q [B, H, R, 576] with ANY R and indices [B, R, topk] int32 on the GPU, the key POSITIONS row r of
+    sequence b attends to, shared by all H heads, as flash_mla_sparse_decode takes them -- in ONE launch, where a loop of
+    flash_mla_sparse_decode calls takes 32 rows at a time with per-chunk lengths kept by the caller.
+    A position is logical (paged: translated through block_table).  -1, entries below -1, a position at or past cache_lengths[b] and,
+    with `causal`, a position past r + max(len - q_lengths[b], 0) are holes: their cache rows are never loaded, nor is any key that no
+    list names.  A position that appears twice counts twice; the order of a list is free.  Rows at or past q_lengths[b] are neither
+    read (q, their lists) nor written: they come back uninitialised.  A row without a visible entry gets O = 0.  For every row the
+    arithmetic is flash_mla_sparse_decode's at one piece, bit for bit.  kv_cache (bf16 or fp16, q's type), cache_lengths, softmax_scale
+    (required), return_lse and O [B, H, R, 512] are flash_mla_prefill's.  Nothing is read on the host: one capture in a graph serves
+    changed lists and lengths.  Forward only, GPU only.  Goes through the torch.library op `mfa::attention_mla_sparse_prefill` where
+    torch has custom ops, so it traces under torch.compile."""
+    who = "flash_mla_sparse_prefill"
+    if not (q.is_cuda and kv_cache.is_cuda and cache_lengths.is_cuda and indices.is_cuda) or (q_lengths is not None and not q_lengths.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, kv_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} is forward only (no autograd): detach the inputs")
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, 0)
+    _check_mla_indices(who, q, indices)
+    if q_lengths is not None:
+        _check_lengths(who, "q_lengths", q_lengths, int(q.shape[0]))
+    o, l = _call_op(_HAVE_MLA_SPARSE_PREFILL_OP, "attention_mla_sparse_prefill", q, kv_cache, cache_lengths, indices, q_lengths, block_table,
+                    bool(causal), float(softmax_scale))
     return (o, l * _LN2) if return_lse else o
 
 
