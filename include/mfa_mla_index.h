@@ -58,8 +58,8 @@
  * Kernels: attn_mlai_d128_<bf16|f16> (logits), attn_mlai_select.
  *
  * Deliberately not here: e4m3 index caches and per-key scales; an FP8 matrix-instruction path; writing the index cache (the caller
- * stores its index keys with plain torch); rows > 32 (prefill); cutting one row's selection across several workgroups; physical-slot
- * indices.
+ * stores its index keys with plain torch); rows > 32 under THESE entries (a prompt chunk is mfa_mla_index_prefill.h); cutting one
+ * row's selection across several workgroups; physical-slot indices.
  */
 #ifndef MFA_MLA_INDEX_H
 #define MFA_MLA_INDEX_H

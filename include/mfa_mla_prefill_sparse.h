@@ -38,8 +38,7 @@
  * Kernels: attn_mla16px1_d576_<bf16|f16> (64 KiB of LDS, two workgroups a compute unit).
  *
  * Deliberately not here: e4m3 latent caches under prefill lists; pieces of slots with a combine pass (few rows under a long list leave
- * compute units idle); lifting the indexer's rows <= 32 (mfa_mla_index.h: a chunk's lists are made 32 rows at a time); ragged
- * (packed-axis) rows.
+ * compute units idle); ragged (packed-axis) rows.  (A chunk's lists, any number of rows in one call, are mfa_mla_index_prefill.h's.)
  */
 #ifndef MFA_MLA_PREFILL_SPARSE_H
 #define MFA_MLA_PREFILL_SPARSE_H

@@ -14,6 +14,7 @@ from .attention import (  # noqa: F401
     AttentionMLADecode,
     AttentionMLADecodeFP8,
     AttentionMLAIndex,
+    AttentionMLAIndexPrefill,
     AttentionMLAPrefill,
     AttentionMLAPrefillFP8,
     AttentionMLAPrefillFP8Split,
@@ -44,7 +45,7 @@ def __getattr__(name):
     # the torch functions of the KV-cache loop, on first use: torch stays optional for everything above
     if name in ("kv_cache_compact", "tree_path", "flash_mla_decode", "flash_mla_decode_fp8", "mla_cache_append", "flash_mla_sparse_decode",
                 "flash_mla_sparse_decode_fp8", "flash_mla_prefill", "flash_mla_prefill_split", "flash_mla_prefill_fp8", "mla_index_logits", "mla_index_select",
-                "mla_index_topk", "flash_mla_sparse_prefill"):
+                "mla_index_topk", "flash_mla_sparse_prefill", "mla_index_prefill_logits", "mla_index_prefill_select", "mla_index_prefill_topk"):
         from . import torch_binding
         return getattr(torch_binding, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -521,6 +521,16 @@ for _stage, _bufs in MLA_INDEX_BUFS.items():
                           (f"mfa_mla_index_{_stage}_launch_form", ctypes.c_int, [_MLA_INDEX, ctypes.c_char_p, ctypes.c_size_t]),
                           (f"mfa_mla_index_{_stage}_time", ctypes.c_int, _bufs + [_MLA_INDEX] + _TIMED)]
 
+# include/mfa_mla_index_prefill.h: the same three launches for a chunk of any number of rows (`queryLengths`, device uint32, after `params`)
+MLA_INDEX_PREFILL_SYMBOLS = [
+    ("mfa_mla_index_prefill_workspace_size", ctypes.c_int, [_MLA_INDEX, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+]
+for _stage, _bufs in MLA_INDEX_BUFS.items():
+    MLA_INDEX_PREFILL_SYMBOLS += [(f"mfa_mla_index_prefill_{_stage}_launch", ctypes.c_int, _bufs + [_MLA_INDEX, ctypes.c_void_p, ctypes.c_void_p]),
+                                  (f"mfa_mla_index_prefill_{_stage}_launch_form", ctypes.c_int, [_MLA_INDEX, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]),
+                                  (f"mfa_mla_index_prefill_{_stage}_time", ctypes.c_int, _bufs + [_MLA_INDEX, ctypes.c_void_p] + _TIMED)]
+MFA_MLA_INDEX_PREFILL_TILE, MFA_MLA_INDEX_PREFILL_MIN_SPAN, MFA_MLA_INDEX_PREFILL_MAX_SPAN, MFA_MLA_INDEX_PREFILL_WORKSPACE_CAP = 256, 32, 256, 256 << 20
+
 # ---- the laddered entries of the launches over a KV cache, described once:
 #     mfa_attention_<launch>_<family><verb>(*<the verb's head>, params, *<the options the family owns>, *<the verb's tail>)
 # CACHE_FAMILIES: launch -> family -> the options its entries take, in the order of their signatures (each family is an earlier one plus an
@@ -627,7 +637,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS + MLA_SPARSE_SYMBOLS + MLA_SPARSE_FP8_SYMBOLS + MLA_PREFILL_SYMBOLS + MLA_PREFILL_SPLIT_SYMBOLS + MLA_PREFILL_FP8_SYMBOLS + MLA_INDEX_SYMBOLS + MLA_PREFILL_SPARSE_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS + MLA_SPARSE_SYMBOLS + MLA_SPARSE_FP8_SYMBOLS + MLA_PREFILL_SYMBOLS + MLA_PREFILL_SPLIT_SYMBOLS + MLA_PREFILL_FP8_SYMBOLS + MLA_INDEX_SYMBOLS + MLA_PREFILL_SPARSE_SYMBOLS + MLA_INDEX_PREFILL_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -1398,37 +1398,71 @@ class AttentionMLAIndex:
         p.workspaceBytes = int(workspaceBytes)
         return p, (cacheLengths, blockTable, workspace)
 
+    PREFIX = "mfa_mla_index_"
+
     def _entry(self, stage, verb):
         if stage not in self.STAGES:
             raise ValueError(f"stage must be one of {self.STAGES}, not {stage!r}")
-        return getattr(lib(), f"mfa_mla_index_{stage}_{verb}")
+        return getattr(lib(), f"{self.PREFIX}{stage}_{verb}")
+
+    @staticmethod
+    def _block(p, keep):
+        """what an entry takes between its buffers and its tail: the params"""
+        return (ctypes.byref(p),)
 
     def workspaceSize(self, **shape) -> int:
         """Bytes of the logits the "topk" stage keeps in `workspace`: batches x rows x (column rounded up to 4) x 4"""
-        p, _keep = self._params(**shape)
+        p, keep = self._params(**shape)
         nbytes = ctypes.c_uint64(0)
-        check(lib().mfa_mla_index_workspace_size(ctypes.byref(p), ctypes.byref(nbytes)))
+        check(getattr(lib(), self.PREFIX + "workspace_size")(*self._block(p, keep), ctypes.byref(nbytes)))
         return int(nbytes.value)
 
     def launchForm(self, *, stage: str = "topk", **shape) -> str:
         """What `dispatch` with the same arguments would run (nothing is launched): the kernels' names and their grids"""
-        p, _keep = self._params(**shape)
+        p, keep = self._params(**shape)
         out = ctypes.create_string_buffer(512)
-        check(self._entry(stage, "launch_form")(ctypes.byref(p), out, len(out)))
+        check(self._entry(stage, "launch_form")(*self._block(p, keep), out, len(out)))
         return out.value.decode()
 
     def dispatch(self, *buffers, stage: str = "topk", stream: Optional[int] = None, **shape) -> None:
         """mfa_mla_index_<stage>_launch over the stage's buffers"""
-        p, _keep = self._params(**shape)
-        check(self._entry(stage, "launch")(*_pointers(*buffers), ctypes.byref(p), ctypes.c_void_p(stream or 0)))
+        p, keep = self._params(**shape)
+        check(self._entry(stage, "launch")(*_pointers(*buffers), *self._block(p, keep), ctypes.c_void_p(stream or 0)))
 
     def time(self, *buffers, stage: str = "topk", stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
         """Milliseconds for `iterations` back-to-back launches of the stage (HIP events on `stream`)."""
-        p, _keep = self._params(**shape)
+        p, keep = self._params(**shape)
         ms = ctypes.c_float(0.0)
-        check(self._entry(stage, "time")(*_pointers(*buffers), ctypes.byref(p), ctypes.c_void_p(stream or 0), int(warmup), int(iterations),
+        check(self._entry(stage, "time")(*_pointers(*buffers), *self._block(p, keep), ctypes.c_void_p(stream or 0), int(warmup), int(iterations),
                                          ctypes.byref(ms)))
         return float(ms.value)
+
+
+class AttentionMLAIndexPrefill(AttentionMLAIndex):
+    """The prefill indexer (include/mfa_mla_index_prefill.h), the producer of AttentionMLAPrefillSparse's `indices`: AttentionMLAIndex's
+    stages, buffers and arguments for a prompt chunk of ANY number of rows, plus `queryLengths` (device uint32 [batches], None = rows): row
+    r < qn = min(queryLengths[b], rows) sees the keys below prefill's frontier, min(n, r + max(n - qn, 0) + 1); rows at or past qn get no
+    logits and a list of -1.  The "topk" stage runs passes of as many rows as `workspace` holds; workspaceSize recommends the whole chunk
+    or 256 MiB.  `launch` is `dispatch` under the name the header uses.
+
+        index = AttentionMLAIndexPrefill(GEMMOperandPrecision.BF16)
+        ws = torch.empty(index.workspaceSize(rows=4096, column=C, indexHeads=64, batches=B, topk=2048), dtype=torch.uint8, device="cuda")
+        index.launch(qi, w, ki, indices, cacheLengths=lengths, queryLengths=new, rows=4096, column=C, indexHeads=64, batches=B, topk=2048, workspace=ws)
+    """
+
+    PREFIX = "mfa_mla_index_prefill_"
+
+    def _params(self, *, queryLengths=None, **shape):
+        p, keep = super()._params(**shape)
+        return p, keep + (queryLengths,)
+
+    @staticmethod
+    def _block(p, keep):
+        """the params, then queryLengths"""
+        return (ctypes.byref(p), _pointer(keep[-1]))
+
+    def launch(self, *buffers, **shape) -> None:
+        self.dispatch(*buffers, **shape)
 
 
 class MLACacheAppend:

@@ -156,15 +156,25 @@ __device__ __forceinline__ uint32_t mlai_order_key(float x) {
   return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
-__device__ __forceinline__ void mla_index_select_body(const MlaIndexArgs &a) {
+// The select kernel's visibility rule: which row of the launch a workgroup's local row is (first_row + local; the logits of a launch
+// start at its first row, the lists at row 0) and the prefix that row sees.  This one is the decode indexer's; the prefill indexer's
+// (attn_mla_index_prefill.h) counts rows from a pass's first row and gives a row at or past queryLengths the prefix 0: all holes, no
+// logit read.
+struct MlaiDecodeRule {
+  static __device__ __forceinline__ uint32_t first_row(const MlaIndexArgs &) { return 0u; }
+  static __device__ __forceinline__ uint32_t visible(const MlaIndexArgs &a, uint32_t batch, uint32_t row) { return mlai_visible(a, batch, row); }
+};
+
+template <typename Rule, typename Args>
+__device__ __forceinline__ void mla_index_select_body(const Args &a) {
   __shared__ uint32_t hist[256];
   __shared__ uint32_t pick[2];                          // the pass's digit; what is still wanted inside it
   __shared__ uint32_t totals[2][MLAI_SELECT_UNROLL * MLAI_SELECT_WAVES];   // per (u, wave): greater | ties << 16, double buffered
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t row = blockIdx.x % a.R, batch = blockIdx.x / a.R;
-  const uint32_t v = mlai_visible(a, batch, row), topk = a.topk;
-  const float *x = a.logits + (int64_t)batch * a.lbs + (int64_t)row * a.lrs;
+  const uint32_t local = blockIdx.x % a.R, batch = blockIdx.x / a.R, row = Rule::first_row(a) + local;
+  const uint32_t v = Rule::visible(a, batch, row), topk = a.topk;
+  const float *x = a.logits + (int64_t)batch * a.lbs + (int64_t)local * a.lrs;
   int32_t *out = a.indices + (int64_t)batch * a.ibs + (int64_t)row * a.irs;
 
   if (v <= topk) {   // every visible position, then holes: no logit is read

@@ -1,7 +1,7 @@
 // attn_mla_index.hip -- the MLA sparse indexer: the kernels' code objects (attn_mla_index.h) and the C ABI of include/mfa_mla_index.h --
 // the index logits, the top-k selection and their chain.  A translation unit of its own.  The checks of the cache's paging and of the
-// operands' strides are cache_launch.h's, in its words; what this unit adds is the checks of its own fields, the tile plan of the
-// logits launch and the argument block.
+// operands' strides are cache_launch.h's, in its words; the checks of the block's own fields are mla_index_checks.h's, shared with the
+// prefill indexer; what this unit adds is its rows limit, the tile plan of the logits launch and its workspace.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN where nothing is visible.)
 #include <hip/hip_runtime.h>
 
@@ -10,18 +10,15 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/mfa_mla_index.h"
-#include "attn_mla_index.h"
-#include "cache_launch.h"
 #include "launchers.h"
-#include "mfa_internal.h"
+#include "mla_index_checks.h"
 
 using namespace mfa;
 
 // Kernel names are plain C symbols, stable for a profiler's kernel trace.
 extern "C" __global__ __launch_bounds__(256) void attn_mlai_d128_bf16(const mfa::MlaIndexArgs a) { mfa::mla_index_logits_body<__bf16>(a); }
 extern "C" __global__ __launch_bounds__(256) void attn_mlai_d128_f16(const mfa::MlaIndexArgs a) { mfa::mla_index_logits_body<_Float16>(a); }
-extern "C" __global__ __launch_bounds__(1024) void attn_mlai_select(const mfa::MlaIndexArgs a) { mfa::mla_index_select_body(a); }
+extern "C" __global__ __launch_bounds__(1024) void attn_mlai_select(const mfa::MlaIndexArgs a) { mfa::mla_index_select_body<mfa::MlaiDecodeRule>(a); }
 
 namespace {
 
@@ -33,9 +30,9 @@ constexpr uint32_t kTileKeys = MFA_MLA_INDEX_KEY_STEP * MLAI_WAVES;   // keys of
 constexpr uint64_t kWorkgroupTarget = 1024;                           // a tile grows while the grid keeps this many workgroups
 constexpr uint32_t kMaxSteps = 8;
 
-enum Stage { LOGITS = 1, SELECT = 2, TOPK = 3 };
+enum Stage { LOGITS = MLAI_LOGITS, SELECT = MLAI_SELECT, TOPK = MLAI_TOPK };
 
-inline uint64_t padded_column(uint32_t column) { return ((uint64_t)column + 3) & ~3ull; }
+inline uint64_t padded_column(uint32_t column) { return mlai_padded_column(column); }
 inline uint64_t workspace_bytes(const mfa_mla_index_params *p) { return (uint64_t)p->batches * p->rows * padded_column(p->column) * sizeof(float); }
 
 struct IndexPlan {
@@ -56,51 +53,22 @@ struct IndexPlan {
 
 // every check that needs no GPU, and the kernels' argument block (the buffer pointers are filled in by the entries)
 mfa_status IndexPlan::prepare(const mfa_mla_index_params *p, int which) {
-  if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  mfa_status st = check_index_block(p, MFA_MLA_PACKED_ROWS);
+  if (st != MFA_OK) return st;
   stage = which;
-  if (p->reserved != 0) return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_mla_index_params.reserved must be 0, not " + std::to_string(p->reserved));
-  if (p->rows == 0 || p->column == 0 || p->batches == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "rows, column and batches must be non-zero");
-  if (p->rows > MFA_MLA_PACKED_ROWS)
-    return fail(MFA_ERR_UNSUPPORTED, "the MLA indexer takes at most 32 rows per sequence, not rows = " + std::to_string(p->rows) +
-                                         ": the limit of the sparse decode it feeds (a longer block of query rows is a prefill)");
-  if (!p->cacheLengths) return fail(MFA_ERR_INVALID_ARGUMENT, "cacheLengths is required (device array of `batches` uint32)");
   const uint64_t lists64 = (uint64_t)p->rows * p->batches;
   uint32_t pageShift = 0;
   uint64_t tiles = 1, steps = 1;
   logits = nullptr;
   if (stage & LOGITS) {
-    if (p->indexDimension != MFA_MLA_INDEX_DIMENSION)
-      return fail(MFA_ERR_UNSUPPORTED, "the MLA indexer is compiled for indexDimension = 128, not " + std::to_string(p->indexDimension));
-    if (p->precision != MFA_BF16 && p->precision != MFA_FP16)
-      return fail(MFA_ERR_UNSUPPORTED, "the MLA indexer reads 16-bit index queries and caches (precision MFA_BF16 or MFA_FP16); e4m3 index "
-                                       "caches and FP32 have no kernel");
-    if (p->indexHeads == 0 || p->indexHeads > MFA_MLA_INDEX_MAX_HEADS)
-      return fail(MFA_ERR_INVALID_ARGUMENT, "indexHeads must be 1 .. 64, not " + std::to_string(p->indexHeads));
-    mfa_status st = check_paging(p->pageSize, p->blockTable, p->blockTableStride, p->column, &pageShift);
-    if (st != MFA_OK) return st;
-    static const char *names[2] = {"QI", "KI"};
-    for (int i = 0; i < 2; ++i) {
-      st = check_operand_strides(names[i], p->indexDimension, p->leadingDimension[i], i == 1 ? 0 : p->headStride[i],
-                                 i == 1 && p->pageSize ? p->pageStride : p->batchStride[i], 8, "(16-byte rows for QI and KI)");
-      if (st != MFA_OK) return st;
-    }
-    if (p->rows > 1 && p->weightRowStride < (int64_t)p->indexHeads)
-      return fail(MFA_ERR_INVALID_ARGUMENT, "weightRowStride must be at least indexHeads = " + std::to_string(p->indexHeads) + " elements, not " +
-                                                std::to_string(p->weightRowStride));
+    if ((st = check_index_logits(p, &pageShift)) != MFA_OK) return st;
     // the tile: a wave walks `steps` steps, doubled while the grid keeps kWorkgroupTarget workgroups
     const uint64_t steps128 = ((uint64_t)p->column + kTileKeys - 1) / kTileKeys;
     while (steps < kMaxSteps && (steps128 / (2 * steps)) * lists64 >= kWorkgroupTarget) steps *= 2;
     tiles = (steps128 + steps - 1) / steps;
     if (tiles * lists64 > 0x7FFFFFFFull) return fail(MFA_ERR_INVALID_ARGUMENT, "tiles x rows x batches must fit a grid of 2^31 - 1 workgroups");
   }
-  if (stage & SELECT) {
-    if (p->topk == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "topk must be at least 1 (the slots of a row's list)");
-    if (p->indexRowStride < (int64_t)p->topk)
-      return fail(MFA_ERR_INVALID_ARGUMENT, "indexRowStride must be at least topk = " + std::to_string(p->topk) + " entries, not " +
-                                                std::to_string(p->indexRowStride));
-    if (p->column > 0x7FFFFFFFu) return fail(MFA_ERR_INVALID_ARGUMENT, "column must be below 2^31 keys for the selection (its position arithmetic is 32-bit)");
-    if (lists64 > 0x7FFFFFFFull) return fail(MFA_ERR_INVALID_ARGUMENT, "rows x batches must fit a grid of 2^31 - 1 workgroups");
-  }
+  if ((stage & SELECT) && (st = check_index_select(p)) != MFA_OK) return st;
   int64_t lrs = p->logitRowStride, lbs = p->logitBatchStride;
   if (stage == TOPK) {   // the logits live in the workspace, packed
     const uint64_t need = workspace_bytes(p);
@@ -113,52 +81,18 @@ mfa_status IndexPlan::prepare(const mfa_mla_index_params *p, int which) {
     if ((uintptr_t)p->workspace % 16 != 0) return fail(MFA_ERR_INVALID_ARGUMENT, "workspace must be 16-byte aligned");
     lrs = (int64_t)padded_column(p->column);
     lbs = lrs * p->rows;
-  } else if (lrs < (int64_t)p->column) {
-    return fail(MFA_ERR_INVALID_ARGUMENT, "logitRowStride must be at least column = " + std::to_string(p->column) + " elements, not " +
-                                              std::to_string(lrs));
+  } else if ((st = check_index_logit_stride(p)) != MFA_OK) {
+    return st;
   }
   grid = (uint32_t)(tiles * lists64);
   lists = (uint32_t)lists64;
   MlaIndexArgs &a = args;
   std::memset(&a, 0, sizeof(a));
-  a.lengths = p->cacheLengths;
-  a.table = p->blockTable;
-  a.tableStride = p->blockTableStride;
-  a.ldq = p->leadingDimension[0]; a.hsq = p->headStride[0]; a.bsq = p->batchStride[0];
-  a.ldk = p->leadingDimension[1]; a.bsk = p->batchStride[1]; a.psk = p->pageStride;
-  a.wrs = p->weightRowStride; a.wbs = p->weightBatchStride;
+  fill_index_args(a, p, pageShift);
   a.lrs = lrs; a.lbs = lbs;
-  a.irs = p->indexRowStride; a.ibs = p->indexBatchStride;
-  a.R = p->rows; a.H = p->indexHeads; a.batches = p->batches; a.column = p->column; a.topk = p->topk;
   a.steps = (uint32_t)steps; a.tiles = (uint32_t)tiles;
-  a.paged = p->pageSize != 0; a.pageShift = pageShift;
-  a.causal = p->causal != 0;
   if (stage & LOGITS) logits = &kLogits[p->precision == MFA_FP16];
   if (stage == TOPK) a.logits = (float *)p->workspace;
-  return MFA_OK;
-}
-
-// the buffers of a launch into the argument block: what the stage does not take is null and not looked at
-mfa_status bind_index(IndexPlan *plan, const void *qi, const float *w, const void *ki, float *logits, int32_t *indices) {
-  mfa_status st = MFA_OK;
-  MlaIndexArgs &a = plan->args;
-  if (plan->stage & LOGITS) {
-    st = check_buffers({qi, ki}, "QI and KI");
-    if (st == MFA_OK && !w) st = fail(MFA_ERR_INVALID_ARGUMENT, "W is required (device FP32 [batches][rows][indexHeads])");
-    if (st == MFA_OK) st = check_float_arrays({w}, "W");
-    if (st != MFA_OK) return st;
-    a.q = (const char *)qi; a.w = w; a.k = (const char *)ki;
-  }
-  if (plan->stage != TOPK) {
-    if (!logits) return fail(MFA_ERR_INVALID_ARGUMENT, "logits is required (device FP32 [batches][rows][logitRowStride])");
-    if ((st = check_float_arrays({logits}, "logits")) != MFA_OK) return st;
-    a.logits = logits;
-  }
-  if (plan->stage & SELECT) {
-    if (!indices) return fail(MFA_ERR_INVALID_ARGUMENT, "indices is required (device int32 [batches][rows][topk])");
-    if ((uintptr_t)indices % 4 != 0) return fail(MFA_ERR_INVALID_ARGUMENT, "indices must be 4-byte aligned");
-    a.indices = indices;
-  }
   return MFA_OK;
 }
 
@@ -166,7 +100,7 @@ mfa_status index_launch(int stage, const void *qi, const float *w, const void *k
                         const mfa_mla_index_params *params, void *stream) {
   IndexPlan plan;
   mfa_status st = plan.prepare(params, stage);
-  if (st == MFA_OK) st = bind_index(&plan, qi, w, ki, logits, indices);
+  if (st == MFA_OK) st = bind_index(plan.args, stage, qi, w, ki, logits, indices);
   if (st != MFA_OK) return st;
   const hipError_t err = plan.run((hipStream_t)stream);
   if (err != hipSuccess) return hip_fail(err, plan.name());
@@ -178,7 +112,7 @@ mfa_status index_time(int stage, const void *qi, const float *w, const void *ki,
   if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
   IndexPlan plan;
   mfa_status st = plan.prepare(params, stage);
-  if (st == MFA_OK) st = bind_index(&plan, qi, w, ki, logits, indices);
+  if (st == MFA_OK) st = bind_index(plan.args, stage, qi, w, ki, logits, indices);
   if (st != MFA_OK) return st;
   return time_launches((hipStream_t)stream, warmup, iterations, milliseconds, plan.name(), [&](hipStream_t s) { return plan.run(s); });
 }

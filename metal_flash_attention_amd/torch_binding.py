@@ -33,7 +33,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAIndex, AttentionMLAPrefill, AttentionMLAPrefillFP8Split, AttentionMLAPrefillSparse, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAIndex, AttentionMLAIndexPrefill, AttentionMLAPrefill, AttentionMLAPrefillFP8Split, AttentionMLAPrefillSparse, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
                         KVCachePrecision, MLACacheAppend)
 
@@ -682,9 +682,10 @@ def _run_mla_decode(q, kv_cache, cache_lengths, block_table, causal, softmax_sca
     return o, l
 
 
-def _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, logits, topk):
+def _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, logits, topk, prefill=False):
     """the operands of mla_index_logits / mla_index_select / mla_index_topk (include/mfa_mla_index.h), checked where the public function
-    and the op both pass: shapes, types, devices.  What a function does not take is None"""
+    and the op both pass: shapes, types, devices.  What a function does not take is None.  `prefill`: the mla_index_prefill_* functions
+    (include/mfa_mla_index_prefill.h), the same operands with any number of rows"""
     Di = AttentionMLAIndex.INDEX_DIMENSION
     given = [t for t in (q_index, weights, index_cache, cache_lengths, block_table, logits) if t is not None]
     if not all(t.is_cuda and t.device == given[0].device for t in given):
@@ -699,7 +700,9 @@ def _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_ta
             raise ValueError(f"{who}: expected q_index [B, Hi, R, {Di}] and index_cache [B, C, {Di}] (paged: [pages, pageSize, {Di}]): one row of "
                              f"{Di} values per key (got {tuple(q_index.shape)}, {tuple(index_cache.shape)})")
         B, Hi, R, _Di = (int(n) for n in q_index.shape)
-        if not 1 <= Hi <= 64 or not 1 <= R <= 32:
+        if prefill and not (1 <= Hi <= 64 and R >= 1):
+            raise ValueError(f"{who}: q_index [B, Hi, R, {Di}] takes 1 .. 64 index heads and at least one row (got Hi = {Hi}, R = {R})")
+        if not prefill and (not 1 <= Hi <= 64 or not 1 <= R <= 32):
             raise ValueError(f"{who}: q_index [B, Hi, R, {Di}] takes 1 .. 64 index heads and 1 .. 32 rows (got Hi = {Hi}, R = {R})")
         if index_cache.stride(2) != 1 or any(st < 0 for st in index_cache.stride()):
             raise ValueError(f"{who}: index_cache must have a contiguous last dimension (a cache is never copied)")
@@ -710,7 +713,9 @@ def _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_ta
             raise ValueError(f"{who}: block_table must be an int32 GPU tensor [B, pages per sequence] = [{B}, n] with a contiguous last dimension "
                              f"(got {tuple(block_table.shape)}, {block_table.dtype})")
     else:
-        if logits.dtype != torch.float32 or logits.dim() != 3 or logits.shape[2] < 1 or not 1 <= logits.shape[1] <= 32:
+        if prefill and (logits.dtype != torch.float32 or logits.dim() != 3 or logits.shape[2] < 1 or logits.shape[1] < 1):
+            raise ValueError(f"{who}: logits must be float32 [B, R, C], as mla_index_prefill_logits returns them (got {tuple(logits.shape)}, {logits.dtype})")
+        if not prefill and (logits.dtype != torch.float32 or logits.dim() != 3 or logits.shape[2] < 1 or not 1 <= logits.shape[1] <= 32):
             raise ValueError(f"{who}: logits must be float32 [B, R, C] with R <= 32, as mla_index_logits returns them (got {tuple(logits.shape)}, "
                              f"{logits.dtype})")
         B = int(logits.shape[0])
@@ -725,12 +730,16 @@ def _rows_view(t):
     return t, (int(t.stride(1)) if t.shape[1] > 1 else int(t.shape[2]), int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]) * int(t.shape[2]))
 
 
-def _run_mla_index(stage, q_index, weights, index_cache, cache_lengths, block_table, causal, logits=None, topk=None):
+def _run_mla_index(stage, q_index, weights, index_cache, cache_lengths, block_table, causal, logits=None, topk=None, prefill=False, q_lengths=None):
     """the launches of include/mfa_mla_index.h on the operands' device and torch's current stream.  "logits" -> FP32 [B, R, column], -inf
-    where the kernel writes nothing; "select" and "topk" -> int32 [B, R, topk]; the logits of "topk" live in a workspace allocated here"""
-    who = "mla_index_" + stage
-    _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, logits, topk)
+    where the kernel writes nothing; "select" and "topk" -> int32 [B, R, topk]; the logits of "topk" live in a workspace allocated here.
+    `prefill`: the launches of include/mfa_mla_index_prefill.h, any number of rows and `q_lengths`"""
+    who = ("mla_index_prefill_" if prefill else "mla_index_") + stage
+    _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, logits, topk, prefill)
     kw = dict(causal=bool(causal), cacheLengths=cache_lengths.to(torch.int32))
+    if q_lengths is not None:
+        _check_lengths(who, "q_lengths", q_lengths, int(cache_lengths.shape[0]))
+        kw.update(queryLengths=q_lengths.to(torch.int32))
     if stage == "select":
         logits, kw["logitStrides"] = _rows_view(logits)
         (B, R, column), device, dtype = logits.shape, logits.device, torch.bfloat16
@@ -747,10 +756,11 @@ def _run_mla_index(stage, q_index, weights, index_cache, cache_lengths, block_ta
             kw.update(pageSize=int(index_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)),
                       pageStride=int(index_cache.stride(0)))
     kw.update(rows=int(R), batches=int(B), column=int(column))
-    key = (AttentionMLAIndex, dtype)
+    cls = AttentionMLAIndexPrefill if prefill else AttentionMLAIndex
+    key = (cls, dtype)
     host = _HOSTS.get(key)
     if host is None:
-        host = _HOSTS[key] = AttentionMLAIndex(P.BF16 if dtype == torch.bfloat16 else P.FP16)
+        host = _HOSTS[key] = cls(P.BF16 if dtype == torch.bfloat16 else P.FP16)
     if stage == "logits":
         out = torch.full((B, R, column), float("-inf"), dtype=torch.float32, device=device)
         buffers = (q_index, weights, index_cache, out)
@@ -1135,12 +1145,28 @@ def _op_mla_index_topk(q_index: torch.Tensor, weights: torch.Tensor, index_cache
     return _run_mla_index("topk", q_index, weights, index_cache, cache_lengths, block_table, causal, None, topk)
 
 
-def _fake_mla_index_logits(q_index, weights, index_cache, cache_lengths, block_table, causal):
+def _op_mla_index_prefill_logits(q_index: torch.Tensor, weights: torch.Tensor, index_cache: torch.Tensor, cache_lengths: torch.Tensor,
+                                 block_table: Optional[torch.Tensor], causal: bool, q_lengths: Optional[torch.Tensor]) -> torch.Tensor:
+    """(mla_index_logits' arguments; `q_lengths` last)"""
+    return _run_mla_index("logits", q_index, weights, index_cache, cache_lengths, block_table, causal, None, None, True, q_lengths)
+
+
+def _op_mla_index_prefill_select(logits: torch.Tensor, cache_lengths: torch.Tensor, topk: int, causal: bool,
+                                 q_lengths: Optional[torch.Tensor]) -> torch.Tensor:
+    return _run_mla_index("select", None, None, None, cache_lengths, None, causal, logits, topk, True, q_lengths)
+
+
+def _op_mla_index_prefill_topk(q_index: torch.Tensor, weights: torch.Tensor, index_cache: torch.Tensor, cache_lengths: torch.Tensor, topk: int,
+                               block_table: Optional[torch.Tensor], causal: bool, q_lengths: Optional[torch.Tensor]) -> torch.Tensor:
+    return _run_mla_index("topk", q_index, weights, index_cache, cache_lengths, block_table, causal, None, topk, True, q_lengths)
+
+
+def _fake_mla_index_logits(q_index, weights, index_cache, cache_lengths, block_table, causal, q_lengths=None):
     column = index_cache.shape[1] * (block_table.shape[1] if block_table is not None else 1)
     return q_index.new_empty((q_index.shape[0], q_index.shape[2], column), dtype=torch.float32)
 
 
-def _fake_mla_index_select(logits, cache_lengths, topk, causal):
+def _fake_mla_index_select(logits, cache_lengths, topk, causal, q_lengths=None):
     return logits.new_empty((logits.shape[0], logits.shape[1], topk), dtype=torch.int32)
 
 
@@ -1284,6 +1310,14 @@ _MLA_SPARSE_PREFILL_OPS = [
 ]
 _HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_SPARSE_PREFILL_OPS})
 _HAVE_MLA_SPARSE_PREFILL_OP = _HAVE["attention_mla_sparse_prefill"]
+# the ops of include/mfa_mla_index_prefill.h, in a list of their own (the fakes are the decode indexer's: the shapes are the same)
+_MLA_INDEX_PREFILL_OPS = [
+    ("mla_index_prefill_logits", _op_mla_index_prefill_logits, _fake_mla_index_logits, ()),
+    ("mla_index_prefill_select", _op_mla_index_prefill_select, _fake_mla_index_select, ()),
+    ("mla_index_prefill_topk", _op_mla_index_prefill_topk, _fake_mla_index_topk, ()),
+]
+_HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_INDEX_PREFILL_OPS})
+_HAVE_MLA_INDEX_PREFILL_OPS = all(_HAVE[_op[0]] for _op in _MLA_INDEX_PREFILL_OPS)
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1768,3 +1802,35 @@ def mla_index_topk(q_index: torch.Tensor, weights: torch.Tensor, index_cache: to
     who = "mla_index_topk"
     _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, None, topk)
     return _call_op(_HAVE_MLA_INDEX_OPS, who, q_index, weights, index_cache, cache_lengths, int(topk), block_table, bool(causal))
+
+
+def mla_index_prefill_logits(q_index: torch.Tensor, weights: torch.Tensor, index_cache: torch.Tensor, cache_lengths: torch.Tensor, *,
+                             block_table: Optional[torch.Tensor] = None, causal: bool = True, q_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mla_index_logits for a prompt chunk of ANY number of rows (include/mfa_mla_index_prefill.h): q_index [B, Hi, R, 128], weights
+    [B, R, Hi], the index cache and cache_lengths as there; q_lengths (int32 [B] on the GPU, None = R) counts the live rows of each
+    sequence.  Row r < qn sees the keys below flash_mla_sparse_prefill's frontier, min(n, r + max(n - qn, 0) + 1); -inf everywhere else,
+    rows at or past qn included.  A workgroup keeps 256 keys in registers and streams the rows through LDS.  Forward only, GPU only; the
+    torch.library op is `mfa::mla_index_prefill_logits`."""
+    who = "mla_index_prefill_logits"
+    _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, None, None, True)
+    return _call_op(_HAVE_MLA_INDEX_PREFILL_OPS, who, q_index, weights, index_cache, cache_lengths, block_table, bool(causal), q_lengths)
+
+
+def mla_index_prefill_select(logits: torch.Tensor, cache_lengths: torch.Tensor, topk: int, *, causal: bool = True,
+                             q_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mla_index_select under the prefill rule: logits float32 [B, R, C] as mla_index_prefill_logits returns them -> int32 [B, R, topk],
+    the lists flash_mla_sparse_prefill reads; rows at or past q_lengths[b] are all -1.  The torch.library op is
+    `mfa::mla_index_prefill_select`."""
+    who = "mla_index_prefill_select"
+    _check_mla_index(who, None, None, None, cache_lengths, None, logits, topk, True)
+    return _call_op(_HAVE_MLA_INDEX_PREFILL_OPS, who, logits, cache_lengths, int(topk), bool(causal), q_lengths)
+
+
+def mla_index_prefill_topk(q_index: torch.Tensor, weights: torch.Tensor, index_cache: torch.Tensor, cache_lengths: torch.Tensor, topk: int, *,
+                           block_table: Optional[torch.Tensor] = None, causal: bool = True, q_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mla_index_prefill_select(mla_index_prefill_logits(...), cache_lengths, topk) in passes of rows, bit for bit the same lists, the
+    logits of a pass in a workspace of at most 256 MiB allocated here.  The result goes straight into flash_mla_sparse_prefill(q,
+    kv_cache, cache_lengths, indices, q_lengths=...).  The torch.library op is `mfa::mla_index_prefill_topk`."""
+    who = "mla_index_prefill_topk"
+    _check_mla_index(who, q_index, weights, index_cache, cache_lengths, block_table, None, topk, True)
+    return _call_op(_HAVE_MLA_INDEX_PREFILL_OPS, who, q_index, weights, index_cache, cache_lengths, int(topk), block_table, bool(causal), q_lengths)
