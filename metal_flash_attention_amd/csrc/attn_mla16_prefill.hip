@@ -1,23 +1,19 @@
 // attn_mla16_prefill.hip -- multi-head latent attention prefill over the compressed KV cache: the kernels' code objects
-// (attn_mla16_prefill.h) and the C ABI of include/mfa_mla_prefill.h.  An entry of its own beside attn_mla16.hip: it is in no family
-// table, takes no option and no workspace, and takes from cache_launch.h what every launch over a cache shares -- the paging, stride,
-// buffer and precision checks in their one wording and the timing loop.  What it refuses for the reason attn_mla16.hip refuses it, it
-// refuses in that file's words.
+// (attn_mla16_prefill.h), their table and the C ABI of include/mfa_mla_prefill.h.  An entry of its own beside attn_mla16.hip: it is in no
+// family table and takes no option and no workspace.  Its checks and its argument block are mla_launch.h's prepare_mla_prefill_args,
+// which the cut, e4m3 and sparse prefill units take too; what this unit adds is the kernel and its grid of batches x blocks.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN past a length.)
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstddef>
-#include <cstdio>
 #include <cstring>
-#include <string>
 
 #include "../../include/mfa_mla_prefill.h"
 #include "attn_mla16_prefill.h"
-#include "attn_mla16_prefill_launch.h"
 #include "cache_launch.h"
 #include "launchers.h"
 #include "mfa_internal.h"
+#include "mla_launch.h"
 
 using namespace mfa;
 
@@ -42,78 +38,22 @@ struct MlaPrefillPlan {
   const MlaPrefillSet *set;
   uint32_t grid;   // batches x blocks
   const char *name() const { return set->kernel.name; }
-  mfa_status prepare(const mfa_mla_prefill_params *p);
+  mfa_status prepare(const mfa_mla_prefill_params *p) {
+    std::memset(&args, 0, sizeof(args));
+    const mfa_status st = prepare_mla_prefill_args(p, args);
+    if (st != MFA_OK) return st;
+    set = find_mla_set(kSets, p->precision);
+    grid = args.blocks * args.batches;
+    return MFA_OK;
+  }
+  mfa_status bind(const void *q, const void *kv, void *o, float *l) { return bind_mla(args, nullptr, q, kv, o, l); }
   hipError_t run(hipStream_t stream) const {
     const hipError_t err = launch_kernel(set->kernel.launch, dim3(grid), dim3(256), (uint32_t)MLAP_LDS, stream, args);
     return err != hipSuccess ? err : hipGetLastError();
   }
 };
 
-// every check that needs no GPU, and the kernel's argument block (the buffer pointers are filled in by the entries)
-mfa_status MlaPrefillPlan::prepare(const mfa_mla_prefill_params *p) {
-  if (!p) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  if (p->precision == MFA_FP32)
-    return fail(MFA_ERR_UNSUPPORTED, "MLA prefill reads 16-bit caches (MFA_BF16 or MFA_FP16); an FP32 cache has no kernel");
-  mfa_status st = check_precisions(p->precision, p->outputPrecision);
-  if (st != MFA_OK) return st;
-  if (p->headDimension != MFA_MLA_HEAD_DIMENSION || p->valueDimension != MFA_MLA_VALUE_DIMENSION)
-    return fail(MFA_ERR_UNSUPPORTED, "MLA prefill is compiled for (headDimension, valueDimension) = (576, 512), not (" +
-                                         std::to_string(p->headDimension) + ", " + std::to_string(p->valueDimension) + ")");
-  if (!(p->scale > 0.0f) || std::isinf(p->scale))   // (a NaN fails the comparison)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "scale is required: the model's softmax scale in natural units, finite and > 0 (there is no default), not " +
-                                              std::to_string(p->scale));
-  if ((st = check_sizes(p)) != MFA_OK) return st;
-  const uint64_t M = (uint64_t)p->heads * p->rows, blocks = (M + MFA_MLA_PREFILL_PACKED_ROWS - 1) / MFA_MLA_PREFILL_PACKED_ROWS;
-  if (M > 0x7FFFFFFFull || blocks * p->batches > 0x7FFFFFFFull)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "rows x heads, and blocks x batches, must fit a grid of 2^31 - 1 workgroups");
-  if (!p->cacheLengths) return fail(MFA_ERR_INVALID_ARGUMENT, "cacheLengths is required (device array of `batches` uint32)");
-  uint32_t pageShift = 0;
-  if ((st = check_paging(p->pageSize, p->blockTable, p->blockTableStride, p->column, &pageShift)) != MFA_OK) return st;
-  static const char *names[3] = {"Q", "KV", "O"};
-  for (int i = 0; i < 3; ++i) {
-    const int64_t outer = i == 1 && p->pageSize ? p->pageStride : p->batchStride[i];
-    st = check_operand_strides(names[i], i == 2 ? p->valueDimension : p->headDimension, p->leadingDimension[i], i == 1 ? 0 : p->headStride[i],
-                               outer, i == 2 ? 4 : 8, "(16-byte rows for Q and KV; whole 4-element stores for O)");
-    if (st != MFA_OK) return st;
-  }
-  set = nullptr;
-  for (const MlaPrefillSet &s : kSets)
-    if (s.precision == p->precision) set = &s;
-  grid = (uint32_t)(blocks * p->batches);
-  MlaPrefillArgs &a = args;
-  std::memset(&a, 0, sizeof(a));
-  a.lengths = p->cacheLengths;
-  a.qlengths = p->queryLengths;
-  a.table = p->blockTable;
-  a.tableStride = p->blockTableStride;
-  a.ldq = p->leadingDimension[0]; a.hsq = p->headStride[0]; a.bsq = p->batchStride[0];
-  a.ldk = p->leadingDimension[1]; a.bsk = p->batchStride[1]; a.psk = p->pageStride;
-  a.ldo = p->leadingDimension[2]; a.hso = p->headStride[2]; a.bso = p->batchStride[2];
-  a.lhs = p->lHeadStride; a.lbs = p->lBatchStride;
-  a.R = p->rows; a.H = p->heads; a.blocks = (uint32_t)blocks; a.batches = p->batches; a.column = p->column;
-  a.paged = p->pageSize != 0; a.pageShift = pageShift;
-  a.causal = p->causal != 0; a.outF32 = p->outputPrecision == MFA_FP32;
-  a.scale2 = p->scale * 1.44269504089f;   // fl(scale x log2 e)
-  return MFA_OK;
-}
-
-mfa_status bind_mla_prefill(MlaPrefillPlan *plan, const void *q, const void *kv, void *o, float *l) {
-  mfa_status st = check_buffers({q, kv, o}, "Q, KV and O");
-  if (st == MFA_OK) st = check_float_arrays({l}, "L");
-  if (st != MFA_OK) return st;
-  plan->args.q = (const char *)q; plan->args.kv = (const char *)kv; plan->args.o = (char *)o; plan->args.l = l;
-  return MFA_OK;
-}
-
 } // namespace
-
-// what the split entries (attn_mla16_prefill_split.hip) take from this plan: its checks in its words, and its argument block
-mfa_status mfa::mla_prefill_prepare_args(const mfa_mla_prefill_params *p, MlaPrefillArgs *args) {
-  MlaPrefillPlan plan;
-  const mfa_status st = plan.prepare(p);
-  if (st == MFA_OK) *args = plan.args;
-  return st;
-}
 
 extern "C" {
 
@@ -145,13 +85,7 @@ mfa_status mfa_mla_prefill_params_offsets(uint32_t *offsets, uint32_t capacity, 
 
 mfa_status mfa_attention_mla_prefill_launch(const void *q, const void *kv, void *o, float *l, const mfa_mla_prefill_params *params,
                                             void *stream) {
-  MlaPrefillPlan plan;
-  mfa_status st = plan.prepare(params);
-  if (st == MFA_OK) st = bind_mla_prefill(&plan, q, kv, o, l);
-  if (st != MFA_OK) return st;
-  const hipError_t err = plan.run((hipStream_t)stream);
-  if (err != hipSuccess) return hip_fail(err, plan.name());
-  return MFA_OK;
+  return mla_launch<MlaPrefillPlan>(q, kv, o, l, stream, params);
 }
 
 mfa_status mfa_attention_mla_prefill_launch_form(const mfa_mla_prefill_params *params, char *out, size_t capacity) {
@@ -160,22 +94,13 @@ mfa_status mfa_attention_mla_prefill_launch_form(const mfa_mla_prefill_params *p
   MlaPrefillPlan plan;
   const mfa_status st = plan.prepare(params);
   if (st != MFA_OK) return st;
-  const MlaPrefillArgs &a = plan.args;
-  char text[512];
-  std::snprintf(text, sizeof(text), "%s (grid %u = %u blocks x %u sequences, %llu packed rows in blocks of %d, %s)", plan.name(), plan.grid,
-                a.blocks, a.batches, (unsigned long long)a.R * a.H, MFA_MLA_PREFILL_PACKED_ROWS, a.paged ? "paged" : "contiguous");
-  copy_text(out, capacity, text);
+  mla_prefill_form(plan.name(), plan.args, plan.grid, 1, 1, 0, "", nullptr, out, capacity);
   return MFA_OK;
 }
 
 mfa_status mfa_attention_mla_prefill_time(const void *q, const void *kv, void *o, float *l, const mfa_mla_prefill_params *params,
                                           void *stream, int warmup, int iterations, float *milliseconds) {
-  if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
-  MlaPrefillPlan plan;
-  mfa_status st = plan.prepare(params);
-  if (st == MFA_OK) st = bind_mla_prefill(&plan, q, kv, o, l);
-  if (st != MFA_OK) return st;
-  return time_launches((hipStream_t)stream, warmup, iterations, milliseconds, plan.name(), [&](hipStream_t s) { return plan.run(s); });
+  return mla_time<MlaPrefillPlan>(q, kv, o, l, stream, warmup, iterations, milliseconds, params);
 }
 
 mfa_status mfa_attention_mla_prefill_step_range(uint32_t length, uint32_t queryLength, uint32_t firstPacked, uint32_t heads,

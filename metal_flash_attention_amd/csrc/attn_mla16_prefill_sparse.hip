@@ -1,22 +1,21 @@
 // attn_mla16_prefill_sparse.hip -- sparse MLA prefill, the launch of mfa_mla_prefill.h over per-row lists of key positions: the kernels'
-// code objects (attn_mla16_prefill_sparse.h) and the C ABI of include/mfa_mla_prefill_sparse.h.  A translation unit of its own, so that
-// the kernels of attn_mla16_prefill.hip and attn_mla16_sparse.hip stay the code objects they are.  The params are the dense prefill's
-// and are refused by the dense prefill's own plan, in its words (mla_prefill_prepare_args, attn_mla16_prefill_launch.h); what this unit
-// adds is the block's checks, the packing by (sequence, row, group of heads) and the argument block.  No workspace, no pieces.
+// code objects (attn_mla16_prefill_sparse.h), their table and the C ABI of include/mfa_mla_prefill_sparse.h.  A translation unit of its
+// own, so that the kernels of attn_mla16_prefill.hip and attn_mla16_sparse.hip stay the code objects they are.  The block's checks and
+// the dense prefill's checks of the params, in its words, are mla_launch.h's; what this unit adds is the packing by (sequence, row,
+// group of heads), its grid and the list in the argument block.  No workspace, no pieces.
 // (Not named attn_fwd16*: the Makefile gives those -ffinite-math-only, and this unit's inputs may hold NaN wherever no list points.)
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
-#include <string>
 
 #include "../../include/mfa_mla_prefill_sparse.h"
-#include "attn_mla16_prefill_launch.h"
 #include "attn_mla16_prefill_sparse.h"
 #include "cache_launch.h"
 #include "launchers.h"
 #include "mfa_internal.h"
+#include "mla_launch.h"
 
 using namespace mfa;
 
@@ -56,21 +55,6 @@ struct SparsePrefillSet {
 #endif
 const SparsePrefillSet kSets[] = {MFA_MLA_PREFILL_SPARSE_SET(bf16, MFA_BF16), MFA_MLA_PREFILL_SPARSE_SET(f16, MFA_FP16)};
 
-// the block, looked at before the params: mfa_mla_sparse.h's rule in its words
-mfa_status check_sparse(const mfa_mla_sparse *s) {
-  if (!s)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "null mfa_mla_sparse: the sparse entries require the block (mfa_mla_sparse_init; a launch over "
-                                          "every key below the frontier: the mfa_mla_prefill.h entries)");
-  if (!s->indices) return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_mla_sparse.indices is required (device array [batches][rows][topk] of int32 key positions)");
-  if (s->topk == 0) return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_mla_sparse.topk must be at least 1 (the slots of a row's list)");
-  if (s->reserved != 0) return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_mla_sparse.reserved must be 0, not " + std::to_string(s->reserved));
-  if (s->indexRowStride < (int64_t)s->topk)
-    return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_mla_sparse.indexRowStride must be at least topk = " + std::to_string(s->topk) + " entries, not " +
-                                              std::to_string(s->indexRowStride));
-  if ((uintptr_t)s->indices % 4 != 0) return fail(MFA_ERR_INVALID_ARGUMENT, "mfa_mla_sparse.indices must be 4-byte aligned");
-  return MFA_OK;
-}
-
 struct SparsePrefillPlan {
   MlaPrefillSparseArgs args;
   const SparsePrefillSet *set;
@@ -80,6 +64,7 @@ struct SparsePrefillPlan {
   const char *name() const { return kernel().name; }
   // (`out`: launch_form's buffer, refused after the block and ahead of the params; the launches pass none)
   mfa_status prepare(const mfa_mla_prefill_params *p, const mfa_mla_sparse *s, const char *const *out = nullptr);
+  mfa_status bind(const void *q, const void *kv, void *o, float *l) { return bind_mla(args.a, nullptr, q, kv, o, l); }
   hipError_t run(hipStream_t stream) const {
     const uint32_t lds = tiles == 1 ? (uint32_t)mlapx_lds<1>() : (uint32_t)mlapx_lds<2>();
     const hipError_t err = launch_kernel(kernel().launch, dim3(grid), dim3(256), lds, stream, args);
@@ -88,19 +73,17 @@ struct SparsePrefillPlan {
 };
 
 mfa_status SparsePrefillPlan::prepare(const mfa_mla_prefill_params *p, const mfa_mla_sparse *s, const char *const *out) {
-  mfa_status st = check_sparse(s);
+  mfa_status st = check_mla_sparse(s, kMlaDensePrefill);
   if (st != MFA_OK) return st;
   if (out && !*out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   // everything the dense prefill refuses for these params, in its words
   std::memset(&args, 0, sizeof(args));
-  if ((st = mla_prefill_prepare_args(p, &args.a)) != MFA_OK) return st;
+  if ((st = prepare_mla_prefill_args(p, args.a)) != MFA_OK) return st;
   tiles = kTwoTiles && p->heads > (uint32_t)MLA_ROWS ? (uint32_t)MLAP_TILES : 1u;
   const uint64_t per = (uint64_t)tiles * MLA_ROWS, groups = ((uint64_t)p->heads + per - 1) / per;
   const uint64_t wide = groups * p->rows * p->batches;
   if (wide > 0x7FFFFFFFull) return fail(MFA_ERR_INVALID_ARGUMENT, "groups x rows x batches must fit a grid of 2^31 - 1 workgroups");
-  set = nullptr;
-  for (const SparsePrefillSet &k : kSets)
-    if (k.precision == p->precision) set = &k;
+  set = find_mla_set(kSets, p->precision);
   grid = (uint32_t)wide;
   args.a.blocks = (uint32_t)groups;   // the groups of heads of one (sequence, row), not prefill's blocks of packed rows
   args.indices = s->indices;
@@ -110,28 +93,13 @@ mfa_status SparsePrefillPlan::prepare(const mfa_mla_prefill_params *p, const mfa
   return MFA_OK;
 }
 
-mfa_status bind_sparse_prefill(SparsePrefillPlan *plan, const void *q, const void *kv, void *o, float *l) {
-  mfa_status st = check_buffers({q, kv, o}, "Q, KV and O");
-  if (st == MFA_OK) st = check_float_arrays({l}, "L");
-  if (st != MFA_OK) return st;
-  MlaPrefillArgs &a = plan->args.a;
-  a.q = (const char *)q; a.kv = (const char *)kv; a.o = (char *)o; a.l = l;
-  return MFA_OK;
-}
-
 } // namespace
 
 extern "C" {
 
 mfa_status mfa_attention_mla_prefill_sparse_launch(const void *q, const void *kv, void *o, float *l, const mfa_mla_prefill_params *params,
                                                    const mfa_mla_sparse *sparse, void *stream) {
-  SparsePrefillPlan plan;
-  mfa_status st = plan.prepare(params, sparse);
-  if (st == MFA_OK) st = bind_sparse_prefill(&plan, q, kv, o, l);
-  if (st != MFA_OK) return st;
-  const hipError_t err = plan.run((hipStream_t)stream);
-  if (err != hipSuccess) return hip_fail(err, plan.name());
-  return MFA_OK;
+  return mla_launch<SparsePrefillPlan>(q, kv, o, l, stream, params, sparse);
 }
 
 mfa_status mfa_attention_mla_prefill_sparse_launch_form(const mfa_mla_prefill_params *params, const mfa_mla_sparse *sparse, char *out,
@@ -151,12 +119,7 @@ mfa_status mfa_attention_mla_prefill_sparse_launch_form(const mfa_mla_prefill_pa
 
 mfa_status mfa_attention_mla_prefill_sparse_time(const void *q, const void *kv, void *o, float *l, const mfa_mla_prefill_params *params,
                                                  const mfa_mla_sparse *sparse, void *stream, int warmup, int iterations, float *milliseconds) {
-  if (!milliseconds || iterations <= 0 || warmup < 0) return fail(MFA_ERR_INVALID_ARGUMENT, "bad timing arguments");
-  SparsePrefillPlan plan;
-  mfa_status st = plan.prepare(params, sparse);
-  if (st == MFA_OK) st = bind_sparse_prefill(&plan, q, kv, o, l);
-  if (st != MFA_OK) return st;
-  return time_launches((hipStream_t)stream, warmup, iterations, milliseconds, plan.name(), [&](hipStream_t s) { return plan.run(s); });
+  return mla_time<SparsePrefillPlan>(q, kv, o, l, stream, warmup, iterations, milliseconds, params, sparse);
 }
 
 } // extern "C"
