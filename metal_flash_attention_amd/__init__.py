@@ -19,6 +19,7 @@ from .attention import (  # noqa: F401
     AttentionMLAPrefillFP8,
     AttentionMLAPrefillFP8Split,
     AttentionMLAPrefillSparse,
+    AttentionMLAPrefillSparseFP8,
     AttentionMLAPrefillSplit,
     AttentionMLASparseDecode,
     AttentionMLASparseDecodeFP8,
@@ -45,7 +46,8 @@ def __getattr__(name):
     # the torch functions of the KV-cache loop, on first use: torch stays optional for everything above
     if name in ("kv_cache_compact", "tree_path", "flash_mla_decode", "flash_mla_decode_fp8", "mla_cache_append", "flash_mla_sparse_decode",
                 "flash_mla_sparse_decode_fp8", "flash_mla_prefill", "flash_mla_prefill_split", "flash_mla_prefill_fp8", "mla_index_logits", "mla_index_select",
-                "mla_index_topk", "flash_mla_sparse_prefill", "mla_index_prefill_logits", "mla_index_prefill_select", "mla_index_prefill_topk"):
+                "mla_index_topk", "flash_mla_sparse_prefill", "mla_index_prefill_logits", "mla_index_prefill_select", "mla_index_prefill_topk",
+                "flash_mla_sparse_prefill_fp8"):
         from . import torch_binding
         return getattr(torch_binding, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -488,6 +488,13 @@ MLA_PREFILL_SPARSE_SYMBOLS = [   # include/mfa_mla_prefill_sparse.h: MLA prefill
      _MLA_BUFS + [_MLA_PREFILL, _MLA_SPARSE, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
 ]
 
+MLA_PREFILL_SPARSE_FP8_SYMBOLS = [   # include/mfa_mla_prefill_sparse_fp8.h: the sparse prefill over an e4m3 latent cache (`sparse`, then `quant`, after `params`)
+    ("mfa_attention_mla_prefill_sparse_fp8_launch", ctypes.c_int, _MLA_BUFS + [_MLA_PREFILL, _MLA_SPARSE, _MLA_QUANT, ctypes.c_void_p]),
+    ("mfa_attention_mla_prefill_sparse_fp8_launch_form", ctypes.c_int, [_MLA_PREFILL, _MLA_SPARSE, _MLA_QUANT, ctypes.c_char_p, ctypes.c_size_t]),
+    ("mfa_attention_mla_prefill_sparse_fp8_time", ctypes.c_int,
+     _MLA_BUFS + [_MLA_PREFILL, _MLA_SPARSE, _MLA_QUANT, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+]
+
 class mfa_mla_index_params(ctypes.Structure):   # include/mfa_mla_index.h
     _fields_ = [
         ("rows", ctypes.c_uint32), ("column", ctypes.c_uint32), ("indexHeads", ctypes.c_uint32), ("batches", ctypes.c_uint32),
@@ -637,7 +644,7 @@ def lib() -> ctypes.CDLL:
     if got != EXPECTED_ABI:   # the struct mirrors above describe exactly one layout of mfa_launch_params & co.
         raise ImportError(f"{LIB_PATH} reports ABI version {got}, these bindings were written for {EXPECTED_ABI}: "
                           f"rebuild the library (make -C metal_flash_attention_amd/csrc)")
-    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS + MLA_SPARSE_SYMBOLS + MLA_SPARSE_FP8_SYMBOLS + MLA_PREFILL_SYMBOLS + MLA_PREFILL_SPLIT_SYMBOLS + MLA_PREFILL_FP8_SYMBOLS + MLA_INDEX_SYMBOLS + MLA_PREFILL_SPARSE_SYMBOLS + MLA_INDEX_PREFILL_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + GEMM_SYMBOLS + DECODE_SYMBOLS + KVCACHE_SYMBOLS + PREFILL_SYMBOLS + WINDOW_SYMBOLS + SINK_SYMBOLS + RAGGED_SYMBOLS + SOFTCAP_SYMBOLS + TREE_SYMBOLS + COMPACT_SYMBOLS + SPLIT_SYMBOLS + MLA_SYMBOLS + MLA_CACHE_SYMBOLS + MLA_SPARSE_SYMBOLS + MLA_SPARSE_FP8_SYMBOLS + MLA_PREFILL_SYMBOLS + MLA_PREFILL_SPLIT_SYMBOLS + MLA_PREFILL_FP8_SYMBOLS + MLA_INDEX_SYMBOLS + MLA_PREFILL_SPARSE_SYMBOLS + MLA_INDEX_PREFILL_SYMBOLS + MLA_PREFILL_SPARSE_FP8_SYMBOLS:
         fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

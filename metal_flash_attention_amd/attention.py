@@ -1351,6 +1351,49 @@ class AttentionMLAPrefillSparse(AttentionMLAPrefill):
         return float(ms.value)
 
 
+class AttentionMLAPrefillSparseFP8(AttentionMLAPrefillSparse):
+    """Sparse MLA prefill over an FP8 (OCP e4m3) latent cache (include/mfa_mla_prefill_sparse_fp8.h): AttentionMLAPrefillSparse's methods
+    and arguments -- the KV strides count bytes, multiples of 16 -- plus kvScale (device FP32, one entry, None = 1.0), as
+    AttentionMLAPrefillFP8 takes it.  `precision` is the 16-bit type of Q.  For every row the arithmetic is AttentionMLASparseDecodeFP8's
+    at one piece, bit for bit; over the identity list it is AttentionMLAPrefillFP8's.
+
+        mla = AttentionMLAPrefillSparseFP8(GEMMOperandPrecision.BF16)
+        mla.launch(q, kv8, o, l, cacheLengths=lengths, queryLengths=new, rows=512, column=C, heads=128, batches=B, scale=s, indices=idx,
+                   topk=2048, kvScale=kv_scale)"""
+
+    def __init__(self, precision: GEMMOperandPrecision = GEMMOperandPrecision.BF16, outputPrecision: Optional[GEMMOperandPrecision] = None,
+                 cachePrecision: int = KVCachePrecision.E4M3, **widths):
+        super().__init__(precision, outputPrecision, **widths)
+        self.cachePrecision = int(cachePrecision)
+
+    def _blocks(self, shape):
+        sparse, kept = _mla_sparse_block(shape)
+        quant, scale = _mla_quant_block(self.cachePrecision, shape)
+        p, keep = self._params(**shape)
+        return p, sparse, quant, (keep, kept, scale)
+
+    def launchForm(self, **shape) -> str:
+        """What `dispatch` with the same arguments would run (nothing is launched): the kernel's name, the grid's factors and topk"""
+        p, sparse, quant, _keep = self._blocks(shape)
+        out = ctypes.create_string_buffer(512)
+        check(lib().mfa_attention_mla_prefill_sparse_fp8_launch_form(ctypes.byref(p), ctypes.byref(sparse), ctypes.byref(quant), out, len(out)))
+        return out.value.decode()
+
+    def dispatch(self, q, kv, o, l=None, *, stream: Optional[int] = None, **shape) -> None:
+        """mfa_attention_mla_prefill_sparse_fp8_launch"""
+        p, sparse, quant, _keep = self._blocks(shape)
+        check(lib().mfa_attention_mla_prefill_sparse_fp8_launch(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.byref(sparse), ctypes.byref(quant),
+                                                                ctypes.c_void_p(stream or 0)))
+
+    def time(self, q, kv, o, l=None, *, stream: Optional[int] = None, warmup: int = 1, iterations: int = 5, **shape) -> float:
+        """Milliseconds for `iterations` back-to-back launches (HIP events on `stream`)."""
+        p, sparse, quant, _keep = self._blocks(shape)
+        ms = ctypes.c_float(0.0)
+        check(lib().mfa_attention_mla_prefill_sparse_fp8_time(*_pointers(q, kv, o, l), ctypes.byref(p), ctypes.byref(sparse), ctypes.byref(quant),
+                                                              ctypes.c_void_p(stream or 0), int(warmup), int(iterations), ctypes.byref(ms)))
+        return float(ms.value)
+
+
 class AttentionMLAIndex:
     """The MLA sparse indexer (include/mfa_mla_index.h), the producer of AttentionMLASparseDecode's `indices`: three launches chosen by
     `stage` -- "logits": logits[b][r][c] = sum_h w[b][r][h] max(qi[b][h][r] . ki[b][c], 0) at every visible key; "select": the topk

@@ -33,7 +33,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAIndex, AttentionMLAIndexPrefill, AttentionMLAPrefill, AttentionMLAPrefillFP8Split, AttentionMLAPrefillSparse, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
+from .attention import (AttentionDecode, AttentionDecodeFP8, AttentionMLADecode, AttentionMLADecodeFP8, AttentionMLAIndex, AttentionMLAIndexPrefill, AttentionMLAPrefill, AttentionMLAPrefillFP8Split, AttentionMLAPrefillSparse, AttentionMLAPrefillSparseFP8, AttentionMLAPrefillSplit, AttentionMLASparseDecode, AttentionMLASparseDecodeFP8, AttentionPrefill, AttentionDescriptor, AttentionKernel, AttentionKernelType,
                         AttentionOperand as Op, GEMMOperandPrecision as P, KVCacheAppend, KVCacheCompact,
                         KVCachePrecision, MLACacheAppend)
 
@@ -782,12 +782,15 @@ def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal,
     flash_mla_prefill_split's launch, cut along the keys (include/mfa_mla_prefill_split.h); its workspace is allocated here.  `fp8`:
     flash_mla_prefill_fp8's, over an e4m3 latent cache with `kv_scale` (include/mfa_mla_prefill_fp8.h; always its cut entries, which at
     one piece run the unsplit kernel) -- the strides of such a cache count bytes, which are its elements.  `indices`:
-    flash_mla_sparse_prefill's lists (include/mfa_mla_prefill_sparse.h), passed where they lie; a 16-bit cache, no pieces"""
+    flash_mla_sparse_prefill's lists (include/mfa_mla_prefill_sparse.h), passed where they lie, no pieces; with `fp8`,
+    flash_mla_sparse_prefill_fp8's (include/mfa_mla_prefill_sparse_fp8.h)"""
     split = key_pieces is not None
-    who = "flash_mla_sparse_prefill" if indices is not None else "flash_mla_prefill_fp8" if fp8 else "flash_mla_prefill_split" if split else "flash_mla_prefill"
+    sparse = indices is not None
+    who = ("flash_mla_sparse_prefill_fp8" if fp8 else "flash_mla_sparse_prefill") if sparse else \
+        "flash_mla_prefill_fp8" if fp8 else "flash_mla_prefill_split" if split else "flash_mla_prefill"
     if fp8 and kv_cache.dtype != torch.float8_e4m3fn:
-        raise TypeError(f"{who}: the latent cache must be torch.float8_e4m3fn (got {kv_cache.dtype}); a 16-bit latent cache is flash_mla_prefill's, "
-                        "and e5m2 and fnuz caches have no kernel")
+        raise TypeError(f"{who}: the latent cache must be torch.float8_e4m3fn (got {kv_cache.dtype}); a 16-bit latent cache is "
+                        f"{'flash_mla_sparse_prefill' if sparse else 'flash_mla_prefill'}'s, and e5m2 and fnuz caches have no kernel")
     _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, key_pieces if split else 0, fp8)
     if indices is not None:
         _check_mla_indices(who, q, indices)
@@ -805,7 +808,8 @@ def _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal,
               column=int(kv_cache.shape[1]) * (int(block_table.shape[1]) if paged else 1))
     if paged:
         kw.update(pageSize=int(kv_cache.shape[1]), blockTable=block_table, blockTableStride=int(block_table.stride(0)), pageStride=int(kv_cache.stride(0)))
-    cls = AttentionMLAPrefillSparse if indices is not None else AttentionMLAPrefillFP8Split if fp8 else AttentionMLAPrefillSplit if split else AttentionMLAPrefill
+    cls = (AttentionMLAPrefillSparseFP8 if fp8 else AttentionMLAPrefillSparse) if sparse else \
+        AttentionMLAPrefillFP8Split if fp8 else AttentionMLAPrefillSplit if split else AttentionMLAPrefill
     if fp8:
         kw.update(kvScale=_latent_scale(who, kv_scale, kv_cache.device))
     if indices is not None:
@@ -1130,6 +1134,13 @@ def _op_mla_sparse_prefill(q: torch.Tensor, kv_cache: torch.Tensor, cache_length
     return _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, indices=indices)
 
 
+def _op_mla_sparse_prefill_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, indices: torch.Tensor,
+                               q_lengths: Optional[torch.Tensor], block_table: Optional[torch.Tensor], causal: bool, softmax_scale: float,
+                               kv_scale: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(attention_mla_sparse_prefill's arguments; `kv_scale` last, as attention_mla_prefill_fp8's)"""
+    return _run_mla_prefill(q, kv_cache, cache_lengths, q_lengths, block_table, causal, softmax_scale, None, True, kv_scale, indices)
+
+
 def _op_mla_index_logits(q_index: torch.Tensor, weights: torch.Tensor, index_cache: torch.Tensor, cache_lengths: torch.Tensor,
                          block_table: Optional[torch.Tensor], causal: bool) -> torch.Tensor:
     return _run_mla_index("logits", q_index, weights, index_cache, cache_lengths, block_table, causal)
@@ -1318,6 +1329,12 @@ _MLA_INDEX_PREFILL_OPS = [
 ]
 _HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_INDEX_PREFILL_OPS})
 _HAVE_MLA_INDEX_PREFILL_OPS = all(_HAVE[_op[0]] for _op in _MLA_INDEX_PREFILL_OPS)
+# the op of include/mfa_mla_prefill_sparse_fp8.h, in a list of its own
+_MLA_SPARSE_PREFILL_FP8_OPS = [
+    ("attention_mla_sparse_prefill_fp8", _op_mla_sparse_prefill_fp8, _fake_mla, ()),
+]
+_HAVE.update({_op[0]: _register_cache_op(*_op) for _op in _MLA_SPARSE_PREFILL_FP8_OPS})
+_HAVE_MLA_SPARSE_PREFILL_FP8_OP = _HAVE["attention_mla_sparse_prefill_fp8"]
 
 
 def _forward_only(who, q, k_cache, v_cache, cache_lengths):
@@ -1766,6 +1783,37 @@ def flash_mla_sparse_prefill(q: torch.Tensor, kv_cache: torch.Tensor, cache_leng
         _check_lengths(who, "q_lengths", q_lengths, int(q.shape[0]))
     o, l = _call_op(_HAVE_MLA_SPARSE_PREFILL_OP, "attention_mla_sparse_prefill", q, kv_cache, cache_lengths, indices, q_lengths, block_table,
                     bool(causal), float(softmax_scale))
+    return (o, l * _LN2) if return_lse else o
+
+
+def flash_mla_sparse_prefill_fp8(q: torch.Tensor, kv_cache: torch.Tensor, cache_lengths: torch.Tensor, indices: torch.Tensor, *,
+                                 softmax_scale: float, kv_scale: Optional[torch.Tensor] = None, q_lengths: Optional[torch.Tensor] = None,
+                                 block_table: Optional[torch.Tensor] = None, causal: bool = True, return_lse: bool = False):
+    """flash_mla_sparse_prefill over an FP8 latent cache (include/mfa_mla_prefill_sparse_fp8.h): kv_cache is torch.float8_e4m3fn,
+    [B, C, 576] or a page pool [pages, pageSize, 576], contiguous or strided, read where it lies -- the cache mla_cache_append writes
+    and flash_mla_sparse_decode_fp8 reads, so that a sparse prompt chunk over an FP8 latent cache is one launch.  kv_scale (float32 [1]
+    on the GPU; None: 1.0) is the cache's one scale: a byte b stands for kv_scale x e4m3(b); the host never reads it.  q is bfloat16 or
+    float16; indices, the holes, q_lengths, the rows that are not written and the results are flash_mla_sparse_prefill's.  The NaN
+    bytes of rows no list names are never loaded.  For every row the arithmetic is flash_mla_sparse_decode_fp8's at one piece, bit for
+    bit; over the list 0 .. C - 1 it is flash_mla_prefill_fp8's.  Nothing is read on the host: one capture in a graph serves changed
+    lists and lengths.  Forward only, GPU only.  Goes through the torch.library op `mfa::attention_mla_sparse_prefill_fp8` where torch
+    has custom ops."""
+    who = "flash_mla_sparse_prefill_fp8"
+    if not (q.is_cuda and kv_cache.is_cuda and cache_lengths.is_cuda and indices.is_cuda) or (q_lengths is not None and not q_lengths.is_cuda):
+        raise RuntimeError(f"{who}: tensors must live on the GPU (there is no CPU path)")
+    for t in (q, kv_cache):
+        if t.requires_grad:
+            raise RuntimeError(f"{who} is forward only (no autograd): detach the inputs")
+    if kv_cache.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"{who}: the latent cache must be torch.float8_e4m3fn (got {kv_cache.dtype}); a 16-bit latent cache is "
+                        "flash_mla_sparse_prefill's, and e5m2 and fnuz caches have no kernel")
+    _check_mla(who, q, kv_cache, cache_lengths, block_table, softmax_scale, 0, True)
+    _check_mla_indices(who, q, indices)
+    if q_lengths is not None:
+        _check_lengths(who, "q_lengths", q_lengths, int(q.shape[0]))
+    _latent_scale(who, kv_scale, kv_cache.device)
+    o, l = _call_op(_HAVE_MLA_SPARSE_PREFILL_FP8_OP, "attention_mla_sparse_prefill_fp8", q, kv_cache, cache_lengths, indices, q_lengths,
+                    block_table, bool(causal), float(softmax_scale), kv_scale)
     return (o, l * _LN2) if return_lse else o
 
 
